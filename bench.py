@@ -2,6 +2,7 @@
 """bench.py -- BASELINE.json's metric: encode+decode MPix/s on 4K RGB8, bit-exact, with achieved HBM GB/s vs peak.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--content g3|g2|mid|nat] [--tile-w TW --tile-h TH] [--interleaved]
+                    [--dump-outputs DIR]
 
 N = 1 (default): BASELINE config 3.  A "step" = one pass of the hot path over one batch: F frames of 3840x2160 RGB8 already
 resident in HBM are encoded into the sliced container payload (stage A -> k_encode_slices -> scan + pack) and decoded back
@@ -11,6 +12,11 @@ kernels of one overlap the issue-bound slice kernels of another.  value = pixels
 w*h / (t_enc + t_dec) per frame.  `also` = the other workloads of DESIGN.md section 7, a few steps each, measured in the
 same run: other contents, 2-D tiles, one-frame latency, batched legacy streams, the PCIe-inclusive C5 stream, and the C4
 workload on one GPU (the N = 1 point of the strong-scaling curve).
+
+--dump-outputs DIR (N = 1): after the timed steps, the arrays the headline's LAST timed step handed its caller go to DIR/<name>.npy:
+payload_bytes (per pipeline, float64), payload and slice_lengths (the encoder's output, all pipelines in order), decoded (the
+decoder's pixels) and status, float32; an array of more than 2^22 elements is a sample at positions drawn from a fixed seed.
+The frames are generated from fixed seeds, so two builds run with the same arguments can be compared file for file.
 
 N > 1: one rank per GPU over RCCL.  Started bare (`python bench.py --gpus N`, no WORLD_SIZE in the environment) this
 process touches no GPU: it starts `python -m torch.distributed.run --nproc-per-node N ... bench.py <same arguments>` as a
@@ -178,11 +184,41 @@ def cpu_baseline(img, label, tile_w, tile_h, planar, same_slicing=False):
     return res
 
 
-def measure(frames_np, tile_w, tile_h, planar, streams, steps, warmup, local_rank, barrier=None, isolated=False, per_step=False):
+DUMP_SAMPLE = 1 << 22  # elements per dumped array at most (16 MB as float32): the three large arrays + the small ones stay under 64 MB
+
+
+def sampled(t, seed, n=DUMP_SAMPLE):
+    """a device tensor -> flat float32 host array: all of it when it has at most n elements, else n elements at positions
+    drawn from a fixed seed (sorted; the same positions in every run of the same size)"""
+    import numpy as np
+    import torch
+
+    t = t.reshape(-1)
+    if t.numel() > n:
+        idx = np.sort(np.random.default_rng(seed).integers(0, t.numel(), n))
+        t = t[torch.from_numpy(idx).to(t.device)]
+    return t.to(torch.float32).cpu().numpy()
+
+
+def step_outputs(parts, d_out):
+    """--dump-outputs: what the last timed step handed its caller, per pipeline in order: the payload bytes, the slice
+    lengths, the decoded pixels and the status words, as float32 (float64 for the byte counts)"""
+    import numpy as np
+    import torch
+
+    tot = [int(p["tot"].item()) for p in parts]
+    return {"payload_bytes": np.array(tot, dtype=np.float64),
+            "payload": sampled(torch.cat([p["pay"][:t] for p, t in zip(parts, tot)]), seed=1),
+            "slice_lengths": sampled(torch.cat([p["len"] for p in parts]), seed=2),
+            "decoded": sampled(d_out, seed=3),
+            "status": torch.stack([p["st"] for p in parts]).to(torch.float32).cpu().numpy()}
+
+
+def measure(frames_np, tile_w, tile_h, planar, streams, steps, warmup, local_rank, barrier=None, isolated=False, per_step=False, dump=None):
     """The device-resident round trip of bench.py: frames_np [F,h,w,c] resident in HBM, split over `streams` pipelines.
     Returns a dict with the wall time of `steps` timed steps and the per-kernel event timings.  per_step: every step is
     bracketed by a device synchronisation of its own and timed alone (`step_ms`, for legs that report median and range); the
-    wall time is then the sum of the steps."""
+    wall time is then the sum of the steps.  dump: a dict, filled with step_outputs() of the last timed step."""
     import torch
 
     import llcomp_amd as mi
@@ -268,6 +304,8 @@ def measure(frames_np, tile_w, tile_h, planar, streams, steps, warmup, local_ran
             prof[k] = prof.get(k, 0.0) + v
         n_enc, n_dec = n_enc + ne, n_dec + nd
     check()
+    if dump is not None:  # before the isolated launches below run the pipelines again
+        dump.update(step_outputs(parts, d_out))
 
     # The same launches once more with every pipeline ALONE on the GPU (outside the timed region): per-launch durations
     # without the other streams' kernels beside them, reported next to the live ones (roofline.isolated).
@@ -915,7 +953,14 @@ def main():
     ap.add_argument("--legs-timeout", type=float, default=300.0, help="N > 1: seconds the secondary legs (config 4, config 5) may take before the line goes out without them")
     ap.add_argument("--rehearse-one-gpu", action="store_true",
                     help="rehearsal of the N > 1 code path on a one-GPU box: all ranks use cuda:0 and exchange over gloo (RCCL refuses two ranks on one device); the numbers mean nothing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="N = 1: after the timed steps, write what the headline's last timed step computed as DIR/<name>.npy (float32/float64, "
+                         "large arrays as a fixed seeded sample, under 64 MB in all), so that two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs: N = 1 only")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args.gpus)  # (does not return)
@@ -1123,8 +1168,15 @@ def main():
     # headline leg -- profiles/r03_c5_repeat.txt run 6), so the reference for the config-5 leg is taken while the process is young
     link0 = link_rate() if not args.no_also and (not args.also_only or "c5" in args.also_only.split(",")) else None
     frames_np = make_frames(args.content, F, rank)
-    m = measure(frames_np, args.tile_w, args.tile_h, planar, args.streams, args.steps, args.warmup, local_rank, isolated=not args.no_isolated)
+    dump = {} if args.dump_outputs else None
+    m = measure(frames_np, args.tile_w, args.tile_h, planar, args.streams, args.steps, args.warmup, local_rank, isolated=not args.no_isolated, dump=dump)
     res = headline(args, m, world, planar)
+    if dump is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in dump.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
+        res["dump_outputs"] = {"dir": args.dump_outputs, "files": sorted(name + ".npy" for name in dump),
+                               "bytes": sum(int(a.nbytes) for a in dump.values())}
     # byte-level pin of the measured workload: frame 0 of the default batch is the golden vector's image (std::mt19937(1234)),
     # its container length must be the one the real reference's per-slice streams add up to (tests/golden, also hashed in
     # tests/test_gpu_stream.py::test_c3_4k_bench_slicing_golden)
