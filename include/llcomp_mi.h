@@ -25,7 +25,8 @@ extern "C" {
 #endif
 
 /* ABI 4 (round 6: device lists -- llcomp_mi_opts.devices, llcomp_mi_decode_devices, llcomp_mi_stream_create_multi,
- * llcomp_mi_plan_chunks, llcomp_mi_codec_get_counters).  The library and its callers are built from ONE header: structs have one layout per ABI version (llcomp_mi_opts is
+ * llcomp_mi_plan_chunks, llcomp_mi_codec_get_counters; later, functions only: region decode -- llcomp_mi_region_plan,
+ * llcomp_mi_decode_region(_into), llcomp_mi_codec_decode_region, llcomp_mi_codec_region_family, LLCOMP_MI_PREPARE_REGION).  The library and its callers are built from ONE header: structs have one layout per ABI version (llcomp_mi_opts is
  * checked through struct_size and refused when it differs; llcomp_mi_info and llcomp_mi_stream_result are written in full),
  * so a binding compares llcomp_mi_abi_version() with the LLCOMP_MI_ABI_VERSION it was generated from and refuses to run on
  * a mismatch -- there is no cross-version compatibility mode. */
@@ -99,6 +100,20 @@ int llcomp_mi_decode(const uint8_t* data, size_t len, int32_t device, uint8_t** 
 int llcomp_mi_decode_flags(const uint8_t* data, size_t len, int32_t device, uint32_t flags, uint8_t** px, uint32_t* w,
                            uint32_t* h, uint32_t* c);
 void llcomp_mi_free(void* p);
+/* Region decode: the rectangle (x, y, rw, rh) of the picture, rw >= 1, rh >= 1, x + rw <= w, y + rh <= h (checked in 64 bits;
+ * anything else is BAD_ARGS), as rh x rw x c bytes, row-major, channels interleaved -- the same bytes as that rectangle of the full
+ * decode.  Only the slices of the tiles the rectangle touches are read, copied to the GPU and decoded (llcomp_mi_region_plan): the
+ * header and slice table cross PCIe, then the payload bytes from the first covered slice's first byte to the last one's end, and
+ * only rw * rh * c bytes come back.  A LEGACY stream, and a container of one tile, is one serial chain: it is decoded whole and
+ * cropped on the GPU.  BAD_EXPONENT and TRUNCATED come from covered slices only (a covered slice whose bytes run past the data is
+ * TRUNCATED); a region decode does NOT validate the container -- damage in slices outside the rectangle is never seen.  A header or
+ * slice table that is cut short fails as in llcomp_mi_probe.  flags: LLCOMP_MI_FLAG_SMALL_MODEL as in llcomp_mi_decode_flags.  *c
+ * reports the channel count.  One device only: there is no region decode over a device list or through the streaming pipeline. */
+int llcomp_mi_decode_region(const uint8_t* data, size_t len, int32_t device, uint32_t flags, uint32_t x, uint32_t y, uint32_t rw,
+                            uint32_t rh, uint8_t** px, uint32_t* c);
+/* ... into a caller's buffer: OUTPUT_OVERFLOW (with *c set, nothing written) when px_cap < rw * rh * c. */
+int llcomp_mi_decode_region_into(const uint8_t* data, size_t len, int32_t device, uint32_t flags, uint32_t x, uint32_t y, uint32_t rw,
+                                 uint32_t rh, uint8_t* px, size_t px_cap, uint32_t* c);
 /* Decoding over a device list: the mirror image of llcomp_mi_opts.devices -- every device receives the table entries and payload
  * bytes of its chunks of tile rows, decodes them and copies its rows straight to their place in the picture.  Nothing is written to
  * the output before EVERY device has reported success (the first failing device in list order decides the status).  How the
@@ -155,6 +170,12 @@ typedef struct llcomp_mi_info {
     uint32_t reserved;
 } llcomp_mi_info;
 int llcomp_mi_probe(const uint8_t* data, size_t len, llcomp_mi_info* info);
+/* The tiles a rectangle (x, y, rw, rh) of one frame covers: box = {tx0, ty0, tx1, ty1} (tile columns [tx0, tx1), tile rows
+ * [ty0, ty1)), *slices_per_frame = the covered slices of one frame ((tx1 - tx0) * (ty1 - ty0), times c for planar slices).  tile_w /
+ * tile_h 0 = the whole width / height.  BAD_ARGS for an empty rectangle or one outside the image (see llcomp_mi_decode_region).
+ * Host-only: no GPU involved.  Every region call plans with this. */
+int llcomp_mi_region_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar, uint32_t x, uint32_t y,
+                          uint32_t rw, uint32_t rh, uint32_t box[4], uint32_t* slices_per_frame);
 uint32_t llcomp_mi_slice_count(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar);
 /* Slice width for one-row slices (tile_h = 1) when `frames` frames are coded per call: the widest slice (64..480 pixels) that
  * still keeps about four wavefronts per SIMD busy.  A call that codes few frames is latency-bound with wide slices; this
@@ -213,6 +234,7 @@ uint64_t llcomp_mi_codec_workspace_bytes(const llcomp_mi_codec* codec);
  * middle of a pipeline).  Idempotent; LLCOMP_MI_NOMEM when the device cannot give the memory. */
 #define LLCOMP_MI_PREPARE_ENCODE 1u
 #define LLCOMP_MI_PREPARE_DECODE 2u
+#define LLCOMP_MI_PREPARE_REGION 8u /* the region decode's two arrays (12 B per slice), and state tables if a region may need them (bit 2 stays unused) */
 int llcomp_mi_codec_prepare(llcomp_mi_codec* codec, uint32_t what);
 /* Upper bound on the packed payload bytes the codec can emit for any input (13 B per sample + slack). */
 uint64_t llcomp_mi_codec_max_payload_bytes(const llcomp_mi_codec* codec);
@@ -226,6 +248,16 @@ int llcomp_mi_codec_encode(llcomp_mi_codec* codec, const void* d_px, void* d_pay
 /* decode: inverse.  d_payload/d_slice_len as produced by encode (payload_bytes = total), d_px out. */
 int llcomp_mi_codec_decode(llcomp_mi_codec* codec, const void* d_payload, uint64_t payload_bytes,
                            const void* d_slice_len, void* d_px, void* d_status, void* stream);
+/* Region decode of a batch: the rectangle (x, y, rw, rh) of every frame (one rectangle for all frames of the call) -> d_px
+ * [frames][rh][rw][c].  d_payload / payload_bytes / d_slice_len are the FULL batch's, as for llcomp_mi_codec_decode; only the covered
+ * slices' table entries and payload bytes are read (semantics and verdicts: llcomp_mi_decode_region).  The decoder runs on the geometry
+ * of the covered sub-image inside the codec's own workspace.  Asynchronous on `stream` like a decode; profile slots 4, 5, 6 (and 7).
+ * The first region call allocates 12 B per slice (LLCOMP_MI_PREPARE_REGION does it ahead) and can return LLCOMP_MI_NOMEM. */
+int llcomp_mi_codec_decode_region(llcomp_mi_codec* codec, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                  uint32_t x, uint32_t y, uint32_t rw, uint32_t rh, void* d_px, void* d_status, void* stream);
+/* Diagnostic: the kernel family (encoding of llcomp_mi_codec_kernel_family) a region decode of this rectangle runs -- the sub-image's
+ * geometry may select another one than the codec's (a 1-row remainder of 2-row tiles runs the row kernels).  0 for a bad rectangle. */
+uint32_t llcomp_mi_codec_region_family(const llcomp_mi_codec* codec, uint32_t x, uint32_t y, uint32_t rw, uint32_t rh);
 /* Stage-A only (context + prediction model), for tests and profiling: d_sym u32[frames*h*w*c],
  * low 16 bits = folded context (0..7925), high 16 bits = folded residual (two's complement). */
 int llcomp_mi_codec_model(llcomp_mi_codec* codec, const void* d_px, void* d_sym, void* stream);

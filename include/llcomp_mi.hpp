@@ -10,6 +10,7 @@
 //   std::vector<uint8_t> llcomp::compressImage(rgb,w,h,c)      :358     same signature (+ optional llcomp::Options)
 //   struct llcomp::RawImage{pixels,width,height,channels}      :454     same members (width/height widened to 32 bit)
 //   llcomp::RawImage llcomp::decompressImage(data)             :461     same signature (+ overload with a device list)
+//                                                                       + llcomp::decompressRegion(data, x, y, w, h): one rectangle
 //   throw std::runtime_error("Invalid magic number")           :466     same text
 //   throw std::runtime_error("Invalid exponent")               :233     same text
 //
@@ -116,6 +117,22 @@ inline RawImage decompressImage(const std::vector<uint8_t>& data, const std::vec
     uint32_t w = 0, h = 0, c = 0;
     if (int rc = llcomp_mi_decode_devices(data.data(), data.size(), devs.data(), uint32_t(devs.size()), 0,
                                           legacy_small_model ? LLCOMP_MI_FLAG_SMALL_MODEL : 0u, &px, &w, &h, &c))
+        detail::raise(rc);
+    RawImage img{std::vector<uint8_t>(px, px + size_t(w) * h * c), w, h, uint8_t(c)};
+    llcomp_mi_free(px);
+    return img;
+}
+
+// The rectangle (x, y, w, h) of the picture only (llcomp_mi_decode_region): only the slices of the tiles it touches are read and decoded.
+// RawImage{pixels: h x w x channels, w, h, channels}.  Throws like decompressImage; std::invalid_argument for a rectangle the picture
+// does not hold.  A region decode does not validate the rest of the container.
+inline RawImage decompressRegion(const std::vector<uint8_t>& data, uint32_t x, uint32_t y, uint32_t w, uint32_t h, int device = -1,
+                                 bool legacy_small_model = false) {
+    detail::check_abi();
+    uint8_t* px = nullptr;
+    uint32_t c = 0;
+    if (int rc = llcomp_mi_decode_region(data.data(), data.size(), device, legacy_small_model ? LLCOMP_MI_FLAG_SMALL_MODEL : 0u, x, y, w, h,
+                                         &px, &c))
         detail::raise(rc);
     RawImage img{std::vector<uint8_t>(px, px + size_t(w) * h * c), w, h, uint8_t(c)};
     llcomp_mi_free(px);

@@ -6,6 +6,7 @@ with ctypes and keeps the reference's names and error behaviour:
 
     compress_image(rgb, width, height, channels)  <->  llcomp::compressImage    (/root/reference/llcomp.hpp:358)
     decompress_image(data) -> RawImage            <->  llcomp::decompressImage  (/root/reference/llcomp.hpp:461)
+    decompress_region(data, x, y, w, h)           <->  llcomp::decompressRegion (include/llcomp_mi.hpp: one rectangle, covered slices only)
     RawImage(pixels, width, height, channels)     <->  llcomp::RawImage         (/root/reference/llcomp.hpp:454-459)
     EXT = ".llcomp"                               <->  llcomp::ext              (/root/reference/llcomp.hpp:18)
 
@@ -114,6 +115,44 @@ def decompress_image(data, *, device=-1, small_model=False, devices=None, chunks
     finally:
         L.llcomp_mi_free(px)
     return RawImage(pixels, w.value, h.value, c.value)
+
+
+def region_plan(w, h, c, tile_w, tile_h, planar, x, y, rw, rh):
+    """((tx0, ty0, tx1, ty1), covered slices per frame) of the rectangle (x, y, rw, rh) -- llcomp_mi_region_plan, host only.  tile_w /
+    tile_h 0 = the whole width / height.  LlcompError(BAD_ARGS) for an empty rectangle or one outside the image."""
+    box, n = (C.c_uint32 * 4)(), C.c_uint32()
+    _check(_lib.load().llcomp_mi_region_plan(w, h, c, tile_w, tile_h, int(bool(planar)), x, y, rw, rh, box, C.byref(n)))
+    return tuple(box), n.value
+
+
+def decompress_region(data, x, y, w, h, *, device=-1, small_model=False):
+    """RawImage(pixels: np.uint8[h,w,c], w, h, c) of the rectangle (x, y, w, h) of the picture (llcomp_mi_decode_region): only the
+    slices of the tiles it touches are read and decoded.  A region decode does not validate the rest of the container."""
+    L = _lib.load()
+    data = bytes(data)
+    src = C.cast(C.c_char_p(data or b"\0"), _lib.u8p)
+    px, c = _lib.u8p(), C.c_uint32()
+    _check(L.llcomp_mi_decode_region(src, len(data), device, 1 if small_model else 0, x, y, w, h, C.byref(px), C.byref(c)))
+    try:
+        n = w * h * c.value
+        pixels = np.ctypeslib.as_array(px, shape=(max(n, 1),))[:n].copy().reshape(h, w, c.value)
+    finally:
+        L.llcomp_mi_free(px)
+    return RawImage(pixels, w, h, c.value)
+
+
+def decompress_region_into(data, out, x, y, w, h, *, device=-1, small_model=False):
+    """llcomp_mi_decode_region_into: `data` / `out` numpy uint8 arrays owned by the caller -> channels.  Raises
+    LlcompError(OUTPUT_OVERFLOW) with .channels set (and `out` untouched) when `out` is smaller than w * h * channels."""
+    L = _lib.load()
+    c = C.c_uint32()
+    rc = L.llcomp_mi_decode_region_into(data.ctypes.data, data.size, device, 1 if small_model else 0, x, y, w, h, out.ctypes.data, out.size,
+                                        C.byref(c))
+    if rc != OK:
+        e = LlcompError(rc)
+        e.channels = c.value
+        raise e
+    return c.value
 
 
 def trim():
@@ -457,6 +496,19 @@ class Codec:
     def decode(self, d_payload, payload_bytes, d_slice_len, d_px, d_status, stream=0):
         _check(self._L.llcomp_mi_codec_decode(self._h, d_payload, payload_bytes, d_slice_len, d_px, d_status, stream))
 
+    def decode_region(self, d_payload, payload_bytes, d_slice_len, x, y, rw, rh, d_px, d_status, stream=0):
+        """the rectangle (x, y, rw, rh) of every frame -> d_px [frames][rh][rw][c] (llcomp_mi_codec_decode_region); d_payload /
+        d_slice_len are the full batch's"""
+        _check(self._L.llcomp_mi_codec_decode_region(self._h, d_payload, payload_bytes, d_slice_len, x, y, rw, rh, d_px, d_status, stream))
+
+    def region_family(self, x, y, rw, rh):
+        """the kernel family a region decode of this rectangle runs (the keys of .family), None for a bad rectangle"""
+        fam = self._L.llcomp_mi_codec_region_family(self._h, x, y, rw, rh)
+        if not fam:
+            return None
+        return {"rows": bool(fam & 1), "lds_table": bool(fam & 2), "snapshot": bool(fam & 16), "bank_cache": bool(fam & 32),
+                "lane_shift": (fam >> 8) & 0xFF, "slices_per_wave": (fam >> 16) & 0xFF}
+
     def model(self, d_px, d_sym, stream=0):
         _check(self._L.llcomp_mi_codec_model(self._h, d_px, d_sym, stream))
 
@@ -472,9 +524,9 @@ class Codec:
         _check(self._L.llcomp_mi_codec_get_profile(self._h, ms, C.byref(ne), C.byref(nd)))
         return dict(zip(self.PROFILE_SLOTS, list(ms))), ne.value, nd.value
 
-    def prepare(self, encode=True, decode=True):
-        """allocate now what the first encode / decode would allocate inside the call (llcomp_mi_codec_prepare)"""
-        _check(self._L.llcomp_mi_codec_prepare(self._h, (1 if encode else 0) | (2 if decode else 0)))
+    def prepare(self, encode=True, decode=True, region=False):
+        """allocate now what the first encode / decode / region decode would allocate inside the call (llcomp_mi_codec_prepare)"""
+        _check(self._L.llcomp_mi_codec_prepare(self._h, (1 if encode else 0) | (2 if decode else 0) | (8 if region else 0)))
 
     COUNTERS = ("dec_cached_waves", "dec_bypassed_waves", "cache_lookups", "cache_misses", "cache_writebacks", "dec_replays", "enc_carry_backs",
                 "generation_wraps", "dec_launches_cached", "dec_launches_plain")

@@ -29,6 +29,8 @@ SYMBOLS = [
     "llcomp_mi_set_pool_limit", "llcomp_mi_pool_limit", "llcomp_mi_pool_idle_bytes", "llcomp_mi_fnv1a64", "llcomp_mi_suggest_tile_w", "llcomp_mi_decode_into_flags", "llcomp_mi_device_range_sums",
     "llcomp_mi_decode_devices", "llcomp_mi_decode_into_devices", "llcomp_mi_last_device_error", "llcomp_mi_plan_chunks",
     "llcomp_mi_stream_create_multi", "llcomp_mi_stream_devices", "llcomp_mi_codec_get_counters", "llcomp_mi_codec_prepare",
+    "llcomp_mi_region_plan", "llcomp_mi_decode_region", "llcomp_mi_decode_region_into", "llcomp_mi_codec_decode_region",
+    "llcomp_mi_codec_region_family",
 ]
 
 u8p = C.POINTER(C.c_uint8)
@@ -211,6 +213,18 @@ def load():
         L.llcomp_mi_codec_prepare.argtypes = [C.c_void_p, C.c_uint32]
         L.llcomp_mi_codec_get_counters.restype = C.c_int
         L.llcomp_mi_codec_get_counters.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32, C.c_int]
+    if "LLCOMP_MI_LIB" not in os.environ or hasattr(L, "llcomp_mi_region_plan"):  # region decode
+        u32p = C.POINTER(C.c_uint32)
+        L.llcomp_mi_region_plan.restype = C.c_int
+        L.llcomp_mi_region_plan.argtypes = [C.c_uint32] * 10 + [u32p, u32p]
+        L.llcomp_mi_decode_region.restype = C.c_int
+        L.llcomp_mi_decode_region.argtypes = [u8p, C.c_size_t, C.c_int32, C.c_uint32] + [C.c_uint32] * 4 + [C.POINTER(u8p), u32p]
+        L.llcomp_mi_decode_region_into.restype = C.c_int
+        L.llcomp_mi_decode_region_into.argtypes = [C.c_void_p, C.c_size_t, C.c_int32, C.c_uint32] + [C.c_uint32] * 4 + [C.c_void_p, C.c_size_t, u32p]
+        L.llcomp_mi_codec_decode_region.restype = C.c_int
+        L.llcomp_mi_codec_decode_region.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p] * 3
+        L.llcomp_mi_codec_region_family.restype = C.c_uint32
+        L.llcomp_mi_codec_region_family.argtypes = [C.c_void_p] + [C.c_uint32] * 4
     if "LLCOMP_MI_LIB" not in os.environ and L.llcomp_mi_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.llcomp_mi_abi_version()}, this binding was written for {ABI_VERSION}: rebuild the library")
     _lib = L

@@ -90,8 +90,10 @@ struct Timed {
 
 // State tables in HBM are tagged with the generation of the call that wrote them instead of being cleared per call
 // (kernels.hpp): a real clear happens before the first call and whenever the 8-bit generation would repeat.
-int ensure_state_tables(llcomp_mi_codec* k) {
-    if (!k->need_states || k->d_states) return LLCOMP_MI_OK;
+// (need: the geometry about to run keeps its tables in HBM -- the codec's own, or a region's sub-geometry, which may need them where the
+// full geometry does not; the table is sized for the full geometry either way, and region_fits makes sure that is enough)
+int ensure_state_tables(llcomp_mi_codec* k, bool need) {
+    if (!need || k->d_states) return LLCOMP_MI_OK;
     const Geometry& g = k->g;
     if (dev_alloc(reinterpret_cast<void**>(&k->d_states), (uint64_t(lane_groups(g)) * kContexts << g.lane_shift) * 8) != hipSuccess) {
         k->d_states = nullptr;
@@ -101,10 +103,10 @@ int ensure_state_tables(llcomp_mi_codec* k) {
     k->state_generation = 0;
     return LLCOMP_MI_OK;
 }
-int next_state_generation(llcomp_mi_codec* k, hipStream_t s) {
-    if (!k->need_states) return LLCOMP_MI_OK;
+int next_state_generation(llcomp_mi_codec* k, hipStream_t s, bool need) {
+    if (!need) return LLCOMP_MI_OK;
     // first call that needs the tables (an encode-only codec with the snapshot pass never gets here; llcomp_mi_codec_prepare allocates them ahead)
-    if (int rc = ensure_state_tables(k)) return rc;
+    if (int rc = ensure_state_tables(k, true)) return rc;
     if (k->state_generation == 0 || k->state_generation >= 255) {
         const Geometry& g = k->g;
         if (k->state_generation >= 255) ++k->host_counters[kCtrGenerationWraps];
@@ -177,8 +179,8 @@ int ensure_snapshot_arrays(llcomp_mi_codec* k) {
 // kernels count {wavefronts, wavefronts that gave up}; when (nearly) all of the last cached launch did, the codec's next kPlainRun
 // decode calls run the plain kernel, then one call probes with the cache again.  Nothing waits: a result that has not arrived yet
 // leaves things as they are.  Same bytes either way (the tables are per call).
-bool use_bank_cache(llcomp_mi_codec* k) {
-    if (bank_cache_log2(k->g) == 0) return false;
+bool use_bank_cache(llcomp_mi_codec* k, const Geometry& g) {
+    if (bank_cache_log2(g) == 0) return false;
     if (k->fb_pending && k->fb_event && hipEventQuery(k->fb_event) == hipSuccess) {
         k->fb_pending = false;
         const uint64_t waves = k->h_feedback[0] - k->fb_seen[0], gave_up = k->h_feedback[1] - k->fb_seen[1];
@@ -225,6 +227,34 @@ struct DoneGuard {
     ~DoneGuard() { mark_done(k, s); }
 };
 
+// region decode: u32 lengths + u64 offsets of the covered slices (at most all of them)
+int ensure_region_arrays(llcomp_mi_codec* k) {
+    if (k->d_region_len) return LLCOMP_MI_OK;
+    const uint64_t n = k->g.n_slices;
+    if (dev_alloc(reinterpret_cast<void**>(&k->d_region_len), n * 4) != hipSuccess ||
+        dev_alloc(reinterpret_cast<void**>(&k->d_region_off), n * 8) != hipSuccess) {
+        dev_free(k->d_region_len);
+        dev_free(k->d_region_off);
+        k->d_region_len = nullptr;
+        k->d_region_off = nullptr;
+        return LLCOMP_MI_NOMEM;
+    }
+    k->allocated_bytes += n * 12;
+    return LLCOMP_MI_OK;
+}
+// A family that keeps its states on chip for the full geometry may not for a region's: one slice per wavefront (few big slices) can
+// become several per wavefront for a sub-image whose tiles were clamped.  (1-row slices stay 1-row slices.)
+bool region_may_need_states(const llcomp_mi_codec* k) { return !k->need_states && !rows_mode(k->g); }
+
+// the covered tiles and the sub-geometry of a rectangle; BAD_ARGS for a rectangle the frame does not hold, HIP_ERROR if the
+// sub-geometry's arrays would not fit the codec's workspace (region_fits: never by default, checked all the same)
+int region_setup(const llcomp_mi_codec* k, uint32_t x, uint32_t y, uint32_t rw, uint32_t rh, RegionBox& box, Geometry& sub) {
+    const Geometry& g = k->g;
+    if (!region_box(g.w, g.h, g.tile_w, g.tile_h, x, y, rw, rh, box)) return LLCOMP_MI_BAD_ARGS;
+    if (!region_geometry(g, box, k->tune, sub) || !region_fits(g, sub)) return LLCOMP_MI_HIP_ERROR;
+    return LLCOMP_MI_OK;
+}
+
 }  // namespace
 
 namespace llcomp_mi {
@@ -247,6 +277,8 @@ void codec_release(llcomp_mi_codec* k) {
     dev_free(k->d_scratch, k->done);
     dev_free(k->d_group_off, k->done);
     dev_free(k->d_total_tmp, k->done);
+    dev_free(k->d_region_len, k->done);
+    dev_free(k->d_region_off, k->done);
     dev_free(k->d_snap_sorted, k->done);
     dev_free(k->d_snap_banks, k->done);
     dev_free(k->d_snap_res, k->done);
@@ -330,6 +362,7 @@ int llcomp_mi_codec_create_ex(llcomp_mi_codec** out, int32_t device, uint32_t fr
     llcomp_mi_codec* k = new (std::nothrow) llcomp_mi_codec;
     if (!k) return LLCOMP_MI_NOMEM;
     k->g = g;
+    k->tune = current_tuning();
     k->device = dev;
     k->feedback = !current_tuning().nofeedback;
     k->overlap = current_tuning().overlap != 0;
@@ -348,7 +381,11 @@ int llcomp_mi_codec_create_ex(llcomp_mi_codec** out, int32_t device, uint32_t fr
     // What the codec can hold at most.  The state tables (decode, and encode without the snapshot pass) and the snapshot arrays
     // (encode) are allocated by the first call that needs them: a codec that only ever encodes, or only ever decodes, 64x64 tiles
     // holds 8.8 GB resp. 6.2 GB less per 16 frames of 4K than this figure.
-    k->workspace_bytes = b_sym + b_lanes + b_states + b_scratch + b_off + 8 + snap_el * (snapshot_chunked(g) ? 28 : 18);
+    // ... plus the two arrays of a region decode (12 B per slice), and the state tables a region's sub-geometry may need where the codec's
+    // own family keeps its states on chip (region_may_need_states)
+    const uint64_t b_region = uint64_t(g.n_slices) * 12 +
+                              (!k->need_states && !rows_mode(g) ? (uint64_t(lane_groups(g)) * kContexts << g.lane_shift) * 8 : 0);
+    k->workspace_bytes = b_sym + b_lanes + b_states + b_scratch + b_off + 8 + snap_el * (snapshot_chunked(g) ? 28 : 18) + b_region;
     const bool ok = dev_alloc(&k->d_sym_or_rec, b_sym) == hipSuccess && dev_alloc(&k->d_lane_order, b_lanes) == hipSuccess &&
                     dev_alloc(reinterpret_cast<void**>(&k->d_scratch), b_scratch) == hipSuccess &&
                     dev_alloc(reinterpret_cast<void**>(&k->d_group_off), b_off) == hipSuccess &&
@@ -372,7 +409,7 @@ void llcomp_mi_codec_destroy(llcomp_mi_codec* k) {
 }
 
 int llcomp_mi_codec_prepare(llcomp_mi_codec* k, uint32_t what) {
-    if (!k || (what & ~(LLCOMP_MI_PREPARE_ENCODE | LLCOMP_MI_PREPARE_DECODE))) return LLCOMP_MI_BAD_ARGS;
+    if (!k || (what & ~(LLCOMP_MI_PREPARE_ENCODE | LLCOMP_MI_PREPARE_DECODE | LLCOMP_MI_PREPARE_REGION))) return LLCOMP_MI_BAD_ARGS;
     DeviceGuard guard(k->device);
     if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
     if (what & LLCOMP_MI_PREPARE_ENCODE) {
@@ -380,10 +417,15 @@ int llcomp_mi_codec_prepare(llcomp_mi_codec* k, uint32_t what) {
             if (int rc = ensure_snapshot_arrays(k)) return rc;
         }
         if (!snapshot_mode(k->g) || snapshot_chunked(k->g))
-            if (int rc = ensure_state_tables(k)) return rc;
+            if (int rc = ensure_state_tables(k, k->need_states)) return rc;
     }
     if (what & LLCOMP_MI_PREPARE_DECODE)
-        if (int rc = ensure_state_tables(k)) return rc;
+        if (int rc = ensure_state_tables(k, k->need_states)) return rc;
+    if (what & LLCOMP_MI_PREPARE_REGION) {
+        if (int rc = ensure_region_arrays(k)) return rc;
+        if (region_may_need_states(k))
+            if (int rc = ensure_state_tables(k, true)) return rc;
+    }
     return LLCOMP_MI_OK;
 }
 
@@ -416,7 +458,7 @@ int llcomp_mi_codec_encode(llcomp_mi_codec* k, const void* d_px, void* d_payload
     // the pass carries a context's states from chunk to chunk through them, under a generation of its own)
     if (!snapshot_mode(g) || snapshot_chunked(g)) {
         Timed t(k, s, 0);
-        if (int rc = next_state_generation(k, s)) return rc;
+        if (int rc = next_state_generation(k, s, k->need_states)) return rc;
     }
     {
         Timed t(k, s, 1);
@@ -514,7 +556,7 @@ int llcomp_mi_codec_decode(llcomp_mi_codec* k, const void* d_payload, uint64_t p
     HIP_TRY(hipMemsetAsync(d_status, 0, 4, s));
     {
         Timed t(k, s, 7);
-        if (int rc = next_state_generation(k, s)) return rc;
+        if (int rc = next_state_generation(k, s, k->need_states)) return rc;
     }
     {
         Timed t(k, s, 4);
@@ -529,7 +571,7 @@ int llcomp_mi_codec_decode(llcomp_mi_codec* k, const void* d_payload, uint64_t p
     }
     {
         Timed t(k, s, 5);
-        const bool cache = use_bank_cache(k);
+        const bool cache = use_bank_cache(k, g);
         HIP_TRY(launch_decode_slices(g, k->d_scratch, static_cast<const uint32_t*>(d_slice_len), k->d_states, k->state_generation,
                                      static_cast<int16_t*>(k->d_lane_order), static_cast<uint32_t*>(d_status), k->d_counters, cache, s));
         if (cache) queue_feedback(k, s);
@@ -542,6 +584,64 @@ int llcomp_mi_codec_decode(llcomp_mi_codec* k, const void* d_payload, uint64_t p
             HIP_TRY(launch_from_lane_order_i16(g, static_cast<const int16_t*>(k->d_lane_order),
                                                static_cast<int16_t*>(k->d_sym_or_rec), s));
             HIP_TRY(launch_model_inv(g, static_cast<const int16_t*>(k->d_sym_or_rec), static_cast<uint8_t*>(d_px), s));
+        }
+    }
+    ++k->n_decode;
+    return LLCOMP_MI_OK;
+}
+
+uint32_t llcomp_mi_codec_region_family(const llcomp_mi_codec* k, uint32_t x, uint32_t y, uint32_t rw, uint32_t rh) {
+    RegionBox box;
+    Geometry sub;
+    if (!k || region_setup(k, x, y, rw, rh, box, sub)) return 0;
+    return (sub.flags & 0xFFu) | (sub.lane_shift << 8) | (sub.lpw << 16);
+}
+
+// Region decode (DESIGN.md "Region decode"): the full geometry's group offsets locate the covered slices in the full payload, and the
+// decoder runs on the covered sub-image's geometry in the codec's own workspace.  Same verdicts as a full decode, from the covered
+// slices only.
+int llcomp_mi_codec_decode_region(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len, uint32_t x,
+                                  uint32_t y, uint32_t rw, uint32_t rh, void* d_px, void* d_status, void* stream) {
+    if (!k || !d_payload || !d_slice_len || !d_px || !d_status) return LLCOMP_MI_BAD_ARGS;
+    RegionBox box;
+    Geometry sub;
+    if (int rc = region_setup(k, x, y, rw, rh, box, sub)) return rc;
+    DeviceGuard guard(k->device);
+    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
+    if (int rc = ensure_region_arrays(k)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Geometry& g = k->g;
+    DoneGuard done_guard{k, s};
+    HIP_TRY(hipMemsetAsync(d_status, 0, 4, s));
+    {
+        // (a generation of its own: the sub-geometry maps slices to lane groups differently, and the tagged tables are shared with
+        // the full decodes)
+        Timed t(k, s, 7);
+        if (int rc = next_state_generation(k, s, slices_need_state_tables(sub))) return rc;
+    }
+    {
+        Timed t(k, s, 4);
+        HIP_TRY(launch_group_sums(g, static_cast<const uint32_t*>(d_slice_len), k->d_group_off, s));
+        HIP_TRY(launch_scan_groups(g, k->d_group_off, k->d_total_tmp, s));
+        HIP_TRY(launch_region_index(g, sub, box, static_cast<const uint32_t*>(d_slice_len), k->d_group_off, k->d_region_len, k->d_region_off, s));
+        HIP_TRY(launch_stage_region_streams(sub, static_cast<const uint8_t*>(d_payload), payload_bytes, k->d_region_len, k->d_region_off,
+                                            k->d_scratch, static_cast<uint32_t*>(d_status), s));
+    }
+    {
+        Timed t(k, s, 5);
+        const bool cache = use_bank_cache(k, sub);
+        HIP_TRY(launch_decode_slices(sub, k->d_scratch, k->d_region_len, k->d_states, k->state_generation, static_cast<int16_t*>(k->d_lane_order),
+                                     static_cast<uint32_t*>(d_status), k->d_counters, cache, s));
+        if (cache) queue_feedback(k, s);
+    }
+    {
+        Timed t(k, s, 6);
+        const Crop cr{x - box.tx0 * g.tile_w, y - box.ty0 * g.tile_h, rw, rh};
+        if (model_is_fused(sub)) {
+            HIP_TRY(launch_model_rows_inv_crop(sub, static_cast<const int16_t*>(k->d_lane_order), static_cast<uint8_t*>(d_px), cr, s));
+        } else {
+            HIP_TRY(launch_from_lane_order_i16(sub, static_cast<const int16_t*>(k->d_lane_order), static_cast<int16_t*>(k->d_sym_or_rec), s));
+            HIP_TRY(launch_model_inv_crop(sub, static_cast<const int16_t*>(k->d_sym_or_rec), static_cast<uint8_t*>(d_px), cr, s));
         }
     }
     ++k->n_decode;

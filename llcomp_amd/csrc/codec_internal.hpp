@@ -29,6 +29,11 @@ struct llcomp_mi_codec {
     uint8_t* d_scratch = nullptr;    // slice streams in stream lane order: 16-byte units [group][unit][lane]
     uint64_t* d_group_off = nullptr; // u64[lane groups + 1]: payload offset of every lane group's first slice
     uint64_t* d_total_tmp = nullptr;
+    // region decode (llcomp_mi_codec_decode_region): length and payload offset of every covered slice, u32[n_slices] + u64[n_slices],
+    // allocated by the first region call (or llcomp_mi_codec_prepare(LLCOMP_MI_PREPARE_REGION))
+    uint32_t* d_region_len = nullptr;
+    uint64_t* d_region_off = nullptr;
+    llcomp_mi::Tuning tune{};        // the hooks the geometry was made with (a region's sub-geometry is made with the same)
     void* d_snap_sorted = nullptr;   // snapshot pass of the 2-D encoder (snapshot.hpp): banks in context-sorted order,
     void* d_snap_banks = nullptr;    // banks in stream order, residuals in stream order; null unless snapshot_mode(g)
     void* d_snap_res = nullptr;

@@ -92,6 +92,21 @@ uint32_t llcomp_mi_slice_count(uint32_t w, uint32_t h, uint32_t c, uint32_t tile
     return g.slices_per_frame;
 }
 
+int llcomp_mi_region_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar, uint32_t x, uint32_t y,
+                          uint32_t rw, uint32_t rh, uint32_t box[4], uint32_t* slices_per_frame) {
+    if (!box || !slices_per_frame || c < 1 || c > kMaxChannels) return LLCOMP_MI_BAD_ARGS;
+    RegionBox b;
+    if (!region_box(w, h, tile_w, tile_h, x, y, rw, rh, b)) return LLCOMP_MI_BAD_ARGS;
+    const uint64_t n = uint64_t(b.tx1 - b.tx0) * (b.ty1 - b.ty0) * (planar ? c : 1u);
+    if (n >= (1ull << 31)) return LLCOMP_MI_OUT_OF_RANGE;
+    box[0] = b.tx0;
+    box[1] = b.ty0;
+    box[2] = b.tx1;
+    box[3] = b.ty1;
+    *slices_per_frame = uint32_t(n);
+    return LLCOMP_MI_OK;
+}
+
 int llcomp_mi_probe(const uint8_t* data, size_t len, llcomp_mi_info* info) {
     if (!data || !info) return LLCOMP_MI_BAD_ARGS;
     std::memset(info, 0, sizeof(*info));

@@ -5,6 +5,7 @@
 // sub-image, llcomp.hpp:390-449) or one colour-transformed channel plane of it (planar == 1).  Slices have
 // fresh adaptive state and slice-local border rules, so they are independent: one GPU lane each.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 
@@ -176,6 +177,58 @@ inline bool make_geometry(Geometry& g, uint32_t frames, uint32_t w, uint32_t h, 
     if (!(g.flags & (kGeoRows | kGeoLdsTable)) && g.nch <= 4 && !tune.nocache) g.flags |= kGeoBankCache;
     if (tune.force_replay) g.flags |= kGeoForceReplay;
     if (small_model) g.flags |= kGeoSmallModel;
+    return true;
+}
+
+// ---- region decode (DESIGN.md "Region decode") ----------------------------------------------------------------------------
+// A rectangle (x, y, rw, rh) of one frame is rebuilt from the slices of the tiles it touches alone: every slice is the reference
+// stream of its own crop, with fresh state and slice-local borders.  Tile columns [tx0, tx1) x tile rows [ty0, ty1) are covered.
+struct RegionBox {
+    uint32_t tx0, ty0, tx1, ty1;
+};
+// false for an empty rectangle or one that leaves the image (the sums are taken in 64 bits: an x + rw that wraps is refused);
+// tile_w / tile_h 0 (or beyond the image) = the whole width / height
+inline bool region_box(uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h, uint32_t x, uint32_t y, uint32_t rw, uint32_t rh,
+                       RegionBox& b) {
+    if (!w || !h || !rw || !rh || uint64_t(x) + rw > w || uint64_t(y) + rh > h) return false;
+    if (tile_w == 0 || tile_w > w) tile_w = w;
+    if (tile_h == 0 || tile_h > h) tile_h = h;
+    const uint64_t ntx = (uint64_t(w) + tile_w - 1) / tile_w, nty = (uint64_t(h) + tile_h - 1) / tile_h;
+    b.tx0 = x / tile_w;
+    b.ty0 = y / tile_h;
+    b.tx1 = uint32_t(std::min<uint64_t>((uint64_t(x) + rw + tile_w - 1) / tile_w, ntx));
+    b.ty1 = uint32_t(std::min<uint64_t>((uint64_t(y) + rh + tile_h - 1) / tile_h, nty));
+    return true;
+}
+// The geometry of the covered sub-image: same frames, channels, tiling, planar setting, tuning and small model as `full`, width
+// min(tx1 * tile_w, w) - tx0 * tile_w (height alike).  Sub-slice j IS covered slice j of `full`, with the same dimensions (ids run
+// frame-major, then tile row, tile column, plane; region_full_id).  When only the partial last tile column / row is covered,
+// make_geometry clamps tile_w / tile_h to the sub-image and the kernel family may change (a 1-row remainder of 2-row tiles runs the
+// row kernels): the bytes cannot, each slice being the reference stream of its crop.
+inline bool region_geometry(const Geometry& full, const RegionBox& b, const Tuning& tune, Geometry& sub) {
+    const uint32_t w = std::min<uint64_t>(uint64_t(b.tx1) * full.tile_w, full.w) - b.tx0 * full.tile_w;
+    const uint32_t h = std::min<uint64_t>(uint64_t(b.ty1) * full.tile_h, full.h) - b.ty0 * full.tile_h;
+    return make_geometry(sub, full.frames, w, h, full.c, full.tile_w, full.tile_h, full.planar, tune, (full.flags & kGeoSmallModel) != 0);
+}
+LLMI_HD inline uint32_t region_full_id(const Geometry& full, const Geometry& sub, const RegionBox& b, uint32_t j) {
+    const uint32_t f = j / sub.slices_per_frame, s = j - f * sub.slices_per_frame;
+    const uint32_t planes = full.planar ? full.c : 1u;
+    const uint32_t tile = s / planes, ch = s - tile * planes;
+    const uint32_t ty = tile / sub.ntx, tx = tile - ty * sub.ntx;
+    return f * full.slices_per_frame + ((b.ty0 + ty) * full.ntx + b.tx0 + tx) * planes + ch;
+}
+// Does every array the decoder touches for `sub` fit the one the codec sized for `full`?  Lane groups x group width (scratch, state
+// tables), x samples per slice (lane-order arrays), bytes per slice (scratch).  default_lane_shift is monotone, so this holds by
+// default; forced LLCOMP_MI_LANE_SHIFT / LLCOMP_MI_LPW and the "few big slices: one per wavefront" rule are checked, not assumed.
+// A sub-geometry that needs the image-order intermediate needs it of a codec that has one (`full` not on the fused row path).
+inline bool region_fits(const Geometry& full, const Geometry& sub) {
+    auto lanes = [](const Geometry& g) { return ((uint64_t(g.n_slices) + (1u << g.lane_shift) - 1) >> g.lane_shift) << g.lane_shift; };
+    auto fused = [](const Geometry& g) { return g.planar && (g.flags & kGeoRows) && g.c <= 4; };
+    if (sub.frames != full.frames || sub.c != full.c || sub.n_slices > full.n_slices) return false;
+    if (lanes(sub) > lanes(full)) return false;
+    if (lanes(sub) * sub.slice_samples > lanes(full) * full.slice_samples) return false;
+    if (uint64_t(lanes(sub)) * sub.slice_cap > uint64_t(lanes(full)) * full.slice_cap) return false;
+    if (!fused(sub) && fused(full)) return false;
     return true;
 }
 

@@ -328,6 +328,70 @@ int decode_common(const uint8_t* data, size_t len, int32_t device, uint32_t flag
     return LLCOMP_MI_OK;
 }
 
+// Region decode (llcomp_mi_decode_region): the lane of the container's full shape, but only the header + slice table and the payload
+// span of the covered slices cross PCIe (the span lies at its own offset in the lane's container buffer; the bytes around it are never
+// read), and only the rectangle comes back
+int decode_region_common(const uint8_t* data, size_t len, int32_t device, uint32_t flags, uint32_t x, uint32_t y, uint32_t rw, uint32_t rh,
+                         uint8_t* px, size_t px_cap, uint8_t** px_alloc, uint32_t* c) {
+    if (flags & ~LLCOMP_MI_FLAG_SMALL_MODEL) return LLCOMP_MI_BAD_ARGS;
+    llcomp_mi_info info;
+    if (int rc = llcomp_mi_probe(data, len, &info)) return rc;
+    const bool legacy = info.format == LLCOMP_MI_FORMAT_LEGACY;
+    if (int rc = check_shape(info.width, info.height, info.channels, legacy)) return rc;
+    uint32_t box[4], covered = 0;
+    if (int rc = llcomp_mi_region_plan(info.width, info.height, info.channels, info.tile_w, info.tile_h, info.planar, x, y, rw, rh, box, &covered))
+        return rc;
+    *c = info.channels;
+    const uint64_t out = uint64_t(rw) * rh * info.channels;
+    if (px && out > px_cap) return LLCOMP_MI_OUTPUT_OVERFLOW;  // the channel count is reported: the caller can size its buffer
+    LaneLease lease;
+    if (int rc = lane_acquire(&lease.l, device, info.width, info.height, info.channels, info.tile_w, info.tile_h, info.planar, legacy,
+                              len - info.payload_offset + 16, legacy ? (flags & LLCOMP_MI_FLAG_SMALL_MODEL) != 0 : info.small_model != 0))
+        return rc;
+    HostLane* l = lease.l;
+    DeviceGuard guard(l->k->device);
+    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
+    const uint64_t payload = len - l->head_bytes;
+    // the covered slices' bytes: from the first covered slice's first byte to the last one's end (slices run tile row, tile column,
+    // plane; the table lies in host memory, probe has made sure it is all there)
+    uint64_t begin = 0, end = payload;
+    if (!legacy) {
+        const uint32_t planes = info.planar ? info.channels : 1u, ntx = (info.width + info.tile_w - 1) / info.tile_w;
+        const uint64_t first = (uint64_t(box[1]) * ntx + box[0]) * planes, last = ((uint64_t(box[3]) - 1) * ntx + box[2] - 1) * planes + planes - 1;
+        const uint8_t* table = data + info.table_offset;
+        auto len_at = [&](uint64_t i) { uint32_t v; std::memcpy(&v, table + 4 * i, 4); return uint64_t(v); };  // (little-endian hosts)
+        uint64_t pos = 0;
+        for (uint64_t i = 0; i <= last; ++i) {
+            if (i == first) begin = pos;
+            pos += len_at(i);
+        }
+        begin = std::min(begin, payload);
+        end = std::min(pos, payload);
+    }
+    LLMI_HIP_TRY(copy_user(l->d_container, data, l->head_bytes, hipMemcpyHostToDevice, l->stream));
+    LLMI_HIP_TRY(copy_user(l->d_payload() + begin, data + l->head_bytes + begin, end - begin, hipMemcpyHostToDevice, l->stream));
+    if (legacy) {
+        const uint32_t one = uint32_t(std::min<uint64_t>(payload, 0xFFFFFFFFull));
+        LLMI_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(l->d_len_legacy), int(one), 1, l->stream));
+    }
+    if (int rc = llcomp_mi_codec_decode_region(l->k, l->d_payload(), payload, l->d_len(), x, y, rw, rh, l->d_px, l->d_meta + 1, l->stream))
+        return rc;
+    LLMI_HIP_TRY(hipMemcpyAsync(l->h_meta, l->d_meta, 16, hipMemcpyDeviceToHost, l->stream));
+    LLMI_HIP_TRY(hipStreamSynchronize(l->stream));
+    if (int rc = status_from_bits(uint32_t(l->h_meta[1]))) return rc;
+    uint8_t* dst = px;
+    if (!dst) {
+        dst = static_cast<uint8_t*>(std::malloc(out));
+        if (!dst) return LLCOMP_MI_NOMEM;
+    }
+    if (copy_user(dst, l->d_px, out, hipMemcpyDeviceToHost, l->stream) != hipSuccess) {
+        if (!px) std::free(dst);
+        return LLCOMP_MI_HIP_ERROR;
+    }
+    if (px_alloc) *px_alloc = dst;
+    return LLCOMP_MI_OK;
+}
+
 // decode over a device list: sliced containers whose table fits their payload are dealt over the devices (multidev.hip); a legacy
 // stream, a list of one device and damaged containers (the one-device path forms their verdict) go to devices[0]
 int decode_devices_common(const uint8_t* data, size_t len, const DeviceList& dl, uint32_t flags, uint8_t* px, size_t px_cap, uint8_t** px_alloc,
@@ -399,6 +463,19 @@ int llcomp_mi_decode_into_devices(const uint8_t* data, size_t len, const int32_t
                                   uint32_t flags, uint8_t* px, size_t px_cap, uint32_t* w, uint32_t* h, uint32_t* c) {
     if (!data || !px || !w || !h || !c || !devices || !n_devices || n_devices > LLCOMP_MI_MAX_DEVICES) return LLCOMP_MI_BAD_ARGS;
     return decode_devices_common(data, len, DeviceList{devices, n_devices, chunks_per_device}, flags, px, px_cap, nullptr, w, h, c);
+}
+
+int llcomp_mi_decode_region(const uint8_t* data, size_t len, int32_t device, uint32_t flags, uint32_t x, uint32_t y, uint32_t rw,
+                            uint32_t rh, uint8_t** px, uint32_t* c) {
+    if (!data || !px || !c) return LLCOMP_MI_BAD_ARGS;
+    *px = nullptr;
+    return decode_region_common(data, len, device, flags, x, y, rw, rh, nullptr, 0, px, c);
+}
+
+int llcomp_mi_decode_region_into(const uint8_t* data, size_t len, int32_t device, uint32_t flags, uint32_t x, uint32_t y, uint32_t rw,
+                                 uint32_t rh, uint8_t* px, size_t px_cap, uint32_t* c) {
+    if (!data || !px || !c) return LLCOMP_MI_BAD_ARGS;
+    return decode_region_common(data, len, device, flags, x, y, rw, rh, px, px_cap, nullptr, c);
 }
 
 void llcomp_mi_trim(void) {

@@ -105,4 +105,22 @@ hipError_t launch_decode_slices(const Geometry& g, const uint8_t* d_units, const
                                 uint64_t* d_states, uint32_t generation, int16_t* d_rec, uint32_t* d_status, unsigned long long* d_counters,
                                 bool bank_cache, hipStream_t stream);
 
+// ---- region decode (codec.hip: llcomp_mi_codec_decode_region; DESIGN.md "Region decode") ----------------------------------------
+// Sub-slice j of the covered sub-image `sub` = full slice region_full_id(j): its length (from the FULL table) and its offset in the
+// full payload (from the full geometry's group offsets, launch_group_sums + launch_scan_groups) -> d_sub_len u32[n'], d_sub_off u64[n'].
+hipError_t launch_region_index(const Geometry& full, const Geometry& sub, const RegionBox& box, const uint32_t* d_slice_len,
+                               const uint64_t* d_group_off, uint32_t* d_sub_len, uint64_t* d_sub_off, hipStream_t stream);
+// launch_stage_streams with one offset per slice: the covered slices -> the sub-geometry's stream lane order (TRUNCATED as there)
+hipError_t launch_stage_region_streams(const Geometry& sub, const uint8_t* d_payload, uint64_t payload_bytes, const uint32_t* d_sub_len,
+                                       const uint64_t* d_sub_off, uint8_t* d_units, uint32_t* d_status, hipStream_t stream);
+// The rectangle of the sub-image that becomes the output, in the sub-image's pixel coordinates.  The crop variants of stage A's
+// inverse write exactly frames x rh x rw x c bytes, [frames][rh][rw][c], and nothing else.
+struct Crop {
+    uint32_t x0, y0, rw, rh;
+};
+// image-order samples of the sub-image (after launch_from_lane_order_i16 on `sub`) -> the rectangle; any channel count
+hipError_t launch_model_inv_crop(const Geometry& sub, const int16_t* d_rec, uint8_t* d_px, const Crop& cr, hipStream_t stream);
+// the fused row path (model_is_fused(sub)): lane-order samples -> the rectangle
+hipError_t launch_model_rows_inv_crop(const Geometry& sub, const int16_t* d_lanes, uint8_t* d_px, const Crop& cr, hipStream_t stream);
+
 }  // namespace llcomp_mi

@@ -13,6 +13,8 @@
 //                 prefix sum of the slice lengths, one value per lane group (the rest is a wave prefix in pack / stage).
 //   k_pack_payload / k_stage_streams
 //                 LDS-tile moves between the packed payload and the stream lane order the serial kernels use.
+//   k_region_index / k_stage_region_streams / k_model_inv_crop / k_model_rows_inv_crop
+//                 region decode: the covered slices of a full payload -> lane order, and stage A's inverse of one rectangle.
 // None of this is GEMM-shaped; there is no MFMA here on purpose.
 #include <algorithm>
 
@@ -225,6 +227,36 @@ __global__ __launch_bounds__(256) void k_model_inv_any(const Geometry g, const i
     for (; k < g.c; ++k) o[k] = uint8_t(rec[sample_index(g, frame, y, x, k)]);  // llcomp.hpp:541-543
 }
 
+// ---- stage A inverse of a region -------------------------------------------------------------------------------------------
+// `rec` holds the reconstructed samples of the covered sub-image (image order of the sub-geometry g); only the rectangle
+// (cr.x0, cr.y0, cr.rw, cr.rh) of it is turned into pixels, densely: px = [frames][rh][rw][c].  One thread per pixel of the
+// rectangle, so nothing outside it is ever stored.  C = 1..4 channels, or 0: any count (the plain form, like k_model_inv_any).
+// (Crop: kernels.hpp)
+template <int C>
+__global__ __launch_bounds__(256) void k_model_inv_crop(const Geometry g, const int16_t* __restrict__ rec, uint8_t* __restrict__ px,
+                                                        const Crop cr, size_t npix) {
+    const uint32_t c = C ? uint32_t(C) : g.c;
+    const size_t per_frame = size_t(cr.rw) * cr.rh;
+    for (size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x; i < npix; i += size_t(gridDim.x) * blockDim.x) {
+        const uint32_t f = uint32_t(i / per_frame);
+        const uint32_t rem = uint32_t(i - f * per_frame), yy = rem / cr.rw, xx = rem - yy * cr.rw;
+        const uint32_t y = cr.y0 + yy, x = cr.x0 + xx;
+        uint8_t* o = px + i * c;
+        uint32_t k = 0;
+        if (c >= 3) {  // llcomp.hpp:532-540
+            int r = rec[sample_index(g, f, y, x, 0)], gg = rec[sample_index(g, f, y, x, 1)], b = rec[sample_index(g, f, y, x, 2)];
+            gg -= (r + b) / 4;
+            r += gg;
+            b += gg;
+            o[0] = uint8_t(min(max(r, 0), 255));
+            o[1] = uint8_t(min(max(gg, 0), 255));
+            o[2] = uint8_t(min(max(b, 0), 255));
+            k = 3;
+        }
+        for (; k < c; ++k) o[k] = uint8_t(rec[sample_index(g, f, y, x, k)]);  // llcomp.hpp:541-543
+    }
+}
+
 // ---- slice length scan ------------------------------------------------------------------------------------------------
 // The packed payload holds the slices back to back in slice order, so slice i starts at the sum of the lengths before
 // it.  pack / stage work on whole lane groups (64 consecutive slices) and find a slice's offset as
@@ -326,6 +358,9 @@ struct GroupStreams {
     uint32_t len[64];
     uint32_t max_len;
 };
+// SLICE_OFF = false: `off` holds one offset per lane group (the slices of a group lie back to back); true: one per slice (region
+// decode: the covered slices of a group lie anywhere in the payload)
+template <bool SLICE_OFF = false>
 __device__ __forceinline__ void load_group_streams(const Geometry& g, uint32_t group, const uint32_t* slice_len,
                                                    const uint64_t* group_off, uint64_t limit, uint32_t* status,
                                                    uint32_t err_bit, GroupStreams& gs) {
@@ -334,7 +369,9 @@ __device__ __forceinline__ void load_group_streams(const Geometry& g, uint32_t g
         const bool live = threadIdx.x < (1u << g.lane_shift) && id < g.n_slices;
         uint32_t n = live ? slice_len[id] : 0;
         // offset of the slice = offset of its lane group + the lengths of the group's slices before it
-        unsigned long long o = group_off[group] + wave_inclusive_scan(n, threadIdx.x) - n;
+        unsigned long long o;
+        if constexpr (SLICE_OFF) o = live ? group_off[id] : 0ull;
+        else o = group_off[group] + wave_inclusive_scan(n, threadIdx.x) - n;
         if (live) {
             if (o + n > limit) {  // the slice does not fit the payload (decode: table promises too much)
                 atomicOr(status, err_bit);
@@ -457,6 +494,73 @@ __global__ __launch_bounds__(256) void k_stage_streams(const Geometry g, const u
         }
         __syncthreads();
     }
+}
+// region decode: the covered slices of the full payload -> the sub-geometry's stream lane order.  k_stage_streams with one offset
+// per slice (off = region_off of k_region_index) in place of one per lane group; the same verdicts.
+__global__ __launch_bounds__(256) void k_stage_region_streams(const Geometry g, const uint8_t* __restrict__ payload,
+                                                              uint64_t payload_bytes, const uint32_t* __restrict__ slice_len,
+                                                              const uint64_t* __restrict__ off, uint4* __restrict__ units,
+                                                              uint32_t* status) {
+    __shared__ uint32_t tile[64][kChunkDwords + 1];
+    __shared__ GroupStreams gs;
+    const uint32_t group = blockIdx.x;
+    load_group_streams<true>(g, group, slice_len, off, payload_bytes, status, kStTruncated, gs);
+    const uint32_t capdw = g.slice_cap >> 2;
+    const uint32_t a = threadIdx.x & 63, b = threadIdx.x >> 6;
+    const uint32_t dwi = threadIdx.x % kRunThreads, jb = threadIdx.x / kRunThreads;
+    // "+ 4": the dword right behind every stream is staged too (as zeros) -- the decoder clamps its reads to it.
+    // All loads of a thread are in flight before the first is stored, and the loads of the NEXT chunk are issued
+    // before this chunk's stores.  The last, partial dword of a stream is read as a whole dword and masked wherever the
+    // payload has the bytes (always, except at its very end).
+    constexpr int LPT = 64 / kRunsPerPass;  // slices per thread and chunk
+    uint32_t w[LPT];
+    auto request = [&](uint32_t c0) {
+#pragma unroll
+        for (int t = 0; t < LPT; ++t) {
+            const uint32_t j = jb + kRunsPerPass * t, n = gs.len[j], p = c0 * kChunkBytes + dwi * 4;
+            w[t] = 0;
+            if (p < n) {
+                const unsigned long long at = gs.off[j] + p;
+                const uint8_t* src = payload + at;
+                if (at + 4 <= payload_bytes) __builtin_memcpy(&w[t], src, 4);
+                else w[t] = load_bytes_le(src, n - p);
+            }
+        }
+    };
+    request(0);
+    for (uint32_t c0 = 0; c0 * kChunkBytes < gs.max_len + 4; ++c0) {
+#pragma unroll
+        for (int t = 0; t < LPT; ++t) {  // (the mask is applied here, not above: nothing waits for a load before all are issued)
+            const uint32_t j = jb + kRunsPerPass * t, n = gs.len[j], p = c0 * kChunkBytes + dwi * 4;
+            const uint32_t keep = n >= p + 4 ? 0xFFFFFFFFu : n > p ? 0xFFFFFFFFu >> (8 * (p + 4 - n)) : 0u;
+            tile[j][dwi] = w[t] & keep;
+        }
+        __syncthreads();
+        if ((c0 + 1) * kChunkBytes < gs.max_len + 4) request(c0 + 1);
+        // DWORD lane order for the decoder, [group][dword k][lane]: a wavefront stores one 256-byte row per dword index
+        uint32_t* const dw = reinterpret_cast<uint32_t*>(units);
+        for (uint32_t kk = b; kk < kChunkDwords; kk += 4) {
+            const uint32_t k = c0 * kChunkDwords + kk;
+            if (k < capdw && a < (1u << g.lane_shift)) dw[((size_t(group) * capdw + k) << g.lane_shift) + a] = tile[a][kk];
+        }
+        __syncthreads();
+    }
+}
+
+// Region decode: length and payload offset of every covered slice, from the FULL table and the full geometry's group offsets
+// (k_group_sums + k_scan_groups): sub-slice j is full slice region_full_id(j), at group_off[its group] + the lengths of the
+// group's slices before it (fewer than 64 loads, from lines the neighbouring threads read too).  Ranges past the payload are
+// left to the stage kernel, which reports them as for a full decode.
+__global__ __launch_bounds__(256) void k_region_index(const Geometry full, const Geometry sub, const RegionBox box,
+                                                      const uint32_t* __restrict__ slice_len, const uint64_t* __restrict__ group_off,
+                                                      uint32_t* __restrict__ sub_len, uint64_t* __restrict__ sub_off) {
+    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= sub.n_slices) return;
+    const uint32_t id = region_full_id(full, sub, box, j);
+    unsigned long long o = group_off[id >> full.lane_shift];
+    for (uint32_t i = id & ~((1u << full.lane_shift) - 1); i < id; ++i) o += slice_len[i];
+    sub_len[j] = slice_len[id];
+    sub_off[j] = o;
 }
 
 // ---- byte segments: the device-side concatenator of the multi-GPU path ------------------------------------------------
@@ -906,6 +1010,119 @@ __global__ __launch_bounds__(256) void k_model_rows_inv(const Geometry g, const 
     }
 }
 
+// Region decode: k_model_rows_inv for the covered sub-image g, writing only the rectangle `cr` of it, densely ([frames][rh][rw][c]).
+// The tiles' pixel runs are clipped to it; stores at its left and right edges go byte by byte.
+struct RowTileCrop {
+    long long base;      // output byte offset of the tile's pixel 0 (< 0 when the tile starts left of the rectangle)
+    uint32_t klo, khi;   // pixels [klo, khi) of the tile lie in the rectangle (khi = 0: none, e.g. a row above or below it)
+};
+template <int C>
+__device__ __forceinline__ void load_row_tiles_crop(const Geometry& g, uint32_t first_tile, uint32_t ntiles, const Crop& cr,
+                                                    RowTileCrop* tiles) {
+    if (threadIdx.x < ntiles) {
+        const uint32_t tile = first_tile + threadIdx.x;
+        const uint32_t per_frame = g.ntx * g.nty;
+        const uint32_t frame = tile / per_frame, rem = tile - frame * per_frame;
+        const uint32_t y = rem / g.ntx, tx = rem - y * g.ntx;
+        const uint32_t x0 = tx * g.tile_w;
+        const uint32_t sw = g.w - x0 < g.tile_w ? g.w - x0 : g.tile_w;
+        const uint32_t klo = cr.x0 > x0 ? cr.x0 - x0 : 0u;
+        uint32_t khi = cr.x0 + cr.rw > x0 ? min(sw, cr.x0 + cr.rw - x0) : 0u;
+        if (y < cr.y0 || y >= cr.y0 + cr.rh || khi <= klo) khi = 0;
+        tiles[threadIdx.x].base = ((long long)(size_t(frame) * cr.rh + (y - cr.y0)) * cr.rw + (long long)x0 - (long long)cr.x0) * C;
+        tiles[threadIdx.x].klo = klo;
+        tiles[threadIdx.x].khi = khi;
+    }
+}
+template <int C>
+__global__ __launch_bounds__(256) void k_model_rows_inv_crop(const Geometry g, const int16_t* __restrict__ lanes,
+                                                             uint8_t* __restrict__ px, const Crop cr) {
+    constexpr int K = 64, TPG = 64 / C + 2;
+    __shared__ __attribute__((aligned(4))) int16_t tile[K][64 + C + 1 + ((C + 1) & 1)];  // even row length: dword rows
+    __shared__ RowTileCrop tiles[TPG];
+    const uint32_t chunks = (g.tile_w + K - 1) / K;
+    uint32_t group, chunk;
+    if (!xcd_chunk_group((g.n_slices + (1u << g.lane_shift) - 1) >> g.lane_shift, chunks, group, chunk)) return;  // (uniform per block)
+    const uint32_t k0 = chunk * K;
+    const uint32_t gw = 1u << g.lane_shift;
+    const uint32_t first_id = group << g.lane_shift;
+    const uint32_t end_id = first_id + gw < g.n_slices ? first_id + gw : g.n_slices;
+    const uint32_t first_tile = (first_id + C - 1) / C;          // first tile whose channel 0 is in this group
+    const uint32_t end_tile = (end_id + C - 1) / C;              // one past the last such tile
+    if (first_tile >= end_tile) return;
+    const uint32_t ntiles = end_tile - first_tile;
+    load_row_tiles_crop<C>(g, first_tile, ntiles, cr, tiles);
+    // LDS column = lane index relative to this group (0..gw-1), columns gw.. = first C-1 lanes of the NEXT group.
+    // Rows of this group are read as whole 128-byte pieces (32 dwords = 64 samples); the few extra lanes one by one.
+    {   // (all eight loads of a thread are in flight before the first one is stored to LDS: the kernel is bound by the
+        // latency of its phases, one memory round trip per block instead of eight)
+        uint32_t w[K * 32 / 256];
+#pragma unroll
+        for (int it = 0; it < K * 32 / 256; ++it) {
+            const uint32_t i = threadIdx.x + 256 * it, kk = i >> 5, d = i & 31, k = k0 + kk;
+            w[it] = 0;
+            if (k < g.tile_w && g.lane_shift == 6)
+                w[it] = *reinterpret_cast<const uint32_t*>(lanes + lane_order_index(g, first_id + 2 * d, k));
+        }
+#pragma unroll
+        for (int it = 0; it < K * 32 / 256; ++it) {
+            const uint32_t i = threadIdx.x + 256 * it, kk = i >> 5, d = i & 31;
+            *reinterpret_cast<uint32_t*>(&tile[kk][2 * d]) = w[it];
+        }
+    }
+    if (g.lane_shift != 6) {  // fewer than 64 slices in total: narrow group, plain element loads
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < uint32_t(K) * gw; i += 256) {
+            const uint32_t kk = i / gw, col = i - kk * gw, k = k0 + kk;
+            tile[kk][col] = (first_id + col < g.n_slices && k < g.tile_w) ? lanes[lane_order_index(g, first_id + col, k)] : int16_t(0);
+        }
+    }
+    if constexpr (C > 1) {
+        for (uint32_t i = threadIdx.x; i < uint32_t(K) * (C - 1); i += 256) {
+            const uint32_t kk = i / (C - 1), e = i - kk * (C - 1), k = k0 + kk;
+            const uint32_t id = first_id + gw + e;
+            tile[kk][gw + e] = (id < g.n_slices && k < g.tile_w) ? lanes[lane_order_index(g, id, k)] : int16_t(0);
+        }
+    }
+    __syncthreads();
+    const uint32_t col0 = first_tile * C - first_id;  // group-relative lane of the first tile's channel 0
+    const uint32_t q4 = threadIdx.x & 15;  // which group of 4 pixels of the 64-sample chunk
+    for (uint32_t tt = threadIdx.x >> 4; tt < ntiles; tt += 16) {
+        const uint32_t sw = tiles[tt].khi, klo = tiles[tt].klo, kb = k0 + 4 * q4;
+        if (kb >= sw || kb + 4 <= klo) continue;
+        uint8_t bytes[4 * C];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int16_t* s = &tile[4 * q4 + i][col0 + tt * C];
+            if constexpr (C >= 3) {  // llcomp.hpp:532-543
+                int r = s[0], gg = s[1], bb = s[2];
+                gg -= (r + bb) / 4;
+                r += gg;
+                bb += gg;
+                bytes[i * C + 0] = uint8_t(min(max(r, 0), 255));
+                bytes[i * C + 1] = uint8_t(min(max(gg, 0), 255));
+                bytes[i * C + 2] = uint8_t(min(max(bb, 0), 255));
+                if constexpr (C == 4) bytes[i * C + 3] = uint8_t(s[3]);
+            } else {
+#pragma unroll
+                for (int c = 0; c < C; ++c) bytes[i * C + c] = uint8_t(s[c]);
+            }
+        }
+        const uint32_t npx = sw - kb < 4 ? sw - kb : 4;
+        if (npx < 4 || kb < klo) {  // the rectangle's left / right edge: only the pixels inside it
+            for (uint32_t i = kb < klo ? klo - kb : 0u; i < npx; ++i)
+                for (uint32_t c = 0; c < uint32_t(C); ++c) px[tiles[tt].base + (long long)(kb + i) * C + c] = bytes[i * C + c];
+            continue;
+        }
+        uint32_t w[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+            w[c] = uint32_t(bytes[4 * c]) | (uint32_t(bytes[4 * c + 1]) << 8) | (uint32_t(bytes[4 * c + 2]) << 16) |
+                   (uint32_t(bytes[4 * c + 3]) << 24);
+        __builtin_memcpy(px + tiles[tt].base + size_t(kb) * C, w, 4 * C);  // four pixels inside the rectangle: unaligned dword stores
+    }
+}
+
 }  // namespace
 
 #define LLMI_DISPATCH_C(c, CALL) \
@@ -1014,6 +1231,42 @@ hipError_t launch_pack_payload(const Geometry& g, const uint8_t* d_units, const 
                                uint32_t* d_status, hipStream_t stream) {
     k_pack_payload<<<dim3(lane_groups(g)), dim3(256), 0, stream>>>(g, reinterpret_cast<const uint4*>(d_units), d_slice_len,
                                                                    d_offsets, d_payload, payload_cap, d_status);
+    return hipGetLastError();
+}
+
+hipError_t launch_region_index(const Geometry& full, const Geometry& sub, const RegionBox& box, const uint32_t* d_slice_len,
+                               const uint64_t* d_group_off, uint32_t* d_sub_len, uint64_t* d_sub_off, hipStream_t stream) {
+    if (sub.n_slices == 0) return hipErrorInvalidValue;
+    k_region_index<<<dim3((sub.n_slices + 255) / 256), dim3(256), 0, stream>>>(full, sub, box, d_slice_len, d_group_off, d_sub_len, d_sub_off);
+    return hipGetLastError();
+}
+
+hipError_t launch_stage_region_streams(const Geometry& sub, const uint8_t* d_payload, uint64_t payload_bytes, const uint32_t* d_sub_len,
+                                       const uint64_t* d_sub_off, uint8_t* d_units, uint32_t* d_status, hipStream_t stream) {
+    k_stage_region_streams<<<dim3(lane_groups(sub)), dim3(256), 0, stream>>>(sub, d_payload, payload_bytes, d_sub_len, d_sub_off,
+                                                                             reinterpret_cast<uint4*>(d_units), d_status);
+    return hipGetLastError();
+}
+
+hipError_t launch_model_inv_crop(const Geometry& sub, const int16_t* d_rec, uint8_t* d_px, const Crop& cr, hipStream_t stream) {
+    const size_t npix = size_t(sub.frames) * cr.rh * cr.rw;
+    if (npix == 0 || uint64_t(cr.x0) + cr.rw > sub.w || uint64_t(cr.y0) + cr.rh > sub.h) return hipErrorInvalidValue;
+    const uint32_t blocks = uint32_t(std::min<size_t>((npix + 255) / 256, 256 * 16));
+    switch (sub.c) {
+        case 1: k_model_inv_crop<1><<<dim3(blocks), dim3(256), 0, stream>>>(sub, d_rec, d_px, cr, npix); break;
+        case 2: k_model_inv_crop<2><<<dim3(blocks), dim3(256), 0, stream>>>(sub, d_rec, d_px, cr, npix); break;
+        case 3: k_model_inv_crop<3><<<dim3(blocks), dim3(256), 0, stream>>>(sub, d_rec, d_px, cr, npix); break;
+        case 4: k_model_inv_crop<4><<<dim3(blocks), dim3(256), 0, stream>>>(sub, d_rec, d_px, cr, npix); break;
+        default: k_model_inv_crop<0><<<dim3(blocks), dim3(256), 0, stream>>>(sub, d_rec, d_px, cr, npix); break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_model_rows_inv_crop(const Geometry& sub, const int16_t* d_lanes, uint8_t* d_px, const Crop& cr, hipStream_t stream) {
+    if (!cr.rw || !cr.rh || uint64_t(cr.x0) + cr.rw > sub.w || uint64_t(cr.y0) + cr.rh > sub.h) return hipErrorInvalidValue;
+    const uint64_t blocks = xcd_chunk_grid(lane_groups(sub), (sub.tile_w + 63) / 64);
+    if (blocks == 0 || blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    LLMI_DISPATCH_C(sub.c, (k_model_rows_inv_crop<C><<<dim3(uint32_t(blocks)), dim3(256), 0, stream>>>(sub, d_lanes, d_px, cr)));
     return hipGetLastError();
 }
 
