@@ -48,7 +48,10 @@ typedef enum llcomp_mi_status {
     LLCOMP_MI_OK = 0,
     LLCOMP_MI_BAD_MAGIC = 1,       /* reference throws "Invalid magic number"  (llcomp.hpp:465-467) */
     LLCOMP_MI_BAD_EXPONENT = 2,    /* reference throws "Invalid exponent"      (llcomp.hpp:232-234) */
-    LLCOMP_MI_TRUNCATED = 3,       /* header or slice table longer than the data (reference: UB, D5) */
+    LLCOMP_MI_TRUNCATED = 3,       /* header or slice table longer than the data (reference: UB, D5), or a SLICED table entry longer
+                                      than no encoder writes: 13 * n + 16 bytes rounded up to a multiple of 16, n = samples of a full
+                                      tile (tile_w * tile_h * (planar ? 1 : c)).  A LEGACY stream has no such limit: bytes beyond the
+                                      65 * w * h * c + 2 a decoder can read are ignored, as the reference ignores them. */
     LLCOMP_MI_BAD_ARGS = 4,        /* null pointers, zero sizes, unsupported channel count, bad opts */
     LLCOMP_MI_OUT_OF_RANGE = 5,    /* legacy format with w or h > 65535, or w*h*c >= 2^31 (reference: silent truncation, D4) */
     LLCOMP_MI_OUTPUT_OVERFLOW = 6, /* caller-provided output capacity too small (reference: heap overflow, D1) */

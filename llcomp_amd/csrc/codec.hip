@@ -347,6 +347,13 @@ int llcomp_mi_codec_create(llcomp_mi_codec** out, int32_t device, uint32_t frame
 
 int llcomp_mi_codec_create_ex(llcomp_mi_codec** out, int32_t device, uint32_t frames, uint32_t w, uint32_t h, uint32_t c,
                               uint32_t tile_w, uint32_t tile_h, uint32_t planar, uint32_t flags) {
+    return llcomp_mi::codec_create(out, device, frames, w, h, c, tile_w, tile_h, planar, flags, 0);
+}
+
+}  // extern "C"
+
+int llcomp_mi::codec_create(llcomp_mi_codec** out, int32_t device, uint32_t frames, uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w,
+                            uint32_t tile_h, uint32_t planar, uint32_t flags, uint64_t legacy_stream) {
     if (!out || (flags & ~LLCOMP_MI_FLAG_SMALL_MODEL)) return LLCOMP_MI_BAD_ARGS;
     *out = nullptr;
     if (!frames) return LLCOMP_MI_BAD_ARGS;
@@ -355,6 +362,7 @@ int llcomp_mi_codec_create_ex(llcomp_mi_codec** out, int32_t device, uint32_t fr
     // kernel family and lane-group width are fixed here, for the life of the codec object
     if (!make_geometry(g, frames, w, h, c, tile_w, tile_h, planar, current_tuning(), (flags & LLCOMP_MI_FLAG_SMALL_MODEL) != 0))
         return LLCOMP_MI_OUT_OF_RANGE;
+    if (legacy_stream) fit_legacy_stream(g, legacy_stream);
     int dev = 0;
     if (int rc = resolve_device(device, &dev)) return rc;
     DeviceGuard guard(dev);
@@ -400,6 +408,8 @@ int llcomp_mi_codec_create_ex(llcomp_mi_codec** out, int32_t device, uint32_t fr
     *out = k;
     return LLCOMP_MI_OK;
 }
+
+extern "C" {
 
 void llcomp_mi_codec_destroy(llcomp_mi_codec* k) {
     // No device-wide wait: the blocks go back to the library's cache (devmem.hip) together with the event recorded behind

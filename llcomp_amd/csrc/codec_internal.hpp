@@ -128,8 +128,9 @@ struct HostLane {
     size_t meta_bytes() const { return 16 + 8 * size_t(frames); }
 };
 // builds a lane for this shape on `dev` (geometry + tuning hooks are fixed here); payload capacity `cap` bytes
+// legacy_stream: bytes of the LEGACY stream the lane's decoder has to stage (fit_legacy_stream; 0 = the proven encoder bound)
 int lane_create(HostLane** out, int dev, uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar,
-                bool legacy, uint64_t payload_cap, bool small_model = false, uint32_t frames = 1);
+                bool legacy, uint64_t payload_cap, bool small_model = false, uint32_t frames = 1, uint64_t legacy_stream = 0);
 int lane_grow(HostLane* l, uint64_t payload_cap);  // reallocates the container buffer (contents lost)
 void lane_destroy(HostLane* l);
 // enqueue on the lane's stream (asynchronous): frame in d_px -> container in d_container, {bytes, status} -> h_meta
@@ -139,7 +140,7 @@ int lane_enqueue_decode(HostLane* l, uint64_t payload_bytes);
 
 // hostapi.hip: a lane for this shape on `device` (-1 = current) from the cache of idle lanes, or a new one; lane_release parks it again
 int lane_acquire(HostLane** out, int32_t device, uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar,
-                 bool legacy, uint64_t min_cap, bool small_model);
+                 bool legacy, uint64_t min_cap, bool small_model, uint64_t legacy_stream = 0);
 void lane_release(HostLane* l);
 
 // multidev.hip: one image over a device list, in this process (llcomp_mi_opts.devices / llcomp_mi_decode_devices)
@@ -158,7 +159,10 @@ int decode_multi(const uint8_t* data, size_t len, const llcomp_mi_info& info, co
 void clear_device_error();
 int device_failed(int32_t device, uint32_t index, int status);  // records it and returns LLCOMP_MI_DEVICE_FAILED
 
-void codec_release(llcomp_mi_codec* k);  // codec.hip: destroy without the device-wide wait (its work is known to be done)
+void codec_release(llcomp_mi_codec* k);
+// codec.hip: llcomp_mi_codec_create_ex whose slices can stage a LEGACY stream of `legacy_stream` bytes (fit_legacy_stream)
+int codec_create(llcomp_mi_codec** out, int32_t device, uint32_t frames, uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h,
+                 uint32_t planar, uint32_t flags, uint64_t legacy_stream);  // codec.hip: destroy without the device-wide wait (its work is known to be done)
 
 // devmem.hip: every device buffer of the library comes from here.  dev_alloc is hipMalloc on the current device through a
 // cache of parked blocks; dev_free parks a block -- either the caller has made sure nothing in flight still uses it (the

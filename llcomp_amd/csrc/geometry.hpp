@@ -180,6 +180,19 @@ inline bool make_geometry(Geometry& g, uint32_t frames, uint32_t w, uint32_t h, 
     return true;
 }
 
+// A LEGACY stream has no length on the wire: it is whatever follows the header.  No decoder reads more than 2 bytes + 65 a sample of
+// it (the range decoder takes at most one byte per bin; a sample is at most the zero flag, 31 ones and the closing zero, 31 mantissa
+// bits and the sign, and a run of 32 ones ends the stream), so bytes beyond that bound are never read and the length is clamped to it.
+// (64-bit: the bound passes 2^32 beyond 66 M samples.)
+inline uint64_t legacy_read_bound(uint64_t samples) { return 65 * samples + 2; }
+// A geometry whose one slice can stage a LEGACY stream of `bytes` (already clamped to legacy_read_bound): the decoder's TRUNCATED
+// limit, slice_cap - 16, must not cut a stream the reference reads whole.  Beyond the kernels' 32-bit stream positions it stays
+// capped (a > 2 GB stream is TRUNCATED).
+inline void fit_legacy_stream(Geometry& g, uint64_t bytes) {
+    const uint64_t cap = (bytes + 16 + 15) & ~15ull;
+    if (cap > g.slice_cap) g.slice_cap = uint32_t(cap < 0x7FFFFFF0ull ? cap : 0x7FFFFFF0ull);
+}
+
 // ---- region decode (DESIGN.md "Region decode") ----------------------------------------------------------------------------
 // A rectangle (x, y, rw, rh) of one frame is rebuilt from the slices of the tiles it touches alone: every slice is the reference
 // stream of its own crop, with fresh state and slice-local borders.  Tile columns [tx0, tx1) x tile rows [ty0, ty1) are covered.
@@ -205,10 +218,15 @@ inline bool region_box(uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h,
 // frame-major, then tile row, tile column, plane; region_full_id).  When only the partial last tile column / row is covered,
 // make_geometry clamps tile_w / tile_h to the sub-image and the kernel family may change (a 1-row remainder of 2-row tiles runs the
 // row kernels): the bytes cannot, each slice being the reference stream of its crop.
+// The sub-geometry keeps the full one's bytes per slice: the same TRUNCATED limit as a full decode (the nominal tile's, also for a
+// partial tile alone), and a LEGACY stream longer than 13 B/sample (fit_legacy_stream) stages whole.
 inline bool region_geometry(const Geometry& full, const RegionBox& b, const Tuning& tune, Geometry& sub) {
     const uint32_t w = std::min<uint64_t>(uint64_t(b.tx1) * full.tile_w, full.w) - b.tx0 * full.tile_w;
     const uint32_t h = std::min<uint64_t>(uint64_t(b.ty1) * full.tile_h, full.h) - b.ty0 * full.tile_h;
-    return make_geometry(sub, full.frames, w, h, full.c, full.tile_w, full.tile_h, full.planar, tune, (full.flags & kGeoSmallModel) != 0);
+    if (!make_geometry(sub, full.frames, w, h, full.c, full.tile_w, full.tile_h, full.planar, tune, (full.flags & kGeoSmallModel) != 0))
+        return false;
+    sub.slice_cap = full.slice_cap;
+    return true;
 }
 LLMI_HD inline uint32_t region_full_id(const Geometry& full, const Geometry& sub, const RegionBox& b, uint32_t j) {
     const uint32_t f = j / sub.slices_per_frame, s = j - f * sub.slices_per_frame;

@@ -67,13 +67,14 @@ int lane_grow(HostLane* l, uint64_t payload_cap) {
 }
 
 int lane_create(HostLane** out, int dev, uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar,
-                bool legacy, uint64_t payload_cap, bool small_model, uint32_t frames) {
+                bool legacy, uint64_t payload_cap, bool small_model, uint32_t frames, uint64_t legacy_stream) {
     *out = nullptr;
     HostLane* l = new (std::nothrow) HostLane;
     if (!l) return LLCOMP_MI_NOMEM;
     l->legacy = legacy;
     l->frames = frames;
-    if (int rc = llcomp_mi_codec_create_ex(&l->k, dev, frames, w, h, c, tile_w, tile_h, planar, small_model ? LLCOMP_MI_FLAG_SMALL_MODEL : 0)) {
+    if (int rc = codec_create(&l->k, dev, frames, w, h, c, tile_w, tile_h, planar, small_model ? LLCOMP_MI_FLAG_SMALL_MODEL : 0,
+                              legacy ? legacy_stream : 0)) {
         delete l;
         return rc;
     }
@@ -183,10 +184,11 @@ LaneCache& lane_cache() {
 
 namespace llcomp_mi {
 int lane_acquire(HostLane** out, int32_t device, uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar,
-                 bool legacy, uint64_t min_cap, bool small_model) {
+                 bool legacy, uint64_t min_cap, bool small_model, uint64_t legacy_stream) {
     Geometry g;
     std::memset(&g, 0, sizeof(g));
     if (!make_geometry(g, 1, w, h, c, tile_w, tile_h, planar, current_tuning(), small_model)) return LLCOMP_MI_OUT_OF_RANGE;
+    if (legacy && legacy_stream) fit_legacy_stream(g, legacy_stream);  // (part of the key: such a lane serves streams up to its size)
     int dev = 0;
     if (int rc = resolve_device(device, &dev)) return rc;
     if ((*out = lane_cache().take(dev, g, legacy))) {
@@ -197,7 +199,7 @@ int lane_acquire(HostLane** out, int32_t device, uint32_t w, uint32_t h, uint32_
         }
         return LLCOMP_MI_OK;
     }
-    return lane_create(out, dev, w, h, c, tile_w, tile_h, planar, legacy, min_cap, small_model);
+    return lane_create(out, dev, w, h, c, tile_w, tile_h, planar, legacy, min_cap, small_model, 1, legacy_stream);
 }
 void lane_release(HostLane* l) {
     if (l) lane_cache().give(l);
@@ -303,9 +305,11 @@ int decode_common(const uint8_t* data, size_t len, int32_t device, uint32_t flag
     *h = info.height;
     *c = info.channels;
     if (px && raw > px_cap) return LLCOMP_MI_OUTPUT_OVERFLOW;  // dimensions are reported: the caller can size its buffer
+    if (legacy) len = size_t(std::min<uint64_t>(len, info.payload_offset + legacy_read_bound(raw)));  // the rest is never read
     LaneLease lease;
     if (int rc = lane_acquire(&lease.l, device, info.width, info.height, info.channels, info.tile_w, info.tile_h, info.planar, legacy,
-                              len - info.payload_offset + 16, legacy ? (flags & LLCOMP_MI_FLAG_SMALL_MODEL) != 0 : info.small_model != 0))
+                              len - info.payload_offset + 16, legacy ? (flags & LLCOMP_MI_FLAG_SMALL_MODEL) != 0 : info.small_model != 0,
+                              legacy ? len - info.payload_offset : 0))
         return rc;
     HostLane* l = lease.l;
     DeviceGuard guard(l->k->device);
@@ -344,9 +348,11 @@ int decode_region_common(const uint8_t* data, size_t len, int32_t device, uint32
     *c = info.channels;
     const uint64_t out = uint64_t(rw) * rh * info.channels;
     if (px && out > px_cap) return LLCOMP_MI_OUTPUT_OVERFLOW;  // the channel count is reported: the caller can size its buffer
+    if (legacy) len = size_t(std::min<uint64_t>(len, info.payload_offset + legacy_read_bound(uint64_t(info.width) * info.height * info.channels)));
     LaneLease lease;
     if (int rc = lane_acquire(&lease.l, device, info.width, info.height, info.channels, info.tile_w, info.tile_h, info.planar, legacy,
-                              len - info.payload_offset + 16, legacy ? (flags & LLCOMP_MI_FLAG_SMALL_MODEL) != 0 : info.small_model != 0))
+                              len - info.payload_offset + 16, legacy ? (flags & LLCOMP_MI_FLAG_SMALL_MODEL) != 0 : info.small_model != 0,
+                              legacy ? len - info.payload_offset : 0))
         return rc;
     HostLane* l = lease.l;
     DeviceGuard guard(l->k->device);

@@ -1238,6 +1238,7 @@ __global__ __launch_bounds__(64) void k_decode_slices(const Geometry g, const ui
                     }
                 }
             }
+            publish_count(counters, kCtrDecReplays, d.replays);
         } else {
         const ptrdiff_t up = ptrdiff_t(r.sw) * NCH * GW;  // one slice row back, in lane-order elements
         uint32_t held_ctx = ~0u;   // context of the previous sample; its updated bank is still in registers

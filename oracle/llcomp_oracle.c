@@ -300,6 +300,63 @@ long orc_encode_rect(const int16_t* base, long rs, int ps, int nch, int tw, int 
     return (long)sk.n;
 }
 
+/* Test streams with chosen residuals: the coded value of every sample comes from the caller, contexts and
+ * predictions from the samples as the decoder rebuilds them (orc_decode_rect: int16(pred + v), v modulo 2^32).
+ * mag[i] < 2^32 and neg[i] give sample i's coded residual (coding order, as orc_model_rect); a zero magnitude
+ * codes the zero flag.  run_len >= 32 at sample run_at instead codes the zero flag's 0 and run_len ones on
+ * the unary slots (the reference throws "Invalid exponent", hpp:232-234) and ends the stream there.  Writes
+ * the decoder's view of every sample before the end into the rect. */
+long orc_encode_residuals(const uint32_t* mag, const uint8_t* neg, long run_at, int run_len, int16_t* base, long rs,
+                          int ps, int nch, int tw, int th, uint8_t** out) {
+    tables_init();
+    sink_t sk = {0, 0, 0, 0};
+    renc_t e;
+    renc_init(&e, &sk);
+    uint8_t* table = (uint8_t*)calloc(ORC_N_CTX, 8);
+    if (!table) return -1;
+    long i = 0;
+    for (int y = 0; y < th; ++y)
+        for (int x = 0; x < tw; ++x)
+            for (int k = 0; k < nch; ++k, ++i) {
+                if (i == run_at && run_len >= 32) goto done;
+                hood_t n = hood(base, rs, ps, tw, x, y, k);
+                int ctx = context_of(&n), flip = 0;
+                if (ctx < 0) { ctx = -ctx; flip = 1; }
+                uint8_t* bank = table + (size_t)ctx * 8;
+                const uint32_t a = mag[i];
+                uint32_t v = 0;
+                if (a == 0) {
+                    code_bin(&e, bank, 0, 1);
+                } else {
+                    const int ex = 31 - __builtin_clz(a);
+                    code_bin(&e, bank, 0, 0);
+                    for (int j = 0; j < ex; ++j) code_bin(&e, bank, 1 + j < 4 ? 1 + j : 4, 1);
+                    code_bin(&e, bank, 1 + ex < 4 ? 1 + ex : 4, 0);
+                    for (int b = ex - 1, j = 0; b >= 0; --b, ++j) code_bin(&e, bank, 5 + j < 6 ? 5 + j : 6, (a >> b) & 1);
+                    code_bin(&e, bank, 7, neg[i] != 0);
+                    v = neg[i] ? 0u - a : a;
+                }
+                if (flip) v = 0u - v;
+                base[(long)y * rs + (long)x * ps + k] = (int16_t)(uint32_t)((uint32_t)orc_median(n.l, n.l + n.t - n.tl, n.t) + v);
+            }
+    if (run_len >= 32) { free(table); free(sk.p); return -1; } /* run_at beyond the rect */
+done:
+    if (run_len >= 32) {
+        int y = (int)(run_at / ((long)tw * nch)), x = (int)(run_at / nch % tw), k = (int)(run_at % nch);
+        hood_t n = hood(base, rs, ps, tw, x, y, k);
+        int ctx = context_of(&n);
+        uint8_t* bank = table + (size_t)(ctx < 0 ? -ctx : ctx) * 8;
+        code_bin(&e, bank, 0, 0);
+        for (int j = 0; j < run_len; ++j) code_bin(&e, bank, 1 + j < 4 ? 1 + j : 4, 1);
+    }
+    renc_finish(&e);
+    free(table);
+    if (sk.oom) { free(sk.p); return -1; }
+    if (!sk.p) sk.p = (uint8_t*)malloc(1);
+    *out = sk.p;
+    return (long)sk.n;
+}
+
 int orc_decode_rect(const uint8_t* data, size_t len, int16_t* base, long rs, int ps, int nch, int tw,
                     int th) {
     tables_init();

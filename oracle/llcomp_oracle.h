@@ -52,6 +52,11 @@ void orc_model_rect(const int16_t* base, long row_stride, int pix_stride, int nc
  * (llcomp.hpp:390-449).  *out is malloc'd; returns length or -1. */
 long orc_encode_rect(const int16_t* base, long row_stride, int pix_stride, int nch, int tw, int th,
                      uint8_t** out);
+/* Stream of chosen coded residuals (magnitude < 2^32 + sign per sample, coding order), or a unary run of run_len >= 32
+ * ones at sample run_at that ends the stream (the reference's "Invalid exponent").  Contexts and predictions come from
+ * the samples as orc_decode_rect rebuilds them, which are written into the rect.  Returns the length or -1. */
+long orc_encode_residuals(const uint32_t* mag, const uint8_t* neg, long run_at, int run_len, int16_t* base, long row_stride,
+                          int pix_stride, int nch, int tw, int th, uint8_t** out);
 /* Inverse (llcomp.hpp:486-530): writes reconstructed int16 samples into the rect. */
 int orc_decode_rect(const uint8_t* data, size_t len, int16_t* base, long row_stride, int pix_stride,
                     int nch, int tw, int th);

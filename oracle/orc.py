@@ -55,6 +55,8 @@ class Orc:
         L.orc_decompress.argtypes = [_u8p, C.c_size_t, C.POINTER(_u8p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.orc_encode_rect.restype = C.c_long
         L.orc_encode_rect.argtypes = [_i16p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_u8p)]
+        L.orc_encode_residuals.restype = C.c_long
+        L.orc_encode_residuals.argtypes = [C.POINTER(C.c_uint32), _u8p, C.c_long, C.c_int, _i16p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_u8p)]
         L.orc_decode_rect.restype = C.c_int
         L.orc_decode_rect.argtypes = [_u8p, C.c_size_t, _i16p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int]
         L.orc_model_rect.restype = None
@@ -153,6 +155,26 @@ class Orc:
         rc = self.lib.orc_decode_rect(_p(buf, _u8p) if len(data) else None, len(data), _p(out, _i16p), w * c, c, c, w, h)
         return rc, out
 
+    def encode_residuals(self, res, run_at=-1, run_len=0):
+        """bare stream with fresh state of chosen coded residuals: `res` (h,w,c) int64 in coding order, |v| < 2^32 (the
+        magnitude and sign of what is coded, after the context's sign fold); run_len >= 32 at flat sample index run_at codes a
+        unary run that long instead and ends the stream.  -> (stream, int16 (h,w,c) samples as the decoder rebuilds them;
+        zeros from run_at on)"""
+        res = np.asarray(res, dtype=np.int64)
+        h, w, c = res.shape
+        a = np.abs(res).reshape(-1)
+        if a.size and a.max() >= 1 << 32:
+            raise ValueError("coded magnitudes are below 2^32")
+        mag = np.ascontiguousarray(a, dtype=np.uint32)
+        neg = np.ascontiguousarray(res.reshape(-1) < 0, dtype=np.uint8)
+        out = np.zeros((h, w, c), dtype=np.int16)
+        ptr = _u8p()
+        n = self.lib.orc_encode_residuals(mag.ctypes.data_as(C.POINTER(C.c_uint32)), _p(neg, _u8p), run_at, run_len, _p(out, _i16p),
+                                          w * c, c, c, w, h, C.byref(ptr))
+        if n < 0:
+            raise ValueError("orc_encode_residuals rejected the arguments")
+        return self._take(ptr, n), out
+
     def model_samples(self, s):
         """(ctx u16, res i16) per sample in coding order for an interleaved int16 (h,w,c) image"""
         s = np.ascontiguousarray(s, dtype=np.int16)
@@ -164,6 +186,60 @@ class Orc:
 
     def slice_count(self, w, h, c, tile_w, tile_h, planar):
         return self.lib.orc_slice_count(w, h, c, tile_w, tile_h, int(planar))
+
+
+def adversarial_residuals(rng, h, w, c, kind, max_ex=31):
+    """coded residuals (int64 (h,w,c), coding order) for decoder tests beyond what 8-bit images produce:
+      "sparse": mostly |v| <= 3, 2-10 % of the samples at exponents 10..max_ex
+      "wrap":   a third of the samples at |v| in [2^15, 2^17): rebuilt samples wrap int16 and land anywhere in it
+      "ex31":   small residuals, sample 0 at exponent max_ex (31: a magnitude in [2^31, 2^32))
+      "small":  |v| <= 3 only"""
+    n = h * w * c
+    v = rng.integers(-3, 4, size=n).astype(np.int64)
+    if kind == "sparse":
+        big = rng.random(n) < rng.uniform(0.02, 0.10)
+        ex = rng.integers(10, max_ex + 1, size=n)
+        mag = (np.int64(1) << ex) + (rng.integers(0, 1 << 62, size=n) & ((np.int64(1) << ex) - 1))
+        v = np.where(big, np.where(rng.random(n) < 0.5, -mag, mag), v)
+    elif kind == "wrap":
+        big = rng.random(n) < 0.33
+        mag = rng.integers(1 << 15, 1 << 17, size=n)
+        v = np.where(big, np.where(rng.random(n) < 0.5, -mag, mag), v)
+    elif kind == "ex31":
+        v[0] = (1 << max_ex) + int(rng.integers(0, 1 << max_ex))
+        if rng.random() < 0.5:
+            v[0] = -v[0]
+    elif kind != "small":
+        raise ValueError(kind)
+    return v.reshape(h, w, c)
+
+
+def slice_rects(w, h, c, tile_w, tile_h, planar):
+    """(x0, y0, tw, th, plane or None) of every slice of a sliced container, in the order of orc_compress_sliced"""
+    tile_w = w if tile_w <= 0 or tile_w > w else tile_w
+    tile_h = h if tile_h <= 0 or tile_h > h else tile_h
+    out = []
+    for y0 in range(0, h, tile_h):
+        for x0 in range(0, w, tile_w):
+            tw, th = min(tile_w, w - x0), min(tile_h, h - y0)
+            out += [(x0, y0, tw, th, k) for k in range(c)] if planar else [(x0, y0, tw, th, None)]
+    return out
+
+
+def sliced_container(w, h, c, tile_w, tile_h, planar, payloads, small_model=False, lens=None):
+    """a sliced container (DESIGN.md "Container") around chosen per-slice payloads; `lens` overrides the table entries"""
+    import struct
+
+    tile_w = w if tile_w <= 0 or tile_w > w else tile_w
+    tile_h = h if tile_h <= 0 or tile_h > h else tile_h
+    lens = [len(p) for p in payloads] if lens is None else list(lens)
+    head = bytes([0x9C, 1, c, (1 if planar else 0) | (2 if small_model else 0)]) + struct.pack("<5I", w, h, tile_w, tile_h, len(lens))
+    return head + struct.pack("<%dI" % len(lens), *lens) + b"".join(payloads)
+
+
+def legacy_stream(w, h, c, payload):
+    """a LEGACY stream (llcomp.hpp:375-378) around a bare payload"""
+    return bytes([0x79, c, w & 0xFF, w >> 8, h & 0xFF, h >> 8]) + payload
 
 
 class Ref:
