@@ -26,7 +26,8 @@ extern "C" {
 
 /* ABI 4 (round 6: device lists -- llcomp_mi_opts.devices, llcomp_mi_decode_devices, llcomp_mi_stream_create_multi,
  * llcomp_mi_plan_chunks, llcomp_mi_codec_get_counters; later, functions only: region decode -- llcomp_mi_region_plan,
- * llcomp_mi_decode_region(_into), llcomp_mi_codec_decode_region, llcomp_mi_codec_region_family, LLCOMP_MI_PREPARE_REGION).  The library and its callers are built from ONE header: structs have one layout per ABI version (llcomp_mi_opts is
+ * llcomp_mi_decode_region(_into), llcomp_mi_codec_decode_region, llcomp_mi_codec_region_family, LLCOMP_MI_PREPARE_REGION; a rectangle
+ * per frame -- llcomp_mi_regions_plan, llcomp_mi_codec_decode_regions, llcomp_mi_codec_regions_family, LLCOMP_MI_PREPARE_REGIONS).  The library and its callers are built from ONE header: structs have one layout per ABI version (llcomp_mi_opts is
  * checked through struct_size and refused when it differs; llcomp_mi_info and llcomp_mi_stream_result are written in full),
  * so a binding compares llcomp_mi_abi_version() with the LLCOMP_MI_ABI_VERSION it was generated from and refuses to run on
  * a mismatch -- there is no cross-version compatibility mode. */
@@ -179,6 +180,17 @@ int llcomp_mi_probe(const uint8_t* data, size_t len, llcomp_mi_info* info);
  * Host-only: no GPU involved.  Every region call plans with this. */
 int llcomp_mi_region_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar, uint32_t x, uint32_t y,
                           uint32_t rw, uint32_t rh, uint32_t box[4], uint32_t* slices_per_frame);
+/* A rectangle of one size (rw, rh) at an offset of its own in each of n frames: xy = {x_0, y_0, x_1, y_1, ...} (2 * n).  To decode
+ * every frame on ONE sub-geometry, frame f decodes a WINDOW of tiles of a fixed size that contains its covered box:
+ *   Wx = min(ntx, (rw + tile_w - 2) / tile_w + 1)  -- the most tile columns a rectangle of width rw can touch --
+ *   wx0_f = min(x_f / tile_w, ntx - Wx), and the same in y (tile_w / tile_h 0 = the whole width / height, as in llcomp_mi_region_plan).
+ * windows (4 * n, NULL ok) = {wx0, wy0, wx1, wy1} per frame (tile columns [wx0, wx1), tile rows [wy0, wy1)).  A window that holds the
+ * partial last tile column (row) is narrower (lower) in pixels, so the frames fall into at most 2 x 2 classes -- "the window ends at a
+ * partial last tile column: yes / no" x the same for rows; the x split exists only when w % tile_w != 0, the y split only when
+ * h % tile_h != 0 -- and *n_classes = the number of classes that have frames.  A decode runs one launch chain per class.  BAD_ARGS for
+ * n = 0, a NULL xy or n_classes, or any rectangle outside the image.  Host-only; every regions call plans with this rule. */
+int llcomp_mi_regions_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar, uint32_t rw, uint32_t rh,
+                           const uint32_t* xy, uint32_t n, uint32_t* windows, uint32_t* n_classes);
 uint32_t llcomp_mi_slice_count(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar);
 /* Slice width for one-row slices (tile_h = 1) when `frames` frames are coded per call: the widest slice (64..480 pixels) that
  * still keeps about four wavefronts per SIMD busy.  A call that codes few frames is latency-bound with wide slices; this
@@ -238,6 +250,7 @@ uint64_t llcomp_mi_codec_workspace_bytes(const llcomp_mi_codec* codec);
 #define LLCOMP_MI_PREPARE_ENCODE 1u
 #define LLCOMP_MI_PREPARE_DECODE 2u
 #define LLCOMP_MI_PREPARE_REGION 8u /* the region decode's two arrays (12 B per slice), and state tables if a region may need them (bit 2 stays unused) */
+#define LLCOMP_MI_PREPARE_REGIONS 16u /* ... and the per-frame table of a regions decode (32 B per frame in HBM, a pinned staging ring) */
 int llcomp_mi_codec_prepare(llcomp_mi_codec* codec, uint32_t what);
 /* Upper bound on the packed payload bytes the codec can emit for any input (13 B per sample + slack). */
 uint64_t llcomp_mi_codec_max_payload_bytes(const llcomp_mi_codec* codec);
@@ -261,6 +274,23 @@ int llcomp_mi_codec_decode_region(llcomp_mi_codec* codec, const void* d_payload,
 /* Diagnostic: the kernel family (encoding of llcomp_mi_codec_kernel_family) a region decode of this rectangle runs -- the sub-image's
  * geometry may select another one than the codec's (a 1-row remainder of 2-row tiles runs the row kernels).  0 for a bad rectangle. */
 uint32_t llcomp_mi_codec_region_family(const llcomp_mi_codec* codec, uint32_t x, uint32_t y, uint32_t rw, uint32_t rh);
+/* Regions decode of a batch: frame f's rectangle (xy[2f], xy[2f + 1], rw, rh) -> d_px[f] of [frames][rh][rw][c], dense, in frame order:
+ * byte for byte full_decode[f, y_f : y_f + rh, x_f : x_f + rw].  xy is HOST memory, 2 * frames values, read during the call and never
+ * after it returns.  d_payload / payload_bytes / d_slice_len are the full batch's, as for llcomp_mi_codec_decode.  Each frame decodes
+ * its window of tiles (llcomp_mi_regions_plan); each class of windows is one sub-geometry and one launch chain, the classes run in
+ * order on `stream`, and the call is asynchronous like a decode.  Verdicts (BAD_EXPONENT, TRUNCATED) come from the slices of the
+ * decoded WINDOWS: damage in a window tile outside the rectangle IS reported (unlike llcomp_mi_codec_decode_region, which reads the
+ * covered box only), damage outside every window is never seen.  Any rectangle outside the image is BAD_ARGS, and nothing is launched
+ * or written.  Profile slots 4-7 and the counters accumulate as for a region decode; each class takes a state generation of its own.
+ * The first call allocates what LLCOMP_MI_PREPARE_REGIONS allocates ahead and can return LLCOMP_MI_NOMEM.  The per-frame table reaches
+ * the GPU from a small pinned ring: a call waits only for the table copy of the call four before it on that codec. */
+int llcomp_mi_codec_decode_regions(llcomp_mi_codec* codec, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                   const uint32_t* xy, uint32_t rw, uint32_t rh, void* d_px, void* d_status, void* stream);
+/* Diagnostic: the kernel family (encoding of llcomp_mi_codec_kernel_family) of every class a regions decode of these rectangles runs,
+ * in class order (bit 0 = partial last tile column, bit 1 = partial last tile row), the first `cap` of them to fam.  Returns the
+ * number of classes; 0 for bad arguments. */
+uint32_t llcomp_mi_codec_regions_family(const llcomp_mi_codec* codec, const uint32_t* xy, uint32_t rw, uint32_t rh, uint32_t* fam,
+                                        uint32_t cap);
 /* Stage-A only (context + prediction model), for tests and profiling: d_sym u32[frames*h*w*c],
  * low 16 bits = folded context (0..7925), high 16 bits = folded residual (two's complement). */
 int llcomp_mi_codec_model(llcomp_mi_codec* codec, const void* d_px, void* d_sym, void* stream);

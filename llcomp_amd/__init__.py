@@ -7,6 +7,7 @@ with ctypes and keeps the reference's names and error behaviour:
     compress_image(rgb, width, height, channels)  <->  llcomp::compressImage    (/root/reference/llcomp.hpp:358)
     decompress_image(data) -> RawImage            <->  llcomp::decompressImage  (/root/reference/llcomp.hpp:461)
     decompress_region(data, x, y, w, h)           <->  llcomp::decompressRegion (include/llcomp_mi.hpp: one rectangle, covered slices only)
+    regions_plan(w, h, c, tw, th, planar, rw, rh, xy) / Codec.decode_regions  (a rectangle per frame of a batch; pack_batch feeds it)
     RawImage(pixels, width, height, channels)     <->  llcomp::RawImage         (/root/reference/llcomp.hpp:454-459)
     EXT = ".llcomp"                               <->  llcomp::ext              (/root/reference/llcomp.hpp:18)
 
@@ -123,6 +124,52 @@ def region_plan(w, h, c, tile_w, tile_h, planar, x, y, rw, rh):
     box, n = (C.c_uint32 * 4)(), C.c_uint32()
     _check(_lib.load().llcomp_mi_region_plan(w, h, c, tile_w, tile_h, int(bool(planar)), x, y, rw, rh, box, C.byref(n)))
     return tuple(box), n.value
+
+
+def _xy_table(xy, n=None):
+    """a sequence of (x, y) pairs or an int / uint32 array of shape [n, 2] -> (ctypes u32 array of 2n values, n); BAD_ARGS otherwise"""
+    a = np.asarray(xy)
+    if a.ndim != 2 or a.shape[1] != 2 or a.shape[0] < 1 or (n is not None and a.shape[0] != n) or not np.issubdtype(a.dtype, np.integer) \
+            or (a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF)):
+        raise LlcompError(BAD_ARGS, f"xy must be {n if n is not None else 'n'} x 2 non-negative integers, got shape {a.shape} {a.dtype}")
+    flat = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1)
+    return (C.c_uint32 * flat.size)(*flat.tolist()), a.shape[0]
+
+
+def regions_plan(w, h, c, tile_w, tile_h, planar, rw, rh, xy):
+    """(windows, n_classes) of a rectangle of size (rw, rh) at every offset of `xy` ([n, 2]) -- llcomp_mi_regions_plan, host only.
+    windows = [n, 4] uint32 array of (wx0, wy0, wx1, wy1) tile windows.  LlcompError(BAD_ARGS) for a rectangle outside the image."""
+    tab, n = _xy_table(xy)
+    win, k = (C.c_uint32 * (4 * n))(), C.c_uint32()
+    _check(_lib.load().llcomp_mi_regions_plan(w, h, c, tile_w, tile_h, int(bool(planar)), rw, rh, tab, n, win, C.byref(k)))
+    return np.array(win, dtype=np.uint32).reshape(n, 4), k.value
+
+
+def pack_batch(containers):
+    """(payload, slice_len) for Codec.decode / decode_region / decode_regions from single-frame SLICED containers of one shape, tiling,
+    planar setting and model: the payloads back to back (np.uint8) and the slice tables back to back (np.uint32), in container order.
+    LlcompError(BAD_ARGS) for an empty list, a LEGACY stream or a container that differs from the first; TRUNCATED for one whose payload
+    is shorter than its table says (bytes after the last slice are dropped)."""
+    if not containers:
+        raise LlcompError(BAD_ARGS, "no containers")
+    pays, lens, key0 = [], [], None
+    for i, d in enumerate(containers):
+        d = bytes(d)
+        info = probe(d)
+        key = (info.format, info.width, info.height, info.channels, info.tile_w, info.tile_h, info.planar, info.small_model, info.n_slices)
+        if info.format != FORMAT_SLICED:
+            raise LlcompError(BAD_ARGS, f"container {i} is not SLICED")
+        if key0 is None:
+            key0 = key
+        elif key != key0:
+            raise LlcompError(BAD_ARGS, f"container {i} differs from container 0 in shape, tiling, planar setting or model")
+        t = np.frombuffer(d, dtype="<u4", count=info.n_slices, offset=info.table_offset).astype(np.uint32)
+        n = int(t.sum(dtype=np.uint64))
+        if len(d) - info.payload_offset < n:
+            raise LlcompError(TRUNCATED, f"container {i} holds fewer payload bytes than its table says")
+        lens.append(t)
+        pays.append(np.frombuffer(d, dtype=np.uint8, count=n, offset=info.payload_offset))
+    return np.concatenate(pays), np.concatenate(lens)
 
 
 def decompress_region(data, x, y, w, h, *, device=-1, small_model=False):
@@ -509,6 +556,24 @@ class Codec:
         return {"rows": bool(fam & 1), "lds_table": bool(fam & 2), "snapshot": bool(fam & 16), "bank_cache": bool(fam & 32),
                 "lane_shift": (fam >> 8) & 0xFF, "slices_per_wave": (fam >> 16) & 0xFF}
 
+    def decode_regions(self, d_payload, payload_bytes, d_slice_len, xy, rw, rh, d_px, d_status, stream=0):
+        """frame f's rectangle (xy[f][0], xy[f][1], rw, rh) -> d_px [frames][rh][rw][c] (llcomp_mi_codec_decode_regions); xy = a
+        sequence of (x, y) pairs or an int / uint32 array of shape [frames, 2], read during the call; d_payload / d_slice_len are the
+        full batch's (pack_batch)"""
+        tab, _ = _xy_table(xy, self.frames)
+        _check(self._L.llcomp_mi_codec_decode_regions(self._h, d_payload, payload_bytes, d_slice_len, tab, rw, rh, d_px, d_status, stream))
+
+    def regions_family(self, xy, rw, rh):
+        """the kernel family of every class a regions decode of these rectangles runs, in class order (the keys of .family); None
+        for bad rectangles"""
+        tab, _ = _xy_table(xy, self.frames)
+        fam = (C.c_uint32 * 4)()
+        n = self._L.llcomp_mi_codec_regions_family(self._h, tab, rw, rh, fam, 4)
+        if not n:
+            return None
+        return [{"rows": bool(f & 1), "lds_table": bool(f & 2), "snapshot": bool(f & 16), "bank_cache": bool(f & 32),
+                 "lane_shift": (f >> 8) & 0xFF, "slices_per_wave": (f >> 16) & 0xFF} for f in list(fam)[:n]]
+
     def model(self, d_px, d_sym, stream=0):
         _check(self._L.llcomp_mi_codec_model(self._h, d_px, d_sym, stream))
 
@@ -524,9 +589,10 @@ class Codec:
         _check(self._L.llcomp_mi_codec_get_profile(self._h, ms, C.byref(ne), C.byref(nd)))
         return dict(zip(self.PROFILE_SLOTS, list(ms))), ne.value, nd.value
 
-    def prepare(self, encode=True, decode=True, region=False):
-        """allocate now what the first encode / decode / region decode would allocate inside the call (llcomp_mi_codec_prepare)"""
-        _check(self._L.llcomp_mi_codec_prepare(self._h, (1 if encode else 0) | (2 if decode else 0) | (8 if region else 0)))
+    def prepare(self, encode=True, decode=True, region=False, regions=False):
+        """allocate now what the first encode / decode / region decode / regions decode would allocate inside the call
+        (llcomp_mi_codec_prepare)"""
+        _check(self._L.llcomp_mi_codec_prepare(self._h, (1 if encode else 0) | (2 if decode else 0) | (8 if region else 0) | (16 if regions else 0)))
 
     COUNTERS = ("dec_cached_waves", "dec_bypassed_waves", "cache_lookups", "cache_misses", "cache_writebacks", "dec_replays", "enc_carry_backs",
                 "generation_wraps", "dec_launches_cached", "dec_launches_plain")

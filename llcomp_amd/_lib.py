@@ -30,7 +30,7 @@ SYMBOLS = [
     "llcomp_mi_decode_devices", "llcomp_mi_decode_into_devices", "llcomp_mi_last_device_error", "llcomp_mi_plan_chunks",
     "llcomp_mi_stream_create_multi", "llcomp_mi_stream_devices", "llcomp_mi_codec_get_counters", "llcomp_mi_codec_prepare",
     "llcomp_mi_region_plan", "llcomp_mi_decode_region", "llcomp_mi_decode_region_into", "llcomp_mi_codec_decode_region",
-    "llcomp_mi_codec_region_family",
+    "llcomp_mi_codec_region_family", "llcomp_mi_regions_plan", "llcomp_mi_codec_decode_regions", "llcomp_mi_codec_regions_family",
 ]
 
 u8p = C.POINTER(C.c_uint8)
@@ -225,6 +225,14 @@ def load():
         L.llcomp_mi_codec_decode_region.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p] * 3
         L.llcomp_mi_codec_region_family.restype = C.c_uint32
         L.llcomp_mi_codec_region_family.argtypes = [C.c_void_p] + [C.c_uint32] * 4
+    if "LLCOMP_MI_LIB" not in os.environ or hasattr(L, "llcomp_mi_regions_plan"):  # a rectangle per frame
+        u32p = C.POINTER(C.c_uint32)
+        L.llcomp_mi_regions_plan.restype = C.c_int
+        L.llcomp_mi_regions_plan.argtypes = [C.c_uint32] * 8 + [u32p, C.c_uint32, u32p, u32p]
+        L.llcomp_mi_codec_decode_regions.restype = C.c_int
+        L.llcomp_mi_codec_decode_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, u32p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 3
+        L.llcomp_mi_codec_regions_family.restype = C.c_uint32
+        L.llcomp_mi_codec_regions_family.argtypes = [C.c_void_p, u32p, C.c_uint32, C.c_uint32, u32p, C.c_uint32]
     if "LLCOMP_MI_LIB" not in os.environ and L.llcomp_mi_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.llcomp_mi_abi_version()}, this binding was written for {ABI_VERSION}: rebuild the library")
     _lib = L

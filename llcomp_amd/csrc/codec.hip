@@ -255,6 +255,78 @@ int region_setup(const llcomp_mi_codec* k, uint32_t x, uint32_t y, uint32_t rw, 
     return LLCOMP_MI_OK;
 }
 
+// regions decode: the per-frame table in HBM and its pinned staging ring with one event per slot
+int ensure_regions_table(llcomp_mi_codec* k) {
+    if (k->d_regions) return LLCOMP_MI_OK;
+    const uint64_t bytes = uint64_t(k->g.frames) * sizeof(RegionsFrame);
+    if (!k->h_regions) {
+        if (hipHostMalloc(reinterpret_cast<void**>(&k->h_regions), bytes * llcomp_mi_codec::kRegionsRing, hipHostMallocDefault) != hipSuccess) {
+            k->h_regions = nullptr;
+            (void)hipGetLastError();
+            return LLCOMP_MI_NOMEM;
+        }
+        for (auto& ev : k->regions_ev)
+            if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
+                ev = nullptr;
+                (void)hipGetLastError();
+                return LLCOMP_MI_HIP_ERROR;
+            }
+    }
+    if (dev_alloc(reinterpret_cast<void**>(&k->d_regions), bytes) != hipSuccess) {
+        k->d_regions = nullptr;
+        return LLCOMP_MI_NOMEM;
+    }
+    k->allocated_bytes += bytes;
+    return LLCOMP_MI_OK;
+}
+
+// One class of a regions decode: its sub-geometry, and its frames = entries [first, first + sub.frames) of the table.
+struct RegionsClass {
+    Geometry sub;
+    uint32_t first;
+};
+// Every frame's window and class (geometry.hpp: regions_window) -> `tab` (g.frames entries, class by class, frame order inside a class)
+// and the classes that have frames, in class order.  BAD_ARGS for a rectangle a frame does not hold; HIP_ERROR if a class's
+// sub-geometry would not fit the codec's workspace (regions_fits: never by default, checked all the same).
+int regions_setup(const llcomp_mi_codec* k, const uint32_t* xy, uint32_t rw, uint32_t rh, RegionsFrame* tab, RegionsClass* classes,
+                  uint32_t& n_classes) {
+    const Geometry& g = k->g;
+    if (!xy) return LLCOMP_MI_BAD_ARGS;
+    RegionBox win[kRegionsClasses];
+    uint32_t count[kRegionsClasses] = {}, cls = 0;
+    for (uint32_t f = 0; f < g.frames; ++f) {
+        RegionBox b;
+        if (!regions_window(g.w, g.h, g.tile_w, g.tile_h, xy[2 * f], xy[2 * f + 1], rw, rh, b, cls)) return LLCOMP_MI_BAD_ARGS;
+        win[cls] = b;  // (the window's size, all the sub-geometry depends on, is the class's)
+        ++count[cls];
+    }
+    uint32_t first[kRegionsClasses], next = 0;
+    n_classes = 0;
+    for (uint32_t c = 0; c < kRegionsClasses; ++c) {
+        first[c] = next;
+        next += count[c];
+        if (!count[c]) continue;
+        RegionsClass& rc = classes[n_classes++];
+        rc.first = first[c];
+        if (!regions_geometry(g, win[c], count[c], k->tune, rc.sub) || !regions_fits(g, rc.sub)) return LLCOMP_MI_HIP_ERROR;
+    }
+    for (uint32_t f = 0; f < g.frames; ++f) {
+        RegionBox b;
+        (void)regions_window(g.w, g.h, g.tile_w, g.tile_h, xy[2 * f], xy[2 * f + 1], rw, rh, b, cls);
+        RegionsFrame& e = tab[first[cls]++];
+        e = RegionsFrame{f, b.tx0, b.ty0, xy[2 * f] - b.tx0 * g.tile_w, xy[2 * f + 1] - b.ty0 * g.tile_h, f, cls, 0};
+    }
+    // (what the crop kernels rely on; the window contains the rectangle by construction)
+    for (uint32_t i = 0; i < n_classes; ++i) {
+        const RegionsClass& rc = classes[i];
+        for (uint32_t j = 0; j < rc.sub.frames; ++j) {
+            const RegionsFrame& e = tab[rc.first + j];
+            if (uint64_t(e.cx0) + rw > rc.sub.w || uint64_t(e.cy0) + rh > rc.sub.h || e.out >= g.frames) return LLCOMP_MI_HIP_ERROR;
+        }
+    }
+    return LLCOMP_MI_OK;
+}
+
 }  // namespace
 
 namespace llcomp_mi {
@@ -279,6 +351,15 @@ void codec_release(llcomp_mi_codec* k) {
     dev_free(k->d_total_tmp, k->done);
     dev_free(k->d_region_len, k->done);
     dev_free(k->d_region_off, k->done);
+    dev_free(k->d_regions, k->done);
+    if (k->h_regions) {
+        // (a table copy may still be queued on a caller's stream: it must not read freed memory)
+        for (uint32_t i = 0; i < llcomp_mi_codec::kRegionsRing; ++i)
+            if (k->regions_ev_live[i] && k->regions_ev[i] && hipEventQuery(k->regions_ev[i]) == hipErrorNotReady) (void)hipEventSynchronize(k->regions_ev[i]);
+        (void)hipGetLastError();
+        (void)hipHostFree(k->h_regions);
+    }
+    for (auto& ev : k->regions_ev) if (ev) (void)hipEventDestroy(ev);
     dev_free(k->d_snap_sorted, k->done);
     dev_free(k->d_snap_banks, k->done);
     dev_free(k->d_snap_res, k->done);
@@ -393,7 +474,9 @@ int llcomp_mi::codec_create(llcomp_mi_codec** out, int32_t device, uint32_t fram
     // own family keeps its states on chip (region_may_need_states)
     const uint64_t b_region = uint64_t(g.n_slices) * 12 +
                               (!k->need_states && !rows_mode(g) ? (uint64_t(lane_groups(g)) * kContexts << g.lane_shift) * 8 : 0);
-    k->workspace_bytes = b_sym + b_lanes + b_states + b_scratch + b_off + 8 + snap_el * (snapshot_chunked(g) ? 28 : 18) + b_region;
+    // ... plus the per-frame table of a regions decode
+    const uint64_t b_regions = uint64_t(frames) * sizeof(RegionsFrame);
+    k->workspace_bytes = b_sym + b_lanes + b_states + b_scratch + b_off + 8 + snap_el * (snapshot_chunked(g) ? 28 : 18) + b_region + b_regions;
     const bool ok = dev_alloc(&k->d_sym_or_rec, b_sym) == hipSuccess && dev_alloc(&k->d_lane_order, b_lanes) == hipSuccess &&
                     dev_alloc(reinterpret_cast<void**>(&k->d_scratch), b_scratch) == hipSuccess &&
                     dev_alloc(reinterpret_cast<void**>(&k->d_group_off), b_off) == hipSuccess &&
@@ -419,7 +502,8 @@ void llcomp_mi_codec_destroy(llcomp_mi_codec* k) {
 }
 
 int llcomp_mi_codec_prepare(llcomp_mi_codec* k, uint32_t what) {
-    if (!k || (what & ~(LLCOMP_MI_PREPARE_ENCODE | LLCOMP_MI_PREPARE_DECODE | LLCOMP_MI_PREPARE_REGION))) return LLCOMP_MI_BAD_ARGS;
+    if (!k || (what & ~(LLCOMP_MI_PREPARE_ENCODE | LLCOMP_MI_PREPARE_DECODE | LLCOMP_MI_PREPARE_REGION | LLCOMP_MI_PREPARE_REGIONS)))
+        return LLCOMP_MI_BAD_ARGS;
     DeviceGuard guard(k->device);
     if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
     if (what & LLCOMP_MI_PREPARE_ENCODE) {
@@ -431,11 +515,13 @@ int llcomp_mi_codec_prepare(llcomp_mi_codec* k, uint32_t what) {
     }
     if (what & LLCOMP_MI_PREPARE_DECODE)
         if (int rc = ensure_state_tables(k, k->need_states)) return rc;
-    if (what & LLCOMP_MI_PREPARE_REGION) {
+    if (what & (LLCOMP_MI_PREPARE_REGION | LLCOMP_MI_PREPARE_REGIONS)) {
         if (int rc = ensure_region_arrays(k)) return rc;
         if (region_may_need_states(k))
             if (int rc = ensure_state_tables(k, true)) return rc;
     }
+    if (what & LLCOMP_MI_PREPARE_REGIONS)
+        if (int rc = ensure_regions_table(k)) return rc;
     return LLCOMP_MI_OK;
 }
 
@@ -652,6 +738,88 @@ int llcomp_mi_codec_decode_region(llcomp_mi_codec* k, const void* d_payload, uin
         } else {
             HIP_TRY(launch_from_lane_order_i16(sub, static_cast<const int16_t*>(k->d_lane_order), static_cast<int16_t*>(k->d_sym_or_rec), s));
             HIP_TRY(launch_model_inv_crop(sub, static_cast<const int16_t*>(k->d_sym_or_rec), static_cast<uint8_t*>(d_px), cr, s));
+        }
+    }
+    ++k->n_decode;
+    return LLCOMP_MI_OK;
+}
+
+uint32_t llcomp_mi_codec_regions_family(const llcomp_mi_codec* k, const uint32_t* xy, uint32_t rw, uint32_t rh, uint32_t* fam, uint32_t cap) {
+    if (!k || (cap && !fam)) return 0;
+    std::vector<RegionsFrame> tab(k->g.frames);
+    RegionsClass classes[kRegionsClasses];
+    uint32_t n = 0;
+    if (regions_setup(k, xy, rw, rh, tab.data(), classes, n)) return 0;
+    for (uint32_t i = 0; i < n && i < cap; ++i) {
+        const Geometry& sub = classes[i].sub;
+        fam[i] = (sub.flags & 0xFFu) | (sub.lane_shift << 8) | (sub.lpw << 16);
+    }
+    return n;
+}
+
+// Regions decode (DESIGN.md "Region decode"): the region decode, class by class (geometry.hpp: regions_window), in order on the
+// caller's stream.  The full geometry's group offsets are found once; the per-frame table crosses to HBM in one copy from a slot of
+// the pinned ring, and every class reads its own entries of it.  Each class takes a state generation of its own.
+int llcomp_mi_codec_decode_regions(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                   const uint32_t* xy, uint32_t rw, uint32_t rh, void* d_px, void* d_status, void* stream) {
+    if (!k || !d_payload || !d_slice_len || !d_px || !d_status || !xy) return LLCOMP_MI_BAD_ARGS;
+    const Geometry& g = k->g;
+    std::vector<RegionsFrame> tab(g.frames);
+    RegionsClass classes[kRegionsClasses];
+    uint32_t n_classes = 0;
+    if (int rc = regions_setup(k, xy, rw, rh, tab.data(), classes, n_classes)) return rc;
+    DeviceGuard guard(k->device);
+    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
+    if (int rc = ensure_region_arrays(k)) return rc;
+    if (int rc = ensure_regions_table(k)) return rc;
+    // the slot's previous copy has to have left it (it was queued four calls ago: this waits only when the caller runs that far ahead)
+    const uint32_t slot = k->regions_slot;
+    if (k->regions_ev_live[slot]) {
+        if (hipEventSynchronize(k->regions_ev[slot]) != hipSuccess) return LLCOMP_MI_HIP_ERROR;
+        k->regions_ev_live[slot] = false;
+    }
+    RegionsFrame* h_tab = k->h_regions + size_t(slot) * g.frames;
+    std::memcpy(h_tab, tab.data(), tab.size() * sizeof(RegionsFrame));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DoneGuard done_guard{k, s};
+    HIP_TRY(hipMemsetAsync(d_status, 0, 4, s));
+    {
+        Timed t(k, s, 4);
+        HIP_TRY(hipMemcpyAsync(k->d_regions, h_tab, tab.size() * sizeof(RegionsFrame), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(k->regions_ev[slot], s));
+        k->regions_ev_live[slot] = true;
+        k->regions_slot = (slot + 1) % llcomp_mi_codec::kRegionsRing;
+        HIP_TRY(launch_group_sums(g, static_cast<const uint32_t*>(d_slice_len), k->d_group_off, s));
+        HIP_TRY(launch_scan_groups(g, k->d_group_off, k->d_total_tmp, s));
+    }
+    for (uint32_t i = 0; i < n_classes; ++i) {
+        const Geometry& sub = classes[i].sub;
+        const RegionsFrame* d_tab = k->d_regions + classes[i].first;
+        {
+            Timed t(k, s, 7);
+            if (int rc = next_state_generation(k, s, slices_need_state_tables(sub))) return rc;
+        }
+        {
+            Timed t(k, s, 4);
+            HIP_TRY(launch_regions_index(g, sub, d_tab, static_cast<const uint32_t*>(d_slice_len), k->d_group_off, k->d_region_len, k->d_region_off, s));
+            HIP_TRY(launch_stage_region_streams(sub, static_cast<const uint8_t*>(d_payload), payload_bytes, k->d_region_len, k->d_region_off,
+                                                k->d_scratch, static_cast<uint32_t*>(d_status), s));
+        }
+        {
+            Timed t(k, s, 5);
+            const bool cache = use_bank_cache(k, sub);
+            HIP_TRY(launch_decode_slices(sub, k->d_scratch, k->d_region_len, k->d_states, k->state_generation, static_cast<int16_t*>(k->d_lane_order),
+                                         static_cast<uint32_t*>(d_status), k->d_counters, cache, s));
+            if (cache) queue_feedback(k, s);
+        }
+        {
+            Timed t(k, s, 6);
+            if (model_is_fused(sub)) {
+                HIP_TRY(launch_model_rows_inv_crops(sub, static_cast<const int16_t*>(k->d_lane_order), static_cast<uint8_t*>(d_px), d_tab, rw, rh, s));
+            } else {
+                HIP_TRY(launch_from_lane_order_i16(sub, static_cast<const int16_t*>(k->d_lane_order), static_cast<int16_t*>(k->d_sym_or_rec), s));
+                HIP_TRY(launch_model_inv_crops(sub, static_cast<const int16_t*>(k->d_sym_or_rec), static_cast<uint8_t*>(d_px), d_tab, rw, rh, s));
+            }
         }
     }
     ++k->n_decode;

@@ -34,6 +34,15 @@ struct llcomp_mi_codec {
     uint32_t* d_region_len = nullptr;
     uint64_t* d_region_off = nullptr;
     llcomp_mi::Tuning tune{};        // the hooks the geometry was made with (a region's sub-geometry is made with the same)
+    // regions decode (llcomp_mi_codec_decode_regions): the per-frame table (RegionsFrame[frames], class by class) in HBM, and the
+    // pinned staging it is copied from -- a ring of kRegionsRing tables, each reused only after the event behind ITS last copy
+    // (the copy of a call sits in the stream behind that call's predecessors: one slot would make every call wait for the last one)
+    static constexpr uint32_t kRegionsRing = 4;
+    llcomp_mi::RegionsFrame* d_regions = nullptr;
+    llcomp_mi::RegionsFrame* h_regions = nullptr;  // pinned, kRegionsRing * frames
+    hipEvent_t regions_ev[kRegionsRing] = {};
+    bool regions_ev_live[kRegionsRing] = {};     // the slot's event has been recorded (a copy from it may be queued)
+    uint32_t regions_slot = 0;                   // the slot the next call uses
     void* d_snap_sorted = nullptr;   // snapshot pass of the 2-D encoder (snapshot.hpp): banks in context-sorted order,
     void* d_snap_banks = nullptr;    // banks in stream order, residuals in stream order; null unless snapshot_mode(g)
     void* d_snap_res = nullptr;

@@ -107,6 +107,32 @@ int llcomp_mi_region_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, u
     return LLCOMP_MI_OK;
 }
 
+int llcomp_mi_regions_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar, uint32_t rw, uint32_t rh,
+                           const uint32_t* xy, uint32_t n, uint32_t* windows, uint32_t* n_classes) {
+    (void)planar;
+    if (!xy || !n || !n_classes || c < 1 || c > kMaxChannels) return LLCOMP_MI_BAD_ARGS;
+    uint32_t seen = 0;
+    for (uint32_t f = 0; f < n; ++f) {  // (every rectangle is checked before anything is written)
+        RegionBox b;
+        uint32_t cls = 0;
+        if (!regions_window(w, h, tile_w, tile_h, xy[2 * f], xy[2 * f + 1], rw, rh, b, cls)) return LLCOMP_MI_BAD_ARGS;
+        seen |= 1u << cls;
+    }
+    for (uint32_t f = 0; f < n && windows; ++f) {
+        RegionBox b;
+        uint32_t cls = 0;
+        (void)regions_window(w, h, tile_w, tile_h, xy[2 * f], xy[2 * f + 1], rw, rh, b, cls);
+        {
+            windows[4 * f + 0] = b.tx0;
+            windows[4 * f + 1] = b.ty0;
+            windows[4 * f + 2] = b.tx1;
+            windows[4 * f + 3] = b.ty1;
+        }
+    }
+    *n_classes = uint32_t(__builtin_popcount(seen));
+    return LLCOMP_MI_OK;
+}
+
 int llcomp_mi_probe(const uint8_t* data, size_t len, llcomp_mi_info* info) {
     if (!data || !info) return LLCOMP_MI_BAD_ARGS;
     std::memset(info, 0, sizeof(*info));

@@ -239,15 +239,69 @@ LLMI_HD inline uint32_t region_full_id(const Geometry& full, const Geometry& sub
 // tables), x samples per slice (lane-order arrays), bytes per slice (scratch).  default_lane_shift is monotone, so this holds by
 // default; forced LLCOMP_MI_LANE_SHIFT / LLCOMP_MI_LPW and the "few big slices: one per wavefront" rule are checked, not assumed.
 // A sub-geometry that needs the image-order intermediate needs it of a codec that has one (`full` not on the fused row path).
-inline bool region_fits(const Geometry& full, const Geometry& sub) {
+// (region_fits: the same frames; regions_fits: a class of them)
+inline bool sub_arrays_fit(const Geometry& full, const Geometry& sub) {
     auto lanes = [](const Geometry& g) { return ((uint64_t(g.n_slices) + (1u << g.lane_shift) - 1) >> g.lane_shift) << g.lane_shift; };
     auto fused = [](const Geometry& g) { return g.planar && (g.flags & kGeoRows) && g.c <= 4; };
-    if (sub.frames != full.frames || sub.c != full.c || sub.n_slices > full.n_slices) return false;
+    if (sub.c != full.c || sub.n_slices > full.n_slices) return false;
     if (lanes(sub) > lanes(full)) return false;
     if (lanes(sub) * sub.slice_samples > lanes(full) * full.slice_samples) return false;
     if (uint64_t(lanes(sub)) * sub.slice_cap > uint64_t(lanes(full)) * full.slice_cap) return false;
     if (!fused(sub) && fused(full)) return false;
     return true;
 }
+inline bool region_fits(const Geometry& full, const Geometry& sub) { return sub.frames == full.frames && sub_arrays_fit(full, sub); }
+
+// ---- regions decode: a rectangle of one size at an offset of its own in every frame (DESIGN.md "Region decode") -----------------
+// To run the decoder on ONE sub-geometry, every frame decodes a WINDOW of tiles of a fixed size instead of its exact covered box:
+// Wx = min(ntx, (rw + tile_w - 2) / tile_w + 1) tile columns, the most a rectangle of width rw can touch, from
+// wx0 = min(x / tile_w, ntx - Wx) (rows alike).  The window always contains region_box's box.  Where the window holds the partial
+// last tile column (row) its pixel width (height) differs, so frames fall into at most 2 x 2 classes: bit 0 = the window ends at
+// a partial last tile column, bit 1 = at a partial last tile row.  Each class is one sub-geometry.
+constexpr uint32_t kRegionsClasses = 4;
+// false for an empty rectangle or one that leaves the image (region_box); tile_w / tile_h 0 (or beyond the image) = the whole width / height
+inline bool regions_window(uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h, uint32_t x, uint32_t y, uint32_t rw, uint32_t rh,
+                           RegionBox& win, uint32_t& cls) {
+    RegionBox b;
+    if (!region_box(w, h, tile_w, tile_h, x, y, rw, rh, b)) return false;
+    if (tile_w == 0 || tile_w > w) tile_w = w;
+    if (tile_h == 0 || tile_h > h) tile_h = h;
+    const uint32_t ntx = uint32_t((uint64_t(w) + tile_w - 1) / tile_w), nty = uint32_t((uint64_t(h) + tile_h - 1) / tile_h);
+    const uint32_t wx = uint32_t(std::min<uint64_t>(ntx, (uint64_t(rw) + tile_w - 2) / tile_w + 1));
+    const uint32_t wy = uint32_t(std::min<uint64_t>(nty, (uint64_t(rh) + tile_h - 2) / tile_h + 1));
+    win.tx0 = std::min(x / tile_w, ntx - wx);
+    win.ty0 = std::min(y / tile_h, nty - wy);
+    win.tx1 = win.tx0 + wx;
+    win.ty1 = win.ty0 + wy;
+    cls = (w % tile_w != 0 && win.tx1 == ntx ? 1u : 0u) | (h % tile_h != 0 && win.ty1 == nty ? 2u : 0u);
+    return true;
+}
+// One class's sub-geometry: region_geometry of its window, with the class's frame count.
+inline bool regions_geometry(const Geometry& full, const RegionBox& win, uint32_t frames, const Tuning& tune, Geometry& sub) {
+    const uint32_t w = std::min<uint64_t>(uint64_t(win.tx1) * full.tile_w, full.w) - win.tx0 * full.tile_w;
+    const uint32_t h = std::min<uint64_t>(uint64_t(win.ty1) * full.tile_h, full.h) - win.ty0 * full.tile_h;
+    if (!make_geometry(sub, frames, w, h, full.c, full.tile_w, full.tile_h, full.planar, tune, (full.flags & kGeoSmallModel) != 0))
+        return false;
+    sub.slice_cap = full.slice_cap;
+    return true;
+}
+// One frame of a class, as the kernels see it (kernels.hpp): the class's frames are entries [first, first + frames) of one table.
+struct RegionsFrame {
+    uint32_t frame;     // the frame of the full batch whose slices are read
+    uint32_t wx0, wy0;  // the window's first tile column / row
+    uint32_t cx0, cy0;  // the rectangle's origin inside the window, in pixels
+    uint32_t out;       // output frame: the rectangle goes to d_px[out]
+    uint32_t cls, pad;
+};
+// sub-slice j of a class -> its slice of the full batch (frame-major, then tile row, tile column, plane, as region_full_id)
+LLMI_HD inline uint32_t regions_full_id(const Geometry& full, const Geometry& sub, const RegionsFrame* tab, uint32_t j) {
+    const uint32_t f = j / sub.slices_per_frame, s = j - f * sub.slices_per_frame;
+    const uint32_t planes = full.planar ? full.c : 1u;
+    const uint32_t tile = s / planes, ch = s - tile * planes;
+    const uint32_t ty = tile / sub.ntx, tx = tile - ty * sub.ntx;
+    return tab[f].frame * full.slices_per_frame + ((tab[f].wy0 + ty) * full.ntx + tab[f].wx0 + tx) * planes + ch;
+}
+// region_fits for a class: its frames are some of the batch's
+inline bool regions_fits(const Geometry& full, const Geometry& sub) { return sub.frames <= full.frames && sub_arrays_fit(full, sub); }
 
 }  // namespace llcomp_mi

@@ -123,4 +123,16 @@ hipError_t launch_model_inv_crop(const Geometry& sub, const int16_t* d_rec, uint
 // the fused row path (model_is_fused(sub)): lane-order samples -> the rectangle
 hipError_t launch_model_rows_inv_crop(const Geometry& sub, const int16_t* d_lanes, uint8_t* d_px, const Crop& cr, hipStream_t stream);
 
+// ---- regions decode (codec.hip: llcomp_mi_codec_decode_regions; DESIGN.md "Region decode") -----------------------------------
+// One class of frames (geometry.hpp: regions_window) on its sub-geometry `sub`; d_tab = the class's RegionsFrame entries, sub.frames
+// of them.  launch_region_index with a window per frame: sub-slice j = full slice regions_full_id(j).
+hipError_t launch_regions_index(const Geometry& full, const Geometry& sub, const RegionsFrame* d_tab, const uint32_t* d_slice_len,
+                                const uint64_t* d_group_off, uint32_t* d_sub_len, uint64_t* d_sub_off, hipStream_t stream);
+// The crop variants with a crop origin and an output frame per class frame: rw x rh x c bytes to d_px[d_tab[f].out], nothing else.
+// The caller guarantees cx0 + rw <= sub.w, cy0 + rh <= sub.h and out < the output's frames for every entry.
+hipError_t launch_model_inv_crops(const Geometry& sub, const int16_t* d_rec, uint8_t* d_px, const RegionsFrame* d_tab, uint32_t rw,
+                                  uint32_t rh, hipStream_t stream);
+hipError_t launch_model_rows_inv_crops(const Geometry& sub, const int16_t* d_lanes, uint8_t* d_px, const RegionsFrame* d_tab, uint32_t rw,
+                                       uint32_t rh, hipStream_t stream);
+
 }  // namespace llcomp_mi

@@ -15,6 +15,8 @@
 //                 LDS-tile moves between the packed payload and the stream lane order the serial kernels use.
 //   k_region_index / k_stage_region_streams / k_model_inv_crop / k_model_rows_inv_crop
 //                 region decode: the covered slices of a full payload -> lane order, and stage A's inverse of one rectangle.
+//   k_regions_index / k_model_inv_crops / k_model_rows_inv_crops
+//                 regions decode: the same with a window, a crop origin and an output frame per frame (a RegionsFrame table).
 // None of this is GEMM-shaped; there is no MFMA here on purpose.
 #include <algorithm>
 
@@ -1123,6 +1125,161 @@ __global__ __launch_bounds__(256) void k_model_rows_inv_crop(const Geometry g, c
     }
 }
 
+
+// ---- regions decode: a rectangle at an offset of its own in every frame of a class ------------------------------------------------
+// (codec.hip: llcomp_mi_codec_decode_regions.)  The crop kernels above with a RegionsFrame entry per class frame f: the rectangle
+// (tab[f].cx0, tab[f].cy0, rw, rh) of window f goes to output frame tab[f].out, densely ([out][rh][rw][c]); nothing else is stored.
+
+// k_region_index with one window per class frame: sub-slice j = full slice regions_full_id(j)
+__global__ __launch_bounds__(256) void k_regions_index(const Geometry full, const Geometry sub, const RegionsFrame* __restrict__ tab,
+                                                       const uint32_t* __restrict__ slice_len, const uint64_t* __restrict__ group_off,
+                                                       uint32_t* __restrict__ sub_len, uint64_t* __restrict__ sub_off) {
+    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= sub.n_slices) return;
+    const uint32_t id = regions_full_id(full, sub, tab, j);
+    unsigned long long o = group_off[id >> full.lane_shift];
+    for (uint32_t i = id & ~((1u << full.lane_shift) - 1); i < id; ++i) o += slice_len[i];
+    sub_len[j] = slice_len[id];
+    sub_off[j] = o;
+}
+
+// k_model_inv_crop: image-order samples of the class's windows -> the rectangles; C = 1..4, or 0: any count
+template <int C>
+__global__ __launch_bounds__(256) void k_model_inv_crops(const Geometry g, const int16_t* __restrict__ rec, uint8_t* __restrict__ px,
+                                                         const RegionsFrame* __restrict__ tab, uint32_t rw, uint32_t rh, size_t npix) {
+    const uint32_t c = C ? uint32_t(C) : g.c;
+    const size_t per_frame = size_t(rw) * rh;
+    for (size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x; i < npix; i += size_t(gridDim.x) * blockDim.x) {
+        const uint32_t f = uint32_t(i / per_frame);
+        const uint32_t rem = uint32_t(i - f * per_frame), yy = rem / rw, xx = rem - yy * rw;
+        const uint32_t y = tab[f].cy0 + yy, x = tab[f].cx0 + xx;
+        uint8_t* o = px + (size_t(tab[f].out) * per_frame + rem) * c;
+        uint32_t k = 0;
+        if (c >= 3) {  // llcomp.hpp:532-540
+            int r = rec[sample_index(g, f, y, x, 0)], gg = rec[sample_index(g, f, y, x, 1)], b = rec[sample_index(g, f, y, x, 2)];
+            gg -= (r + b) / 4;
+            r += gg;
+            b += gg;
+            o[0] = uint8_t(min(max(r, 0), 255));
+            o[1] = uint8_t(min(max(gg, 0), 255));
+            o[2] = uint8_t(min(max(b, 0), 255));
+            k = 3;
+        }
+        for (; k < c; ++k) o[k] = uint8_t(rec[sample_index(g, f, y, x, k)]);  // llcomp.hpp:541-543
+    }
+}
+
+// k_model_rows_inv_crop (the fused row path): each tile row's pixel run is clipped to its frame's rectangle
+template <int C>
+__device__ __forceinline__ void load_row_tiles_crops(const Geometry& g, uint32_t first_tile, uint32_t ntiles, const RegionsFrame* tab,
+                                                     uint32_t rw, uint32_t rh, RowTileCrop* tiles) {
+    if (threadIdx.x < ntiles) {
+        const uint32_t tile = first_tile + threadIdx.x;
+        const uint32_t per_frame = g.ntx * g.nty;
+        const uint32_t frame = tile / per_frame, rem = tile - frame * per_frame;
+        const uint32_t y = rem / g.ntx, tx = rem - y * g.ntx;
+        const uint32_t x0 = tx * g.tile_w;
+        const uint32_t sw = g.w - x0 < g.tile_w ? g.w - x0 : g.tile_w;
+        const uint32_t cx0 = tab[frame].cx0, cy0 = tab[frame].cy0;
+        const uint32_t klo = cx0 > x0 ? cx0 - x0 : 0u;
+        uint32_t khi = cx0 + rw > x0 ? min(sw, cx0 + rw - x0) : 0u;
+        if (y < cy0 || y >= cy0 + rh || khi <= klo) khi = 0;
+        tiles[threadIdx.x].base = ((long long)(size_t(tab[frame].out) * rh + (y - cy0)) * rw + (long long)x0 - (long long)cx0) * C;
+        tiles[threadIdx.x].klo = klo;
+        tiles[threadIdx.x].khi = khi;
+    }
+}
+template <int C>
+__global__ __launch_bounds__(256) void k_model_rows_inv_crops(const Geometry g, const int16_t* __restrict__ lanes,
+                                                              uint8_t* __restrict__ px, const RegionsFrame* __restrict__ tab,
+                                                              uint32_t rw, uint32_t rh) {
+    constexpr int K = 64, TPG = 64 / C + 2;
+    __shared__ __attribute__((aligned(4))) int16_t tile[K][64 + C + 1 + ((C + 1) & 1)];  // even row length: dword rows
+    __shared__ RowTileCrop tiles[TPG];
+    const uint32_t chunks = (g.tile_w + K - 1) / K;
+    uint32_t group, chunk;
+    if (!xcd_chunk_group((g.n_slices + (1u << g.lane_shift) - 1) >> g.lane_shift, chunks, group, chunk)) return;  // (uniform per block)
+    const uint32_t k0 = chunk * K;
+    const uint32_t gw = 1u << g.lane_shift;
+    const uint32_t first_id = group << g.lane_shift;
+    const uint32_t end_id = first_id + gw < g.n_slices ? first_id + gw : g.n_slices;
+    const uint32_t first_tile = (first_id + C - 1) / C;          // first tile whose channel 0 is in this group
+    const uint32_t end_tile = (end_id + C - 1) / C;              // one past the last such tile
+    if (first_tile >= end_tile) return;
+    const uint32_t ntiles = end_tile - first_tile;
+    load_row_tiles_crops<C>(g, first_tile, ntiles, tab, rw, rh, tiles);
+    // LDS column = lane index relative to this group (0..gw-1), columns gw.. = first C-1 lanes of the NEXT group.
+    // Rows of this group are read as whole 128-byte pieces (32 dwords = 64 samples); the few extra lanes one by one.
+    {   // (all eight loads of a thread are in flight before the first one is stored to LDS: the kernel is bound by the
+        // latency of its phases, one memory round trip per block instead of eight)
+        uint32_t w[K * 32 / 256];
+#pragma unroll
+        for (int it = 0; it < K * 32 / 256; ++it) {
+            const uint32_t i = threadIdx.x + 256 * it, kk = i >> 5, d = i & 31, k = k0 + kk;
+            w[it] = 0;
+            if (k < g.tile_w && g.lane_shift == 6)
+                w[it] = *reinterpret_cast<const uint32_t*>(lanes + lane_order_index(g, first_id + 2 * d, k));
+        }
+#pragma unroll
+        for (int it = 0; it < K * 32 / 256; ++it) {
+            const uint32_t i = threadIdx.x + 256 * it, kk = i >> 5, d = i & 31;
+            *reinterpret_cast<uint32_t*>(&tile[kk][2 * d]) = w[it];
+        }
+    }
+    if (g.lane_shift != 6) {  // fewer than 64 slices in total: narrow group, plain element loads
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < uint32_t(K) * gw; i += 256) {
+            const uint32_t kk = i / gw, col = i - kk * gw, k = k0 + kk;
+            tile[kk][col] = (first_id + col < g.n_slices && k < g.tile_w) ? lanes[lane_order_index(g, first_id + col, k)] : int16_t(0);
+        }
+    }
+    if constexpr (C > 1) {
+        for (uint32_t i = threadIdx.x; i < uint32_t(K) * (C - 1); i += 256) {
+            const uint32_t kk = i / (C - 1), e = i - kk * (C - 1), k = k0 + kk;
+            const uint32_t id = first_id + gw + e;
+            tile[kk][gw + e] = (id < g.n_slices && k < g.tile_w) ? lanes[lane_order_index(g, id, k)] : int16_t(0);
+        }
+    }
+    __syncthreads();
+    const uint32_t col0 = first_tile * C - first_id;  // group-relative lane of the first tile's channel 0
+    const uint32_t q4 = threadIdx.x & 15;  // which group of 4 pixels of the 64-sample chunk
+    for (uint32_t tt = threadIdx.x >> 4; tt < ntiles; tt += 16) {
+        const uint32_t sw = tiles[tt].khi, klo = tiles[tt].klo, kb = k0 + 4 * q4;
+        if (kb >= sw || kb + 4 <= klo) continue;
+        uint8_t bytes[4 * C];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int16_t* s = &tile[4 * q4 + i][col0 + tt * C];
+            if constexpr (C >= 3) {  // llcomp.hpp:532-543
+                int r = s[0], gg = s[1], bb = s[2];
+                gg -= (r + bb) / 4;
+                r += gg;
+                bb += gg;
+                bytes[i * C + 0] = uint8_t(min(max(r, 0), 255));
+                bytes[i * C + 1] = uint8_t(min(max(gg, 0), 255));
+                bytes[i * C + 2] = uint8_t(min(max(bb, 0), 255));
+                if constexpr (C == 4) bytes[i * C + 3] = uint8_t(s[3]);
+            } else {
+#pragma unroll
+                for (int c = 0; c < C; ++c) bytes[i * C + c] = uint8_t(s[c]);
+            }
+        }
+        const uint32_t npx = sw - kb < 4 ? sw - kb : 4;
+        if (npx < 4 || kb < klo) {  // the rectangle's left / right edge: only the pixels inside it
+            for (uint32_t i = kb < klo ? klo - kb : 0u; i < npx; ++i)
+                for (uint32_t c = 0; c < uint32_t(C); ++c) px[tiles[tt].base + (long long)(kb + i) * C + c] = bytes[i * C + c];
+            continue;
+        }
+        uint32_t w[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+            w[c] = uint32_t(bytes[4 * c]) | (uint32_t(bytes[4 * c + 1]) << 8) | (uint32_t(bytes[4 * c + 2]) << 16) |
+                   (uint32_t(bytes[4 * c + 3]) << 24);
+        __builtin_memcpy(px + tiles[tt].base + size_t(kb) * C, w, 4 * C);  // four pixels inside the rectangle: unaligned dword stores
+    }
+}
+
+
 }  // namespace
 
 #define LLMI_DISPATCH_C(c, CALL) \
@@ -1267,6 +1424,37 @@ hipError_t launch_model_rows_inv_crop(const Geometry& sub, const int16_t* d_lane
     const uint64_t blocks = xcd_chunk_grid(lane_groups(sub), (sub.tile_w + 63) / 64);
     if (blocks == 0 || blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
     LLMI_DISPATCH_C(sub.c, (k_model_rows_inv_crop<C><<<dim3(uint32_t(blocks)), dim3(256), 0, stream>>>(sub, d_lanes, d_px, cr)));
+    return hipGetLastError();
+}
+
+hipError_t launch_regions_index(const Geometry& full, const Geometry& sub, const RegionsFrame* d_tab, const uint32_t* d_slice_len,
+                                const uint64_t* d_group_off, uint32_t* d_sub_len, uint64_t* d_sub_off, hipStream_t stream) {
+    if (sub.n_slices == 0) return hipErrorInvalidValue;
+    k_regions_index<<<dim3((sub.n_slices + 255) / 256), dim3(256), 0, stream>>>(full, sub, d_tab, d_slice_len, d_group_off, d_sub_len, d_sub_off);
+    return hipGetLastError();
+}
+
+hipError_t launch_model_inv_crops(const Geometry& sub, const int16_t* d_rec, uint8_t* d_px, const RegionsFrame* d_tab, uint32_t rw,
+                                  uint32_t rh, hipStream_t stream) {
+    const size_t npix = size_t(sub.frames) * rh * rw;
+    if (npix == 0 || rw > sub.w || rh > sub.h) return hipErrorInvalidValue;
+    const uint32_t blocks = uint32_t(std::min<size_t>((npix + 255) / 256, 256 * 16));
+    switch (sub.c) {
+        case 1: k_model_inv_crops<1><<<dim3(blocks), dim3(256), 0, stream>>>(sub, d_rec, d_px, d_tab, rw, rh, npix); break;
+        case 2: k_model_inv_crops<2><<<dim3(blocks), dim3(256), 0, stream>>>(sub, d_rec, d_px, d_tab, rw, rh, npix); break;
+        case 3: k_model_inv_crops<3><<<dim3(blocks), dim3(256), 0, stream>>>(sub, d_rec, d_px, d_tab, rw, rh, npix); break;
+        case 4: k_model_inv_crops<4><<<dim3(blocks), dim3(256), 0, stream>>>(sub, d_rec, d_px, d_tab, rw, rh, npix); break;
+        default: k_model_inv_crops<0><<<dim3(blocks), dim3(256), 0, stream>>>(sub, d_rec, d_px, d_tab, rw, rh, npix); break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_model_rows_inv_crops(const Geometry& sub, const int16_t* d_lanes, uint8_t* d_px, const RegionsFrame* d_tab, uint32_t rw,
+                                       uint32_t rh, hipStream_t stream) {
+    if (!rw || !rh || rw > sub.w || rh > sub.h) return hipErrorInvalidValue;
+    const uint64_t blocks = xcd_chunk_grid(lane_groups(sub), (sub.tile_w + 63) / 64);
+    if (blocks == 0 || blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    LLMI_DISPATCH_C(sub.c, (k_model_rows_inv_crops<C><<<dim3(uint32_t(blocks)), dim3(256), 0, stream>>>(sub, d_lanes, d_px, d_tab, rw, rh)));
     return hipGetLastError();
 }
 
