@@ -27,7 +27,9 @@ extern "C" {
 /* ABI 4 (round 6: device lists -- llcomp_mi_opts.devices, llcomp_mi_decode_devices, llcomp_mi_stream_create_multi,
  * llcomp_mi_plan_chunks, llcomp_mi_codec_get_counters; later, functions only: region decode -- llcomp_mi_region_plan,
  * llcomp_mi_decode_region(_into), llcomp_mi_codec_decode_region, llcomp_mi_codec_region_family, LLCOMP_MI_PREPARE_REGION; a rectangle
- * per frame -- llcomp_mi_regions_plan, llcomp_mi_codec_decode_regions, llcomp_mi_codec_regions_family, LLCOMP_MI_PREPARE_REGIONS).  The library and its callers are built from ONE header: structs have one layout per ABI version (llcomp_mi_opts is
+ * per frame -- llcomp_mi_regions_plan, llcomp_mi_codec_decode_regions, llcomp_mi_codec_regions_family, LLCOMP_MI_PREPARE_REGIONS; crops
+ * of host containers -- llcomp_mi_regions_gather, llcomp_mi_codec_decode_regions_host, llcomp_mi_stream_submit_decode_regions,
+ * LLCOMP_MI_JOB_DECODE_REGIONS, LLCOMP_MI_CTR_HOST_STAGED_BYTES).  The library and its callers are built from ONE header: structs have one layout per ABI version (llcomp_mi_opts is
  * checked through struct_size and refused when it differs; llcomp_mi_info and llcomp_mi_stream_result are written in full),
  * so a binding compares llcomp_mi_abi_version() with the LLCOMP_MI_ABI_VERSION it was generated from and refuses to run on
  * a mismatch -- there is no cross-version compatibility mode. */
@@ -112,7 +114,8 @@ void llcomp_mi_free(void* p);
  * cropped on the GPU.  BAD_EXPONENT and TRUNCATED come from covered slices only (a covered slice whose bytes run past the data is
  * TRUNCATED); a region decode does NOT validate the container -- damage in slices outside the rectangle is never seen.  A header or
  * slice table that is cut short fails as in llcomp_mi_probe.  flags: LLCOMP_MI_FLAG_SMALL_MODEL as in llcomp_mi_decode_flags.  *c
- * reports the channel count.  One device only: there is no region decode over a device list or through the streaming pipeline. */
+ * reports the channel count.  One device only: there is no region decode over a device list.  Crops of many containers at once:
+ * llcomp_mi_codec_decode_regions_host (into HBM) and llcomp_mi_stream_submit_decode_regions (host to host). */
 int llcomp_mi_decode_region(const uint8_t* data, size_t len, int32_t device, uint32_t flags, uint32_t x, uint32_t y, uint32_t rw,
                             uint32_t rh, uint8_t** px, uint32_t* c);
 /* ... into a caller's buffer: OUTPUT_OVERFLOW (with *c set, nothing written) when px_cap < rw * rh * c. */
@@ -191,6 +194,20 @@ int llcomp_mi_region_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, u
  * n = 0, a NULL xy or n_classes, or any rectangle outside the image.  Host-only; every regions call plans with this rule. */
 int llcomp_mi_regions_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar, uint32_t rw, uint32_t rh,
                            const uint32_t* xy, uint32_t n, uint32_t* windows, uint32_t* n_classes);
+/* The bytes a regions decode of n single-frame SLICED containers (data[f], lens[f]; one shape, tiling, planar setting and model) needs:
+ * the table entries and payload bytes of every frame's window (llcomp_mi_regions_plan) and nothing else.  slice_len (room for len_cap
+ * entries) gets the windows' table entries verbatim, payload (room for payload_cap bytes) the same slices' bytes back to back, both in
+ * one order: class by class (class 0..3), frame order inside a class, and inside a frame tile row, tile column, plane.  A window's tile
+ * row is one run of consecutive slices of its container, so this is one memcpy per window tile row and frame.  *payload_bytes,
+ * *n_slices (entries) and *n_classes are always set (0 on an error); payload == NULL or slice_len == NULL only reports them, and a
+ * capacity too small is OUTPUT_OVERFLOW with nothing written.  Errors, all decided before anything is written: BAD_ARGS for n = 0, a
+ * NULL pointer among data / lens / xy / the three counts, a LEGACY stream, a container that differs from container 0, or any rectangle
+ * outside the image; a header or table cut short fails as in llcomp_mi_probe; TRUNCATED for a window slice whose bytes run past its
+ * container or whose table entry is above the SLICED limit (LLCOMP_MI_TRUNCATED).  Damage outside every window is never seen.
+ * Host-only: no GPU involved. */
+int llcomp_mi_regions_gather(const uint8_t* const* data, const size_t* lens, uint32_t n, const uint32_t* xy, uint32_t rw, uint32_t rh,
+                             uint8_t* payload, uint64_t payload_cap, uint32_t* slice_len, uint32_t len_cap, uint64_t* payload_bytes,
+                             uint32_t* n_slices, uint32_t* n_classes);
 uint32_t llcomp_mi_slice_count(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar);
 /* Slice width for one-row slices (tile_h = 1) when `frames` frames are coded per call: the widest slice (64..480 pixels) that
  * still keeps about four wavefronts per SIMD busy.  A call that codes few frames is latency-bound with wide slices; this
@@ -291,6 +308,19 @@ int llcomp_mi_codec_decode_regions(llcomp_mi_codec* codec, const void* d_payload
  * number of classes; 0 for bad arguments. */
 uint32_t llcomp_mi_codec_regions_family(const llcomp_mi_codec* codec, const uint32_t* xy, uint32_t rw, uint32_t rh, uint32_t* fam,
                                         uint32_t cap);
+/* The same regions decode from HOST containers: data[f] / lens[f] are the frames' single-frame SLICED containers (f < frames; the codec's
+ * shape, tiling, planar setting and model), and only their windows' bytes cross PCIe.  d_px and the status word get the same bytes as
+ * llcomp_mi_codec_decode_regions on the payload and table of the same containers packed back to back, for every input whose slice
+ * tables fit their containers.  The call runs llcomp_mi_regions_gather into a slot of the codec's pinned ring (with the per-frame table
+ * and every window slice's offset) and queues ONE host-to-device copy of it into a staging buffer of the codec; the decode then runs as
+ * for llcomp_mi_codec_decode_regions, class by class on `stream`.  The containers and xy are read during the call only: the caller may
+ * free or overwrite them as soon as it returns.  A gather error (llcomp_mi_regions_gather; BAD_ARGS also for containers that do not match
+ * the codec) is returned before anything is queued, and d_px / d_status stay untouched.  The pinned slots and the staging buffer grow
+ * geometrically when a call needs more (never per call; llcomp_mi_codec_workspace_bytes counts the buffer's upper bound): such a call can
+ * return LLCOMP_MI_NOMEM.  A call waits only for the copy of the call four before it on that codec.  LLCOMP_MI_CTR_HOST_STAGED_BYTES
+ * counts the payload bytes staged.  Profile slots as for a regions decode. */
+int llcomp_mi_codec_decode_regions_host(llcomp_mi_codec* codec, const uint8_t* const* data, const size_t* lens, const uint32_t* xy, uint32_t rw,
+                                        uint32_t rh, void* d_px, void* d_status, void* stream);
 /* Stage-A only (context + prediction model), for tests and profiling: d_sym u32[frames*h*w*c],
  * low 16 bits = folded context (0..7925), high 16 bits = folded residual (two's complement). */
 int llcomp_mi_codec_model(llcomp_mi_codec* codec, const void* d_px, void* d_sym, void* stream);
@@ -327,6 +357,7 @@ enum {
     LLCOMP_MI_CTR_DEC_LAUNCHES_CACHED = 8, /* 2-D decode launches that ran with the bank cache */
     LLCOMP_MI_CTR_DEC_LAUNCHES_PLAIN = 9,  /* ... and without it, because (nearly) every wavefront of the last cached launch had given
                                               it up: the plain kernel holds no LDS for a cache nobody uses; re-probed every 16th call */
+    LLCOMP_MI_CTR_HOST_STAGED_BYTES = 10,  /* payload bytes llcomp_mi_codec_decode_regions_host copied to the GPU (host-side count) */
     LLCOMP_MI_CTR_COUNT = 16
 };
 int llcomp_mi_codec_get_counters(llcomp_mi_codec* codec, uint64_t* out, uint32_t n, int reset);
@@ -345,15 +376,16 @@ int llcomp_mi_codec_get_profile(llcomp_mi_codec* codec, double* ms8, uint32_t* n
  * pipeline.  `depth` slots (1..16), each with its own codec object, HIP stream, HBM buffers and a pinned output buffer;
  * a job is one frame (SLICED container).  submit_* returns at once: LLCOMP_MI_OK, or LLCOMP_MI_BUSY when every slot is
  * occupied (back-pressure: take a result and release it).  `px` / `data` must stay valid until the job's result has
- * been returned by llcomp_mi_stream_wait; pinned memory (llcomp_mi_host_alloc, or the `data` of an earlier result that
+ * been returned by llcomp_mi_stream_wait (except for llcomp_mi_stream_submit_decode_regions, which reads them during the call only); pinned memory (llcomp_mi_host_alloc, or the `data` of an earlier result that
  * has not been released) is copied by DMA while other jobs compute.  Results come back in submission order.  A
  * container that needs more than 2x the raw size fails with OUTPUT_OVERFLOW (llcomp_mi_encode handles such a frame).
  * One object is driven by one thread at a time (calls are serialised internally). */
 typedef struct llcomp_mi_stream llcomp_mi_stream;
-enum { LLCOMP_MI_JOB_ENCODE = 0, LLCOMP_MI_JOB_DECODE = 1 };
+enum { LLCOMP_MI_JOB_ENCODE = 0, LLCOMP_MI_JOB_DECODE = 1, LLCOMP_MI_JOB_DECODE_REGIONS = 2 };
 typedef struct llcomp_mi_stream_result {
     uint32_t slot;       /* hand back with llcomp_mi_stream_release when `data` is no longer needed */
-    uint32_t kind;       /* LLCOMP_MI_JOB_ENCODE: data = container, LLCOMP_MI_JOB_DECODE: data = h*w*c pixels */
+    uint32_t kind;       /* LLCOMP_MI_JOB_ENCODE: data = container, LLCOMP_MI_JOB_DECODE: data = h*w*c pixels,
+                            LLCOMP_MI_JOB_DECODE_REGIONS: data = frames_per_job crops of rh*rw*c pixels */
     int32_t status;      /* llcomp_mi_status of this job */
     uint32_t reserved;
     uint64_t tag;        /* the caller's tag from submit */
@@ -383,6 +415,13 @@ void llcomp_mi_stream_destroy(llcomp_mi_stream* stream);
 uint64_t llcomp_mi_stream_container_capacity(const llcomp_mi_stream* stream); /* largest container a slot can return */
 int llcomp_mi_stream_submit_encode(llcomp_mi_stream* stream, const uint8_t* px, uint64_t tag);
 int llcomp_mi_stream_submit_decode(llcomp_mi_stream* stream, const uint8_t* data, size_t len, uint64_t tag);
+/* A job of crops: frames_per_job containers (data[f], lens[f]) and frame f's rectangle (xy[2f], xy[2f + 1], rw, rh).  The slot's codec
+ * runs llcomp_mi_codec_decode_regions_host on the slot's stream (only the windows' bytes cross PCIe), then the crops come back:
+ * kind = LLCOMP_MI_JOB_DECODE_REGIONS, len = frames_per_job * rw * rh * c, dense [frames][rh][rw][c], and llcomp_mi_stream_result_part
+ * hands out crop f.  UNLIKE the other submits, the containers and xy are read during the call only: they may be reused as soon as it
+ * returns.  A gather error is the call's return value (nothing is queued).  Region jobs and whole-frame jobs mix in one object. */
+int llcomp_mi_stream_submit_decode_regions(llcomp_mi_stream* stream, const uint8_t* const* data, const size_t* lens, const uint32_t* xy,
+                                           uint32_t rw, uint32_t rh, uint64_t tag);
 int llcomp_mi_stream_pending(llcomp_mi_stream* stream); /* jobs submitted and not yet returned by wait */
 /* LLCOMP_MI_OK when llcomp_mi_stream_wait would not block (or nothing is pending), LLCOMP_MI_BUSY otherwise. */
 int llcomp_mi_stream_poll(llcomp_mi_stream* stream);

@@ -8,6 +8,7 @@ with ctypes and keeps the reference's names and error behaviour:
     decompress_image(data) -> RawImage            <->  llcomp::decompressImage  (/root/reference/llcomp.hpp:461)
     decompress_region(data, x, y, w, h)           <->  llcomp::decompressRegion (include/llcomp_mi.hpp: one rectangle, covered slices only)
     regions_plan(w, h, c, tw, th, planar, rw, rh, xy) / Codec.decode_regions  (a rectangle per frame of a batch; pack_batch feeds it)
+    regions_gather / Codec.decode_regions_host / Stream.submit_decode_regions  (the same from host containers: only the windows cross)
     RawImage(pixels, width, height, channels)     <->  llcomp::RawImage         (/root/reference/llcomp.hpp:454-459)
     EXT = ".llcomp"                               <->  llcomp::ext              (/root/reference/llcomp.hpp:18)
 
@@ -25,7 +26,7 @@ from ._lib import Info, Opts
 EXT = ".llcomp"
 FORMAT_LEGACY, FORMAT_SLICED = 0, 1
 (OK, BAD_MAGIC, BAD_EXPONENT, TRUNCATED, BAD_ARGS, OUT_OF_RANGE, OUTPUT_OVERFLOW, HIP_ERROR, NO_DEVICE, NOMEM, BUSY, DEVICE_FAILED) = range(12)
-JOB_ENCODE, JOB_DECODE = 0, 1
+JOB_ENCODE, JOB_DECODE, JOB_DECODE_REGIONS = 0, 1, 2
 
 RawImage = namedtuple("RawImage", "pixels width height channels")
 
@@ -172,6 +173,37 @@ def pack_batch(containers):
     return np.concatenate(pays), np.concatenate(lens)
 
 
+def _containers(containers):
+    """(void* array, size_t array, keep-alive list) of a list of containers: bytes, bytearray, memoryview or contiguous uint8 arrays, passed
+    without a copy"""
+    keep, ptrs = [], []
+    for d in containers:
+        if isinstance(d, bytes):
+            ptrs.append(C.cast(C.c_char_p(d), C.c_void_p).value)
+        else:
+            d = np.frombuffer(d, dtype=np.uint8) if not isinstance(d, np.ndarray) else d
+            if d.dtype != np.uint8 or not d.flags["C_CONTIGUOUS"]:
+                raise LlcompError(BAD_ARGS, "a container must be bytes or a contiguous uint8 array")
+            ptrs.append(d.ctypes.data if d.size else C.cast(C.c_char_p(b""), C.c_void_p).value)
+        keep.append(d)
+    return (C.c_void_p * max(1, len(keep)))(*ptrs), (C.c_size_t * max(1, len(keep)))(*[len(d) if isinstance(d, bytes) else d.size for d in keep]), keep
+
+
+def regions_gather(containers, xy, rw, rh):
+    """(payload np.uint8, slice_len np.uint32, n_classes): the table entries and payload bytes of every frame's window (regions_plan) of
+    single-frame SLICED containers, class by class, frame order inside a class -- exactly what a regions decode of them reads
+    (llcomp_mi_regions_gather, host only).  LlcompError as llcomp_mi_regions_gather reports it."""
+    L = _lib.load()
+    ptrs, lens, keep = _containers(containers)
+    tab, n = _xy_table(xy, len(keep))
+    nb, ns, nc = C.c_uint64(), C.c_uint32(), C.c_uint32()
+    _check(L.llcomp_mi_regions_gather(ptrs, lens, n, tab, rw, rh, None, 0, None, 0, C.byref(nb), C.byref(ns), C.byref(nc)))
+    pay, sl = np.empty(max(1, nb.value), np.uint8), np.empty(max(1, ns.value), np.uint32)
+    _check(L.llcomp_mi_regions_gather(ptrs, lens, n, tab, rw, rh, pay.ctypes.data, nb.value, sl.ctypes.data, ns.value, C.byref(nb), C.byref(ns),
+                                      C.byref(nc)))
+    return pay[:nb.value], sl[:ns.value], nc.value
+
+
 def decompress_region(data, x, y, w, h, *, device=-1, small_model=False):
     """RawImage(pixels: np.uint8[h,w,c], w, h, c) of the rectangle (x, y, w, h) of the picture (llcomp_mi_decode_region): only the
     slices of the tiles it touches are read and decoded.  A region decode does not validate the rest of the container."""
@@ -295,6 +327,7 @@ class Stream:
             _check(self._L.llcomp_mi_stream_create_ex(C.byref(self._h), device, w, h, c, tile_w, tile_h, int(bool(planar)), depth, frames_per_job))
         self.n_devices = self._L.llcomp_mi_stream_devices(self._h)
         self.shape = (h, w, c)
+        self._shapes = []  # the frame shape of every pending job, in submission order (results come back in that order)
         self.frames_per_job = frames_per_job
         self.container_capacity = self._L.llcomp_mi_stream_container_capacity(self._h)
 
@@ -305,10 +338,11 @@ class Stream:
 
     __del__ = close
 
-    def _submit(self, rc):
+    def _submit(self, rc, shape=None):
         if rc == BUSY:
             return False
         _check(rc)
+        self._shapes.append(shape or self.shape)
         return True
 
     def submit_encode(self, px, tag=0):
@@ -326,6 +360,17 @@ class Stream:
         lens = (C.c_size_t * len(parts))(*[p.size for p in parts])
         return self._submit(self._L.llcomp_mi_stream_submit_decode_batch(self._h, ptrs, lens, tag))
 
+    def submit_decode_regions(self, containers, xy, rw, rh, tag=0):
+        """frames_per_job containers (bytes or uint8 arrays) and their rectangles' origins xy ([frames_per_job, 2]) -> a job whose
+        .data is the crop [rh,rw,c] (one frame per job) / the crops [F,rh,rw,c].  Only the windows' bytes cross PCIe; the containers
+        are read during this call only and may be reused as soon as it returns."""
+        ptrs, lens, keep = _containers(containers)
+        if len(keep) != self.frames_per_job:
+            raise LlcompError(BAD_ARGS, f"a job takes {self.frames_per_job} containers, got {len(keep)}")
+        tab, _ = _xy_table(xy, self.frames_per_job)
+        rc = self._L.llcomp_mi_stream_submit_decode_regions(self._h, ptrs, lens, tab, rw, rh, tag)
+        return self._submit(rc, (rh, rw, self.shape[2]))
+
     def pending(self):
         return self._L.llcomp_mi_stream_pending(self._h)
 
@@ -335,11 +380,12 @@ class Stream:
     def wait(self):
         r = _lib.StreamResult()
         _check(self._L.llcomp_mi_stream_wait(self._h, C.byref(r)))
+        shape = self._shapes.pop(0)
         data = None
         if r.status == OK:
             whole = np.ctypeslib.as_array(C.cast(r.data, _lib.u8p), shape=(max(int(r.len), 1),))[: int(r.len)]
-            if r.kind == JOB_DECODE:
-                data = whole.reshape(self.shape) if self.frames_per_job == 1 else whole.reshape((self.frames_per_job,) + self.shape)
+            if r.kind in (JOB_DECODE, JOB_DECODE_REGIONS):
+                data = whole.reshape(shape) if self.frames_per_job == 1 else whole.reshape((self.frames_per_job,) + shape)
             elif self.frames_per_job == 1:
                 data = whole
             else:
@@ -563,6 +609,16 @@ class Codec:
         tab, _ = _xy_table(xy, self.frames)
         _check(self._L.llcomp_mi_codec_decode_regions(self._h, d_payload, payload_bytes, d_slice_len, tab, rw, rh, d_px, d_status, stream))
 
+    def decode_regions_host(self, containers, xy, rw, rh, d_px, d_status, stream=0):
+        """decode_regions of host containers (llcomp_mi_codec_decode_regions_host): `containers` = the frames' single-frame SLICED
+        containers (bytes or uint8 arrays), and only their windows' bytes cross PCIe.  The containers and xy are read during the call
+        only; the decode is asynchronous on `stream`."""
+        ptrs, lens, keep = _containers(containers)
+        if len(keep) != self.frames:
+            raise LlcompError(BAD_ARGS, f"the codec takes {self.frames} containers, got {len(keep)}")
+        tab, _ = _xy_table(xy, self.frames)
+        _check(self._L.llcomp_mi_codec_decode_regions_host(self._h, ptrs, lens, tab, rw, rh, d_px, d_status, stream))
+
     def regions_family(self, xy, rw, rh):
         """the kernel family of every class a regions decode of these rectangles runs, in class order (the keys of .family); None
         for bad rectangles"""
@@ -595,7 +651,7 @@ class Codec:
         _check(self._L.llcomp_mi_codec_prepare(self._h, (1 if encode else 0) | (2 if decode else 0) | (8 if region else 0) | (16 if regions else 0)))
 
     COUNTERS = ("dec_cached_waves", "dec_bypassed_waves", "cache_lookups", "cache_misses", "cache_writebacks", "dec_replays", "enc_carry_backs",
-                "generation_wraps", "dec_launches_cached", "dec_launches_plain")
+                "generation_wraps", "dec_launches_cached", "dec_launches_plain", "host_staged_bytes")
 
     def counters(self, reset=False):
         """{name: count} -- what the rare and adaptive paths of this codec's kernels did so far (llcomp_mi_codec_get_counters);

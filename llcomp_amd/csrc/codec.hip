@@ -259,24 +259,89 @@ int region_setup(const llcomp_mi_codec* k, uint32_t x, uint32_t y, uint32_t rw, 
 int ensure_regions_table(llcomp_mi_codec* k) {
     if (k->d_regions) return LLCOMP_MI_OK;
     const uint64_t bytes = uint64_t(k->g.frames) * sizeof(RegionsFrame);
-    if (!k->h_regions) {
-        if (hipHostMalloc(reinterpret_cast<void**>(&k->h_regions), bytes * llcomp_mi_codec::kRegionsRing, hipHostMallocDefault) != hipSuccess) {
-            k->h_regions = nullptr;
+    for (uint32_t i = 0; i < llcomp_mi_codec::kRegionsRing; ++i) {
+        if (k->h_regions[i]) continue;
+        if (hipHostMalloc(reinterpret_cast<void**>(&k->h_regions[i]), bytes, hipHostMallocDefault) != hipSuccess) {
+            k->h_regions[i] = nullptr;
             (void)hipGetLastError();
             return LLCOMP_MI_NOMEM;
         }
-        for (auto& ev : k->regions_ev)
-            if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
-                ev = nullptr;
-                (void)hipGetLastError();
-                return LLCOMP_MI_HIP_ERROR;
-            }
+        k->h_regions_cap[i] = bytes;
     }
+    for (auto& ev : k->regions_ev)
+        if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
+            ev = nullptr;
+            (void)hipGetLastError();
+            return LLCOMP_MI_HIP_ERROR;
+        }
     if (dev_alloc(reinterpret_cast<void**>(&k->d_regions), bytes) != hipSuccess) {
         k->d_regions = nullptr;
         return LLCOMP_MI_NOMEM;
     }
     k->allocated_bytes += bytes;
+    return LLCOMP_MI_OK;
+}
+// The ring's next slot, for a call that writes `bytes` to it: the slot's last copy has to have left it (queued four calls ago: this
+// waits only when the caller runs that far ahead), and a slot too small is replaced by one of max(bytes, twice its size, at most
+// `bound`) bytes.  The caller fills it, queues its copy and then calls regions_slot_queued.
+int regions_slot_take(llcomp_mi_codec* k, uint64_t bytes, uint64_t bound, uint32_t& slot) {
+    slot = k->regions_slot;
+    if (k->regions_ev_live[slot]) {
+        if (hipEventSynchronize(k->regions_ev[slot]) != hipSuccess) return LLCOMP_MI_HIP_ERROR;
+        k->regions_ev_live[slot] = false;
+    }
+    if (bytes <= k->h_regions_cap[slot]) return LLCOMP_MI_OK;
+    const uint64_t cap = std::max(bytes, std::min(2 * k->h_regions_cap[slot], bound));
+    (void)hipHostFree(k->h_regions[slot]);
+    k->h_regions[slot] = nullptr;
+    k->h_regions_cap[slot] = 0;
+    if (hipHostMalloc(reinterpret_cast<void**>(&k->h_regions[slot]), cap, hipHostMallocDefault) != hipSuccess) {
+        k->h_regions[slot] = nullptr;
+        (void)hipGetLastError();
+        return LLCOMP_MI_NOMEM;
+    }
+    k->h_regions_cap[slot] = cap;
+    return LLCOMP_MI_OK;
+}
+// ... behind the copy out of it, on the caller's stream
+int regions_slot_queued(llcomp_mi_codec* k, uint32_t slot, hipStream_t s) {
+    HIP_TRY(hipEventRecord(k->regions_ev[slot], s));
+    k->regions_ev_live[slot] = true;
+    k->regions_slot = (slot + 1) % llcomp_mi_codec::kRegionsRing;
+    return LLCOMP_MI_OK;
+}
+
+// What a host-staged regions decode copies to the GPU in one piece (pinned slot -> d_stage): the per-frame table, the window slices'
+// lengths and payload offsets (in the order of the table: class by class, llcomp_mi_regions_gather), then their payload bytes.
+struct StageLayout {
+    uint64_t len_at, off_at, pay_at, bytes;
+    StageLayout(uint32_t frames, uint64_t slices, uint64_t payload) {
+        len_at = uint64_t(frames) * sizeof(RegionsFrame);
+        off_at = (len_at + 4 * slices + 7) & ~7ull;
+        pay_at = off_at + 8 * slices;
+        bytes = pay_at + payload;
+    }
+};
+// ... at most: every slice of the batch, each at the SLICED entry limit (the gather refuses a window entry above it)
+uint64_t stage_bound(const Geometry& g) { return StageLayout(g.frames, g.n_slices, uint64_t(g.n_slices) * (g.slice_cap - 16)).bytes; }
+// The staging buffer in HBM for `bytes`: grown to max(bytes, twice its size, at most stage_bound) when too small.  The old buffer may
+// still be read by the codec's last call: that call is waited for (only a call that grows the buffer waits).
+int ensure_stage(llcomp_mi_codec* k, uint64_t bytes) {
+    if (bytes <= k->stage_cap) return LLCOMP_MI_OK;
+    const uint64_t cap = std::max(bytes, std::min(2 * k->stage_cap, stage_bound(k->g)));
+    if (k->d_stage) {
+        if (k->done && k->done->ev && hipEventSynchronize(k->done->ev) != hipSuccess) return LLCOMP_MI_HIP_ERROR;
+        dev_free(k->d_stage);
+        k->allocated_bytes -= k->stage_cap;
+        k->d_stage = nullptr;
+        k->stage_cap = 0;
+    }
+    if (dev_alloc(reinterpret_cast<void**>(&k->d_stage), cap) != hipSuccess) {
+        k->d_stage = nullptr;
+        return LLCOMP_MI_NOMEM;
+    }
+    k->stage_cap = cap;
+    k->allocated_bytes += cap;
     return LLCOMP_MI_OK;
 }
 
@@ -327,6 +392,58 @@ int regions_setup(const llcomp_mi_codec* k, const uint32_t* xy, uint32_t rw, uin
     return LLCOMP_MI_OK;
 }
 
+// Where the classes of a regions decode find their slices: `payload` (payload_bytes long) and, per slice of a class, its length and offset
+// in it -- found by k_regions_index over the FULL table (full_len; the group offsets of the full geometry must be in d_group_off), or
+// read from compact arrays that hold every class's slices back to back in class order (staged_len / staged_off: a host-staged call).
+struct RegionsSource {
+    const uint8_t* payload;
+    uint64_t payload_bytes;
+    const uint32_t* full_len;
+    const uint32_t* staged_len;
+    const uint64_t* staged_off;
+};
+// The launch chain of every class, in order on `s`: state generation, its slices to stream lane order, the decoder, the crops.
+// d_tab: the per-frame table in HBM (class by class, regions_setup).
+int regions_classes(llcomp_mi_codec* k, const RegionsClass* classes, uint32_t n_classes, const RegionsFrame* d_tab, const RegionsSource& src,
+                    uint32_t rw, uint32_t rh, uint8_t* d_px, uint32_t* d_status, hipStream_t s) {
+    const Geometry& g = k->g;
+    uint64_t base = 0;  // the class's first slice in the staged arrays
+    for (uint32_t i = 0; i < n_classes; ++i) {
+        const Geometry& sub = classes[i].sub;
+        const RegionsFrame* c_tab = d_tab + classes[i].first;
+        const uint32_t* len = src.full_len ? k->d_region_len : src.staged_len + base;
+        const uint64_t* off = src.full_len ? k->d_region_off : src.staged_off + base;
+        base += sub.n_slices;
+        {
+            Timed t(k, s, 7);
+            if (int rc = next_state_generation(k, s, slices_need_state_tables(sub))) return rc;
+        }
+        {
+            Timed t(k, s, 4);
+            if (src.full_len)
+                HIP_TRY(launch_regions_index(g, sub, c_tab, src.full_len, k->d_group_off, k->d_region_len, k->d_region_off, s));
+            HIP_TRY(launch_stage_region_streams(sub, src.payload, src.payload_bytes, len, off, k->d_scratch, d_status, s));
+        }
+        {
+            Timed t(k, s, 5);
+            const bool cache = use_bank_cache(k, sub);
+            HIP_TRY(launch_decode_slices(sub, k->d_scratch, len, k->d_states, k->state_generation, static_cast<int16_t*>(k->d_lane_order), d_status,
+                                         k->d_counters, cache, s));
+            if (cache) queue_feedback(k, s);
+        }
+        {
+            Timed t(k, s, 6);
+            if (model_is_fused(sub)) {
+                HIP_TRY(launch_model_rows_inv_crops(sub, static_cast<const int16_t*>(k->d_lane_order), d_px, c_tab, rw, rh, s));
+            } else {
+                HIP_TRY(launch_from_lane_order_i16(sub, static_cast<const int16_t*>(k->d_lane_order), static_cast<int16_t*>(k->d_sym_or_rec), s));
+                HIP_TRY(launch_model_inv_crops(sub, static_cast<const int16_t*>(k->d_sym_or_rec), d_px, c_tab, rw, rh, s));
+            }
+        }
+    }
+    return LLCOMP_MI_OK;
+}
+
 }  // namespace
 
 namespace llcomp_mi {
@@ -352,12 +469,13 @@ void codec_release(llcomp_mi_codec* k) {
     dev_free(k->d_region_len, k->done);
     dev_free(k->d_region_off, k->done);
     dev_free(k->d_regions, k->done);
-    if (k->h_regions) {
-        // (a table copy may still be queued on a caller's stream: it must not read freed memory)
-        for (uint32_t i = 0; i < llcomp_mi_codec::kRegionsRing; ++i)
-            if (k->regions_ev_live[i] && k->regions_ev[i] && hipEventQuery(k->regions_ev[i]) == hipErrorNotReady) (void)hipEventSynchronize(k->regions_ev[i]);
+    dev_free(k->d_stage, k->done);
+    for (uint32_t i = 0; i < llcomp_mi_codec::kRegionsRing; ++i) {
+        if (!k->h_regions[i]) continue;
+        // (a copy out of the slot may still be queued on a caller's stream: it must not read freed memory)
+        if (k->regions_ev_live[i] && k->regions_ev[i] && hipEventQuery(k->regions_ev[i]) == hipErrorNotReady) (void)hipEventSynchronize(k->regions_ev[i]);
         (void)hipGetLastError();
-        (void)hipHostFree(k->h_regions);
+        (void)hipHostFree(k->h_regions[i]);
     }
     for (auto& ev : k->regions_ev) if (ev) (void)hipEventDestroy(ev);
     dev_free(k->d_snap_sorted, k->done);
@@ -474,8 +592,8 @@ int llcomp_mi::codec_create(llcomp_mi_codec** out, int32_t device, uint32_t fram
     // own family keeps its states on chip (region_may_need_states)
     const uint64_t b_region = uint64_t(g.n_slices) * 12 +
                               (!k->need_states && !rows_mode(g) ? (uint64_t(lane_groups(g)) * kContexts << g.lane_shift) * 8 : 0);
-    // ... plus the per-frame table of a regions decode
-    const uint64_t b_regions = uint64_t(frames) * sizeof(RegionsFrame);
+    // ... plus the per-frame table of a regions decode, and the staging buffer of a host-staged one (its upper bound)
+    const uint64_t b_regions = uint64_t(frames) * sizeof(RegionsFrame) + stage_bound(g);
     k->workspace_bytes = b_sym + b_lanes + b_states + b_scratch + b_off + 8 + snap_el * (snapshot_chunked(g) ? 28 : 18) + b_region + b_regions;
     const bool ok = dev_alloc(&k->d_sym_or_rec, b_sym) == hipSuccess && dev_alloc(&k->d_lane_order, b_lanes) == hipSuccess &&
                     dev_alloc(reinterpret_cast<void**>(&k->d_scratch), b_scratch) == hipSuccess &&
@@ -772,56 +890,72 @@ int llcomp_mi_codec_decode_regions(llcomp_mi_codec* k, const void* d_payload, ui
     if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
     if (int rc = ensure_region_arrays(k)) return rc;
     if (int rc = ensure_regions_table(k)) return rc;
-    // the slot's previous copy has to have left it (it was queued four calls ago: this waits only when the caller runs that far ahead)
-    const uint32_t slot = k->regions_slot;
-    if (k->regions_ev_live[slot]) {
-        if (hipEventSynchronize(k->regions_ev[slot]) != hipSuccess) return LLCOMP_MI_HIP_ERROR;
-        k->regions_ev_live[slot] = false;
-    }
-    RegionsFrame* h_tab = k->h_regions + size_t(slot) * g.frames;
-    std::memcpy(h_tab, tab.data(), tab.size() * sizeof(RegionsFrame));
+    uint32_t slot = 0;
+    if (int rc = regions_slot_take(k, tab.size() * sizeof(RegionsFrame), 0, slot)) return rc;
+    std::memcpy(k->h_regions[slot], tab.data(), tab.size() * sizeof(RegionsFrame));
     hipStream_t s = static_cast<hipStream_t>(stream);
     DoneGuard done_guard{k, s};
     HIP_TRY(hipMemsetAsync(d_status, 0, 4, s));
     {
         Timed t(k, s, 4);
-        HIP_TRY(hipMemcpyAsync(k->d_regions, h_tab, tab.size() * sizeof(RegionsFrame), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipEventRecord(k->regions_ev[slot], s));
-        k->regions_ev_live[slot] = true;
-        k->regions_slot = (slot + 1) % llcomp_mi_codec::kRegionsRing;
+        HIP_TRY(hipMemcpyAsync(k->d_regions, k->h_regions[slot], tab.size() * sizeof(RegionsFrame), hipMemcpyHostToDevice, s));
+        if (int rc = regions_slot_queued(k, slot, s)) return rc;
         HIP_TRY(launch_group_sums(g, static_cast<const uint32_t*>(d_slice_len), k->d_group_off, s));
         HIP_TRY(launch_scan_groups(g, k->d_group_off, k->d_total_tmp, s));
     }
-    for (uint32_t i = 0; i < n_classes; ++i) {
-        const Geometry& sub = classes[i].sub;
-        const RegionsFrame* d_tab = k->d_regions + classes[i].first;
-        {
-            Timed t(k, s, 7);
-            if (int rc = next_state_generation(k, s, slices_need_state_tables(sub))) return rc;
-        }
-        {
-            Timed t(k, s, 4);
-            HIP_TRY(launch_regions_index(g, sub, d_tab, static_cast<const uint32_t*>(d_slice_len), k->d_group_off, k->d_region_len, k->d_region_off, s));
-            HIP_TRY(launch_stage_region_streams(sub, static_cast<const uint8_t*>(d_payload), payload_bytes, k->d_region_len, k->d_region_off,
-                                                k->d_scratch, static_cast<uint32_t*>(d_status), s));
-        }
-        {
-            Timed t(k, s, 5);
-            const bool cache = use_bank_cache(k, sub);
-            HIP_TRY(launch_decode_slices(sub, k->d_scratch, k->d_region_len, k->d_states, k->state_generation, static_cast<int16_t*>(k->d_lane_order),
-                                         static_cast<uint32_t*>(d_status), k->d_counters, cache, s));
-            if (cache) queue_feedback(k, s);
-        }
-        {
-            Timed t(k, s, 6);
-            if (model_is_fused(sub)) {
-                HIP_TRY(launch_model_rows_inv_crops(sub, static_cast<const int16_t*>(k->d_lane_order), static_cast<uint8_t*>(d_px), d_tab, rw, rh, s));
-            } else {
-                HIP_TRY(launch_from_lane_order_i16(sub, static_cast<const int16_t*>(k->d_lane_order), static_cast<int16_t*>(k->d_sym_or_rec), s));
-                HIP_TRY(launch_model_inv_crops(sub, static_cast<const int16_t*>(k->d_sym_or_rec), static_cast<uint8_t*>(d_px), d_tab, rw, rh, s));
-            }
-        }
+    const RegionsSource src{static_cast<const uint8_t*>(d_payload), payload_bytes, static_cast<const uint32_t*>(d_slice_len), nullptr, nullptr};
+    if (int rc = regions_classes(k, classes, n_classes, k->d_regions, src, rw, rh, static_cast<uint8_t*>(d_px), static_cast<uint32_t*>(d_status), s))
+        return rc;
+    ++k->n_decode;
+    return LLCOMP_MI_OK;
+}
+
+// Regions decode of host containers: the gather (container.cpp) writes the table, the window slices' lengths and offsets and their
+// payload bytes into one slot of the pinned ring; ONE copy takes it to d_stage, and the classes run as above with their slices' lengths
+// and offsets read straight from it (no group sums: the offsets are the host's).  Every error of the gather comes before anything is
+// queued.
+int llcomp_mi_codec_decode_regions_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens, const uint32_t* xy, uint32_t rw,
+                                        uint32_t rh, void* d_px, void* d_status, void* stream) {
+    if (!k || !data || !lens || !d_px || !d_status || !xy) return LLCOMP_MI_BAD_ARGS;
+    const Geometry& g = k->g;
+    RegionsGather p;
+    if (int rc = regions_gather_plan(data, lens, g.frames, xy, rw, rh, p)) return rc;
+    // the containers have to be of the codec's shape, tiling, planar setting and model
+    const Geometry& cg = p.g;
+    if (cg.w != g.w || cg.h != g.h || cg.c != g.c || cg.tile_w != g.tile_w || cg.tile_h != g.tile_h || cg.planar != g.planar ||
+        (cg.flags & kGeoSmallModel) != (g.flags & kGeoSmallModel))
+        return LLCOMP_MI_BAD_ARGS;
+    std::vector<RegionsFrame> tab(g.frames);
+    RegionsClass classes[kRegionsClasses];
+    uint32_t n_classes = 0;
+    if (int rc = regions_setup(k, xy, rw, rh, tab.data(), classes, n_classes)) return rc;
+    uint64_t sub_slices = 0;  // (the gather's order is the table's: class by class, and a class's slices are its sub-geometry's)
+    for (uint32_t i = 0; i < n_classes; ++i) sub_slices += classes[i].sub.n_slices;
+    if (sub_slices != p.n_slices) return LLCOMP_MI_HIP_ERROR;
+    const StageLayout lay(g.frames, p.n_slices, p.payload_bytes);
+    DeviceGuard guard(k->device);
+    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
+    if (int rc = ensure_regions_table(k)) return rc;
+    if (int rc = ensure_stage(k, lay.bytes)) return rc;
+    uint32_t slot = 0;
+    if (int rc = regions_slot_take(k, lay.bytes, stage_bound(g), slot)) return rc;
+    uint8_t* h = k->h_regions[slot];
+    std::memcpy(h, tab.data(), tab.size() * sizeof(RegionsFrame));
+    regions_gather_copy(p, data, h + lay.pay_at, reinterpret_cast<uint32_t*>(h + lay.len_at), reinterpret_cast<uint64_t*>(h + lay.off_at));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DoneGuard done_guard{k, s};
+    HIP_TRY(hipMemsetAsync(d_status, 0, 4, s));
+    {
+        Timed t(k, s, 4);
+        HIP_TRY(hipMemcpyAsync(k->d_stage, h, lay.bytes, hipMemcpyHostToDevice, s));
+        if (int rc = regions_slot_queued(k, slot, s)) return rc;
     }
+    k->host_counters[LLCOMP_MI_CTR_HOST_STAGED_BYTES] += p.payload_bytes;
+    const RegionsSource src{k->d_stage + lay.pay_at, p.payload_bytes, nullptr, reinterpret_cast<const uint32_t*>(k->d_stage + lay.len_at),
+                            reinterpret_cast<const uint64_t*>(k->d_stage + lay.off_at)};
+    if (int rc = regions_classes(k, classes, n_classes, reinterpret_cast<const RegionsFrame*>(k->d_stage), src, rw, rh, static_cast<uint8_t*>(d_px),
+                                 static_cast<uint32_t*>(d_status), s))
+        return rc;
     ++k->n_decode;
     return LLCOMP_MI_OK;
 }

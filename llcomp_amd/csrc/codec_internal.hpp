@@ -35,14 +35,20 @@ struct llcomp_mi_codec {
     uint64_t* d_region_off = nullptr;
     llcomp_mi::Tuning tune{};        // the hooks the geometry was made with (a region's sub-geometry is made with the same)
     // regions decode (llcomp_mi_codec_decode_regions): the per-frame table (RegionsFrame[frames], class by class) in HBM, and the
-    // pinned staging it is copied from -- a ring of kRegionsRing tables, each reused only after the event behind ITS last copy
-    // (the copy of a call sits in the stream behind that call's predecessors: one slot would make every call wait for the last one)
+    // pinned staging it is copied from -- a ring of kRegionsRing slots, each reused only after the event behind ITS last copy
+    // (the copy of a call sits in the stream behind that call's predecessors: one slot would make every call wait for the last one).
+    // A slot holds one table; a host-staged call (llcomp_mi_codec_decode_regions_host) grows the slot it uses to hold all it stages.
     static constexpr uint32_t kRegionsRing = 4;
     llcomp_mi::RegionsFrame* d_regions = nullptr;
-    llcomp_mi::RegionsFrame* h_regions = nullptr;  // pinned, kRegionsRing * frames
+    uint8_t* h_regions[kRegionsRing] = {};       // pinned, h_regions_cap[i] bytes each (at least frames table entries)
+    uint64_t h_regions_cap[kRegionsRing] = {};
     hipEvent_t regions_ev[kRegionsRing] = {};
     bool regions_ev_live[kRegionsRing] = {};     // the slot's event has been recorded (a copy from it may be queued)
     uint32_t regions_slot = 0;                   // the slot the next call uses
+    // host-staged regions decode: where a slot's one copy lands -- [RegionsFrame table][u32 window lengths][u64 offsets][payload]
+    // (codec.hip: StageLayout); grown geometrically up to stage_bound(g), allocated by the first such call
+    uint8_t* d_stage = nullptr;
+    uint64_t stage_cap = 0;
     void* d_snap_sorted = nullptr;   // snapshot pass of the 2-D encoder (snapshot.hpp): banks in context-sorted order,
     void* d_snap_banks = nullptr;    // banks in stream order, residuals in stream order; null unless snapshot_mode(g)
     void* d_snap_res = nullptr;

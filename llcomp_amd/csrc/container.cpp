@@ -25,6 +25,87 @@ void write_sliced_header(uint8_t* o, const Geometry& g) {
     put_u32le(o + 20, g.slices_per_frame);
 }
 
+int regions_gather_plan(const uint8_t* const* data, const size_t* lens, uint32_t n, const uint32_t* xy, uint32_t rw, uint32_t rh,
+                        RegionsGather& p) {
+    p = RegionsGather{};
+    if (!data || !lens || !xy || !n) return LLCOMP_MI_BAD_ARGS;
+    llcomp_mi_info i0{};
+    std::vector<uint32_t> cls(n), first_run(n + 1);
+    std::vector<GatherRun> runs;  // frame order
+    uint32_t limit = 0, seen = 0;
+    for (uint32_t f = 0; f < n; ++f) {
+        if (!data[f]) return LLCOMP_MI_BAD_ARGS;
+        llcomp_mi_info a;
+        if (int rc = llcomp_mi_probe(data[f], lens[f], &a)) return rc;
+        if (a.format != LLCOMP_MI_FORMAT_SLICED) return LLCOMP_MI_BAD_ARGS;
+        if (f == 0) {
+            i0 = a;
+            if (!make_geometry(p.g, 1, a.width, a.height, a.channels, a.tile_w, a.tile_h, a.planar, Tuning{}, a.small_model != 0))
+                return LLCOMP_MI_BAD_ARGS;
+            limit = p.g.slice_cap - 16;  // the SLICED per-entry limit (LLCOMP_MI_TRUNCATED; the decoders' own check)
+        } else if (a.width != i0.width || a.height != i0.height || a.channels != i0.channels || a.tile_w != i0.tile_w ||
+                   a.tile_h != i0.tile_h || a.planar != i0.planar || a.small_model != i0.small_model) {
+            return LLCOMP_MI_BAD_ARGS;
+        }
+        RegionBox win;
+        if (!regions_window(a.width, a.height, a.tile_w, a.tile_h, xy[2 * f], xy[2 * f + 1], rw, rh, win, cls[f])) return LLCOMP_MI_BAD_ARGS;
+        seen |= 1u << cls[f];
+        // one window tile row = (wx1 - wx0) * planes consecutive slices; the table is summed up to the end of the last one only
+        const uint32_t planes = a.planar ? a.channels : 1u, per_row = (win.tx1 - win.tx0) * planes;
+        const uint8_t* tab = data[f] + a.table_offset;
+        first_run[f] = uint32_t(runs.size());
+        uint64_t off = 0;
+        uint32_t s = 0;
+        for (uint32_t ty = win.ty0; ty < win.ty1; ++ty) {
+            const uint32_t first = (ty * p.g.ntx + win.tx0) * planes;
+            for (; s < first; ++s) off += get_u32le(tab + 4ull * s);
+            uint64_t bytes = 0;
+            for (uint32_t j = 0; j < per_row; ++j, ++s) {
+                const uint32_t l = get_u32le(tab + 4ull * s);
+                if (l > limit) return LLCOMP_MI_TRUNCATED;
+                bytes += l;
+            }
+            if (a.payload_offset + off + bytes > lens[f]) return LLCOMP_MI_TRUNCATED;
+            runs.push_back(GatherRun{f, first, per_row, a.payload_offset + off, bytes});
+            off += bytes;
+        }
+    }
+    first_run[n] = uint32_t(runs.size());
+    uint64_t slices = 0;
+    p.runs.reserve(runs.size());
+    for (uint32_t c = 0; c < kRegionsClasses; ++c)
+        for (uint32_t f = 0; f < n; ++f)
+            if (cls[f] == c)
+                for (uint32_t r = first_run[f]; r < first_run[f + 1]; ++r) {
+                    p.runs.push_back(runs[r]);
+                    slices += runs[r].count;
+                    p.payload_bytes += runs[r].bytes;
+                }
+    if (slices >= (1ull << 31)) return LLCOMP_MI_OUT_OF_RANGE;
+    p.n_slices = uint32_t(slices);
+    p.n_classes = uint32_t(__builtin_popcount(seen));
+    return LLCOMP_MI_OK;
+}
+
+void regions_gather_copy(const RegionsGather& p, const uint8_t* const* data, uint8_t* payload, uint32_t* slice_len, uint64_t* slice_off) {
+    uint64_t at = 0;
+    uint32_t k = 0;
+    for (const GatherRun& r : p.runs) {
+        const uint8_t* tab = data[r.frame] + LLCOMP_MI_SLICED_HEADER_BYTES + 4ull * r.first;
+        for (uint32_t j = 0; j < r.count; ++j) slice_len[k + j] = get_u32le(tab + 4ull * j);
+        if (slice_off) {
+            uint64_t o = at;
+            for (uint32_t j = 0; j < r.count; ++j) {
+                slice_off[k + j] = o;
+                o += slice_len[k + j];
+            }
+        }
+        if (r.bytes) std::memcpy(payload + at, data[r.frame] + r.src, r.bytes);
+        at += r.bytes;
+        k += r.count;
+    }
+}
+
 }  // namespace llcomp_mi
 
 using namespace llcomp_mi;
@@ -130,6 +211,23 @@ int llcomp_mi_regions_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, 
         }
     }
     *n_classes = uint32_t(__builtin_popcount(seen));
+    return LLCOMP_MI_OK;
+}
+
+int llcomp_mi_regions_gather(const uint8_t* const* data, const size_t* lens, uint32_t n, const uint32_t* xy, uint32_t rw, uint32_t rh,
+                             uint8_t* payload, uint64_t payload_cap, uint32_t* slice_len, uint32_t len_cap, uint64_t* payload_bytes,
+                             uint32_t* n_slices, uint32_t* n_classes) {
+    if (!payload_bytes || !n_slices || !n_classes) return LLCOMP_MI_BAD_ARGS;
+    *payload_bytes = 0;
+    *n_slices = *n_classes = 0;
+    RegionsGather p;
+    if (int rc = regions_gather_plan(data, lens, n, xy, rw, rh, p)) return rc;
+    *payload_bytes = p.payload_bytes;
+    *n_slices = p.n_slices;
+    *n_classes = p.n_classes;
+    if (!payload || !slice_len) return LLCOMP_MI_OK;
+    if (payload_cap < p.payload_bytes || len_cap < p.n_slices) return LLCOMP_MI_OUTPUT_OVERFLOW;
+    regions_gather_copy(p, data, payload, slice_len, nullptr);
     return LLCOMP_MI_OK;
 }
 

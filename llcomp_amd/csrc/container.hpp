@@ -3,6 +3,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 #include "geometry.hpp"
 
@@ -17,5 +18,26 @@ inline uint32_t get_u32le(const uint8_t* p) {
 
 void write_legacy_header(uint8_t* out6, uint32_t w, uint32_t h, uint32_t c);
 void write_sliced_header(uint8_t* out24, const Geometry& g);  // g.frames must be 1
+
+// Regions gather (llcomp_mi_regions_gather, and the host path of llcomp_mi_codec_decode_regions_host): which bytes of which container a
+// regions decode needs.  A run is one window tile row of one frame: `count` consecutive table entries from entry `first` of container
+// `frame`, and the payload bytes [src, src + bytes) of that container (offsets from its first byte).  Runs are in output order: class by
+// class, frame order inside a class, tile rows top down.
+struct GatherRun {
+    uint32_t frame, first, count;
+    uint64_t src, bytes;
+};
+struct RegionsGather {
+    Geometry g{};                 // container 0's geometry, one frame
+    uint32_t n_classes = 0, n_slices = 0;
+    uint64_t payload_bytes = 0;
+    std::vector<GatherRun> runs;
+};
+// every check of llcomp_mi_regions_gather; nothing is copied
+int regions_gather_plan(const uint8_t* const* data, const size_t* lens, uint32_t n, const uint32_t* xy, uint32_t rw, uint32_t rh,
+                        RegionsGather& p);
+// the planned bytes: payload (p.payload_bytes), slice_len (p.n_slices entries) and, when slice_off is not null, the offset of every
+// slice in `payload`
+void regions_gather_copy(const RegionsGather& p, const uint8_t* const* data, uint8_t* payload, uint32_t* slice_len, uint64_t* slice_off);
 
 }  // namespace llcomp_mi

@@ -7,6 +7,7 @@
 // launches and the link larger copies), every frame its own SLICED container:
 //   encode  H2D frame -> kernels -> D2H {payload bytes, status} (16 B, event e1) -> D2H container of the EXACT size (event e2)
 //   decode  H2D container -> kernels -> D2H frame + status (event e2)
+//   regions H2D the windows' bytes of the containers (llcomp_mi_codec_decode_regions_host) -> kernels -> D2H crops + status (event e2)
 // The size of a container is known on the GPU only.  Nobody waits for it at submit time: the 16-byte mailbox copy is
 // queued behind the kernels and whoever enters the library next (submit, wait or poll) looks at the events of the
 // jobs in flight ("pump") and queues the container copies whose size has arrived; wait() blocks on the EVENT that comes
@@ -355,6 +356,36 @@ int llcomp_mi_stream_submit_decode_batch(llcomp_mi_stream* s, const uint8_t* con
     return LLCOMP_MI_OK;
 }
 
+// A job of crops: the lane's codec stages the windows of the job's containers from the host (read during this call only) and decodes
+// them on the lane's stream; the status and the crops follow into the slot's pinned output (fpj * rw * rh * c <= raw * fpj bytes).
+int llcomp_mi_stream_submit_decode_regions(llcomp_mi_stream* s, const uint8_t* const* data, const size_t* lens, const uint32_t* xy, uint32_t rw,
+                                           uint32_t rh, uint64_t tag) {
+    if (!s || !data || !lens || !xy) return LLCOMP_MI_BAD_ARGS;
+    if (!s->subs.empty())
+        return deal(s, [&](llcomp_mi_stream* sub) { return llcomp_mi_stream_submit_decode_regions(sub, data, lens, xy, rw, rh, tag); });
+    std::lock_guard<std::mutex> lock(s->mu);
+    DeviceGuard guard(s->device);
+    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
+    pump(s);
+    const int i = free_slot(s);
+    if (i < 0) return LLCOMP_MI_BUSY;
+    Slot& sl = s->slots[size_t(i)];
+    HostLane* l = sl.lane;
+    // (a gather error, a rectangle outside the image among them, returns before anything is queued: the slot stays free)
+    if (int rc = llcomp_mi_codec_decode_regions_host(l->k, data, lens, xy, rw, rh, l->d_px, l->d_meta + 1, l->stream)) return drained(l, rc);
+    const uint64_t bytes = uint64_t(rw) * rh * s->c * s->fpj;
+    if (hipMemcpyAsync(l->h_meta, l->d_meta, 16, hipMemcpyDeviceToHost, l->stream) != hipSuccess ||
+        hipMemcpyAsync(sl.h_out, l->d_px, bytes, hipMemcpyDeviceToHost, l->stream) != hipSuccess || hipEventRecord(sl.e2, l->stream) != hipSuccess)
+        return drained(l, LLCOMP_MI_HIP_ERROR);
+    sl.state = kCopying;
+    sl.kind = LLCOMP_MI_JOB_DECODE_REGIONS;
+    sl.tag = tag;
+    sl.status = LLCOMP_MI_OK;
+    sl.out_len = bytes;
+    s->fifo.push_back(uint32_t(i));
+    return LLCOMP_MI_OK;
+}
+
 uint32_t llcomp_mi_stream_frames_per_job(const llcomp_mi_stream* s) { return s ? s->fpj : 0; }
 
 int llcomp_mi_stream_result_part(llcomp_mi_stream* s, uint32_t slot, uint32_t frame, const uint8_t** data, uint64_t* len) {
@@ -367,6 +398,9 @@ int llcomp_mi_stream_result_part(llcomp_mi_stream* s, uint32_t slot, uint32_t fr
     if (sl.kind == LLCOMP_MI_JOB_ENCODE) {
         *data = sl.h_out + sl.part_off[frame];
         *len = sl.part_len[frame];
+    } else if (sl.kind == LLCOMP_MI_JOB_DECODE_REGIONS) {
+        *len = sl.out_len / s->fpj;
+        *data = sl.h_out + *len * frame;
     } else {
         *data = sl.h_out + s->raw * frame;
         *len = s->raw;
@@ -476,7 +510,8 @@ int llcomp_mi_stream_wait(llcomp_mi_stream* s, llcomp_mi_stream_result* r) {
             if (owner == &sl) break;
         }
     }
-    if (sl.state == kCopying && sl.kind == LLCOMP_MI_JOB_DECODE) sl.status = status_from_bits(uint32_t(sl.lane->h_meta[1]));
+    if (sl.state == kCopying && (sl.kind == LLCOMP_MI_JOB_DECODE || sl.kind == LLCOMP_MI_JOB_DECODE_REGIONS))
+        sl.status = status_from_bits(uint32_t(sl.lane->h_meta[1]));
     s->fifo.pop_front();
     sl.state = kHeld;
     ++s->jobs_done;
