@@ -2,16 +2,21 @@
 """bench.py -- BASELINE.json's metric: encode+decode MPix/s on 4K RGB8, bit-exact, with achieved HBM GB/s vs peak.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--content g3|g2|mid|nat] [--tile-w TW --tile-h TH] [--interleaved]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full]
 
 N = 1 (default): BASELINE config 3.  A "step" = one pass of the hot path over one batch: F frames of 3840x2160 RGB8 already
 resident in HBM are encoded into the sliced container payload (stage A -> k_encode_slices -> scan + pack) and decoded back
 (stage streams -> k_decode_slices -> stage A inverse); the round trip is verified bit-exact outside the timed region.  The
 frames of a step are split over --streams independent pipelines (codec object + HIP stream each) so that the memory-bound
 kernels of one overlap the issue-bound slice kernels of another.  value = pixels coded / wall time, i.e.
-w*h / (t_enc + t_dec) per frame.  `also` = the other workloads of DESIGN.md section 7, a few steps each, measured in the
-same run: other contents, 2-D tiles, one-frame latency, batched legacy streams, the PCIe-inclusive C5 stream, and the C4
-workload on one GPU (the N = 1 point of the strong-scaling curve).
+w*h / (t_enc + t_dec) per frame.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, write --dump-outputs, print the line.
+--full adds everything else, in the same process after the headline: `roofline.isolated` (the launches once more with one
+pipeline at a time), `golden_pin` (frame 0's container against the real reference's), `also` = the other workloads of
+DESIGN.md section 7, a few steps each: other contents, 2-D tiles, one-frame latency, batched legacy streams, the PCIe-inclusive
+C5 stream, and the C4 workload on one GPU (the N = 1 point of the strong-scaling curve); the CPU legs (`cpu_baseline`); and
+`full_model`.  --no-isolated, --no-also, --also-only and --no-cpu-baseline narrow what --full adds.
 
 --dump-outputs DIR (N = 1): after the timed steps, the arrays the headline's LAST timed step handed its caller go to DIR/<name>.npy:
 payload_bytes (per pipeline, float64), payload and slice_lengths (the encoder's output, all pipelines in order), decoded (the
@@ -31,10 +36,10 @@ exchange is inside the timed region and container 0 is compared with the one-pie
 measured in the same run (rank 0 codes the same batch through a one-rank subgroup first): `one_gpu_value`,
 `scaling_vs_one_gpu`, `ranks_seen`.  `c5_replica_pcie` = config 5 in replica mode.  `c4_inprocess_devices` = config 4 from ONE
 process through the C ABI's device list (llcomp_mi_opts.devices / llcomp_mi_decode_into_devices, host buffers in, host buffers out):
-rank 0 alone drives all N GPUs while the other ranks wait on the store (no collective, N PCIe links).  The secondary legs sit behind a
-watchdog: if one of them fails or hangs, the line still goes out with the headline and says which leg was lost.
+rank 0 alone drives all N GPUs while the other ranks wait on the store (no collective, N PCIe links).  These three secondary legs run
+with --full only, behind a watchdog: if one of them fails or hangs, the line still goes out with the headline and says which leg was lost.
 
-Key order of the line: the full-model figures (`full_model`, then `value_full_model`) are the LAST keys, behind `also` and the CPU
+Key order of the --full line: the full-model figures (`full_model`, then `value_full_model`) are the LAST keys, behind `also` and the CPU
 legs, so that a record which keeps only the tail of the line still shows the real-model number.
 
 LLCOMP_BENCH_STANDIN=<module> (tests/test_bench_world8.py only): the named module -- it lives under tests/, nothing of it is in the
@@ -941,16 +946,19 @@ def main():
     ap.add_argument("--tile-h", type=int, default=1)
     ap.add_argument("--interleaved", action="store_true", help="channels interleaved in one slice instead of per-channel planes")
     ap.add_argument("--streams", type=int, default=3, help="split the frames of a step over this many HIP streams (codec objects)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-isolated", action="store_true", help="skip the extra one-pipeline-at-a-time launches behind the timed region (profiler runs)")
-    ap.add_argument("--no-also", action="store_true", help="only the headline workload (profiler runs, sweeps)")
-    ap.add_argument("--also-only", default="", help="comma-separated subset of the `also` legs: full,contents,tiles,latency,legacy,c5,c4,inproc,c2 (profiling)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline too (docstring): isolated launches, golden pin, the `also` legs, "
+                         "the CPU legs, full_model; at N > 1 the c4_sharded, c5_replica_pcie and c4_inprocess_devices legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU legs")
+    ap.add_argument("--no-isolated", action="store_true", help="--full without the extra one-pipeline-at-a-time launches behind the timed region")
+    ap.add_argument("--no-also", action="store_true", help="--full without the `also` legs and full_model")
+    ap.add_argument("--also-only", default="", help="--full: comma-separated subset of the `also` legs: full,contents,tiles,latency,legacy,c5,c4,inproc,c2 (profiling)")
     ap.add_argument("--c4-parts", type=int, default=0, help="part batches (ShardedCodec objects on their own HIP streams) of the config-4 step; 0 = three where the image count allows")
     ap.add_argument("--c4-images", type=int, default=24, help="8192x8192 images per step of the sharded (config 4) workload (fixed total: strong scaling)")
     ap.add_argument("--c4-size", type=int, default=8192, help="side of the square config-4 images (8192 = BASELINE; smaller only for rehearsals)")
     ap.add_argument("--c4-tile-w", type=int, default=512)
     ap.add_argument("--c4-tile-h", type=int, default=1)
-    ap.add_argument("--legs-timeout", type=float, default=300.0, help="N > 1: seconds the secondary legs (config 4, config 5) may take before the line goes out without them")
+    ap.add_argument("--legs-timeout", type=float, default=300.0, help="N > 1 with --full: seconds the secondary legs (config 4, config 5) may take before the line goes out without them")
     ap.add_argument("--rehearse-one-gpu", action="store_true",
                     help="rehearsal of the N > 1 code path on a one-GPU box: all ranks use cuda:0 and exchange over gloo (RCCL refuses two ranks on one device); the numbers mean nothing")
     ap.add_argument("--dump-outputs", metavar="DIR", default="",
@@ -961,6 +969,8 @@ def main():
         ap.error("--steps must be at least 1")
     if args.dump_outputs and args.gpus > 1:
         ap.error("--dump-outputs: N = 1 only")
+    if not args.full:  # a plain run: the headline alone
+        args.no_cpu_baseline = args.no_isolated = args.no_also = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args.gpus)  # (does not return)
@@ -991,7 +1001,7 @@ def main():
             raise SystemExit(f"rank {rank}: no GPU {local_rank} on this node ({torch.cuda.device_count()} visible)")
         torch.cuda.set_device(local_rank)
     DEV = Hooks.device
-    if world == 1:  # the sharded workload runs under torch.distributed at every N, so the N = 1 point is the same code
+    if world == 1 and args.full:  # the sharded workload runs under torch.distributed at every N, so the N = 1 point is the same code
         import socket
 
         sk = socket.socket()
@@ -999,14 +1009,15 @@ def main():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", str(sk.getsockname()[1]))
         sk.close()
-    with quiet_stdout():
-        if args.rehearse_one_gpu or Hooks.backend == "gloo":
-            dist.init_process_group("gloo", rank=rank, world_size=world)
-        else:
-            dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
-        warm = torch.zeros(1, device=DEV)
-        dist.all_reduce(warm)
-        Hooks.sync()
+    if world > 1 or args.full:  # (a plain N = 1 run has no collective: no process group)
+        with quiet_stdout():
+            if args.rehearse_one_gpu or Hooks.backend == "gloo":
+                dist.init_process_group("gloo", rank=rank, world_size=world)
+            else:
+                dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
+            warm = torch.zeros(1, device=DEV)
+            dist.all_reduce(warm)
+            Hooks.sync()
     barrier = dist.barrier if world > 1 else None
 
     planar = not args.interleaved
@@ -1036,6 +1047,11 @@ def main():
             res["collective_backend"] = dist.get_backend()
         if dist.get_world_size() != args.gpus:  # (cannot happen behind the check above; a line from fewer ranks must not look green)
             raise SystemExit(4)
+        if not args.full:
+            if rank == 0:
+                print(json.dumps(res), flush=True)
+            dist.destroy_process_group()
+            return
         dog = Watchdog(rank, res)
         dog.arm(args.legs_timeout, "c4_sharded + c5_replica_pcie + c4_inprocess_devices")
         t_legs = time.perf_counter()
@@ -1179,18 +1195,19 @@ def main():
                                "bytes": sum(int(a.nbytes) for a in dump.values())}
     # byte-level pin of the measured workload: frame 0 of the default batch is the golden vector's image (std::mt19937(1234)),
     # its container length must be the one the real reference's per-slice streams add up to (tests/golden, also hashed in
-    # tests/test_gpu_stream.py::test_c3_4k_bench_slicing_golden)
-    try:
-        gold = [v for v in json.load(open(os.path.join(ROOT, "tests", "golden", "slice_payloads.json")))["vectors"]
-                if (v["gen"], v["w"], v["tile_w"], v["tile_h"], v["planar"]) == (args.content, W4K, args.tile_w, args.tile_h, planar)]
-        if gold and args.content in ("g3", "g2"):  # frame 0 of these two IS the golden vector's image (mid / nat use other seeds here)
-            res["golden_pin"] = {"frame0_container_bytes": m["frame0_container"], "reference_bytes": gold[0]["container_len"],
-                                 "frame0_container_fnv1a64": m["frame0_fnv"], "reference_fnv1a64": gold[0]["container_fnv1a64"],
-                                 "match": m["frame0_container"] == gold[0]["container_len"] and m["frame0_fnv"] == gold[0]["container_fnv1a64"],
-                                 "source": "tests/golden/slice_payloads.json (container assembled from the real reference's per-slice streams)"}
-            assert res["golden_pin"]["match"], "frame 0's container differs from the reference's (length or FNV-1a-64)"
-    except OSError:
-        pass
+    # tests/test_gpu_stream.py::test_c3_4k_bench_slicing_golden); --full only
+    if args.full:
+        try:
+            gold = [v for v in json.load(open(os.path.join(ROOT, "tests", "golden", "slice_payloads.json")))["vectors"]
+                    if (v["gen"], v["w"], v["tile_w"], v["tile_h"], v["planar"]) == (args.content, W4K, args.tile_w, args.tile_h, planar)]
+            if gold and args.content in ("g3", "g2"):  # frame 0 of these two IS the golden vector's image (mid / nat use other seeds here)
+                res["golden_pin"] = {"frame0_container_bytes": m["frame0_container"], "reference_bytes": gold[0]["container_len"],
+                                     "frame0_container_fnv1a64": m["frame0_fnv"], "reference_fnv1a64": gold[0]["container_fnv1a64"],
+                                     "match": m["frame0_container"] == gold[0]["container_len"] and m["frame0_fnv"] == gold[0]["container_fnv1a64"],
+                                     "source": "tests/golden/slice_payloads.json (container assembled from the real reference's per-slice streams)"}
+                assert res["golden_pin"]["match"], "frame 0's container differs from the reference's (length or FNV-1a-64)"
+        except OSError:
+            pass
     full_box = {}
     if not args.no_also:
         also = {}
@@ -1353,7 +1370,8 @@ def main():
             if k in full_box:
                 res[k] = full_box[k]
     print(json.dumps(res), flush=True)
-    dist.destroy_process_group()
+    if dist.is_initialized():
+        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -166,7 +166,7 @@ def test_bench_line_from_four_ranks_rehearsed_on_one_gpu():
 
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--rehearse-one-gpu", "--steps", "2", "--warmup", "1",
-                        "--frames", "4", "--streams", "2", "--c4-images", "4", "--no-cpu-baseline", "--legs-timeout", "400"],
+                        "--frames", "4", "--streams", "2", "--c4-images", "4", "--no-cpu-baseline", "--legs-timeout", "400", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

@@ -13,7 +13,7 @@ for cfg in $configs; do
   f=${cfg%x*}; s=${cfg#*x}
   for c in $contents; do
     for k in ${KS:-0 5 6}; do
-      A="--no-cpu-baseline --no-also --frames $f --streams $s --tile-w 64 --tile-h 64 --steps $steps --warmup 2 --content $c"
+      A="--full --no-cpu-baseline --no-also --frames $f --streams $s --tile-w 64 --tile-h 64 --steps $steps --warmup 2 --content $c"
       LLCOMP_MI_CACHE=$k LLCOMP_MI_NOCACHE=$([ $k = 0 ] && echo 1 || echo 0) timeout -k 10 300 python3 bench.py $A > $out/c${k}_${cfg}_$c.json 2> $out/c${k}_${cfg}_$c.err || exit 1
     done
   done

@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 out=gpurun_out/${1:-lib_ab_tiles}; other=$2; contents=${3:-g3 nat}; configs=${4:-16x1 48x3}; reps=${5:-2}
 mkdir -p $out
 for r in $(seq 1 $reps); do for cfg in $configs; do f=${cfg%x*}; s=${cfg#*x}; for c in $contents; do for lib in libllcomp_mi.so $other; do
-  A="--no-cpu-baseline --no-also --frames $f --streams $s --tile-w 64 --tile-h 64 --steps 8 --warmup 2 --content $c"
+  A="--full --no-cpu-baseline --no-also --frames $f --streams $s --tile-w 64 --tile-h 64 --steps 8 --warmup 2 --content $c"
   LLCOMP_MI_LIB=$PWD/llcomp_amd/$lib timeout -k 10 300 python3 bench.py $A > $out/${lib%.so}_${cfg}_${c}_$r.json 2>/dev/null || exit 1
 done; done; done; done
 python3 - <<PY

@@ -5,7 +5,7 @@
 cd $GRAFT_REPO_ROOT
 out=gpurun_out/pad_ab; mkdir -p $out
 for r in 1 2; do for lib in libllcomp_mi.so libllcomp_mi_ch32.so; do
-  LLCOMP_MI_LIB=$PWD/llcomp_amd/$lib timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-also --frames 48 --streams 3 --tile-w 64 --tile-h 64 --steps 8 --warmup 2 --content g3 > $out/${lib%.so}_tiles_$r.json 2>/dev/null || exit 1
+  LLCOMP_MI_LIB=$PWD/llcomp_amd/$lib timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-also --frames 48 --streams 3 --tile-w 64 --tile-h 64 --steps 8 --warmup 2 --content g3 > $out/${lib%.so}_tiles_$r.json 2>/dev/null || exit 1
   LLCOMP_MI_LIB=$PWD/llcomp_amd/$lib timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-also --no-isolated --steps 20 --warmup 3 > $out/${lib%.so}_head_$r.json 2>/dev/null || exit 1
 done; done
 python3 - <<PY

@@ -9,7 +9,7 @@ extra=$3
 mkdir -p $out
 for r in $(seq 1 $reps); do
   for k in 0 1; do
-    LLCOMP_MI_SCANKERNELS=$k timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-also --steps 20 --warmup 3 $extra > $out/k${k}_$r.json 2> $out/k${k}_$r.err || exit 1
+    LLCOMP_MI_SCANKERNELS=$k timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-also --steps 20 --warmup 3 $extra > $out/k${k}_$r.json 2> $out/k${k}_$r.err || exit 1
   done
 done
 python3 - <<PY

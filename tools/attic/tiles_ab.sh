@@ -8,7 +8,7 @@ streams=${3:-1}
 cd $GRAFT_REPO_ROOT
 mkdir -p $out
 for c in $contents; do
-  A="--no-cpu-baseline --no-also --frames 16 --streams $streams --tile-w 64 --tile-h 64 --steps 5 --warmup 2 --content $c"
+  A="--full --no-cpu-baseline --no-also --frames 16 --streams $streams --tile-w 64 --tile-h 64 --steps 5 --warmup 2 --content $c"
   timeout -k 10 300 python3 bench.py $A > $out/snap_$c.json 2> $out/snap_$c.err || exit 1
   LLCOMP_MI_NOSNAP=1 timeout -k 10 300 python3 bench.py $A > $out/nosnap_$c.json 2> $out/nosnap_$c.err || exit 1
 done
