@@ -29,7 +29,9 @@ extern "C" {
  * llcomp_mi_decode_region(_into), llcomp_mi_codec_decode_region, llcomp_mi_codec_region_family, LLCOMP_MI_PREPARE_REGION; a rectangle
  * per frame -- llcomp_mi_regions_plan, llcomp_mi_codec_decode_regions, llcomp_mi_codec_regions_family, LLCOMP_MI_PREPARE_REGIONS; crops
  * of host containers -- llcomp_mi_regions_gather, llcomp_mi_codec_decode_regions_host, llcomp_mi_stream_submit_decode_regions,
- * LLCOMP_MI_JOB_DECODE_REGIONS, LLCOMP_MI_CTR_HOST_STAGED_BYTES).  The library and its callers are built from ONE header: structs have one layout per ABI version (llcomp_mi_opts is
+ * LLCOMP_MI_JOB_DECODE_REGIONS, LLCOMP_MI_CTR_HOST_STAGED_BYTES; crops of different sizes resized to one shape -- llcomp_mi_resize_weights,
+ * llcomp_mi_resized_regions_plan, llcomp_mi_codec_decode_resized_regions(_host), llcomp_mi_stream_submit_decode_resized_regions,
+ * LLCOMP_MI_PREPARE_RESIZED, LLCOMP_MI_JOB_DECODE_RESIZED_REGIONS, llcomp_mi_codec_allocated_bytes).  The library and its callers are built from ONE header: structs have one layout per ABI version (llcomp_mi_opts is
  * checked through struct_size and refused when it differs; llcomp_mi_info and llcomp_mi_stream_result are written in full),
  * so a binding compares llcomp_mi_abi_version() with the LLCOMP_MI_ABI_VERSION it was generated from and refuses to run on
  * a mismatch -- there is no cross-version compatibility mode. */
@@ -208,6 +210,25 @@ int llcomp_mi_regions_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, 
 int llcomp_mi_regions_gather(const uint8_t* const* data, const size_t* lens, uint32_t n, const uint32_t* xy, uint32_t rw, uint32_t rh,
                              uint8_t* payload, uint64_t payload_cap, uint32_t* slice_len, uint32_t len_cap, uint64_t* payload_bytes,
                              uint32_t* n_slices, uint32_t* n_classes);
+/* The resampling rule of llcomp_mi_codec_decode_resized_regions for one axis, in_len -> out_len: the triangle ("bilinear") filter with
+ * antialiasing of PIL and of torch's interpolate(mode="bilinear", align_corners=False, antialias=True), in integers:
+ *   scale = in_len / out_len, support = max(scale, 1); output i: center = (i + 0.5) * scale,
+ *   lo = max(int(center - support + 0.5), 0), hi = min(int(center + support + 0.5), in_len),
+ *   w_j = max(0, 1 - |(lo + j - center + 0.5) / support|) for j in [0, hi - lo), normalised to sum 1 (double),
+ *   q_j = floor(0.5 + w_j * 2^22) (Q22);  out = clamp((sum_j q_j * in[lo + j] + 2^21) >> 22, 0, 255).
+ * A frame is resampled horizontally first, rounded to u8, then vertically.  in_len == out_len is the identity (one weight 2^22 at
+ * lo = i).  Returns K, the taps per output (trailing taps that are 0 for every output are left out; K <= 129), and, when lo / q are not
+ * NULL, fills lo[out_len] and q[out_len][K] (zero-padded).  0 for in_len or out_len 0 or a downscale above 64x (in_len > 64 * out_len).
+ * Host-only; the GPU runs exactly these weights. */
+uint32_t llcomp_mi_resize_weights(uint32_t in_len, uint32_t out_len, uint32_t* lo, int32_t* q);
+/* The windows of a rectangle of its own size per frame: rects = {x_0, y_0, rw_0, rh_0, x_1, ...} (4 * n).  The rule of
+ * llcomp_mi_regions_plan, sized by the batch's LARGEST rectangle: Wx from max_f rw_f, wx0_f = min(x_f / tile_w, ntx - Wx), the same in
+ * y, so every window has one tile count and contains its frame's rectangle; the 2 x 2 class rule is unchanged.  With every rectangle of
+ * one size this is llcomp_mi_regions_plan window for window.  A frame with a small rectangle decodes a window sized for the largest one.
+ * windows (4 * n, NULL ok) and *n_classes as in llcomp_mi_regions_plan.  BAD_ARGS for n = 0, a NULL rects or n_classes, or any rectangle
+ * empty or outside the image.  Host-only. */
+int llcomp_mi_resized_regions_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar, const uint32_t* rects,
+                                   uint32_t n, uint32_t* windows, uint32_t* n_classes);
 uint32_t llcomp_mi_slice_count(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar);
 /* Slice width for one-row slices (tile_h = 1) when `frames` frames are coded per call: the widest slice (64..480 pixels) that
  * still keeps about four wavefronts per SIMD busy.  A call that codes few frames is latency-bound with wide slices; this
@@ -260,6 +281,9 @@ uint32_t llcomp_mi_codec_kernel_family(const llcomp_mi_codec* codec);
  * arrays of the 2-D encoder (22 B per sample) are allocated by the first call that needs them, so an encode-only or decode-only
  * codec stays below this figure; that first call can return LLCOMP_MI_NOMEM. */
 uint64_t llcomp_mi_codec_workspace_bytes(const llcomp_mi_codec* codec);
+/* Diagnostic: the device bytes the codec holds right now (what the calls so far have allocated; never above
+ * llcomp_mi_codec_workspace_bytes, except through a resized regions decode to an output larger than the image). */
+uint64_t llcomp_mi_codec_allocated_bytes(const llcomp_mi_codec* codec);
 /* Allocates NOW what the first encode (LLCOMP_MI_PREPARE_ENCODE: the 2-D encoder's snapshot arrays, or its state tables) and / or
  * the first decode (LLCOMP_MI_PREPARE_DECODE: the state tables of 2-D slices) would otherwise allocate inside the call -- for callers
  * that need the first call to be like every other one (no hipMalloc behind work already queued on their stream, no NOMEM in the
@@ -268,6 +292,7 @@ uint64_t llcomp_mi_codec_workspace_bytes(const llcomp_mi_codec* codec);
 #define LLCOMP_MI_PREPARE_DECODE 2u
 #define LLCOMP_MI_PREPARE_REGION 8u /* the region decode's two arrays (12 B per slice), and state tables if a region may need them (bit 2 stays unused) */
 #define LLCOMP_MI_PREPARE_REGIONS 16u /* ... and the per-frame table of a regions decode (32 B per frame in HBM, a pinned staging ring) */
+#define LLCOMP_MI_PREPARE_RESIZED 32u /* ... and the boxes and the horizontal pass's rows of a resized regions decode (frames * w * h * c bytes each) */
 int llcomp_mi_codec_prepare(llcomp_mi_codec* codec, uint32_t what);
 /* Upper bound on the packed payload bytes the codec can emit for any input (13 B per sample + slack). */
 uint64_t llcomp_mi_codec_max_payload_bytes(const llcomp_mi_codec* codec);
@@ -321,6 +346,30 @@ uint32_t llcomp_mi_codec_regions_family(const llcomp_mi_codec* codec, const uint
  * counts the payload bytes staged.  Profile slots as for a regions decode. */
 int llcomp_mi_codec_decode_regions_host(llcomp_mi_codec* codec, const uint8_t* const* data, const size_t* lens, const uint32_t* xy, uint32_t rw,
                                         uint32_t rh, void* d_px, void* d_status, void* stream);
+/* Regions decode with a rectangle of its own size per frame, every rectangle resampled to one output shape (torchvision's
+ * RandomResizedCrop, and RandomHorizontalFlip through flags): rects = {x, y, rw, rh} per frame (4 * frames, HOST memory), flags = one
+ * byte per frame (HOST memory, NULL = none; bit 0 mirrors the frame's output horizontally after resampling) -> d_px [frames][oh][ow][c],
+ * dense: byte for byte the rule of llcomp_mi_resize_weights applied to full_decode[f, y_f : y_f + rh_f, x_f : x_f + rw_f].  rects and
+ * flags are read during the call only.  Every frame decodes a window of tiles sized for the batch's largest rectangle
+ * (llcomp_mi_resized_regions_plan): a frame with a small rectangle decodes as much as one with the largest.  The classes run as in
+ * llcomp_mi_codec_decode_regions and crop every frame's BOX (the largest rectangle's size, containing the frame's rectangle) into a buffer
+ * of the codec; two resample kernels then write d_px.  Asynchronous on `stream`; verdicts as for llcomp_mi_codec_decode_regions (from the
+ * decoded windows' slices).  BAD_ARGS, before anything is launched or written: a NULL pointer, ow or oh 0, a rectangle empty or outside the
+ * image, or a downscale above 64x on either axis (rw_f > 64 * ow or rh_f > 64 * oh).  Profile slots as for a regions decode; the resample
+ * is timed in slot 6 with the crops.  The boxes (frames * rw_max * rh_max * c bytes) and the horizontal pass's rows (frames * rh_max * ow *
+ * c) are buffers of the codec that grow geometrically, never per call, and never past frames * w * h * c each but where a call needs
+ * more (LLCOMP_MI_PREPARE_RESIZED allocates both at that size).  llcomp_mi_codec_workspace_bytes counts both at that size and the tables
+ * and weights the staging buffer carries, for outputs no larger than the image (ow <= w, oh <= h); a larger output can take the rows'
+ * buffer and the staging buffer beyond it.  A call that grows a buffer waits for the codec's last call and can return LLCOMP_MI_NOMEM.  The regions table, the per-frame resample table and every
+ * frame's weights reach the GPU in ONE copy from the pinned ring of llcomp_mi_codec_decode_regions. */
+int llcomp_mi_codec_decode_resized_regions(llcomp_mi_codec* codec, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                           const uint32_t* rects, const uint8_t* flags, uint32_t ow, uint32_t oh, void* d_px, void* d_status,
+                                           void* stream);
+/* ... from HOST containers, as llcomp_mi_codec_decode_regions_host is to llcomp_mi_codec_decode_regions: only the windows' bytes cross
+ * PCIe (in the same one copy as the tables and weights), the containers, rects and flags may be reused as soon as the call returns, a
+ * gather error is returned before anything is queued, LLCOMP_MI_CTR_HOST_STAGED_BYTES counts the staged payload bytes. */
+int llcomp_mi_codec_decode_resized_regions_host(llcomp_mi_codec* codec, const uint8_t* const* data, const size_t* lens, const uint32_t* rects,
+                                                const uint8_t* flags, uint32_t ow, uint32_t oh, void* d_px, void* d_status, void* stream);
 /* Stage-A only (context + prediction model), for tests and profiling: d_sym u32[frames*h*w*c],
  * low 16 bits = folded context (0..7925), high 16 bits = folded residual (two's complement). */
 int llcomp_mi_codec_model(llcomp_mi_codec* codec, const void* d_px, void* d_sym, void* stream);
@@ -381,11 +430,12 @@ int llcomp_mi_codec_get_profile(llcomp_mi_codec* codec, double* ms8, uint32_t* n
  * container that needs more than 2x the raw size fails with OUTPUT_OVERFLOW (llcomp_mi_encode handles such a frame).
  * One object is driven by one thread at a time (calls are serialised internally). */
 typedef struct llcomp_mi_stream llcomp_mi_stream;
-enum { LLCOMP_MI_JOB_ENCODE = 0, LLCOMP_MI_JOB_DECODE = 1, LLCOMP_MI_JOB_DECODE_REGIONS = 2 };
+enum { LLCOMP_MI_JOB_ENCODE = 0, LLCOMP_MI_JOB_DECODE = 1, LLCOMP_MI_JOB_DECODE_REGIONS = 2, LLCOMP_MI_JOB_DECODE_RESIZED_REGIONS = 3 };
 typedef struct llcomp_mi_stream_result {
     uint32_t slot;       /* hand back with llcomp_mi_stream_release when `data` is no longer needed */
     uint32_t kind;       /* LLCOMP_MI_JOB_ENCODE: data = container, LLCOMP_MI_JOB_DECODE: data = h*w*c pixels,
-                            LLCOMP_MI_JOB_DECODE_REGIONS: data = frames_per_job crops of rh*rw*c pixels */
+                            LLCOMP_MI_JOB_DECODE_REGIONS: data = frames_per_job crops of rh*rw*c pixels,
+                            LLCOMP_MI_JOB_DECODE_RESIZED_REGIONS: data = frames_per_job outputs of oh*ow*c pixels */
     int32_t status;      /* llcomp_mi_status of this job */
     uint32_t reserved;
     uint64_t tag;        /* the caller's tag from submit */
@@ -422,6 +472,14 @@ int llcomp_mi_stream_submit_decode(llcomp_mi_stream* stream, const uint8_t* data
  * returns.  A gather error is the call's return value (nothing is queued).  Region jobs and whole-frame jobs mix in one object. */
 int llcomp_mi_stream_submit_decode_regions(llcomp_mi_stream* stream, const uint8_t* const* data, const size_t* lens, const uint32_t* xy,
                                            uint32_t rw, uint32_t rh, uint64_t tag);
+/* A job of resized crops: frames_per_job containers, frame f's rectangle rects[4f .. 4f + 3] = {x, y, rw, rh} and flags[f] (NULL = none),
+ * resampled to ow x oh (llcomp_mi_codec_decode_resized_regions_host on the slot's codec and stream): kind =
+ * LLCOMP_MI_JOB_DECODE_RESIZED_REGIONS, len = frames_per_job * oh * ow * c, and llcomp_mi_stream_result_part hands out frame f.  The
+ * output has to fit a slot: a job of more than frames_per_job * w * h * c bytes (llcomp_mi_stream_container_capacity bounds the slot's
+ * pinned buffer) is BAD_ARGS at submit.  Containers, rects and flags are read during the call only, as for
+ * llcomp_mi_stream_submit_decode_regions. */
+int llcomp_mi_stream_submit_decode_resized_regions(llcomp_mi_stream* stream, const uint8_t* const* data, const size_t* lens, const uint32_t* rects,
+                                                   const uint8_t* flags, uint32_t ow, uint32_t oh, uint64_t tag);
 int llcomp_mi_stream_pending(llcomp_mi_stream* stream); /* jobs submitted and not yet returned by wait */
 /* LLCOMP_MI_OK when llcomp_mi_stream_wait would not block (or nothing is pending), LLCOMP_MI_BUSY otherwise. */
 int llcomp_mi_stream_poll(llcomp_mi_stream* stream);

@@ -9,6 +9,8 @@ with ctypes and keeps the reference's names and error behaviour:
     decompress_region(data, x, y, w, h)           <->  llcomp::decompressRegion (include/llcomp_mi.hpp: one rectangle, covered slices only)
     regions_plan(w, h, c, tw, th, planar, rw, rh, xy) / Codec.decode_regions  (a rectangle per frame of a batch; pack_batch feeds it)
     regions_gather / Codec.decode_regions_host / Stream.submit_decode_regions  (the same from host containers: only the windows cross)
+    resize_weights / resized_regions_plan / Codec.decode_resized_regions(_host) / Stream.submit_decode_resized_regions  (a rectangle of
+        its own size per frame, resampled to one output shape with an optional mirror: RandomResizedCrop + RandomHorizontalFlip)
     RawImage(pixels, width, height, channels)     <->  llcomp::RawImage         (/root/reference/llcomp.hpp:454-459)
     EXT = ".llcomp"                               <->  llcomp::ext              (/root/reference/llcomp.hpp:18)
 
@@ -26,7 +28,7 @@ from ._lib import Info, Opts
 EXT = ".llcomp"
 FORMAT_LEGACY, FORMAT_SLICED = 0, 1
 (OK, BAD_MAGIC, BAD_EXPONENT, TRUNCATED, BAD_ARGS, OUT_OF_RANGE, OUTPUT_OVERFLOW, HIP_ERROR, NO_DEVICE, NOMEM, BUSY, DEVICE_FAILED) = range(12)
-JOB_ENCODE, JOB_DECODE, JOB_DECODE_REGIONS = 0, 1, 2
+JOB_ENCODE, JOB_DECODE, JOB_DECODE_REGIONS, JOB_DECODE_RESIZED_REGIONS = 0, 1, 2, 3
 
 RawImage = namedtuple("RawImage", "pixels width height channels")
 
@@ -143,6 +145,47 @@ def regions_plan(w, h, c, tile_w, tile_h, planar, rw, rh, xy):
     tab, n = _xy_table(xy)
     win, k = (C.c_uint32 * (4 * n))(), C.c_uint32()
     _check(_lib.load().llcomp_mi_regions_plan(w, h, c, tile_w, tile_h, int(bool(planar)), rw, rh, tab, n, win, C.byref(k)))
+    return np.array(win, dtype=np.uint32).reshape(n, 4), k.value
+
+
+def _rects_table(rects, n=None):
+    """a sequence of (x, y, rw, rh) or an int array of shape [n, 4] -> (ctypes u32 array of 4n values, n); BAD_ARGS otherwise"""
+    a = np.asarray(rects)
+    if a.ndim != 2 or a.shape[1] != 4 or a.shape[0] < 1 or (n is not None and a.shape[0] != n) or not np.issubdtype(a.dtype, np.integer) \
+            or (a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF)):
+        raise LlcompError(BAD_ARGS, f"rects must be {n if n is not None else 'n'} x 4 non-negative integers, got shape {a.shape} {a.dtype}")
+    flat = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1)
+    return (C.c_uint32 * flat.size)(*flat.tolist()), a.shape[0]
+
+
+def _flags_table(flags, n):
+    """None, or n per-frame flags (bit 0: mirror horizontally) -> (ctypes u8 array or None)"""
+    if flags is None:
+        return None
+    a = np.asarray(flags)
+    if a.shape != (n,) or (a.size and (a.min() < 0 or a.max() > 255)):
+        raise LlcompError(BAD_ARGS, f"flags must be {n} values in 0..255, got shape {a.shape}")
+    return (C.c_uint8 * n)(*[int(v) for v in a.tolist()])
+
+
+def resize_weights(in_len, out_len):
+    """(lo np.uint32[out_len], q np.int32[out_len, K]) of the resampling rule of one axis (llcomp_mi_resize_weights, host only): the
+    triangle filter with antialiasing in Q22, exactly what the GPU runs.  LlcompError(BAD_ARGS) for a side of 0 or a downscale above 64x."""
+    L = _lib.load()
+    k = L.llcomp_mi_resize_weights(in_len, out_len, None, None)
+    if not k:
+        raise LlcompError(BAD_ARGS, f"no resampling {in_len} -> {out_len}")
+    lo, q = np.zeros(out_len, np.uint32), np.zeros((out_len, k), np.int32)
+    L.llcomp_mi_resize_weights(in_len, out_len, lo.ctypes.data, q.ctypes.data)
+    return lo, q
+
+
+def resized_regions_plan(w, h, c, tile_w, tile_h, planar, rects):
+    """(windows, n_classes) of a rectangle of its own size per frame (rects [n, 4] of (x, y, rw, rh)), every window sized for the largest
+    one -- llcomp_mi_resized_regions_plan, host only.  LlcompError(BAD_ARGS) for a rectangle empty or outside the image."""
+    tab, n = _rects_table(rects)
+    win, k = (C.c_uint32 * (4 * n))(), C.c_uint32()
+    _check(_lib.load().llcomp_mi_resized_regions_plan(w, h, c, tile_w, tile_h, int(bool(planar)), tab, n, win, C.byref(k)))
     return np.array(win, dtype=np.uint32).reshape(n, 4), k.value
 
 
@@ -371,6 +414,17 @@ class Stream:
         rc = self._L.llcomp_mi_stream_submit_decode_regions(self._h, ptrs, lens, tab, rw, rh, tag)
         return self._submit(rc, (rh, rw, self.shape[2]))
 
+    def submit_decode_resized_regions(self, containers, rects, ow, oh, flags=None, tag=0):
+        """frames_per_job containers, their rectangles rects ([frames_per_job, 4] of (x, y, rw, rh)) and optional mirror flags -> a job
+        whose .data is the output [oh,ow,c] (one frame per job) / [F,oh,ow,c].  The containers are read during this call only."""
+        ptrs, lens, keep = _containers(containers)
+        if len(keep) != self.frames_per_job:
+            raise LlcompError(BAD_ARGS, f"a job takes {self.frames_per_job} containers, got {len(keep)}")
+        tab, _ = _rects_table(rects, self.frames_per_job)
+        fl = _flags_table(flags, self.frames_per_job)
+        rc = self._L.llcomp_mi_stream_submit_decode_resized_regions(self._h, ptrs, lens, tab, fl, ow, oh, tag)
+        return self._submit(rc, (oh, ow, self.shape[2]))
+
     def pending(self):
         return self._L.llcomp_mi_stream_pending(self._h)
 
@@ -384,7 +438,7 @@ class Stream:
         data = None
         if r.status == OK:
             whole = np.ctypeslib.as_array(C.cast(r.data, _lib.u8p), shape=(max(int(r.len), 1),))[: int(r.len)]
-            if r.kind in (JOB_DECODE, JOB_DECODE_REGIONS):
+            if r.kind in (JOB_DECODE, JOB_DECODE_REGIONS, JOB_DECODE_RESIZED_REGIONS):
                 data = whole.reshape(shape) if self.frames_per_job == 1 else whole.reshape((self.frames_per_job,) + shape)
             elif self.frames_per_job == 1:
                 data = whole
@@ -619,6 +673,29 @@ class Codec:
         tab, _ = _xy_table(xy, self.frames)
         _check(self._L.llcomp_mi_codec_decode_regions_host(self._h, ptrs, lens, tab, rw, rh, d_px, d_status, stream))
 
+    def decode_resized_regions(self, d_payload, payload_bytes, d_slice_len, rects, ow, oh, d_px, d_status, flags=None, stream=0):
+        """frame f's rectangle rects[f] = (x, y, rw, rh), resampled to ow x oh (and mirrored where flags[f] & 1) -> d_px
+        [frames][oh][ow][c] (llcomp_mi_codec_decode_resized_regions); rects and flags are read during the call"""
+        tab, _ = _rects_table(rects, self.frames)
+        fl = _flags_table(flags, self.frames)
+        _check(self._L.llcomp_mi_codec_decode_resized_regions(self._h, d_payload, payload_bytes, d_slice_len, tab, fl, ow, oh, d_px, d_status,
+                                                               stream))
+
+    def decode_resized_regions_host(self, containers, rects, ow, oh, d_px, d_status, flags=None, stream=0):
+        """decode_resized_regions of host containers (llcomp_mi_codec_decode_resized_regions_host): only the windows' bytes cross PCIe;
+        the containers, rects and flags are read during the call only"""
+        ptrs, lens, keep = _containers(containers)
+        if len(keep) != self.frames:
+            raise LlcompError(BAD_ARGS, f"the codec takes {self.frames} containers, got {len(keep)}")
+        tab, _ = _rects_table(rects, self.frames)
+        fl = _flags_table(flags, self.frames)
+        _check(self._L.llcomp_mi_codec_decode_resized_regions_host(self._h, ptrs, lens, tab, fl, ow, oh, d_px, d_status, stream))
+
+    def allocated_bytes(self):
+        """device bytes the codec holds right now (llcomp_mi_codec_allocated_bytes; at most .workspace_bytes for outputs up to the image's
+        size)"""
+        return self._L.llcomp_mi_codec_allocated_bytes(self._h)
+
     def regions_family(self, xy, rw, rh):
         """the kernel family of every class a regions decode of these rectangles runs, in class order (the keys of .family); None
         for bad rectangles"""
@@ -645,10 +722,11 @@ class Codec:
         _check(self._L.llcomp_mi_codec_get_profile(self._h, ms, C.byref(ne), C.byref(nd)))
         return dict(zip(self.PROFILE_SLOTS, list(ms))), ne.value, nd.value
 
-    def prepare(self, encode=True, decode=True, region=False, regions=False):
-        """allocate now what the first encode / decode / region decode / regions decode would allocate inside the call
-        (llcomp_mi_codec_prepare)"""
-        _check(self._L.llcomp_mi_codec_prepare(self._h, (1 if encode else 0) | (2 if decode else 0) | (8 if region else 0) | (16 if regions else 0)))
+    def prepare(self, encode=True, decode=True, region=False, regions=False, resized=False):
+        """allocate now what the first encode / decode / region decode / regions decode / resized regions decode would allocate inside
+        the call (llcomp_mi_codec_prepare)"""
+        _check(self._L.llcomp_mi_codec_prepare(self._h, (1 if encode else 0) | (2 if decode else 0) | (8 if region else 0) | (16 if regions else 0)
+                                               | (32 if resized else 0)))
 
     COUNTERS = ("dec_cached_waves", "dec_bypassed_waves", "cache_lookups", "cache_misses", "cache_writebacks", "dec_replays", "enc_carry_backs",
                 "generation_wraps", "dec_launches_cached", "dec_launches_plain", "host_staged_bytes")

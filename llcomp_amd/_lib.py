@@ -32,6 +32,8 @@ SYMBOLS = [
     "llcomp_mi_region_plan", "llcomp_mi_decode_region", "llcomp_mi_decode_region_into", "llcomp_mi_codec_decode_region",
     "llcomp_mi_codec_region_family", "llcomp_mi_regions_plan", "llcomp_mi_codec_decode_regions", "llcomp_mi_codec_regions_family",
     "llcomp_mi_regions_gather", "llcomp_mi_codec_decode_regions_host", "llcomp_mi_stream_submit_decode_regions",
+    "llcomp_mi_resize_weights", "llcomp_mi_resized_regions_plan", "llcomp_mi_codec_decode_resized_regions",
+    "llcomp_mi_codec_decode_resized_regions_host", "llcomp_mi_stream_submit_decode_resized_regions", "llcomp_mi_codec_allocated_bytes",
 ]
 
 u8p = C.POINTER(C.c_uint8)
@@ -243,6 +245,21 @@ def load():
         L.llcomp_mi_codec_decode_regions_host.argtypes = [C.c_void_p, ptrs, sizes, u32p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 3
         L.llcomp_mi_stream_submit_decode_regions.restype = C.c_int
         L.llcomp_mi_stream_submit_decode_regions.argtypes = [C.c_void_p, ptrs, sizes, u32p, C.c_uint32, C.c_uint32, C.c_uint64]
+    if "LLCOMP_MI_LIB" not in os.environ or hasattr(L, "llcomp_mi_resize_weights"):  # crops of different sizes, resized to one shape
+        u32p, i32p, ptrs, sizes = C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)
+        L.llcomp_mi_resize_weights.restype = C.c_uint32
+        L.llcomp_mi_resize_weights.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.llcomp_mi_resized_regions_plan.restype = C.c_int
+        L.llcomp_mi_resized_regions_plan.argtypes = [C.c_uint32] * 6 + [u32p, C.c_uint32, u32p, u32p]
+        L.llcomp_mi_codec_decode_resized_regions.restype = C.c_int
+        L.llcomp_mi_codec_decode_resized_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, u32p, C.c_void_p, C.c_uint32,
+                                                             C.c_uint32] + [C.c_void_p] * 3
+        L.llcomp_mi_codec_decode_resized_regions_host.restype = C.c_int
+        L.llcomp_mi_codec_decode_resized_regions_host.argtypes = [C.c_void_p, ptrs, sizes, u32p, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 3
+        L.llcomp_mi_stream_submit_decode_resized_regions.restype = C.c_int
+        L.llcomp_mi_stream_submit_decode_resized_regions.argtypes = [C.c_void_p, ptrs, sizes, u32p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64]
+        L.llcomp_mi_codec_allocated_bytes.restype = C.c_uint64
+        L.llcomp_mi_codec_allocated_bytes.argtypes = [C.c_void_p]
     if "LLCOMP_MI_LIB" not in os.environ and L.llcomp_mi_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.llcomp_mi_abi_version()}, this binding was written for {ABI_VERSION}: rebuild the library")
     _lib = L

@@ -16,6 +16,7 @@
 #include "container.hpp"
 #include "geometry.hpp"
 #include "kernels.hpp"
+#include "resize.hpp"
 #include "snapshot.hpp"
 #include "tables.hpp"
 
@@ -255,9 +256,8 @@ int region_setup(const llcomp_mi_codec* k, uint32_t x, uint32_t y, uint32_t rw, 
     return LLCOMP_MI_OK;
 }
 
-// regions decode: the per-frame table in HBM and its pinned staging ring with one event per slot
-int ensure_regions_table(llcomp_mi_codec* k) {
-    if (k->d_regions) return LLCOMP_MI_OK;
+// regions decode: the pinned staging ring with one event per slot (what every regions call copies its tables from) ...
+int ensure_regions_ring(llcomp_mi_codec* k) {
     const uint64_t bytes = uint64_t(k->g.frames) * sizeof(RegionsFrame);
     for (uint32_t i = 0; i < llcomp_mi_codec::kRegionsRing; ++i) {
         if (k->h_regions[i]) continue;
@@ -274,6 +274,13 @@ int ensure_regions_table(llcomp_mi_codec* k) {
             (void)hipGetLastError();
             return LLCOMP_MI_HIP_ERROR;
         }
+    return LLCOMP_MI_OK;
+}
+// ... and the per-frame table in HBM that a regions decode from HBM copies into
+int ensure_regions_table(llcomp_mi_codec* k) {
+    if (k->d_regions) return LLCOMP_MI_OK;
+    if (int rc = ensure_regions_ring(k)) return rc;
+    const uint64_t bytes = uint64_t(k->g.frames) * sizeof(RegionsFrame);
     if (dev_alloc(reinterpret_cast<void**>(&k->d_regions), bytes) != hipSuccess) {
         k->d_regions = nullptr;
         return LLCOMP_MI_NOMEM;
@@ -324,11 +331,16 @@ struct StageLayout {
 };
 // ... at most: every slice of the batch, each at the SLICED entry limit (the gather refuses a window entry above it)
 uint64_t stage_bound(const Geometry& g) { return StageLayout(g.frames, g.n_slices, uint64_t(g.n_slices) * (g.slice_cap - 16)).bytes; }
-// The staging buffer in HBM for `bytes`: grown to max(bytes, twice its size, at most stage_bound) when too small.  The old buffer may
-// still be read by the codec's last call: that call is waited for (only a call that grows the buffer waits).
-int ensure_stage(llcomp_mi_codec* k, uint64_t bytes) {
+// What a resized regions decode adds to the one copy at most, for outputs no larger than the image (ow <= w, oh <= h): 16 bytes of
+// alignment, and per frame its ResizeFrame and its weights -- out * (K + 1) int32 per axis, K <= 2 * max(in / out, 1) + 3, so at most
+// 2 * max(in, out) + 4 * out <= 6 * side of the image.
+uint64_t resized_tables_bound(const Geometry& g) { return 16 + uint64_t(g.frames) * (sizeof(ResizeFrame) + 4 * 6 * (uint64_t(g.w) + g.h)); }
+// The staging buffer in HBM for `bytes`: grown to max(bytes, twice its size, at most `bound`) when too small (bound: stage_bound, plus
+// resized_tables_bound for a resized regions decode).  The old buffer may still be read by the codec's last call: that call is waited
+// for (only a call that grows the buffer waits).
+int ensure_stage(llcomp_mi_codec* k, uint64_t bytes, uint64_t bound) {
     if (bytes <= k->stage_cap) return LLCOMP_MI_OK;
-    const uint64_t cap = std::max(bytes, std::min(2 * k->stage_cap, stage_bound(k->g)));
+    const uint64_t cap = std::max(bytes, std::min(2 * k->stage_cap, bound));
     if (k->d_stage) {
         if (k->done && k->done->ev && hipEventSynchronize(k->done->ev) != hipSuccess) return LLCOMP_MI_HIP_ERROR;
         dev_free(k->d_stage);
@@ -345,48 +357,95 @@ int ensure_stage(llcomp_mi_codec* k, uint64_t bytes) {
     return LLCOMP_MI_OK;
 }
 
+// A resized regions decode's buffer `p` (cap bytes) for `bytes`: grown to max(bytes, twice its size, at most `bound`) when too small --
+// bound = frames * w * h * c, what the boxes never exceed and the horizontal pass's rows do not for ow <= w.  The old buffer may still be
+// used by the codec's last call: that call is waited for (only a call that grows a buffer waits).
+int ensure_grown(llcomp_mi_codec* k, uint8_t*& p, uint64_t& cap, uint64_t bytes, uint64_t bound) {
+    if (bytes <= cap) return LLCOMP_MI_OK;
+    const uint64_t want = std::max(bytes, std::min(2 * cap, bound));
+    if (p) {
+        if (k->done && k->done->ev && hipEventSynchronize(k->done->ev) != hipSuccess) return LLCOMP_MI_HIP_ERROR;
+        dev_free(p);
+        k->allocated_bytes -= cap;
+        p = nullptr;
+        cap = 0;
+    }
+    if (dev_alloc(reinterpret_cast<void**>(&p), want) != hipSuccess) {
+        p = nullptr;
+        return LLCOMP_MI_NOMEM;
+    }
+    cap = want;
+    k->allocated_bytes += want;
+    return LLCOMP_MI_OK;
+}
+
 // One class of a regions decode: its sub-geometry, and its frames = entries [first, first + sub.frames) of the table.
 struct RegionsClass {
     Geometry sub;
     uint32_t first;
 };
+int regions_setup_sized(const llcomp_mi_codec* k, const uint32_t* rects, uint32_t wmax, uint32_t hmax, RegionsFrame* tab, RegionsClass* classes,
+                        uint32_t& n_classes);
 // Every frame's window and class (geometry.hpp: regions_window) -> `tab` (g.frames entries, class by class, frame order inside a class)
 // and the classes that have frames, in class order.  BAD_ARGS for a rectangle a frame does not hold; HIP_ERROR if a class's
 // sub-geometry would not fit the codec's workspace (regions_fits: never by default, checked all the same).
 int regions_setup(const llcomp_mi_codec* k, const uint32_t* xy, uint32_t rw, uint32_t rh, RegionsFrame* tab, RegionsClass* classes,
                   uint32_t& n_classes) {
-    const Geometry& g = k->g;
     if (!xy) return LLCOMP_MI_BAD_ARGS;
+    std::vector<uint32_t> rects(4 * size_t(k->g.frames));
+    for (uint32_t f = 0; f < k->g.frames; ++f) {
+        rects[4 * f + 0] = xy[2 * f];
+        rects[4 * f + 1] = xy[2 * f + 1];
+        rects[4 * f + 2] = rw;
+        rects[4 * f + 3] = rh;
+    }
+    return regions_setup_sized(k, rects.data(), rw, rh, tab, classes, n_classes);
+}
+// ... with a rectangle of its own size per frame (rects = {x, y, rw, rh} per frame): every window is sized for the largest, wmax x hmax
+// (regions_window_sized), and the table's crop is a wmax x hmax BOX inside the window that contains the frame's rectangle, at
+// min(the rectangle's origin, the window's side - wmax) -- the rectangle's own origin when all sizes are equal.
+int regions_setup_sized(const llcomp_mi_codec* k, const uint32_t* rects, uint32_t wmax, uint32_t hmax, RegionsFrame* tab, RegionsClass* classes,
+                        uint32_t& n_classes) {
+    const Geometry& g = k->g;
+    if (!rects) return LLCOMP_MI_BAD_ARGS;
     RegionBox win[kRegionsClasses];
     uint32_t count[kRegionsClasses] = {}, cls = 0;
     for (uint32_t f = 0; f < g.frames; ++f) {
         RegionBox b;
-        if (!regions_window(g.w, g.h, g.tile_w, g.tile_h, xy[2 * f], xy[2 * f + 1], rw, rh, b, cls)) return LLCOMP_MI_BAD_ARGS;
+        const uint32_t* r = rects + 4 * size_t(f);
+        if (!regions_window_sized(g.w, g.h, g.tile_w, g.tile_h, r[0], r[1], r[2], r[3], wmax, hmax, b, cls)) return LLCOMP_MI_BAD_ARGS;
         win[cls] = b;  // (the window's size, all the sub-geometry depends on, is the class's)
         ++count[cls];
     }
     uint32_t first[kRegionsClasses], next = 0;
+    const Geometry* sub_of[kRegionsClasses] = {};
     n_classes = 0;
     for (uint32_t c = 0; c < kRegionsClasses; ++c) {
         first[c] = next;
         next += count[c];
         if (!count[c]) continue;
         RegionsClass& rc = classes[n_classes++];
+        sub_of[c] = &rc.sub;
         rc.first = first[c];
         if (!regions_geometry(g, win[c], count[c], k->tune, rc.sub) || !regions_fits(g, rc.sub)) return LLCOMP_MI_HIP_ERROR;
     }
     for (uint32_t f = 0; f < g.frames; ++f) {
         RegionBox b;
-        (void)regions_window(g.w, g.h, g.tile_w, g.tile_h, xy[2 * f], xy[2 * f + 1], rw, rh, b, cls);
+        const uint32_t* r = rects + 4 * size_t(f);
+        (void)regions_window_sized(g.w, g.h, g.tile_w, g.tile_h, r[0], r[1], r[2], r[3], wmax, hmax, b, cls);
+        const uint32_t cx = r[0] - b.tx0 * g.tile_w, cy = r[1] - b.ty0 * g.tile_h;
+        // (sub.w >= wmax: a window of Wx tile columns is at least wmax pixels wide, also where it ends at a partial column)
+        const uint32_t bx = std::min(cx, sub_of[cls]->w >= wmax ? sub_of[cls]->w - wmax : 0u);
+        const uint32_t by = std::min(cy, sub_of[cls]->h >= hmax ? sub_of[cls]->h - hmax : 0u);
         RegionsFrame& e = tab[first[cls]++];
-        e = RegionsFrame{f, b.tx0, b.ty0, xy[2 * f] - b.tx0 * g.tile_w, xy[2 * f + 1] - b.ty0 * g.tile_h, f, cls, 0};
+        e = RegionsFrame{f, b.tx0, b.ty0, bx, by, f, cls, 0};
     }
-    // (what the crop kernels rely on; the window contains the rectangle by construction)
+    // (what the crop kernels rely on; the window contains the box by construction)
     for (uint32_t i = 0; i < n_classes; ++i) {
         const RegionsClass& rc = classes[i];
         for (uint32_t j = 0; j < rc.sub.frames; ++j) {
             const RegionsFrame& e = tab[rc.first + j];
-            if (uint64_t(e.cx0) + rw > rc.sub.w || uint64_t(e.cy0) + rh > rc.sub.h || e.out >= g.frames) return LLCOMP_MI_HIP_ERROR;
+            if (uint64_t(e.cx0) + wmax > rc.sub.w || uint64_t(e.cy0) + hmax > rc.sub.h || e.out >= g.frames) return LLCOMP_MI_HIP_ERROR;
         }
     }
     return LLCOMP_MI_OK;
@@ -444,6 +503,50 @@ int regions_classes(llcomp_mi_codec* k, const RegionsClass* classes, uint32_t n_
     return LLCOMP_MI_OK;
 }
 
+// Everything of a resized regions decode the host decides: every frame's window, class and box (regions_setup_sized, sized for the
+// batch's largest rectangle wmax x hmax), its rectangle inside the box, its flags and its weights (resize.hpp).  BAD_ARGS for a null
+// rects, an output side of 0, any rectangle outside the image and a downscale above kResizeMaxDown on either axis.
+struct ResizedPlan {
+    std::vector<RegionsFrame> tab;
+    RegionsClass classes[kRegionsClasses];
+    uint32_t n_classes = 0, wmax = 0, hmax = 0;
+    std::vector<ResizeFrame> rs;  // frame order
+    std::vector<int32_t> w;
+    uint64_t box_bytes = 0, mid_bytes = 0;
+    // what the one copy carries, behind the regions table (or behind the staged payload): [ResizeFrame[frames]][int32 weights]
+    uint64_t bytes() const { return uint64_t(rs.size()) * sizeof(ResizeFrame) + 4 * uint64_t(w.size()); }
+    void put(uint8_t* at) const {
+        std::memcpy(at, rs.data(), rs.size() * sizeof(ResizeFrame));
+        std::memcpy(at + rs.size() * sizeof(ResizeFrame), w.data(), 4 * w.size());
+    }
+};
+int resized_setup(const llcomp_mi_codec* k, const uint32_t* rects, const uint8_t* flags, uint32_t ow, uint32_t oh, ResizedPlan& p) {
+    const Geometry& g = k->g;
+    if (!rects || !ow || !oh || g.frames > 65535) return LLCOMP_MI_BAD_ARGS;
+    for (uint32_t f = 0; f < g.frames; ++f) {
+        const uint32_t rw = rects[4 * f + 2], rh = rects[4 * f + 3];
+        if (uint64_t(rw) > uint64_t(kResizeMaxDown) * ow || uint64_t(rh) > uint64_t(kResizeMaxDown) * oh) return LLCOMP_MI_BAD_ARGS;
+        p.wmax = std::max(p.wmax, rw);
+        p.hmax = std::max(p.hmax, rh);
+    }
+    p.tab.resize(g.frames);
+    if (int rc = regions_setup_sized(k, rects, p.wmax, p.hmax, p.tab.data(), p.classes, p.n_classes)) return rc;
+    p.rs.assign(g.frames, ResizeFrame{});
+    std::vector<uint32_t> seen;  // (axes already computed in this call)
+    for (const RegionsFrame& e : p.tab) {
+        const uint32_t* r = rects + 4 * size_t(e.frame);
+        ResizeFrame& z = p.rs[e.frame];
+        z.ox = r[0] - e.wx0 * g.tile_w - e.cx0;
+        z.oy = r[1] - e.wy0 * g.tile_h - e.cy0;
+        z.flags = flags ? flags[e.frame] & 1u : 0u;
+        if (!resize_frame_weights(r[2], r[3], ow, oh, z, p.w, seen)) return LLCOMP_MI_BAD_ARGS;
+        if (uint64_t(z.ox) + z.rw > p.wmax || uint64_t(z.oy) + z.rh > p.hmax) return LLCOMP_MI_HIP_ERROR;  // (the box holds it by construction)
+    }
+    p.box_bytes = uint64_t(g.frames) * p.wmax * p.hmax * g.c;
+    p.mid_bytes = uint64_t(g.frames) * p.hmax * ow * g.c;
+    return LLCOMP_MI_OK;
+}
+
 }  // namespace
 
 namespace llcomp_mi {
@@ -470,6 +573,8 @@ void codec_release(llcomp_mi_codec* k) {
     dev_free(k->d_region_off, k->done);
     dev_free(k->d_regions, k->done);
     dev_free(k->d_stage, k->done);
+    dev_free(k->d_box, k->done);
+    dev_free(k->d_mid, k->done);
     for (uint32_t i = 0; i < llcomp_mi_codec::kRegionsRing; ++i) {
         if (!k->h_regions[i]) continue;
         // (a copy out of the slot may still be queued on a caller's stream: it must not read freed memory)
@@ -594,7 +699,11 @@ int llcomp_mi::codec_create(llcomp_mi_codec** out, int32_t device, uint32_t fram
                               (!k->need_states && !rows_mode(g) ? (uint64_t(lane_groups(g)) * kContexts << g.lane_shift) * 8 : 0);
     // ... plus the per-frame table of a regions decode, and the staging buffer of a host-staged one (its upper bound)
     const uint64_t b_regions = uint64_t(frames) * sizeof(RegionsFrame) + stage_bound(g);
-    k->workspace_bytes = b_sym + b_lanes + b_states + b_scratch + b_off + 8 + snap_el * (snapshot_chunked(g) ? 28 : 18) + b_region + b_regions;
+    // ... plus the boxes and the horizontal pass's rows of a resized regions decode (frames * w * h * c each) and what its tables add to
+    // the staging buffer (resized_tables_bound), for outputs no larger than the image
+    const uint64_t b_resized = 2 * samples + resized_tables_bound(g);
+    k->workspace_bytes =
+        b_sym + b_lanes + b_states + b_scratch + b_off + 8 + snap_el * (snapshot_chunked(g) ? 28 : 18) + b_region + b_regions + b_resized;
     const bool ok = dev_alloc(&k->d_sym_or_rec, b_sym) == hipSuccess && dev_alloc(&k->d_lane_order, b_lanes) == hipSuccess &&
                     dev_alloc(reinterpret_cast<void**>(&k->d_scratch), b_scratch) == hipSuccess &&
                     dev_alloc(reinterpret_cast<void**>(&k->d_group_off), b_off) == hipSuccess &&
@@ -620,7 +729,8 @@ void llcomp_mi_codec_destroy(llcomp_mi_codec* k) {
 }
 
 int llcomp_mi_codec_prepare(llcomp_mi_codec* k, uint32_t what) {
-    if (!k || (what & ~(LLCOMP_MI_PREPARE_ENCODE | LLCOMP_MI_PREPARE_DECODE | LLCOMP_MI_PREPARE_REGION | LLCOMP_MI_PREPARE_REGIONS)))
+    if (!k || (what & ~(LLCOMP_MI_PREPARE_ENCODE | LLCOMP_MI_PREPARE_DECODE | LLCOMP_MI_PREPARE_REGION | LLCOMP_MI_PREPARE_REGIONS |
+                        LLCOMP_MI_PREPARE_RESIZED)))
         return LLCOMP_MI_BAD_ARGS;
     DeviceGuard guard(k->device);
     if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
@@ -633,19 +743,26 @@ int llcomp_mi_codec_prepare(llcomp_mi_codec* k, uint32_t what) {
     }
     if (what & LLCOMP_MI_PREPARE_DECODE)
         if (int rc = ensure_state_tables(k, k->need_states)) return rc;
-    if (what & (LLCOMP_MI_PREPARE_REGION | LLCOMP_MI_PREPARE_REGIONS)) {
+    if (what & (LLCOMP_MI_PREPARE_REGION | LLCOMP_MI_PREPARE_REGIONS | LLCOMP_MI_PREPARE_RESIZED)) {
         if (int rc = ensure_region_arrays(k)) return rc;
         if (region_may_need_states(k))
             if (int rc = ensure_state_tables(k, true)) return rc;
     }
     if (what & LLCOMP_MI_PREPARE_REGIONS)
         if (int rc = ensure_regions_table(k)) return rc;
+    if (what & LLCOMP_MI_PREPARE_RESIZED) {
+        const uint64_t samples = uint64_t(k->g.frames) * k->g.w * k->g.h * k->g.c;
+        if (int rc = ensure_regions_ring(k)) return rc;
+        if (int rc = ensure_grown(k, k->d_box, k->box_cap, samples, samples)) return rc;
+        if (int rc = ensure_grown(k, k->d_mid, k->mid_cap, samples, samples)) return rc;
+    }
     return LLCOMP_MI_OK;
 }
 
 uint32_t llcomp_mi_codec_slices(const llcomp_mi_codec* k) { return k ? k->g.n_slices : 0; }
 uint32_t llcomp_mi_codec_kernel_family(const llcomp_mi_codec* k) { return k ? (k->g.flags & 0xFFu) | (k->g.lane_shift << 8) | (k->g.lpw << 16) : 0; }
 uint64_t llcomp_mi_codec_workspace_bytes(const llcomp_mi_codec* k) { return k ? k->workspace_bytes : 0; }
+uint64_t llcomp_mi_codec_allocated_bytes(const llcomp_mi_codec* k) { return k ? k->allocated_bytes : 0; }
 uint64_t llcomp_mi_codec_max_payload_bytes(const llcomp_mi_codec* k) {
     return k ? uint64_t(k->g.n_slices) * k->g.slice_cap : 0;
 }
@@ -936,7 +1053,7 @@ int llcomp_mi_codec_decode_regions_host(llcomp_mi_codec* k, const uint8_t* const
     DeviceGuard guard(k->device);
     if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
     if (int rc = ensure_regions_table(k)) return rc;
-    if (int rc = ensure_stage(k, lay.bytes)) return rc;
+    if (int rc = ensure_stage(k, lay.bytes, stage_bound(g))) return rc;
     uint32_t slot = 0;
     if (int rc = regions_slot_take(k, lay.bytes, stage_bound(g), slot)) return rc;
     uint8_t* h = k->h_regions[slot];
@@ -956,6 +1073,110 @@ int llcomp_mi_codec_decode_regions_host(llcomp_mi_codec* k, const uint8_t* const
     if (int rc = regions_classes(k, classes, n_classes, reinterpret_cast<const RegionsFrame*>(k->d_stage), src, rw, rh, static_cast<uint8_t*>(d_px),
                                  static_cast<uint32_t*>(d_status), s))
         return rc;
+    ++k->n_decode;
+    return LLCOMP_MI_OK;
+}
+
+// Resized regions decode (DESIGN.md "Crops of different sizes, resized to one shape"): the regions decode's classes, unchanged, crop
+// every frame's box (the batch's largest rectangle size) into d_box; then the two resample passes read every frame's rectangle from its
+// box and write d_px.  The regions table, the resample table and the weights cross in ONE copy from a slot of the pinned ring to d_stage.
+int llcomp_mi_codec_decode_resized_regions(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                           const uint32_t* rects, const uint8_t* flags, uint32_t ow, uint32_t oh, void* d_px, void* d_status,
+                                           void* stream) {
+    if (!k || !d_payload || !d_slice_len || !d_px || !d_status || !rects) return LLCOMP_MI_BAD_ARGS;
+    const Geometry& g = k->g;
+    ResizedPlan p;
+    if (int rc = resized_setup(k, rects, flags, ow, oh, p)) return rc;
+    const uint64_t rs_at = (uint64_t(g.frames) * sizeof(RegionsFrame) + 15) & ~15ull, bytes = rs_at + p.bytes();
+    DeviceGuard guard(k->device);
+    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
+    if (int rc = ensure_region_arrays(k)) return rc;
+    const uint64_t samples = uint64_t(g.frames) * g.w * g.h * g.c, bound = stage_bound(g) + resized_tables_bound(g);
+    if (int rc = ensure_regions_ring(k)) return rc;
+    if (int rc = ensure_stage(k, bytes, bound)) return rc;
+    if (int rc = ensure_grown(k, k->d_box, k->box_cap, p.box_bytes, samples)) return rc;
+    if (int rc = ensure_grown(k, k->d_mid, k->mid_cap, p.mid_bytes, samples)) return rc;
+    uint32_t slot = 0;
+    if (int rc = regions_slot_take(k, bytes, bound, slot)) return rc;
+    uint8_t* h = k->h_regions[slot];
+    std::memcpy(h, p.tab.data(), p.tab.size() * sizeof(RegionsFrame));
+    p.put(h + rs_at);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DoneGuard done_guard{k, s};
+    HIP_TRY(hipMemsetAsync(d_status, 0, 4, s));
+    {
+        Timed t(k, s, 4);
+        HIP_TRY(hipMemcpyAsync(k->d_stage, h, bytes, hipMemcpyHostToDevice, s));
+        if (int rc = regions_slot_queued(k, slot, s)) return rc;
+        HIP_TRY(launch_group_sums(g, static_cast<const uint32_t*>(d_slice_len), k->d_group_off, s));
+        HIP_TRY(launch_scan_groups(g, k->d_group_off, k->d_total_tmp, s));
+    }
+    const RegionsSource src{static_cast<const uint8_t*>(d_payload), payload_bytes, static_cast<const uint32_t*>(d_slice_len), nullptr, nullptr};
+    if (int rc = regions_classes(k, p.classes, p.n_classes, reinterpret_cast<const RegionsFrame*>(k->d_stage), src, p.wmax, p.hmax, k->d_box,
+                                 static_cast<uint32_t*>(d_status), s))
+        return rc;
+    {
+        Timed t(k, s, 6);
+        HIP_TRY(launch_resize(k->d_box, k->d_mid, static_cast<uint8_t*>(d_px), reinterpret_cast<const ResizeFrame*>(k->d_stage + rs_at),
+                              reinterpret_cast<const int32_t*>(k->d_stage + rs_at + p.rs.size() * sizeof(ResizeFrame)), g.frames, g.c, p.wmax,
+                              p.hmax, ow, oh, s));
+    }
+    ++k->n_decode;
+    return LLCOMP_MI_OK;
+}
+
+// ... of host containers: the gather of llcomp_mi_codec_decode_regions_host with every window sized for the largest rectangle; the
+// resample table and the weights ride behind the staged payload in the same copy.
+int llcomp_mi_codec_decode_resized_regions_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens, const uint32_t* rects,
+                                                const uint8_t* flags, uint32_t ow, uint32_t oh, void* d_px, void* d_status, void* stream) {
+    if (!k || !data || !lens || !d_px || !d_status || !rects) return LLCOMP_MI_BAD_ARGS;
+    const Geometry& g = k->g;
+    ResizedPlan p;
+    if (int rc = resized_setup(k, rects, flags, ow, oh, p)) return rc;
+    RegionsGather gp;
+    if (int rc = regions_gather_plan_sized(data, lens, g.frames, rects, p.wmax, p.hmax, gp)) return rc;
+    const Geometry& cg = gp.g;
+    if (cg.w != g.w || cg.h != g.h || cg.c != g.c || cg.tile_w != g.tile_w || cg.tile_h != g.tile_h || cg.planar != g.planar ||
+        (cg.flags & kGeoSmallModel) != (g.flags & kGeoSmallModel))
+        return LLCOMP_MI_BAD_ARGS;
+    uint64_t sub_slices = 0;  // (the gather's order is the table's: class by class, and a class's slices are its sub-geometry's)
+    for (uint32_t i = 0; i < p.n_classes; ++i) sub_slices += p.classes[i].sub.n_slices;
+    if (sub_slices != gp.n_slices) return LLCOMP_MI_HIP_ERROR;
+    const StageLayout lay(g.frames, gp.n_slices, gp.payload_bytes);
+    const uint64_t rs_at = (lay.bytes + 15) & ~15ull, bytes = rs_at + p.bytes();
+    DeviceGuard guard(k->device);
+    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
+    const uint64_t samples = uint64_t(g.frames) * g.w * g.h * g.c, bound = stage_bound(g) + resized_tables_bound(g);
+    if (int rc = ensure_regions_ring(k)) return rc;
+    if (int rc = ensure_stage(k, bytes, bound)) return rc;
+    if (int rc = ensure_grown(k, k->d_box, k->box_cap, p.box_bytes, samples)) return rc;
+    if (int rc = ensure_grown(k, k->d_mid, k->mid_cap, p.mid_bytes, samples)) return rc;
+    uint32_t slot = 0;
+    if (int rc = regions_slot_take(k, bytes, bound, slot)) return rc;
+    uint8_t* h = k->h_regions[slot];
+    std::memcpy(h, p.tab.data(), p.tab.size() * sizeof(RegionsFrame));
+    regions_gather_copy(gp, data, h + lay.pay_at, reinterpret_cast<uint32_t*>(h + lay.len_at), reinterpret_cast<uint64_t*>(h + lay.off_at));
+    p.put(h + rs_at);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DoneGuard done_guard{k, s};
+    HIP_TRY(hipMemsetAsync(d_status, 0, 4, s));
+    {
+        Timed t(k, s, 4);
+        HIP_TRY(hipMemcpyAsync(k->d_stage, h, bytes, hipMemcpyHostToDevice, s));
+        if (int rc = regions_slot_queued(k, slot, s)) return rc;
+    }
+    k->host_counters[LLCOMP_MI_CTR_HOST_STAGED_BYTES] += gp.payload_bytes;
+    const RegionsSource src{k->d_stage + lay.pay_at, gp.payload_bytes, nullptr, reinterpret_cast<const uint32_t*>(k->d_stage + lay.len_at),
+                            reinterpret_cast<const uint64_t*>(k->d_stage + lay.off_at)};
+    if (int rc = regions_classes(k, p.classes, p.n_classes, reinterpret_cast<const RegionsFrame*>(k->d_stage), src, p.wmax, p.hmax, k->d_box,
+                                 static_cast<uint32_t*>(d_status), s))
+        return rc;
+    {
+        Timed t(k, s, 6);
+        HIP_TRY(launch_resize(k->d_box, k->d_mid, static_cast<uint8_t*>(d_px), reinterpret_cast<const ResizeFrame*>(k->d_stage + rs_at),
+                              reinterpret_cast<const int32_t*>(k->d_stage + rs_at + p.rs.size() * sizeof(ResizeFrame)), g.frames, g.c, p.wmax,
+                              p.hmax, ow, oh, s));
+    }
     ++k->n_decode;
     return LLCOMP_MI_OK;
 }

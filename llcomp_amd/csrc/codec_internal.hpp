@@ -49,6 +49,12 @@ struct llcomp_mi_codec {
     // (codec.hip: StageLayout); grown geometrically up to stage_bound(g), allocated by the first such call
     uint8_t* d_stage = nullptr;
     uint64_t stage_cap = 0;
+    // resized regions decode (llcomp_mi_codec_decode_resized_regions): every frame's box [frames][bh][bw][c] and the horizontal pass's
+    // rows [frames][bh][ow][c], each grown geometrically (LLCOMP_MI_PREPARE_RESIZED allocates both at frames * w * h * c)
+    uint8_t* d_box = nullptr;
+    uint64_t box_cap = 0;
+    uint8_t* d_mid = nullptr;
+    uint64_t mid_cap = 0;
     void* d_snap_sorted = nullptr;   // snapshot pass of the 2-D encoder (snapshot.hpp): banks in context-sorted order,
     void* d_snap_banks = nullptr;    // banks in stream order, residuals in stream order; null unless snapshot_mode(g)
     void* d_snap_res = nullptr;

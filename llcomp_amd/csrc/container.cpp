@@ -2,6 +2,7 @@
 // Host-only logic (no kernels, no coded bytes are produced here): it moves slice tables and payloads around.
 #include "container.hpp"
 
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -29,6 +30,20 @@ int regions_gather_plan(const uint8_t* const* data, const size_t* lens, uint32_t
                         RegionsGather& p) {
     p = RegionsGather{};
     if (!data || !lens || !xy || !n) return LLCOMP_MI_BAD_ARGS;
+    std::vector<uint32_t> rects(4 * size_t(n));
+    for (uint32_t f = 0; f < n; ++f) {
+        rects[4 * f + 0] = xy[2 * f];
+        rects[4 * f + 1] = xy[2 * f + 1];
+        rects[4 * f + 2] = rw;
+        rects[4 * f + 3] = rh;
+    }
+    return regions_gather_plan_sized(data, lens, n, rects.data(), rw, rh, p);
+}
+
+int regions_gather_plan_sized(const uint8_t* const* data, const size_t* lens, uint32_t n, const uint32_t* rects, uint32_t wmax, uint32_t hmax,
+                              RegionsGather& p) {
+    p = RegionsGather{};
+    if (!data || !lens || !rects || !n) return LLCOMP_MI_BAD_ARGS;
     llcomp_mi_info i0{};
     std::vector<uint32_t> cls(n), first_run(n + 1);
     std::vector<GatherRun> runs;  // frame order
@@ -48,7 +63,9 @@ int regions_gather_plan(const uint8_t* const* data, const size_t* lens, uint32_t
             return LLCOMP_MI_BAD_ARGS;
         }
         RegionBox win;
-        if (!regions_window(a.width, a.height, a.tile_w, a.tile_h, xy[2 * f], xy[2 * f + 1], rw, rh, win, cls[f])) return LLCOMP_MI_BAD_ARGS;
+        if (!regions_window_sized(a.width, a.height, a.tile_w, a.tile_h, rects[4 * f], rects[4 * f + 1], rects[4 * f + 2], rects[4 * f + 3], wmax,
+                                  hmax, win, cls[f]))
+            return LLCOMP_MI_BAD_ARGS;
         seen |= 1u << cls[f];
         // one window tile row = (wx1 - wx0) * planes consecutive slices; the table is summed up to the end of the last one only
         const uint32_t planes = a.planar ? a.channels : 1u, per_row = (win.tx1 - win.tx0) * planes;
@@ -209,6 +226,36 @@ int llcomp_mi_regions_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, 
             windows[4 * f + 2] = b.tx1;
             windows[4 * f + 3] = b.ty1;
         }
+    }
+    *n_classes = uint32_t(__builtin_popcount(seen));
+    return LLCOMP_MI_OK;
+}
+
+int llcomp_mi_resized_regions_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar, const uint32_t* rects,
+                                   uint32_t n, uint32_t* windows, uint32_t* n_classes) {
+    (void)planar;
+    if (!rects || !n || !n_classes || c < 1 || c > kMaxChannels) return LLCOMP_MI_BAD_ARGS;
+    uint32_t wmax = 0, hmax = 0;
+    for (uint32_t f = 0; f < n; ++f) {
+        wmax = std::max(wmax, rects[4 * f + 2]);
+        hmax = std::max(hmax, rects[4 * f + 3]);
+    }
+    uint32_t seen = 0;
+    for (uint32_t f = 0; f < n; ++f) {  // (every rectangle is checked before anything is written)
+        RegionBox b;
+        uint32_t cls = 0;
+        if (!regions_window_sized(w, h, tile_w, tile_h, rects[4 * f], rects[4 * f + 1], rects[4 * f + 2], rects[4 * f + 3], wmax, hmax, b, cls))
+            return LLCOMP_MI_BAD_ARGS;
+        seen |= 1u << cls;
+    }
+    for (uint32_t f = 0; f < n && windows; ++f) {
+        RegionBox b;
+        uint32_t cls = 0;
+        (void)regions_window_sized(w, h, tile_w, tile_h, rects[4 * f], rects[4 * f + 1], rects[4 * f + 2], rects[4 * f + 3], wmax, hmax, b, cls);
+        windows[4 * f + 0] = b.tx0;
+        windows[4 * f + 1] = b.ty0;
+        windows[4 * f + 2] = b.tx1;
+        windows[4 * f + 3] = b.ty1;
     }
     *n_classes = uint32_t(__builtin_popcount(seen));
     return LLCOMP_MI_OK;

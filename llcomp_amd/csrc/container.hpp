@@ -36,6 +36,10 @@ struct RegionsGather {
 // every check of llcomp_mi_regions_gather; nothing is copied
 int regions_gather_plan(const uint8_t* const* data, const size_t* lens, uint32_t n, const uint32_t* xy, uint32_t rw, uint32_t rh,
                         RegionsGather& p);
+// ... of a rectangle of its own size per frame (rects = {x, y, rw, rh} per frame), every window sized for wmax x hmax
+// (regions_window_sized; llcomp_mi_codec_decode_resized_regions_host)
+int regions_gather_plan_sized(const uint8_t* const* data, const size_t* lens, uint32_t n, const uint32_t* rects, uint32_t wmax, uint32_t hmax,
+                              RegionsGather& p);
 // the planned bytes: payload (p.payload_bytes), slice_len (p.n_slices entries) and, when slice_off is not null, the offset of every
 // slice in `payload`
 void regions_gather_copy(const RegionsGather& p, const uint8_t* const* data, uint8_t* payload, uint32_t* slice_len, uint64_t* slice_off);

@@ -259,22 +259,29 @@ inline bool region_fits(const Geometry& full, const Geometry& sub) { return sub.
 // last tile column (row) its pixel width (height) differs, so frames fall into at most 2 x 2 classes: bit 0 = the window ends at
 // a partial last tile column, bit 1 = at a partial last tile row.  Each class is one sub-geometry.
 constexpr uint32_t kRegionsClasses = 4;
-// false for an empty rectangle or one that leaves the image (region_box); tile_w / tile_h 0 (or beyond the image) = the whole width / height
-inline bool regions_window(uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h, uint32_t x, uint32_t y, uint32_t rw, uint32_t rh,
-                           RegionBox& win, uint32_t& cls) {
+// The window of a rectangle (x, y, rw, rh) sized for a batch whose largest rectangle is wmax x hmax (rw <= wmax <= w, rh <= hmax <= h):
+// Wx from wmax, wx0 = min(x / tile_w, ntx - Wx).  It contains the rectangle's box, and a wmax x hmax box that contains the rectangle
+// fits in it.  false for an empty rectangle, one that leaves the image (region_box), or a size above wmax / hmax.
+inline bool regions_window_sized(uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h, uint32_t x, uint32_t y, uint32_t rw, uint32_t rh,
+                                 uint32_t wmax, uint32_t hmax, RegionBox& win, uint32_t& cls) {
     RegionBox b;
-    if (!region_box(w, h, tile_w, tile_h, x, y, rw, rh, b)) return false;
+    if (!region_box(w, h, tile_w, tile_h, x, y, rw, rh, b) || rw > wmax || rh > hmax || wmax > w || hmax > h) return false;
     if (tile_w == 0 || tile_w > w) tile_w = w;
     if (tile_h == 0 || tile_h > h) tile_h = h;
     const uint32_t ntx = uint32_t((uint64_t(w) + tile_w - 1) / tile_w), nty = uint32_t((uint64_t(h) + tile_h - 1) / tile_h);
-    const uint32_t wx = uint32_t(std::min<uint64_t>(ntx, (uint64_t(rw) + tile_w - 2) / tile_w + 1));
-    const uint32_t wy = uint32_t(std::min<uint64_t>(nty, (uint64_t(rh) + tile_h - 2) / tile_h + 1));
+    const uint32_t wx = uint32_t(std::min<uint64_t>(ntx, (uint64_t(wmax) + tile_w - 2) / tile_w + 1));
+    const uint32_t wy = uint32_t(std::min<uint64_t>(nty, (uint64_t(hmax) + tile_h - 2) / tile_h + 1));
     win.tx0 = std::min(x / tile_w, ntx - wx);
     win.ty0 = std::min(y / tile_h, nty - wy);
     win.tx1 = win.tx0 + wx;
     win.ty1 = win.ty0 + wy;
     cls = (w % tile_w != 0 && win.tx1 == ntx ? 1u : 0u) | (h % tile_h != 0 && win.ty1 == nty ? 2u : 0u);
     return true;
+}
+// false for an empty rectangle or one that leaves the image (region_box); tile_w / tile_h 0 (or beyond the image) = the whole width / height
+inline bool regions_window(uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h, uint32_t x, uint32_t y, uint32_t rw, uint32_t rh,
+                           RegionBox& win, uint32_t& cls) {
+    return regions_window_sized(w, h, tile_w, tile_h, x, y, rw, rh, rw, rh, win, cls);
 }
 // One class's sub-geometry: region_geometry of its window, with the class's frame count.
 inline bool regions_geometry(const Geometry& full, const RegionBox& win, uint32_t frames, const Tuning& tune, Geometry& sub) {

@@ -1,0 +1,229 @@
+// resize_kernels.hip -- the resampling of a resized regions decode (llcomp_mi_codec_decode_resized_regions): every frame's rectangle,
+// cut from its box by the regions decode, to one output shape with the triangle filter with antialiasing (PIL's bilinear, torch's
+// interpolate(mode="bilinear", align_corners=False, antialias=True)) in Q22 integers, horizontal pass first, rounded to u8 in between.
+// The rule is include/llcomp_mi.h's llcomp_mi_resize_weights; the GPU runs exactly the weights resize_weights computes.
+#include "resize.hpp"
+
+#include <algorithm>
+#include <cmath>
+
+#include "../../include/llcomp_mi.h"
+
+namespace llcomp_mi {
+
+// One pass over the outputs: every output's lo and its Q22 run (at most `span` taps) into lo_all / q_all, and K.
+static uint32_t weights_pass(uint32_t in_len, uint32_t out_len, std::vector<uint32_t>& lo_all, std::vector<int32_t>& q_all, uint32_t& span) {
+    const double scale = double(in_len) / double(out_len), support = std::max(scale, 1.0), ss = 1.0 / support;
+    span = uint32_t(std::ceil(2.0 * support)) + 2;
+    lo_all.resize(out_len);
+    q_all.assign(size_t(out_len) * span, 0);
+    double w[2 * kResizeMaxDown + 4];
+    uint32_t k = 1;
+    for (uint32_t i = 0; i < out_len; ++i) {
+        const double center = (i + 0.5) * scale;
+        const int64_t a = std::max<int64_t>(int64_t(center - support + 0.5), 0);
+        const int64_t b = std::min<int64_t>(int64_t(center + support + 0.5), in_len);
+        const uint32_t n = uint32_t(std::min<int64_t>(std::max<int64_t>(b - a, 0), span));
+        double sum = 0.0;
+        for (uint32_t j = 0; j < n; ++j) {
+            w[j] = std::max(0.0, 1.0 - std::fabs((double(a + int64_t(j)) - center + 0.5) * ss));
+            sum += w[j];
+        }
+        int32_t* q = q_all.data() + size_t(i) * span;
+        uint32_t last = 0;
+        for (uint32_t j = 0; j < n; ++j) {
+            q[j] = sum > 0.0 ? int32_t(std::floor(0.5 + w[j] / sum * double(1 << 22))) : 0;
+            if (q[j]) last = j + 1;
+        }
+        lo_all[i] = uint32_t(a);
+        k = std::max(k, last);
+    }
+    return k;
+}
+
+uint32_t resize_weights(uint32_t in_len, uint32_t out_len, uint32_t* lo, int32_t* q) {
+    if (!in_len || !out_len || uint64_t(in_len) > uint64_t(kResizeMaxDown) * out_len) return 0;
+    std::vector<uint32_t> lo_all;
+    std::vector<int32_t> q_all;
+    uint32_t span = 0;
+    const uint32_t k = weights_pass(in_len, out_len, lo_all, q_all, span);
+    for (uint32_t i = 0; i < out_len; ++i) {
+        if (lo) lo[i] = lo_all[i];
+        if (q)
+            for (uint32_t j = 0; j < k; ++j) q[size_t(i) * k + j] = q_all[size_t(i) * span + j];
+    }
+    return k;
+}
+
+// One axis for the kernels: lo moved left over zero weights until lo + k <= in_len, weights tap-major.  An axis already in `w` (the
+// same in_len -> out_len earlier in the call: `seen` holds {in_len, out_len, k, at} of each) is shared, not computed again.
+static uint32_t axis_weights(uint32_t in_len, uint32_t out_len, std::vector<int32_t>& w, uint32_t& at, std::vector<uint32_t>& seen) {
+    if (!in_len || !out_len || uint64_t(in_len) > uint64_t(kResizeMaxDown) * out_len) return 0;
+    for (size_t i = 0; i + 4 <= seen.size(); i += 4)
+        if (seen[i] == in_len && seen[i + 1] == out_len) {
+            at = seen[i + 3];
+            return seen[i + 2];
+        }
+    thread_local std::vector<uint32_t> lo;  // (scratch, reused from call to call)
+    thread_local std::vector<int32_t> q;
+    uint32_t span = 0;
+    const uint32_t k = weights_pass(in_len, out_len, lo, q, span);
+    at = uint32_t(w.size());
+    w.resize(w.size() + size_t(out_len) * (k + 1), 0);
+    int32_t* l = w.data() + at;
+    int32_t* t = l + out_len;
+    for (uint32_t i = 0; i < out_len; ++i) {
+        const uint32_t a = std::min(lo[i], in_len - k), s = lo[i] - a;  // (k <= in_len: every run lies inside [0, in_len))
+        l[i] = int32_t(a);
+        for (uint32_t j = 0; j + s < k; ++j) t[size_t(j + s) * out_len + i] = q[size_t(i) * span + j];
+    }
+    seen.insert(seen.end(), {in_len, out_len, k, at});
+    return k;
+}
+
+bool resize_frame_weights(uint32_t rw, uint32_t rh, uint32_t ow, uint32_t oh, ResizeFrame& e, std::vector<int32_t>& w, std::vector<uint32_t>& seen) {
+    e.rw = rw;
+    e.rh = rh;
+    e.kx = axis_weights(rw, ow, w, e.hx, seen);
+    e.ky = axis_weights(rh, oh, w, e.vy, seen);
+    return e.kx && e.ky;
+}
+
+namespace {
+
+__device__ __forceinline__ uint32_t q22_round(int32_t acc) { return uint32_t(min((acc + (1 << 21)) >> 22, 255)); }
+
+// Horizontal pass: one lane per (frame, rectangle row, output x), all channels; lanes of a row read neighbouring weights (tap-major).
+template <int C>
+__global__ __launch_bounds__(256) void k_resize_h(const uint8_t* __restrict__ box, uint8_t* __restrict__ mid, const ResizeFrame* __restrict__ tab,
+                                                  const int32_t* __restrict__ wts, uint32_t bw, uint32_t bh, uint32_t ow, uint32_t c_rt) {
+    const uint32_t c = C ? uint32_t(C) : c_rt;
+    const uint32_t f = blockIdx.y;
+    const ResizeFrame& e = tab[f];
+    const uint32_t rh = e.rh, kx = e.kx;
+    const uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= uint64_t(rh) * ow) return;
+    const uint32_t r = uint32_t(i / ow), x = uint32_t(i - uint64_t(r) * ow);
+    const int32_t* lo = wts + e.hx;
+    const int32_t* q = lo + ow + x;
+    const uint8_t* src = box + ((size_t(f) * bh + e.oy + r) * bw + e.ox + uint32_t(lo[x])) * c;
+    uint8_t* dst = mid + ((size_t(f) * bh + r) * ow + x) * c;
+    if constexpr (C == 4) {
+        int32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+        for (uint32_t j = 0; j < kx; ++j) {
+            const int32_t wj = q[size_t(j) * ow];
+            const uint32_t p = *reinterpret_cast<const uint32_t*>(src + 4 * j);
+            a0 += wj * int32_t(p & 0xFF);
+            a1 += wj * int32_t((p >> 8) & 0xFF);
+            a2 += wj * int32_t((p >> 16) & 0xFF);
+            a3 += wj * int32_t(p >> 24);
+        }
+        *reinterpret_cast<uint32_t*>(dst) = q22_round(a0) | (q22_round(a1) << 8) | (q22_round(a2) << 16) | (q22_round(a3) << 24);
+    } else if constexpr (C == 3) {
+        int32_t a0 = 0, a1 = 0, a2 = 0;
+        for (uint32_t j = 0; j < kx; ++j) {
+            const int32_t wj = q[size_t(j) * ow];
+            a0 += wj * int32_t(src[3 * j]);
+            a1 += wj * int32_t(src[3 * j + 1]);
+            a2 += wj * int32_t(src[3 * j + 2]);
+        }
+        dst[0] = uint8_t(q22_round(a0));
+        dst[1] = uint8_t(q22_round(a1));
+        dst[2] = uint8_t(q22_round(a2));
+    } else {
+        for (uint32_t ch = 0; ch < c; ++ch) {
+            int32_t a = 0;
+            for (uint32_t j = 0; j < kx; ++j) a += q[size_t(j) * ow] * int32_t(src[size_t(j) * c + ch]);
+            dst[ch] = uint8_t(q22_round(a));
+        }
+    }
+}
+
+// Vertical pass: one lane per output pixel, coalesced along x; a row's weights are the same for all its lanes.  The mirror is applied
+// on the store.
+template <int C>
+__global__ __launch_bounds__(256) void k_resize_v(const uint8_t* __restrict__ mid, uint8_t* __restrict__ out, const ResizeFrame* __restrict__ tab,
+                                                  const int32_t* __restrict__ wts, uint32_t bh, uint32_t ow, uint32_t oh, uint32_t c_rt) {
+    const uint32_t c = C ? uint32_t(C) : c_rt;
+    const uint32_t f = blockIdx.y;
+    const ResizeFrame& e = tab[f];
+    const uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= uint64_t(oh) * ow) return;
+    const uint32_t y = uint32_t(i / ow), x = uint32_t(i - uint64_t(y) * ow), ky = e.ky;
+    const int32_t* lo = wts + e.vy;
+    const int32_t* q = lo + oh + y;
+    const size_t stride = size_t(ow) * c;
+    const uint8_t* src = mid + ((size_t(f) * bh + uint32_t(lo[y])) * ow + x) * c;
+    const uint32_t xo = (e.flags & 1u) ? ow - 1 - x : x;
+    uint8_t* dst = out + ((size_t(f) * oh + y) * ow + xo) * c;
+    if constexpr (C == 4) {
+        int32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+        for (uint32_t j = 0; j < ky; ++j) {
+            const int32_t wj = q[size_t(j) * oh];
+            const uint32_t p = *reinterpret_cast<const uint32_t*>(src + j * stride);
+            a0 += wj * int32_t(p & 0xFF);
+            a1 += wj * int32_t((p >> 8) & 0xFF);
+            a2 += wj * int32_t((p >> 16) & 0xFF);
+            a3 += wj * int32_t(p >> 24);
+        }
+        *reinterpret_cast<uint32_t*>(dst) = q22_round(a0) | (q22_round(a1) << 8) | (q22_round(a2) << 16) | (q22_round(a3) << 24);
+    } else if constexpr (C == 3) {
+        int32_t a0 = 0, a1 = 0, a2 = 0;
+        for (uint32_t j = 0; j < ky; ++j) {
+            const int32_t wj = q[size_t(j) * oh];
+            const uint8_t* p = src + j * stride;
+            a0 += wj * int32_t(p[0]);
+            a1 += wj * int32_t(p[1]);
+            a2 += wj * int32_t(p[2]);
+        }
+        dst[0] = uint8_t(q22_round(a0));
+        dst[1] = uint8_t(q22_round(a1));
+        dst[2] = uint8_t(q22_round(a2));
+    } else {
+        for (uint32_t ch = 0; ch < c; ++ch) {
+            int32_t a = 0;
+            for (uint32_t j = 0; j < ky; ++j) a += q[size_t(j) * oh] * int32_t(src[j * stride + ch]);
+            dst[ch] = uint8_t(q22_round(a));
+        }
+    }
+}
+
+}  // namespace
+
+hipError_t launch_resize(const uint8_t* d_box, uint8_t* d_mid, uint8_t* d_px, const ResizeFrame* d_tab, const int32_t* d_w, uint32_t frames,
+                         uint32_t c, uint32_t bw, uint32_t bh, uint32_t ow, uint32_t oh, hipStream_t stream) {
+    if (!frames || !c || !bw || !bh || !ow || !oh || frames > 65535) return hipErrorInvalidValue;
+    const uint64_t hb = (uint64_t(bh) * ow + 255) / 256, vb = (uint64_t(oh) * ow + 255) / 256;
+    if (hb > 0x7FFFFFFFull || vb > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const dim3 gh(uint32_t(hb), frames), gv(uint32_t(vb), frames), blk(256);
+    // (the box and the intermediate are the codec's own, 4-byte aligned; the output is the caller's: 32-bit stores only when aligned)
+    const bool out4 = (reinterpret_cast<uintptr_t>(d_px) & 3u) == 0;
+    switch (c) {
+        case 1:
+            k_resize_h<1><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, ow, c);
+            k_resize_v<1><<<gv, blk, 0, stream>>>(d_mid, d_px, d_tab, d_w, bh, ow, oh, c);
+            break;
+        case 3:
+            k_resize_h<3><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, ow, c);
+            k_resize_v<3><<<gv, blk, 0, stream>>>(d_mid, d_px, d_tab, d_w, bh, ow, oh, c);
+            break;
+        case 4:
+            k_resize_h<4><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, ow, c);
+            if (out4)
+                k_resize_v<4><<<gv, blk, 0, stream>>>(d_mid, d_px, d_tab, d_w, bh, ow, oh, c);
+            else
+                k_resize_v<0><<<gv, blk, 0, stream>>>(d_mid, d_px, d_tab, d_w, bh, ow, oh, c);
+            break;
+        default:
+            k_resize_h<0><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, ow, c);
+            k_resize_v<0><<<gv, blk, 0, stream>>>(d_mid, d_px, d_tab, d_w, bh, ow, oh, c);
+            break;
+    }
+    return hipGetLastError();
+}
+
+}  // namespace llcomp_mi
+
+extern "C" uint32_t llcomp_mi_resize_weights(uint32_t in_len, uint32_t out_len, uint32_t* lo, int32_t* q) {
+    return llcomp_mi::resize_weights(in_len, out_len, lo, q);
+}

@@ -8,6 +8,7 @@
 //   encode  H2D frame -> kernels -> D2H {payload bytes, status} (16 B, event e1) -> D2H container of the EXACT size (event e2)
 //   decode  H2D container -> kernels -> D2H frame + status (event e2)
 //   regions H2D the windows' bytes of the containers (llcomp_mi_codec_decode_regions_host) -> kernels -> D2H crops + status (event e2)
+//   resized the same with the crops resampled to one shape (llcomp_mi_codec_decode_resized_regions_host)
 // The size of a container is known on the GPU only.  Nobody waits for it at submit time: the 16-byte mailbox copy is
 // queued behind the kernels and whoever enters the library next (submit, wait or poll) looks at the events of the
 // jobs in flight ("pump") and queues the container copies whose size has arrived; wait() blocks on the EVENT that comes
@@ -386,6 +387,37 @@ int llcomp_mi_stream_submit_decode_regions(llcomp_mi_stream* s, const uint8_t* c
     return LLCOMP_MI_OK;
 }
 
+// A job of resized crops: as a job of crops, with the output resampled to ow x oh on the lane's codec.  The output lands in the lane's
+// frame buffer and the slot's pinned output: more than raw * fpj bytes is BAD_ARGS before anything is queued.
+int llcomp_mi_stream_submit_decode_resized_regions(llcomp_mi_stream* s, const uint8_t* const* data, const size_t* lens, const uint32_t* rects,
+                                                   const uint8_t* flags, uint32_t ow, uint32_t oh, uint64_t tag) {
+    if (!s || !data || !lens || !rects) return LLCOMP_MI_BAD_ARGS;
+    if (!s->subs.empty())
+        return deal(s, [&](llcomp_mi_stream* sub) { return llcomp_mi_stream_submit_decode_resized_regions(sub, data, lens, rects, flags, ow, oh, tag); });
+    std::lock_guard<std::mutex> lock(s->mu);
+    const uint64_t bytes = uint64_t(ow) * oh * s->c * s->fpj;
+    if (bytes > s->raw * s->fpj || bytes > s->out_cap) return LLCOMP_MI_BAD_ARGS;
+    DeviceGuard guard(s->device);
+    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
+    pump(s);
+    const int i = free_slot(s);
+    if (i < 0) return LLCOMP_MI_BUSY;
+    Slot& sl = s->slots[size_t(i)];
+    HostLane* l = sl.lane;
+    if (int rc = llcomp_mi_codec_decode_resized_regions_host(l->k, data, lens, rects, flags, ow, oh, l->d_px, l->d_meta + 1, l->stream))
+        return drained(l, rc);
+    if (hipMemcpyAsync(l->h_meta, l->d_meta, 16, hipMemcpyDeviceToHost, l->stream) != hipSuccess ||
+        hipMemcpyAsync(sl.h_out, l->d_px, bytes, hipMemcpyDeviceToHost, l->stream) != hipSuccess || hipEventRecord(sl.e2, l->stream) != hipSuccess)
+        return drained(l, LLCOMP_MI_HIP_ERROR);
+    sl.state = kCopying;
+    sl.kind = LLCOMP_MI_JOB_DECODE_RESIZED_REGIONS;
+    sl.tag = tag;
+    sl.status = LLCOMP_MI_OK;
+    sl.out_len = bytes;
+    s->fifo.push_back(uint32_t(i));
+    return LLCOMP_MI_OK;
+}
+
 uint32_t llcomp_mi_stream_frames_per_job(const llcomp_mi_stream* s) { return s ? s->fpj : 0; }
 
 int llcomp_mi_stream_result_part(llcomp_mi_stream* s, uint32_t slot, uint32_t frame, const uint8_t** data, uint64_t* len) {
@@ -398,7 +430,7 @@ int llcomp_mi_stream_result_part(llcomp_mi_stream* s, uint32_t slot, uint32_t fr
     if (sl.kind == LLCOMP_MI_JOB_ENCODE) {
         *data = sl.h_out + sl.part_off[frame];
         *len = sl.part_len[frame];
-    } else if (sl.kind == LLCOMP_MI_JOB_DECODE_REGIONS) {
+    } else if (sl.kind == LLCOMP_MI_JOB_DECODE_REGIONS || sl.kind == LLCOMP_MI_JOB_DECODE_RESIZED_REGIONS) {
         *len = sl.out_len / s->fpj;
         *data = sl.h_out + *len * frame;
     } else {
@@ -510,7 +542,8 @@ int llcomp_mi_stream_wait(llcomp_mi_stream* s, llcomp_mi_stream_result* r) {
             if (owner == &sl) break;
         }
     }
-    if (sl.state == kCopying && (sl.kind == LLCOMP_MI_JOB_DECODE || sl.kind == LLCOMP_MI_JOB_DECODE_REGIONS))
+    if (sl.state == kCopying &&
+        (sl.kind == LLCOMP_MI_JOB_DECODE || sl.kind == LLCOMP_MI_JOB_DECODE_REGIONS || sl.kind == LLCOMP_MI_JOB_DECODE_RESIZED_REGIONS))
         sl.status = status_from_bits(uint32_t(sl.lane->h_meta[1]));
     s->fifo.pop_front();
     sl.state = kHeld;
