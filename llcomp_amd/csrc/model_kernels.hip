@@ -816,8 +816,9 @@ __global__ __launch_bounds__(256) void k_model_rows_fwd(const Geometry g, const 
         if (tt < ntiles) {
             const long long start = (long long)tiles[tt].base + (long long)(int(k0) - 2) * C;  // may be < 0 for the first run
             const unsigned long long a0u = (unsigned long long)(start & ~3ll);
-            const long long a0 = (long long)((unsigned long long)__builtin_amdgcn_readfirstlane(uint32_t(a0u)) |
-                                             ((unsigned long long)__builtin_amdgcn_readfirstlane(uint32_t(a0u >> 32)) << 32));
+            // (readfirstlane returns an int: through uint32_t, or a low word at or past 2^31 would sign-extend over the high word)
+            const long long a0 = (long long)((unsigned long long)uint32_t(__builtin_amdgcn_readfirstlane(uint32_t(a0u))) |
+                                             ((unsigned long long)uint32_t(__builtin_amdgcn_readfirstlane(uint32_t(a0u >> 32))) << 32));
             if (a0 >= 0 && size_t(a0) + 4 * size_t(RUNW) <= total_bytes) {
 #pragma unroll
                 for (int e = 0; e < DPT; ++e) {
