@@ -31,7 +31,8 @@ extern "C" {
  * of host containers -- llcomp_mi_regions_gather, llcomp_mi_codec_decode_regions_host, llcomp_mi_stream_submit_decode_regions,
  * LLCOMP_MI_JOB_DECODE_REGIONS, LLCOMP_MI_CTR_HOST_STAGED_BYTES; crops of different sizes resized to one shape -- llcomp_mi_resize_weights,
  * llcomp_mi_resized_regions_plan, llcomp_mi_codec_decode_resized_regions(_host), llcomp_mi_stream_submit_decode_resized_regions,
- * LLCOMP_MI_PREPARE_RESIZED, LLCOMP_MI_JOB_DECODE_RESIZED_REGIONS, llcomp_mi_codec_allocated_bytes).  The library and its callers are built from ONE header: structs have one layout per ABI version (llcomp_mi_opts is
+ * LLCOMP_MI_PREPARE_RESIZED, LLCOMP_MI_JOB_DECODE_RESIZED_REGIONS, llcomp_mi_codec_allocated_bytes; their output as a model takes it,
+ * float or normalised, CHW or HWC -- llcomp_mi_output_format, llcomp_mi_output_table and the _ex forms of the three resized calls).  The library and its callers are built from ONE header: structs have one layout per ABI version (llcomp_mi_opts is
  * checked through struct_size and refused when it differs; llcomp_mi_info and llcomp_mi_stream_result are written in full),
  * so a binding compares llcomp_mi_abi_version() with the LLCOMP_MI_ABI_VERSION it was generated from and refuses to run on
  * a mismatch -- there is no cross-version compatibility mode. */
@@ -229,6 +230,27 @@ uint32_t llcomp_mi_resize_weights(uint32_t in_len, uint32_t out_len, uint32_t* l
  * empty or outside the image.  Host-only. */
 int llcomp_mi_resized_regions_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar, const uint32_t* rects,
                                    uint32_t n, uint32_t* windows, uint32_t* n_classes);
+/* The output of a resized regions decode as a model takes it (the _ex calls below): the element type, the layout, and torchvision's
+ * ToTensor() + Normalize(mean, std).  The rule, for the u8 value v the u8 call writes for output pixel (f, y, x) and channel ch (the
+ * mirror included), in IEEE binary32 with no fused operations, in this order:
+ *   t = (float)v;  if scale: t = t / 255.0f (a division);  if mean: t = t - mean[ch];  if std: t = t / std[ch];
+ *   F32: t;  F16 / BF16: t rounded to nearest even (overflow to +-inf);  U8: v.
+ * Normalisation comes after the u8 rounding of the resample.  v takes 256 values: the rule is a table of c x 256 entries, which
+ * llcomp_mi_output_table states and the GPU only looks up.  A NULL format is U8 HWC: the u8 call's bytes. */
+enum { LLCOMP_MI_DTYPE_U8 = 0, LLCOMP_MI_DTYPE_F32 = 1, LLCOMP_MI_DTYPE_F16 = 2, LLCOMP_MI_DTYPE_BF16 = 3 };
+enum { LLCOMP_MI_LAYOUT_HWC = 0, LLCOMP_MI_LAYOUT_CHW = 1 };
+typedef struct llcomp_mi_output_format {
+    uint32_t struct_size; /* sizeof(llcomp_mi_output_format) (at least) */
+    uint32_t dtype;       /* LLCOMP_MI_DTYPE_* */
+    uint32_t layout;      /* HWC: [frames][oh][ow][c]; CHW: [frames][c][oh][ow] */
+    uint32_t scale;       /* 1: divide by 255 first (float dtypes only) */
+    const float* mean;    /* c values or NULL; read during the call only */
+    const float* std;     /* c values or NULL; read during the call only */
+} llcomp_mi_output_format; /* 32 bytes on LP64 */
+/* The rule above as a table: table[ch * 256 + v] for ch < c, elements of the dtype's size (1, 2 or 4 bytes; F16 / BF16 as their bit
+ * patterns).  BAD_ARGS for a NULL fmt or table, c = 0 or above 255, a struct_size below the struct's, an unknown dtype or layout, a scale
+ * above 1, U8 with scale, mean or std set, a mean that is not finite, a std that is 0 or not finite.  Host-only. */
+int llcomp_mi_output_table(const llcomp_mi_output_format* fmt, uint32_t c, void* table);
 uint32_t llcomp_mi_slice_count(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar);
 /* Slice width for one-row slices (tile_h = 1) when `frames` frames are coded per call: the widest slice (64..480 pixels) that
  * still keeps about four wavefronts per SIMD busy.  A call that codes few frames is latency-bound with wide slices; this
@@ -370,6 +392,17 @@ int llcomp_mi_codec_decode_resized_regions(llcomp_mi_codec* codec, const void* d
  * gather error is returned before anything is queued, LLCOMP_MI_CTR_HOST_STAGED_BYTES counts the staged payload bytes. */
 int llcomp_mi_codec_decode_resized_regions_host(llcomp_mi_codec* codec, const uint8_t* const* data, const size_t* lens, const uint32_t* rects,
                                                 const uint8_t* flags, uint32_t ow, uint32_t oh, void* d_px, void* d_status, void* stream);
+/* The two calls above with an output format (llcomp_mi_output_format; NULL = U8 HWC, the calls above exactly): d_out receives
+ * frames * oh * ow * c elements of fmt's dtype in its layout, element [f][ch][y][x] (CHW) or [f][y][x][ch] (HWC) = the table of
+ * llcomp_mi_output_table at [ch][v], v the u8 call's byte for (f, y, x, ch).  The table travels in the call's one copy, behind the
+ * weights.  BAD_ARGS, before anything is queued or written (d_status untouched): every case of the calls above, every case of the
+ * table's, and a d_out not aligned to the element size.  fmt, mean and std are read during the call only. */
+int llcomp_mi_codec_decode_resized_regions_ex(llcomp_mi_codec* codec, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                              const uint32_t* rects, const uint8_t* flags, uint32_t ow, uint32_t oh,
+                                              const llcomp_mi_output_format* fmt, void* d_out, void* d_status, void* stream);
+int llcomp_mi_codec_decode_resized_regions_host_ex(llcomp_mi_codec* codec, const uint8_t* const* data, const size_t* lens, const uint32_t* rects,
+                                                   const uint8_t* flags, uint32_t ow, uint32_t oh, const llcomp_mi_output_format* fmt,
+                                                   void* d_out, void* d_status, void* stream);
 /* Stage-A only (context + prediction model), for tests and profiling: d_sym u32[frames*h*w*c],
  * low 16 bits = folded context (0..7925), high 16 bits = folded residual (two's complement). */
 int llcomp_mi_codec_model(llcomp_mi_codec* codec, const void* d_px, void* d_sym, void* stream);
@@ -480,6 +513,11 @@ int llcomp_mi_stream_submit_decode_regions(llcomp_mi_stream* stream, const uint8
  * llcomp_mi_stream_submit_decode_regions. */
 int llcomp_mi_stream_submit_decode_resized_regions(llcomp_mi_stream* stream, const uint8_t* const* data, const size_t* lens, const uint32_t* rects,
                                                    const uint8_t* flags, uint32_t ow, uint32_t oh, uint64_t tag);
+/* ... with an output format (NULL = the call above exactly): len = frames_per_job * oh * ow * c * the dtype's size, in fmt's layout, and
+ * a job of more than frames_per_job * w * h * c bytes is BAD_ARGS at submit.  fmt, mean and std are read during the call only. */
+int llcomp_mi_stream_submit_decode_resized_regions_ex(llcomp_mi_stream* stream, const uint8_t* const* data, const size_t* lens,
+                                                      const uint32_t* rects, const uint8_t* flags, uint32_t ow, uint32_t oh,
+                                                      const llcomp_mi_output_format* fmt, uint64_t tag);
 int llcomp_mi_stream_pending(llcomp_mi_stream* stream); /* jobs submitted and not yet returned by wait */
 /* LLCOMP_MI_OK when llcomp_mi_stream_wait would not block (or nothing is pending), LLCOMP_MI_BUSY otherwise. */
 int llcomp_mi_stream_poll(llcomp_mi_stream* stream);

@@ -11,6 +11,8 @@ with ctypes and keeps the reference's names and error behaviour:
     regions_gather / Codec.decode_regions_host / Stream.submit_decode_regions  (the same from host containers: only the windows cross)
     resize_weights / resized_regions_plan / Codec.decode_resized_regions(_host) / Stream.submit_decode_resized_regions  (a rectangle of
         its own size per frame, resampled to one output shape with an optional mirror: RandomResizedCrop + RandomHorizontalFlip)
+    output_table / dtype=, layout=, scale=, mean=, std= of the three resized calls  (their output as a model takes it: float32, float16
+        or bfloat16, CHW or HWC, ToTensor() + Normalize(mean, std) -- the _ex calls and llcomp_mi_output_format)
     RawImage(pixels, width, height, channels)     <->  llcomp::RawImage         (/root/reference/llcomp.hpp:454-459)
     EXT = ".llcomp"                               <->  llcomp::ext              (/root/reference/llcomp.hpp:18)
 
@@ -23,12 +25,14 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib
-from ._lib import Info, Opts
+from ._lib import Info, Opts, OutputFormat
 
 EXT = ".llcomp"
 FORMAT_LEGACY, FORMAT_SLICED = 0, 1
 (OK, BAD_MAGIC, BAD_EXPONENT, TRUNCATED, BAD_ARGS, OUT_OF_RANGE, OUTPUT_OVERFLOW, HIP_ERROR, NO_DEVICE, NOMEM, BUSY, DEVICE_FAILED) = range(12)
 JOB_ENCODE, JOB_DECODE, JOB_DECODE_REGIONS, JOB_DECODE_RESIZED_REGIONS = 0, 1, 2, 3
+DTYPE_U8, DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2, 3
+LAYOUT_HWC, LAYOUT_CHW = 0, 1
 
 RawImage = namedtuple("RawImage", "pixels width height channels")
 
@@ -166,6 +170,68 @@ def _flags_table(flags, n):
     if a.shape != (n,) or (a.size and (a.min() < 0 or a.max() > 255)):
         raise LlcompError(BAD_ARGS, f"flags must be {n} values in 0..255, got shape {a.shape}")
     return (C.c_uint8 * n)(*[int(v) for v in a.tolist()])
+
+
+_DTYPES = {"uint8": DTYPE_U8, "u8": DTYPE_U8, "float32": DTYPE_F32, "float": DTYPE_F32, "f32": DTYPE_F32, "float16": DTYPE_F16,
+           "half": DTYPE_F16, "f16": DTYPE_F16, "bfloat16": DTYPE_BF16, "bf16": DTYPE_BF16}
+# numpy type of each dtype's elements (bfloat16: its bit patterns, numpy has no bfloat16)
+_NP_OF_DTYPE = {DTYPE_U8: np.uint8, DTYPE_F32: np.float32, DTYPE_F16: np.float16, DTYPE_BF16: np.uint16}
+
+
+def _dtype_code(dtype):
+    """None / "float32" / np.float16 / torch.bfloat16 / ... -> DTYPE_*; BAD_ARGS for anything else"""
+    if dtype is None:
+        return DTYPE_U8
+    if isinstance(dtype, (int, np.integer)) and not isinstance(dtype, bool) and int(dtype) in _NP_OF_DTYPE:
+        return int(dtype)
+    name = str(dtype).replace("torch.", "")
+    if name not in _DTYPES:
+        try:
+            name = np.dtype(dtype).name
+        except TypeError:
+            pass
+    if name not in _DTYPES:
+        raise LlcompError(BAD_ARGS, f"dtype must be uint8, float32, float16 or bfloat16, got {dtype!r}")
+    return _DTYPES[name]
+
+
+def _output_format(c, dtype=None, layout="hwc", scale=False, mean=None, std=None):
+    """(OutputFormat, numpy element type, what must stay alive during the call); the format is None where every argument is its
+    default (the u8 calls exactly).  mean / std: c values (one value is used for every channel); the library checks them."""
+    code = _dtype_code(dtype)
+    lay = {"hwc": LAYOUT_HWC, "chw": LAYOUT_CHW}.get(str(layout).lower()) if not isinstance(layout, int) else layout
+    if lay is None:
+        raise LlcompError(BAD_ARGS, f"layout must be 'hwc' or 'chw', got {layout!r}")
+    if dtype is None and lay == LAYOUT_HWC and not scale and mean is None and std is None:
+        return None, np.uint8, ()
+    keep = []
+
+    def vec(v):
+        if v is None:
+            return None
+        a = np.asarray(v, dtype=np.float32).reshape(-1)
+        if a.size == 1:
+            a = np.full(c, a[0], np.float32)
+        if a.size != c:
+            raise LlcompError(BAD_ARGS, f"mean / std take {c} values, got {a.size}")
+        arr = (C.c_float * c)(*a.tolist())
+        keep.append(arr)
+        return C.cast(arr, C.POINTER(C.c_float))
+
+    fmt = OutputFormat(C.sizeof(OutputFormat), code, lay, int(bool(scale)), vec(mean), vec(std))
+    return fmt, _NP_OF_DTYPE[code], (fmt, keep)
+
+
+def output_table(c, dtype, scale=False, mean=None, std=None):
+    """The output rule of the resized calls as a table [c, 256] (llcomp_mi_output_table, host only): entry [ch, v] is what an output in
+    this format holds where the u8 call writes v in channel ch -- float32, float16, uint8, or uint16 holding the bfloat16 bits.
+    LlcompError(BAD_ARGS) for a format the calls refuse (U8 with scale / mean / std, a mean not finite, a std 0 or not finite)."""
+    fmt, np_t, keep = _output_format(c, dtype, "hwc", scale, mean, std)
+    if fmt is None:
+        fmt, np_t, keep = _output_format(c, DTYPE_U8, "chw")
+    out = np.zeros((c, 256), np_t)
+    _check(_lib.load().llcomp_mi_output_table(C.byref(fmt), c, out.ctypes.data))
+    return out
 
 
 def resize_weights(in_len, out_len):
@@ -370,7 +436,7 @@ class Stream:
             _check(self._L.llcomp_mi_stream_create_ex(C.byref(self._h), device, w, h, c, tile_w, tile_h, int(bool(planar)), depth, frames_per_job))
         self.n_devices = self._L.llcomp_mi_stream_devices(self._h)
         self.shape = (h, w, c)
-        self._shapes = []  # the frame shape of every pending job, in submission order (results come back in that order)
+        self._shapes = []  # (frame shape, numpy element type) of every pending job, in submission order (results come back in that order)
         self.frames_per_job = frames_per_job
         self.container_capacity = self._L.llcomp_mi_stream_container_capacity(self._h)
 
@@ -381,11 +447,11 @@ class Stream:
 
     __del__ = close
 
-    def _submit(self, rc, shape=None):
+    def _submit(self, rc, shape=None, dtype=np.uint8):
         if rc == BUSY:
             return False
         _check(rc)
-        self._shapes.append(shape or self.shape)
+        self._shapes.append((shape or self.shape, dtype))
         return True
 
     def submit_encode(self, px, tag=0):
@@ -414,16 +480,24 @@ class Stream:
         rc = self._L.llcomp_mi_stream_submit_decode_regions(self._h, ptrs, lens, tab, rw, rh, tag)
         return self._submit(rc, (rh, rw, self.shape[2]))
 
-    def submit_decode_resized_regions(self, containers, rects, ow, oh, flags=None, tag=0):
+    def submit_decode_resized_regions(self, containers, rects, ow, oh, flags=None, tag=0, dtype=None, layout="hwc", scale=False, mean=None,
+                                      std=None):
         """frames_per_job containers, their rectangles rects ([frames_per_job, 4] of (x, y, rw, rh)) and optional mirror flags -> a job
-        whose .data is the output [oh,ow,c] (one frame per job) / [F,oh,ow,c].  The containers are read during this call only."""
+        whose .data is the output [oh,ow,c] (one frame per job) / [F,oh,ow,c] -- [c,oh,ow] / [F,c,oh,ow] for layout="chw" -- in
+        `dtype` (output_table: bfloat16 as uint16 bits), normalised by scale / mean / std.  The containers are read during this call
+        only."""
         ptrs, lens, keep = _containers(containers)
         if len(keep) != self.frames_per_job:
             raise LlcompError(BAD_ARGS, f"a job takes {self.frames_per_job} containers, got {len(keep)}")
         tab, _ = _rects_table(rects, self.frames_per_job)
         fl = _flags_table(flags, self.frames_per_job)
-        rc = self._L.llcomp_mi_stream_submit_decode_resized_regions(self._h, ptrs, lens, tab, fl, ow, oh, tag)
-        return self._submit(rc, (oh, ow, self.shape[2]))
+        c = self.shape[2]
+        fmt, np_t, _keep = _output_format(c, dtype, layout, scale, mean, std)
+        if fmt is None:
+            rc = self._L.llcomp_mi_stream_submit_decode_resized_regions(self._h, ptrs, lens, tab, fl, ow, oh, tag)
+        else:
+            rc = self._L.llcomp_mi_stream_submit_decode_resized_regions_ex(self._h, ptrs, lens, tab, fl, ow, oh, C.byref(fmt), tag)
+        return self._submit(rc, (c, oh, ow) if fmt is not None and fmt.layout == LAYOUT_CHW else (oh, ow, c), np_t)
 
     def pending(self):
         return self._L.llcomp_mi_stream_pending(self._h)
@@ -434,11 +508,12 @@ class Stream:
     def wait(self):
         r = _lib.StreamResult()
         _check(self._L.llcomp_mi_stream_wait(self._h, C.byref(r)))
-        shape = self._shapes.pop(0)
+        shape, np_t = self._shapes.pop(0)
         data = None
         if r.status == OK:
             whole = np.ctypeslib.as_array(C.cast(r.data, _lib.u8p), shape=(max(int(r.len), 1),))[: int(r.len)]
             if r.kind in (JOB_DECODE, JOB_DECODE_REGIONS, JOB_DECODE_RESIZED_REGIONS):
+                whole = whole.view(np_t) if np_t is not np.uint8 else whole
                 data = whole.reshape(shape) if self.frames_per_job == 1 else whole.reshape((self.frames_per_job,) + shape)
             elif self.frames_per_job == 1:
                 data = whole
@@ -673,23 +748,38 @@ class Codec:
         tab, _ = _xy_table(xy, self.frames)
         _check(self._L.llcomp_mi_codec_decode_regions_host(self._h, ptrs, lens, tab, rw, rh, d_px, d_status, stream))
 
-    def decode_resized_regions(self, d_payload, payload_bytes, d_slice_len, rects, ow, oh, d_px, d_status, flags=None, stream=0):
+    def decode_resized_regions(self, d_payload, payload_bytes, d_slice_len, rects, ow, oh, d_px, d_status, flags=None, stream=0, dtype=None,
+                               layout="hwc", scale=False, mean=None, std=None):
         """frame f's rectangle rects[f] = (x, y, rw, rh), resampled to ow x oh (and mirrored where flags[f] & 1) -> d_px
-        [frames][oh][ow][c] (llcomp_mi_codec_decode_resized_regions); rects and flags are read during the call"""
+        [frames][oh][ow][c] (llcomp_mi_codec_decode_resized_regions); rects and flags are read during the call.  dtype ("float32",
+        "float16", "bfloat16", "uint8" or the numpy / torch type), layout ("hwc" or "chw": [frames][c][oh][ow]), scale (divide by 255)
+        and mean / std (c values) give the output as a model takes it (llcomp_mi_codec_decode_resized_regions_ex; output_table
+        states the rule); d_px must be aligned to the element size."""
         tab, _ = _rects_table(rects, self.frames)
         fl = _flags_table(flags, self.frames)
-        _check(self._L.llcomp_mi_codec_decode_resized_regions(self._h, d_payload, payload_bytes, d_slice_len, tab, fl, ow, oh, d_px, d_status,
-                                                               stream))
+        fmt, _, _keep = _output_format(self.c, dtype, layout, scale, mean, std)
+        if fmt is None:
+            _check(self._L.llcomp_mi_codec_decode_resized_regions(self._h, d_payload, payload_bytes, d_slice_len, tab, fl, ow, oh, d_px, d_status,
+                                                                   stream))
+        else:
+            _check(self._L.llcomp_mi_codec_decode_resized_regions_ex(self._h, d_payload, payload_bytes, d_slice_len, tab, fl, ow, oh, C.byref(fmt),
+                                                                      d_px, d_status, stream))
 
-    def decode_resized_regions_host(self, containers, rects, ow, oh, d_px, d_status, flags=None, stream=0):
-        """decode_resized_regions of host containers (llcomp_mi_codec_decode_resized_regions_host): only the windows' bytes cross PCIe;
-        the containers, rects and flags are read during the call only"""
+    def decode_resized_regions_host(self, containers, rects, ow, oh, d_px, d_status, flags=None, stream=0, dtype=None, layout="hwc", scale=False,
+                                    mean=None, std=None):
+        """decode_resized_regions of host containers (llcomp_mi_codec_decode_resized_regions_host(_ex)): only the windows' bytes cross
+        PCIe; the containers, rects and flags are read during the call only"""
         ptrs, lens, keep = _containers(containers)
         if len(keep) != self.frames:
             raise LlcompError(BAD_ARGS, f"the codec takes {self.frames} containers, got {len(keep)}")
         tab, _ = _rects_table(rects, self.frames)
         fl = _flags_table(flags, self.frames)
-        _check(self._L.llcomp_mi_codec_decode_resized_regions_host(self._h, ptrs, lens, tab, fl, ow, oh, d_px, d_status, stream))
+        fmt, _, _keep = _output_format(self.c, dtype, layout, scale, mean, std)
+        if fmt is None:
+            _check(self._L.llcomp_mi_codec_decode_resized_regions_host(self._h, ptrs, lens, tab, fl, ow, oh, d_px, d_status, stream))
+        else:
+            _check(self._L.llcomp_mi_codec_decode_resized_regions_host_ex(self._h, ptrs, lens, tab, fl, ow, oh, C.byref(fmt), d_px, d_status,
+                                                                           stream))
 
     def allocated_bytes(self):
         """device bytes the codec holds right now (llcomp_mi_codec_allocated_bytes; at most .workspace_bytes for outputs up to the image's

@@ -34,6 +34,8 @@ SYMBOLS = [
     "llcomp_mi_regions_gather", "llcomp_mi_codec_decode_regions_host", "llcomp_mi_stream_submit_decode_regions",
     "llcomp_mi_resize_weights", "llcomp_mi_resized_regions_plan", "llcomp_mi_codec_decode_resized_regions",
     "llcomp_mi_codec_decode_resized_regions_host", "llcomp_mi_stream_submit_decode_resized_regions", "llcomp_mi_codec_allocated_bytes",
+    "llcomp_mi_output_table", "llcomp_mi_codec_decode_resized_regions_ex", "llcomp_mi_codec_decode_resized_regions_host_ex",
+    "llcomp_mi_stream_submit_decode_resized_regions_ex",
 ]
 
 u8p = C.POINTER(C.c_uint8)
@@ -43,6 +45,12 @@ class Opts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("format", C.c_uint32), ("tile_w", C.c_uint32), ("tile_h", C.c_uint32),
                 ("planar", C.c_uint32), ("device", C.c_int32), ("small_model", C.c_uint32),
                 ("n_devices", C.c_uint32), ("devices", C.POINTER(C.c_int32)), ("chunks_per_device", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class OutputFormat(C.Structure):
+    """llcomp_mi_output_format (include/llcomp_mi.h): 32 bytes, mean at 16, std at 24"""
+    _fields_ = [("struct_size", C.c_uint32), ("dtype", C.c_uint32), ("layout", C.c_uint32), ("scale", C.c_uint32),
+                ("mean", C.POINTER(C.c_float)), ("std", C.POINTER(C.c_float))]
 
 
 class Info(C.Structure):
@@ -260,6 +268,19 @@ def load():
         L.llcomp_mi_stream_submit_decode_resized_regions.argtypes = [C.c_void_p, ptrs, sizes, u32p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64]
         L.llcomp_mi_codec_allocated_bytes.restype = C.c_uint64
         L.llcomp_mi_codec_allocated_bytes.argtypes = [C.c_void_p]
+    if "LLCOMP_MI_LIB" not in os.environ or hasattr(L, "llcomp_mi_output_table"):  # ... in an output format (dtype, layout, normalisation)
+        u32p, ptrs, sizes, fmtp = C.POINTER(C.c_uint32), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(OutputFormat)
+        L.llcomp_mi_output_table.restype = C.c_int
+        L.llcomp_mi_output_table.argtypes = [fmtp, C.c_uint32, C.c_void_p]
+        L.llcomp_mi_codec_decode_resized_regions_ex.restype = C.c_int
+        L.llcomp_mi_codec_decode_resized_regions_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, u32p, C.c_void_p, C.c_uint32,
+                                                                C.c_uint32, fmtp] + [C.c_void_p] * 3
+        L.llcomp_mi_codec_decode_resized_regions_host_ex.restype = C.c_int
+        L.llcomp_mi_codec_decode_resized_regions_host_ex.argtypes = [C.c_void_p, ptrs, sizes, u32p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                                     fmtp] + [C.c_void_p] * 3
+        L.llcomp_mi_stream_submit_decode_resized_regions_ex.restype = C.c_int
+        L.llcomp_mi_stream_submit_decode_resized_regions_ex.argtypes = [C.c_void_p, ptrs, sizes, u32p, C.c_void_p, C.c_uint32, C.c_uint32, fmtp,
+                                                                        C.c_uint64]
     if "LLCOMP_MI_LIB" not in os.environ and L.llcomp_mi_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.llcomp_mi_abi_version()}, this binding was written for {ABI_VERSION}: rebuild the library")
     _lib = L

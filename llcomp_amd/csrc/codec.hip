@@ -333,8 +333,11 @@ struct StageLayout {
 uint64_t stage_bound(const Geometry& g) { return StageLayout(g.frames, g.n_slices, uint64_t(g.n_slices) * (g.slice_cap - 16)).bytes; }
 // What a resized regions decode adds to the one copy at most, for outputs no larger than the image (ow <= w, oh <= h): 16 bytes of
 // alignment, and per frame its ResizeFrame and its weights -- out * (K + 1) int32 per axis, K <= 2 * max(in / out, 1) + 3, so at most
-// 2 * max(in, out) + 4 * out <= 6 * side of the image.
-uint64_t resized_tables_bound(const Geometry& g) { return 16 + uint64_t(g.frames) * (sizeof(ResizeFrame) + 4 * 6 * (uint64_t(g.w) + g.h)); }
+// 2 * max(in, out) + 4 * out <= 6 * side of the image -- and the output format's table behind them (16 bytes of alignment, at most
+// 256 * c elements of 4 bytes).
+uint64_t resized_tables_bound(const Geometry& g) {
+    return 16 + uint64_t(g.frames) * (sizeof(ResizeFrame) + 4 * 6 * (uint64_t(g.w) + g.h)) + 16 + 256 * 4 * uint64_t(g.c);
+}
 // The staging buffer in HBM for `bytes`: grown to max(bytes, twice its size, at most `bound`) when too small (bound: stage_bound, plus
 // resized_tables_bound for a resized regions decode).  The old buffer may still be read by the codec's last call: that call is waited
 // for (only a call that grows the buffer waits).
@@ -504,24 +507,35 @@ int regions_classes(llcomp_mi_codec* k, const RegionsClass* classes, uint32_t n_
 }
 
 // Everything of a resized regions decode the host decides: every frame's window, class and box (regions_setup_sized, sized for the
-// batch's largest rectangle wmax x hmax), its rectangle inside the box, its flags and its weights (resize.hpp).  BAD_ARGS for a null
-// rects, an output side of 0, any rectangle outside the image and a downscale above kResizeMaxDown on either axis.
+// batch's largest rectangle wmax x hmax), its rectangle inside the box, its flags, its weights (resize.hpp) and the output format's table.
+// BAD_ARGS for a null rects, an output side of 0, any rectangle outside the image, a downscale above kResizeMaxDown on either axis, a bad
+// output format (check_output_format) and an output not aligned to the format's element size.
 struct ResizedPlan {
     std::vector<RegionsFrame> tab;
     RegionsClass classes[kRegionsClasses];
     uint32_t n_classes = 0, wmax = 0, hmax = 0;
     std::vector<ResizeFrame> rs;  // frame order
     std::vector<int32_t> w;
+    OutFormat out;
+    std::vector<uint8_t> table;  // empty for the plain u8 HWC output
     uint64_t box_bytes = 0, mid_bytes = 0;
-    // what the one copy carries, behind the regions table (or behind the staged payload): [ResizeFrame[frames]][int32 weights]
-    uint64_t bytes() const { return uint64_t(rs.size()) * sizeof(ResizeFrame) + 4 * uint64_t(w.size()); }
+    // what the one copy carries, behind the regions table (or behind the staged payload): [ResizeFrame[frames]][int32 weights], then the
+    // output table at the next multiple of 16 (table_at, relative to the ResizeFrames) where there is one
+    uint64_t table_at() const { return (uint64_t(rs.size()) * sizeof(ResizeFrame) + 4 * uint64_t(w.size()) + 15) & ~15ull; }
+    uint64_t bytes() const {
+        return table.empty() ? uint64_t(rs.size()) * sizeof(ResizeFrame) + 4 * uint64_t(w.size()) : table_at() + table.size();
+    }
     void put(uint8_t* at) const {
         std::memcpy(at, rs.data(), rs.size() * sizeof(ResizeFrame));
         std::memcpy(at + rs.size() * sizeof(ResizeFrame), w.data(), 4 * w.size());
+        if (!table.empty()) std::memcpy(at + table_at(), table.data(), table.size());
     }
 };
-int resized_setup(const llcomp_mi_codec* k, const uint32_t* rects, const uint8_t* flags, uint32_t ow, uint32_t oh, ResizedPlan& p) {
+int resized_setup(const llcomp_mi_codec* k, const uint32_t* rects, const uint8_t* flags, uint32_t ow, uint32_t oh, const llcomp_mi_output_format* fmt,
+                  const void* d_out, ResizedPlan& p) {
     const Geometry& g = k->g;
+    if (int rc = check_output_format(fmt, g.c, p.out)) return rc;
+    if (reinterpret_cast<uintptr_t>(d_out) & (p.out.esize - 1)) return LLCOMP_MI_BAD_ARGS;
     if (!rects || !ow || !oh || g.frames > 65535) return LLCOMP_MI_BAD_ARGS;
     for (uint32_t f = 0; f < g.frames; ++f) {
         const uint32_t rw = rects[4 * f + 2], rh = rects[4 * f + 3];
@@ -544,6 +558,8 @@ int resized_setup(const llcomp_mi_codec* k, const uint32_t* rects, const uint8_t
     }
     p.box_bytes = uint64_t(g.frames) * p.wmax * p.hmax * g.c;
     p.mid_bytes = uint64_t(g.frames) * p.hmax * ow * g.c;
+    p.table.resize(p.out.table_bytes(g.c));
+    if (!p.table.empty()) output_table(fmt, g.c, p.out, p.table.data());
     return LLCOMP_MI_OK;
 }
 
@@ -1080,13 +1096,14 @@ int llcomp_mi_codec_decode_regions_host(llcomp_mi_codec* k, const uint8_t* const
 // Resized regions decode (DESIGN.md "Crops of different sizes, resized to one shape"): the regions decode's classes, unchanged, crop
 // every frame's box (the batch's largest rectangle size) into d_box; then the two resample passes read every frame's rectangle from its
 // box and write d_px.  The regions table, the resample table and the weights cross in ONE copy from a slot of the pinned ring to d_stage.
-int llcomp_mi_codec_decode_resized_regions(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
-                                           const uint32_t* rects, const uint8_t* flags, uint32_t ow, uint32_t oh, void* d_px, void* d_status,
-                                           void* stream) {
+// The output format's table rides behind the weights (ResizedPlan::table_at) and the vertical pass looks every value up in it.
+int llcomp_mi_codec_decode_resized_regions_ex(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                              const uint32_t* rects, const uint8_t* flags, uint32_t ow, uint32_t oh,
+                                              const llcomp_mi_output_format* fmt, void* d_px, void* d_status, void* stream) {
     if (!k || !d_payload || !d_slice_len || !d_px || !d_status || !rects) return LLCOMP_MI_BAD_ARGS;
     const Geometry& g = k->g;
     ResizedPlan p;
-    if (int rc = resized_setup(k, rects, flags, ow, oh, p)) return rc;
+    if (int rc = resized_setup(k, rects, flags, ow, oh, fmt, d_px, p)) return rc;
     const uint64_t rs_at = (uint64_t(g.frames) * sizeof(RegionsFrame) + 15) & ~15ull, bytes = rs_at + p.bytes();
     DeviceGuard guard(k->device);
     if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
@@ -1117,9 +1134,9 @@ int llcomp_mi_codec_decode_resized_regions(llcomp_mi_codec* k, const void* d_pay
         return rc;
     {
         Timed t(k, s, 6);
-        HIP_TRY(launch_resize(k->d_box, k->d_mid, static_cast<uint8_t*>(d_px), reinterpret_cast<const ResizeFrame*>(k->d_stage + rs_at),
-                              reinterpret_cast<const int32_t*>(k->d_stage + rs_at + p.rs.size() * sizeof(ResizeFrame)), g.frames, g.c, p.wmax,
-                              p.hmax, ow, oh, s));
+        HIP_TRY(launch_resize_out(k->d_box, k->d_mid, d_px, reinterpret_cast<const ResizeFrame*>(k->d_stage + rs_at),
+                                  reinterpret_cast<const int32_t*>(k->d_stage + rs_at + p.rs.size() * sizeof(ResizeFrame)),
+                                  k->d_stage + rs_at + p.table_at(), p.out, g.frames, g.c, p.wmax, p.hmax, ow, oh, s));
     }
     ++k->n_decode;
     return LLCOMP_MI_OK;
@@ -1127,12 +1144,13 @@ int llcomp_mi_codec_decode_resized_regions(llcomp_mi_codec* k, const void* d_pay
 
 // ... of host containers: the gather of llcomp_mi_codec_decode_regions_host with every window sized for the largest rectangle; the
 // resample table and the weights ride behind the staged payload in the same copy.
-int llcomp_mi_codec_decode_resized_regions_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens, const uint32_t* rects,
-                                                const uint8_t* flags, uint32_t ow, uint32_t oh, void* d_px, void* d_status, void* stream) {
+int llcomp_mi_codec_decode_resized_regions_host_ex(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens, const uint32_t* rects,
+                                                   const uint8_t* flags, uint32_t ow, uint32_t oh, const llcomp_mi_output_format* fmt,
+                                                   void* d_px, void* d_status, void* stream) {
     if (!k || !data || !lens || !d_px || !d_status || !rects) return LLCOMP_MI_BAD_ARGS;
     const Geometry& g = k->g;
     ResizedPlan p;
-    if (int rc = resized_setup(k, rects, flags, ow, oh, p)) return rc;
+    if (int rc = resized_setup(k, rects, flags, ow, oh, fmt, d_px, p)) return rc;
     RegionsGather gp;
     if (int rc = regions_gather_plan_sized(data, lens, g.frames, rects, p.wmax, p.hmax, gp)) return rc;
     const Geometry& cg = gp.g;
@@ -1173,12 +1191,23 @@ int llcomp_mi_codec_decode_resized_regions_host(llcomp_mi_codec* k, const uint8_
         return rc;
     {
         Timed t(k, s, 6);
-        HIP_TRY(launch_resize(k->d_box, k->d_mid, static_cast<uint8_t*>(d_px), reinterpret_cast<const ResizeFrame*>(k->d_stage + rs_at),
-                              reinterpret_cast<const int32_t*>(k->d_stage + rs_at + p.rs.size() * sizeof(ResizeFrame)), g.frames, g.c, p.wmax,
-                              p.hmax, ow, oh, s));
+        HIP_TRY(launch_resize_out(k->d_box, k->d_mid, d_px, reinterpret_cast<const ResizeFrame*>(k->d_stage + rs_at),
+                                  reinterpret_cast<const int32_t*>(k->d_stage + rs_at + p.rs.size() * sizeof(ResizeFrame)),
+                                  k->d_stage + rs_at + p.table_at(), p.out, g.frames, g.c, p.wmax, p.hmax, ow, oh, s));
     }
     ++k->n_decode;
     return LLCOMP_MI_OK;
+}
+
+int llcomp_mi_codec_decode_resized_regions(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                           const uint32_t* rects, const uint8_t* flags, uint32_t ow, uint32_t oh, void* d_px, void* d_status,
+                                           void* stream) {
+    return llcomp_mi_codec_decode_resized_regions_ex(k, d_payload, payload_bytes, d_slice_len, rects, flags, ow, oh, nullptr, d_px, d_status,
+                                                     stream);
+}
+int llcomp_mi_codec_decode_resized_regions_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens, const uint32_t* rects,
+                                                const uint8_t* flags, uint32_t ow, uint32_t oh, void* d_px, void* d_status, void* stream) {
+    return llcomp_mi_codec_decode_resized_regions_host_ex(k, data, lens, rects, flags, ow, oh, nullptr, d_px, d_status, stream);
 }
 
 uint32_t llcomp_mi_status_from_bits(uint32_t bits) { return uint32_t(status_from_bits(bits)); }

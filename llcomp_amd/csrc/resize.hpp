@@ -6,6 +6,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "../../include/llcomp_mi.h"
+
 namespace llcomp_mi {
 
 // The triangle filter with antialiasing for one axis, in_len -> out_len (include/llcomp_mi.h: llcomp_mi_resize_weights): the taps per
@@ -35,5 +37,23 @@ bool resize_frame_weights(uint32_t rw, uint32_t rh, uint32_t ow, uint32_t oh, Re
 // [frames][oh][ow][c] (the vertical pass, then the mirror).  The caller guarantees ox + rw <= bw, oy + rh <= bh for every entry.
 hipError_t launch_resize(const uint8_t* d_box, uint8_t* d_mid, uint8_t* d_px, const ResizeFrame* d_tab, const int32_t* d_w, uint32_t frames,
                          uint32_t c, uint32_t bw, uint32_t bh, uint32_t ow, uint32_t oh, hipStream_t stream);
+
+// The output format of an _ex call (include/llcomp_mi.h: llcomp_mi_output_format), checked: dtype, layout, element size, and whether the
+// output is anything but today's u8 HWC (`plain`: no table, the two kernels above).  BAD_ARGS for every case the header lists but the
+// output pointer's alignment, which the caller checks against esize.  A NULL fmt is U8 HWC.
+struct OutFormat {
+    uint32_t dtype = 0, layout = 0, esize = 1;
+    bool plain = true;
+    uint64_t table_bytes(uint32_t c) const { return plain ? 0 : uint64_t(c) * 256 * esize; }
+};
+int check_output_format(const llcomp_mi_output_format* fmt, uint32_t c, OutFormat& o);
+// The table of a checked format: table[ch * 256 + v], esize bytes each (include/llcomp_mi.h: the output rule).
+void output_table(const llcomp_mi_output_format* fmt, uint32_t c, const OutFormat& o, uint8_t* table);
+
+// launch_resize with the vertical pass writing fmt's table entries in its layout (o.plain is launch_resize itself): d_table is the
+// table of output_table in device memory, 4-byte aligned; d_out is aligned to o.esize.
+hipError_t launch_resize_out(const uint8_t* d_box, uint8_t* d_mid, void* d_out, const ResizeFrame* d_tab, const int32_t* d_w, const void* d_table,
+                             const OutFormat& o, uint32_t frames, uint32_t c, uint32_t bw, uint32_t bh, uint32_t ow, uint32_t oh,
+                             hipStream_t stream);
 
 }  // namespace llcomp_mi

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 
 #include "../../include/llcomp_mi.h"
 
@@ -87,6 +88,79 @@ bool resize_frame_weights(uint32_t rw, uint32_t rh, uint32_t ow, uint32_t oh, Re
     e.kx = axis_weights(rw, ow, w, e.hx, seen);
     e.ky = axis_weights(rh, oh, w, e.vy, seen);
     return e.kx && e.ky;
+}
+
+int check_output_format(const llcomp_mi_output_format* fmt, uint32_t c, OutFormat& o) {
+    o = OutFormat{};
+    if (!fmt) return LLCOMP_MI_OK;
+    if (fmt->struct_size < sizeof(llcomp_mi_output_format) || fmt->dtype > LLCOMP_MI_DTYPE_BF16 || fmt->layout > LLCOMP_MI_LAYOUT_CHW ||
+        fmt->scale > 1 || !c || c > 255)
+        return LLCOMP_MI_BAD_ARGS;
+    if (fmt->dtype == LLCOMP_MI_DTYPE_U8 && (fmt->scale || fmt->mean || fmt->std)) return LLCOMP_MI_BAD_ARGS;
+    for (uint32_t ch = 0; ch < c; ++ch) {
+        if (fmt->mean && !std::isfinite(fmt->mean[ch])) return LLCOMP_MI_BAD_ARGS;
+        if (fmt->std && (!std::isfinite(fmt->std[ch]) || fmt->std[ch] == 0.0f)) return LLCOMP_MI_BAD_ARGS;
+    }
+    static constexpr uint32_t kSize[4] = {1, 4, 2, 2};
+    o.dtype = fmt->dtype;
+    o.layout = fmt->layout;
+    o.esize = kSize[fmt->dtype];
+    o.plain = fmt->dtype == LLCOMP_MI_DTYPE_U8 && fmt->layout == LLCOMP_MI_LAYOUT_HWC;
+    return LLCOMP_MI_OK;
+}
+
+// binary32 -> binary16, round to nearest even, overflow to +-inf (F. Giesen's float_to_half_fast3_rtne, public domain): the subnormal
+// range through a float addition that rounds at the right bit, the normal range through integer rounding of the mantissa.
+static uint16_t f32_to_f16(float f) {
+    uint32_t u;
+    std::memcpy(&u, &f, 4);
+    const uint32_t sign = u & 0x80000000u;
+    u ^= sign;
+    uint32_t o;
+    if (u >= (127u + 16) << 23) {  // at or past 2^16: inf (or NaN)
+        o = u > 0x7F800000u ? 0x7E00u : 0x7C00u;
+    } else if (u < 113u << 23) {  // below 2^-14: a subnormal half or zero
+        const uint32_t magic_u = ((127u - 15) + (23 - 10) + 1) << 23;
+        float magic, g;
+        std::memcpy(&magic, &magic_u, 4);
+        std::memcpy(&g, &u, 4);
+        g += magic;
+        std::memcpy(&o, &g, 4);
+        o -= magic_u;
+    } else {
+        const uint32_t odd = (u >> 13) & 1u;
+        u += (uint32_t(15 - 127) << 23) + 0xFFFu + odd;
+        o = u >> 13;
+    }
+    return uint16_t(o | (sign >> 16));
+}
+
+void output_table(const llcomp_mi_output_format* fmt, uint32_t c, const OutFormat& o, uint8_t* table) {
+    for (uint32_t ch = 0; ch < c; ++ch)
+        for (uint32_t v = 0; v < 256; ++v) {
+            // (the rule: binary32, no fused operations -- none can fuse here, there is no multiply -- in this order)
+            float t = float(v);
+            if (fmt && fmt->scale) t = t / 255.0f;
+            if (fmt && fmt->mean) t = t - fmt->mean[ch];
+            if (fmt && fmt->std) t = t / fmt->std[ch];
+            uint32_t u;
+            std::memcpy(&u, &t, 4);
+            const size_t at = size_t(ch) * 256 + v;
+            switch (o.dtype) {
+                case LLCOMP_MI_DTYPE_F32: std::memcpy(table + 4 * at, &u, 4); break;
+                case LLCOMP_MI_DTYPE_F16: {
+                    const uint16_t h = f32_to_f16(t);
+                    std::memcpy(table + 2 * at, &h, 2);
+                    break;
+                }
+                case LLCOMP_MI_DTYPE_BF16: {
+                    const uint16_t b = uint16_t((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);  // (no NaN reaches here: every input is finite)
+                    std::memcpy(table + 2 * at, &b, 2);
+                    break;
+                }
+                default: table[at] = uint8_t(v); break;
+            }
+        }
 }
 
 namespace {
@@ -188,6 +262,112 @@ __global__ __launch_bounds__(256) void k_resize_v(const uint8_t* __restrict__ mi
     }
 }
 
+template <int E> struct Elem;
+template <> struct Elem<1> { using T = uint8_t; };
+template <> struct Elem<2> { using T = uint16_t; };
+template <> struct Elem<4> { using T = uint32_t; };
+
+// Vertical pass with an output format: k_resize_v's u8 value of every channel, looked up in the format's table (output_table, [c][256]
+// elements of E bytes) and stored in the layout.  CHW: one element per channel plane, so a wave's lanes store consecutive elements of
+// every plane (reversed under the mirror); HWC: the pixel's c elements, one vector store for C = 4 (the caller checks that d_out is
+// aligned for it).  C = 1 / 3 / 4 copy the table to LDS (at most 4 KiB); the generic path (C = 0, any c up to 255) reads it where it lies.
+template <int C, int E, bool CHW>
+__global__ __launch_bounds__(256) void k_resize_v_out(const uint8_t* __restrict__ mid, void* __restrict__ out, const ResizeFrame* __restrict__ tab,
+                                                      const int32_t* __restrict__ wts, const uint32_t* __restrict__ table, uint32_t bh, uint32_t ow,
+                                                      uint32_t oh, uint32_t c_rt) {
+    using T = typename Elem<E>::T;
+    const uint32_t c = C ? uint32_t(C) : c_rt;
+    __shared__ uint32_t s_lut[C ? C * 64 * E : 1];
+    if constexpr (C != 0) {
+        for (uint32_t j = threadIdx.x; j < uint32_t(C * 64 * E); j += 256) s_lut[j] = table[j];
+        __syncthreads();
+    }
+    const T* __restrict__ lut = reinterpret_cast<const T*>(C ? s_lut : table);
+    const uint32_t f = blockIdx.y;
+    const ResizeFrame& e = tab[f];
+    const uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= uint64_t(oh) * ow) return;
+    const uint32_t y = uint32_t(i / ow), x = uint32_t(i - uint64_t(y) * ow), ky = e.ky;
+    const int32_t* lo = wts + e.vy;
+    const int32_t* q = lo + oh + y;
+    const size_t stride = size_t(ow) * c;
+    const uint8_t* src = mid + ((size_t(f) * bh + uint32_t(lo[y])) * ow + x) * c;
+    const uint32_t xo = (e.flags & 1u) ? ow - 1 - x : x;
+    T* const o = static_cast<T*>(out);
+    const size_t plane = size_t(oh) * ow, px = size_t(y) * ow + xo;  // (CHW: element [f][ch][y][xo] = (f * c + ch) * plane + px)
+    auto put = [&](uint32_t ch, uint32_t v) {
+        if constexpr (CHW)
+            o[(size_t(f) * c + ch) * plane + px] = lut[ch * 256 + v];
+        else
+            o[(size_t(f) * plane + px) * c + ch] = lut[ch * 256 + v];
+    };
+    if constexpr (C == 4) {
+        int32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+        for (uint32_t j = 0; j < ky; ++j) {
+            const int32_t wj = q[size_t(j) * oh];
+            const uint32_t p = *reinterpret_cast<const uint32_t*>(src + j * stride);
+            a0 += wj * int32_t(p & 0xFF);
+            a1 += wj * int32_t((p >> 8) & 0xFF);
+            a2 += wj * int32_t((p >> 16) & 0xFF);
+            a3 += wj * int32_t(p >> 24);
+        }
+        const uint32_t l0 = lut[q22_round(a0)], l1 = lut[256 + q22_round(a1)], l2 = lut[512 + q22_round(a2)], l3 = lut[768 + q22_round(a3)];
+        if constexpr (CHW) {
+            o[size_t(f) * 4 * plane + px] = T(l0);
+            o[(size_t(f) * 4 + 1) * plane + px] = T(l1);
+            o[(size_t(f) * 4 + 2) * plane + px] = T(l2);
+            o[(size_t(f) * 4 + 3) * plane + px] = T(l3);
+        } else {
+            T* d = o + (size_t(f) * plane + px) * 4;
+            if constexpr (E == 1)
+                *reinterpret_cast<uint32_t*>(d) = l0 | (l1 << 8) | (l2 << 16) | (l3 << 24);
+            else if constexpr (E == 2)
+                *reinterpret_cast<uint2*>(d) = make_uint2(l0 | (l1 << 16), l2 | (l3 << 16));
+            else
+                *reinterpret_cast<uint4*>(d) = make_uint4(l0, l1, l2, l3);
+        }
+    } else if constexpr (C == 3) {
+        int32_t a0 = 0, a1 = 0, a2 = 0;
+        for (uint32_t j = 0; j < ky; ++j) {
+            const int32_t wj = q[size_t(j) * oh];
+            const uint8_t* p = src + j * stride;
+            a0 += wj * int32_t(p[0]);
+            a1 += wj * int32_t(p[1]);
+            a2 += wj * int32_t(p[2]);
+        }
+        put(0, q22_round(a0));
+        put(1, q22_round(a1));
+        put(2, q22_round(a2));
+    } else if constexpr (C == 1) {
+        int32_t a = 0;
+        for (uint32_t j = 0; j < ky; ++j) a += q[size_t(j) * oh] * int32_t(src[j * stride]);
+        put(0, q22_round(a));
+    } else {
+        for (uint32_t ch = 0; ch < c; ++ch) {
+            int32_t a = 0;
+            for (uint32_t j = 0; j < ky; ++j) a += q[size_t(j) * oh] * int32_t(src[j * stride + ch]);
+            put(ch, q22_round(a));
+        }
+    }
+}
+
+template <int E, bool CHW>
+void launch_v_out(dim3 gv, hipStream_t stream, const uint8_t* d_mid, void* d_out, const ResizeFrame* d_tab, const int32_t* d_w, const uint32_t* d_table,
+                  uint32_t c, uint32_t bh, uint32_t ow, uint32_t oh, bool vec4) {
+    const dim3 blk(256);
+    switch (c) {
+        case 1: k_resize_v_out<1, E, CHW><<<gv, blk, 0, stream>>>(d_mid, d_out, d_tab, d_w, d_table, bh, ow, oh, c); break;
+        case 3: k_resize_v_out<3, E, CHW><<<gv, blk, 0, stream>>>(d_mid, d_out, d_tab, d_w, d_table, bh, ow, oh, c); break;
+        case 4:
+            if (CHW || vec4)
+                k_resize_v_out<4, E, CHW><<<gv, blk, 0, stream>>>(d_mid, d_out, d_tab, d_w, d_table, bh, ow, oh, c);
+            else
+                k_resize_v_out<0, E, CHW><<<gv, blk, 0, stream>>>(d_mid, d_out, d_tab, d_w, d_table, bh, ow, oh, c);
+            break;
+        default: k_resize_v_out<0, E, CHW><<<gv, blk, 0, stream>>>(d_mid, d_out, d_tab, d_w, d_table, bh, ow, oh, c); break;
+    }
+}
+
 }  // namespace
 
 hipError_t launch_resize(const uint8_t* d_box, uint8_t* d_mid, uint8_t* d_px, const ResizeFrame* d_tab, const int32_t* d_w, uint32_t frames,
@@ -222,8 +402,46 @@ hipError_t launch_resize(const uint8_t* d_box, uint8_t* d_mid, uint8_t* d_px, co
     return hipGetLastError();
 }
 
+hipError_t launch_resize_out(const uint8_t* d_box, uint8_t* d_mid, void* d_out, const ResizeFrame* d_tab, const int32_t* d_w, const void* d_table,
+                             const OutFormat& o, uint32_t frames, uint32_t c, uint32_t bw, uint32_t bh, uint32_t ow, uint32_t oh,
+                             hipStream_t stream) {
+    if (o.plain) return launch_resize(d_box, d_mid, static_cast<uint8_t*>(d_out), d_tab, d_w, frames, c, bw, bh, ow, oh, stream);
+    if (!frames || !c || c > 255 || !bw || !bh || !ow || !oh || frames > 65535 || !d_table) return hipErrorInvalidValue;
+    if ((reinterpret_cast<uintptr_t>(d_table) & 3u) || (reinterpret_cast<uintptr_t>(d_out) & (o.esize - 1))) return hipErrorInvalidValue;
+    const uint64_t hb = (uint64_t(bh) * ow + 255) / 256, vb = (uint64_t(oh) * ow + 255) / 256;
+    if (hb > 0x7FFFFFFFull || vb > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const dim3 gh(uint32_t(hb), frames), gv(uint32_t(vb), frames), blk(256);
+    switch (c) {  // (the horizontal pass of launch_resize)
+        case 1: k_resize_h<1><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, ow, c); break;
+        case 3: k_resize_h<3><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, ow, c); break;
+        case 4: k_resize_h<4><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, ow, c); break;
+        default: k_resize_h<0><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, ow, c); break;
+    }
+    // (HWC at c = 4 stores a pixel's 4 elements at once: only where d_out is aligned to 4 elements)
+    const bool vec4 = (reinterpret_cast<uintptr_t>(d_out) & (4 * o.esize - 1)) == 0;
+    const uint32_t* t = static_cast<const uint32_t*>(d_table);
+    const bool chw = o.layout == LLCOMP_MI_LAYOUT_CHW;
+    if (o.esize == 1)  // (U8 CHW: U8 HWC is plain)
+        launch_v_out<1, true>(gv, stream, d_mid, d_out, d_tab, d_w, t, c, bh, ow, oh, vec4);
+    else if (o.esize == 2)
+        chw ? launch_v_out<2, true>(gv, stream, d_mid, d_out, d_tab, d_w, t, c, bh, ow, oh, vec4)
+            : launch_v_out<2, false>(gv, stream, d_mid, d_out, d_tab, d_w, t, c, bh, ow, oh, vec4);
+    else
+        chw ? launch_v_out<4, true>(gv, stream, d_mid, d_out, d_tab, d_w, t, c, bh, ow, oh, vec4)
+            : launch_v_out<4, false>(gv, stream, d_mid, d_out, d_tab, d_w, t, c, bh, ow, oh, vec4);
+    return hipGetLastError();
+}
+
 }  // namespace llcomp_mi
 
 extern "C" uint32_t llcomp_mi_resize_weights(uint32_t in_len, uint32_t out_len, uint32_t* lo, int32_t* q) {
     return llcomp_mi::resize_weights(in_len, out_len, lo, q);
+}
+
+extern "C" int llcomp_mi_output_table(const llcomp_mi_output_format* fmt, uint32_t c, void* table) {
+    llcomp_mi::OutFormat o;
+    if (!fmt || !table) return LLCOMP_MI_BAD_ARGS;
+    if (int rc = llcomp_mi::check_output_format(fmt, c, o)) return rc;
+    llcomp_mi::output_table(fmt, c, o, static_cast<uint8_t*>(table));
+    return LLCOMP_MI_OK;
 }

@@ -8,7 +8,7 @@
 //   encode  H2D frame -> kernels -> D2H {payload bytes, status} (16 B, event e1) -> D2H container of the EXACT size (event e2)
 //   decode  H2D container -> kernels -> D2H frame + status (event e2)
 //   regions H2D the windows' bytes of the containers (llcomp_mi_codec_decode_regions_host) -> kernels -> D2H crops + status (event e2)
-//   resized the same with the crops resampled to one shape (llcomp_mi_codec_decode_resized_regions_host)
+//   resized the same with the crops resampled to one shape (llcomp_mi_codec_decode_resized_regions_host(_ex)), u8 or in an output format
 // The size of a container is known on the GPU only.  Nobody waits for it at submit time: the 16-byte mailbox copy is
 // queued behind the kernels and whoever enters the library next (submit, wait or poll) looks at the events of the
 // jobs in flight ("pump") and queues the container copies whose size has arrived; wait() blocks on the EVENT that comes
@@ -37,6 +37,7 @@
 #include "../../include/llcomp_mi.h"
 #include "codec_internal.hpp"
 #include "container.hpp"
+#include "resize.hpp"
 
 using namespace llcomp_mi;
 
@@ -387,15 +388,21 @@ int llcomp_mi_stream_submit_decode_regions(llcomp_mi_stream* s, const uint8_t* c
     return LLCOMP_MI_OK;
 }
 
-// A job of resized crops: as a job of crops, with the output resampled to ow x oh on the lane's codec.  The output lands in the lane's
-// frame buffer and the slot's pinned output: more than raw * fpj bytes is BAD_ARGS before anything is queued.
-int llcomp_mi_stream_submit_decode_resized_regions(llcomp_mi_stream* s, const uint8_t* const* data, const size_t* lens, const uint32_t* rects,
-                                                   const uint8_t* flags, uint32_t ow, uint32_t oh, uint64_t tag) {
+// A job of resized crops: as a job of crops, with the output resampled to ow x oh on the lane's codec, in fmt's dtype and layout (NULL:
+// u8 HWC).  The output lands in the lane's frame buffer and the slot's pinned output: more than raw * fpj bytes is BAD_ARGS before
+// anything is queued.
+int llcomp_mi_stream_submit_decode_resized_regions_ex(llcomp_mi_stream* s, const uint8_t* const* data, const size_t* lens, const uint32_t* rects,
+                                                      const uint8_t* flags, uint32_t ow, uint32_t oh, const llcomp_mi_output_format* fmt,
+                                                      uint64_t tag) {
     if (!s || !data || !lens || !rects) return LLCOMP_MI_BAD_ARGS;
     if (!s->subs.empty())
-        return deal(s, [&](llcomp_mi_stream* sub) { return llcomp_mi_stream_submit_decode_resized_regions(sub, data, lens, rects, flags, ow, oh, tag); });
+        return deal(s, [&](llcomp_mi_stream* sub) {
+            return llcomp_mi_stream_submit_decode_resized_regions_ex(sub, data, lens, rects, flags, ow, oh, fmt, tag);
+        });
     std::lock_guard<std::mutex> lock(s->mu);
-    const uint64_t bytes = uint64_t(ow) * oh * s->c * s->fpj;
+    OutFormat out;
+    if (int rc = check_output_format(fmt, s->c, out)) return rc;
+    const uint64_t bytes = uint64_t(ow) * oh * s->c * s->fpj * out.esize;
     if (bytes > s->raw * s->fpj || bytes > s->out_cap) return LLCOMP_MI_BAD_ARGS;
     DeviceGuard guard(s->device);
     if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
@@ -404,7 +411,7 @@ int llcomp_mi_stream_submit_decode_resized_regions(llcomp_mi_stream* s, const ui
     if (i < 0) return LLCOMP_MI_BUSY;
     Slot& sl = s->slots[size_t(i)];
     HostLane* l = sl.lane;
-    if (int rc = llcomp_mi_codec_decode_resized_regions_host(l->k, data, lens, rects, flags, ow, oh, l->d_px, l->d_meta + 1, l->stream))
+    if (int rc = llcomp_mi_codec_decode_resized_regions_host_ex(l->k, data, lens, rects, flags, ow, oh, fmt, l->d_px, l->d_meta + 1, l->stream))
         return drained(l, rc);
     if (hipMemcpyAsync(l->h_meta, l->d_meta, 16, hipMemcpyDeviceToHost, l->stream) != hipSuccess ||
         hipMemcpyAsync(sl.h_out, l->d_px, bytes, hipMemcpyDeviceToHost, l->stream) != hipSuccess || hipEventRecord(sl.e2, l->stream) != hipSuccess)
@@ -416,6 +423,11 @@ int llcomp_mi_stream_submit_decode_resized_regions(llcomp_mi_stream* s, const ui
     sl.out_len = bytes;
     s->fifo.push_back(uint32_t(i));
     return LLCOMP_MI_OK;
+}
+
+int llcomp_mi_stream_submit_decode_resized_regions(llcomp_mi_stream* s, const uint8_t* const* data, const size_t* lens, const uint32_t* rects,
+                                                   const uint8_t* flags, uint32_t ow, uint32_t oh, uint64_t tag) {
+    return llcomp_mi_stream_submit_decode_resized_regions_ex(s, data, lens, rects, flags, ow, oh, nullptr, tag);
 }
 
 uint32_t llcomp_mi_stream_frames_per_job(const llcomp_mi_stream* s) { return s ? s->fpj : 0; }
