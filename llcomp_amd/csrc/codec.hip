@@ -809,7 +809,9 @@ int llcomp_mi_codec_encode(llcomp_mi_codec* k, const void* d_px, void* d_payload
     }
     {
         Timed t(k, s, 1);
-        if (model_is_fused(g)) {
+        if (rows_encoder_reads_pixels(g)) {
+            // nothing: the coder reads the pixels itself
+        } else if (model_is_fused(g)) {
             HIP_TRY(launch_model_rows_fwd(g, static_cast<const uint8_t*>(d_px), static_cast<uint16_t*>(k->d_lane_order), s));
         } else {
             HIP_TRY(launch_model_fwd(g, static_cast<const uint8_t*>(d_px), static_cast<uint32_t*>(k->d_sym_or_rec), s));
@@ -876,7 +878,8 @@ int llcomp_mi_codec_encode(llcomp_mi_codec* k, const void* d_px, void* d_payload
     {
         Timed t(k, s, 2);
         const bool snap = snapshot_mode(g);
-        HIP_TRY(launch_encode_slices(g, snap ? k->d_snap_res : k->d_lane_order, snap ? static_cast<uint64_t*>(k->d_snap_banks) : k->d_states,
+        const void* in = snap ? k->d_snap_res : rows_encoder_reads_pixels(g) ? d_px : k->d_lane_order;
+        HIP_TRY(launch_encode_slices(g, in, snap ? static_cast<uint64_t*>(k->d_snap_banks) : k->d_states,
                                      k->state_generation, k->d_scratch, static_cast<uint32_t*>(d_slice_len),
                                      k->d_group_off, static_cast<uint32_t*>(d_status), k->d_counters, s));
     }

@@ -97,6 +97,21 @@ LLMI_HD inline uint32_t snapshot_cap(const Geometry& g) {
 constexpr int kBankCacheLog2 = 5;  // entries per lane of the 2-D decoder's bank cache (slice_kernels.hip): ONE constant for flag, launcher, kernel
 inline int bank_cache_log2(const Geometry& g) { return (g.flags & kGeoBankCache) ? kBankCacheLog2 : 0; }
 
+// ---- the row encoder's pixel reads (planar 1-row slices that the encoder reads from the pixel batch: rows_encoder_reads_pixels) ----
+// A lane reads sample k of its slice as ONE dword at tile_base + k*C.  That dword stays inside the caller's batch of T bytes iff
+// tile_base + k*C + 4 <= T.  Only the last u = ceil(4/C) - 1 pixels of the batch fail that (3 for C = 1, 1 for C = 2 and 3, none for
+// C = 4), and each of them is among the last u samples of its own slice (the pixels behind it in the batch include the rest of its
+// tile).  rows_px_dwords: how many leading samples of a slice may be read as a dword -- at least samples - u, since sample
+// samples - 1 - u ends at tile_base + (samples - 1 - u)*C + 4 <= T - (u + 1)*C + 4 <= T; the rest are read byte by byte.
+LLMI_HD inline uint32_t rows_px_dwords(uint64_t tile_base, uint32_t samples, uint32_t c, uint64_t batch_bytes) {
+    if (tile_base + 4 > batch_bytes) return 0;
+    const uint64_t k = (batch_bytes - 4 - tile_base) / c + 1;  // samples 0 .. k-1 end at or before the batch's end
+    return k < samples ? uint32_t(k) : samples;
+}
+// The samples at the end of a slice that the encoder's bulk loop (no per-lane tests; sample i + 2 is loaded while sample i is coded)
+// leaves to the loop with tests: it loads samples up to samples - rows_px_tail(c) + 1 = samples - 1 - u, all of them dwords by the above.
+LLMI_HD inline uint32_t rows_px_tail(uint32_t c) { return 1 + (4 + c - 1) / c; }
+
 // lane order: element k of slice `id` inside an array laid out [group][k][group width]
 LLMI_HD inline size_t lane_order_index(const Geometry& g, uint32_t id, uint32_t k) {
     const uint32_t gw = 1u << g.lane_shift;

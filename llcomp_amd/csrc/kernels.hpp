@@ -43,6 +43,10 @@ hipError_t launch_from_lane_order_i16(const Geometry& g, const int16_t* d_lanes,
 
 // Planar 1-row slices: stage A fused with the lane-order transpose (pixels <-> lane-order arrays directly).
 bool model_is_fused(const Geometry& g);
+// ... and the encoder runs stage A itself, reading the pixel batch (no 16-bit symbol array, no launch_model_rows_fwd): every fused
+// geometry whose wavefront of tiles, (63 / C + 2) * tile_w * C bytes, spans less than 2^31 (the kernel's 32-bit per-lane offsets):
+// tiles (tile_w * C) below about 33 / 65 / 93 / 126 MB for C = 1 / 2 / 3 / 4
+bool rows_encoder_reads_pixels(const Geometry& g);
 hipError_t launch_model_rows_fwd(const Geometry& g, const uint8_t* d_px, uint16_t* d_lanes, hipStream_t stream);  // 16-bit symbols
 hipError_t launch_model_rows_inv(const Geometry& g, const int16_t* d_lanes, uint8_t* d_px, hipStream_t stream);
 
@@ -53,7 +57,7 @@ bool slices_need_state_tables(const Geometry& g);
 
 // One lane per slice: binarisation + adaptive states + range encoder.  llcomp.hpp:33-89, 166-206, 283-293, 439-449.
 //   d_sym     : symbols in LANE ORDER: u32 (ctx | residual << 16), or the 16-bit form of the fused path when
-//               model_is_fused(g)
+//               model_is_fused(g) -- or, when rows_encoder_reads_pixels(g), the caller's pixel batch itself (u8[frames][h][w][c])
 //   d_states  : u64[lane group][kContexts][lanes of the group] (8 state bytes per context and slice), unused unless
 //               slices_need_state_tables(g).  NOT cleared per call: every bank carries the `generation` (1..255) of the call
 //               that wrote it in the spare top bits of its state bytes, and a bank of another generation reads as zeros.

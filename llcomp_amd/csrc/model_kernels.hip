@@ -1326,6 +1326,10 @@ hipError_t launch_from_lane_order_i16(const Geometry& g, const int16_t* d_lanes,
 }
 
 bool model_is_fused(const Geometry& g) { return g.planar && rows_mode(g) && g.c <= 4; }
+// the 64 lanes of a wavefront cover at most 63 / C + 2 consecutive tiles, which lie back to back in the batch (tile_h == 1)
+bool rows_encoder_reads_pixels(const Geometry& g) {
+    return model_is_fused(g) && (uint64_t(63 / g.c + 2) * g.tile_w * g.c + 4 < (1ull << 31));
+}
 
 hipError_t launch_model_rows_fwd(const Geometry& g, const uint8_t* d_px, uint16_t* d_lanes, hipStream_t stream) {
     const uint64_t blocks = xcd_grid(lane_groups(g), (g.tile_w + 63) / 64);

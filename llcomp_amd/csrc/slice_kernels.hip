@@ -662,16 +662,71 @@ __global__ __launch_bounds__(64) void k_encode_slices(const Geometry g, const ui
         // contexts 0 / 605 / 1210 only: their state bytes sit in LDS, [context][lane] (a read + a write per sample
         // instead of selecting among / writing back to three register pairs: twelve v_cndmask)
         for (uint32_t k = 0; k < 6; ++k) rowbank[k * 64 + threadIdx.x] = 0;
-        // Symbols come through a wave-uniform base (all lanes of a wavefront sit in one lane group) and a running 32-bit byte
-        // offset: one global_load with a scalar base and one 2-cycle add per sample, no 64-bit address arithmetic.
-        const uint32_t grp = __builtin_amdgcn_readfirstlane(id >> g.lane_shift);
-        const char* const gsym = reinterpret_cast<const char*>(sym + ((size_t(grp) * g.slice_samples) << g.lane_shift));
-        uint32_t sofs = (id & ((1u << g.lane_shift) - 1)) * uint32_t(sizeof(SYM)), sstep = uint32_t(sizeof(SYM)) << g.lane_shift;
+        // PX (SYM = uint8_t, planar 1-row slices: rows_encoder_reads_pixels): `sym` is the caller's pixel batch and the lane runs stage A
+        // itself -- it reads its own pixels (tile base + k*C), keeps its plane's l and L in registers and forms the context's byte offset
+        // and the folded residual exactly as k_model_rows_fwd + the 16-bit symbol below do.  Otherwise symbols in lane order.
+        // Either way the input comes through a wave-uniform base and a running 32-bit byte offset per lane: one global_load with a
+        // scalar base and one 2-cycle add per sample, no 64-bit address arithmetic.
+        constexpr bool PX = sizeof(SYM) == 1;
+        const char* gsym;
+        uint32_t sofs, sstep;
+        [[maybe_unused]] uint32_t n_dword = total;  // PX: samples 0 .. n_dword-1 are read as dwords, the rest byte by byte (rows_px_dwords)
+        [[maybe_unused]] uint32_t psh = 0, msub = 0, my = 0, large = 0;
+        [[maybe_unused]] int pl = 128, pL = 128;  // PX: l and L of the lane's plane (llcomp.hpp:417-419: 128 at the slice start)
+        if constexpr (PX) {
+            // tile_h == 1: the tiles of a batch lie back to back in raster order, so lane 0's tile starts lowest and the wavefront's
+            // tiles span (64 / C + 2) tiles at most (< 2^31 bytes: rows_encoder_reads_pixels)
+            const uint32_t C = g.c;
+            const unsigned long long tbase = ((unsigned long long)(r.frame) * g.h + r.y0) * g.w * C + (unsigned long long)(r.x0) * C;
+            // (readfirstlane returns an int: both halves through uint32_t, or a low word at or past 2^31 would sign-extend)
+            const unsigned long long wbase = (unsigned long long)uint32_t(__builtin_amdgcn_readfirstlane(uint32_t(tbase))) |
+                                             ((unsigned long long)uint32_t(__builtin_amdgcn_readfirstlane(uint32_t(tbase >> 32))) << 32);
+            gsym = reinterpret_cast<const char*>(sym) + wbase;
+            sofs = uint32_t(tbase - wbase);
+            sstep = C;
+            const unsigned long long total_bytes = (unsigned long long)(g.frames) * g.h * g.w * C;
+            n_dword = rows_px_dwords(tbase, total, C, total_bytes);
+            // the plane from the pixel's dword d (llcomp.hpp:396-414), without a branch: v = own byte - (G & msub) + (t & my), where
+            // t = (R - G + B - G) / 4 truncated -- plane 0: R - G, plane 1: G + t, plane 2: B - G, plane 3 and C < 3: the byte itself
+            psh = 8 * r.ch;
+            msub = C >= 3 && (r.ch == 0 || r.ch == 2) ? ~0u : 0u;
+            my = C >= 3 && r.ch == 1 ? ~0u : 0u;
+            large = (g.flags & kGeoSmallModel) ? 0u : ~0u;  // LargeModel = false: no quant5 term, context 0 (llcomp.hpp:427-429)
+            asm volatile("" : "+v"(psh), "+v"(msub), "+v"(my));
+        } else {
+            const uint32_t grp = __builtin_amdgcn_readfirstlane(id >> g.lane_shift);
+            gsym = reinterpret_cast<const char*>(sym + ((size_t(grp) * g.slice_samples) << g.lane_shift));
+            sofs = (id & ((1u << g.lane_shift) - 1)) * uint32_t(sizeof(SYM));
+            sstep = uint32_t(sizeof(SYM)) << g.lane_shift;
+        }
         asm volatile("" : "+v"(sstep));  // (a vector value: a VALU add with a scalar operand costs twice as much)
-        auto load_sym = [&](uint32_t ofs) -> uint32_t { return *reinterpret_cast<const SYM*>(gsym + ofs); };
-        uint32_t s0 = load_sym(sofs);
+        auto load_sym = [&](uint32_t ofs) -> uint32_t {
+            if constexpr (PX) {
+                uint32_t w;
+                __builtin_memcpy(&w, gsym + ofs, 4);  // (pixels start at any byte offset: an unaligned dword load)
+                return w;
+            } else {
+                return *reinterpret_cast<const SYM*>(gsym + ofs);
+            }
+        };
+        // sample k with a per-lane test (the prologue and the loop with the tests): PX, the samples whose dword would leave the caller's
+        // buffer -- at most three pixels at the very end of the batch, geometry.hpp -- read their C bytes alone
+        auto load_at = [&](uint32_t ofs, uint32_t k) -> uint32_t {
+            if constexpr (PX) {
+                if (k >= n_dword) {
+                    const uint8_t* p = reinterpret_cast<const uint8_t*>(gsym + ofs);
+                    uint32_t w = p[0];
+                    if (g.c > 1) w |= uint32_t(p[1]) << 8;
+                    if (g.c > 2) w |= uint32_t(p[2]) << 16;
+                    if (g.c > 3) w |= uint32_t(p[3]) << 24;
+                    return w;
+                }
+            }
+            return load_sym(ofs);
+        };
+        uint32_t s0 = load_at(sofs, 0);
         sofs += sstep;
-        uint32_t s1 = total > 1 ? load_sym(sofs) : 0;
+        uint32_t s1 = total > 1 ? load_at(sofs, 1) : 0;
         sofs += sstep;
         uint32_t bank_base = uint32_t(uintptr_t((lds_u8_ptr) reinterpret_cast<uint8_t*>(rowbank))) + threadIdx.x * 4;
         asm volatile("" : "+v"(bank_base));
@@ -679,11 +734,26 @@ __global__ __launch_bounds__(64) void k_encode_slices(const Geometry g, const ui
         EncRowsExtra xs{0u, 0u, 0u};
         unsigned long long low_range = e.low | ((unsigned long long)e.range << 32);  // (one register pair: enc_rows_asm.hpp)
 #endif
-        // one sample: context -> row bank, residual -> bins
-        auto code = [&](uint32_t sy) {
+        // one sample (i: its index, wave-uniform): context -> row bank, residual -> bins
+        auto code = [&](uint32_t sy, uint32_t i) {
             uint32_t bofs;  // |quant5(L - l)| * 512: byte offset of the context's row bank
             int res;
-            if constexpr (sizeof(SYM) == 2) {  // fused stage A: |quant5| in bits 12..13, residual in bits 0..11
+            if constexpr (PX) {  // stage A of k_model_rows_fwd for one sample of the lane's plane
+                const uint32_t G = (sy >> 8) & 0xFF;
+                const int sum = int(sy & 0xFF) + int((sy >> 16) & 0xFF) - 2 * int(G);
+                const int t = (sum + int((uint32_t(sum) >> 31) * 3u)) >> 2;  // truncating division, llcomp.hpp:402
+                const int v = int(__builtin_amdgcn_ubfe(sy, psh, 8)) - int(G & msub) + (t & int(my));
+                // "no L at x <= 1" (llcomp.hpp:417-419): L - l = 0 for samples 0 and 1
+                const int dq = (pL - pl) & int(i >= 2 ? large : 0u);
+                const int sg = dq >> 31;  // hash = 605*quant5(L - l) < 0: the residual is folded (llcomp.hpp:433-436)
+                const uint32_t aq = uint32_t((dq ^ sg) - sg);
+                // |quant5| * 512 = 512 * ([aq >= 1] + [aq >= 4]); planes lie in [-255, 255], so aq <= 510 and bit 9 of aq + 511
+                // (aq + 508) says aq >= 1 (aq >= 4)
+                bofs = ((aq + 511u) & 0x200u) + ((aq + 508u) & 0x200u);
+                res = ((v - pl) ^ sg) - sg;
+                pL = pl;
+                pl = v;
+            } else if constexpr (sizeof(SYM) == 2) {  // fused stage A: |quant5| in bits 12..13, residual in bits 0..11
                 bofs = (sy >> 3) & 0x600u;
                 res = int(sy << 20) >> 20;
             } else {
@@ -708,27 +778,29 @@ __global__ __launch_bounds__(64) void k_encode_slices(const Geometry g, const ui
         // inside an iteration is: consume what was requested a sample ago (long back, no stall) -> issue the next prefetch
         // -> issue the stores of the previous sample's output.  Nothing is ever waited for right after it was issued.
         // When all slices of the wavefront have the same length (all but those with the ragged last tile column), the bulk
-        // runs under a scalar loop counter with no per-lane tests; the last two samples, and ragged wavefronts, take
-        // the loop with the tests.
+        // runs under a scalar loop counter with no per-lane tests; the last two samples (PX: rows_px_tail(C) -- the bulk loads
+        // no sample that may need byte reads: 5 for C = 1, 3 for C = 2 and 3, 2 for C = 4), and ragged wavefronts, take the loop
+        // with the tests.
         const uint32_t total0 = __builtin_amdgcn_readfirstlane(total);
         const bool same = __builtin_amdgcn_ballot_w64(total != total0) == 0;
-        const uint32_t n_bulk = same && total0 > 2 ? total0 - 2 : 0;
+        const uint32_t tail = PX ? rows_px_tail(g.c) : 2u;
+        const uint32_t n_bulk = same && total0 > tail ? total0 - tail : 0;
         uint32_t i = 0;
         for (; i < n_bulk; ++i) {
             s0 = consume_here(s0);  // loaded two samples ago
             const uint32_t s2 = load_sym(sofs);
             sofs += sstep;
             if (e.wp >= e.base + 16) enc_flush16(e);  // 16 bytes staged (LDS addresses: no wrap-around, wp >= base - 1)
-            code(s0);
+            code(s0, i);
             s0 = s1;
             s1 = s2;
         }
         for (; i < total; ++i) {
             s0 = consume_here(s0);
-            const uint32_t s2 = i + 2 < total ? load_sym(sofs) : 0;
+            const uint32_t s2 = i + 2 < total ? load_at(sofs, i + 2) : 0;
             sofs += sstep;
             if (e.wp >= e.base + 16) enc_flush16(e);
-            code(s0);
+            code(s0, i);
             s0 = s1;
             s1 = s2;
         }
@@ -1490,7 +1562,12 @@ hipError_t launch_encode_slices(const Geometry& g, const void* d_sym, uint64_t* 
     const uint32_t lpw = g.lpw;
     const uint32_t blocks = (g.n_slices + lpw - 1) / lpw;
     uint64_t* const d_group_sum = encoder_writes_group_sums(g) ? d_group_off : nullptr;
-    if (model_is_fused(g)) {  // planar 1-row slices: 16-bit symbols, always the ROWS kernel
+    if (rows_encoder_reads_pixels(g)) {  // planar 1-row slices: the ROWS kernel reads the pixels and runs stage A itself
+        k_encode_slices<1, true, uint8_t><<<dim3(blocks), dim3(64), LLMI_ASM_ENC ? kRowsEncLdsBytes : 0, stream>>>(
+            g, lpw, static_cast<const uint8_t*>(d_sym), d_states, d_scratch, d_slice_len, d_group_sum, d_status, gpat, d_counters);
+        return hipGetLastError();
+    }
+    if (model_is_fused(g)) {  // ... tiles too wide for that: 16-bit symbols from launch_model_rows_fwd
         k_encode_slices<1, true, uint16_t><<<dim3(blocks), dim3(64), LLMI_ASM_ENC ? kRowsEncLdsBytes : 0, stream>>>(
             g, lpw, static_cast<const uint16_t*>(d_sym), d_states, d_scratch, d_slice_len, d_group_sum, d_status, gpat, d_counters);
         return hipGetLastError();
