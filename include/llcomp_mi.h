@@ -32,7 +32,9 @@ extern "C" {
  * LLCOMP_MI_JOB_DECODE_REGIONS, LLCOMP_MI_CTR_HOST_STAGED_BYTES; crops of different sizes resized to one shape -- llcomp_mi_resize_weights,
  * llcomp_mi_resized_regions_plan, llcomp_mi_codec_decode_resized_regions(_host), llcomp_mi_stream_submit_decode_resized_regions,
  * LLCOMP_MI_PREPARE_RESIZED, LLCOMP_MI_JOB_DECODE_RESIZED_REGIONS, llcomp_mi_codec_allocated_bytes; their output as a model takes it,
- * float or normalised, CHW or HWC -- llcomp_mi_output_format, llcomp_mi_output_table and the _ex forms of the three resized calls).  The library and its callers are built from ONE header: structs have one layout per ABI version (llcomp_mi_opts is
+ * float or normalised, CHW or HWC -- llcomp_mi_output_format, llcomp_mi_output_table and the _ex forms of the three resized calls; region
+ * update -- llcomp_mi_replace_slices(_into), llcomp_mi_update_region(_into), llcomp_mi_codec_encode_region,
+ * llcomp_mi_codec_update_region, LLCOMP_MI_PREPARE_UPDATE).  The library and its callers are built from ONE header: structs have one layout per ABI version (llcomp_mi_opts is
  * checked through struct_size and refused when it differs; llcomp_mi_info and llcomp_mi_stream_result are written in full),
  * so a binding compares llcomp_mi_abi_version() with the LLCOMP_MI_ABI_VERSION it was generated from and refuses to run on
  * a mismatch -- there is no cross-version compatibility mode. */
@@ -124,6 +126,22 @@ int llcomp_mi_decode_region(const uint8_t* data, size_t len, int32_t device, uin
 /* ... into a caller's buffer: OUTPUT_OVERFLOW (with *c set, nothing written) when px_cap < rw * rh * c. */
 int llcomp_mi_decode_region_into(const uint8_t* data, size_t len, int32_t device, uint32_t flags, uint32_t x, uint32_t y, uint32_t rw,
                                  uint32_t rh, uint8_t* px, size_t px_cap, uint32_t* c);
+/* Region update, the write side of llcomp_mi_decode_region: the rectangle (x, y, rw, rh) of the picture (the same rule; anything else
+ * is BAD_ARGS) is replaced by px (rh x rw x c bytes, row-major, channels interleaved; c = the container's channel count), and *out is
+ * the container a full encode of the modified picture gives, byte for byte, in the container's own format, tiling and model.  Only the
+ * slices of the tiles the rectangle touches are coded again (llcomp_mi_codec_encode_region), and only their bytes cross PCIe: the
+ * header and slice table and rw * rh * c bytes of pixels go up; when the rectangle is not exactly its box's pixels (tile-aligned, or
+ * reaching the image edge) the covered slices' payload span goes up too, to be decoded and pasted into; the new lengths and streams of
+ * the covered slices come down, and llcomp_mi_replace_slices assembles the result on the host.  BAD_EXPONENT and TRUNCATED come from
+ * the covered slices when they had to be decoded, and never otherwise: with an aligned rectangle the old covered slices are not read
+ * at all.  Damage in slices outside the box is never seen and is carried over verbatim; an uncovered slice whose bytes run past the data
+ * is TRUNCATED.  A LEGACY stream is one serial chain: unless the rectangle is the whole picture it is decoded whole, pasted into and
+ * encoded whole, and the result is a LEGACY stream again.  flags as in llcomp_mi_decode_region.  On any error *out is untouched (_into:
+ * the buffer; OUTPUT_OVERFLOW with *out_len = the size it takes when out_cap is too small).  One device only. */
+int llcomp_mi_update_region(const uint8_t* data, size_t len, int32_t device, uint32_t flags, uint32_t x, uint32_t y, uint32_t rw,
+                            uint32_t rh, const uint8_t* px, uint8_t** out, size_t* out_len);
+int llcomp_mi_update_region_into(const uint8_t* data, size_t len, int32_t device, uint32_t flags, uint32_t x, uint32_t y, uint32_t rw,
+                                 uint32_t rh, const uint8_t* px, uint8_t* out, size_t out_cap, size_t* out_len);
 /* Decoding over a device list: the mirror image of llcomp_mi_opts.devices -- every device receives the table entries and payload
  * bytes of its chunks of tile rows, decodes them and copies its rows straight to their place in the picture.  Nothing is written to
  * the output before EVERY device has reported success (the first failing device in list order decides the status).  How the
@@ -211,6 +229,20 @@ int llcomp_mi_regions_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, 
 int llcomp_mi_regions_gather(const uint8_t* const* data, const size_t* lens, uint32_t n, const uint32_t* xy, uint32_t rw, uint32_t rh,
                              uint8_t* payload, uint64_t payload_cap, uint32_t* slice_len, uint32_t len_cap, uint64_t* payload_bytes,
                              uint32_t* n_slices, uint32_t* n_classes);
+/* Splice of a SLICED container: the slices of the tiles box = {tx0, ty0, tx1, ty1} covers (as llcomp_mi_region_plan returns it) are
+ * replaced, every other slice stays byte for byte where it was in the payload's order.  new_len = the covered slices' new lengths,
+ * u32[covered]; new_payload = their streams back to back; both in sub-slice order: tile row, tile column, plane.  The result has the
+ * same header, the new table, the unchanged runs of the old payload (one memcpy each) and the new slices in between.  Because every
+ * slice is the reference stream of its own crop, new slices that are the streams of the modified crops make the result the container
+ * a full encode of the modified picture gives, byte for byte.  Old covered slices are never read: they may be damaged.  Errors, all
+ * decided before anything is written (*out and the _into buffer stay untouched): BAD_ARGS for a NULL pointer, a LEGACY stream, an empty
+ * box or one outside the tile grid; a header or table cut short fails as in llcomp_mi_probe; TRUNCATED for a new length above the SLICED
+ * limit (LLCOMP_MI_TRUNCATED) or an uncovered slice whose bytes run past the data; _into: OUTPUT_OVERFLOW for a buffer too small, with
+ * *out_len = the size it takes.  Bytes of `data` behind the last slice are dropped.  Host-only: no GPU involved. */
+int llcomp_mi_replace_slices(const uint8_t* data, size_t len, const uint32_t box[4], const uint32_t* new_len, const uint8_t* new_payload,
+                             uint8_t** out, size_t* out_len);
+int llcomp_mi_replace_slices_into(const uint8_t* data, size_t len, const uint32_t box[4], const uint32_t* new_len, const uint8_t* new_payload,
+                                  uint8_t* out, size_t out_cap, size_t* out_len);
 /* The resampling rule of llcomp_mi_codec_decode_resized_regions for one axis, in_len -> out_len: the triangle ("bilinear") filter with
  * antialiasing of PIL and of torch's interpolate(mode="bilinear", align_corners=False, antialias=True), in integers:
  *   scale = in_len / out_len, support = max(scale, 1); output i: center = (i + 0.5) * scale,
@@ -315,6 +347,7 @@ uint64_t llcomp_mi_codec_allocated_bytes(const llcomp_mi_codec* codec);
 #define LLCOMP_MI_PREPARE_REGION 8u /* the region decode's two arrays (12 B per slice), and state tables if a region may need them (bit 2 stays unused) */
 #define LLCOMP_MI_PREPARE_REGIONS 16u /* ... and the per-frame table of a regions decode (32 B per frame in HBM, a pinned staging ring) */
 #define LLCOMP_MI_PREPARE_RESIZED 32u /* ... and the boxes and the horizontal pass's rows of a resized regions decode (frames * w * h * c bytes each) */
+#define LLCOMP_MI_PREPARE_UPDATE 64u /* ... and a region update's offset arrays (8 B per slice) and its box pixel buffer (frames * w * h * c bytes) */
 int llcomp_mi_codec_prepare(llcomp_mi_codec* codec, uint32_t what);
 /* Upper bound on the packed payload bytes the codec can emit for any input (13 B per sample + slack). */
 uint64_t llcomp_mi_codec_max_payload_bytes(const llcomp_mi_codec* codec);
@@ -338,6 +371,33 @@ int llcomp_mi_codec_decode_region(llcomp_mi_codec* codec, const void* d_payload,
 /* Diagnostic: the kernel family (encoding of llcomp_mi_codec_kernel_family) a region decode of this rectangle runs -- the sub-image's
  * geometry may select another one than the codec's (a 1-row remainder of 2-row tiles runs the row kernels).  0 for a bad rectangle. */
 uint32_t llcomp_mi_codec_region_family(const llcomp_mi_codec* codec, uint32_t x, uint32_t y, uint32_t rw, uint32_t rh);
+/* Region update of a batch, the write side of llcomp_mi_codec_decode_region: the rectangle (x, y, rw, rh) of every frame (one rectangle
+ * for all frames of the call) is replaced by d_rect [frames][rh][rw][c], and only the slices of the tiles it touches are coded again.
+ * Because every slice is the reference stream of its own crop, the result is byte for byte what llcomp_mi_codec_encode gives for the
+ * modified frames.  Both calls are asynchronous on `stream`, run in the codec's workspace on the geometry of the covered box
+ * (llcomp_mi_codec_region_family reports its kernel family) and write d_status like an encode.
+ *   encode_region: -> d_sub_payload (the covered slices' new streams back to back, capacity sub_payload_cap, OVERFLOW as for an encode),
+ *     d_sub_len u32[covered slices of all frames], d_sub_total u64[1]; order: frame, tile row, tile column, plane -- per frame what
+ *     llcomp_mi_replace_slices takes.
+ *   update_region: the same work, then the splice in HBM: -> d_payload_out (capacity payload_cap; a slice that would end past it is
+ *     not written and the status is OVERFLOW), d_slice_len_out u32[slices], d_total u64[1], as llcomp_mi_codec_encode would
+ *     write them for the modified frames.  The outputs must not overlap d_payload / d_slice_len: both are read to the end of the call.
+ * A rectangle that is exactly its box's pixels (tile-aligned, or reaching the image edge) needs nothing of the old covered slices: the
+ * encoder reads d_rect itself, no decoder runs (n_decode of llcomp_mi_codec_get_profile does not move), and d_payload / d_slice_len may
+ * be NULL for encode_region.  Otherwise the box is decoded first (the chain of llcomp_mi_codec_decode_region, whole box), the rectangle is
+ * pasted into it and the box is encoded: BAD_EXPONENT and TRUNCATED then come from the covered slices, through the status word, and
+ * what the call has written is not to be used.  Slices outside the box are never decoded: damage there is carried over verbatim; an
+ * uncovered slice whose table entry runs past payload_bytes is TRUNCATED (update_region; nothing is read past the payload).  BAD_ARGS,
+ * before anything is launched or written: a NULL pointer, a rectangle empty or outside the image.  HIP_ERROR, likewise, if the
+ * sub-geometry's arrays would not fit the workspace (never with default tuning).  The first call allocates what LLCOMP_MI_PREPARE_UPDATE
+ * | LLCOMP_MI_PREPARE_ENCODE allocate ahead, and the state tables or snapshot arrays a sub-geometry needs where the codec's own family
+ * does not (llcomp_mi_codec_workspace_bytes counts them); it can return LLCOMP_MI_NOMEM. */
+int llcomp_mi_codec_encode_region(llcomp_mi_codec* codec, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len, uint32_t x,
+                                  uint32_t y, uint32_t rw, uint32_t rh, const void* d_rect, void* d_sub_payload, uint64_t sub_payload_cap,
+                                  void* d_sub_len, void* d_sub_total, void* d_status, void* stream);
+int llcomp_mi_codec_update_region(llcomp_mi_codec* codec, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len, uint32_t x,
+                                  uint32_t y, uint32_t rw, uint32_t rh, const void* d_rect, void* d_payload_out, uint64_t payload_cap,
+                                  void* d_slice_len_out, void* d_total, void* d_status, void* stream);
 /* Regions decode of a batch: frame f's rectangle (xy[2f], xy[2f + 1], rw, rh) -> d_px[f] of [frames][rh][rw][c], dense, in frame order:
  * byte for byte full_decode[f, y_f : y_f + rh, x_f : x_f + rw].  xy is HOST memory, 2 * frames values, read during the call and never
  * after it returns.  d_payload / payload_bytes / d_slice_len are the full batch's, as for llcomp_mi_codec_decode.  Each frame decodes

@@ -11,6 +11,7 @@
 //   struct llcomp::RawImage{pixels,width,height,channels}      :454     same members (width/height widened to 32 bit)
 //   llcomp::RawImage llcomp::decompressImage(data)             :461     same signature (+ overload with a device list)
 //                                                                       + llcomp::decompressRegion(data, x, y, w, h): one rectangle
+//                                                                       + llcomp::updateRegion(data, x, y, patch): replace one
 //   throw std::runtime_error("Invalid magic number")           :466     same text
 //   throw std::runtime_error("Invalid exponent")               :233     same text
 //
@@ -137,6 +138,28 @@ inline RawImage decompressRegion(const std::vector<uint8_t>& data, uint32_t x, u
     RawImage img{std::vector<uint8_t>(px, px + size_t(w) * h * c), w, h, uint8_t(c)};
     llcomp_mi_free(px);
     return img;
+}
+
+// The container `data` with the rectangle at (x, y) of the picture replaced by `patch` (llcomp_mi_update_region): byte for byte what
+// compressImage gives for the modified picture in the container's own format, tiling and model, but only the slices of the tiles the
+// rectangle touches are coded again.  Throws like decompressImage; std::invalid_argument for a rectangle the picture does not hold, a
+// patch whose pixels do not match its size, or whose channel count is not the container's.
+inline std::vector<uint8_t> updateRegion(const std::vector<uint8_t>& data, uint32_t x, uint32_t y, const RawImage& patch, int device = -1,
+                                         bool legacy_small_model = false) {
+    detail::check_abi();
+    llcomp_mi_info info;
+    if (int rc = llcomp_mi_probe(data.data(), data.size(), &info)) detail::raise(rc);
+    if (!patch.width || !patch.height || patch.channels != info.channels ||
+        patch.pixels.size() != size_t(patch.width) * patch.height * patch.channels)
+        detail::raise(LLCOMP_MI_BAD_ARGS);
+    uint8_t* out = nullptr;
+    size_t n = 0;
+    if (int rc = llcomp_mi_update_region(data.data(), data.size(), device, legacy_small_model ? LLCOMP_MI_FLAG_SMALL_MODEL : 0u, x, y,
+                                         patch.width, patch.height, patch.pixels.data(), &out, &n))
+        detail::raise(rc);
+    std::vector<uint8_t> v(out, out + n);
+    llcomp_mi_free(out);
+    return v;
 }
 
 }  // namespace llcomp

@@ -7,6 +7,8 @@ with ctypes and keeps the reference's names and error behaviour:
     compress_image(rgb, width, height, channels)  <->  llcomp::compressImage    (/root/reference/llcomp.hpp:358)
     decompress_image(data) -> RawImage            <->  llcomp::decompressImage  (/root/reference/llcomp.hpp:461)
     decompress_region(data, x, y, w, h)           <->  llcomp::decompressRegion (include/llcomp_mi.hpp: one rectangle, covered slices only)
+    update_region(data, x, y, patch)              <->  llcomp::updateRegion     (the write side: only the covered tiles are coded again)
+    replace_slices / Codec.encode_region / Codec.update_region  (the host-only splice, and the update of a batch in HBM)
     regions_plan(w, h, c, tw, th, planar, rw, rh, xy) / Codec.decode_regions  (a rectangle per frame of a batch; pack_batch feeds it)
     regions_gather / Codec.decode_regions_host / Stream.submit_decode_regions  (the same from host containers: only the windows cross)
     resize_weights / resized_regions_plan / Codec.decode_resized_regions(_host) / Stream.submit_decode_resized_regions  (a rectangle of
@@ -341,6 +343,104 @@ def decompress_region_into(data, out, x, y, w, h, *, device=-1, small_model=Fals
         e.channels = c.value
         raise e
     return c.value
+
+
+def _as_u8(a):
+    """a contiguous uint8 array of bytes-like or array input (kept alive by the caller for the call)"""
+    if isinstance(a, np.ndarray):
+        return np.ascontiguousarray(a, dtype=np.uint8)
+    return np.frombuffer(bytes(a), dtype=np.uint8)
+
+
+def _take(L, out, n):
+    """bytes of a buffer the library allocated, which is then freed"""
+    try:
+        return bytes(np.ctypeslib.as_array(out, shape=(max(n, 1),))[:n])
+    finally:
+        L.llcomp_mi_free(out)
+
+
+def replace_slices(data, box, new_len, new_payload):
+    """bytes of the SLICED container `data` with the slices of the tiles box = (tx0, ty0, tx1, ty1) (region_plan) replaced: new_len = the
+    covered slices' new lengths, new_payload = their streams back to back, both in sub-slice order (tile row, tile column, plane); every
+    other slice stays byte for byte (llcomp_mi_replace_slices, host only).  LlcompError as llcomp_mi_replace_slices reports it."""
+    L = _lib.load()
+    src = _as_u8(data)
+    lens = np.ascontiguousarray(new_len, dtype=np.uint32)
+    pay = _as_u8(new_payload)
+    if pay.size < int(lens.sum(dtype=np.uint64)):
+        raise LlcompError(BAD_ARGS, "new_payload is shorter than the sum of new_len")
+    b = (C.c_uint32 * 4)(*[int(v) for v in box])
+    out, n = _lib.u8p(), C.c_size_t()
+    _check(L.llcomp_mi_replace_slices(src.ctypes.data, src.size, b, lens.ctypes.data, pay.ctypes.data if pay.size else src.ctypes.data, C.byref(out),
+                                      C.byref(n)))
+    return _take(L, out, n.value)
+
+
+def replace_slices_into(data, box, new_len, new_payload, out):
+    """llcomp_mi_replace_slices_into: `out` a numpy uint8 array owned by the caller -> bytes written.  Raises LlcompError(OUTPUT_OVERFLOW)
+    with .needed set (and `out` untouched) when `out` is too small."""
+    L = _lib.load()
+    src = _as_u8(data)
+    lens = np.ascontiguousarray(new_len, dtype=np.uint32)
+    pay = _as_u8(new_payload)
+    if pay.size < int(lens.sum(dtype=np.uint64)):
+        raise LlcompError(BAD_ARGS, "new_payload is shorter than the sum of new_len")
+    b = (C.c_uint32 * 4)(*[int(v) for v in box])
+    n = C.c_size_t()
+    rc = L.llcomp_mi_replace_slices_into(src.ctypes.data, src.size, b, lens.ctypes.data, pay.ctypes.data if pay.size else src.ctypes.data,
+                                         out.ctypes.data, out.size, C.byref(n))
+    if rc != OK:
+        e = LlcompError(rc)
+        e.needed = n.value
+        raise e
+    return n.value
+
+
+def _patch(patch):
+    p = np.ascontiguousarray(patch, dtype=np.uint8)
+    if p.ndim == 2:
+        p = p[:, :, None]
+    if p.ndim != 3 or p.size == 0:
+        raise LlcompError(BAD_ARGS, "patch must be [h][w][c] (or [h][w]) and not empty")
+    return p
+
+
+def _check_patch_channels(src, p):
+    """the channel byte of either header against the patch (a container too short or of no known magic is left to the C call's verdict)"""
+    at = {0x79: 1, 0x9C: 2}.get(int(src[0])) if src.size >= 3 else None
+    if at is not None and int(src[at]) != p.shape[2]:
+        raise LlcompError(BAD_ARGS, "the patch's channel count is not the container's")
+
+
+def update_region(data, x, y, patch, *, device=-1, small_model=False):
+    """bytes of the container `data` (either format) with the rectangle at (x, y) of the picture replaced by patch (np.uint8 [h][w][c]):
+    byte for byte what a full encode of the modified picture gives, but only the slices of the tiles the rectangle touches are coded
+    again and only their bytes cross PCIe (llcomp_mi_update_region).  The patch's channel count must be the container's."""
+    L = _lib.load()
+    src = _as_u8(data)
+    p = _patch(patch)
+    _check_patch_channels(src, p)
+    out, n = _lib.u8p(), C.c_size_t()
+    _check(L.llcomp_mi_update_region(src.ctypes.data, src.size, device, 1 if small_model else 0, x, y, p.shape[1], p.shape[0], p.ctypes.data,
+                                     C.byref(out), C.byref(n)))
+    return _take(L, out, n.value)
+
+
+def update_region_into(data, out, x, y, patch, *, device=-1, small_model=False):
+    """llcomp_mi_update_region_into: `data` / `out` numpy uint8 arrays owned by the caller -> bytes written.  Raises
+    LlcompError(OUTPUT_OVERFLOW) with .needed set (and `out` untouched) when `out` is too small."""
+    L = _lib.load()
+    p = _patch(patch)
+    _check_patch_channels(data, p)
+    n = C.c_size_t()
+    rc = L.llcomp_mi_update_region_into(data.ctypes.data, data.size, device, 1 if small_model else 0, x, y, p.shape[1], p.shape[0], p.ctypes.data,
+                                        out.ctypes.data, out.size, C.byref(n))
+    if rc != OK:
+        e = LlcompError(rc)
+        e.needed = n.value
+        raise e
+    return n.value
 
 
 def trim():
@@ -723,6 +823,21 @@ class Codec:
         d_slice_len are the full batch's"""
         _check(self._L.llcomp_mi_codec_decode_region(self._h, d_payload, payload_bytes, d_slice_len, x, y, rw, rh, d_px, d_status, stream))
 
+    def encode_region(self, d_payload, payload_bytes, d_slice_len, x, y, rw, rh, d_rect, d_sub_payload, sub_payload_cap, d_sub_len, d_sub_total,
+                      d_status, stream=0):
+        """the rectangle (x, y, rw, rh) of every frame replaced by d_rect [frames][rh][rw][c]: the covered slices' new streams ->
+        d_sub_payload (packed, sub-slice order), d_sub_len u32[covered slices of all frames], d_sub_total (llcomp_mi_codec_encode_region).
+        d_payload / d_slice_len are the full batch's; they may be 0 when the rectangle is exactly its box's pixels."""
+        _check(self._L.llcomp_mi_codec_encode_region(self._h, d_payload or None, payload_bytes, d_slice_len or None, x, y, rw, rh, d_rect,
+                                                     d_sub_payload, sub_payload_cap, d_sub_len, d_sub_total, d_status, stream))
+
+    def update_region(self, d_payload, payload_bytes, d_slice_len, x, y, rw, rh, d_rect, d_payload_out, payload_cap, d_slice_len_out, d_total,
+                      d_status, stream=0):
+        """... and the splice in HBM: the full batch's new d_payload_out, d_slice_len_out u32[slices] and d_total, as encode would write
+        them for the modified frames (llcomp_mi_codec_update_region); the outputs must not overlap the inputs"""
+        _check(self._L.llcomp_mi_codec_update_region(self._h, d_payload or None, payload_bytes, d_slice_len or None, x, y, rw, rh, d_rect,
+                                                     d_payload_out, payload_cap, d_slice_len_out, d_total, d_status, stream))
+
     def region_family(self, x, y, rw, rh):
         """the kernel family a region decode of this rectangle runs (the keys of .family), None for a bad rectangle"""
         fam = self._L.llcomp_mi_codec_region_family(self._h, x, y, rw, rh)
@@ -812,11 +927,11 @@ class Codec:
         _check(self._L.llcomp_mi_codec_get_profile(self._h, ms, C.byref(ne), C.byref(nd)))
         return dict(zip(self.PROFILE_SLOTS, list(ms))), ne.value, nd.value
 
-    def prepare(self, encode=True, decode=True, region=False, regions=False, resized=False):
-        """allocate now what the first encode / decode / region decode / regions decode / resized regions decode would allocate inside
-        the call (llcomp_mi_codec_prepare)"""
+    def prepare(self, encode=True, decode=True, region=False, regions=False, resized=False, update=False):
+        """allocate now what the first encode / decode / region decode / regions decode / resized regions decode / region update would
+        allocate inside the call (llcomp_mi_codec_prepare)"""
         _check(self._L.llcomp_mi_codec_prepare(self._h, (1 if encode else 0) | (2 if decode else 0) | (8 if region else 0) | (16 if regions else 0)
-                                               | (32 if resized else 0)))
+                                               | (32 if resized else 0) | (64 if update else 0)))
 
     COUNTERS = ("dec_cached_waves", "dec_bypassed_waves", "cache_lookups", "cache_misses", "cache_writebacks", "dec_replays", "enc_carry_backs",
                 "generation_wraps", "dec_launches_cached", "dec_launches_plain", "host_staged_bytes")

@@ -36,6 +36,8 @@ SYMBOLS = [
     "llcomp_mi_codec_decode_resized_regions_host", "llcomp_mi_stream_submit_decode_resized_regions", "llcomp_mi_codec_allocated_bytes",
     "llcomp_mi_output_table", "llcomp_mi_codec_decode_resized_regions_ex", "llcomp_mi_codec_decode_resized_regions_host_ex",
     "llcomp_mi_stream_submit_decode_resized_regions_ex",
+    "llcomp_mi_replace_slices", "llcomp_mi_replace_slices_into", "llcomp_mi_update_region", "llcomp_mi_update_region_into",
+    "llcomp_mi_codec_encode_region", "llcomp_mi_codec_update_region",
 ]
 
 u8p = C.POINTER(C.c_uint8)
@@ -281,6 +283,23 @@ def load():
         L.llcomp_mi_stream_submit_decode_resized_regions_ex.restype = C.c_int
         L.llcomp_mi_stream_submit_decode_resized_regions_ex.argtypes = [C.c_void_p, ptrs, sizes, u32p, C.c_void_p, C.c_uint32, C.c_uint32, fmtp,
                                                                         C.c_uint64]
+    if "LLCOMP_MI_LIB" not in os.environ or hasattr(L, "llcomp_mi_replace_slices"):  # region update
+        u32p, sizep = C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)
+        L.llcomp_mi_replace_slices.restype = C.c_int
+        L.llcomp_mi_replace_slices.argtypes = [C.c_void_p, C.c_size_t, u32p, C.c_void_p, C.c_void_p, C.POINTER(u8p), sizep]
+        L.llcomp_mi_replace_slices_into.restype = C.c_int
+        L.llcomp_mi_replace_slices_into.argtypes = [C.c_void_p, C.c_size_t, u32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, sizep]
+        L.llcomp_mi_update_region.restype = C.c_int
+        L.llcomp_mi_update_region.argtypes = [C.c_void_p, C.c_size_t, C.c_int32, C.c_uint32] + [C.c_uint32] * 4 + [C.c_void_p, C.POINTER(u8p), sizep]
+        L.llcomp_mi_update_region_into.restype = C.c_int
+        L.llcomp_mi_update_region_into.argtypes = [C.c_void_p, C.c_size_t, C.c_int32, C.c_uint32] + [C.c_uint32] * 4 + [C.c_void_p, C.c_void_p,
+                                                                                                                    C.c_size_t, sizep]
+        L.llcomp_mi_codec_encode_region.restype = C.c_int
+        L.llcomp_mi_codec_encode_region.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p, C.c_void_p,
+                                                                                                                        C.c_uint64] + [C.c_void_p] * 4
+        L.llcomp_mi_codec_update_region.restype = C.c_int
+        L.llcomp_mi_codec_update_region.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p, C.c_void_p,
+                                                                                                                        C.c_uint64] + [C.c_void_p] * 4
     if "LLCOMP_MI_LIB" not in os.environ and L.llcomp_mi_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.llcomp_mi_abi_version()}, this binding was written for {ABI_VERSION}: rebuild the library")
     _lib = L

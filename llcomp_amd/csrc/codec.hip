@@ -19,6 +19,7 @@
 #include "resize.hpp"
 #include "snapshot.hpp"
 #include "tables.hpp"
+#include "update.hpp"
 
 using namespace llcomp_mi;
 
@@ -140,14 +141,31 @@ hipStream_t shared_second_stream(int device) {
     return streams[device];
 }
 
-// the snapshot pass's arrays (2-D encoder): allocated by the first encode -- a decode-only codec never pays for them
-int ensure_snapshot_arrays(llcomp_mi_codec* k) {
-    if (k->d_snap_sorted) return LLCOMP_MI_OK;
-    const uint64_t el = snapshot_elems(k->g);
-    const bool chunked = snapshot_chunked(k->g);
+// the snapshot pass's arrays (2-D encoder): allocated by the first encode -- a decode-only codec never pays for them.
+// g: the geometry about to run -- the codec's own, whose arrays hold every sub-geometry's too (region_encode_fits), or a region update's
+// sub-geometry that runs the pass where the codec's family does not: then the arrays are sized for what the call needs and grown
+// geometrically, up to region_snapshot_bound (the old ones may still be used by the codec's last call: that call is waited for).
+int ensure_snapshot_arrays(llcomp_mi_codec* k, const Geometry& g) {
+    const bool own = snapshot_mode(k->g);
+    const bool chunked = snapshot_chunked(g);
+    const uint64_t need = snapshot_elems(g);
+    if (k->d_snap_sorted && need <= k->snap_el && (!chunked || k->d_snap_ctx)) return LLCOMP_MI_OK;
+    const uint64_t el = own ? snapshot_elems(k->g) : std::max(need, std::min(2 * k->snap_el, region_snapshot_bound(k->g)));
+    const bool with_chunks = own ? snapshot_chunked(k->g) : true;  // (a region of a codec without the pass: its slices may be above 4096 samples)
+    if (k->d_snap_sorted) {
+        if (k->done && k->done->ev && hipEventSynchronize(k->done->ev) != hipSuccess) return LLCOMP_MI_HIP_ERROR;
+        dev_free(k->d_snap_sorted);
+        dev_free(k->d_snap_banks);
+        dev_free(k->d_snap_res);
+        dev_free(k->d_snap_ctx);
+        dev_free(k->d_snap_io);
+        k->allocated_bytes -= k->snap_el * (k->d_snap_ctx ? 28 : 18);
+        k->d_snap_sorted = k->d_snap_banks = k->d_snap_res = k->d_snap_ctx = k->d_snap_io = nullptr;
+        k->snap_el = 0;
+    }
     if (dev_alloc(&k->d_snap_sorted, el * 8) != hipSuccess || dev_alloc(&k->d_snap_banks, el * 8) != hipSuccess ||
         dev_alloc(&k->d_snap_res, el * 2) != hipSuccess ||
-        (chunked && (dev_alloc(&k->d_snap_ctx, el * 2) != hipSuccess || dev_alloc(&k->d_snap_io, el * 8) != hipSuccess))) {
+        (with_chunks && (dev_alloc(&k->d_snap_ctx, el * 2) != hipSuccess || dev_alloc(&k->d_snap_io, el * 8) != hipSuccess))) {
         dev_free(k->d_snap_sorted);
         dev_free(k->d_snap_banks);
         dev_free(k->d_snap_res);
@@ -156,15 +174,17 @@ int ensure_snapshot_arrays(llcomp_mi_codec* k) {
         k->d_snap_sorted = k->d_snap_banks = k->d_snap_res = k->d_snap_ctx = k->d_snap_io = nullptr;
         return LLCOMP_MI_NOMEM;
     }
-    k->allocated_bytes += el * (chunked ? 28 : 18);
-    if (chunked) {  // the coder's parking records, the second stream and the events of the fork / join
+    k->snap_el = el;
+    k->allocated_bytes += el * (with_chunks ? 28 : 18);
+    if (with_chunks && !k->d_seg_state) {  // the coder's parking records, the second stream and the events of the fork / join
         if (dev_alloc(reinterpret_cast<void**>(&k->d_seg_state), uint64_t(k->g.n_slices) * 64) != hipSuccess) { k->d_seg_state = nullptr; return LLCOMP_MI_NOMEM; }
         k->allocated_bytes += uint64_t(k->g.n_slices) * 64;
         if (k->overlap) {
             bool ok = (k->aux_shared ? (k->aux = shared_second_stream(k->device)) != nullptr
                                      : hipStreamCreateWithFlags(&k->aux, hipStreamNonBlocking) == hipSuccess) &&
                       hipEventCreateWithFlags(&k->ev_fork, hipEventDisableTiming) == hipSuccess;
-            for (uint32_t c = 0; ok && c < snapshot_chunks(k->g); ++c) ok = hipEventCreateWithFlags(&k->ev_chunk[c], hipEventDisableTiming) == hipSuccess;
+            for (uint32_t c = 0; ok && c < kSnapMaxChunks; ++c)
+                if (!k->ev_chunk[c]) ok = hipEventCreateWithFlags(&k->ev_chunk[c], hipEventDisableTiming) == hipSuccess;
             if (!ok) {  // no second stream to be had: the pass runs on the caller's (slower at few frames in flight, same bytes)
                 (void)hipGetLastError();
                 k->overlap = false;
@@ -241,6 +261,17 @@ int ensure_region_arrays(llcomp_mi_codec* k) {
         return LLCOMP_MI_NOMEM;
     }
     k->allocated_bytes += n * 12;
+    return LLCOMP_MI_OK;
+}
+// region update: the sub-geometry's group offsets (at most one lane group per slice) and the full geometry's for the new table
+int ensure_update_arrays(llcomp_mi_codec* k) {
+    if (k->d_upd_goff) return LLCOMP_MI_OK;
+    const uint64_t bytes = (uint64_t(k->g.n_slices) + 1 + lane_groups(k->g) + 1) * 8;
+    if (dev_alloc(reinterpret_cast<void**>(&k->d_upd_goff), bytes) != hipSuccess) {
+        k->d_upd_goff = nullptr;
+        return LLCOMP_MI_NOMEM;
+    }
+    k->allocated_bytes += bytes;
     return LLCOMP_MI_OK;
 }
 // A family that keeps its states on chip for the full geometry may not for a region's: one slice per wavefront (few big slices) can
@@ -563,6 +594,107 @@ int resized_setup(const llcomp_mi_codec* k, const uint32_t* rects, const uint8_t
     return LLCOMP_MI_OK;
 }
 
+// The encoder on geometry g, in the codec's workspace, up to the slices' streams in d_scratch (stream lane order) and their lengths in
+// d_slice_len: the codec's own geometry (llcomp_mi_codec_encode) or the sub-geometry of a region update's box, whose kernel family may
+// be another one.  d_px: g.frames * g.h * g.w * g.c bytes, exactly (the row encoder that reads pixels sizes its dword reads by it).
+// d_group_off: u64[lane groups of g + 1]; it holds the group sums afterwards where encoder_writes_group_sums(g).
+int encode_streams(llcomp_mi_codec* k, const Geometry& g, const void* d_px, uint32_t* d_slice_len, uint64_t* d_group_off, uint32_t* d_status,
+                   hipStream_t s) {
+    // (the snapshot encoder of slices up to 4096 samples never touches the state tables: they are the decoder's alone; above that
+    // the pass carries a context's states from chunk to chunk through them, under a generation of its own)
+    if (!snapshot_mode(g) || snapshot_chunked(g)) {
+        Timed t(k, s, 0);
+        if (int rc = next_state_generation(k, s, slices_need_state_tables(g))) return rc;
+    }
+    {
+        Timed t(k, s, 1);
+        if (rows_encoder_reads_pixels(g)) {
+            // nothing: the coder reads the pixels itself
+        } else if (model_is_fused(g)) {
+            HIP_TRY(launch_model_rows_fwd(g, static_cast<const uint8_t*>(d_px), static_cast<uint16_t*>(k->d_lane_order), s));
+        } else {
+            HIP_TRY(launch_model_fwd(g, static_cast<const uint8_t*>(d_px), static_cast<uint32_t*>(k->d_sym_or_rec), s));
+            if (!snapshot_mode(g))
+                HIP_TRY(launch_to_lane_order_u32(g, static_cast<const uint32_t*>(k->d_sym_or_rec),
+                                                 static_cast<uint32_t*>(k->d_lane_order), s));
+        }
+    }
+    if (snapshot_mode(g) && snapshot_chunked(g)) {
+        // Slices above 4096 samples: pass and coder chunk by chunk.  The pass of chunk c + 1 needs the WALK of chunk c (the contexts'
+        // states travel through the table), the coder of chunk c needs the pass of chunk c only: so the pass runs AHEAD on a second
+        // stream and the coder follows on the caller's, each segment behind its chunk's event (fork / join: the caller's stream still
+        // orders everything).  A launch of such slices is a few hundred wavefronts -- one wavefront's dependent chain -- and the
+        // pass's nine or twelve launches in FRONT of it cost 8-11 % against the table encoder at few frames in flight; beside it they
+        // are hidden.  The second stream is ONE PER DEVICE, shared by all codec objects (the passes are throughput kernels: they may
+        // queue behind each other): a second stream per codec left the GPU idle as soon as three pipelines made six streams (25 %
+        // below in-order; more hardware queues change nothing) -- profiles/r06_chunked_snapshot_ab.txt.  LLCOMP_MI_OVERLAP=0: in order.
+        if (int rc = ensure_snapshot_arrays(k, g)) return rc;
+        const uint64_t gpat = state_generation_tag(k->state_generation);
+        const uint32_t chunks = snapshot_chunks(g);
+        hipStream_t ps = k->overlap ? k->aux : s;
+        if (k->overlap) {  // fork: the pass starts behind stage A
+            HIP_TRY(hipEventRecord(k->ev_fork, s));
+            HIP_TRY(hipStreamWaitEvent(k->aux, k->ev_fork, 0));
+        }
+        auto pass = [&](uint32_t c) -> int {
+            Timed t(k, ps, 0);
+            HIP_TRY(launch_snapshot_chunk(g, c, static_cast<const uint32_t*>(k->d_sym_or_rec), k->d_lane_order, k->d_snap_sorted, k->d_snap_banks,
+                                          k->d_snap_res, k->d_snap_ctx, k->d_snap_io, k->d_states, gpat, ps));
+            return LLCOMP_MI_OK;
+        };
+        auto coder = [&](uint32_t c) -> int {
+            Timed t(k, s, 2);
+            HIP_TRY(launch_encode_segment(g, k->d_snap_res, static_cast<uint64_t*>(k->d_snap_banks), k->d_scratch, d_slice_len,
+                                          d_status, k->d_counters, c * kSnapMaxSamples, k->d_seg_state, s));
+            return LLCOMP_MI_OK;
+        };
+        int rc = LLCOMP_MI_OK;
+        if (k->overlap) {
+            for (uint32_t c = 0; c < chunks && !rc; ++c) {
+                rc = pass(c);
+                if (!rc && hipEventRecord(k->ev_chunk[c], k->aux) != hipSuccess) rc = LLCOMP_MI_HIP_ERROR;
+            }
+            // join: every segment waits for its chunk -- also when something failed above: whatever was queued on the second stream
+            // has to be behind the caller's stream before this call returns its buffers to anybody
+            for (uint32_t c = 0; c < chunks; ++c) {
+                if (hipStreamWaitEvent(s, k->ev_chunk[c], 0) != hipSuccess) { (void)hipGetLastError(); (void)hipStreamSynchronize(k->aux); }
+                if (!rc) rc = coder(c);
+            }
+        } else {
+            for (uint32_t c = 0; c < chunks && !rc; ++c) {
+                rc = pass(c);
+                if (!rc) rc = coder(c);
+            }
+        }
+        if (rc) return rc;
+    } else {
+    if (snapshot_mode(g)) {  // states replayed ahead of the coder: it reads banks + residuals front to back, no table
+        if (int rc = ensure_snapshot_arrays(k, g)) return rc;
+        Timed t(k, s, 0);    // (profile slot 0: the pass takes the place of the state tables whose clear the slot times otherwise)
+        HIP_TRY(launch_snapshot(g, static_cast<const uint32_t*>(k->d_sym_or_rec), k->d_lane_order, k->d_snap_sorted,
+                                k->d_snap_banks, k->d_snap_res, s));
+    }
+    {
+        Timed t(k, s, 2);
+        const bool snap = snapshot_mode(g);
+        const void* in = snap ? k->d_snap_res : rows_encoder_reads_pixels(g) ? d_px : k->d_lane_order;
+        HIP_TRY(launch_encode_slices(g, in, snap ? static_cast<uint64_t*>(k->d_snap_banks) : k->d_states,
+                                     k->state_generation, k->d_scratch, d_slice_len,
+                                     d_group_off, d_status, k->d_counters, s));
+    }
+    }
+    return LLCOMP_MI_OK;
+}
+// ... and from there to the packed payload: group sums -> offsets and *d_total, streams -> d_payload (kStOverflow past payload_cap)
+int pack_streams(llcomp_mi_codec* k, const Geometry& g, const uint32_t* d_slice_len, uint64_t* d_group_off, uint8_t* d_payload, uint64_t payload_cap,
+                 uint64_t* d_total, uint32_t* d_status, hipStream_t s) {
+    Timed t(k, s, 3);
+    if (!encoder_writes_group_sums(g)) HIP_TRY(launch_group_sums(g, d_slice_len, d_group_off, s));
+    HIP_TRY(launch_scan_groups(g, d_group_off, d_total, s));
+    HIP_TRY(launch_pack_payload(g, k->d_scratch, d_slice_len, d_group_off, d_payload, payload_cap, d_status, s));
+    return LLCOMP_MI_OK;
+}
+
 }  // namespace
 
 namespace llcomp_mi {
@@ -591,6 +723,7 @@ void codec_release(llcomp_mi_codec* k) {
     dev_free(k->d_stage, k->done);
     dev_free(k->d_box, k->done);
     dev_free(k->d_mid, k->done);
+    dev_free(k->d_upd_goff, k->done);
     for (uint32_t i = 0; i < llcomp_mi_codec::kRegionsRing; ++i) {
         if (!k->h_regions[i]) continue;
         // (a copy out of the slot may still be queued on a caller's stream: it must not read freed memory)
@@ -718,8 +851,12 @@ int llcomp_mi::codec_create(llcomp_mi_codec** out, int32_t device, uint32_t fram
     // ... plus the boxes and the horizontal pass's rows of a resized regions decode (frames * w * h * c each) and what its tables add to
     // the staging buffer (resized_tables_bound), for outputs no larger than the image
     const uint64_t b_resized = 2 * samples + resized_tables_bound(g);
-    k->workspace_bytes =
-        b_sym + b_lanes + b_states + b_scratch + b_off + 8 + snap_el * (snapshot_chunked(g) ? 28 : 18) + b_region + b_regions + b_resized;
+    // ... plus a region update's two offset arrays, and the snapshot arrays + parking records of a box whose sub-geometry runs the pass
+    // where the codec's family does not (region_snapshot_bound; the decoded box is the resized path's)
+    const uint64_t b_update = (uint64_t(g.n_slices) + 1 + lane_groups(g) + 1) * 8 +
+                              (snap ? 0 : region_snapshot_bound(g) ? region_snapshot_bound(g) * 28 + uint64_t(g.n_slices) * 64 : 0);
+    k->workspace_bytes = b_sym + b_lanes + b_states + b_scratch + b_off + 8 + snap_el * (snapshot_chunked(g) ? 28 : 18) + b_region + b_regions +
+                         b_resized + b_update;
     const bool ok = dev_alloc(&k->d_sym_or_rec, b_sym) == hipSuccess && dev_alloc(&k->d_lane_order, b_lanes) == hipSuccess &&
                     dev_alloc(reinterpret_cast<void**>(&k->d_scratch), b_scratch) == hipSuccess &&
                     dev_alloc(reinterpret_cast<void**>(&k->d_group_off), b_off) == hipSuccess &&
@@ -746,26 +883,31 @@ void llcomp_mi_codec_destroy(llcomp_mi_codec* k) {
 
 int llcomp_mi_codec_prepare(llcomp_mi_codec* k, uint32_t what) {
     if (!k || (what & ~(LLCOMP_MI_PREPARE_ENCODE | LLCOMP_MI_PREPARE_DECODE | LLCOMP_MI_PREPARE_REGION | LLCOMP_MI_PREPARE_REGIONS |
-                        LLCOMP_MI_PREPARE_RESIZED)))
+                        LLCOMP_MI_PREPARE_RESIZED | LLCOMP_MI_PREPARE_UPDATE)))
         return LLCOMP_MI_BAD_ARGS;
     DeviceGuard guard(k->device);
     if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
     if (what & LLCOMP_MI_PREPARE_ENCODE) {
         if (snapshot_mode(k->g)) {
-            if (int rc = ensure_snapshot_arrays(k)) return rc;
+            if (int rc = ensure_snapshot_arrays(k, k->g)) return rc;
         }
         if (!snapshot_mode(k->g) || snapshot_chunked(k->g))
             if (int rc = ensure_state_tables(k, k->need_states)) return rc;
     }
     if (what & LLCOMP_MI_PREPARE_DECODE)
         if (int rc = ensure_state_tables(k, k->need_states)) return rc;
-    if (what & (LLCOMP_MI_PREPARE_REGION | LLCOMP_MI_PREPARE_REGIONS | LLCOMP_MI_PREPARE_RESIZED)) {
+    if (what & (LLCOMP_MI_PREPARE_REGION | LLCOMP_MI_PREPARE_REGIONS | LLCOMP_MI_PREPARE_RESIZED | LLCOMP_MI_PREPARE_UPDATE)) {
         if (int rc = ensure_region_arrays(k)) return rc;
         if (region_may_need_states(k))
             if (int rc = ensure_state_tables(k, true)) return rc;
     }
     if (what & LLCOMP_MI_PREPARE_REGIONS)
         if (int rc = ensure_regions_table(k)) return rc;
+    if (what & LLCOMP_MI_PREPARE_UPDATE) {  // (the encoder's own arrays: LLCOMP_MI_PREPARE_ENCODE)
+        const uint64_t samples = uint64_t(k->g.frames) * k->g.w * k->g.h * k->g.c;
+        if (int rc = ensure_update_arrays(k)) return rc;
+        if (int rc = ensure_grown(k, k->d_box, k->box_cap, samples, samples)) return rc;
+    }
     if (what & LLCOMP_MI_PREPARE_RESIZED) {
         const uint64_t samples = uint64_t(k->g.frames) * k->g.w * k->g.h * k->g.c;
         if (int rc = ensure_regions_ring(k)) return rc;
@@ -798,99 +940,12 @@ int llcomp_mi_codec_encode(llcomp_mi_codec* k, const void* d_px, void* d_payload
     DeviceGuard guard(k->device);
     if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const Geometry& g = k->g;
     DoneGuard done_guard{k, s};
     HIP_TRY(hipMemsetAsync(d_status, 0, 4, s));
-    // (the snapshot encoder of slices up to 4096 samples never touches the state tables: they are the decoder's alone; above that
-    // the pass carries a context's states from chunk to chunk through them, under a generation of its own)
-    if (!snapshot_mode(g) || snapshot_chunked(g)) {
-        Timed t(k, s, 0);
-        if (int rc = next_state_generation(k, s, k->need_states)) return rc;
-    }
-    {
-        Timed t(k, s, 1);
-        if (rows_encoder_reads_pixels(g)) {
-            // nothing: the coder reads the pixels itself
-        } else if (model_is_fused(g)) {
-            HIP_TRY(launch_model_rows_fwd(g, static_cast<const uint8_t*>(d_px), static_cast<uint16_t*>(k->d_lane_order), s));
-        } else {
-            HIP_TRY(launch_model_fwd(g, static_cast<const uint8_t*>(d_px), static_cast<uint32_t*>(k->d_sym_or_rec), s));
-            if (!snapshot_mode(g))
-                HIP_TRY(launch_to_lane_order_u32(g, static_cast<const uint32_t*>(k->d_sym_or_rec),
-                                                 static_cast<uint32_t*>(k->d_lane_order), s));
-        }
-    }
-    if (snapshot_mode(g) && snapshot_chunked(g)) {
-        // Slices above 4096 samples: pass and coder chunk by chunk.  The pass of chunk c + 1 needs the WALK of chunk c (the contexts'
-        // states travel through the table), the coder of chunk c needs the pass of chunk c only: so the pass runs AHEAD on a second
-        // stream and the coder follows on the caller's, each segment behind its chunk's event (fork / join: the caller's stream still
-        // orders everything).  A launch of such slices is a few hundred wavefronts -- one wavefront's dependent chain -- and the
-        // pass's nine or twelve launches in FRONT of it cost 8-11 % against the table encoder at few frames in flight; beside it they
-        // are hidden.  The second stream is ONE PER DEVICE, shared by all codec objects (the passes are throughput kernels: they may
-        // queue behind each other): a second stream per codec left the GPU idle as soon as three pipelines made six streams (25 %
-        // below in-order; more hardware queues change nothing) -- profiles/r06_chunked_snapshot_ab.txt.  LLCOMP_MI_OVERLAP=0: in order.
-        if (int rc = ensure_snapshot_arrays(k)) return rc;
-        const uint64_t gpat = state_generation_tag(k->state_generation);
-        const uint32_t chunks = snapshot_chunks(g);
-        hipStream_t ps = k->overlap ? k->aux : s;
-        if (k->overlap) {  // fork: the pass starts behind stage A
-            HIP_TRY(hipEventRecord(k->ev_fork, s));
-            HIP_TRY(hipStreamWaitEvent(k->aux, k->ev_fork, 0));
-        }
-        auto pass = [&](uint32_t c) -> int {
-            Timed t(k, ps, 0);
-            HIP_TRY(launch_snapshot_chunk(g, c, static_cast<const uint32_t*>(k->d_sym_or_rec), k->d_lane_order, k->d_snap_sorted, k->d_snap_banks,
-                                          k->d_snap_res, k->d_snap_ctx, k->d_snap_io, k->d_states, gpat, ps));
-            return LLCOMP_MI_OK;
-        };
-        auto coder = [&](uint32_t c) -> int {
-            Timed t(k, s, 2);
-            HIP_TRY(launch_encode_segment(g, k->d_snap_res, static_cast<uint64_t*>(k->d_snap_banks), k->d_scratch, static_cast<uint32_t*>(d_slice_len),
-                                          static_cast<uint32_t*>(d_status), k->d_counters, c * kSnapMaxSamples, k->d_seg_state, s));
-            return LLCOMP_MI_OK;
-        };
-        int rc = LLCOMP_MI_OK;
-        if (k->overlap) {
-            for (uint32_t c = 0; c < chunks && !rc; ++c) {
-                rc = pass(c);
-                if (!rc && hipEventRecord(k->ev_chunk[c], k->aux) != hipSuccess) rc = LLCOMP_MI_HIP_ERROR;
-            }
-            // join: every segment waits for its chunk -- also when something failed above: whatever was queued on the second stream
-            // has to be behind the caller's stream before this call returns its buffers to anybody
-            for (uint32_t c = 0; c < chunks; ++c) {
-                if (hipStreamWaitEvent(s, k->ev_chunk[c], 0) != hipSuccess) { (void)hipGetLastError(); (void)hipStreamSynchronize(k->aux); }
-                if (!rc) rc = coder(c);
-            }
-        } else {
-            for (uint32_t c = 0; c < chunks && !rc; ++c) {
-                rc = pass(c);
-                if (!rc) rc = coder(c);
-            }
-        }
-        if (rc) return rc;
-    } else {
-    if (snapshot_mode(g)) {  // states replayed ahead of the coder: it reads banks + residuals front to back, no table
-        if (int rc = ensure_snapshot_arrays(k)) return rc;
-        Timed t(k, s, 0);    // (profile slot 0: the pass takes the place of the state tables whose clear the slot times otherwise)
-        HIP_TRY(launch_snapshot(g, static_cast<const uint32_t*>(k->d_sym_or_rec), k->d_lane_order, k->d_snap_sorted,
-                                k->d_snap_banks, k->d_snap_res, s));
-    }
-    {
-        Timed t(k, s, 2);
-        const bool snap = snapshot_mode(g);
-        const void* in = snap ? k->d_snap_res : rows_encoder_reads_pixels(g) ? d_px : k->d_lane_order;
-        HIP_TRY(launch_encode_slices(g, in, snap ? static_cast<uint64_t*>(k->d_snap_banks) : k->d_states,
-                                     k->state_generation, k->d_scratch, static_cast<uint32_t*>(d_slice_len),
-                                     k->d_group_off, static_cast<uint32_t*>(d_status), k->d_counters, s));
-    }
-    }
-    {
-        Timed t(k, s, 3);
-        if (!encoder_writes_group_sums(g)) HIP_TRY(launch_group_sums(g, static_cast<const uint32_t*>(d_slice_len), k->d_group_off, s));
-        HIP_TRY(launch_scan_groups(g, k->d_group_off, static_cast<uint64_t*>(d_total), s));
-        HIP_TRY(launch_pack_payload(g, k->d_scratch, static_cast<const uint32_t*>(d_slice_len), k->d_group_off,
-                                    static_cast<uint8_t*>(d_payload), payload_cap, static_cast<uint32_t*>(d_status), s));
-    }
+    if (int rc = encode_streams(k, k->g, d_px, static_cast<uint32_t*>(d_slice_len), k->d_group_off, static_cast<uint32_t*>(d_status), s)) return rc;
+    if (int rc = pack_streams(k, k->g, static_cast<const uint32_t*>(d_slice_len), k->d_group_off, static_cast<uint8_t*>(d_payload), payload_cap,
+                              static_cast<uint64_t*>(d_total), static_cast<uint32_t*>(d_status), s))
+        return rc;
     ++k->n_encode;
     return LLCOMP_MI_OK;
 }
@@ -997,6 +1052,148 @@ int llcomp_mi_codec_decode_region(llcomp_mi_codec* k, const void* d_payload, uin
     ++k->n_decode;
     return LLCOMP_MI_OK;
 }
+
+}  // extern "C"
+
+namespace {
+// A region update's plan: the covered box, its sub-geometry, and whether the rectangle is exactly the box's pixels.  BAD_ARGS for a
+// rectangle the frame does not hold; HIP_ERROR if the sub-geometry's arrays would not fit the codec's workspace (region_encode_fits:
+// never by default, checked all the same) -- both before anything is launched.
+struct UpdatePlan {
+    RegionBox box;
+    Geometry sub;
+    bool whole;
+};
+int update_setup(const llcomp_mi_codec* k, uint32_t x, uint32_t y, uint32_t rw, uint32_t rh, UpdatePlan& p) {
+    if (int rc = region_setup(k, x, y, rw, rh, p.box, p.sub)) return rc;
+    if (!region_encode_fits(k->g, p.sub)) return LLCOMP_MI_HIP_ERROR;
+    p.whole = region_is_whole_box(k->g, p.sub, p.box, x, y, rw, rh);
+    return LLCOMP_MI_OK;
+}
+// The box's new pixels, [frames][sub.h][sub.w][c]: the caller's rectangle itself when it is the whole box; else the box is decoded from
+// the old batch into the codec's box buffer (llcomp_mi_codec_decode_region's chain up to the inverse model on the sub-geometry, written
+// whole: no crop) and the rectangle is pasted over it.  Leaves the old table's group offsets of the FULL geometry in d_group_off.
+int update_box_pixels(llcomp_mi_codec* k, const UpdatePlan& p, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len, uint32_t x,
+                      uint32_t y, uint32_t rw, uint32_t rh, const void* d_rect, uint32_t* d_status, hipStream_t s, const void** d_box_px) {
+    const Geometry& g = k->g;
+    const Geometry& sub = p.sub;
+    if (p.whole) {
+        *d_box_px = d_rect;
+        return LLCOMP_MI_OK;
+    }
+    {
+        Timed t(k, s, 7);
+        if (int rc = next_state_generation(k, s, slices_need_state_tables(sub))) return rc;
+    }
+    {
+        Timed t(k, s, 4);
+        HIP_TRY(launch_group_sums(g, static_cast<const uint32_t*>(d_slice_len), k->d_group_off, s));
+        HIP_TRY(launch_scan_groups(g, k->d_group_off, k->d_total_tmp, s));
+        HIP_TRY(launch_region_index(g, sub, p.box, static_cast<const uint32_t*>(d_slice_len), k->d_group_off, k->d_region_len, k->d_region_off, s));
+        HIP_TRY(launch_stage_region_streams(sub, static_cast<const uint8_t*>(d_payload), payload_bytes, k->d_region_len, k->d_region_off,
+                                            k->d_scratch, d_status, s));
+    }
+    {
+        Timed t(k, s, 5);
+        const bool cache = use_bank_cache(k, sub);
+        HIP_TRY(launch_decode_slices(sub, k->d_scratch, k->d_region_len, k->d_states, k->state_generation, static_cast<int16_t*>(k->d_lane_order),
+                                     d_status, k->d_counters, cache, s));
+        if (cache) queue_feedback(k, s);
+    }
+    {
+        Timed t(k, s, 6);
+        if (model_is_fused(sub)) {
+            HIP_TRY(launch_model_rows_inv(sub, static_cast<const int16_t*>(k->d_lane_order), k->d_box, s));
+        } else {
+            HIP_TRY(launch_from_lane_order_i16(sub, static_cast<const int16_t*>(k->d_lane_order), static_cast<int16_t*>(k->d_sym_or_rec), s));
+            HIP_TRY(launch_model_inv(sub, static_cast<const int16_t*>(k->d_sym_or_rec), k->d_box, s));
+        }
+        HIP_TRY(launch_paste_rect(static_cast<const uint8_t*>(d_rect), k->d_box, sub.frames, sub.c, rw, rh, sub.w, sub.h, x - p.box.tx0 * g.tile_w,
+                                  y - p.box.ty0 * g.tile_h, s));
+    }
+    ++k->n_decode;
+    *d_box_px = k->d_box;
+    return LLCOMP_MI_OK;
+}
+// what both calls allocate before they queue anything
+int update_ensure(llcomp_mi_codec* k, const UpdatePlan& p) {
+    if (int rc = ensure_region_arrays(k)) return rc;
+    if (int rc = ensure_update_arrays(k)) return rc;
+    if (p.whole) return LLCOMP_MI_OK;
+    const uint64_t samples = uint64_t(k->g.frames) * k->g.w * k->g.h * k->g.c;
+    return ensure_grown(k, k->d_box, k->box_cap, uint64_t(p.sub.frames) * p.sub.w * p.sub.h * p.sub.c, samples);
+}
+}  // namespace
+
+extern "C" {
+
+// Region update (DESIGN.md "Region update"): the covered box's new pixels (update_box_pixels) through the encoder on the box's
+// sub-geometry (encode_streams), then either packed as they are (encode_region) or spliced into the full batch in HBM (update_region).
+int llcomp_mi_codec_encode_region(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len, uint32_t x,
+                                  uint32_t y, uint32_t rw, uint32_t rh, const void* d_rect, void* d_sub_payload, uint64_t sub_payload_cap,
+                                  void* d_sub_len, void* d_sub_total, void* d_status, void* stream) {
+    if (!k || !d_rect || !d_sub_payload || !d_sub_len || !d_sub_total || !d_status) return LLCOMP_MI_BAD_ARGS;
+    UpdatePlan p;
+    if (int rc = update_setup(k, x, y, rw, rh, p)) return rc;
+    if (!p.whole && (!d_payload || !d_slice_len)) return LLCOMP_MI_BAD_ARGS;
+    DeviceGuard guard(k->device);
+    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
+    if (int rc = update_ensure(k, p)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DoneGuard done_guard{k, s};
+    HIP_TRY(hipMemsetAsync(d_status, 0, 4, s));
+    const void* px = nullptr;
+    if (int rc = update_box_pixels(k, p, d_payload, payload_bytes, d_slice_len, x, y, rw, rh, d_rect, static_cast<uint32_t*>(d_status), s, &px))
+        return rc;
+    if (int rc = encode_streams(k, p.sub, px, static_cast<uint32_t*>(d_sub_len), k->d_upd_goff, static_cast<uint32_t*>(d_status), s)) return rc;
+    if (int rc = pack_streams(k, p.sub, static_cast<const uint32_t*>(d_sub_len), k->d_upd_goff, static_cast<uint8_t*>(d_sub_payload),
+                              sub_payload_cap, static_cast<uint64_t*>(d_sub_total), static_cast<uint32_t*>(d_status), s))
+        return rc;
+    ++k->n_encode;
+    return LLCOMP_MI_OK;
+}
+
+int llcomp_mi_codec_update_region(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len, uint32_t x,
+                                  uint32_t y, uint32_t rw, uint32_t rh, const void* d_rect, void* d_payload_out, uint64_t payload_cap,
+                                  void* d_slice_len_out, void* d_total, void* d_status, void* stream) {
+    if (!k || !d_rect || !d_payload_out || !d_slice_len_out || !d_total || !d_status) return LLCOMP_MI_BAD_ARGS;
+    UpdatePlan p;
+    if (int rc = update_setup(k, x, y, rw, rh, p)) return rc;
+    const Geometry& g = k->g;
+    const bool all = p.sub.n_slices == g.n_slices;  // every slice is covered: nothing of the old batch is carried over
+    if (!(p.whole && all) && (!d_payload || !d_slice_len)) return LLCOMP_MI_BAD_ARGS;
+    DeviceGuard guard(k->device);
+    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
+    if (int rc = update_ensure(k, p)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DoneGuard done_guard{k, s};
+    uint32_t* const status = static_cast<uint32_t*>(d_status);
+    HIP_TRY(hipMemsetAsync(d_status, 0, 4, s));
+    const void* px = nullptr;
+    if (int rc = update_box_pixels(k, p, d_payload, payload_bytes, d_slice_len, x, y, rw, rh, d_rect, status, s, &px)) return rc;
+    // the covered slices' new lengths go where the decoder's copy of the old ones was (it is done with them: same stream)
+    if (int rc = encode_streams(k, p.sub, px, k->d_region_len, k->d_upd_goff, status, s)) return rc;
+    {
+        Timed t(k, s, 3);
+        uint64_t* const new_goff = k->d_upd_goff + g.n_slices + 1;
+        if (p.whole && !all) {  // (the decode of an unaligned rectangle has left the old table's offsets in d_group_off)
+            HIP_TRY(launch_group_sums(g, static_cast<const uint32_t*>(d_slice_len), k->d_group_off, s));
+            HIP_TRY(launch_scan_groups(g, k->d_group_off, k->d_total_tmp, s));
+        }
+        HIP_TRY(launch_merge_table(g, p.sub, p.box, static_cast<const uint32_t*>(d_slice_len), k->d_region_len, static_cast<uint32_t*>(d_slice_len_out), s));
+        HIP_TRY(launch_group_sums(g, static_cast<const uint32_t*>(d_slice_len_out), new_goff, s));
+        HIP_TRY(launch_scan_groups(g, new_goff, static_cast<uint64_t*>(d_total), s));
+        HIP_TRY(launch_splice_slices(g, p.sub, p.box, static_cast<const uint8_t*>(d_payload), payload_bytes, static_cast<const uint32_t*>(d_slice_len),
+                                     k->d_group_off, k->d_scratch, static_cast<const uint32_t*>(d_slice_len_out), new_goff,
+                                     static_cast<uint8_t*>(d_payload_out), payload_cap, status, s));
+    }
+    ++k->n_encode;
+    return LLCOMP_MI_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
 
 uint32_t llcomp_mi_codec_regions_family(const llcomp_mi_codec* k, const uint32_t* xy, uint32_t rw, uint32_t rh, uint32_t* fam, uint32_t cap) {
     if (!k || (cap && !fam)) return 0;

@@ -55,6 +55,12 @@ struct llcomp_mi_codec {
     uint64_t box_cap = 0;
     uint8_t* d_mid = nullptr;
     uint64_t mid_cap = 0;
+    // region update (llcomp_mi_codec_encode_region / _update_region): the encoder runs on the box's sub-geometry, which can have MORE lane
+    // groups than the full one, so its group offsets go to an array of their own, u64[n_slices + 1]; behind it, u64[lane groups + 1], the
+    // full geometry's group offsets for the NEW table (d_group_off holds the old table's).  The decoded box shares d_box with the resized
+    // path.  Allocated by the first such call (or LLCOMP_MI_PREPARE_UPDATE).
+    uint64_t* d_upd_goff = nullptr;
+    uint64_t snap_el = 0;            // elements every snapshot array holds
     void* d_snap_sorted = nullptr;   // snapshot pass of the 2-D encoder (snapshot.hpp): banks in context-sorted order,
     void* d_snap_banks = nullptr;    // banks in stream order, residuals in stream order; null unless snapshot_mode(g)
     void* d_snap_res = nullptr;

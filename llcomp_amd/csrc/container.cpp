@@ -123,6 +123,75 @@ void regions_gather_copy(const RegionsGather& p, const uint8_t* const* data, uin
     }
 }
 
+// llcomp_mi_replace_slices(_into): every check first, then the header, the new table, and the payload as runs of unchanged slices (one
+// memcpy each) with the new slices in between.  out != nullptr: the caller's buffer of out_cap bytes, else malloc'ed -> *out_alloc.
+static int replace_slices_common(const uint8_t* data, size_t len, const uint32_t* box, const uint32_t* new_len, const uint8_t* new_payload,
+                                 uint8_t* out, size_t out_cap, uint8_t** out_alloc, size_t* out_len) {
+    if (!data || !box || !new_len || !new_payload || !out_len || (!out && !out_alloc)) return LLCOMP_MI_BAD_ARGS;
+    llcomp_mi_info a;
+    if (int rc = llcomp_mi_probe(data, len, &a)) return rc;
+    if (a.format != LLCOMP_MI_FORMAT_SLICED) return LLCOMP_MI_BAD_ARGS;
+    Geometry g;
+    if (!make_geometry(g, 1, a.width, a.height, a.channels, a.tile_w, a.tile_h, a.planar, Tuning{}, a.small_model != 0)) return LLCOMP_MI_BAD_ARGS;
+    if (box[0] >= box[2] || box[1] >= box[3] || box[2] > g.ntx || box[3] > g.nty) return LLCOMP_MI_BAD_ARGS;
+    const uint32_t limit = g.slice_cap - 16, planes = g.planar ? g.c : 1u;
+    const uint8_t* tab = data + a.table_offset;
+    const uint64_t old_payload = len - a.payload_offset;
+    auto covered = [&](uint32_t i) {
+        const uint32_t tile = i / planes, ty = tile / g.ntx, tx = tile - ty * g.ntx;
+        return tx >= box[0] && tx < box[2] && ty >= box[1] && ty < box[3];
+    };
+    uint64_t old_off = 0, total = 0;
+    uint32_t j = 0;
+    for (uint32_t i = 0; i < g.slices_per_frame; ++i) {
+        const uint32_t l = get_u32le(tab + 4ull * i);
+        if (covered(i)) {
+            if (new_len[j] > limit) return LLCOMP_MI_TRUNCATED;
+            total += new_len[j++];
+        } else {
+            if (old_off + l > old_payload) return LLCOMP_MI_TRUNCATED;
+            total += l;
+        }
+        old_off += l;  // (a covered slice's old bytes are skipped, never read)
+    }
+    const size_t n = size_t(a.payload_offset + total);
+    *out_len = n;
+    uint8_t* o = out;
+    if (!o) {
+        o = static_cast<uint8_t*>(std::malloc(n + 1));
+        if (!o) return LLCOMP_MI_NOMEM;
+    } else if (n > out_cap) {
+        return LLCOMP_MI_OUTPUT_OVERFLOW;  // *out_len tells the caller what it takes
+    }
+    std::memcpy(o, data, LLCOMP_MI_SLICED_HEADER_BYTES);
+    uint8_t* otab = o + LLCOMP_MI_SLICED_HEADER_BYTES;
+    uint8_t* pay = o + a.payload_offset;
+    const uint8_t* src = data + a.payload_offset;
+    uint64_t run_at = 0, run = 0, new_at = 0;  // the pending run of unchanged slices: old payload bytes [run_at, run_at + run)
+    old_off = 0;
+    j = 0;
+    for (uint32_t i = 0; i < g.slices_per_frame; ++i) {
+        const uint32_t l = get_u32le(tab + 4ull * i);
+        if (covered(i)) {
+            if (run) std::memcpy(pay, src + run_at, run);
+            pay += run;
+            run = 0;
+            put_u32le(otab + 4ull * i, new_len[j]);
+            if (new_len[j]) std::memcpy(pay, new_payload + new_at, new_len[j]);
+            pay += new_len[j];
+            new_at += new_len[j++];
+        } else {
+            if (!run) run_at = old_off;
+            run += l;
+            put_u32le(otab + 4ull * i, l);
+        }
+        old_off += l;
+    }
+    if (run) std::memcpy(pay, src + run_at, run);
+    if (out_alloc) *out_alloc = o;
+    return LLCOMP_MI_OK;
+}
+
 }  // namespace llcomp_mi
 
 using namespace llcomp_mi;
@@ -276,6 +345,23 @@ int llcomp_mi_regions_gather(const uint8_t* const* data, const size_t* lens, uin
     if (payload_cap < p.payload_bytes || len_cap < p.n_slices) return LLCOMP_MI_OUTPUT_OVERFLOW;
     regions_gather_copy(p, data, payload, slice_len, nullptr);
     return LLCOMP_MI_OK;
+}
+
+int llcomp_mi_replace_slices(const uint8_t* data, size_t len, const uint32_t box[4], const uint32_t* new_len, const uint8_t* new_payload,
+                             uint8_t** out, size_t* out_len) {
+    if (!out || !out_len) return LLCOMP_MI_BAD_ARGS;
+    uint8_t* o = nullptr;
+    size_t n = 0;
+    if (int rc = replace_slices_common(data, len, box, new_len, new_payload, nullptr, 0, &o, &n)) return rc;
+    *out = o;
+    *out_len = n;
+    return LLCOMP_MI_OK;
+}
+
+int llcomp_mi_replace_slices_into(const uint8_t* data, size_t len, const uint32_t box[4], const uint32_t* new_len, const uint8_t* new_payload,
+                                  uint8_t* out, size_t out_cap, size_t* out_len) {
+    if (!out || !out_len) return LLCOMP_MI_BAD_ARGS;
+    return replace_slices_common(data, len, box, new_len, new_payload, out, out_cap, nullptr, out_len);
 }
 
 int llcomp_mi_probe(const uint8_t* data, size_t len, llcomp_mi_info* info) {

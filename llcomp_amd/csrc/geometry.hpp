@@ -267,6 +267,56 @@ inline bool sub_arrays_fit(const Geometry& full, const Geometry& sub) {
 }
 inline bool region_fits(const Geometry& full, const Geometry& sub) { return sub.frames == full.frames && sub_arrays_fit(full, sub); }
 
+// ---- region update (DESIGN.md "Region update"): the ENCODER on the covered box's sub-geometry ---------------------------------------
+// region_full_id the other way round: the sub-slice that full slice `id` is, or ~0u for a slice outside the box
+LLMI_HD inline uint32_t region_sub_id(const Geometry& full, const Geometry& sub, const RegionBox& b, uint32_t id) {
+    const uint32_t f = id / full.slices_per_frame, s = id - f * full.slices_per_frame;
+    const uint32_t planes = full.planar ? full.c : 1u;
+    const uint32_t tile = s / planes, ch = s - tile * planes;
+    const uint32_t ty = tile / full.ntx, tx = tile - ty * full.ntx;
+    if (tx < b.tx0 || tx >= b.tx1 || ty < b.ty0 || ty >= b.ty1) return ~0u;
+    return f * sub.slices_per_frame + ((ty - b.ty0) * sub.ntx + tx - b.tx0) * planes + ch;
+}
+// is the rectangle exactly the box's pixels (tile-aligned, or reaching the image edge)?  Then nothing of the old box is needed.
+inline bool region_is_whole_box(const Geometry& full, const Geometry& sub, const RegionBox& b, uint32_t x, uint32_t y, uint32_t rw, uint32_t rh) {
+    return x == b.tx0 * full.tile_w && y == b.ty0 * full.tile_h && rw == sub.w && rh == sub.h;
+}
+// elements per snapshot array of `g` (snapshot_kernels.hip: snapshot_elems), 0 for a family without the pass
+inline uint64_t snapshot_elems_of(const Geometry& g) {
+    if (!(g.flags & kGeoSnapshot)) return 0;
+    return (((uint64_t(g.n_slices) + (1u << g.lane_shift) - 1) >> g.lane_shift) * snapshot_cap(g)) << g.lane_shift;
+}
+// The most elements the snapshot arrays of a sub-geometry of `full` can take (what the codec counts in its workspace): the codec's own
+// arrays when it runs the pass itself; else a sub-image of clamped tiles, or of more slices per wavefront, may run it where the codec's
+// family does not (tables in LDS, or slices above 16384 samples) -- at most the full geometry's lanes x the full slice's capacity in the
+// arrays, 16384 samples at the most.  None for 1-row slices (they stay 1-row slices) and where LLCOMP_MI_NOSNAP took the pass away.
+inline uint64_t region_snapshot_bound(const Geometry& full) {
+    if (full.flags & kGeoSnapshot) return snapshot_elems_of(full);
+    if (full.flags & kGeoRows) return 0;
+    if (!(full.flags & kGeoLdsTable) && full.slice_samples <= kSnapMaxSamples * kSnapMaxChunks) return 0;
+    const uint64_t lanes = ((uint64_t(full.n_slices) + (1u << full.lane_shift) - 1) >> full.lane_shift) << full.lane_shift;
+    const uint64_t cap = full.slice_samples <= kSnapMaxSamples ? (full.slice_samples + 15u) & ~15u
+                                                               : uint64_t(std::min(snapshot_chunks(full), kSnapMaxChunks)) * kSnapMaxSamples;
+    return lanes * cap;
+}
+// Does every array the ENCODER touches for `sub` fit what the codec sized for `full`?  What the decoder touches (sub_arrays_fit) and:
+//   * the lane-order array, which is also the snapshot pass's entries (u32 per element): bytes, not samples -- a fused codec holds 16-bit
+//     symbols, and the pass's capacity per slice is rounded up (to 16 samples, or to whole chunks of 4096);
+//   * the snapshot arrays, against region_snapshot_bound;
+//   * the coder's parking records (64 B per slice) and the group offsets: the sub-geometry can have MORE lane groups than the full one
+//     (a narrower lane group for fewer slices), so the encoder's offsets go to an array of n_slices + 1 entries of its own, which
+//     always holds them: lane groups <= slices of the sub-geometry <= slices of the full one.
+inline bool region_encode_fits(const Geometry& full, const Geometry& sub) {
+    if (!region_fits(full, sub)) return false;
+    auto lanes = [](const Geometry& g) { return ((uint64_t(g.n_slices) + (1u << g.lane_shift) - 1) >> g.lane_shift) << g.lane_shift; };
+    auto fused = [](const Geometry& g) { return g.planar && (g.flags & kGeoRows) && g.c <= 4; };
+    auto lane_bytes = [&](const Geometry& g) { return std::max(lanes(g) * g.slice_samples * (fused(g) ? 2u : 4u), snapshot_elems_of(g) * 4); };
+    if (lane_bytes(sub) > lane_bytes(full)) return false;
+    if (snapshot_elems_of(sub) > region_snapshot_bound(full)) return false;
+    if (lanes(sub) >> sub.lane_shift > uint64_t(full.n_slices)) return false;
+    return true;
+}
+
 // ---- regions decode: a rectangle of one size at an offset of its own in every frame (DESIGN.md "Region decode") -----------------
 // To run the decoder on ONE sub-geometry, every frame decodes a WINDOW of tiles of a fixed size instead of its exact covered box:
 // Wx = min(ntx, (rw + tile_w - 2) / tile_w + 1) tile columns, the most a rectangle of width rw can touch, from

@@ -398,6 +398,115 @@ int decode_region_common(const uint8_t* data, size_t len, int32_t device, uint32
     return LLCOMP_MI_OK;
 }
 
+// Region update (llcomp_mi_update_region): the lane of the container's full shape.  Up: header + slice table, the rectangle's pixels
+// and -- only when the rectangle is not exactly its box's pixels, so that the box has to be decoded -- the payload span of the covered
+// slices, at its own offset in the lane's container buffer as for a region decode.  llcomp_mi_codec_encode_region codes the box; down come
+// {bytes, status}, then the covered slices' new lengths and streams in one copy; llcomp_mi_replace_slices assembles the container here.
+// Nothing else of the container crosses PCIe in either direction.
+int update_region_common(const uint8_t* data, size_t len, int32_t device, uint32_t flags, uint32_t x, uint32_t y, uint32_t rw, uint32_t rh,
+                         const uint8_t* px, uint8_t* out, size_t out_cap, uint8_t** out_alloc, size_t* out_len) {
+    if (flags & ~LLCOMP_MI_FLAG_SMALL_MODEL) return LLCOMP_MI_BAD_ARGS;
+    llcomp_mi_info info;
+    if (int rc = llcomp_mi_probe(data, len, &info)) return rc;
+    const bool legacy = info.format == LLCOMP_MI_FORMAT_LEGACY;
+    if (int rc = check_shape(info.width, info.height, info.channels, legacy)) return rc;
+    uint32_t box[4], covered = 0;
+    if (int rc = llcomp_mi_region_plan(info.width, info.height, info.channels, info.tile_w, info.tile_h, info.planar, x, y, rw, rh, box, &covered))
+        return rc;
+    if (legacy) len = size_t(std::min<uint64_t>(len, info.payload_offset + legacy_read_bound(uint64_t(info.width) * info.height * info.channels)));
+    LaneLease lease;
+    if (int rc = lane_acquire(&lease.l, device, info.width, info.height, info.channels, info.tile_w, info.tile_h, info.planar, legacy,
+                              len - info.payload_offset + 16, legacy ? (flags & LLCOMP_MI_FLAG_SMALL_MODEL) != 0 : info.small_model != 0,
+                              legacy ? len - info.payload_offset : 0))
+        return rc;
+    HostLane* l = lease.l;
+    DeviceGuard guard(l->k->device);
+    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
+    const Geometry& g = l->k->g;
+    RegionBox b{box[0], box[1], box[2], box[3]};
+    Geometry sub;
+    if (!region_geometry(g, b, l->k->tune, sub)) return LLCOMP_MI_HIP_ERROR;
+    const bool whole = region_is_whole_box(g, sub, b, x, y, rw, rh);
+    const uint64_t payload = len - l->head_bytes, rect_bytes = uint64_t(rw) * rh * info.channels;
+    if (!whole) {
+        // the covered slices' bytes: from the first covered slice's first byte to the last one's end (decode_region_common)
+        uint64_t begin = 0, end = payload;
+        if (!legacy) {
+            const uint32_t planes = info.planar ? info.channels : 1u;
+            const uint64_t first = (uint64_t(box[1]) * g.ntx + box[0]) * planes, last = ((uint64_t(box[3]) - 1) * g.ntx + box[2] - 1) * planes + planes - 1;
+            const uint8_t* table = data + info.table_offset;
+            uint64_t pos = 0;
+            for (uint64_t i = 0; i <= last; ++i) {
+                if (i == first) begin = pos;
+                pos += get_u32le(table + 4 * i);
+            }
+            begin = std::min(begin, payload);
+            end = std::min(pos, payload);
+        }
+        LLMI_HIP_TRY(copy_user(l->d_container, data, l->head_bytes, hipMemcpyHostToDevice, l->stream));
+        LLMI_HIP_TRY(copy_user(l->d_payload() + begin, data + l->head_bytes + begin, end - begin, hipMemcpyHostToDevice, l->stream));
+        if (legacy) {
+            const uint32_t one = uint32_t(std::min<uint64_t>(payload, 0xFFFFFFFFull));
+            LLMI_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(l->d_len_legacy), int(one), 1, l->stream));
+        }
+    }
+    // the rectangle rides in the lane's frame buffer (rw * rh <= w * h); the new slices come back through a block of their own:
+    // [u32 lengths][streams], first with room for twice the box's raw bytes, then for the proven worst case
+    LLMI_HIP_TRY(copy_user(l->d_px, px, rect_bytes, hipMemcpyHostToDevice, l->stream));
+    const uint64_t table_bytes = (4ull * covered + 15) & ~15ull, max_sub = uint64_t(covered) * g.slice_cap;
+    uint64_t cap = std::min<uint64_t>(2 * uint64_t(sub.w) * sub.h * sub.c + 64ull * covered + 4096, max_sub);
+    struct Block {
+        uint8_t* p = nullptr;
+        ~Block() { dev_free(p); }  // (the lane's stream has been drained on every path that gets here with p set)
+    } blk;
+    std::vector<uint8_t> host;
+    int rc = LLCOMP_MI_OK;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        if (dev_alloc(reinterpret_cast<void**>(&blk.p), table_bytes + cap + 16) != hipSuccess) { blk.p = nullptr; return LLCOMP_MI_NOMEM; }
+        rc = llcomp_mi_codec_encode_region(l->k, whole ? nullptr : l->d_payload(), payload, whole ? nullptr : l->d_len(), x, y, rw, rh, l->d_px,
+                                           blk.p + table_bytes, cap, blk.p, l->d_meta, l->d_meta + 1, l->stream);
+        if (rc) {
+            (void)hipStreamSynchronize(l->stream);
+            return rc;
+        }
+        if (hipMemcpyAsync(l->h_meta, l->d_meta, 16, hipMemcpyDeviceToHost, l->stream) != hipSuccess || hipStreamSynchronize(l->stream) != hipSuccess) {
+            (void)hipStreamSynchronize(l->stream);
+            return LLCOMP_MI_HIP_ERROR;
+        }
+        rc = status_from_bits(uint32_t(l->h_meta[1]));
+        if (rc == LLCOMP_MI_OUTPUT_OVERFLOW && cap < max_sub) {
+            dev_free(blk.p);
+            blk.p = nullptr;
+            cap = max_sub;
+            continue;
+        }
+        break;
+    }
+    if (rc) return rc;
+    const uint64_t sub_bytes = l->h_meta[0];
+    host.resize(size_t(table_bytes + sub_bytes));
+    LLMI_HIP_TRY(copy_user(host.data(), blk.p, host.size(), hipMemcpyDeviceToHost, l->stream));
+    const uint32_t* new_len = reinterpret_cast<const uint32_t*>(host.data());  // (little-endian hosts, as the table on the wire)
+    if (!legacy) {
+        if (out) return llcomp_mi_replace_slices_into(data, len, box, new_len, host.data() + table_bytes, out, out_cap, out_len);
+        return llcomp_mi_replace_slices(data, len, box, new_len, host.data() + table_bytes, out_alloc, out_len);
+    }
+    // a LEGACY stream: the 6-byte header and the one new stream
+    const size_t n = 6 + size_t(sub_bytes);
+    *out_len = n;
+    uint8_t* dst = out;
+    if (!dst) {
+        dst = static_cast<uint8_t*>(std::malloc(n + 1));
+        if (!dst) return LLCOMP_MI_NOMEM;
+    } else if (n > out_cap) {
+        return LLCOMP_MI_OUTPUT_OVERFLOW;
+    }
+    std::memcpy(dst, data, 6);
+    std::memcpy(dst + 6, host.data() + table_bytes, size_t(sub_bytes));
+    if (out_alloc) *out_alloc = dst;
+    return LLCOMP_MI_OK;
+}
+
 // decode over a device list: sliced containers whose table fits their payload are dealt over the devices (multidev.hip); a legacy
 // stream, a list of one device and damaged containers (the one-device path forms their verdict) go to devices[0]
 int decode_devices_common(const uint8_t* data, size_t len, const DeviceList& dl, uint32_t flags, uint8_t* px, size_t px_cap, uint8_t** px_alloc,
@@ -482,6 +591,23 @@ int llcomp_mi_decode_region_into(const uint8_t* data, size_t len, int32_t device
                                  uint32_t rh, uint8_t* px, size_t px_cap, uint32_t* c) {
     if (!data || !px || !c) return LLCOMP_MI_BAD_ARGS;
     return decode_region_common(data, len, device, flags, x, y, rw, rh, px, px_cap, nullptr, c);
+}
+
+int llcomp_mi_update_region(const uint8_t* data, size_t len, int32_t device, uint32_t flags, uint32_t x, uint32_t y, uint32_t rw, uint32_t rh,
+                            const uint8_t* px, uint8_t** out, size_t* out_len) {
+    if (!data || !px || !out || !out_len) return LLCOMP_MI_BAD_ARGS;
+    uint8_t* o = nullptr;
+    size_t n = 0;
+    if (int rc = update_region_common(data, len, device, flags, x, y, rw, rh, px, nullptr, 0, &o, &n)) return rc;
+    *out = o;
+    *out_len = n;
+    return LLCOMP_MI_OK;
+}
+
+int llcomp_mi_update_region_into(const uint8_t* data, size_t len, int32_t device, uint32_t flags, uint32_t x, uint32_t y, uint32_t rw,
+                                 uint32_t rh, const uint8_t* px, uint8_t* out, size_t out_cap, size_t* out_len) {
+    if (!data || !px || !out || !out_len) return LLCOMP_MI_BAD_ARGS;
+    return update_region_common(data, len, device, flags, x, y, rw, rh, px, out, out_cap, nullptr, out_len);
 }
 
 void llcomp_mi_trim(void) {
