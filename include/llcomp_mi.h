@@ -30,6 +30,7 @@ extern "C" {
  * per frame -- llcomp_mi_regions_plan, llcomp_mi_codec_decode_regions, llcomp_mi_codec_regions_family, LLCOMP_MI_PREPARE_REGIONS; crops
  * of host containers -- llcomp_mi_regions_gather, llcomp_mi_codec_decode_regions_host, llcomp_mi_stream_submit_decode_regions,
  * LLCOMP_MI_JOB_DECODE_REGIONS, LLCOMP_MI_CTR_HOST_STAGED_BYTES; crops of different sizes resized to one shape -- llcomp_mi_resize_weights,
+ * llcomp_mi_resize_filter_weights (PIL's filters, one per frame through bits 4-6 of the flags),
  * llcomp_mi_resized_regions_plan, llcomp_mi_codec_decode_resized_regions(_host), llcomp_mi_stream_submit_decode_resized_regions,
  * LLCOMP_MI_PREPARE_RESIZED, LLCOMP_MI_JOB_DECODE_RESIZED_REGIONS, llcomp_mi_codec_allocated_bytes; their output as a model takes it,
  * float or normalised, CHW or HWC -- llcomp_mi_output_format, llcomp_mi_output_table and the _ex forms of the three resized calls; region
@@ -243,16 +244,43 @@ int llcomp_mi_replace_slices(const uint8_t* data, size_t len, const uint32_t box
                              uint8_t** out, size_t* out_len);
 int llcomp_mi_replace_slices_into(const uint8_t* data, size_t len, const uint32_t box[4], const uint32_t* new_len, const uint8_t* new_payload,
                                   uint8_t* out, size_t out_cap, size_t* out_len);
-/* The resampling rule of llcomp_mi_codec_decode_resized_regions for one axis, in_len -> out_len: the triangle ("bilinear") filter with
- * antialiasing of PIL and of torch's interpolate(mode="bilinear", align_corners=False, antialias=True), in integers:
- *   scale = in_len / out_len, support = max(scale, 1); output i: center = (i + 0.5) * scale,
+/* The resampling rule of llcomp_mi_codec_decode_resized_regions for one axis, in_len -> out_len, under one of PIL's filters: the rule of
+ * PIL's 8-bit resampler (Image.resize of a crop), in integers.  With the filter's kernel function f and radius S:
+ *   scale = in_len / out_len, fs = max(scale, 1), support = S * fs, ss = 1 / fs (double); output i: center = (i + 0.5) * scale,
  *   lo = max(int(center - support + 0.5), 0), hi = min(int(center + support + 0.5), in_len),
- *   w_j = max(0, 1 - |(lo + j - center + 0.5) / support|) for j in [0, hi - lo), normalised to sum 1 (double),
- *   q_j = floor(0.5 + w_j * 2^22) (Q22);  out = clamp((sum_j q_j * in[lo + j] + 2^21) >> 22, 0, 255).
- * A frame is resampled horizontally first, rounded to u8, then vertically.  in_len == out_len is the identity (one weight 2^22 at
- * lo = i).  Returns K, the taps per output (trailing taps that are 0 for every output are left out; K <= 129), and, when lo / q are not
- * NULL, fills lo[out_len] and q[out_len][K] (zero-padded).  0 for in_len or out_len 0 or a downscale above 64x (in_len > 64 * out_len).
- * Host-only; the GPU runs exactly these weights. */
+ *   w_j = f((lo + j - center + 0.5) * ss) for j in [0, hi - lo), divided by their sum when it is not 0,
+ *   q_j = int(w_j * 2^22 + 0.5) for w_j >= 0, int(w_j * 2^22 - 0.5) for w_j < 0, both truncating toward zero (Q22);
+ *   out = clamp((sum_j q_j * in[lo + j] + 2^21) >> 22, 0, 255).
+ * A frame is resampled horizontally first, rounded to u8, then vertically.  The filters:
+ *   BILINEAR  S = 1    f(x) = max(0, 1 - |x|)  (the triangle; also torch's interpolate(mode="bilinear", antialias=True))
+ *   BOX       S = 0.5  f(x) = 1 for -0.5 < x <= 0.5, else 0
+ *   HAMMING   S = 1    f(0) = 1, f(x) = 0 for |x| >= 1, else sin(pi x) / (pi x) * (0.54 + 0.46 * cos(pi x))
+ *   BICUBIC   S = 2    a = -0.5: ((a + 2)|x| - (a + 3)) x^2 + 1 for |x| < 1, (((|x| - 5)|x| + 8)|x| - 4) a for |x| < 2, else 0
+ *   LANCZOS   S = 3    sinc(x) * sinc(x / 3) for -3 <= x < 3, else 0; sinc(0) = 1, sinc(x) = sin(pi x) / (pi x)
+ *   NEAREST   one tap of 2^22 at lo_i = ((2 i + 1) * in_len) div (2 * out_len), in exact integers (K = 1): floor((i + 0.5) * in / out)
+ *             without rounding error, torch's "nearest-exact" -- the filter for label images, it invents no value
+ * in_len == out_len is the identity for every filter (one weight 2^22 at lo <= i).  Only BICUBIC and LANCZOS have negative weights; the
+ * sum of |q_j| * 255 stays below 2^31.  Returns K, the taps per output (trailing taps that are 0 for every output are left out; K <= 129),
+ * and, when lo / q are not NULL, fills lo[out_len] and q[out_len][K] (zero-padded).  0 for in_len or out_len 0, an unknown filter, or a
+ * downscale above the filter's limit: R * in_len > 64 * out_len with R = 1 (64x), but 2 for BICUBIC (32x) and 3 for LANCZOS (21.33x).
+ * Host-only; the GPU runs exactly these weights.  llcomp_mi_resize_weights is filter 0, BILINEAR. */
+enum {
+    LLCOMP_MI_FILTER_BILINEAR = 0,
+    LLCOMP_MI_FILTER_NEAREST = 1,
+    LLCOMP_MI_FILTER_BOX = 2,
+    LLCOMP_MI_FILTER_HAMMING = 3,
+    LLCOMP_MI_FILTER_BICUBIC = 4,
+    LLCOMP_MI_FILTER_LANCZOS = 5
+};
+uint32_t llcomp_mi_resize_filter_weights(uint32_t filter, uint32_t in_len, uint32_t out_len, uint32_t* lo, int32_t* q);
+/* The per-frame flags byte of the resized calls: bit 0 mirrors the frame's output horizontally, bits 4-6 hold the frame's filter code
+ * (0 = BILINEAR, so a flags byte of 0 or 1 and a NULL flags mean what they always meant; codes 6 and 7 are BAD_ARGS); bits 1-3 and 7 are
+ * ignored. */
+#define LLCOMP_MI_FLAG_MIRROR 1u
+#define LLCOMP_MI_FLAG_FILTER_SHIFT 4
+#define LLCOMP_MI_FLAG_FILTER_MASK 0x70u
+#define LLCOMP_MI_FLAG_FILTER(code) (((code) << LLCOMP_MI_FLAG_FILTER_SHIFT) & LLCOMP_MI_FLAG_FILTER_MASK)
+#define LLCOMP_MI_FLAG_FILTER_OF(flags) (((flags) & LLCOMP_MI_FLAG_FILTER_MASK) >> LLCOMP_MI_FLAG_FILTER_SHIFT)
 uint32_t llcomp_mi_resize_weights(uint32_t in_len, uint32_t out_len, uint32_t* lo, int32_t* q);
 /* The windows of a rectangle of its own size per frame: rects = {x_0, y_0, rw_0, rh_0, x_1, ...} (4 * n).  The rule of
  * llcomp_mi_regions_plan, sized by the batch's LARGEST rectangle: Wx from max_f rw_f, wx0_f = min(x_f / tile_w, ntx - Wx), the same in
@@ -430,14 +458,16 @@ int llcomp_mi_codec_decode_regions_host(llcomp_mi_codec* codec, const uint8_t* c
                                         uint32_t rh, void* d_px, void* d_status, void* stream);
 /* Regions decode with a rectangle of its own size per frame, every rectangle resampled to one output shape (torchvision's
  * RandomResizedCrop, and RandomHorizontalFlip through flags): rects = {x, y, rw, rh} per frame (4 * frames, HOST memory), flags = one
- * byte per frame (HOST memory, NULL = none; bit 0 mirrors the frame's output horizontally after resampling) -> d_px [frames][oh][ow][c],
- * dense: byte for byte the rule of llcomp_mi_resize_weights applied to full_decode[f, y_f : y_f + rh_f, x_f : x_f + rw_f].  rects and
+ * byte per frame (HOST memory, NULL = none; bit 0 mirrors the frame's output horizontally after resampling, bits 4-6 choose the frame's
+ * filter, LLCOMP_MI_FLAG_FILTER(LLCOMP_MI_FILTER_*): a batch may mix filters, e.g. pictures and their label images) -> d_px
+ * [frames][oh][ow][c], dense: byte for byte the rule of llcomp_mi_resize_filter_weights applied to full_decode[f, y_f : y_f + rh_f, x_f : x_f + rw_f].  rects and
  * flags are read during the call only.  Every frame decodes a window of tiles sized for the batch's largest rectangle
  * (llcomp_mi_resized_regions_plan): a frame with a small rectangle decodes as much as one with the largest.  The classes run as in
  * llcomp_mi_codec_decode_regions and crop every frame's BOX (the largest rectangle's size, containing the frame's rectangle) into a buffer
  * of the codec; two resample kernels then write d_px.  Asynchronous on `stream`; verdicts as for llcomp_mi_codec_decode_regions (from the
  * decoded windows' slices).  BAD_ARGS, before anything is launched or written: a NULL pointer, ow or oh 0, a rectangle empty or outside the
- * image, or a downscale above 64x on either axis (rw_f > 64 * ow or rh_f > 64 * oh).  Profile slots as for a regions decode; the resample
+ * image, a filter code of 6 or 7, or a downscale above the frame's filter's limit on either axis (R * rw_f > 64 * ow or R * rh_f > 64 * oh;
+ * R = 1, BICUBIC 2, LANCZOS 3).  Profile slots as for a regions decode; the resample
  * is timed in slot 6 with the crops.  The boxes (frames * rw_max * rh_max * c bytes) and the horizontal pass's rows (frames * rh_max * ow *
  * c) are buffers of the codec that grow geometrically, never per call, and never past frames * w * h * c each but where a call needs
  * more (LLCOMP_MI_PREPARE_RESIZED allocates both at that size).  llcomp_mi_codec_workspace_bytes counts both at that size and the tables

@@ -12,7 +12,8 @@ with ctypes and keeps the reference's names and error behaviour:
     regions_plan(w, h, c, tw, th, planar, rw, rh, xy) / Codec.decode_regions  (a rectangle per frame of a batch; pack_batch feeds it)
     regions_gather / Codec.decode_regions_host / Stream.submit_decode_regions  (the same from host containers: only the windows cross)
     resize_weights / resized_regions_plan / Codec.decode_resized_regions(_host) / Stream.submit_decode_resized_regions  (a rectangle of
-        its own size per frame, resampled to one output shape with an optional mirror: RandomResizedCrop + RandomHorizontalFlip)
+        its own size per frame, resampled to one output shape with an optional mirror: RandomResizedCrop + RandomHorizontalFlip;
+        filter= chooses PIL's bilinear, box, hamming, bicubic or lanczos, or nearest for label images, for the call or per frame)
     output_table / dtype=, layout=, scale=, mean=, std= of the three resized calls  (their output as a model takes it: float32, float16
         or bfloat16, CHW or HWC, ToTensor() + Normalize(mean, std) -- the _ex calls and llcomp_mi_output_format)
     RawImage(pixels, width, height, channels)     <->  llcomp::RawImage         (/root/reference/llcomp.hpp:454-459)
@@ -35,6 +36,10 @@ FORMAT_LEGACY, FORMAT_SLICED = 0, 1
 JOB_ENCODE, JOB_DECODE, JOB_DECODE_REGIONS, JOB_DECODE_RESIZED_REGIONS = 0, 1, 2, 3
 DTYPE_U8, DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2, 3
 LAYOUT_HWC, LAYOUT_CHW = 0, 1
+# the resampling filters of the resized calls (LLCOMP_MI_FILTER_*): PIL's, and NEAREST for label images
+FILTER_BILINEAR, FILTER_NEAREST, FILTER_BOX, FILTER_HAMMING, FILTER_BICUBIC, FILTER_LANCZOS = range(6)
+FILTER_NAMES = ("bilinear", "nearest", "box", "hamming", "bicubic", "lanczos")
+FLAG_MIRROR, FLAG_FILTER_SHIFT = 1, 4
 
 RawImage = namedtuple("RawImage", "pixels width height channels")
 
@@ -164,14 +169,30 @@ def _rects_table(rects, n=None):
     return (C.c_uint32 * flat.size)(*flat.tolist()), a.shape[0]
 
 
-def _flags_table(flags, n):
-    """None, or n per-frame flags (bit 0: mirror horizontally) -> (ctypes u8 array or None)"""
-    if flags is None:
+def filter_code(filter):
+    """FILTER_* of a code (0..5) or a name ("bilinear", "nearest", "box", "hamming", "bicubic", "lanczos"); BAD_ARGS for anything else"""
+    if isinstance(filter, str) and filter.lower() in FILTER_NAMES:
+        return FILTER_NAMES.index(filter.lower())
+    if isinstance(filter, (int, np.integer)) and not isinstance(filter, bool) and 0 <= int(filter) < len(FILTER_NAMES):
+        return int(filter)
+    raise LlcompError(BAD_ARGS, f"filter must be one of {FILTER_NAMES} or its code 0..{len(FILTER_NAMES) - 1}, got {filter!r}")
+
+
+def _flags_table(flags, n, filter=None):
+    """None, or n per-frame flags (bit 0: mirror horizontally, bits 4-6: the frame's filter) -> (ctypes u8 array or None).  filter: one
+    code or name for every frame, or a sequence of n; it is OR-ed into bits 4-6."""
+    if flags is None and filter is None:
         return None
-    a = np.asarray(flags)
+    a = np.zeros(n, np.int64) if flags is None else np.asarray(flags)
     if a.shape != (n,) or (a.size and (a.min() < 0 or a.max() > 255)):
         raise LlcompError(BAD_ARGS, f"flags must be {n} values in 0..255, got shape {a.shape}")
-    return (C.c_uint8 * n)(*[int(v) for v in a.tolist()])
+    vals = [int(v) for v in a.tolist()]
+    if filter is not None:
+        per_frame = [filter] * n if isinstance(filter, (str, int, np.integer)) else list(filter)
+        if len(per_frame) != n:
+            raise LlcompError(BAD_ARGS, f"filter must be one filter or {n} of them, got {len(per_frame)}")
+        vals = [v | (filter_code(f) << FLAG_FILTER_SHIFT) for v, f in zip(vals, per_frame)]
+    return (C.c_uint8 * n)(*vals)
 
 
 _DTYPES = {"uint8": DTYPE_U8, "u8": DTYPE_U8, "float32": DTYPE_F32, "float": DTYPE_F32, "f32": DTYPE_F32, "float16": DTYPE_F16,
@@ -236,15 +257,22 @@ def output_table(c, dtype, scale=False, mean=None, std=None):
     return out
 
 
-def resize_weights(in_len, out_len):
-    """(lo np.uint32[out_len], q np.int32[out_len, K]) of the resampling rule of one axis (llcomp_mi_resize_weights, host only): the
-    triangle filter with antialiasing in Q22, exactly what the GPU runs.  LlcompError(BAD_ARGS) for a side of 0 or a downscale above 64x."""
+def resize_weights(in_len, out_len, filter=0):
+    """(lo np.uint32[out_len], q np.int32[out_len, K]) of the resampling rule of one axis under `filter` (a FILTER_* code or its name;
+    llcomp_mi_resize_filter_weights, host only): PIL's filter in Q22, exactly what the GPU runs.  LlcompError(BAD_ARGS) for a side of
+    0, an unknown filter, or a downscale above the filter's limit (64x; bicubic 32x; Lanczos 64/3)."""
     L = _lib.load()
-    k = L.llcomp_mi_resize_weights(in_len, out_len, None, None)
-    if not k:
+    if isinstance(filter, (int, np.integer)) and not isinstance(filter, bool) and 0 <= int(filter) <= 0xFFFFFFFF:
+        code = int(filter)  # (an unknown code is the library's to refuse)
+    else:
+        code = filter_code(filter)
+    if not (0 <= int(in_len) <= 0xFFFFFFFF and 0 <= int(out_len) <= 0xFFFFFFFF):
         raise LlcompError(BAD_ARGS, f"no resampling {in_len} -> {out_len}")
+    k = L.llcomp_mi_resize_filter_weights(code, in_len, out_len, None, None)
+    if not k:
+        raise LlcompError(BAD_ARGS, f"no resampling {in_len} -> {out_len} with filter {filter!r}")
     lo, q = np.zeros(out_len, np.uint32), np.zeros((out_len, k), np.int32)
-    L.llcomp_mi_resize_weights(in_len, out_len, lo.ctypes.data, q.ctypes.data)
+    L.llcomp_mi_resize_filter_weights(code, in_len, out_len, lo.ctypes.data, q.ctypes.data)
     return lo, q
 
 
@@ -581,8 +609,9 @@ class Stream:
         return self._submit(rc, (rh, rw, self.shape[2]))
 
     def submit_decode_resized_regions(self, containers, rects, ow, oh, flags=None, tag=0, dtype=None, layout="hwc", scale=False, mean=None,
-                                      std=None):
-        """frames_per_job containers, their rectangles rects ([frames_per_job, 4] of (x, y, rw, rh)) and optional mirror flags -> a job
+                                      std=None, filter=None):
+        """frames_per_job containers, their rectangles rects ([frames_per_job, 4] of (x, y, rw, rh)), optional mirror flags and the
+        filter (one for the job or one per frame, as Codec.decode_resized_regions takes it) -> a job
         whose .data is the output [oh,ow,c] (one frame per job) / [F,oh,ow,c] -- [c,oh,ow] / [F,c,oh,ow] for layout="chw" -- in
         `dtype` (output_table: bfloat16 as uint16 bits), normalised by scale / mean / std.  The containers are read during this call
         only."""
@@ -590,7 +619,7 @@ class Stream:
         if len(keep) != self.frames_per_job:
             raise LlcompError(BAD_ARGS, f"a job takes {self.frames_per_job} containers, got {len(keep)}")
         tab, _ = _rects_table(rects, self.frames_per_job)
-        fl = _flags_table(flags, self.frames_per_job)
+        fl = _flags_table(flags, self.frames_per_job, filter)
         c = self.shape[2]
         fmt, np_t, _keep = _output_format(c, dtype, layout, scale, mean, std)
         if fmt is None:
@@ -864,14 +893,16 @@ class Codec:
         _check(self._L.llcomp_mi_codec_decode_regions_host(self._h, ptrs, lens, tab, rw, rh, d_px, d_status, stream))
 
     def decode_resized_regions(self, d_payload, payload_bytes, d_slice_len, rects, ow, oh, d_px, d_status, flags=None, stream=0, dtype=None,
-                               layout="hwc", scale=False, mean=None, std=None):
+                               layout="hwc", scale=False, mean=None, std=None, filter=None):
         """frame f's rectangle rects[f] = (x, y, rw, rh), resampled to ow x oh (and mirrored where flags[f] & 1) -> d_px
-        [frames][oh][ow][c] (llcomp_mi_codec_decode_resized_regions); rects and flags are read during the call.  dtype ("float32",
+        [frames][oh][ow][c] (llcomp_mi_codec_decode_resized_regions); rects and flags are read during the call.  filter: PIL's
+        "bilinear" (the default), "box", "hamming", "bicubic", "lanczos", or "nearest" for label images -- a name or FILTER_* code for
+        every frame, or a sequence of one per frame (a batch may mix them); it is OR-ed into bits 4-6 of the flags.  dtype ("float32",
         "float16", "bfloat16", "uint8" or the numpy / torch type), layout ("hwc" or "chw": [frames][c][oh][ow]), scale (divide by 255)
         and mean / std (c values) give the output as a model takes it (llcomp_mi_codec_decode_resized_regions_ex; output_table
         states the rule); d_px must be aligned to the element size."""
         tab, _ = _rects_table(rects, self.frames)
-        fl = _flags_table(flags, self.frames)
+        fl = _flags_table(flags, self.frames, filter)
         fmt, _, _keep = _output_format(self.c, dtype, layout, scale, mean, std)
         if fmt is None:
             _check(self._L.llcomp_mi_codec_decode_resized_regions(self._h, d_payload, payload_bytes, d_slice_len, tab, fl, ow, oh, d_px, d_status,
@@ -881,14 +912,14 @@ class Codec:
                                                                       d_px, d_status, stream))
 
     def decode_resized_regions_host(self, containers, rects, ow, oh, d_px, d_status, flags=None, stream=0, dtype=None, layout="hwc", scale=False,
-                                    mean=None, std=None):
+                                    mean=None, std=None, filter=None):
         """decode_resized_regions of host containers (llcomp_mi_codec_decode_resized_regions_host(_ex)): only the windows' bytes cross
-        PCIe; the containers, rects and flags are read during the call only"""
+        PCIe; the containers, rects and flags are read during the call only; filter as decode_resized_regions takes it"""
         ptrs, lens, keep = _containers(containers)
         if len(keep) != self.frames:
             raise LlcompError(BAD_ARGS, f"the codec takes {self.frames} containers, got {len(keep)}")
         tab, _ = _rects_table(rects, self.frames)
-        fl = _flags_table(flags, self.frames)
+        fl = _flags_table(flags, self.frames, filter)
         fmt, _, _keep = _output_format(self.c, dtype, layout, scale, mean, std)
         if fmt is None:
             _check(self._L.llcomp_mi_codec_decode_resized_regions_host(self._h, ptrs, lens, tab, fl, ow, oh, d_px, d_status, stream))

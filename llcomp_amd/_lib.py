@@ -37,7 +37,7 @@ SYMBOLS = [
     "llcomp_mi_output_table", "llcomp_mi_codec_decode_resized_regions_ex", "llcomp_mi_codec_decode_resized_regions_host_ex",
     "llcomp_mi_stream_submit_decode_resized_regions_ex",
     "llcomp_mi_replace_slices", "llcomp_mi_replace_slices_into", "llcomp_mi_update_region", "llcomp_mi_update_region_into",
-    "llcomp_mi_codec_encode_region", "llcomp_mi_codec_update_region",
+    "llcomp_mi_codec_encode_region", "llcomp_mi_codec_update_region", "llcomp_mi_resize_filter_weights",
 ]
 
 u8p = C.POINTER(C.c_uint8)
@@ -300,6 +300,9 @@ def load():
         L.llcomp_mi_codec_update_region.restype = C.c_int
         L.llcomp_mi_codec_update_region.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p, C.c_void_p,
                                                                                                                         C.c_uint64] + [C.c_void_p] * 4
+    if "LLCOMP_MI_LIB" not in os.environ or hasattr(L, "llcomp_mi_resize_filter_weights"):  # PIL's filters, one per frame
+        L.llcomp_mi_resize_filter_weights.restype = C.c_uint32
+        L.llcomp_mi_resize_filter_weights.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     if "LLCOMP_MI_LIB" not in os.environ and L.llcomp_mi_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.llcomp_mi_abi_version()}, this binding was written for {ABI_VERSION}: rebuild the library")
     _lib = L

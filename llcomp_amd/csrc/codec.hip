@@ -363,11 +363,11 @@ struct StageLayout {
 // ... at most: every slice of the batch, each at the SLICED entry limit (the gather refuses a window entry above it)
 uint64_t stage_bound(const Geometry& g) { return StageLayout(g.frames, g.n_slices, uint64_t(g.n_slices) * (g.slice_cap - 16)).bytes; }
 // What a resized regions decode adds to the one copy at most, for outputs no larger than the image (ow <= w, oh <= h): 16 bytes of
-// alignment, and per frame its ResizeFrame and its weights -- out * (K + 1) int32 per axis, K <= 2 * max(in / out, 1) + 3, so at most
-// 2 * max(in, out) + 4 * out <= 6 * side of the image -- and the output format's table behind them (16 bytes of alignment, at most
-// 256 * c elements of 4 bytes).
+// alignment, and per frame its ResizeFrame and its weights -- out * (K + 1) int32 per axis, K <= 2 * S * max(in / out, 1) + 3 with the
+// filter's radius S <= 3 (Lanczos), so at most 6 * max(in, out) + 4 * out <= 10 * side of the image -- and the output format's table
+// behind them (16 bytes of alignment, at most 256 * c elements of 4 bytes).
 uint64_t resized_tables_bound(const Geometry& g) {
-    return 16 + uint64_t(g.frames) * (sizeof(ResizeFrame) + 4 * 6 * (uint64_t(g.w) + g.h)) + 16 + 256 * 4 * uint64_t(g.c);
+    return 16 + uint64_t(g.frames) * (sizeof(ResizeFrame) + 4 * 10 * (uint64_t(g.w) + g.h)) + 16 + 256 * 4 * uint64_t(g.c);
 }
 // The staging buffer in HBM for `bytes`: grown to max(bytes, twice its size, at most `bound`) when too small (bound: stage_bound, plus
 // resized_tables_bound for a resized regions decode).  The old buffer may still be read by the codec's last call: that call is waited
@@ -539,7 +539,8 @@ int regions_classes(llcomp_mi_codec* k, const RegionsClass* classes, uint32_t n_
 
 // Everything of a resized regions decode the host decides: every frame's window, class and box (regions_setup_sized, sized for the
 // batch's largest rectangle wmax x hmax), its rectangle inside the box, its flags, its weights (resize.hpp) and the output format's table.
-// BAD_ARGS for a null rects, an output side of 0, any rectangle outside the image, a downscale above kResizeMaxDown on either axis, a bad
+// BAD_ARGS for a null rects, an output side of 0, any rectangle outside the image, a filter code above 5 in a frame's flags, a downscale
+// above the frame's filter's limit on either axis (resize.hpp: resize_axis_ok), a bad
 // output format (check_output_format) and an output not aligned to the format's element size.
 struct ResizedPlan {
     std::vector<RegionsFrame> tab;
@@ -569,8 +570,9 @@ int resized_setup(const llcomp_mi_codec* k, const uint32_t* rects, const uint8_t
     if (reinterpret_cast<uintptr_t>(d_out) & (p.out.esize - 1)) return LLCOMP_MI_BAD_ARGS;
     if (!rects || !ow || !oh || g.frames > 65535) return LLCOMP_MI_BAD_ARGS;
     for (uint32_t f = 0; f < g.frames; ++f) {
-        const uint32_t rw = rects[4 * f + 2], rh = rects[4 * f + 3];
-        if (uint64_t(rw) > uint64_t(kResizeMaxDown) * ow || uint64_t(rh) > uint64_t(kResizeMaxDown) * oh) return LLCOMP_MI_BAD_ARGS;
+        const uint32_t rw = rects[4 * f + 2], rh = rects[4 * f + 3], filter = flags ? LLCOMP_MI_FLAG_FILTER_OF(flags[f]) : 0u;
+        // (an empty rectangle is regions_setup_sized's to refuse; an unknown filter and a downscale above the filter's limit are refused here)
+        if (filter >= kResizeFilters || (rw && !resize_axis_ok(filter, rw, ow)) || (rh && !resize_axis_ok(filter, rh, oh))) return LLCOMP_MI_BAD_ARGS;
         p.wmax = std::max(p.wmax, rw);
         p.hmax = std::max(p.hmax, rh);
     }
@@ -583,8 +585,8 @@ int resized_setup(const llcomp_mi_codec* k, const uint32_t* rects, const uint8_t
         ResizeFrame& z = p.rs[e.frame];
         z.ox = r[0] - e.wx0 * g.tile_w - e.cx0;
         z.oy = r[1] - e.wy0 * g.tile_h - e.cy0;
-        z.flags = flags ? flags[e.frame] & 1u : 0u;
-        if (!resize_frame_weights(r[2], r[3], ow, oh, z, p.w, seen)) return LLCOMP_MI_BAD_ARGS;
+        z.flags = flags ? flags[e.frame] & (1u | LLCOMP_MI_FLAG_FILTER_MASK) : 0u;
+        if (!resize_frame_weights(LLCOMP_MI_FLAG_FILTER_OF(z.flags), r[2], r[3], ow, oh, z, p.w, seen)) return LLCOMP_MI_BAD_ARGS;
         if (uint64_t(z.ox) + z.rw > p.wmax || uint64_t(z.oy) + z.rh > p.hmax) return LLCOMP_MI_HIP_ERROR;  // (the box holds it by construction)
     }
     p.box_bytes = uint64_t(g.frames) * p.wmax * p.hmax * g.c;

@@ -10,11 +10,14 @@
 
 namespace llcomp_mi {
 
-// The triangle filter with antialiasing for one axis, in_len -> out_len (include/llcomp_mi.h: llcomp_mi_resize_weights): the taps per
+// One axis, in_len -> out_len, under filter LLCOMP_MI_FILTER_* (include/llcomp_mi.h: llcomp_mi_resize_filter_weights): the taps per
 // output K (trailing taps that are zero for every output are left out), lo[out_len] and q[out_len][K] in Q22, zero-padded.  0 for
-// in_len or out_len 0 or a downscale above kResizeMaxDown.
+// in_len or out_len 0, an unknown filter, or a downscale above the filter's limit (resize_axis_ok): R * in_len > kResizeMaxDown * out_len
+// with R = 1, but 2 for bicubic and 3 for Lanczos, so that the filter's support never passes kResizeMaxDown input samples and K <= 129.
 constexpr uint32_t kResizeMaxDown = 64;
-uint32_t resize_weights(uint32_t in_len, uint32_t out_len, uint32_t* lo, int32_t* q);
+constexpr uint32_t kResizeFilters = 6;
+bool resize_axis_ok(uint32_t filter, uint32_t in_len, uint32_t out_len);
+uint32_t resize_weights(uint32_t filter, uint32_t in_len, uint32_t out_len, uint32_t* lo, int32_t* q);
 
 // One frame of a resized regions decode, as the kernels see it.  The frame's box (the batch's largest rectangle size, bw x bh) is
 // d_box[f]; its rectangle starts at (ox, oy) inside it.  The weights live in one int32 array: the horizontal pass's at hx -- lo[ow],
@@ -25,13 +28,15 @@ struct ResizeFrame {
     uint32_t rw, rh;  // the rectangle
     uint32_t kx, ky;  // taps per output, horizontal / vertical
     uint32_t hx, vy;  // offsets of the weights, in int32 units
-    uint32_t flags;   // bit 0: mirror the output horizontally
+    uint32_t flags;   // bit 0: mirror the output horizontally; bits 4-6: the frame's filter (the kernels read bit 0 only)
     uint32_t pad[3];
 };
-// Appends the weights of a rw x rh rectangle for ow x oh to `w` and fills `e` (ox / oy / flags are the caller's).  An axis (side -> output
-// side) that an earlier frame of the call already put in `w` is shared: `seen` (empty at the start of a call) records them.  false for a
-// downscale above the limit.
-bool resize_frame_weights(uint32_t rw, uint32_t rh, uint32_t ow, uint32_t oh, ResizeFrame& e, std::vector<int32_t>& w, std::vector<uint32_t>& seen);
+static_assert(sizeof(ResizeFrame) == 48, "the kernels and the staging layout count on 48 bytes");
+// Appends the weights of a rw x rh rectangle for ow x oh under `filter` to `w` and fills `e` (ox / oy / flags are the caller's).  An axis
+// (filter, side -> output side) that an earlier frame of the call already put in `w` is shared: `seen` (empty at the start of a call)
+// records them.  false for an unknown filter or a downscale above its limit.
+bool resize_frame_weights(uint32_t filter, uint32_t rw, uint32_t rh, uint32_t ow, uint32_t oh, ResizeFrame& e, std::vector<int32_t>& w,
+                          std::vector<uint32_t>& seen);
 
 // d_box [frames][bh][bw][c] -> d_mid [frames][bh][ow][c] (rows [0, rh) of every frame: the horizontal pass, rounded to u8) -> d_px
 // [frames][oh][ow][c] (the vertical pass, then the mirror).  The caller guarantees ox + rw <= bw, oy + rh <= bh for every entry.

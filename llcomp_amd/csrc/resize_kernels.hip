@@ -12,11 +12,58 @@
 
 namespace llcomp_mi {
 
+// The filters' kernel functions, as PIL's Resample.c states them (operation for operation: the weights are compared bit for bit).
+static double f_box(double x) { return (x > -0.5 && x <= 0.5) ? 1.0 : 0.0; }
+static double f_triangle(double x) { return std::max(0.0, 1.0 - std::fabs(x)); }
+static double f_hamming(double x) {
+    x = std::fabs(x);
+    if (x == 0.0) return 1.0;
+    if (x >= 1.0) return 0.0;
+    x = x * M_PI;
+    return std::sin(x) / x * (0.54 + 0.46 * std::cos(x));
+}
+static double f_bicubic(double x) {
+    constexpr double a = -0.5;
+    x = std::fabs(x);
+    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+    return 0.0;
+}
+static double f_sinc(double x) {
+    if (x == 0.0) return 1.0;
+    x = x * M_PI;
+    return std::sin(x) / x;
+}
+static double f_lanczos(double x) { return (-3.0 <= x && x < 3.0) ? f_sinc(x) * f_sinc(x / 3) : 0.0; }
+
+struct FilterRule {
+    double (*f)(double);
+    double radius;    // S: the kernel function's support at scale 1
+    uint32_t reach;   // R: in_len * R <= kResizeMaxDown * out_len, so that S * max(scale, 1) <= kResizeMaxDown and K <= 129
+};
+static const FilterRule* filter_rule(uint32_t filter) {
+    static const FilterRule kRules[kResizeFilters] = {{f_triangle, 1.0, 1}, {nullptr, 0.0, 1},  {f_box, 0.5, 1},
+                                                      {f_hamming, 1.0, 1},  {f_bicubic, 2.0, 2}, {f_lanczos, 3.0, 3}};
+    return filter < kResizeFilters ? &kRules[filter] : nullptr;
+}
+bool resize_axis_ok(uint32_t filter, uint32_t in_len, uint32_t out_len) {
+    const FilterRule* r = filter_rule(filter);
+    return r && in_len && out_len && uint64_t(r->reach) * in_len <= uint64_t(kResizeMaxDown) * out_len;
+}
+
 // One pass over the outputs: every output's lo and its Q22 run (at most `span` taps) into lo_all / q_all, and K.
-static uint32_t weights_pass(uint32_t in_len, uint32_t out_len, std::vector<uint32_t>& lo_all, std::vector<int32_t>& q_all, uint32_t& span) {
-    const double scale = double(in_len) / double(out_len), support = std::max(scale, 1.0), ss = 1.0 / support;
-    span = uint32_t(std::ceil(2.0 * support)) + 2;
+static uint32_t weights_pass(uint32_t filter, uint32_t in_len, uint32_t out_len, std::vector<uint32_t>& lo_all, std::vector<int32_t>& q_all,
+                             uint32_t& span) {
     lo_all.resize(out_len);
+    if (filter == LLCOMP_MI_FILTER_NEAREST) {  // (the centre-aligned rule in exact integers: one tap of 1.0)
+        span = 1;
+        q_all.assign(out_len, 1 << 22);
+        for (uint32_t i = 0; i < out_len; ++i) lo_all[i] = uint32_t((2 * uint64_t(i) + 1) * in_len / (2 * uint64_t(out_len)));
+        return 1;
+    }
+    const FilterRule& r = *filter_rule(filter);
+    const double scale = double(in_len) / double(out_len), support = r.radius * std::max(scale, 1.0), ss = 1.0 / std::max(scale, 1.0);
+    span = uint32_t(std::ceil(2.0 * support)) + 2;  // (support <= kResizeMaxDown: resize_axis_ok)
     q_all.assign(size_t(out_len) * span, 0);
     double w[2 * kResizeMaxDown + 4];
     uint32_t k = 1;
@@ -27,13 +74,14 @@ static uint32_t weights_pass(uint32_t in_len, uint32_t out_len, std::vector<uint
         const uint32_t n = uint32_t(std::min<int64_t>(std::max<int64_t>(b - a, 0), span));
         double sum = 0.0;
         for (uint32_t j = 0; j < n; ++j) {
-            w[j] = std::max(0.0, 1.0 - std::fabs((double(a + int64_t(j)) - center + 0.5) * ss));
+            w[j] = r.f((double(a + int64_t(j)) - center + 0.5) * ss);
             sum += w[j];
         }
         int32_t* q = q_all.data() + size_t(i) * span;
         uint32_t last = 0;
         for (uint32_t j = 0; j < n; ++j) {
-            q[j] = sum > 0.0 ? int32_t(std::floor(0.5 + w[j] / sum * double(1 << 22))) : 0;
+            const double v = sum != 0.0 ? w[j] / sum : w[j];
+            q[j] = v < 0.0 ? int32_t(-0.5 + v * double(1 << 22)) : int32_t(0.5 + v * double(1 << 22));  // (both truncate toward zero)
             if (q[j]) last = j + 1;
         }
         lo_all[i] = uint32_t(a);
@@ -42,12 +90,12 @@ static uint32_t weights_pass(uint32_t in_len, uint32_t out_len, std::vector<uint
     return k;
 }
 
-uint32_t resize_weights(uint32_t in_len, uint32_t out_len, uint32_t* lo, int32_t* q) {
-    if (!in_len || !out_len || uint64_t(in_len) > uint64_t(kResizeMaxDown) * out_len) return 0;
+uint32_t resize_weights(uint32_t filter, uint32_t in_len, uint32_t out_len, uint32_t* lo, int32_t* q) {
+    if (!resize_axis_ok(filter, in_len, out_len)) return 0;
     std::vector<uint32_t> lo_all;
     std::vector<int32_t> q_all;
     uint32_t span = 0;
-    const uint32_t k = weights_pass(in_len, out_len, lo_all, q_all, span);
+    const uint32_t k = weights_pass(filter, in_len, out_len, lo_all, q_all, span);
     for (uint32_t i = 0; i < out_len; ++i) {
         if (lo) lo[i] = lo_all[i];
         if (q)
@@ -57,18 +105,19 @@ uint32_t resize_weights(uint32_t in_len, uint32_t out_len, uint32_t* lo, int32_t
 }
 
 // One axis for the kernels: lo moved left over zero weights until lo + k <= in_len, weights tap-major.  An axis already in `w` (the
-// same in_len -> out_len earlier in the call: `seen` holds {in_len, out_len, k, at} of each) is shared, not computed again.
-static uint32_t axis_weights(uint32_t in_len, uint32_t out_len, std::vector<int32_t>& w, uint32_t& at, std::vector<uint32_t>& seen) {
-    if (!in_len || !out_len || uint64_t(in_len) > uint64_t(kResizeMaxDown) * out_len) return 0;
-    for (size_t i = 0; i + 4 <= seen.size(); i += 4)
-        if (seen[i] == in_len && seen[i + 1] == out_len) {
-            at = seen[i + 3];
-            return seen[i + 2];
+// same filter and in_len -> out_len earlier in the call: `seen` holds {filter, in_len, out_len, k, at} of each) is shared, not computed
+// again.
+static uint32_t axis_weights(uint32_t filter, uint32_t in_len, uint32_t out_len, std::vector<int32_t>& w, uint32_t& at, std::vector<uint32_t>& seen) {
+    if (!resize_axis_ok(filter, in_len, out_len)) return 0;
+    for (size_t i = 0; i + 5 <= seen.size(); i += 5)
+        if (seen[i] == filter && seen[i + 1] == in_len && seen[i + 2] == out_len) {
+            at = seen[i + 4];
+            return seen[i + 3];
         }
     thread_local std::vector<uint32_t> lo;  // (scratch, reused from call to call)
     thread_local std::vector<int32_t> q;
     uint32_t span = 0;
-    const uint32_t k = weights_pass(in_len, out_len, lo, q, span);
+    const uint32_t k = weights_pass(filter, in_len, out_len, lo, q, span);
     at = uint32_t(w.size());
     w.resize(w.size() + size_t(out_len) * (k + 1), 0);
     int32_t* l = w.data() + at;
@@ -78,15 +127,16 @@ static uint32_t axis_weights(uint32_t in_len, uint32_t out_len, std::vector<int3
         l[i] = int32_t(a);
         for (uint32_t j = 0; j + s < k; ++j) t[size_t(j + s) * out_len + i] = q[size_t(i) * span + j];
     }
-    seen.insert(seen.end(), {in_len, out_len, k, at});
+    seen.insert(seen.end(), {filter, in_len, out_len, k, at});
     return k;
 }
 
-bool resize_frame_weights(uint32_t rw, uint32_t rh, uint32_t ow, uint32_t oh, ResizeFrame& e, std::vector<int32_t>& w, std::vector<uint32_t>& seen) {
+bool resize_frame_weights(uint32_t filter, uint32_t rw, uint32_t rh, uint32_t ow, uint32_t oh, ResizeFrame& e, std::vector<int32_t>& w,
+                          std::vector<uint32_t>& seen) {
     e.rw = rw;
     e.rh = rh;
-    e.kx = axis_weights(rw, ow, w, e.hx, seen);
-    e.ky = axis_weights(rh, oh, w, e.vy, seen);
+    e.kx = axis_weights(filter, rw, ow, w, e.hx, seen);
+    e.ky = axis_weights(filter, rh, oh, w, e.vy, seen);
     return e.kx && e.ky;
 }
 
@@ -165,7 +215,16 @@ void output_table(const llcomp_mi_output_format* fmt, uint32_t c, const OutForma
 
 namespace {
 
-__device__ __forceinline__ uint32_t q22_round(int32_t acc) { return uint32_t(min((acc + (1 << 21)) >> 22, 255)); }
+// Clamped at both ends: bicubic and Lanczos have negative lobes, so a sum can leave [0, 255] on either side.  One v_med3_i32, written
+// out: from min(max(x >> 22, 0), 255) hipcc (ROCm 7.0) selects gfx950's v_ashr_pk_u8_i32 for two channels at a time and ORs the other
+// channels into the register as if its upper half were zero, and on the MI355X the c = 4 paths then stored wrong bytes in channels
+// 2 and 3 (channels 0 and 1, the packed pair, were right).  The asm keeps the value opaque, so every channel takes this one instruction.
+__device__ __forceinline__ uint32_t q22_round(int32_t acc) {
+    const int32_t v = (acc + (1 << 21)) >> 22;
+    int32_t r;
+    asm("v_med3_i32 %0, %1, 0, %2" : "=v"(r) : "v"(v), "v"(255));
+    return uint32_t(r);
+}
 
 // Horizontal pass: one lane per (frame, rectangle row, output x), all channels; lanes of a row read neighbouring weights (tap-major).
 template <int C>
@@ -370,34 +429,40 @@ void launch_v_out(dim3 gv, hipStream_t stream, const uint8_t* d_mid, void* d_out
 
 }  // namespace
 
+// The horizontal pass of both launchers.
+static hipError_t launch_h(const uint8_t* d_box, uint8_t* d_mid, const ResizeFrame* d_tab, const int32_t* d_w, uint32_t frames, uint32_t c, uint32_t bw,
+                           uint32_t bh, uint32_t ow, hipStream_t stream) {
+    const uint64_t hb = (uint64_t(bh) * ow + 255) / 256;
+    if (hb > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const dim3 gh(uint32_t(hb), frames), blk(256);
+    switch (c) {
+        case 1: k_resize_h<1><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, ow, c); break;
+        case 3: k_resize_h<3><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, ow, c); break;
+        case 4: k_resize_h<4><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, ow, c); break;
+        default: k_resize_h<0><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, ow, c); break;
+    }
+    return hipSuccess;
+}
+
 hipError_t launch_resize(const uint8_t* d_box, uint8_t* d_mid, uint8_t* d_px, const ResizeFrame* d_tab, const int32_t* d_w, uint32_t frames,
                          uint32_t c, uint32_t bw, uint32_t bh, uint32_t ow, uint32_t oh, hipStream_t stream) {
     if (!frames || !c || !bw || !bh || !ow || !oh || frames > 65535) return hipErrorInvalidValue;
-    const uint64_t hb = (uint64_t(bh) * ow + 255) / 256, vb = (uint64_t(oh) * ow + 255) / 256;
-    if (hb > 0x7FFFFFFFull || vb > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    const dim3 gh(uint32_t(hb), frames), gv(uint32_t(vb), frames), blk(256);
+    const uint64_t vb = (uint64_t(oh) * ow + 255) / 256;
+    if (vb > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const dim3 gv(uint32_t(vb), frames), blk(256);
     // (the box and the intermediate are the codec's own, 4-byte aligned; the output is the caller's: 32-bit stores only when aligned)
     const bool out4 = (reinterpret_cast<uintptr_t>(d_px) & 3u) == 0;
+    if (hipError_t err = launch_h(d_box, d_mid, d_tab, d_w, frames, c, bw, bh, ow, stream)) return err;
     switch (c) {
-        case 1:
-            k_resize_h<1><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, ow, c);
-            k_resize_v<1><<<gv, blk, 0, stream>>>(d_mid, d_px, d_tab, d_w, bh, ow, oh, c);
-            break;
-        case 3:
-            k_resize_h<3><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, ow, c);
-            k_resize_v<3><<<gv, blk, 0, stream>>>(d_mid, d_px, d_tab, d_w, bh, ow, oh, c);
-            break;
+        case 1: k_resize_v<1><<<gv, blk, 0, stream>>>(d_mid, d_px, d_tab, d_w, bh, ow, oh, c); break;
+        case 3: k_resize_v<3><<<gv, blk, 0, stream>>>(d_mid, d_px, d_tab, d_w, bh, ow, oh, c); break;
         case 4:
-            k_resize_h<4><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, ow, c);
             if (out4)
                 k_resize_v<4><<<gv, blk, 0, stream>>>(d_mid, d_px, d_tab, d_w, bh, ow, oh, c);
             else
                 k_resize_v<0><<<gv, blk, 0, stream>>>(d_mid, d_px, d_tab, d_w, bh, ow, oh, c);
             break;
-        default:
-            k_resize_h<0><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, ow, c);
-            k_resize_v<0><<<gv, blk, 0, stream>>>(d_mid, d_px, d_tab, d_w, bh, ow, oh, c);
-            break;
+        default: k_resize_v<0><<<gv, blk, 0, stream>>>(d_mid, d_px, d_tab, d_w, bh, ow, oh, c); break;
     }
     return hipGetLastError();
 }
@@ -408,15 +473,10 @@ hipError_t launch_resize_out(const uint8_t* d_box, uint8_t* d_mid, void* d_out, 
     if (o.plain) return launch_resize(d_box, d_mid, static_cast<uint8_t*>(d_out), d_tab, d_w, frames, c, bw, bh, ow, oh, stream);
     if (!frames || !c || c > 255 || !bw || !bh || !ow || !oh || frames > 65535 || !d_table) return hipErrorInvalidValue;
     if ((reinterpret_cast<uintptr_t>(d_table) & 3u) || (reinterpret_cast<uintptr_t>(d_out) & (o.esize - 1))) return hipErrorInvalidValue;
-    const uint64_t hb = (uint64_t(bh) * ow + 255) / 256, vb = (uint64_t(oh) * ow + 255) / 256;
-    if (hb > 0x7FFFFFFFull || vb > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    const dim3 gh(uint32_t(hb), frames), gv(uint32_t(vb), frames), blk(256);
-    switch (c) {  // (the horizontal pass of launch_resize)
-        case 1: k_resize_h<1><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, ow, c); break;
-        case 3: k_resize_h<3><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, ow, c); break;
-        case 4: k_resize_h<4><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, ow, c); break;
-        default: k_resize_h<0><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, ow, c); break;
-    }
+    const uint64_t vb = (uint64_t(oh) * ow + 255) / 256;
+    if (vb > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const dim3 gv(uint32_t(vb), frames);
+    if (hipError_t err = launch_h(d_box, d_mid, d_tab, d_w, frames, c, bw, bh, ow, stream)) return err;
     // (HWC at c = 4 stores a pixel's 4 elements at once: only where d_out is aligned to 4 elements)
     const bool vec4 = (reinterpret_cast<uintptr_t>(d_out) & (4 * o.esize - 1)) == 0;
     const uint32_t* t = static_cast<const uint32_t*>(d_table);
@@ -435,7 +495,11 @@ hipError_t launch_resize_out(const uint8_t* d_box, uint8_t* d_mid, void* d_out, 
 }  // namespace llcomp_mi
 
 extern "C" uint32_t llcomp_mi_resize_weights(uint32_t in_len, uint32_t out_len, uint32_t* lo, int32_t* q) {
-    return llcomp_mi::resize_weights(in_len, out_len, lo, q);
+    return llcomp_mi::resize_weights(LLCOMP_MI_FILTER_BILINEAR, in_len, out_len, lo, q);
+}
+
+extern "C" uint32_t llcomp_mi_resize_filter_weights(uint32_t filter, uint32_t in_len, uint32_t out_len, uint32_t* lo, int32_t* q) {
+    return llcomp_mi::resize_weights(filter, in_len, out_len, lo, q);
 }
 
 extern "C" int llcomp_mi_output_table(const llcomp_mi_output_format* fmt, uint32_t c, void* table) {

@@ -12,6 +12,11 @@ repeat; timing is hipEvents on the stream with a synchronise behind each call.  
 the numpy statement of the rule (tests/resize_spec.py); the torch paths are checked to agree with it within 1 LSB.
 
     python tools/resized_regions_sweep.py [out.jsonl] [--reps N] [--tag TEXT] [--quick]    # on a GPU box; one JSON line per case
+
+With --filter NAME[,NAME...] (or "all") the tool measures the new call alone, per filter (bilinear, nearest, box, hamming, bicubic,
+lanczos), on the same four cases and rectangles, the filters in rotating order from repeat to repeat.  Per case and filter: the median,
+the smallest and the largest of the repeats, and the largest K.  Frame 0 of each is checked byte for byte against the rule restated in
+tests/resize_filters_spec.py.  --quick with --filter: one case (for a kernel trace of one filter).
 """
 import argparse
 import json
@@ -33,7 +38,10 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--tag", default="")
     ap.add_argument("--quick", action="store_true", help="one case (nat, 480x1p), the new call only: for a kernel trace")
+    ap.add_argument("--filter", default="", help="comma-separated filters, or 'all': the new call alone, per filter")
     a = ap.parse_args()
+    if a.filter:
+        return filter_sweep(a)
     import numpy as np
     import torch
     import torch.nn.functional as F
@@ -148,6 +156,86 @@ def main():
             codec.close()
             one.close()
             del d_pay, d_len, d_full, d_out, d_box, d_one
+            torch.cuda.empty_cache()
+    if out:
+        out.close()
+
+
+def filter_sweep(a):
+    """--filter: the resized call per filter"""
+    import numpy as np
+    import torch
+
+    import bench
+    import llcomp_amd as mi
+    import resize_filters_spec as spec
+    from resize_spec import random_resized_crop
+
+    names = list(mi.FILTER_NAMES) if a.filter == "all" else [n.strip().lower() for n in a.filter.split(",")]
+    out = open(a.out, "a") if a.out else None
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if out:
+            print(line, file=out, flush=True)
+
+    emit({"tool": "resized_regions_sweep --filter", "tag": a.tag, "frames": FRAMES, "w": W, "h": H, "c": C, "out": [OW, OH], "reps": a.reps,
+          "filters": names, "device": torch.cuda.get_device_name(0)})
+    st = torch.cuda.current_stream()
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def timed(fn):
+        ev0.record(st)
+        fn()
+        ev1.record(st)
+        torch.cuda.synchronize()
+        return ev0.elapsed_time(ev1)
+
+    rng = np.random.default_rng(224)
+    for content in (("nat",) if a.quick else ("nat", "g3")):
+        d_img = torch.from_numpy(bench.make_frames(content, FRAMES, 0, distinct=4)).cuda()
+        for tw, th, planar in (SLICINGS[:1] if a.quick else SLICINGS):
+            codec = mi.Codec(FRAMES, W, H, C, tw, th, planar, device=0)
+            codec.prepare(encode=True, decode=True, region=True, regions=True, resized=True)
+            cap = min(codec.max_payload_bytes, 2 * d_img.numel() + 64 * codec.n_slices + 4096)
+            d_pay = torch.empty(cap, dtype=torch.uint8, device="cuda")
+            d_len = torch.empty(codec.n_slices, dtype=torch.int32, device="cuda")
+            d_tot = torch.zeros(1, dtype=torch.int64, device="cuda")
+            d_st = torch.zeros(1, dtype=torch.int32, device="cuda")
+            codec.encode(d_img.data_ptr(), d_pay.data_ptr(), cap, d_len.data_ptr(), d_tot.data_ptr(), d_st.data_ptr(), st.cuda_stream)
+            torch.cuda.synchronize()
+            assert int(d_st.item()) == 0
+            total = int(d_tot.item())
+            rects = np.array([random_resized_crop(rng, W, H) for _ in range(FRAMES)], np.uint32)
+            flags = np.array([f % 2 for f in range(FRAMES)], np.uint8)
+            d_out = torch.empty((FRAMES, OH, OW, C), dtype=torch.uint8, device="cuda")
+            x0, y0, rw0, rh0 = rects[0].tolist()
+            crop0 = d_img[0, y0:y0 + rh0, x0:x0 + rw0].cpu().numpy()
+
+            def call(code):
+                codec.decode_resized_regions(d_pay.data_ptr(), total, d_len.data_ptr(), rects, OW, OH, d_out.data_ptr(), d_st.data_ptr(),
+                                             flags=flags, stream=st.cuda_stream, filter=code)
+
+            codes = [mi.filter_code(n) for n in names]
+            for code in codes:
+                d_out.zero_()
+                call(code)
+                call(code)
+                torch.cuda.synchronize()
+                assert int(d_st.item()) == 0 and np.array_equal(d_out[0].cpu().numpy(), spec.resize(crop0, OW, OH, code, False)), code
+            times = {code: [] for code in codes}
+            for rep in range(a.reps):
+                k = rep % len(codes)
+                for code in codes[k:] + codes[:k]:
+                    times[code].append(timed(lambda: call(code)))
+            for name, code in zip(names, codes):
+                kmax = max(mi.resize_weights(int(r[2]), OW, code)[1].shape[1] for r in rects)
+                emit({"content": content, "slicing": f"{tw}x{th}{'p' if planar else 'i'}", "filter": name, "kx_max": int(kmax),
+                      "largest": [int(rects[:, 2].max()), int(rects[:, 3].max())], "resized_ms": round(float(np.median(times[code])), 3),
+                      "min_ms": round(float(min(times[code])), 3), "max_ms": round(float(max(times[code])), 3)})
+            codec.close()
+            del d_pay, d_len, d_out
             torch.cuda.empty_cache()
     if out:
         out.close()
