@@ -89,23 +89,55 @@ static void sink_put(sink_t* s, uint8_t b) {
 typedef struct {
     int low, range, held, pend;
     sink_t* out;
+    long opened; /* event log only: the sample that was being coded when the first byte of the pending run was counted */
+    int finishing;
 } renc_t;
 
-static void renc_init(renc_t* e, sink_t* out) {  /* hpp:35 */
-    e->low = 0; e->range = 0xFF00; e->held = -1; e->pend = 0; e->out = out;
-}
 /* test coverage only: how often a carry had to travel through a run of undecided 0xFF bytes, and the longest run */
 static long g_carry_runs, g_carry_longest;
+/* ... and a bounded log of the runs themselves (orc_carry_log).  g_sample: the sample orc_encode_rect is coding (the sample count
+ * once it has reached finish()); g_stream: bare streams begun since the last reset. */
+#define ORC_CARRY_LOG_CAP 256
+static orc_carry_event_t g_log[ORC_CARRY_LOG_CAP];
+static long g_log_total, g_log_min_run = 1, g_sample, g_stream;
 void orc_carry_stats(long* runs, long* longest, int reset) {
     if (runs) *runs = g_carry_runs;
     if (longest) *longest = g_carry_longest;
-    if (reset) g_carry_runs = g_carry_longest = 0;
+    if (reset) g_carry_runs = g_carry_longest = g_log_total = g_stream = 0;
+}
+void orc_carry_log_min_run(long min_run) { g_log_min_run = min_run < 1 ? 1 : min_run; }
+long orc_carry_log(orc_carry_event_t* out, long cap, long* total) {
+    long n = g_log_total < ORC_CARRY_LOG_CAP ? g_log_total : ORC_CARRY_LOG_CAP;
+    if (total) *total = g_log_total;
+    if (n > cap) n = cap;
+    if (out && n > 0) memcpy(out, g_log, (size_t)n * sizeof *out);
+    return n;
+}
+/* the held byte is about to be written at offset out->n, the e->pend bytes of the run behind it */
+static void log_run(const renc_t* e, int carried) {
+    if (e->pend < g_log_min_run) return;
+    if (g_log_total < ORC_CARRY_LOG_CAP) {
+        orc_carry_event_t* v = &g_log[g_log_total];
+        v->stream = g_stream - 1;
+        v->offset = (long)e->out->n;
+        v->run = e->pend;
+        v->how = (carried ? ORC_RUN_CARRIED : ORC_RUN_STAYED_FF) | (e->finishing ? ORC_RUN_IN_FINISH : 0);
+        v->opened = e->opened;
+        v->resolved = g_sample;
+    }
+    g_log_total++;
+}
+static void renc_init(renc_t* e, sink_t* out) {  /* hpp:35 */
+    e->low = 0; e->range = 0xFF00; e->held = -1; e->pend = 0; e->out = out;
+    e->opened = 0; e->finishing = 0;
+    g_stream++;
 }
 static void renc_renorm(renc_t* e) {  /* hpp:38-58 */
     while (e->range < 0x100) {
         if (e->held < 0) {
             e->held = e->low >> 8;
         } else if (e->low <= 0xFF00) {
+            if (e->pend) log_run(e, 0);
             sink_put(e->out, (uint8_t)e->held);
             for (; e->pend; e->pend--) sink_put(e->out, 0xFF);
             e->held = e->low >> 8;
@@ -113,11 +145,13 @@ static void renc_renorm(renc_t* e) {  /* hpp:38-58 */
             if (e->pend) {
                 g_carry_runs++;
                 if (e->pend > g_carry_longest) g_carry_longest = e->pend;
+                log_run(e, 1);
             }
             sink_put(e->out, (uint8_t)(e->held + 1));
             for (; e->pend; e->pend--) sink_put(e->out, 0x00);
             e->held = (e->low >> 8) & 0xFF;
         } else {
+            if (!e->pend) e->opened = g_sample;
             e->pend++;
         }
         e->low = (e->low & 0xFF) << 8;
@@ -135,6 +169,7 @@ static inline void renc_put(renc_t* e, int bit, int p) {  /* hpp:60-73 */
     if (e->range < 0x100) renc_renorm(e);
 }
 static void renc_finish(renc_t* e) {  /* hpp:75-81 */
+    e->finishing = 1;
     e->range = 0xFF; e->low += 0xFF; renc_renorm(e);
     e->range = 0xFF; renc_renorm(e);
 }
@@ -283,9 +318,10 @@ long orc_encode_rect(const int16_t* base, long rs, int ps, int nch, int tw, int 
     renc_init(&e, &sk);
     uint8_t* table = (uint8_t*)calloc(ORC_N_CTX, 8); /* hpp:385, all states 0; 8 slots per context */
     if (!table) return -1;
+    g_sample = 0;
     for (int y = 0; y < th; ++y)
         for (int x = 0; x < tw; ++x)
-            for (int k = 0; k < nch; ++k) {
+            for (int k = 0; k < nch; ++k, ++g_sample) {
                 hood_t n = hood(base, rs, ps, tw, x, y, k);
                 int ctx = context_of(&n);
                 int res = base[(long)y * rs + (long)x * ps + k] - orc_median(n.l, n.l + n.t - n.tl, n.t);

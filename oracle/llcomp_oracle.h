@@ -78,6 +78,19 @@ uint64_t orc_fnv1a64(const uint8_t* p, size_t n);
 /* coverage counters of the encoder since the last reset: carries that travelled through a run of undecided 0xFF
    bytes (hpp:49-50 with outstanding_count > 0) and the longest such run.  Not thread-safe; tests only. */
 void orc_carry_stats(long* runs, long* longest, int reset);
+/* ... and the runs themselves: every run of undecided 0xFF bytes at least min_run long (default 1) that the encoder resolved since
+   the last reset of orc_carry_stats, the first 256 of them.  `stream`: which bare stream since that reset (slices of a container
+   in its order); `offset`: where in that stream the held byte in front of the run went, the run's bytes behind it; `how`: carried
+   (byte + 1, 00...) or stayed (byte, FF...), ORed with ORC_RUN_IN_FINISH when the run was still open on entry to finish();
+   `opened` / `resolved`: the sample orc_encode_rect was coding when the run's first byte was held back and when the run went out
+   (the sample count for one that went out in finish(); other encoders leave the counter alone).  orc_carry_log copies at most
+   cap events and returns how many; *total: how many there were, logged or not. */
+enum { ORC_RUN_CARRIED = 1, ORC_RUN_STAYED_FF = 2, ORC_RUN_IN_FINISH = 4 };
+typedef struct {
+    long stream, offset, run, how, opened, resolved;
+} orc_carry_event_t;
+void orc_carry_log_min_run(long min_run);
+long orc_carry_log(orc_carry_event_t* out, long cap, long* total);
 void orc_free(void* p);
 
 #ifdef __cplusplus

@@ -5,6 +5,7 @@
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module.
 """
+import collections
 import ctypes as C
 import os
 
@@ -20,6 +21,15 @@ OK, BAD_MAGIC, BAD_EXPONENT, TRUNCATED, BAD_ARGS, NOMEM = range(6)
 _u8p = C.POINTER(C.c_uint8)
 _i16p = C.POINTER(C.c_int16)
 _u16p = C.POINTER(C.c_uint16)
+
+RUN_CARRIED, RUN_STAYED_FF, RUN_IN_FINISH = 1, 2, 4  # llcomp_oracle.h: orc_carry_event_t.how
+
+
+class _CarryEvent(C.Structure):
+    _fields_ = [(n, C.c_long) for n in ("stream", "offset", "run", "how", "opened", "resolved")]
+
+
+CarryEvent = collections.namedtuple("CarryEvent", "stream offset run carried in_finish opened resolved")
 
 
 def _p(a, t):
@@ -74,6 +84,10 @@ class Orc:
         L.orc_set_small_model.argtypes = [C.c_int]
         L.orc_carry_stats.restype = None
         L.orc_carry_stats.argtypes = [C.POINTER(C.c_long), C.POINTER(C.c_long), C.c_int]
+        L.orc_carry_log_min_run.restype = None
+        L.orc_carry_log_min_run.argtypes = [C.c_long]
+        L.orc_carry_log.restype = C.c_long
+        L.orc_carry_log.argtypes = [C.POINTER(_CarryEvent), C.c_long, C.POINTER(C.c_long)]
         for f in ("orc_quant11", "orc_quant5", "orc_state_p"):
             getattr(L, f).restype = C.c_int
             getattr(L, f).argtypes = [C.c_int]
@@ -91,6 +105,21 @@ class Orc:
         runs, longest = C.c_long(), C.c_long()
         self.lib.orc_carry_stats(C.byref(runs), C.byref(longest), int(reset))
         return runs.value, longest.value
+
+    def carry_log(self, min_run=None):
+        """Without min_run: the runs of undecided 0xFF bytes that the encoder resolved since carry_stats(reset=True), as CarryEvent
+        (stream: which bare stream since the reset; offset: of the held byte in front of the run; run: its length; carried: byte + 1
+        and 00s, else FFs; in_finish: still open when finish() began; opened / resolved: sample indices of encode_samples and the
+        container encoders).  Raises when there were more than the log holds.  With min_run: from now on only runs at least that long
+        are logged (process-wide, 1 = all); returns nothing."""
+        if min_run is not None:
+            self.lib.orc_carry_log_min_run(int(min_run))
+            return None
+        buf, total = (_CarryEvent * 256)(), C.c_long()
+        n = self.lib.orc_carry_log(buf, 256, C.byref(total))
+        if total.value > n:
+            raise OverflowError(f"{total.value} runs since the reset, the log holds {n}: raise carry_log(min_run=...)")
+        return [CarryEvent(e.stream, e.offset, e.run, bool(e.how & RUN_CARRIED), bool(e.how & RUN_IN_FINISH), e.opened, e.resolved) for e in buf[:n]]
 
     def _take(self, ptr, n):
         out = C.string_at(ptr, n)

@@ -2,7 +2,8 @@
 """Child process of tests/test_gpu_asm_guard.py: runs a fixed set of cases through WHICHEVER build of the library
 LLCOMP_MI_LIB names and prints one JSON line {case: [container FNV-1a-64, decoded-pixels FNV-1a-64]}.
 
-    python tests/helpers/guard_child.py cases     the stress set (general + one-row path) and the 4K goldens' slicing
+    python tests/helpers/guard_child.py cases     the stress set (general + one-row path), mosaics of crafted tiles whose carries travel
+                                                  through long runs of undecided bytes, and the 4K goldens' slicing
     python tests/helpers/guard_child.py refuse    one encode that the build must refuse (prints the status)
 """
 import json
@@ -50,6 +51,25 @@ def main():
             px = mi.decompress_image(s).pixels
             assert np.array_equal(px, img), f"round trip {seed} {tw}x{th}"
             out[f"s{seed}-{tw}x{th}{'p' if planar else 'i'}"] = [fnv(mi, s), fnv(mi, px.tobytes())]
+    # long runs of undecided 0xFF bytes (tests/carry_streams.py: crafted tiles in turn; one-row slices, 64x64 tiles, tiles of 6144 samples
+    # through the segmented coder): the carry subroutine of the blocks and the walk into HBM behind it against hipcc's walk
+    import carry_streams as cs
+    import orc as orc_mod
+
+    orc = orc_mod.Orc()
+    for name, (img, tw, th, _), shift in (("rows", cs.rows_mosaic(orc, 3, 3), None), ("64x64", cs.tiles_mosaic(orc, 64, 64, 3, 1), None),
+                                          ("128x48", cs.segmented_mosaic(orc, 128, 48, 3), "6")):
+        if shift:  # (so few tiles would get a wavefront each and their tables in LDS, another encoder: the lane-group width is forced)
+            os.environ["LLCOMP_MI_LANE_SHIFT"] = shift
+            mi.reload_tuning()
+        h, w, c = img.shape
+        s = mi.compress_image(img, w, h, c, format=mi.FORMAT_SLICED, tile_w=tw, tile_h=th, planar=True)
+        px = mi.decompress_image(s).pixels
+        assert np.array_equal(px, img), f"round trip carry-{name}"
+        out[f"carry-{name}-{tw}x{th}p"] = [fnv(mi, s), fnv(mi, px.tobytes())]
+        if shift:
+            del os.environ["LLCOMP_MI_LANE_SHIFT"]
+            mi.reload_tuning()
     for gen in ("g3", "mid", "nat"):  # the benchmarked slicing at full size: 4K, planar 480x1
         img = synth.GENERATORS[gen](3840, 2160, 3)
         s = mi.compress_image(img, 3840, 2160, 3, format=mi.FORMAT_SLICED, tile_w=480, tile_h=1, planar=True)

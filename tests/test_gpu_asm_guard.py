@@ -33,7 +33,8 @@ def run_child(lib, what):
 
 @pytest.mark.gpu
 def test_hand_written_blocks_equal_hipcc_code():
-    """120 sliced containers (one-row slices planar and interleaved, 2-D tiles) of random shapes and the three 4K contents at
+    """120 sliced containers (one-row slices planar and interleaved, 2-D tiles) of random shapes, three mosaics of crafted tiles whose
+    carries travel through 17 to 64 undecided bytes (tests/carry_streams.py) and the three 4K contents at
     the benchmarked slicing: containers AND decoded pixels of the product build == those of the build without the blocks;
     the 4K containers also against the golden hashes from the real reference."""
     asm = run_child("libllcomp_mi.so", "cases")

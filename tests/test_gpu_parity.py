@@ -470,7 +470,9 @@ def test_carries_through_ff_runs_match_oracle(mi, orc):
     """The encoder propagates carries eagerly into bytes it has already written (LDS ring, or its units in HBM behind
     the last 16-byte flush) where the reference resolves a held run lazily (llcomp.hpp:40-57).  Noise makes both happen
     thousands of times: the oracle counts its carries through 0xFF runs for this very input, the containers must agree
-    byte for byte, and a run of 2+ bytes plus the number of events make a flush-boundary crossing certain."""
+    byte for byte, and a run of 2+ bytes plus the number of events make a flush-boundary crossing certain.  (Noise never holds back
+    more than a few bytes; carries through runs of 17 to 64, runs that stay FF, runs open at the end of a slice or across the launches
+    of the segmented coder: test_gpu_carry_runs.py, on tiles crafted for it.)"""
     img = make_image("g3", 1920, 1080, 3)
     # (64x64 and 32x32 tiles: the same through the 2-D encoder, whose hand-written sample is the snapshot form of the block)
     for tw, th, planar in ((480, 1, True), (1920, 1, False), (64, 64, True), (32, 32, False)):
