@@ -399,102 +399,165 @@ __device__ __forceinline__ void load_group_streams(const Geometry& g, uint32_t g
 // 256 / kChunkDwords slices per pass.
 constexpr uint32_t kRunThreads = kChunkDwords, kRunsPerPass = 256 / kChunkDwords, kChunkBytes = kChunkDwords * 4, kChunkUnits = kChunkDwords / 4;
 static_assert(kChunkUnits % 4 == 0 && kChunkDwords % 4 == 0 && 256 % kChunkDwords == 0, "thread layouts of pack / stage");
+// Chunks per load batch of k_pack_payload / k_stage_streams: one memory round trip moves that many times 128 bytes of every
+// slice of the group, held in registers (pack: 2 uint4, stage: 8 dwords per thread and chunk).  A helper wave of up to 64
+// VGPRs displaces one coder wave beside the slice kernels, one of 65..128 displaces two: 4 is the largest of 2 / 4 / 6 that
+// stays within 64 (pack 54, stage 57; 6: 70 and 73, and slower on the headline than no batches at all --
+// profiles/r08_helper_round_trips_ab.txt).  -DLLMI_PACK_BATCH=n / -DLLMI_STAGE_BATCH=n build the other sizes for an A/B.
+#ifndef LLMI_PACK_BATCH
+#define LLMI_PACK_BATCH 4
+#endif
+#ifndef LLMI_STAGE_BATCH
+#define LLMI_STAGE_BATCH 4
+#endif
+static_assert(LLMI_PACK_BATCH >= 1 && LLMI_STAGE_BATCH >= 1, "chunks per load batch");
 __global__ __launch_bounds__(256) void k_pack_payload(const Geometry g, const uint4* __restrict__ units,
                                                       const uint32_t* __restrict__ slice_len,
                                                       const uint64_t* __restrict__ off, uint8_t* __restrict__ payload,
                                                       uint64_t payload_cap, uint32_t* status) {
+    constexpr int kBatchChunks = LLMI_PACK_BATCH;
     __shared__ uint32_t tile[64][kChunkDwords + 1];
     __shared__ GroupStreams gs;
     const uint32_t group = blockIdx.x;
-    load_group_streams(g, group, slice_len, off, payload_cap, status, kStOverflow, gs);
     const uint32_t cap16 = g.slice_cap >> 4;
-    const uint32_t a = threadIdx.x & 63, b = threadIdx.x >> 6;
+    // (b is the same for a whole wavefront: told to the compiler, the row addresses of the unit loads are scalar)
+    const uint32_t a = threadIdx.x & 63, b = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t dw = threadIdx.x % kRunThreads, jb = threadIdx.x / kRunThreads;
-    // 1 KiB rows of units.  All loads of a thread are in flight before the first is stored (see k_model_rows_inv),
-    // and the loads of the NEXT chunk are issued before this chunk's stores: they fly during the store phase.
+    // 1 KiB rows of units, a BATCH of chunks per memory round trip: all unit loads of a batch are in flight before the first
+    // is stored, and the loads of the NEXT batch are issued behind the last LDS write of this one, so they fly during its
+    // store phase.  The LDS tile stays one chunk.
     constexpr int LPT = kChunkUnits / 4;  // units per thread and chunk
-    uint4 v[LPT];
-    auto request = [&](uint32_t c0) {
+    uint4 v[kBatchChunks][LPT];
+    // The FIRST batch does not wait for the lengths: the unit addresses do not depend on them, so it is requested in front of
+    // load_group_streams and shares its round trip.  Its loads carry no condition (nothing for a wait to merge over): the unit
+    // index is clamped to cap16 - 1 and the lane to the group's width, so every address lies inside this group's
+    // cap16 << lane_shift units of the workspace, which is allocated for whole lane groups.  Units beyond max_len, and the
+    // clamped duplicates, are loaded and dropped: the store phase below takes only bytes below len[j] <= slice_cap - 16.
+    const uint32_t al = a & ((1u << g.lane_shift) - 1);
+    auto request = [&](uint32_t c0, uint32_t limit) {  // the chunks of the batch at c0 that begin below `limit` bytes
 #pragma unroll
-        for (int t = 0; t < LPT; ++t) {
-            const uint32_t u = c0 * kChunkUnits + b + 4 * t;
-            v[t] = make_uint4(0, 0, 0, 0);
-            if (u < cap16 && a < (1u << g.lane_shift)) v[t] = units[((size_t(group) * cap16 + u) << g.lane_shift) + a];
-        }
-    };
-    if (gs.max_len) request(0);
-    for (uint32_t c0 = 0; c0 * kChunkBytes < gs.max_len; ++c0) {
+        for (int i = 0; i < kBatchChunks; ++i) {
+            if ((c0 + i) * kChunkBytes >= limit) break;  // (uniform)
 #pragma unroll
-        for (int t = 0; t < LPT; ++t) {
-            const uint32_t uu = b + 4 * t;
-            tile[a][uu * 4 + 0] = v[t].x; tile[a][uu * 4 + 1] = v[t].y; tile[a][uu * 4 + 2] = v[t].z; tile[a][uu * 4 + 3] = v[t].w;
-        }
-        __syncthreads();
-        if ((c0 + 1) * kChunkBytes < gs.max_len) request(c0 + 1);
-        for (uint32_t j = jb; j < 64; j += kRunsPerPass) {  // runs of one slice
-            const uint32_t n = gs.len[j], p = c0 * kChunkBytes + dw * 4;
-            if (p < n) {
-                uint8_t* dst = payload + gs.off[j] + p;
-                const uint32_t w = tile[j][dw];
-                if (p + 4 <= n) {
-                    __builtin_memcpy(dst, &w, 4);  // byte offset of a slice is arbitrary: unaligned dword store
-                } else {
-                    for (uint32_t i = 0; i < n - p; ++i) dst[i] = uint8_t(w >> (8 * i));
-                }
+            for (int t = 0; t < LPT; ++t) {
+                const uint32_t u = min((c0 + i) * kChunkUnits + b + 4 * t, cap16 - 1);
+                v[i][t] = (units + ((size_t(group) * cap16 + u) << g.lane_shift))[al];
             }
         }
-        __syncthreads();
+    };
+    request(0, g.slice_cap);
+    load_group_streams(g, group, slice_len, off, payload_cap, status, kStOverflow, gs);
+    const uint32_t max_len = gs.max_len;
+    for (uint32_t c0 = 0; c0 * kChunkBytes < max_len; c0 += kBatchChunks) {
+#pragma unroll
+        for (int i = 0; i < kBatchChunks; ++i) {
+            const uint32_t c = c0 + i;
+            if (c * kChunkBytes >= max_len) break;  // (uniform)
+#pragma unroll
+            for (int t = 0; t < LPT; ++t) {
+                const uint32_t uu = b + 4 * t;
+                tile[a][uu * 4 + 0] = v[i][t].x; tile[a][uu * 4 + 1] = v[i][t].y; tile[a][uu * 4 + 2] = v[i][t].z; tile[a][uu * 4 + 3] = v[i][t].w;
+            }
+            __syncthreads();
+            // every register of the batch is in LDS or stored: request the next batch, clipped to max_len
+            if (i == kBatchChunks - 1) request(c0 + kBatchChunks, max_len);
+            for (uint32_t j = jb; j < 64; j += kRunsPerPass) {  // runs of one slice
+                const uint32_t n = gs.len[j], p = c * kChunkBytes + dw * 4;
+                if (p < n) {
+                    uint8_t* dst = payload + gs.off[j] + p;
+                    const uint32_t w = tile[j][dw];
+                    if (p + 4 <= n) {
+                        __builtin_memcpy(dst, &w, 4);  // byte offset of a slice is arbitrary: unaligned dword store
+                    } else {  // the last one to three bytes of the slice
+                        const uint32_t r = n - p;
+                        if (r >= 2) {
+                            const uint16_t h = uint16_t(w);
+                            __builtin_memcpy(dst, &h, 2);
+                        }
+                        if (r & 1) dst[r - 1] = uint8_t(w >> (8 * (r - 1)));
+                    }
+                }
+            }
+            __syncthreads();
+        }
     }
 }
 
 // packed payload -> stream lane order (before the decoder)
+// true: the partial last dword of the stream (n bytes at `off`) cannot be read as a whole dword, the payload ends inside it
+__device__ __forceinline__ bool stage_tail(unsigned long long off, uint32_t n, unsigned long long payload_bytes) {
+    return (n & 3) && off + (n & ~3u) + 4 > payload_bytes;
+}
 __global__ __launch_bounds__(256) void k_stage_streams(const Geometry g, const uint8_t* __restrict__ payload,
                                                        uint64_t payload_bytes, const uint32_t* __restrict__ slice_len,
                                                        const uint64_t* __restrict__ off, uint4* __restrict__ units,
                                                        uint32_t* status) {
+    constexpr int kBatchChunks = LLMI_STAGE_BATCH;
     __shared__ uint32_t tile[64][kChunkDwords + 1];
     __shared__ GroupStreams gs;
     const uint32_t group = blockIdx.x;
     load_group_streams(g, group, slice_len, off, payload_bytes, status, kStTruncated, gs);
     const uint32_t capdw = g.slice_cap >> 2;
-    const uint32_t a = threadIdx.x & 63, b = threadIdx.x >> 6;
+    const uint32_t a = threadIdx.x & 63, b = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (b: uniform, scalar store rows)
     const uint32_t dwi = threadIdx.x % kRunThreads, jb = threadIdx.x / kRunThreads;
     // "+ 4": the dword right behind every stream is staged too (as zeros) -- the decoder clamps its reads to it.
-    // All loads of a thread are in flight before the first is stored, and the loads of the NEXT chunk are issued
-    // before this chunk's stores.  The last, partial dword of a stream is read as a whole dword and masked wherever the
-    // payload has the bytes (always, except at its very end).
+    // A BATCH of chunks per memory round trip, as in k_pack_payload: all loads of a batch are in flight before the first is
+    // stored, and the loads of the NEXT batch are issued behind the last LDS write of this one.  The last, partial dword of a
+    // stream is read as a whole dword and masked wherever the payload has the bytes (always, except at its very end).
     constexpr int LPT = 64 / kRunsPerPass;  // slices per thread and chunk
-    uint32_t w[LPT];
+    const uint32_t bound = gs.max_len + 4;
+    uint32_t w[kBatchChunks][LPT];
+    // A thread reads the same dword column of the same LPT slices in every chunk: one address per slice and batch, the chunks
+    // of the batch at constant offsets from it (nothing about a slice stays in registers between batches).  nl = the slice's
+    // length as far as whole dwords may be read: the length itself, or without its partial last dword where the payload ends
+    // less than four bytes behind that dword's start (stage_tail).
+    uint32_t tails = 0;  // bit t: slice t of this thread has such a last dword (one slice of the whole payload, or none)
+#pragma unroll
+    for (int t = 0; t < LPT; ++t) tails |= uint32_t(stage_tail(gs.off[jb + kRunsPerPass * t], gs.len[jb + kRunsPerPass * t], payload_bytes)) << t;
     auto request = [&](uint32_t c0) {
 #pragma unroll
         for (int t = 0; t < LPT; ++t) {
-            const uint32_t j = jb + kRunsPerPass * t, n = gs.len[j], p = c0 * kChunkBytes + dwi * 4;
-            w[t] = 0;
-            if (p < n) {
-                const unsigned long long at = gs.off[j] + p;
-                const uint8_t* src = payload + at;
-                if (at + 4 <= payload_bytes) __builtin_memcpy(&w[t], src, 4);
-                else w[t] = load_bytes_le(src, n - p);
+            const uint32_t j = jb + kRunsPerPass * t, n = gs.len[j], nl = (tails >> t) & 1 ? n & ~3u : n;
+            const uint32_t p0 = c0 * kChunkBytes + dwi * 4;
+            const uint8_t* const src = payload + gs.off[j] + p0;
+#pragma unroll
+            for (int i = 0; i < kBatchChunks; ++i) {
+                w[i][t] = 0;
+                if (p0 + i * kChunkBytes < nl) __builtin_memcpy(&w[i][t], src + i * kChunkBytes, 4);
             }
         }
     };
     request(0);
-    for (uint32_t c0 = 0; c0 * kChunkBytes < gs.max_len + 4; ++c0) {
+    for (uint32_t c0 = 0; c0 * kChunkBytes < bound; c0 += kBatchChunks) {
 #pragma unroll
-        for (int t = 0; t < LPT; ++t) {  // (the mask is applied here, not above: nothing waits for a load before all are issued)
-            const uint32_t j = jb + kRunsPerPass * t, n = gs.len[j], p = c0 * kChunkBytes + dwi * 4;
-            const uint32_t keep = n >= p + 4 ? 0xFFFFFFFFu : n > p ? 0xFFFFFFFFu >> (8 * (p + 4 - n)) : 0u;
-            tile[j][dwi] = w[t] & keep;
+        for (int i = 0; i < kBatchChunks; ++i) {
+            const uint32_t c = c0 + i;
+            if (c * kChunkBytes >= bound) break;  // (uniform)
+#pragma unroll
+            for (int t = 0; t < LPT; ++t) {  // (the mask is applied here, not above: nothing waits for a load before all are issued)
+                const uint32_t j = jb + kRunsPerPass * t, n = gs.len[j], p = c * kChunkBytes + dwi * 4;
+                const uint32_t keep = n >= p + 4 ? 0xFFFFFFFFu : n > p ? 0xFFFFFFFFu >> (8 * (p + 4 - n)) : 0u;
+                tile[j][dwi] = w[i][t] & keep;
+            }
+            // The byte-wise tail at the very end of the payload: at most three bytes, which no batch has requested.  Its loads
+            // wait for one another, so it stays out of the straight-line code: the common path has no wait between its loads.
+            if (tails) {
+#pragma unroll 1
+                for (uint32_t t = 0; t < uint32_t(LPT); ++t) {
+                    const uint32_t j = jb + kRunsPerPass * t, n = gs.len[j], p = c * kChunkBytes + dwi * 4;
+                    if (((tails >> t) & 1) && p < n && p + 4 > n) tile[j][dwi] = load_bytes_le(payload + gs.off[j] + p, n - p);
+                }
+            }
+            __syncthreads();
+            if (i == kBatchChunks - 1 && (c0 + kBatchChunks) * kChunkBytes < bound) request(c0 + kBatchChunks);
+            // DWORD lane order for the decoder, [group][dword k][lane]: a wavefront stores one 256-byte row per dword index
+            uint32_t* const dw = reinterpret_cast<uint32_t*>(units);
+            for (uint32_t kk = b; kk < kChunkDwords; kk += 4) {
+                const uint32_t k = c * kChunkDwords + kk;
+                if (k < capdw && a < (1u << g.lane_shift)) (dw + ((size_t(group) * capdw + k) << g.lane_shift))[a] = tile[a][kk];
+            }
+            __syncthreads();
         }
-        __syncthreads();
-        if ((c0 + 1) * kChunkBytes < gs.max_len + 4) request(c0 + 1);
-        // DWORD lane order for the decoder, [group][dword k][lane]: a wavefront stores one 256-byte row per dword index
-        uint32_t* const dw = reinterpret_cast<uint32_t*>(units);
-        for (uint32_t kk = b; kk < kChunkDwords; kk += 4) {
-            const uint32_t k = c0 * kChunkDwords + kk;
-            if (k < capdw && a < (1u << g.lane_shift)) dw[((size_t(group) * capdw + k) << g.lane_shift) + a] = tile[a][kk];
-        }
-        __syncthreads();
     }
 }
 // region decode: the covered slices of the full payload -> the sub-geometry's stream lane order.  k_stage_streams with one offset
@@ -944,8 +1007,8 @@ __global__ __launch_bounds__(256) void k_model_rows_inv(const Geometry g, const 
     load_row_tiles<C>(g, first_tile, ntiles, tiles);
     // LDS column = lane index relative to this group (0..gw-1), columns gw.. = first C-1 lanes of the NEXT group.
     // Rows of this group are read as whole 128-byte pieces (32 dwords = 64 samples); the few extra lanes one by one.
-    {   // (all eight loads of a thread are in flight before the first one is stored to LDS: the kernel is bound by the
-        // latency of its phases, one memory round trip per block instead of eight)
+    {   // (all loads of a thread, the eight row pieces and its one extra lane sample, are in flight before the first one is
+        // stored to LDS: the kernel is bound by the latency of its phases, one memory round trip per block)
         uint32_t w[K * 32 / 256];
 #pragma unroll
         for (int it = 0; it < K * 32 / 256; ++it) {
@@ -954,24 +1017,27 @@ __global__ __launch_bounds__(256) void k_model_rows_inv(const Geometry g, const 
             if (k < g.tile_w && g.lane_shift == 6)
                 w[it] = *reinterpret_cast<const uint32_t*>(lanes + lane_order_index(g, first_id + 2 * d, k));
         }
+        static_assert(K * (C - 1) <= 256, "one extra lane sample per thread");
+        const uint32_t xk = threadIdx.x / (C > 1 ? C - 1 : 1), xe = threadIdx.x - xk * (C - 1);  // extra lane xe of sample k0 + xk
+        int16_t x = 0;
+        if constexpr (C > 1) {
+            const uint32_t id = first_id + gw + xe;
+            if (xk < uint32_t(K) && id < g.n_slices && k0 + xk < g.tile_w) x = lanes[lane_order_index(g, id, k0 + xk)];
+        }
 #pragma unroll
         for (int it = 0; it < K * 32 / 256; ++it) {
             const uint32_t i = threadIdx.x + 256 * it, kk = i >> 5, d = i & 31;
             *reinterpret_cast<uint32_t*>(&tile[kk][2 * d]) = w[it];
         }
-    }
-    if (g.lane_shift != 6) {  // fewer than 64 slices in total: narrow group, plain element loads
-        __syncthreads();
-        for (uint32_t i = threadIdx.x; i < uint32_t(K) * gw; i += 256) {
-            const uint32_t kk = i / gw, col = i - kk * gw, k = k0 + kk;
-            tile[kk][col] = (first_id + col < g.n_slices && k < g.tile_w) ? lanes[lane_order_index(g, first_id + col, k)] : int16_t(0);
+        if (g.lane_shift != 6) {  // fewer than 64 slices in total: narrow group, plain element loads
+            __syncthreads();
+            for (uint32_t i = threadIdx.x; i < uint32_t(K) * gw; i += 256) {
+                const uint32_t kk = i / gw, col = i - kk * gw, k = k0 + kk;
+                tile[kk][col] = (first_id + col < g.n_slices && k < g.tile_w) ? lanes[lane_order_index(g, first_id + col, k)] : int16_t(0);
+            }
         }
-    }
-    if constexpr (C > 1) {
-        for (uint32_t i = threadIdx.x; i < uint32_t(K) * (C - 1); i += 256) {
-            const uint32_t kk = i / (C - 1), e = i - kk * (C - 1), k = k0 + kk;
-            const uint32_t id = first_id + gw + e;
-            tile[kk][gw + e] = (id < g.n_slices && k < g.tile_w) ? lanes[lane_order_index(g, id, k)] : int16_t(0);
+        if constexpr (C > 1) {
+            if (xk < uint32_t(K)) tile[xk][gw + xe] = x;
         }
     }
     __syncthreads();
