@@ -340,7 +340,17 @@ int llcomp_mi_plan_chunks(uint32_t height, uint32_t tile_h, uint32_t n_parts, ui
 /* ---- device-resident batch codec: buffers stay in HBM, work is enqueued on the caller's stream --------- */
 /* One codec object = fixed geometry (frames x h x w x c, tiling) + its own workspace on one device.
  * `frames` images of identical shape are coded per call; every frame gets the slices of the SLICED format
- * (slice ids run frame-major).  All device pointers are hipMalloc'ed (or torch) memory on that device.  */
+ * (slice ids run frame-major).  All device pointers are hipMalloc'ed (or torch) memory on that device.
+ *
+ * Alignment of the device pointers.
+ *   Any byte address: pixels in and out (d_px, d_rect), payloads in and out (d_payload, d_sub_payload, d_payload_out), and both byte
+ *     ranges of llcomp_mi_device_copy_segments.  A frame of a batch, a payload inside a container in HBM (24 + 4n bytes in) or a piece
+ *     of a receive buffer is passed as it lies.
+ *   Natural alignment: d_slice_len, d_sub_len, d_slice_len_out, d_status and d_sym 4 bytes; d_total and d_sub_total 8 bytes; the u64
+ *     tables of llcomp_mi_device_copy_segments / _range_sums 8 bytes (d_vals 4); a float output of the _ex calls its element size.
+ *     A pointer of this kind that is not aligned is LLCOMP_MI_BAD_ARGS before anything is launched or written.
+ *   Bounds: a call reads nothing outside [d_payload, d_payload + payload_bytes) and the frames*h*w*c bytes of its pixels, and writes
+ *     nothing outside [d_payload, d_payload + payload_cap) and the frames*rh*rw*c (h*w*c, oh*ow*c) bytes of its output. */
 typedef struct llcomp_mi_codec llcomp_mi_codec;
 int llcomp_mi_codec_create(llcomp_mi_codec** codec, int32_t device, uint32_t frames, uint32_t w, uint32_t h,
                            uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar);
@@ -498,8 +508,9 @@ int llcomp_mi_codec_decode_resized_regions_host_ex(llcomp_mi_codec* codec, const
 int llcomp_mi_codec_model(llcomp_mi_codec* codec, const void* d_px, void* d_sym, void* stream);
 /* Device-side concatenator (multi-GPU sharding: the gathering rank interleaves the ranks' packed payloads into image
  * order): copies n_seg byte ranges src[src_off[i] .. +len[i]) -> dst[dst_off[i] .. +len[i]) in one launch.  All five
- * pointers are device memory (offsets / lengths: u64[n_seg], computed on the GPU); any alignment; ranges must not overlap.
- * max_len = an upper bound of the lengths (sizes the grid only); n_seg <= 65535.  Asynchronous on `stream`. */
+ * pointers are device memory (offsets / lengths: u64[n_seg], computed on the GPU, 8-byte aligned); the byte ranges have any alignment
+ * and must not overlap.  max_len = an upper bound of the lengths (sizes the grid only: the bytes copied do not depend on it);
+ * n_seg <= 65535 (0: nothing is done; more: BAD_ARGS, nothing is launched).  Asynchronous on `stream`. */
 int llcomp_mi_device_copy_segments(const void* d_src, void* d_dst, const void* d_src_off, const void* d_dst_off,
                                    const void* d_len, uint32_t n_seg, uint64_t max_len, void* stream);
 /* Sums over ranges of a u32 table in HBM: d_out[i] (u64) = sum of min(d_vals[j], cap) for j in [d_start[i], d_start[i] + d_count[i])

@@ -72,6 +72,12 @@ namespace {
 
 #define HIP_TRY(expr) LLMI_HIP_TRY(expr)
 
+// The caller's tables and result words are read and written as what they are declared to be (u32 / u64 loads and stores, atomics on the
+// status word): a pointer of that kind that does not have its type's alignment is BAD_ARGS before anything is launched or written
+// (include/llcomp_mi.h, "Alignment of the device pointers").  Pixels, payloads and d_rect may sit at any byte address.  NULL passes: the
+// calls that allow a NULL table check for it themselves.
+inline bool misaligned(const void* p, uintptr_t align) { return (reinterpret_cast<uintptr_t>(p) & (align - 1)) != 0; }
+
 // brackets a group of launches with two events when profiling is on
 struct Timed {
     llcomp_mi_codec* k;
@@ -928,7 +934,7 @@ uint64_t llcomp_mi_codec_max_payload_bytes(const llcomp_mi_codec* k) {
 }
 
 int llcomp_mi_codec_model(llcomp_mi_codec* k, const void* d_px, void* d_sym, void* stream) {
-    if (!k || !d_px || !d_sym) return LLCOMP_MI_BAD_ARGS;
+    if (!k || !d_px || !d_sym || misaligned(d_sym, 4)) return LLCOMP_MI_BAD_ARGS;
     DeviceGuard guard(k->device);
     if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
     HIP_TRY(launch_model_fwd(k->g, static_cast<const uint8_t*>(d_px), static_cast<uint32_t*>(d_sym),
@@ -939,6 +945,7 @@ int llcomp_mi_codec_model(llcomp_mi_codec* k, const void* d_px, void* d_sym, voi
 int llcomp_mi_codec_encode(llcomp_mi_codec* k, const void* d_px, void* d_payload, uint64_t payload_cap, void* d_slice_len,
                            void* d_total, void* d_status, void* stream) {
     if (!k || !d_px || !d_payload || !d_slice_len || !d_total || !d_status) return LLCOMP_MI_BAD_ARGS;
+    if (misaligned(d_slice_len, 4) || misaligned(d_total, 8) || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
     DeviceGuard guard(k->device);
     if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -955,6 +962,7 @@ int llcomp_mi_codec_encode(llcomp_mi_codec* k, const void* d_px, void* d_payload
 int llcomp_mi_codec_decode(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
                            void* d_px, void* d_status, void* stream) {
     if (!k || !d_payload || !d_slice_len || !d_px || !d_status) return LLCOMP_MI_BAD_ARGS;
+    if (misaligned(d_slice_len, 4) || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
     DeviceGuard guard(k->device);
     if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1010,6 +1018,7 @@ uint32_t llcomp_mi_codec_region_family(const llcomp_mi_codec* k, uint32_t x, uin
 int llcomp_mi_codec_decode_region(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len, uint32_t x,
                                   uint32_t y, uint32_t rw, uint32_t rh, void* d_px, void* d_status, void* stream) {
     if (!k || !d_payload || !d_slice_len || !d_px || !d_status) return LLCOMP_MI_BAD_ARGS;
+    if (misaligned(d_slice_len, 4) || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
     RegionBox box;
     Geometry sub;
     if (int rc = region_setup(k, x, y, rw, rh, box, sub)) return rc;
@@ -1135,6 +1144,7 @@ int llcomp_mi_codec_encode_region(llcomp_mi_codec* k, const void* d_payload, uin
                                   uint32_t y, uint32_t rw, uint32_t rh, const void* d_rect, void* d_sub_payload, uint64_t sub_payload_cap,
                                   void* d_sub_len, void* d_sub_total, void* d_status, void* stream) {
     if (!k || !d_rect || !d_sub_payload || !d_sub_len || !d_sub_total || !d_status) return LLCOMP_MI_BAD_ARGS;
+    if (misaligned(d_slice_len, 4) || misaligned(d_sub_len, 4) || misaligned(d_sub_total, 8) || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
     UpdatePlan p;
     if (int rc = update_setup(k, x, y, rw, rh, p)) return rc;
     if (!p.whole && (!d_payload || !d_slice_len)) return LLCOMP_MI_BAD_ARGS;
@@ -1159,6 +1169,7 @@ int llcomp_mi_codec_update_region(llcomp_mi_codec* k, const void* d_payload, uin
                                   uint32_t y, uint32_t rw, uint32_t rh, const void* d_rect, void* d_payload_out, uint64_t payload_cap,
                                   void* d_slice_len_out, void* d_total, void* d_status, void* stream) {
     if (!k || !d_rect || !d_payload_out || !d_slice_len_out || !d_total || !d_status) return LLCOMP_MI_BAD_ARGS;
+    if (misaligned(d_slice_len, 4) || misaligned(d_slice_len_out, 4) || misaligned(d_total, 8) || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
     UpdatePlan p;
     if (int rc = update_setup(k, x, y, rw, rh, p)) return rc;
     const Geometry& g = k->g;
@@ -1216,6 +1227,7 @@ uint32_t llcomp_mi_codec_regions_family(const llcomp_mi_codec* k, const uint32_t
 int llcomp_mi_codec_decode_regions(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
                                    const uint32_t* xy, uint32_t rw, uint32_t rh, void* d_px, void* d_status, void* stream) {
     if (!k || !d_payload || !d_slice_len || !d_px || !d_status || !xy) return LLCOMP_MI_BAD_ARGS;
+    if (misaligned(d_slice_len, 4) || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
     const Geometry& g = k->g;
     std::vector<RegionsFrame> tab(g.frames);
     RegionsClass classes[kRegionsClasses];
@@ -1251,7 +1263,7 @@ int llcomp_mi_codec_decode_regions(llcomp_mi_codec* k, const void* d_payload, ui
 // queued.
 int llcomp_mi_codec_decode_regions_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens, const uint32_t* xy, uint32_t rw,
                                         uint32_t rh, void* d_px, void* d_status, void* stream) {
-    if (!k || !data || !lens || !d_px || !d_status || !xy) return LLCOMP_MI_BAD_ARGS;
+    if (!k || !data || !lens || !d_px || !d_status || !xy || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
     const Geometry& g = k->g;
     RegionsGather p;
     if (int rc = regions_gather_plan(data, lens, g.frames, xy, rw, rh, p)) return rc;
@@ -1303,6 +1315,7 @@ int llcomp_mi_codec_decode_resized_regions_ex(llcomp_mi_codec* k, const void* d_
                                               const uint32_t* rects, const uint8_t* flags, uint32_t ow, uint32_t oh,
                                               const llcomp_mi_output_format* fmt, void* d_px, void* d_status, void* stream) {
     if (!k || !d_payload || !d_slice_len || !d_px || !d_status || !rects) return LLCOMP_MI_BAD_ARGS;
+    if (misaligned(d_slice_len, 4) || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
     const Geometry& g = k->g;
     ResizedPlan p;
     if (int rc = resized_setup(k, rects, flags, ow, oh, fmt, d_px, p)) return rc;
@@ -1349,7 +1362,7 @@ int llcomp_mi_codec_decode_resized_regions_ex(llcomp_mi_codec* k, const void* d_
 int llcomp_mi_codec_decode_resized_regions_host_ex(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens, const uint32_t* rects,
                                                    const uint8_t* flags, uint32_t ow, uint32_t oh, const llcomp_mi_output_format* fmt,
                                                    void* d_px, void* d_status, void* stream) {
-    if (!k || !data || !lens || !d_px || !d_status || !rects) return LLCOMP_MI_BAD_ARGS;
+    if (!k || !data || !lens || !d_px || !d_status || !rects || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
     const Geometry& g = k->g;
     ResizedPlan p;
     if (int rc = resized_setup(k, rects, flags, ow, oh, fmt, d_px, p)) return rc;
@@ -1418,6 +1431,7 @@ int llcomp_mi_device_copy_segments(const void* d_src, void* d_dst, const void* d
                                    uint32_t n_seg, uint64_t max_len, void* stream) {
     if (!n_seg) return LLCOMP_MI_OK;
     if (!d_src || !d_dst || !d_src_off || !d_dst_off || !d_len || n_seg > 65535) return LLCOMP_MI_BAD_ARGS;
+    if (misaligned(d_src_off, 8) || misaligned(d_dst_off, 8) || misaligned(d_len, 8)) return LLCOMP_MI_BAD_ARGS;  // (u64 tables; the bytes: any address)
     HIP_TRY(launch_copy_segments(static_cast<const uint8_t*>(d_src), static_cast<uint8_t*>(d_dst), static_cast<const uint64_t*>(d_src_off),
                                  static_cast<const uint64_t*>(d_dst_off), static_cast<const uint64_t*>(d_len), n_seg, max_len,
                                  static_cast<hipStream_t>(stream)));
@@ -1428,6 +1442,7 @@ int llcomp_mi_device_range_sums(const void* d_vals, const void* d_start, const v
                                 void* stream) {
     if (!n) return LLCOMP_MI_OK;
     if (!d_vals || !d_start || !d_count || !d_out) return LLCOMP_MI_BAD_ARGS;
+    if (misaligned(d_vals, 4) || misaligned(d_start, 8) || misaligned(d_count, 8) || misaligned(d_out, 8)) return LLCOMP_MI_BAD_ARGS;
     HIP_TRY(launch_range_sums(static_cast<const uint32_t*>(d_vals), static_cast<const uint64_t*>(d_start), static_cast<const uint64_t*>(d_count),
                               static_cast<uint64_t*>(d_out), n, cap, static_cast<hipStream_t>(stream)));
     return LLCOMP_MI_OK;
