@@ -35,7 +35,9 @@ extern "C" {
  * LLCOMP_MI_PREPARE_RESIZED, LLCOMP_MI_JOB_DECODE_RESIZED_REGIONS, llcomp_mi_codec_allocated_bytes; their output as a model takes it,
  * float or normalised, CHW or HWC -- llcomp_mi_output_format, llcomp_mi_output_table and the _ex forms of the three resized calls; region
  * update -- llcomp_mi_replace_slices(_into), llcomp_mi_update_region(_into), llcomp_mi_codec_encode_region,
- * llcomp_mi_codec_update_region, LLCOMP_MI_PREPARE_UPDATE).  The library and its callers are built from ONE header: structs have one layout per ABI version (llcomp_mi_opts is
+ * llcomp_mi_codec_update_region, LLCOMP_MI_PREPARE_UPDATE; several views of each frame, each frame decoded once -- llcomp_mi_view,
+ * llcomp_mi_view_group, llcomp_mi_views_plan, llcomp_mi_codec_decode_views(_host), llcomp_mi_codec_views_workspace_bytes,
+ * LLCOMP_MI_PREPARE_VIEWS).  The library and its callers are built from ONE header: structs have one layout per ABI version (llcomp_mi_opts is
  * checked through struct_size and refused when it differs; llcomp_mi_info and llcomp_mi_stream_result are written in full),
  * so a binding compares llcomp_mi_abi_version() with the LLCOMP_MI_ABI_VERSION it was generated from and refuses to run on
  * a mismatch -- there is no cross-version compatibility mode. */
@@ -311,6 +313,35 @@ typedef struct llcomp_mi_output_format {
  * patterns).  BAD_ARGS for a NULL fmt or table, c = 0 or above 255, a struct_size below the struct's, an unknown dtype or layout, a scale
  * above 1, U8 with scale, mean or std set, a mean that is not finite, a std that is 0 or not finite.  Host-only. */
 int llcomp_mi_output_table(const llcomp_mi_output_format* fmt, uint32_t c, void* table);
+/* Several views of each frame in one call (llcomp_mi_codec_decode_views below; multi-crop and two-view training).  A VIEW is a rectangle
+ * of one frame with the per-frame flags byte of the resized calls (bit 0 mirror, bits 4-6 the filter); a VIEW GROUP is a list of views
+ * that share one output: ow x oh, an output format (NULL = U8 HWC) and a device pointer, written dense in view order as
+ * [n_views][oh][ow][c] (CHW: [n_views][c][oh][ow]).  A frame may have any number of views across the groups of a call, including none. */
+typedef struct llcomp_mi_view {
+    uint32_t frame;        /* the frame of the batch the view is cut from */
+    uint32_t x, y, rw, rh; /* its rectangle */
+    uint32_t flags;        /* the flags byte of the resized calls (LLCOMP_MI_FLAG_MIRROR, LLCOMP_MI_FLAG_FILTER); bits above 7 are ignored */
+} llcomp_mi_view; /* 24 bytes */
+typedef struct llcomp_mi_view_group {
+    uint32_t struct_size;               /* = sizeof(llcomp_mi_view_group); also the stride of an array of groups */
+    uint32_t n_views;                   /* 1 .. 65535 */
+    const llcomp_mi_view* views;        /* HOST memory, read during the call only */
+    uint32_t ow, oh;                    /* the output shape of every view of the group */
+    const llcomp_mi_output_format* fmt; /* NULL = U8 HWC; read during the call only */
+    void* d_out;                        /* device memory, aligned to the format's element size (llcomp_mi_views_plan does not read it) */
+} llcomp_mi_view_group; /* 40 bytes on LP64 */
+/* What a views decode of these groups decodes: per frame the UNION rectangle (bounding box) of the frame's views over all groups ->
+ * unions[4f .. 4f + 3] = {x, y, rw, rh}, or four zeros for a frame without a view; from the union rectangles of the USED frames alone,
+ * in frame order, the windows and classes exactly as llcomp_mi_resized_regions_plan gives them for those rectangles -> windows[4f .. 4f + 3]
+ * (four zeros for an unused frame), *n_used and *n_classes.  A frame decodes its window ONCE however many views it has -- and it decodes
+ * everything inside the bounding box: a frame with two small views far apart decodes all that lies between them.  unions and windows
+ * hold 4 * frames values each and may be NULL.  BAD_ARGS, with every output untouched: no groups, a NULL groups / n_used / n_classes, a
+ * struct_size that is not the struct's, a group with no views, more than 65535 views, a NULL views or ow or oh 0; a view whose frame is
+ * >= frames; a rectangle empty or outside the image; a filter code of 6 or 7 in a view's flags; a downscale above the view's filter's
+ * limit for its group's output on either axis (llcomp_mi_resize_filter_weights).  Host-only. */
+int llcomp_mi_views_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar, uint32_t frames,
+                         const llcomp_mi_view_group* groups, uint32_t n_groups, uint32_t* unions, uint32_t* windows, uint32_t* n_used,
+                         uint32_t* n_classes);
 uint32_t llcomp_mi_slice_count(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar);
 /* Slice width for one-row slices (tile_h = 1) when `frames` frames are coded per call: the widest slice (64..480 pixels) that
  * still keeps about four wavefronts per SIMD busy.  A call that codes few frames is latency-bound with wide slices; this
@@ -374,7 +405,8 @@ uint32_t llcomp_mi_codec_kernel_family(const llcomp_mi_codec* codec);
  * codec stays below this figure; that first call can return LLCOMP_MI_NOMEM. */
 uint64_t llcomp_mi_codec_workspace_bytes(const llcomp_mi_codec* codec);
 /* Diagnostic: the device bytes the codec holds right now (what the calls so far have allocated; never above
- * llcomp_mi_codec_workspace_bytes, except through a resized regions decode to an output larger than the image). */
+ * llcomp_mi_codec_workspace_bytes, except through a resized regions decode to an output larger than the image, or a views decode of
+ * more views than frames: llcomp_mi_codec_views_workspace_bytes). */
 uint64_t llcomp_mi_codec_allocated_bytes(const llcomp_mi_codec* codec);
 /* Allocates NOW what the first encode (LLCOMP_MI_PREPARE_ENCODE: the 2-D encoder's snapshot arrays, or its state tables) and / or
  * the first decode (LLCOMP_MI_PREPARE_DECODE: the state tables of 2-D slices) would otherwise allocate inside the call -- for callers
@@ -386,6 +418,8 @@ uint64_t llcomp_mi_codec_allocated_bytes(const llcomp_mi_codec* codec);
 #define LLCOMP_MI_PREPARE_REGIONS 16u /* ... and the per-frame table of a regions decode (32 B per frame in HBM, a pinned staging ring) */
 #define LLCOMP_MI_PREPARE_RESIZED 32u /* ... and the boxes and the horizontal pass's rows of a resized regions decode (frames * w * h * c bytes each) */
 #define LLCOMP_MI_PREPARE_UPDATE 64u /* ... and a region update's offset arrays (8 B per slice) and its box pixel buffer (frames * w * h * c bytes) */
+#define LLCOMP_MI_PREPARE_VIEWS 128u /* ... what LLCOMP_MI_PREPARE_RESIZED allocates, and the staging buffer for the tables of a views decode
+                                        from HBM of up to `frames` views (a _host call's staged payload and more views grow it) */
 int llcomp_mi_codec_prepare(llcomp_mi_codec* codec, uint32_t what);
 /* Upper bound on the packed payload bytes the codec can emit for any input (13 B per sample + slack). */
 uint64_t llcomp_mi_codec_max_payload_bytes(const llcomp_mi_codec* codec);
@@ -503,6 +537,35 @@ int llcomp_mi_codec_decode_resized_regions_ex(llcomp_mi_codec* codec, const void
 int llcomp_mi_codec_decode_resized_regions_host_ex(llcomp_mi_codec* codec, const uint8_t* const* data, const size_t* lens, const uint32_t* rects,
                                                    const uint8_t* flags, uint32_t ow, uint32_t oh, const llcomp_mi_output_format* fmt,
                                                    void* d_out, void* d_status, void* stream);
+/* Several views of each frame, each frame decoded ONCE (llcomp_mi_view / llcomp_mi_view_group / llcomp_mi_views_plan above): every
+ * used frame decodes the window of its views' union rectangle -- the classes of llcomp_mi_codec_decode_resized_regions, unchanged, over the
+ * used frames only, sized for the largest union, each cutting its frame's box into a buffer of the codec; a frame without a view has no
+ * table entry and none of its slices is read.  Then, group by group, the two resample kernels read every view's rectangle from ITS
+ * FRAME's box and write the group's d_out: view v of a group gets byte for byte what llcomp_mi_codec_decode_resized_regions_ex writes for
+ * that rectangle of that frame with the view's flags and the group's ow, oh and fmt (a view's bytes do not depend on the box it is read
+ * from: no tap leaves the rectangle).  d_payload / payload_bytes / d_slice_len are the full batch's.  Asynchronous on `stream`; d_status
+ * and the verdicts as for llcomp_mi_codec_decode_resized_regions on the union rectangles of the used frames (damage outside every
+ * window, and anywhere in an unused frame, is never seen).  BAD_ARGS, before anything is queued or written (d_status untouched): a NULL
+ * codec, payload, table or status, a misaligned d_slice_len or d_status, every case of llcomp_mi_views_plan, a bad output format
+ * (llcomp_mi_output_table), and a group's d_out NULL or not aligned to its element size.  The regions table, every group's view table,
+ * the weights (an axis that several views share is computed and sent once per call) and the output tables cross in the call's ONE copy
+ * from the pinned ring.  Memory: the boxes take used frames * union_w_max * union_h_max * c bytes, never above frames * w * h * c; the
+ * horizontal pass's rows of a group take n_views * rh_max * ow * c bytes (rh_max: the group's largest view height), and where that passes
+ * frames * w * h * c the group is resampled in chunks of views, so the rows' buffer never grows past that bound for ow <= w (one view
+ * always fits).  Profile slots and n_decode as for one resized regions decode. */
+int llcomp_mi_codec_decode_views(llcomp_mi_codec* codec, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                 const llcomp_mi_view_group* groups, uint32_t n_groups, void* d_status, void* stream);
+/* ... from HOST containers, as llcomp_mi_codec_decode_resized_regions_host: data[f] / lens[f] for f < frames, and only the union windows'
+ * bytes cross PCIe, in the same one copy as the tables (LLCOMP_MI_CTR_HOST_STAGED_BYTES counts them: what the resized call stages for the
+ * union rectangles).  data[f] of a frame without a view may be NULL and is never read; a NULL container of a used frame is BAD_ARGS.  Same
+ * bytes and status as the call above on the same containers packed back to back. */
+int llcomp_mi_codec_decode_views_host(llcomp_mi_codec* codec, const uint8_t* const* data, const size_t* lens, const llcomp_mi_view_group* groups,
+                                      uint32_t n_groups, void* d_status, void* stream);
+/* llcomp_mi_codec_workspace_bytes for calls of up to total_views views: it bounds llcomp_mi_codec_allocated_bytes for outputs no larger
+ * than the image (ow <= w, oh <= h) and at most 1 + max(total_views - frames, 0) groups with an output format.  The staged tables grow
+ * with the views: every view beyond `frames` adds 48 + 40 * (w + h) + 16 + 1024 * c bytes (its table entry, its weights at their upper
+ * bound, and an output table); for total_views <= frames this is llcomp_mi_codec_workspace_bytes. */
+uint64_t llcomp_mi_codec_views_workspace_bytes(const llcomp_mi_codec* codec, uint64_t total_views);
 /* Stage-A only (context + prediction model), for tests and profiling: d_sym u32[frames*h*w*c],
  * low 16 bits = folded context (0..7925), high 16 bits = folded residual (two's complement). */
 int llcomp_mi_codec_model(llcomp_mi_codec* codec, const void* d_px, void* d_sym, void* stream);

@@ -16,6 +16,9 @@ with ctypes and keeps the reference's names and error behaviour:
         filter= chooses PIL's bilinear, box, hamming, bicubic or lanczos, or nearest for label images, for the call or per frame)
     output_table / dtype=, layout=, scale=, mean=, std= of the three resized calls  (their output as a model takes it: float32, float16
         or bfloat16, CHW or HWC, ToTensor() + Normalize(mean, std) -- the _ex calls and llcomp_mi_output_format)
+    views_plan / ViewGroup / Codec.decode_views(_host) / Codec.views_workspace_bytes  (several views of each frame in one call, each
+        frame decoded once: a view = (frame, x, y, rw, rh, flags), a group = views that share one output shape, format and buffer --
+        multi-crop (2 x 224 + 8 x 96) and two-view training; a frame decodes the bounding box of its views)
     RawImage(pixels, width, height, channels)     <->  llcomp::RawImage         (/root/reference/llcomp.hpp:454-459)
     EXT = ".llcomp"                               <->  llcomp::ext              (/root/reference/llcomp.hpp:18)
 
@@ -29,6 +32,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import Info, Opts, OutputFormat
+from ._lib import View as _View, ViewGroup as _ViewGroup
 
 EXT = ".llcomp"
 FORMAT_LEGACY, FORMAT_SLICED = 0, 1
@@ -283,6 +287,58 @@ def resized_regions_plan(w, h, c, tile_w, tile_h, planar, rects):
     win, k = (C.c_uint32 * (4 * n))(), C.c_uint32()
     _check(_lib.load().llcomp_mi_resized_regions_plan(w, h, c, tile_w, tile_h, int(bool(planar)), tab, n, win, C.byref(k)))
     return np.array(win, dtype=np.uint32).reshape(n, 4), k.value
+
+
+class ViewGroup:
+    """Views that share one output (llcomp_mi_view_group): views = a sequence of (frame, x, y, rw, rh) or (frame, x, y, rw, rh, flags) or
+    an int array [n, 5 or 6]; the output is [n][oh][ow][c] at device address d_out (layout="chw": [n][c][oh][ow]) in the format that
+    dtype, layout, scale, mean and std give (as Codec.decode_resized_regions takes them); filter: one name or FILTER_* code for every view
+    of the group, or one per view, OR-ed into bits 4-6 of the views' flags.  A plain tuple (views, ow, oh, d_out) is a group too."""
+
+    def __init__(self, views, ow, oh, d_out=0, dtype=None, layout="hwc", scale=False, mean=None, std=None, filter=None):
+        self.views, self.ow, self.oh, self.d_out = views, ow, oh, d_out
+        self.format = dict(dtype=dtype, layout=layout, scale=scale, mean=mean, std=std)
+        self.filter = filter
+
+
+def _view_groups(groups, c):
+    """a sequence of ViewGroup (or (views, ow, oh[, d_out]) tuples) -> (ctypes array of llcomp_mi_view_group, n, keep-alive list);
+    everything about their contents is the library's to refuse"""
+    groups = list(groups) if groups is not None else []
+    arr, keep = (_ViewGroup * max(1, len(groups)))(), []
+    for i, gr in enumerate(groups):
+        if not isinstance(gr, ViewGroup):
+            if not isinstance(gr, (tuple, list)) or not 3 <= len(gr) <= 4:
+                raise LlcompError(BAD_ARGS, f"group {i} must be a ViewGroup or (views, ow, oh, d_out)")
+            gr = ViewGroup(*gr)
+        a = np.asarray(gr.views if len(gr.views) else np.zeros((0, 6), np.int64))
+        if a.ndim != 2 or a.shape[1] not in (5, 6) or not np.issubdtype(a.dtype, np.integer) or (a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF)):
+            raise LlcompError(BAD_ARGS, f"the views of group {i} must be n x 5 or n x 6 non-negative integers, got shape {a.shape} {a.dtype}")
+        n = a.shape[0]
+        if a.shape[1] == 5:
+            a = np.concatenate([a, np.zeros((n, 1), a.dtype)], axis=1)
+        fl = _flags_table(a[:, 5] & 0xFF, n, gr.filter) if n else None
+        views = (_View * max(1, n))(*[_View(*[int(v) for v in row[:5]], int(fl[j])) for j, row in enumerate(a.tolist())])
+        fmt, _, keep_fmt = _output_format(c, **gr.format)
+        keep += [views, keep_fmt]
+        arr[i] = _ViewGroup(C.sizeof(_ViewGroup), n, C.cast(views, C.POINTER(_View)) if n else None, int(gr.ow), int(gr.oh),
+                            C.pointer(fmt) if fmt is not None else None, gr.d_out or None)
+    return arr, len(groups), keep
+
+
+def views_plan(w, h, c, tile_w, tile_h, planar, frames, groups):
+    """(unions, windows, n_used, n_classes) of a views decode (llcomp_mi_views_plan, host only): unions [frames, 4] = every frame's
+    bounding box (x, y, rw, rh) of its views over all groups, zeros for a frame without a view; windows [frames, 4] and n_classes =
+    resized_regions_plan of the used frames' unions.  groups: ViewGroup objects or (views, ow, oh) tuples.  LlcompError(BAD_ARGS) as the
+    header lists: no groups, an empty group, a view of a frame >= frames, a rectangle empty or outside the image, an unknown filter, a
+    downscale above the filter's limit."""
+    arr, n, _keep = _view_groups(groups, c)
+    uni, win = np.zeros((frames, 4), np.uint32), np.zeros((frames, 4), np.uint32)
+    used, k = C.c_uint32(), C.c_uint32()
+    u32p = C.POINTER(C.c_uint32)
+    _check(_lib.load().llcomp_mi_views_plan(w, h, c, tile_w, tile_h, int(bool(planar)), frames, arr, n, uni.ctypes.data_as(u32p),
+                                            win.ctypes.data_as(u32p), C.byref(used), C.byref(k)))
+    return uni, win, used.value, k.value
 
 
 def pack_batch(containers):
@@ -927,6 +983,31 @@ class Codec:
             _check(self._L.llcomp_mi_codec_decode_resized_regions_host_ex(self._h, ptrs, lens, tab, fl, ow, oh, C.byref(fmt), d_px, d_status,
                                                                            stream))
 
+    def decode_views(self, d_payload, payload_bytes, d_slice_len, groups, d_status, stream=0):
+        """several views of each frame, each frame decoded once (llcomp_mi_codec_decode_views): groups = ViewGroup objects (or
+        (views, ow, oh, d_out) tuples); view v of a group -> d_out[v], byte for byte what decode_resized_regions writes for that rectangle
+        of that frame.  A frame decodes the bounding box of all its views; a frame without a view is not read.  d_payload / d_slice_len
+        are the full batch's (pack_batch)."""
+        arr, n, _keep = _view_groups(groups, self.c)
+        _check(self._L.llcomp_mi_codec_decode_views(self._h, d_payload, payload_bytes, d_slice_len, arr, n, d_status, stream))
+
+    def decode_views_host(self, containers, groups, d_status, stream=0):
+        """decode_views of host containers (llcomp_mi_codec_decode_views_host): only the union windows' bytes cross PCIe; the container
+        of a frame without a view may be None and is never read"""
+        conts = list(containers)
+        if len(conts) != self.frames:
+            raise LlcompError(BAD_ARGS, f"the codec takes {self.frames} containers, got {len(conts)}")
+        ptrs, lens, keep = _containers([d if d is not None else b"" for d in conts])
+        for f, d in enumerate(conts):
+            if d is None:
+                ptrs[f], lens[f] = None, 0
+        arr, n, _keep = _view_groups(groups, self.c)
+        _check(self._L.llcomp_mi_codec_decode_views_host(self._h, ptrs, lens, arr, n, d_status, stream))
+
+    def views_workspace_bytes(self, total_views):
+        """.workspace_bytes for calls of up to total_views views (llcomp_mi_codec_views_workspace_bytes): the staged tables grow with them"""
+        return self._L.llcomp_mi_codec_views_workspace_bytes(self._h, int(total_views))
+
     def allocated_bytes(self):
         """device bytes the codec holds right now (llcomp_mi_codec_allocated_bytes; at most .workspace_bytes for outputs up to the image's
         size)"""
@@ -958,11 +1039,11 @@ class Codec:
         _check(self._L.llcomp_mi_codec_get_profile(self._h, ms, C.byref(ne), C.byref(nd)))
         return dict(zip(self.PROFILE_SLOTS, list(ms))), ne.value, nd.value
 
-    def prepare(self, encode=True, decode=True, region=False, regions=False, resized=False, update=False):
-        """allocate now what the first encode / decode / region decode / regions decode / resized regions decode / region update would
-        allocate inside the call (llcomp_mi_codec_prepare)"""
+    def prepare(self, encode=True, decode=True, region=False, regions=False, resized=False, update=False, views=False):
+        """allocate now what the first encode / decode / region decode / regions decode / resized regions decode / region update / views
+        decode would allocate inside the call (llcomp_mi_codec_prepare)"""
         _check(self._L.llcomp_mi_codec_prepare(self._h, (1 if encode else 0) | (2 if decode else 0) | (8 if region else 0) | (16 if regions else 0)
-                                               | (32 if resized else 0) | (64 if update else 0)))
+                                               | (32 if resized else 0) | (64 if update else 0) | (128 if views else 0)))
 
     COUNTERS = ("dec_cached_waves", "dec_bypassed_waves", "cache_lookups", "cache_misses", "cache_writebacks", "dec_replays", "enc_carry_backs",
                 "generation_wraps", "dec_launches_cached", "dec_launches_plain", "host_staged_bytes")

@@ -38,6 +38,7 @@ SYMBOLS = [
     "llcomp_mi_stream_submit_decode_resized_regions_ex",
     "llcomp_mi_replace_slices", "llcomp_mi_replace_slices_into", "llcomp_mi_update_region", "llcomp_mi_update_region_into",
     "llcomp_mi_codec_encode_region", "llcomp_mi_codec_update_region", "llcomp_mi_resize_filter_weights",
+    "llcomp_mi_views_plan", "llcomp_mi_codec_decode_views", "llcomp_mi_codec_decode_views_host", "llcomp_mi_codec_views_workspace_bytes",
 ]
 
 u8p = C.POINTER(C.c_uint8)
@@ -53,6 +54,17 @@ class OutputFormat(C.Structure):
     """llcomp_mi_output_format (include/llcomp_mi.h): 32 bytes, mean at 16, std at 24"""
     _fields_ = [("struct_size", C.c_uint32), ("dtype", C.c_uint32), ("layout", C.c_uint32), ("scale", C.c_uint32),
                 ("mean", C.POINTER(C.c_float)), ("std", C.POINTER(C.c_float))]
+
+
+class View(C.Structure):
+    """llcomp_mi_view (include/llcomp_mi.h): 24 bytes"""
+    _fields_ = [("frame", C.c_uint32), ("x", C.c_uint32), ("y", C.c_uint32), ("rw", C.c_uint32), ("rh", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class ViewGroup(C.Structure):
+    """llcomp_mi_view_group (include/llcomp_mi.h): 40 bytes, views at 8, fmt at 24, d_out at 32"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_views", C.c_uint32), ("views", C.POINTER(View)), ("ow", C.c_uint32), ("oh", C.c_uint32),
+                ("fmt", C.POINTER(OutputFormat)), ("d_out", C.c_void_p)]
 
 
 class Info(C.Structure):
@@ -303,6 +315,16 @@ def load():
     if "LLCOMP_MI_LIB" not in os.environ or hasattr(L, "llcomp_mi_resize_filter_weights"):  # PIL's filters, one per frame
         L.llcomp_mi_resize_filter_weights.restype = C.c_uint32
         L.llcomp_mi_resize_filter_weights.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    if "LLCOMP_MI_LIB" not in os.environ or hasattr(L, "llcomp_mi_views_plan"):  # several views of each frame
+        u32p, ptrs, sizes, grp = C.POINTER(C.c_uint32), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(ViewGroup)
+        L.llcomp_mi_views_plan.restype = C.c_int
+        L.llcomp_mi_views_plan.argtypes = [C.c_uint32] * 7 + [grp, C.c_uint32, u32p, u32p, u32p, u32p]
+        L.llcomp_mi_codec_decode_views.restype = C.c_int
+        L.llcomp_mi_codec_decode_views.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, grp, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.llcomp_mi_codec_decode_views_host.restype = C.c_int
+        L.llcomp_mi_codec_decode_views_host.argtypes = [C.c_void_p, ptrs, sizes, grp, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.llcomp_mi_codec_views_workspace_bytes.restype = C.c_uint64
+        L.llcomp_mi_codec_views_workspace_bytes.argtypes = [C.c_void_p, C.c_uint64]
     if "LLCOMP_MI_LIB" not in os.environ and L.llcomp_mi_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.llcomp_mi_abi_version()}, this binding was written for {ABI_VERSION}: rebuild the library")
     _lib = L

@@ -425,7 +425,7 @@ struct RegionsClass {
     uint32_t first;
 };
 int regions_setup_sized(const llcomp_mi_codec* k, const uint32_t* rects, uint32_t wmax, uint32_t hmax, RegionsFrame* tab, RegionsClass* classes,
-                        uint32_t& n_classes);
+                        uint32_t& n_classes, const uint32_t* used = nullptr, uint32_t n_used = 0);
 // Every frame's window and class (geometry.hpp: regions_window) -> `tab` (g.frames entries, class by class, frame order inside a class)
 // and the classes that have frames, in class order.  BAD_ARGS for a rectangle a frame does not hold; HIP_ERROR if a class's
 // sub-geometry would not fit the codec's workspace (regions_fits: never by default, checked all the same).
@@ -444,14 +444,20 @@ int regions_setup(const llcomp_mi_codec* k, const uint32_t* xy, uint32_t rw, uin
 // ... with a rectangle of its own size per frame (rects = {x, y, rw, rh} per frame): every window is sized for the largest, wmax x hmax
 // (regions_window_sized), and the table's crop is a wmax x hmax BOX inside the window that contains the frame's rectangle, at
 // min(the rectangle's origin, the window's side - wmax) -- the rectangle's own origin when all sizes are equal.
+// used != nullptr (a views decode): a FRAME LIST -- only the n_used frames it names, in its order, get a table entry (`tab` holds n_used
+// of them), rects is still indexed by frame, and entry i's box goes to output slot i, not to its frame's: a frame that is not listed
+// has no entry, so none of its slices is touched.
 int regions_setup_sized(const llcomp_mi_codec* k, const uint32_t* rects, uint32_t wmax, uint32_t hmax, RegionsFrame* tab, RegionsClass* classes,
-                        uint32_t& n_classes) {
+                        uint32_t& n_classes, const uint32_t* used, uint32_t n_used) {
     const Geometry& g = k->g;
-    if (!rects) return LLCOMP_MI_BAD_ARGS;
+    if (!rects || (used && (!n_used || n_used > g.frames))) return LLCOMP_MI_BAD_ARGS;
+    const uint32_t m = used ? n_used : g.frames;
     RegionBox win[kRegionsClasses];
     uint32_t count[kRegionsClasses] = {}, cls = 0;
-    for (uint32_t f = 0; f < g.frames; ++f) {
+    for (uint32_t i = 0; i < m; ++i) {
         RegionBox b;
+        const uint32_t f = used ? used[i] : i;
+        if (f >= g.frames) return LLCOMP_MI_BAD_ARGS;
         const uint32_t* r = rects + 4 * size_t(f);
         if (!regions_window_sized(g.w, g.h, g.tile_w, g.tile_h, r[0], r[1], r[2], r[3], wmax, hmax, b, cls)) return LLCOMP_MI_BAD_ARGS;
         win[cls] = b;  // (the window's size, all the sub-geometry depends on, is the class's)
@@ -469,8 +475,9 @@ int regions_setup_sized(const llcomp_mi_codec* k, const uint32_t* rects, uint32_
         rc.first = first[c];
         if (!regions_geometry(g, win[c], count[c], k->tune, rc.sub) || !regions_fits(g, rc.sub)) return LLCOMP_MI_HIP_ERROR;
     }
-    for (uint32_t f = 0; f < g.frames; ++f) {
+    for (uint32_t i = 0; i < m; ++i) {
         RegionBox b;
+        const uint32_t f = used ? used[i] : i;
         const uint32_t* r = rects + 4 * size_t(f);
         (void)regions_window_sized(g.w, g.h, g.tile_w, g.tile_h, r[0], r[1], r[2], r[3], wmax, hmax, b, cls);
         const uint32_t cx = r[0] - b.tx0 * g.tile_w, cy = r[1] - b.ty0 * g.tile_h;
@@ -478,14 +485,14 @@ int regions_setup_sized(const llcomp_mi_codec* k, const uint32_t* rects, uint32_
         const uint32_t bx = std::min(cx, sub_of[cls]->w >= wmax ? sub_of[cls]->w - wmax : 0u);
         const uint32_t by = std::min(cy, sub_of[cls]->h >= hmax ? sub_of[cls]->h - hmax : 0u);
         RegionsFrame& e = tab[first[cls]++];
-        e = RegionsFrame{f, b.tx0, b.ty0, bx, by, f, cls, 0};
+        e = RegionsFrame{f, b.tx0, b.ty0, bx, by, used ? i : f, cls, 0};
     }
     // (what the crop kernels rely on; the window contains the box by construction)
     for (uint32_t i = 0; i < n_classes; ++i) {
         const RegionsClass& rc = classes[i];
         for (uint32_t j = 0; j < rc.sub.frames; ++j) {
             const RegionsFrame& e = tab[rc.first + j];
-            if (uint64_t(e.cx0) + wmax > rc.sub.w || uint64_t(e.cy0) + hmax > rc.sub.h || e.out >= g.frames) return LLCOMP_MI_HIP_ERROR;
+            if (uint64_t(e.cx0) + wmax > rc.sub.w || uint64_t(e.cy0) + hmax > rc.sub.h || e.out >= m || e.frame >= g.frames) return LLCOMP_MI_HIP_ERROR;
         }
     }
     return LLCOMP_MI_OK;
@@ -592,6 +599,7 @@ int resized_setup(const llcomp_mi_codec* k, const uint32_t* rects, const uint8_t
         z.ox = r[0] - e.wx0 * g.tile_w - e.cx0;
         z.oy = r[1] - e.wy0 * g.tile_h - e.cy0;
         z.flags = flags ? flags[e.frame] & (1u | LLCOMP_MI_FLAG_FILTER_MASK) : 0u;
+        z.box = e.out;  // (the frame's own box)
         if (!resize_frame_weights(LLCOMP_MI_FLAG_FILTER_OF(z.flags), r[2], r[3], ow, oh, z, p.w, seen)) return LLCOMP_MI_BAD_ARGS;
         if (uint64_t(z.ox) + z.rw > p.wmax || uint64_t(z.oy) + z.rh > p.hmax) return LLCOMP_MI_HIP_ERROR;  // (the box holds it by construction)
     }
@@ -599,6 +607,116 @@ int resized_setup(const llcomp_mi_codec* k, const uint32_t* rects, const uint8_t
     p.mid_bytes = uint64_t(g.frames) * p.hmax * ow * g.c;
     p.table.resize(p.out.table_bytes(g.c));
     if (!p.table.empty()) output_table(fmt, g.c, p.out, p.table.data());
+    return LLCOMP_MI_OK;
+}
+
+// Everything of a views decode the host decides (include/llcomp_mi.h: llcomp_mi_codec_decode_views): the union rectangle of every used
+// frame (container.cpp: views_union), the regions table of the USED frames alone (regions_setup_sized with the frame list, sized for the
+// largest union: entry i cuts its frame's box into d_box[i]), and per group its views' entries -- each names its frame's box and its
+// rectangle inside it -- with the weights of the whole call in one array (an axis is shared across views AND groups: `seen` lives for
+// the call) and the groups' output tables.  A group whose rows [n][mh][ow][c] (mh: ITS largest view height) would pass frames * w * h * c
+// is resampled `chunk` views at a time, so d_mid keeps its bound for ow <= w (one view: mh * ow * c <= h * w * c).
+// BAD_ARGS: views_union's cases, a bad output format, a group's d_out NULL or not aligned to its element size.
+struct ViewsGroup {
+    uint32_t n = 0, ow = 0, oh = 0, mh = 0, chunk = 0, first = 0;  // first: the group's first entry in rs
+    OutFormat out;
+    void* d_out = nullptr;
+    uint64_t table_at = 0;  // in `tables`
+};
+struct ViewsPlan {
+    ViewsUnion u;
+    std::vector<RegionsFrame> tab;
+    RegionsClass classes[kRegionsClasses];
+    uint32_t n_classes = 0;
+    std::vector<ViewsGroup> groups;
+    std::vector<ResizeFrame> rs;  // group by group, view order
+    std::vector<int32_t> w;
+    std::vector<uint8_t> tables;  // every formatted group's table, each at a multiple of 16
+    uint64_t box_bytes = 0, mid_bytes = 0;
+    // what the one copy carries behind the regions table (or behind the staged payload): [ResizeFrame[views]][int32 weights], then the
+    // output tables at the next multiple of 16
+    uint64_t w_at() const { return uint64_t(rs.size()) * sizeof(ResizeFrame); }
+    uint64_t tables_at() const { return (w_at() + 4 * uint64_t(w.size()) + 15) & ~15ull; }
+    uint64_t bytes() const { return tables.empty() ? w_at() + 4 * uint64_t(w.size()) : tables_at() + tables.size(); }
+    void put(uint8_t* at) const {
+        std::memcpy(at, rs.data(), rs.size() * sizeof(ResizeFrame));
+        std::memcpy(at + w_at(), w.data(), 4 * w.size());
+        if (!tables.empty()) std::memcpy(at + tables_at(), tables.data(), tables.size());
+    }
+};
+int views_setup(const llcomp_mi_codec* k, const llcomp_mi_view_group* groups, uint32_t n_groups, ViewsPlan& p) {
+    const Geometry& g = k->g;
+    if (int rc = views_union(g.w, g.h, g.frames, groups, n_groups, p.u)) return rc;
+    p.groups.resize(n_groups);
+    for (uint32_t gi = 0; gi < n_groups; ++gi) {
+        const llcomp_mi_view_group& gr = *view_group_at(groups, gi);
+        ViewsGroup& vg = p.groups[gi];
+        if (int rc = check_output_format(gr.fmt, g.c, vg.out)) return rc;
+        if (!gr.d_out || (reinterpret_cast<uintptr_t>(gr.d_out) & (vg.out.esize - 1))) return LLCOMP_MI_BAD_ARGS;
+    }
+    const uint32_t n_used = uint32_t(p.u.used.size());
+    p.tab.resize(n_used);
+    if (int rc = regions_setup_sized(k, p.u.rects.data(), p.u.wmax, p.u.hmax, p.tab.data(), p.classes, p.n_classes, p.u.used.data(), n_used))
+        return rc;
+    std::vector<uint32_t> entry_of(g.frames, 0);  // a used frame's entry of the regions table
+    for (uint32_t i = 0; i < n_used; ++i) entry_of[p.tab[i].frame] = i;
+    const uint64_t samples = uint64_t(g.frames) * g.w * g.h * g.c;
+    std::vector<uint32_t> seen;  // (axes already computed in this call)
+    p.rs.reserve(size_t(p.u.total_views));
+    for (uint32_t gi = 0; gi < n_groups; ++gi) {
+        const llcomp_mi_view_group& gr = *view_group_at(groups, gi);
+        ViewsGroup& vg = p.groups[gi];
+        vg.n = gr.n_views;
+        vg.ow = gr.ow;
+        vg.oh = gr.oh;
+        vg.d_out = gr.d_out;
+        vg.first = uint32_t(p.rs.size());
+        for (uint32_t i = 0; i < gr.n_views; ++i) {
+            const llcomp_mi_view& v = gr.views[i];
+            const RegionsFrame& e = p.tab[entry_of[v.frame]];
+            ResizeFrame z{};
+            z.ox = v.x - e.wx0 * g.tile_w - e.cx0;  // (the box starts at or before the union's origin, which no view starts before)
+            z.oy = v.y - e.wy0 * g.tile_h - e.cy0;
+            z.flags = v.flags & (1u | LLCOMP_MI_FLAG_FILTER_MASK);
+            z.box = e.out;
+            if (!resize_frame_weights(LLCOMP_MI_FLAG_FILTER_OF(z.flags), v.rw, v.rh, gr.ow, gr.oh, z, p.w, seen)) return LLCOMP_MI_BAD_ARGS;
+            // (the box holds the union, and the union the view, by construction)
+            if (e.frame != v.frame || uint64_t(z.ox) + z.rw > p.u.wmax || uint64_t(z.oy) + z.rh > p.u.hmax || z.box >= n_used) return LLCOMP_MI_HIP_ERROR;
+            vg.mh = std::max(vg.mh, v.rh);
+            p.rs.push_back(z);
+        }
+        const uint64_t per_view = uint64_t(vg.mh) * vg.ow * g.c;
+        vg.chunk = uint32_t(std::min<uint64_t>(vg.n, std::max<uint64_t>(samples / per_view, 1)));
+        p.mid_bytes = std::max(p.mid_bytes, vg.chunk * per_view);
+        if (!vg.out.plain) {
+            vg.table_at = (p.tables.size() + 15) & ~size_t(15);
+            p.tables.resize(vg.table_at + vg.out.table_bytes(g.c));
+            output_table(gr.fmt, g.c, vg.out, p.tables.data() + vg.table_at);
+        }
+    }
+    p.box_bytes = uint64_t(n_used) * p.u.wmax * p.u.hmax * g.c;
+    return LLCOMP_MI_OK;
+}
+// What the staged tables of a views decode add per view beyond `frames` (include/llcomp_mi.h: llcomp_mi_codec_views_workspace_bytes): its
+// entry, its weights at resized_tables_bound's upper bound, and an output table with its alignment.
+uint64_t view_term(const Geometry& g) { return sizeof(ResizeFrame) + 4 * 10 * (uint64_t(g.w) + g.h) + 16 + 256 * 4 * uint64_t(g.c); }
+uint64_t views_tables_bound(const Geometry& g, uint64_t total_views) {
+    return resized_tables_bound(g) + (total_views > g.frames ? (total_views - g.frames) * view_term(g) : 0);
+}
+// The resample passes of a views decode, group by group and chunk by chunk, behind the classes: d_block is ViewsPlan::put's copy in HBM.
+int views_resample(llcomp_mi_codec* k, const ViewsPlan& p, const uint8_t* d_block, hipStream_t s) {
+    const Geometry& g = k->g;
+    const ResizeFrame* d_rs = reinterpret_cast<const ResizeFrame*>(d_block);
+    const int32_t* d_w = reinterpret_cast<const int32_t*>(d_block + p.w_at());
+    Timed t(k, s, 6);
+    for (const ViewsGroup& vg : p.groups) {
+        const uint64_t view_bytes = uint64_t(vg.oh) * vg.ow * g.c * vg.out.esize;
+        for (uint32_t at = 0; at < vg.n; at += vg.chunk) {
+            const uint32_t cnt = std::min(vg.chunk, vg.n - at);
+            HIP_TRY(launch_resize_out(k->d_box, k->d_mid, static_cast<uint8_t*>(vg.d_out) + at * view_bytes, d_rs + vg.first + at, d_w,
+                                      d_block + p.tables_at() + vg.table_at, vg.out, cnt, g.c, p.u.wmax, p.u.hmax, vg.mh, vg.ow, vg.oh, s));
+        }
+    }
     return LLCOMP_MI_OK;
 }
 
@@ -891,7 +1009,7 @@ void llcomp_mi_codec_destroy(llcomp_mi_codec* k) {
 
 int llcomp_mi_codec_prepare(llcomp_mi_codec* k, uint32_t what) {
     if (!k || (what & ~(LLCOMP_MI_PREPARE_ENCODE | LLCOMP_MI_PREPARE_DECODE | LLCOMP_MI_PREPARE_REGION | LLCOMP_MI_PREPARE_REGIONS |
-                        LLCOMP_MI_PREPARE_RESIZED | LLCOMP_MI_PREPARE_UPDATE)))
+                        LLCOMP_MI_PREPARE_RESIZED | LLCOMP_MI_PREPARE_UPDATE | LLCOMP_MI_PREPARE_VIEWS)))
         return LLCOMP_MI_BAD_ARGS;
     DeviceGuard guard(k->device);
     if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
@@ -904,7 +1022,8 @@ int llcomp_mi_codec_prepare(llcomp_mi_codec* k, uint32_t what) {
     }
     if (what & LLCOMP_MI_PREPARE_DECODE)
         if (int rc = ensure_state_tables(k, k->need_states)) return rc;
-    if (what & (LLCOMP_MI_PREPARE_REGION | LLCOMP_MI_PREPARE_REGIONS | LLCOMP_MI_PREPARE_RESIZED | LLCOMP_MI_PREPARE_UPDATE)) {
+    if (what & (LLCOMP_MI_PREPARE_REGION | LLCOMP_MI_PREPARE_REGIONS | LLCOMP_MI_PREPARE_RESIZED | LLCOMP_MI_PREPARE_UPDATE |
+                LLCOMP_MI_PREPARE_VIEWS)) {
         if (int rc = ensure_region_arrays(k)) return rc;
         if (region_may_need_states(k))
             if (int rc = ensure_state_tables(k, true)) return rc;
@@ -916,11 +1035,15 @@ int llcomp_mi_codec_prepare(llcomp_mi_codec* k, uint32_t what) {
         if (int rc = ensure_update_arrays(k)) return rc;
         if (int rc = ensure_grown(k, k->d_box, k->box_cap, samples, samples)) return rc;
     }
-    if (what & LLCOMP_MI_PREPARE_RESIZED) {
+    if (what & (LLCOMP_MI_PREPARE_RESIZED | LLCOMP_MI_PREPARE_VIEWS)) {
         const uint64_t samples = uint64_t(k->g.frames) * k->g.w * k->g.h * k->g.c;
         if (int rc = ensure_regions_ring(k)) return rc;
         if (int rc = ensure_grown(k, k->d_box, k->box_cap, samples, samples)) return rc;
         if (int rc = ensure_grown(k, k->d_mid, k->mid_cap, samples, samples)) return rc;
+    }
+    if (what & LLCOMP_MI_PREPARE_VIEWS) {  // (the regions table of every frame and the tables of `frames` views: a call from HBM)
+        const uint64_t tables = ((uint64_t(k->g.frames) * sizeof(RegionsFrame) + 15) & ~15ull) + resized_tables_bound(k->g);
+        if (int rc = ensure_stage(k, tables, stage_bound(k->g) + resized_tables_bound(k->g))) return rc;
     }
     return LLCOMP_MI_OK;
 }
@@ -1351,7 +1474,7 @@ int llcomp_mi_codec_decode_resized_regions_ex(llcomp_mi_codec* k, const void* d_
         Timed t(k, s, 6);
         HIP_TRY(launch_resize_out(k->d_box, k->d_mid, d_px, reinterpret_cast<const ResizeFrame*>(k->d_stage + rs_at),
                                   reinterpret_cast<const int32_t*>(k->d_stage + rs_at + p.rs.size() * sizeof(ResizeFrame)),
-                                  k->d_stage + rs_at + p.table_at(), p.out, g.frames, g.c, p.wmax, p.hmax, ow, oh, s));
+                                  k->d_stage + rs_at + p.table_at(), p.out, g.frames, g.c, p.wmax, p.hmax, p.hmax, ow, oh, s));
     }
     ++k->n_decode;
     return LLCOMP_MI_OK;
@@ -1408,7 +1531,7 @@ int llcomp_mi_codec_decode_resized_regions_host_ex(llcomp_mi_codec* k, const uin
         Timed t(k, s, 6);
         HIP_TRY(launch_resize_out(k->d_box, k->d_mid, d_px, reinterpret_cast<const ResizeFrame*>(k->d_stage + rs_at),
                                   reinterpret_cast<const int32_t*>(k->d_stage + rs_at + p.rs.size() * sizeof(ResizeFrame)),
-                                  k->d_stage + rs_at + p.table_at(), p.out, g.frames, g.c, p.wmax, p.hmax, ow, oh, s));
+                                  k->d_stage + rs_at + p.table_at(), p.out, g.frames, g.c, p.wmax, p.hmax, p.hmax, ow, oh, s));
     }
     ++k->n_decode;
     return LLCOMP_MI_OK;
@@ -1423,6 +1546,105 @@ int llcomp_mi_codec_decode_resized_regions(llcomp_mi_codec* k, const void* d_pay
 int llcomp_mi_codec_decode_resized_regions_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens, const uint32_t* rects,
                                                 const uint8_t* flags, uint32_t ow, uint32_t oh, void* d_px, void* d_status, void* stream) {
     return llcomp_mi_codec_decode_resized_regions_host_ex(k, data, lens, rects, flags, ow, oh, nullptr, d_px, d_status, stream);
+}
+
+// Views decode (DESIGN.md "Several views of each frame"): llcomp_mi_codec_decode_resized_regions_ex on the used frames' union rectangles
+// up to the boxes -- the classes unchanged, over the frame list -- then every group's views resampled from their frames' boxes.
+int llcomp_mi_codec_decode_views(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                 const llcomp_mi_view_group* groups, uint32_t n_groups, void* d_status, void* stream) {
+    if (!k || !d_payload || !d_slice_len || !d_status) return LLCOMP_MI_BAD_ARGS;
+    if (misaligned(d_slice_len, 4) || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
+    const Geometry& g = k->g;
+    ViewsPlan p;
+    if (int rc = views_setup(k, groups, n_groups, p)) return rc;
+    const uint64_t rs_at = (uint64_t(p.tab.size()) * sizeof(RegionsFrame) + 15) & ~15ull, bytes = rs_at + p.bytes();
+    DeviceGuard guard(k->device);
+    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
+    if (int rc = ensure_region_arrays(k)) return rc;
+    const uint64_t samples = uint64_t(g.frames) * g.w * g.h * g.c, bound = stage_bound(g) + views_tables_bound(g, p.u.total_views);
+    if (int rc = ensure_regions_ring(k)) return rc;
+    if (int rc = ensure_stage(k, bytes, bound)) return rc;
+    if (int rc = ensure_grown(k, k->d_box, k->box_cap, p.box_bytes, samples)) return rc;
+    if (int rc = ensure_grown(k, k->d_mid, k->mid_cap, p.mid_bytes, samples)) return rc;
+    uint32_t slot = 0;
+    if (int rc = regions_slot_take(k, bytes, bound, slot)) return rc;
+    uint8_t* h = k->h_regions[slot];
+    std::memcpy(h, p.tab.data(), p.tab.size() * sizeof(RegionsFrame));
+    p.put(h + rs_at);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DoneGuard done_guard{k, s};
+    HIP_TRY(hipMemsetAsync(d_status, 0, 4, s));
+    {
+        Timed t(k, s, 4);
+        HIP_TRY(hipMemcpyAsync(k->d_stage, h, bytes, hipMemcpyHostToDevice, s));
+        if (int rc = regions_slot_queued(k, slot, s)) return rc;
+        HIP_TRY(launch_group_sums(g, static_cast<const uint32_t*>(d_slice_len), k->d_group_off, s));
+        HIP_TRY(launch_scan_groups(g, k->d_group_off, k->d_total_tmp, s));
+    }
+    const RegionsSource src{static_cast<const uint8_t*>(d_payload), payload_bytes, static_cast<const uint32_t*>(d_slice_len), nullptr, nullptr};
+    if (int rc = regions_classes(k, p.classes, p.n_classes, reinterpret_cast<const RegionsFrame*>(k->d_stage), src, p.u.wmax, p.u.hmax, k->d_box,
+                                 static_cast<uint32_t*>(d_status), s))
+        return rc;
+    if (int rc = views_resample(k, p, k->d_stage + rs_at, s)) return rc;
+    ++k->n_decode;
+    return LLCOMP_MI_OK;
+}
+
+// ... of host containers: the gather of llcomp_mi_codec_decode_resized_regions_host over the used frames' union rectangles (a frame
+// without a view is not looked at: its container may be NULL); the view tables ride behind the staged payload in the same copy.
+int llcomp_mi_codec_decode_views_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens, const llcomp_mi_view_group* groups,
+                                      uint32_t n_groups, void* d_status, void* stream) {
+    if (!k || !data || !lens || !d_status || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
+    const Geometry& g = k->g;
+    ViewsPlan p;
+    if (int rc = views_setup(k, groups, n_groups, p)) return rc;
+    const uint32_t n_used = uint32_t(p.u.used.size());
+    RegionsGather gp;
+    if (int rc = regions_gather_plan_sized(data, lens, g.frames, p.u.rects.data(), p.u.wmax, p.u.hmax, gp, p.u.used.data(), n_used)) return rc;
+    const Geometry& cg = gp.g;
+    if (cg.w != g.w || cg.h != g.h || cg.c != g.c || cg.tile_w != g.tile_w || cg.tile_h != g.tile_h || cg.planar != g.planar ||
+        (cg.flags & kGeoSmallModel) != (g.flags & kGeoSmallModel))
+        return LLCOMP_MI_BAD_ARGS;
+    uint64_t sub_slices = 0;  // (the gather's order is the table's: class by class, and a class's slices are its sub-geometry's)
+    for (uint32_t i = 0; i < p.n_classes; ++i) sub_slices += p.classes[i].sub.n_slices;
+    if (sub_slices != gp.n_slices) return LLCOMP_MI_HIP_ERROR;
+    const StageLayout lay(n_used, gp.n_slices, gp.payload_bytes);
+    const uint64_t rs_at = (lay.bytes + 15) & ~15ull, bytes = rs_at + p.bytes();
+    DeviceGuard guard(k->device);
+    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
+    const uint64_t samples = uint64_t(g.frames) * g.w * g.h * g.c, bound = stage_bound(g) + views_tables_bound(g, p.u.total_views);
+    if (int rc = ensure_regions_ring(k)) return rc;
+    if (int rc = ensure_stage(k, bytes, bound)) return rc;
+    if (int rc = ensure_grown(k, k->d_box, k->box_cap, p.box_bytes, samples)) return rc;
+    if (int rc = ensure_grown(k, k->d_mid, k->mid_cap, p.mid_bytes, samples)) return rc;
+    uint32_t slot = 0;
+    if (int rc = regions_slot_take(k, bytes, bound, slot)) return rc;
+    uint8_t* h = k->h_regions[slot];
+    std::memcpy(h, p.tab.data(), p.tab.size() * sizeof(RegionsFrame));
+    regions_gather_copy(gp, data, h + lay.pay_at, reinterpret_cast<uint32_t*>(h + lay.len_at), reinterpret_cast<uint64_t*>(h + lay.off_at));
+    p.put(h + rs_at);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DoneGuard done_guard{k, s};
+    HIP_TRY(hipMemsetAsync(d_status, 0, 4, s));
+    {
+        Timed t(k, s, 4);
+        HIP_TRY(hipMemcpyAsync(k->d_stage, h, bytes, hipMemcpyHostToDevice, s));
+        if (int rc = regions_slot_queued(k, slot, s)) return rc;
+    }
+    k->host_counters[LLCOMP_MI_CTR_HOST_STAGED_BYTES] += gp.payload_bytes;
+    const RegionsSource src{k->d_stage + lay.pay_at, gp.payload_bytes, nullptr, reinterpret_cast<const uint32_t*>(k->d_stage + lay.len_at),
+                            reinterpret_cast<const uint64_t*>(k->d_stage + lay.off_at)};
+    if (int rc = regions_classes(k, p.classes, p.n_classes, reinterpret_cast<const RegionsFrame*>(k->d_stage), src, p.u.wmax, p.u.hmax, k->d_box,
+                                 static_cast<uint32_t*>(d_status), s))
+        return rc;
+    if (int rc = views_resample(k, p, k->d_stage + rs_at, s)) return rc;
+    ++k->n_decode;
+    return LLCOMP_MI_OK;
+}
+
+uint64_t llcomp_mi_codec_views_workspace_bytes(const llcomp_mi_codec* k, uint64_t total_views) {
+    if (!k) return 0;
+    return k->workspace_bytes + (total_views > k->g.frames ? (total_views - k->g.frames) * view_term(k->g) : 0);
 }
 
 uint32_t llcomp_mi_status_from_bits(uint32_t bits) { return uint32_t(status_from_bits(bits)); }

@@ -41,19 +41,21 @@ int regions_gather_plan(const uint8_t* const* data, const size_t* lens, uint32_t
 }
 
 int regions_gather_plan_sized(const uint8_t* const* data, const size_t* lens, uint32_t n, const uint32_t* rects, uint32_t wmax, uint32_t hmax,
-                              RegionsGather& p) {
+                              RegionsGather& p, const uint32_t* used, uint32_t n_used) {
     p = RegionsGather{};
-    if (!data || !lens || !rects || !n) return LLCOMP_MI_BAD_ARGS;
+    if (!data || !lens || !rects || !n || (used && !n_used)) return LLCOMP_MI_BAD_ARGS;
+    const uint32_t m = used ? n_used : n;  // the frames that take part: entry i is frame used[i], or frame i
     llcomp_mi_info i0{};
-    std::vector<uint32_t> cls(n), first_run(n + 1);
+    std::vector<uint32_t> cls(m), first_run(m + 1);
     std::vector<GatherRun> runs;  // frame order
     uint32_t limit = 0, seen = 0;
-    for (uint32_t f = 0; f < n; ++f) {
-        if (!data[f]) return LLCOMP_MI_BAD_ARGS;
+    for (uint32_t i = 0; i < m; ++i) {
+        const uint32_t f = used ? used[i] : i;
+        if (f >= n || !data[f]) return LLCOMP_MI_BAD_ARGS;
         llcomp_mi_info a;
         if (int rc = llcomp_mi_probe(data[f], lens[f], &a)) return rc;
         if (a.format != LLCOMP_MI_FORMAT_SLICED) return LLCOMP_MI_BAD_ARGS;
-        if (f == 0) {
+        if (i == 0) {
             i0 = a;
             if (!make_geometry(p.g, 1, a.width, a.height, a.channels, a.tile_w, a.tile_h, a.planar, Tuning{}, a.small_model != 0))
                 return LLCOMP_MI_BAD_ARGS;
@@ -63,14 +65,14 @@ int regions_gather_plan_sized(const uint8_t* const* data, const size_t* lens, ui
             return LLCOMP_MI_BAD_ARGS;
         }
         RegionBox win;
-        if (!regions_window_sized(a.width, a.height, a.tile_w, a.tile_h, rects[4 * f], rects[4 * f + 1], rects[4 * f + 2], rects[4 * f + 3], wmax,
-                                  hmax, win, cls[f]))
+        if (!regions_window_sized(a.width, a.height, a.tile_w, a.tile_h, rects[4 * size_t(f)], rects[4 * size_t(f) + 1], rects[4 * size_t(f) + 2],
+                                  rects[4 * size_t(f) + 3], wmax, hmax, win, cls[i]))
             return LLCOMP_MI_BAD_ARGS;
-        seen |= 1u << cls[f];
+        seen |= 1u << cls[i];
         // one window tile row = (wx1 - wx0) * planes consecutive slices; the table is summed up to the end of the last one only
         const uint32_t planes = a.planar ? a.channels : 1u, per_row = (win.tx1 - win.tx0) * planes;
         const uint8_t* tab = data[f] + a.table_offset;
-        first_run[f] = uint32_t(runs.size());
+        first_run[i] = uint32_t(runs.size());
         uint64_t off = 0;
         uint32_t s = 0;
         for (uint32_t ty = win.ty0; ty < win.ty1; ++ty) {
@@ -87,13 +89,13 @@ int regions_gather_plan_sized(const uint8_t* const* data, const size_t* lens, ui
             off += bytes;
         }
     }
-    first_run[n] = uint32_t(runs.size());
+    first_run[m] = uint32_t(runs.size());
     uint64_t slices = 0;
     p.runs.reserve(runs.size());
     for (uint32_t c = 0; c < kRegionsClasses; ++c)
-        for (uint32_t f = 0; f < n; ++f)
-            if (cls[f] == c)
-                for (uint32_t r = first_run[f]; r < first_run[f + 1]; ++r) {
+        for (uint32_t i = 0; i < m; ++i)
+            if (cls[i] == c)
+                for (uint32_t r = first_run[i]; r < first_run[i + 1]; ++r) {
                     p.runs.push_back(runs[r]);
                     slices += runs[r].count;
                     p.payload_bytes += runs[r].bytes;
@@ -101,6 +103,49 @@ int regions_gather_plan_sized(const uint8_t* const* data, const size_t* lens, ui
     if (slices >= (1ull << 31)) return LLCOMP_MI_OUT_OF_RANGE;
     p.n_slices = uint32_t(slices);
     p.n_classes = uint32_t(__builtin_popcount(seen));
+    return LLCOMP_MI_OK;
+}
+
+const llcomp_mi_view_group* view_group_at(const llcomp_mi_view_group* groups, uint32_t i) {
+    return reinterpret_cast<const llcomp_mi_view_group*>(reinterpret_cast<const uint8_t*>(groups) + size_t(i) * groups->struct_size);
+}
+
+int views_union(uint32_t w, uint32_t h, uint32_t frames, const llcomp_mi_view_group* groups, uint32_t n_groups, ViewsUnion& u) {
+    u = ViewsUnion{};
+    if (!groups || !n_groups || !frames || !w || !h || groups->struct_size != sizeof(llcomp_mi_view_group)) return LLCOMP_MI_BAD_ARGS;
+    std::vector<uint32_t> x1(frames, 0), y1(frames, 0);  // (exclusive ends; rects holds the origins until the end)
+    u.rects.assign(4 * size_t(frames), 0);
+    for (uint32_t gi = 0; gi < n_groups; ++gi) {
+        const llcomp_mi_view_group& gr = *view_group_at(groups, gi);
+        if (gr.struct_size != sizeof(llcomp_mi_view_group) || !gr.n_views || gr.n_views > 65535 || !gr.views || !gr.ow || !gr.oh)
+            return LLCOMP_MI_BAD_ARGS;
+        for (uint32_t i = 0; i < gr.n_views; ++i) {
+            const llcomp_mi_view& v = gr.views[i];
+            const uint32_t filter = LLCOMP_MI_FLAG_FILTER_OF(v.flags & 0xFFu);
+            if (v.frame >= frames || !v.rw || !v.rh || uint64_t(v.x) + v.rw > w || uint64_t(v.y) + v.rh > h) return LLCOMP_MI_BAD_ARGS;
+            if (!resize_axis_ok(filter, v.rw, gr.ow) || !resize_axis_ok(filter, v.rh, gr.oh)) return LLCOMP_MI_BAD_ARGS;
+            uint32_t* r = u.rects.data() + 4 * size_t(v.frame);
+            if (!x1[v.frame]) {
+                r[0] = v.x;
+                r[1] = v.y;
+            } else {
+                r[0] = std::min(r[0], v.x);
+                r[1] = std::min(r[1], v.y);
+            }
+            x1[v.frame] = std::max(x1[v.frame], v.x + v.rw);
+            y1[v.frame] = std::max(y1[v.frame], v.y + v.rh);
+        }
+        u.total_views += gr.n_views;
+    }
+    for (uint32_t f = 0; f < frames; ++f) {
+        if (!x1[f]) continue;
+        uint32_t* r = u.rects.data() + 4 * size_t(f);
+        r[2] = x1[f] - r[0];
+        r[3] = y1[f] - r[1];
+        u.wmax = std::max(u.wmax, r[2]);
+        u.hmax = std::max(u.hmax, r[3]);
+        u.used.push_back(f);
+    }
     return LLCOMP_MI_OK;
 }
 
@@ -326,6 +371,38 @@ int llcomp_mi_resized_regions_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t 
         windows[4 * f + 2] = b.tx1;
         windows[4 * f + 3] = b.ty1;
     }
+    *n_classes = uint32_t(__builtin_popcount(seen));
+    return LLCOMP_MI_OK;
+}
+
+int llcomp_mi_views_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar, uint32_t frames,
+                         const llcomp_mi_view_group* groups, uint32_t n_groups, uint32_t* unions, uint32_t* windows, uint32_t* n_used,
+                         uint32_t* n_classes) {
+    (void)planar;
+    if (!n_used || !n_classes || c < 1 || c > kMaxChannels) return LLCOMP_MI_BAD_ARGS;
+    ViewsUnion u;
+    if (int rc = views_union(w, h, frames, groups, n_groups, u)) return rc;
+    // (the union of rectangles inside the image is inside the image: regions_window_sized cannot refuse one)
+    std::vector<RegionBox> win(u.used.size());
+    uint32_t seen = 0;
+    for (size_t i = 0; i < u.used.size(); ++i) {
+        const uint32_t* r = u.rects.data() + 4 * size_t(u.used[i]);
+        uint32_t cls = 0;
+        if (!regions_window_sized(w, h, tile_w, tile_h, r[0], r[1], r[2], r[3], u.wmax, u.hmax, win[i], cls)) return LLCOMP_MI_BAD_ARGS;
+        seen |= 1u << cls;
+    }
+    if (unions) std::memcpy(unions, u.rects.data(), u.rects.size() * 4);
+    if (windows) {
+        std::memset(windows, 0, 16 * size_t(frames));
+        for (size_t i = 0; i < u.used.size(); ++i) {
+            uint32_t* o = windows + 4 * size_t(u.used[i]);
+            o[0] = win[i].tx0;
+            o[1] = win[i].ty0;
+            o[2] = win[i].tx1;
+            o[3] = win[i].ty1;
+        }
+    }
+    *n_used = uint32_t(u.used.size());
     *n_classes = uint32_t(__builtin_popcount(seen));
     return LLCOMP_MI_OK;
 }

@@ -7,6 +7,8 @@
 
 #include "geometry.hpp"
 
+struct llcomp_mi_view_group;  // include/llcomp_mi.h
+
 namespace llcomp_mi {
 
 inline void put_u32le(uint8_t* p, uint32_t v) {
@@ -37,11 +39,26 @@ struct RegionsGather {
 int regions_gather_plan(const uint8_t* const* data, const size_t* lens, uint32_t n, const uint32_t* xy, uint32_t rw, uint32_t rh,
                         RegionsGather& p);
 // ... of a rectangle of its own size per frame (rects = {x, y, rw, rh} per frame), every window sized for wmax x hmax
-// (regions_window_sized; llcomp_mi_codec_decode_resized_regions_host)
+// (regions_window_sized; llcomp_mi_codec_decode_resized_regions_host).  used != nullptr (llcomp_mi_codec_decode_views_host): only the
+// n_used frames it lists, in its order, take part -- data / lens / rects are still indexed by frame, no other frame's container is
+// looked at (it may be NULL), and `g` is the first listed container's geometry.
 int regions_gather_plan_sized(const uint8_t* const* data, const size_t* lens, uint32_t n, const uint32_t* rects, uint32_t wmax, uint32_t hmax,
-                              RegionsGather& p);
+                              RegionsGather& p, const uint32_t* used = nullptr, uint32_t n_used = 0);
 // the planned bytes: payload (p.payload_bytes), slice_len (p.n_slices entries) and, when slice_off is not null, the offset of every
 // slice in `payload`
 void regions_gather_copy(const RegionsGather& p, const uint8_t* const* data, uint8_t* payload, uint32_t* slice_len, uint64_t* slice_off);
+
+// Views (llcomp_mi_views_plan, llcomp_mi_codec_decode_views): every check of the plan, and per frame the union rectangle (bounding box)
+// of its views over all groups -- rects[4f .. 4f + 3] = {x, y, rw, rh}, four zeros for a frame without a view -- the used frames in
+// frame order, the largest union's sides and the number of views.
+struct ViewsUnion {
+    std::vector<uint32_t> rects;  // 4 * frames
+    std::vector<uint32_t> used;
+    uint32_t wmax = 0, hmax = 0;
+    uint64_t total_views = 0;
+};
+// group i of an array of groups (its stride is the groups' struct_size, which views_union has checked)
+const llcomp_mi_view_group* view_group_at(const llcomp_mi_view_group* groups, uint32_t i);
+int views_union(uint32_t w, uint32_t h, uint32_t frames, const llcomp_mi_view_group* groups, uint32_t n_groups, ViewsUnion& u);
 
 }  // namespace llcomp_mi

@@ -38,17 +38,11 @@ static double f_lanczos(double x) { return (-3.0 <= x && x < 3.0) ? f_sinc(x) * 
 
 struct FilterRule {
     double (*f)(double);
-    double radius;    // S: the kernel function's support at scale 1
-    uint32_t reach;   // R: in_len * R <= kResizeMaxDown * out_len, so that S * max(scale, 1) <= kResizeMaxDown and K <= 129
+    double radius;  // S: the kernel function's support at scale 1 (geometry.hpp: resize_axis_ok keeps S * max(scale, 1) <= kResizeMaxDown)
 };
 static const FilterRule* filter_rule(uint32_t filter) {
-    static const FilterRule kRules[kResizeFilters] = {{f_triangle, 1.0, 1}, {nullptr, 0.0, 1},  {f_box, 0.5, 1},
-                                                      {f_hamming, 1.0, 1},  {f_bicubic, 2.0, 2}, {f_lanczos, 3.0, 3}};
+    static const FilterRule kRules[kResizeFilters] = {{f_triangle, 1.0}, {nullptr, 0.0}, {f_box, 0.5}, {f_hamming, 1.0}, {f_bicubic, 2.0}, {f_lanczos, 3.0}};
     return filter < kResizeFilters ? &kRules[filter] : nullptr;
-}
-bool resize_axis_ok(uint32_t filter, uint32_t in_len, uint32_t out_len) {
-    const FilterRule* r = filter_rule(filter);
-    return r && in_len && out_len && uint64_t(r->reach) * in_len <= uint64_t(kResizeMaxDown) * out_len;
 }
 
 // One pass over the outputs: every output's lo and its Q22 run (at most `span` taps) into lo_all / q_all, and K.
@@ -226,10 +220,14 @@ __device__ __forceinline__ uint32_t q22_round(int32_t acc) {
     return uint32_t(r);
 }
 
-// Horizontal pass: one lane per (frame, rectangle row, output x), all channels; lanes of a row read neighbouring weights (tap-major).
+// Horizontal pass: one lane per (entry, rectangle row, output x), all channels; lanes of a row read neighbouring weights (tap-major).
+// Entry f (blockIdx.y) reads its rectangle from box e.box -- its own frame's for a resized regions decode, the box of the view's frame
+// for a views decode, where several entries share a box -- and writes rows [0, rh) of mid[f], whose pitch mh is the launch's largest
+// rectangle height, not the box's.
 template <int C>
 __global__ __launch_bounds__(256) void k_resize_h(const uint8_t* __restrict__ box, uint8_t* __restrict__ mid, const ResizeFrame* __restrict__ tab,
-                                                  const int32_t* __restrict__ wts, uint32_t bw, uint32_t bh, uint32_t ow, uint32_t c_rt) {
+                                                  const int32_t* __restrict__ wts, uint32_t bw, uint32_t bh, uint32_t mh, uint32_t ow,
+                                                  uint32_t c_rt) {
     const uint32_t c = C ? uint32_t(C) : c_rt;
     const uint32_t f = blockIdx.y;
     const ResizeFrame& e = tab[f];
@@ -239,8 +237,8 @@ __global__ __launch_bounds__(256) void k_resize_h(const uint8_t* __restrict__ bo
     const uint32_t r = uint32_t(i / ow), x = uint32_t(i - uint64_t(r) * ow);
     const int32_t* lo = wts + e.hx;
     const int32_t* q = lo + ow + x;
-    const uint8_t* src = box + ((size_t(f) * bh + e.oy + r) * bw + e.ox + uint32_t(lo[x])) * c;
-    uint8_t* dst = mid + ((size_t(f) * bh + r) * ow + x) * c;
+    const uint8_t* src = box + ((size_t(e.box) * bh + e.oy + r) * bw + e.ox + uint32_t(lo[x])) * c;
+    uint8_t* dst = mid + ((size_t(f) * mh + r) * ow + x) * c;
     if constexpr (C == 4) {
         int32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0;
         for (uint32_t j = 0; j < kx; ++j) {
@@ -273,10 +271,10 @@ __global__ __launch_bounds__(256) void k_resize_h(const uint8_t* __restrict__ bo
 }
 
 // Vertical pass: one lane per output pixel, coalesced along x; a row's weights are the same for all its lanes.  The mirror is applied
-// on the store.
+// on the store.  Entry f reads mid[f] (pitch mh rows) and writes out[f].
 template <int C>
 __global__ __launch_bounds__(256) void k_resize_v(const uint8_t* __restrict__ mid, uint8_t* __restrict__ out, const ResizeFrame* __restrict__ tab,
-                                                  const int32_t* __restrict__ wts, uint32_t bh, uint32_t ow, uint32_t oh, uint32_t c_rt) {
+                                                  const int32_t* __restrict__ wts, uint32_t mh, uint32_t ow, uint32_t oh, uint32_t c_rt) {
     const uint32_t c = C ? uint32_t(C) : c_rt;
     const uint32_t f = blockIdx.y;
     const ResizeFrame& e = tab[f];
@@ -286,7 +284,7 @@ __global__ __launch_bounds__(256) void k_resize_v(const uint8_t* __restrict__ mi
     const int32_t* lo = wts + e.vy;
     const int32_t* q = lo + oh + y;
     const size_t stride = size_t(ow) * c;
-    const uint8_t* src = mid + ((size_t(f) * bh + uint32_t(lo[y])) * ow + x) * c;
+    const uint8_t* src = mid + ((size_t(f) * mh + uint32_t(lo[y])) * ow + x) * c;
     const uint32_t xo = (e.flags & 1u) ? ow - 1 - x : x;
     uint8_t* dst = out + ((size_t(f) * oh + y) * ow + xo) * c;
     if constexpr (C == 4) {
@@ -332,7 +330,7 @@ template <> struct Elem<4> { using T = uint32_t; };
 // aligned for it).  C = 1 / 3 / 4 copy the table to LDS (at most 4 KiB); the generic path (C = 0, any c up to 255) reads it where it lies.
 template <int C, int E, bool CHW>
 __global__ __launch_bounds__(256) void k_resize_v_out(const uint8_t* __restrict__ mid, void* __restrict__ out, const ResizeFrame* __restrict__ tab,
-                                                      const int32_t* __restrict__ wts, const uint32_t* __restrict__ table, uint32_t bh, uint32_t ow,
+                                                      const int32_t* __restrict__ wts, const uint32_t* __restrict__ table, uint32_t mh, uint32_t ow,
                                                       uint32_t oh, uint32_t c_rt) {
     using T = typename Elem<E>::T;
     const uint32_t c = C ? uint32_t(C) : c_rt;
@@ -350,7 +348,7 @@ __global__ __launch_bounds__(256) void k_resize_v_out(const uint8_t* __restrict_
     const int32_t* lo = wts + e.vy;
     const int32_t* q = lo + oh + y;
     const size_t stride = size_t(ow) * c;
-    const uint8_t* src = mid + ((size_t(f) * bh + uint32_t(lo[y])) * ow + x) * c;
+    const uint8_t* src = mid + ((size_t(f) * mh + uint32_t(lo[y])) * ow + x) * c;
     const uint32_t xo = (e.flags & 1u) ? ow - 1 - x : x;
     T* const o = static_cast<T*>(out);
     const size_t plane = size_t(oh) * ow, px = size_t(y) * ow + xo;  // (CHW: element [f][ch][y][xo] = (f * c + ch) * plane + px)
@@ -412,18 +410,18 @@ __global__ __launch_bounds__(256) void k_resize_v_out(const uint8_t* __restrict_
 
 template <int E, bool CHW>
 void launch_v_out(dim3 gv, hipStream_t stream, const uint8_t* d_mid, void* d_out, const ResizeFrame* d_tab, const int32_t* d_w, const uint32_t* d_table,
-                  uint32_t c, uint32_t bh, uint32_t ow, uint32_t oh, bool vec4) {
+                  uint32_t c, uint32_t mh, uint32_t ow, uint32_t oh, bool vec4) {
     const dim3 blk(256);
     switch (c) {
-        case 1: k_resize_v_out<1, E, CHW><<<gv, blk, 0, stream>>>(d_mid, d_out, d_tab, d_w, d_table, bh, ow, oh, c); break;
-        case 3: k_resize_v_out<3, E, CHW><<<gv, blk, 0, stream>>>(d_mid, d_out, d_tab, d_w, d_table, bh, ow, oh, c); break;
+        case 1: k_resize_v_out<1, E, CHW><<<gv, blk, 0, stream>>>(d_mid, d_out, d_tab, d_w, d_table, mh, ow, oh, c); break;
+        case 3: k_resize_v_out<3, E, CHW><<<gv, blk, 0, stream>>>(d_mid, d_out, d_tab, d_w, d_table, mh, ow, oh, c); break;
         case 4:
             if (CHW || vec4)
-                k_resize_v_out<4, E, CHW><<<gv, blk, 0, stream>>>(d_mid, d_out, d_tab, d_w, d_table, bh, ow, oh, c);
+                k_resize_v_out<4, E, CHW><<<gv, blk, 0, stream>>>(d_mid, d_out, d_tab, d_w, d_table, mh, ow, oh, c);
             else
-                k_resize_v_out<0, E, CHW><<<gv, blk, 0, stream>>>(d_mid, d_out, d_tab, d_w, d_table, bh, ow, oh, c);
+                k_resize_v_out<0, E, CHW><<<gv, blk, 0, stream>>>(d_mid, d_out, d_tab, d_w, d_table, mh, ow, oh, c);
             break;
-        default: k_resize_v_out<0, E, CHW><<<gv, blk, 0, stream>>>(d_mid, d_out, d_tab, d_w, d_table, bh, ow, oh, c); break;
+        default: k_resize_v_out<0, E, CHW><<<gv, blk, 0, stream>>>(d_mid, d_out, d_tab, d_w, d_table, mh, ow, oh, c); break;
     }
 }
 
@@ -431,64 +429,64 @@ void launch_v_out(dim3 gv, hipStream_t stream, const uint8_t* d_mid, void* d_out
 
 // The horizontal pass of both launchers.
 static hipError_t launch_h(const uint8_t* d_box, uint8_t* d_mid, const ResizeFrame* d_tab, const int32_t* d_w, uint32_t frames, uint32_t c, uint32_t bw,
-                           uint32_t bh, uint32_t ow, hipStream_t stream) {
-    const uint64_t hb = (uint64_t(bh) * ow + 255) / 256;
+                           uint32_t bh, uint32_t mh, uint32_t ow, hipStream_t stream) {
+    const uint64_t hb = (uint64_t(mh) * ow + 255) / 256;
     if (hb > 0x7FFFFFFFull) return hipErrorInvalidValue;
     const dim3 gh(uint32_t(hb), frames), blk(256);
     switch (c) {
-        case 1: k_resize_h<1><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, ow, c); break;
-        case 3: k_resize_h<3><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, ow, c); break;
-        case 4: k_resize_h<4><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, ow, c); break;
-        default: k_resize_h<0><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, ow, c); break;
+        case 1: k_resize_h<1><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, mh, ow, c); break;
+        case 3: k_resize_h<3><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, mh, ow, c); break;
+        case 4: k_resize_h<4><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, mh, ow, c); break;
+        default: k_resize_h<0><<<gh, blk, 0, stream>>>(d_box, d_mid, d_tab, d_w, bw, bh, mh, ow, c); break;
     }
     return hipSuccess;
 }
 
 hipError_t launch_resize(const uint8_t* d_box, uint8_t* d_mid, uint8_t* d_px, const ResizeFrame* d_tab, const int32_t* d_w, uint32_t frames,
-                         uint32_t c, uint32_t bw, uint32_t bh, uint32_t ow, uint32_t oh, hipStream_t stream) {
-    if (!frames || !c || !bw || !bh || !ow || !oh || frames > 65535) return hipErrorInvalidValue;
+                         uint32_t c, uint32_t bw, uint32_t bh, uint32_t mh, uint32_t ow, uint32_t oh, hipStream_t stream) {
+    if (!frames || !c || !bw || !bh || !mh || !ow || !oh || frames > 65535) return hipErrorInvalidValue;
     const uint64_t vb = (uint64_t(oh) * ow + 255) / 256;
     if (vb > 0x7FFFFFFFull) return hipErrorInvalidValue;
     const dim3 gv(uint32_t(vb), frames), blk(256);
     // (the box and the intermediate are the codec's own, 4-byte aligned; the output is the caller's: 32-bit stores only when aligned)
     const bool out4 = (reinterpret_cast<uintptr_t>(d_px) & 3u) == 0;
-    if (hipError_t err = launch_h(d_box, d_mid, d_tab, d_w, frames, c, bw, bh, ow, stream)) return err;
+    if (hipError_t err = launch_h(d_box, d_mid, d_tab, d_w, frames, c, bw, bh, mh, ow, stream)) return err;
     switch (c) {
-        case 1: k_resize_v<1><<<gv, blk, 0, stream>>>(d_mid, d_px, d_tab, d_w, bh, ow, oh, c); break;
-        case 3: k_resize_v<3><<<gv, blk, 0, stream>>>(d_mid, d_px, d_tab, d_w, bh, ow, oh, c); break;
+        case 1: k_resize_v<1><<<gv, blk, 0, stream>>>(d_mid, d_px, d_tab, d_w, mh, ow, oh, c); break;
+        case 3: k_resize_v<3><<<gv, blk, 0, stream>>>(d_mid, d_px, d_tab, d_w, mh, ow, oh, c); break;
         case 4:
             if (out4)
-                k_resize_v<4><<<gv, blk, 0, stream>>>(d_mid, d_px, d_tab, d_w, bh, ow, oh, c);
+                k_resize_v<4><<<gv, blk, 0, stream>>>(d_mid, d_px, d_tab, d_w, mh, ow, oh, c);
             else
-                k_resize_v<0><<<gv, blk, 0, stream>>>(d_mid, d_px, d_tab, d_w, bh, ow, oh, c);
+                k_resize_v<0><<<gv, blk, 0, stream>>>(d_mid, d_px, d_tab, d_w, mh, ow, oh, c);
             break;
-        default: k_resize_v<0><<<gv, blk, 0, stream>>>(d_mid, d_px, d_tab, d_w, bh, ow, oh, c); break;
+        default: k_resize_v<0><<<gv, blk, 0, stream>>>(d_mid, d_px, d_tab, d_w, mh, ow, oh, c); break;
     }
     return hipGetLastError();
 }
 
 hipError_t launch_resize_out(const uint8_t* d_box, uint8_t* d_mid, void* d_out, const ResizeFrame* d_tab, const int32_t* d_w, const void* d_table,
-                             const OutFormat& o, uint32_t frames, uint32_t c, uint32_t bw, uint32_t bh, uint32_t ow, uint32_t oh,
-                             hipStream_t stream) {
-    if (o.plain) return launch_resize(d_box, d_mid, static_cast<uint8_t*>(d_out), d_tab, d_w, frames, c, bw, bh, ow, oh, stream);
-    if (!frames || !c || c > 255 || !bw || !bh || !ow || !oh || frames > 65535 || !d_table) return hipErrorInvalidValue;
+                             const OutFormat& o, uint32_t frames, uint32_t c, uint32_t bw, uint32_t bh, uint32_t mh, uint32_t ow,
+                             uint32_t oh, hipStream_t stream) {
+    if (o.plain) return launch_resize(d_box, d_mid, static_cast<uint8_t*>(d_out), d_tab, d_w, frames, c, bw, bh, mh, ow, oh, stream);
+    if (!frames || !c || c > 255 || !bw || !bh || !mh || !ow || !oh || frames > 65535 || !d_table) return hipErrorInvalidValue;
     if ((reinterpret_cast<uintptr_t>(d_table) & 3u) || (reinterpret_cast<uintptr_t>(d_out) & (o.esize - 1))) return hipErrorInvalidValue;
     const uint64_t vb = (uint64_t(oh) * ow + 255) / 256;
     if (vb > 0x7FFFFFFFull) return hipErrorInvalidValue;
     const dim3 gv(uint32_t(vb), frames);
-    if (hipError_t err = launch_h(d_box, d_mid, d_tab, d_w, frames, c, bw, bh, ow, stream)) return err;
+    if (hipError_t err = launch_h(d_box, d_mid, d_tab, d_w, frames, c, bw, bh, mh, ow, stream)) return err;
     // (HWC at c = 4 stores a pixel's 4 elements at once: only where d_out is aligned to 4 elements)
     const bool vec4 = (reinterpret_cast<uintptr_t>(d_out) & (4 * o.esize - 1)) == 0;
     const uint32_t* t = static_cast<const uint32_t*>(d_table);
     const bool chw = o.layout == LLCOMP_MI_LAYOUT_CHW;
     if (o.esize == 1)  // (U8 CHW: U8 HWC is plain)
-        launch_v_out<1, true>(gv, stream, d_mid, d_out, d_tab, d_w, t, c, bh, ow, oh, vec4);
+        launch_v_out<1, true>(gv, stream, d_mid, d_out, d_tab, d_w, t, c, mh, ow, oh, vec4);
     else if (o.esize == 2)
-        chw ? launch_v_out<2, true>(gv, stream, d_mid, d_out, d_tab, d_w, t, c, bh, ow, oh, vec4)
-            : launch_v_out<2, false>(gv, stream, d_mid, d_out, d_tab, d_w, t, c, bh, ow, oh, vec4);
+        chw ? launch_v_out<2, true>(gv, stream, d_mid, d_out, d_tab, d_w, t, c, mh, ow, oh, vec4)
+            : launch_v_out<2, false>(gv, stream, d_mid, d_out, d_tab, d_w, t, c, mh, ow, oh, vec4);
     else
-        chw ? launch_v_out<4, true>(gv, stream, d_mid, d_out, d_tab, d_w, t, c, bh, ow, oh, vec4)
-            : launch_v_out<4, false>(gv, stream, d_mid, d_out, d_tab, d_w, t, c, bh, ow, oh, vec4);
+        chw ? launch_v_out<4, true>(gv, stream, d_mid, d_out, d_tab, d_w, t, c, mh, ow, oh, vec4)
+            : launch_v_out<4, false>(gv, stream, d_mid, d_out, d_tab, d_w, t, c, mh, ow, oh, vec4);
     return hipGetLastError();
 }
 
