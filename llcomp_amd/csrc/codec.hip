@@ -20,6 +20,7 @@
 #include "snapshot.hpp"
 #include "tables.hpp"
 #include "update.hpp"
+#include "windows_plan.hpp"
 
 using namespace llcomp_mi;
 
@@ -355,51 +356,9 @@ int regions_slot_queued(llcomp_mi_codec* k, uint32_t slot, hipStream_t s) {
     return LLCOMP_MI_OK;
 }
 
-// What a host-staged regions decode copies to the GPU in one piece (pinned slot -> d_stage): the per-frame table, the window slices'
-// lengths and payload offsets (in the order of the table: class by class, llcomp_mi_regions_gather), then their payload bytes.
-struct StageLayout {
-    uint64_t len_at, off_at, pay_at, bytes;
-    StageLayout(uint32_t frames, uint64_t slices, uint64_t payload) {
-        len_at = uint64_t(frames) * sizeof(RegionsFrame);
-        off_at = (len_at + 4 * slices + 7) & ~7ull;
-        pay_at = off_at + 8 * slices;
-        bytes = pay_at + payload;
-    }
-};
-// ... at most: every slice of the batch, each at the SLICED entry limit (the gather refuses a window entry above it)
-uint64_t stage_bound(const Geometry& g) { return StageLayout(g.frames, g.n_slices, uint64_t(g.n_slices) * (g.slice_cap - 16)).bytes; }
-// What a resized regions decode adds to the one copy at most, for outputs no larger than the image (ow <= w, oh <= h): 16 bytes of
-// alignment, and per frame its ResizeFrame and its weights -- out * (K + 1) int32 per axis, K <= 2 * S * max(in / out, 1) + 3 with the
-// filter's radius S <= 3 (Lanczos), so at most 6 * max(in, out) + 4 * out <= 10 * side of the image -- and the output format's table
-// behind them (16 bytes of alignment, at most 256 * c elements of 4 bytes).
-uint64_t resized_tables_bound(const Geometry& g) {
-    return 16 + uint64_t(g.frames) * (sizeof(ResizeFrame) + 4 * 10 * (uint64_t(g.w) + g.h)) + 16 + 256 * 4 * uint64_t(g.c);
-}
-// The staging buffer in HBM for `bytes`: grown to max(bytes, twice its size, at most `bound`) when too small (bound: stage_bound, plus
-// resized_tables_bound for a resized regions decode).  The old buffer may still be read by the codec's last call: that call is waited
-// for (only a call that grows the buffer waits).
-int ensure_stage(llcomp_mi_codec* k, uint64_t bytes, uint64_t bound) {
-    if (bytes <= k->stage_cap) return LLCOMP_MI_OK;
-    const uint64_t cap = std::max(bytes, std::min(2 * k->stage_cap, bound));
-    if (k->d_stage) {
-        if (k->done && k->done->ev && hipEventSynchronize(k->done->ev) != hipSuccess) return LLCOMP_MI_HIP_ERROR;
-        dev_free(k->d_stage);
-        k->allocated_bytes -= k->stage_cap;
-        k->d_stage = nullptr;
-        k->stage_cap = 0;
-    }
-    if (dev_alloc(reinterpret_cast<void**>(&k->d_stage), cap) != hipSuccess) {
-        k->d_stage = nullptr;
-        return LLCOMP_MI_NOMEM;
-    }
-    k->stage_cap = cap;
-    k->allocated_bytes += cap;
-    return LLCOMP_MI_OK;
-}
-
-// A resized regions decode's buffer `p` (cap bytes) for `bytes`: grown to max(bytes, twice its size, at most `bound`) when too small --
-// bound = frames * w * h * c, what the boxes never exceed and the horizontal pass's rows do not for ow <= w.  The old buffer may still be
-// used by the codec's last call: that call is waited for (only a call that grows a buffer waits).
+// A buffer `p` of the codec (cap bytes) for `bytes`: grown to max(bytes, twice its size, at most `bound`) when too small.  For the boxes and
+// the horizontal pass's rows of a resized regions decode bound = frames * w * h * c, what the boxes never exceed and the rows do not for
+// ow <= w.  The old buffer may still be used by the codec's last call: that call is waited for (only a call that grows a buffer waits).
 int ensure_grown(llcomp_mi_codec* k, uint8_t*& p, uint64_t& cap, uint64_t bytes, uint64_t bound) {
     if (bytes <= cap) return LLCOMP_MI_OK;
     const uint64_t want = std::max(bytes, std::min(2 * cap, bound));
@@ -419,82 +378,45 @@ int ensure_grown(llcomp_mi_codec* k, uint8_t*& p, uint64_t& cap, uint64_t bytes,
     return LLCOMP_MI_OK;
 }
 
-// One class of a regions decode: its sub-geometry, and its frames = entries [first, first + sub.frames) of the table.
-struct RegionsClass {
-    Geometry sub;
-    uint32_t first;
-};
-int regions_setup_sized(const llcomp_mi_codec* k, const uint32_t* rects, uint32_t wmax, uint32_t hmax, RegionsFrame* tab, RegionsClass* classes,
-                        uint32_t& n_classes, const uint32_t* used = nullptr, uint32_t n_used = 0);
-// Every frame's window and class (geometry.hpp: regions_window) -> `tab` (g.frames entries, class by class, frame order inside a class)
-// and the classes that have frames, in class order.  BAD_ARGS for a rectangle a frame does not hold; HIP_ERROR if a class's
-// sub-geometry would not fit the codec's workspace (regions_fits: never by default, checked all the same).
-int regions_setup(const llcomp_mi_codec* k, const uint32_t* xy, uint32_t rw, uint32_t rh, RegionsFrame* tab, RegionsClass* classes,
-                  uint32_t& n_classes) {
-    if (!xy) return LLCOMP_MI_BAD_ARGS;
-    std::vector<uint32_t> rects(4 * size_t(k->g.frames));
-    for (uint32_t f = 0; f < k->g.frames; ++f) {
-        rects[4 * f + 0] = xy[2 * f];
-        rects[4 * f + 1] = xy[2 * f + 1];
-        rects[4 * f + 2] = rw;
-        rects[4 * f + 3] = rh;
+// The staging buffer in HBM for `bytes` (bound: stage_bound, plus resized_tables_bound / views_tables_bound for a call with a resample tail)
+int ensure_stage(llcomp_mi_codec* k, uint64_t bytes, uint64_t bound) { return ensure_grown(k, k->d_stage, k->stage_cap, bytes, bound); }
+
+// The decode chain on geometry `sub` -- the codec's own, or the sub-geometry of a region, a box or a class -- in order on `s`: a state
+// generation of its own (a sub-geometry maps slices to lane groups differently, and the tagged tables are shared with the full decodes);
+// `locate`, which finds the slices' lengths `len` and stages their streams into d_scratch in stream lane order; the decoder, with the
+// bank cache's feedback behind it; and the inverse model into `sink(fused, samples)` -- samples: the lane-order array on the fused row
+// path, the image-order intermediate otherwise.
+template <class Locate, class Sink>
+int decode_chain(llcomp_mi_codec* k, const Geometry& sub, const uint32_t* len, uint32_t* d_status, hipStream_t s, Locate&& locate, Sink&& sink) {
+    {
+        Timed t(k, s, 7);
+        if (int rc = next_state_generation(k, s, slices_need_state_tables(sub))) return rc;
     }
-    return regions_setup_sized(k, rects.data(), rw, rh, tab, classes, n_classes);
+    {
+        Timed t(k, s, 4);
+        if (int rc = locate()) return rc;
+    }
+    {
+        Timed t(k, s, 5);
+        const bool cache = use_bank_cache(k, sub);
+        HIP_TRY(launch_decode_slices(sub, k->d_scratch, len, k->d_states, k->state_generation, static_cast<int16_t*>(k->d_lane_order), d_status,
+                                     k->d_counters, cache, s));
+        if (cache) queue_feedback(k, s);
+    }
+    Timed t(k, s, 6);
+    const bool fused = model_is_fused(sub);
+    if (!fused) HIP_TRY(launch_from_lane_order_i16(sub, static_cast<const int16_t*>(k->d_lane_order), static_cast<int16_t*>(k->d_sym_or_rec), s));
+    return sink(fused, static_cast<const int16_t*>(fused ? k->d_lane_order : k->d_sym_or_rec));
 }
-// ... with a rectangle of its own size per frame (rects = {x, y, rw, rh} per frame): every window is sized for the largest, wmax x hmax
-// (regions_window_sized), and the table's crop is a wmax x hmax BOX inside the window that contains the frame's rectangle, at
-// min(the rectangle's origin, the window's side - wmax) -- the rectangle's own origin when all sizes are equal.
-// used != nullptr (a views decode): a FRAME LIST -- only the n_used frames it names, in its order, get a table entry (`tab` holds n_used
-// of them), rects is still indexed by frame, and entry i's box goes to output slot i, not to its frame's: a frame that is not listed
-// has no entry, so none of its slices is touched.
-int regions_setup_sized(const llcomp_mi_codec* k, const uint32_t* rects, uint32_t wmax, uint32_t hmax, RegionsFrame* tab, RegionsClass* classes,
-                        uint32_t& n_classes, const uint32_t* used, uint32_t n_used) {
+// ... the locator of the calls that cut a box out of the full batch in HBM: the full geometry's group offsets, the box's slices in them
+int locate_box(llcomp_mi_codec* k, const Geometry& sub, const RegionBox& box, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+               uint32_t* d_status, hipStream_t s) {
     const Geometry& g = k->g;
-    if (!rects || (used && (!n_used || n_used > g.frames))) return LLCOMP_MI_BAD_ARGS;
-    const uint32_t m = used ? n_used : g.frames;
-    RegionBox win[kRegionsClasses];
-    uint32_t count[kRegionsClasses] = {}, cls = 0;
-    for (uint32_t i = 0; i < m; ++i) {
-        RegionBox b;
-        const uint32_t f = used ? used[i] : i;
-        if (f >= g.frames) return LLCOMP_MI_BAD_ARGS;
-        const uint32_t* r = rects + 4 * size_t(f);
-        if (!regions_window_sized(g.w, g.h, g.tile_w, g.tile_h, r[0], r[1], r[2], r[3], wmax, hmax, b, cls)) return LLCOMP_MI_BAD_ARGS;
-        win[cls] = b;  // (the window's size, all the sub-geometry depends on, is the class's)
-        ++count[cls];
-    }
-    uint32_t first[kRegionsClasses], next = 0;
-    const Geometry* sub_of[kRegionsClasses] = {};
-    n_classes = 0;
-    for (uint32_t c = 0; c < kRegionsClasses; ++c) {
-        first[c] = next;
-        next += count[c];
-        if (!count[c]) continue;
-        RegionsClass& rc = classes[n_classes++];
-        sub_of[c] = &rc.sub;
-        rc.first = first[c];
-        if (!regions_geometry(g, win[c], count[c], k->tune, rc.sub) || !regions_fits(g, rc.sub)) return LLCOMP_MI_HIP_ERROR;
-    }
-    for (uint32_t i = 0; i < m; ++i) {
-        RegionBox b;
-        const uint32_t f = used ? used[i] : i;
-        const uint32_t* r = rects + 4 * size_t(f);
-        (void)regions_window_sized(g.w, g.h, g.tile_w, g.tile_h, r[0], r[1], r[2], r[3], wmax, hmax, b, cls);
-        const uint32_t cx = r[0] - b.tx0 * g.tile_w, cy = r[1] - b.ty0 * g.tile_h;
-        // (sub.w >= wmax: a window of Wx tile columns is at least wmax pixels wide, also where it ends at a partial column)
-        const uint32_t bx = std::min(cx, sub_of[cls]->w >= wmax ? sub_of[cls]->w - wmax : 0u);
-        const uint32_t by = std::min(cy, sub_of[cls]->h >= hmax ? sub_of[cls]->h - hmax : 0u);
-        RegionsFrame& e = tab[first[cls]++];
-        e = RegionsFrame{f, b.tx0, b.ty0, bx, by, used ? i : f, cls, 0};
-    }
-    // (what the crop kernels rely on; the window contains the box by construction)
-    for (uint32_t i = 0; i < n_classes; ++i) {
-        const RegionsClass& rc = classes[i];
-        for (uint32_t j = 0; j < rc.sub.frames; ++j) {
-            const RegionsFrame& e = tab[rc.first + j];
-            if (uint64_t(e.cx0) + wmax > rc.sub.w || uint64_t(e.cy0) + hmax > rc.sub.h || e.out >= m || e.frame >= g.frames) return LLCOMP_MI_HIP_ERROR;
-        }
-    }
+    HIP_TRY(launch_group_sums(g, static_cast<const uint32_t*>(d_slice_len), k->d_group_off, s));
+    HIP_TRY(launch_scan_groups(g, k->d_group_off, k->d_total_tmp, s));
+    HIP_TRY(launch_region_index(g, sub, box, static_cast<const uint32_t*>(d_slice_len), k->d_group_off, k->d_region_len, k->d_region_off, s));
+    HIP_TRY(launch_stage_region_streams(sub, static_cast<const uint8_t*>(d_payload), payload_bytes, k->d_region_len, k->d_region_off, k->d_scratch,
+                                        d_status, s));
     return LLCOMP_MI_OK;
 }
 
@@ -508,11 +430,10 @@ struct RegionsSource {
     const uint32_t* staged_len;
     const uint64_t* staged_off;
 };
-// The launch chain of every class, in order on `s`: state generation, its slices to stream lane order, the decoder, the crops.
-// d_tab: the per-frame table in HBM (class by class, regions_setup).
+// The decode chain of every class, in order on `s`, each cropping rw x rh per entry into d_px.  d_tab: the per-frame table in HBM (class
+// by class, windows_plan.hpp: regions_setup_sized).
 int regions_classes(llcomp_mi_codec* k, const RegionsClass* classes, uint32_t n_classes, const RegionsFrame* d_tab, const RegionsSource& src,
                     uint32_t rw, uint32_t rh, uint8_t* d_px, uint32_t* d_status, hipStream_t s) {
-    const Geometry& g = k->g;
     uint64_t base = 0;  // the class's first slice in the staged arrays
     for (uint32_t i = 0; i < n_classes; ++i) {
         const Geometry& sub = classes[i].sub;
@@ -520,203 +441,127 @@ int regions_classes(llcomp_mi_codec* k, const RegionsClass* classes, uint32_t n_
         const uint32_t* len = src.full_len ? k->d_region_len : src.staged_len + base;
         const uint64_t* off = src.full_len ? k->d_region_off : src.staged_off + base;
         base += sub.n_slices;
-        {
-            Timed t(k, s, 7);
-            if (int rc = next_state_generation(k, s, slices_need_state_tables(sub))) return rc;
-        }
-        {
-            Timed t(k, s, 4);
-            if (src.full_len)
-                HIP_TRY(launch_regions_index(g, sub, c_tab, src.full_len, k->d_group_off, k->d_region_len, k->d_region_off, s));
-            HIP_TRY(launch_stage_region_streams(sub, src.payload, src.payload_bytes, len, off, k->d_scratch, d_status, s));
-        }
-        {
-            Timed t(k, s, 5);
-            const bool cache = use_bank_cache(k, sub);
-            HIP_TRY(launch_decode_slices(sub, k->d_scratch, len, k->d_states, k->state_generation, static_cast<int16_t*>(k->d_lane_order), d_status,
-                                         k->d_counters, cache, s));
-            if (cache) queue_feedback(k, s);
-        }
-        {
-            Timed t(k, s, 6);
-            if (model_is_fused(sub)) {
-                HIP_TRY(launch_model_rows_inv_crops(sub, static_cast<const int16_t*>(k->d_lane_order), d_px, c_tab, rw, rh, s));
-            } else {
-                HIP_TRY(launch_from_lane_order_i16(sub, static_cast<const int16_t*>(k->d_lane_order), static_cast<int16_t*>(k->d_sym_or_rec), s));
-                HIP_TRY(launch_model_inv_crops(sub, static_cast<const int16_t*>(k->d_sym_or_rec), d_px, c_tab, rw, rh, s));
-            }
-        }
+        const int rc = decode_chain(
+            k, sub, len, d_status, s,
+            [&]() -> int {
+                if (src.full_len)
+                    HIP_TRY(launch_regions_index(k->g, sub, c_tab, src.full_len, k->d_group_off, k->d_region_len, k->d_region_off, s));
+                HIP_TRY(launch_stage_region_streams(sub, src.payload, src.payload_bytes, len, off, k->d_scratch, d_status, s));
+                return LLCOMP_MI_OK;
+            },
+            [&](bool fused, const int16_t* v) -> int {
+                HIP_TRY(fused ? launch_model_rows_inv_crops(sub, v, d_px, c_tab, rw, rh, s) : launch_model_inv_crops(sub, v, d_px, c_tab, rw, rh, s));
+                return LLCOMP_MI_OK;
+            });
+        if (rc) return rc;
     }
     return LLCOMP_MI_OK;
 }
 
-// Everything of a resized regions decode the host decides: every frame's window, class and box (regions_setup_sized, sized for the
-// batch's largest rectangle wmax x hmax), its rectangle inside the box, its flags, its weights (resize.hpp) and the output format's table.
-// BAD_ARGS for a null rects, an output side of 0, any rectangle outside the image, a filter code above 5 in a frame's flags, a downscale
-// above the frame's filter's limit on either axis (resize.hpp: resize_axis_ok), a bad
-// output format (check_output_format) and an output not aligned to the format's element size.
-struct ResizedPlan {
-    std::vector<RegionsFrame> tab;
-    RegionsClass classes[kRegionsClasses];
-    uint32_t n_classes = 0, wmax = 0, hmax = 0;
-    std::vector<ResizeFrame> rs;  // frame order
-    std::vector<int32_t> w;
-    OutFormat out;
-    std::vector<uint8_t> table;  // empty for the plain u8 HWC output
-    uint64_t box_bytes = 0, mid_bytes = 0;
-    // what the one copy carries, behind the regions table (or behind the staged payload): [ResizeFrame[frames]][int32 weights], then the
-    // output table at the next multiple of 16 (table_at, relative to the ResizeFrames) where there is one
-    uint64_t table_at() const { return (uint64_t(rs.size()) * sizeof(ResizeFrame) + 4 * uint64_t(w.size()) + 15) & ~15ull; }
-    uint64_t bytes() const {
-        return table.empty() ? uint64_t(rs.size()) * sizeof(ResizeFrame) + 4 * uint64_t(w.size()) : table_at() + table.size();
-    }
-    void put(uint8_t* at) const {
-        std::memcpy(at, rs.data(), rs.size() * sizeof(ResizeFrame));
-        std::memcpy(at + rs.size() * sizeof(ResizeFrame), w.data(), 4 * w.size());
-        if (!table.empty()) std::memcpy(at + table_at(), table.data(), table.size());
-    }
-};
-int resized_setup(const llcomp_mi_codec* k, const uint32_t* rects, const uint8_t* flags, uint32_t ow, uint32_t oh, const llcomp_mi_output_format* fmt,
-                  const void* d_out, ResizedPlan& p) {
-    const Geometry& g = k->g;
-    if (int rc = check_output_format(fmt, g.c, p.out)) return rc;
-    if (reinterpret_cast<uintptr_t>(d_out) & (p.out.esize - 1)) return LLCOMP_MI_BAD_ARGS;
-    if (!rects || !ow || !oh || g.frames > 65535) return LLCOMP_MI_BAD_ARGS;
-    for (uint32_t f = 0; f < g.frames; ++f) {
-        const uint32_t rw = rects[4 * f + 2], rh = rects[4 * f + 3], filter = flags ? LLCOMP_MI_FLAG_FILTER_OF(flags[f]) : 0u;
-        // (an empty rectangle is regions_setup_sized's to refuse; an unknown filter and a downscale above the filter's limit are refused here)
-        if (filter >= kResizeFilters || (rw && !resize_axis_ok(filter, rw, ow)) || (rh && !resize_axis_ok(filter, rh, oh))) return LLCOMP_MI_BAD_ARGS;
-        p.wmax = std::max(p.wmax, rw);
-        p.hmax = std::max(p.hmax, rh);
-    }
-    p.tab.resize(g.frames);
-    if (int rc = regions_setup_sized(k, rects, p.wmax, p.hmax, p.tab.data(), p.classes, p.n_classes)) return rc;
-    p.rs.assign(g.frames, ResizeFrame{});
-    std::vector<uint32_t> seen;  // (axes already computed in this call)
-    for (const RegionsFrame& e : p.tab) {
-        const uint32_t* r = rects + 4 * size_t(e.frame);
-        ResizeFrame& z = p.rs[e.frame];
-        z.ox = r[0] - e.wx0 * g.tile_w - e.cx0;
-        z.oy = r[1] - e.wy0 * g.tile_h - e.cy0;
-        z.flags = flags ? flags[e.frame] & (1u | LLCOMP_MI_FLAG_FILTER_MASK) : 0u;
-        z.box = e.out;  // (the frame's own box)
-        if (!resize_frame_weights(LLCOMP_MI_FLAG_FILTER_OF(z.flags), r[2], r[3], ow, oh, z, p.w, seen)) return LLCOMP_MI_BAD_ARGS;
-        if (uint64_t(z.ox) + z.rw > p.wmax || uint64_t(z.oy) + z.rh > p.hmax) return LLCOMP_MI_HIP_ERROR;  // (the box holds it by construction)
-    }
-    p.box_bytes = uint64_t(g.frames) * p.wmax * p.hmax * g.c;
-    p.mid_bytes = uint64_t(g.frames) * p.hmax * ow * g.c;
-    p.table.resize(p.out.table_bytes(g.c));
-    if (!p.table.empty()) output_table(fmt, g.c, p.out, p.table.data());
-    return LLCOMP_MI_OK;
-}
-
-// Everything of a views decode the host decides (include/llcomp_mi.h: llcomp_mi_codec_decode_views): the union rectangle of every used
-// frame (container.cpp: views_union), the regions table of the USED frames alone (regions_setup_sized with the frame list, sized for the
-// largest union: entry i cuts its frame's box into d_box[i]), and per group its views' entries -- each names its frame's box and its
-// rectangle inside it -- with the weights of the whole call in one array (an axis is shared across views AND groups: `seen` lives for
-// the call) and the groups' output tables.  A group whose rows [n][mh][ow][c] (mh: ITS largest view height) would pass frames * w * h * c
-// is resampled `chunk` views at a time, so d_mid keeps its bound for ow <= w (one view: mh * ow * c <= h * w * c).
-// BAD_ARGS: views_union's cases, a bad output format, a group's d_out NULL or not aligned to its element size.
-struct ViewsGroup {
-    uint32_t n = 0, ow = 0, oh = 0, mh = 0, chunk = 0, first = 0;  // first: the group's first entry in rs
-    OutFormat out;
-    void* d_out = nullptr;
-    uint64_t table_at = 0;  // in `tables`
-};
-struct ViewsPlan {
-    ViewsUnion u;
-    std::vector<RegionsFrame> tab;
-    RegionsClass classes[kRegionsClasses];
-    uint32_t n_classes = 0;
-    std::vector<ViewsGroup> groups;
-    std::vector<ResizeFrame> rs;  // group by group, view order
-    std::vector<int32_t> w;
-    std::vector<uint8_t> tables;  // every formatted group's table, each at a multiple of 16
-    uint64_t box_bytes = 0, mid_bytes = 0;
-    // what the one copy carries behind the regions table (or behind the staged payload): [ResizeFrame[views]][int32 weights], then the
-    // output tables at the next multiple of 16
-    uint64_t w_at() const { return uint64_t(rs.size()) * sizeof(ResizeFrame); }
-    uint64_t tables_at() const { return (w_at() + 4 * uint64_t(w.size()) + 15) & ~15ull; }
-    uint64_t bytes() const { return tables.empty() ? w_at() + 4 * uint64_t(w.size()) : tables_at() + tables.size(); }
-    void put(uint8_t* at) const {
-        std::memcpy(at, rs.data(), rs.size() * sizeof(ResizeFrame));
-        std::memcpy(at + w_at(), w.data(), 4 * w.size());
-        if (!tables.empty()) std::memcpy(at + tables_at(), tables.data(), tables.size());
-    }
-};
-int views_setup(const llcomp_mi_codec* k, const llcomp_mi_view_group* groups, uint32_t n_groups, ViewsPlan& p) {
-    const Geometry& g = k->g;
-    if (int rc = views_union(g.w, g.h, g.frames, groups, n_groups, p.u)) return rc;
-    p.groups.resize(n_groups);
-    for (uint32_t gi = 0; gi < n_groups; ++gi) {
-        const llcomp_mi_view_group& gr = *view_group_at(groups, gi);
-        ViewsGroup& vg = p.groups[gi];
-        if (int rc = check_output_format(gr.fmt, g.c, vg.out)) return rc;
-        if (!gr.d_out || (reinterpret_cast<uintptr_t>(gr.d_out) & (vg.out.esize - 1))) return LLCOMP_MI_BAD_ARGS;
-    }
-    const uint32_t n_used = uint32_t(p.u.used.size());
-    p.tab.resize(n_used);
-    if (int rc = regions_setup_sized(k, p.u.rects.data(), p.u.wmax, p.u.hmax, p.tab.data(), p.classes, p.n_classes, p.u.used.data(), n_used))
-        return rc;
-    std::vector<uint32_t> entry_of(g.frames, 0);  // a used frame's entry of the regions table
-    for (uint32_t i = 0; i < n_used; ++i) entry_of[p.tab[i].frame] = i;
-    const uint64_t samples = uint64_t(g.frames) * g.w * g.h * g.c;
-    std::vector<uint32_t> seen;  // (axes already computed in this call)
-    p.rs.reserve(size_t(p.u.total_views));
-    for (uint32_t gi = 0; gi < n_groups; ++gi) {
-        const llcomp_mi_view_group& gr = *view_group_at(groups, gi);
-        ViewsGroup& vg = p.groups[gi];
-        vg.n = gr.n_views;
-        vg.ow = gr.ow;
-        vg.oh = gr.oh;
-        vg.d_out = gr.d_out;
-        vg.first = uint32_t(p.rs.size());
-        for (uint32_t i = 0; i < gr.n_views; ++i) {
-            const llcomp_mi_view& v = gr.views[i];
-            const RegionsFrame& e = p.tab[entry_of[v.frame]];
-            ResizeFrame z{};
-            z.ox = v.x - e.wx0 * g.tile_w - e.cx0;  // (the box starts at or before the union's origin, which no view starts before)
-            z.oy = v.y - e.wy0 * g.tile_h - e.cy0;
-            z.flags = v.flags & (1u | LLCOMP_MI_FLAG_FILTER_MASK);
-            z.box = e.out;
-            if (!resize_frame_weights(LLCOMP_MI_FLAG_FILTER_OF(z.flags), v.rw, v.rh, gr.ow, gr.oh, z, p.w, seen)) return LLCOMP_MI_BAD_ARGS;
-            // (the box holds the union, and the union the view, by construction)
-            if (e.frame != v.frame || uint64_t(z.ox) + z.rw > p.u.wmax || uint64_t(z.oy) + z.rh > p.u.hmax || z.box >= n_used) return LLCOMP_MI_HIP_ERROR;
-            vg.mh = std::max(vg.mh, v.rh);
-            p.rs.push_back(z);
-        }
-        const uint64_t per_view = uint64_t(vg.mh) * vg.ow * g.c;
-        vg.chunk = uint32_t(std::min<uint64_t>(vg.n, std::max<uint64_t>(samples / per_view, 1)));
-        p.mid_bytes = std::max(p.mid_bytes, vg.chunk * per_view);
-        if (!vg.out.plain) {
-            vg.table_at = (p.tables.size() + 15) & ~size_t(15);
-            p.tables.resize(vg.table_at + vg.out.table_bytes(g.c));
-            output_table(gr.fmt, g.c, vg.out, p.tables.data() + vg.table_at);
-        }
-    }
-    p.box_bytes = uint64_t(n_used) * p.u.wmax * p.u.hmax * g.c;
-    return LLCOMP_MI_OK;
-}
-// What the staged tables of a views decode add per view beyond `frames` (include/llcomp_mi.h: llcomp_mi_codec_views_workspace_bytes): its
-// entry, its weights at resized_tables_bound's upper bound, and an output table with its alignment.
-uint64_t view_term(const Geometry& g) { return sizeof(ResizeFrame) + 4 * 10 * (uint64_t(g.w) + g.h) + 16 + 256 * 4 * uint64_t(g.c); }
-uint64_t views_tables_bound(const Geometry& g, uint64_t total_views) {
-    return resized_tables_bound(g) + (total_views > g.frames ? (total_views - g.frames) * view_term(g) : 0);
-}
-// The resample passes of a views decode, group by group and chunk by chunk, behind the classes: d_block is ViewsPlan::put's copy in HBM.
-int views_resample(llcomp_mi_codec* k, const ViewsPlan& p, const uint8_t* d_block, hipStream_t s) {
+// The resample passes of a tail, group by group and chunk by chunk, behind the classes: d_block is the tail's block in HBM.
+int windows_resample(llcomp_mi_codec* k, const WindowsPlan& p, const ResampleTail& tail, const uint8_t* d_block, hipStream_t s) {
     const Geometry& g = k->g;
     const ResizeFrame* d_rs = reinterpret_cast<const ResizeFrame*>(d_block);
-    const int32_t* d_w = reinterpret_cast<const int32_t*>(d_block + p.w_at());
+    const int32_t* d_w = reinterpret_cast<const int32_t*>(d_block + tail.block.w_at());
     Timed t(k, s, 6);
-    for (const ViewsGroup& vg : p.groups) {
+    for (const ResampleGroup& vg : tail.groups) {
         const uint64_t view_bytes = uint64_t(vg.oh) * vg.ow * g.c * vg.out.esize;
         for (uint32_t at = 0; at < vg.n; at += vg.chunk) {
             const uint32_t cnt = std::min(vg.chunk, vg.n - at);
             HIP_TRY(launch_resize_out(k->d_box, k->d_mid, static_cast<uint8_t*>(vg.d_out) + at * view_bytes, d_rs + vg.first + at, d_w,
-                                      d_block + p.tables_at() + vg.table_at, vg.out, cnt, g.c, p.u.wmax, p.u.hmax, vg.mh, vg.ow, vg.oh, s));
+                                      d_block + tail.block.tables_at() + vg.table_at, vg.out, cnt, g.c, p.wmax, p.hmax, vg.mh, vg.ow, vg.oh, s));
         }
     }
+    return LLCOMP_MI_OK;
+}
+
+// Where a windowed decode finds its slices: the full batch in HBM (d_payload, payload_bytes, d_slice_len), or host containers with the
+// gather planned over the plan's windows (data, gather; d_payload is null then).
+struct WindowsSource {
+    const void* d_payload;
+    uint64_t payload_bytes;
+    const void* d_slice_len;
+    const uint8_t* const* data;
+    const RegionsGather* gather;
+};
+// The containers of a host source have to be of the codec's shape, tiling, planar setting and model ...
+bool same_shape(const Geometry& g, const Geometry& cg) {
+    return cg.w == g.w && cg.h == g.h && cg.c == g.c && cg.tile_w == g.tile_w && cg.tile_h == g.tile_h && cg.planar == g.planar &&
+           (cg.flags & kGeoSmallModel) == (g.flags & kGeoSmallModel);
+}
+// ... and the gather's slices the classes' (its order is the table's: class by class, and a class's slices are its sub-geometry's)
+bool gather_matches(const WindowsPlan& p, const RegionsGather& gp) {
+    uint64_t sub_slices = 0;
+    for (uint32_t i = 0; i < p.n_classes; ++i) sub_slices += p.classes[i].sub.n_slices;
+    return sub_slices == gp.n_slices;
+}
+
+// the plan of a plain regions decode: every class crops the rectangle itself
+int regions_plan(const llcomp_mi_codec* k, const uint32_t* xy, uint32_t rw, uint32_t rh, WindowsPlan& p) {
+    p.tab.resize(k->g.frames);
+    p.wmax = rw;
+    p.hmax = rh;
+    return regions_setup(k->g, k->tune, xy, rw, rh, p.tab.data(), p.classes, p.n_classes);
+}
+
+// The driver of every windowed decode (DESIGN.md "Region decode"): plan `p` -- every class crops p.wmax x p.hmax per entry -- from `src`,
+// into d_px, or with a tail into the boxes that the tail's groups are resampled from.  Everything the kernels read from the host crosses
+// in ONE copy out of a slot of the pinned ring (windows_plan.hpp: CopyLayout): the regions table; for a host source the window slices'
+// lengths, offsets and payload bytes behind it, so the classes read their slices straight from the copy and no group sums run; and the
+// tail's block at the next multiple of 16.  The copy lands in d_stage, grown up to stage_bound + tables_bound -- but the table alone of
+// a plain call from HBM in d_regions.  Each class takes a state generation of its own; for a source in HBM the full geometry's group
+// offsets are found once, ahead of the first class.
+int decode_windows(llcomp_mi_codec* k, const WindowsPlan& p, const ResampleTail* tail, uint64_t tables_bound, const WindowsSource& src, void* d_px,
+                   void* d_status, void* stream) {
+    const Geometry& g = k->g;
+    const RegionsGather* gp = src.gather;
+    const CopyLayout cl(p.tab.size(), gp, tail);
+    const StageLayout& lay = cl.stage;
+    const uint64_t rs_at = cl.rs_at, bytes = cl.bytes;
+    const bool table_only = !gp && !tail;
+    const uint64_t bound = table_only ? 0 : stage_bound(g) + tables_bound;
+    DeviceGuard guard(k->device);
+    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
+    if (!gp)
+        if (int rc = ensure_region_arrays(k)) return rc;
+    if (int rc = tail ? ensure_regions_ring(k) : ensure_regions_table(k)) return rc;
+    if (!table_only)
+        if (int rc = ensure_stage(k, bytes, bound)) return rc;
+    if (tail) {
+        const uint64_t samples = uint64_t(g.frames) * g.w * g.h * g.c;
+        if (int rc = ensure_grown(k, k->d_box, k->box_cap, tail->box_bytes, samples)) return rc;
+        if (int rc = ensure_grown(k, k->d_mid, k->mid_cap, tail->mid_bytes, samples)) return rc;
+    }
+    uint32_t slot = 0;
+    if (int rc = regions_slot_take(k, bytes, bound, slot)) return rc;
+    uint8_t* h = k->h_regions[slot];
+    std::memcpy(h, p.tab.data(), p.tab.size() * sizeof(RegionsFrame));
+    if (gp) regions_gather_copy(*gp, src.data, h + lay.pay_at, reinterpret_cast<uint32_t*>(h + lay.len_at), reinterpret_cast<uint64_t*>(h + lay.off_at));
+    if (tail) tail->block.put(h + rs_at);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint8_t* const d_copy = table_only ? reinterpret_cast<uint8_t*>(k->d_regions) : k->d_stage;
+    DoneGuard done_guard{k, s};
+    HIP_TRY(hipMemsetAsync(d_status, 0, 4, s));
+    {
+        Timed t(k, s, 4);
+        HIP_TRY(hipMemcpyAsync(d_copy, h, bytes, hipMemcpyHostToDevice, s));
+        if (int rc = regions_slot_queued(k, slot, s)) return rc;
+        if (!gp) {
+            HIP_TRY(launch_group_sums(g, static_cast<const uint32_t*>(src.d_slice_len), k->d_group_off, s));
+            HIP_TRY(launch_scan_groups(g, k->d_group_off, k->d_total_tmp, s));
+        }
+    }
+    if (gp) k->host_counters[LLCOMP_MI_CTR_HOST_STAGED_BYTES] += gp->payload_bytes;
+    const RegionsSource from = gp ? RegionsSource{d_copy + lay.pay_at, gp->payload_bytes, nullptr, reinterpret_cast<const uint32_t*>(d_copy + lay.len_at),
+                                                  reinterpret_cast<const uint64_t*>(d_copy + lay.off_at)}
+                                  : RegionsSource{static_cast<const uint8_t*>(src.d_payload), src.payload_bytes,
+                                                  static_cast<const uint32_t*>(src.d_slice_len), nullptr, nullptr};
+    if (int rc = regions_classes(k, p.classes, p.n_classes, reinterpret_cast<const RegionsFrame*>(d_copy), from, p.wmax, p.hmax,
+                                 tail ? k->d_box : static_cast<uint8_t*>(d_px), static_cast<uint32_t*>(d_status), s))
+        return rc;
+    if (tail)
+        if (int rc = windows_resample(k, p, *tail, k->d_stage + rs_at, s)) return rc;
+    ++k->n_decode;
     return LLCOMP_MI_OK;
 }
 
@@ -1092,38 +937,20 @@ int llcomp_mi_codec_decode(llcomp_mi_codec* k, const void* d_payload, uint64_t p
     const Geometry& g = k->g;
     DoneGuard done_guard{k, s};
     HIP_TRY(hipMemsetAsync(d_status, 0, 4, s));
-    {
-        Timed t(k, s, 7);
-        if (int rc = next_state_generation(k, s, k->need_states)) return rc;
-    }
-    {
-        Timed t(k, s, 4);
-        HIP_TRY(launch_group_sums(g, static_cast<const uint32_t*>(d_slice_len), k->d_group_off, s));
-        HIP_TRY(launch_scan_groups(g, k->d_group_off, k->d_total_tmp, s));
-    }
-    {
-        Timed t(k, s, 4);
-        HIP_TRY(launch_stage_streams(g, static_cast<const uint8_t*>(d_payload), payload_bytes,
-                                     static_cast<const uint32_t*>(d_slice_len), k->d_group_off, k->d_scratch,
-                                     static_cast<uint32_t*>(d_status), s));
-    }
-    {
-        Timed t(k, s, 5);
-        const bool cache = use_bank_cache(k, g);
-        HIP_TRY(launch_decode_slices(g, k->d_scratch, static_cast<const uint32_t*>(d_slice_len), k->d_states, k->state_generation,
-                                     static_cast<int16_t*>(k->d_lane_order), static_cast<uint32_t*>(d_status), k->d_counters, cache, s));
-        if (cache) queue_feedback(k, s);
-    }
-    {
-        Timed t(k, s, 6);
-        if (model_is_fused(g)) {
-            HIP_TRY(launch_model_rows_inv(g, static_cast<const int16_t*>(k->d_lane_order), static_cast<uint8_t*>(d_px), s));
-        } else {
-            HIP_TRY(launch_from_lane_order_i16(g, static_cast<const int16_t*>(k->d_lane_order),
-                                               static_cast<int16_t*>(k->d_sym_or_rec), s));
-            HIP_TRY(launch_model_inv(g, static_cast<const int16_t*>(k->d_sym_or_rec), static_cast<uint8_t*>(d_px), s));
-        }
-    }
+    const int rc = decode_chain(
+        k, g, static_cast<const uint32_t*>(d_slice_len), static_cast<uint32_t*>(d_status), s,
+        [&]() -> int {
+            HIP_TRY(launch_group_sums(g, static_cast<const uint32_t*>(d_slice_len), k->d_group_off, s));
+            HIP_TRY(launch_scan_groups(g, k->d_group_off, k->d_total_tmp, s));
+            HIP_TRY(launch_stage_streams(g, static_cast<const uint8_t*>(d_payload), payload_bytes, static_cast<const uint32_t*>(d_slice_len),
+                                         k->d_group_off, k->d_scratch, static_cast<uint32_t*>(d_status), s));
+            return LLCOMP_MI_OK;
+        },
+        [&](bool fused, const int16_t* v) -> int {
+            HIP_TRY(fused ? launch_model_rows_inv(g, v, static_cast<uint8_t*>(d_px), s) : launch_model_inv(g, v, static_cast<uint8_t*>(d_px), s));
+            return LLCOMP_MI_OK;
+        });
+    if (rc) return rc;
     ++k->n_decode;
     return LLCOMP_MI_OK;
 }
@@ -1152,37 +979,16 @@ int llcomp_mi_codec_decode_region(llcomp_mi_codec* k, const void* d_payload, uin
     const Geometry& g = k->g;
     DoneGuard done_guard{k, s};
     HIP_TRY(hipMemsetAsync(d_status, 0, 4, s));
-    {
-        // (a generation of its own: the sub-geometry maps slices to lane groups differently, and the tagged tables are shared with
-        // the full decodes)
-        Timed t(k, s, 7);
-        if (int rc = next_state_generation(k, s, slices_need_state_tables(sub))) return rc;
-    }
-    {
-        Timed t(k, s, 4);
-        HIP_TRY(launch_group_sums(g, static_cast<const uint32_t*>(d_slice_len), k->d_group_off, s));
-        HIP_TRY(launch_scan_groups(g, k->d_group_off, k->d_total_tmp, s));
-        HIP_TRY(launch_region_index(g, sub, box, static_cast<const uint32_t*>(d_slice_len), k->d_group_off, k->d_region_len, k->d_region_off, s));
-        HIP_TRY(launch_stage_region_streams(sub, static_cast<const uint8_t*>(d_payload), payload_bytes, k->d_region_len, k->d_region_off,
-                                            k->d_scratch, static_cast<uint32_t*>(d_status), s));
-    }
-    {
-        Timed t(k, s, 5);
-        const bool cache = use_bank_cache(k, sub);
-        HIP_TRY(launch_decode_slices(sub, k->d_scratch, k->d_region_len, k->d_states, k->state_generation, static_cast<int16_t*>(k->d_lane_order),
-                                     static_cast<uint32_t*>(d_status), k->d_counters, cache, s));
-        if (cache) queue_feedback(k, s);
-    }
-    {
-        Timed t(k, s, 6);
-        const Crop cr{x - box.tx0 * g.tile_w, y - box.ty0 * g.tile_h, rw, rh};
-        if (model_is_fused(sub)) {
-            HIP_TRY(launch_model_rows_inv_crop(sub, static_cast<const int16_t*>(k->d_lane_order), static_cast<uint8_t*>(d_px), cr, s));
-        } else {
-            HIP_TRY(launch_from_lane_order_i16(sub, static_cast<const int16_t*>(k->d_lane_order), static_cast<int16_t*>(k->d_sym_or_rec), s));
-            HIP_TRY(launch_model_inv_crop(sub, static_cast<const int16_t*>(k->d_sym_or_rec), static_cast<uint8_t*>(d_px), cr, s));
-        }
-    }
+    const int rc = decode_chain(
+        k, sub, k->d_region_len, static_cast<uint32_t*>(d_status), s,
+        [&]() -> int { return locate_box(k, sub, box, d_payload, payload_bytes, d_slice_len, static_cast<uint32_t*>(d_status), s); },
+        [&](bool fused, const int16_t* v) -> int {
+            const Crop cr{x - box.tx0 * g.tile_w, y - box.ty0 * g.tile_h, rw, rh};
+            HIP_TRY(fused ? launch_model_rows_inv_crop(sub, v, static_cast<uint8_t*>(d_px), cr, s)
+                          : launch_model_inv_crop(sub, v, static_cast<uint8_t*>(d_px), cr, s));
+            return LLCOMP_MI_OK;
+        });
+    if (rc) return rc;
     ++k->n_decode;
     return LLCOMP_MI_OK;
 }
@@ -1215,36 +1021,16 @@ int update_box_pixels(llcomp_mi_codec* k, const UpdatePlan& p, const void* d_pay
         *d_box_px = d_rect;
         return LLCOMP_MI_OK;
     }
-    {
-        Timed t(k, s, 7);
-        if (int rc = next_state_generation(k, s, slices_need_state_tables(sub))) return rc;
-    }
-    {
-        Timed t(k, s, 4);
-        HIP_TRY(launch_group_sums(g, static_cast<const uint32_t*>(d_slice_len), k->d_group_off, s));
-        HIP_TRY(launch_scan_groups(g, k->d_group_off, k->d_total_tmp, s));
-        HIP_TRY(launch_region_index(g, sub, p.box, static_cast<const uint32_t*>(d_slice_len), k->d_group_off, k->d_region_len, k->d_region_off, s));
-        HIP_TRY(launch_stage_region_streams(sub, static_cast<const uint8_t*>(d_payload), payload_bytes, k->d_region_len, k->d_region_off,
-                                            k->d_scratch, d_status, s));
-    }
-    {
-        Timed t(k, s, 5);
-        const bool cache = use_bank_cache(k, sub);
-        HIP_TRY(launch_decode_slices(sub, k->d_scratch, k->d_region_len, k->d_states, k->state_generation, static_cast<int16_t*>(k->d_lane_order),
-                                     d_status, k->d_counters, cache, s));
-        if (cache) queue_feedback(k, s);
-    }
-    {
-        Timed t(k, s, 6);
-        if (model_is_fused(sub)) {
-            HIP_TRY(launch_model_rows_inv(sub, static_cast<const int16_t*>(k->d_lane_order), k->d_box, s));
-        } else {
-            HIP_TRY(launch_from_lane_order_i16(sub, static_cast<const int16_t*>(k->d_lane_order), static_cast<int16_t*>(k->d_sym_or_rec), s));
-            HIP_TRY(launch_model_inv(sub, static_cast<const int16_t*>(k->d_sym_or_rec), k->d_box, s));
-        }
-        HIP_TRY(launch_paste_rect(static_cast<const uint8_t*>(d_rect), k->d_box, sub.frames, sub.c, rw, rh, sub.w, sub.h, x - p.box.tx0 * g.tile_w,
-                                  y - p.box.ty0 * g.tile_h, s));
-    }
+    const int rc = decode_chain(
+        k, sub, k->d_region_len, d_status, s,
+        [&]() -> int { return locate_box(k, sub, p.box, d_payload, payload_bytes, d_slice_len, d_status, s); },
+        [&](bool fused, const int16_t* v) -> int {
+            HIP_TRY(fused ? launch_model_rows_inv(sub, v, k->d_box, s) : launch_model_inv(sub, v, k->d_box, s));
+            HIP_TRY(launch_paste_rect(static_cast<const uint8_t*>(d_rect), k->d_box, sub.frames, sub.c, rw, rh, sub.w, sub.h, x - p.box.tx0 * g.tile_w,
+                                      y - p.box.ty0 * g.tile_h, s));
+            return LLCOMP_MI_OK;
+        });
+    if (rc) return rc;
     ++k->n_decode;
     *d_box_px = k->d_box;
     return LLCOMP_MI_OK;
@@ -1333,208 +1119,66 @@ extern "C" {
 
 uint32_t llcomp_mi_codec_regions_family(const llcomp_mi_codec* k, const uint32_t* xy, uint32_t rw, uint32_t rh, uint32_t* fam, uint32_t cap) {
     if (!k || (cap && !fam)) return 0;
-    std::vector<RegionsFrame> tab(k->g.frames);
-    RegionsClass classes[kRegionsClasses];
-    uint32_t n = 0;
-    if (regions_setup(k, xy, rw, rh, tab.data(), classes, n)) return 0;
-    for (uint32_t i = 0; i < n && i < cap; ++i) {
-        const Geometry& sub = classes[i].sub;
+    WindowsPlan p;
+    if (regions_plan(k, xy, rw, rh, p)) return 0;
+    for (uint32_t i = 0; i < p.n_classes && i < cap; ++i) {
+        const Geometry& sub = p.classes[i].sub;
         fam[i] = (sub.flags & 0xFFu) | (sub.lane_shift << 8) | (sub.lpw << 16);
     }
-    return n;
+    return p.n_classes;
 }
 
-// Regions decode (DESIGN.md "Region decode"): the region decode, class by class (geometry.hpp: regions_window), in order on the
-// caller's stream.  The full geometry's group offsets are found once; the per-frame table crosses to HBM in one copy from a slot of
-// the pinned ring, and every class reads its own entries of it.  Each class takes a state generation of its own.
+// The windowed decodes (DESIGN.md "Region decode"; "Crops of different sizes, resized to one shape"; "Several views of each frame"): each
+// checks its pointers, builds its plan (windows_plan.hpp) -- for host containers also the gather over the plan's windows (container.cpp),
+// whose every error comes before anything is queued -- and hands both to decode_windows.
+// Regions decode: the region decode, class by class (geometry.hpp: regions_window), in order on the caller's stream.
 int llcomp_mi_codec_decode_regions(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
                                    const uint32_t* xy, uint32_t rw, uint32_t rh, void* d_px, void* d_status, void* stream) {
     if (!k || !d_payload || !d_slice_len || !d_px || !d_status || !xy) return LLCOMP_MI_BAD_ARGS;
     if (misaligned(d_slice_len, 4) || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
-    const Geometry& g = k->g;
-    std::vector<RegionsFrame> tab(g.frames);
-    RegionsClass classes[kRegionsClasses];
-    uint32_t n_classes = 0;
-    if (int rc = regions_setup(k, xy, rw, rh, tab.data(), classes, n_classes)) return rc;
-    DeviceGuard guard(k->device);
-    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
-    if (int rc = ensure_region_arrays(k)) return rc;
-    if (int rc = ensure_regions_table(k)) return rc;
-    uint32_t slot = 0;
-    if (int rc = regions_slot_take(k, tab.size() * sizeof(RegionsFrame), 0, slot)) return rc;
-    std::memcpy(k->h_regions[slot], tab.data(), tab.size() * sizeof(RegionsFrame));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    DoneGuard done_guard{k, s};
-    HIP_TRY(hipMemsetAsync(d_status, 0, 4, s));
-    {
-        Timed t(k, s, 4);
-        HIP_TRY(hipMemcpyAsync(k->d_regions, k->h_regions[slot], tab.size() * sizeof(RegionsFrame), hipMemcpyHostToDevice, s));
-        if (int rc = regions_slot_queued(k, slot, s)) return rc;
-        HIP_TRY(launch_group_sums(g, static_cast<const uint32_t*>(d_slice_len), k->d_group_off, s));
-        HIP_TRY(launch_scan_groups(g, k->d_group_off, k->d_total_tmp, s));
-    }
-    const RegionsSource src{static_cast<const uint8_t*>(d_payload), payload_bytes, static_cast<const uint32_t*>(d_slice_len), nullptr, nullptr};
-    if (int rc = regions_classes(k, classes, n_classes, k->d_regions, src, rw, rh, static_cast<uint8_t*>(d_px), static_cast<uint32_t*>(d_status), s))
-        return rc;
-    ++k->n_decode;
-    return LLCOMP_MI_OK;
+    WindowsPlan p;
+    if (int rc = regions_plan(k, xy, rw, rh, p)) return rc;
+    return decode_windows(k, p, nullptr, 0, WindowsSource{d_payload, payload_bytes, d_slice_len, nullptr, nullptr}, d_px, d_status, stream);
 }
 
-// Regions decode of host containers: the gather (container.cpp) writes the table, the window slices' lengths and offsets and their
-// payload bytes into one slot of the pinned ring; ONE copy takes it to d_stage, and the classes run as above with their slices' lengths
-// and offsets read straight from it (no group sums: the offsets are the host's).  Every error of the gather comes before anything is
-// queued.
+// ... of host containers: only the window slices' bytes cross to the GPU.
 int llcomp_mi_codec_decode_regions_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens, const uint32_t* xy, uint32_t rw,
                                         uint32_t rh, void* d_px, void* d_status, void* stream) {
     if (!k || !data || !lens || !d_px || !d_status || !xy || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
-    const Geometry& g = k->g;
-    RegionsGather p;
-    if (int rc = regions_gather_plan(data, lens, g.frames, xy, rw, rh, p)) return rc;
-    // the containers have to be of the codec's shape, tiling, planar setting and model
-    const Geometry& cg = p.g;
-    if (cg.w != g.w || cg.h != g.h || cg.c != g.c || cg.tile_w != g.tile_w || cg.tile_h != g.tile_h || cg.planar != g.planar ||
-        (cg.flags & kGeoSmallModel) != (g.flags & kGeoSmallModel))
-        return LLCOMP_MI_BAD_ARGS;
-    std::vector<RegionsFrame> tab(g.frames);
-    RegionsClass classes[kRegionsClasses];
-    uint32_t n_classes = 0;
-    if (int rc = regions_setup(k, xy, rw, rh, tab.data(), classes, n_classes)) return rc;
-    uint64_t sub_slices = 0;  // (the gather's order is the table's: class by class, and a class's slices are its sub-geometry's)
-    for (uint32_t i = 0; i < n_classes; ++i) sub_slices += classes[i].sub.n_slices;
-    if (sub_slices != p.n_slices) return LLCOMP_MI_HIP_ERROR;
-    const StageLayout lay(g.frames, p.n_slices, p.payload_bytes);
-    DeviceGuard guard(k->device);
-    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
-    if (int rc = ensure_regions_table(k)) return rc;
-    if (int rc = ensure_stage(k, lay.bytes, stage_bound(g))) return rc;
-    uint32_t slot = 0;
-    if (int rc = regions_slot_take(k, lay.bytes, stage_bound(g), slot)) return rc;
-    uint8_t* h = k->h_regions[slot];
-    std::memcpy(h, tab.data(), tab.size() * sizeof(RegionsFrame));
-    regions_gather_copy(p, data, h + lay.pay_at, reinterpret_cast<uint32_t*>(h + lay.len_at), reinterpret_cast<uint64_t*>(h + lay.off_at));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    DoneGuard done_guard{k, s};
-    HIP_TRY(hipMemsetAsync(d_status, 0, 4, s));
-    {
-        Timed t(k, s, 4);
-        HIP_TRY(hipMemcpyAsync(k->d_stage, h, lay.bytes, hipMemcpyHostToDevice, s));
-        if (int rc = regions_slot_queued(k, slot, s)) return rc;
-    }
-    k->host_counters[LLCOMP_MI_CTR_HOST_STAGED_BYTES] += p.payload_bytes;
-    const RegionsSource src{k->d_stage + lay.pay_at, p.payload_bytes, nullptr, reinterpret_cast<const uint32_t*>(k->d_stage + lay.len_at),
-                            reinterpret_cast<const uint64_t*>(k->d_stage + lay.off_at)};
-    if (int rc = regions_classes(k, classes, n_classes, reinterpret_cast<const RegionsFrame*>(k->d_stage), src, rw, rh, static_cast<uint8_t*>(d_px),
-                                 static_cast<uint32_t*>(d_status), s))
-        return rc;
-    ++k->n_decode;
-    return LLCOMP_MI_OK;
+    RegionsGather gp;
+    if (int rc = regions_gather_plan(data, lens, k->g.frames, xy, rw, rh, gp)) return rc;
+    if (!same_shape(k->g, gp.g)) return LLCOMP_MI_BAD_ARGS;
+    WindowsPlan p;
+    if (int rc = regions_plan(k, xy, rw, rh, p)) return rc;
+    if (!gather_matches(p, gp)) return LLCOMP_MI_HIP_ERROR;
+    return decode_windows(k, p, nullptr, 0, WindowsSource{nullptr, 0, nullptr, data, &gp}, d_px, d_status, stream);
 }
 
-// Resized regions decode (DESIGN.md "Crops of different sizes, resized to one shape"): the regions decode's classes, unchanged, crop
-// every frame's box (the batch's largest rectangle size) into d_box; then the two resample passes read every frame's rectangle from its
-// box and write d_px.  The regions table, the resample table and the weights cross in ONE copy from a slot of the pinned ring to d_stage.
-// The output format's table rides behind the weights (ResizedPlan::table_at) and the vertical pass looks every value up in it.
+// Resized regions decode: the classes crop every frame's box (the batch's largest rectangle size) into d_box; then the two resample passes
+// read every frame's rectangle from its box and write d_px, the vertical pass through the output format's table where there is one.
 int llcomp_mi_codec_decode_resized_regions_ex(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
                                               const uint32_t* rects, const uint8_t* flags, uint32_t ow, uint32_t oh,
                                               const llcomp_mi_output_format* fmt, void* d_px, void* d_status, void* stream) {
     if (!k || !d_payload || !d_slice_len || !d_px || !d_status || !rects) return LLCOMP_MI_BAD_ARGS;
     if (misaligned(d_slice_len, 4) || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
-    const Geometry& g = k->g;
     ResizedPlan p;
-    if (int rc = resized_setup(k, rects, flags, ow, oh, fmt, d_px, p)) return rc;
-    const uint64_t rs_at = (uint64_t(g.frames) * sizeof(RegionsFrame) + 15) & ~15ull, bytes = rs_at + p.bytes();
-    DeviceGuard guard(k->device);
-    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
-    if (int rc = ensure_region_arrays(k)) return rc;
-    const uint64_t samples = uint64_t(g.frames) * g.w * g.h * g.c, bound = stage_bound(g) + resized_tables_bound(g);
-    if (int rc = ensure_regions_ring(k)) return rc;
-    if (int rc = ensure_stage(k, bytes, bound)) return rc;
-    if (int rc = ensure_grown(k, k->d_box, k->box_cap, p.box_bytes, samples)) return rc;
-    if (int rc = ensure_grown(k, k->d_mid, k->mid_cap, p.mid_bytes, samples)) return rc;
-    uint32_t slot = 0;
-    if (int rc = regions_slot_take(k, bytes, bound, slot)) return rc;
-    uint8_t* h = k->h_regions[slot];
-    std::memcpy(h, p.tab.data(), p.tab.size() * sizeof(RegionsFrame));
-    p.put(h + rs_at);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    DoneGuard done_guard{k, s};
-    HIP_TRY(hipMemsetAsync(d_status, 0, 4, s));
-    {
-        Timed t(k, s, 4);
-        HIP_TRY(hipMemcpyAsync(k->d_stage, h, bytes, hipMemcpyHostToDevice, s));
-        if (int rc = regions_slot_queued(k, slot, s)) return rc;
-        HIP_TRY(launch_group_sums(g, static_cast<const uint32_t*>(d_slice_len), k->d_group_off, s));
-        HIP_TRY(launch_scan_groups(g, k->d_group_off, k->d_total_tmp, s));
-    }
-    const RegionsSource src{static_cast<const uint8_t*>(d_payload), payload_bytes, static_cast<const uint32_t*>(d_slice_len), nullptr, nullptr};
-    if (int rc = regions_classes(k, p.classes, p.n_classes, reinterpret_cast<const RegionsFrame*>(k->d_stage), src, p.wmax, p.hmax, k->d_box,
-                                 static_cast<uint32_t*>(d_status), s))
-        return rc;
-    {
-        Timed t(k, s, 6);
-        HIP_TRY(launch_resize_out(k->d_box, k->d_mid, d_px, reinterpret_cast<const ResizeFrame*>(k->d_stage + rs_at),
-                                  reinterpret_cast<const int32_t*>(k->d_stage + rs_at + p.rs.size() * sizeof(ResizeFrame)),
-                                  k->d_stage + rs_at + p.table_at(), p.out, g.frames, g.c, p.wmax, p.hmax, p.hmax, ow, oh, s));
-    }
-    ++k->n_decode;
-    return LLCOMP_MI_OK;
+    if (int rc = resized_setup(k->g, k->tune, rects, flags, ow, oh, fmt, d_px, p)) return rc;
+    return decode_windows(k, p, &p.tail, resized_tables_bound(k->g), WindowsSource{d_payload, payload_bytes, d_slice_len, nullptr, nullptr}, nullptr,
+                          d_status, stream);
 }
 
-// ... of host containers: the gather of llcomp_mi_codec_decode_regions_host with every window sized for the largest rectangle; the
-// resample table and the weights ride behind the staged payload in the same copy.
+// ... of host containers: the gather with every window sized for the largest rectangle.
 int llcomp_mi_codec_decode_resized_regions_host_ex(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens, const uint32_t* rects,
                                                    const uint8_t* flags, uint32_t ow, uint32_t oh, const llcomp_mi_output_format* fmt,
                                                    void* d_px, void* d_status, void* stream) {
     if (!k || !data || !lens || !d_px || !d_status || !rects || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
-    const Geometry& g = k->g;
     ResizedPlan p;
-    if (int rc = resized_setup(k, rects, flags, ow, oh, fmt, d_px, p)) return rc;
+    if (int rc = resized_setup(k->g, k->tune, rects, flags, ow, oh, fmt, d_px, p)) return rc;
     RegionsGather gp;
-    if (int rc = regions_gather_plan_sized(data, lens, g.frames, rects, p.wmax, p.hmax, gp)) return rc;
-    const Geometry& cg = gp.g;
-    if (cg.w != g.w || cg.h != g.h || cg.c != g.c || cg.tile_w != g.tile_w || cg.tile_h != g.tile_h || cg.planar != g.planar ||
-        (cg.flags & kGeoSmallModel) != (g.flags & kGeoSmallModel))
-        return LLCOMP_MI_BAD_ARGS;
-    uint64_t sub_slices = 0;  // (the gather's order is the table's: class by class, and a class's slices are its sub-geometry's)
-    for (uint32_t i = 0; i < p.n_classes; ++i) sub_slices += p.classes[i].sub.n_slices;
-    if (sub_slices != gp.n_slices) return LLCOMP_MI_HIP_ERROR;
-    const StageLayout lay(g.frames, gp.n_slices, gp.payload_bytes);
-    const uint64_t rs_at = (lay.bytes + 15) & ~15ull, bytes = rs_at + p.bytes();
-    DeviceGuard guard(k->device);
-    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
-    const uint64_t samples = uint64_t(g.frames) * g.w * g.h * g.c, bound = stage_bound(g) + resized_tables_bound(g);
-    if (int rc = ensure_regions_ring(k)) return rc;
-    if (int rc = ensure_stage(k, bytes, bound)) return rc;
-    if (int rc = ensure_grown(k, k->d_box, k->box_cap, p.box_bytes, samples)) return rc;
-    if (int rc = ensure_grown(k, k->d_mid, k->mid_cap, p.mid_bytes, samples)) return rc;
-    uint32_t slot = 0;
-    if (int rc = regions_slot_take(k, bytes, bound, slot)) return rc;
-    uint8_t* h = k->h_regions[slot];
-    std::memcpy(h, p.tab.data(), p.tab.size() * sizeof(RegionsFrame));
-    regions_gather_copy(gp, data, h + lay.pay_at, reinterpret_cast<uint32_t*>(h + lay.len_at), reinterpret_cast<uint64_t*>(h + lay.off_at));
-    p.put(h + rs_at);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    DoneGuard done_guard{k, s};
-    HIP_TRY(hipMemsetAsync(d_status, 0, 4, s));
-    {
-        Timed t(k, s, 4);
-        HIP_TRY(hipMemcpyAsync(k->d_stage, h, bytes, hipMemcpyHostToDevice, s));
-        if (int rc = regions_slot_queued(k, slot, s)) return rc;
-    }
-    k->host_counters[LLCOMP_MI_CTR_HOST_STAGED_BYTES] += gp.payload_bytes;
-    const RegionsSource src{k->d_stage + lay.pay_at, gp.payload_bytes, nullptr, reinterpret_cast<const uint32_t*>(k->d_stage + lay.len_at),
-                            reinterpret_cast<const uint64_t*>(k->d_stage + lay.off_at)};
-    if (int rc = regions_classes(k, p.classes, p.n_classes, reinterpret_cast<const RegionsFrame*>(k->d_stage), src, p.wmax, p.hmax, k->d_box,
-                                 static_cast<uint32_t*>(d_status), s))
-        return rc;
-    {
-        Timed t(k, s, 6);
-        HIP_TRY(launch_resize_out(k->d_box, k->d_mid, d_px, reinterpret_cast<const ResizeFrame*>(k->d_stage + rs_at),
-                                  reinterpret_cast<const int32_t*>(k->d_stage + rs_at + p.rs.size() * sizeof(ResizeFrame)),
-                                  k->d_stage + rs_at + p.table_at(), p.out, g.frames, g.c, p.wmax, p.hmax, p.hmax, ow, oh, s));
-    }
-    ++k->n_decode;
-    return LLCOMP_MI_OK;
+    if (int rc = regions_gather_plan_sized(data, lens, k->g.frames, rects, p.wmax, p.hmax, gp)) return rc;
+    if (!same_shape(k->g, gp.g)) return LLCOMP_MI_BAD_ARGS;
+    if (!gather_matches(p, gp)) return LLCOMP_MI_HIP_ERROR;
+    return decode_windows(k, p, &p.tail, resized_tables_bound(k->g), WindowsSource{nullptr, 0, nullptr, data, &gp}, nullptr, d_status, stream);
 }
 
 int llcomp_mi_codec_decode_resized_regions(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
@@ -1548,98 +1192,32 @@ int llcomp_mi_codec_decode_resized_regions_host(llcomp_mi_codec* k, const uint8_
     return llcomp_mi_codec_decode_resized_regions_host_ex(k, data, lens, rects, flags, ow, oh, nullptr, d_px, d_status, stream);
 }
 
-// Views decode (DESIGN.md "Several views of each frame"): llcomp_mi_codec_decode_resized_regions_ex on the used frames' union rectangles
-// up to the boxes -- the classes unchanged, over the frame list -- then every group's views resampled from their frames' boxes.
+// Views decode: the resized regions decode on the used frames' union rectangles up to the boxes -- the classes unchanged, over the frame
+// list -- then every group's views resampled from their frames' boxes.
 int llcomp_mi_codec_decode_views(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
                                  const llcomp_mi_view_group* groups, uint32_t n_groups, void* d_status, void* stream) {
     if (!k || !d_payload || !d_slice_len || !d_status) return LLCOMP_MI_BAD_ARGS;
     if (misaligned(d_slice_len, 4) || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
-    const Geometry& g = k->g;
     ViewsPlan p;
-    if (int rc = views_setup(k, groups, n_groups, p)) return rc;
-    const uint64_t rs_at = (uint64_t(p.tab.size()) * sizeof(RegionsFrame) + 15) & ~15ull, bytes = rs_at + p.bytes();
-    DeviceGuard guard(k->device);
-    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
-    if (int rc = ensure_region_arrays(k)) return rc;
-    const uint64_t samples = uint64_t(g.frames) * g.w * g.h * g.c, bound = stage_bound(g) + views_tables_bound(g, p.u.total_views);
-    if (int rc = ensure_regions_ring(k)) return rc;
-    if (int rc = ensure_stage(k, bytes, bound)) return rc;
-    if (int rc = ensure_grown(k, k->d_box, k->box_cap, p.box_bytes, samples)) return rc;
-    if (int rc = ensure_grown(k, k->d_mid, k->mid_cap, p.mid_bytes, samples)) return rc;
-    uint32_t slot = 0;
-    if (int rc = regions_slot_take(k, bytes, bound, slot)) return rc;
-    uint8_t* h = k->h_regions[slot];
-    std::memcpy(h, p.tab.data(), p.tab.size() * sizeof(RegionsFrame));
-    p.put(h + rs_at);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    DoneGuard done_guard{k, s};
-    HIP_TRY(hipMemsetAsync(d_status, 0, 4, s));
-    {
-        Timed t(k, s, 4);
-        HIP_TRY(hipMemcpyAsync(k->d_stage, h, bytes, hipMemcpyHostToDevice, s));
-        if (int rc = regions_slot_queued(k, slot, s)) return rc;
-        HIP_TRY(launch_group_sums(g, static_cast<const uint32_t*>(d_slice_len), k->d_group_off, s));
-        HIP_TRY(launch_scan_groups(g, k->d_group_off, k->d_total_tmp, s));
-    }
-    const RegionsSource src{static_cast<const uint8_t*>(d_payload), payload_bytes, static_cast<const uint32_t*>(d_slice_len), nullptr, nullptr};
-    if (int rc = regions_classes(k, p.classes, p.n_classes, reinterpret_cast<const RegionsFrame*>(k->d_stage), src, p.u.wmax, p.u.hmax, k->d_box,
-                                 static_cast<uint32_t*>(d_status), s))
-        return rc;
-    if (int rc = views_resample(k, p, k->d_stage + rs_at, s)) return rc;
-    ++k->n_decode;
-    return LLCOMP_MI_OK;
+    if (int rc = views_setup(k->g, k->tune, groups, n_groups, p)) return rc;
+    return decode_windows(k, p, &p.tail, views_tables_bound(k->g, p.u.total_views), WindowsSource{d_payload, payload_bytes, d_slice_len, nullptr, nullptr},
+                          nullptr, d_status, stream);
 }
 
-// ... of host containers: the gather of llcomp_mi_codec_decode_resized_regions_host over the used frames' union rectangles (a frame
-// without a view is not looked at: its container may be NULL); the view tables ride behind the staged payload in the same copy.
+// ... of host containers: the gather over the used frames' union rectangles (a frame without a view is not looked at: its container may
+// be NULL).
 int llcomp_mi_codec_decode_views_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens, const llcomp_mi_view_group* groups,
                                       uint32_t n_groups, void* d_status, void* stream) {
     if (!k || !data || !lens || !d_status || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
-    const Geometry& g = k->g;
     ViewsPlan p;
-    if (int rc = views_setup(k, groups, n_groups, p)) return rc;
-    const uint32_t n_used = uint32_t(p.u.used.size());
+    if (int rc = views_setup(k->g, k->tune, groups, n_groups, p)) return rc;
     RegionsGather gp;
-    if (int rc = regions_gather_plan_sized(data, lens, g.frames, p.u.rects.data(), p.u.wmax, p.u.hmax, gp, p.u.used.data(), n_used)) return rc;
-    const Geometry& cg = gp.g;
-    if (cg.w != g.w || cg.h != g.h || cg.c != g.c || cg.tile_w != g.tile_w || cg.tile_h != g.tile_h || cg.planar != g.planar ||
-        (cg.flags & kGeoSmallModel) != (g.flags & kGeoSmallModel))
-        return LLCOMP_MI_BAD_ARGS;
-    uint64_t sub_slices = 0;  // (the gather's order is the table's: class by class, and a class's slices are its sub-geometry's)
-    for (uint32_t i = 0; i < p.n_classes; ++i) sub_slices += p.classes[i].sub.n_slices;
-    if (sub_slices != gp.n_slices) return LLCOMP_MI_HIP_ERROR;
-    const StageLayout lay(n_used, gp.n_slices, gp.payload_bytes);
-    const uint64_t rs_at = (lay.bytes + 15) & ~15ull, bytes = rs_at + p.bytes();
-    DeviceGuard guard(k->device);
-    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
-    const uint64_t samples = uint64_t(g.frames) * g.w * g.h * g.c, bound = stage_bound(g) + views_tables_bound(g, p.u.total_views);
-    if (int rc = ensure_regions_ring(k)) return rc;
-    if (int rc = ensure_stage(k, bytes, bound)) return rc;
-    if (int rc = ensure_grown(k, k->d_box, k->box_cap, p.box_bytes, samples)) return rc;
-    if (int rc = ensure_grown(k, k->d_mid, k->mid_cap, p.mid_bytes, samples)) return rc;
-    uint32_t slot = 0;
-    if (int rc = regions_slot_take(k, bytes, bound, slot)) return rc;
-    uint8_t* h = k->h_regions[slot];
-    std::memcpy(h, p.tab.data(), p.tab.size() * sizeof(RegionsFrame));
-    regions_gather_copy(gp, data, h + lay.pay_at, reinterpret_cast<uint32_t*>(h + lay.len_at), reinterpret_cast<uint64_t*>(h + lay.off_at));
-    p.put(h + rs_at);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    DoneGuard done_guard{k, s};
-    HIP_TRY(hipMemsetAsync(d_status, 0, 4, s));
-    {
-        Timed t(k, s, 4);
-        HIP_TRY(hipMemcpyAsync(k->d_stage, h, bytes, hipMemcpyHostToDevice, s));
-        if (int rc = regions_slot_queued(k, slot, s)) return rc;
-    }
-    k->host_counters[LLCOMP_MI_CTR_HOST_STAGED_BYTES] += gp.payload_bytes;
-    const RegionsSource src{k->d_stage + lay.pay_at, gp.payload_bytes, nullptr, reinterpret_cast<const uint32_t*>(k->d_stage + lay.len_at),
-                            reinterpret_cast<const uint64_t*>(k->d_stage + lay.off_at)};
-    if (int rc = regions_classes(k, p.classes, p.n_classes, reinterpret_cast<const RegionsFrame*>(k->d_stage), src, p.u.wmax, p.u.hmax, k->d_box,
-                                 static_cast<uint32_t*>(d_status), s))
+    if (int rc = regions_gather_plan_sized(data, lens, k->g.frames, p.u.rects.data(), p.wmax, p.hmax, gp, p.u.used.data(), uint32_t(p.u.used.size())))
         return rc;
-    if (int rc = views_resample(k, p, k->d_stage + rs_at, s)) return rc;
-    ++k->n_decode;
-    return LLCOMP_MI_OK;
+    if (!same_shape(k->g, gp.g)) return LLCOMP_MI_BAD_ARGS;
+    if (!gather_matches(p, gp)) return LLCOMP_MI_HIP_ERROR;
+    return decode_windows(k, p, &p.tail, views_tables_bound(k->g, p.u.total_views), WindowsSource{nullptr, 0, nullptr, data, &gp}, nullptr, d_status,
+                          stream);
 }
 
 uint64_t llcomp_mi_codec_views_workspace_bytes(const llcomp_mi_codec* k, uint64_t total_views) {

@@ -46,7 +46,8 @@ struct llcomp_mi_codec {
     bool regions_ev_live[kRegionsRing] = {};     // the slot's event has been recorded (a copy from it may be queued)
     uint32_t regions_slot = 0;                   // the slot the next call uses
     // host-staged regions decode: where a slot's one copy lands -- [RegionsFrame table][u32 window lengths][u64 offsets][payload]
-    // (codec.hip: StageLayout); grown geometrically up to stage_bound(g), allocated by the first such call
+    // (windows_plan.hpp: StageLayout), the resample block of a resized or views call behind it; grown geometrically up to stage_bound(g)
+    // plus the call's tables bound, allocated by the first such call
     uint8_t* d_stage = nullptr;
     uint64_t stage_cap = 0;
     // resized regions decode (llcomp_mi_codec_decode_resized_regions): every frame's box [frames][bh][bw][c] and the horizontal pass's

@@ -319,30 +319,44 @@ int llcomp_mi_region_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, u
     return LLCOMP_MI_OK;
 }
 
-int llcomp_mi_regions_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar, uint32_t rw, uint32_t rh,
-                           const uint32_t* xy, uint32_t n, uint32_t* windows, uint32_t* n_classes) {
-    (void)planar;
-    if (!xy || !n || !n_classes || c < 1 || c > kMaxChannels) return LLCOMP_MI_BAD_ARGS;
+// The window loop of the three plans below: the windows (sized for wmax x hmax) of the n rectangles rects[4 * f ..], f = used[i], or i
+// where there is no frame list.  Every rectangle is checked before anything is written; then frame f's window goes to windows[4 * f ..]
+// (`clear` frames of zeros first, for the frames a list does not name) and the number of classes met to *n_classes.
+static int plan_windows(uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h, const uint32_t* rects, const uint32_t* used, uint32_t n,
+                        uint32_t wmax, uint32_t hmax, uint32_t clear, uint32_t* windows, uint32_t* n_classes) {
     uint32_t seen = 0;
-    for (uint32_t f = 0; f < n; ++f) {  // (every rectangle is checked before anything is written)
-        RegionBox b;
-        uint32_t cls = 0;
-        if (!regions_window(w, h, tile_w, tile_h, xy[2 * f], xy[2 * f + 1], rw, rh, b, cls)) return LLCOMP_MI_BAD_ARGS;
-        seen |= 1u << cls;
-    }
-    for (uint32_t f = 0; f < n && windows; ++f) {
-        RegionBox b;
-        uint32_t cls = 0;
-        (void)regions_window(w, h, tile_w, tile_h, xy[2 * f], xy[2 * f + 1], rw, rh, b, cls);
-        {
-            windows[4 * f + 0] = b.tx0;
-            windows[4 * f + 1] = b.ty0;
-            windows[4 * f + 2] = b.tx1;
-            windows[4 * f + 3] = b.ty1;
+    for (int pass = 0; pass < (windows ? 2 : 1); ++pass) {
+        if (pass && clear) std::memset(windows, 0, 16 * size_t(clear));
+        for (uint32_t i = 0; i < n; ++i) {
+            const uint32_t f = used ? used[i] : i;
+            const uint32_t* r = rects + 4 * size_t(f);
+            RegionBox b;
+            uint32_t cls = 0;
+            if (!regions_window_sized(w, h, tile_w, tile_h, r[0], r[1], r[2], r[3], wmax, hmax, b, cls)) return LLCOMP_MI_BAD_ARGS;
+            seen |= 1u << cls;
+            if (!pass) continue;
+            windows[4 * size_t(f) + 0] = b.tx0;
+            windows[4 * size_t(f) + 1] = b.ty0;
+            windows[4 * size_t(f) + 2] = b.tx1;
+            windows[4 * size_t(f) + 3] = b.ty1;
         }
     }
     *n_classes = uint32_t(__builtin_popcount(seen));
     return LLCOMP_MI_OK;
+}
+
+int llcomp_mi_regions_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar, uint32_t rw, uint32_t rh,
+                           const uint32_t* xy, uint32_t n, uint32_t* windows, uint32_t* n_classes) {
+    (void)planar;
+    if (!xy || !n || !n_classes || c < 1 || c > kMaxChannels) return LLCOMP_MI_BAD_ARGS;
+    std::vector<uint32_t> rects(4 * size_t(n));
+    for (uint32_t f = 0; f < n; ++f) {
+        rects[4 * size_t(f) + 0] = xy[2 * size_t(f)];
+        rects[4 * size_t(f) + 1] = xy[2 * size_t(f) + 1];
+        rects[4 * size_t(f) + 2] = rw;
+        rects[4 * size_t(f) + 3] = rh;
+    }
+    return plan_windows(w, h, tile_w, tile_h, rects.data(), nullptr, n, rw, rh, 0, windows, n_classes);
 }
 
 int llcomp_mi_resized_regions_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar, const uint32_t* rects,
@@ -351,28 +365,10 @@ int llcomp_mi_resized_regions_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t 
     if (!rects || !n || !n_classes || c < 1 || c > kMaxChannels) return LLCOMP_MI_BAD_ARGS;
     uint32_t wmax = 0, hmax = 0;
     for (uint32_t f = 0; f < n; ++f) {
-        wmax = std::max(wmax, rects[4 * f + 2]);
-        hmax = std::max(hmax, rects[4 * f + 3]);
+        wmax = std::max(wmax, rects[4 * size_t(f) + 2]);
+        hmax = std::max(hmax, rects[4 * size_t(f) + 3]);
     }
-    uint32_t seen = 0;
-    for (uint32_t f = 0; f < n; ++f) {  // (every rectangle is checked before anything is written)
-        RegionBox b;
-        uint32_t cls = 0;
-        if (!regions_window_sized(w, h, tile_w, tile_h, rects[4 * f], rects[4 * f + 1], rects[4 * f + 2], rects[4 * f + 3], wmax, hmax, b, cls))
-            return LLCOMP_MI_BAD_ARGS;
-        seen |= 1u << cls;
-    }
-    for (uint32_t f = 0; f < n && windows; ++f) {
-        RegionBox b;
-        uint32_t cls = 0;
-        (void)regions_window_sized(w, h, tile_w, tile_h, rects[4 * f], rects[4 * f + 1], rects[4 * f + 2], rects[4 * f + 3], wmax, hmax, b, cls);
-        windows[4 * f + 0] = b.tx0;
-        windows[4 * f + 1] = b.ty0;
-        windows[4 * f + 2] = b.tx1;
-        windows[4 * f + 3] = b.ty1;
-    }
-    *n_classes = uint32_t(__builtin_popcount(seen));
-    return LLCOMP_MI_OK;
+    return plan_windows(w, h, tile_w, tile_h, rects, nullptr, n, wmax, hmax, 0, windows, n_classes);
 }
 
 int llcomp_mi_views_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar, uint32_t frames,
@@ -383,27 +379,10 @@ int llcomp_mi_views_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, ui
     ViewsUnion u;
     if (int rc = views_union(w, h, frames, groups, n_groups, u)) return rc;
     // (the union of rectangles inside the image is inside the image: regions_window_sized cannot refuse one)
-    std::vector<RegionBox> win(u.used.size());
-    uint32_t seen = 0;
-    for (size_t i = 0; i < u.used.size(); ++i) {
-        const uint32_t* r = u.rects.data() + 4 * size_t(u.used[i]);
-        uint32_t cls = 0;
-        if (!regions_window_sized(w, h, tile_w, tile_h, r[0], r[1], r[2], r[3], u.wmax, u.hmax, win[i], cls)) return LLCOMP_MI_BAD_ARGS;
-        seen |= 1u << cls;
-    }
+    if (int rc = plan_windows(w, h, tile_w, tile_h, u.rects.data(), u.used.data(), uint32_t(u.used.size()), u.wmax, u.hmax, frames, windows, n_classes))
+        return rc;
     if (unions) std::memcpy(unions, u.rects.data(), u.rects.size() * 4);
-    if (windows) {
-        std::memset(windows, 0, 16 * size_t(frames));
-        for (size_t i = 0; i < u.used.size(); ++i) {
-            uint32_t* o = windows + 4 * size_t(u.used[i]);
-            o[0] = win[i].tx0;
-            o[1] = win[i].ty0;
-            o[2] = win[i].tx1;
-            o[3] = win[i].ty1;
-        }
-    }
     *n_used = uint32_t(u.used.size());
-    *n_classes = uint32_t(__builtin_popcount(seen));
     return LLCOMP_MI_OK;
 }
 

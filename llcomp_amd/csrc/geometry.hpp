@@ -376,7 +376,7 @@ LLMI_HD inline uint32_t regions_full_id(const Geometry& full, const Geometry& su
 // region_fits for a class: its frames are some of the batch's
 inline bool regions_fits(const Geometry& full, const Geometry& sub) { return sub.frames <= full.frames && sub_arrays_fit(full, sub); }
 
-// ---- resampling limits of the resized calls and the views plan (resize.hpp; container.cpp: views_union) -------------------------------
+// ---- resampling limits of the resized calls and the views plan (resize_plan.hpp; container.cpp: views_union) --------------------------
 // An axis in_len -> out_len under filter code `filter` (LLCOMP_MI_FILTER_*) is refused for in_len or out_len 0, an unknown filter, or a
 // downscale above the filter's limit: R * in_len > kResizeMaxDown * out_len with R = 1, but 2 for bicubic and 3 for Lanczos, so that the
 // filter's support never passes kResizeMaxDown input samples and K <= 129.

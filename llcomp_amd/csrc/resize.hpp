@@ -1,61 +1,19 @@
-// resize.hpp -- the resampling of a resized regions decode (resize_kernels.hip; codec.hip: llcomp_mi_codec_decode_resized_regions;
-// DESIGN.md "Crops of different sizes, resized to one shape").
+// resize.hpp -- the launchers of the resampling of a resized regions decode (resize_kernels.hip; codec.hip: windows_resample;
+// DESIGN.md "Crops of different sizes, resized to one shape").  What the host decides -- weights, entries, output format: resize_plan.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <vector>
 
-#include "../../include/llcomp_mi.h"
-#include "geometry.hpp"
+#include "resize_plan.hpp"
 
 namespace llcomp_mi {
-
-// One axis, in_len -> out_len, under filter LLCOMP_MI_FILTER_* (include/llcomp_mi.h: llcomp_mi_resize_filter_weights): the taps per
-// output K (trailing taps that are zero for every output are left out), lo[out_len] and q[out_len][K] in Q22, zero-padded.  0 for
-// in_len or out_len 0, an unknown filter, or a downscale above the filter's limit (geometry.hpp: resize_axis_ok).
-uint32_t resize_weights(uint32_t filter, uint32_t in_len, uint32_t out_len, uint32_t* lo, int32_t* q);
-
-// One entry of a resample launch, as the kernels see it: a frame of a resized regions decode, or a view of a views decode.  Its
-// rectangle starts at (ox, oy) inside box `box` of d_box (every box bw x bh: the call's largest rectangle, or largest union of a frame's
-// views) -- the frame's own box for a resized regions decode, the box of the view's frame for a views decode, where the views of one
-// frame share a box.  The weights live in one int32 array: the horizontal pass's at hx -- lo[ow], then q tap-major [kx][ow] -- and the
-// vertical pass's at vy -- lo[oh], then q [ky][oh].  Every lo is placed so that lo + k <= the rectangle's side (resize_weights' lo
-// moved left over leading zero weights where needed): no tap reads outside the rectangle, so an entry's output does not depend on what
-// else its box holds.
-struct ResizeFrame {
-    uint32_t ox, oy;  // the rectangle's origin inside the box
-    uint32_t rw, rh;  // the rectangle
-    uint32_t kx, ky;  // taps per output, horizontal / vertical
-    uint32_t hx, vy;  // offsets of the weights, in int32 units
-    uint32_t flags;   // bit 0: mirror the output horizontally; bits 4-6: the entry's filter (the kernels read bit 0 only)
-    uint32_t box;     // which box of d_box holds the rectangle
-    uint32_t pad[2];
-};
-static_assert(sizeof(ResizeFrame) == 48, "the kernels and the staging layout count on 48 bytes");
-// Appends the weights of a rw x rh rectangle for ow x oh under `filter` to `w` and fills `e` (ox / oy / flags / box are the caller's).  An axis
-// (filter, side -> output side) that an earlier frame of the call already put in `w` is shared: `seen` (empty at the start of a call)
-// records them.  false for an unknown filter or a downscale above its limit.
-bool resize_frame_weights(uint32_t filter, uint32_t rw, uint32_t rh, uint32_t ow, uint32_t oh, ResizeFrame& e, std::vector<int32_t>& w,
-                          std::vector<uint32_t>& seen);
 
 // d_box [boxes][bh][bw][c] -> d_mid [entries][mh][ow][c] (rows [0, rh) of every entry: the horizontal pass, rounded to u8) -> d_px
 // [entries][oh][ow][c] (the vertical pass, then the mirror).  The caller guarantees ox + rw <= bw, oy + rh <= bh, rh <= mh and a box
 // inside d_box for every entry.
 hipError_t launch_resize(const uint8_t* d_box, uint8_t* d_mid, uint8_t* d_px, const ResizeFrame* d_tab, const int32_t* d_w, uint32_t entries,
                          uint32_t c, uint32_t bw, uint32_t bh, uint32_t mh, uint32_t ow, uint32_t oh, hipStream_t stream);
-
-// The output format of an _ex call (include/llcomp_mi.h: llcomp_mi_output_format), checked: dtype, layout, element size, and whether the
-// output is anything but today's u8 HWC (`plain`: no table, the two kernels above).  BAD_ARGS for every case the header lists but the
-// output pointer's alignment, which the caller checks against esize.  A NULL fmt is U8 HWC.
-struct OutFormat {
-    uint32_t dtype = 0, layout = 0, esize = 1;
-    bool plain = true;
-    uint64_t table_bytes(uint32_t c) const { return plain ? 0 : uint64_t(c) * 256 * esize; }
-};
-int check_output_format(const llcomp_mi_output_format* fmt, uint32_t c, OutFormat& o);
-// The table of a checked format: table[ch * 256 + v], esize bytes each (include/llcomp_mi.h: the output rule).
-void output_table(const llcomp_mi_output_format* fmt, uint32_t c, const OutFormat& o, uint8_t* table);
 
 // launch_resize with the vertical pass writing fmt's table entries in its layout (o.plain is launch_resize itself): d_table is the
 // table of output_table in device memory, 4-byte aligned; d_out is aligned to o.esize.
