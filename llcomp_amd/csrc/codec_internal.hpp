@@ -165,6 +165,11 @@ void lane_destroy(HostLane* l);
 int lane_enqueue_encode(HostLane* l);
 // container in d_container (header + tables + `payload_bytes` of payload) -> frame(s) in d_px, status -> h_meta
 int lane_enqueue_decode(HostLane* l, uint64_t payload_bytes);
+// drains the lane's stream and returns the status the last enqueued call left in the mailbox
+int lane_wait_status(HostLane* l);
+// lane_enqueue_encode + lane_wait_status; a payload that overflows the lane's capacity is coded once more with room for the codec's
+// proven bound (lane_grow; the frame is still in d_px).  The one OUTPUT_OVERFLOW retry of the encoders.
+int lane_encode_sync(HostLane* l);
 
 // hostapi.hip: a lane for this shape on `device` (-1 = current) from the cache of idle lanes, or a new one; lane_release parks it again
 int lane_acquire(HostLane** out, int32_t device, uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar,

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/llcomp_mi.h"
+#include "host_result.hpp"
 
 namespace llcomp_mi {
 
@@ -24,6 +25,20 @@ void write_sliced_header(uint8_t* o, const Geometry& g) {
     put_u32le(o + 4, g.w); put_u32le(o + 8, g.h);
     put_u32le(o + 12, g.tile_w); put_u32le(o + 16, g.tile_h);
     put_u32le(o + 20, g.slices_per_frame);
+}
+
+PayloadSpan covered_span(const llcomp_mi_info& info, const uint8_t* data, size_t len, const uint32_t box[4]) {
+    const uint64_t payload = len - info.payload_offset;
+    if (info.format == LLCOMP_MI_FORMAT_LEGACY) return {0, payload};
+    const uint32_t planes = info.planar ? info.channels : 1u, ntx = (info.width + info.tile_w - 1) / info.tile_w;
+    const uint64_t first = (uint64_t(box[1]) * ntx + box[0]) * planes, last = ((uint64_t(box[3]) - 1) * ntx + box[2] - 1) * planes + planes - 1;
+    const uint8_t* tab = data + info.table_offset;  // (probe has made sure the table is all there)
+    uint64_t begin = 0, pos = 0;
+    for (uint64_t i = 0; i <= last; ++i) {
+        if (i == first) begin = pos;
+        pos += get_u32le(tab + 4 * i);
+    }
+    return {std::min(begin, payload), std::min(pos, payload)};
 }
 
 int regions_gather_plan(const uint8_t* const* data, const size_t* lens, uint32_t n, const uint32_t* xy, uint32_t rw, uint32_t rh,
@@ -199,15 +214,9 @@ static int replace_slices_common(const uint8_t* data, size_t len, const uint32_t
         }
         old_off += l;  // (a covered slice's old bytes are skipped, never read)
     }
-    const size_t n = size_t(a.payload_offset + total);
-    *out_len = n;
-    uint8_t* o = out;
-    if (!o) {
-        o = static_cast<uint8_t*>(std::malloc(n + 1));
-        if (!o) return LLCOMP_MI_NOMEM;
-    } else if (n > out_cap) {
-        return LLCOMP_MI_OUTPUT_OVERFLOW;  // *out_len tells the caller what it takes
-    }
+    HostOut res(out, out_cap, out_alloc, out_len);
+    uint8_t* o = nullptr;
+    if (int rc = res.take(size_t(a.payload_offset + total), o)) return rc;
     std::memcpy(o, data, LLCOMP_MI_SLICED_HEADER_BYTES);
     uint8_t* otab = o + LLCOMP_MI_SLICED_HEADER_BYTES;
     uint8_t* pay = o + a.payload_offset;
@@ -233,7 +242,7 @@ static int replace_slices_common(const uint8_t* data, size_t len, const uint32_t
         old_off += l;
     }
     if (run) std::memcpy(pay, src + run_at, run);
-    if (out_alloc) *out_alloc = o;
+    res.commit();
     return LLCOMP_MI_OK;
 }
 

@@ -8,6 +8,7 @@
 #include "geometry.hpp"
 
 struct llcomp_mi_view_group;  // include/llcomp_mi.h
+struct llcomp_mi_info;
 
 namespace llcomp_mi {
 
@@ -20,6 +21,14 @@ inline uint32_t get_u32le(const uint8_t* p) {
 
 void write_legacy_header(uint8_t* out6, uint32_t w, uint32_t h, uint32_t c);
 void write_sliced_header(uint8_t* out24, const Geometry& g);  // g.frames must be 1
+
+// The payload bytes [begin, end) that hold the slices of tile box {tx0, ty0, tx1, ty1} of a probed container of `len` bytes: from the
+// first covered slice's first byte to the last one's end (slices run tile row, tile column, plane, so the span also holds what lies
+// between them), both ends clamped to the payload that is there.  A LEGACY stream is one slice: [0, payload).
+struct PayloadSpan {
+    uint64_t begin, end;
+};
+PayloadSpan covered_span(const llcomp_mi_info& info, const uint8_t* data, size_t len, const uint32_t box[4]);
 
 // Regions gather (llcomp_mi_regions_gather, and the host path of llcomp_mi_codec_decode_regions_host): which bytes of which container a
 // regions decode needs.  A run is one window tile row of one frame: `count` consecutive table entries from entry `first` of container

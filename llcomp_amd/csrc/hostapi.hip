@@ -14,11 +14,13 @@
 #include <cstring>
 #include <mutex>
 #include <new>
+#include <optional>
 #include <vector>
 
 #include "../../include/llcomp_mi.h"
 #include "codec_internal.hpp"
 #include "container.hpp"
+#include "host_result.hpp"
 
 using namespace llcomp_mi;
 
@@ -108,14 +110,32 @@ int lane_enqueue_encode(HostLane* l) {
     return LLCOMP_MI_OK;
 }
 
+// a LEGACY stream has no table on the wire: its one length is what follows the header
+static int lane_set_legacy_len(HostLane* l, uint64_t payload_bytes) {
+    if (!l->legacy) return LLCOMP_MI_OK;
+    const uint32_t one = uint32_t(std::min<uint64_t>(payload_bytes, 0xFFFFFFFFull));
+    LLMI_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(l->d_len_legacy), int(one), 1, l->stream));
+    return LLCOMP_MI_OK;
+}
+
 int lane_enqueue_decode(HostLane* l, uint64_t payload_bytes) {
-    if (l->legacy) {
-        const uint32_t one = uint32_t(std::min<uint64_t>(payload_bytes, 0xFFFFFFFFull));
-        LLMI_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(l->d_len_legacy), int(one), 1, l->stream));
-    }
+    if (int rc = lane_set_legacy_len(l, payload_bytes)) return rc;
     if (int rc = llcomp_mi_codec_decode(l->k, l->d_payload(), payload_bytes, l->d_len(), l->d_px, l->d_meta + 1, l->stream)) return rc;
     LLMI_HIP_TRY(hipMemcpyAsync(l->h_meta, l->d_meta, 16, hipMemcpyDeviceToHost, l->stream));
     return LLCOMP_MI_OK;
+}
+
+int lane_wait_status(HostLane* l) {
+    LLMI_HIP_TRY(hipStreamSynchronize(l->stream));
+    return status_from_bits(uint32_t(l->h_meta[1]));
+}
+
+int lane_encode_sync(HostLane* l) {
+    return with_overflow_retry(l->payload_cap, llcomp_mi_codec_max_payload_bytes(l->k), [&](uint64_t cap) {
+        if (int rc = lane_grow(l, cap)) return rc;  // (the container buffer's contents are lost, the frame is still in d_px)
+        if (int rc = lane_enqueue_encode(l)) return rc;
+        return lane_wait_status(l);
+    });
 }
 
 }  // namespace llcomp_mi
@@ -211,7 +231,7 @@ namespace {
 // Copies between a CALLER's buffer and HBM, stream-ordered on the lane's private stream and complete on return (staged by
 // the runtime for pageable memory, plain DMA for pinned memory).  Measured on a 4K noise frame, buffers reused across
 // calls: 2.1 ms encode + 2.1 ms decode with pageable and with pinned buffers alike; what makes the allocating calls
-// slower is the first touch of a fresh 30 MB malloc per call, not the copy.
+// slower is the first touch of a fresh 30 MB allocation per call, not the copy.
 inline hipError_t copy_user(void* dst, const void* src, size_t n, hipMemcpyKind kind, hipStream_t s) {
     return n ? hipMemcpyWithStream(dst, src, n, kind, s) : hipSuccess;
 }
@@ -221,7 +241,51 @@ struct LaneLease {  // returns the lane to the cache on every exit path
     ~LaneLease() { lane_release(l); }
 };
 
-// encode into `out` (capacity out_cap) when out != nullptr, else into a malloc'ed buffer returned through *out_alloc
+// lane_wait_status behind a codec call that was made on the lane's buffers directly: the 16-byte mailbox copy first
+int lane_read_status(HostLane* l) {
+    LLMI_HIP_TRY(hipMemcpyAsync(l->h_meta, l->d_meta, 16, hipMemcpyDeviceToHost, l->stream));
+    return lane_wait_status(l);
+}
+
+// A container on its way into a decode, a region decode or a region update: probed, its shape checked, a LEGACY stream's length clamped
+// to what a decoder can read, a lane of its full shape leased and that lane's device current until the call returns.
+struct Opened {
+    llcomp_mi_info info{};
+    size_t len = 0;  // (clamped)
+    bool legacy = false;
+    LaneLease lease;
+    std::optional<DeviceGuard> guard;  // (after the lease: the device is restored before the lane goes back)
+    uint64_t payload() const { return len - info.payload_offset; }
+};
+// header_check(info) runs on the probed header before a lane is taken: what a call refuses or reports from the header alone
+template <typename Check>
+int open_container(const uint8_t* data, size_t len, int32_t device, uint32_t flags, Opened& o, Check header_check) {
+    if (flags & ~LLCOMP_MI_FLAG_SMALL_MODEL) return LLCOMP_MI_BAD_ARGS;
+    llcomp_mi_info& info = o.info;
+    if (int rc = llcomp_mi_probe(data, len, &info)) return rc;
+    o.legacy = info.format == LLCOMP_MI_FORMAT_LEGACY;
+    if (int rc = check_shape(info.width, info.height, info.channels, o.legacy)) return rc;
+    if (int rc = header_check(info)) return rc;
+    const uint64_t raw = uint64_t(info.width) * info.height * info.channels;
+    o.len = o.legacy ? size_t(std::min<uint64_t>(len, info.payload_offset + legacy_read_bound(raw))) : len;  // the rest is never read
+    if (int rc = lane_acquire(&o.lease.l, device, info.width, info.height, info.channels, info.tile_w, info.tile_h, info.planar, o.legacy,
+                              o.payload() + 16, o.legacy ? (flags & LLCOMP_MI_FLAG_SMALL_MODEL) != 0 : info.small_model != 0,
+                              o.legacy ? o.payload() : 0))
+        return rc;
+    o.guard.emplace(o.lease.l->k->device);
+    return o.guard->ok ? LLCOMP_MI_OK : LLCOMP_MI_HIP_ERROR;
+}
+
+// Up goes what a decode of tile box `box` reads and no more: the header + slice table, and the payload span of the covered slices at its
+// own offset in the lane's container buffer (the bytes around it are never read)
+int stage_covered(HostLane* l, const uint8_t* data, const Opened& o, const uint32_t box[4]) {
+    const PayloadSpan s = covered_span(o.info, data, o.len, box);
+    LLMI_HIP_TRY(copy_user(l->d_container, data, l->head_bytes, hipMemcpyHostToDevice, l->stream));
+    LLMI_HIP_TRY(copy_user(l->d_payload() + s.begin, data + l->head_bytes + s.begin, s.end - s.begin, hipMemcpyHostToDevice, l->stream));
+    return lane_set_legacy_len(l, o.payload());
+}
+
+// encode into `out` (capacity out_cap) when out != nullptr, else into an allocated buffer returned through *out_alloc (HostOut)
 int encode_common(const uint8_t* px, uint32_t w, uint32_t h, uint32_t c, const llcomp_mi_opts* opts, uint8_t* out, size_t out_cap,
                   uint8_t** out_alloc, size_t* out_len) {
     *out_len = 0;
@@ -254,256 +318,133 @@ int encode_common(const uint8_t* px, uint32_t w, uint32_t h, uint32_t c, const l
     }
 
     LaneLease lease;
-    // first try with room for 2x raw (incompressible noise needs ~1.25x), then the proven worst case
-    const uint64_t first_cap = 2 * raw + 64ull * llcomp_mi_slice_count(w, h, c, tile_w, tile_h, planar) + 4096;
     if (int rc = lane_acquire(&lease.l, o.device, w, h, c, tile_w, tile_h, planar, legacy, 0, o.small_model != 0)) return rc;
     HostLane* l = lease.l;
-    const uint64_t max_payload = llcomp_mi_codec_max_payload_bytes(l->k);
-    if (int rc = lane_grow(l, std::min(first_cap, max_payload))) return rc;
+    // room for 2x raw first (incompressible noise needs ~1.25x); lane_encode_sync grows to the proven worst case if it has to
+    const uint64_t first_cap = 2 * raw + 64ull * llcomp_mi_slice_count(w, h, c, tile_w, tile_h, planar) + 4096;
+    if (int rc = lane_grow(l, std::min(first_cap, llcomp_mi_codec_max_payload_bytes(l->k)))) return rc;
     DeviceGuard guard(l->k->device);
     if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
     LLMI_HIP_TRY(copy_user(l->d_px, px, raw, hipMemcpyHostToDevice, l->stream));
-    int rc = LLCOMP_MI_OK;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        if ((rc = lane_enqueue_encode(l))) return rc;
-        LLMI_HIP_TRY(hipStreamSynchronize(l->stream));
-        rc = status_from_bits(uint32_t(l->h_meta[1]));
-        if (rc == LLCOMP_MI_OUTPUT_OVERFLOW && l->payload_cap < max_payload) {
-            if (int rc2 = lane_grow(l, max_payload)) return rc2;
-            continue;
-        }
-        break;
-    }
-    if (rc) return rc;
+    if (int rc = lane_encode_sync(l)) return rc;
     const size_t n = size_t(l->head_bytes) + size_t(l->h_meta[0]);
-    *out_len = n;
-    uint8_t* dst = out;
-    if (!dst) {
-        dst = static_cast<uint8_t*>(std::malloc(n + 1));
-        if (!dst) return LLCOMP_MI_NOMEM;
-    } else if (n > out_cap) {
-        return LLCOMP_MI_OUTPUT_OVERFLOW;  // *out_len tells the caller what it takes
-    }
+    HostOut res(out, out_cap, out_alloc, out_len);
+    uint8_t* dst = nullptr;
+    if (int rc = res.take(n, dst)) return rc;
     // header, slice table and payload sit in HBM exactly as on the wire (little-endian u32 on both sides): one copy
-    if (copy_user(dst, l->d_container, n, hipMemcpyDeviceToHost, l->stream) != hipSuccess) {
-        if (!out) std::free(dst);
-        return LLCOMP_MI_HIP_ERROR;
-    }
-    if (out_alloc) *out_alloc = dst;
+    LLMI_HIP_TRY(copy_user(dst, l->d_container, n, hipMemcpyDeviceToHost, l->stream));
+    res.commit();
     return LLCOMP_MI_OK;
 }
 
 int decode_common(const uint8_t* data, size_t len, int32_t device, uint32_t flags, uint8_t* px, size_t px_cap, uint8_t** px_alloc,
                   uint32_t* w, uint32_t* h, uint32_t* c) {
-    if (flags & ~LLCOMP_MI_FLAG_SMALL_MODEL) return LLCOMP_MI_BAD_ARGS;
-    llcomp_mi_info info;
-    if (int rc = llcomp_mi_probe(data, len, &info)) return rc;
-    const bool legacy = info.format == LLCOMP_MI_FORMAT_LEGACY;
-    if (int rc = check_shape(info.width, info.height, info.channels, legacy)) return rc;
-    const uint64_t raw = uint64_t(info.width) * info.height * info.channels;
-    *w = info.width;
-    *h = info.height;
-    *c = info.channels;
-    if (px && raw > px_cap) return LLCOMP_MI_OUTPUT_OVERFLOW;  // dimensions are reported: the caller can size its buffer
-    if (legacy) len = size_t(std::min<uint64_t>(len, info.payload_offset + legacy_read_bound(raw)));  // the rest is never read
-    LaneLease lease;
-    if (int rc = lane_acquire(&lease.l, device, info.width, info.height, info.channels, info.tile_w, info.tile_h, info.planar, legacy,
-                              len - info.payload_offset + 16, legacy ? (flags & LLCOMP_MI_FLAG_SMALL_MODEL) != 0 : info.small_model != 0,
-                              legacy ? len - info.payload_offset : 0))
+    HostOut res(px, px_cap, px_alloc, nullptr);
+    uint8_t* dst = nullptr;
+    uint64_t raw = 0;
+    Opened o;
+    if (int rc = open_container(data, len, device, flags, o, [&](const llcomp_mi_info& info) {
+            *w = info.width;
+            *h = info.height;
+            *c = info.channels;
+            raw = uint64_t(info.width) * info.height * info.channels;
+            return res.take(raw, dst);  // (the dimensions are reported: the caller of an OUTPUT_OVERFLOW can size its buffer)
+        }))
         return rc;
-    HostLane* l = lease.l;
-    DeviceGuard guard(l->k->device);
-    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
+    HostLane* l = o.lease.l;
     // the container goes to HBM as it is: the slice table is read where it lies (offset 24, dword aligned)
-    LLMI_HIP_TRY(copy_user(l->d_container, data, len, hipMemcpyHostToDevice, l->stream));
-    if (int rc = lane_enqueue_decode(l, len - l->head_bytes)) return rc;
-    LLMI_HIP_TRY(hipStreamSynchronize(l->stream));
-    if (int rc = status_from_bits(uint32_t(l->h_meta[1]))) return rc;
-    uint8_t* dst = px;
-    if (!dst) {
-        dst = static_cast<uint8_t*>(std::malloc(raw ? raw : 1));
-        if (!dst) return LLCOMP_MI_NOMEM;
-    }
-    if (copy_user(dst, l->d_px, raw, hipMemcpyDeviceToHost, l->stream) != hipSuccess) {
-        if (!px) std::free(dst);
-        return LLCOMP_MI_HIP_ERROR;
-    }
-    if (px_alloc) *px_alloc = dst;
+    LLMI_HIP_TRY(copy_user(l->d_container, data, o.len, hipMemcpyHostToDevice, l->stream));
+    if (int rc = lane_enqueue_decode(l, o.payload())) return rc;
+    if (int rc = lane_wait_status(l)) return rc;
+    LLMI_HIP_TRY(copy_user(dst, l->d_px, raw, hipMemcpyDeviceToHost, l->stream));
+    res.commit();
     return LLCOMP_MI_OK;
 }
 
-// Region decode (llcomp_mi_decode_region): the lane of the container's full shape, but only the header + slice table and the payload
-// span of the covered slices cross PCIe (the span lies at its own offset in the lane's container buffer; the bytes around it are never
-// read), and only the rectangle comes back
+// Region decode (llcomp_mi_decode_region): the lane of the container's full shape, but only what stage_covered sends crosses PCIe, and
+// only the rectangle comes back
 int decode_region_common(const uint8_t* data, size_t len, int32_t device, uint32_t flags, uint32_t x, uint32_t y, uint32_t rw, uint32_t rh,
                          uint8_t* px, size_t px_cap, uint8_t** px_alloc, uint32_t* c) {
-    if (flags & ~LLCOMP_MI_FLAG_SMALL_MODEL) return LLCOMP_MI_BAD_ARGS;
-    llcomp_mi_info info;
-    if (int rc = llcomp_mi_probe(data, len, &info)) return rc;
-    const bool legacy = info.format == LLCOMP_MI_FORMAT_LEGACY;
-    if (int rc = check_shape(info.width, info.height, info.channels, legacy)) return rc;
+    HostOut res(px, px_cap, px_alloc, nullptr);
+    uint8_t* dst = nullptr;
     uint32_t box[4], covered = 0;
-    if (int rc = llcomp_mi_region_plan(info.width, info.height, info.channels, info.tile_w, info.tile_h, info.planar, x, y, rw, rh, box, &covered))
+    uint64_t out = 0;
+    Opened o;
+    if (int rc = open_container(data, len, device, flags, o, [&](const llcomp_mi_info& info) {
+            if (int rc = llcomp_mi_region_plan(info.width, info.height, info.channels, info.tile_w, info.tile_h, info.planar, x, y, rw, rh, box, &covered))
+                return rc;
+            *c = info.channels;
+            out = uint64_t(rw) * rh * info.channels;
+            return res.take(out, dst);  // (the channel count is reported: the caller of an OUTPUT_OVERFLOW can size its buffer)
+        }))
         return rc;
-    *c = info.channels;
-    const uint64_t out = uint64_t(rw) * rh * info.channels;
-    if (px && out > px_cap) return LLCOMP_MI_OUTPUT_OVERFLOW;  // the channel count is reported: the caller can size its buffer
-    if (legacy) len = size_t(std::min<uint64_t>(len, info.payload_offset + legacy_read_bound(uint64_t(info.width) * info.height * info.channels)));
-    LaneLease lease;
-    if (int rc = lane_acquire(&lease.l, device, info.width, info.height, info.channels, info.tile_w, info.tile_h, info.planar, legacy,
-                              len - info.payload_offset + 16, legacy ? (flags & LLCOMP_MI_FLAG_SMALL_MODEL) != 0 : info.small_model != 0,
-                              legacy ? len - info.payload_offset : 0))
+    HostLane* l = o.lease.l;
+    if (int rc = stage_covered(l, data, o, box)) return rc;
+    if (int rc = llcomp_mi_codec_decode_region(l->k, l->d_payload(), o.payload(), l->d_len(), x, y, rw, rh, l->d_px, l->d_meta + 1, l->stream))
         return rc;
-    HostLane* l = lease.l;
-    DeviceGuard guard(l->k->device);
-    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
-    const uint64_t payload = len - l->head_bytes;
-    // the covered slices' bytes: from the first covered slice's first byte to the last one's end (slices run tile row, tile column,
-    // plane; the table lies in host memory, probe has made sure it is all there)
-    uint64_t begin = 0, end = payload;
-    if (!legacy) {
-        const uint32_t planes = info.planar ? info.channels : 1u, ntx = (info.width + info.tile_w - 1) / info.tile_w;
-        const uint64_t first = (uint64_t(box[1]) * ntx + box[0]) * planes, last = ((uint64_t(box[3]) - 1) * ntx + box[2] - 1) * planes + planes - 1;
-        const uint8_t* table = data + info.table_offset;
-        auto len_at = [&](uint64_t i) { uint32_t v; std::memcpy(&v, table + 4 * i, 4); return uint64_t(v); };  // (little-endian hosts)
-        uint64_t pos = 0;
-        for (uint64_t i = 0; i <= last; ++i) {
-            if (i == first) begin = pos;
-            pos += len_at(i);
-        }
-        begin = std::min(begin, payload);
-        end = std::min(pos, payload);
-    }
-    LLMI_HIP_TRY(copy_user(l->d_container, data, l->head_bytes, hipMemcpyHostToDevice, l->stream));
-    LLMI_HIP_TRY(copy_user(l->d_payload() + begin, data + l->head_bytes + begin, end - begin, hipMemcpyHostToDevice, l->stream));
-    if (legacy) {
-        const uint32_t one = uint32_t(std::min<uint64_t>(payload, 0xFFFFFFFFull));
-        LLMI_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(l->d_len_legacy), int(one), 1, l->stream));
-    }
-    if (int rc = llcomp_mi_codec_decode_region(l->k, l->d_payload(), payload, l->d_len(), x, y, rw, rh, l->d_px, l->d_meta + 1, l->stream))
-        return rc;
-    LLMI_HIP_TRY(hipMemcpyAsync(l->h_meta, l->d_meta, 16, hipMemcpyDeviceToHost, l->stream));
-    LLMI_HIP_TRY(hipStreamSynchronize(l->stream));
-    if (int rc = status_from_bits(uint32_t(l->h_meta[1]))) return rc;
-    uint8_t* dst = px;
-    if (!dst) {
-        dst = static_cast<uint8_t*>(std::malloc(out));
-        if (!dst) return LLCOMP_MI_NOMEM;
-    }
-    if (copy_user(dst, l->d_px, out, hipMemcpyDeviceToHost, l->stream) != hipSuccess) {
-        if (!px) std::free(dst);
-        return LLCOMP_MI_HIP_ERROR;
-    }
-    if (px_alloc) *px_alloc = dst;
+    if (int rc = lane_read_status(l)) return rc;
+    LLMI_HIP_TRY(copy_user(dst, l->d_px, out, hipMemcpyDeviceToHost, l->stream));
+    res.commit();
     return LLCOMP_MI_OK;
 }
 
-// Region update (llcomp_mi_update_region): the lane of the container's full shape.  Up: header + slice table, the rectangle's pixels
-// and -- only when the rectangle is not exactly its box's pixels, so that the box has to be decoded -- the payload span of the covered
-// slices, at its own offset in the lane's container buffer as for a region decode.  llcomp_mi_codec_encode_region codes the box; down come
-// {bytes, status}, then the covered slices' new lengths and streams in one copy; llcomp_mi_replace_slices assembles the container here.
-// Nothing else of the container crosses PCIe in either direction.
+// Region update (llcomp_mi_update_region): the lane of the container's full shape.  Up: the rectangle's pixels and -- only when the
+// rectangle is not exactly its box's pixels, so that the box has to be decoded -- what stage_covered sends, as for a region decode.
+// llcomp_mi_codec_encode_region codes the box; down come {bytes, status}, then the covered slices' new lengths and streams in one copy;
+// llcomp_mi_replace_slices assembles the container here.  Nothing else of the container crosses PCIe in either direction.
 int update_region_common(const uint8_t* data, size_t len, int32_t device, uint32_t flags, uint32_t x, uint32_t y, uint32_t rw, uint32_t rh,
                          const uint8_t* px, uint8_t* out, size_t out_cap, uint8_t** out_alloc, size_t* out_len) {
-    if (flags & ~LLCOMP_MI_FLAG_SMALL_MODEL) return LLCOMP_MI_BAD_ARGS;
-    llcomp_mi_info info;
-    if (int rc = llcomp_mi_probe(data, len, &info)) return rc;
-    const bool legacy = info.format == LLCOMP_MI_FORMAT_LEGACY;
-    if (int rc = check_shape(info.width, info.height, info.channels, legacy)) return rc;
     uint32_t box[4], covered = 0;
-    if (int rc = llcomp_mi_region_plan(info.width, info.height, info.channels, info.tile_w, info.tile_h, info.planar, x, y, rw, rh, box, &covered))
+    Opened o;
+    if (int rc = open_container(data, len, device, flags, o, [&](const llcomp_mi_info& info) {
+            return llcomp_mi_region_plan(info.width, info.height, info.channels, info.tile_w, info.tile_h, info.planar, x, y, rw, rh, box, &covered);
+        }))
         return rc;
-    if (legacy) len = size_t(std::min<uint64_t>(len, info.payload_offset + legacy_read_bound(uint64_t(info.width) * info.height * info.channels)));
-    LaneLease lease;
-    if (int rc = lane_acquire(&lease.l, device, info.width, info.height, info.channels, info.tile_w, info.tile_h, info.planar, legacy,
-                              len - info.payload_offset + 16, legacy ? (flags & LLCOMP_MI_FLAG_SMALL_MODEL) != 0 : info.small_model != 0,
-                              legacy ? len - info.payload_offset : 0))
-        return rc;
-    HostLane* l = lease.l;
-    DeviceGuard guard(l->k->device);
-    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
+    HostLane* l = o.lease.l;
     const Geometry& g = l->k->g;
     RegionBox b{box[0], box[1], box[2], box[3]};
     Geometry sub;
     if (!region_geometry(g, b, l->k->tune, sub)) return LLCOMP_MI_HIP_ERROR;
     const bool whole = region_is_whole_box(g, sub, b, x, y, rw, rh);
-    const uint64_t payload = len - l->head_bytes, rect_bytes = uint64_t(rw) * rh * info.channels;
-    if (!whole) {
-        // the covered slices' bytes: from the first covered slice's first byte to the last one's end (decode_region_common)
-        uint64_t begin = 0, end = payload;
-        if (!legacy) {
-            const uint32_t planes = info.planar ? info.channels : 1u;
-            const uint64_t first = (uint64_t(box[1]) * g.ntx + box[0]) * planes, last = ((uint64_t(box[3]) - 1) * g.ntx + box[2] - 1) * planes + planes - 1;
-            const uint8_t* table = data + info.table_offset;
-            uint64_t pos = 0;
-            for (uint64_t i = 0; i <= last; ++i) {
-                if (i == first) begin = pos;
-                pos += get_u32le(table + 4 * i);
-            }
-            begin = std::min(begin, payload);
-            end = std::min(pos, payload);
-        }
-        LLMI_HIP_TRY(copy_user(l->d_container, data, l->head_bytes, hipMemcpyHostToDevice, l->stream));
-        LLMI_HIP_TRY(copy_user(l->d_payload() + begin, data + l->head_bytes + begin, end - begin, hipMemcpyHostToDevice, l->stream));
-        if (legacy) {
-            const uint32_t one = uint32_t(std::min<uint64_t>(payload, 0xFFFFFFFFull));
-            LLMI_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(l->d_len_legacy), int(one), 1, l->stream));
-        }
-    }
+    if (!whole)
+        if (int rc = stage_covered(l, data, o, box)) return rc;
     // the rectangle rides in the lane's frame buffer (rw * rh <= w * h); the new slices come back through a block of their own:
     // [u32 lengths][streams], first with room for twice the box's raw bytes, then for the proven worst case
-    LLMI_HIP_TRY(copy_user(l->d_px, px, rect_bytes, hipMemcpyHostToDevice, l->stream));
+    LLMI_HIP_TRY(copy_user(l->d_px, px, uint64_t(rw) * rh * o.info.channels, hipMemcpyHostToDevice, l->stream));
     const uint64_t table_bytes = (4ull * covered + 15) & ~15ull, max_sub = uint64_t(covered) * g.slice_cap;
-    uint64_t cap = std::min<uint64_t>(2 * uint64_t(sub.w) * sub.h * sub.c + 64ull * covered + 4096, max_sub);
     struct Block {
         uint8_t* p = nullptr;
         ~Block() { dev_free(p); }  // (the lane's stream has been drained on every path that gets here with p set)
     } blk;
-    std::vector<uint8_t> host;
-    int rc = LLCOMP_MI_OK;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        if (dev_alloc(reinterpret_cast<void**>(&blk.p), table_bytes + cap + 16) != hipSuccess) { blk.p = nullptr; return LLCOMP_MI_NOMEM; }
-        rc = llcomp_mi_codec_encode_region(l->k, whole ? nullptr : l->d_payload(), payload, whole ? nullptr : l->d_len(), x, y, rw, rh, l->d_px,
-                                           blk.p + table_bytes, cap, blk.p, l->d_meta, l->d_meta + 1, l->stream);
-        if (rc) {
-            (void)hipStreamSynchronize(l->stream);
-            return rc;
-        }
-        if (hipMemcpyAsync(l->h_meta, l->d_meta, 16, hipMemcpyDeviceToHost, l->stream) != hipSuccess || hipStreamSynchronize(l->stream) != hipSuccess) {
-            (void)hipStreamSynchronize(l->stream);
-            return LLCOMP_MI_HIP_ERROR;
-        }
-        rc = status_from_bits(uint32_t(l->h_meta[1]));
-        if (rc == LLCOMP_MI_OUTPUT_OVERFLOW && cap < max_sub) {
+    if (int rc = with_overflow_retry(std::min<uint64_t>(2 * uint64_t(sub.w) * sub.h * sub.c + 64ull * covered + 4096, max_sub), max_sub, [&](uint64_t cap) {
             dev_free(blk.p);
             blk.p = nullptr;
-            cap = max_sub;
-            continue;
-        }
-        break;
-    }
-    if (rc) return rc;
+            if (dev_alloc(reinterpret_cast<void**>(&blk.p), table_bytes + cap + 16) != hipSuccess) {
+                blk.p = nullptr;
+                return int(LLCOMP_MI_NOMEM);
+            }
+            int rc = llcomp_mi_codec_encode_region(l->k, whole ? nullptr : l->d_payload(), o.payload(), whole ? nullptr : l->d_len(), x, y, rw, rh,
+                                                   l->d_px, blk.p + table_bytes, cap, blk.p, l->d_meta, l->d_meta + 1, l->stream);
+            if (!rc) rc = lane_read_status(l);
+            if (rc) (void)hipStreamSynchronize(l->stream);  // whatever was queued may still write the block that is about to be freed
+            return rc;
+        }))
+        return rc;
     const uint64_t sub_bytes = l->h_meta[0];
-    host.resize(size_t(table_bytes + sub_bytes));
+    std::vector<uint8_t> host(size_t(table_bytes + sub_bytes));
     LLMI_HIP_TRY(copy_user(host.data(), blk.p, host.size(), hipMemcpyDeviceToHost, l->stream));
     const uint32_t* new_len = reinterpret_cast<const uint32_t*>(host.data());  // (little-endian hosts, as the table on the wire)
-    if (!legacy) {
-        if (out) return llcomp_mi_replace_slices_into(data, len, box, new_len, host.data() + table_bytes, out, out_cap, out_len);
-        return llcomp_mi_replace_slices(data, len, box, new_len, host.data() + table_bytes, out_alloc, out_len);
+    if (!o.legacy) {
+        if (out) return llcomp_mi_replace_slices_into(data, o.len, box, new_len, host.data() + table_bytes, out, out_cap, out_len);
+        return llcomp_mi_replace_slices(data, o.len, box, new_len, host.data() + table_bytes, out_alloc, out_len);
     }
     // a LEGACY stream: the 6-byte header and the one new stream
-    const size_t n = 6 + size_t(sub_bytes);
-    *out_len = n;
-    uint8_t* dst = out;
-    if (!dst) {
-        dst = static_cast<uint8_t*>(std::malloc(n + 1));
-        if (!dst) return LLCOMP_MI_NOMEM;
-    } else if (n > out_cap) {
-        return LLCOMP_MI_OUTPUT_OVERFLOW;
-    }
+    HostOut res(out, out_cap, out_alloc, out_len);
+    uint8_t* dst = nullptr;
+    if (int rc = res.take(6 + size_t(sub_bytes), dst)) return rc;
     std::memcpy(dst, data, 6);
     std::memcpy(dst + 6, host.data() + table_bytes, size_t(sub_bytes));
-    if (out_alloc) *out_alloc = dst;
+    res.commit();
     return LLCOMP_MI_OK;
 }
 

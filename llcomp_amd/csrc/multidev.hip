@@ -25,7 +25,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <thread>
@@ -34,6 +33,7 @@
 #include "../../include/llcomp_mi.h"
 #include "codec_internal.hpp"
 #include "container.hpp"
+#include "host_result.hpp"
 
 using namespace llcomp_mi;
 
@@ -184,8 +184,7 @@ int encode_multi(const uint8_t* px, uint32_t w, uint32_t h, uint32_t c, uint32_t
         HostLane* l = p.lane;
         if (l->k->g.n_slices != p.local_slices) return LLCOMP_MI_HIP_ERROR;  // (the band's tiling is not the image's: cannot happen)
         const uint64_t raw = uint64_t(p.local_h) * pl.row_bytes;
-        const uint64_t max_payload = llcomp_mi_codec_max_payload_bytes(l->k);
-        if (int rc = lane_grow(l, std::min<uint64_t>(2 * raw + 64ull * p.local_slices + 4096, max_payload))) return rc;
+        if (int rc = lane_grow(l, std::min<uint64_t>(2 * raw + 64ull * p.local_slices + 4096, llcomp_mi_codec_max_payload_bytes(l->k)))) return rc;
         DeviceGuard guard(l->k->device);
         if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
         for (uint32_t ci : p.chunks) {
@@ -193,18 +192,7 @@ int encode_multi(const uint8_t* px, uint32_t w, uint32_t h, uint32_t c, uint32_t
             LLMI_HIP_TRY(hipMemcpyAsync(l->d_px + size_t(ch.local_y0) * pl.row_bytes, px + size_t(ch.y0) * pl.row_bytes,
                                         size_t(ch.y1 - ch.y0) * pl.row_bytes, hipMemcpyHostToDevice, l->stream));
         }
-        int rc = LLCOMP_MI_OK;
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            if ((rc = lane_enqueue_encode(l))) return rc;
-            LLMI_HIP_TRY(hipStreamSynchronize(l->stream));
-            rc = status_from_bits(uint32_t(l->h_meta[1]));
-            if (rc == LLCOMP_MI_OUTPUT_OVERFLOW && l->payload_cap < max_payload) {  // (the frame is still in d_px)
-                if (int rc2 = lane_grow(l, max_payload)) return rc2;
-                continue;
-            }
-            break;
-        }
-        if (rc) return rc;
+        if (int rc = lane_encode_sync(l)) return rc;
         p.payload_bytes = l->h_meta[0];
         for (uint32_t ci : p.chunks) {
             const Chunk& ch = pl.chunks[ci];
@@ -232,15 +220,9 @@ int encode_multi(const uint8_t* px, uint32_t w, uint32_t h, uint32_t c, uint32_t
     for (size_t i = 0; i < pl.parts.size(); ++i)
         if (part_at[i] != pl.parts[i].payload_bytes)  // table and payload of a part disagree: never publish that
             return device_failed(pl.parts[i].device, pl.parts[i].index, LLCOMP_MI_HIP_ERROR);
-    const size_t n = head_bytes + size_t(total);
-    *out_len = n;
-    uint8_t* dst = out;
-    if (!dst) {
-        dst = static_cast<uint8_t*>(std::malloc(n + 1));
-        if (!dst) return LLCOMP_MI_NOMEM;
-    } else if (n > out_cap) {
-        return LLCOMP_MI_OUTPUT_OVERFLOW;  // *out_len tells the caller what it takes; nothing was written
-    }
+    HostOut res(out, out_cap, out_alloc, out_len);
+    uint8_t* dst = nullptr;
+    if (int rc = res.take(head_bytes + size_t(total), dst)) return rc;  // (an OUTPUT_OVERFLOW: *out_len tells what it takes, nothing was written)
 
     // phase 2: every part's payload straight to its place behind the table (N links, no gather)
     for_each_part(pl.parts, [&](Part& p) -> int {
@@ -256,12 +238,11 @@ int encode_multi(const uint8_t* px, uint32_t w, uint32_t h, uint32_t c, uint32_t
         return LLCOMP_MI_OK;
     });
     if (int rc = verdict(pl.parts)) {
-        if (!out) std::free(dst);
         *out_len = 0;
         return rc;
     }
     std::memcpy(dst, head.data(), head_bytes);  // the header last: a buffer without it is not a container
-    if (out_alloc) *out_alloc = dst;
+    res.commit();
     return LLCOMP_MI_OK;
 }
 
@@ -300,7 +281,9 @@ int decode_multi(const uint8_t* data, size_t len, const llcomp_mi_info& info, co
     *w = pl.w;
     *h = pl.h;
     *c = pl.c;
-    if (px && raw > px_cap) return LLCOMP_MI_OUTPUT_OVERFLOW;  // dimensions are reported: the caller can size its buffer
+    HostOut res(px, px_cap, px_alloc, nullptr);
+    uint8_t* dst = nullptr;
+    if (int rc = res.take(raw, dst)) return rc;  // (an OUTPUT_OVERFLOW: dimensions are reported, the caller can size its buffer)
     LaneReturn lanes{pl.parts};
     const uint8_t* payload = data + info.payload_offset;
 
@@ -321,16 +304,10 @@ int decode_multi(const uint8_t* data, size_t len, const llcomp_mi_info& info, co
                 LLMI_HIP_TRY(hipMemcpyAsync(l->d_payload() + ch.local_off, payload + ch.final_off, ch.bytes, hipMemcpyHostToDevice, l->stream));
         }
         if (int rc = lane_enqueue_decode(l, bytes)) return rc;
-        LLMI_HIP_TRY(hipStreamSynchronize(l->stream));
-        return status_from_bits(uint32_t(l->h_meta[1]));
+        return lane_wait_status(l);
     });
     if (int rc = verdict(pl.parts)) return rc;
 
-    uint8_t* dst = px;
-    if (!dst) {
-        dst = static_cast<uint8_t*>(std::malloc(raw ? raw : 1));
-        if (!dst) return LLCOMP_MI_NOMEM;
-    }
     // phase 2: every chunk's rows straight to their place in the picture
     for_each_part(pl.parts, [&](Part& p) -> int {
         HostLane* l = p.lane;
@@ -344,11 +321,8 @@ int decode_multi(const uint8_t* data, size_t len, const llcomp_mi_info& info, co
         LLMI_HIP_TRY(hipStreamSynchronize(l->stream));
         return LLCOMP_MI_OK;
     });
-    if (int rc = verdict(pl.parts)) {
-        if (!px) std::free(dst);
-        return rc;
-    }
-    if (px_alloc) *px_alloc = dst;
+    if (int rc = verdict(pl.parts)) return rc;
+    res.commit();
     return LLCOMP_MI_OK;
 }
 

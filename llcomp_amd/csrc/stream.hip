@@ -165,6 +165,40 @@ int free_slot(llcomp_mi_stream* s) {
     return -1;
 }
 
+// One job into a free slot (BUSY when there is none).  body(slot, lane, out_len) queues the job's copies and its codec call on the lane's
+// stream and sets the bytes of its result; the job's closing event goes behind them -- e1, the size mailbox, for an encode (pump queues
+// the container copies once it has arrived), e2 for the others, whose result is complete with it.  Whatever fails once the slot is
+// chosen drains the lane (drained) and leaves the slot free.
+template <typename Body>
+int submit_job(llcomp_mi_stream* s, uint32_t kind, uint64_t tag, Body body) {
+    std::lock_guard<std::mutex> lock(s->mu);
+    DeviceGuard guard(s->device);
+    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
+    pump(s);
+    const int i = free_slot(s);
+    if (i < 0) return LLCOMP_MI_BUSY;
+    Slot& sl = s->slots[size_t(i)];
+    HostLane* l = sl.lane;
+    const bool encode = kind == LLCOMP_MI_JOB_ENCODE;
+    uint64_t out_len = 0;
+    if (int rc = body(sl, l, out_len)) return drained(l, rc);
+    if (hipEventRecord(encode ? sl.e1 : sl.e2, l->stream) != hipSuccess) return drained(l, LLCOMP_MI_HIP_ERROR);
+    sl.state = encode ? kEncSizing : kCopying;
+    sl.kind = kind;
+    sl.tag = tag;
+    sl.status = LLCOMP_MI_OK;
+    sl.out_len = out_len;
+    s->fifo.push_back(uint32_t(i));
+    return LLCOMP_MI_OK;
+}
+
+// the tail of the two crop jobs: the status mailbox and the job's `bytes` of output into the slot's pinned buffer
+int queue_crops_out(Slot& sl, HostLane* l, uint64_t bytes) {
+    LLMI_HIP_TRY(hipMemcpyAsync(l->h_meta, l->d_meta, 16, hipMemcpyDeviceToHost, l->stream));
+    LLMI_HIP_TRY(hipMemcpyAsync(sl.h_out, l->d_px, bytes, hipMemcpyDeviceToHost, l->stream));
+    return LLCOMP_MI_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -272,24 +306,10 @@ uint64_t llcomp_mi_stream_container_capacity(const llcomp_mi_stream* s) {
 int llcomp_mi_stream_submit_encode(llcomp_mi_stream* s, const uint8_t* px, uint64_t tag) {
     if (!s || !px) return LLCOMP_MI_BAD_ARGS;
     if (!s->subs.empty()) return deal(s, [&](llcomp_mi_stream* sub) { return llcomp_mi_stream_submit_encode(sub, px, tag); });
-    std::lock_guard<std::mutex> lock(s->mu);
-    DeviceGuard guard(s->device);
-    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
-    pump(s);
-    const int i = free_slot(s);
-    if (i < 0) return LLCOMP_MI_BUSY;
-    Slot& sl = s->slots[size_t(i)];
-    HostLane* l = sl.lane;
-    LLMI_HIP_TRY(hipMemcpyAsync(l->d_px, px, s->raw * s->fpj, hipMemcpyHostToDevice, l->stream));  // the job's frames, back to back
-    if (int rc = lane_enqueue_encode(l)) return drained(l, rc);
-    if (hipEventRecord(sl.e1, l->stream) != hipSuccess) return drained(l, LLCOMP_MI_HIP_ERROR);
-    sl.state = kEncSizing;
-    sl.kind = LLCOMP_MI_JOB_ENCODE;
-    sl.tag = tag;
-    sl.status = LLCOMP_MI_OK;
-    sl.out_len = 0;
-    s->fifo.push_back(uint32_t(i));
-    return LLCOMP_MI_OK;
+    return submit_job(s, LLCOMP_MI_JOB_ENCODE, tag, [&](Slot&, HostLane* l, uint64_t&) -> int {
+        LLMI_HIP_TRY(hipMemcpyAsync(l->d_px, px, s->raw * s->fpj, hipMemcpyHostToDevice, l->stream));  // the job's frames, back to back
+        return lane_enqueue_encode(l);
+    });
 }
 
 int llcomp_mi_stream_submit_decode(llcomp_mi_stream* s, const uint8_t* data, size_t len, uint64_t tag) {
@@ -316,46 +336,29 @@ int llcomp_mi_stream_submit_decode_batch(llcomp_mi_stream* s, const uint8_t* con
             pay[f] = sum;
         }
     }
-    std::lock_guard<std::mutex> lock(s->mu);
-    DeviceGuard guard(s->device);
-    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
-    pump(s);
-    const int i = free_slot(s);
-    if (i < 0) return LLCOMP_MI_BUSY;
-    Slot& sl = s->slots[size_t(i)];
-    HostLane* l = sl.lane;
-    uint64_t payload_bytes = 0;
-    if (s->fpj > 1) {  // (checked before anything is queued)
-        uint64_t all = 0;
-        for (uint32_t f = 0; f < s->fpj; ++f) all += pay[f];
-        if (all > l->payload_cap) return LLCOMP_MI_OUTPUT_OVERFLOW;
-    }
-    if (s->fpj == 1) {
-        // a container longer than the slot's buffer carries bytes no slice can use (the table is bounds-checked on the GPU)
-        const uint64_t n = std::min<uint64_t>(lens[0], uint64_t(l->head_bytes) + l->payload_cap);
-        LLMI_HIP_TRY(hipMemcpyAsync(l->d_container, data[0], n, hipMemcpyHostToDevice, l->stream));
-        payload_bytes = n - l->head_bytes;
-    } else {
-        for (uint32_t f = 0; f < s->fpj; ++f) {
-            if (hipMemcpyAsync(l->d_len() + size_t(f) * s->spf, data[f] + LLCOMP_MI_SLICED_HEADER_BYTES, 4ull * s->spf,
-                               hipMemcpyHostToDevice, l->stream) != hipSuccess)
-                return drained(l, LLCOMP_MI_HIP_ERROR);
-            if (pay[f] && hipMemcpyAsync(l->d_payload() + payload_bytes, data[f] + head1, pay[f], hipMemcpyHostToDevice, l->stream) != hipSuccess)
-                return drained(l, LLCOMP_MI_HIP_ERROR);
-            payload_bytes += pay[f];
+    return submit_job(s, LLCOMP_MI_JOB_DECODE, tag, [&](Slot& sl, HostLane* l, uint64_t& out_len) -> int {
+        uint64_t payload_bytes = 0;
+        if (s->fpj == 1) {
+            // a container longer than the slot's buffer carries bytes no slice can use (the table is bounds-checked on the GPU)
+            const uint64_t n = std::min<uint64_t>(lens[0], uint64_t(l->head_bytes) + l->payload_cap);
+            LLMI_HIP_TRY(hipMemcpyAsync(l->d_container, data[0], n, hipMemcpyHostToDevice, l->stream));
+            payload_bytes = n - l->head_bytes;
+        } else {
+            for (uint32_t f = 0; f < s->fpj; ++f) payload_bytes += pay[f];
+            if (payload_bytes > l->payload_cap) return LLCOMP_MI_OUTPUT_OVERFLOW;  // (checked before anything is queued)
+            uint64_t at = 0;
+            for (uint32_t f = 0; f < s->fpj; ++f) {
+                LLMI_HIP_TRY(hipMemcpyAsync(l->d_len() + size_t(f) * s->spf, data[f] + LLCOMP_MI_SLICED_HEADER_BYTES, 4ull * s->spf,
+                                            hipMemcpyHostToDevice, l->stream));
+                if (pay[f]) LLMI_HIP_TRY(hipMemcpyAsync(l->d_payload() + at, data[f] + head1, pay[f], hipMemcpyHostToDevice, l->stream));
+                at += pay[f];
+            }
         }
-    }
-    if (int rc = lane_enqueue_decode(l, payload_bytes)) return drained(l, rc);
-    if (hipMemcpyAsync(sl.h_out, l->d_px, s->raw * s->fpj, hipMemcpyDeviceToHost, l->stream) != hipSuccess ||
-        hipEventRecord(sl.e2, l->stream) != hipSuccess)
-        return drained(l, LLCOMP_MI_HIP_ERROR);
-    sl.state = kCopying;
-    sl.kind = LLCOMP_MI_JOB_DECODE;
-    sl.tag = tag;
-    sl.status = LLCOMP_MI_OK;
-    sl.out_len = s->raw * s->fpj;
-    s->fifo.push_back(uint32_t(i));
-    return LLCOMP_MI_OK;
+        if (int rc = lane_enqueue_decode(l, payload_bytes)) return rc;
+        out_len = s->raw * s->fpj;
+        LLMI_HIP_TRY(hipMemcpyAsync(sl.h_out, l->d_px, out_len, hipMemcpyDeviceToHost, l->stream));
+        return LLCOMP_MI_OK;
+    });
 }
 
 // A job of crops: the lane's codec stages the windows of the job's containers from the host (read during this call only) and decodes
@@ -365,27 +368,12 @@ int llcomp_mi_stream_submit_decode_regions(llcomp_mi_stream* s, const uint8_t* c
     if (!s || !data || !lens || !xy) return LLCOMP_MI_BAD_ARGS;
     if (!s->subs.empty())
         return deal(s, [&](llcomp_mi_stream* sub) { return llcomp_mi_stream_submit_decode_regions(sub, data, lens, xy, rw, rh, tag); });
-    std::lock_guard<std::mutex> lock(s->mu);
-    DeviceGuard guard(s->device);
-    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
-    pump(s);
-    const int i = free_slot(s);
-    if (i < 0) return LLCOMP_MI_BUSY;
-    Slot& sl = s->slots[size_t(i)];
-    HostLane* l = sl.lane;
-    // (a gather error, a rectangle outside the image among them, returns before anything is queued: the slot stays free)
-    if (int rc = llcomp_mi_codec_decode_regions_host(l->k, data, lens, xy, rw, rh, l->d_px, l->d_meta + 1, l->stream)) return drained(l, rc);
-    const uint64_t bytes = uint64_t(rw) * rh * s->c * s->fpj;
-    if (hipMemcpyAsync(l->h_meta, l->d_meta, 16, hipMemcpyDeviceToHost, l->stream) != hipSuccess ||
-        hipMemcpyAsync(sl.h_out, l->d_px, bytes, hipMemcpyDeviceToHost, l->stream) != hipSuccess || hipEventRecord(sl.e2, l->stream) != hipSuccess)
-        return drained(l, LLCOMP_MI_HIP_ERROR);
-    sl.state = kCopying;
-    sl.kind = LLCOMP_MI_JOB_DECODE_REGIONS;
-    sl.tag = tag;
-    sl.status = LLCOMP_MI_OK;
-    sl.out_len = bytes;
-    s->fifo.push_back(uint32_t(i));
-    return LLCOMP_MI_OK;
+    return submit_job(s, LLCOMP_MI_JOB_DECODE_REGIONS, tag, [&](Slot& sl, HostLane* l, uint64_t& out_len) -> int {
+        // (a gather error, a rectangle outside the image among them, returns before anything is queued: the slot stays free)
+        if (int rc = llcomp_mi_codec_decode_regions_host(l->k, data, lens, xy, rw, rh, l->d_px, l->d_meta + 1, l->stream)) return rc;
+        out_len = uint64_t(rw) * rh * s->c * s->fpj;
+        return queue_crops_out(sl, l, out_len);
+    });
 }
 
 // A job of resized crops: as a job of crops, with the output resampled to ow x oh on the lane's codec, in fmt's dtype and layout (NULL:
@@ -399,30 +387,16 @@ int llcomp_mi_stream_submit_decode_resized_regions_ex(llcomp_mi_stream* s, const
         return deal(s, [&](llcomp_mi_stream* sub) {
             return llcomp_mi_stream_submit_decode_resized_regions_ex(sub, data, lens, rects, flags, ow, oh, fmt, tag);
         });
-    std::lock_guard<std::mutex> lock(s->mu);
     OutFormat out;
     if (int rc = check_output_format(fmt, s->c, out)) return rc;
     const uint64_t bytes = uint64_t(ow) * oh * s->c * s->fpj * out.esize;
     if (bytes > s->raw * s->fpj || bytes > s->out_cap) return LLCOMP_MI_BAD_ARGS;
-    DeviceGuard guard(s->device);
-    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
-    pump(s);
-    const int i = free_slot(s);
-    if (i < 0) return LLCOMP_MI_BUSY;
-    Slot& sl = s->slots[size_t(i)];
-    HostLane* l = sl.lane;
-    if (int rc = llcomp_mi_codec_decode_resized_regions_host_ex(l->k, data, lens, rects, flags, ow, oh, fmt, l->d_px, l->d_meta + 1, l->stream))
-        return drained(l, rc);
-    if (hipMemcpyAsync(l->h_meta, l->d_meta, 16, hipMemcpyDeviceToHost, l->stream) != hipSuccess ||
-        hipMemcpyAsync(sl.h_out, l->d_px, bytes, hipMemcpyDeviceToHost, l->stream) != hipSuccess || hipEventRecord(sl.e2, l->stream) != hipSuccess)
-        return drained(l, LLCOMP_MI_HIP_ERROR);
-    sl.state = kCopying;
-    sl.kind = LLCOMP_MI_JOB_DECODE_RESIZED_REGIONS;
-    sl.tag = tag;
-    sl.status = LLCOMP_MI_OK;
-    sl.out_len = bytes;
-    s->fifo.push_back(uint32_t(i));
-    return LLCOMP_MI_OK;
+    return submit_job(s, LLCOMP_MI_JOB_DECODE_RESIZED_REGIONS, tag, [&](Slot& sl, HostLane* l, uint64_t& out_len) -> int {
+        if (int rc = llcomp_mi_codec_decode_resized_regions_host_ex(l->k, data, lens, rects, flags, ow, oh, fmt, l->d_px, l->d_meta + 1, l->stream))
+            return rc;
+        out_len = bytes;
+        return queue_crops_out(sl, l, out_len);
+    });
 }
 
 int llcomp_mi_stream_submit_decode_resized_regions(llcomp_mi_stream* s, const uint8_t* const* data, const size_t* lens, const uint32_t* rects,

@@ -142,6 +142,48 @@ def test_stream_api_errors_and_backpressure(mi):
     st.close()
 
 
+def test_refused_submits_leave_the_slots_free(mi, orc):
+    """One refused job of each kind on a stream of 100x44x3 in 32x16 tiles, two slots, two frames per job: a decode batch whose second
+    container has another tile size, a crops job with a rectangle outside the image, a resized job whose output exceeds the slot.  Each
+    keeps its status and queues nothing; then two encode jobs and two crops jobs go through both slots and equal the oracle's."""
+    w, h, c, tw, th, fpj = 100, 44, 3, 32, 16, 2
+    buf = np.stack([np.roll(make_image(("g3", "mid", "nat", "checker")[i], w, h, c), 5 * i, axis=1) for i in range(4)])
+    want = [orc.compress_sliced(buf[i], tw, th, False) for i in range(4)]
+    decoded = [orc.decompress(x)[1] for x in want]
+    st = mi.Stream(w, h, c, tw, th, False, depth=2, frames_per_job=fpj)
+    try:
+        other = np.frombuffer(orc.compress_sliced(buf[1], 16, 16, False), np.uint8)
+        refused = (
+            (lambda: st.submit_decode([np.frombuffer(want[0], np.uint8), other]), mi.BAD_ARGS),
+            (lambda: st.submit_decode_regions(want[:2], [(0, 0), (w - 40 + 1, 0)], 40, 20), mi.BAD_ARGS),
+            (lambda: st.submit_decode_resized_regions(want[:2], [(0, 0, 40, 20)] * 2, w, h + 1), mi.BAD_ARGS),
+        )
+        for submit, status in refused:
+            with pytest.raises(mi.LlcompError) as e:
+                submit()
+            assert e.value.status == status and st.pending() == 0
+        for j in range(2):  # both slots, so a slot that a refusal had left occupied or in flight would show as BUSY or as wrong bytes
+            assert st.submit_encode(buf[2 * j:2 * j + 2], tag=j)
+        assert st.pending() == 2
+        for j in range(2):
+            job = st.wait()
+            assert (job.status, job.kind, job.tag) == (mi.OK, mi.JOB_ENCODE, j)
+            assert [d.tobytes() for d in job.data] == want[2 * j:2 * j + 2]
+            st.release(job)
+        xy = [[(3, 7), (60, 24)], [(33, 0), (0, 17)]]
+        for j in range(2):
+            assert st.submit_decode_regions(want[2 * j:2 * j + 2], xy[j], 40, 20, tag=10 + j)
+        for j in range(2):
+            job = st.wait()
+            assert (job.status, job.kind, job.tag) == (mi.OK, mi.JOB_DECODE_REGIONS, 10 + j)
+            for f, (x, y) in enumerate(xy[j]):
+                assert np.array_equal(job.data[f], decoded[2 * j + f][y:y + 20, x:x + 40])
+            st.release(job)
+        assert st.pending() == 0
+    finally:
+        st.close()
+
+
 def test_host_calls_with_caller_provided_pinned_buffers(mi, orc):
     """llcomp_mi_encode_into / llcomp_mi_decode_into with pinned buffers from llcomp_mi_host_alloc: same bytes as the
     allocating calls; too-small buffers are reported with the size it takes and are not written."""
