@@ -17,9 +17,12 @@
 //
 // LDS contract: the entries of the model table carry absolute LDS addresses of their successors (load_table); the row bank is
 // the decoder's wide one (16-bit table addresses, [word 0..3][lane] 256 bytes apart, slot k in half k & 1 of word k / 2).
-// Register contract: the window lives in v[46:47] (an operand tied to the pair: the block needs its low half by name), the block
-// owns v32..v45, v48..v52 and s56..s71 for its length; with what hipcc needs around it the kernel stays at 56 VGPRs / 80 SGPRs
-// (eight wavefronts per SIMD with room to spare).  gfx950 hazards the assembler does not handle inside inline asm, checked by
+// Register contract: low, range and the window come in as READ-ONLY operands and leave as separate outputs (the block's first write
+// of each goes to the output), so the inputs are still the state before the sample when the block is done: they are the rollback
+// snapshot of the checked replay, nothing is saved per sample, and two consecutive samples can swap the roles of the two register
+// sets without a copy between them.  The window pair is an ordinary operand too (its low half is passed a second time as a 32-bit
+// operand: the block needs it by name).  The block owns v32..v45, v48..v52 and s56..s71 for its length; with what hipcc needs
+// around it the kernel stays below 64 VGPRs / 80 SGPRs (eight wavefronts per SIMD).  gfx950 hazards the assembler does not handle inside inline asm, checked by
 // hand: a vector instruction that reads VCC follows the vector instruction that wrote it by two wait states (s_nop 1).
 #pragma once
 #include <cstdint>
@@ -50,8 +53,6 @@ namespace llcomp_mi {
 #define LD_E4L "v48"
 #define LD_E4H "v49"
 #define LD_E4 "v[48:49]"
-#define LD_WINL "v46"
-#define LD_WIN "v[46:47]"
 #define LD_PROD "v50"  // range * P
 #define LD_R1 "v51"    // range * P >> 8
 #define LD_DIFF "v52"  // low - r0
@@ -78,6 +79,11 @@ namespace llcomp_mi {
     "v_mul_u32_u24_sdwa " LD_PROD ", " EL ", %[range] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:DWORD\n\t" \
     "v_lshrrev_b32_e32 " LD_R1 ", 8, " LD_PROD "\n\t"                                                                      \
     "v_sub_u32_e32 %[range], %[range], " LD_R1 "\n\t"
+// the same for the sample's first bin: reads the incoming range, writes the outgoing one
+#define LD_SPLIT_IN(EL)                                                                                                       \
+    "v_mul_u32_u24_sdwa " LD_PROD ", " EL ", %[range_in] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:DWORD\n\t" \
+    "v_lshrrev_b32_e32 " LD_R1 ", 8, " LD_PROD "\n\t"                                                                      \
+    "v_sub_u32_e32 %[range], %[range_in], " LD_R1 "\n\t"
 // refill (llcomp.hpp:115-120) of the lanes in exec
 #define LD_REFILL(N)                                         \
     "v_cmp_gt_u32_e32 vcc, %[c100], %[range]\n\t"            \
@@ -127,18 +133,20 @@ namespace llcomp_mi {
     "ds_read_b64 " LD_E6 ", " LD_E6L "\n\t"                   \
     "ds_read_b64 " LD_E7 ", " LD_E7L "\n\t"
 
-// in: exec = the lanes of the wavefront's slices; low / range / win as in RangeDec; w0..w3 = the context's wide row bank (read by
+// in: exec = the lanes of the wavefront's slices; low_in / range_in / win_in as in RangeDec (left untouched; low / range / win: the
+// same behind the sample); w0..w3 = the context's wide row bank (read by
 // the caller, who also needs it to roll back), bank = its LDS address; hot = wave-uniform "most lanes had a non-zero residual
 // last time" (in: entries of slots 1..7 are requested up front; out: the new flag).  out: value = the decoded residual's
 // magnitude with the sign bin applied (0 for a zero residual); w32 = what is left of the sample's private copy of the window's
 // next three bytes (refills take their byte from it and shift it down by a 2-cycle 32-bit shift; the 64-bit window moves once,
 // behind the sample, by the bytes that went): 0 = the sample wanted more than the three, or its exponent exceeded 31 ("Invalid
 // exponent", llcomp.hpp:230-235: the lane stops behind the exponent) -- the caller replays that lane on the checked path.
-__device__ __forceinline__ void dec_rows_sample_asm(uint32_t& low, uint32_t& range, unsigned long long& win, uint32_t w0, uint32_t w1,
-                                                    uint32_t w2, uint32_t w3, uint32_t bank, uint32_t& hot, uint32_t& value, uint32_t& w32) {
+__device__ __forceinline__ void dec_rows_sample_asm(uint32_t low_in, uint32_t range_in, unsigned long long win_in, uint32_t& low,
+                                                    uint32_t& range, unsigned long long& win, uint32_t w0, uint32_t w1, uint32_t w2,
+                                                    uint32_t w3, uint32_t bank, uint32_t& hot, uint32_t& value, uint32_t& w32) {
     asm volatile(
         "s_mov_b64 " LD_SX ", exec\n\t"
-        "v_and_b32_e32 %[w32], 0xffffff, " LD_WINL "\n\t"  // the sample's bytes: the window's next three under a sentinel 1
+        "v_and_b32_e32 %[w32], 0xffffff, %[winl_in]\n\t"  // the sample's bytes: the window's next three under a sentinel 1
         "v_or_b32_e32 %[w32], 0x1000000, %[w32]\n\t"
         "v_and_b32_e32 " LD_OFF ", 0xffff, %[w0]\n\t"
         "ds_read_b64 " LD_E0 ", " LD_OFF "\n\t"
@@ -152,13 +160,15 @@ __device__ __forceinline__ void dec_rows_sample_asm(uint32_t& low, uint32_t& ran
         "s_waitcnt lgkmcnt(0)\n"
         // ---- slot 0: a 1 = the residual is zero (the lane is done), a 0 (borrow) = it goes on
         ".Lzero_%=:\n\t"
-        LD_SPLIT(LD_E0L)
-        "v_sub_co_u32_e32 " LD_DIFF ", vcc, %[low], %[range]\n\t"
+        // (the outgoing low is the difference; the lanes with a borrow keep the incoming one -- the select stands where the move of
+        // the difference stood, two instructions behind the v_sub_co that wrote VCC)
+        LD_SPLIT_IN(LD_E0L)
+        "v_sub_co_u32_e32 %[low], vcc, %[low_in], %[range]\n\t"
         "ds_write_b16_d16_hi %[bank], " LD_E0L "\n\t"
         "s_and_b64 " LD_SA ", exec, vcc\n\t"
+        "v_cndmask_b32_e32 %[low], %[low], %[low_in], vcc\n\t"
         "s_andn2_b64 exec, exec, vcc\n\t"
         "s_cbranch_execz .Lz1_%=\n\t"
-        "v_mov_b32_e32 %[low], " LD_DIFF "\n\t"
         "v_mov_b32_e32 %[range], " LD_R1 "\n\t"
         "ds_write_b16_d16_hi %[bank], " LD_E0H "\n"
         ".Lz1_%=:\n\t"
@@ -285,15 +295,15 @@ __device__ __forceinline__ void dec_rows_sample_asm(uint32_t& low, uint32_t& ran
         "s_mov_b64 exec, " LD_SX "\n\t"
         "v_ffbh_u32_e32 " LD_DIFF ", %[w32]\n\t"          // the sentinel has moved down by 8 bits per byte consumed:
         "v_add_u32_e32 " LD_DIFF ", -7, " LD_DIFF "\n\t"  // clz - 7 bits  (a copy that is used up gives nonsense: that lane is replayed)
-        "v_lshrrev_b64 " LD_WIN ", " LD_DIFF ", " LD_WIN "\n\t"
+        "v_lshrrev_b64 %[win], " LD_DIFF ", %[win_in]\n\t"
         "s_bcnt1_i32_b64 " LD_S1 ", " LD_SA "\n\t"
         "s_bcnt1_i32_b64 " LD_S2 ", " LD_SX "\n\t"
         "s_lshl_b32 " LD_S1 ", " LD_S1 ", 1\n\t"
         "s_cmp_ge_u32 " LD_S1 ", " LD_S2 "\n\t"
         "s_cselect_b32 %[hot], 1, 0\n\t"
         "s_mov_b64 exec, " LD_SX "\n\t"
-        : [low] "+v"(low), [range] "+v"(range), "+{v[46:47]}"(win), [hot] "+s"(hot), [value] "=&v"(value), [w32] "=&v"(w32)
-        : [w0] "v"(w0), [w1] "v"(w1), [w2] "v"(w2), [w3] "v"(w3), [bank] "v"(bank), [c100] "s"(0x100u), [sel] "s"(0x06050400u),
+        : [low] "=&v"(low), [range] "=&v"(range), [win] "=&v"(win), [hot] "+s"(hot), [value] "=&v"(value), [w32] "=&v"(w32)
+        : [low_in] "v"(low_in), [range_in] "v"(range_in), [win_in] "v"(win_in), [winl_in] "v"(uint32_t(win_in)), [w0] "v"(w0), [w1] "v"(w1), [w2] "v"(w2), [w3] "v"(w3), [bank] "v"(bank), [c100] "s"(0x100u), [sel] "s"(0x06050400u),
           [sentv] "v"(0x80000000u)
         : "vcc", "scc", "memory", "v32", "v33", "v34", "v35", "v36", "v37", "v38", "v39", "v40", "v41", "v42", "v43", "v44", "v45",
           "v48", "v49", "v50", "v51", "v52", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65", "s66",

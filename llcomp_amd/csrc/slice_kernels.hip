@@ -22,6 +22,7 @@
 //     below states the same algorithm, serves every other kernel family and the decoder's checked replay, and is what
 //     the blocks are A/B-tested against (LLMI_ASM_ENC / LLMI_ASM_DEC = 0).
 #include <algorithm>
+#include <type_traits>
 
 #include "device_common.hpp"
 #include "kernels.hpp"
@@ -229,6 +230,12 @@ __device__ __forceinline__ void publish_count(unsigned long long* counters, uint
     }
     if (threadIdx.x == uint32_t(__builtin_ctzll(all))) atomicAdd(counters + which, sum);
 }
+
+// How the sample loops of a 1-row-slice kernel form L - l, the difference behind the context (llcomp.hpp:417-429 with h == 0).  The
+// model is fixed per launch, so it is a template flag of the kernels (SMALL): no loop carries a mask for it.
+constexpr int kModelSmall = 0;  // LargeModel = false -- and the first samples of a slice, which have no L: no difference, context 0
+constexpr int kModelLarge = 1;  // the difference as it is
+constexpr std::integral_constant<int, kModelSmall> no_model{};
 
 // ================================================ ENCODER ========================================================
 // Range encoder of one lane (llcomp.hpp:33-89).  Output bytes are staged in a per-lane 32-byte LDS area and leave for
@@ -471,11 +478,13 @@ extern __shared__ __attribute__((aligned(32))) unsigned char dyn_lds[];
 constexpr uint32_t kRowsEncTabOff = 0, kRowsEncStageOff = 1024, kRowsEncBankOff = 1024 + 16 + 32 * 64;
 constexpr uint32_t kRowsEncLdsBytes = kRowsEncBankOff + 3 * 64 * 8;
 // rare: a carry that the block could not finish inside the staging area goes on into the bytes already stored to HBM
-[[maybe_unused]] __device__ __forceinline__ void enc_carry_back_flushed(RangeEnc& e) {
+// (`out`: the lane's first unit, RangeEnc::out -- a parameter, so that a sample loop which can form it on the spot need not hold the
+// pointer in a register pair for the whole slice)
+[[maybe_unused]] __device__ __forceinline__ void enc_carry_back_flushed(RangeEnc& e, uint8_t* out) {
     if (e.flushed > 0 && e.flushed - 1 < e.cap) ++e.carries;
     for (int32_t k = e.flushed - 1; k >= 0; --k) {
         if (k >= e.cap) break;  // beyond the scratch capacity: the slice is reported as overflowed anyway
-        uint8_t* g = unit_byte(e, uint32_t(k));
+        uint8_t* g = out + ((size_t(uint32_t(k) >> 4) << (e.shift + 4)) + (uint32_t(k) & 15));  // unit_byte()
         const uint32_t v = *g;
         *g = uint8_t(v + 1);
         if (v != 0xFF) break;
@@ -495,14 +504,18 @@ __device__ __forceinline__ void clear_lds_states() {
 // seg_first + 4096) of every slice and parks the lane's coder -- low, range, the staged bytes, the count of flushed ones -- in a
 // 64-byte record per slice (`seg_state`) for the launch that codes the next segment, so that the coding of chunk c runs while the
 // pass prepares chunk c + 1 on another stream (codec.hip).  The last segment of a slice finishes its stream as ever.
-template <int NCH, bool ROWS, typename SYM, bool LDSTAB = false, bool SNAP = false, bool SEG = false>
-__global__ __launch_bounds__(64) void k_encode_slices(const Geometry g, const uint32_t lpw,
+// (the 1-row-slice kernels are held to the registers of eight wavefronts per SIMD: they are bound by instruction issue and live on
+// the other wavefronts' instructions while one waits)
+// SMALL (ROWS with SYM = uint8_t only, where the kernel forms the contexts itself): LargeModel = false.
+template <int NCH, bool ROWS, typename SYM, bool LDSTAB = false, bool SNAP = false, bool SEG = false, bool SMALL = false>
+__global__ __launch_bounds__(64, ROWS ? 8 : 1) void k_encode_slices(const Geometry g, const uint32_t lpw,
                                                       const SYM* __restrict__ sym, uint64_t* __restrict__ states,
                                                       uint8_t* __restrict__ scratch, uint32_t* __restrict__ slice_len,
                                                       uint64_t* __restrict__ group_sum, uint32_t* status, const uint64_t gpat,
                                                       unsigned long long* __restrict__ counters, const uint32_t seg_first = 0,
                                                       uint32_t* __restrict__ seg_state = nullptr) {
     static_assert(!(SNAP && (ROWS || LDSTAB)) && (SNAP || !SEG), "one kernel family at a time");
+    static_assert(!SMALL || (ROWS && sizeof(SYM) == 1), "the model is a template flag only where the kernel forms the contexts");
     constexpr bool ASM = (ROWS || SNAP) && LLMI_ASM_ENC != 0;
     entry_t* tab;
     uint8_t* stage;
@@ -600,7 +613,7 @@ __global__ __launch_bounds__(64) void k_encode_slices(const Geometry g, const ui
             enc_snap_sample_asm(low_range, e.wp, xs, bk.x, bk.y, res, e.base);
             if (__builtin_expect(xs.any_pend != 0, 0)) {
                 xs.any_pend = 0;
-                if (xs.pend) enc_carry_back_flushed(e);
+                if (xs.pend) enc_carry_back_flushed(e, e.out);
                 xs.pend = 0;
             }
 #else
@@ -671,7 +684,7 @@ __global__ __launch_bounds__(64) void k_encode_slices(const Geometry g, const ui
         const char* gsym;
         uint32_t sofs, sstep;
         [[maybe_unused]] uint32_t n_dword = total;  // PX: samples 0 .. n_dword-1 are read as dwords, the rest byte by byte (rows_px_dwords)
-        [[maybe_unused]] uint32_t psh = 0, msub = 0, my = 0, large = 0;
+        [[maybe_unused]] uint32_t psh = 0, msub = 0, my = 0;
         [[maybe_unused]] int pl = 128, pL = 128;  // PX: l and L of the lane's plane (llcomp.hpp:417-419: 128 at the slice start)
         if constexpr (PX) {
             // tile_h == 1: the tiles of a batch lie back to back in raster order, so lane 0's tile starts lowest and the wavefront's
@@ -691,7 +704,6 @@ __global__ __launch_bounds__(64) void k_encode_slices(const Geometry g, const ui
             psh = 8 * r.ch;
             msub = C >= 3 && (r.ch == 0 || r.ch == 2) ? ~0u : 0u;
             my = C >= 3 && r.ch == 1 ? ~0u : 0u;
-            large = (g.flags & kGeoSmallModel) ? 0u : ~0u;  // LargeModel = false: no quant5 term, context 0 (llcomp.hpp:427-429)
             asm volatile("" : "+v"(psh), "+v"(msub), "+v"(my));
         } else {
             const uint32_t grp = __builtin_amdgcn_readfirstlane(id >> g.lane_shift);
@@ -734,23 +746,51 @@ __global__ __launch_bounds__(64) void k_encode_slices(const Geometry g, const ui
         EncRowsExtra xs{0u, 0u, 0u};
         unsigned long long low_range = e.low | ((unsigned long long)e.range << 32);  // (one register pair: enc_rows_asm.hpp)
 #endif
-        // one sample (i: its index, wave-uniform): context -> row bank, residual -> bins
-        auto code = [&](uint32_t sy, uint32_t i) {
-            uint32_t bofs;  // |quant5(L - l)| * 512: byte offset of the context's row bank
-            int res;
-            if constexpr (PX) {  // stage A of k_model_rows_fwd for one sample of the lane's plane
+        // What the coding needs of a loaded symbol, formed BEFORE the load of the sample two ahead is issued (the asm pins the order):
+        // the symbol's register is free by then and the load can take it.  PX: the value of the lane's plane (stage A of
+        // k_model_rows_fwd for one sample); otherwise the symbol itself.
+        auto front = [&](uint32_t sy) -> uint32_t {
+            uint32_t t = sy;
+            if constexpr (PX) {
                 const uint32_t G = (sy >> 8) & 0xFF;
                 const int sum = int(sy & 0xFF) + int((sy >> 16) & 0xFF) - 2 * int(G);
-                const int t = (sum + int((uint32_t(sum) >> 31) * 3u)) >> 2;  // truncating division, llcomp.hpp:402
-                const int v = int(__builtin_amdgcn_ubfe(sy, psh, 8)) - int(G & msub) + (t & int(my));
-                // "no L at x <= 1" (llcomp.hpp:417-419): L - l = 0 for samples 0 and 1
-                const int dq = (pL - pl) & int(i >= 2 ? large : 0u);
-                const int sg = dq >> 31;  // hash = 605*quant5(L - l) < 0: the residual is folded (llcomp.hpp:433-436)
-                const uint32_t aq = uint32_t((dq ^ sg) - sg);
+                const int q = (sum + int((uint32_t(sum) >> 31) * 3u)) >> 2;  // truncating division, llcomp.hpp:402
+                t = uint32_t(int(__builtin_amdgcn_ubfe(sy, psh, 8)) - int(G & msub) + (q & int(my)));
+            }
+            asm volatile("" : "+v"(t) : : "memory");
+            return t;
+        };
+        // The context of a sample needs no symbol: PX, it hangs on pl and pL alone.  Formed in front of front(), it is the last reader
+        // of pL -- the value front() forms can then take pL's register, and pl / pL swap roles from sample to sample.  MODEL (PX only):
+        // how L - l is formed -- kModelSmall for the slice's first two samples ("no L at x <= 1", llcomp.hpp:417-419) and under
+        // LargeModel = false.
+        struct Ctx {
+            uint32_t bofs;  // |quant5(L - l)| * 512: byte offset of the context's row bank
+            int sg;         // hash = 605*quant5(L - l) < 0: the residual is folded (llcomp.hpp:433-436)
+        };
+        auto context = [&](auto model) -> Ctx {
+            constexpr int MODEL = decltype(model)::value;
+            Ctx c{0u, 0};
+            if constexpr (PX && MODEL != kModelSmall) {
+                const int dq = pL - pl;
+                c.sg = dq >> 31;
+                asm volatile("" : "+v"(c.sg));  // (or hipcc forms |d| with v_sub + v_max_i32, a 4-cycle form)
+                const uint32_t aq = uint32_t((dq ^ c.sg) - c.sg);
                 // |quant5| * 512 = 512 * ([aq >= 1] + [aq >= 4]); planes lie in [-255, 255], so aq <= 510 and bit 9 of aq + 511
                 // (aq + 508) says aq >= 1 (aq >= 4)
-                bofs = ((aq + 511u) & 0x200u) + ((aq + 508u) & 0x200u);
-                res = ((v - pl) ^ sg) - sg;
+                c.bofs = ((aq + 511u) & 0x200u) + ((aq + 508u) & 0x200u);
+                asm volatile("" : "+v"(c.bofs));
+            }
+            return c;
+        };
+        // one sample: context -> row bank, residual -> bins
+        auto code = [&](uint32_t sy, Ctx c, auto model) {
+            constexpr int MODEL = decltype(model)::value;
+            uint32_t bofs = c.bofs;
+            int res;
+            if constexpr (PX) {
+                const int v = int(sy);
+                res = MODEL == kModelSmall ? v - pl : ((v - pl) ^ c.sg) - c.sg;
                 pL = pl;
                 pl = v;
             } else if constexpr (sizeof(SYM) == 2) {  // fused stage A: |quant5| in bits 12..13, residual in bits 0..11
@@ -764,7 +804,8 @@ __global__ __launch_bounds__(64) void k_encode_slices(const Geometry g, const ui
             enc_rows_sample_asm(low_range, e.wp, xs, bank_base + bofs, res, e.base);
             if (__builtin_expect(xs.any_pend != 0, 0)) {
                 xs.any_pend = 0;
-                if (xs.pend) enc_carry_back_flushed(e);
+                // (all lanes of the wavefront belong to one lane group: the lane's first unit from the group's)
+                if (xs.pend) enc_carry_back_flushed(e, e.gout + (size_t(id & ((1u << g.lane_shift) - 1)) << 4));
                 xs.pend = 0;
             }
 #else
@@ -775,35 +816,57 @@ __global__ __launch_bounds__(64) void k_encode_slices(const Geometry g, const ui
 #endif
         };
         // Memory operations of one wave retire in order and s_waitcnt counts loads and stores together, so the order
-        // inside an iteration is: consume what was requested a sample ago (long back, no stall) -> issue the next prefetch
+        // inside a sample is: consume what was requested two samples ago (long back, no stall) -> issue the next prefetch
         // -> issue the stores of the previous sample's output.  Nothing is ever waited for right after it was issued.
-        // When all slices of the wavefront have the same length (all but those with the ragged last tile column), the bulk
-        // runs under a scalar loop counter with no per-lane tests; the last two samples (PX: rows_px_tail(C) -- the bulk loads
-        // no sample that may need byte reads: 5 for C = 1, 3 for C = 2 and 3, 2 for C = 4), and ragged wavefronts, take the loop
-        // with the tests.
+        // The slice's first two samples are coded in front of the loops, with their per-lane tests: they have no L, and no loop
+        // carries a test for them.  When all slices of the wavefront have the same length (all but those with the ragged last
+        // tile column), the bulk then runs under a scalar loop counter with no per-lane tests, two samples per turn: the prefetch
+        // distance is two, so the load for sample i + 2 goes into the register sample i has just left and pl / pL swap roles --
+        // nothing is copied at the back edge.  An odd sample, the last two samples (PX: rows_px_tail(C) -- the bulk loads no sample
+        // that may need byte reads: 5 for C = 1, 3 for C = 2 and 3, 2 for C = 4), and ragged wavefronts, take the loop with the tests.
         const uint32_t total0 = __builtin_amdgcn_readfirstlane(total);
         const bool same = __builtin_amdgcn_ballot_w64(total != total0) == 0;
         const uint32_t tail = PX ? rows_px_tail(g.c) : 2u;
         const uint32_t n_bulk = same && total0 > tail ? total0 - tail : 0;
-        uint32_t i = 0;
-        for (; i < n_bulk; ++i) {
-            s0 = consume_here(s0);  // loaded two samples ago
-            const uint32_t s2 = load_sym(sofs);
-            sofs += sstep;
-            if (e.wp >= e.base + 16) enc_flush16(e);  // 16 bytes staged (LDS addresses: no wrap-around, wp >= base - 1)
-            code(s0, i);
-            s0 = s1;
-            s1 = s2;
-        }
-        for (; i < total; ++i) {
+        auto sample_tested = [&](uint32_t i, auto model) {
             s0 = consume_here(s0);
+            const Ctx c0 = context(model);
+            const uint32_t t0 = front(s0);
             const uint32_t s2 = i + 2 < total ? load_at(sofs, i + 2) : 0;
             sofs += sstep;
-            if (e.wp >= e.base + 16) enc_flush16(e);
-            code(s0, i);
+            if (e.wp >= e.base + 16) enc_flush16(e);  // 16 bytes staged (LDS addresses: no wrap-around, wp >= base - 1)
+            code(t0, c0, model);
             s0 = s1;
             s1 = s2;
-        }
+        };
+        auto bulk = [&](uint32_t& i, auto model) {
+            for (; i + 1 < n_bulk; i += 2) {
+                s0 = consume_here(s0);  // loaded two samples ago
+                const Ctx c0 = context(model);
+                const uint32_t t0 = front(s0);
+                s0 = load_sym(sofs);
+                sofs += sstep;
+                if (e.wp >= e.base + 16) enc_flush16(e);
+                code(t0, c0, model);
+                s1 = consume_here(s1);
+                const Ctx c1 = context(model);
+                const uint32_t t1 = front(s1);
+                s1 = load_sym(sofs);
+                sofs += sstep;
+                if (e.wp >= e.base + 16) enc_flush16(e);
+                code(t1, c1, model);
+            }
+            for (; i < total; ++i) sample_tested(i, model);
+        };
+        sample_tested(0, no_model);  // (a slice has at least one sample)
+        if (total > 1) sample_tested(1, no_model);
+#if LLMI_ASM_ENC
+        // (behind a per-lane test hipcc holds the block's wave-uniform flags in vector registers: back to scalars)
+        xs.hot = __builtin_amdgcn_readfirstlane(xs.hot);
+        xs.any_pend = 0;
+#endif
+        uint32_t i = 2;
+        bulk(i, std::integral_constant<int, SMALL ? kModelSmall : kModelLarge>{});
 #if LLMI_ASM_ENC
         e.low = uint32_t(low_range);
         e.range = uint32_t(low_range >> 32);
@@ -1114,36 +1177,61 @@ __device__ __forceinline__ bool dec_residual(RangeDec& d, Bank& bank, const entr
 template <bool INLDS>
 __device__ __forceinline__ bool dec_sample(RangeDec& d, Bank& bank, const entry_t* tab, uint32_t& hot, bool replay_always,
                                            uint32_t& v) {
-    const uint32_t s_low = d.low, s_range = d.range, s_b0 = bank.w[0], s_b1 = bank.w[1], s_b2 = bank.w[2], s_b3 = bank.w[3];
-    const unsigned long long s_win = d.win;
-    bool ok;
 #if LLMI_ASM_DEC
-    if constexpr (INLDS) {  // the fast path of the 1-row-slice kernels is one hand-written block (dec_rows_asm.hpp)
-        uint32_t left;
-        dec_rows_sample_asm(d.low, d.range, d.win, bank.w[0], bank.w[1], bank.w[2], bank.w[3], lds_address(bank.lds), hot, v, left);
-        ok = left != 0;  // (more than three bytes wanted, or an invalid exponent: replayed below, where the verdict is formed)
+    if constexpr (INLDS) {
+        // The fast path of the 1-row-slice kernels is one hand-written block (dec_rows_asm.hpp).  It reads low, range, the window and
+        // the bank words and writes none of them: the coder's state behind the sample arrives in registers of its own, so what the
+        // block read IS the rollback snapshot -- nothing is copied per sample, and the registers of two consecutive samples simply
+        // swap roles (the bulk loops below code two samples per turn for that).
+        uint32_t low, range, left;
+        unsigned long long win;
+        dec_rows_sample_asm(d.low, d.range, d.win, low, range, win, bank.w[0], bank.w[1], bank.w[2], bank.w[3], lds_address(bank.lds), hot, v,
+                            left);
+        // left == 0: more than three bytes wanted, or an invalid exponent -- replayed, and the verdict is formed there
+        if (__builtin_expect(left == 0 || replay_always, 0)) {
+            ++d.replays;
+            // the fast path has already stored new states: put the old ones back
+            reinterpret_cast<uint32_t*>(bank.lds)[0] = bank.w[0];
+            reinterpret_cast<uint32_t*>(bank.lds)[64] = bank.w[1];
+            reinterpret_cast<uint32_t*>(bank.lds)[128] = bank.w[2];
+            reinterpret_cast<uint32_t*>(bank.lds)[192] = bank.w[3];
+            // The replay starts from the untouched inputs, IN the registers of the block's outputs (the copy is written out, or
+            // hipcc replays in place and has the fast path of every sample copy its results back instead).
+            asm("v_mov_b32_e32 %0, %3\n\tv_mov_b32_e32 %1, %4\n\tv_mov_b64_e32 %2, %5"
+                : "+v"(low), "+v"(range), "+v"(win)
+                : "v"(d.low), "v"(d.range), "v"(d.win));
+            d.low = low;
+            d.range = range;
+            d.win = win;
+            return dec_residual<false, true, true>(d, bank, tab, v);
+        }
+        d.low = low;
+        d.range = range;
+        d.win = win;
+        return true;
     } else
 #endif
     {
-        ok = hot ? dec_residual<true, false, INLDS>(d, bank, tab, v) : dec_residual<false, false, INLDS>(d, bank, tab, v);
+        const uint32_t s_low = d.low, s_range = d.range, s_b0 = bank.w[0], s_b1 = bank.w[1], s_b2 = bank.w[2], s_b3 = bank.w[3];
+        const unsigned long long s_win = d.win;
+        bool ok = hot ? dec_residual<true, false, INLDS>(d, bank, tab, v) : dec_residual<false, false, INLDS>(d, bank, tab, v);
         hot = 2 * __popcll(__ballot(v != 0)) >= __popcll(__ballot(true));  // (ballots are wave-uniform: scalar arithmetic)
-    }
-    // (hipcc's fast path signals a sample that ran out of window bytes by an empty window; the block signals it through `ok`)
-    const bool ran_dry = (INLDS && LLMI_ASM_DEC != 0) ? false : d.win == 0;
-    if (__builtin_expect(!ok || ran_dry || replay_always, 0)) {
-        ++d.replays;
-        d.low = s_low; d.range = s_range; d.win = s_win;
-        bank.w[0] = s_b0; bank.w[1] = s_b1;
-        if constexpr (INLDS) {  // the fast path has already stored new states: put the old ones back
-            bank.w[2] = s_b2; bank.w[3] = s_b3;
-            reinterpret_cast<uint32_t*>(bank.lds)[0] = s_b0;
-            reinterpret_cast<uint32_t*>(bank.lds)[64] = s_b1;
-            reinterpret_cast<uint32_t*>(bank.lds)[128] = s_b2;
-            reinterpret_cast<uint32_t*>(bank.lds)[192] = s_b3;
+        // (a sample that ran out of window bytes shows by an empty window)
+        if (__builtin_expect(!ok || d.win == 0 || replay_always, 0)) {
+            ++d.replays;
+            d.low = s_low; d.range = s_range; d.win = s_win;
+            bank.w[0] = s_b0; bank.w[1] = s_b1;
+            if constexpr (INLDS) {  // the fast path has already stored new states: put the old ones back
+                bank.w[2] = s_b2; bank.w[3] = s_b3;
+                reinterpret_cast<uint32_t*>(bank.lds)[0] = s_b0;
+                reinterpret_cast<uint32_t*>(bank.lds)[64] = s_b1;
+                reinterpret_cast<uint32_t*>(bank.lds)[128] = s_b2;
+                reinterpret_cast<uint32_t*>(bank.lds)[192] = s_b3;
+            }
+            ok = dec_residual<false, true, INLDS>(d, bank, tab, v);
         }
-        ok = dec_residual<false, true, INLDS>(d, bank, tab, v);
+        return ok;
     }
-    return ok;
 }
 
 // CACHE (2-D slices with their tables in HBM): log2 of the entries of a per-lane, direct-mapped, write-back cache of state
@@ -1155,8 +1243,9 @@ __device__ __forceinline__ bool dec_sample(RangeDec& d, Bank& bank, const entry_
 // (profiles/r05_bank_cache_ab.txt).  0 = no cache.  The entry count is geometry.hpp's kBankCacheLog2 (one constant for the flag, the
 // launcher and the kernel).
 constexpr uint32_t bank_cache_lds_bytes(int log2_entries) { return log2_entries ? (64u * 9u) << log2_entries : 0u; }
-template <int NCH, bool ROWS, bool LDSTAB = false, int CACHE = 0>
-__global__ __launch_bounds__(64) void k_decode_slices(const Geometry g, const uint32_t lpw_and_flags,
+// SMALL (ROWS only): LargeModel = false; the other families read the model from the geometry.
+template <int NCH, bool ROWS, bool LDSTAB = false, int CACHE = 0, bool SMALL = false>
+__global__ __launch_bounds__(64, ROWS && NCH == 1 ? 8 : 1) void k_decode_slices(const Geometry g, const uint32_t lpw_and_flags,
                                                       const uint8_t* __restrict__ units,
                                                       const uint32_t* __restrict__ slice_len,
                                                       uint64_t* __restrict__ states, int16_t* __restrict__ rec,
@@ -1174,6 +1263,7 @@ __global__ __launch_bounds__(64) void k_decode_slices(const Geometry g, const ui
         }
     }
     static_assert(CACHE == 0 || (!ROWS && !LDSTAB && NCH != 0), "the bank cache belongs to the 2-D kernels with tables in HBM");
+    static_assert(!SMALL || ROWS, "the model is a template flag of the 1-row-slice kernels only");
     // tags are bytes holding context >> CACHE, 0xFF = empty: no real tag may reach 0xFF
     static_assert(CACHE == 0 || ((kContexts - 1) >> CACHE) < 0xFF, "bank cache: a context's tag would alias the empty marker");
     // the wavefront's misses / look-ups since the last bypass check (CACHE): lanes add theirs, every lane reads the sums
@@ -1187,7 +1277,7 @@ __global__ __launch_bounds__(64) void k_decode_slices(const Geometry g, const ui
     load_table(tab);
     const uint32_t lpw = lpw_and_flags & 0xFF;
     const bool replay_always = (lpw_and_flags >> 8) & 1;  // test hook: send every sample through the checked replay too
-    const bool small_model = (g.flags & kGeoSmallModel) != 0;
+    [[maybe_unused]] const bool small_model = (g.flags & kGeoSmallModel) != 0;
     const uint32_t id = blockIdx.x * lpw + threadIdx.x;
     if (threadIdx.x >= lpw || id >= g.n_slices) return;
     const SliceRect r = slice_rect(g, id);
@@ -1217,57 +1307,77 @@ __global__ __launch_bounds__(64) void k_decode_slices(const Geometry g, const ui
 #pragma unroll
         for (int k = 0; k < NCH; ++k) l[k] = L[k] = 128;
         // The previous sample is stored only AFTER the window top-up of the next one, so the top-up never waits for a
-        // store that was issued a moment ago (see the encoder).  The very first store is a dummy to sample 0's own slot.
+        // store that was issued a moment ago (see the encoder).  The very first sample has nothing to store.
         // Per-sample bookkeeping in 2-cycle operations only (add / sub / and / xor / right shifts; tools/ubench/valu_rate3:
         // compares, selects on a scalar mask, min / max, LEFT shifts and everything with a scalar operand cost 4):
         //   * the context index |quant5(L - l)| = [|d| >= 1] + [|d| >= 4] goes straight into the byte offset of its row
         //     bank (1024 bytes per context): bit 31 of |d| + (2^31 - t) says |d| >= t, shifted down to bit 10;
-        //   * "no L at x <= 1" (llcomp.hpp:496) without a select: L starts equal to l, and behind sample 0 L takes the
-        //     decoded value instead of the old l, so L - l is 0 at x = 0 and x = 1 by itself;
-        //   * the sign fold is (v ^ s) - s with s = (L - l) >> 31; LargeModel = false masks the difference to 0;
-        //   * the store goes through a running 32-bit byte offset from the wave-uniform base (one instruction).
+        //   * "no L at x <= 1" (llcomp.hpp:496) without a select: L starts equal to l, and behind the slice's first pixel L takes
+        //     the decoded value instead of the old l, so L - l is 0 at x = 0 and x = 1 by itself.  The first pixel is coded in
+        //     front of the loops (START), so that no loop carries a mask for it;
+        //   * the sign fold is (v ^ s) - s with s = (L - l) >> 31.  LargeModel = false (SMALL) has no difference at all: context 0,
+        //     no fold;
+        //   * the store goes through ONE running 32-bit byte offset from the wave-uniform base: the delayed store of the sample
+        //     before uses it, then it moves on.
         int held_val = 0;
-        uint32_t held_ofs = lane_in_group * 2, next_ofs = held_ofs, step_ofs = 2u << g.lane_shift;
-        uint32_t large = small_model ? 0u : ~0u, first = ~0u;
-        asm volatile("" : "+v"(large), "+v"(first), "+v"(step_ofs));  // (vector values: keeps hipcc from going back to selects)
+        uint32_t store_ofs = lane_in_group * 2, step_ofs = 2u << g.lane_shift;
+        asm volatile("" : "+v"(step_ofs));  // (a vector value: an add with a scalar operand costs twice as much)
         uint8_t* const bank0 = reinterpret_cast<uint8_t*>(rowbank) + threadIdx.x * 4;
         // "Invalid exponent" (llcomp.hpp:230-235) does not leave the loop: the lane notes it and decodes on (whatever it
         // reads stays inside its own stream and slice, and the call reports the error) -- so the loop has no per-lane exit,
         // and when all slices of the wavefront are equally wide it runs under a scalar counter with no per-lane tests at all.
         bool bad = false;
-        auto pixel = [&]() {
+        auto pixel = [&](auto model, auto start) {
+            constexpr int MODEL = decltype(model)::value;
+            constexpr bool START = decltype(start)::value;
 #pragma unroll
             for (int k = 0; k < NCH; ++k) {
                 if (window_low(d)) dec_append(d);
-                asm volatile("global_store_short %0, %1, %2" : : "v"(held_ofs), "v"(held_val), "s"(gbase) : "memory");
+                if (!(START && k == 0)) {
+                    asm volatile("global_store_short %0, %1, %2" : : "v"(store_ofs), "v"(held_val), "s"(gbase) : "memory");
+                    store_ofs += step_ofs;
+                }
                 const int lv = l[k];  // x == 0: 128
-                const int dq = (L[k] - lv) & int(large);
-                int sg = dq >> 31;  // hash = 605*quant5(L-l) < 0: the residual was folded
-                asm volatile("" : "+v"(sg));  // (or hipcc forms |d| with v_max and the offset with v_and_or: 4-cycle operations)
-                const uint32_t aq = uint32_t((dq ^ sg) - sg);
-                uint32_t o1 = ((aq + 0x7FFFFFFFu) >> 21) & 0x400u, o2 = ((aq + 0x7FFFFFFCu) >> 21) & 0x400u;
-                asm volatile("" : "+v"(o1), "+v"(o2));
-                uint32_t* bp = reinterpret_cast<uint32_t*>(bank0 + (o1 + o2));  // |quant5(L - l)| * 1024
+                uint32_t sg = 0, bofs = 0;
+                if constexpr (MODEL != kModelSmall) {
+                    const int dq = L[k] - lv;
+                    sg = uint32_t(dq >> 31);  // hash = 605*quant5(L-l) < 0: the residual was folded
+                    asm volatile("" : "+v"(sg));  // (or hipcc forms |d| with v_max and the offset with v_and_or: 4-cycle operations)
+                    const uint32_t aq = (uint32_t(dq) ^ sg) - sg;
+                    uint32_t o1 = ((aq + 0x7FFFFFFFu) >> 21) & 0x400u, o2 = ((aq + 0x7FFFFFFCu) >> 21) & 0x400u;
+                    asm volatile("" : "+v"(o1), "+v"(o2));
+                    bofs = o1 + o2;  // |quant5(L - l)| * 1024
+                }
+                uint32_t* bp = reinterpret_cast<uint32_t*>(bank0 + bofs);
                 Bank bank{{bp[0], bp[64], bp[128], bp[192]}, reinterpret_cast<uint8_t*>(bp)};
                 uint32_t v = 0;
                 if (!dec_sample<true>(d, bank, tab, hot, replay_always, v)) bad = true;
-                v = (v ^ uint32_t(sg)) - uint32_t(sg);
+                if constexpr (MODEL != kModelSmall) v = (v ^ sg) - sg;
                 const int val = int(int16_t(uint32_t(lv) + v));
                 held_val = val;
-                held_ofs = next_ofs;
-                next_ofs += step_ofs;
-                L[k] = lv ^ ((lv ^ val) & int(first));
+                L[k] = START ? val : lv;
                 l[k] = val;
             }
-            first = 0;
         };
+        // Two pixels per turn of the bulk loop: the coder's state, l / L and the bank words of consecutive samples alternate between
+        // two sets of registers (a sample reads one and leaves the other), so nothing is copied at the back edge.  An odd pixel is
+        // left to the loop with the per-lane tests, as are ragged wavefronts.
         const uint32_t sw0 = __builtin_amdgcn_readfirstlane(r.sw);
         const uint32_t n_bulk = __builtin_amdgcn_ballot_w64(r.sw != sw0) == 0 ? sw0 : 0;
-        uint32_t x = 0;
-        for (; x < n_bulk; ++x) pixel();
-        for (; x < r.sw; ++x) pixel();
+        uint32_t x = 1;
+        pixel(no_model, std::true_type{});  // (a slice has at least one pixel; L == l here: no difference under either model)
+        constexpr std::integral_constant<int, SMALL ? kModelSmall : kModelLarge> model{};
+        if constexpr (NCH == 1) {
+            for (; x + 1 < n_bulk; x += 2) {
+                pixel(model, std::false_type{});
+                pixel(model, std::false_type{});
+            }
+        } else {  // (interleaved channels: a pixel is several samples already)
+            for (; x < n_bulk; ++x) pixel(model, std::false_type{});
+        }
+        for (; x < r.sw; ++x) pixel(model, std::false_type{});
         if (bad) atomicOr(status, kStBadExponent);
-        asm volatile("global_store_short %0, %1, %2" : : "v"(held_ofs), "v"(held_val), "s"(gbase) : "memory");
+        asm volatile("global_store_short %0, %1, %2" : : "v"(store_ofs), "v"(held_val), "s"(gbase) : "memory");
         publish_count(counters, kCtrDecReplays, d.replays);
     } else {
         // Neighbours of the row above rotate through registers (tl <- t <- tr); the two values the NEXT pixel needs
@@ -1563,8 +1673,9 @@ hipError_t launch_encode_slices(const Geometry& g, const void* d_sym, uint64_t* 
     const uint32_t blocks = (g.n_slices + lpw - 1) / lpw;
     uint64_t* const d_group_sum = encoder_writes_group_sums(g) ? d_group_off : nullptr;
     if (rows_encoder_reads_pixels(g)) {  // planar 1-row slices: the ROWS kernel reads the pixels and runs stage A itself
-        k_encode_slices<1, true, uint8_t><<<dim3(blocks), dim3(64), LLMI_ASM_ENC ? kRowsEncLdsBytes : 0, stream>>>(
-            g, lpw, static_cast<const uint8_t*>(d_sym), d_states, d_scratch, d_slice_len, d_group_sum, d_status, gpat, d_counters);
+        auto kernel = (g.flags & kGeoSmallModel) ? k_encode_slices<1, true, uint8_t, false, false, false, true> : k_encode_slices<1, true, uint8_t>;
+        kernel<<<dim3(blocks), dim3(64), LLMI_ASM_ENC ? kRowsEncLdsBytes : 0, stream>>>(
+            g, lpw, static_cast<const uint8_t*>(d_sym), d_states, d_scratch, d_slice_len, d_group_sum, d_status, gpat, d_counters, 0u, nullptr);
         return hipGetLastError();
     }
     if (model_is_fused(g)) {  // ... tiles too wide for that: 16-bit symbols from launch_model_rows_fwd
@@ -1616,6 +1727,9 @@ hipError_t launch_decode_slices(const Geometry& g, const uint8_t* d_units, const
     }
     LLMI_DISPATCH_SLICE(g.nch, rows_mode(g), lds, {
         auto kernel = k_decode_slices<C, R, T>;
+        if constexpr (R) {  // the 1-row-slice kernels have the model as a template flag
+            if (g.flags & kGeoSmallModel) kernel = k_decode_slices<C, R, T, 0, true>;
+        }
         if (T) {
             const hipError_t e = allow_big_lds(kernel);
             if (e != hipSuccess) return e;
