@@ -37,7 +37,9 @@ extern "C" {
  * update -- llcomp_mi_replace_slices(_into), llcomp_mi_update_region(_into), llcomp_mi_codec_encode_region,
  * llcomp_mi_codec_update_region, LLCOMP_MI_PREPARE_UPDATE; several views of each frame, each frame decoded once -- llcomp_mi_view,
  * llcomp_mi_view_group, llcomp_mi_views_plan, llcomp_mi_codec_decode_views(_host), llcomp_mi_codec_views_workspace_bytes,
- * LLCOMP_MI_PREPARE_VIEWS).  The library and its callers are built from ONE header: structs have one layout per ABI version (llcomp_mi_opts is
+ * LLCOMP_MI_PREPARE_VIEWS; crops that leave the image -- llcomp_mi_pad, llcomp_mi_pad_axis, llcomp_mi_padded_filter_weights,
+ * llcomp_mi_padded_regions_plan, llcomp_mi_codec_decode_padded_regions(_host), llcomp_mi_codec_decode_padded_views(_host),
+ * llcomp_mi_codec_padded_workspace_bytes, LLCOMP_MI_CTR_BIAS_LAUNCHES).  The library and its callers are built from ONE header: structs have one layout per ABI version (llcomp_mi_opts is
  * checked through struct_size and refused when it differs; llcomp_mi_info and llcomp_mi_stream_result are written in full),
  * so a binding compares llcomp_mi_abi_version() with the LLCOMP_MI_ABI_VERSION it was generated from and refuses to run on
  * a mismatch -- there is no cross-version compatibility mode. */
@@ -342,6 +344,49 @@ typedef struct llcomp_mi_view_group {
 int llcomp_mi_views_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar, uint32_t frames,
                          const llcomp_mi_view_group* groups, uint32_t n_groups, uint32_t* unions, uint32_t* windows, uint32_t* n_used,
                          uint32_t* n_classes);
+/* Crops that leave the image (the padded calls below: RandomCrop(padding=...), pad_if_needed, a CenterCrop larger than the picture, a
+ * random translate).  "Pad, then crop, then resize" without a padded copy: for one axis of side n and the rectangle [x, x + r) -- x a
+ * signed 32-bit value, r >= 1, left pad p = max(-x, 0), right pad e = max(x + r - n, 0) -- an index t outside [0, n) stands for
+ *   mode                         t < 0        t >= n            limit
+ *   LLCOMP_MI_PAD_CONSTANT  0    the channel's fill value       p, e <= n
+ *   LLCOMP_MI_PAD_EDGE      1    0            n - 1             p, e <= n
+ *   LLCOMP_MI_PAD_REFLECT   2    -t           2 (n - 1) - t     p, e <= n - 1
+ *   LLCOMP_MI_PAD_SYMMETRIC 3    -t - 1       2 n - 1 - t       p, e <= n
+ * (source index m(t); numpy's np.pad modes and torchvision's padding_mode of the same names).  The rectangle must hold at least one
+ * image pixel on each axis (x < n and x + r > 0), so r <= 3 n.
+ * SOURCE INTERVAL [s0, s0 + s_len): the set of m(t) over the rectangle's indices -- contiguous, and for CONSTANT and EDGE
+ * [max(x, 0), min(x + r, n)).  A frame's SOURCE RECTANGLE is the product of its two intervals: it lies inside the image and is all the
+ * decoder sees.
+ * FOLDED WEIGHTS AND BIAS: with (lo_i, q_ij) = llcomp_mi_resize_filter_weights(filter, r, out) -- the downscale limit is checked on
+ * r -> out -- output i of the axis has Q_i[s] = sum_j { q_ij : m(x + lo_i + j) = s } over the source interval, and the bias
+ * B_i = sum_j { q_ij : x + lo_i + j outside the image } for CONSTANT, 0 for every other mode; emitted as lo'[out] (relative to s0) and
+ * q'[out][K'], zero taps trimmed, lo' + K' <= s_len (a run moved left over zero weights where needed).  K' <= K and
+ * sum |Q| + |B| <= sum |q|, so the int32 accumulators hold.
+ * OUTPUT: a pass computes clamp((sum_s Q_i[s] * in[s] + B_i * fill[ch] + 2^21) >> 22, 0, 255) -- the horizontal pass first, over the
+ * SOURCE ROWS only, rounded to u8, then the vertical pass, the mirror and the output table.  A padded row needs no row in between: its
+ * horizontal result is exactly fill[ch] (|fill * (sum q - 2^22)| < 2^21), which is what the vertical bias adds.  A rectangle inside the
+ * image gives s0 = x, the unfolded weights and no bias: the unpadded call, byte for byte. */
+enum { LLCOMP_MI_PAD_CONSTANT = 0, LLCOMP_MI_PAD_EDGE = 1, LLCOMP_MI_PAD_REFLECT = 2, LLCOMP_MI_PAD_SYMMETRIC = 3 };
+typedef struct llcomp_mi_pad {
+    uint32_t struct_size; /* sizeof(llcomp_mi_pad) (at least) */
+    uint32_t mode;        /* LLCOMP_MI_PAD_*: one mode per call */
+    const uint8_t* fill;  /* CONSTANT: c HOST values, NULL = zeros; ignored by every other mode; read during the call only */
+} llcomp_mi_pad; /* 16 bytes on LP64 */
+/* The source interval of one axis.  BAD_ARGS for a NULL s0 or s_len, a mode above 3, n or r 0, a rectangle with no image pixel, or a
+ * pad above the mode's limit.  Host-only. */
+int llcomp_mi_pad_axis(uint32_t mode, uint32_t n, int32_t x, uint32_t r, uint32_t* s0, uint32_t* s_len);
+/* The folded rule of one axis: returns K' and fills *s0, lo[out_len], q[out_len][K'] (zero-padded) and bias[out_len]; each of the four
+ * may be NULL.  For a rectangle inside the image lo and q are llcomp_mi_resize_filter_weights' with every run moved left until
+ * lo + K <= r.  0 for what llcomp_mi_pad_axis or llcomp_mi_resize_filter_weights(filter, r, out_len) refuse.  Host-only; the GPU runs
+ * exactly these weights. */
+uint32_t llcomp_mi_padded_filter_weights(uint32_t filter, uint32_t mode, uint32_t n, int32_t x, uint32_t r, uint32_t out_len, uint32_t* s0,
+                                         uint32_t* lo, int32_t* q, int32_t* bias);
+/* Every frame's source rectangle: rects = {x, y, rw, rh} per frame (4 * n, x and y signed) -> src[4 * n] = {s0x, s0y, s_len_x, s_len_y}.
+ * What a padded call decodes is what the unpadded calls decode for these rectangles: llcomp_mi_resized_regions_plan on them gives the
+ * windows of a padded resized call, llcomp_mi_views_plan on the views' source rectangles the unions and windows of a padded views call.
+ * BAD_ARGS, with src untouched: n = 0, a NULL rects, pad or src, a struct_size below the struct's, a mode above 3, a size below 1, a
+ * rectangle with no image pixel on an axis, a pad above the mode's limit.  Host-only. */
+int llcomp_mi_padded_regions_plan(uint32_t w, uint32_t h, const int32_t* rects, uint32_t n, const llcomp_mi_pad* pad, uint32_t* src);
 uint32_t llcomp_mi_slice_count(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar);
 /* Slice width for one-row slices (tile_h = 1) when `frames` frames are coded per call: the widest slice (64..480 pixels) that
  * still keeps about four wavefronts per SIMD busy.  A call that codes few frames is latency-bound with wide slices; this
@@ -566,6 +611,40 @@ int llcomp_mi_codec_decode_views_host(llcomp_mi_codec* codec, const uint8_t* con
  * with the views: every view beyond `frames` adds 48 + 40 * (w + h) + 16 + 1024 * c bytes (its table entry, its weights at their upper
  * bound, and an output table); for total_views <= frames this is llcomp_mi_codec_workspace_bytes. */
 uint64_t llcomp_mi_codec_views_workspace_bytes(const llcomp_mi_codec* codec, uint64_t total_views);
+/* The _ex resized calls with rectangles that may leave the image (llcomp_mi_pad above): rects = {x, y, rw, rh} per frame, x and y signed;
+ * fmt NULL = U8 HWC.  Every frame decodes the window of its SOURCE rectangle -- the classes, the gather and the one copy of
+ * llcomp_mi_codec_decode_resized_regions_ex on the source rectangles, unchanged -- and the resample kernels run the folded weights on
+ * it: no pass over padded pixels and no padded copy in HBM.  Frame f gets byte for byte the _ex call's output for np.pad(frame, mode)
+ * cut at the rectangle; a rectangle inside the image gives the _ex call's bytes for it.  Only CONSTANT with a fill other than 0 on a
+ * rectangle that leaves the image needs what the unpadded kernels do not have: the bias forms of the three resample kernels, which start
+ * every accumulator at bias * fill[ch]; a launch uses them when an entry of its chunk has a bias that is not 0
+ * (LLCOMP_MI_CTR_BIAS_LAUNCHES counts those launches) and the parent's kernels otherwise.  d_status and the verdicts as for the _ex call
+ * on the source rectangles.  BAD_ARGS, before anything is queued or written (d_status untouched): every case of the _ex call, a NULL pad, a
+ * struct_size below the struct's, a mode above 3, a size below 1, a pad above the mode's limit, a rectangle with no image pixel on an
+ * axis. */
+int llcomp_mi_codec_decode_padded_regions(llcomp_mi_codec* codec, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                          const int32_t* rects, const uint8_t* flags, uint32_t ow, uint32_t oh, const llcomp_mi_pad* pad,
+                                          const llcomp_mi_output_format* fmt, void* d_out, void* d_status, void* stream);
+int llcomp_mi_codec_decode_padded_regions_host(llcomp_mi_codec* codec, const uint8_t* const* data, const size_t* lens, const int32_t* rects,
+                                               const uint8_t* flags, uint32_t ow, uint32_t oh, const llcomp_mi_pad* pad,
+                                               const llcomp_mi_output_format* fmt, void* d_out, void* d_status, void* stream);
+/* llcomp_mi_codec_decode_views(_host) with views that may leave the image: the same group and view structs, a view's x and y read as
+ * two's-complement int32, one pad for the call.  A frame decodes the bounding box of its views' SOURCE rectangles; view v of a group gets
+ * byte for byte what llcomp_mi_codec_decode_padded_regions writes for that rectangle.  BAD_ARGS: every case of the views call (on the
+ * source rectangles) and of the pad, as above. */
+int llcomp_mi_codec_decode_padded_views(llcomp_mi_codec* codec, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                        const llcomp_mi_view_group* groups, uint32_t n_groups, const llcomp_mi_pad* pad, void* d_status,
+                                        void* stream);
+int llcomp_mi_codec_decode_padded_views_host(llcomp_mi_codec* codec, const uint8_t* const* data, const size_t* lens,
+                                             const llcomp_mi_view_group* groups, uint32_t n_groups, const llcomp_mi_pad* pad, void* d_status,
+                                             void* stream);
+/* The bound on llcomp_mi_codec_allocated_bytes for padded calls of up to total_views views (a padded resized call: `frames`) with
+ * ow <= w, oh <= h.  The boxes and the horizontal pass's rows shrink or stay -- source rectangles lie inside the image -- but the staged
+ * tables grow: r reaches 3 n, so an axis takes out * (K' + 1) int32 of weights and `out` of bias with K' <= K <= 6 * max(r / out, 1) + 3,
+ * at most 6 * max(r, out) + 5 * out <= 23 * side against the unpadded 10 * side, and the call adds c int32 of fill values.  So this is
+ * llcomp_mi_codec_views_workspace_bytes(total_views) + max(total_views, frames) * 52 * (w + h) + 4 * c: every view beyond `frames` adds
+ * 48 + 92 * (w + h) + 16 + 1024 * c bytes.  llcomp_mi_codec_workspace_bytes and _views_workspace_bytes keep their values. */
+uint64_t llcomp_mi_codec_padded_workspace_bytes(const llcomp_mi_codec* codec, uint64_t total_views);
 /* Stage-A only (context + prediction model), for tests and profiling: d_sym u32[frames*h*w*c],
  * low 16 bits = folded context (0..7925), high 16 bits = folded residual (two's complement). */
 int llcomp_mi_codec_model(llcomp_mi_codec* codec, const void* d_px, void* d_sym, void* stream);
@@ -604,6 +683,8 @@ enum {
     LLCOMP_MI_CTR_DEC_LAUNCHES_PLAIN = 9,  /* ... and without it, because (nearly) every wavefront of the last cached launch had given
                                               it up: the plain kernel holds no LDS for a cache nobody uses; re-probed every 16th call */
     LLCOMP_MI_CTR_HOST_STAGED_BYTES = 10,  /* payload bytes llcomp_mi_codec_decode_regions_host copied to the GPU (host-side count) */
+    LLCOMP_MI_CTR_BIAS_LAUNCHES = 11,      /* resample launches of the padded calls that ran the kernels' bias forms: a chunk with an entry
+                                              whose constant fill other than 0 has weight (host-side count) */
     LLCOMP_MI_CTR_COUNT = 16
 };
 int llcomp_mi_codec_get_counters(llcomp_mi_codec* codec, uint64_t* out, uint32_t n, int reset);

@@ -19,6 +19,10 @@ with ctypes and keeps the reference's names and error behaviour:
     views_plan / ViewGroup / Codec.decode_views(_host) / Codec.views_workspace_bytes  (several views of each frame in one call, each
         frame decoded once: a view = (frame, x, y, rw, rh, flags), a group = views that share one output shape, format and buffer --
         multi-crop (2 x 224 + 8 x 96) and two-view training; a frame decodes the bounding box of its views)
+    PAD_* / pad_axis / padded_weights / padded_regions_plan / pad_mode=, fill= of Codec.decode_resized_regions(_host) and
+        Codec.decode_views(_host) / Codec.padded_workspace_bytes  (crops that leave the image -- RandomCrop(padding=...), pad_if_needed, a
+        CenterCrop larger than the picture, a translate: rectangles and view origins may be negative, the outside is np.pad's
+        "constant" (with fill), "edge", "reflect" or "symmetric", and only the part inside the image is decoded)
     RawImage(pixels, width, height, channels)     <->  llcomp::RawImage         (/root/reference/llcomp.hpp:454-459)
     EXT = ".llcomp"                               <->  llcomp::ext              (/root/reference/llcomp.hpp:18)
 
@@ -32,6 +36,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import Info, Opts, OutputFormat
+from ._lib import Pad as _Pad
 from ._lib import View as _View, ViewGroup as _ViewGroup
 
 EXT = ".llcomp"
@@ -44,6 +49,9 @@ LAYOUT_HWC, LAYOUT_CHW = 0, 1
 FILTER_BILINEAR, FILTER_NEAREST, FILTER_BOX, FILTER_HAMMING, FILTER_BICUBIC, FILTER_LANCZOS = range(6)
 FILTER_NAMES = ("bilinear", "nearest", "box", "hamming", "bicubic", "lanczos")
 FLAG_MIRROR, FLAG_FILTER_SHIFT = 1, 4
+# what stands outside the image in a padded call (LLCOMP_MI_PAD_*): numpy's np.pad modes and torchvision's padding_mode of these names
+PAD_CONSTANT, PAD_EDGE, PAD_REFLECT, PAD_SYMMETRIC = range(4)
+PAD_NAMES = ("constant", "edge", "reflect", "symmetric")
 
 RawImage = namedtuple("RawImage", "pixels width height channels")
 
@@ -171,6 +179,81 @@ def _rects_table(rects, n=None):
         raise LlcompError(BAD_ARGS, f"rects must be {n if n is not None else 'n'} x 4 non-negative integers, got shape {a.shape} {a.dtype}")
     flat = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1)
     return (C.c_uint32 * flat.size)(*flat.tolist()), a.shape[0]
+
+
+def _signed_rects_table(rects, n=None):
+    """a sequence of (x, y, rw, rh) with x and y of either sign -> (ctypes i32 array of 4n values, n); BAD_ARGS otherwise"""
+    a = np.asarray(rects)
+    if a.ndim != 2 or a.shape[1] != 4 or a.shape[0] < 1 or (n is not None and a.shape[0] != n) or not np.issubdtype(a.dtype, np.integer) \
+            or (a.size and (a.min() < -0x80000000 or a.max() > 0x7FFFFFFF)):
+        raise LlcompError(BAD_ARGS, f"rects must be {n if n is not None else 'n'} x 4 integers of 32 bits, got shape {a.shape} {a.dtype}")
+    flat = np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+    return (C.c_int32 * flat.size)(*flat.tolist()), a.shape[0]
+
+
+def pad_code(pad_mode):
+    """PAD_* of a code (0..3) or a name ("constant", "edge", "reflect", "symmetric"); BAD_ARGS for anything else"""
+    if isinstance(pad_mode, str) and pad_mode.lower() in PAD_NAMES:
+        return PAD_NAMES.index(pad_mode.lower())
+    if isinstance(pad_mode, (int, np.integer)) and not isinstance(pad_mode, bool) and 0 <= int(pad_mode) < len(PAD_NAMES):
+        return int(pad_mode)
+    raise LlcompError(BAD_ARGS, f"pad_mode must be one of {PAD_NAMES} or its code 0..{len(PAD_NAMES) - 1}, got {pad_mode!r}")
+
+
+def _pad(c, pad_mode, fill=None):
+    """(llcomp_mi_pad, what must stay alive during the call).  pad_mode None with a fill is "constant"; fill: one value or c values in 0..255"""
+    mode = PAD_CONSTANT if pad_mode is None else pad_code(pad_mode)
+    arr = None
+    if fill is not None:
+        a = np.asarray(fill).reshape(-1)
+        if a.size == 1:
+            a = np.full(c, a[0])
+        if a.size != c or not np.issubdtype(a.dtype, np.integer) or a.min() < 0 or a.max() > 255:
+            raise LlcompError(BAD_ARGS, f"fill takes one or {c} integers in 0..255, got {fill!r}")
+        arr = (C.c_uint8 * c)(*[int(v) for v in a.tolist()])
+    pad = _Pad(C.sizeof(_Pad), mode, C.cast(arr, _lib.u8p) if arr is not None else None)
+    return pad, (pad, arr)
+
+
+def pad_axis(pad_mode, n, x, r):
+    """(s0, s_len): the source interval of the rectangle [x, x + r) of an axis of side n under pad_mode (llcomp_mi_pad_axis, host only) --
+    the image pixels the padded rectangle is made of.  LlcompError(BAD_ARGS) for a rectangle with no image pixel or a pad above the mode's
+    limit (n - 1 for "reflect", else n)."""
+    if not (-0x80000000 <= int(x) <= 0x7FFFFFFF and 0 <= int(n) <= 0xFFFFFFFF and 0 <= int(r) <= 0xFFFFFFFF):
+        raise LlcompError(BAD_ARGS, f"no rectangle [{x}, {x} + {r}) of an axis of {n}")
+    s0, sl = C.c_uint32(), C.c_uint32()
+    _check(_lib.load().llcomp_mi_pad_axis(pad_code(pad_mode), n, x, r, C.byref(s0), C.byref(sl)))
+    return s0.value, sl.value
+
+
+def padded_weights(filter, pad_mode, n, x, r, out_len):
+    """(s0, lo np.uint32[out_len], q np.int32[out_len, K'], bias np.int32[out_len]) of one axis of a padded call
+    (llcomp_mi_padded_filter_weights, host only): output i = clamp((sum_j q[i, j] * src[s0 + lo[i] + j] + bias[i] * fill + 2^21) >> 22) --
+    resize_weights(r, out_len, filter) with every tap on a padded index folded onto the source pixel it stands for, or into the bias for
+    "constant".  LlcompError(BAD_ARGS) for what pad_axis or resize_weights refuse."""
+    L = _lib.load()
+    code = int(filter) if isinstance(filter, (int, np.integer)) and not isinstance(filter, bool) and 0 <= int(filter) <= 0xFFFFFFFF else filter_code(filter)
+    mode = pad_code(pad_mode)
+    if not (-0x80000000 <= int(x) <= 0x7FFFFFFF and 0 <= int(n) <= 0xFFFFFFFF and 0 <= int(r) <= 0xFFFFFFFF and 0 <= int(out_len) <= 0xFFFFFFFF):
+        raise LlcompError(BAD_ARGS, f"no resampling of [{x}, {x} + {r}) of an axis of {n} to {out_len}")
+    s0 = C.c_uint32()
+    k = L.llcomp_mi_padded_filter_weights(code, mode, n, x, r, out_len, C.byref(s0), None, None, None)
+    if not k:
+        raise LlcompError(BAD_ARGS, f"no resampling of [{x}, {x} + {r}) of an axis of {n} to {out_len} with filter {filter!r}, pad {pad_mode!r}")
+    lo, q, bias = np.zeros(out_len, np.uint32), np.zeros((out_len, k), np.int32), np.zeros(out_len, np.int32)
+    L.llcomp_mi_padded_filter_weights(code, mode, n, x, r, out_len, C.byref(s0), lo.ctypes.data, q.ctypes.data, bias.ctypes.data)
+    return s0.value, lo, q, bias
+
+
+def padded_regions_plan(w, h, rects, pad_mode):
+    """every rectangle's SOURCE rectangle [n, 4] of (x, y, rw, rh) inside the image (llcomp_mi_padded_regions_plan, host only): what a padded
+    call decodes is what the unpadded calls decode for these -- resized_regions_plan of them gives its windows, views_plan of the views'
+    source rectangles its unions.  LlcompError(BAD_ARGS) for a rectangle with no image pixel on an axis or a pad above the mode's limit."""
+    tab, n = _signed_rects_table(rects)
+    pad, _keep = _pad(1, pad_mode)
+    src = np.zeros((n, 4), np.uint32)
+    _check(_lib.load().llcomp_mi_padded_regions_plan(w, h, tab, n, C.byref(pad), src.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return src
 
 
 def filter_code(filter):
@@ -301,9 +384,10 @@ class ViewGroup:
         self.filter = filter
 
 
-def _view_groups(groups, c):
+def _view_groups(groups, c, signed=False):
     """a sequence of ViewGroup (or (views, ow, oh[, d_out]) tuples) -> (ctypes array of llcomp_mi_view_group, n, keep-alive list);
-    everything about their contents is the library's to refuse"""
+    everything about their contents is the library's to refuse.  signed (a padded call): a view's x and y may be negative, and go into
+    the struct as two's complement"""
     groups = list(groups) if groups is not None else []
     arr, keep = (_ViewGroup * max(1, len(groups)))(), []
     for i, gr in enumerate(groups):
@@ -313,7 +397,12 @@ def _view_groups(groups, c):
             gr = ViewGroup(*gr)
         a = np.asarray(gr.views if len(gr.views) else np.zeros((0, 6), np.int64))
         if a.ndim != 2 or a.shape[1] not in (5, 6) or not np.issubdtype(a.dtype, np.integer) or (a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF)):
-            raise LlcompError(BAD_ARGS, f"the views of group {i} must be n x 5 or n x 6 non-negative integers, got shape {a.shape} {a.dtype}")
+            ok = signed and a.ndim == 2 and a.shape[1] in (5, 6) and np.issubdtype(a.dtype, np.integer) and a.max() <= 0x7FFFFFFF \
+                and a[:, 1:3].min() >= -0x80000000 and np.delete(a, (1, 2), axis=1).min() >= 0
+            if not ok:
+                raise LlcompError(BAD_ARGS, f"the views of group {i} must be n x 5 or n x 6 non-negative integers, got shape {a.shape} {a.dtype}")
+            a = a.astype(np.int64)
+            a[:, 1:3] &= 0xFFFFFFFF
         n = a.shape[0]
         if a.shape[1] == 5:
             a = np.concatenate([a, np.zeros((n, 1), a.dtype)], axis=1)
@@ -949,17 +1038,26 @@ class Codec:
         _check(self._L.llcomp_mi_codec_decode_regions_host(self._h, ptrs, lens, tab, rw, rh, d_px, d_status, stream))
 
     def decode_resized_regions(self, d_payload, payload_bytes, d_slice_len, rects, ow, oh, d_px, d_status, flags=None, stream=0, dtype=None,
-                               layout="hwc", scale=False, mean=None, std=None, filter=None):
+                               layout="hwc", scale=False, mean=None, std=None, filter=None, pad_mode=None, fill=None):
         """frame f's rectangle rects[f] = (x, y, rw, rh), resampled to ow x oh (and mirrored where flags[f] & 1) -> d_px
         [frames][oh][ow][c] (llcomp_mi_codec_decode_resized_regions); rects and flags are read during the call.  filter: PIL's
         "bilinear" (the default), "box", "hamming", "bicubic", "lanczos", or "nearest" for label images -- a name or FILTER_* code for
         every frame, or a sequence of one per frame (a batch may mix them); it is OR-ed into bits 4-6 of the flags.  dtype ("float32",
         "float16", "bfloat16", "uint8" or the numpy / torch type), layout ("hwc" or "chw": [frames][c][oh][ow]), scale (divide by 255)
         and mean / std (c values) give the output as a model takes it (llcomp_mi_codec_decode_resized_regions_ex; output_table
-        states the rule); d_px must be aligned to the element size."""
-        tab, _ = _rects_table(rects, self.frames)
+        states the rule); d_px must be aligned to the element size.  pad_mode ("constant", "edge", "reflect", "symmetric" or a PAD_* code)
+        and fill (one value or c values, "constant" only; alone it means "constant"): rectangles may leave the image, x and y may be
+        negative, and frame f is np.pad(frame, pad_mode) cut at its rectangle (llcomp_mi_codec_decode_padded_regions) -- only the part
+        inside the image is decoded.  Without them a rectangle outside the image stays BAD_ARGS."""
         fl = _flags_table(flags, self.frames, filter)
         fmt, _, _keep = _output_format(self.c, dtype, layout, scale, mean, std)
+        if pad_mode is not None or fill is not None:
+            tab, _ = _signed_rects_table(rects, self.frames)
+            pad, _keep_pad = _pad(self.c, pad_mode, fill)
+            _check(self._L.llcomp_mi_codec_decode_padded_regions(self._h, d_payload, payload_bytes, d_slice_len, tab, fl, ow, oh, C.byref(pad),
+                                                                  C.byref(fmt) if fmt is not None else None, d_px, d_status, stream))
+            return
+        tab, _ = _rects_table(rects, self.frames)
         if fmt is None:
             _check(self._L.llcomp_mi_codec_decode_resized_regions(self._h, d_payload, payload_bytes, d_slice_len, tab, fl, ow, oh, d_px, d_status,
                                                                    stream))
@@ -968,32 +1066,46 @@ class Codec:
                                                                       d_px, d_status, stream))
 
     def decode_resized_regions_host(self, containers, rects, ow, oh, d_px, d_status, flags=None, stream=0, dtype=None, layout="hwc", scale=False,
-                                    mean=None, std=None, filter=None):
+                                    mean=None, std=None, filter=None, pad_mode=None, fill=None):
         """decode_resized_regions of host containers (llcomp_mi_codec_decode_resized_regions_host(_ex)): only the windows' bytes cross
-        PCIe; the containers, rects and flags are read during the call only; filter as decode_resized_regions takes it"""
+        PCIe; the containers, rects and flags are read during the call only; filter, pad_mode and fill as decode_resized_regions takes
+        them (llcomp_mi_codec_decode_padded_regions_host: only the windows of the source rectangles cross)"""
         ptrs, lens, keep = _containers(containers)
         if len(keep) != self.frames:
             raise LlcompError(BAD_ARGS, f"the codec takes {self.frames} containers, got {len(keep)}")
-        tab, _ = _rects_table(rects, self.frames)
         fl = _flags_table(flags, self.frames, filter)
         fmt, _, _keep = _output_format(self.c, dtype, layout, scale, mean, std)
+        if pad_mode is not None or fill is not None:
+            tab, _ = _signed_rects_table(rects, self.frames)
+            pad, _keep_pad = _pad(self.c, pad_mode, fill)
+            _check(self._L.llcomp_mi_codec_decode_padded_regions_host(self._h, ptrs, lens, tab, fl, ow, oh, C.byref(pad),
+                                                                       C.byref(fmt) if fmt is not None else None, d_px, d_status, stream))
+            return
+        tab, _ = _rects_table(rects, self.frames)
         if fmt is None:
             _check(self._L.llcomp_mi_codec_decode_resized_regions_host(self._h, ptrs, lens, tab, fl, ow, oh, d_px, d_status, stream))
         else:
             _check(self._L.llcomp_mi_codec_decode_resized_regions_host_ex(self._h, ptrs, lens, tab, fl, ow, oh, C.byref(fmt), d_px, d_status,
                                                                            stream))
 
-    def decode_views(self, d_payload, payload_bytes, d_slice_len, groups, d_status, stream=0):
+    def decode_views(self, d_payload, payload_bytes, d_slice_len, groups, d_status, stream=0, pad_mode=None, fill=None):
         """several views of each frame, each frame decoded once (llcomp_mi_codec_decode_views): groups = ViewGroup objects (or
         (views, ow, oh, d_out) tuples); view v of a group -> d_out[v], byte for byte what decode_resized_regions writes for that rectangle
         of that frame.  A frame decodes the bounding box of all its views; a frame without a view is not read.  d_payload / d_slice_len
-        are the full batch's (pack_batch)."""
+        are the full batch's (pack_batch).  pad_mode / fill as decode_resized_regions takes them: views may leave the image, a view's x and
+        y may be negative (llcomp_mi_codec_decode_padded_views), and a frame decodes the bounding box of its views' source rectangles."""
+        if pad_mode is not None or fill is not None:
+            arr, n, _keep = _view_groups(groups, self.c, signed=True)
+            pad, _keep_pad = _pad(self.c, pad_mode, fill)
+            _check(self._L.llcomp_mi_codec_decode_padded_views(self._h, d_payload, payload_bytes, d_slice_len, arr, n, C.byref(pad), d_status, stream))
+            return
         arr, n, _keep = _view_groups(groups, self.c)
         _check(self._L.llcomp_mi_codec_decode_views(self._h, d_payload, payload_bytes, d_slice_len, arr, n, d_status, stream))
 
-    def decode_views_host(self, containers, groups, d_status, stream=0):
+    def decode_views_host(self, containers, groups, d_status, stream=0, pad_mode=None, fill=None):
         """decode_views of host containers (llcomp_mi_codec_decode_views_host): only the union windows' bytes cross PCIe; the container
-        of a frame without a view may be None and is never read"""
+        of a frame without a view may be None and is never read; pad_mode / fill as decode_views takes them
+        (llcomp_mi_codec_decode_padded_views_host)"""
         conts = list(containers)
         if len(conts) != self.frames:
             raise LlcompError(BAD_ARGS, f"the codec takes {self.frames} containers, got {len(conts)}")
@@ -1001,12 +1113,22 @@ class Codec:
         for f, d in enumerate(conts):
             if d is None:
                 ptrs[f], lens[f] = None, 0
+        if pad_mode is not None or fill is not None:
+            arr, n, _keep = _view_groups(groups, self.c, signed=True)
+            pad, _keep_pad = _pad(self.c, pad_mode, fill)
+            _check(self._L.llcomp_mi_codec_decode_padded_views_host(self._h, ptrs, lens, arr, n, C.byref(pad), d_status, stream))
+            return
         arr, n, _keep = _view_groups(groups, self.c)
         _check(self._L.llcomp_mi_codec_decode_views_host(self._h, ptrs, lens, arr, n, d_status, stream))
 
     def views_workspace_bytes(self, total_views):
         """.workspace_bytes for calls of up to total_views views (llcomp_mi_codec_views_workspace_bytes): the staged tables grow with them"""
         return self._L.llcomp_mi_codec_views_workspace_bytes(self._h, int(total_views))
+
+    def padded_workspace_bytes(self, total_views=None):
+        """the bound on .allocated_bytes() for padded calls of up to total_views views (default: one per frame, a padded resized call) with
+        outputs no larger than the image (llcomp_mi_codec_padded_workspace_bytes): their staged tables are larger than the unpadded calls'"""
+        return self._L.llcomp_mi_codec_padded_workspace_bytes(self._h, int(self.frames if total_views is None else total_views))
 
     def allocated_bytes(self):
         """device bytes the codec holds right now (llcomp_mi_codec_allocated_bytes; at most .workspace_bytes for outputs up to the image's
@@ -1046,7 +1168,7 @@ class Codec:
                                                | (32 if resized else 0) | (64 if update else 0) | (128 if views else 0)))
 
     COUNTERS = ("dec_cached_waves", "dec_bypassed_waves", "cache_lookups", "cache_misses", "cache_writebacks", "dec_replays", "enc_carry_backs",
-                "generation_wraps", "dec_launches_cached", "dec_launches_plain", "host_staged_bytes")
+                "generation_wraps", "dec_launches_cached", "dec_launches_plain", "host_staged_bytes", "bias_launches")
 
     def counters(self, reset=False):
         """{name: count} -- what the rare and adaptive paths of this codec's kernels did so far (llcomp_mi_codec_get_counters);

@@ -39,6 +39,9 @@ SYMBOLS = [
     "llcomp_mi_replace_slices", "llcomp_mi_replace_slices_into", "llcomp_mi_update_region", "llcomp_mi_update_region_into",
     "llcomp_mi_codec_encode_region", "llcomp_mi_codec_update_region", "llcomp_mi_resize_filter_weights",
     "llcomp_mi_views_plan", "llcomp_mi_codec_decode_views", "llcomp_mi_codec_decode_views_host", "llcomp_mi_codec_views_workspace_bytes",
+    "llcomp_mi_pad_axis", "llcomp_mi_padded_filter_weights", "llcomp_mi_padded_regions_plan", "llcomp_mi_codec_decode_padded_regions",
+    "llcomp_mi_codec_decode_padded_regions_host", "llcomp_mi_codec_decode_padded_views", "llcomp_mi_codec_decode_padded_views_host",
+    "llcomp_mi_codec_padded_workspace_bytes",
 ]
 
 u8p = C.POINTER(C.c_uint8)
@@ -65,6 +68,11 @@ class ViewGroup(C.Structure):
     """llcomp_mi_view_group (include/llcomp_mi.h): 40 bytes, views at 8, fmt at 24, d_out at 32"""
     _fields_ = [("struct_size", C.c_uint32), ("n_views", C.c_uint32), ("views", C.POINTER(View)), ("ow", C.c_uint32), ("oh", C.c_uint32),
                 ("fmt", C.POINTER(OutputFormat)), ("d_out", C.c_void_p)]
+
+
+class Pad(C.Structure):
+    """llcomp_mi_pad (include/llcomp_mi.h): 16 bytes, fill at 8"""
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_uint32), ("fill", u8p)]
 
 
 class Info(C.Structure):
@@ -325,6 +333,27 @@ def load():
         L.llcomp_mi_codec_decode_views_host.argtypes = [C.c_void_p, ptrs, sizes, grp, C.c_uint32, C.c_void_p, C.c_void_p]
         L.llcomp_mi_codec_views_workspace_bytes.restype = C.c_uint64
         L.llcomp_mi_codec_views_workspace_bytes.argtypes = [C.c_void_p, C.c_uint64]
+    if "LLCOMP_MI_LIB" not in os.environ or hasattr(L, "llcomp_mi_pad_axis"):  # crops that leave the image
+        u32p, i32p, ptrs, sizes = C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)
+        grp, fmtp, padp = C.POINTER(ViewGroup), C.POINTER(OutputFormat), C.POINTER(Pad)
+        L.llcomp_mi_pad_axis.restype = C.c_int
+        L.llcomp_mi_pad_axis.argtypes = [C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, u32p, u32p]
+        L.llcomp_mi_padded_filter_weights.restype = C.c_uint32
+        L.llcomp_mi_padded_filter_weights.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, u32p] + [C.c_void_p] * 3
+        L.llcomp_mi_padded_regions_plan.restype = C.c_int
+        L.llcomp_mi_padded_regions_plan.argtypes = [C.c_uint32, C.c_uint32, i32p, C.c_uint32, padp, u32p]
+        L.llcomp_mi_codec_decode_padded_regions.restype = C.c_int
+        L.llcomp_mi_codec_decode_padded_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, i32p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                            padp, fmtp] + [C.c_void_p] * 3
+        L.llcomp_mi_codec_decode_padded_regions_host.restype = C.c_int
+        L.llcomp_mi_codec_decode_padded_regions_host.argtypes = [C.c_void_p, ptrs, sizes, i32p, C.c_void_p, C.c_uint32, C.c_uint32, padp,
+                                                                 fmtp] + [C.c_void_p] * 3
+        L.llcomp_mi_codec_decode_padded_views.restype = C.c_int
+        L.llcomp_mi_codec_decode_padded_views.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, grp, C.c_uint32, padp, C.c_void_p, C.c_void_p]
+        L.llcomp_mi_codec_decode_padded_views_host.restype = C.c_int
+        L.llcomp_mi_codec_decode_padded_views_host.argtypes = [C.c_void_p, ptrs, sizes, grp, C.c_uint32, padp, C.c_void_p, C.c_void_p]
+        L.llcomp_mi_codec_padded_workspace_bytes.restype = C.c_uint64
+        L.llcomp_mi_codec_padded_workspace_bytes.argtypes = [C.c_void_p, C.c_uint64]
     if "LLCOMP_MI_LIB" not in os.environ and L.llcomp_mi_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.llcomp_mi_abi_version()}, this binding was written for {ABI_VERSION}: rebuild the library")
     _lib = L

@@ -468,8 +468,12 @@ int windows_resample(llcomp_mi_codec* k, const WindowsPlan& p, const ResampleTai
         const uint64_t view_bytes = uint64_t(vg.oh) * vg.ow * g.c * vg.out.esize;
         for (uint32_t at = 0; at < vg.n; at += vg.chunk) {
             const uint32_t cnt = std::min(vg.chunk, vg.n - at);
+            // (a padded call with a constant fill other than 0: the bias forms for a chunk that has an entry with a bias, and only for it)
+            const std::vector<uint8_t>& biased = tail.block.biased;
+            const bool bias = !biased.empty() && std::any_of(biased.begin() + vg.first + at, biased.begin() + vg.first + at + cnt, [](uint8_t b) { return b != 0; });
+            if (bias) ++k->host_counters[LLCOMP_MI_CTR_BIAS_LAUNCHES];
             HIP_TRY(launch_resize_out(k->d_box, k->d_mid, static_cast<uint8_t*>(vg.d_out) + at * view_bytes, d_rs + vg.first + at, d_w,
-                                      d_block + tail.block.tables_at() + vg.table_at, vg.out, cnt, g.c, p.wmax, p.hmax, vg.mh, vg.ow, vg.oh, s));
+                                      d_block + tail.block.tables_at() + vg.table_at, vg.out, cnt, g.c, p.wmax, p.hmax, vg.mh, vg.ow, vg.oh, s, bias));
         }
     }
     return LLCOMP_MI_OK;
@@ -1218,6 +1222,66 @@ int llcomp_mi_codec_decode_views_host(llcomp_mi_codec* k, const uint8_t* const* 
     if (!gather_matches(p, gp)) return LLCOMP_MI_HIP_ERROR;
     return decode_windows(k, p, &p.tail, views_tables_bound(k->g, p.u.total_views), WindowsSource{nullptr, 0, nullptr, data, &gp}, nullptr, d_status,
                           stream);
+}
+
+// The padded calls: the plans of the resized and the views decode on the SOURCE rectangles (windows_plan.hpp: padded_setup,
+// padded_views_setup), driven as they are; the gather of a host source is the unpadded call's over the source rectangles.
+int llcomp_mi_codec_decode_padded_regions(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                          const int32_t* rects, const uint8_t* flags, uint32_t ow, uint32_t oh, const llcomp_mi_pad* pad,
+                                          const llcomp_mi_output_format* fmt, void* d_px, void* d_status, void* stream) {
+    if (!k || !d_payload || !d_slice_len || !d_px || !d_status || !rects) return LLCOMP_MI_BAD_ARGS;
+    if (misaligned(d_slice_len, 4) || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
+    ResizedPlan p;
+    std::vector<uint32_t> src;
+    if (int rc = padded_setup(k->g, k->tune, rects, flags, ow, oh, pad, fmt, d_px, p, src)) return rc;
+    return decode_windows(k, p, &p.tail, padded_tables_bound(k->g, k->g.frames), WindowsSource{d_payload, payload_bytes, d_slice_len, nullptr, nullptr},
+                          nullptr, d_status, stream);
+}
+
+int llcomp_mi_codec_decode_padded_regions_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens, const int32_t* rects,
+                                               const uint8_t* flags, uint32_t ow, uint32_t oh, const llcomp_mi_pad* pad,
+                                               const llcomp_mi_output_format* fmt, void* d_px, void* d_status, void* stream) {
+    if (!k || !data || !lens || !d_px || !d_status || !rects || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
+    ResizedPlan p;
+    std::vector<uint32_t> src;  // the source rectangles: what the gather is planned over
+    if (int rc = padded_setup(k->g, k->tune, rects, flags, ow, oh, pad, fmt, d_px, p, src)) return rc;
+    RegionsGather gp;
+    if (int rc = regions_gather_plan_sized(data, lens, k->g.frames, src.data(), p.wmax, p.hmax, gp)) return rc;
+    if (!same_shape(k->g, gp.g)) return LLCOMP_MI_BAD_ARGS;
+    if (!gather_matches(p, gp)) return LLCOMP_MI_HIP_ERROR;
+    return decode_windows(k, p, &p.tail, padded_tables_bound(k->g, k->g.frames), WindowsSource{nullptr, 0, nullptr, data, &gp}, nullptr, d_status,
+                          stream);
+}
+
+int llcomp_mi_codec_decode_padded_views(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                        const llcomp_mi_view_group* groups, uint32_t n_groups, const llcomp_mi_pad* pad, void* d_status,
+                                        void* stream) {
+    if (!k || !d_payload || !d_slice_len || !d_status) return LLCOMP_MI_BAD_ARGS;
+    if (misaligned(d_slice_len, 4) || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
+    ViewsPlan p;
+    if (int rc = padded_views_setup(k->g, k->tune, groups, n_groups, pad, p)) return rc;
+    return decode_windows(k, p, &p.tail, padded_tables_bound(k->g, p.u.total_views), WindowsSource{d_payload, payload_bytes, d_slice_len, nullptr, nullptr},
+                          nullptr, d_status, stream);
+}
+
+int llcomp_mi_codec_decode_padded_views_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens,
+                                             const llcomp_mi_view_group* groups, uint32_t n_groups, const llcomp_mi_pad* pad, void* d_status,
+                                             void* stream) {
+    if (!k || !data || !lens || !d_status || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
+    ViewsPlan p;
+    if (int rc = padded_views_setup(k->g, k->tune, groups, n_groups, pad, p)) return rc;
+    RegionsGather gp;
+    if (int rc = regions_gather_plan_sized(data, lens, k->g.frames, p.u.rects.data(), p.wmax, p.hmax, gp, p.u.used.data(), uint32_t(p.u.used.size())))
+        return rc;
+    if (!same_shape(k->g, gp.g)) return LLCOMP_MI_BAD_ARGS;
+    if (!gather_matches(p, gp)) return LLCOMP_MI_HIP_ERROR;
+    return decode_windows(k, p, &p.tail, padded_tables_bound(k->g, p.u.total_views), WindowsSource{nullptr, 0, nullptr, data, &gp}, nullptr,
+                          d_status, stream);
+}
+
+uint64_t llcomp_mi_codec_padded_workspace_bytes(const llcomp_mi_codec* k, uint64_t total_views) {
+    if (!k) return 0;
+    return llcomp_mi_codec_views_workspace_bytes(k, total_views) + std::max<uint64_t>(total_views, k->g.frames) * padded_term(k->g) + 4 * uint64_t(k->g.c);
 }
 
 uint64_t llcomp_mi_codec_views_workspace_bytes(const llcomp_mi_codec* k, uint64_t total_views) {

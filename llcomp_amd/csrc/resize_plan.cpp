@@ -131,6 +131,163 @@ bool resize_frame_weights(uint32_t filter, uint32_t rw, uint32_t rh, uint32_t ow
     return e.kx && e.ky;
 }
 
+// ---- rectangles that leave the image ------------------------------------------------------------------------------------------------
+
+// The index map of a padded index t (outside [0, n)) for the modes that have one; numpy's np.pad modes of the same names.
+static int64_t pad_index(uint32_t mode, int64_t n, int64_t t) {
+    switch (mode) {
+        case LLCOMP_MI_PAD_EDGE: return t < 0 ? 0 : n - 1;
+        case LLCOMP_MI_PAD_REFLECT: return t < 0 ? -t : 2 * (n - 1) - t;
+        default: return t < 0 ? -t - 1 : 2 * n - 1 - t;  // SYMMETRIC
+    }
+}
+
+bool pad_axis(uint32_t mode, uint32_t n, int32_t x, uint32_t r, uint32_t& s0, uint32_t& s_len) {
+    if (mode > LLCOMP_MI_PAD_SYMMETRIC || !n || !r) return false;
+    const int64_t N = n, X = x, end = X + int64_t(r);
+    if (X >= N || end <= 0) return false;  // no image pixel
+    const int64_t p = std::max<int64_t>(-X, 0), e = std::max<int64_t>(end - N, 0);
+    if (std::max(p, e) > (mode == LLCOMP_MI_PAD_REFLECT ? N - 1 : N)) return false;
+    int64_t a = std::max<int64_t>(X, 0), b = std::min(end, N);  // the part inside; the padded indices map next to it or into it
+    if (mode == LLCOMP_MI_PAD_REFLECT) {
+        if (p) b = std::max(b, p + 1);      // t = -1 .. -p -> 1 .. p
+        if (e) a = std::min(a, N - 1 - e);  // t = n .. n + e - 1 -> n - 2 .. n - 1 - e
+    } else if (mode == LLCOMP_MI_PAD_SYMMETRIC) {
+        if (p) b = std::max(b, p);      // -> 0 .. p - 1
+        if (e) a = std::min(a, N - e);  // -> n - 1 .. n - e
+    }
+    s0 = uint32_t(a);
+    s_len = uint32_t(b - a);
+    return true;
+}
+
+bool padded_axis(uint32_t filter, uint32_t mode, uint32_t n, int32_t x, uint32_t r, uint32_t out_len, PaddedAxis& ax) {
+    ax = PaddedAxis{};
+    if (!pad_axis(mode, n, x, r, ax.s0, ax.s_len) || !resize_axis_ok(filter, r, out_len)) return false;
+    thread_local std::vector<uint32_t> lo;  // (scratch, reused from call to call)
+    thread_local std::vector<int32_t> q, run;
+    thread_local std::vector<uint32_t> first, len;
+    uint32_t span = 0;
+    weights_pass(filter, r, out_len, lo, q, span);
+    const int64_t N = n, X = x;
+    const bool inside = X >= 0 && X + int64_t(r) <= N;  // (then nothing folds, and no leading zero is trimmed: the unpadded tables)
+    // every output's folded run, in place over its taps: m is 1-Lipschitz, so the sources of `span` consecutive taps span at most `span`
+    run.assign(size_t(out_len) * span, 0);
+    first.assign(out_len, 0);
+    len.assign(out_len, 0);
+    ax.bias.assign(out_len, 0);
+    for (uint32_t i = 0; i < out_len; ++i) {
+        const int32_t* qi = q.data() + size_t(i) * span;
+        int64_t smin = INT64_MAX, smax = -1;
+        int64_t src[2 * kResizeMaxDown + 4];
+        for (uint32_t j = 0; j < span; ++j) {
+            src[j] = -1;
+            if (!qi[j]) continue;
+            const int64_t t = X + int64_t(lo[i]) + j;
+            if (t >= 0 && t < N)
+                src[j] = t;
+            else if (mode == LLCOMP_MI_PAD_CONSTANT)
+                ax.bias[i] += qi[j];
+            else
+                src[j] = pad_index(mode, N, t);
+            if (src[j] >= 0) {
+                smin = std::min(smin, src[j]);
+                smax = std::max(smax, src[j]);
+            }
+        }
+        if (ax.bias[i]) ax.any_bias = true;
+        if (smax < 0) continue;  // (every tap outside, or no weight at all: a run of no taps at 0)
+        if (inside) smin = X + int64_t(lo[i]);
+        int32_t* ri = run.data() + size_t(i) * span;
+        for (uint32_t j = 0; j < span; ++j)
+            if (src[j] >= 0) ri[src[j] - smin] += qi[j];
+        uint32_t a = 0, b = uint32_t(smax - smin + 1);
+        while (b > 0 && !ri[b - 1]) --b;
+        if (!inside)
+            while (a < b && !ri[a]) ++a;
+        first[i] = uint32_t(smin - int64_t(ax.s0)) + a;
+        len[i] = b - a;
+        if (a) std::memmove(ri, ri + a, size_t(b - a) * sizeof(int32_t));
+        if (b == a) first[i] = 0;
+    }
+    ax.k = 1;
+    for (uint32_t i = 0; i < out_len; ++i) ax.k = std::max(ax.k, len[i]);
+    ax.lo.assign(out_len, 0);
+    ax.q.assign(size_t(out_len) * ax.k, 0);
+    for (uint32_t i = 0; i < out_len; ++i) {
+        const uint32_t a = std::min(first[i], ax.s_len - ax.k), s = first[i] - a;  // (k <= s_len: every run lies inside the interval)
+        ax.lo[i] = int32_t(a);
+        for (uint32_t j = 0; j < len[i]; ++j) ax.q[size_t(i) * ax.k + s + j] = run[size_t(i) * span + j];
+    }
+    return true;
+}
+
+// One padded axis for the kernels (axis_weights for it): lo[out], then the folded weights tap-major.
+static const PaddedSeen::Axis* padded_axis_weights(uint32_t filter, uint32_t mode, uint32_t n, int32_t x, uint32_t r, uint32_t out_len,
+                                                   std::vector<int32_t>& w, PaddedSeen& seen) {
+    for (const PaddedSeen::Axis& a : seen.axes)
+        if (a.filter == filter && a.mode == mode && a.n == n && a.x == x && a.r == r && a.out == out_len) return &a;
+    PaddedSeen::Axis rec{filter, mode, n, r, out_len, x, 0, 0, 0, 0, 0, false};
+    if (x >= 0 && uint64_t(x) + r <= n) {  // inside the image: the unpadded axis, shared with every other rectangle of this size
+        rec.k = axis_weights(filter, r, out_len, w, rec.at, seen.plain);
+        if (!rec.k) return nullptr;
+        rec.s0 = uint32_t(x);
+        rec.s_len = r;
+        rec.bias_at = uint32_t(seen.bias.size());
+        seen.bias.resize(seen.bias.size() + out_len, 0);
+    } else {
+        thread_local PaddedAxis ax;
+        if (!padded_axis(filter, mode, n, x, r, out_len, ax)) return nullptr;
+        rec.k = ax.k;
+        rec.s0 = ax.s0;
+        rec.s_len = ax.s_len;
+        rec.any_bias = ax.any_bias;
+        rec.at = uint32_t(w.size());
+        w.resize(w.size() + size_t(out_len) * (ax.k + 1), 0);
+        int32_t* l = w.data() + rec.at;
+        int32_t* t = l + out_len;
+        for (uint32_t i = 0; i < out_len; ++i) {
+            l[i] = ax.lo[i];
+            for (uint32_t j = 0; j < ax.k; ++j) t[size_t(j) * out_len + i] = ax.q[size_t(i) * ax.k + j];
+        }
+        rec.bias_at = uint32_t(seen.bias.size());
+        seen.bias.insert(seen.bias.end(), ax.bias.begin(), ax.bias.end());
+    }
+    seen.axes.push_back(rec);
+    return &seen.axes.back();
+}
+
+bool padded_frame_weights(uint32_t filter, uint32_t mode, uint32_t w, uint32_t h, const int32_t* rect, uint32_t ow, uint32_t oh, bool with_bias,
+                          ResizeFrame& e, uint32_t src[4], bool* biased, std::vector<int32_t>& wts, PaddedSeen& seen) {
+    if (rect[2] <= 0 || rect[3] <= 0) return false;
+    const PaddedSeen::Axis* ax = padded_axis_weights(filter, mode, w, rect[0], uint32_t(rect[2]), ow, wts, seen);
+    if (!ax) return false;
+    const PaddedSeen::Axis hx = *ax;  // (a copy: the next call may move the records)
+    ax = padded_axis_weights(filter, mode, h, rect[1], uint32_t(rect[3]), oh, wts, seen);
+    if (!ax) return false;
+    const PaddedSeen::Axis vy = *ax;
+    src[0] = hx.s0;
+    src[1] = vy.s0;
+    e.rw = src[2] = hx.s_len;
+    e.rh = src[3] = vy.s_len;
+    e.kx = hx.k;
+    e.ky = vy.k;
+    e.hx = hx.at;
+    e.vy = vy.at;
+    if (biased) *biased = hx.any_bias || vy.any_bias;
+    if (!with_bias) return true;
+    for (const PaddedSeen::Pair& p : seen.pairs)
+        if (p.hx == hx.at && p.vy == vy.at) {
+            e.pad[0] = p.at;
+            return true;
+        }
+    e.pad[0] = uint32_t(wts.size());
+    wts.insert(wts.end(), seen.bias.begin() + hx.bias_at, seen.bias.begin() + hx.bias_at + ow);
+    wts.insert(wts.end(), seen.bias.begin() + vy.bias_at, seen.bias.begin() + vy.bias_at + oh);
+    seen.pairs.push_back(PaddedSeen::Pair{hx.at, vy.at, e.pad[0]});
+    return true;
+}
+
 int check_output_format(const llcomp_mi_output_format* fmt, uint32_t c, OutFormat& o) {
     o = OutFormat{};
     if (!fmt) return LLCOMP_MI_OK;

@@ -78,6 +78,11 @@ uint64_t views_tables_bound(const Geometry& g, uint64_t total_views) {
     return resized_tables_bound(g) + (total_views > g.frames ? (total_views - g.frames) * view_term(g) : 0);
 }
 
+uint64_t padded_term(const Geometry& g) { return 4 * 13 * (uint64_t(g.w) + g.h); }
+uint64_t padded_tables_bound(const Geometry& g, uint64_t total_views) {
+    return views_tables_bound(g, total_views) + std::max<uint64_t>(total_views, g.frames) * padded_term(g) + 4 * uint64_t(g.c);
+}
+
 void ResampleBlock::put(uint8_t* at) const {
     std::memcpy(at, rs.data(), rs.size() * sizeof(ResizeFrame));
     std::memcpy(at + w_at(), w.data(), 4 * w.size());
@@ -183,4 +188,196 @@ int views_setup(const Geometry& g, const Tuning& tune, const llcomp_mi_view_grou
     return LLCOMP_MI_OK;
 }
 
+int check_pad(const llcomp_mi_pad* pad) {
+    return pad && pad->struct_size >= sizeof(llcomp_mi_pad) && pad->mode <= LLCOMP_MI_PAD_SYMMETRIC ? LLCOMP_MI_OK : LLCOMP_MI_BAD_ARGS;
+}
+// whether the call needs the bias arrays: CONSTANT with a fill other than 0
+static bool pad_has_fill(const llcomp_mi_pad& pad, uint32_t c) {
+    if (pad.mode != LLCOMP_MI_PAD_CONSTANT || !pad.fill) return false;
+    for (uint32_t ch = 0; ch < c; ++ch)
+        if (pad.fill[ch]) return true;
+    return false;
+}
+// the call's fill values behind the weights, and their offset into every entry
+static void put_fill(const llcomp_mi_pad& pad, uint32_t c, ResampleBlock& blk) {
+    const uint32_t at = uint32_t(blk.w.size());
+    for (uint32_t ch = 0; ch < c; ++ch) blk.w.push_back(int32_t(pad.fill[ch]));
+    for (ResizeFrame& z : blk.rs) z.pad[1] = at;
+}
+
+int padded_setup(const Geometry& g, const Tuning& tune, const int32_t* rects, const uint8_t* flags, uint32_t ow, uint32_t oh,
+                 const llcomp_mi_pad* pad, const llcomp_mi_output_format* fmt, void* d_out, ResizedPlan& p, std::vector<uint32_t>& src) {
+    ResampleGroup vg;
+    if (int rc = check_output_format(fmt, g.c, vg.out)) return rc;
+    if (reinterpret_cast<uintptr_t>(d_out) & (vg.out.esize - 1)) return LLCOMP_MI_BAD_ARGS;
+    if (!rects || !ow || !oh || g.frames > 65535) return LLCOMP_MI_BAD_ARGS;
+    if (int rc = check_pad(pad)) return rc;
+    src.assign(4 * size_t(g.frames), 0);
+    for (uint32_t f = 0; f < g.frames; ++f) {
+        const int32_t* r = rects + 4 * size_t(f);
+        const uint32_t filter = flags ? LLCOMP_MI_FLAG_FILTER_OF(flags[f]) : 0u;
+        uint32_t* s = src.data() + 4 * size_t(f);
+        if (r[2] < 1 || r[3] < 1 || !pad_axis(pad->mode, g.w, r[0], uint32_t(r[2]), s[0], s[2]) ||
+            !pad_axis(pad->mode, g.h, r[1], uint32_t(r[3]), s[1], s[3]))
+            return LLCOMP_MI_BAD_ARGS;
+        if (!resize_axis_ok(filter, uint32_t(r[2]), ow) || !resize_axis_ok(filter, uint32_t(r[3]), oh)) return LLCOMP_MI_BAD_ARGS;
+        p.wmax = std::max(p.wmax, s[2]);
+        p.hmax = std::max(p.hmax, s[3]);
+    }
+    p.tab.resize(g.frames);
+    if (int rc = regions_setup_sized(g, tune, src.data(), p.wmax, p.hmax, p.tab.data(), p.classes, p.n_classes)) return rc;
+    const bool with_bias = pad_has_fill(*pad, g.c);
+    ResampleBlock& blk = p.tail.block;
+    blk.rs.assign(g.frames, ResizeFrame{});
+    if (with_bias) blk.biased.assign(g.frames, 0);
+    PaddedSeen seen;  // (axes already computed in this call)
+    for (const RegionsFrame& e : p.tab) {
+        const uint32_t* s = src.data() + 4 * size_t(e.frame);
+        ResizeFrame& z = blk.rs[e.frame];
+        z.ox = s[0] - e.wx0 * g.tile_w - e.cx0;
+        z.oy = s[1] - e.wy0 * g.tile_h - e.cy0;
+        z.flags = flags ? flags[e.frame] & (1u | LLCOMP_MI_FLAG_FILTER_MASK) : 0u;
+        z.box = e.out;  // (the frame's own box)
+        uint32_t got[4];
+        bool biased = false;
+        if (!padded_frame_weights(LLCOMP_MI_FLAG_FILTER_OF(z.flags), pad->mode, g.w, g.h, rects + 4 * size_t(e.frame), ow, oh, with_bias, z, got,
+                                  &biased, blk.w, seen))
+            return LLCOMP_MI_BAD_ARGS;
+        if (with_bias) blk.biased[e.frame] = biased;
+        // (the weights are those of the source rectangle the windows were planned for, and the box holds it by construction)
+        if (std::memcmp(got, s, sizeof got) != 0 || uint64_t(z.ox) + z.rw > p.wmax || uint64_t(z.oy) + z.rh > p.hmax) return LLCOMP_MI_HIP_ERROR;
+    }
+    if (with_bias) put_fill(*pad, g.c, blk);
+    vg.n = vg.chunk = g.frames;
+    vg.ow = ow;
+    vg.oh = oh;
+    vg.mh = p.hmax;
+    vg.d_out = d_out;
+    vg.table_at = blk.add_table(fmt, g.c, vg.out);
+    p.tail.groups.assign(1, vg);
+    p.tail.box_bytes = uint64_t(g.frames) * p.wmax * p.hmax * g.c;
+    p.tail.mid_bytes = uint64_t(g.frames) * p.hmax * ow * g.c;
+    return LLCOMP_MI_OK;
+}
+
+int padded_views_setup(const Geometry& g, const Tuning& tune, const llcomp_mi_view_group* groups, uint32_t n_groups, const llcomp_mi_pad* pad,
+                       ViewsPlan& p) {
+    if (!groups || !n_groups || groups->struct_size != sizeof(llcomp_mi_view_group)) return LLCOMP_MI_BAD_ARGS;
+    if (int rc = check_pad(pad)) return rc;
+    // the groups again with every view's source rectangle in place of its rectangle: what views_union and the windows see
+    std::vector<llcomp_mi_view_group> sgroups(n_groups);
+    std::vector<std::vector<llcomp_mi_view>> sviews(n_groups);
+    for (uint32_t gi = 0; gi < n_groups; ++gi) {
+        const llcomp_mi_view_group& gr = *view_group_at(groups, gi);
+        if (gr.struct_size != sizeof(llcomp_mi_view_group) || !gr.n_views || gr.n_views > 65535 || !gr.views || !gr.ow || !gr.oh)
+            return LLCOMP_MI_BAD_ARGS;
+        sviews[gi].assign(gr.views, gr.views + gr.n_views);
+        for (llcomp_mi_view& v : sviews[gi]) {
+            const uint32_t filter = LLCOMP_MI_FLAG_FILTER_OF(v.flags & 0xFFu);
+            const uint32_t rw = v.rw, rh = v.rh;
+            if (!rw || !rh || rw > 0x7FFFFFFFu || rh > 0x7FFFFFFFu || !resize_axis_ok(filter, rw, gr.ow) || !resize_axis_ok(filter, rh, gr.oh))
+                return LLCOMP_MI_BAD_ARGS;
+            if (!pad_axis(pad->mode, g.w, int32_t(v.x), rw, v.x, v.rw) || !pad_axis(pad->mode, g.h, int32_t(v.y), rh, v.y, v.rh))
+                return LLCOMP_MI_BAD_ARGS;
+        }
+        sgroups[gi] = gr;
+        sgroups[gi].views = sviews[gi].data();
+    }
+    if (int rc = views_union(g.w, g.h, g.frames, sgroups.data(), n_groups, p.u)) return rc;
+    std::vector<ResampleGroup>& out = p.tail.groups;
+    out.resize(n_groups);
+    for (uint32_t gi = 0; gi < n_groups; ++gi) {
+        const llcomp_mi_view_group& gr = sgroups[gi];
+        if (int rc = check_output_format(gr.fmt, g.c, out[gi].out)) return rc;
+        if (!gr.d_out || (reinterpret_cast<uintptr_t>(gr.d_out) & (out[gi].out.esize - 1))) return LLCOMP_MI_BAD_ARGS;
+    }
+    const uint32_t n_used = uint32_t(p.u.used.size());
+    p.wmax = p.u.wmax;
+    p.hmax = p.u.hmax;
+    p.tab.resize(n_used);
+    if (int rc = regions_setup_sized(g, tune, p.u.rects.data(), p.wmax, p.hmax, p.tab.data(), p.classes, p.n_classes, p.u.used.data(), n_used))
+        return rc;
+    std::vector<uint32_t> entry_of(g.frames, 0);  // a used frame's entry of the regions table
+    for (uint32_t i = 0; i < n_used; ++i) entry_of[p.tab[i].frame] = i;
+    const uint64_t samples = uint64_t(g.frames) * g.w * g.h * g.c;
+    const bool with_bias = pad_has_fill(*pad, g.c);
+    ResampleBlock& blk = p.tail.block;
+    PaddedSeen seen;  // (axes already computed in this call)
+    blk.rs.reserve(size_t(p.u.total_views));
+    for (uint32_t gi = 0; gi < n_groups; ++gi) {
+        const llcomp_mi_view_group& gr = *view_group_at(groups, gi);
+        ResampleGroup& vg = out[gi];
+        vg.n = gr.n_views;
+        vg.ow = gr.ow;
+        vg.oh = gr.oh;
+        vg.d_out = gr.d_out;
+        vg.first = uint32_t(blk.rs.size());
+        for (uint32_t i = 0; i < gr.n_views; ++i) {
+            const llcomp_mi_view& v = gr.views[i];
+            const llcomp_mi_view& sv = sviews[gi][i];
+            const RegionsFrame& e = p.tab[entry_of[v.frame]];
+            ResizeFrame z{};
+            z.ox = sv.x - e.wx0 * g.tile_w - e.cx0;  // (the box starts at or before the union's origin, which no source rectangle starts before)
+            z.oy = sv.y - e.wy0 * g.tile_h - e.cy0;
+            z.flags = v.flags & (1u | LLCOMP_MI_FLAG_FILTER_MASK);
+            z.box = e.out;
+            const int32_t rect[4] = {int32_t(v.x), int32_t(v.y), int32_t(v.rw), int32_t(v.rh)};
+            uint32_t got[4];
+            bool biased = false;
+            if (!padded_frame_weights(LLCOMP_MI_FLAG_FILTER_OF(z.flags), pad->mode, g.w, g.h, rect, gr.ow, gr.oh, with_bias, z, got, &biased, blk.w, seen))
+                return LLCOMP_MI_BAD_ARGS;
+            if (e.frame != v.frame || got[0] != sv.x || got[1] != sv.y || got[2] != sv.rw || got[3] != sv.rh || uint64_t(z.ox) + z.rw > p.wmax ||
+                uint64_t(z.oy) + z.rh > p.hmax || z.box >= n_used)
+                return LLCOMP_MI_HIP_ERROR;
+            vg.mh = std::max(vg.mh, z.rh);
+            blk.rs.push_back(z);
+            if (with_bias) blk.biased.push_back(biased);
+        }
+        const uint64_t per_view = uint64_t(vg.mh) * vg.ow * g.c;
+        vg.chunk = uint32_t(std::min<uint64_t>(vg.n, std::max<uint64_t>(samples / per_view, 1)));
+        p.tail.mid_bytes = std::max(p.tail.mid_bytes, vg.chunk * per_view);
+        vg.table_at = blk.add_table(gr.fmt, g.c, vg.out);
+    }
+    if (with_bias) put_fill(*pad, g.c, blk);
+    p.tail.box_bytes = uint64_t(n_used) * p.wmax * p.hmax * g.c;
+    return LLCOMP_MI_OK;
+}
+
 }  // namespace llcomp_mi
+
+extern "C" {
+
+int llcomp_mi_pad_axis(uint32_t mode, uint32_t n, int32_t x, uint32_t r, uint32_t* s0, uint32_t* s_len) {
+    uint32_t a = 0, l = 0;
+    if (!s0 || !s_len || !llcomp_mi::pad_axis(mode, n, x, r, a, l)) return LLCOMP_MI_BAD_ARGS;
+    *s0 = a;
+    *s_len = l;
+    return LLCOMP_MI_OK;
+}
+
+uint32_t llcomp_mi_padded_filter_weights(uint32_t filter, uint32_t mode, uint32_t n, int32_t x, uint32_t r, uint32_t out_len, uint32_t* s0,
+                                         uint32_t* lo, int32_t* q, int32_t* bias) {
+    llcomp_mi::PaddedAxis a;
+    if (!llcomp_mi::padded_axis(filter, mode, n, x, r, out_len, a)) return 0;
+    if (s0) *s0 = a.s0;
+    if (lo) std::memcpy(lo, a.lo.data(), 4 * size_t(out_len));
+    if (q) std::memcpy(q, a.q.data(), 4 * a.q.size());
+    if (bias) std::memcpy(bias, a.bias.data(), 4 * size_t(out_len));
+    return a.k;
+}
+
+int llcomp_mi_padded_regions_plan(uint32_t w, uint32_t h, const int32_t* rects, uint32_t n, const llcomp_mi_pad* pad, uint32_t* src) {
+    if (!rects || !n || !src || llcomp_mi::check_pad(pad)) return LLCOMP_MI_BAD_ARGS;
+    std::vector<uint32_t> s(4 * size_t(n));
+    for (uint32_t f = 0; f < n; ++f) {
+        const int32_t* r = rects + 4 * size_t(f);
+        uint32_t* o = s.data() + 4 * size_t(f);
+        if (r[2] < 1 || r[3] < 1 || !llcomp_mi::pad_axis(pad->mode, w, r[0], uint32_t(r[2]), o[0], o[2]) ||
+            !llcomp_mi::pad_axis(pad->mode, h, r[1], uint32_t(r[3]), o[1], o[3]))
+            return LLCOMP_MI_BAD_ARGS;
+    }
+    std::memcpy(src, s.data(), 4 * s.size());
+    return LLCOMP_MI_OK;
+}
+
+}  // extern "C"

@@ -55,6 +55,11 @@ uint64_t resized_tables_bound(const Geometry& g);
 // entry, its weights at resized_tables_bound's upper bound, and an output table with its alignment.
 uint64_t view_term(const Geometry& g);
 uint64_t views_tables_bound(const Geometry& g, uint64_t total_views);
+// ... of the padded calls (include/llcomp_mi.h: llcomp_mi_codec_padded_workspace_bytes): a rectangle's side r reaches 3 * side, so an axis takes
+// out * (K' + 1) of weights and `out` of bias, K' <= 6 * max(r / out, 1) + 3: at most 6 * max(r, out) + 5 * out <= 23 * side int32 for
+// out <= side, where the unpadded bound has 10 * side; and c int32 of fill values per call.
+uint64_t padded_term(const Geometry& g);  // what an entry adds to view_term / a frame to resized_tables_bound
+uint64_t padded_tables_bound(const Geometry& g, uint64_t total_views);
 
 // The windows of a call, as the driver takes them: the regions table, its classes, and the size every class crops per entry -- the
 // rectangle itself for a plain regions decode, the box (the largest rectangle, or the largest union of a frame's views) otherwise.
@@ -71,6 +76,7 @@ struct ResampleBlock {
     std::vector<ResizeFrame> rs;
     std::vector<int32_t> w;
     std::vector<uint8_t> tables;
+    std::vector<uint8_t> biased;  // host only, a padded call with a constant fill other than 0: per entry, whether any of its bias is not 0
     uint64_t w_at() const { return uint64_t(rs.size()) * sizeof(ResizeFrame); }
     uint64_t tables_at() const { return (w_at() + 4 * uint64_t(w.size()) + 15) & ~15ull; }
     uint64_t bytes() const { return tables.empty() ? w_at() + 4 * uint64_t(w.size()) : tables_at() + tables.size(); }
@@ -129,5 +135,19 @@ struct ViewsPlan : WindowsPlan {
     ResampleTail tail;  // block.rs group by group, view order
 };
 int views_setup(const Geometry& g, const Tuning& tune, const llcomp_mi_view_group* groups, uint32_t n_groups, ViewsPlan& p);
+
+// The two plans for rectangles that may leave the image (include/llcomp_mi.h: llcomp_mi_pad): every rectangle's SOURCE rectangle first
+// (resize_plan.hpp: pad_axis); then regions_setup_sized resp. views_union, unchanged, on the source rectangles -- the windows, classes,
+// boxes and the gather are those of the unpadded call for them -- and a block whose entries describe the source rectangles with folded
+// weights.  A CONSTANT pad with a fill other than 0 also puts every entry's bias pair and the call's fill values (c int32) into the
+// weights and marks the entries with a bias in block.biased: the driver launches the kernels' bias forms for a chunk that has one.
+// rects = {x, y, rw, rh} per frame, signed; a view's x / y are read as int32.  src: the source rectangles, 4 per frame (what the gather
+// of a host source is planned over; a views plan has its unions in p.u).  BAD_ARGS: the unpadded plan's cases, a NULL pad, a
+// struct_size below the struct's, a mode above 3, a size below 1, a pad above the mode's limit, a rectangle with no image pixel on an axis.
+int check_pad(const llcomp_mi_pad* pad);
+int padded_setup(const Geometry& g, const Tuning& tune, const int32_t* rects, const uint8_t* flags, uint32_t ow, uint32_t oh,
+                 const llcomp_mi_pad* pad, const llcomp_mi_output_format* fmt, void* d_out, ResizedPlan& p, std::vector<uint32_t>& src);
+int padded_views_setup(const Geometry& g, const Tuning& tune, const llcomp_mi_view_group* groups, uint32_t n_groups, const llcomp_mi_pad* pad,
+                       ViewsPlan& p);
 
 }  // namespace llcomp_mi
