@@ -387,6 +387,66 @@ uint32_t llcomp_mi_padded_filter_weights(uint32_t filter, uint32_t mode, uint32_
  * BAD_ARGS, with src untouched: n = 0, a NULL rects, pad or src, a struct_size below the struct's, a mode above 3, a size below 1, a
  * rectangle with no image pixel on an axis, a pad above the mode's limit.  Host-only. */
 int llcomp_mi_padded_regions_plan(uint32_t w, uint32_t h, const int32_t* rects, uint32_t n, const llcomp_mi_pad* pad, uint32_t* src);
+/* Views under an affine map (llcomp_mi_codec_decode_warped_views below: RandomRotation, RandomAffine, PIL's Image.rotate and
+ * Image.transform(AFFINE)).  A WARP VIEW is a frame and six numbers m[0..5]; view v of a group is byte for byte what
+ *   PIL.Image.transform((ow, oh), Image.AFFINE, m, resample, fillcolor=fill)
+ * gives on the decoded frame, for resample NEAREST, BILINEAR or BICUBIC.  Channels are independent bands, PIL's modes L, RGB and CMYK:
+ * PIL premultiplies alpha for RGBA and LA under the two smooth filters, this library does not.
+ * THE RULE.  The frame is P[h][w][c] of u8, the output ow x oh, fill[c] the fill.  All arithmetic is IEEE binary64, every operation
+ * rounded by itself -- no fused multiply-add -- in the order written; cl(t, n) = min(max(t, 0), n - 1); every channel by itself.
+ *   BILINEAR and BICUBIC, output pixel (x, y): xs = x + 0.5, ys = y + 0.5; xin = (m0 xs + m1 ys) + m2, yin = (m3 xs + m4 ys) + m5.  If not
+ *     (0 <= xin < w and 0 <= yin < h) the pixel is fill.  Otherwise xin -= 0.5, yin -= 0.5, X = floor(xin), Y = floor(yin), dx = xin - X,
+ *     dy = yin - Y, and
+ *     BILINEAR: row(r) = P[r][cl(X, w)] + (P[r][cl(X + 1, w)] - P[r][cl(X, w)]) dx; v1 = row(cl(Y, h)); v2 = row(Y + 1) if 0 <= Y + 1 < h,
+ *       else v1; v = v1 + (v2 - v1) dy; the output is v truncated toward zero.
+ *     BICUBIC: cub(p0, p1, p2, p3, d) = p1 + d ((-p0 + p2) + d ((((2 (p0 - p1)) + p2) - p3) + d ((((-p0) + p1) - p2) + p3)));
+ *       r0 = cub over columns cl(X - 1 .. X + 2, w) of row cl(Y - 1, h); for k = 1, 2, 3: the same on row Y - 1 + k if 0 <= Y - 1 + k < h,
+ *       else r_k = r_(k-1); v = cub(r0, r1, r2, r3, dy); the output is 0 for v <= 0, 255 for v >= 255, else v truncated.
+ *   NEAREST.  FIX(t) = floor(t * 65536 + 0.5) as int32.
+ *     A pure scale (m1 == 0 and m3 == 0): xo_0 = m2 + m0 * 0.5, xo_(k+1) = xo_k + m0 -- accumulated, not k * m0; xi_k = -1 if xo_k < 0, else
+ *       xo_k truncated; yi likewise from m5 + m4 * 0.5 in steps of m4.
+ *     Any other matrix (PIL's 16.16 path): A0, A1, A3, A4 = FIX(m0), FIX(m1), FIX(m3), FIX(m4); A2 = FIX(m2 + m0 * 0.5 + m1 * 0.5),
+ *       A5 = FIX(m5 + m3 * 0.5 + m4 * 0.5); xi = (A2 + x A0 + y A1) >> 16, yi = (A5 + x A3 + y A4) >> 16, in wrapping int32 with an
+ *       arithmetic shift.
+ *     Both: the output is P[yi][xi] if 0 <= xi < w and 0 <= yi < h, else fill.
+ *   The mirror bit mirrors the view's output horizontally afterwards, and the output table (llcomp_mi_output_table) comes last, as in the other calls.
+ * LIMITS (BAD_ARGS): a coefficient that is not finite; NEAREST: PIL's check_fixed must hold at (p, q) = (0, 0), (ow, 0), (0, oh),
+ * (ow, oh): |p m0 + q m1 + m2| < 32768 and |p m3 + q m4 + m5| < 32768 (outside it PIL accumulates floats along every row, which is not
+ * reproduced); BILINEAR and BICUBIC: |xin|, |yin| < 2^30 at the four corner pixels; a filter other than these three.  A view with no
+ * pixel inside the image is NOT an error: its output is all fill. */
+typedef struct llcomp_mi_warp_view {
+    uint32_t frame; /* the frame of the batch the view is taken from */
+    uint32_t flags; /* the flags byte of the resized calls: bit 0 mirrors the view's output, bits 4-6 hold the filter code; bits above 7 are ignored */
+    double m[6];    /* output pixel -> source coordinate, as PIL's AFFINE data */
+} llcomp_mi_warp_view; /* 56 bytes */
+typedef struct llcomp_mi_warp_group {
+    uint32_t struct_size;               /* = sizeof(llcomp_mi_warp_group); also the stride of an array of groups */
+    uint32_t n_views;                   /* 1 .. 65535 */
+    const llcomp_mi_warp_view* views;   /* HOST memory, read during the call only */
+    uint32_t ow, oh;                    /* the output shape of every view of the group */
+    const llcomp_mi_output_format* fmt; /* NULL = U8 HWC; read during the call only */
+    void* d_out;                        /* device memory, aligned to the format's element size (the plan does not read it) */
+    const uint8_t* fill;                /* c HOST bytes, NULL = zeros; read during the call only */
+} llcomp_mi_warp_group; /* 48 bytes on LP64 */
+/* The rectangle rect = {x, y, rw, rh} of image pixels one view reads: the bounding box of the rule's taps over the output pixels that lie
+ * inside the image; *empty = 1 and four zeros when no output pixel does.  The coordinates are monotone in x and in y under the rule's
+ * rounding, so every output row's inside pixels are one interval with the extremes at its ends (and, with all four corner pixels inside,
+ * at those).  BAD_ARGS, outputs untouched: a NULL pointer, w or h 0, ow or oh 0, and the rule's limits.  Host-only. */
+int llcomp_mi_warp_source_rect(uint32_t w, uint32_t h, const double* m, uint32_t filter, uint32_t ow, uint32_t oh, uint32_t rect[4],
+                               uint32_t* empty);
+/* What a warped views decode of these groups decodes, in the shape of llcomp_mi_views_plan: a frame's union is the bounding box of its
+ * views' source rectangles, the windows and classes are llcomp_mi_views_plan's for those rectangles; a frame whose views are all empty
+ * is unused (four zeros), and with no used frame *n_used = *n_classes = 0.  BAD_ARGS, with every output untouched: no groups, a NULL
+ * groups / n_used / n_classes, a struct_size that is not the struct's, a group with no views, more than 65535 views, a NULL views, ow or
+ * oh 0, a view whose frame is >= frames, and the rule's limits.  Host-only. */
+int llcomp_mi_warp_views_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar, uint32_t frames,
+                              const llcomp_mi_warp_group* groups, uint32_t n_groups, uint32_t* unions, uint32_t* windows, uint32_t* n_used,
+                              uint32_t* n_classes);
+/* The rule above on a host image: src [h][w][c] -> out [oh][ow][c] (no mirror, no output format), fill = c bytes or NULL for zeros.  It
+ * is compiled from the same functions as the GPU's kernel and states the rule as llcomp_mi_resize_filter_weights does for the resized
+ * calls; it is not fast.  BAD_ARGS, out untouched: a NULL src, m or out, a side or c of 0, and the rule's limits.  Host-only. */
+int llcomp_mi_warp_reference(const uint8_t* src, uint32_t w, uint32_t h, uint32_t c, const double* m, uint32_t filter, const uint8_t* fill,
+                             uint32_t ow, uint32_t oh, uint8_t* out);
 uint32_t llcomp_mi_slice_count(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar);
 /* Slice width for one-row slices (tile_h = 1) when `frames` frames are coded per call: the widest slice (64..480 pixels) that
  * still keeps about four wavefronts per SIMD busy.  A call that codes few frames is latency-bound with wide slices; this
@@ -645,6 +705,29 @@ int llcomp_mi_codec_decode_padded_views_host(llcomp_mi_codec* codec, const uint8
  * llcomp_mi_codec_views_workspace_bytes(total_views) + max(total_views, frames) * 52 * (w + h) + 4 * c: every view beyond `frames` adds
  * 48 + 92 * (w + h) + 16 + 1024 * c bytes.  llcomp_mi_codec_workspace_bytes and _views_workspace_bytes keep their values. */
 uint64_t llcomp_mi_codec_padded_workspace_bytes(const llcomp_mi_codec* codec, uint64_t total_views);
+/* llcomp_mi_codec_decode_views(_host) with views that are affine maps (llcomp_mi_warp_view / llcomp_mi_warp_group / the rule above).
+ * Every used frame decodes ONCE, and only the window of the bounding box of the source pixels its views read (llcomp_mi_warp_views_plan):
+ * the windows, classes, boxes, the gather of a host source and the one copy are those of a views call on the source rectangles,
+ * unchanged.  Then one gather kernel per group -- one thread per output pixel, no intermediate buffer -- reads every view from ITS
+ * FRAME's box and writes the group's d_out, dense in view order as the views call does: view v gets byte for byte the rule's output
+ * for its frame, mirrored if bit 0 of its flags is set, through the group's output format.  Each view's entry (its matrix, or the six
+ * fixed-point integers, or the offsets of its xi / yi tables for the pure-scale form, which the host computes), the groups' fill values
+ * and the output tables cross in the call's ONE copy.  d_status and the verdicts are those of the views call on the unions (damage outside
+ * every window, and anywhere in an unused frame, is never seen); with no used frame the call decodes nothing and the status is OK.
+ * BAD_ARGS, before anything is queued or written (d_status untouched): a NULL codec, payload, table or status, a misaligned d_slice_len
+ * or d_status, every case of llcomp_mi_warp_views_plan, a bad output format, a group's d_out NULL or not aligned to its element size.
+ * _host: data[f] / lens[f] for f < frames; only the union windows' bytes cross PCIe (LLCOMP_MI_CTR_HOST_STAGED_BYTES: what
+ * llcomp_mi_codec_decode_views_host stages for the unions); data[f] of an unused frame may be NULL and is never read.  Same bytes and
+ * status as the device form on the same containers packed back to back.  Profile slots and n_decode as for one views decode. */
+int llcomp_mi_codec_decode_warped_views(llcomp_mi_codec* codec, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                        const llcomp_mi_warp_group* groups, uint32_t n_groups, void* d_status, void* stream);
+int llcomp_mi_codec_decode_warped_views_host(llcomp_mi_codec* codec, const uint8_t* const* data, const size_t* lens,
+                                             const llcomp_mi_warp_group* groups, uint32_t n_groups, void* d_status, void* stream);
+/* The bound on llcomp_mi_codec_allocated_bytes for warped views calls of up to total_views views with ow <= w, oh <= h: the boxes stay
+ * within frames * w * h * c and there are no rows in between, but the staged block takes, per view, 64 bytes of entry, 4 * (w + h) of
+ * index tables, c fill bytes and an output table (16 + 1024 * c): llcomp_mi_codec_workspace_bytes + 48 + max(total_views, 1) * (64 +
+ * 4 * (w + h) + c + 16 + 1024 * c). */
+uint64_t llcomp_mi_codec_warp_workspace_bytes(const llcomp_mi_codec* codec, uint64_t total_views);
 /* Stage-A only (context + prediction model), for tests and profiling: d_sym u32[frames*h*w*c],
  * low 16 bits = folded context (0..7925), high 16 bits = folded residual (two's complement). */
 int llcomp_mi_codec_model(llcomp_mi_codec* codec, const void* d_px, void* d_sym, void* stream);

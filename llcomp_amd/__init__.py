@@ -23,6 +23,10 @@ with ctypes and keeps the reference's names and error behaviour:
         Codec.decode_views(_host) / Codec.padded_workspace_bytes  (crops that leave the image -- RandomCrop(padding=...), pad_if_needed, a
         CenterCrop larger than the picture, a translate: rectangles and view origins may be negative, the outside is np.pad's
         "constant" (with fill), "edge", "reflect" or "symmetric", and only the part inside the image is decoded)
+    WarpGroup / warp_source_rect / warp_views_plan / warp_reference / rotate_matrix / Codec.decode_warped_views(_host) /
+        Codec.warp_workspace_bytes  (views under an affine map: a view = (frame, m0..m5[, flags]), byte for byte PIL's
+        Image.transform(AFFINE) -- Image.rotate, RandomRotation, RandomAffine -- under nearest, bilinear or bicubic; a frame decodes
+        the bounding box of the source pixels its views read)
     RawImage(pixels, width, height, channels)     <->  llcomp::RawImage         (/root/reference/llcomp.hpp:454-459)
     EXT = ".llcomp"                               <->  llcomp::ext              (/root/reference/llcomp.hpp:18)
 
@@ -38,6 +42,7 @@ from . import _lib
 from ._lib import Info, Opts, OutputFormat
 from ._lib import Pad as _Pad
 from ._lib import View as _View, ViewGroup as _ViewGroup
+from ._lib import WarpView as _WarpView, WarpGroup as _WarpGroup
 
 EXT = ".llcomp"
 FORMAT_LEGACY, FORMAT_SLICED = 0, 1
@@ -428,6 +433,124 @@ def views_plan(w, h, c, tile_w, tile_h, planar, frames, groups):
     _check(_lib.load().llcomp_mi_views_plan(w, h, c, tile_w, tile_h, int(bool(planar)), frames, arr, n, uni.ctypes.data_as(u32p),
                                             win.ctypes.data_as(u32p), C.byref(used), C.byref(k)))
     return uni, win, used.value, k.value
+
+
+class WarpGroup:
+    """Views under an affine map that share one output (llcomp_mi_warp_group): views = a sequence of (frame, m0, m1, m2, m3, m4, m5) or
+    (frame, m0, ..., m5, flags) -- PIL's AFFINE data: output pixel (x, y) reads the frame at (m0 x + m1 y + m2, m3 x + m4 y + m5), pixel
+    centres at + 0.5 -- the output is [n][oh][ow][c] at device address d_out in the format dtype, layout, scale, mean and std give;
+    filter: "nearest", "bilinear" or "bicubic" (or its FILTER_* code) for every view of the group, or one per view, OR-ed into bits 4-6
+    of the views' flags; fill: c values 0..255 for what lies outside the frame (None: zeros)."""
+
+    def __init__(self, views, ow, oh, d_out=0, dtype=None, layout="hwc", scale=False, mean=None, std=None, filter=None, fill=None):
+        self.views, self.ow, self.oh, self.d_out = views, ow, oh, d_out
+        self.format = dict(dtype=dtype, layout=layout, scale=scale, mean=mean, std=std)
+        self.filter, self.fill = filter, fill
+
+
+def _matrix(m):
+    a = np.asarray(m, dtype=np.float64).reshape(-1)
+    if a.size != 6:
+        raise LlcompError(BAD_ARGS, f"an affine map takes six numbers, got {a.size}")
+    return (C.c_double * 6)(*a.tolist())
+
+
+def _warp_groups(groups, c):
+    """a sequence of WarpGroup (or (views, ow, oh[, d_out]) tuples) -> (ctypes array of llcomp_mi_warp_group, n, keep-alive list);
+    everything about their contents is the library's to refuse"""
+    groups = list(groups) if groups is not None else []
+    arr, keep = (_WarpGroup * max(1, len(groups)))(), []
+    for i, gr in enumerate(groups):
+        if not isinstance(gr, WarpGroup):
+            if not isinstance(gr, (tuple, list)) or not 3 <= len(gr) <= 4:
+                raise LlcompError(BAD_ARGS, f"group {i} must be a WarpGroup or (views, ow, oh, d_out)")
+            gr = WarpGroup(*gr)
+        rows = [list(v) for v in gr.views]
+        n = len(rows)
+        if any(len(r) not in (7, 8) for r in rows):
+            raise LlcompError(BAD_ARGS, f"the views of group {i} must be (frame, m0..m5) or (frame, m0..m5, flags)")
+        frames = [int(r[0]) for r in rows]
+        fl = [int(r[7]) if len(r) == 8 else 0 for r in rows]
+        if any(not 0 <= f <= 0xFFFFFFFF for f in frames) or any(not 0 <= f <= 255 for f in fl):
+            raise LlcompError(BAD_ARGS, f"group {i}: a frame index or flags byte out of range")
+        fl = _flags_table(fl, n, gr.filter) if n else None
+        views = (_WarpView * max(1, n))(*[_WarpView(frames[j], int(fl[j]), _matrix(rows[j][1:7])) for j in range(n)])
+        fmt, _, keep_fmt = _output_format(c, **gr.format)
+        fill = None
+        if gr.fill is not None:
+            f = np.asarray(gr.fill).reshape(-1)
+            if f.size == 1:
+                f = np.full(c, f[0])
+            if f.size != c or f.min() < 0 or f.max() > 255:
+                raise LlcompError(BAD_ARGS, f"fill takes {c} values in 0..255")
+            fill = (C.c_uint8 * c)(*[int(v) for v in f.tolist()])
+        keep += [views, keep_fmt, fill]
+        arr[i] = _WarpGroup(C.sizeof(_WarpGroup), n, C.cast(views, C.POINTER(_WarpView)) if n else None, int(gr.ow), int(gr.oh),
+                            C.pointer(fmt) if fmt is not None else None, gr.d_out or None, C.cast(fill, _lib.u8p) if fill is not None else None)
+    return arr, len(groups), keep
+
+
+def warp_source_rect(w, h, m, filter, ow, oh):
+    """((x, y, rw, rh), empty) of one view under an affine map (llcomp_mi_warp_source_rect, host only): the bounding box of the frame's
+    pixels the rule reads for the output pixels that lie inside the frame; empty = True (and four zeros) when none does.
+    LlcompError(BAD_ARGS) for the rule's limits."""
+    rect, empty = (C.c_uint32 * 4)(), C.c_uint32()
+    _check(_lib.load().llcomp_mi_warp_source_rect(w, h, _matrix(m), filter_code(filter), ow, oh, rect, C.byref(empty)))
+    return tuple(rect), bool(empty.value)
+
+
+def warp_views_plan(w, h, c, tile_w, tile_h, planar, frames, groups):
+    """(unions, windows, n_used, n_classes) of a warped views decode (llcomp_mi_warp_views_plan, host only), in the shape of views_plan:
+    a frame's union is the bounding box of its views' source rectangles; a frame whose views are all empty is unused."""
+    arr, n, _keep = _warp_groups(groups, c)
+    uni, win = np.zeros((frames, 4), np.uint32), np.zeros((frames, 4), np.uint32)
+    used, k = C.c_uint32(), C.c_uint32()
+    u32p = C.POINTER(C.c_uint32)
+    _check(_lib.load().llcomp_mi_warp_views_plan(w, h, c, tile_w, tile_h, int(bool(planar)), frames, arr, n, uni.ctypes.data_as(u32p),
+                                                 win.ctypes.data_as(u32p), C.byref(used), C.byref(k)))
+    return uni, win, used.value, k.value
+
+
+def warp_reference(frame, m, filter="nearest", ow=None, oh=None, fill=None):
+    """The rule of the warped views on a host image (llcomp_mi_warp_reference): frame [h, w] or [h, w, c] uint8 -> [oh, ow(, c)], byte
+    for byte PIL's Image.transform((ow, oh), Image.AFFINE, m, resample, fillcolor=fill) with independent bands.  ow / oh default to the
+    frame's size (Image.rotate's output)."""
+    a = np.ascontiguousarray(frame, dtype=np.uint8)
+    if a.ndim not in (2, 3) or not a.size:
+        raise LlcompError(BAD_ARGS, f"a frame is [h, w] or [h, w, c], got shape {a.shape}")
+    h, w = a.shape[:2]
+    c = a.shape[2] if a.ndim == 3 else 1
+    ow, oh = int(w if ow is None else ow), int(h if oh is None else oh)
+    if not (0 < ow <= 0xFFFFFFFF and 0 < oh <= 0xFFFFFFFF):
+        raise LlcompError(BAD_ARGS, f"no output of {ow} x {oh}")
+    fl = None
+    if fill is not None:
+        f = np.asarray(fill).reshape(-1)
+        f = np.full(c, f[0]) if f.size == 1 else f
+        if f.size != c or f.min() < 0 or f.max() > 255:
+            raise LlcompError(BAD_ARGS, f"fill takes {c} values in 0..255")
+        fl = np.ascontiguousarray(f, dtype=np.uint8)
+    out = np.zeros((oh, ow) + a.shape[2:], np.uint8)
+    _check(_lib.load().llcomp_mi_warp_reference(a.ctypes.data, w, h, c, _matrix(m), filter_code(filter), fl.ctypes.data if fl is not None else None,
+                                                ow, oh, out.ctypes.data))
+    return out
+
+
+def rotate_matrix(w, h, angle, center=None, translate=None):
+    """The six numbers PIL's Image.rotate(angle, expand=False, center=center, translate=translate) builds for a w x h image -- degrees
+    counter clockwise, the entries rounded to 15 decimals as PIL rounds them -- so warp_reference(frame, rotate_matrix(w, h, angle),
+    filter) is Image.rotate for angles that are no multiples of 90 (at those PIL transposes instead)."""
+    import math
+
+    tx, ty = (0, 0) if translate is None else translate
+    cx, cy = (w / 2, h / 2) if center is None else center
+    a = -math.radians(angle % 360.0)
+    m = [round(math.cos(a), 15), round(math.sin(a), 15), 0.0, round(-math.sin(a), 15), round(math.cos(a), 15), 0.0]
+    x, y = -cx - tx, -cy - ty
+    m[2], m[5] = m[0] * x + m[1] * y + m[2], m[3] * x + m[4] * y + m[5]
+    m[2] += cx
+    m[5] += cy
+    return tuple(m)
 
 
 def pack_batch(containers):
@@ -1120,6 +1243,31 @@ class Codec:
             return
         arr, n, _keep = _view_groups(groups, self.c)
         _check(self._L.llcomp_mi_codec_decode_views_host(self._h, ptrs, lens, arr, n, d_status, stream))
+
+    def decode_warped_views(self, d_payload, payload_bytes, d_slice_len, groups, d_status, stream=0):
+        """views under an affine map (llcomp_mi_codec_decode_warped_views): groups = WarpGroup objects; view v of a group -> d_out[v], byte
+        for byte warp_reference of its frame (PIL's Image.transform(AFFINE)), mirrored and formatted as the other calls do.  A frame
+        decodes once, and only the bounding box of the source pixels its views read; a frame without a view is not read."""
+        arr, n, _keep = _warp_groups(groups, self.c)
+        _check(self._L.llcomp_mi_codec_decode_warped_views(self._h, d_payload, payload_bytes, d_slice_len, arr, n, d_status, stream))
+
+    def decode_warped_views_host(self, containers, groups, d_status, stream=0):
+        """decode_warped_views of host containers (llcomp_mi_codec_decode_warped_views_host): only the union windows' bytes cross PCIe;
+        the container of a frame no view reads may be None and is never read"""
+        conts = list(containers)
+        if len(conts) != self.frames:
+            raise LlcompError(BAD_ARGS, f"the codec takes {self.frames} containers, got {len(conts)}")
+        ptrs, lens, keep = _containers([d if d is not None else b"" for d in conts])
+        for f, d in enumerate(conts):
+            if d is None:
+                ptrs[f], lens[f] = None, 0
+        arr, n, _keep = _warp_groups(groups, self.c)
+        _check(self._L.llcomp_mi_codec_decode_warped_views_host(self._h, ptrs, lens, arr, n, d_status, stream))
+
+    def warp_workspace_bytes(self, total_views):
+        """the bound on .allocated_bytes() for warped views calls of up to total_views views with outputs no larger than the image
+        (llcomp_mi_codec_warp_workspace_bytes)"""
+        return self._L.llcomp_mi_codec_warp_workspace_bytes(self._h, int(total_views))
 
     def views_workspace_bytes(self, total_views):
         """.workspace_bytes for calls of up to total_views views (llcomp_mi_codec_views_workspace_bytes): the staged tables grow with them"""

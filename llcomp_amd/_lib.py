@@ -42,6 +42,8 @@ SYMBOLS = [
     "llcomp_mi_pad_axis", "llcomp_mi_padded_filter_weights", "llcomp_mi_padded_regions_plan", "llcomp_mi_codec_decode_padded_regions",
     "llcomp_mi_codec_decode_padded_regions_host", "llcomp_mi_codec_decode_padded_views", "llcomp_mi_codec_decode_padded_views_host",
     "llcomp_mi_codec_padded_workspace_bytes",
+    "llcomp_mi_warp_source_rect", "llcomp_mi_warp_views_plan", "llcomp_mi_warp_reference", "llcomp_mi_codec_decode_warped_views",
+    "llcomp_mi_codec_decode_warped_views_host", "llcomp_mi_codec_warp_workspace_bytes",
 ]
 
 u8p = C.POINTER(C.c_uint8)
@@ -73,6 +75,17 @@ class ViewGroup(C.Structure):
 class Pad(C.Structure):
     """llcomp_mi_pad (include/llcomp_mi.h): 16 bytes, fill at 8"""
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_uint32), ("fill", u8p)]
+
+
+class WarpView(C.Structure):
+    """llcomp_mi_warp_view (include/llcomp_mi.h): 56 bytes, m at 8"""
+    _fields_ = [("frame", C.c_uint32), ("flags", C.c_uint32), ("m", C.c_double * 6)]
+
+
+class WarpGroup(C.Structure):
+    """llcomp_mi_warp_group (include/llcomp_mi.h): 48 bytes, views at 8, fmt at 24, d_out at 32, fill at 40"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_views", C.c_uint32), ("views", C.POINTER(WarpView)), ("ow", C.c_uint32), ("oh", C.c_uint32),
+                ("fmt", C.POINTER(OutputFormat)), ("d_out", C.c_void_p), ("fill", u8p)]
 
 
 class Info(C.Structure):
@@ -354,6 +367,21 @@ def load():
         L.llcomp_mi_codec_decode_padded_views_host.argtypes = [C.c_void_p, ptrs, sizes, grp, C.c_uint32, padp, C.c_void_p, C.c_void_p]
         L.llcomp_mi_codec_padded_workspace_bytes.restype = C.c_uint64
         L.llcomp_mi_codec_padded_workspace_bytes.argtypes = [C.c_void_p, C.c_uint64]
+    if "LLCOMP_MI_LIB" not in os.environ or hasattr(L, "llcomp_mi_warp_source_rect"):  # views under an affine map
+        u32p, f64p, ptrs, sizes, wgrp = C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(WarpGroup)
+        L.llcomp_mi_warp_source_rect.restype = C.c_int
+        L.llcomp_mi_warp_source_rect.argtypes = [C.c_uint32, C.c_uint32, f64p, C.c_uint32, C.c_uint32, C.c_uint32, u32p, u32p]
+        L.llcomp_mi_warp_views_plan.restype = C.c_int
+        L.llcomp_mi_warp_views_plan.argtypes = [C.c_uint32] * 7 + [wgrp, C.c_uint32, u32p, u32p, u32p, u32p]
+        L.llcomp_mi_warp_reference.restype = C.c_int
+        L.llcomp_mi_warp_reference.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, f64p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
+                                               C.c_void_p]
+        L.llcomp_mi_codec_decode_warped_views.restype = C.c_int
+        L.llcomp_mi_codec_decode_warped_views.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, wgrp, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.llcomp_mi_codec_decode_warped_views_host.restype = C.c_int
+        L.llcomp_mi_codec_decode_warped_views_host.argtypes = [C.c_void_p, ptrs, sizes, wgrp, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.llcomp_mi_codec_warp_workspace_bytes.restype = C.c_uint64
+        L.llcomp_mi_codec_warp_workspace_bytes.argtypes = [C.c_void_p, C.c_uint64]
     if "LLCOMP_MI_LIB" not in os.environ and L.llcomp_mi_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.llcomp_mi_abi_version()}, this binding was written for {ABI_VERSION}: rebuild the library")
     _lib = L

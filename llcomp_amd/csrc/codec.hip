@@ -20,6 +20,7 @@
 #include "snapshot.hpp"
 #include "tables.hpp"
 #include "update.hpp"
+#include "warp.hpp"
 #include "windows_plan.hpp"
 
 using namespace llcomp_mi;
@@ -479,6 +480,19 @@ int windows_resample(llcomp_mi_codec* k, const WindowsPlan& p, const ResampleTai
     return LLCOMP_MI_OK;
 }
 
+// The gather of a warp tail, group by group, behind the classes: d_block is the tail's block in HBM.  One launch per group, no
+// intermediate buffer; timed in slot 6 with the crops, like the resample passes.
+int windows_warp(llcomp_mi_codec* k, const WindowsPlan& p, const WarpTail& tail, const uint8_t* d_block, hipStream_t s) {
+    const Geometry& g = k->g;
+    const WarpEntry* d_ws = reinterpret_cast<const WarpEntry*>(d_block);
+    const int32_t* d_tabs = reinterpret_cast<const int32_t*>(d_block + tail.tabs_at());
+    Timed t(k, s, 6);
+    for (const WarpOut& vg : tail.groups)
+        HIP_TRY(launch_warp(k->d_box, d_ws + vg.first, d_tabs, d_block + tail.fills_at() + vg.fill_at, d_block + tail.tables_at() + vg.table_at, vg.out,
+                            vg.d_out, vg.n, g.c, p.wmax, p.hmax, g.w, g.h, vg.ow, vg.oh, s));
+    return LLCOMP_MI_OK;
+}
+
 // Where a windowed decode finds its slices: the full batch in HBM (d_payload, payload_bytes, d_slice_len), or host containers with the
 // gather planned over the plan's windows (data, gather; d_payload is null then).
 struct WindowsSource {
@@ -514,27 +528,30 @@ int regions_plan(const llcomp_mi_codec* k, const uint32_t* xy, uint32_t rw, uint
 // lengths, offsets and payload bytes behind it, so the classes read their slices straight from the copy and no group sums run; and the
 // tail's block at the next multiple of 16.  The copy lands in d_stage, grown up to stage_bound + tables_bound -- but the table alone of
 // a plain call from HBM in d_regions.  Each class takes a state generation of its own; for a source in HBM the full geometry's group
-// offsets are found once, ahead of the first class.
+// offsets are found once, ahead of the first class.  A third kind of tail (`warp`, in place of `tail`; warp_plan.hpp: WarpTail) carries the
+// block of a warped views decode in the same place of the copy and is gathered from the boxes by windows_warp; it has no d_mid.
 int decode_windows(llcomp_mi_codec* k, const WindowsPlan& p, const ResampleTail* tail, uint64_t tables_bound, const WindowsSource& src, void* d_px,
-                   void* d_status, void* stream) {
+                   void* d_status, void* stream, const WarpTail* warp = nullptr) {
     const Geometry& g = k->g;
     const RegionsGather* gp = src.gather;
     const CopyLayout cl(p.tab.size(), gp, tail);
     const StageLayout& lay = cl.stage;
-    const uint64_t rs_at = cl.rs_at, bytes = cl.bytes;
-    const bool table_only = !gp && !tail;
+    const uint64_t rs_at = cl.rs_at, bytes = warp ? rs_at + warp->bytes() : cl.bytes;
+    const bool any_tail = tail || warp;
+    const bool table_only = !gp && !any_tail;
     const uint64_t bound = table_only ? 0 : stage_bound(g) + tables_bound;
     DeviceGuard guard(k->device);
     if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
     if (!gp)
         if (int rc = ensure_region_arrays(k)) return rc;
-    if (int rc = tail ? ensure_regions_ring(k) : ensure_regions_table(k)) return rc;
+    if (int rc = any_tail ? ensure_regions_ring(k) : ensure_regions_table(k)) return rc;
     if (!table_only)
         if (int rc = ensure_stage(k, bytes, bound)) return rc;
-    if (tail) {
+    if (any_tail) {
         const uint64_t samples = uint64_t(g.frames) * g.w * g.h * g.c;
-        if (int rc = ensure_grown(k, k->d_box, k->box_cap, tail->box_bytes, samples)) return rc;
-        if (int rc = ensure_grown(k, k->d_mid, k->mid_cap, tail->mid_bytes, samples)) return rc;
+        if (int rc = ensure_grown(k, k->d_box, k->box_cap, tail ? tail->box_bytes : warp->box_bytes, samples)) return rc;
+        if (tail)
+            if (int rc = ensure_grown(k, k->d_mid, k->mid_cap, tail->mid_bytes, samples)) return rc;
     }
     uint32_t slot = 0;
     if (int rc = regions_slot_take(k, bytes, bound, slot)) return rc;
@@ -542,6 +559,7 @@ int decode_windows(llcomp_mi_codec* k, const WindowsPlan& p, const ResampleTail*
     std::memcpy(h, p.tab.data(), p.tab.size() * sizeof(RegionsFrame));
     if (gp) regions_gather_copy(*gp, src.data, h + lay.pay_at, reinterpret_cast<uint32_t*>(h + lay.len_at), reinterpret_cast<uint64_t*>(h + lay.off_at));
     if (tail) tail->block.put(h + rs_at);
+    if (warp) warp->put(h + rs_at);
     hipStream_t s = static_cast<hipStream_t>(stream);
     uint8_t* const d_copy = table_only ? reinterpret_cast<uint8_t*>(k->d_regions) : k->d_stage;
     DoneGuard done_guard{k, s};
@@ -550,7 +568,7 @@ int decode_windows(llcomp_mi_codec* k, const WindowsPlan& p, const ResampleTail*
         Timed t(k, s, 4);
         HIP_TRY(hipMemcpyAsync(d_copy, h, bytes, hipMemcpyHostToDevice, s));
         if (int rc = regions_slot_queued(k, slot, s)) return rc;
-        if (!gp) {
+        if (!gp && p.n_classes) {  // (no class: a warped views call whose every view is all fill)
             HIP_TRY(launch_group_sums(g, static_cast<const uint32_t*>(src.d_slice_len), k->d_group_off, s));
             HIP_TRY(launch_scan_groups(g, k->d_group_off, k->d_total_tmp, s));
         }
@@ -561,10 +579,12 @@ int decode_windows(llcomp_mi_codec* k, const WindowsPlan& p, const ResampleTail*
                                   : RegionsSource{static_cast<const uint8_t*>(src.d_payload), src.payload_bytes,
                                                   static_cast<const uint32_t*>(src.d_slice_len), nullptr, nullptr};
     if (int rc = regions_classes(k, p.classes, p.n_classes, reinterpret_cast<const RegionsFrame*>(d_copy), from, p.wmax, p.hmax,
-                                 tail ? k->d_box : static_cast<uint8_t*>(d_px), static_cast<uint32_t*>(d_status), s))
+                                 any_tail ? k->d_box : static_cast<uint8_t*>(d_px), static_cast<uint32_t*>(d_status), s))
         return rc;
     if (tail)
         if (int rc = windows_resample(k, p, *tail, k->d_stage + rs_at, s)) return rc;
+    if (warp)
+        if (int rc = windows_warp(k, p, *warp, k->d_stage + rs_at, s)) return rc;
     ++k->n_decode;
     return LLCOMP_MI_OK;
 }
@@ -1277,6 +1297,40 @@ int llcomp_mi_codec_decode_padded_views_host(llcomp_mi_codec* k, const uint8_t* 
     if (!gather_matches(p, gp)) return LLCOMP_MI_HIP_ERROR;
     return decode_windows(k, p, &p.tail, padded_tables_bound(k->g, p.u.total_views), WindowsSource{nullptr, 0, nullptr, data, &gp}, nullptr,
                           d_status, stream);
+}
+
+// Warped views: the views decode on the views' SOURCE rectangles up to the boxes (warp_plan.hpp: warp_setup -- views_union and
+// regions_setup_sized, unchanged), then the third kind of tail: one gather launch per group reads every view from its frame's box.
+int llcomp_mi_codec_decode_warped_views(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                        const llcomp_mi_warp_group* groups, uint32_t n_groups, void* d_status, void* stream) {
+    if (!k || !d_payload || !d_slice_len || !d_status) return LLCOMP_MI_BAD_ARGS;
+    if (misaligned(d_slice_len, 4) || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
+    WarpPlan p;
+    if (int rc = warp_setup(k->g, k->tune, groups, n_groups, p)) return rc;
+    return decode_windows(k, p, nullptr, warp_tables_bound(k->g, p.total_views), WindowsSource{d_payload, payload_bytes, d_slice_len, nullptr, nullptr},
+                          nullptr, d_status, stream, &p.tail);
+}
+
+// ... of host containers: the gather over the used frames' union rectangles; with no used frame (every view all fill) nothing is read.
+int llcomp_mi_codec_decode_warped_views_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens,
+                                             const llcomp_mi_warp_group* groups, uint32_t n_groups, void* d_status, void* stream) {
+    if (!k || !data || !lens || !d_status || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
+    WarpPlan p;
+    if (int rc = warp_setup(k->g, k->tune, groups, n_groups, p)) return rc;
+    RegionsGather gp;
+    if (!p.u.used.empty()) {
+        if (int rc = regions_gather_plan_sized(data, lens, k->g.frames, p.u.rects.data(), p.wmax, p.hmax, gp, p.u.used.data(), uint32_t(p.u.used.size())))
+            return rc;
+        if (!same_shape(k->g, gp.g)) return LLCOMP_MI_BAD_ARGS;
+    }
+    if (!gather_matches(p, gp)) return LLCOMP_MI_HIP_ERROR;
+    return decode_windows(k, p, nullptr, warp_tables_bound(k->g, p.total_views), WindowsSource{nullptr, 0, nullptr, data, &gp}, nullptr, d_status,
+                          stream, &p.tail);
+}
+
+uint64_t llcomp_mi_codec_warp_workspace_bytes(const llcomp_mi_codec* k, uint64_t total_views) {
+    if (!k) return 0;
+    return k->workspace_bytes + warp_tables_bound(k->g, total_views);
 }
 
 uint64_t llcomp_mi_codec_padded_workspace_bytes(const llcomp_mi_codec* k, uint64_t total_views) {
