@@ -102,6 +102,11 @@ namespace llcomp_mi {
 #else
 #define LL_RENORM_SKIP(N) "s_cbranch_execz .Lskip" N "_%=\n\t"
 #endif
+// exec &= (A OP B) over the lanes in exec.  v_cmpx writes EXEC itself (and VCC, dead at every use) at the price of v_cmp: no
+// s_and_b64 through the CU's one scalar unit.  gfx950: a SALU read of EXEC, s_cbranch_execz / execnz and an ordinary VALU or LDS
+// instruction behind a VALU write of EXEC need no wait state (DPP, v_readlane / v_readfirstlane and EXECZ as a VALU operand
+// would: none follows inside the block, and the block ends in a scalar write of EXEC).
+#define LL_NARROW(OP, A, B) "v_cmpx_" OP "_e32 vcc, " A ", " B "\n\t"
 // range -= (r1 = range * P(entry) >> 8): the outcome of a 0
 #define LL_SPLIT(EL)                                                                                              \
     "v_mul_u32_u24_sdwa " LL_R1 ", " EL ", " LL_RANGE " dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:DWORD\n\t" \

@@ -12,8 +12,7 @@
 #define LL_UNARY(K, KM1, EL, EH, N, SAVE)                  \
     LL_SPLIT(EL)                                           \
     LL_STATE("ds_write_b8 %[bank], " EL " offset:" K "\n\t") \
-    "v_cmp_lt_u32_e32 vcc, " KM1 ", " LL_EX "\n\t"         \
-    "s_and_b64 exec, exec, vcc\n\t"                        \
+    LL_NARROW("lt_u32", KM1, LL_EX)                        \
     SAVE                                                   \
     "s_cbranch_execz .Lunary_done_%=\n\t"                  \
     LL_ONE                                                 \
@@ -75,19 +74,21 @@ __device__ __forceinline__ void enc_rows_sample_asm(unsigned long long& low_rang
         "s_mov_b64 " LL_SU ", exec\n\t"
         "v_add_u32_e32 " LL_N ", -3, " LL_EX "\n\t"
         "s_mov_b32 " LL_SI ", 0\n\t"
+        // (both run loops are tested at the bottom: the first test stands in front, the back edge is the exit test's own branch)
+        LL_SPLIT(LL_E4L)
+        LL_NARROW("lt_u32", LL_SI, LL_N)
+        "s_cbranch_execz .Ltail_done_%=\n\t"
         ".p2align 6\n"  // (the two run loops start on a 64-byte line of the instruction cache)
         ".Ltail_%=:\n\t"
-        LL_SPLIT(LL_E4L)
-        "v_cmp_lt_u32_e32 vcc, " LL_SI ", " LL_N "\n\t"
-        "s_and_b64 exec, exec, vcc\n\t"
-        "s_cbranch_execz .Ltail_done_%=\n\t"
         "v_lshrrev_b32_e32 " LL_OFF ", 16, " LL_E4H "\n\t"
         "ds_read_b64 " LL_E4 ", " LL_OFF "\n\t"
         LL_ONE
         LL_RENORM("4")
         "s_add_i32 " LL_SI ", " LL_SI ", 1\n\t"
         "s_waitcnt lgkmcnt(0)\n\t"
-        "s_branch .Ltail_%=\n"
+        LL_SPLIT(LL_E4L)
+        LL_NARROW("lt_u32", LL_SI, LL_N)
+        "s_cbranch_execnz .Ltail_%=\n"
         ".Ltail_done_%=:\n\t"
         "s_mov_b64 exec, " LL_SU "\n\t"
         LL_STATE("ds_write_b8 %[bank], " LL_E4L " offset:256\n")
@@ -109,11 +110,10 @@ __device__ __forceinline__ void enc_rows_sample_asm(unsigned long long& low_rang
         LL_STATE("ds_write_b8 %[bank], " LL_E5H " offset:257\n")
         LL_PATCH_END("5")
         LL_RENORM("6")
+        LL_NARROW("ne_u32", "%[sent]", LL_BITS)
+        "s_cbranch_execz .Lman_done_%=\n\t"
         ".p2align 6\n"
         ".Lman_%=:\n\t"
-        "v_cmp_ne_u32_e32 vcc, %[sent], " LL_BITS "\n\t"
-        "s_and_b64 exec, exec, vcc\n\t"
-        "s_cbranch_execz .Lman_done_%=\n\t"
         "v_add_co_u32_e32 " LL_BITS ", vcc, " LL_BITS ", " LL_BITS "\n\t"
         "s_waitcnt lgkmcnt(0)\n\t"
         LL_SPLIT(LL_E6L)
@@ -125,7 +125,9 @@ __device__ __forceinline__ void enc_rows_sample_asm(unsigned long long& low_rang
         LL_PATCH_END("6")
         "ds_read_b64 " LL_E6 ", " LL_OFF "\n\t"
         LL_RENORM("7")
-        "s_branch .Lman_%=\n"
+        LL_NARROW("ne_u32", "%[sent]", LL_BITS)
+        "s_cbranch_execnz .Lman_%=\n\t"
+        "s_branch .Lman_done_%=\n"  // (once per sample, over the out-of-line part)
         // ---- out of line: the carry subroutine and its call stubs
         LL_RARE_STUB("0") LL_RARE_STUB("1") LL_RARE_STUB("2") LL_RARE_STUB("3") LL_RARE_STUB("4")
         LL_RARE_STUB("5") LL_RARE_STUB("6") LL_RARE_STUB("7") LL_RARE_STUB("8")

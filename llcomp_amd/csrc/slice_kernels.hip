@@ -269,12 +269,24 @@ struct RangeEnc {
 };
 // Staging area: 32 bytes per lane, filled LINEARLY -- the renormalisation stores its byte at `wp` and adds one, no index
 // arithmetic (round 2 kept a ring and paid a v_and_or per renormalisation, which the wavefront executes for every bin
-// because some lane renormalises in nearly every bin).  Once per sample, when 16 bytes have gathered, they leave for HBM
-// as one aligned 16-byte store and the rest (at most 12 bytes) moves down by 16.  A sample adds at most 13 bytes to at
-// most 15, so 28 of the 32 bytes are ever used; the reference's "no byte on the first renormalisation" is a dummy byte
-// at position -1, i.e. the unused last byte of the neighbouring lane's area (16 bytes of padding in front of lane 0).
+// because some lane renormalises in nearly every bin).  The reference's "no byte on the first renormalisation" is a dummy byte
+// at position -1, i.e. the last byte of the neighbouring lane's area (16 bytes of padding in front of lane 0).
+// Two flush policies, both once per sample and in front of its coding:
+//   * every sample (enc_flush16 under `wp >= base + 16`): a lane enters a sample with at most 15 bytes, a sample adds at most
+//     kSampleBytesMax, so 28 of the 32 bytes are ever used -- the 2-D, snapshot and table-in-HBM families;
+//   * in batches (enc_flush_batched, the 1-row-slice kernels): the wavefront enters the flush region only when SOME lane holds at
+//     least kFlushAt bytes, and every lane with a whole unit then stores one.  INVARIANT: a lane enters a sample with at most
+//     kFlushAt - 1 bytes (below the threshold, or at most kStageFill - 16 behind its flush) and leaves it with at most
+//     kStageFill = kFlushAt - 1 + kSampleBytesMax.  kStageFill stops ONE short of kStageBytes: the area's last byte is where the
+//     next lane's dummy byte lands, whenever that lane renormalises first -- a flat row does so many samples after a noisy
+//     neighbour has filled its area, so the byte can never hold output.  (kFlushAt = 20 would use all 32.)
 constexpr int kStageBytes = 32;
 constexpr int kStagePad = 16;
+constexpr int kSampleBytesMax = 13;  // bytes one sample can add: one per bin at the most (putSymbol<true,4,6,7> on 8-bit planes)
+constexpr int kFlushAt = 19;
+constexpr int kStageFill = kFlushAt - 1 + kSampleBytesMax;
+static_assert(kStageFill <= kStageBytes - 1, "the staging area's last byte belongs to the next lane's dummy byte");
+static_assert(kStageFill - 16 <= kFlushAt - 1 && kFlushAt >= 16, "one unit per lane and flush event must be enough");
 __device__ __forceinline__ int32_t enc_pos(const RangeEnc& e) { return e.flushed + int32_t(e.wp - e.base); }
 // stream lane order: unit u of this lane is (u << lane_shift) units further on
 __device__ __forceinline__ uint8_t* unit_byte(RangeEnc& e, uint32_t k) {
@@ -292,6 +304,14 @@ __device__ __forceinline__ void enc_flush16(RangeEnc& e) {
     a[0] = rest.x; a[1] = rest.y; a[2] = rest.z; a[3] = rest.w;
     e.flushed += 16;
     e.wp -= 16;
+}
+// The batched policy (see the staging area): one compare and one wave-uniform branch per sample outside the region.
+__device__ __forceinline__ void enc_flush_batched(RangeEnc& e) {
+    if (__builtin_amdgcn_ballot_w64(e.wp >= e.base + uint32_t(kFlushAt)) != 0) {
+        uint32_t w = e.wp + uint32_t(kFlushAt - 16);
+        asm volatile("" : "+v"(w));  // (pinned inside the region: hipcc otherwise folds both tests into one exec mask, two compares a sample)
+        if (w >= e.base + uint32_t(kFlushAt)) enc_flush16(e);
+    }
 }
 // rare: +1 into the bytes before position `pos` (the byte at `pos` itself just wrapped from 0xFF to 0x00)
 __device__ __forceinline__ void enc_carry_back(RangeEnc& e) {
@@ -460,7 +480,12 @@ __device__ __forceinline__ void enc_residual(RangeEnc& e, Bank& bank, const entr
     }
 }
 
+template <bool BATCHED>
 __device__ __forceinline__ void enc_finish_and_count(RangeEnc& e, int32_t& n_bytes) {  // llcomp.hpp:75-81
+    // the batched policy leaves up to kStageFill bytes behind the last sample: room for the two bytes below
+    if constexpr (BATCHED) {
+        if (e.wp >= e.base + 16) enc_flush16(e);
+    }
     e.range = 0xFF; e.low += 0xFF; enc_renorm(e);
     e.range = 0xFF; enc_renorm(e);
     n_bytes = enc_pos(e);
@@ -684,8 +709,8 @@ __global__ __launch_bounds__(64, ROWS ? 8 : 1) void k_encode_slices(const Geomet
         const char* gsym;
         uint32_t sofs, sstep;
         [[maybe_unused]] uint32_t n_dword = total;  // PX: samples 0 .. n_dword-1 are read as dwords, the rest byte by byte (rows_px_dwords)
-        [[maybe_unused]] uint32_t psh = 0, msub = 0, my = 0;
-        [[maybe_unused]] int pl = 128, pL = 128;  // PX: l and L of the lane's plane (llcomp.hpp:417-419: 128 at the slice start)
+        [[maybe_unused]] uint32_t xm = 0, coef = 0, my = 0;
+        [[maybe_unused]] int pl = 128, pL = 128;  // PX: l and L of the lane's plane (llcomp.hpp:417-419: 128 at the slice start; see xm)
         if constexpr (PX) {
             // tile_h == 1: the tiles of a batch lie back to back in raster order, so lane 0's tile starts lowest and the wavefront's
             // tiles span (64 / C + 2) tiles at most (< 2^31 bytes: rows_encoder_reads_pixels)
@@ -699,12 +724,19 @@ __global__ __launch_bounds__(64, ROWS ? 8 : 1) void k_encode_slices(const Geomet
             sstep = C;
             const unsigned long long total_bytes = (unsigned long long)(g.frames) * g.h * g.w * C;
             n_dword = rows_px_dwords(tbase, total, C, total_bytes);
-            // the plane from the pixel's dword d (llcomp.hpp:396-414), without a branch: v = own byte - (G & msub) + (t & my), where
-            // t = (R - G + B - G) / 4 truncated -- plane 0: R - G, plane 1: G + t, plane 2: B - G, plane 3 and C < 3: the byte itself
-            psh = 8 * r.ch;
-            msub = C >= 3 && (r.ch == 0 || r.ch == 2) ? ~0u : 0u;
+            // the plane from the pixel's dword d (llcomp.hpp:396-414), without a branch and without extracting a byte: two byte dot
+            // products (v_dot4_u32_u8).  With G' = 255 - G in byte 1 of d ^ 0xFF00 every term is non-negative:
+            //   plane 0: R - G + 255 = (1,1,0,0) . (d ^ 0xFF00)      plane 2: B - G + 255 = (0,1,1,0) . (d ^ 0xFF00)
+            //   plane 1: G + (t & my), t = (R + B - 2G) / 4 truncated, R + B - 2G = (1,2,1,0) . (d ^ 0xFF00) - 510
+            //   plane 3 and C < 3: the own byte.
+            // t & my goes in as the second product's accumulator.  Planes 0 and 2 are carried 255 too high, l and L with them from
+            // their start value on: the coder only ever sees v - l and L - l.
+            const bool diff = C >= 3 && (r.ch == 0 || r.ch == 2);
+            xm = diff ? 0xFF00u : 0u;
+            coef = diff ? (r.ch == 0 ? 0x0101u : 0x010100u) : 1u << (8 * r.ch);
             my = C >= 3 && r.ch == 1 ? ~0u : 0u;
-            asm volatile("" : "+v"(psh), "+v"(msub), "+v"(my));
+            pl = pL = 128 + int(xm >> 8);
+            asm volatile("" : "+v"(xm), "+v"(coef), "+v"(my));
         } else {
             const uint32_t grp = __builtin_amdgcn_readfirstlane(id >> g.lane_shift);
             gsym = reinterpret_cast<const char*>(sym + ((size_t(grp) * g.slice_samples) << g.lane_shift));
@@ -752,10 +784,11 @@ __global__ __launch_bounds__(64, ROWS ? 8 : 1) void k_encode_slices(const Geomet
         auto front = [&](uint32_t sy) -> uint32_t {
             uint32_t t = sy;
             if constexpr (PX) {
-                const uint32_t G = (sy >> 8) & 0xFF;
-                const int sum = int(sy & 0xFF) + int((sy >> 16) & 0xFF) - 2 * int(G);
-                const int q = (sum + int((uint32_t(sum) >> 31) * 3u)) >> 2;  // truncating division, llcomp.hpp:402
-                t = uint32_t(int(__builtin_amdgcn_ubfe(sy, psh, 8)) - int(G & msub) + (q & int(my)));
+                const int sum = int(__builtin_amdgcn_udot4(sy ^ 0xFF00u, 0x010201u, uint32_t(-510), false));
+                int neg = sum >> 31;
+                asm volatile("" : "+v"(neg));  // (2-cycle forms only: ashr, and, add, ashr -- not a bit-field extract)
+                const int q = (sum + (neg & 3)) >> 2;  // truncating division, llcomp.hpp:402
+                t = __builtin_amdgcn_udot4(sy ^ xm, coef, uint32_t(q & int(my)), false);
             }
             asm volatile("" : "+v"(t) : : "memory");
             return t;
@@ -834,7 +867,7 @@ __global__ __launch_bounds__(64, ROWS ? 8 : 1) void k_encode_slices(const Geomet
             const uint32_t t0 = front(s0);
             const uint32_t s2 = i + 2 < total ? load_at(sofs, i + 2) : 0;
             sofs += sstep;
-            if (e.wp >= e.base + 16) enc_flush16(e);  // 16 bytes staged (LDS addresses: no wrap-around, wp >= base - 1)
+            enc_flush_batched(e);  // (LDS addresses: no wrap-around, wp >= base - 1)
             code(t0, c0, model);
             s0 = s1;
             s1 = s2;
@@ -846,14 +879,14 @@ __global__ __launch_bounds__(64, ROWS ? 8 : 1) void k_encode_slices(const Geomet
                 const uint32_t t0 = front(s0);
                 s0 = load_sym(sofs);
                 sofs += sstep;
-                if (e.wp >= e.base + 16) enc_flush16(e);
+                enc_flush_batched(e);
                 code(t0, c0, model);
                 s1 = consume_here(s1);
                 const Ctx c1 = context(model);
                 const uint32_t t1 = front(s1);
                 s1 = load_sym(sofs);
                 sofs += sstep;
-                if (e.wp >= e.base + 16) enc_flush16(e);
+                enc_flush_batched(e);
                 code(t1, c1, model);
             }
             for (; i < total; ++i) sample_tested(i, model);
@@ -915,7 +948,7 @@ __global__ __launch_bounds__(64, ROWS ? 8 : 1) void k_encode_slices(const Geomet
         }
     }
     int32_t n_bytes = enc_pos(e);  // (before the tail flush moves wp)
-    enc_finish_and_count(e, n_bytes);
+    enc_finish_and_count<ROWS>(e, n_bytes);
     LLMI_PROBE_STOP(0);
     if (n_bytes > e.cap) {
         atomicOr(status, kStOverflow);
