@@ -447,6 +447,64 @@ int llcomp_mi_warp_views_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_
  * calls; it is not fast.  BAD_ARGS, out untouched: a NULL src, m or out, a side or c of 0, and the rule's limits.  Host-only. */
 int llcomp_mi_warp_reference(const uint8_t* src, uint32_t w, uint32_t h, uint32_t c, const double* m, uint32_t filter, const uint8_t* fill,
                              uint32_t ow, uint32_t oh, uint8_t* out);
+/* Photometric chains (llcomp_mi_codec_decode_photo_views / _photo_warped_views below: torchvision's ColorJitter without hue,
+ * RandomGrayscale, and the colour ops of RandAugment / AutoAugment / TrivialAugment, PIL backend).  A PHOTO CHAIN is 0 to
+ * LLCOMP_MI_PHOTO_MAX_OPS ops {op, param}, applied in order to one view.
+ * THE RULE.  The chain's input is what the call it extends writes for that view as U8 HWC: after the resample or the warp, and after the
+ * mirror bit (every op commutes with the mirror: "mirror, then chain" is PIL's "flip, then jitter" and the reverse order alike).  The
+ * output table (llcomp_mi_output_table) and the layout come after the chain, as they come last everywhere else.  Statistics are those of
+ * the view's own oh x ow pixels as they stand when the op is reached, never those of the frame, the box or the group; n = oh * ow.
+ *   L(r, g, b) = (19595 r + 38470 g + 7471 b + 0x8000) >> 16 for c = 3; L = v for c = 1.
+ *   blend(d, v, a) is PIL's ImagingBlend, in IEEE binary32 with every operation rounded by itself, no fused multiply-add:
+ *     t = (float)d + a * (float)(v - d); for 0 <= a <= 1 the result is t truncated toward zero; otherwise 0 for t <= 0, 255 for
+ *     t >= 255, else t truncated.
+ *   BRIGHTNESS  a  blend(0, v, a)                                           ImageEnhance.Brightness, adjust_brightness
+ *   CONTRAST    a  m = (int)((double)sum of L / (double)n + 0.5) over the view, in binary64; then blend(m, v, a)
+ *                                                                           ImageEnhance.Contrast, adjust_contrast
+ *   COLOR       a  blend(L(pixel), v, a); identity for c = 1                ImageEnhance.Color, adjust_saturation
+ *   GRAYSCALE   -  every channel becomes L(pixel); identity for c = 1       convert("L") replicated, RandomGrayscale
+ *   INVERT      -  255 - v                                                  ImageOps.invert
+ *   SOLARIZE    t  v if v < t, else 255 - v                                 ImageOps.solarize
+ *   POSTERIZE   b  v & ~(2^(8 - b) - 1)                                     ImageOps.posterize
+ *   AUTOCONTRAST -  per channel, from its histogram over the view: lo, hi = the lowest and highest value present; hi <= lo leaves the
+ *                  channel unchanged; otherwise, in binary64, s = 255.0 / (hi - lo), o = -lo * s, lut[i] = clamp((int)(i * s + o), 0, 255),
+ *                  the multiply and the add rounded separately, (int) truncating toward zero      ImageOps.autocontrast (cutoff 0)
+ *   EQUALIZE    -  per channel, from its histogram h over the view: fewer than two values present leave the channel unchanged;
+ *                  step = (n - h[last value present]) / 255 in integers, and step == 0 leaves it unchanged; otherwise acc = step / 2 and
+ *                  for i = 0..255: lut[i] = min(255, acc / step), then acc += h[i]                ImageOps.equalize
+ * LIMITS (BAD_ARGS): a factor a that is not finite or not within 0..256; a threshold t that is not an integer within 0..256; bits b
+ * that are not an integer within 1..8; an unknown op code; more than LLCOMP_MI_PHOTO_MAX_OPS ops; and a chain that is not empty on a
+ * codec whose c is neither 1 nor 3 (PIL's L and RGB).  The parameter of an op that takes none is ignored.
+ * NOT COVERED: hue (PIL's HSV round trip), sharpness and blur (neighbourhood filters: ImageEnhance.Sharpness, GaussianBlur), alpha. */
+#define LLCOMP_MI_PHOTO_MAX_OPS 8
+enum {
+    LLCOMP_MI_PHOTO_BRIGHTNESS = 0,
+    LLCOMP_MI_PHOTO_CONTRAST = 1,
+    LLCOMP_MI_PHOTO_COLOR = 2,
+    LLCOMP_MI_PHOTO_GRAYSCALE = 3,
+    LLCOMP_MI_PHOTO_INVERT = 4,
+    LLCOMP_MI_PHOTO_SOLARIZE = 5,
+    LLCOMP_MI_PHOTO_POSTERIZE = 6,
+    LLCOMP_MI_PHOTO_AUTOCONTRAST = 7,
+    LLCOMP_MI_PHOTO_EQUALIZE = 8,
+    LLCOMP_MI_PHOTO_OP_COUNT = 9
+};
+typedef struct llcomp_mi_photo_op {
+    uint32_t op; /* LLCOMP_MI_PHOTO_* */
+    float param;
+} llcomp_mi_photo_op;
+typedef struct llcomp_mi_photo_chain {
+    uint32_t n_ops; /* 0 .. LLCOMP_MI_PHOTO_MAX_OPS; 0 = the view as the extended call writes it */
+    llcomp_mi_photo_op ops[LLCOMP_MI_PHOTO_MAX_OPS];
+} llcomp_mi_photo_chain; /* 68 bytes */
+typedef struct llcomp_mi_photo_group {
+    uint32_t struct_size;                /* = sizeof(llcomp_mi_photo_group); also the stride of an array of them */
+    const llcomp_mi_photo_chain* chains; /* one per view of the group it travels beside, HOST memory, read during the call only; NULL = none */
+} llcomp_mi_photo_group; /* 16 bytes on LP64 */
+/* The rule above on a host image, in place of a decode: src [h][w][c] -> out [h][w][c] (out may be src).  It is compiled from the same
+ * functions as the GPU's kernels and states the rule as llcomp_mi_warp_reference does; it is not fast.  BAD_ARGS, out untouched: a NULL
+ * src or out, a side of 0, a NULL ops with n_ops > 0, and the limits above (c other than 1 and 3 also with no op).  Host-only. */
+int llcomp_mi_photo_reference(const uint8_t* src, uint32_t w, uint32_t h, uint32_t c, const llcomp_mi_photo_op* ops, uint32_t n_ops, uint8_t* out);
 uint32_t llcomp_mi_slice_count(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar);
 /* Slice width for one-row slices (tile_h = 1) when `frames` frames are coded per call: the widest slice (64..480 pixels) that
  * still keeps about four wavefronts per SIMD busy.  A call that codes few frames is latency-bound with wide slices; this
@@ -511,7 +569,7 @@ uint32_t llcomp_mi_codec_kernel_family(const llcomp_mi_codec* codec);
 uint64_t llcomp_mi_codec_workspace_bytes(const llcomp_mi_codec* codec);
 /* Diagnostic: the device bytes the codec holds right now (what the calls so far have allocated; never above
  * llcomp_mi_codec_workspace_bytes, except through a resized regions decode to an output larger than the image, or a views decode of
- * more views than frames: llcomp_mi_codec_views_workspace_bytes). */
+ * more views than frames: llcomp_mi_codec_views_workspace_bytes; the padded, warped and photometric calls have bounds of their own). */
 uint64_t llcomp_mi_codec_allocated_bytes(const llcomp_mi_codec* codec);
 /* Allocates NOW what the first encode (LLCOMP_MI_PREPARE_ENCODE: the 2-D encoder's snapshot arrays, or its state tables) and / or
  * the first decode (LLCOMP_MI_PREPARE_DECODE: the state tables of 2-D slices) would otherwise allocate inside the call -- for callers
@@ -728,6 +786,39 @@ int llcomp_mi_codec_decode_warped_views_host(llcomp_mi_codec* codec, const uint8
  * index tables, c fill bytes and an output table (16 + 1024 * c): llcomp_mi_codec_workspace_bytes + 48 + max(total_views, 1) * (64 +
  * 4 * (w + h) + c + 16 + 1024 * c). */
 uint64_t llcomp_mi_codec_warp_workspace_bytes(const llcomp_mi_codec* codec, uint64_t total_views);
+/* llcomp_mi_codec_decode_padded_views(_host) and llcomp_mi_codec_decode_warped_views(_host) with a photometric chain per view
+ * (llcomp_mi_photo_chain / llcomp_mi_photo_group / the rule above).  photo: n_groups entries, photo[i].chains the n_views chains of
+ * groups[i]; a NULL photo, a NULL chains and a group whose chains are all empty mean no chain: such a group takes the extended call's path
+ * untouched, and with no chain at all the call writes exactly the bytes and the status of the call it extends.  pad (the padded form):
+ * NULL = plain views, llcomp_mi_codec_decode_views exactly.
+ * A group with a chain is resampled or warped by the extended call's kernels, unchanged, as U8 HWC into a staging buffer of the codec,
+ * `chunk` views at a time where the group's n_views * oh * ow * c bytes would pass frames * w * h * c -- the buffer never grows past that
+ * for ow <= w, oh <= h (one view always fits).  Then the chunk's views run their chains together, step by step on the stream, views with
+ * shorter chains sitting out: a statistics pass where some view's op of that step needs one (per view, c histograms of 256 u32 and the sum
+ * of L as u64, summed with integer atomics: the result does not depend on the order), one table [c][256] per view built from the
+ * parameter and the statistics for every op but COLOR and GRAYSCALE, and a per-pixel pass in place.  A view's last step writes through the
+ * group's output table and layout to d_out; a view with an empty chain in such a group is written by the first step, byte for byte as
+ * the extended call writes it.  The chains cross in the call's ONE copy, behind the tail's block; nothing goes back to the host between
+ * the steps.  d_status and the verdicts are the extended call's.  BAD_ARGS, before anything is queued or written (d_status untouched):
+ * every case of the extended call, a photo[i].struct_size that is not the struct's, and the rule's limits.
+ * _host: as the extended calls' _host forms; LLCOMP_MI_CTR_HOST_STAGED_BYTES counts what they count. */
+int llcomp_mi_codec_decode_photo_views(llcomp_mi_codec* codec, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                       const llcomp_mi_view_group* groups, uint32_t n_groups, const llcomp_mi_pad* pad,
+                                       const llcomp_mi_photo_group* photo, void* d_status, void* stream);
+int llcomp_mi_codec_decode_photo_views_host(llcomp_mi_codec* codec, const uint8_t* const* data, const size_t* lens,
+                                            const llcomp_mi_view_group* groups, uint32_t n_groups, const llcomp_mi_pad* pad,
+                                            const llcomp_mi_photo_group* photo, void* d_status, void* stream);
+int llcomp_mi_codec_decode_photo_warped_views(llcomp_mi_codec* codec, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                              const llcomp_mi_warp_group* groups, uint32_t n_groups, const llcomp_mi_photo_group* photo,
+                                              void* d_status, void* stream);
+int llcomp_mi_codec_decode_photo_warped_views_host(llcomp_mi_codec* codec, const uint8_t* const* data, const size_t* lens,
+                                                   const llcomp_mi_warp_group* groups, uint32_t n_groups, const llcomp_mi_photo_group* photo,
+                                                   void* d_status, void* stream);
+/* The bound on llcomp_mi_codec_allocated_bytes for the four calls above with up to total_views views and ow <= w, oh <= h: the larger of
+ * llcomp_mi_codec_padded_workspace_bytes and llcomp_mi_codec_warp_workspace_bytes for them, plus the staging buffer (frames * w * h * c),
+ * and per view its statistics and table (8 + 1024 * c + 256 * c bytes) and its chain in the staged block (68 bytes, and 16 of alignment
+ * per call). */
+uint64_t llcomp_mi_codec_photo_workspace_bytes(const llcomp_mi_codec* codec, uint64_t total_views);
 /* Stage-A only (context + prediction model), for tests and profiling: d_sym u32[frames*h*w*c],
  * low 16 bits = folded context (0..7925), high 16 bits = folded residual (two's complement). */
 int llcomp_mi_codec_model(llcomp_mi_codec* codec, const void* d_px, void* d_sym, void* stream);

@@ -43,6 +43,7 @@ from ._lib import Info, Opts, OutputFormat
 from ._lib import Pad as _Pad
 from ._lib import View as _View, ViewGroup as _ViewGroup
 from ._lib import WarpView as _WarpView, WarpGroup as _WarpGroup
+from ._lib import PhotoOp as _PhotoOp, PhotoChain as _PhotoChain, PhotoGroup as _PhotoGroup
 
 EXT = ".llcomp"
 FORMAT_LEGACY, FORMAT_SLICED = 0, 1
@@ -57,6 +58,11 @@ FLAG_MIRROR, FLAG_FILTER_SHIFT = 1, 4
 # what stands outside the image in a padded call (LLCOMP_MI_PAD_*): numpy's np.pad modes and torchvision's padding_mode of these names
 PAD_CONSTANT, PAD_EDGE, PAD_REFLECT, PAD_SYMMETRIC = range(4)
 PAD_NAMES = ("constant", "edge", "reflect", "symmetric")
+# photometric ops (LLCOMP_MI_PHOTO_*; include/llcomp_mi.h "Photometric chains")
+(PHOTO_BRIGHTNESS, PHOTO_CONTRAST, PHOTO_COLOR, PHOTO_GRAYSCALE, PHOTO_INVERT, PHOTO_SOLARIZE, PHOTO_POSTERIZE, PHOTO_AUTOCONTRAST,
+ PHOTO_EQUALIZE) = range(9)
+PHOTO_MAX_OPS = 8
+PHOTO_NAMES = ("brightness", "contrast", "color", "grayscale", "invert", "solarize", "posterize", "autocontrast", "equalize")
 
 RawImage = namedtuple("RawImage", "pixels width height channels")
 
@@ -381,12 +387,103 @@ class ViewGroup:
     """Views that share one output (llcomp_mi_view_group): views = a sequence of (frame, x, y, rw, rh) or (frame, x, y, rw, rh, flags) or
     an int array [n, 5 or 6]; the output is [n][oh][ow][c] at device address d_out (layout="chw": [n][c][oh][ow]) in the format that
     dtype, layout, scale, mean and std give (as Codec.decode_resized_regions takes them); filter: one name or FILTER_* code for every view
-    of the group, or one per view, OR-ed into bits 4-6 of the views' flags.  A plain tuple (views, ow, oh, d_out) is a group too."""
+    of the group, or one per view, OR-ed into bits 4-6 of the views' flags.  A plain tuple (views, ow, oh, d_out) is a group too.
+    photo: a photometric chain for every view of the group -- a list of (op, param) or (name, param) pairs or bare names, such as
+    [("brightness", 1.2), "grayscale"] -- or a list of one chain per view (photo_chain); None: none."""
 
-    def __init__(self, views, ow, oh, d_out=0, dtype=None, layout="hwc", scale=False, mean=None, std=None, filter=None):
+    def __init__(self, views, ow, oh, d_out=0, dtype=None, layout="hwc", scale=False, mean=None, std=None, filter=None, photo=None):
         self.views, self.ow, self.oh, self.d_out = views, ow, oh, d_out
         self.format = dict(dtype=dtype, layout=layout, scale=scale, mean=mean, std=std)
         self.filter = filter
+        self.photo = photo
+
+
+def photo_code(op):
+    """PHOTO_* code of an op given by name ("brightness", "contrast", "color" or "saturation", "grayscale", "invert", "solarize",
+    "posterize", "autocontrast", "equalize") or by code"""
+    if isinstance(op, str):
+        name = "color" if op.lower() == "saturation" else op.lower()
+        if name not in PHOTO_NAMES:
+            raise LlcompError(BAD_ARGS, f"no photometric op {op!r}: one of {PHOTO_NAMES}")
+        return PHOTO_NAMES.index(name)
+    code = int(op)
+    if not 0 <= code <= 0xFFFFFFFF:
+        raise LlcompError(BAD_ARGS, f"no photometric op {op!r}")
+    return code
+
+
+def photo_chain(ops):
+    """a chain -- a sequence of (op, param) pairs, (op,) tuples, names or codes -- as a list of (code, float32 param); the limits are the
+    library's to check, but for the length: a chain holds at most PHOTO_MAX_OPS ops"""
+    out = []
+    for o in ops if ops is not None else ():
+        if isinstance(o, (str, int, np.integer)):
+            o = (o,)
+        o = tuple(o)
+        if not 1 <= len(o) <= 2:
+            raise LlcompError(BAD_ARGS, f"an op is (op, param) or (op,), got {o!r}")
+        out.append((photo_code(o[0]), float(np.float32(o[1] if len(o) == 2 and o[1] is not None else 0.0))))
+    if len(out) > PHOTO_MAX_OPS:
+        raise LlcompError(BAD_ARGS, f"a chain holds at most {PHOTO_MAX_OPS} ops, got {len(out)}")
+    return out
+
+
+def _is_op(o):
+    """whether an element of a photo= list is ONE op -- a name, a code, an (op, param) pair with a number for param, or a 1-tuple (op,) --
+    and not a view's chain (a list of ops)"""
+    if isinstance(o, (str, int, np.integer)):
+        return True
+    if not isinstance(o, (tuple, list)) or not o or not isinstance(o[0], (str, int, np.integer)):
+        return False
+    if len(o) == 1:
+        return isinstance(o, tuple)
+    return len(o) == 2 and (o[1] is None or isinstance(o[1], (int, float, np.integer, np.floating)))
+
+
+def _photo_groups(groups, n_views):
+    """the photo= of every group -> (ctypes array of llcomp_mi_photo_group or None when no group has one, keep-alive list); n_views: the
+    groups' view counts"""
+    specs = [getattr(gr, "photo", None) for gr in groups]
+    if all(p is None for p in specs):
+        return None, []
+    arr, keep = (_PhotoGroup * max(1, len(groups)))(), []
+    for i, spec in enumerate(specs):
+        arr[i] = _PhotoGroup(C.sizeof(_PhotoGroup), None)
+        if spec is None:
+            continue
+        spec = list(spec)
+        if all(_is_op(o) for o in spec):  # one chain for all views (an empty list: the empty chain)
+            chains = [photo_chain(spec)] * n_views[i]
+        else:
+            if len(spec) != n_views[i]:
+                raise LlcompError(BAD_ARGS, f"group {i}: photo takes one chain, or one per view ({n_views[i]}), got {len(spec)}")
+            chains = [photo_chain(ch) for ch in spec]
+        carr = (_PhotoChain * max(1, len(chains)))()
+        for j, ch in enumerate(chains):
+            carr[j].n_ops = len(ch)
+            for k, (op, param) in enumerate(ch):
+                carr[j].ops[k] = _PhotoOp(op, param)
+        keep.append(carr)
+        arr[i] = _PhotoGroup(C.sizeof(_PhotoGroup), C.cast(carr, C.POINTER(_PhotoChain)))
+    return arr, keep
+
+
+def photo_reference(frame, ops):
+    """The rule of the photometric chains on a host image (llcomp_mi_photo_reference): frame [h, w] or [h, w, c] uint8 with c = 1 or 3,
+    ops a chain as photo_chain takes it -> the image after the chain, byte for byte PIL's ImageEnhance / ImageOps applied in order."""
+    a = np.ascontiguousarray(frame, dtype=np.uint8)
+    if a.ndim not in (2, 3) or not a.size:
+        raise LlcompError(BAD_ARGS, f"a frame is [h, w] or [h, w, c], got shape {a.shape}")
+    h, w = a.shape[:2]
+    c = a.shape[2] if a.ndim == 3 else 1
+    ch = list(ops if ops is not None else ())
+    raw = []
+    for o in ch:  # (the length is the library's to refuse here: no PHOTO_MAX_OPS check on this side)
+        raw += photo_chain([o])
+    arr = (_PhotoOp * max(1, len(raw)))(*[_PhotoOp(op, p) for op, p in raw])
+    out = np.zeros_like(a)
+    _check(_lib.load().llcomp_mi_photo_reference(a.ctypes.data, w, h, c, arr, len(raw), out.ctypes.data))
+    return out
 
 
 def _view_groups(groups, c, signed=False):
@@ -442,10 +539,11 @@ class WarpGroup:
     filter: "nearest", "bilinear" or "bicubic" (or its FILTER_* code) for every view of the group, or one per view, OR-ed into bits 4-6
     of the views' flags; fill: c values 0..255 for what lies outside the frame (None: zeros)."""
 
-    def __init__(self, views, ow, oh, d_out=0, dtype=None, layout="hwc", scale=False, mean=None, std=None, filter=None, fill=None):
+    def __init__(self, views, ow, oh, d_out=0, dtype=None, layout="hwc", scale=False, mean=None, std=None, filter=None, fill=None, photo=None):
         self.views, self.ow, self.oh, self.d_out = views, ow, oh, d_out
         self.format = dict(dtype=dtype, layout=layout, scale=scale, mean=mean, std=std)
         self.filter, self.fill = filter, fill
+        self.photo = photo  # (a photometric chain for every view, or one per view: ViewGroup)
 
 
 def _matrix(m):
@@ -1217,7 +1315,16 @@ class Codec:
         of that frame.  A frame decodes the bounding box of all its views; a frame without a view is not read.  d_payload / d_slice_len
         are the full batch's (pack_batch).  pad_mode / fill as decode_resized_regions takes them: views may leave the image, a view's x and
         y may be negative (llcomp_mi_codec_decode_padded_views), and a frame decodes the bounding box of its views' source rectangles."""
-        if pad_mode is not None or fill is not None:
+        groups = list(groups) if groups is not None else []
+        padded = pad_mode is not None or fill is not None
+        if any(getattr(gr, "photo", None) is not None for gr in groups):  # (llcomp_mi_codec_decode_photo_views)
+            arr, n, _keep = _view_groups(groups, self.c, signed=padded)
+            photo, _keep_photo = _photo_groups(groups, [arr[i].n_views for i in range(n)])
+            pad, _keep_pad = _pad(self.c, pad_mode, fill) if padded else (None, None)
+            _check(self._L.llcomp_mi_codec_decode_photo_views(self._h, d_payload, payload_bytes, d_slice_len, arr, n,
+                                                              C.byref(pad) if padded else None, photo, d_status, stream))
+            return
+        if padded:
             arr, n, _keep = _view_groups(groups, self.c, signed=True)
             pad, _keep_pad = _pad(self.c, pad_mode, fill)
             _check(self._L.llcomp_mi_codec_decode_padded_views(self._h, d_payload, payload_bytes, d_slice_len, arr, n, C.byref(pad), d_status, stream))
@@ -1236,7 +1343,16 @@ class Codec:
         for f, d in enumerate(conts):
             if d is None:
                 ptrs[f], lens[f] = None, 0
-        if pad_mode is not None or fill is not None:
+        groups = list(groups) if groups is not None else []
+        padded = pad_mode is not None or fill is not None
+        if any(getattr(gr, "photo", None) is not None for gr in groups):  # (llcomp_mi_codec_decode_photo_views_host)
+            arr, n, _keep = _view_groups(groups, self.c, signed=padded)
+            photo, _keep_photo = _photo_groups(groups, [arr[i].n_views for i in range(n)])
+            pad, _keep_pad = _pad(self.c, pad_mode, fill) if padded else (None, None)
+            _check(self._L.llcomp_mi_codec_decode_photo_views_host(self._h, ptrs, lens, arr, n, C.byref(pad) if padded else None, photo, d_status,
+                                                                   stream))
+            return
+        if padded:
             arr, n, _keep = _view_groups(groups, self.c, signed=True)
             pad, _keep_pad = _pad(self.c, pad_mode, fill)
             _check(self._L.llcomp_mi_codec_decode_padded_views_host(self._h, ptrs, lens, arr, n, C.byref(pad), d_status, stream))
@@ -1248,7 +1364,12 @@ class Codec:
         """views under an affine map (llcomp_mi_codec_decode_warped_views): groups = WarpGroup objects; view v of a group -> d_out[v], byte
         for byte warp_reference of its frame (PIL's Image.transform(AFFINE)), mirrored and formatted as the other calls do.  A frame
         decodes once, and only the bounding box of the source pixels its views read; a frame without a view is not read."""
+        groups = list(groups) if groups is not None else []
         arr, n, _keep = _warp_groups(groups, self.c)
+        if any(getattr(gr, "photo", None) is not None for gr in groups):  # (llcomp_mi_codec_decode_photo_warped_views)
+            photo, _keep_photo = _photo_groups(groups, [arr[i].n_views for i in range(n)])
+            _check(self._L.llcomp_mi_codec_decode_photo_warped_views(self._h, d_payload, payload_bytes, d_slice_len, arr, n, photo, d_status, stream))
+            return
         _check(self._L.llcomp_mi_codec_decode_warped_views(self._h, d_payload, payload_bytes, d_slice_len, arr, n, d_status, stream))
 
     def decode_warped_views_host(self, containers, groups, d_status, stream=0):
@@ -1261,13 +1382,23 @@ class Codec:
         for f, d in enumerate(conts):
             if d is None:
                 ptrs[f], lens[f] = None, 0
+        groups = list(groups) if groups is not None else []
         arr, n, _keep = _warp_groups(groups, self.c)
+        if any(getattr(gr, "photo", None) is not None for gr in groups):  # (llcomp_mi_codec_decode_photo_warped_views_host)
+            photo, _keep_photo = _photo_groups(groups, [arr[i].n_views for i in range(n)])
+            _check(self._L.llcomp_mi_codec_decode_photo_warped_views_host(self._h, ptrs, lens, arr, n, photo, d_status, stream))
+            return
         _check(self._L.llcomp_mi_codec_decode_warped_views_host(self._h, ptrs, lens, arr, n, d_status, stream))
 
     def warp_workspace_bytes(self, total_views):
         """the bound on .allocated_bytes() for warped views calls of up to total_views views with outputs no larger than the image
         (llcomp_mi_codec_warp_workspace_bytes)"""
         return self._L.llcomp_mi_codec_warp_workspace_bytes(self._h, int(total_views))
+
+    def photo_workspace_bytes(self, total_views):
+        """the bound on .allocated_bytes() for views and warped views calls with photometric chains (a group with photo=) of up to
+        total_views views with outputs no larger than the image (llcomp_mi_codec_photo_workspace_bytes)"""
+        return self._L.llcomp_mi_codec_photo_workspace_bytes(self._h, int(total_views))
 
     def views_workspace_bytes(self, total_views):
         """.workspace_bytes for calls of up to total_views views (llcomp_mi_codec_views_workspace_bytes): the staged tables grow with them"""

@@ -44,6 +44,8 @@ SYMBOLS = [
     "llcomp_mi_codec_padded_workspace_bytes",
     "llcomp_mi_warp_source_rect", "llcomp_mi_warp_views_plan", "llcomp_mi_warp_reference", "llcomp_mi_codec_decode_warped_views",
     "llcomp_mi_codec_decode_warped_views_host", "llcomp_mi_codec_warp_workspace_bytes",
+    "llcomp_mi_photo_reference", "llcomp_mi_codec_decode_photo_views", "llcomp_mi_codec_decode_photo_views_host",
+    "llcomp_mi_codec_decode_photo_warped_views", "llcomp_mi_codec_decode_photo_warped_views_host", "llcomp_mi_codec_photo_workspace_bytes",
 ]
 
 u8p = C.POINTER(C.c_uint8)
@@ -86,6 +88,24 @@ class WarpGroup(C.Structure):
     """llcomp_mi_warp_group (include/llcomp_mi.h): 48 bytes, views at 8, fmt at 24, d_out at 32, fill at 40"""
     _fields_ = [("struct_size", C.c_uint32), ("n_views", C.c_uint32), ("views", C.POINTER(WarpView)), ("ow", C.c_uint32), ("oh", C.c_uint32),
                 ("fmt", C.POINTER(OutputFormat)), ("d_out", C.c_void_p), ("fill", u8p)]
+
+
+PHOTO_MAX_OPS = 8
+
+
+class PhotoOp(C.Structure):
+    """llcomp_mi_photo_op (include/llcomp_mi.h): 8 bytes"""
+    _fields_ = [("op", C.c_uint32), ("param", C.c_float)]
+
+
+class PhotoChain(C.Structure):
+    """llcomp_mi_photo_chain (include/llcomp_mi.h): 68 bytes"""
+    _fields_ = [("n_ops", C.c_uint32), ("ops", PhotoOp * PHOTO_MAX_OPS)]
+
+
+class PhotoGroup(C.Structure):
+    """llcomp_mi_photo_group (include/llcomp_mi.h): 16 bytes, chains at 8"""
+    _fields_ = [("struct_size", C.c_uint32), ("chains", C.POINTER(PhotoChain))]
 
 
 class Info(C.Structure):
@@ -382,6 +402,23 @@ def load():
         L.llcomp_mi_codec_decode_warped_views_host.argtypes = [C.c_void_p, ptrs, sizes, wgrp, C.c_uint32, C.c_void_p, C.c_void_p]
         L.llcomp_mi_codec_warp_workspace_bytes.restype = C.c_uint64
         L.llcomp_mi_codec_warp_workspace_bytes.argtypes = [C.c_void_p, C.c_uint64]
+    if "LLCOMP_MI_LIB" not in os.environ or hasattr(L, "llcomp_mi_photo_reference"):  # photometric chains
+        ptrs, sizes, padp = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(Pad)
+        grp, wgrp, pgrp = C.POINTER(ViewGroup), C.POINTER(WarpGroup), C.POINTER(PhotoGroup)
+        L.llcomp_mi_photo_reference.restype = C.c_int
+        L.llcomp_mi_photo_reference.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PhotoOp), C.c_uint32, C.c_void_p]
+        L.llcomp_mi_codec_decode_photo_views.restype = C.c_int
+        L.llcomp_mi_codec_decode_photo_views.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, grp, C.c_uint32, padp, pgrp, C.c_void_p,
+                                                         C.c_void_p]
+        L.llcomp_mi_codec_decode_photo_views_host.restype = C.c_int
+        L.llcomp_mi_codec_decode_photo_views_host.argtypes = [C.c_void_p, ptrs, sizes, grp, C.c_uint32, padp, pgrp, C.c_void_p, C.c_void_p]
+        L.llcomp_mi_codec_decode_photo_warped_views.restype = C.c_int
+        L.llcomp_mi_codec_decode_photo_warped_views.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, wgrp, C.c_uint32, pgrp, C.c_void_p,
+                                                                C.c_void_p]
+        L.llcomp_mi_codec_decode_photo_warped_views_host.restype = C.c_int
+        L.llcomp_mi_codec_decode_photo_warped_views_host.argtypes = [C.c_void_p, ptrs, sizes, wgrp, C.c_uint32, pgrp, C.c_void_p, C.c_void_p]
+        L.llcomp_mi_codec_photo_workspace_bytes.restype = C.c_uint64
+        L.llcomp_mi_codec_photo_workspace_bytes.argtypes = [C.c_void_p, C.c_uint64]
     if "LLCOMP_MI_LIB" not in os.environ and L.llcomp_mi_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.llcomp_mi_abi_version()}, this binding was written for {ABI_VERSION}: rebuild the library")
     _lib = L

@@ -16,6 +16,7 @@
 #include "container.hpp"
 #include "geometry.hpp"
 #include "kernels.hpp"
+#include "photo.hpp"
 #include "resize.hpp"
 #include "snapshot.hpp"
 #include "tables.hpp"
@@ -459,22 +460,50 @@ int regions_classes(llcomp_mi_codec* k, const RegionsClass* classes, uint32_t n_
     return LLCOMP_MI_OK;
 }
 
-// The resample passes of a tail, group by group and chunk by chunk, behind the classes: d_block is the tail's block in HBM.
-int windows_resample(llcomp_mi_codec* k, const WindowsPlan& p, const ResampleTail& tail, const uint8_t* d_block, hipStream_t s) {
+// The chains of views [at, at + cnt) of group pg, which lie in d_photo as U8 HWC: step by step on the stream, every view of the chunk
+// together (photo.hpp: launch_photo_step); a view's last step writes its place of the group's d_out through the group's format, whose
+// table lies at pg.table_at of d_tables.  d_chains: the call's block of chains in HBM.
+int windows_photo(llcomp_mi_codec* k, const PhotoTail& photo, const PhotoGroup& pg, const uint8_t* d_tables, const llcomp_mi_photo_chain* d_chains,
+                  uint32_t at, uint32_t cnt, hipStream_t s) {
+    const uint32_t c = k->g.c;
+    const uint64_t view_bytes = uint64_t(pg.oh) * pg.ow * c * pg.out.esize;
+    uint8_t* const d_luts = k->d_photo_tab + photo.tab_views * photo_stats_stride(c);
+    for (uint32_t step = 0; step < std::max(pg.steps, 1u); ++step)
+        HIP_TRY(launch_photo_step(k->d_photo, d_chains + pg.first + at, k->d_photo_tab, d_luts, d_tables + pg.table_at, pg.out,
+                                  static_cast<uint8_t*>(pg.d_out) + at * view_bytes, cnt, c, pg.ow, pg.oh, step, (pg.stats_steps >> step) & 1u,
+                                  (pg.table_steps >> step) & 1u, s));
+    return LLCOMP_MI_OK;
+}
+const PhotoGroup* photo_group(const PhotoTail* photo, size_t gi) { return photo && photo->groups[gi].active ? &photo->groups[gi] : nullptr; }
+
+// The resample passes of a tail, group by group and chunk by chunk, behind the classes: d_block is the tail's block in HBM.  A group
+// with photometric chains (photo, d_chains) writes plain U8 HWC into d_photo, pg->chunk views at a time, and windows_photo takes every
+// such chunk on to the group's output.
+int windows_resample(llcomp_mi_codec* k, const WindowsPlan& p, const ResampleTail& tail, const uint8_t* d_block, hipStream_t s,
+                     const PhotoTail* photo = nullptr, const llcomp_mi_photo_chain* d_chains = nullptr) {
     const Geometry& g = k->g;
     const ResizeFrame* d_rs = reinterpret_cast<const ResizeFrame*>(d_block);
     const int32_t* d_w = reinterpret_cast<const int32_t*>(d_block + tail.block.w_at());
     Timed t(k, s, 6);
-    for (const ResampleGroup& vg : tail.groups) {
+    for (size_t gi = 0; gi < tail.groups.size(); ++gi) {
+        const ResampleGroup& vg = tail.groups[gi];
+        const PhotoGroup* pg = photo_group(photo, gi);
         const uint64_t view_bytes = uint64_t(vg.oh) * vg.ow * g.c * vg.out.esize;
-        for (uint32_t at = 0; at < vg.n; at += vg.chunk) {
-            const uint32_t cnt = std::min(vg.chunk, vg.n - at);
-            // (a padded call with a constant fill other than 0: the bias forms for a chunk that has an entry with a bias, and only for it)
-            const std::vector<uint8_t>& biased = tail.block.biased;
-            const bool bias = !biased.empty() && std::any_of(biased.begin() + vg.first + at, biased.begin() + vg.first + at + cnt, [](uint8_t b) { return b != 0; });
-            if (bias) ++k->host_counters[LLCOMP_MI_CTR_BIAS_LAUNCHES];
-            HIP_TRY(launch_resize_out(k->d_box, k->d_mid, static_cast<uint8_t*>(vg.d_out) + at * view_bytes, d_rs + vg.first + at, d_w,
-                                      d_block + tail.block.tables_at() + vg.table_at, vg.out, cnt, g.c, p.wmax, p.hmax, vg.mh, vg.ow, vg.oh, s, bias));
+        const uint32_t pchunk = pg ? pg->chunk : vg.n;
+        for (uint32_t pa = 0; pa < vg.n; pa += pchunk) {
+            const uint32_t pend = pa + std::min(pchunk, vg.n - pa);
+            for (uint32_t at = pa; at < pend; at += vg.chunk) {
+                const uint32_t cnt = std::min(vg.chunk, pend - at);
+                // (a padded call with a constant fill other than 0: the bias forms for a chunk that has an entry with a bias, and only for it)
+                const std::vector<uint8_t>& biased = tail.block.biased;
+                const bool bias = !biased.empty() && std::any_of(biased.begin() + vg.first + at, biased.begin() + vg.first + at + cnt, [](uint8_t b) { return b != 0; });
+                if (bias) ++k->host_counters[LLCOMP_MI_CTR_BIAS_LAUNCHES];
+                uint8_t* const dst = pg ? k->d_photo + (at - pa) * view_bytes : static_cast<uint8_t*>(vg.d_out) + at * view_bytes;
+                HIP_TRY(launch_resize_out(k->d_box, k->d_mid, dst, d_rs + vg.first + at, d_w, d_block + tail.block.tables_at() + vg.table_at, vg.out, cnt,
+                                          g.c, p.wmax, p.hmax, vg.mh, vg.ow, vg.oh, s, bias));
+            }
+            if (pg)
+                if (int rc = windows_photo(k, *photo, *pg, d_block + tail.block.tables_at(), d_chains, pa, pend - pa, s)) return rc;
         }
     }
     return LLCOMP_MI_OK;
@@ -482,14 +511,26 @@ int windows_resample(llcomp_mi_codec* k, const WindowsPlan& p, const ResampleTai
 
 // The gather of a warp tail, group by group, behind the classes: d_block is the tail's block in HBM.  One launch per group, no
 // intermediate buffer; timed in slot 6 with the crops, like the resample passes.
-int windows_warp(llcomp_mi_codec* k, const WindowsPlan& p, const WarpTail& tail, const uint8_t* d_block, hipStream_t s) {
+// A group with photometric chains is gathered pg->chunk views at a time into d_photo as plain U8 HWC, as in windows_resample.
+int windows_warp(llcomp_mi_codec* k, const WindowsPlan& p, const WarpTail& tail, const uint8_t* d_block, hipStream_t s,
+                 const PhotoTail* photo = nullptr, const llcomp_mi_photo_chain* d_chains = nullptr) {
     const Geometry& g = k->g;
     const WarpEntry* d_ws = reinterpret_cast<const WarpEntry*>(d_block);
     const int32_t* d_tabs = reinterpret_cast<const int32_t*>(d_block + tail.tabs_at());
     Timed t(k, s, 6);
-    for (const WarpOut& vg : tail.groups)
-        HIP_TRY(launch_warp(k->d_box, d_ws + vg.first, d_tabs, d_block + tail.fills_at() + vg.fill_at, d_block + tail.tables_at() + vg.table_at, vg.out,
-                            vg.d_out, vg.n, g.c, p.wmax, p.hmax, g.w, g.h, vg.ow, vg.oh, s));
+    for (size_t gi = 0; gi < tail.groups.size(); ++gi) {
+        const WarpOut& vg = tail.groups[gi];
+        const PhotoGroup* pg = photo_group(photo, gi);
+        const uint32_t pchunk = pg ? pg->chunk : vg.n;
+        for (uint32_t pa = 0; pa < vg.n; pa += pchunk) {
+            const uint32_t cnt = std::min(pchunk, vg.n - pa);
+            HIP_TRY(launch_warp(k->d_box, d_ws + vg.first + pa, d_tabs, d_block + tail.fills_at() + vg.fill_at,
+                                d_block + tail.tables_at() + vg.table_at, vg.out, pg ? static_cast<void*>(k->d_photo) : vg.d_out, cnt, g.c, p.wmax,
+                                p.hmax, g.w, g.h, vg.ow, vg.oh, s));
+            if (pg)
+                if (int rc = windows_photo(k, *photo, *pg, d_block + tail.tables_at(), d_chains, pa, cnt, s)) return rc;
+        }
+    }
     return LLCOMP_MI_OK;
 }
 
@@ -530,13 +571,17 @@ int regions_plan(const llcomp_mi_codec* k, const uint32_t* xy, uint32_t rw, uint
 // a plain call from HBM in d_regions.  Each class takes a state generation of its own; for a source in HBM the full geometry's group
 // offsets are found once, ahead of the first class.  A third kind of tail (`warp`, in place of `tail`; warp_plan.hpp: WarpTail) carries the
 // block of a warped views decode in the same place of the copy and is gathered from the boxes by windows_warp; it has no d_mid.
+// `photo` (photo_plan.hpp: PhotoTail), beside either kind of tail: the views' photometric chains travel at the next multiple of 16
+// behind the tail's block, and the groups that have one go through d_photo (windows_photo).
 int decode_windows(llcomp_mi_codec* k, const WindowsPlan& p, const ResampleTail* tail, uint64_t tables_bound, const WindowsSource& src, void* d_px,
-                   void* d_status, void* stream, const WarpTail* warp = nullptr) {
+                   void* d_status, void* stream, const WarpTail* warp = nullptr, const PhotoTail* photo = nullptr) {
     const Geometry& g = k->g;
     const RegionsGather* gp = src.gather;
     const CopyLayout cl(p.tab.size(), gp, tail);
     const StageLayout& lay = cl.stage;
-    const uint64_t rs_at = cl.rs_at, bytes = warp ? rs_at + warp->bytes() : cl.bytes;
+    // (photometric chains, behind either kind of tail: the block of chains at the next multiple of 16)
+    const uint64_t rs_at = cl.rs_at, tail_end = warp ? rs_at + warp->bytes() : cl.bytes, photo_at = (tail_end + 15) & ~15ull;
+    const uint64_t bytes = photo ? photo_at + photo->bytes() : tail_end;
     const bool any_tail = tail || warp;
     const bool table_only = !gp && !any_tail;
     const uint64_t bound = table_only ? 0 : stage_bound(g) + tables_bound;
@@ -552,6 +597,11 @@ int decode_windows(llcomp_mi_codec* k, const WindowsPlan& p, const ResampleTail*
         if (int rc = ensure_grown(k, k->d_box, k->box_cap, tail ? tail->box_bytes : warp->box_bytes, samples)) return rc;
         if (tail)
             if (int rc = ensure_grown(k, k->d_mid, k->mid_cap, tail->mid_bytes, samples)) return rc;
+        if (photo) {
+            const uint64_t tab_bytes = photo->tab_views * (photo_stats_stride(g.c) + photo_lut_stride(g.c));
+            if (int rc = ensure_grown(k, k->d_photo, k->photo_cap, photo->stage_bytes, samples)) return rc;
+            if (int rc = ensure_grown(k, k->d_photo_tab, k->photo_tab_cap, tab_bytes, tab_bytes)) return rc;
+        }
     }
     uint32_t slot = 0;
     if (int rc = regions_slot_take(k, bytes, bound, slot)) return rc;
@@ -560,6 +610,10 @@ int decode_windows(llcomp_mi_codec* k, const WindowsPlan& p, const ResampleTail*
     if (gp) regions_gather_copy(*gp, src.data, h + lay.pay_at, reinterpret_cast<uint32_t*>(h + lay.len_at), reinterpret_cast<uint64_t*>(h + lay.off_at));
     if (tail) tail->block.put(h + rs_at);
     if (warp) warp->put(h + rs_at);
+    if (photo) {
+        std::memset(h + tail_end, 0, size_t(photo_at - tail_end));
+        photo->put(h + photo_at);
+    }
     hipStream_t s = static_cast<hipStream_t>(stream);
     uint8_t* const d_copy = table_only ? reinterpret_cast<uint8_t*>(k->d_regions) : k->d_stage;
     DoneGuard done_guard{k, s};
@@ -581,10 +635,11 @@ int decode_windows(llcomp_mi_codec* k, const WindowsPlan& p, const ResampleTail*
     if (int rc = regions_classes(k, p.classes, p.n_classes, reinterpret_cast<const RegionsFrame*>(d_copy), from, p.wmax, p.hmax,
                                  any_tail ? k->d_box : static_cast<uint8_t*>(d_px), static_cast<uint32_t*>(d_status), s))
         return rc;
+    const llcomp_mi_photo_chain* d_chains = photo ? reinterpret_cast<const llcomp_mi_photo_chain*>(k->d_stage + photo_at) : nullptr;
     if (tail)
-        if (int rc = windows_resample(k, p, *tail, k->d_stage + rs_at, s)) return rc;
+        if (int rc = windows_resample(k, p, *tail, k->d_stage + rs_at, s, photo, d_chains)) return rc;
     if (warp)
-        if (int rc = windows_warp(k, p, *warp, k->d_stage + rs_at, s)) return rc;
+        if (int rc = windows_warp(k, p, *warp, k->d_stage + rs_at, s, photo, d_chains)) return rc;
     ++k->n_decode;
     return LLCOMP_MI_OK;
 }
@@ -718,6 +773,8 @@ void codec_release(llcomp_mi_codec* k) {
     dev_free(k->d_stage, k->done);
     dev_free(k->d_box, k->done);
     dev_free(k->d_mid, k->done);
+    dev_free(k->d_photo, k->done);
+    dev_free(k->d_photo_tab, k->done);
     dev_free(k->d_upd_goff, k->done);
     for (uint32_t i = 0; i < llcomp_mi_codec::kRegionsRing; ++i) {
         if (!k->h_regions[i]) continue;
@@ -1326,6 +1383,119 @@ int llcomp_mi_codec_decode_warped_views_host(llcomp_mi_codec* k, const uint8_t* 
     if (!gather_matches(p, gp)) return LLCOMP_MI_HIP_ERROR;
     return decode_windows(k, p, nullptr, warp_tables_bound(k->g, p.total_views), WindowsSource{nullptr, 0, nullptr, data, &gp}, nullptr, d_status,
                           stream, &p.tail);
+}
+
+// The photometric calls: the plan of the call they extend, then the chains beside its groups (photo_plan.hpp: photo_setup).  A group
+// with a chain hands its output -- format, table and d_out -- over to the chain's last step and becomes a plain U8 HWC group whose
+// output is the staging buffer (windows_resample / windows_warp put the address in); with no chain at all the extended call runs as it is.
+}  // extern "C"
+
+namespace {
+
+template <class Group>
+int photo_tail_of(const Geometry& g, std::vector<Group>& groups, const llcomp_mi_photo_group* photo, PhotoTail& pt) {
+    std::vector<uint32_t> n, ow, oh;
+    for (const Group& gr : groups) {
+        n.push_back(gr.n);
+        ow.push_back(gr.ow);
+        oh.push_back(gr.oh);
+    }
+    if (int rc = photo_setup(g.c, uint64_t(g.frames) * g.w * g.h * g.c, photo, uint32_t(groups.size()), n.data(), ow.data(), oh.data(), pt)) return rc;
+    for (size_t i = 0; i < groups.size(); ++i) {
+        PhotoGroup& pg = pt.groups[i];
+        if (!pg.active) continue;
+        pg.out = groups[i].out;
+        pg.d_out = groups[i].d_out;
+        pg.table_at = groups[i].table_at;
+        groups[i].out = OutFormat{};
+        groups[i].d_out = nullptr;
+        groups[i].table_at = 0;
+    }
+    return LLCOMP_MI_OK;
+}
+
+// dev: the batch in HBM, or null for host containers (data, lens)
+int photo_views(llcomp_mi_codec* k, const WindowsSource* dev, const uint8_t* const* data, const size_t* lens, const llcomp_mi_view_group* groups,
+                       uint32_t n_groups, const llcomp_mi_pad* pad, const llcomp_mi_photo_group* photo, void* d_status, void* stream) {
+    ViewsPlan p;
+    if (int rc = pad ? padded_views_setup(k->g, k->tune, groups, n_groups, pad, p) : views_setup(k->g, k->tune, groups, n_groups, p)) return rc;
+    PhotoTail pt;
+    if (int rc = photo_tail_of(k->g, p.tail.groups, photo, pt)) return rc;
+    const uint64_t bound = (pad ? padded_tables_bound(k->g, p.u.total_views) : views_tables_bound(k->g, p.u.total_views)) +
+                           (pt.any() ? photo_tables_bound(p.u.total_views) : 0);
+    RegionsGather gp;
+    if (!dev) {
+        if (int rc = regions_gather_plan_sized(data, lens, k->g.frames, p.u.rects.data(), p.wmax, p.hmax, gp, p.u.used.data(), uint32_t(p.u.used.size())))
+            return rc;
+        if (!same_shape(k->g, gp.g)) return LLCOMP_MI_BAD_ARGS;
+        if (!gather_matches(p, gp)) return LLCOMP_MI_HIP_ERROR;
+    }
+    return decode_windows(k, p, &p.tail, bound, dev ? *dev : WindowsSource{nullptr, 0, nullptr, data, &gp}, nullptr, d_status, stream, nullptr,
+                          pt.any() ? &pt : nullptr);
+}
+
+int photo_warped_views(llcomp_mi_codec* k, const WindowsSource* dev, const uint8_t* const* data, const size_t* lens,
+                              const llcomp_mi_warp_group* groups, uint32_t n_groups, const llcomp_mi_photo_group* photo, void* d_status, void* stream) {
+    WarpPlan p;
+    if (int rc = warp_setup(k->g, k->tune, groups, n_groups, p)) return rc;
+    PhotoTail pt;
+    if (int rc = photo_tail_of(k->g, p.tail.groups, photo, pt)) return rc;
+    const uint64_t bound = warp_tables_bound(k->g, p.total_views) + (pt.any() ? photo_tables_bound(p.total_views) : 0);
+    RegionsGather gp;
+    if (!dev) {
+        if (!p.u.used.empty()) {
+            if (int rc = regions_gather_plan_sized(data, lens, k->g.frames, p.u.rects.data(), p.wmax, p.hmax, gp, p.u.used.data(), uint32_t(p.u.used.size())))
+                return rc;
+            if (!same_shape(k->g, gp.g)) return LLCOMP_MI_BAD_ARGS;
+        }
+        if (!gather_matches(p, gp)) return LLCOMP_MI_HIP_ERROR;
+    }
+    return decode_windows(k, p, nullptr, bound, dev ? *dev : WindowsSource{nullptr, 0, nullptr, data, &gp}, nullptr, d_status, stream, &p.tail,
+                          pt.any() ? &pt : nullptr);
+}
+
+}  // namespace
+
+extern "C" {
+
+int llcomp_mi_codec_decode_photo_views(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                       const llcomp_mi_view_group* groups, uint32_t n_groups, const llcomp_mi_pad* pad,
+                                       const llcomp_mi_photo_group* photo, void* d_status, void* stream) {
+    if (!k || !d_payload || !d_slice_len || !d_status) return LLCOMP_MI_BAD_ARGS;
+    if (misaligned(d_slice_len, 4) || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
+    const WindowsSource dev{d_payload, payload_bytes, d_slice_len, nullptr, nullptr};
+    return photo_views(k, &dev, nullptr, nullptr, groups, n_groups, pad, photo, d_status, stream);
+}
+
+int llcomp_mi_codec_decode_photo_views_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens,
+                                            const llcomp_mi_view_group* groups, uint32_t n_groups, const llcomp_mi_pad* pad,
+                                            const llcomp_mi_photo_group* photo, void* d_status, void* stream) {
+    if (!k || !data || !lens || !d_status || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
+    return photo_views(k, nullptr, data, lens, groups, n_groups, pad, photo, d_status, stream);
+}
+
+int llcomp_mi_codec_decode_photo_warped_views(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                              const llcomp_mi_warp_group* groups, uint32_t n_groups, const llcomp_mi_photo_group* photo,
+                                              void* d_status, void* stream) {
+    if (!k || !d_payload || !d_slice_len || !d_status) return LLCOMP_MI_BAD_ARGS;
+    if (misaligned(d_slice_len, 4) || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
+    const WindowsSource dev{d_payload, payload_bytes, d_slice_len, nullptr, nullptr};
+    return photo_warped_views(k, &dev, nullptr, nullptr, groups, n_groups, photo, d_status, stream);
+}
+
+int llcomp_mi_codec_decode_photo_warped_views_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens,
+                                                   const llcomp_mi_warp_group* groups, uint32_t n_groups, const llcomp_mi_photo_group* photo,
+                                                   void* d_status, void* stream) {
+    if (!k || !data || !lens || !d_status || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
+    return photo_warped_views(k, nullptr, data, lens, groups, n_groups, photo, d_status, stream);
+}
+
+uint64_t llcomp_mi_codec_photo_workspace_bytes(const llcomp_mi_codec* k, uint64_t total_views) {
+    if (!k) return 0;
+    const Geometry& g = k->g;
+    const uint64_t views = std::max<uint64_t>(total_views, 1);
+    return std::max(llcomp_mi_codec_padded_workspace_bytes(k, total_views), llcomp_mi_codec_warp_workspace_bytes(k, total_views)) +
+           uint64_t(g.frames) * g.w * g.h * g.c + views * (photo_stats_stride(g.c) + photo_lut_stride(g.c)) + photo_tables_bound(total_views);
 }
 
 uint64_t llcomp_mi_codec_warp_workspace_bytes(const llcomp_mi_codec* k, uint64_t total_views) {

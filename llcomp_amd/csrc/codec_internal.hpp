@@ -56,6 +56,13 @@ struct llcomp_mi_codec {
     uint64_t box_cap = 0;
     uint8_t* d_mid = nullptr;
     uint64_t mid_cap = 0;
+    // photometric chains (llcomp_mi_codec_decode_photo_views / _photo_warped_views): the staging buffer a group with chains is resampled
+    // or warped into as U8 HWC, a chunk of views at a time, grown like d_mid and never past frames * w * h * c for outputs no larger than
+    // the image; and the statistics (u64 + c * 256 u32 per view) and tables (c * 256 bytes per view) of the largest chunk's views
+    uint8_t* d_photo = nullptr;
+    uint64_t photo_cap = 0;
+    uint8_t* d_photo_tab = nullptr;
+    uint64_t photo_tab_cap = 0;
     // region update (llcomp_mi_codec_encode_region / _update_region): the encoder runs on the box's sub-geometry, which can have MORE lane
     // groups than the full one, so its group offsets go to an array of their own, u64[n_slices + 1]; behind it, u64[lane groups + 1], the
     // full geometry's group offsets for the NEW table (d_group_off holds the old table's).  The decoded box shares d_box with the resized

@@ -1,0 +1,112 @@
+// photo_plan.cpp -- the host planner of the photometric chains (photo_plan.hpp) and llcomp_mi_photo_reference.  Plain C++, no GPU.
+#include "photo_plan.hpp"
+
+#include <algorithm>
+#include <cstring>
+
+#include "photo_rule.hpp"
+
+namespace llcomp_mi {
+
+uint64_t photo_tables_bound(uint64_t total_views) { return 16 + std::max<uint64_t>(total_views, 1) * sizeof(llcomp_mi_photo_chain); }
+
+void PhotoTail::put(uint8_t* at) const {
+    if (!chains.empty()) std::memcpy(at, chains.data(), chains.size() * sizeof(llcomp_mi_photo_chain));
+}
+
+int photo_check_chain(const llcomp_mi_photo_chain& ch, uint32_t c) {
+    if (ch.n_ops > LLCOMP_MI_PHOTO_MAX_OPS) return LLCOMP_MI_BAD_ARGS;
+    if (ch.n_ops && c != 1 && c != 3) return LLCOMP_MI_BAD_ARGS;
+    for (uint32_t k = 0; k < ch.n_ops; ++k)
+        if (!photo_op_ok(ch.ops[k].op, ch.ops[k].param)) return LLCOMP_MI_BAD_ARGS;
+    return LLCOMP_MI_OK;
+}
+
+int photo_setup(uint32_t c, uint64_t samples, const llcomp_mi_photo_group* photo, uint32_t n_groups, const uint32_t* n_views, const uint32_t* ow,
+                const uint32_t* oh, PhotoTail& t) {
+    t = PhotoTail{};
+    t.groups.resize(n_groups);
+    if (!photo) return LLCOMP_MI_OK;
+    for (uint32_t gi = 0; gi < n_groups; ++gi) {
+        const llcomp_mi_photo_group& pg = photo[gi];
+        if (pg.struct_size != sizeof(llcomp_mi_photo_group)) return LLCOMP_MI_BAD_ARGS;
+        if (!pg.chains) continue;
+        PhotoGroup& g = t.groups[gi];
+        for (uint32_t i = 0; i < n_views[gi]; ++i) {
+            const llcomp_mi_photo_chain& ch = pg.chains[i];
+            if (int rc = photo_check_chain(ch, c)) return rc;
+            g.steps = std::max(g.steps, ch.n_ops);
+            for (uint32_t k = 0; k < ch.n_ops; ++k) {
+                if (photo_needs_stats(ch.ops[k].op)) g.stats_steps |= 1u << k;
+                if (photo_is_table(ch.ops[k].op)) g.table_steps |= 1u << k;
+            }
+        }
+        if (!g.steps) continue;  // (every chain empty: the group takes the extended call's path)
+        g.active = true;
+        g.n = n_views[gi];
+        g.ow = ow[gi];
+        g.oh = oh[gi];
+        g.first = uint32_t(t.chains.size());
+        for (uint32_t i = 0; i < g.n; ++i) {
+            llcomp_mi_photo_chain ch;
+            std::memset(&ch, 0, sizeof ch);  // (what lies behind a chain's ops does not travel)
+            ch.n_ops = pg.chains[i].n_ops;
+            std::memcpy(ch.ops, pg.chains[i].ops, ch.n_ops * sizeof(llcomp_mi_photo_op));
+            t.chains.push_back(ch);
+        }
+        const uint64_t per_view = uint64_t(g.oh) * g.ow * c;
+        g.chunk = uint32_t(std::min<uint64_t>(g.n, std::max<uint64_t>(samples / std::max<uint64_t>(per_view, 1), 1)));
+        t.stage_bytes = std::max(t.stage_bytes, g.chunk * per_view);
+        t.tab_views = std::max<uint64_t>(t.tab_views, g.chunk);
+    }
+    return LLCOMP_MI_OK;
+}
+
+int photo_reference(const uint8_t* src, uint32_t w, uint32_t h, uint32_t c, const llcomp_mi_photo_op* ops, uint32_t n_ops, uint8_t* out) {
+    if (!src || !out || !w || !h || (c != 1 && c != 3) || (n_ops && !ops) || n_ops > LLCOMP_MI_PHOTO_MAX_OPS) return LLCOMP_MI_BAD_ARGS;
+    for (uint32_t k = 0; k < n_ops; ++k)
+        if (!photo_op_ok(ops[k].op, ops[k].param)) return LLCOMP_MI_BAD_ARGS;
+    const uint64_t n = uint64_t(w) * h;
+    if (out != src) std::memmove(out, src, size_t(n * c));
+    std::vector<uint32_t> hist(size_t(256) * c);
+    for (uint32_t k = 0; k < n_ops; ++k) {
+        const uint32_t op = ops[k].op;
+        const float a = ops[k].param;
+        if (!photo_is_table(op)) {
+            if (c != 3) continue;
+            for (uint64_t i = 0; i < n; ++i) {
+                uint8_t* p = out + 3 * i;
+                uint32_t r = p[0], g = p[1], b = p[2];
+                if (op == LLCOMP_MI_PHOTO_COLOR)
+                    photo_color(r, g, b, a);
+                else
+                    photo_grayscale(r, g, b);
+                p[0] = uint8_t(r);
+                p[1] = uint8_t(g);
+                p[2] = uint8_t(b);
+            }
+            continue;
+        }
+        uint64_t sum_l = 0;
+        if (photo_needs_stats(op)) {
+            std::fill(hist.begin(), hist.end(), 0u);
+            for (uint64_t i = 0; i < n; ++i) {
+                const uint8_t* p = out + c * i;
+                for (uint32_t ch = 0; ch < c; ++ch) ++hist[256 * ch + p[ch]];
+                sum_l += c == 3 ? photo_luma(p[0], p[1], p[2]) : p[0];
+            }
+        }
+        uint8_t lut[3][256];
+        for (uint32_t ch = 0; ch < c; ++ch) photo_table(op, a, hist.data() + 256 * ch, sum_l, n, lut[ch]);
+        for (uint64_t i = 0; i < n; ++i)
+            for (uint32_t ch = 0; ch < c; ++ch) out[c * i + ch] = lut[ch][out[c * i + ch]];
+    }
+    return LLCOMP_MI_OK;
+}
+
+}  // namespace llcomp_mi
+
+extern "C" int llcomp_mi_photo_reference(const uint8_t* src, uint32_t w, uint32_t h, uint32_t c, const llcomp_mi_photo_op* ops, uint32_t n_ops,
+                                         uint8_t* out) {
+    return llcomp_mi::photo_reference(src, w, h, c, ops, n_ops, out);
+}

@@ -1,0 +1,56 @@
+// photo_plan.hpp -- the host half of the photometric chains (include/llcomp_mi.h: llcomp_mi_codec_decode_photo_views /
+// _photo_warped_views): the limits, which groups run chains, how their views are chunked through the staging buffer, which steps need a
+// statistics or a table launch, and the block of chains the call's one copy carries behind its tail's block.  Plain C++
+// (photo_plan.cpp), like windows_plan.cpp: it builds and runs under a host sanitizer (tests/helpers/photo_plan_check.cpp).  The rule
+// itself: photo_rule.hpp.  The driver: codec.hip, windows_photo.
+#pragma once
+#include <cstdint>
+#include <vector>
+
+#include "../../include/llcomp_mi.h"
+#include "resize_plan.hpp"
+
+namespace llcomp_mi {
+
+// What a view's statistics take in HBM: the sum of L as u64, then c histograms of 256 u32 ...
+inline uint64_t photo_stats_stride(uint32_t c) { return 8 + 1024 * uint64_t(c); }
+// ... and its table, [c][256] u8
+inline uint64_t photo_lut_stride(uint32_t c) { return 256 * uint64_t(c); }
+
+// One group of the call.  active: some view has a chain that is not empty -- the group's tail entry then writes plain U8 HWC into the
+// staging buffer, `chunk` views at a time, and the chain's last step writes d_out in format `out` through the table at table_at of the
+// tail's output tables (all three taken over from the tail's group).  first: the group's chains in the block.  steps: the longest chain.
+// Bit k of stats_steps / table_steps: some view's op k needs the statistics pass / is a table.
+struct PhotoGroup {
+    bool active = false;
+    uint32_t n = 0, ow = 0, oh = 0, first = 0, chunk = 0, steps = 0, stats_steps = 0, table_steps = 0;
+    OutFormat out;
+    void* d_out = nullptr;
+    uint64_t table_at = 0;
+};
+// The chains' part of a call: the block -- llcomp_mi_photo_chain per view of every ACTIVE group, group by group -- and what the driver
+// allocates: the staging buffer (the largest chunk's U8 HWC views) and the statistics and tables of the largest chunk's views.
+struct PhotoTail {
+    std::vector<llcomp_mi_photo_chain> chains;
+    std::vector<PhotoGroup> groups;  // one per group of the call
+    uint64_t stage_bytes = 0, tab_views = 0;
+    bool any() const { return !chains.empty(); }
+    uint64_t bytes() const { return uint64_t(chains.size()) * sizeof(llcomp_mi_photo_chain); }
+    void put(uint8_t* at) const;
+};
+// What the chains add to a call's one copy at most: 16 bytes of alignment and one chain per view
+uint64_t photo_tables_bound(uint64_t total_views);
+
+// The limits of one chain on a codec of c channels: OK, or BAD_ARGS for more than LLCOMP_MI_PHOTO_MAX_OPS ops, an unknown op, a
+// parameter outside its limits, and any op at all where c is neither 1 nor 3.
+int photo_check_chain(const llcomp_mi_photo_chain& ch, uint32_t c);
+// Everything of the chains the host decides.  photo: n_groups entries or null; n_views / ow / oh: per group of the call.  samples: the
+// staging buffer's bound, frames * w * h * c -- a group of more views than fit is chunked, and one view always goes through.
+// BAD_ARGS: a struct_size that is not the struct's, and photo_check_chain's cases.
+int photo_setup(uint32_t c, uint64_t samples, const llcomp_mi_photo_group* photo, uint32_t n_groups, const uint32_t* n_views, const uint32_t* ow,
+                const uint32_t* oh, PhotoTail& t);
+
+// The rule on a host image: src [h][w][c] -> out [h][w][c] (out may be src).
+int photo_reference(const uint8_t* src, uint32_t w, uint32_t h, uint32_t c, const llcomp_mi_photo_op* ops, uint32_t n_ops, uint8_t* out);
+
+}  // namespace llcomp_mi

@@ -4,6 +4,7 @@
 // llcomp_mi_warp_reference runs on the host -- in binary64 with NO fused multiply-add: the header's pragma holds for this whole file.
 #include "warp_rule.hpp"
 
+#include "out_store.hpp"
 #include "warp.hpp"
 
 #if defined(__clang__)
@@ -13,11 +14,6 @@
 namespace llcomp_mi {
 
 namespace {
-
-template <int E> struct WarpElem;
-template <> struct WarpElem<1> { using T = uint8_t; };
-template <> struct WarpElem<2> { using T = uint16_t; };
-template <> struct WarpElem<4> { using T = uint32_t; };
 
 // Workgroups of 16 x 16 output pixels (blockIdx.x: the tile, row-major; blockIdx.y: the view), so that the taps of a rotated tile stay
 // close together in the box.  C: the channel count where it is 1..4 (the loops over channels unroll), 0 for any other (c_rt).  LUT: the
@@ -29,7 +25,7 @@ template <int C, int E, bool CHW, bool LUT>
 __global__ __launch_bounds__(256) void k_warp(const uint8_t* __restrict__ box, const WarpEntry* __restrict__ ws, const int32_t* __restrict__ tabs,
                                               const uint8_t* __restrict__ fill, const void* __restrict__ table, void* __restrict__ out, uint32_t bw,
                                               uint32_t bh, uint32_t w, uint32_t h, uint32_t ow, uint32_t oh, uint32_t c_rt) {
-    using T = typename WarpElem<E>::T;
+    using T = typename OutElem<E>::T;
     const uint32_t c = C ? uint32_t(C) : c_rt;
     const uint32_t tiles_x = ow / 16 + (ow % 16 != 0), v = blockIdx.y, ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
     const uint32_t x = tx * 16 + threadIdx.x, y = ty * 16 + threadIdx.y;
@@ -40,13 +36,7 @@ __global__ __launch_bounds__(256) void k_warp(const uint8_t* __restrict__ box, c
     const size_t plane = size_t(oh) * ow, px = size_t(y) * ow + xo;
     T* const o = static_cast<T*>(out);
     const T* const lut = static_cast<const T*>(table);
-    auto put = [&](uint32_t ch, uint32_t val) {
-        const T el = LUT ? lut[ch * 256 + val] : T(val);
-        if constexpr (CHW)
-            o[(size_t(v) * c + ch) * plane + px] = el;
-        else
-            o[(size_t(v) * plane + px) * c + ch] = el;
-    };
+    auto put = [&](uint32_t ch, uint32_t val) { out_store<T, CHW, LUT>(o, lut, v, c, plane, px, ch, val); };
     const uint8_t* const b = box + size_t(e.box) * bh * bw * c;
     const int32_t bx = e.bx, by = e.by;
     auto at = [&](int32_t row, int32_t col) {
