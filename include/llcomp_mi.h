@@ -447,8 +447,9 @@ int llcomp_mi_warp_views_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_
  * calls; it is not fast.  BAD_ARGS, out untouched: a NULL src, m or out, a side or c of 0, and the rule's limits.  Host-only. */
 int llcomp_mi_warp_reference(const uint8_t* src, uint32_t w, uint32_t h, uint32_t c, const double* m, uint32_t filter, const uint8_t* fill,
                              uint32_t ow, uint32_t oh, uint8_t* out);
-/* Photometric chains (llcomp_mi_codec_decode_photo_views / _photo_warped_views below: torchvision's ColorJitter without hue,
- * RandomGrayscale, and the colour ops of RandAugment / AutoAugment / TrivialAugment, PIL backend).  A PHOTO CHAIN is 0 to
+/* Photometric chains (llcomp_mi_codec_decode_photo_views / _photo_warped_views below: torchvision's ColorJitter with hue,
+ * RandomGrayscale, PIL's GaussianBlur as the DINO and MoCo recipes apply it, and the colour ops of RandAugment / AutoAugment /
+ * TrivialAugment, PIL backend).  A PHOTO CHAIN is 0 to
  * LLCOMP_MI_PHOTO_MAX_OPS ops {op, param}, applied in order to one view.
  * THE RULE.  The chain's input is what the call it extends writes for that view as U8 HWC: after the resample or the warp, and after the
  * mirror bit (every op commutes with the mirror: "mirror, then chain" is PIL's "flip, then jitter" and the reverse order alike).  The
@@ -472,11 +473,37 @@ int llcomp_mi_warp_reference(const uint8_t* src, uint32_t w, uint32_t h, uint32_
  *   EQUALIZE    -  per channel, from its histogram h over the view: fewer than two values present leave the channel unchanged;
  *                  step = (n - h[last value present]) / 255 in integers, and step == 0 leaves it unchanged; otherwise acc = step / 2 and
  *                  for i = 0..255: lut[i] = min(255, acc / step), then acc += h[i]                ImageOps.equalize
+ *   GAUSSIAN_BLUR radius  ImageFilter.GaussianBlur(radius): three box passes along every row, each reading the bytes the pass before
+ *                  it wrote, then three along every column; every channel by itself; the window is symmetric, so the op commutes with
+ *                  the mirror.  "f32": every operation rounded to binary32.
+ *                  The box radius fr, f32: s2 = radius * radius / 3; L = (float)sqrt((double)(12 * s2 + 1)); l = floor((L - 1) / 2);
+ *                    a = ((2l + 1) * (l * (l + 1) - 3 * s2)) / (6 * (s2 - (l + 1) * (l + 1))); fr = l + a
+ *                    (radius 1 gives 0.25000003, radius 2 gives 1.375, radius 12 gives 11.479167).
+ *                  The weights: r = (int)fr; ww = (uint32)((float)(1 << 24) / (fr * 2 + 1)), the division in f32;
+ *                    fw = (uint32)((1 << 24) - (2r + 1) * ww) / 2, in wrapping uint32.
+ *                  One pass over a line in[0..n-1], cl(i) = min(max(i, 0), n - 1): acc(x) = sum over k = -r..r of in[cl(x + k)];
+ *                    far(x) = in[cl(x - r - 1)] + in[cl(x + r + 1)]; out[x] = (uint8)((acc * ww + far * fw + (1 << 23)) >> 24), in
+ *                    wrapping uint32.  Radius 0 is the identity (r = 0, ww = 2^24, fw = 0).
+ *   ADJUST_HUE  f  torchvision's adjust_hue(hue_factor = f), PIL backend; identity for c = 1.  shift = (uint8)(int32)((double)f * 255.0),
+ *                  truncated toward zero, then mod 256; per pixel (H, S, V) = PIL's convert("HSV"), H = (H + shift) & 255, the pixel =
+ *                  PIL's convert("RGB") of that.
+ *                  RGB -> HSV: V = max; max == min gives H = S = 0; otherwise, f32: cr = max - min; s = cr / max;
+ *                    rc, gc, bc = (max - r | g | b) / cr; h, in binary64 from these and then stored to f32: bc - gc where r is the max,
+ *                    else (2.0 + rc) - bc where g is, else (4.0 + gc) - rc; h = (float)fmod((double)h / 6.0 + 1.0, 1.0);
+ *                    H = clip8((int)((double)h * 255.0)); S = clip8((int)((double)s * 255.0)).
+ *                  HSV -> RGB: S == 0 gives r = g = b = V; otherwise, in binary64 on f32 values: hh = (double)(float)H * 6.0 / 255.0;
+ *                    i = floor(hh); f = (float)(hh - (float)i); fs = (float)((float)S / 255.0); p = round(V * (1.0 - fs));
+ *                    q = round(V * (1.0 - fs * f)); t = round(V * (1.0 - fs * (1.0 - f))), round C's (halves away from zero), each
+ *                    clipped to 0..255; i % 6 selects (V,t,p), (q,V,p), (p,V,t), (p,q,V), (t,p,V), (V,p,q).  No fused multiply-add.
  * LIMITS (BAD_ARGS): a factor a that is not finite or not within 0..256; a threshold t that is not an integer within 0..256; bits b
- * that are not an integer within 1..8; an unknown op code; more than LLCOMP_MI_PHOTO_MAX_OPS ops; and a chain that is not empty on a
- * codec whose c is neither 1 nor 3 (PIL's L and RGB).  The parameter of an op that takes none is ignored.
- * NOT COVERED: hue (PIL's HSV round trip), sharpness and blur (neighbourhood filters: ImageEnhance.Sharpness, GaussianBlur), alpha. */
+ * that are not an integer within 1..8; a radius that is not finite or not within 0..LLCOMP_MI_PHOTO_MAX_RADIUS; a hue factor that is not
+ * finite or not within -0.5..0.5; an unknown op code (9..15 among them); more than LLCOMP_MI_PHOTO_MAX_OPS ops; and a chain that is not
+ * empty on a codec whose c is neither 1 nor 3 (PIL's L and RGB).  The parameter of an op that takes none is ignored.  Views of any
+ * width and height may blur: there is no side limit.
+ * NOT COVERED: sharpness (PIL's 3 x 3 SMOOTH blended in: ImageEnhance.Sharpness), torchvision's tensor-path GaussianBlur (a float
+ * convolution: another rule), alpha. */
 #define LLCOMP_MI_PHOTO_MAX_OPS 8
+#define LLCOMP_MI_PHOTO_MAX_RADIUS 32
 enum {
     LLCOMP_MI_PHOTO_BRIGHTNESS = 0,
     LLCOMP_MI_PHOTO_CONTRAST = 1,
@@ -487,7 +514,9 @@ enum {
     LLCOMP_MI_PHOTO_POSTERIZE = 6,
     LLCOMP_MI_PHOTO_AUTOCONTRAST = 7,
     LLCOMP_MI_PHOTO_EQUALIZE = 8,
-    LLCOMP_MI_PHOTO_OP_COUNT = 9
+    LLCOMP_MI_PHOTO_OP_COUNT = 9, /* the count of the pointwise family 0..8; codes 9..15 are no op */
+    LLCOMP_MI_PHOTO_GAUSSIAN_BLUR = 16,
+    LLCOMP_MI_PHOTO_ADJUST_HUE = 17
 };
 typedef struct llcomp_mi_photo_op {
     uint32_t op; /* LLCOMP_MI_PHOTO_* */

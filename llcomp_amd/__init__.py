@@ -63,6 +63,11 @@ PAD_NAMES = ("constant", "edge", "reflect", "symmetric")
  PHOTO_EQUALIZE) = range(9)
 PHOTO_MAX_OPS = 8
 PHOTO_NAMES = ("brightness", "contrast", "color", "grayscale", "invert", "solarize", "posterize", "autocontrast", "equalize")
+# the two ops outside the pointwise family 0..8, under torchvision's functional names: PIL's ImageFilter.GaussianBlur(radius) and
+# adjust_hue(hue_factor)
+PHOTO_GAUSSIAN_BLUR, PHOTO_ADJUST_HUE = 16, 17
+PHOTO_MAX_RADIUS = 32
+PHOTO_MORE_NAMES = {"gaussian_blur": PHOTO_GAUSSIAN_BLUR, "adjust_hue": PHOTO_ADJUST_HUE}
 
 RawImage = namedtuple("RawImage", "pixels width height channels")
 
@@ -389,7 +394,8 @@ class ViewGroup:
     dtype, layout, scale, mean and std give (as Codec.decode_resized_regions takes them); filter: one name or FILTER_* code for every view
     of the group, or one per view, OR-ed into bits 4-6 of the views' flags.  A plain tuple (views, ow, oh, d_out) is a group too.
     photo: a photometric chain for every view of the group -- a list of (op, param) or (name, param) pairs or bare names, such as
-    [("brightness", 1.2), "grayscale"] -- or a list of one chain per view (photo_chain); None: none."""
+    [("brightness", 1.2), ("adjust_hue", 0.05), "grayscale", ("gaussian_blur", 1.5)] -- or a list of one chain per view (photo_chain);
+    None: none."""
 
     def __init__(self, views, ow, oh, d_out=0, dtype=None, layout="hwc", scale=False, mean=None, std=None, filter=None, photo=None):
         self.views, self.ow, self.oh, self.d_out = views, ow, oh, d_out
@@ -400,11 +406,13 @@ class ViewGroup:
 
 def photo_code(op):
     """PHOTO_* code of an op given by name ("brightness", "contrast", "color" or "saturation", "grayscale", "invert", "solarize",
-    "posterize", "autocontrast", "equalize") or by code"""
+    "posterize", "autocontrast", "equalize", "gaussian_blur", "adjust_hue") or by code"""
     if isinstance(op, str):
         name = "color" if op.lower() == "saturation" else op.lower()
+        if name in PHOTO_MORE_NAMES:
+            return PHOTO_MORE_NAMES[name]
         if name not in PHOTO_NAMES:
-            raise LlcompError(BAD_ARGS, f"no photometric op {op!r}: one of {PHOTO_NAMES}")
+            raise LlcompError(BAD_ARGS, f"no photometric op {op!r}: one of {PHOTO_NAMES + tuple(PHOTO_MORE_NAMES)}")
         return PHOTO_NAMES.index(name)
     code = int(op)
     if not 0 <= code <= 0xFFFFFFFF:
@@ -470,7 +478,8 @@ def _photo_groups(groups, n_views):
 
 def photo_reference(frame, ops):
     """The rule of the photometric chains on a host image (llcomp_mi_photo_reference): frame [h, w] or [h, w, c] uint8 with c = 1 or 3,
-    ops a chain as photo_chain takes it -> the image after the chain, byte for byte PIL's ImageEnhance / ImageOps applied in order."""
+    ops a chain as photo_chain takes it -> the image after the chain, byte for byte PIL's ImageEnhance / ImageOps / ImageFilter.GaussianBlur
+    and torchvision's adjust_hue applied in order."""
     a = np.ascontiguousarray(frame, dtype=np.uint8)
     if a.ndim not in (2, 3) or not a.size:
         raise LlcompError(BAD_ARGS, f"a frame is [h, w] or [h, w, c], got shape {a.shape}")

@@ -471,7 +471,7 @@ int windows_photo(llcomp_mi_codec* k, const PhotoTail& photo, const PhotoGroup& 
     for (uint32_t step = 0; step < std::max(pg.steps, 1u); ++step)
         HIP_TRY(launch_photo_step(k->d_photo, d_chains + pg.first + at, k->d_photo_tab, d_luts, d_tables + pg.table_at, pg.out,
                                   static_cast<uint8_t*>(pg.d_out) + at * view_bytes, cnt, c, pg.ow, pg.oh, step, (pg.stats_steps >> step) & 1u,
-                                  (pg.table_steps >> step) & 1u, s));
+                                  (pg.table_steps >> step) & 1u, (pg.area_steps >> step) & 1u, s));
     return LLCOMP_MI_OK;
 }
 const PhotoGroup* photo_group(const PhotoTail* photo, size_t gi) { return photo && photo->groups[gi].active ? &photo->groups[gi] : nullptr; }

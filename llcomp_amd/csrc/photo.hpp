@@ -14,9 +14,11 @@ namespace llcomp_mi {
 // table in device memory, aligned to the element size, and d_out is aligned to it too); a view whose chain has ended sits out.
 // stats: some view's op of this step reads statistics -- d_stats (views * photo_stats_stride(c) bytes, 8-byte aligned) is zeroed on the
 // stream and filled by k_photo_stats first.  table: some view's op is a table -- k_photo_lut builds d_luts (views *
-// photo_lut_stride(c) bytes) from the parameters and d_stats.  c is 1 or 3.
+// photo_lut_stride(c) bytes) from the parameters and d_stats.  area: some view's op is the blur -- those views sit out of the per-pixel
+// pass, and k_photo_blur_rows and k_photo_blur_cols run them, three passes each inside LDS and in place on d_px (the column kernel
+// writes d_out where the blur ends the chain): no buffer beside d_px, and a view of any width and height.  c is 1 or 3.
 hipError_t launch_photo_step(uint8_t* d_px, const llcomp_mi_photo_chain* d_chains, void* d_stats, uint8_t* d_luts, const void* d_table,
                              const OutFormat& o, void* d_out, uint32_t views, uint32_t c, uint32_t ow, uint32_t oh, uint32_t step, bool stats,
-                             bool table, hipStream_t stream);
+                             bool table, bool area, hipStream_t stream);
 
 }  // namespace llcomp_mi

@@ -1,7 +1,8 @@
-// photo_kernels.hip -- the three kernels of the photometric chains (llcomp_mi_codec_decode_photo_views / _photo_warped_views): the
-// statistics of every view whose op of the step reads them, the table of every view whose op is one, and the per-pixel pass.  All views
-// of a chunk run a step together; nothing goes back to the host in between.  The arithmetic is photo_rule.hpp's -- the functions
-// llcomp_mi_photo_reference runs on the host -- with NO fused multiply-add: the header's pragma holds for this whole file.
+// photo_kernels.hip -- the kernels of the photometric chains (llcomp_mi_codec_decode_photo_views / _photo_warped_views): the
+// statistics of every view whose op of the step reads them, the table of every view whose op is one, the per-pixel pass, and the row
+// and the column kernel of the views whose op is the blur.  All views of a chunk run a step together; nothing goes back to the host in
+// between.  The arithmetic is photo_rule.hpp's -- the functions llcomp_mi_photo_reference runs on the host -- with NO fused
+// multiply-add: the header's pragma holds for this whole file.
 #include "photo_rule.hpp"
 
 #include "out_store.hpp"
@@ -99,8 +100,9 @@ __global__ __launch_bounds__(64) void k_photo_lut(const llcomp_mi_photo_chain* _
 }
 
 // The per-pixel pass: blockIdx.y the view, a workgroup takes 1024 of its pixels.  A table op looks every channel up in the view's table
-// (copied to LDS), COLOR and GRAYSCALE are computed from the pixel, the step of an empty chain changes nothing.  The value goes back in
-// place, or -- the chain's last step -- through the group's output format to `out`.  E, CHW, LUT as in the gather of the warped views.
+// (copied to LDS), COLOR, GRAYSCALE and ADJUST_HUE are computed from the pixel, the step of an empty chain changes nothing, and a view
+// whose op is the blur sits out: k_photo_blur_rows and k_photo_blur_cols run it.  The value goes back in place, or -- the chain's
+// last step -- through the group's output format to `out`.  E, CHW, LUT as in the gather of the warped views.
 template <int C, int E, bool CHW, bool LUT>
 __global__ __launch_bounds__(256) void k_photo_apply(uint8_t* __restrict__ px, const llcomp_mi_photo_chain* __restrict__ chains,
                                                      const uint8_t* __restrict__ luts, const void* __restrict__ table, void* __restrict__ out,
@@ -112,7 +114,9 @@ __global__ __launch_bounds__(256) void k_photo_apply(uint8_t* __restrict__ px, c
     float param;
     bool last;
     if (!photo_step_op(chains[v], step, op, param, last)) return;  // (the whole workgroup alike)
+    if (op != kPhotoNoOp && photo_is_area(op)) return;             // (the blur kernels' view in this step)
     const bool tab = op != kPhotoNoOp && photo_is_table(op);
+    const uint32_t shift = op == LLCOMP_MI_PHOTO_ADJUST_HUE ? photo_hue_shift(param) : 0u;
     if (tab) {
         for (uint32_t j = threadIdx.x; j < uint32_t(C * 256); j += 256) s_lut[j] = luts[size_t(v) * (C * 256) + j];
         __syncthreads();
@@ -131,6 +135,8 @@ __global__ __launch_bounds__(256) void k_photo_apply(uint8_t* __restrict__ px, c
                 photo_color(s[0], s[1], s[2], param);
             else if (op == LLCOMP_MI_PHOTO_GRAYSCALE)
                 photo_grayscale(s[0], s[1], s[2]);
+            else if (op == LLCOMP_MI_PHOTO_ADJUST_HUE)
+                photo_hue(s[0], s[1], s[2], shift);
         }
         if (last) {
             for (int ch = 0; ch < C; ++ch) out_store<T, CHW, LUT>(o, lut, v, C, npix, i, ch, s[ch]);
@@ -138,6 +144,175 @@ __global__ __launch_bounds__(256) void k_photo_apply(uint8_t* __restrict__ px, c
             for (int ch = 0; ch < C; ++ch) p[i * C + ch] = uint8_t(s[ch]);
         }
     }
+}
+
+// The blur (LLCOMP_MI_PHOTO_GAUSSIAN_BLUR): three box passes along every row, then three along every column, each kernel with its
+// three passes inside LDS and IN PLACE on px -- lines of one direction do not read each other.  A line, or a piece of one, lies in
+// LDS with at most kBlurLine samples.  A longer line is done in pieces of kBlurSeg output samples, one after the other by the same
+// workgroup: a piece is loaded with photo_blur_reach(r) <= kBlurHalo samples to each side, every pass clamps its taps to the piece, so
+// that what a cut end spoils -- r + 1 samples per pass -- stays inside the halo, and a true end of the line is clamped as the rule
+// says.  The samples the piece's store overwrites, and the next pieces still have to read as they were, stay behind in s_keep.
+constexpr uint32_t kBlurLine = 256;                        // samples of a line in LDS, halo included
+constexpr uint32_t kBlurHalo = 3 * (LLCOMP_MI_PHOTO_MAX_RADIUS + 1);  // 99
+constexpr uint32_t kBlurSeg = kBlurLine - 2 * kBlurHalo;   // 58
+constexpr uint32_t kBlurRowSlots = 1024;                   // pixels of the row kernel's tile: as many rows (pieces) as fit
+constexpr uint32_t kBlurStrip = 32;                        // byte columns of the column kernel's tile
+static_assert(kBlurSeg >= 1 && kBlurRowSlots % kBlurLine == 0 && kBlurStrip % 4 == 0, "the blur's tiles");
+
+// the pieces of a line of n samples: their count, and piece `seg` as outputs [s, e) inside loaded samples [lo, hi)
+__host__ __device__ inline uint32_t blur_pieces(uint32_t n) { return n <= kBlurLine ? 1u : (n + kBlurSeg - 1) / kBlurSeg; }
+__device__ __forceinline__ void blur_piece(uint32_t n, uint32_t seg, uint32_t reach, uint32_t& s, uint32_t& e, uint32_t& lo, uint32_t& hi) {
+    if (n <= kBlurLine) {
+        s = lo = 0;
+        e = hi = n;
+        return;
+    }
+    s = seg * kBlurSeg;
+    e = s + kBlurSeg < n ? s + kBlurSeg : n;
+    lo = s > reach ? s - reach : 0u;
+    hi = n - e > reach ? e + reach : n;
+}
+// rows of a view the row kernel's workgroup takes: as many as fit, a multiple of its four wavefronts
+__host__ __device__ inline uint32_t blur_rows_per_group(uint32_t ow) { return (kBlurRowSlots / (ow < kBlurLine ? ow : kBlurLine)) & ~3u; }
+
+// Rows: blockIdx.y the view, a workgroup takes blur_rows_per_group(ow) whole rows of it, wavefront w the rows w, w + 4, ...  Lane per
+// byte: byte b of a row's piece is channel b % C of sample b / C, and its taps lie C bytes apart.
+template <int C>
+__global__ __launch_bounds__(256) void k_photo_blur_rows(uint8_t* __restrict__ px, const llcomp_mi_photo_chain* __restrict__ chains, uint32_t ow,
+                                                         uint32_t oh, uint32_t step) {
+    __shared__ uint8_t s_a[kBlurRowSlots * C], s_b[kBlurRowSlots * C], s_keep[(kBlurRowSlots / kBlurLine) * kBlurHalo * C];
+    const uint32_t v = blockIdx.y;
+    uint32_t op;
+    float param;
+    bool last;
+    if (!photo_step_op(chains[v], step, op, param, last) || op == kPhotoNoOp || !photo_is_area(op)) return;  // (the whole workgroup alike)
+    uint32_t r, ww, fw;
+    photo_blur_weights(param, r, ww, fw);
+    const uint32_t reach = photo_blur_reach(r);
+    const uint32_t rows = blur_rows_per_group(ow), row0 = blockIdx.x * rows;
+    const uint32_t nrows = oh - row0 < rows ? oh - row0 : rows;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const size_t pitch = size_t(ow) * C;
+    uint8_t* const p = px + (size_t(v) * oh + row0) * pitch;
+    const uint32_t pieces = blur_pieces(ow);
+    for (uint32_t seg = 0; seg < pieces; ++seg) {
+        uint32_t s, e, lo, hi;
+        blur_piece(ow, seg, reach, s, e, lo, hi);
+        const uint32_t len = hi - lo, lb = len * C;  // (len <= kBlurLine, nrows * len <= kBlurRowSlots)
+        const uint32_t kb = (s - lo) * C;            // bytes of a row that come from s_keep
+        for (uint32_t row = wave; row < nrows; row += 4)
+            for (uint32_t b = lane; b < lb; b += 64)
+                s_a[row * lb + b] = seg && b < kb ? s_keep[row * (kBlurHalo * C) + b] : p[row * pitch + size_t(lo) * C + b];
+        __syncthreads();
+        if (seg + 1 < pieces) {  // what the next piece reads below its own outputs: [e - reach, e) as it is now
+            const uint32_t klo = e > reach ? e - reach : 0u, kl = (e - klo) * C;
+            for (uint32_t row = wave; row < nrows; row += 4)
+                for (uint32_t b = lane; b < kl; b += 64) s_keep[row * (kBlurHalo * C) + b] = s_a[row * lb + (klo - lo) * C + b];
+        }
+        for (int pass = 0; pass < 3; ++pass) {
+            const uint8_t* const src = pass == 1 ? s_b : s_a;
+            uint8_t* const dst = pass == 1 ? s_a : s_b;
+            for (uint32_t row = wave; row < nrows; row += 4)
+                for (uint32_t b = lane; b < lb; b += 64) {
+                    const int32_t x = int32_t(b / C), ch = int32_t(b) - x * C, top = int32_t(len) - 1;
+                    const uint8_t* const line = src + row * lb + ch;
+                    uint32_t acc = 0;
+                    for (int32_t k = x - int32_t(r); k <= x + int32_t(r); ++k) acc += line[(k < 0 ? 0 : (k > top ? top : k)) * C];
+                    const int32_t fl = x - int32_t(r) - 1, fh = x + int32_t(r) + 1;
+                    const uint32_t far = uint32_t(line[(fl < 0 ? 0 : fl) * C]) + line[(fh > top ? top : fh) * C];
+                    dst[row * lb + b] = uint8_t(photo_blur_tap(acc, far, ww, fw));
+                }
+            __syncthreads();
+        }
+        const uint32_t ob = (e - s) * C;
+        for (uint32_t row = wave; row < nrows; row += 4)
+            for (uint32_t b = lane; b < ob; b += 64) p[row * pitch + size_t(s) * C + b] = s_b[row * lb + kb + b];
+    }
+}
+
+// Columns: blockIdx.y the view, a workgroup takes a strip of kBlurStrip adjacent byte columns of it -- one row of the strip is one
+// contiguous run of bytes in HBM -- held as [rows][kBlurStrip] in LDS.  In the passes a thread takes FOUR adjacent columns as one
+// dword: a wavefront reads 64 consecutive dwords (eight rows of the strip), every bank once in each half, where a thread per byte
+// column would read a byte per lane.  The four sums ride in two registers as 16-bit fields (67 samples of 255 at most).  The strip is
+// narrow because a view has few of them and a workgroup walks its strip's whole height: 32 columns gave 25 us per launch where 64
+// gave 38 (DESIGN.md "Blur and hue").  The chain's last step stores through the group's output table and layout to `out`
+// (out_store.hpp), as k_photo_apply does; E, CHW, LUT as there.
+template <int C, int E, bool CHW, bool LUT>
+__global__ __launch_bounds__(256) void k_photo_blur_cols(uint8_t* __restrict__ px, const llcomp_mi_photo_chain* __restrict__ chains,
+                                                         const void* __restrict__ table, void* __restrict__ out, uint32_t ow, uint32_t oh,
+                                                         uint32_t step) {
+    using T = typename OutElem<E>::T;
+    constexpr uint32_t W4 = kBlurStrip / 4;
+    __shared__ uint32_t s_a[kBlurLine * W4], s_b[kBlurLine * W4], s_keep[kBlurHalo * W4];
+    const uint32_t v = blockIdx.y;
+    uint32_t op;
+    float param;
+    bool last;
+    if (!photo_step_op(chains[v], step, op, param, last) || op == kPhotoNoOp || !photo_is_area(op)) return;  // (the whole workgroup alike)
+    uint32_t r, ww, fw;
+    photo_blur_weights(param, r, ww, fw);
+    const uint32_t reach = photo_blur_reach(r);
+    const size_t pitch = size_t(ow) * C, plane = size_t(oh) * ow;
+    const size_t col0 = size_t(blockIdx.x) * kBlurStrip;
+    const uint32_t sw = pitch - col0 < kBlurStrip ? uint32_t(pitch - col0) : kBlurStrip;  // the strip's byte columns
+    uint8_t* const p = px + size_t(v) * plane * C + col0;
+    uint8_t* const a8 = reinterpret_cast<uint8_t*>(s_a);
+    uint8_t* const k8 = reinterpret_cast<uint8_t*>(s_keep);
+    const uint8_t* const b8 = reinterpret_cast<const uint8_t*>(s_b);
+    T* const o = static_cast<T*>(out);
+    const T* const lut = static_cast<const T*>(table);
+    const uint32_t pieces = blur_pieces(oh);
+    for (uint32_t seg = 0; seg < pieces; ++seg) {
+        uint32_t s, e, lo, hi;
+        blur_piece(oh, seg, reach, s, e, lo, hi);
+        const uint32_t len = hi - lo;  // (<= kBlurLine)
+        for (uint32_t j = threadIdx.x; j < len * kBlurStrip; j += 256) {
+            const uint32_t row = j / kBlurStrip, col = j % kBlurStrip;
+            if (col < sw) a8[j] = seg && lo + row < s ? k8[j] : p[(size_t(lo) + row) * pitch + col];
+        }
+        __syncthreads();
+        if (seg + 1 < pieces) {  // what the next piece reads above its own outputs: rows [e - reach, e) as they are now
+            const uint32_t klo = e > reach ? e - reach : 0u;
+            for (uint32_t j = threadIdx.x; j < (e - klo) * W4; j += 256) s_keep[j] = s_a[(klo - lo) * W4 + j];
+        }
+        for (int pass = 0; pass < 3; ++pass) {
+            const uint32_t* const src = pass == 1 ? s_b : s_a;
+            uint32_t* const dst = pass == 1 ? s_a : s_b;
+            for (uint32_t j = threadIdx.x; j < len * W4; j += 256) {
+                const int32_t y = int32_t(j / W4), top = int32_t(len) - 1;
+                const uint32_t* const line = src + j % W4;
+                uint32_t even = 0, odd = 0;  // the sums of bytes 0 and 2, and of bytes 1 and 3, as two 16-bit fields each
+                for (int32_t k = y - int32_t(r); k <= y + int32_t(r); ++k) {
+                    const uint32_t d = line[(k < 0 ? 0 : (k > top ? top : k)) * W4];
+                    even += d & 0x00FF00FFu;
+                    odd += (d >> 8) & 0x00FF00FFu;
+                }
+                const int32_t fl = y - int32_t(r) - 1, fh = y + int32_t(r) + 1;
+                const uint32_t d0 = line[(fl < 0 ? 0 : fl) * W4], d1 = line[(fh > top ? top : fh) * W4];
+                const uint32_t feven = (d0 & 0x00FF00FFu) + (d1 & 0x00FF00FFu), fodd = ((d0 >> 8) & 0x00FF00FFu) + ((d1 >> 8) & 0x00FF00FFu);
+                dst[j] = photo_blur_tap(even & 0xFFFFu, feven & 0xFFFFu, ww, fw) | photo_blur_tap(odd & 0xFFFFu, fodd & 0xFFFFu, ww, fw) << 8 |
+                         photo_blur_tap(even >> 16, feven >> 16, ww, fw) << 16 | photo_blur_tap(odd >> 16, fodd >> 16, ww, fw) << 24;
+            }
+            __syncthreads();
+        }
+        for (uint32_t j = threadIdx.x; j < (e - s) * kBlurStrip; j += 256) {
+            const uint32_t row = j / kBlurStrip, col = j % kBlurStrip;
+            if (col >= sw) continue;
+            const uint32_t val = b8[(s - lo + row) * kBlurStrip + col];
+            if (last) {
+                const size_t bx = col0 + col, x = bx / C;
+                out_store<T, CHW, LUT>(o, lut, v, C, plane, (size_t(s) + row) * ow + x, uint32_t(bx - x * C), val);
+            } else {
+                p[(size_t(s) + row) * pitch + col] = uint8_t(val);
+            }
+        }
+    }
+}
+
+template <int C, int E, bool CHW, bool LUT>
+void launch_blur_cols(dim3 grid, hipStream_t s, uint8_t* d_px, const llcomp_mi_photo_chain* d_chains, const void* d_table, void* d_out, uint32_t ow,
+                      uint32_t oh, uint32_t step) {
+    k_photo_blur_cols<C, E, CHW, LUT><<<grid, dim3(256), 0, s>>>(d_px, d_chains, d_table, d_out, ow, oh, step);
 }
 
 template <int C, int E, bool CHW, bool LUT>
@@ -148,7 +323,9 @@ void launch_apply(dim3 grid, hipStream_t s, uint8_t* d_px, const llcomp_mi_photo
 
 template <int C>
 hipError_t launch_step_c(uint8_t* d_px, const llcomp_mi_photo_chain* d_chains, uint8_t* d_stats, uint8_t* d_luts, const void* d_table,
-                         const OutFormat& o, void* d_out, uint32_t views, uint64_t npix, uint32_t step, bool stats, bool table, hipStream_t s) {
+                         const OutFormat& o, void* d_out, uint32_t views, uint32_t ow, uint32_t oh, uint32_t step, bool stats, bool table, bool area,
+                         hipStream_t s) {
+    const uint64_t npix = uint64_t(oh) * ow;
     if (stats) {
         if (hipError_t err = hipMemsetAsync(d_stats, 0, size_t(views) * photo_stats_stride(C), s)) return err;
         // (4096 pixels per workgroup and round, at most 32 workgroups per view: a 224 x 224 view takes 13)
@@ -168,6 +345,20 @@ hipError_t launch_step_c(uint8_t* d_px, const llcomp_mi_photo_chain* d_chains, u
     else
         chw ? LLMI_PHOTO(4, true, true) : LLMI_PHOTO(4, false, true);
 #undef LLMI_PHOTO
+    if (area) {  // the views that blur in this step sat the pass above out: rows in place, then columns, in place or to d_out
+        k_photo_blur_rows<C><<<dim3((oh + blur_rows_per_group(ow) - 1) / blur_rows_per_group(ow), views), dim3(256), 0, s>>>(d_px, d_chains, ow, oh, step);
+        const dim3 cols(uint32_t((uint64_t(ow) * C + kBlurStrip - 1) / kBlurStrip), views);
+#define LLMI_PHOTO(E, CHW, LUT) launch_blur_cols<C, E, CHW, LUT>(cols, s, d_px, d_chains, d_table, d_out, ow, oh, step)
+        if (o.plain)
+            LLMI_PHOTO(1, false, false);
+        else if (o.esize == 1)
+            LLMI_PHOTO(1, true, true);
+        else if (o.esize == 2)
+            chw ? LLMI_PHOTO(2, true, true) : LLMI_PHOTO(2, false, true);
+        else
+            chw ? LLMI_PHOTO(4, true, true) : LLMI_PHOTO(4, false, true);
+#undef LLMI_PHOTO
+    }
     return hipGetLastError();
 }
 
@@ -175,7 +366,7 @@ hipError_t launch_step_c(uint8_t* d_px, const llcomp_mi_photo_chain* d_chains, u
 
 hipError_t launch_photo_step(uint8_t* d_px, const llcomp_mi_photo_chain* d_chains, void* d_stats, uint8_t* d_luts, const void* d_table,
                              const OutFormat& o, void* d_out, uint32_t views, uint32_t c, uint32_t ow, uint32_t oh, uint32_t step, bool stats,
-                             bool table, hipStream_t stream) {
+                             bool table, bool area, hipStream_t stream) {
     if (!views || views > 65535 || (c != 1 && c != 3) || !ow || !oh || step >= LLCOMP_MI_PHOTO_MAX_OPS) return hipErrorInvalidValue;
     if (!d_px || !d_chains || !d_out || (reinterpret_cast<uintptr_t>(d_chains) & 3u)) return hipErrorInvalidValue;
     if ((stats || table) && (!d_stats || !d_luts || (reinterpret_cast<uintptr_t>(d_stats) & 7u))) return hipErrorInvalidValue;
@@ -183,9 +374,10 @@ hipError_t launch_photo_step(uint8_t* d_px, const llcomp_mi_photo_chain* d_chain
     if (reinterpret_cast<uintptr_t>(d_out) & (o.esize - 1)) return hipErrorInvalidValue;
     const uint64_t npix = uint64_t(oh) * ow;
     if ((npix + 1023) / 1024 > 0x7FFFFFFFull) return hipErrorInvalidValue;  // (an output of 2^41 pixels: no buffer holds it)
+    if (area && uint64_t(ow) * c > 0x7FFFFFFFull * kBlurStrip) return hipErrorInvalidValue;  // (the column kernel's grid; a row of 2^37 bytes)
     uint8_t* st = static_cast<uint8_t*>(d_stats);
-    return c == 3 ? launch_step_c<3>(d_px, d_chains, st, d_luts, d_table, o, d_out, views, npix, step, stats, table, stream)
-                  : launch_step_c<1>(d_px, d_chains, st, d_luts, d_table, o, d_out, views, npix, step, stats, table, stream);
+    return c == 3 ? launch_step_c<3>(d_px, d_chains, st, d_luts, d_table, o, d_out, views, ow, oh, step, stats, table, area, stream)
+                  : launch_step_c<1>(d_px, d_chains, st, d_luts, d_table, o, d_out, views, ow, oh, step, stats, table, area, stream);
 }
 
 }  // namespace llcomp_mi

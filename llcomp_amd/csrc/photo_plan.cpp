@@ -39,6 +39,7 @@ int photo_setup(uint32_t c, uint64_t samples, const llcomp_mi_photo_group* photo
             for (uint32_t k = 0; k < ch.n_ops; ++k) {
                 if (photo_needs_stats(ch.ops[k].op)) g.stats_steps |= 1u << k;
                 if (photo_is_table(ch.ops[k].op)) g.table_steps |= 1u << k;
+                if (photo_is_area(ch.ops[k].op)) g.area_steps |= 1u << k;
             }
         }
         if (!g.steps) continue;  // (every chain empty: the group takes the extended call's path)
@@ -62,6 +63,20 @@ int photo_setup(uint32_t c, uint64_t samples, const llcomp_mi_photo_group* photo
     return LLCOMP_MI_OK;
 }
 
+namespace {
+// One box pass over the line p[0], p[stride], ..., p[(n - 1) * stride], in place through tmp[n]
+void blur_line(uint8_t* p, uint32_t n, uint64_t stride, uint32_t r, uint32_t ww, uint32_t fw, uint8_t* tmp) {
+    const int64_t last = int64_t(n) - 1;
+    auto at = [&](int64_t i) -> uint32_t { return p[uint64_t(i < 0 ? 0 : (i > last ? last : i)) * stride]; };
+    for (int64_t x = 0; x <= last; ++x) {
+        uint32_t acc = 0;
+        for (int64_t k = -int64_t(r); k <= int64_t(r); ++k) acc += at(x + k);
+        tmp[x] = uint8_t(photo_blur_tap(acc, at(x - int64_t(r) - 1) + at(x + int64_t(r) + 1), ww, fw));
+    }
+    for (int64_t x = 0; x <= last; ++x) p[uint64_t(x) * stride] = tmp[x];
+}
+}  // namespace
+
 int photo_reference(const uint8_t* src, uint32_t w, uint32_t h, uint32_t c, const llcomp_mi_photo_op* ops, uint32_t n_ops, uint8_t* out) {
     if (!src || !out || !w || !h || (c != 1 && c != 3) || (n_ops && !ops) || n_ops > LLCOMP_MI_PHOTO_MAX_OPS) return LLCOMP_MI_BAD_ARGS;
     for (uint32_t k = 0; k < n_ops; ++k)
@@ -69,16 +84,32 @@ int photo_reference(const uint8_t* src, uint32_t w, uint32_t h, uint32_t c, cons
     const uint64_t n = uint64_t(w) * h;
     if (out != src) std::memmove(out, src, size_t(n * c));
     std::vector<uint32_t> hist(size_t(256) * c);
+    std::vector<uint8_t> line;
     for (uint32_t k = 0; k < n_ops; ++k) {
         const uint32_t op = ops[k].op;
         const float a = ops[k].param;
+        if (photo_is_area(op)) {
+            uint32_t r, ww, fw;
+            photo_blur_weights(a, r, ww, fw);
+            line.resize(std::max(w, h));
+            for (int pass = 0; pass < 3; ++pass)  // along every row
+                for (uint64_t y = 0; y < h; ++y)
+                    for (uint32_t ch = 0; ch < c; ++ch) blur_line(out + y * w * c + ch, w, c, r, ww, fw, line.data());
+            for (int pass = 0; pass < 3; ++pass)  // along every column
+                for (uint64_t x = 0; x < w; ++x)
+                    for (uint32_t ch = 0; ch < c; ++ch) blur_line(out + x * c + ch, h, uint64_t(w) * c, r, ww, fw, line.data());
+            continue;
+        }
         if (!photo_is_table(op)) {
             if (c != 3) continue;
+            const uint32_t shift = op == LLCOMP_MI_PHOTO_ADJUST_HUE ? photo_hue_shift(a) : 0u;
             for (uint64_t i = 0; i < n; ++i) {
                 uint8_t* p = out + 3 * i;
                 uint32_t r = p[0], g = p[1], b = p[2];
                 if (op == LLCOMP_MI_PHOTO_COLOR)
                     photo_color(r, g, b, a);
+                else if (op == LLCOMP_MI_PHOTO_ADJUST_HUE)
+                    photo_hue(r, g, b, shift);
                 else
                     photo_grayscale(r, g, b);
                 p[0] = uint8_t(r);

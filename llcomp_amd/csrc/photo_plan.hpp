@@ -20,10 +20,11 @@ inline uint64_t photo_lut_stride(uint32_t c) { return 256 * uint64_t(c); }
 // One group of the call.  active: some view has a chain that is not empty -- the group's tail entry then writes plain U8 HWC into the
 // staging buffer, `chunk` views at a time, and the chain's last step writes d_out in format `out` through the table at table_at of the
 // tail's output tables (all three taken over from the tail's group).  first: the group's chains in the block.  steps: the longest chain.
-// Bit k of stats_steps / table_steps: some view's op k needs the statistics pass / is a table.
+// Bit k of stats_steps / table_steps / area_steps: some view's op k needs the statistics pass / is a table / is the blur, which the
+// row and column kernels run in place of the per-pixel pass.
 struct PhotoGroup {
     bool active = false;
-    uint32_t n = 0, ow = 0, oh = 0, first = 0, chunk = 0, steps = 0, stats_steps = 0, table_steps = 0;
+    uint32_t n = 0, ow = 0, oh = 0, first = 0, chunk = 0, steps = 0, stats_steps = 0, table_steps = 0, area_steps = 0;
     OutFormat out;
     void* d_out = nullptr;
     uint64_t table_at = 0;

@@ -33,12 +33,15 @@ LLMI_HD inline uint32_t photo_blend(uint32_t d, uint32_t v, float a) {
 LLMI_HD inline bool photo_needs_stats(uint32_t op) {
     return op == LLCOMP_MI_PHOTO_CONTRAST || op == LLCOMP_MI_PHOTO_AUTOCONTRAST || op == LLCOMP_MI_PHOTO_EQUALIZE;
 }
-// ... and the ops that are one table per channel (every op but the two that mix channels)
+// ... and the ops that are one table per channel (every op of the pointwise family 0..8 but the two that mix channels)
 LLMI_HD inline bool photo_is_table(uint32_t op) {
     return op < LLCOMP_MI_PHOTO_OP_COUNT && op != LLCOMP_MI_PHOTO_COLOR && op != LLCOMP_MI_PHOTO_GRAYSCALE;
 }
+// ... and the op whose output sample reads other samples of the view: it has kernels of its own (photo_kernels.hip: k_photo_blur_*)
+LLMI_HD inline bool photo_is_area(uint32_t op) { return op == LLCOMP_MI_PHOTO_GAUSSIAN_BLUR; }
 
-// the limits of one op: finite factors within 0..256, an integer threshold within 0..256, integer bits within 1..8
+// the limits of one op: finite factors within 0..256, an integer threshold within 0..256, integer bits within 1..8, a finite radius
+// within 0..LLCOMP_MI_PHOTO_MAX_RADIUS, a finite hue factor within -0.5..0.5
 LLMI_HD inline bool photo_op_ok(uint32_t op, float param) {
     switch (op) {
         case LLCOMP_MI_PHOTO_BRIGHTNESS:
@@ -50,6 +53,8 @@ LLMI_HD inline bool photo_op_ok(uint32_t op, float param) {
         case LLCOMP_MI_PHOTO_INVERT:
         case LLCOMP_MI_PHOTO_AUTOCONTRAST:
         case LLCOMP_MI_PHOTO_EQUALIZE: return true;
+        case LLCOMP_MI_PHOTO_GAUSSIAN_BLUR: return param >= 0.0f && param <= float(LLCOMP_MI_PHOTO_MAX_RADIUS);
+        case LLCOMP_MI_PHOTO_ADJUST_HUE: return param >= -0.5f && param <= 0.5f;
         default: return false;
     }
 }
@@ -134,5 +139,82 @@ LLMI_HD inline void photo_color(uint32_t& r, uint32_t& g, uint32_t& b, float a) 
     b = photo_blend(l, b, a);
 }
 LLMI_HD inline void photo_grayscale(uint32_t& r, uint32_t& g, uint32_t& b) { r = g = b = photo_luma(r, g, b); }
+
+// GAUSSIAN_BLUR: the box of ImageFilter.GaussianBlur(radius) with three passes -- r its whole radius, ww the weight of the 2r + 1
+// samples inside, fw that of the two samples at r + 1, in units of 2^-24.  Binary32 throughout but the square root.
+LLMI_HD inline void photo_blur_weights(float radius, uint32_t& r, uint32_t& ww, uint32_t& fw) {
+    const float s2 = radius * radius / 3.0f;
+    const float big_l = float(sqrt(double(12.0f * s2 + 1.0f)));
+    const float l = floorf((big_l - 1.0f) / 2.0f);
+    const float num = (2.0f * l + 1.0f) * (l * (l + 1.0f) - 3.0f * s2);
+    const float den = 6.0f * (s2 - (l + 1.0f) * (l + 1.0f));
+    const float fr = l + num / den;
+    r = uint32_t(int32_t(fr));
+    ww = uint32_t(float(1u << 24) / (fr * 2.0f + 1.0f));
+    fw = ((1u << 24) - (2u * r + 1u) * ww) / 2u;
+}
+// ... and one output sample of a line pass: acc the sum of the 2r + 1 samples around it, far that of the two at r + 1 (the line's
+// ends replicated), in wrapping 32-bit arithmetic
+LLMI_HD inline uint32_t photo_blur_tap(uint32_t acc, uint32_t far, uint32_t ww, uint32_t fw) {
+    return (acc * ww + far * fw + (1u << 23)) >> 24;
+}
+// How far the three passes reach to each side of a sample
+LLMI_HD inline uint32_t photo_blur_reach(uint32_t r) { return 3u * (r + 1u); }
+
+// ADJUST_HUE: the byte added to H ...
+LLMI_HD inline uint32_t photo_hue_shift(float factor) { return uint32_t(int32_t(double(factor) * 255.0)) & 0xFFu; }
+LLMI_HD inline uint32_t photo_clip8(int32_t v) { return v < 0 ? 0u : (v > 255 ? 255u : uint32_t(v)); }
+// ... PIL's convert("HSV") of one pixel ...
+LLMI_HD inline void photo_rgb2hsv(uint32_t r, uint32_t g, uint32_t b, uint32_t& hh, uint32_t& ss, uint32_t& vv) {
+    const uint32_t mx = r > g ? (r > b ? r : b) : (g > b ? g : b), mn = r < g ? (r < b ? r : b) : (g < b ? g : b);
+    vv = mx;
+    hh = ss = 0;
+    if (mx == mn) return;
+    const float cr = float(int32_t(mx - mn));
+    const float s = cr / float(int32_t(mx));
+    const float rc = float(int32_t(mx - r)) / cr, gc = float(int32_t(mx - g)) / cr, bc = float(int32_t(mx - b)) / cr;
+    float h;
+    if (r == mx)
+        h = float(double(bc) - double(gc));
+    else if (g == mx)
+        h = float((2.0 + double(rc)) - double(bc));
+    else
+        h = float((4.0 + double(gc)) - double(rc));
+    const double q = double(h) / 6.0 + 1.0;
+    h = float(fmod(q, 1.0));
+    hh = photo_clip8(int32_t(double(h) * 255.0));
+    ss = photo_clip8(int32_t(double(s) * 255.0));
+}
+// ... and its convert("RGB") of an HSV pixel
+LLMI_HD inline void photo_hsv2rgb(uint32_t hh, uint32_t ss, uint32_t vv, uint32_t& r, uint32_t& g, uint32_t& b) {
+    r = g = b = vv;
+    if (!ss) return;
+    const double h = double(float(int32_t(hh))) * 6.0 / 255.0;
+    const double fl = floor(h);
+    const int32_t i = int32_t(fl);
+    const float f = float(h - double(float(i)));
+    const float fs = float(double(float(int32_t(ss))) / 255.0);
+    const double v = double(int32_t(vv));
+    const double ps = 1.0 - double(fs);
+    const double qm = double(fs) * double(f);
+    const double tm = double(fs) * (1.0 - double(f));
+    const uint32_t p = photo_clip8(int32_t(round(v * ps)));
+    const uint32_t q = photo_clip8(int32_t(round(v * (1.0 - qm))));
+    const uint32_t t = photo_clip8(int32_t(round(v * (1.0 - tm))));
+    switch (i % 6) {
+        case 0: r = vv, g = t, b = p; break;
+        case 1: r = q, g = vv, b = p; break;
+        case 2: r = p, g = vv, b = t; break;
+        case 3: r = p, g = q, b = vv; break;
+        case 4: r = t, g = p, b = vv; break;
+        default: r = vv, g = p, b = q; break;
+    }
+}
+// ... on one RGB pixel in place
+LLMI_HD inline void photo_hue(uint32_t& r, uint32_t& g, uint32_t& b, uint32_t shift) {
+    uint32_t hh, ss, vv;
+    photo_rgb2hsv(r, g, b, hh, ss, vv);
+    photo_hsv2rgb((hh + shift) & 0xFFu, ss, vv, r, g, b);
+}
 
 }  // namespace llcomp_mi

@@ -4,10 +4,12 @@
     P  Codec.decode_views            2 views of 224 x 224 and 8 of 96 x 96 per frame (a multi-crop), bilinear, float16 CHW normalised
     J  ... with photo=               ColorJitter without hue + RandomGrayscale on every view: brightness, contrast, color, grayscale
     R  ... with photo=               a RandAugment-style pair on every view: solarize, equalize
+    D  ... with photo=               the DINO global-view chain on every view: brightness, contrast, color, adjust_hue, grayscale,
+                                     gaussian_blur with radius 1.0
 
 on frames of 3840 x 2160 x 3 in 64 x 64 tiles.  All three decode the same unions and resample the same views; P writes the formatted
-output from the vertical pass, J and R write U8 HWC into the staging buffer and run their chains from there.  The calls alternate
-P, J, R, P, J, R, ...; each is timed with the host clock from the call to the end of a stream synchronise (what a caller waits for) and
+output from the vertical pass, J, R and D write U8 HWC into the staging buffer and run their chains from there.  The calls alternate
+P, J, R, D, P, J, R, D, ...; each is timed with the host clock from the call to the end of a stream synchronise (what a caller waits for) and
 with device events around it (what the GPU does).  A second pass with the codec's profiling on gives the split of a call: slot 5 the
 slice decoder, slot 6 the inverse model with the crops, the resample passes and the chains.
 
@@ -26,6 +28,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 
 JITTER = [("brightness", 1.2), ("contrast", 0.8), ("color", 1.3), ("grayscale", None)]
 RANDAUG = [("solarize", 128), ("equalize", None)]
+DINO = [("brightness", 1.2), ("contrast", 0.8), ("color", 1.3), ("adjust_hue", 0.05), ("grayscale", None), ("gaussian_blur", 1.0)]
 
 
 def main():
@@ -81,12 +84,12 @@ def main():
         return [mi.ViewGroup(big, 224, 224, o_big.data_ptr(), filter="bilinear", photo=photo, **fmt),
                 mi.ViewGroup(small, 96, 96, o_small.data_ptr(), filter="bilinear", photo=photo, **fmt)]
 
-    legs = {"P": groups(None), "J": groups(JITTER), "R": groups(RANDAUG)}
+    legs = {"P": groups(None), "J": groups(JITTER), "R": groups(RANDAUG), "D": groups(DINO)}
 
     def call(which):
         codec.decode_views(pay.data_ptr(), nbytes, lens.data_ptr(), legs[which], st.data_ptr(), s)
 
-    order = ["P", "J", "R"] * (a.warmup + a.calls)
+    order = ["P", "J", "R", "D"] * (a.warmup + a.calls)
     wall, dev = {k: [] for k in legs}, {k: [] for k in legs}
     for i, which in enumerate(order):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -98,7 +101,7 @@ def main():
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         assert int(st.item()) == 0
-        if i >= 3 * a.warmup:
+        if i >= len(legs) * a.warmup:
             wall[which].append((t1 - t0) * 1e3)
             dev[which].append(e0.elapsed_time(e1))
     split = {}
@@ -113,18 +116,22 @@ def main():
     codec.close()
 
     med = statistics.median
+
+    def row(label, t, note=""):
+        return (f"  {label:<34}" + "".join(f"{med(t[k]):10.3f}  " for k in legs) + " " +
+                "".join(f"{med(t[k]) / med(t['P']):6.3f}   " for k in list(legs)[1:]) + note)
+
     lines = [
         "Photometric chains on top of the views call (tools/ubench/photo_views.py)",
         f"  {frames} frames of {w} x {h} x {c}, {a.tile} x {a.tile} tiles planar; per frame 2 views of 224 x 224 and 8 of 96 x 96 "
         f"({len(big) + len(small)} views), bilinear, float16 CHW normalised",
-        "  P = decode_views; J = the same with brightness, contrast, color, grayscale on every view; R = with solarize, equalize on every view",
-        f"  run order: {' '.join(order[:3 * a.warmup])} (warm-up, not counted) then P J R x {a.calls}",
+        "  P = decode_views; J = the same with brightness, contrast, color, grayscale on every view; R = with solarize, equalize on every view;",
+        "  D = with brightness, contrast, color, adjust_hue, grayscale, gaussian_blur(1.0) on every view",
+        f"  run order: {' '.join(order[:len(legs) * a.warmup])} (warm-up, not counted) then P J R D x {a.calls}",
         "",
-        "  ms per call                         P (plain)   J (jitter)   R (randaug)    J / P    R / P",
-        f"  host clock, call to synchronise   {med(wall['P']):10.3f}  {med(wall['J']):10.3f}  {med(wall['R']):10.3f}   {med(wall['J']) / med(wall['P']):6.3f}   "
-        f"{med(wall['R']) / med(wall['P']):6.3f}   (median of {a.calls})",
-        f"  device events around the call     {med(dev['P']):10.3f}  {med(dev['J']):10.3f}  {med(dev['R']):10.3f}   {med(dev['J']) / med(dev['P']):6.3f}   "
-        f"{med(dev['R']) / med(dev['P']):6.3f}",
+        "  ms per call                         P (plain)   J (jitter)  R (randaug)     D (dino)     J / P    R / P    D / P",
+        row("host clock, call to synchronise", wall, f"(median of {a.calls})"),
+        row("device events around the call", dev),
         "  min / max of the host clock       " + "    ".join(f"{min(wall[k]):.3f} / {max(wall[k]):.3f}" for k in legs),
         "",
         "  the codec's profile, ms per call (3 calls each, profiling on): slot 4 locate + copy, 5 slice decoder, 6 inverse model + crops + resample + chains, 7 clear",
