@@ -495,13 +495,24 @@ int llcomp_mi_warp_reference(const uint8_t* src, uint32_t w, uint32_t h, uint32_
  *                    i = floor(hh); f = (float)(hh - (float)i); fs = (float)((float)S / 255.0); p = round(V * (1.0 - fs));
  *                    q = round(V * (1.0 - fs * f)); t = round(V * (1.0 - fs * (1.0 - f))), round C's (halves away from zero), each
  *                    clipped to 0..255; i % 6 selects (V,t,p), (q,V,p), (p,V,t), (p,q,V), (t,p,V), (V,p,q).  No fused multiply-add.
+ *   ADJUST_SHARPNESS a  ImageEnhance.Sharpness(view).enhance(a) = Image.blend(view.filter(ImageFilter.SMOOTH), view, a), which is
+ *                  torchvision's adjust_sharpness(img, a) on the PIL backend (RandomAdjustSharpness, the Sharpness op of RandAugment /
+ *                  AutoAugment / TrivialAugmentWide); every channel by itself, c = 1 and c = 3; stated in integers:
+ *                  d(x, y) = v(x, y) where x is 0 or ow - 1 or y is 0 or oh - 1 -- the outermost rows and columns, and so every
+ *                    sample of a view with ow < 3 or oh < 3; otherwise d = (S + 6) / 13, floor division, with S = the sum of the nine
+ *                    samples v(x - 1 .. x + 1, y - 1 .. y + 1) as they stand BEFORE the op, plus four times v(x, y).
+ *                  The result is blend(d, v, a): a = 1 is the identity, a = 0 is SMOOTH itself, a > 1 sharpens.
+ *                  (PIL sums the nine binary32 products of the kernel (1 1 1 / 1 5 1 / 1 1 1) / 13 onto 0.5 and truncates; the exact
+ *                  (S + 6.5) / 13 is never nearer than 1 / 26 to an integer and PIL's rounding error stays below 3e-4, so the integer
+ *                  form is PIL's byte whatever the order of the sum.)  The window and the border rule are symmetric, so the op
+ *                  commutes with the mirror.
  * LIMITS (BAD_ARGS): a factor a that is not finite or not within 0..256; a threshold t that is not an integer within 0..256; bits b
  * that are not an integer within 1..8; a radius that is not finite or not within 0..LLCOMP_MI_PHOTO_MAX_RADIUS; a hue factor that is not
- * finite or not within -0.5..0.5; an unknown op code (9..15 among them); more than LLCOMP_MI_PHOTO_MAX_OPS ops; and a chain that is not
- * empty on a codec whose c is neither 1 nor 3 (PIL's L and RGB).  The parameter of an op that takes none is ignored.  Views of any
- * width and height may blur: there is no side limit.
- * NOT COVERED: sharpness (PIL's 3 x 3 SMOOTH blended in: ImageEnhance.Sharpness), torchvision's tensor-path GaussianBlur (a float
- * convolution: another rule), alpha. */
+ * finite or not within -0.5..0.5; an unknown op code (9..15 and 18 among them); more than LLCOMP_MI_PHOTO_MAX_OPS ops; and a chain that
+ * is not empty on a codec whose c is neither 1 nor 3 (PIL's L and RGB).  The parameter of an op that takes none is ignored.  Views of
+ * any width and height may blur and sharpen: there is no side limit.
+ * NOT COVERED: torchvision's tensor-path GaussianBlur and adjust_sharpness (float convolutions: other rules), the other ImageFilter
+ * kernels, alpha. */
 #define LLCOMP_MI_PHOTO_MAX_OPS 8
 #define LLCOMP_MI_PHOTO_MAX_RADIUS 32
 enum {
@@ -516,7 +527,8 @@ enum {
     LLCOMP_MI_PHOTO_EQUALIZE = 8,
     LLCOMP_MI_PHOTO_OP_COUNT = 9, /* the count of the pointwise family 0..8; codes 9..15 are no op */
     LLCOMP_MI_PHOTO_GAUSSIAN_BLUR = 16,
-    LLCOMP_MI_PHOTO_ADJUST_HUE = 17
+    LLCOMP_MI_PHOTO_ADJUST_HUE = 17,
+    LLCOMP_MI_PHOTO_ADJUST_SHARPNESS = 19 /* code 18, like 9..15, is no op and stays refused */
 };
 typedef struct llcomp_mi_photo_op {
     uint32_t op; /* LLCOMP_MI_PHOTO_* */

@@ -64,10 +64,11 @@ PAD_NAMES = ("constant", "edge", "reflect", "symmetric")
 PHOTO_MAX_OPS = 8
 PHOTO_NAMES = ("brightness", "contrast", "color", "grayscale", "invert", "solarize", "posterize", "autocontrast", "equalize")
 # the two ops outside the pointwise family 0..8, under torchvision's functional names: PIL's ImageFilter.GaussianBlur(radius) and
-# adjust_hue(hue_factor)
+# adjust_hue(hue_factor); and adjust_sharpness(sharpness_factor), PIL's ImageEnhance.Sharpness (code 18 is no op)
 PHOTO_GAUSSIAN_BLUR, PHOTO_ADJUST_HUE = 16, 17
+PHOTO_ADJUST_SHARPNESS = 19
 PHOTO_MAX_RADIUS = 32
-PHOTO_MORE_NAMES = {"gaussian_blur": PHOTO_GAUSSIAN_BLUR, "adjust_hue": PHOTO_ADJUST_HUE}
+PHOTO_MORE_NAMES = {"gaussian_blur": PHOTO_GAUSSIAN_BLUR, "adjust_hue": PHOTO_ADJUST_HUE, "adjust_sharpness": PHOTO_ADJUST_SHARPNESS}
 
 RawImage = namedtuple("RawImage", "pixels width height channels")
 
@@ -406,7 +407,7 @@ class ViewGroup:
 
 def photo_code(op):
     """PHOTO_* code of an op given by name ("brightness", "contrast", "color" or "saturation", "grayscale", "invert", "solarize",
-    "posterize", "autocontrast", "equalize", "gaussian_blur", "adjust_hue") or by code"""
+    "posterize", "autocontrast", "equalize", "gaussian_blur", "adjust_hue", "adjust_sharpness") or by code"""
     if isinstance(op, str):
         name = "color" if op.lower() == "saturation" else op.lower()
         if name in PHOTO_MORE_NAMES:
@@ -479,7 +480,7 @@ def _photo_groups(groups, n_views):
 def photo_reference(frame, ops):
     """The rule of the photometric chains on a host image (llcomp_mi_photo_reference): frame [h, w] or [h, w, c] uint8 with c = 1 or 3,
     ops a chain as photo_chain takes it -> the image after the chain, byte for byte PIL's ImageEnhance / ImageOps / ImageFilter.GaussianBlur
-    and torchvision's adjust_hue applied in order."""
+    / ImageEnhance.Sharpness and torchvision's adjust_hue applied in order."""
     a = np.ascontiguousarray(frame, dtype=np.uint8)
     if a.ndim not in (2, 3) or not a.size:
         raise LlcompError(BAD_ARGS, f"a frame is [h, w] or [h, w, c], got shape {a.shape}")

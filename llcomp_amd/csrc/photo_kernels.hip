@@ -1,6 +1,6 @@
 // photo_kernels.hip -- the kernels of the photometric chains (llcomp_mi_codec_decode_photo_views / _photo_warped_views): the
-// statistics of every view whose op of the step reads them, the table of every view whose op is one, the per-pixel pass, and the row
-// and the column kernel of the views whose op is the blur.  All views of a chunk run a step together; nothing goes back to the host in
+// statistics of every view whose op of the step reads them, the table of every view whose op is one, the per-pixel pass, the row
+// and the column kernel of the views whose op is the blur, and the band kernel of the views whose op is the sharpness.  All views of a chunk run a step together; nothing goes back to the host in
 // between.  The arithmetic is photo_rule.hpp's -- the functions llcomp_mi_photo_reference runs on the host -- with NO fused
 // multiply-add: the header's pragma holds for this whole file.
 #include "photo_rule.hpp"
@@ -101,7 +101,8 @@ __global__ __launch_bounds__(64) void k_photo_lut(const llcomp_mi_photo_chain* _
 
 // The per-pixel pass: blockIdx.y the view, a workgroup takes 1024 of its pixels.  A table op looks every channel up in the view's table
 // (copied to LDS), COLOR, GRAYSCALE and ADJUST_HUE are computed from the pixel, the step of an empty chain changes nothing, and a view
-// whose op is the blur sits out: k_photo_blur_rows and k_photo_blur_cols run it.  The value goes back in place, or -- the chain's
+// whose op is the blur sits out: k_photo_blur_rows and k_photo_blur_cols run it; so does a view whose op is the sharpness, which is
+// k_photo_sharp's.  The value goes back in place, or -- the chain's
 // last step -- through the group's output format to `out`.  E, CHW, LUT as in the gather of the warped views.
 template <int C, int E, bool CHW, bool LUT>
 __global__ __launch_bounds__(256) void k_photo_apply(uint8_t* __restrict__ px, const llcomp_mi_photo_chain* __restrict__ chains,
@@ -115,6 +116,7 @@ __global__ __launch_bounds__(256) void k_photo_apply(uint8_t* __restrict__ px, c
     bool last;
     if (!photo_step_op(chains[v], step, op, param, last)) return;  // (the whole workgroup alike)
     if (op != kPhotoNoOp && photo_is_area(op)) return;             // (the blur kernels' view in this step)
+    if (op != kPhotoNoOp && photo_is_sharp(op)) return;            // (k_photo_sharp's)
     const bool tab = op != kPhotoNoOp && photo_is_table(op);
     const uint32_t shift = op == LLCOMP_MI_PHOTO_ADJUST_HUE ? photo_hue_shift(param) : 0u;
     if (tab) {
@@ -309,6 +311,138 @@ __global__ __launch_bounds__(256) void k_photo_blur_cols(uint8_t* __restrict__ p
     }
 }
 
+// The sharpness (LLCOMP_MI_PHOTO_ADJUST_SHARPNESS): an output sample reads its eight neighbours as they were BEFORE the op, and the op
+// runs in place on px, so no sample may be written while another workgroup still has to read it.  A workgroup therefore owns a BAND of
+// band_rows whole rows of one view -- no edge between workgroups inside a row -- and the two rows a band reads outside itself, the one
+// above its first and the one below its last, are saved as they stand by k_photo_sharp_save, a launch before this one, into the
+// view's halo area: rows (j + 1) * band_rows - 1 and (j + 1) * band_rows, which lie next to each other in px, for every pair of
+// neighbouring bands j, j + 1.  A band reads px only inside its own rows, and the halo area is not written after the save.
+//   The workgroup walks down its band with a ring of kSharpSlots original rows in LDS: load row y + 1, barrier, compute row y from
+// rows y - 1, y, y + 1 of the ring, store row y.  With four slots the load of row y + 1 overwrites row y - 3, and a wavefront that
+// is still behind the barrier before computes row y - 1 from rows y - 2 .. y: one barrier a row is enough (three slots would need
+// two).  Lane per byte, taps C bytes apart, integers (photo_smooth).  A row comes
+// into its slot by dwords between the first and the last aligned address of its span in HBM and by bytes before and after; the slot
+// keeps the address's low two bits, so that byte q of the span lies at q + (address & 3): the three rows of a window may differ in it.
+//   A row longer than kSharpRowBytes is walked in column PIECES of that many bytes, one after the other by the same workgroup, each
+// loaded with C more bytes to each side.  The piece to the left has overwritten the C bytes a piece reads left of itself: those stay
+// behind in LDS for every row of the band (s_keep; photo_plan.hpp caps such a band at kSharpKeepRows), the halo rows are read again
+// from the halo area.  The chain's last step stores through the group's output table and layout to `out` (out_store.hpp); E, CHW,
+// LUT as in k_photo_apply.  The thresholds -- kSharpBandRows, kSharpRowBytes, kSharpKeepRows -- are photo_plan.hpp's, because the
+// planner charges the halo areas to the staging buffer by them.
+constexpr uint32_t kSharpSlots = 4;
+// the bytes of a ring slot: a row's span with C bytes to each side and up to 3 of misalignment, in whole 16s
+__host__ __device__ inline uint32_t sharp_slot_bytes(uint64_t pitch) {
+    return (uint32_t(pitch < kSharpRowBytes ? pitch : kSharpRowBytes) + 2u * 3u + 3u + 15u) & ~15u;
+}
+__host__ __device__ inline uint64_t sharp_pieces(uint64_t pitch) { return pitch <= kSharpRowBytes ? 1 : (pitch + kSharpRowBytes - 1) / kSharpRowBytes; }
+static_assert(kSharpSlots * ((kSharpRowBytes + 24u) & ~15u) + kSharpKeepRows * 3u <= 65536u, "the ring and the kept columns in 64 KiB of LDS");
+
+template <int C>
+__global__ __launch_bounds__(256) void k_photo_sharp_save(const uint8_t* __restrict__ px, const llcomp_mi_photo_chain* __restrict__ chains,
+                                                          uint8_t* __restrict__ halo, uint32_t ow, uint32_t oh, uint32_t band_rows,
+                                                          uint64_t halo_stride, uint32_t step) {
+    const uint32_t v = blockIdx.y, j = blockIdx.x;  // the pair of rows between bands j and j + 1
+    uint32_t op;
+    float param;
+    bool last;
+    if (!photo_step_op(chains[v], step, op, param, last) || op == kPhotoNoOp || !photo_is_sharp(op)) return;  // (the whole workgroup alike)
+    const size_t pitch = size_t(ow) * C;
+    const uint8_t* const src = px + (size_t(v) * oh + (size_t(j) + 1) * band_rows - 1) * pitch;
+    uint8_t* const dst = halo + size_t(v) * halo_stride + size_t(j) * 2 * pitch;
+    for (size_t b = threadIdx.x; b < 2 * pitch; b += 256) dst[b] = src[b];
+}
+
+template <int C, int E, bool CHW, bool LUT>
+__global__ __launch_bounds__(256) void k_photo_sharp(uint8_t* __restrict__ px, const llcomp_mi_photo_chain* __restrict__ chains,
+                                                     const uint8_t* __restrict__ halo, const void* __restrict__ table, void* __restrict__ out,
+                                                     uint32_t ow, uint32_t oh, uint32_t band_rows, uint64_t halo_stride, uint32_t step) {
+    using T = typename OutElem<E>::T;
+    extern __shared__ __align__(16) uint8_t s_sharp[];  // kSharpSlots slots, then -- a row in pieces -- band_rows * C kept bytes
+    const uint32_t v = blockIdx.y, band = blockIdx.x;
+    uint32_t op;
+    float param;
+    bool last;
+    if (!photo_step_op(chains[v], step, op, param, last) || op == kPhotoNoOp || !photo_is_sharp(op)) return;  // (the whole workgroup alike)
+    const size_t pitch = size_t(ow) * C, plane = size_t(oh) * ow;
+    const uint32_t slot_bytes = sharp_slot_bytes(pitch);
+    const uint32_t r0 = band * band_rows, r1 = oh - r0 < band_rows ? oh : r0 + band_rows;
+    uint8_t* const p = px + size_t(v) * plane * C;
+    const uint8_t* const hv = halo + size_t(v) * halo_stride;
+    uint8_t* const s_keep = s_sharp + kSharpSlots * slot_bytes;
+    T* const o = static_cast<T*>(out);
+    const T* const lut = static_cast<const T*>(table);
+    const uint64_t pieces = sharp_pieces(pitch);
+    // row yy of r0 - 1 .. r1 as it stood before the op: the band's own from px, the two beside it from the halo area
+    auto row_of = [&](uint32_t yy) -> const uint8_t* {
+        if (yy + 1 == r0) return hv + (size_t(band) - 1) * 2 * pitch;
+        if (yy == r1) return hv + size_t(band) * 2 * pitch + pitch;
+        return p + size_t(yy) * pitch;
+    };
+    for (uint64_t piece = 0; piece < pieces; ++piece) {
+        // the piece's outputs are bytes [s, e) of a row, its slot holds [lo, hi)
+        const size_t s = size_t(piece) * kSharpRowBytes, e = pitch - s < kSharpRowBytes ? pitch : s + kSharpRowBytes;
+        const size_t lo = piece ? s - C : 0, hi = pitch - e < size_t(C) ? pitch : e + C;
+        auto fetch = [&](uint32_t yy) {
+            const bool own = yy >= r0 && yy < r1;
+            const uint8_t* const row = row_of(yy);
+            uint8_t* const sl = s_sharp + ((yy + 1 - r0) & (kSharpSlots - 1)) * slot_bytes;
+            const uint32_t sh = uint32_t(reinterpret_cast<uintptr_t>(row + lo) & 3u);
+            const size_t q0 = own && piece ? s : lo;  // (px no longer has an own row's bytes left of s as they were)
+            const uint8_t* const b = row + q0;
+            const uint32_t at = uint32_t(q0 - lo) + sh, n = uint32_t(hi - q0);  // (at = b mod 4)
+            uint32_t head = uint32_t(-reinterpret_cast<uintptr_t>(b)) & 3u;
+            head = head < n ? head : n;
+            const uint32_t body = (n - head) >> 2, tail = n - head - 4 * body;
+            const uint32_t* const b4 = reinterpret_cast<const uint32_t*>(b + head);
+            uint32_t* const s4 = reinterpret_cast<uint32_t*>(sl + at + head);
+            for (uint32_t t = threadIdx.x; t < body; t += 256) s4[t] = b4[t];
+            if (threadIdx.x < head) sl[at + threadIdx.x] = b[threadIdx.x];
+            if (threadIdx.x < tail) sl[at + head + 4 * body + threadIdx.x] = b[head + 4 * body + threadIdx.x];
+            if (own && pieces > 1 && threadIdx.x < uint32_t(C)) {  // (the same thread reads a kept byte and replaces it)
+                uint8_t* const k = s_keep + size_t(yy - r0) * C + threadIdx.x;
+                if (piece) sl[sh + threadIdx.x] = *k;
+                if (piece + 1 < pieces) *k = row[e - C + threadIdx.x];
+            }
+        };
+        if (piece) __syncthreads();  // (the last row of the piece before is still being computed from the ring)
+        if (r0) fetch(r0 - 1);
+        fetch(r0);
+        for (uint32_t y = r0; y < r1; ++y) {
+            if (y + 1 < oh) fetch(y + 1);
+            __syncthreads();
+            const bool inner = y >= 1 && y + 1 < oh;
+            const uint8_t* const sc = s_sharp + ((y + 1 - r0) & (kSharpSlots - 1)) * slot_bytes + (reinterpret_cast<uintptr_t>(row_of(y) + lo) & 3u);
+            const uint8_t* su = sc;
+            const uint8_t* sd = sc;
+            if (inner) {
+                su = s_sharp + ((y - r0) & (kSharpSlots - 1)) * slot_bytes + (reinterpret_cast<uintptr_t>(row_of(y - 1) + lo) & 3u);
+                sd = s_sharp + ((y + 2 - r0) & (kSharpSlots - 1)) * slot_bytes + (reinterpret_cast<uintptr_t>(row_of(y + 1) + lo) & 3u);
+            }
+            for (size_t q = s + threadIdx.x; q < e; q += 256) {
+                const size_t x = q / C;
+                const uint32_t ch = uint32_t(q - x * C), i = uint32_t(q - lo);
+                const uint32_t val = sc[i];
+                uint32_t d = val;
+                if (inner && x >= 1 && x + 1 < ow) {
+                    const uint32_t sum9 = uint32_t(su[i - C]) + su[i] + su[i + C] + sc[i - C] + val + sc[i + C] + sd[i - C] + sd[i] + sd[i + C];
+                    d = photo_smooth(sum9, val);
+                }
+                const uint32_t res = photo_blend(d, val, param);
+                if (last)
+                    out_store<T, CHW, LUT>(o, lut, v, C, plane, size_t(y) * ow + x, ch, res);
+                else
+                    p[size_t(y) * pitch + q] = uint8_t(res);
+            }
+        }
+    }
+}
+
+template <int C, int E, bool CHW, bool LUT>
+void launch_sharp(dim3 grid, uint32_t lds, hipStream_t s, uint8_t* d_px, const llcomp_mi_photo_chain* d_chains, const uint8_t* d_halo,
+                  const void* d_table, void* d_out, uint32_t ow, uint32_t oh, uint32_t band_rows, uint64_t halo_stride, uint32_t step) {
+    k_photo_sharp<C, E, CHW, LUT><<<grid, dim3(256), lds, s>>>(d_px, d_chains, d_halo, d_table, d_out, ow, oh, band_rows, halo_stride, step);
+}
+
 template <int C, int E, bool CHW, bool LUT>
 void launch_blur_cols(dim3 grid, hipStream_t s, uint8_t* d_px, const llcomp_mi_photo_chain* d_chains, const void* d_table, void* d_out, uint32_t ow,
                       uint32_t oh, uint32_t step) {
@@ -324,7 +458,7 @@ void launch_apply(dim3 grid, hipStream_t s, uint8_t* d_px, const llcomp_mi_photo
 template <int C>
 hipError_t launch_step_c(uint8_t* d_px, const llcomp_mi_photo_chain* d_chains, uint8_t* d_stats, uint8_t* d_luts, const void* d_table,
                          const OutFormat& o, void* d_out, uint32_t views, uint32_t ow, uint32_t oh, uint32_t step, bool stats, bool table, bool area,
-                         hipStream_t s) {
+                         uint8_t* d_halo, uint32_t sharp_rows, hipStream_t s) {
     const uint64_t npix = uint64_t(oh) * ow;
     if (stats) {
         if (hipError_t err = hipMemsetAsync(d_stats, 0, size_t(views) * photo_stats_stride(C), s)) return err;
@@ -359,6 +493,23 @@ hipError_t launch_step_c(uint8_t* d_px, const llcomp_mi_photo_chain* d_chains, u
             chw ? LLMI_PHOTO(4, true, true) : LLMI_PHOTO(4, false, true);
 #undef LLMI_PHOTO
     }
+    if (sharp_rows) {  // the views that sharpen in this step: the rows between the bands first, as they stand, then the bands
+        const uint32_t bands = photo_sharp_bands(oh, sharp_rows);
+        const uint64_t pitch = uint64_t(ow) * C, halo_stride = photo_sharp_halo_bytes(ow, oh, C, sharp_rows);
+        if (bands > 1) k_photo_sharp_save<C><<<dim3(bands - 1, views), dim3(256), 0, s>>>(d_px, d_chains, d_halo, ow, oh, sharp_rows, halo_stride, step);
+        const uint32_t lds = kSharpSlots * sharp_slot_bytes(pitch) + (sharp_pieces(pitch) > 1 ? sharp_rows * C : 0u);
+        const dim3 grid_s(bands, views);
+#define LLMI_PHOTO(E, CHW, LUT) launch_sharp<C, E, CHW, LUT>(grid_s, lds, s, d_px, d_chains, d_halo, d_table, d_out, ow, oh, sharp_rows, halo_stride, step)
+        if (o.plain)
+            LLMI_PHOTO(1, false, false);
+        else if (o.esize == 1)
+            LLMI_PHOTO(1, true, true);
+        else if (o.esize == 2)
+            chw ? LLMI_PHOTO(2, true, true) : LLMI_PHOTO(2, false, true);
+        else
+            chw ? LLMI_PHOTO(4, true, true) : LLMI_PHOTO(4, false, true);
+#undef LLMI_PHOTO
+    }
     return hipGetLastError();
 }
 
@@ -366,7 +517,7 @@ hipError_t launch_step_c(uint8_t* d_px, const llcomp_mi_photo_chain* d_chains, u
 
 hipError_t launch_photo_step(uint8_t* d_px, const llcomp_mi_photo_chain* d_chains, void* d_stats, uint8_t* d_luts, const void* d_table,
                              const OutFormat& o, void* d_out, uint32_t views, uint32_t c, uint32_t ow, uint32_t oh, uint32_t step, bool stats,
-                             bool table, bool area, hipStream_t stream) {
+                             bool table, bool area, uint8_t* d_halo, uint32_t sharp_rows, hipStream_t stream) {
     if (!views || views > 65535 || (c != 1 && c != 3) || !ow || !oh || step >= LLCOMP_MI_PHOTO_MAX_OPS) return hipErrorInvalidValue;
     if (!d_px || !d_chains || !d_out || (reinterpret_cast<uintptr_t>(d_chains) & 3u)) return hipErrorInvalidValue;
     if ((stats || table) && (!d_stats || !d_luts || (reinterpret_cast<uintptr_t>(d_stats) & 7u))) return hipErrorInvalidValue;
@@ -375,9 +526,13 @@ hipError_t launch_photo_step(uint8_t* d_px, const llcomp_mi_photo_chain* d_chain
     const uint64_t npix = uint64_t(oh) * ow;
     if ((npix + 1023) / 1024 > 0x7FFFFFFFull) return hipErrorInvalidValue;  // (an output of 2^41 pixels: no buffer holds it)
     if (area && uint64_t(ow) * c > 0x7FFFFFFFull * kBlurStrip) return hipErrorInvalidValue;  // (the column kernel's grid; a row of 2^37 bytes)
+    if (sharp_rows) {  // (the band's grid; the halo area of a view in bands; the kept columns of a row in pieces, which are LDS)
+        if (sharp_rows > oh || (photo_sharp_bands(oh, sharp_rows) > 1 && !d_halo)) return hipErrorInvalidValue;
+        if (sharp_pieces(uint64_t(ow) * c) > 1 && sharp_rows > kSharpKeepRows) return hipErrorInvalidValue;
+    }
     uint8_t* st = static_cast<uint8_t*>(d_stats);
-    return c == 3 ? launch_step_c<3>(d_px, d_chains, st, d_luts, d_table, o, d_out, views, ow, oh, step, stats, table, area, stream)
-                  : launch_step_c<1>(d_px, d_chains, st, d_luts, d_table, o, d_out, views, ow, oh, step, stats, table, area, stream);
+    return c == 3 ? launch_step_c<3>(d_px, d_chains, st, d_luts, d_table, o, d_out, views, ow, oh, step, stats, table, area, d_halo, sharp_rows, stream)
+                  : launch_step_c<1>(d_px, d_chains, st, d_luts, d_table, o, d_out, views, ow, oh, step, stats, table, area, d_halo, sharp_rows, stream);
 }
 
 }  // namespace llcomp_mi

@@ -22,6 +22,19 @@ int photo_check_chain(const llcomp_mi_photo_chain& ch, uint32_t c) {
     return LLCOMP_MI_OK;
 }
 
+uint32_t photo_sharp_band_rows(uint32_t ow, uint32_t oh, uint32_t c, uint64_t samples) {
+    const uint64_t pitch = uint64_t(ow) * c, view = pitch * oh;
+    if (ow < 3 || oh < 3) return oh;  // (the identity: nothing reads a neighbour)
+    uint32_t rows = std::min(oh, kSharpBandRows);
+    if (view + photo_sharp_halo_bytes(ow, oh, c, rows) > samples) {
+        // the most bands whose halos still fit beside the view, one where the view alone fills the bound or exceeds it
+        const uint64_t bands = view < samples ? 1 + (samples - view) / (2 * pitch) : 1;
+        rows = uint32_t((oh + bands - 1) / bands);  // (bands <= oh / kSharpBandRows here, so rows >= kSharpBandRows)
+    }
+    if (pitch > kSharpRowBytes) rows = std::min(rows, kSharpKeepRows);
+    return rows;
+}
+
 int photo_setup(uint32_t c, uint64_t samples, const llcomp_mi_photo_group* photo, uint32_t n_groups, const uint32_t* n_views, const uint32_t* ow,
                 const uint32_t* oh, PhotoTail& t) {
     t = PhotoTail{};
@@ -40,6 +53,7 @@ int photo_setup(uint32_t c, uint64_t samples, const llcomp_mi_photo_group* photo
                 if (photo_needs_stats(ch.ops[k].op)) g.stats_steps |= 1u << k;
                 if (photo_is_table(ch.ops[k].op)) g.table_steps |= 1u << k;
                 if (photo_is_area(ch.ops[k].op)) g.area_steps |= 1u << k;
+                if (photo_is_sharp(ch.ops[k].op)) g.sharp_steps |= 1u << k;
             }
         }
         if (!g.steps) continue;  // (every chain empty: the group takes the extended call's path)
@@ -55,7 +69,11 @@ int photo_setup(uint32_t c, uint64_t samples, const llcomp_mi_photo_group* photo
             std::memcpy(ch.ops, pg.chains[i].ops, ch.n_ops * sizeof(llcomp_mi_photo_op));
             t.chains.push_back(ch);
         }
-        const uint64_t per_view = uint64_t(g.oh) * g.ow * c;
+        uint64_t per_view = uint64_t(g.oh) * g.ow * c;
+        if (g.sharp_steps) {  // (every view of the group alike, so that a chunk is its views and then their halo areas)
+            g.sharp_rows = photo_sharp_band_rows(g.ow, g.oh, c, samples);
+            per_view += photo_sharp_halo_bytes(g.ow, g.oh, c, g.sharp_rows);
+        }
         g.chunk = uint32_t(std::min<uint64_t>(g.n, std::max<uint64_t>(samples / std::max<uint64_t>(per_view, 1), 1)));
         t.stage_bytes = std::max(t.stage_bytes, g.chunk * per_view);
         t.tab_views = std::max<uint64_t>(t.tab_views, g.chunk);
@@ -84,7 +102,7 @@ int photo_reference(const uint8_t* src, uint32_t w, uint32_t h, uint32_t c, cons
     const uint64_t n = uint64_t(w) * h;
     if (out != src) std::memmove(out, src, size_t(n * c));
     std::vector<uint32_t> hist(size_t(256) * c);
-    std::vector<uint8_t> line;
+    std::vector<uint8_t> line, before;
     for (uint32_t k = 0; k < n_ops; ++k) {
         const uint32_t op = ops[k].op;
         const float a = ops[k].param;
@@ -98,6 +116,24 @@ int photo_reference(const uint8_t* src, uint32_t w, uint32_t h, uint32_t c, cons
             for (int pass = 0; pass < 3; ++pass)  // along every column
                 for (uint64_t x = 0; x < w; ++x)
                     for (uint32_t ch = 0; ch < c; ++ch) blur_line(out + x * c + ch, h, uint64_t(w) * c, r, ww, fw, line.data());
+            continue;
+        }
+        if (photo_is_sharp(op)) {  // every sample from the view as it stands before the op: a copy of it
+            before.assign(out, out + size_t(n * c));
+            const uint64_t pitch = uint64_t(w) * c;
+            for (uint64_t y = 0; y < h; ++y)
+                for (uint64_t x = 0; x < w; ++x)
+                    for (uint32_t ch = 0; ch < c; ++ch) {
+                        const uint8_t* const p = before.data() + y * pitch + x * c + ch;
+                        uint32_t d = *p;
+                        if (photo_smooth_interior(x, y, w, h)) {
+                            uint32_t sum9 = 0;
+                            for (int dy = -1; dy <= 1; ++dy)
+                                for (int dx = -1; dx <= 1; ++dx) sum9 += p[int64_t(dy) * int64_t(pitch) + dx * int64_t(c)];
+                            d = photo_smooth(sum9, *p);
+                        }
+                        out[y * pitch + x * c + ch] = uint8_t(photo_blend(d, *p, a));
+                    }
             continue;
         }
         if (!photo_is_table(op)) {

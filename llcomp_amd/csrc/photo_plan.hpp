@@ -17,14 +17,32 @@ inline uint64_t photo_stats_stride(uint32_t c) { return 8 + 1024 * uint64_t(c); 
 // ... and its table, [c][256] u8
 inline uint64_t photo_lut_stride(uint32_t c) { return 256 * uint64_t(c); }
 
+// The sharpness kernel's geometry (photo_kernels.hip: k_photo_sharp), which the planner charges for.  A workgroup owns a BAND of whole
+// rows of a view and walks down it; the rows next to a band -- the last of the band above, the first of the band below -- are saved AS
+// THEY STAND into a halo area behind the chunk's views before any band is written: two rows of ow * c bytes per pair of neighbouring bands.
+constexpr uint32_t kSharpBandRows = 16;    // the rows of a band where the staging bound leaves room for the halos
+constexpr uint32_t kSharpRowBytes = 12288; // the bytes of a row that the kernel's ring in LDS holds: a longer row is walked in column pieces ...
+constexpr uint32_t kSharpKeepRows = 4096;  // ... whose edge columns stay behind in LDS for the band's rows, which caps a band of such a view
+inline uint32_t photo_sharp_bands(uint32_t oh, uint32_t band_rows) { return (oh + band_rows - 1) / band_rows; }
+inline uint64_t photo_sharp_halo_bytes(uint32_t ow, uint32_t oh, uint32_t c, uint32_t band_rows) {
+    return 2 * uint64_t(photo_sharp_bands(oh, band_rows) - 1) * ow * c;
+}
+// The rows of a band for views of ow x oh x c whose chains hold the op, under the staging bound `samples`: kSharpBandRows, or as many
+// more as it takes for one view with its halos to fit -- in the limit the whole view is one band with no halo, so that a view of
+// `samples` bytes needs no byte beyond itself.  (The one exception: a view with rows longer than kSharpRowBytes AND more than
+// kSharpKeepRows of them keeps bands of kSharpKeepRows, whatever they take.)
+uint32_t photo_sharp_band_rows(uint32_t ow, uint32_t oh, uint32_t c, uint64_t samples);
+
 // One group of the call.  active: some view has a chain that is not empty -- the group's tail entry then writes plain U8 HWC into the
 // staging buffer, `chunk` views at a time, and the chain's last step writes d_out in format `out` through the table at table_at of the
 // tail's output tables (all three taken over from the tail's group).  first: the group's chains in the block.  steps: the longest chain.
-// Bit k of stats_steps / table_steps / area_steps: some view's op k needs the statistics pass / is a table / is the blur, which the
-// row and column kernels run in place of the per-pixel pass.
+// Bit k of stats_steps / table_steps / area_steps / sharp_steps: some view's op k needs the statistics pass / is a table / is the blur,
+// which the row and column kernels run in place of the per-pixel pass / is the sharpness, which k_photo_sharp runs in its place.
+// sharp_rows: the rows of a band of the sharpness kernel, 0 for a group without the op; a chunk of such a group is `chunk` views and
+// behind them `chunk` halo areas of photo_sharp_halo_bytes each, and the two together stay within the planner's bound.
 struct PhotoGroup {
     bool active = false;
-    uint32_t n = 0, ow = 0, oh = 0, first = 0, chunk = 0, steps = 0, stats_steps = 0, table_steps = 0, area_steps = 0;
+    uint32_t n = 0, ow = 0, oh = 0, first = 0, chunk = 0, steps = 0, stats_steps = 0, table_steps = 0, area_steps = 0, sharp_steps = 0, sharp_rows = 0;
     OutFormat out;
     void* d_out = nullptr;
     uint64_t table_at = 0;
@@ -46,7 +64,8 @@ uint64_t photo_tables_bound(uint64_t total_views);
 // parameter outside its limits, and any op at all where c is neither 1 nor 3.
 int photo_check_chain(const llcomp_mi_photo_chain& ch, uint32_t c);
 // Everything of the chains the host decides.  photo: n_groups entries or null; n_views / ow / oh: per group of the call.  samples: the
-// staging buffer's bound, frames * w * h * c -- a group of more views than fit is chunked, and one view always goes through.
+// staging buffer's bound, frames * w * h * c -- a group of more views than fit is chunked, and one view always goes through.  A group
+// whose chains hold the sharpness is chunked with every view charged its halo area too (photo_sharp_band_rows).
 // BAD_ARGS: a struct_size that is not the struct's, and photo_check_chain's cases.
 int photo_setup(uint32_t c, uint64_t samples, const llcomp_mi_photo_group* photo, uint32_t n_groups, const uint32_t* n_views, const uint32_t* ow,
                 const uint32_t* oh, PhotoTail& t);

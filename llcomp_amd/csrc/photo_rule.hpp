@@ -39,6 +39,9 @@ LLMI_HD inline bool photo_is_table(uint32_t op) {
 }
 // ... and the op whose output sample reads other samples of the view: it has kernels of its own (photo_kernels.hip: k_photo_blur_*)
 LLMI_HD inline bool photo_is_area(uint32_t op) { return op == LLCOMP_MI_PHOTO_GAUSSIAN_BLUR; }
+// ... and the op whose output sample reads its 3 x 3 neighbourhood: NOT an area op in the sense above -- the blur's kernels and the
+// per-pixel pass both sit out of it, and k_photo_sharp runs it
+LLMI_HD inline bool photo_is_sharp(uint32_t op) { return op == LLCOMP_MI_PHOTO_ADJUST_SHARPNESS; }
 
 // the limits of one op: finite factors within 0..256, an integer threshold within 0..256, integer bits within 1..8, a finite radius
 // within 0..LLCOMP_MI_PHOTO_MAX_RADIUS, a finite hue factor within -0.5..0.5
@@ -46,6 +49,7 @@ LLMI_HD inline bool photo_op_ok(uint32_t op, float param) {
     switch (op) {
         case LLCOMP_MI_PHOTO_BRIGHTNESS:
         case LLCOMP_MI_PHOTO_CONTRAST:
+        case LLCOMP_MI_PHOTO_ADJUST_SHARPNESS:
         case LLCOMP_MI_PHOTO_COLOR: return param >= 0.0f && param <= 256.0f;  // (false for a NaN)
         case LLCOMP_MI_PHOTO_SOLARIZE: return param >= 0.0f && param <= 256.0f && float(int32_t(param)) == param;
         case LLCOMP_MI_PHOTO_POSTERIZE: return param >= 1.0f && param <= 8.0f && float(int32_t(param)) == param;
@@ -160,6 +164,13 @@ LLMI_HD inline uint32_t photo_blur_tap(uint32_t acc, uint32_t far, uint32_t ww, 
 }
 // How far the three passes reach to each side of a sample
 LLMI_HD inline uint32_t photo_blur_reach(uint32_t r) { return 3u * (r + 1u); }
+
+// ADJUST_SHARPNESS: PIL's ImageFilter.SMOOTH of one interior sample -- sum9 the sum of the nine samples of its 3 x 3 window, the sample
+// itself among them.  PIL adds nine binary32 products of (1 1 1 / 1 5 1 / 1 1 1) / 13 onto 0.5 and truncates; the integer form is the
+// same byte in whatever order the nine are summed (include/llcomp_mi.h).  A sample of the outermost rows and columns is its own smooth
+// value; the op's result is photo_blend(smooth, sample, factor).
+LLMI_HD inline uint32_t photo_smooth(uint32_t sum9, uint32_t centre) { return (sum9 + 4u * centre + 6u) / 13u; }
+LLMI_HD inline bool photo_smooth_interior(uint64_t x, uint64_t y, uint64_t w, uint64_t h) { return x >= 1 && x + 1 < w && y >= 1 && y + 1 < h; }
 
 // ADJUST_HUE: the byte added to H ...
 LLMI_HD inline uint32_t photo_hue_shift(float factor) { return uint32_t(int32_t(double(factor) * 255.0)) & 0xFFu; }

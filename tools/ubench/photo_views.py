@@ -6,10 +6,12 @@
     R  ... with photo=               a RandAugment-style pair on every view: solarize, equalize
     D  ... with photo=               the DINO global-view chain on every view: brightness, contrast, color, adjust_hue, grayscale,
                                      gaussian_blur with radius 1.0
+    S  ... with photo=               J's chain and adjust_sharpness with factor 1.8 behind it: S - J is the sharpness step
+    B  ... with photo=               J's chain and gaussian_blur with radius 1.0 behind it: B - J is the blur step, S's yardstick
 
-on frames of 3840 x 2160 x 3 in 64 x 64 tiles.  All three decode the same unions and resample the same views; P writes the formatted
-output from the vertical pass, J, R and D write U8 HWC into the staging buffer and run their chains from there.  The calls alternate
-P, J, R, D, P, J, R, D, ...; each is timed with the host clock from the call to the end of a stream synchronise (what a caller waits for) and
+on frames of 3840 x 2160 x 3 in 64 x 64 tiles.  All of them decode the same unions and resample the same views; P writes the formatted
+output from the vertical pass, the others write U8 HWC into the staging buffer and run their chains from there.  The calls alternate
+P, J, R, D, S, B, P, J, ...; each is timed with the host clock from the call to the end of a stream synchronise (what a caller waits for) and
 with device events around it (what the GPU does).  A second pass with the codec's profiling on gives the split of a call: slot 5 the
 slice decoder, slot 6 the inverse model with the crops, the resample passes and the chains.
 
@@ -29,6 +31,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 JITTER = [("brightness", 1.2), ("contrast", 0.8), ("color", 1.3), ("grayscale", None)]
 RANDAUG = [("solarize", 128), ("equalize", None)]
 DINO = [("brightness", 1.2), ("contrast", 0.8), ("color", 1.3), ("adjust_hue", 0.05), ("grayscale", None), ("gaussian_blur", 1.0)]
+SHARP = JITTER + [("adjust_sharpness", 1.8)]
+BLUR = JITTER + [("gaussian_blur", 1.0)]
 
 
 def main():
@@ -84,12 +88,12 @@ def main():
         return [mi.ViewGroup(big, 224, 224, o_big.data_ptr(), filter="bilinear", photo=photo, **fmt),
                 mi.ViewGroup(small, 96, 96, o_small.data_ptr(), filter="bilinear", photo=photo, **fmt)]
 
-    legs = {"P": groups(None), "J": groups(JITTER), "R": groups(RANDAUG), "D": groups(DINO)}
+    legs = {"P": groups(None), "J": groups(JITTER), "R": groups(RANDAUG), "D": groups(DINO), "S": groups(SHARP), "B": groups(BLUR)}
 
     def call(which):
         codec.decode_views(pay.data_ptr(), nbytes, lens.data_ptr(), legs[which], st.data_ptr(), s)
 
-    order = ["P", "J", "R", "D"] * (a.warmup + a.calls)
+    order = list(legs) * (a.warmup + a.calls)
     wall, dev = {k: [] for k in legs}, {k: [] for k in legs}
     for i, which in enumerate(order):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -126,13 +130,15 @@ def main():
         f"  {frames} frames of {w} x {h} x {c}, {a.tile} x {a.tile} tiles planar; per frame 2 views of 224 x 224 and 8 of 96 x 96 "
         f"({len(big) + len(small)} views), bilinear, float16 CHW normalised",
         "  P = decode_views; J = the same with brightness, contrast, color, grayscale on every view; R = with solarize, equalize on every view;",
-        "  D = with brightness, contrast, color, adjust_hue, grayscale, gaussian_blur(1.0) on every view",
-        f"  run order: {' '.join(order[:len(legs) * a.warmup])} (warm-up, not counted) then P J R D x {a.calls}",
+        "  D = with brightness, contrast, color, adjust_hue, grayscale, gaussian_blur(1.0) on every view;",
+        "  S = J's chain and adjust_sharpness(1.8) on every view; B = J's chain and gaussian_blur(1.0) on every view",
+        f"  run order: {' '.join(order[:len(legs) * a.warmup])} (warm-up, not counted) then {' '.join(legs)} x {a.calls}",
         "",
-        "  ms per call                         P (plain)   J (jitter)  R (randaug)     D (dino)     J / P    R / P    D / P",
+        "  ms per call                         P (plain)   J (jitter)  R (randaug)     D (dino)    S (sharp)     B (blur)     J / P    R / P    D / P    S / P    B / P",
         row("host clock, call to synchronise", wall, f"(median of {a.calls})"),
         row("device events around the call", dev),
         "  min / max of the host clock       " + "    ".join(f"{min(wall[k]):.3f} / {max(wall[k]):.3f}" for k in legs),
+        f"  the last op's step, device events: sharpness S - J = {med(dev['S']) - med(dev['J']):.3f} ms, blur B - J = {med(dev['B']) - med(dev['J']):.3f} ms",
         "",
         "  the codec's profile, ms per call (3 calls each, profiling on): slot 4 locate + copy, 5 slice decoder, 6 inverse model + crops + resample + chains, 7 clear",
     ] + ["    " + k + "  " + "  ".join(f"[{i}] {split[k][i]:.3f}" for i in range(4, 8)) for k in legs]
