@@ -704,6 +704,21 @@ def _containers(containers):
     return (C.c_void_p * max(1, len(keep)))(*ptrs), (C.c_size_t * max(1, len(keep)))(*[len(d) if isinstance(d, bytes) else d.size for d in keep]), keep
 
 
+def _frame_containers(containers, frames, allow_none=False):
+    """_containers of exactly `frames` containers, one per frame of a codec.  allow_none: the container of a frame that the call never
+    reads may be None -- it goes as a NULL pointer of length 0"""
+    conts = list(containers)
+    if allow_none and len(conts) != frames:
+        raise LlcompError(BAD_ARGS, f"the codec takes {frames} containers, got {len(conts)}")
+    ptrs, lens, keep = _containers([b"" if allow_none and d is None else d for d in conts])
+    if len(keep) != frames:
+        raise LlcompError(BAD_ARGS, f"the codec takes {frames} containers, got {len(keep)}")
+    for f, d in enumerate(conts):
+        if allow_none and d is None:
+            ptrs[f], lens[f] = None, 0
+    return ptrs, lens, keep
+
+
 def regions_gather(containers, xy, rw, rh):
     """(payload np.uint8, slice_len np.uint32, n_classes): the table entries and payload bytes of every frame's window (regions_plan) of
     single-frame SLICED containers, class by class, frame order inside a class -- exactly what a regions decode of them reads
@@ -1262,11 +1277,52 @@ class Codec:
         """decode_regions of host containers (llcomp_mi_codec_decode_regions_host): `containers` = the frames' single-frame SLICED
         containers (bytes or uint8 arrays), and only their windows' bytes cross PCIe.  The containers and xy are read during the call
         only; the decode is asynchronous on `stream`."""
-        ptrs, lens, keep = _containers(containers)
-        if len(keep) != self.frames:
-            raise LlcompError(BAD_ARGS, f"the codec takes {self.frames} containers, got {len(keep)}")
+        ptrs, lens, _keep = _frame_containers(containers, self.frames)
         tab, _ = _xy_table(xy, self.frames)
         _check(self._L.llcomp_mi_codec_decode_regions_host(self._h, ptrs, lens, tab, rw, rh, d_px, d_status, stream))
+
+    # The resized, views and warped calls, each from either source: src = (d_payload, payload_bytes, d_slice_len) of the batch in HBM, or
+    # -- host -- (ptrs, lens) of the frames' containers (_frame_containers); the C function by the source and by what the call asks for.
+    def _resized(self, host, src, rects, ow, oh, d_px, d_status, flags, stream, dtype, layout, scale, mean, std, filter, pad_mode, fill):
+        name = "llcomp_mi_codec_decode_%s_regions" + ("_host" if host else "")
+        fl = _flags_table(flags, self.frames, filter)
+        fmt, _, _keep = _output_format(self.c, dtype, layout, scale, mean, std)
+        if pad_mode is not None or fill is not None:
+            tab, _ = _signed_rects_table(rects, self.frames)
+            pad, _keep_pad = _pad(self.c, pad_mode, fill)
+            _check(getattr(self._L, name % "padded")(self._h, *src, tab, fl, ow, oh, C.byref(pad), C.byref(fmt) if fmt is not None else None, d_px,
+                                                    d_status, stream))
+            return
+        tab, _ = _rects_table(rects, self.frames)
+        if fmt is None:
+            _check(getattr(self._L, name % "resized")(self._h, *src, tab, fl, ow, oh, d_px, d_status, stream))
+        else:
+            _check(getattr(self._L, name % "resized" + "_ex")(self._h, *src, tab, fl, ow, oh, C.byref(fmt), d_px, d_status, stream))
+
+    def _views(self, host, src, groups, d_status, stream, pad_mode, fill):
+        name = "llcomp_mi_codec_decode_%sviews" + ("_host" if host else "")
+        groups = list(groups) if groups is not None else []
+        padded = pad_mode is not None or fill is not None
+        arr, n, _keep = _view_groups(groups, self.c, signed=padded)
+        chains = any(getattr(gr, "photo", None) is not None for gr in groups)
+        photo, _keep_photo = _photo_groups(groups, [arr[i].n_views for i in range(n)]) if chains else (None, None)
+        pad, _keep_pad = _pad(self.c, pad_mode, fill) if padded else (None, None)
+        if chains:
+            _check(getattr(self._L, name % "photo_")(self._h, *src, arr, n, C.byref(pad) if padded else None, photo, d_status, stream))
+        elif padded:
+            _check(getattr(self._L, name % "padded_")(self._h, *src, arr, n, C.byref(pad), d_status, stream))
+        else:
+            _check(getattr(self._L, name % "")(self._h, *src, arr, n, d_status, stream))
+
+    def _warped(self, host, src, groups, d_status, stream):
+        name = "llcomp_mi_codec_decode_%swarped_views" + ("_host" if host else "")
+        groups = list(groups) if groups is not None else []
+        arr, n, _keep = _warp_groups(groups, self.c)
+        if any(getattr(gr, "photo", None) is not None for gr in groups):
+            photo, _keep_photo = _photo_groups(groups, [arr[i].n_views for i in range(n)])
+            _check(getattr(self._L, name % "photo_")(self._h, *src, arr, n, photo, d_status, stream))
+        else:
+            _check(getattr(self._L, name % "")(self._h, *src, arr, n, d_status, stream))
 
     def decode_resized_regions(self, d_payload, payload_bytes, d_slice_len, rects, ow, oh, d_px, d_status, flags=None, stream=0, dtype=None,
                                layout="hwc", scale=False, mean=None, std=None, filter=None, pad_mode=None, fill=None):
@@ -1280,44 +1336,16 @@ class Codec:
         and fill (one value or c values, "constant" only; alone it means "constant"): rectangles may leave the image, x and y may be
         negative, and frame f is np.pad(frame, pad_mode) cut at its rectangle (llcomp_mi_codec_decode_padded_regions) -- only the part
         inside the image is decoded.  Without them a rectangle outside the image stays BAD_ARGS."""
-        fl = _flags_table(flags, self.frames, filter)
-        fmt, _, _keep = _output_format(self.c, dtype, layout, scale, mean, std)
-        if pad_mode is not None or fill is not None:
-            tab, _ = _signed_rects_table(rects, self.frames)
-            pad, _keep_pad = _pad(self.c, pad_mode, fill)
-            _check(self._L.llcomp_mi_codec_decode_padded_regions(self._h, d_payload, payload_bytes, d_slice_len, tab, fl, ow, oh, C.byref(pad),
-                                                                  C.byref(fmt) if fmt is not None else None, d_px, d_status, stream))
-            return
-        tab, _ = _rects_table(rects, self.frames)
-        if fmt is None:
-            _check(self._L.llcomp_mi_codec_decode_resized_regions(self._h, d_payload, payload_bytes, d_slice_len, tab, fl, ow, oh, d_px, d_status,
-                                                                   stream))
-        else:
-            _check(self._L.llcomp_mi_codec_decode_resized_regions_ex(self._h, d_payload, payload_bytes, d_slice_len, tab, fl, ow, oh, C.byref(fmt),
-                                                                      d_px, d_status, stream))
+        self._resized(False, (d_payload, payload_bytes, d_slice_len), rects, ow, oh, d_px, d_status, flags, stream, dtype, layout, scale, mean, std,
+                      filter, pad_mode, fill)
 
     def decode_resized_regions_host(self, containers, rects, ow, oh, d_px, d_status, flags=None, stream=0, dtype=None, layout="hwc", scale=False,
                                     mean=None, std=None, filter=None, pad_mode=None, fill=None):
         """decode_resized_regions of host containers (llcomp_mi_codec_decode_resized_regions_host(_ex)): only the windows' bytes cross
         PCIe; the containers, rects and flags are read during the call only; filter, pad_mode and fill as decode_resized_regions takes
         them (llcomp_mi_codec_decode_padded_regions_host: only the windows of the source rectangles cross)"""
-        ptrs, lens, keep = _containers(containers)
-        if len(keep) != self.frames:
-            raise LlcompError(BAD_ARGS, f"the codec takes {self.frames} containers, got {len(keep)}")
-        fl = _flags_table(flags, self.frames, filter)
-        fmt, _, _keep = _output_format(self.c, dtype, layout, scale, mean, std)
-        if pad_mode is not None or fill is not None:
-            tab, _ = _signed_rects_table(rects, self.frames)
-            pad, _keep_pad = _pad(self.c, pad_mode, fill)
-            _check(self._L.llcomp_mi_codec_decode_padded_regions_host(self._h, ptrs, lens, tab, fl, ow, oh, C.byref(pad),
-                                                                       C.byref(fmt) if fmt is not None else None, d_px, d_status, stream))
-            return
-        tab, _ = _rects_table(rects, self.frames)
-        if fmt is None:
-            _check(self._L.llcomp_mi_codec_decode_resized_regions_host(self._h, ptrs, lens, tab, fl, ow, oh, d_px, d_status, stream))
-        else:
-            _check(self._L.llcomp_mi_codec_decode_resized_regions_host_ex(self._h, ptrs, lens, tab, fl, ow, oh, C.byref(fmt), d_px, d_status,
-                                                                           stream))
+        ptrs, lens, _keep = _frame_containers(containers, self.frames)
+        self._resized(True, (ptrs, lens), rects, ow, oh, d_px, d_status, flags, stream, dtype, layout, scale, mean, std, filter, pad_mode, fill)
 
     def decode_views(self, d_payload, payload_bytes, d_slice_len, groups, d_status, stream=0, pad_mode=None, fill=None):
         """several views of each frame, each frame decoded once (llcomp_mi_codec_decode_views): groups = ViewGroup objects (or
@@ -1325,80 +1353,26 @@ class Codec:
         of that frame.  A frame decodes the bounding box of all its views; a frame without a view is not read.  d_payload / d_slice_len
         are the full batch's (pack_batch).  pad_mode / fill as decode_resized_regions takes them: views may leave the image, a view's x and
         y may be negative (llcomp_mi_codec_decode_padded_views), and a frame decodes the bounding box of its views' source rectangles."""
-        groups = list(groups) if groups is not None else []
-        padded = pad_mode is not None or fill is not None
-        if any(getattr(gr, "photo", None) is not None for gr in groups):  # (llcomp_mi_codec_decode_photo_views)
-            arr, n, _keep = _view_groups(groups, self.c, signed=padded)
-            photo, _keep_photo = _photo_groups(groups, [arr[i].n_views for i in range(n)])
-            pad, _keep_pad = _pad(self.c, pad_mode, fill) if padded else (None, None)
-            _check(self._L.llcomp_mi_codec_decode_photo_views(self._h, d_payload, payload_bytes, d_slice_len, arr, n,
-                                                              C.byref(pad) if padded else None, photo, d_status, stream))
-            return
-        if padded:
-            arr, n, _keep = _view_groups(groups, self.c, signed=True)
-            pad, _keep_pad = _pad(self.c, pad_mode, fill)
-            _check(self._L.llcomp_mi_codec_decode_padded_views(self._h, d_payload, payload_bytes, d_slice_len, arr, n, C.byref(pad), d_status, stream))
-            return
-        arr, n, _keep = _view_groups(groups, self.c)
-        _check(self._L.llcomp_mi_codec_decode_views(self._h, d_payload, payload_bytes, d_slice_len, arr, n, d_status, stream))
+        self._views(False, (d_payload, payload_bytes, d_slice_len), groups, d_status, stream, pad_mode, fill)
 
     def decode_views_host(self, containers, groups, d_status, stream=0, pad_mode=None, fill=None):
         """decode_views of host containers (llcomp_mi_codec_decode_views_host): only the union windows' bytes cross PCIe; the container
         of a frame without a view may be None and is never read; pad_mode / fill as decode_views takes them
         (llcomp_mi_codec_decode_padded_views_host)"""
-        conts = list(containers)
-        if len(conts) != self.frames:
-            raise LlcompError(BAD_ARGS, f"the codec takes {self.frames} containers, got {len(conts)}")
-        ptrs, lens, keep = _containers([d if d is not None else b"" for d in conts])
-        for f, d in enumerate(conts):
-            if d is None:
-                ptrs[f], lens[f] = None, 0
-        groups = list(groups) if groups is not None else []
-        padded = pad_mode is not None or fill is not None
-        if any(getattr(gr, "photo", None) is not None for gr in groups):  # (llcomp_mi_codec_decode_photo_views_host)
-            arr, n, _keep = _view_groups(groups, self.c, signed=padded)
-            photo, _keep_photo = _photo_groups(groups, [arr[i].n_views for i in range(n)])
-            pad, _keep_pad = _pad(self.c, pad_mode, fill) if padded else (None, None)
-            _check(self._L.llcomp_mi_codec_decode_photo_views_host(self._h, ptrs, lens, arr, n, C.byref(pad) if padded else None, photo, d_status,
-                                                                   stream))
-            return
-        if padded:
-            arr, n, _keep = _view_groups(groups, self.c, signed=True)
-            pad, _keep_pad = _pad(self.c, pad_mode, fill)
-            _check(self._L.llcomp_mi_codec_decode_padded_views_host(self._h, ptrs, lens, arr, n, C.byref(pad), d_status, stream))
-            return
-        arr, n, _keep = _view_groups(groups, self.c)
-        _check(self._L.llcomp_mi_codec_decode_views_host(self._h, ptrs, lens, arr, n, d_status, stream))
+        ptrs, lens, _keep = _frame_containers(containers, self.frames, allow_none=True)
+        self._views(True, (ptrs, lens), groups, d_status, stream, pad_mode, fill)
 
     def decode_warped_views(self, d_payload, payload_bytes, d_slice_len, groups, d_status, stream=0):
         """views under an affine map (llcomp_mi_codec_decode_warped_views): groups = WarpGroup objects; view v of a group -> d_out[v], byte
         for byte warp_reference of its frame (PIL's Image.transform(AFFINE)), mirrored and formatted as the other calls do.  A frame
         decodes once, and only the bounding box of the source pixels its views read; a frame without a view is not read."""
-        groups = list(groups) if groups is not None else []
-        arr, n, _keep = _warp_groups(groups, self.c)
-        if any(getattr(gr, "photo", None) is not None for gr in groups):  # (llcomp_mi_codec_decode_photo_warped_views)
-            photo, _keep_photo = _photo_groups(groups, [arr[i].n_views for i in range(n)])
-            _check(self._L.llcomp_mi_codec_decode_photo_warped_views(self._h, d_payload, payload_bytes, d_slice_len, arr, n, photo, d_status, stream))
-            return
-        _check(self._L.llcomp_mi_codec_decode_warped_views(self._h, d_payload, payload_bytes, d_slice_len, arr, n, d_status, stream))
+        self._warped(False, (d_payload, payload_bytes, d_slice_len), groups, d_status, stream)
 
     def decode_warped_views_host(self, containers, groups, d_status, stream=0):
         """decode_warped_views of host containers (llcomp_mi_codec_decode_warped_views_host): only the union windows' bytes cross PCIe;
         the container of a frame no view reads may be None and is never read"""
-        conts = list(containers)
-        if len(conts) != self.frames:
-            raise LlcompError(BAD_ARGS, f"the codec takes {self.frames} containers, got {len(conts)}")
-        ptrs, lens, keep = _containers([d if d is not None else b"" for d in conts])
-        for f, d in enumerate(conts):
-            if d is None:
-                ptrs[f], lens[f] = None, 0
-        groups = list(groups) if groups is not None else []
-        arr, n, _keep = _warp_groups(groups, self.c)
-        if any(getattr(gr, "photo", None) is not None for gr in groups):  # (llcomp_mi_codec_decode_photo_warped_views_host)
-            photo, _keep_photo = _photo_groups(groups, [arr[i].n_views for i in range(n)])
-            _check(self._L.llcomp_mi_codec_decode_photo_warped_views_host(self._h, ptrs, lens, arr, n, photo, d_status, stream))
-            return
-        _check(self._L.llcomp_mi_codec_decode_warped_views_host(self._h, ptrs, lens, arr, n, d_status, stream))
+        ptrs, lens, _keep = _frame_containers(containers, self.frames, allow_none=True)
+        self._warped(True, (ptrs, lens), groups, d_status, stream)
 
     def warp_workspace_bytes(self, total_views):
         """the bound on .allocated_bytes() for warped views calls of up to total_views views with outputs no larger than the image

@@ -479,83 +479,110 @@ int windows_photo(llcomp_mi_codec* k, const PhotoTail& photo, const PhotoGroup& 
 }
 const PhotoGroup* photo_group(const PhotoTail* photo, size_t gi) { return photo && photo->groups[gi].active ? &photo->groups[gi] : nullptr; }
 
-// The resample passes of a tail, group by group and chunk by chunk, behind the classes: d_block is the tail's block in HBM.  A group
-// with photometric chains (photo, d_chains) writes plain U8 HWC into d_photo, pg->chunk views at a time, and windows_photo takes every
-// such chunk on to the group's output.
-int windows_resample(llcomp_mi_codec* k, const WindowsPlan& p, const ResampleTail& tail, const uint8_t* d_block, hipStream_t s,
-                     const PhotoTail* photo = nullptr, const llcomp_mi_photo_chain* d_chains = nullptr) {
-    const Geometry& g = k->g;
-    const ResizeFrame* d_rs = reinterpret_cast<const ResizeFrame*>(d_block);
-    const int32_t* d_w = reinterpret_cast<const int32_t*>(d_block + tail.block.w_at());
+// The groups of a tail, one by one behind the classes, timed in slot 6 with the crops: launch(vg, at, cnt, dst) puts views
+// [at, at + cnt) of group vg at dst.  A group without photometric chains is one such piece, all its views into its d_out.  A group
+// with chains (photo, d_chains) writes plain U8 HWC into d_photo, pg->chunk views at a time, and windows_photo takes every such chunk
+// on to the group's output; d_tables: the tail's output tables in HBM.
+template <class Group, class Launch>
+int windows_groups(llcomp_mi_codec* k, const std::vector<Group>& groups, const uint8_t* d_tables, const PhotoTail* photo,
+                   const llcomp_mi_photo_chain* d_chains, hipStream_t s, Launch&& launch) {
     Timed t(k, s, 6);
-    for (size_t gi = 0; gi < tail.groups.size(); ++gi) {
-        const ResampleGroup& vg = tail.groups[gi];
-        const PhotoGroup* pg = photo_group(photo, gi);
-        const uint64_t view_bytes = uint64_t(vg.oh) * vg.ow * g.c * vg.out.esize;
-        const uint32_t pchunk = pg ? pg->chunk : vg.n;
-        for (uint32_t pa = 0; pa < vg.n; pa += pchunk) {
-            const uint32_t pend = pa + std::min(pchunk, vg.n - pa);
-            for (uint32_t at = pa; at < pend; at += vg.chunk) {
-                const uint32_t cnt = std::min(vg.chunk, pend - at);
-                // (a padded call with a constant fill other than 0: the bias forms for a chunk that has an entry with a bias, and only for it)
-                const std::vector<uint8_t>& biased = tail.block.biased;
-                const bool bias = !biased.empty() && std::any_of(biased.begin() + vg.first + at, biased.begin() + vg.first + at + cnt, [](uint8_t b) { return b != 0; });
-                if (bias) ++k->host_counters[LLCOMP_MI_CTR_BIAS_LAUNCHES];
-                uint8_t* const dst = pg ? k->d_photo + (at - pa) * view_bytes : static_cast<uint8_t*>(vg.d_out) + at * view_bytes;
-                HIP_TRY(launch_resize_out(k->d_box, k->d_mid, dst, d_rs + vg.first + at, d_w, d_block + tail.block.tables_at() + vg.table_at, vg.out, cnt,
-                                          g.c, p.wmax, p.hmax, vg.mh, vg.ow, vg.oh, s, bias));
-            }
-            if (pg)
-                if (int rc = windows_photo(k, *photo, *pg, d_block + tail.block.tables_at(), d_chains, pa, pend - pa, s)) return rc;
-        }
-    }
-    return LLCOMP_MI_OK;
-}
-
-// The gather of a warp tail, group by group, behind the classes: d_block is the tail's block in HBM.  One launch per group, no
-// intermediate buffer; timed in slot 6 with the crops, like the resample passes.
-// A group with photometric chains is gathered pg->chunk views at a time into d_photo as plain U8 HWC, as in windows_resample.
-int windows_warp(llcomp_mi_codec* k, const WindowsPlan& p, const WarpTail& tail, const uint8_t* d_block, hipStream_t s,
-                 const PhotoTail* photo = nullptr, const llcomp_mi_photo_chain* d_chains = nullptr) {
-    const Geometry& g = k->g;
-    const WarpEntry* d_ws = reinterpret_cast<const WarpEntry*>(d_block);
-    const int32_t* d_tabs = reinterpret_cast<const int32_t*>(d_block + tail.tabs_at());
-    Timed t(k, s, 6);
-    for (size_t gi = 0; gi < tail.groups.size(); ++gi) {
-        const WarpOut& vg = tail.groups[gi];
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+        const Group& vg = groups[gi];
         const PhotoGroup* pg = photo_group(photo, gi);
         const uint32_t pchunk = pg ? pg->chunk : vg.n;
         for (uint32_t pa = 0; pa < vg.n; pa += pchunk) {
             const uint32_t cnt = std::min(pchunk, vg.n - pa);
-            HIP_TRY(launch_warp(k->d_box, d_ws + vg.first + pa, d_tabs, d_block + tail.fills_at() + vg.fill_at,
-                                d_block + tail.tables_at() + vg.table_at, vg.out, pg ? static_cast<void*>(k->d_photo) : vg.d_out, cnt, g.c, p.wmax,
-                                p.hmax, g.w, g.h, vg.ow, vg.oh, s));
+            if (int rc = launch(vg, pa, cnt, pg ? k->d_photo : static_cast<uint8_t*>(vg.d_out))) return rc;
             if (pg)
-                if (int rc = windows_photo(k, *photo, *pg, d_block + tail.tables_at(), d_chains, pa, cnt, s)) return rc;
+                if (int rc = windows_photo(k, *photo, *pg, d_tables, d_chains, pa, cnt, s)) return rc;
         }
     }
     return LLCOMP_MI_OK;
 }
 
-// Where a windowed decode finds its slices: the full batch in HBM (d_payload, payload_bytes, d_slice_len), or host containers with the
-// gather planned over the plan's windows (data, gather; d_payload is null then).
+// The resample passes of a tail, vg.chunk views per launch: d_block is the tail's block in HBM.
+int windows_resample(llcomp_mi_codec* k, const WindowsPlan& p, const ResampleTail& tail, const uint8_t* d_block, const PhotoTail* photo,
+                     const llcomp_mi_photo_chain* d_chains, hipStream_t s) {
+    const Geometry& g = k->g;
+    const ResizeFrame* d_rs = reinterpret_cast<const ResizeFrame*>(d_block);
+    const int32_t* d_w = reinterpret_cast<const int32_t*>(d_block + tail.block.w_at());
+    const uint8_t* const d_tables = d_block + tail.block.tables_at();
+    return windows_groups(k, tail.groups, d_tables, photo, d_chains, s, [&](const ResampleGroup& vg, uint32_t pa, uint32_t n, uint8_t* dst) -> int {
+        const uint64_t view_bytes = uint64_t(vg.oh) * vg.ow * g.c * vg.out.esize;
+        for (uint32_t at = pa; at < pa + n; at += vg.chunk) {
+            const uint32_t cnt = std::min(vg.chunk, pa + n - at);
+            // (a padded call with a constant fill other than 0: the bias forms for a chunk that has an entry with a bias, and only for it)
+            const std::vector<uint8_t>& biased = tail.block.biased;
+            const bool bias = !biased.empty() && std::any_of(biased.begin() + vg.first + at, biased.begin() + vg.first + at + cnt, [](uint8_t b) { return b != 0; });
+            if (bias) ++k->host_counters[LLCOMP_MI_CTR_BIAS_LAUNCHES];
+            HIP_TRY(launch_resize_out(k->d_box, k->d_mid, dst + (at - pa) * view_bytes, d_rs + vg.first + at, d_w, d_tables + vg.table_at, vg.out, cnt, g.c,
+                                      p.wmax, p.hmax, vg.mh, vg.ow, vg.oh, s, bias));
+        }
+        return LLCOMP_MI_OK;
+    });
+}
+
+// The gather of a warp tail: d_block is the tail's block in HBM.  One launch per piece -- per group, or per chunk of a group with
+// chains -- and no intermediate buffer.
+int windows_warp(llcomp_mi_codec* k, const WindowsPlan& p, const WarpTail& tail, const uint8_t* d_block, const PhotoTail* photo,
+                 const llcomp_mi_photo_chain* d_chains, hipStream_t s) {
+    const Geometry& g = k->g;
+    const WarpEntry* d_ws = reinterpret_cast<const WarpEntry*>(d_block);
+    const int32_t* d_tabs = reinterpret_cast<const int32_t*>(d_block + tail.tabs_at());
+    const uint8_t* const d_tables = d_block + tail.tables_at();
+    return windows_groups(k, tail.groups, d_tables, photo, d_chains, s, [&](const WarpOut& vg, uint32_t at, uint32_t cnt, uint8_t* dst) -> int {
+        HIP_TRY(launch_warp(k->d_box, d_ws + vg.first + at, d_tabs, d_block + tail.fills_at() + vg.fill_at, d_tables + vg.table_at, vg.out, dst, cnt, g.c,
+                            p.wmax, p.hmax, g.w, g.h, vg.ow, vg.oh, s));
+        return LLCOMP_MI_OK;
+    });
+}
+
+// Where a windowed decode finds its slices: the full batch in HBM (d_payload, payload_bytes, d_slice_len), or -- `host` -- the frames'
+// containers (data, lens) with the gather planned over the plan's windows (host_gather).
 struct WindowsSource {
     const void* d_payload;
     uint64_t payload_bytes;
     const void* d_slice_len;
     const uint8_t* const* data;
-    const RegionsGather* gather;
+    const size_t* lens;
+    bool host;
+    RegionsGather gather;
 };
+WindowsSource device_source(const void* d_payload, uint64_t payload_bytes, const void* d_slice_len) {
+    return WindowsSource{d_payload, payload_bytes, d_slice_len, nullptr, nullptr, false, {}};
+}
+WindowsSource host_source(const uint8_t* const* data, const size_t* lens) { return WindowsSource{nullptr, 0, nullptr, data, lens, true, {}}; }
+// What every windowed decode refuses before it plans anything: a null codec, source pointer or status word, and a table or status word
+// that is not 4-byte aligned
+bool source_ok(const llcomp_mi_codec* k, const WindowsSource& src, const void* d_status) {
+    if (!k || !d_status || misaligned(d_status, 4)) return false;
+    return src.host ? src.data && src.lens : src.d_payload && src.d_slice_len && !misaligned(src.d_slice_len, 4);
+}
 // The containers of a host source have to be of the codec's shape, tiling, planar setting and model ...
-bool same_shape(const Geometry& g, const Geometry& cg) {
+int same_shape(const Geometry& g, const Geometry& cg) {
     return cg.w == g.w && cg.h == g.h && cg.c == g.c && cg.tile_w == g.tile_w && cg.tile_h == g.tile_h && cg.planar == g.planar &&
-           (cg.flags & kGeoSmallModel) == (g.flags & kGeoSmallModel);
+                   (cg.flags & kGeoSmallModel) == (g.flags & kGeoSmallModel)
+               ? LLCOMP_MI_OK
+               : LLCOMP_MI_BAD_ARGS;
 }
 // ... and the gather's slices the classes' (its order is the table's: class by class, and a class's slices are its sub-geometry's)
-bool gather_matches(const WindowsPlan& p, const RegionsGather& gp) {
+int gather_matches(const WindowsPlan& p, const WindowsSource& src) {
     uint64_t sub_slices = 0;
     for (uint32_t i = 0; i < p.n_classes; ++i) sub_slices += p.classes[i].sub.n_slices;
-    return sub_slices == gp.n_slices;
+    return !src.host || sub_slices == src.gather.n_slices ? LLCOMP_MI_OK : LLCOMP_MI_HIP_ERROR;
+}
+// The gather of a host source over plan p's windows (container.cpp; nothing for a source in HBM), every error of which comes before
+// anything is queued: rects = a rectangle per frame, `used` = the plan's frame list or null for every frame.  A frame list that names
+// no frame (a warped views call whose every view is all fill) plans no gather: no container is looked at.
+int host_gather(const llcomp_mi_codec* k, WindowsSource& src, const WindowsPlan& p, const uint32_t* rects, const std::vector<uint32_t>* used) {
+    if (src.host && !(used && used->empty())) {
+        if (int rc = regions_gather_plan_sized(src.data, src.lens, k->g.frames, rects, p.wmax, p.hmax, src.gather, used ? used->data() : nullptr,
+                                               used ? uint32_t(used->size()) : 0))
+            return rc;
+        if (int rc = same_shape(k->g, src.gather.g)) return rc;
+    }
+    return gather_matches(p, src);
 }
 
 // the plan of a plain regions decode: every class crops the rectangle itself
@@ -566,28 +593,49 @@ int regions_plan(const llcomp_mi_codec* k, const uint32_t* xy, uint32_t rw, uint
     return regions_setup(k->g, k->tune, xy, rw, rh, p.tab.data(), p.classes, p.n_classes);
 }
 
-// The driver of every windowed decode (DESIGN.md "Region decode"): plan `p` -- every class crops p.wmax x p.hmax per entry -- from `src`,
-// into d_px, or with a tail into the boxes that the tail's groups are resampled from.  Everything the kernels read from the host crosses
+// A call as the driver takes it: the tail is none (the classes crop into d_px), a resample tail or a warp tail.
+struct WindowsTail {
+    const ResampleTail* resample = nullptr;
+    const WarpTail* warp = nullptr;
+    WindowsTail() = default;
+    WindowsTail(const ResampleTail& t) : resample(&t) {}
+    WindowsTail(const WarpTail& t) : warp(&t) {}
+    explicit operator bool() const { return resample || warp; }
+    uint64_t block_bytes() const { return resample ? resample->block.bytes() : warp ? warp->bytes() : 0; }
+};
+struct WindowsCall {
+    const WindowsPlan& plan;
+    WindowsTail tail;
+    const PhotoTail* photo;  // the chains beside the tail's groups; null for a call without a chain
+    uint64_t tables_bound;   // what the tail's block and the chains add to stage_bound at most
+    const WindowsSource& src;
+    void* d_px;              // a call without a tail
+};
+
+// The driver of every windowed decode (DESIGN.md "Region decode"): the call's plan -- every class crops wmax x hmax per entry -- from its
+// source into d_px, or with a tail into the boxes that the tail's groups are resampled from.  Everything the kernels read from the host crosses
 // in ONE copy out of a slot of the pinned ring (windows_plan.hpp: CopyLayout): the regions table; for a host source the window slices'
 // lengths, offsets and payload bytes behind it, so the classes read their slices straight from the copy and no group sums run; and the
 // tail's block at the next multiple of 16.  The copy lands in d_stage, grown up to stage_bound + tables_bound -- but the table alone of
 // a plain call from HBM in d_regions.  Each class takes a state generation of its own; for a source in HBM the full geometry's group
-// offsets are found once, ahead of the first class.  A third kind of tail (`warp`, in place of `tail`; warp_plan.hpp: WarpTail) carries the
-// block of a warped views decode in the same place of the copy and is gathered from the boxes by windows_warp; it has no d_mid.
-// `photo` (photo_plan.hpp: PhotoTail), beside either kind of tail: the views' photometric chains travel at the next multiple of 16
-// behind the tail's block, and the groups that have one go through d_photo (windows_photo).
-int decode_windows(llcomp_mi_codec* k, const WindowsPlan& p, const ResampleTail* tail, uint64_t tables_bound, const WindowsSource& src, void* d_px,
-                   void* d_status, void* stream, const WarpTail* warp = nullptr, const PhotoTail* photo = nullptr) {
+// offsets are found once, ahead of the first class.  A warp tail (warp_plan.hpp: WarpTail) carries the block of a warped views decode
+// in the same place of the copy and is gathered from the boxes by windows_warp; it has no d_mid.  `photo` (photo_plan.hpp: PhotoTail),
+// beside either kind of tail: the views' photometric chains travel at the next multiple of 16 behind the tail's block, and the groups
+// that have one go through d_photo (windows_photo).
+int decode_windows(llcomp_mi_codec* k, const WindowsCall& c, void* d_status, void* stream) {
     const Geometry& g = k->g;
-    const RegionsGather* gp = src.gather;
-    const CopyLayout cl(p.tab.size(), gp, tail);
+    const WindowsPlan& p = c.plan;
+    const WindowsSource& src = c.src;
+    const ResampleTail* tail = c.tail.resample;
+    const WarpTail* warp = c.tail.warp;
+    const PhotoTail* photo = c.photo;
+    const RegionsGather* gp = src.host ? &src.gather : nullptr;
+    const bool any_tail = bool(c.tail);
+    const CopyLayout cl(p.tab.size(), gp, any_tail, c.tail.block_bytes(), photo ? photo->bytes() : 0);
     const StageLayout& lay = cl.stage;
-    // (photometric chains, behind either kind of tail: the block of chains at the next multiple of 16)
-    const uint64_t rs_at = cl.rs_at, tail_end = warp ? rs_at + warp->bytes() : cl.bytes, photo_at = (tail_end + 15) & ~15ull;
-    const uint64_t bytes = photo ? photo_at + photo->bytes() : tail_end;
-    const bool any_tail = tail || warp;
+    const uint64_t bytes = cl.bytes;
     const bool table_only = !gp && !any_tail;
-    const uint64_t bound = table_only ? 0 : stage_bound(g) + tables_bound;
+    const uint64_t bound = table_only ? 0 : stage_bound(g) + c.tables_bound;
     DeviceGuard guard(k->device);
     if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
     if (!gp)
@@ -611,11 +659,11 @@ int decode_windows(llcomp_mi_codec* k, const WindowsPlan& p, const ResampleTail*
     uint8_t* h = k->h_regions[slot];
     std::memcpy(h, p.tab.data(), p.tab.size() * sizeof(RegionsFrame));
     if (gp) regions_gather_copy(*gp, src.data, h + lay.pay_at, reinterpret_cast<uint32_t*>(h + lay.len_at), reinterpret_cast<uint64_t*>(h + lay.off_at));
-    if (tail) tail->block.put(h + rs_at);
-    if (warp) warp->put(h + rs_at);
+    if (tail) tail->block.put(h + cl.rs_at);
+    if (warp) warp->put(h + cl.rs_at);
     if (photo) {
-        std::memset(h + tail_end, 0, size_t(photo_at - tail_end));
-        photo->put(h + photo_at);
+        std::memset(h + cl.block_end, 0, size_t(cl.chains_at - cl.block_end));
+        photo->put(h + cl.chains_at);
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     uint8_t* const d_copy = table_only ? reinterpret_cast<uint8_t*>(k->d_regions) : k->d_stage;
@@ -636,13 +684,13 @@ int decode_windows(llcomp_mi_codec* k, const WindowsPlan& p, const ResampleTail*
                                   : RegionsSource{static_cast<const uint8_t*>(src.d_payload), src.payload_bytes,
                                                   static_cast<const uint32_t*>(src.d_slice_len), nullptr, nullptr};
     if (int rc = regions_classes(k, p.classes, p.n_classes, reinterpret_cast<const RegionsFrame*>(d_copy), from, p.wmax, p.hmax,
-                                 any_tail ? k->d_box : static_cast<uint8_t*>(d_px), static_cast<uint32_t*>(d_status), s))
+                                 any_tail ? k->d_box : static_cast<uint8_t*>(c.d_px), static_cast<uint32_t*>(d_status), s))
         return rc;
-    const llcomp_mi_photo_chain* d_chains = photo ? reinterpret_cast<const llcomp_mi_photo_chain*>(k->d_stage + photo_at) : nullptr;
+    const llcomp_mi_photo_chain* d_chains = photo ? reinterpret_cast<const llcomp_mi_photo_chain*>(k->d_stage + cl.chains_at) : nullptr;
     if (tail)
-        if (int rc = windows_resample(k, p, *tail, k->d_stage + rs_at, s, photo, d_chains)) return rc;
+        if (int rc = windows_resample(k, p, *tail, k->d_stage + cl.rs_at, photo, d_chains, s)) return rc;
     if (warp)
-        if (int rc = windows_warp(k, p, *warp, k->d_stage + rs_at, s, photo, d_chains)) return rc;
+        if (int rc = windows_warp(k, p, *warp, k->d_stage + cl.rs_at, photo, d_chains, s)) return rc;
     ++k->n_decode;
     return LLCOMP_MI_OK;
 }
@@ -1212,189 +1260,50 @@ uint32_t llcomp_mi_codec_regions_family(const llcomp_mi_codec* k, const uint32_t
     return p.n_classes;
 }
 
-// The windowed decodes (DESIGN.md "Region decode"; "Crops of different sizes, resized to one shape"; "Several views of each frame"): each
-// checks its pointers, builds its plan (windows_plan.hpp) -- for host containers also the gather over the plan's windows (container.cpp),
-// whose every error comes before anything is queued -- and hands both to decode_windows.
-// Regions decode: the region decode, class by class (geometry.hpp: regions_window), in order on the caller's stream.
-int llcomp_mi_codec_decode_regions(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
-                                   const uint32_t* xy, uint32_t rw, uint32_t rh, void* d_px, void* d_status, void* stream) {
-    if (!k || !d_payload || !d_slice_len || !d_px || !d_status || !xy) return LLCOMP_MI_BAD_ARGS;
-    if (misaligned(d_slice_len, 4) || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
-    WindowsPlan p;
-    if (int rc = regions_plan(k, xy, rw, rh, p)) return rc;
-    return decode_windows(k, p, nullptr, 0, WindowsSource{d_payload, payload_bytes, d_slice_len, nullptr, nullptr}, d_px, d_status, stream);
-}
-
-// ... of host containers: only the window slices' bytes cross to the GPU.
-int llcomp_mi_codec_decode_regions_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens, const uint32_t* xy, uint32_t rw,
-                                        uint32_t rh, void* d_px, void* d_status, void* stream) {
-    if (!k || !data || !lens || !d_px || !d_status || !xy || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
-    RegionsGather gp;
-    if (int rc = regions_gather_plan(data, lens, k->g.frames, xy, rw, rh, gp)) return rc;
-    if (!same_shape(k->g, gp.g)) return LLCOMP_MI_BAD_ARGS;
-    WindowsPlan p;
-    if (int rc = regions_plan(k, xy, rw, rh, p)) return rc;
-    if (!gather_matches(p, gp)) return LLCOMP_MI_HIP_ERROR;
-    return decode_windows(k, p, nullptr, 0, WindowsSource{nullptr, 0, nullptr, data, &gp}, d_px, d_status, stream);
-}
-
-// Resized regions decode: the classes crop every frame's box (the batch's largest rectangle size) into d_box; then the two resample passes
-// read every frame's rectangle from its box and write d_px, the vertical pass through the output format's table where there is one.
-int llcomp_mi_codec_decode_resized_regions_ex(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
-                                              const uint32_t* rects, const uint8_t* flags, uint32_t ow, uint32_t oh,
-                                              const llcomp_mi_output_format* fmt, void* d_px, void* d_status, void* stream) {
-    if (!k || !d_payload || !d_slice_len || !d_px || !d_status || !rects) return LLCOMP_MI_BAD_ARGS;
-    if (misaligned(d_slice_len, 4) || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
-    ResizedPlan p;
-    if (int rc = resized_setup(k->g, k->tune, rects, flags, ow, oh, fmt, d_px, p)) return rc;
-    return decode_windows(k, p, &p.tail, resized_tables_bound(k->g), WindowsSource{d_payload, payload_bytes, d_slice_len, nullptr, nullptr}, nullptr,
-                          d_status, stream);
-}
-
-// ... of host containers: the gather with every window sized for the largest rectangle.
-int llcomp_mi_codec_decode_resized_regions_host_ex(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens, const uint32_t* rects,
-                                                   const uint8_t* flags, uint32_t ow, uint32_t oh, const llcomp_mi_output_format* fmt,
-                                                   void* d_px, void* d_status, void* stream) {
-    if (!k || !data || !lens || !d_px || !d_status || !rects || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
-    ResizedPlan p;
-    if (int rc = resized_setup(k->g, k->tune, rects, flags, ow, oh, fmt, d_px, p)) return rc;
-    RegionsGather gp;
-    if (int rc = regions_gather_plan_sized(data, lens, k->g.frames, rects, p.wmax, p.hmax, gp)) return rc;
-    if (!same_shape(k->g, gp.g)) return LLCOMP_MI_BAD_ARGS;
-    if (!gather_matches(p, gp)) return LLCOMP_MI_HIP_ERROR;
-    return decode_windows(k, p, &p.tail, resized_tables_bound(k->g), WindowsSource{nullptr, 0, nullptr, data, &gp}, nullptr, d_status, stream);
-}
-
-int llcomp_mi_codec_decode_resized_regions(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
-                                           const uint32_t* rects, const uint8_t* flags, uint32_t ow, uint32_t oh, void* d_px, void* d_status,
-                                           void* stream) {
-    return llcomp_mi_codec_decode_resized_regions_ex(k, d_payload, payload_bytes, d_slice_len, rects, flags, ow, oh, nullptr, d_px, d_status,
-                                                     stream);
-}
-int llcomp_mi_codec_decode_resized_regions_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens, const uint32_t* rects,
-                                                const uint8_t* flags, uint32_t ow, uint32_t oh, void* d_px, void* d_status, void* stream) {
-    return llcomp_mi_codec_decode_resized_regions_host_ex(k, data, lens, rects, flags, ow, oh, nullptr, d_px, d_status, stream);
-}
-
-// Views decode: the resized regions decode on the used frames' union rectangles up to the boxes -- the classes unchanged, over the frame
-// list -- then every group's views resampled from their frames' boxes.
-int llcomp_mi_codec_decode_views(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
-                                 const llcomp_mi_view_group* groups, uint32_t n_groups, void* d_status, void* stream) {
-    if (!k || !d_payload || !d_slice_len || !d_status) return LLCOMP_MI_BAD_ARGS;
-    if (misaligned(d_slice_len, 4) || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
-    ViewsPlan p;
-    if (int rc = views_setup(k->g, k->tune, groups, n_groups, p)) return rc;
-    return decode_windows(k, p, &p.tail, views_tables_bound(k->g, p.u.total_views), WindowsSource{d_payload, payload_bytes, d_slice_len, nullptr, nullptr},
-                          nullptr, d_status, stream);
-}
-
-// ... of host containers: the gather over the used frames' union rectangles (a frame without a view is not looked at: its container may
-// be NULL).
-int llcomp_mi_codec_decode_views_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens, const llcomp_mi_view_group* groups,
-                                      uint32_t n_groups, void* d_status, void* stream) {
-    if (!k || !data || !lens || !d_status || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
-    ViewsPlan p;
-    if (int rc = views_setup(k->g, k->tune, groups, n_groups, p)) return rc;
-    RegionsGather gp;
-    if (int rc = regions_gather_plan_sized(data, lens, k->g.frames, p.u.rects.data(), p.wmax, p.hmax, gp, p.u.used.data(), uint32_t(p.u.used.size())))
-        return rc;
-    if (!same_shape(k->g, gp.g)) return LLCOMP_MI_BAD_ARGS;
-    if (!gather_matches(p, gp)) return LLCOMP_MI_HIP_ERROR;
-    return decode_windows(k, p, &p.tail, views_tables_bound(k->g, p.u.total_views), WindowsSource{nullptr, 0, nullptr, data, &gp}, nullptr, d_status,
-                          stream);
-}
-
-// The padded calls: the plans of the resized and the views decode on the SOURCE rectangles (windows_plan.hpp: padded_setup,
-// padded_views_setup), driven as they are; the gather of a host source is the unpadded call's over the source rectangles.
-int llcomp_mi_codec_decode_padded_regions(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
-                                          const int32_t* rects, const uint8_t* flags, uint32_t ow, uint32_t oh, const llcomp_mi_pad* pad,
-                                          const llcomp_mi_output_format* fmt, void* d_px, void* d_status, void* stream) {
-    if (!k || !d_payload || !d_slice_len || !d_px || !d_status || !rects) return LLCOMP_MI_BAD_ARGS;
-    if (misaligned(d_slice_len, 4) || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
-    ResizedPlan p;
-    std::vector<uint32_t> src;
-    if (int rc = padded_setup(k->g, k->tune, rects, flags, ow, oh, pad, fmt, d_px, p, src)) return rc;
-    return decode_windows(k, p, &p.tail, padded_tables_bound(k->g, k->g.frames), WindowsSource{d_payload, payload_bytes, d_slice_len, nullptr, nullptr},
-                          nullptr, d_status, stream);
-}
-
-int llcomp_mi_codec_decode_padded_regions_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens, const int32_t* rects,
-                                               const uint8_t* flags, uint32_t ow, uint32_t oh, const llcomp_mi_pad* pad,
-                                               const llcomp_mi_output_format* fmt, void* d_px, void* d_status, void* stream) {
-    if (!k || !data || !lens || !d_px || !d_status || !rects || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
-    ResizedPlan p;
-    std::vector<uint32_t> src;  // the source rectangles: what the gather is planned over
-    if (int rc = padded_setup(k->g, k->tune, rects, flags, ow, oh, pad, fmt, d_px, p, src)) return rc;
-    RegionsGather gp;
-    if (int rc = regions_gather_plan_sized(data, lens, k->g.frames, src.data(), p.wmax, p.hmax, gp)) return rc;
-    if (!same_shape(k->g, gp.g)) return LLCOMP_MI_BAD_ARGS;
-    if (!gather_matches(p, gp)) return LLCOMP_MI_HIP_ERROR;
-    return decode_windows(k, p, &p.tail, padded_tables_bound(k->g, k->g.frames), WindowsSource{nullptr, 0, nullptr, data, &gp}, nullptr, d_status,
-                          stream);
-}
-
-int llcomp_mi_codec_decode_padded_views(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
-                                        const llcomp_mi_view_group* groups, uint32_t n_groups, const llcomp_mi_pad* pad, void* d_status,
-                                        void* stream) {
-    if (!k || !d_payload || !d_slice_len || !d_status) return LLCOMP_MI_BAD_ARGS;
-    if (misaligned(d_slice_len, 4) || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
-    ViewsPlan p;
-    if (int rc = padded_views_setup(k->g, k->tune, groups, n_groups, pad, p)) return rc;
-    return decode_windows(k, p, &p.tail, padded_tables_bound(k->g, p.u.total_views), WindowsSource{d_payload, payload_bytes, d_slice_len, nullptr, nullptr},
-                          nullptr, d_status, stream);
-}
-
-int llcomp_mi_codec_decode_padded_views_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens,
-                                             const llcomp_mi_view_group* groups, uint32_t n_groups, const llcomp_mi_pad* pad, void* d_status,
-                                             void* stream) {
-    if (!k || !data || !lens || !d_status || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
-    ViewsPlan p;
-    if (int rc = padded_views_setup(k->g, k->tune, groups, n_groups, pad, p)) return rc;
-    RegionsGather gp;
-    if (int rc = regions_gather_plan_sized(data, lens, k->g.frames, p.u.rects.data(), p.wmax, p.hmax, gp, p.u.used.data(), uint32_t(p.u.used.size())))
-        return rc;
-    if (!same_shape(k->g, gp.g)) return LLCOMP_MI_BAD_ARGS;
-    if (!gather_matches(p, gp)) return LLCOMP_MI_HIP_ERROR;
-    return decode_windows(k, p, &p.tail, padded_tables_bound(k->g, p.u.total_views), WindowsSource{nullptr, 0, nullptr, data, &gp}, nullptr,
-                          d_status, stream);
-}
-
-// Warped views: the views decode on the views' SOURCE rectangles up to the boxes (warp_plan.hpp: warp_setup -- views_union and
-// regions_setup_sized, unchanged), then the third kind of tail: one gather launch per group reads every view from its frame's box.
-int llcomp_mi_codec_decode_warped_views(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
-                                        const llcomp_mi_warp_group* groups, uint32_t n_groups, void* d_status, void* stream) {
-    if (!k || !d_payload || !d_slice_len || !d_status) return LLCOMP_MI_BAD_ARGS;
-    if (misaligned(d_slice_len, 4) || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
-    WarpPlan p;
-    if (int rc = warp_setup(k->g, k->tune, groups, n_groups, p)) return rc;
-    return decode_windows(k, p, nullptr, warp_tables_bound(k->g, p.total_views), WindowsSource{d_payload, payload_bytes, d_slice_len, nullptr, nullptr},
-                          nullptr, d_status, stream, &p.tail);
-}
-
-// ... of host containers: the gather over the used frames' union rectangles; with no used frame (every view all fill) nothing is read.
-int llcomp_mi_codec_decode_warped_views_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens,
-                                             const llcomp_mi_warp_group* groups, uint32_t n_groups, void* d_status, void* stream) {
-    if (!k || !data || !lens || !d_status || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
-    WarpPlan p;
-    if (int rc = warp_setup(k->g, k->tune, groups, n_groups, p)) return rc;
-    RegionsGather gp;
-    if (!p.u.used.empty()) {
-        if (int rc = regions_gather_plan_sized(data, lens, k->g.frames, p.u.rects.data(), p.wmax, p.hmax, gp, p.u.used.data(), uint32_t(p.u.used.size())))
-            return rc;
-        if (!same_shape(k->g, gp.g)) return LLCOMP_MI_BAD_ARGS;
-    }
-    if (!gather_matches(p, gp)) return LLCOMP_MI_HIP_ERROR;
-    return decode_windows(k, p, nullptr, warp_tables_bound(k->g, p.total_views), WindowsSource{nullptr, 0, nullptr, data, &gp}, nullptr, d_status,
-                          stream, &p.tail);
-}
-
-// The photometric calls: the plan of the call they extend, then the chains beside its groups (photo_plan.hpp: photo_setup).  A group
-// with a chain hands its output -- format, table and d_out -- over to the chain's last step and becomes a plain U8 HWC group whose
-// output is the staging buffer (windows_resample / windows_warp put the address in); with no chain at all the extended call runs as it is.
 }  // extern "C"
 
 namespace {
 
+// The windowed decodes (DESIGN.md "Region decode"; "Crops of different sizes, resized to one shape"; "Several views of each frame"): one
+// body per family, behind the entry points below, from either kind of source.  Each refuses its pointers (source_ok), builds its plan
+// (windows_plan.hpp) -- for host containers also the gather over the plan's windows (host_gather) -- and hands both to decode_windows;
+// every refusal comes before anything is queued or grown.
+
+// Regions decode: the region decode, class by class (geometry.hpp: regions_window), in order on the caller's stream.  Of host
+// containers only the window slices' bytes cross to the GPU -- and this call alone plans its gather AHEAD of its windows: an input
+// that is wrong in both ways keeps the gather's status.
+int regions_call(llcomp_mi_codec* k, WindowsSource src, const uint32_t* xy, uint32_t rw, uint32_t rh, void* d_px, void* d_status, void* stream) {
+    if (!source_ok(k, src, d_status) || !d_px || !xy) return LLCOMP_MI_BAD_ARGS;
+    if (src.host) {
+        if (int rc = regions_gather_plan(src.data, src.lens, k->g.frames, xy, rw, rh, src.gather)) return rc;
+        if (int rc = same_shape(k->g, src.gather.g)) return rc;
+    }
+    WindowsPlan p;
+    if (int rc = regions_plan(k, xy, rw, rh, p)) return rc;
+    if (int rc = gather_matches(p, src)) return rc;
+    return decode_windows(k, WindowsCall{p, {}, nullptr, 0, src, d_px}, d_status, stream);
+}
+
+// Resized regions decode: the classes crop every frame's box (the batch's largest rectangle size) into d_box; then the two resample passes
+// read every frame's rectangle from its box and write d_px, the vertical pass through the output format's table where there is one.
+// padded (rects are int32 then, and may leave the image): the plan on the SOURCE rectangles (windows_plan.hpp: padded_setup), driven as
+// it is.  The gather of a host source has every window sized for the largest rectangle -- a padded call's over the source rectangles.
+int resized_call(llcomp_mi_codec* k, WindowsSource src, const void* rects, const uint8_t* flags, uint32_t ow, uint32_t oh, bool padded,
+                 const llcomp_mi_pad* pad, const llcomp_mi_output_format* fmt, void* d_px, void* d_status, void* stream) {
+    if (!source_ok(k, src, d_status) || !d_px || !rects) return LLCOMP_MI_BAD_ARGS;
+    ResizedPlan p;
+    std::vector<uint32_t> from;  // a padded call's source rectangles
+    if (int rc = padded ? padded_setup(k->g, k->tune, static_cast<const int32_t*>(rects), flags, ow, oh, pad, fmt, d_px, p, from)
+                        : resized_setup(k->g, k->tune, static_cast<const uint32_t*>(rects), flags, ow, oh, fmt, d_px, p))
+        return rc;
+    if (int rc = host_gather(k, src, p, padded ? from.data() : static_cast<const uint32_t*>(rects), nullptr)) return rc;
+    const uint64_t bound = padded ? padded_tables_bound(k->g, k->g.frames) : resized_tables_bound(k->g);
+    return decode_windows(k, WindowsCall{p, p.tail, nullptr, bound, src, nullptr}, d_status, stream);
+}
+
+// The chains beside a tail's groups (photo_plan.hpp: photo_setup; photo: one entry per group, or null for a call without chains, which
+// leaves pt.any() false and the groups as they are).  A group with a chain hands its output -- format, table and d_out -- over to the
+// chain's last step and becomes a plain U8 HWC group whose output is the staging buffer (windows_groups puts the address in).
 template <class Group>
 int photo_tail_of(const Geometry& g, std::vector<Group>& groups, const llcomp_mi_photo_group* photo, PhotoTail& pt) {
     std::vector<uint32_t> n, ow, oh;
@@ -1417,80 +1326,127 @@ int photo_tail_of(const Geometry& g, std::vector<Group>& groups, const llcomp_mi
     return LLCOMP_MI_OK;
 }
 
-// dev: the batch in HBM, or null for host containers (data, lens)
-int photo_views(llcomp_mi_codec* k, const WindowsSource* dev, const uint8_t* const* data, const size_t* lens, const llcomp_mi_view_group* groups,
-                       uint32_t n_groups, const llcomp_mi_pad* pad, const llcomp_mi_photo_group* photo, void* d_status, void* stream) {
+// Views decode: the resized regions decode on the used frames' union rectangles up to the boxes -- the classes unchanged, over the frame
+// list -- then every group's views resampled from their frames' boxes.  padded: padded_views_setup, as in resized_call.  The gather of a
+// host source runs over the used frames' union rectangles (a frame without a view is not looked at: its container may be NULL).
+int views_call(llcomp_mi_codec* k, WindowsSource src, const llcomp_mi_view_group* groups, uint32_t n_groups, bool padded, const llcomp_mi_pad* pad,
+               const llcomp_mi_photo_group* photo, void* d_status, void* stream) {
+    if (!source_ok(k, src, d_status)) return LLCOMP_MI_BAD_ARGS;
     ViewsPlan p;
-    if (int rc = pad ? padded_views_setup(k->g, k->tune, groups, n_groups, pad, p) : views_setup(k->g, k->tune, groups, n_groups, p)) return rc;
+    if (int rc = padded ? padded_views_setup(k->g, k->tune, groups, n_groups, pad, p) : views_setup(k->g, k->tune, groups, n_groups, p)) return rc;
     PhotoTail pt;
     if (int rc = photo_tail_of(k->g, p.tail.groups, photo, pt)) return rc;
-    const uint64_t bound = (pad ? padded_tables_bound(k->g, p.u.total_views) : views_tables_bound(k->g, p.u.total_views)) +
+    if (int rc = host_gather(k, src, p, p.u.rects.data(), &p.u.used)) return rc;
+    const uint64_t bound = (padded ? padded_tables_bound(k->g, p.u.total_views) : views_tables_bound(k->g, p.u.total_views)) +
                            (pt.any() ? photo_tables_bound(p.u.total_views) : 0);
-    RegionsGather gp;
-    if (!dev) {
-        if (int rc = regions_gather_plan_sized(data, lens, k->g.frames, p.u.rects.data(), p.wmax, p.hmax, gp, p.u.used.data(), uint32_t(p.u.used.size())))
-            return rc;
-        if (!same_shape(k->g, gp.g)) return LLCOMP_MI_BAD_ARGS;
-        if (!gather_matches(p, gp)) return LLCOMP_MI_HIP_ERROR;
-    }
-    return decode_windows(k, p, &p.tail, bound, dev ? *dev : WindowsSource{nullptr, 0, nullptr, data, &gp}, nullptr, d_status, stream, nullptr,
-                          pt.any() ? &pt : nullptr);
+    return decode_windows(k, WindowsCall{p, p.tail, pt.any() ? &pt : nullptr, bound, src, nullptr}, d_status, stream);
 }
 
-int photo_warped_views(llcomp_mi_codec* k, const WindowsSource* dev, const uint8_t* const* data, const size_t* lens,
-                              const llcomp_mi_warp_group* groups, uint32_t n_groups, const llcomp_mi_photo_group* photo, void* d_status, void* stream) {
+// Warped views: the views decode on the views' SOURCE rectangles up to the boxes (warp_plan.hpp: warp_setup -- views_union and
+// regions_setup_sized, unchanged), then the warp tail: one gather launch per group reads every view from its frame's box.  With no
+// used frame (every view all fill) nothing is read.
+int warped_call(llcomp_mi_codec* k, WindowsSource src, const llcomp_mi_warp_group* groups, uint32_t n_groups, const llcomp_mi_photo_group* photo,
+                void* d_status, void* stream) {
+    if (!source_ok(k, src, d_status)) return LLCOMP_MI_BAD_ARGS;
     WarpPlan p;
     if (int rc = warp_setup(k->g, k->tune, groups, n_groups, p)) return rc;
     PhotoTail pt;
     if (int rc = photo_tail_of(k->g, p.tail.groups, photo, pt)) return rc;
+    if (int rc = host_gather(k, src, p, p.u.rects.data(), &p.u.used)) return rc;
     const uint64_t bound = warp_tables_bound(k->g, p.total_views) + (pt.any() ? photo_tables_bound(p.total_views) : 0);
-    RegionsGather gp;
-    if (!dev) {
-        if (!p.u.used.empty()) {
-            if (int rc = regions_gather_plan_sized(data, lens, k->g.frames, p.u.rects.data(), p.wmax, p.hmax, gp, p.u.used.data(), uint32_t(p.u.used.size())))
-                return rc;
-            if (!same_shape(k->g, gp.g)) return LLCOMP_MI_BAD_ARGS;
-        }
-        if (!gather_matches(p, gp)) return LLCOMP_MI_HIP_ERROR;
-    }
-    return decode_windows(k, p, nullptr, bound, dev ? *dev : WindowsSource{nullptr, 0, nullptr, data, &gp}, nullptr, d_status, stream, &p.tail,
-                          pt.any() ? &pt : nullptr);
+    return decode_windows(k, WindowsCall{p, p.tail, pt.any() ? &pt : nullptr, bound, src, nullptr}, d_status, stream);
 }
 
 }  // namespace
 
 extern "C" {
 
+int llcomp_mi_codec_decode_regions(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                   const uint32_t* xy, uint32_t rw, uint32_t rh, void* d_px, void* d_status, void* stream) {
+    return regions_call(k, device_source(d_payload, payload_bytes, d_slice_len), xy, rw, rh, d_px, d_status, stream);
+}
+int llcomp_mi_codec_decode_regions_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens, const uint32_t* xy, uint32_t rw,
+                                        uint32_t rh, void* d_px, void* d_status, void* stream) {
+    return regions_call(k, host_source(data, lens), xy, rw, rh, d_px, d_status, stream);
+}
+
+int llcomp_mi_codec_decode_resized_regions_ex(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                              const uint32_t* rects, const uint8_t* flags, uint32_t ow, uint32_t oh,
+                                              const llcomp_mi_output_format* fmt, void* d_px, void* d_status, void* stream) {
+    return resized_call(k, device_source(d_payload, payload_bytes, d_slice_len), rects, flags, ow, oh, false, nullptr, fmt, d_px, d_status, stream);
+}
+int llcomp_mi_codec_decode_resized_regions_host_ex(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens, const uint32_t* rects,
+                                                   const uint8_t* flags, uint32_t ow, uint32_t oh, const llcomp_mi_output_format* fmt,
+                                                   void* d_px, void* d_status, void* stream) {
+    return resized_call(k, host_source(data, lens), rects, flags, ow, oh, false, nullptr, fmt, d_px, d_status, stream);
+}
+int llcomp_mi_codec_decode_resized_regions(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                           const uint32_t* rects, const uint8_t* flags, uint32_t ow, uint32_t oh, void* d_px, void* d_status,
+                                           void* stream) {
+    return resized_call(k, device_source(d_payload, payload_bytes, d_slice_len), rects, flags, ow, oh, false, nullptr, nullptr, d_px, d_status, stream);
+}
+int llcomp_mi_codec_decode_resized_regions_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens, const uint32_t* rects,
+                                                const uint8_t* flags, uint32_t ow, uint32_t oh, void* d_px, void* d_status, void* stream) {
+    return resized_call(k, host_source(data, lens), rects, flags, ow, oh, false, nullptr, nullptr, d_px, d_status, stream);
+}
+int llcomp_mi_codec_decode_padded_regions(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                          const int32_t* rects, const uint8_t* flags, uint32_t ow, uint32_t oh, const llcomp_mi_pad* pad,
+                                          const llcomp_mi_output_format* fmt, void* d_px, void* d_status, void* stream) {
+    return resized_call(k, device_source(d_payload, payload_bytes, d_slice_len), rects, flags, ow, oh, true, pad, fmt, d_px, d_status, stream);
+}
+int llcomp_mi_codec_decode_padded_regions_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens, const int32_t* rects,
+                                               const uint8_t* flags, uint32_t ow, uint32_t oh, const llcomp_mi_pad* pad,
+                                               const llcomp_mi_output_format* fmt, void* d_px, void* d_status, void* stream) {
+    return resized_call(k, host_source(data, lens), rects, flags, ow, oh, true, pad, fmt, d_px, d_status, stream);
+}
+
+int llcomp_mi_codec_decode_views(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                 const llcomp_mi_view_group* groups, uint32_t n_groups, void* d_status, void* stream) {
+    return views_call(k, device_source(d_payload, payload_bytes, d_slice_len), groups, n_groups, false, nullptr, nullptr, d_status, stream);
+}
+int llcomp_mi_codec_decode_views_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens, const llcomp_mi_view_group* groups,
+                                      uint32_t n_groups, void* d_status, void* stream) {
+    return views_call(k, host_source(data, lens), groups, n_groups, false, nullptr, nullptr, d_status, stream);
+}
+int llcomp_mi_codec_decode_padded_views(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                        const llcomp_mi_view_group* groups, uint32_t n_groups, const llcomp_mi_pad* pad, void* d_status,
+                                        void* stream) {
+    return views_call(k, device_source(d_payload, payload_bytes, d_slice_len), groups, n_groups, true, pad, nullptr, d_status, stream);
+}
+int llcomp_mi_codec_decode_padded_views_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens,
+                                             const llcomp_mi_view_group* groups, uint32_t n_groups, const llcomp_mi_pad* pad, void* d_status,
+                                             void* stream) {
+    return views_call(k, host_source(data, lens), groups, n_groups, true, pad, nullptr, d_status, stream);
+}
+// (the photometric calls: a NULL pad is the unpadded call)
 int llcomp_mi_codec_decode_photo_views(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
                                        const llcomp_mi_view_group* groups, uint32_t n_groups, const llcomp_mi_pad* pad,
                                        const llcomp_mi_photo_group* photo, void* d_status, void* stream) {
-    if (!k || !d_payload || !d_slice_len || !d_status) return LLCOMP_MI_BAD_ARGS;
-    if (misaligned(d_slice_len, 4) || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
-    const WindowsSource dev{d_payload, payload_bytes, d_slice_len, nullptr, nullptr};
-    return photo_views(k, &dev, nullptr, nullptr, groups, n_groups, pad, photo, d_status, stream);
+    return views_call(k, device_source(d_payload, payload_bytes, d_slice_len), groups, n_groups, pad != nullptr, pad, photo, d_status, stream);
 }
-
 int llcomp_mi_codec_decode_photo_views_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens,
                                             const llcomp_mi_view_group* groups, uint32_t n_groups, const llcomp_mi_pad* pad,
                                             const llcomp_mi_photo_group* photo, void* d_status, void* stream) {
-    if (!k || !data || !lens || !d_status || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
-    return photo_views(k, nullptr, data, lens, groups, n_groups, pad, photo, d_status, stream);
+    return views_call(k, host_source(data, lens), groups, n_groups, pad != nullptr, pad, photo, d_status, stream);
 }
 
+int llcomp_mi_codec_decode_warped_views(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                        const llcomp_mi_warp_group* groups, uint32_t n_groups, void* d_status, void* stream) {
+    return warped_call(k, device_source(d_payload, payload_bytes, d_slice_len), groups, n_groups, nullptr, d_status, stream);
+}
+int llcomp_mi_codec_decode_warped_views_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens,
+                                             const llcomp_mi_warp_group* groups, uint32_t n_groups, void* d_status, void* stream) {
+    return warped_call(k, host_source(data, lens), groups, n_groups, nullptr, d_status, stream);
+}
 int llcomp_mi_codec_decode_photo_warped_views(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
                                               const llcomp_mi_warp_group* groups, uint32_t n_groups, const llcomp_mi_photo_group* photo,
                                               void* d_status, void* stream) {
-    if (!k || !d_payload || !d_slice_len || !d_status) return LLCOMP_MI_BAD_ARGS;
-    if (misaligned(d_slice_len, 4) || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
-    const WindowsSource dev{d_payload, payload_bytes, d_slice_len, nullptr, nullptr};
-    return photo_warped_views(k, &dev, nullptr, nullptr, groups, n_groups, photo, d_status, stream);
+    return warped_call(k, device_source(d_payload, payload_bytes, d_slice_len), groups, n_groups, photo, d_status, stream);
 }
-
 int llcomp_mi_codec_decode_photo_warped_views_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens,
                                                    const llcomp_mi_warp_group* groups, uint32_t n_groups, const llcomp_mi_photo_group* photo,
                                                    void* d_status, void* stream) {
-    if (!k || !data || !lens || !d_status || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
-    return photo_warped_views(k, nullptr, data, lens, groups, n_groups, photo, d_status, stream);
+    return warped_call(k, host_source(data, lens), groups, n_groups, photo, d_status, stream);
 }
 
 uint64_t llcomp_mi_codec_photo_workspace_bytes(const llcomp_mi_codec* k, uint64_t total_views) {

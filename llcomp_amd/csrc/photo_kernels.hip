@@ -437,24 +437,6 @@ __global__ __launch_bounds__(256) void k_photo_sharp(uint8_t* __restrict__ px, c
     }
 }
 
-template <int C, int E, bool CHW, bool LUT>
-void launch_sharp(dim3 grid, uint32_t lds, hipStream_t s, uint8_t* d_px, const llcomp_mi_photo_chain* d_chains, const uint8_t* d_halo,
-                  const void* d_table, void* d_out, uint32_t ow, uint32_t oh, uint32_t band_rows, uint64_t halo_stride, uint32_t step) {
-    k_photo_sharp<C, E, CHW, LUT><<<grid, dim3(256), lds, s>>>(d_px, d_chains, d_halo, d_table, d_out, ow, oh, band_rows, halo_stride, step);
-}
-
-template <int C, int E, bool CHW, bool LUT>
-void launch_blur_cols(dim3 grid, hipStream_t s, uint8_t* d_px, const llcomp_mi_photo_chain* d_chains, const void* d_table, void* d_out, uint32_t ow,
-                      uint32_t oh, uint32_t step) {
-    k_photo_blur_cols<C, E, CHW, LUT><<<grid, dim3(256), 0, s>>>(d_px, d_chains, d_table, d_out, ow, oh, step);
-}
-
-template <int C, int E, bool CHW, bool LUT>
-void launch_apply(dim3 grid, hipStream_t s, uint8_t* d_px, const llcomp_mi_photo_chain* d_chains, const uint8_t* d_luts, const void* d_table,
-                  void* d_out, uint64_t npix, uint32_t step) {
-    k_photo_apply<C, E, CHW, LUT><<<grid, dim3(256), 0, s>>>(d_px, d_chains, d_luts, d_table, d_out, npix, step);
-}
-
 template <int C>
 hipError_t launch_step_c(uint8_t* d_px, const llcomp_mi_photo_chain* d_chains, uint8_t* d_stats, uint8_t* d_luts, const void* d_table,
                          const OutFormat& o, void* d_out, uint32_t views, uint32_t ow, uint32_t oh, uint32_t step, bool stats, bool table, bool area,
@@ -468,30 +450,15 @@ hipError_t launch_step_c(uint8_t* d_px, const llcomp_mi_photo_chain* d_chains, u
     }
     if (table) k_photo_lut<C><<<dim3(views), dim3(64), 0, s>>>(d_chains, d_stats, d_luts, npix, step);
     const dim3 grid(uint32_t((npix + 1023) / 1024), views);
-    const bool chw = o.layout == LLCOMP_MI_LAYOUT_CHW;
-#define LLMI_PHOTO(E, CHW, LUT) launch_apply<C, E, CHW, LUT>(grid, s, d_px, d_chains, d_luts, d_table, d_out, npix, step)
-    if (o.plain)
-        LLMI_PHOTO(1, false, false);
-    else if (o.esize == 1)  // (U8 CHW: U8 HWC is plain)
-        LLMI_PHOTO(1, true, true);
-    else if (o.esize == 2)
-        chw ? LLMI_PHOTO(2, true, true) : LLMI_PHOTO(2, false, true);
-    else
-        chw ? LLMI_PHOTO(4, true, true) : LLMI_PHOTO(4, false, true);
-#undef LLMI_PHOTO
+    dispatch_out(o, [&](auto E, auto CHW, auto LUT) {
+        k_photo_apply<C, E(), CHW(), LUT()><<<grid, dim3(256), 0, s>>>(d_px, d_chains, d_luts, d_table, d_out, npix, step);
+    });
     if (area) {  // the views that blur in this step sat the pass above out: rows in place, then columns, in place or to d_out
         k_photo_blur_rows<C><<<dim3((oh + blur_rows_per_group(ow) - 1) / blur_rows_per_group(ow), views), dim3(256), 0, s>>>(d_px, d_chains, ow, oh, step);
         const dim3 cols(uint32_t((uint64_t(ow) * C + kBlurStrip - 1) / kBlurStrip), views);
-#define LLMI_PHOTO(E, CHW, LUT) launch_blur_cols<C, E, CHW, LUT>(cols, s, d_px, d_chains, d_table, d_out, ow, oh, step)
-        if (o.plain)
-            LLMI_PHOTO(1, false, false);
-        else if (o.esize == 1)
-            LLMI_PHOTO(1, true, true);
-        else if (o.esize == 2)
-            chw ? LLMI_PHOTO(2, true, true) : LLMI_PHOTO(2, false, true);
-        else
-            chw ? LLMI_PHOTO(4, true, true) : LLMI_PHOTO(4, false, true);
-#undef LLMI_PHOTO
+        dispatch_out(o, [&](auto E, auto CHW, auto LUT) {
+            k_photo_blur_cols<C, E(), CHW(), LUT()><<<cols, dim3(256), 0, s>>>(d_px, d_chains, d_table, d_out, ow, oh, step);
+        });
     }
     if (sharp_rows) {  // the views that sharpen in this step: the rows between the bands first, as they stand, then the bands
         const uint32_t bands = photo_sharp_bands(oh, sharp_rows);
@@ -499,16 +466,9 @@ hipError_t launch_step_c(uint8_t* d_px, const llcomp_mi_photo_chain* d_chains, u
         if (bands > 1) k_photo_sharp_save<C><<<dim3(bands - 1, views), dim3(256), 0, s>>>(d_px, d_chains, d_halo, ow, oh, sharp_rows, halo_stride, step);
         const uint32_t lds = kSharpSlots * sharp_slot_bytes(pitch) + (sharp_pieces(pitch) > 1 ? sharp_rows * C : 0u);
         const dim3 grid_s(bands, views);
-#define LLMI_PHOTO(E, CHW, LUT) launch_sharp<C, E, CHW, LUT>(grid_s, lds, s, d_px, d_chains, d_halo, d_table, d_out, ow, oh, sharp_rows, halo_stride, step)
-        if (o.plain)
-            LLMI_PHOTO(1, false, false);
-        else if (o.esize == 1)
-            LLMI_PHOTO(1, true, true);
-        else if (o.esize == 2)
-            chw ? LLMI_PHOTO(2, true, true) : LLMI_PHOTO(2, false, true);
-        else
-            chw ? LLMI_PHOTO(4, true, true) : LLMI_PHOTO(4, false, true);
-#undef LLMI_PHOTO
+        dispatch_out(o, [&](auto E, auto CHW, auto LUT) {
+            k_photo_sharp<C, E(), CHW(), LUT()><<<grid_s, dim3(256), lds, s>>>(d_px, d_chains, d_halo, d_table, d_out, ow, oh, sharp_rows, halo_stride, step);
+        });
     }
     return hipGetLastError();
 }

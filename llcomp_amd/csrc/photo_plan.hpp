@@ -2,7 +2,8 @@
 // _photo_warped_views): the limits, which groups run chains, how their views are chunked through the staging buffer, which steps need a
 // statistics or a table launch, and the block of chains the call's one copy carries behind its tail's block.  Plain C++
 // (photo_plan.cpp), like windows_plan.cpp: it builds and runs under a host sanitizer (tests/helpers/photo_plan_check.cpp).  The rule
-// itself: photo_rule.hpp.  The driver: codec.hip, windows_photo.
+// itself: photo_rule.hpp.  The driver: codec.hip, photo_tail_of (views_call, warped_call) and windows_photo behind every chunk of
+// windows_groups; where the block sits in the copy: windows_plan.hpp, CopyLayout.
 #pragma once
 #include <cstdint>
 #include <vector>

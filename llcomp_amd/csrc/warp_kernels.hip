@@ -103,17 +103,9 @@ hipError_t launch_warp(const uint8_t* d_box, const WarpEntry* d_ws, const int32_
     const uint64_t gx = (uint64_t(ow) + 15) / 16, gy = (uint64_t(oh) + 15) / 16;
     if (gx * gy > 0x7FFFFFFFull) return hipErrorInvalidValue;  // (an output of 2^39 pixels: no buffer holds it)
     const dim3 grid(uint32_t(gx * gy), views);
-    const bool chw = o.layout == LLCOMP_MI_LAYOUT_CHW;
-#define LLMI_WARP(E, CHW, LUT) launch_c<E, CHW, LUT>(grid, stream, d_box, d_ws, d_tabs, d_fill, d_table, d_out, c, bw, bh, w, h, ow, oh)
-    if (o.plain)
-        LLMI_WARP(1, false, false);
-    else if (o.esize == 1)  // (U8 CHW: U8 HWC is plain)
-        LLMI_WARP(1, true, true);
-    else if (o.esize == 2)
-        chw ? LLMI_WARP(2, true, true) : LLMI_WARP(2, false, true);
-    else
-        chw ? LLMI_WARP(4, true, true) : LLMI_WARP(4, false, true);
-#undef LLMI_WARP
+    dispatch_out(o, [&](auto E, auto CHW, auto LUT) {
+        launch_c<E(), CHW(), LUT()>(grid, stream, d_box, d_ws, d_tabs, d_fill, d_table, d_out, c, bw, bh, w, h, ow, oh);
+    });
     return hipGetLastError();
 }
 

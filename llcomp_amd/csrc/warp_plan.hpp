@@ -2,7 +2,8 @@
 // source rectangle, the unions and windows -- those of a views decode on the source rectangles, through views_union and
 // regions_setup_sized unchanged -- and what the gather kernel reads: one entry per view, the pure-scale index tables, the groups' fill
 // values and output tables.  Plain C++ (warp_plan.cpp), like windows_plan.cpp: it builds and runs under a host sanitizer
-// (tests/helpers/warp_plan_check.cpp).  The rule itself: warp_rule.hpp.  The driver: codec.hip, decode_windows with a warp tail.
+// (tests/helpers/warp_plan_check.cpp).  The rule itself: warp_rule.hpp.  The driver: codec.hip, warped_call -> decode_windows with a warp
+// tail -> windows_warp.
 #pragma once
 #include <cstdint>
 #include <vector>

@@ -2,7 +2,8 @@
 // _views and their _host forms; DESIGN.md "Region decode"): every frame's window, class and box, the bytes the call's one copy carries
 // and their bounds, and the resample entries, weights and output tables.  Plain C++ (windows_plan.cpp): functions of the codec's geometry
 // and tuning hooks alone, so that what sizes the pinned slot and d_stage builds and runs under a host sanitizer
-// (tests/helpers/windows_plan_check.cpp).  The driver that lays a plan into a slot and queues it: codec.hip, decode_windows.
+// (tests/helpers/windows_plan_check.cpp).  The driver that lays a plan into a slot by CopyLayout and queues it: codec.hip, decode_windows,
+// which takes one WindowsCall from the four bodies behind the entry points (regions_call, resized_call, views_call, warped_call).
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -101,14 +102,22 @@ struct ResampleTail {
 };
 
 // Where everything sits in a call's one copy, in the pinned slot and in HBM alike: the table, the gather's arrays behind it for a host
-// source (`stage`: the table alone without one), and the tail's block at the next multiple of 16 where there is a tail.
+// source (`stage`: the table alone without one); where the call has a tail, its block of block_bytes (ResampleBlock::bytes, or
+// WarpTail::bytes -- warp_plan.hpp includes this header, so the layout takes the number) at rs_at, the next multiple of 16; and the
+// chain_bytes of photometric chains (PhotoTail::bytes, 0 for a call without chains) at chains_at, the next multiple of 16 behind the
+// block's end -- the slot's bytes [block_end, chains_at) are zeroed.  bytes: the whole copy.
 struct CopyLayout {
     StageLayout stage;
-    uint64_t rs_at, bytes;
-    CopyLayout(size_t entries, const RegionsGather* gather, const ResampleTail* tail)
+    uint64_t rs_at, block_end, chains_at, bytes;
+    CopyLayout(size_t entries, const RegionsGather* gather, bool tail, uint64_t block_bytes, uint64_t chain_bytes)
         : stage(uint32_t(entries), gather ? gather->n_slices : 0, gather ? gather->payload_bytes : 0),
           rs_at((stage.bytes + 15) & ~15ull),
-          bytes(tail ? rs_at + tail->block.bytes() : stage.bytes) {}
+          block_end(tail ? rs_at + block_bytes : stage.bytes),
+          chains_at((block_end + 15) & ~15ull),
+          bytes(chain_bytes ? chains_at + chain_bytes : block_end) {}
+    // ... of a call with a resample tail or none, and no chains
+    CopyLayout(size_t entries, const RegionsGather* gather, const ResampleTail* tail)
+        : CopyLayout(entries, gather, tail != nullptr, tail ? tail->block.bytes() : 0, 0) {}
 };
 
 // Everything of a resized regions decode the host decides: every frame's window, class and box (regions_setup_sized, sized for the

@@ -6,6 +6,7 @@
 // only; built and run by tests/test_pad_plan.py:
 //   g++ -std=c++17 -O1 -g -Wall -Wextra -Werror -fsanitize=address,undefined -fno-sanitize-recover=all -I llcomp_amd/csrc
 //       tests/helpers/pad_plan_check.cpp llcomp_amd/csrc/container.cpp llcomp_amd/csrc/windows_plan.cpp llcomp_amd/csrc/resize_plan.cpp
+//       llcomp_amd/csrc/photo_plan.cpp
 // Prints "ok <rounds>".
 #include <algorithm>
 #include <cstdio>
@@ -17,6 +18,7 @@
 
 #include "../../include/llcomp_mi.h"
 #include "container.hpp"
+#include "copy_layout_check.hpp"
 #include "windows_plan.hpp"
 
 using namespace llcomp_mi;
@@ -87,6 +89,8 @@ int check_block(const Geometry& g, const WindowsPlan& p, const ResampleTail& t, 
         CHECK(cl.rs_at % 16 == 0 && cl.bytes == cl.rs_at + b.bytes());
         if (bound) CHECK(cl.bytes <= stage_bound(g) + bound);
     }
+    // ... and with photometric chains behind the block, as a padded photo views call lays them
+    CHECK(copy_layout_ok(g, p, true, b.bytes(), b.rs.size(), bound ? &bound : nullptr, uint32_t(b.bytes()) + 977u * uint32_t(p.tab.size())));
     return 0;
 }
 

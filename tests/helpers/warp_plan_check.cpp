@@ -5,7 +5,7 @@
 // rule reads inside the source rectangle, and the refusals.  Host code only; built and run by tests/test_warp_plan_sanitizers.py:
 //   g++ -std=c++17 -O1 -g -Wall -Wextra -Werror -fsanitize=address,undefined -fno-sanitize-recover=all -I llcomp_amd/csrc
 //       tests/helpers/warp_plan_check.cpp llcomp_amd/csrc/container.cpp llcomp_amd/csrc/windows_plan.cpp llcomp_amd/csrc/resize_plan.cpp
-//       llcomp_amd/csrc/warp_plan.cpp
+//       llcomp_amd/csrc/warp_plan.cpp llcomp_amd/csrc/photo_plan.cpp
 // Prints "ok <rounds>".
 #include <cmath>
 #include <cstdio>
@@ -18,6 +18,7 @@
 
 #include "../../include/llcomp_mi.h"
 #include "container.hpp"
+#include "copy_layout_check.hpp"
 #include "warp_plan.hpp"
 #include "warp_rule.hpp"
 
@@ -134,6 +135,9 @@ int check_plan(const Geometry& g, const WarpPlan& p, const std::vector<llcomp_mi
     CHECK(t.tabs_at() % 8 == 0 && (t.tables.empty() || t.tables_at() % 16 == 0));
     // the block against the bound the staging buffer is sized by (outputs no larger than the image)
     CHECK(t.bytes() + 16 <= warp_tables_bound(g, p.total_views));
+    // the whole copy, with and without a gather, with and without photometric chains, against the bounds the entry points pass on
+    const uint64_t bound = warp_tables_bound(g, p.total_views);
+    CHECK(copy_layout_ok(g, p, true, t.bytes(), p.total_views, &bound, uint32_t(t.bytes()) + 977u * uint32_t(p.tab.size())));
     return 0;
 }
 

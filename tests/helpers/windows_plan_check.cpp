@@ -4,6 +4,7 @@
 // of one view per frame, and the refusals.  Host code only; built and run by tests/test_windows_plan.py:
 //   g++ -std=c++17 -O1 -g -Wall -Wextra -Werror -fsanitize=address,undefined -fno-sanitize-recover=all -I llcomp_amd/csrc
 //       tests/helpers/windows_plan_check.cpp llcomp_amd/csrc/container.cpp llcomp_amd/csrc/windows_plan.cpp llcomp_amd/csrc/resize_plan.cpp
+//       llcomp_amd/csrc/photo_plan.cpp
 // Prints "ok <rounds>".
 #include <cstdio>
 #include <cstdlib>
@@ -14,6 +15,7 @@
 
 #include "../../include/llcomp_mi.h"
 #include "container.hpp"
+#include "copy_layout_check.hpp"
 #include "windows_plan.hpp"
 
 using namespace llcomp_mi;
@@ -83,6 +85,8 @@ int check_tail(const Geometry& g, const WindowsPlan& p, const ResampleTail& t, u
         CHECK(cl.bytes == cl.rs_at + b.bytes());
         if (bound) CHECK(cl.bytes <= stage_bound(g) + bound);
     }
+    // ... and with photometric chains behind the block, as a photo views call lays them (one chain per view at the most)
+    CHECK(copy_layout_ok(g, p, true, b.bytes(), b.rs.size(), bound ? &bound : nullptr, uint32_t(b.bytes()) + 977u * uint32_t(p.tab.size())));
     return 0;
 }
 
@@ -129,6 +133,8 @@ int main() {
                 for (const RegionsFrame& e : p.tab) CHECK(e.out == e.frame);
                 const CopyLayout cl(p.tab.size(), nullptr, nullptr);
                 CHECK(cl.bytes == frames * sizeof(RegionsFrame));
+                const uint64_t no_tables = 0;  // (a call without a tail adds nothing to stage_bound)
+                CHECK(copy_layout_ok(g, p, false, 0, 0, &no_tables, 131u * p.wmax + p.hmax));
             }
 
             // ---- 2. a resized plan: a rectangle, a mirror bit and a filter per frame; outputs below and above the image's size -----------
