@@ -467,14 +467,15 @@ int windows_photo(llcomp_mi_codec* k, const PhotoTail& photo, const PhotoGroup& 
                   uint32_t at, uint32_t cnt, hipStream_t s) {
     const uint32_t c = k->g.c;
     const uint64_t view_bytes = uint64_t(pg.oh) * pg.ow * c * pg.out.esize;
-    uint8_t* const d_luts = k->d_photo_tab + photo.tab_views * photo_stats_stride(c);
-    // (the halo areas of a group that sharpens: behind the `chunk` views of a full chunk, where the planner charged them)
-    uint8_t* const d_halo = pg.sharp_rows && photo_sharp_halo_bytes(pg.ow, pg.oh, c, pg.sharp_rows) ? k->d_photo + uint64_t(pg.chunk) * pg.oh * pg.ow * c : nullptr;
-    for (uint32_t step = 0; step < std::max(pg.steps, 1u); ++step)
-        HIP_TRY(launch_photo_step(k->d_photo, d_chains + pg.first + at, k->d_photo_tab, d_luts, d_tables + pg.table_at, pg.out,
-                                  static_cast<uint8_t*>(pg.d_out) + at * view_bytes, cnt, c, pg.ow, pg.oh, step, (pg.stats_steps >> step) & 1u,
-                                  (pg.table_steps >> step) & 1u, (pg.area_steps >> step) & 1u, d_halo,
-                                  (pg.sharp_steps >> step) & 1u ? pg.sharp_rows : 0u, s));
+    PhotoStep st{};
+    st.d_px = k->d_photo, st.d_chains = d_chains + pg.first + at, st.d_halo = pg.halo_at == kPhotoNoHalo ? nullptr : k->d_photo + pg.halo_at;
+    st.d_stats = k->d_photo_tab, st.d_luts = k->d_photo_tab + photo.tab_views * photo_stats_stride(c);
+    st.out = pg.out, st.d_table = d_tables + pg.table_at, st.d_out = static_cast<uint8_t*>(pg.d_out) + at * view_bytes;
+    st.views = cnt, st.c = c, st.ow = pg.ow, st.oh = pg.oh, st.sharp_rows = pg.sharp_rows;
+    for (; st.step < pg.steps; ++st.step) {
+        st.info = pg.step[st.step];
+        HIP_TRY(launch_photo_step(st, s));
+    }
     return LLCOMP_MI_OK;
 }
 const PhotoGroup* photo_group(const PhotoTail* photo, size_t gi) { return photo && photo->groups[gi].active ? &photo->groups[gi] : nullptr; }

@@ -1,8 +1,9 @@
 // photo_kernels.hip -- the kernels of the photometric chains (llcomp_mi_codec_decode_photo_views / _photo_warped_views): the
-// statistics of every view whose op of the step reads them, the table of every view whose op is one, the per-pixel pass, the row
-// and the column kernel of the views whose op is the blur, and the band kernel of the views whose op is the sharpness.  All views of a chunk run a step together; nothing goes back to the host in
-// between.  The arithmetic is photo_rule.hpp's -- the functions llcomp_mi_photo_reference runs on the host -- with NO fused
-// multiply-add: the header's pragma holds for this whole file.
+// statistics of every view whose op of the step reads them, and the kernels of each kind of op (photo_rule.hpp: PhotoKind) -- the table
+// of every view whose op is one and the per-pixel pass, the row and the column kernel of the blur, the band kernel of the sharpness.  A
+// view takes part in a step as the kind of its op (photo_step_as); what a step launches is its PhotoStep's (photo.hpp).  All views of a
+// chunk run a step together; nothing goes back to the host in between.  The arithmetic is photo_rule.hpp's -- the functions
+// llcomp_mi_photo_reference runs on the host -- with NO fused multiply-add: the header's pragma holds for this whole file.
 #include "photo_rule.hpp"
 
 #include "out_store.hpp"
@@ -18,15 +19,29 @@ namespace {
 
 constexpr uint32_t kPhotoNoOp = 0xFFFFFFFFu;  // the step of an empty chain: the view goes to the output as it is
 
-// The op of chain `ch` at `step` and whether it is the chain's last; false when the view sits this step out.  An empty chain has one
-// step, step 0, which only writes the output.
-__device__ __forceinline__ bool photo_step_op(const llcomp_mi_photo_chain& ch, uint32_t step, uint32_t& op, float& param, bool& last) {
+// Does the view of chain `ch` take part in `step` as `kind` (or as `also`: the per-pixel pass takes two), and if so with which op and
+// parameter, and is the step its chain's last?  False where the chain has ended or its op is of another kind: every kernel asks for
+// its own, so a view is one kernel family's in a step.  An empty chain has one step, step 0, which only writes the output: kPhotoNoOp
+// is no op code, so it is of kPixel (photo_rule.hpp), for which k_photo_apply alone asks.
+struct PhotoPart { uint32_t op; float param; bool last; };
+__device__ __forceinline__ bool photo_step_as(const llcomp_mi_photo_chain& ch, uint32_t step, PhotoKind kind, PhotoPart& me, PhotoKind also = PhotoKind(~0u)) {
     const uint32_t n = ch.n_ops < LLCOMP_MI_PHOTO_MAX_OPS ? ch.n_ops : uint32_t(LLCOMP_MI_PHOTO_MAX_OPS);
     if (step >= (n ? n : 1u)) return false;
-    op = n ? ch.ops[step].op : kPhotoNoOp;
-    param = n ? ch.ops[step].param : 0.0f;
-    last = step + 1 >= n;
-    return true;
+    me.op = n ? ch.ops[step].op : kPhotoNoOp;
+    me.param = n ? ch.ops[step].param : 0.0f;
+    me.last = step + 1 >= n;
+    return photo_kind(me.op) == kind || photo_kind(me.op) == also;
+}
+
+// N result bytes of view v, val[0 .. N): the chain's last step stores them through the group's output format to o (out_store.hpp:
+// channels ch .. ch + N - 1 of pixel px, plane = oh * ow), any other step back in place at back[0 .. N).
+template <class T, bool CHW, bool LUT, int N = 1>
+__device__ __forceinline__ void photo_store(bool last, T* o, const T* lut, size_t v, uint32_t c, size_t plane, size_t px, uint32_t ch, uint8_t* back,
+                                            const uint32_t* val) {
+    if (last)
+        for (int k = 0; k < N; ++k) out_store<T, CHW, LUT>(o, lut, v, c, plane, px, ch + k, val[k]);
+    else
+        for (int k = 0; k < N; ++k) back[k] = uint8_t(val[k]);
 }
 
 // Statistics: blockIdx.y the view, gridDim.x workgroups share its pixels.  Each wavefront counts into a histogram of its own in LDS
@@ -39,11 +54,9 @@ __global__ __launch_bounds__(256) void k_photo_stats(const uint8_t* __restrict__
     __shared__ uint32_t s_hist[4][C * 256];
     __shared__ unsigned long long s_sum;
     const uint32_t v = blockIdx.y;
-    uint32_t op;
-    float param;
-    bool last;
-    if (!photo_step_op(chains[v], step, op, param, last) || !photo_needs_stats(op)) return;  // (the whole workgroup alike)
-    const bool hist = op != LLCOMP_MI_PHOTO_CONTRAST;
+    PhotoPart me;
+    if (!photo_step_as(chains[v], step, PhotoKind::kTable, me) || !photo_needs_stats(me.op)) return;  // (the whole workgroup alike)
+    const bool hist = me.op != LLCOMP_MI_PHOTO_CONTRAST;
     for (uint32_t j = threadIdx.x; j < uint32_t(4 * C * 256); j += 256) (&s_hist[0][0])[j] = 0;
     if (threadIdx.x == 0) s_sum = 0;
     __syncthreads();
@@ -85,25 +98,22 @@ __global__ __launch_bounds__(64) void k_photo_lut(const llcomp_mi_photo_chain* _
     __shared__ uint32_t s_hist[C * 256];
     __shared__ uint8_t s_lut[C * 256];
     const uint32_t v = blockIdx.x;
-    uint32_t op;
-    float param;
-    bool last;
-    if (!photo_step_op(chains[v], step, op, param, last) || !photo_is_table(op)) return;
-    const bool need = photo_needs_stats(op);
+    PhotoPart me;
+    if (!photo_step_as(chains[v], step, PhotoKind::kTable, me)) return;
+    const bool need = photo_needs_stats(me.op);
     const unsigned long long* g_sum = reinterpret_cast<const unsigned long long*>(stats + size_t(v) * (8 + 1024 * C));
     const uint32_t* g_hist = reinterpret_cast<const uint32_t*>(g_sum + 1);
     for (uint32_t j = threadIdx.x; j < uint32_t(C * 256); j += 64) s_hist[j] = need ? g_hist[j] : 0u;
     __syncthreads();
-    if (threadIdx.x < uint32_t(C)) photo_table(op, param, s_hist + 256 * threadIdx.x, need ? uint64_t(*g_sum) : 0ull, npix, s_lut + 256 * threadIdx.x);
+    if (threadIdx.x < uint32_t(C)) photo_table(me.op, me.param, s_hist + 256 * threadIdx.x, need ? uint64_t(*g_sum) : 0ull, npix, s_lut + 256 * threadIdx.x);
     __syncthreads();
     for (uint32_t j = threadIdx.x; j < uint32_t(C * 256); j += 64) luts[size_t(v) * (C * 256) + j] = s_lut[j];
 }
 
 // The per-pixel pass: blockIdx.y the view, a workgroup takes 1024 of its pixels.  A table op looks every channel up in the view's table
-// (copied to LDS), COLOR, GRAYSCALE and ADJUST_HUE are computed from the pixel, the step of an empty chain changes nothing, and a view
-// whose op is the blur sits out: k_photo_blur_rows and k_photo_blur_cols run it; so does a view whose op is the sharpness, which is
-// k_photo_sharp's.  The value goes back in place, or -- the chain's
-// last step -- through the group's output format to `out`.  E, CHW, LUT as in the gather of the warped views.
+// (copied to LDS), an op of kPixel is computed from the pixel (photo_pixel), the step of an empty chain changes nothing, and a view
+// whose op is of another kind sits out: the blur's or the sharpness's kernels run it.  The value goes back in place, or -- the chain's
+// last step -- through the group's output format to `out` (photo_store).  E, CHW, LUT as in the gather of the warped views.
 template <int C, int E, bool CHW, bool LUT>
 __global__ __launch_bounds__(256) void k_photo_apply(uint8_t* __restrict__ px, const llcomp_mi_photo_chain* __restrict__ chains,
                                                      const uint8_t* __restrict__ luts, const void* __restrict__ table, void* __restrict__ out,
@@ -111,14 +121,10 @@ __global__ __launch_bounds__(256) void k_photo_apply(uint8_t* __restrict__ px, c
     using T = typename OutElem<E>::T;
     __shared__ uint8_t s_lut[C * 256];
     const uint32_t v = blockIdx.y;
-    uint32_t op;
-    float param;
-    bool last;
-    if (!photo_step_op(chains[v], step, op, param, last)) return;  // (the whole workgroup alike)
-    if (op != kPhotoNoOp && photo_is_area(op)) return;             // (the blur kernels' view in this step)
-    if (op != kPhotoNoOp && photo_is_sharp(op)) return;            // (k_photo_sharp's)
-    const bool tab = op != kPhotoNoOp && photo_is_table(op);
-    const uint32_t shift = op == LLCOMP_MI_PHOTO_ADJUST_HUE ? photo_hue_shift(param) : 0u;
+    PhotoPart me;
+    if (!photo_step_as(chains[v], step, PhotoKind::kPixel, me, PhotoKind::kTable)) return;  // (the whole workgroup alike)
+    const bool tab = photo_kind(me.op) == PhotoKind::kTable;
+    const uint32_t shift = me.op == LLCOMP_MI_PHOTO_ADJUST_HUE ? photo_hue_shift(me.param) : 0u;
     if (tab) {
         for (uint32_t j = threadIdx.x; j < uint32_t(C * 256); j += 256) s_lut[j] = luts[size_t(v) * (C * 256) + j];
         __syncthreads();
@@ -133,18 +139,9 @@ __global__ __launch_bounds__(256) void k_photo_apply(uint8_t* __restrict__ px, c
         if (tab) {
             for (int ch = 0; ch < C; ++ch) s[ch] = s_lut[ch * 256 + s[ch]];
         } else if constexpr (C == 3) {
-            if (op == LLCOMP_MI_PHOTO_COLOR)
-                photo_color(s[0], s[1], s[2], param);
-            else if (op == LLCOMP_MI_PHOTO_GRAYSCALE)
-                photo_grayscale(s[0], s[1], s[2]);
-            else if (op == LLCOMP_MI_PHOTO_ADJUST_HUE)
-                photo_hue(s[0], s[1], s[2], shift);
+            photo_pixel(me.op, me.param, shift, s[0], s[1], s[2]);
         }
-        if (last) {
-            for (int ch = 0; ch < C; ++ch) out_store<T, CHW, LUT>(o, lut, v, C, npix, i, ch, s[ch]);
-        } else {
-            for (int ch = 0; ch < C; ++ch) p[i * C + ch] = uint8_t(s[ch]);
-        }
+        photo_store<T, CHW, LUT, C>(me.last, o, lut, v, C, npix, i, 0, p + i * C, s);
     }
 }
 
@@ -184,12 +181,10 @@ __global__ __launch_bounds__(256) void k_photo_blur_rows(uint8_t* __restrict__ p
                                                          uint32_t oh, uint32_t step) {
     __shared__ uint8_t s_a[kBlurRowSlots * C], s_b[kBlurRowSlots * C], s_keep[(kBlurRowSlots / kBlurLine) * kBlurHalo * C];
     const uint32_t v = blockIdx.y;
-    uint32_t op;
-    float param;
-    bool last;
-    if (!photo_step_op(chains[v], step, op, param, last) || op == kPhotoNoOp || !photo_is_area(op)) return;  // (the whole workgroup alike)
+    PhotoPart me;
+    if (!photo_step_as(chains[v], step, PhotoKind::kBlur, me)) return;  // (the whole workgroup alike)
     uint32_t r, ww, fw;
-    photo_blur_weights(param, r, ww, fw);
+    photo_blur_weights(me.param, r, ww, fw);
     const uint32_t reach = photo_blur_reach(r);
     const uint32_t rows = blur_rows_per_group(ow), row0 = blockIdx.x * rows;
     const uint32_t nrows = oh - row0 < rows ? oh - row0 : rows;
@@ -247,12 +242,10 @@ __global__ __launch_bounds__(256) void k_photo_blur_cols(uint8_t* __restrict__ p
     constexpr uint32_t W4 = kBlurStrip / 4;
     __shared__ uint32_t s_a[kBlurLine * W4], s_b[kBlurLine * W4], s_keep[kBlurHalo * W4];
     const uint32_t v = blockIdx.y;
-    uint32_t op;
-    float param;
-    bool last;
-    if (!photo_step_op(chains[v], step, op, param, last) || op == kPhotoNoOp || !photo_is_area(op)) return;  // (the whole workgroup alike)
+    PhotoPart me;
+    if (!photo_step_as(chains[v], step, PhotoKind::kBlur, me)) return;  // (the whole workgroup alike)
     uint32_t r, ww, fw;
-    photo_blur_weights(param, r, ww, fw);
+    photo_blur_weights(me.param, r, ww, fw);
     const uint32_t reach = photo_blur_reach(r);
     const size_t pitch = size_t(ow) * C, plane = size_t(oh) * ow;
     const size_t col0 = size_t(blockIdx.x) * kBlurStrip;
@@ -301,12 +294,8 @@ __global__ __launch_bounds__(256) void k_photo_blur_cols(uint8_t* __restrict__ p
             const uint32_t row = j / kBlurStrip, col = j % kBlurStrip;
             if (col >= sw) continue;
             const uint32_t val = b8[(s - lo + row) * kBlurStrip + col];
-            if (last) {
-                const size_t bx = col0 + col, x = bx / C;
-                out_store<T, CHW, LUT>(o, lut, v, C, plane, (size_t(s) + row) * ow + x, uint32_t(bx - x * C), val);
-            } else {
-                p[(size_t(s) + row) * pitch + col] = uint8_t(val);
-            }
+            const size_t bx = col0 + col, x = bx / C;
+            photo_store<T, CHW, LUT>(me.last, o, lut, v, C, plane, (size_t(s) + row) * ow + x, uint32_t(bx - x * C), p + (size_t(s) + row) * pitch + col, &val);
         }
     }
 }
@@ -342,10 +331,8 @@ __global__ __launch_bounds__(256) void k_photo_sharp_save(const uint8_t* __restr
                                                           uint8_t* __restrict__ halo, uint32_t ow, uint32_t oh, uint32_t band_rows,
                                                           uint64_t halo_stride, uint32_t step) {
     const uint32_t v = blockIdx.y, j = blockIdx.x;  // the pair of rows between bands j and j + 1
-    uint32_t op;
-    float param;
-    bool last;
-    if (!photo_step_op(chains[v], step, op, param, last) || op == kPhotoNoOp || !photo_is_sharp(op)) return;  // (the whole workgroup alike)
+    PhotoPart me;
+    if (!photo_step_as(chains[v], step, PhotoKind::kSharp, me)) return;  // (the whole workgroup alike)
     const size_t pitch = size_t(ow) * C;
     const uint8_t* const src = px + (size_t(v) * oh + (size_t(j) + 1) * band_rows - 1) * pitch;
     uint8_t* const dst = halo + size_t(v) * halo_stride + size_t(j) * 2 * pitch;
@@ -359,10 +346,8 @@ __global__ __launch_bounds__(256) void k_photo_sharp(uint8_t* __restrict__ px, c
     using T = typename OutElem<E>::T;
     extern __shared__ __align__(16) uint8_t s_sharp[];  // kSharpSlots slots, then -- a row in pieces -- band_rows * C kept bytes
     const uint32_t v = blockIdx.y, band = blockIdx.x;
-    uint32_t op;
-    float param;
-    bool last;
-    if (!photo_step_op(chains[v], step, op, param, last) || op == kPhotoNoOp || !photo_is_sharp(op)) return;  // (the whole workgroup alike)
+    PhotoPart me;
+    if (!photo_step_as(chains[v], step, PhotoKind::kSharp, me)) return;  // (the whole workgroup alike)
     const size_t pitch = size_t(ow) * C, plane = size_t(oh) * ow;
     const uint32_t slot_bytes = sharp_slot_bytes(pitch);
     const uint32_t r0 = band * band_rows, r1 = oh - r0 < band_rows ? oh : r0 + band_rows;
@@ -427,47 +412,43 @@ __global__ __launch_bounds__(256) void k_photo_sharp(uint8_t* __restrict__ px, c
                     const uint32_t sum9 = uint32_t(su[i - C]) + su[i] + su[i + C] + sc[i - C] + val + sc[i + C] + sd[i - C] + sd[i] + sd[i + C];
                     d = photo_smooth(sum9, val);
                 }
-                const uint32_t res = photo_blend(d, val, param);
-                if (last)
-                    out_store<T, CHW, LUT>(o, lut, v, C, plane, size_t(y) * ow + x, ch, res);
-                else
-                    p[size_t(y) * pitch + q] = uint8_t(res);
+                const uint32_t res = photo_blend(d, val, me.param);
+                photo_store<T, CHW, LUT>(me.last, o, lut, v, C, plane, size_t(y) * ow + x, ch, p + size_t(y) * pitch + q, &res);
             }
         }
     }
 }
 
 template <int C>
-hipError_t launch_step_c(uint8_t* d_px, const llcomp_mi_photo_chain* d_chains, uint8_t* d_stats, uint8_t* d_luts, const void* d_table,
-                         const OutFormat& o, void* d_out, uint32_t views, uint32_t ow, uint32_t oh, uint32_t step, bool stats, bool table, bool area,
-                         uint8_t* d_halo, uint32_t sharp_rows, hipStream_t s) {
+hipError_t launch_step_c(const PhotoStep& p, hipStream_t s) {
+    const uint32_t views = p.views, ow = p.ow, oh = p.oh, step = p.step;
     const uint64_t npix = uint64_t(oh) * ow;
-    if (stats) {
-        if (hipError_t err = hipMemsetAsync(d_stats, 0, size_t(views) * photo_stats_stride(C), s)) return err;
+    if (p.info.stats) {
+        if (hipError_t err = hipMemsetAsync(p.d_stats, 0, size_t(views) * photo_stats_stride(C), s)) return err;
         // (4096 pixels per workgroup and round, at most 32 workgroups per view: a 224 x 224 view takes 13)
         const uint32_t gx = uint32_t(std::min<uint64_t>((npix + 4095) / 4096, 32));
-        k_photo_stats<C><<<dim3(gx, views), dim3(256), 0, s>>>(d_px, d_chains, d_stats, npix, step);
+        k_photo_stats<C><<<dim3(gx, views), dim3(256), 0, s>>>(p.d_px, p.d_chains, p.d_stats, npix, step);
     }
-    if (table) k_photo_lut<C><<<dim3(views), dim3(64), 0, s>>>(d_chains, d_stats, d_luts, npix, step);
+    if (p.info.has(PhotoKind::kTable)) k_photo_lut<C><<<dim3(views), dim3(64), 0, s>>>(p.d_chains, p.d_stats, p.d_luts, npix, step);
     const dim3 grid(uint32_t((npix + 1023) / 1024), views);
-    dispatch_out(o, [&](auto E, auto CHW, auto LUT) {
-        k_photo_apply<C, E(), CHW(), LUT()><<<grid, dim3(256), 0, s>>>(d_px, d_chains, d_luts, d_table, d_out, npix, step);
+    dispatch_out(p.out, [&](auto E, auto CHW, auto LUT) {
+        k_photo_apply<C, E(), CHW(), LUT()><<<grid, dim3(256), 0, s>>>(p.d_px, p.d_chains, p.d_luts, p.d_table, p.d_out, npix, step);
     });
-    if (area) {  // the views that blur in this step sat the pass above out: rows in place, then columns, in place or to d_out
-        k_photo_blur_rows<C><<<dim3((oh + blur_rows_per_group(ow) - 1) / blur_rows_per_group(ow), views), dim3(256), 0, s>>>(d_px, d_chains, ow, oh, step);
+    if (p.info.has(PhotoKind::kBlur)) {  // the views that blur in this step sat the pass above out: rows in place, then columns, in place or to d_out
+        k_photo_blur_rows<C><<<dim3((oh + blur_rows_per_group(ow) - 1) / blur_rows_per_group(ow), views), dim3(256), 0, s>>>(p.d_px, p.d_chains, ow, oh, step);
         const dim3 cols(uint32_t((uint64_t(ow) * C + kBlurStrip - 1) / kBlurStrip), views);
-        dispatch_out(o, [&](auto E, auto CHW, auto LUT) {
-            k_photo_blur_cols<C, E(), CHW(), LUT()><<<cols, dim3(256), 0, s>>>(d_px, d_chains, d_table, d_out, ow, oh, step);
+        dispatch_out(p.out, [&](auto E, auto CHW, auto LUT) {
+            k_photo_blur_cols<C, E(), CHW(), LUT()><<<cols, dim3(256), 0, s>>>(p.d_px, p.d_chains, p.d_table, p.d_out, ow, oh, step);
         });
     }
-    if (sharp_rows) {  // the views that sharpen in this step: the rows between the bands first, as they stand, then the bands
-        const uint32_t bands = photo_sharp_bands(oh, sharp_rows);
-        const uint64_t pitch = uint64_t(ow) * C, halo_stride = photo_sharp_halo_bytes(ow, oh, C, sharp_rows);
-        if (bands > 1) k_photo_sharp_save<C><<<dim3(bands - 1, views), dim3(256), 0, s>>>(d_px, d_chains, d_halo, ow, oh, sharp_rows, halo_stride, step);
-        const uint32_t lds = kSharpSlots * sharp_slot_bytes(pitch) + (sharp_pieces(pitch) > 1 ? sharp_rows * C : 0u);
+    if (p.info.has(PhotoKind::kSharp)) {  // the views that sharpen in this step: the rows between the bands first, as they stand, then the bands
+        const uint32_t rows = p.sharp_rows, bands = photo_sharp_bands(oh, rows);
+        const uint64_t pitch = uint64_t(ow) * C, halo_stride = photo_sharp_halo_bytes(ow, oh, C, rows);
+        if (bands > 1) k_photo_sharp_save<C><<<dim3(bands - 1, views), dim3(256), 0, s>>>(p.d_px, p.d_chains, p.d_halo, ow, oh, rows, halo_stride, step);
+        const uint32_t lds = kSharpSlots * sharp_slot_bytes(pitch) + (sharp_pieces(pitch) > 1 ? rows * C : 0u);
         const dim3 grid_s(bands, views);
-        dispatch_out(o, [&](auto E, auto CHW, auto LUT) {
-            k_photo_sharp<C, E(), CHW(), LUT()><<<grid_s, dim3(256), lds, s>>>(d_px, d_chains, d_halo, d_table, d_out, ow, oh, sharp_rows, halo_stride, step);
+        dispatch_out(p.out, [&](auto E, auto CHW, auto LUT) {
+            k_photo_sharp<C, E(), CHW(), LUT()><<<grid_s, dim3(256), lds, s>>>(p.d_px, p.d_chains, p.d_halo, p.d_table, p.d_out, ow, oh, rows, halo_stride, step);
         });
     }
     return hipGetLastError();
@@ -475,24 +456,20 @@ hipError_t launch_step_c(uint8_t* d_px, const llcomp_mi_photo_chain* d_chains, u
 
 }  // namespace
 
-hipError_t launch_photo_step(uint8_t* d_px, const llcomp_mi_photo_chain* d_chains, void* d_stats, uint8_t* d_luts, const void* d_table,
-                             const OutFormat& o, void* d_out, uint32_t views, uint32_t c, uint32_t ow, uint32_t oh, uint32_t step, bool stats,
-                             bool table, bool area, uint8_t* d_halo, uint32_t sharp_rows, hipStream_t stream) {
-    if (!views || views > 65535 || (c != 1 && c != 3) || !ow || !oh || step >= LLCOMP_MI_PHOTO_MAX_OPS) return hipErrorInvalidValue;
-    if (!d_px || !d_chains || !d_out || (reinterpret_cast<uintptr_t>(d_chains) & 3u)) return hipErrorInvalidValue;
-    if ((stats || table) && (!d_stats || !d_luts || (reinterpret_cast<uintptr_t>(d_stats) & 7u))) return hipErrorInvalidValue;
-    if (!o.plain && (!d_table || (reinterpret_cast<uintptr_t>(d_table) & (o.esize - 1)))) return hipErrorInvalidValue;
-    if (reinterpret_cast<uintptr_t>(d_out) & (o.esize - 1)) return hipErrorInvalidValue;
-    const uint64_t npix = uint64_t(oh) * ow;
+hipError_t launch_photo_step(const PhotoStep& p, hipStream_t stream) {
+    if (!p.views || p.views > 65535 || (p.c != 1 && p.c != 3) || !p.ow || !p.oh || p.step >= LLCOMP_MI_PHOTO_MAX_OPS) return hipErrorInvalidValue;
+    if (!p.d_px || !p.d_chains || !p.d_out || (reinterpret_cast<uintptr_t>(p.d_chains) & 3u)) return hipErrorInvalidValue;
+    if ((p.info.stats || p.info.has(PhotoKind::kTable)) && (!p.d_stats || !p.d_luts || (reinterpret_cast<uintptr_t>(p.d_stats) & 7u))) return hipErrorInvalidValue;
+    if (!p.out.plain && (!p.d_table || (reinterpret_cast<uintptr_t>(p.d_table) & (p.out.esize - 1)))) return hipErrorInvalidValue;
+    if (reinterpret_cast<uintptr_t>(p.d_out) & (p.out.esize - 1)) return hipErrorInvalidValue;
+    const uint64_t npix = uint64_t(p.oh) * p.ow;
     if ((npix + 1023) / 1024 > 0x7FFFFFFFull) return hipErrorInvalidValue;  // (an output of 2^41 pixels: no buffer holds it)
-    if (area && uint64_t(ow) * c > 0x7FFFFFFFull * kBlurStrip) return hipErrorInvalidValue;  // (the column kernel's grid; a row of 2^37 bytes)
-    if (sharp_rows) {  // (the band's grid; the halo area of a view in bands; the kept columns of a row in pieces, which are LDS)
-        if (sharp_rows > oh || (photo_sharp_bands(oh, sharp_rows) > 1 && !d_halo)) return hipErrorInvalidValue;
-        if (sharp_pieces(uint64_t(ow) * c) > 1 && sharp_rows > kSharpKeepRows) return hipErrorInvalidValue;
+    if (p.info.has(PhotoKind::kBlur) && uint64_t(p.ow) * p.c > 0x7FFFFFFFull * kBlurStrip) return hipErrorInvalidValue;  // (the column kernel's grid; a row of 2^37 bytes)
+    if (p.info.has(PhotoKind::kSharp)) {  // (the band's grid; the halo area of a view in bands; the kept columns of a row in pieces, which are LDS)
+        if (!p.sharp_rows || p.sharp_rows > p.oh || (photo_sharp_bands(p.oh, p.sharp_rows) > 1 && !p.d_halo)) return hipErrorInvalidValue;
+        if (sharp_pieces(uint64_t(p.ow) * p.c) > 1 && p.sharp_rows > kSharpKeepRows) return hipErrorInvalidValue;
     }
-    uint8_t* st = static_cast<uint8_t*>(d_stats);
-    return c == 3 ? launch_step_c<3>(d_px, d_chains, st, d_luts, d_table, o, d_out, views, ow, oh, step, stats, table, area, d_halo, sharp_rows, stream)
-                  : launch_step_c<1>(d_px, d_chains, st, d_luts, d_table, o, d_out, views, ow, oh, step, stats, table, area, d_halo, sharp_rows, stream);
+    return p.c == 3 ? launch_step_c<3>(p, stream) : launch_step_c<1>(p, stream);
 }
 
 }  // namespace llcomp_mi

@@ -50,10 +50,8 @@ int photo_setup(uint32_t c, uint64_t samples, const llcomp_mi_photo_group* photo
             if (int rc = photo_check_chain(ch, c)) return rc;
             g.steps = std::max(g.steps, ch.n_ops);
             for (uint32_t k = 0; k < ch.n_ops; ++k) {
-                if (photo_needs_stats(ch.ops[k].op)) g.stats_steps |= 1u << k;
-                if (photo_is_table(ch.ops[k].op)) g.table_steps |= 1u << k;
-                if (photo_is_area(ch.ops[k].op)) g.area_steps |= 1u << k;
-                if (photo_is_sharp(ch.ops[k].op)) g.sharp_steps |= 1u << k;
+                g.step[k].kinds |= 1u << uint32_t(photo_kind(ch.ops[k].op));
+                g.step[k].stats |= photo_needs_stats(ch.ops[k].op);
             }
         }
         if (!g.steps) continue;  // (every chain empty: the group takes the extended call's path)
@@ -69,13 +67,15 @@ int photo_setup(uint32_t c, uint64_t samples, const llcomp_mi_photo_group* photo
             std::memcpy(ch.ops, pg.chains[i].ops, ch.n_ops * sizeof(llcomp_mi_photo_op));
             t.chains.push_back(ch);
         }
-        uint64_t per_view = uint64_t(g.oh) * g.ow * c;
-        if (g.sharp_steps) {  // (every view of the group alike, so that a chunk is its views and then their halo areas)
+        const uint64_t view = uint64_t(g.oh) * g.ow * c;
+        uint64_t halo = 0;
+        if (std::any_of(g.step, g.step + g.steps, [](const PhotoStepInfo& s) { return s.has(PhotoKind::kSharp); })) {  // (every view alike: a chunk is its views, then their halo areas)
             g.sharp_rows = photo_sharp_band_rows(g.ow, g.oh, c, samples);
-            per_view += photo_sharp_halo_bytes(g.ow, g.oh, c, g.sharp_rows);
+            halo = photo_sharp_halo_bytes(g.ow, g.oh, c, g.sharp_rows);
         }
-        g.chunk = uint32_t(std::min<uint64_t>(g.n, std::max<uint64_t>(samples / std::max<uint64_t>(per_view, 1), 1)));
-        t.stage_bytes = std::max(t.stage_bytes, g.chunk * per_view);
+        g.chunk = uint32_t(std::min<uint64_t>(g.n, std::max<uint64_t>(samples / std::max<uint64_t>(view + halo, 1), 1)));
+        if (halo) g.halo_at = g.chunk * view;
+        t.stage_bytes = std::max(t.stage_bytes, g.chunk * (view + halo));
         t.tab_views = std::max<uint64_t>(t.tab_views, g.chunk);
     }
     return LLCOMP_MI_OK;
@@ -106,67 +106,67 @@ int photo_reference(const uint8_t* src, uint32_t w, uint32_t h, uint32_t c, cons
     for (uint32_t k = 0; k < n_ops; ++k) {
         const uint32_t op = ops[k].op;
         const float a = ops[k].param;
-        if (photo_is_area(op)) {
-            uint32_t r, ww, fw;
-            photo_blur_weights(a, r, ww, fw);
-            line.resize(std::max(w, h));
-            for (int pass = 0; pass < 3; ++pass)  // along every row
+        switch (photo_kind(op)) {
+            case PhotoKind::kBlur: {
+                uint32_t r, ww, fw;
+                photo_blur_weights(a, r, ww, fw);
+                line.resize(std::max(w, h));
+                for (int pass = 0; pass < 3; ++pass)  // along every row
+                    for (uint64_t y = 0; y < h; ++y)
+                        for (uint32_t ch = 0; ch < c; ++ch) blur_line(out + y * w * c + ch, w, c, r, ww, fw, line.data());
+                for (int pass = 0; pass < 3; ++pass)  // along every column
+                    for (uint64_t x = 0; x < w; ++x)
+                        for (uint32_t ch = 0; ch < c; ++ch) blur_line(out + x * c + ch, h, uint64_t(w) * c, r, ww, fw, line.data());
+                break;
+            }
+            case PhotoKind::kSharp: {  // every sample from the view as it stands before the op: a copy of it
+                before.assign(out, out + size_t(n * c));
+                const uint64_t pitch = uint64_t(w) * c;
                 for (uint64_t y = 0; y < h; ++y)
-                    for (uint32_t ch = 0; ch < c; ++ch) blur_line(out + y * w * c + ch, w, c, r, ww, fw, line.data());
-            for (int pass = 0; pass < 3; ++pass)  // along every column
-                for (uint64_t x = 0; x < w; ++x)
-                    for (uint32_t ch = 0; ch < c; ++ch) blur_line(out + x * c + ch, h, uint64_t(w) * c, r, ww, fw, line.data());
-            continue;
-        }
-        if (photo_is_sharp(op)) {  // every sample from the view as it stands before the op: a copy of it
-            before.assign(out, out + size_t(n * c));
-            const uint64_t pitch = uint64_t(w) * c;
-            for (uint64_t y = 0; y < h; ++y)
-                for (uint64_t x = 0; x < w; ++x)
-                    for (uint32_t ch = 0; ch < c; ++ch) {
-                        const uint8_t* const p = before.data() + y * pitch + x * c + ch;
-                        uint32_t d = *p;
-                        if (photo_smooth_interior(x, y, w, h)) {
-                            uint32_t sum9 = 0;
-                            for (int dy = -1; dy <= 1; ++dy)
-                                for (int dx = -1; dx <= 1; ++dx) sum9 += p[int64_t(dy) * int64_t(pitch) + dx * int64_t(c)];
-                            d = photo_smooth(sum9, *p);
+                    for (uint64_t x = 0; x < w; ++x)
+                        for (uint32_t ch = 0; ch < c; ++ch) {
+                            const uint8_t* const p = before.data() + y * pitch + x * c + ch;
+                            uint32_t d = *p;
+                            if (photo_smooth_interior(x, y, w, h)) {
+                                uint32_t sum9 = 0;
+                                for (int dy = -1; dy <= 1; ++dy)
+                                    for (int dx = -1; dx <= 1; ++dx) sum9 += p[int64_t(dy) * int64_t(pitch) + dx * int64_t(c)];
+                                d = photo_smooth(sum9, *p);
+                            }
+                            out[y * pitch + x * c + ch] = uint8_t(photo_blend(d, *p, a));
                         }
-                        out[y * pitch + x * c + ch] = uint8_t(photo_blend(d, *p, a));
+                break;
+            }
+            case PhotoKind::kPixel: {  // (one channel: nothing to mix)
+                if (c != 3) break;
+                const uint32_t shift = op == LLCOMP_MI_PHOTO_ADJUST_HUE ? photo_hue_shift(a) : 0u;
+                for (uint64_t i = 0; i < n; ++i) {
+                    uint8_t* p = out + 3 * i;
+                    uint32_t r = p[0], g = p[1], b = p[2];
+                    photo_pixel(op, a, shift, r, g, b);
+                    p[0] = uint8_t(r);
+                    p[1] = uint8_t(g);
+                    p[2] = uint8_t(b);
+                }
+                break;
+            }
+            case PhotoKind::kTable: {
+                uint64_t sum_l = 0;
+                if (photo_needs_stats(op)) {
+                    std::fill(hist.begin(), hist.end(), 0u);
+                    for (uint64_t i = 0; i < n; ++i) {
+                        const uint8_t* p = out + c * i;
+                        for (uint32_t ch = 0; ch < c; ++ch) ++hist[256 * ch + p[ch]];
+                        sum_l += c == 3 ? photo_luma(p[0], p[1], p[2]) : p[0];
                     }
-            continue;
-        }
-        if (!photo_is_table(op)) {
-            if (c != 3) continue;
-            const uint32_t shift = op == LLCOMP_MI_PHOTO_ADJUST_HUE ? photo_hue_shift(a) : 0u;
-            for (uint64_t i = 0; i < n; ++i) {
-                uint8_t* p = out + 3 * i;
-                uint32_t r = p[0], g = p[1], b = p[2];
-                if (op == LLCOMP_MI_PHOTO_COLOR)
-                    photo_color(r, g, b, a);
-                else if (op == LLCOMP_MI_PHOTO_ADJUST_HUE)
-                    photo_hue(r, g, b, shift);
-                else
-                    photo_grayscale(r, g, b);
-                p[0] = uint8_t(r);
-                p[1] = uint8_t(g);
-                p[2] = uint8_t(b);
-            }
-            continue;
-        }
-        uint64_t sum_l = 0;
-        if (photo_needs_stats(op)) {
-            std::fill(hist.begin(), hist.end(), 0u);
-            for (uint64_t i = 0; i < n; ++i) {
-                const uint8_t* p = out + c * i;
-                for (uint32_t ch = 0; ch < c; ++ch) ++hist[256 * ch + p[ch]];
-                sum_l += c == 3 ? photo_luma(p[0], p[1], p[2]) : p[0];
+                }
+                uint8_t lut[3][256];
+                for (uint32_t ch = 0; ch < c; ++ch) photo_table(op, a, hist.data() + 256 * ch, sum_l, n, lut[ch]);
+                for (uint64_t i = 0; i < n; ++i)
+                    for (uint32_t ch = 0; ch < c; ++ch) out[c * i + ch] = lut[ch][out[c * i + ch]];
+                break;
             }
         }
-        uint8_t lut[3][256];
-        for (uint32_t ch = 0; ch < c; ++ch) photo_table(op, a, hist.data() + 256 * ch, sum_l, n, lut[ch]);
-        for (uint64_t i = 0; i < n; ++i)
-            for (uint32_t ch = 0; ch < c; ++ch) out[c * i + ch] = lut[ch][out[c * i + ch]];
     }
     return LLCOMP_MI_OK;
 }

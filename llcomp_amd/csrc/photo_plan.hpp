@@ -1,6 +1,6 @@
 // photo_plan.hpp -- the host half of the photometric chains (include/llcomp_mi.h: llcomp_mi_codec_decode_photo_views /
-// _photo_warped_views): the limits, which groups run chains, how their views are chunked through the staging buffer, which steps need a
-// statistics or a table launch, and the block of chains the call's one copy carries behind its tail's block.  Plain C++
+// _photo_warped_views): the limits, which groups run chains, how their views are chunked through the staging buffer, what the ops of
+// each step are (PhotoStepInfo: the step's launches), and the block of chains the call's one copy carries behind its tail's block.  Plain C++
 // (photo_plan.cpp), like windows_plan.cpp: it builds and runs under a host sanitizer (tests/helpers/photo_plan_check.cpp).  The rule
 // itself: photo_rule.hpp.  The driver: codec.hip, photo_tail_of (views_call, warped_call) and windows_photo behind every chunk of
 // windows_groups; where the block sits in the copy: windows_plan.hpp, CopyLayout.
@@ -34,16 +34,28 @@ inline uint64_t photo_sharp_halo_bytes(uint32_t ow, uint32_t oh, uint32_t c, uin
 // kSharpKeepRows of them keeps bands of kSharpKeepRows, whatever they take.)
 uint32_t photo_sharp_band_rows(uint32_t ow, uint32_t oh, uint32_t c, uint64_t samples);
 
+// What the views of a group do at one step of their chains, which is what the step launches (photo.hpp): bit K of `kinds` -- some
+// view's op of the step is of PhotoKind K (photo_rule.hpp); stats -- some view's op reads the view's statistics.
+enum class PhotoKind : uint32_t;  // (photo_rule.hpp's, which this header leaves to the files of the rule: its pragma is theirs)
+struct PhotoStepInfo {
+    uint32_t kinds = 0;
+    bool stats = false;
+    bool has(PhotoKind k) const { return (kinds >> uint32_t(k)) & 1u; }
+};
+constexpr uint64_t kPhotoNoHalo = ~uint64_t(0);
+
 // One group of the call.  active: some view has a chain that is not empty -- the group's tail entry then writes plain U8 HWC into the
 // staging buffer, `chunk` views at a time, and the chain's last step writes d_out in format `out` through the table at table_at of the
 // tail's output tables (all three taken over from the tail's group).  first: the group's chains in the block.  steps: the longest chain.
-// Bit k of stats_steps / table_steps / area_steps / sharp_steps: some view's op k needs the statistics pass / is a table / is the blur,
-// which the row and column kernels run in place of the per-pixel pass / is the sharpness, which k_photo_sharp runs in its place.
-// sharp_rows: the rows of a band of the sharpness kernel, 0 for a group without the op; a chunk of such a group is `chunk` views and
-// behind them `chunk` halo areas of photo_sharp_halo_bytes each, and the two together stay within the planner's bound.
+// step[k]: what the views' ops k are, k < steps.  sharp_rows: the rows of a band of the sharpness kernel, 0 for a group without the
+// op; a chunk of such a group is `chunk` views and behind them `chunk` halo areas of photo_sharp_halo_bytes each, and the two together
+// stay within the planner's bound.  halo_at: where in the staging buffer those areas begin -- behind the `chunk` views of a full
+// chunk -- or kPhotoNoHalo for a group that saves no rows (no sharpness, or one band per view).
 struct PhotoGroup {
     bool active = false;
-    uint32_t n = 0, ow = 0, oh = 0, first = 0, chunk = 0, steps = 0, stats_steps = 0, table_steps = 0, area_steps = 0, sharp_steps = 0, sharp_rows = 0;
+    uint32_t n = 0, ow = 0, oh = 0, first = 0, chunk = 0, steps = 0, sharp_rows = 0;
+    uint64_t halo_at = kPhotoNoHalo;
+    PhotoStepInfo step[LLCOMP_MI_PHOTO_MAX_OPS];
     OutFormat out;
     void* d_out = nullptr;
     uint64_t table_at = 0;

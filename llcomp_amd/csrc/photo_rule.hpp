@@ -29,19 +29,18 @@ LLMI_HD inline uint32_t photo_blend(uint32_t d, uint32_t v, float a) {
     return t <= 0.0f ? 0u : (t >= 255.0f ? 255u : uint32_t(int32_t(t)));
 }
 
-// the ops that need the view's statistics first (CONTRAST the sum of L, the other two a histogram per channel) ...
+// Every op is of one kind: it says which kernels take a view in a step (photo_kernels.hip) and which branch the host's reference
+// (photo_plan.cpp).  kPixel: computed from the pixel by itself (photo_pixel), and what is no op code at all, for which nothing is
+// computed.  kTable: one table per channel, the rest of the pointwise family 0..8.  kBlur: GAUSSIAN_BLUR.  kSharp: ADJUST_SHARPNESS.
+enum class PhotoKind : uint32_t { kPixel, kTable, kBlur, kSharp };
+LLMI_HD inline PhotoKind photo_kind(uint32_t op) {
+    if (op < LLCOMP_MI_PHOTO_OP_COUNT) return op == LLCOMP_MI_PHOTO_COLOR || op == LLCOMP_MI_PHOTO_GRAYSCALE ? PhotoKind::kPixel : PhotoKind::kTable;
+    return op == LLCOMP_MI_PHOTO_GAUSSIAN_BLUR ? PhotoKind::kBlur : op == LLCOMP_MI_PHOTO_ADJUST_SHARPNESS ? PhotoKind::kSharp : PhotoKind::kPixel;
+}
+// the ops of kTable that need the view's statistics first (CONTRAST the sum of L, the other two a histogram per channel)
 LLMI_HD inline bool photo_needs_stats(uint32_t op) {
     return op == LLCOMP_MI_PHOTO_CONTRAST || op == LLCOMP_MI_PHOTO_AUTOCONTRAST || op == LLCOMP_MI_PHOTO_EQUALIZE;
 }
-// ... and the ops that are one table per channel (every op of the pointwise family 0..8 but the two that mix channels)
-LLMI_HD inline bool photo_is_table(uint32_t op) {
-    return op < LLCOMP_MI_PHOTO_OP_COUNT && op != LLCOMP_MI_PHOTO_COLOR && op != LLCOMP_MI_PHOTO_GRAYSCALE;
-}
-// ... and the op whose output sample reads other samples of the view: it has kernels of its own (photo_kernels.hip: k_photo_blur_*)
-LLMI_HD inline bool photo_is_area(uint32_t op) { return op == LLCOMP_MI_PHOTO_GAUSSIAN_BLUR; }
-// ... and the op whose output sample reads its 3 x 3 neighbourhood: NOT an area op in the sense above -- the blur's kernels and the
-// per-pixel pass both sit out of it, and k_photo_sharp runs it
-LLMI_HD inline bool photo_is_sharp(uint32_t op) { return op == LLCOMP_MI_PHOTO_ADJUST_SHARPNESS; }
 
 // the limits of one op: finite factors within 0..256, an integer threshold within 0..256, integer bits within 1..8, a finite radius
 // within 0..LLCOMP_MI_PHOTO_MAX_RADIUS, a finite hue factor within -0.5..0.5
@@ -135,15 +134,6 @@ LLMI_HD inline void photo_table(uint32_t op, float param, const Hist& hist, uint
     }
 }
 
-// The two ops that mix channels, on one RGB pixel in place
-LLMI_HD inline void photo_color(uint32_t& r, uint32_t& g, uint32_t& b, float a) {
-    const uint32_t l = photo_luma(r, g, b);
-    r = photo_blend(l, r, a);
-    g = photo_blend(l, g, a);
-    b = photo_blend(l, b, a);
-}
-LLMI_HD inline void photo_grayscale(uint32_t& r, uint32_t& g, uint32_t& b) { r = g = b = photo_luma(r, g, b); }
-
 // GAUSSIAN_BLUR: the box of ImageFilter.GaussianBlur(radius) with three passes -- r its whole radius, ww the weight of the 2r + 1
 // samples inside, fw that of the two samples at r + 1, in units of 2^-24.  Binary32 throughout but the square root.
 LLMI_HD inline void photo_blur_weights(float radius, uint32_t& r, uint32_t& ww, uint32_t& fw) {
@@ -226,6 +216,19 @@ LLMI_HD inline void photo_hue(uint32_t& r, uint32_t& g, uint32_t& b, uint32_t sh
     uint32_t hh, ss, vv;
     photo_rgb2hsv(r, g, b, hh, ss, vv);
     photo_hsv2rgb((hh + shift) & 0xFFu, ss, vv, r, g, b);
+}
+
+// The ops of kPixel on one RGB pixel in place: COLOR blends with the pixel's own L, GRAYSCALE is it, ADJUST_HUE adds `shift` to H --
+// photo_hue_shift(param), the caller's, so that it stays out of the loop over the pixels.  Any other op leaves the pixel as it is.
+LLMI_HD inline void photo_pixel(uint32_t op, float param, uint32_t shift, uint32_t& r, uint32_t& g, uint32_t& b) {
+    if (op == LLCOMP_MI_PHOTO_COLOR) {
+        const uint32_t l = photo_luma(r, g, b);
+        r = photo_blend(l, r, param), g = photo_blend(l, g, param), b = photo_blend(l, b, param);
+    } else if (op == LLCOMP_MI_PHOTO_GRAYSCALE) {
+        r = g = b = photo_luma(r, g, b);
+    } else if (op == LLCOMP_MI_PHOTO_ADJUST_HUE) {
+        photo_hue(r, g, b, shift);
+    }
 }
 
 }  // namespace llcomp_mi

@@ -1,5 +1,5 @@
 // photo_area_check.cpp -- GAUSSIAN_BLUR and ADJUST_HUE of the photometric chains on the host under a sanitizer: the planner
-// (llcomp_amd/csrc/photo_plan.hpp: photo_setup, with its area_steps mask) over seeded groups whose chains lie in heap arrays of exactly
+// (llcomp_amd/csrc/photo_plan.hpp: photo_setup, with the blur in its record of every step) over seeded groups whose chains lie in heap arrays of exactly
 // n_views chains, llcomp_mi_photo_reference with image and output in heap buffers of exactly their sizes -- out of place, in place, op by
 // op -- on chains that mix the two ops with the pointwise family, the rule's functions at the ends of their domains, and the
 // refusals.  Host code only; built and run by tests/test_photo_area_sanitizers.py:
@@ -16,18 +16,11 @@
 #include <vector>
 
 #include "../../include/llcomp_mi.h"
+#include "photo_check.hpp"
 #include "photo_plan.hpp"
 #include "photo_rule.hpp"
 
 using namespace llcomp_mi;
-
-#define CHECK(x)                                                  \
-    do {                                                          \
-        if (!(x)) {                                               \
-            std::printf("FAILED %s (line %d)\n", #x, __LINE__);   \
-            return 1;                                             \
-        }                                                         \
-    } while (0)
 
 namespace {
 
@@ -48,16 +41,6 @@ llcomp_mi_photo_op random_op(std::mt19937& rng) {
     return o;
 }
 
-std::unique_ptr<llcomp_mi_photo_chain[]> random_chains(uint32_t n, std::mt19937& rng) {
-    std::unique_ptr<llcomp_mi_photo_chain[]> ch(new llcomp_mi_photo_chain[n]);
-    for (uint32_t i = 0; i < n; ++i) {
-        std::memset(&ch[i], 0xEE, sizeof ch[i]);
-        ch[i].n_ops = rng() % (LLCOMP_MI_PHOTO_MAX_OPS + 1);
-        for (uint32_t k = 0; k < ch[i].n_ops; ++k) ch[i].ops[k] = random_op(rng);
-    }
-    return ch;
-}
-
 int check_setup(uint32_t c, std::mt19937& rng) {
     const uint32_t n_groups = 1 + rng() % 3;
     std::vector<uint32_t> n(n_groups), ow(n_groups), oh(n_groups);
@@ -67,7 +50,7 @@ int check_setup(uint32_t c, std::mt19937& rng) {
         n[g] = 1 + rng() % 20;
         ow[g] = 1 + rng() % 5000;  // (no side limit: any width and height is taken)
         oh[g] = 1 + rng() % 5000;
-        chains[g] = random_chains(n[g], rng);
+        chains[g] = heap_chains(n[g], rng, random_op);
         photo[g] = llcomp_mi_photo_group{uint32_t(sizeof(llcomp_mi_photo_group)), chains[g].get()};
     }
     PhotoTail t;
@@ -86,7 +69,12 @@ int check_setup(uint32_t c, std::mt19937& rng) {
         const PhotoGroup& pg = t.groups[g];
         CHECK(pg.active == (steps > 0));
         if (!pg.active) continue;
-        CHECK(pg.steps == steps && pg.stats_steps == stats && pg.table_steps == table && pg.area_steps == area);
+        CHECK(pg.steps == steps);
+        for (uint32_t k = 0; k < LLCOMP_MI_PHOTO_MAX_OPS; ++k) {
+            const PhotoStepInfo& st = pg.step[k];
+            CHECK(st.stats == ((stats >> k) & 1u) && st.has(PhotoKind::kTable) == ((table >> k) & 1u) && st.has(PhotoKind::kBlur) == ((area >> k) & 1u));
+            CHECK(!st.has(PhotoKind::kSharp));
+        }
         CHECK(pg.n == n[g] && pg.ow == ow[g] && pg.oh == oh[g] && pg.chunk >= 1 && pg.chunk <= pg.n);
     }
     return 0;
@@ -97,7 +85,7 @@ int check_reference(uint32_t w, uint32_t h, uint32_t c, std::mt19937& rng) {
     std::unique_ptr<uint8_t[]> img(new uint8_t[bytes]), out(new uint8_t[bytes]), twice(new uint8_t[bytes]);
     const uint32_t kind = rng() % 3;  // noise, a constant, two values
     for (size_t i = 0; i < bytes; ++i) img[i] = kind == 0 ? uint8_t(rng()) : kind == 1 ? uint8_t(77) : uint8_t(i % 7 ? 10 : 200);
-    const std::unique_ptr<llcomp_mi_photo_chain[]> ch = random_chains(1, rng);
+    const std::unique_ptr<llcomp_mi_photo_chain[]> ch = heap_chains(1, rng, random_op);
     CHECK(llcomp_mi_photo_reference(img.get(), w, h, c, ch[0].ops, ch[0].n_ops, out.get()) == LLCOMP_MI_OK);
     std::memcpy(twice.get(), img.get(), bytes);
     CHECK(llcomp_mi_photo_reference(twice.get(), w, h, c, ch[0].ops, ch[0].n_ops, twice.get()) == LLCOMP_MI_OK);  // in place
@@ -166,8 +154,8 @@ int check_refusals() {
         CHECK(llcomp_mi_photo_reference(img.get(), 8, 8, 3, ch[1].ops, 2, out.get()) == LLCOMP_MI_BAD_ARGS);
         for (size_t i = 0; i < 8 * 8 * 3; ++i) CHECK(out[i] == 0x5A);
     }
-    CHECK(photo_is_area(LLCOMP_MI_PHOTO_GAUSSIAN_BLUR) && !photo_is_area(LLCOMP_MI_PHOTO_ADJUST_HUE));
-    for (uint32_t op : {uint32_t(LLCOMP_MI_PHOTO_GAUSSIAN_BLUR), uint32_t(LLCOMP_MI_PHOTO_ADJUST_HUE)}) CHECK(!photo_is_table(op) && !photo_needs_stats(op));
+    CHECK(photo_kind(LLCOMP_MI_PHOTO_GAUSSIAN_BLUR) == PhotoKind::kBlur && photo_kind(LLCOMP_MI_PHOTO_ADJUST_HUE) == PhotoKind::kPixel);
+    for (uint32_t op : {uint32_t(LLCOMP_MI_PHOTO_GAUSSIAN_BLUR), uint32_t(LLCOMP_MI_PHOTO_ADJUST_HUE)}) CHECK(!photo_needs_stats(op));
     CHECK(photo_op_ok(LLCOMP_MI_PHOTO_GAUSSIAN_BLUR, 0.0f) && photo_op_ok(LLCOMP_MI_PHOTO_GAUSSIAN_BLUR, 32.0f));
     CHECK(photo_op_ok(LLCOMP_MI_PHOTO_ADJUST_HUE, 0.5f) && photo_op_ok(LLCOMP_MI_PHOTO_ADJUST_HUE, -0.5f));
     return 0;

@@ -1,8 +1,8 @@
 // photo_plan_check.cpp -- the host planner of the photometric chains (llcomp_amd/csrc/photo_plan.hpp) and the rule's host functions
 // (photo_rule.hpp, llcomp_mi_photo_reference) under a sanitizer: seeded random groups with chains read from heap arrays of exactly
 // n_views chains -- the block put into a heap buffer of exactly its size and within the bound the codec sizes its staging buffer by,
-// every chunk within the staging bound and within what the statistics and tables are allocated for, the step masks those of the
-// chains -- the reference with image and output in heap buffers of exactly their sizes, in place too, and the refusals.  Host code
+// every chunk within the staging bound and within what the statistics and tables are allocated for, the record of every step that of
+// the chains' ops, kind by kind -- the reference with image and output in heap buffers of exactly their sizes, in place too, and the refusals.  Host code
 // only; built and run by tests/test_photo_plan_sanitizers.py:
 //   g++ -std=c++17 -O1 -g -Wall -Wextra -Werror -fsanitize=address,undefined -fno-sanitize-recover=all -I llcomp_amd/csrc
 //       tests/helpers/photo_plan_check.cpp llcomp_amd/csrc/photo_plan.cpp
@@ -17,18 +17,11 @@
 #include <vector>
 
 #include "../../include/llcomp_mi.h"
+#include "photo_check.hpp"
 #include "photo_plan.hpp"
 #include "photo_rule.hpp"
 
 using namespace llcomp_mi;
-
-#define CHECK(x)                                                  \
-    do {                                                          \
-        if (!(x)) {                                               \
-            std::printf("FAILED %s (line %d)\n", #x, __LINE__);   \
-            return 1;                                             \
-        }                                                         \
-    } while (0)
 
 namespace {
 
@@ -38,17 +31,6 @@ llcomp_mi_photo_op random_op(std::mt19937& rng) {
     const float factors[5] = {0.0f, 1.0f, 0.37f, 2.75f, 256.0f};
     o.param = o.op == LLCOMP_MI_PHOTO_SOLARIZE ? float(rng() % 257) : o.op == LLCOMP_MI_PHOTO_POSTERIZE ? float(1 + rng() % 8) : factors[rng() % 5];
     return o;
-}
-
-// chains on the heap, exactly n of them: a read past the last one is the sanitizer's to report
-std::unique_ptr<llcomp_mi_photo_chain[]> random_chains(uint32_t n, bool all_empty, std::mt19937& rng) {
-    std::unique_ptr<llcomp_mi_photo_chain[]> ch(new llcomp_mi_photo_chain[n]);
-    for (uint32_t i = 0; i < n; ++i) {
-        std::memset(&ch[i], 0xEE, sizeof ch[i]);  // (what lies behind a chain's ops is never read as an op)
-        ch[i].n_ops = all_empty ? 0 : rng() % (LLCOMP_MI_PHOTO_MAX_OPS + 1);
-        for (uint32_t k = 0; k < ch[i].n_ops; ++k) ch[i].ops[k] = random_op(rng);
-    }
-    return ch;
 }
 
 int check_setup(uint32_t c, uint64_t samples, std::mt19937& rng) {
@@ -63,7 +45,7 @@ int check_setup(uint32_t c, uint64_t samples, std::mt19937& rng) {
         oh[g] = 1 + rng() % 48;
         total += n[g];
         const uint32_t kind = rng() % 4;  // no chains, all empty, or chains
-        if (kind) chains[g] = random_chains(n[g], kind == 1, rng);
+        if (kind) chains[g] = heap_chains(n[g], rng, random_op, kind == 1);
         photo[g] = llcomp_mi_photo_group{uint32_t(sizeof(llcomp_mi_photo_group)), chains[g].get()};
     }
     PhotoTail t;
@@ -74,18 +56,24 @@ int check_setup(uint32_t c, uint64_t samples, std::mt19937& rng) {
     uint64_t at = 0;
     for (uint32_t g = 0; g < n_groups; ++g) {
         const PhotoGroup& pg = t.groups[g];
-        uint32_t steps = 0, stats = 0, table = 0;
+        uint32_t steps = 0, stats = 0, kinds[4] = {};  // bit k: some view's op k reads statistics / is of the kind
         if (chains[g])
             for (uint32_t i = 0; i < n[g]; ++i) {
                 steps = std::max(steps, chains[g][i].n_ops);
                 for (uint32_t k = 0; k < chains[g][i].n_ops; ++k) {
                     if (photo_needs_stats(chains[g][i].ops[k].op)) stats |= 1u << k;
-                    if (photo_is_table(chains[g][i].ops[k].op)) table |= 1u << k;
+                    kinds[uint32_t(photo_kind(chains[g][i].ops[k].op))] |= 1u << k;
                 }
             }
         CHECK(pg.active == (steps > 0));
         if (!pg.active) continue;
-        CHECK(pg.steps == steps && pg.stats_steps == stats && pg.table_steps == table && pg.n == n[g] && pg.ow == ow[g] && pg.oh == oh[g]);
+        CHECK(pg.steps == steps && pg.n == n[g] && pg.ow == ow[g] && pg.oh == oh[g]);
+        for (uint32_t k = 0; k < LLCOMP_MI_PHOTO_MAX_OPS; ++k) {  // (beyond the longest chain: nothing)
+            CHECK(pg.step[k].stats == ((stats >> k) & 1u));
+            for (PhotoKind kind : {PhotoKind::kPixel, PhotoKind::kTable, PhotoKind::kBlur, PhotoKind::kSharp})
+                CHECK(pg.step[k].has(kind) == ((kinds[uint32_t(kind)] >> k) & 1u));
+        }
+        CHECK(pg.sharp_rows == 0 && pg.halo_at == kPhotoNoHalo);  // (this program's ops are the pointwise family)
         CHECK(pg.first == at && pg.chunk >= 1 && pg.chunk <= pg.n && pg.chunk <= t.tab_views);
         const uint64_t per_view = uint64_t(oh[g]) * ow[g] * c;
         CHECK(pg.chunk * per_view <= t.stage_bytes && (pg.chunk == 1 || pg.chunk * per_view <= samples));
@@ -107,7 +95,7 @@ int check_reference(uint32_t w, uint32_t h, uint32_t c, std::mt19937& rng) {
     std::unique_ptr<uint8_t[]> img(new uint8_t[bytes]), out(new uint8_t[bytes]), twice(new uint8_t[bytes]);
     const uint32_t kind = rng() % 3;  // noise, a constant, two values
     for (size_t i = 0; i < bytes; ++i) img[i] = kind == 0 ? uint8_t(rng()) : kind == 1 ? uint8_t(77) : uint8_t(i % 7 ? 10 : 200);
-    const std::unique_ptr<llcomp_mi_photo_chain[]> ch = random_chains(1, false, rng);
+    const std::unique_ptr<llcomp_mi_photo_chain[]> ch = heap_chains(1, rng, random_op);
     CHECK(llcomp_mi_photo_reference(img.get(), w, h, c, ch[0].ops, ch[0].n_ops, out.get()) == LLCOMP_MI_OK);
     std::memcpy(twice.get(), img.get(), bytes);
     CHECK(llcomp_mi_photo_reference(twice.get(), w, h, c, ch[0].ops, ch[0].n_ops, twice.get()) == LLCOMP_MI_OK);  // in place

@@ -17,18 +17,11 @@
 #include <vector>
 
 #include "../../include/llcomp_mi.h"
+#include "photo_check.hpp"
 #include "photo_plan.hpp"
 #include "photo_rule.hpp"
 
 using namespace llcomp_mi;
-
-#define CHECK(x)                                                  \
-    do {                                                          \
-        if (!(x)) {                                               \
-            std::printf("FAILED %s (line %d)\n", #x, __LINE__);   \
-            return 1;                                             \
-        }                                                         \
-    } while (0)
 
 namespace {
 
@@ -45,13 +38,7 @@ llcomp_mi_photo_op random_op(std::mt19937& rng, bool sharp_only) {
 }
 
 std::unique_ptr<llcomp_mi_photo_chain[]> random_chains(uint32_t n, std::mt19937& rng) {
-    std::unique_ptr<llcomp_mi_photo_chain[]> ch(new llcomp_mi_photo_chain[n]);
-    for (uint32_t i = 0; i < n; ++i) {
-        std::memset(&ch[i], 0xEE, sizeof ch[i]);
-        ch[i].n_ops = rng() % (LLCOMP_MI_PHOTO_MAX_OPS + 1);
-        for (uint32_t k = 0; k < ch[i].n_ops; ++k) ch[i].ops[k] = random_op(rng, false);
-    }
-    return ch;
+    return heap_chains(n, rng, [](std::mt19937& r) { return random_op(r, false); });
 }
 
 // The plan of one group against its bound: what the driver and the kernels will address lies inside stage_bytes, and stage_bytes
@@ -59,8 +46,8 @@ std::unique_ptr<llcomp_mi_photo_chain[]> random_chains(uint32_t n, std::mt19937&
 int check_group(const PhotoGroup& pg, const PhotoTail& t, uint32_t c, uint64_t samples) {
     const uint64_t pitch = uint64_t(pg.ow) * c, view = pitch * pg.oh;
     CHECK(pg.chunk >= 1 && pg.chunk <= pg.n);  // (a single view is always planned)
-    if (!pg.sharp_steps) {
-        CHECK(pg.sharp_rows == 0);
+    if (!std::any_of(pg.step, pg.step + pg.steps, [](const PhotoStepInfo& s) { return s.has(PhotoKind::kSharp); })) {
+        CHECK(pg.sharp_rows == 0 && pg.halo_at == kPhotoNoHalo);
         CHECK(pg.chunk * view <= t.stage_bytes && (pg.chunk == 1 || pg.chunk * view <= samples));
         return 0;
     }
@@ -84,6 +71,7 @@ int check_group(const PhotoGroup& pg, const PhotoTail& t, uint32_t c, uint64_t s
     // the addresses: view i of a chunk at i * view, its halo area at chunk * view + i * halo, pair j of rows there at j * 2 * pitch,
     // copied from rows (j + 1) * rows - 1 and (j + 1) * rows of the view
     const uint64_t halo_at = uint64_t(pg.chunk) * view;
+    CHECK(pg.halo_at == (halo ? halo_at : kPhotoNoHalo));  // (the planner's offset is this sum, or none where nothing is saved)
     for (uint32_t i : {0u, pg.chunk - 1}) {
         for (uint32_t j : {0u, bands > 1 ? bands - 2 : 0u}) {
             if (bands < 2) break;
@@ -128,7 +116,9 @@ int check_setup(uint32_t c, std::mt19937& rng) {
         const PhotoGroup& pg = t.groups[g];
         CHECK(pg.active == (steps > 0));
         if (!pg.active) continue;
-        CHECK(pg.steps == steps && pg.sharp_steps == sharp && pg.area_steps == area);
+        CHECK(pg.steps == steps);
+        for (uint32_t k = 0; k < LLCOMP_MI_PHOTO_MAX_OPS; ++k)
+            CHECK(pg.step[k].has(PhotoKind::kSharp) == ((sharp >> k) & 1u) && pg.step[k].has(PhotoKind::kBlur) == ((area >> k) & 1u));
         CHECK(pg.n == n[g] && pg.ow == ow[g] && pg.oh == oh[g]);
         if (check_group(pg, t, c, samples)) return 1;
     }
@@ -154,7 +144,8 @@ int check_corners() {
                 const uint64_t samples = uint64_t(frames) * 100 * 44 * c;
                 PhotoTail t;
                 CHECK(photo_setup(c, samples, photo, 1, n, ow, oh, t) == LLCOMP_MI_OK);
-                CHECK(t.stage_bytes <= samples && t.groups[0].sharp_steps == 2u);
+                CHECK(t.stage_bytes <= samples);
+                for (uint32_t k = 0; k < LLCOMP_MI_PHOTO_MAX_OPS; ++k) CHECK(t.groups[0].step[k].has(PhotoKind::kSharp) == (k == 1));
                 if (check_group(t.groups[0], t, c, samples)) return 1;
                 if (frames == 1) CHECK(t.groups[0].chunk == 1 && t.groups[0].sharp_rows == 44);
                 if (frames == 3) CHECK(t.groups[0].sharp_rows == kSharpBandRows && t.groups[0].chunk == std::min(views, 2u));
@@ -218,8 +209,8 @@ int check_rule() {
     }
     CHECK(photo_smooth_interior(1, 1, 3, 3) && !photo_smooth_interior(0, 1, 3, 3) && !photo_smooth_interior(2, 1, 3, 3) && !photo_smooth_interior(1, 0, 3, 3) &&
           !photo_smooth_interior(1, 2, 3, 3) && !photo_smooth_interior(0, 0, 1, 1) && !photo_smooth_interior(1, 1, 2, 9) && !photo_smooth_interior(1, 1, 9, 2));
-    CHECK(photo_is_sharp(LLCOMP_MI_PHOTO_ADJUST_SHARPNESS) && !photo_is_area(LLCOMP_MI_PHOTO_ADJUST_SHARPNESS) && !photo_is_table(LLCOMP_MI_PHOTO_ADJUST_SHARPNESS) &&
-          !photo_needs_stats(LLCOMP_MI_PHOTO_ADJUST_SHARPNESS) && !photo_is_sharp(LLCOMP_MI_PHOTO_GAUSSIAN_BLUR) && !photo_is_sharp(18));
+    CHECK(photo_kind(LLCOMP_MI_PHOTO_ADJUST_SHARPNESS) == PhotoKind::kSharp && !photo_needs_stats(LLCOMP_MI_PHOTO_ADJUST_SHARPNESS) &&
+          photo_kind(LLCOMP_MI_PHOTO_GAUSSIAN_BLUR) == PhotoKind::kBlur && photo_kind(18) == PhotoKind::kPixel);
     return 0;
 }
 

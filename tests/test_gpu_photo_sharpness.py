@@ -1,6 +1,6 @@
 """ADJUST_SHARPNESS in the photometric chains on the GPU (include/llcomp_mi.h: "Photometric chains"; k_photo_sharp_save and k_photo_sharp,
-llcomp_amd/csrc/photo_kernels.hip).  The way of checking is test_gpu_photo_area.py's: the expected bytes of a view are
-tests/photo_sharpness_spec.py -- the rule restated with numpy in integers, itself pinned to PIL by tests/test_photo_sharpness_rule.py --
+llcomp_amd/csrc/photo_kernels.hip).  The way of checking is tests/photo_gpu.py's: the expected bytes of a view are
+tests/photo_spec.py -- the rule restated with numpy in integers, itself pinned to PIL by tests/test_photo_sharpness_rule.py --
 applied to what the existing call writes for the same view as U8 HWC, then llcomp_mi_output_table for a formatted group, bit for bit.
 
 The kernel's thresholds, each with a shape on either side beside the issue's shapes:
@@ -16,11 +16,10 @@ of more than 12288 bytes is 50 MB, and tests/helpers/photo_sharp_check.cpp check
 import numpy as np
 import pytest
 
-import photo_sharpness_spec as sharp
 import resize_filters_spec as spec
-from test_gpu_photo_views import FRAMES, GEOS, PG, W, flag, run, views_of
+from photo_gpu import FRAMES, GEOS, PG, W, check, close_shared_codecs, flag, mi, run, setup, views_of  # noqa: F401  (mi: the fixture)
 from test_gpu_regions_host import make_batch, stream
-from test_gpu_resized_output import TOut, norm, place, same_bits
+from test_gpu_resized_output import TOut, same_bits
 from test_gpu_resized_regions import packed
 
 pytestmark = pytest.mark.gpu
@@ -36,44 +35,6 @@ EIGHT_LAST = EIGHT_FIRST[1:5] + [("gaussian_blur", 0.8)] + EIGHT_FIRST[6:] + [("
 WARPS = [(0, 0.9, 0.2, 3.0, -0.2, 0.9, 1.0, flag(spec.BILINEAR)), (2, 1.1, -0.3, 20.0, 0.1, 0.5, 0.5, flag(spec.BILINEAR, True)),
          (2, 0.7, 0.0, 5.25, 0.0, 0.4, 0.5, flag(spec.NEAREST))]
 PADDED = [(0, -10, -5, 60, 30, flag(spec.BILINEAR)), (2, 70, 30, 40, 20, flag(spec.BICUBIC, True)), (2, 10, 5, 30, 20, flag(spec.BOX))]
-
-
-@pytest.fixture(scope="module")
-def mi():
-    import llcomp_amd
-
-    assert llcomp_amd.device_count() >= 1, "GPU tests need a HIP device"
-    return llcomp_amd
-
-
-_state = {}
-
-
-def setup(mi, orc, name):
-    """(c, h, imgs, containers, the batch in HBM, codec) of a geometry, made once for this module"""
-    if name not in _state:
-        c, h, tw, th, planar = GEOS[name]
-        imgs, conts = make_batch(orc, FRAMES, W, h, c, tw, th, planar)
-        _state[name] = (c, h, imgs, conts, packed(mi, conts), mi.Codec(FRAMES, W, h, c, tw, th, planar, device=0))
-    return _state[name]
-
-
-def expected(mi, groups, plain_outs, c):
-    want = []
-    for g, u8 in zip(groups, plain_outs):
-        v = np.stack([sharp.apply(u8[i], ch) for i, ch in enumerate(g.chains())])
-        want.append(place(mi.output_table(c, g.dtype, **norm(c, g.dtype)), v, g.layout))
-    return want
-
-
-def check(mi, codec, groups, c, dev, pad_mode=None, conts=None):
-    """the call with chains against photo_sharpness_spec over the existing call's U8 HWC output; conts: the _host form"""
-    st0, plain = run(mi, codec, groups, c, dev=dev, plain=True, pad_mode=pad_mode)
-    st, outs = run(mi, codec, groups, c, dev=None if conts is not None else dev, conts=conts, pad_mode=pad_mode)
-    assert st == st0 == 0
-    for i, (out, exp) in enumerate(zip(outs, expected(mi, groups, plain, c))):
-        assert same_bits(out, exp), (i, np.argwhere(out != exp)[:4].tolist())
-    return outs, plain
 
 
 def shape_of(shape, c):
@@ -192,6 +153,4 @@ def test_a_bad_factor_leaves_output_and_status_untouched(mi, orc):
 
 
 def test_close_shared_codecs():
-    for s in _state.values():
-        s[5].close()
-    _state.clear()
+    close_shared_codecs()

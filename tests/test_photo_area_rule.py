@@ -1,5 +1,5 @@
 """GAUSSIAN_BLUR and ADJUST_HUE of the photometric chains on the host (include/llcomp_mi.h: "Photometric chains"):
-llcomp_mi_photo_reference -- compiled from the functions the GPU's kernels are compiled from -- against tests/photo_area_spec.py (both
+llcomp_mi_photo_reference -- compiled from the functions the GPU's kernels are compiled from -- against tests/photo_spec.py (both
 rules restated with numpy), against the recorded outputs of PIL in tests/golden/photo_area_rule.json, and against PIL itself where it
 is installed; and the limits."""
 import ctypes as C
@@ -7,7 +7,6 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import photo_area_spec
 import photo_spec
 from conftest import load_golden
 from test_photo_rule import fnv1a64, random_chain
@@ -41,12 +40,12 @@ def test_seeded_mixed_chains_equal_the_spec(mi):
         chain = mixed_chain(rng)
         seen |= {op for op, _ in chain}
         ref = mi.photo_reference(img, chain)
-        assert np.array_equal(ref, photo_area_spec.apply(img, chain)), (i, chain)
+        assert np.array_equal(ref, photo_spec.apply(img, chain)), (i, chain)
         step = img
         for op in chain:  # op by op is the chain
             step = mi.photo_reference(step, [op])
         assert np.array_equal(step, ref), (i, chain)
-    assert seen == set(photo_spec.NAMES) | set(photo_area_spec.AREA_NAMES)
+    assert seen == set(photo_spec.NAMES) | set(photo_spec.AREA_NAMES)
 
 
 def test_reference_equals_the_golden_vectors(mi):
@@ -57,16 +56,16 @@ def test_reference_equals_the_golden_vectors(mi):
         chain = [(v["op"], float.fromhex(v["param"]))]
         ref = mi.photo_reference(img, chain)
         assert fnv1a64(ref.tobytes()) == v["fnv"], v
-        assert np.array_equal(ref, photo_area_spec.apply(img, chain)), v
+        assert np.array_equal(ref, photo_spec.apply(img, chain)), v
     for v in doc["full"]:
         img = np.array(v["image"], np.uint8).reshape(v["h"], v["w"], v["c"])
         want = np.array(v["out"], np.uint8).reshape(img.shape)
         chain = [(v["op"], float.fromhex(v["param"]))]
-        assert np.array_equal(mi.photo_reference(img, chain), want) and np.array_equal(photo_area_spec.apply(img, chain), want)
+        assert np.array_equal(mi.photo_reference(img, chain), want) and np.array_equal(photo_spec.apply(img, chain), want)
     # the box radii the rule's statement quotes
-    assert [float(photo_area_spec.blur_weights(r)[0]) for r in (1.0, 2.0, 12.0)] == [float(np.float32(x)) for x in (0.25000003, 1.375, 11.479167)]
+    assert [float(photo_spec.blur_weights(r)[0]) for r in (1.0, 2.0, 12.0)] == [float(np.float32(x)) for x in (0.25000003, 1.375, 11.479167)]
     # the hue's byte: truncation toward zero, then mod 256 (the float32 nearest 1/255 lies above it, so +-1/255 give +-1: 1 and 255)
-    assert [photo_area_spec.hue_shift(f) for f in (0.1, -0.5, 0.5, 1 / 255, -1 / 255, 0.0, -0.001)] == [25, 129, 127, 1, 255, 0, 0]
+    assert [photo_spec.hue_shift(f) for f in (0.1, -0.5, 0.5, 1 / 255, -1 / 255, 0.0, -0.001)] == [25, 129, 127, 1, 255, 0, 0]
 
 
 def test_reference_equals_pil(mi):
@@ -87,7 +86,7 @@ def test_reference_equals_pil(mi):
     hsv = np.array(Image.fromarray(rgb).convert("HSV"))
     for factor in (0.1, -0.5, 1 / 255):
         shifted = hsv.copy()
-        shifted[..., 0] += np.uint8(photo_area_spec.hue_shift(factor))  # (wraps)
+        shifted[..., 0] += np.uint8(photo_spec.hue_shift(factor))  # (wraps)
         want = np.asarray(Image.frombytes("HSV", (4096, 4096), shifted.tobytes()).convert("RGB"))
         got = mi.photo_reference(rgb, [("adjust_hue", factor)])
         assert np.array_equal(got, want), (factor, int((got != want).any(axis=2).sum()))

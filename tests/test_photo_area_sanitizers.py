@@ -9,7 +9,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_photo_area_ops_under_sanitizers(tmp_path):
     """tests/helpers/photo_area_check.cpp: 2 channel counts x 100 seeded rounds of 1 to 3 groups of up to 5000 x 5000 whose chains mix
-    the two ops with the pointwise family (the step masks, area_steps among them, are those of the chains), then 2 x 150 rounds of the
+    the two ops with the pointwise family (the record of every step, the blur in it, is that of the chains), then 2 x 150 rounds of the
     reference on such chains with every buffer on the heap at its exact size (out of place, in place, op by op), the rule's functions
     at the ends of their domains, and the refusals with the output untouched"""
     exe = str(tmp_path / "photo_area_check")

@@ -1,5 +1,5 @@
 """ADJUST_SHARPNESS of the photometric chains on the host (include/llcomp_mi.h: "Photometric chains"): llcomp_mi_photo_reference --
-compiled from the functions the GPU's kernel is compiled from -- against tests/photo_sharpness_spec.py (the rule restated with numpy, in
+compiled from the functions the GPU's kernel is compiled from -- against tests/photo_spec.py (the rule restated with numpy, in
 integers), against the recorded outputs of PIL in tests/golden/photo_sharpness_rule.json, and against PIL itself where it is installed
 (ImageEnhance.Sharpness, and ImageFilter.SMOOTH at a factor of 0); and the limits."""
 import ctypes as C
@@ -7,7 +7,6 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import photo_sharpness_spec as sharp
 import photo_spec
 from conftest import load_golden
 from test_photo_area_rule import mixed_chain
@@ -42,7 +41,7 @@ def test_seeded_chains_with_the_op_equal_the_spec(mi):
         chain = sharp_chain(rng)
         seen |= {op for op, _ in chain}
         ref = mi.photo_reference(img, chain)
-        assert np.array_equal(ref, sharp.apply(img, chain)), (i, chain)
+        assert np.array_equal(ref, photo_spec.apply(img, chain)), (i, chain)
         step = img
         for op in chain:  # op by op is the chain
             step = mi.photo_reference(step, [op])
@@ -55,24 +54,24 @@ def test_the_float_form_is_the_integer_form():
     rng = np.random.default_rng(5)
     for i in range(60):
         c = (1, 3)[i % 2]
-        img = sharp.gen_image(("noise", "narrow", "checker", "ramp")[i % 4], int(rng.integers(3, 81)), int(rng.integers(3, 81)), c, i)
-        assert np.array_equal(sharp.smooth_float(img), sharp.smooth(img)), i
+        img = photo_spec.gen_image(("noise", "narrow", "checker", "ramp")[i % 4], int(rng.integers(3, 81)), int(rng.integers(3, 81)), c, i)
+        assert np.array_equal(photo_spec.smooth_float(img), photo_spec.smooth(img)), i
 
 
 def test_reference_equals_the_golden_vectors(mi):
     doc = load_golden("photo_sharpness_rule.json")
     assert doc["pillow"] and len(doc["vectors"]) == 2 * 8 * 8 and len(doc["full"]) == 5
     for v in doc["vectors"]:
-        img = sharp.gen_image(v["kind"], v["w"], v["h"], v["c"], v["seed"])
+        img = photo_spec.gen_image(v["kind"], v["w"], v["h"], v["c"], v["seed"])
         chain = [("adjust_sharpness", float.fromhex(v["param"]))]
         ref = mi.photo_reference(img, chain)
         assert fnv1a64(ref.tobytes()) == v["fnv"], v
-        assert np.array_equal(ref, sharp.apply(img, chain)), v
+        assert np.array_equal(ref, photo_spec.apply(img, chain)), v
     for v in doc["full"]:
         img = np.array(v["image"], np.uint8).reshape(v["h"], v["w"], v["c"])
         want = np.array(v["out"], np.uint8).reshape(img.shape)
         chain = [("adjust_sharpness", float.fromhex(v["param"]))]
-        assert np.array_equal(mi.photo_reference(img, chain), want) and np.array_equal(sharp.apply(img, chain), want)
+        assert np.array_equal(mi.photo_reference(img, chain), want) and np.array_equal(photo_spec.apply(img, chain), want)
 
 
 def test_reference_equals_pil(mi):
@@ -85,7 +84,7 @@ def test_reference_equals_pil(mi):
         c = (1, 3)[i % 2]
         w = sides[i % 3] if i < 60 else int(rng.integers(1, 81))
         h = sides[(i // 3) % 3] if i < 30 else int(rng.integers(1, 81))
-        img = sharp.gen_image(("noise", "narrow", "constant", "ramp", "checker")[i % 5], w, h, c, 7000 + i)
+        img = photo_spec.gen_image(("noise", "narrow", "constant", "ramp", "checker")[i % 5], w, h, c, 7000 + i)
         a = float(np.float32((FACTORS + [rng.uniform(0, 2)])[i % 7]))
         im = Image.fromarray(img[..., 0] if c == 1 else img)
         want = np.asarray(ImageEnhance.Sharpness(im).enhance(a)).reshape(img.shape)
@@ -94,7 +93,7 @@ def test_reference_equals_pil(mi):
         if a == 0.0:
             assert np.array_equal(got, np.asarray(im.filter(ImageFilter.SMOOTH)).reshape(img.shape)), (i, w, h, c)
     # black and white: the smooth value and both clamps of the blend reach 0 and 255
-    img = sharp.checker(31, 17, 3, 2)
+    img = photo_spec.checker(31, 17, 3, 2)
     for a in (0.0, 7.5, 256.0):
         got = mi.photo_reference(img, [("adjust_sharpness", a)])
         assert np.array_equal(got, np.asarray(ImageEnhance.Sharpness(Image.fromarray(img)).enhance(a)))
@@ -136,5 +135,5 @@ def test_limits(mi):
         src = photo_spec.gen_image("noise", 33, 21, c, 9)
         apart, inplace = np.empty_like(src), src.copy()
         assert rc(chain, src, apart) == 0 and rc(chain, inplace, inplace) == 0
-        assert np.array_equal(apart, inplace) and np.array_equal(apart, sharp.apply(src, [(o, p) for o, p in chain]))
+        assert np.array_equal(apart, inplace) and np.array_equal(apart, photo_spec.apply(src, [(o, p) for o, p in chain]))
     assert C.sizeof(_lib.PhotoOp) == 8 and C.sizeof(_lib.PhotoChain) == 68 and C.sizeof(_lib.PhotoGroup) == 16

@@ -4,8 +4,8 @@ and, at a = 0, under image.filter(ImageFilter.SMOOTH) -- so that a machine witho
 chains (include/llcomp_mi.h) byte for byte (tests/test_photo_sharpness_rule.py).  Needs Pillow and numpy; run once, by hand:
     python tools/make_photo_sharpness_golden.py
 
-A vector names its image by the seeded generator of tests/photo_spec.py (gen_image: kind, w, h, c, seed) or, kind "checker", by
-tests/photo_sharpness_spec.py's checker(), gives the factor as a float32 in hex and the FNV-1a-64 of PIL's output; the vectors under "full" are tiny and carry
+A vector names its image by the seeded generator of tests/photo_spec.py (gen_image: kind, w, h, c, seed; kind "checker": its
+checker()), gives the factor as a float32 in hex and the FNV-1a-64 of PIL's output; the vectors under "full" are tiny and carry
 input and output in full.  The file records the Pillow version that wrote it."""
 import json
 import os
@@ -19,7 +19,6 @@ import PIL
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import photo_spec  # noqa: E402  (the image generators only: the outputs recorded here are PIL's)
-from photo_sharpness_spec import checker  # noqa: E402
 
 FACTORS = [0.0, 1.0, 2.0, 0.5, 1.9, 7.5, 0.3, 256.0]
 SIZES = [(1, 1), (2, 3), (3, 2), (3, 3), (4, 3), (23, 17), (80, 5), (5, 80)]
@@ -30,10 +29,6 @@ def fnv1a64(data):
     for b in bytes(data):
         h = ((h ^ b) * 0x100000001B3) & 0xFFFFFFFFFFFFFFFF
     return "%016x" % h
-
-
-def image(kind, w, h, c, seed):
-    return checker(w, h, c, seed) if kind == "checker" else photo_spec.gen_image(kind, w, h, c, seed)
 
 
 def pil_sharpness(img, a):
@@ -53,7 +48,7 @@ def main():
             for j, a in enumerate(FACTORS):
                 seed += 1
                 kind = ("noise", "narrow", "ramp", "checker")[(i + j) % 4]
-                img = image(kind, w, h, c, seed)
+                img = photo_spec.gen_image(kind, w, h, c, seed)
                 out = pil_sharpness(img, a)
                 if a == 0.0:
                     assert np.array_equal(out, pil_smooth(img))
@@ -61,7 +56,7 @@ def main():
     full = []
     for c, kind, w, h, a in ((3, "noise", 3, 3, 0.0), (1, "noise", 5, 4, 2.0), (3, "checker", 4, 3, 7.5), (1, "checker", 6, 5, 0.5), (3, "noise", 2, 5, 1.9)):
         seed += 1
-        img = image(kind, w, h, c, seed)
+        img = photo_spec.gen_image(kind, w, h, c, seed)
         full.append(dict(w=w, h=h, c=c, param=float(np.float32(a)).hex(), image=img.reshape(-1).tolist(), out=pil_sharpness(img, a).reshape(-1).tolist()))
     doc = dict(about="PIL %s ImageEnhance.Sharpness on the seeded images of tests/photo_spec.py and the checkers of this tool; written by "
                      "tools/make_photo_sharpness_golden.py" % PIL.__version__, pillow=PIL.__version__, vectors=vectors, full=full)
