@@ -447,6 +447,51 @@ int llcomp_mi_warp_views_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_
  * calls; it is not fast.  BAD_ARGS, out untouched: a NULL src, m or out, a side or c of 0, and the rule's limits.  Host-only. */
 int llcomp_mi_warp_reference(const uint8_t* src, uint32_t w, uint32_t h, uint32_t c, const double* m, uint32_t filter, const uint8_t* fill,
                              uint32_t ow, uint32_t oh, uint8_t* out);
+/* Views under a projective map (llcomp_mi_codec_decode_perspective_views below: torchvision's RandomPerspective, PIL's
+ * Image.transform(PERSPECTIVE)).  A PERSPECTIVE VIEW is a frame and eight numbers a[0..7]; view v of a group is byte for byte what
+ *   PIL.Image.transform((ow, oh), Image.PERSPECTIVE, a, resample, fillcolor=fill)
+ * gives on the decoded frame, for resample NEAREST, BILINEAR or BICUBIC, with independent bands as above (no alpha premultiplication).
+ * THE RULE.  IEEE binary64, every operation rounded by itself, in the order written; the two divisions are true divisions (no
+ * reciprocal).  Output pixel (x, y): xs = x + 0.5, ys = y + 0.5; den = (a6 xs + a7 ys) + 1; xin = ((a0 xs + a1 ys) + a2) / den;
+ * yin = ((a3 xs + a4 ys) + a5) / den.
+ *   BILINEAR and BICUBIC: from (xin, yin) on exactly the affine rule above -- the inside test, the tap origin and fractions, the taps.
+ *   NEAREST (NOT the affine call's 16.16 path): xi = -1 if xin < 0, else xin truncated; yi likewise; the output is P[yi][xi] if
+ *     0 <= xi < w and 0 <= yi < h, else fill.  With a6 = a7 = 0 this need not equal the affine call on a0..a5: it equals PIL's PERSPECTIVE.
+ *   The mirror bit, the fill per channel, the output table and layout: as for the affine views.
+ * LIMITS (BAD_ARGS): a coefficient that is not finite; a filter other than the three; an output side of 0; den, as the rule computes it,
+ * not > 0 at one of the four corner pixels (the rounded den is monotone in x and in y, so its minimum sits at a corner: a map whose
+ * denominator vanishes or changes sign inside the output is refused); |xin| or |yin| not below 2^30 at one of the four corner pixels.
+ * A view with no pixel inside the image is NOT an error: its output is all fill. */
+typedef struct llcomp_mi_perspective_view {
+    uint32_t frame; /* the frame of the batch the view is taken from */
+    uint32_t flags; /* as llcomp_mi_warp_view's: bit 0 mirrors the view's output, bits 4-6 hold the filter code; bits above 7 are ignored */
+    double a[8];    /* output pixel -> source coordinate, as PIL's PERSPECTIVE data */
+} llcomp_mi_perspective_view; /* 72 bytes */
+typedef struct llcomp_mi_perspective_group {
+    uint32_t struct_size;                    /* = sizeof(llcomp_mi_perspective_group); also the stride of an array of groups */
+    uint32_t n_views;                        /* 1 .. 65535 */
+    const llcomp_mi_perspective_view* views; /* HOST memory, read during the call only */
+    uint32_t ow, oh;                         /* the output shape of every view of the group */
+    const llcomp_mi_output_format* fmt;      /* NULL = U8 HWC; read during the call only */
+    void* d_out;                             /* device memory, aligned to the format's element size (the plan does not read it) */
+    const uint8_t* fill;                     /* c HOST bytes, NULL = zeros; read during the call only */
+} llcomp_mi_perspective_group; /* 48 bytes on LP64 */
+/* A rectangle rect = {x, y, rw, rh} of image pixels that CONTAINS every pixel the rule reads for the output pixels that lie inside the
+ * image -- a bound, not the exact box: on no side more than one pixel beyond the taps of an inside pixel -- or *empty = 1 and four
+ * zeros, exactly when no output pixel is inside.  Found from the first and last inside pixel of every output row (DESIGN.md "Perspective
+ * views").  BAD_ARGS, outputs untouched: a NULL pointer, w or h 0, and the rule's limits.  Host-only. */
+int llcomp_mi_perspective_source_rect(uint32_t w, uint32_t h, const double* a, uint32_t filter, uint32_t ow, uint32_t oh, uint32_t rect[4],
+                                      uint32_t* empty);
+/* llcomp_mi_warp_views_plan for perspective groups: the unions, windows and classes of llcomp_mi_views_plan on the views' source
+ * rectangles (llcomp_mi_perspective_source_rect); the same BAD_ARGS cases.  Host-only. */
+int llcomp_mi_perspective_views_plan(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar, uint32_t frames,
+                                     const llcomp_mi_perspective_group* groups, uint32_t n_groups, uint32_t* unions, uint32_t* windows,
+                                     uint32_t* n_used, uint32_t* n_classes);
+/* The perspective rule on a host image, as llcomp_mi_warp_reference states the affine one: src [h][w][c] -> out [oh][ow][c], compiled
+ * from the same functions as the GPU's kernel.  BAD_ARGS, out untouched: a NULL src, a or out, a side or c of 0, and the rule's limits.
+ * Host-only. */
+int llcomp_mi_perspective_reference(const uint8_t* src, uint32_t w, uint32_t h, uint32_t c, const double* a, uint32_t filter,
+                                    const uint8_t* fill, uint32_t ow, uint32_t oh, uint8_t* out);
 /* Photometric chains (llcomp_mi_codec_decode_photo_views / _photo_warped_views below: torchvision's ColorJitter with hue,
  * RandomGrayscale, PIL's GaussianBlur as the DINO and MoCo recipes apply it, and the colour ops of RandAugment / AutoAugment /
  * TrivialAugment, PIL backend).  A PHOTO CHAIN is 0 to
@@ -860,6 +905,29 @@ int llcomp_mi_codec_decode_photo_warped_views_host(llcomp_mi_codec* codec, const
  * and per view its statistics and table (8 + 1024 * c + 256 * c bytes) and its chain in the staged block (68 bytes, and 16 of alignment
  * per call). */
 uint64_t llcomp_mi_codec_photo_workspace_bytes(const llcomp_mi_codec* codec, uint64_t total_views);
+/* llcomp_mi_codec_decode_warped_views(_host) with views that are projective maps (llcomp_mi_perspective_view /
+ * llcomp_mi_perspective_group / the rule above): the same plan on the views' source rectangles (llcomp_mi_perspective_views_plan), the
+ * same windows, classes, boxes, gather of a host source and ONE copy, and one gather kernel per group of 16 x 16 output pixels of one
+ * view per workgroup, which computes the two quotients per pixel and reads the view straight from its frame's box.  A view's entry is
+ * its eight coefficients (80 bytes with the box's origin); there are no index tables.  d_status, the verdicts, the BAD_ARGS cases (with
+ * llcomp_mi_perspective_views_plan's) and the _host form: as for the warped views.  _photo_: with a photometric chain per view, as
+ * llcomp_mi_codec_decode_photo_warped_views. */
+int llcomp_mi_codec_decode_perspective_views(llcomp_mi_codec* codec, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                             const llcomp_mi_perspective_group* groups, uint32_t n_groups, void* d_status, void* stream);
+int llcomp_mi_codec_decode_perspective_views_host(llcomp_mi_codec* codec, const uint8_t* const* data, const size_t* lens,
+                                                  const llcomp_mi_perspective_group* groups, uint32_t n_groups, void* d_status, void* stream);
+int llcomp_mi_codec_decode_photo_perspective_views(llcomp_mi_codec* codec, const void* d_payload, uint64_t payload_bytes,
+                                                   const void* d_slice_len, const llcomp_mi_perspective_group* groups, uint32_t n_groups,
+                                                   const llcomp_mi_photo_group* photo, void* d_status, void* stream);
+int llcomp_mi_codec_decode_photo_perspective_views_host(llcomp_mi_codec* codec, const uint8_t* const* data, const size_t* lens,
+                                                        const llcomp_mi_perspective_group* groups, uint32_t n_groups,
+                                                        const llcomp_mi_photo_group* photo, void* d_status, void* stream);
+/* The bound on llcomp_mi_codec_allocated_bytes for perspective views calls of up to total_views views with ow <= w, oh <= h:
+ * llcomp_mi_codec_warp_workspace_bytes + 16 * max(total_views, 1), the longer entry.  With chains (the _photo_ calls):
+ * llcomp_mi_codec_photo_workspace_bytes + 16 * max(total_views, 1) -- a form of its own, because taking this bound into
+ * llcomp_mi_codec_photo_workspace_bytes' maximum would raise that function's value for its present callers. */
+uint64_t llcomp_mi_codec_perspective_workspace_bytes(const llcomp_mi_codec* codec, uint64_t total_views);
+uint64_t llcomp_mi_codec_photo_perspective_workspace_bytes(const llcomp_mi_codec* codec, uint64_t total_views);
 /* Stage-A only (context + prediction model), for tests and profiling: d_sym u32[frames*h*w*c],
  * low 16 bits = folded context (0..7925), high 16 bits = folded residual (two's complement). */
 int llcomp_mi_codec_model(llcomp_mi_codec* codec, const void* d_px, void* d_sym, void* stream);

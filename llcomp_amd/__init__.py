@@ -27,6 +27,9 @@ with ctypes and keeps the reference's names and error behaviour:
         Codec.warp_workspace_bytes  (views under an affine map: a view = (frame, m0..m5[, flags]), byte for byte PIL's
         Image.transform(AFFINE) -- Image.rotate, RandomRotation, RandomAffine -- under nearest, bilinear or bicubic; a frame decodes
         the bounding box of the source pixels its views read)
+    PerspectiveGroup / perspective_source_rect / perspective_views_plan / perspective_reference / perspective_coeffs /
+        Codec.decode_perspective_views(_host) / Codec.perspective_workspace_bytes  (views under a projective map: a view =
+        (frame, a0..a7[, flags]), byte for byte PIL's Image.transform(PERSPECTIVE) -- RandomPerspective -- under the same three filters)
     RawImage(pixels, width, height, channels)     <->  llcomp::RawImage         (/root/reference/llcomp.hpp:454-459)
     EXT = ".llcomp"                               <->  llcomp::ext              (/root/reference/llcomp.hpp:18)
 
@@ -43,6 +46,7 @@ from ._lib import Info, Opts, OutputFormat
 from ._lib import Pad as _Pad
 from ._lib import View as _View, ViewGroup as _ViewGroup
 from ._lib import WarpView as _WarpView, WarpGroup as _WarpGroup
+from ._lib import PerspectiveView as _PerspectiveView, PerspectiveGroup as _PerspectiveGroup
 from ._lib import PhotoOp as _PhotoOp, PhotoChain as _PhotoChain, PhotoGroup as _PhotoGroup
 
 EXT = ".llcomp"
@@ -556,33 +560,41 @@ class WarpGroup:
         self.photo = photo  # (a photometric chain for every view, or one per view: ViewGroup)
 
 
-def _matrix(m):
+class PerspectiveGroup(WarpGroup):
+    """Views under a projective map that share one output (llcomp_mi_perspective_group): views = a sequence of (frame, a0, ..., a7) or
+    (frame, a0, ..., a7, flags) -- PIL's PERSPECTIVE data: output pixel (x, y) reads the frame at ((a0 x + a1 y + a2) / (a6 x + a7 y + 1),
+    (a3 x + a4 y + a5) / (a6 x + a7 y + 1)), pixel centres at + 0.5; perspective_coeffs gives them from four point pairs.  Everything
+    else as WarpGroup takes it."""
+
+
+def _matrix(m, n=6):
     a = np.asarray(m, dtype=np.float64).reshape(-1)
-    if a.size != 6:
-        raise LlcompError(BAD_ARGS, f"an affine map takes six numbers, got {a.size}")
-    return (C.c_double * 6)(*a.tolist())
+    if a.size != n:
+        raise LlcompError(BAD_ARGS, f"{'an affine' if n == 6 else 'a perspective'} map takes {n} numbers, got {a.size}")
+    return (C.c_double * n)(*a.tolist())
 
 
-def _warp_groups(groups, c):
+def _warp_groups(groups, c, persp=False):
     """a sequence of WarpGroup (or (views, ow, oh[, d_out]) tuples) -> (ctypes array of llcomp_mi_warp_group, n, keep-alive list);
-    everything about their contents is the library's to refuse"""
+    everything about their contents is the library's to refuse.  persp: PerspectiveGroup -> llcomp_mi_perspective_group, eight numbers."""
     groups = list(groups) if groups is not None else []
-    arr, keep = (_WarpGroup * max(1, len(groups)))(), []
+    Group, CGroup, CView, k = (PerspectiveGroup, _PerspectiveGroup, _PerspectiveView, 8) if persp else (WarpGroup, _WarpGroup, _WarpView, 6)
+    arr, keep = (CGroup * max(1, len(groups)))(), []
     for i, gr in enumerate(groups):
-        if not isinstance(gr, WarpGroup):
+        if not isinstance(gr, Group):
             if not isinstance(gr, (tuple, list)) or not 3 <= len(gr) <= 4:
-                raise LlcompError(BAD_ARGS, f"group {i} must be a WarpGroup or (views, ow, oh, d_out)")
-            gr = WarpGroup(*gr)
+                raise LlcompError(BAD_ARGS, f"group {i} must be a {Group.__name__} or (views, ow, oh, d_out)")
+            gr = Group(*gr)
         rows = [list(v) for v in gr.views]
         n = len(rows)
-        if any(len(r) not in (7, 8) for r in rows):
-            raise LlcompError(BAD_ARGS, f"the views of group {i} must be (frame, m0..m5) or (frame, m0..m5, flags)")
+        if any(len(r) not in (k + 1, k + 2) for r in rows):
+            raise LlcompError(BAD_ARGS, f"the views of group {i} must be (frame, {k} numbers) or (frame, {k} numbers, flags)")
         frames = [int(r[0]) for r in rows]
-        fl = [int(r[7]) if len(r) == 8 else 0 for r in rows]
+        fl = [int(r[k + 1]) if len(r) == k + 2 else 0 for r in rows]
         if any(not 0 <= f <= 0xFFFFFFFF for f in frames) or any(not 0 <= f <= 255 for f in fl):
             raise LlcompError(BAD_ARGS, f"group {i}: a frame index or flags byte out of range")
         fl = _flags_table(fl, n, gr.filter) if n else None
-        views = (_WarpView * max(1, n))(*[_WarpView(frames[j], int(fl[j]), _matrix(rows[j][1:7])) for j in range(n)])
+        views = (CView * max(1, n))(*[CView(frames[j], int(fl[j]), _matrix(rows[j][1:k + 1], k)) for j in range(n)])
         fmt, _, keep_fmt = _output_format(c, **gr.format)
         fill = None
         if gr.fill is not None:
@@ -593,7 +605,7 @@ def _warp_groups(groups, c):
                 raise LlcompError(BAD_ARGS, f"fill takes {c} values in 0..255")
             fill = (C.c_uint8 * c)(*[int(v) for v in f.tolist()])
         keep += [views, keep_fmt, fill]
-        arr[i] = _WarpGroup(C.sizeof(_WarpGroup), n, C.cast(views, C.POINTER(_WarpView)) if n else None, int(gr.ow), int(gr.oh),
+        arr[i] = CGroup(C.sizeof(CGroup), n, C.cast(views, C.POINTER(CView)) if n else None, int(gr.ow), int(gr.oh),
                             C.pointer(fmt) if fmt is not None else None, gr.d_out or None, C.cast(fill, _lib.u8p) if fill is not None else None)
     return arr, len(groups), keep
 
@@ -619,7 +631,52 @@ def warp_views_plan(w, h, c, tile_w, tile_h, planar, frames, groups):
     return uni, win, used.value, k.value
 
 
-def warp_reference(frame, m, filter="nearest", ow=None, oh=None, fill=None):
+def perspective_source_rect(w, h, a, filter, ow, oh):
+    """((x, y, rw, rh), empty) of one view under a projective map (llcomp_mi_perspective_source_rect, host only): a rectangle that
+    contains every pixel of the frame the rule reads for the output pixels inside the frame -- a bound, at most a pixel beyond them on
+    any side; empty = True (and four zeros) exactly when no output pixel is inside.  LlcompError(BAD_ARGS) for the rule's limits."""
+    rect, empty = (C.c_uint32 * 4)(), C.c_uint32()
+    _check(_lib.load().llcomp_mi_perspective_source_rect(w, h, _matrix(a, 8), filter_code(filter), ow, oh, rect, C.byref(empty)))
+    return tuple(rect), bool(empty.value)
+
+
+def perspective_views_plan(w, h, c, tile_w, tile_h, planar, frames, groups):
+    """(unions, windows, n_used, n_classes) of a perspective views decode (llcomp_mi_perspective_views_plan, host only), in the shape of
+    views_plan: a frame's union is the bounding box of its views' source rectangles; a frame whose views are all empty is unused."""
+    arr, n, _keep = _warp_groups(groups, c, persp=True)
+    uni, win = np.zeros((frames, 4), np.uint32), np.zeros((frames, 4), np.uint32)
+    used, k = C.c_uint32(), C.c_uint32()
+    u32p = C.POINTER(C.c_uint32)
+    _check(_lib.load().llcomp_mi_perspective_views_plan(w, h, c, tile_w, tile_h, int(bool(planar)), frames, arr, n, uni.ctypes.data_as(u32p),
+                                                        win.ctypes.data_as(u32p), C.byref(used), C.byref(k)))
+    return uni, win, used.value, k.value
+
+
+def perspective_reference(frame, a, filter="nearest", ow=None, oh=None, fill=None):
+    """The rule of the perspective views on a host image (llcomp_mi_perspective_reference): frame [h, w] or [h, w, c] uint8 ->
+    [oh, ow(, c)], byte for byte PIL's Image.transform((ow, oh), Image.PERSPECTIVE, a, resample, fillcolor=fill) with independent bands.
+    ow / oh default to the frame's size."""
+    return warp_reference(frame, a, filter, ow, oh, fill, _persp=True)
+
+
+def perspective_coeffs(startpoints, endpoints):
+    """The eight numbers of the projective map that sends the output's `endpoints` to the source's `startpoints` (four (x, y) pairs
+    each), as torchvision's RandomPerspective pairs them: the least-squares solution, in binary64, of the 8 x 8 system that
+    torchvision's _get_perspective_coeffs sets up.  It is that system, not necessarily torchvision's last bits (torchvision solves it
+    with its own routine, in its own precision): the byte-for-byte contract of the perspective calls is on the coefficients a caller
+    passes, whatever produced them -- pass torchvision's own to reproduce torchvision."""
+    sp, ep = np.asarray(startpoints, np.float64).reshape(-1, 2), np.asarray(endpoints, np.float64).reshape(-1, 2)
+    if sp.shape != (4, 2) or ep.shape != (4, 2):
+        raise LlcompError(BAD_ARGS, "startpoints and endpoints are four (x, y) pairs each")
+    A = np.zeros((8, 8), np.float64)
+    for i in range(4):
+        (x, y), (u, v) = ep[i], sp[i]
+        A[2 * i] = [x, y, 1, 0, 0, 0, -u * x, -u * y]
+        A[2 * i + 1] = [0, 0, 0, x, y, 1, -v * x, -v * y]
+    return tuple(np.linalg.lstsq(A, sp.reshape(8), rcond=None)[0].tolist())
+
+
+def warp_reference(frame, m, filter="nearest", ow=None, oh=None, fill=None, _persp=False):
     """The rule of the warped views on a host image (llcomp_mi_warp_reference): frame [h, w] or [h, w, c] uint8 -> [oh, ow(, c)], byte
     for byte PIL's Image.transform((ow, oh), Image.AFFINE, m, resample, fillcolor=fill) with independent bands.  ow / oh default to the
     frame's size (Image.rotate's output)."""
@@ -639,8 +696,10 @@ def warp_reference(frame, m, filter="nearest", ow=None, oh=None, fill=None):
             raise LlcompError(BAD_ARGS, f"fill takes {c} values in 0..255")
         fl = np.ascontiguousarray(f, dtype=np.uint8)
     out = np.zeros((oh, ow) + a.shape[2:], np.uint8)
-    _check(_lib.load().llcomp_mi_warp_reference(a.ctypes.data, w, h, c, _matrix(m), filter_code(filter), fl.ctypes.data if fl is not None else None,
-                                                ow, oh, out.ctypes.data))
+    L = _lib.load()
+    rule = L.llcomp_mi_perspective_reference if _persp else L.llcomp_mi_warp_reference
+    _check(rule(a.ctypes.data, w, h, c, _matrix(m, 8 if _persp else 6), filter_code(filter), fl.ctypes.data if fl is not None else None, ow, oh,
+                out.ctypes.data))
     return out
 
 
@@ -1314,10 +1373,10 @@ class Codec:
         else:
             _check(getattr(self._L, name % "")(self._h, *src, arr, n, d_status, stream))
 
-    def _warped(self, host, src, groups, d_status, stream):
-        name = "llcomp_mi_codec_decode_%swarped_views" + ("_host" if host else "")
+    def _warped(self, host, src, groups, d_status, stream, persp=False):
+        name = "llcomp_mi_codec_decode_%s" + ("perspective" if persp else "warped") + "_views" + ("_host" if host else "")
         groups = list(groups) if groups is not None else []
-        arr, n, _keep = _warp_groups(groups, self.c)
+        arr, n, _keep = _warp_groups(groups, self.c, persp)
         if any(getattr(gr, "photo", None) is not None for gr in groups):
             photo, _keep_photo = _photo_groups(groups, [arr[i].n_views for i in range(n)])
             _check(getattr(self._L, name % "photo_")(self._h, *src, arr, n, photo, d_status, stream))
@@ -1373,6 +1432,27 @@ class Codec:
         the container of a frame no view reads may be None and is never read"""
         ptrs, lens, _keep = _frame_containers(containers, self.frames, allow_none=True)
         self._warped(True, (ptrs, lens), groups, d_status, stream)
+
+    def decode_perspective_views(self, d_payload, payload_bytes, d_slice_len, groups, d_status, stream=0):
+        """views under a projective map (llcomp_mi_codec_decode_perspective_views): groups = PerspectiveGroup objects; view v of a group
+        -> d_out[v], byte for byte perspective_reference of its frame (PIL's Image.transform(PERSPECTIVE)), mirrored and formatted as the
+        other calls do.  A frame decodes once, and only a bounding box of the source pixels its views read; a frame without a view is
+        not read.  A group with photo= runs its chains behind the gather (llcomp_mi_codec_decode_photo_perspective_views)."""
+        self._warped(False, (d_payload, payload_bytes, d_slice_len), groups, d_status, stream, persp=True)
+
+    def decode_perspective_views_host(self, containers, groups, d_status, stream=0):
+        """decode_perspective_views of host containers (llcomp_mi_codec_decode_perspective_views_host): only the union windows' bytes
+        cross PCIe; the container of a frame no view reads may be None and is never read"""
+        ptrs, lens, _keep = _frame_containers(containers, self.frames, allow_none=True)
+        self._warped(True, (ptrs, lens), groups, d_status, stream, persp=True)
+
+    def perspective_workspace_bytes(self, total_views, photo=False):
+        """the bound on .allocated_bytes() for perspective views calls of up to total_views views with outputs no larger than the image
+        (llcomp_mi_codec_perspective_workspace_bytes); photo: for calls with photometric chains
+        (llcomp_mi_codec_photo_perspective_workspace_bytes)"""
+        if photo:
+            return self._L.llcomp_mi_codec_photo_perspective_workspace_bytes(self._h, int(total_views))
+        return self._L.llcomp_mi_codec_perspective_workspace_bytes(self._h, int(total_views))
 
     def warp_workspace_bytes(self, total_views):
         """the bound on .allocated_bytes() for warped views calls of up to total_views views with outputs no larger than the image

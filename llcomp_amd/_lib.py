@@ -46,6 +46,10 @@ SYMBOLS = [
     "llcomp_mi_codec_decode_warped_views_host", "llcomp_mi_codec_warp_workspace_bytes",
     "llcomp_mi_photo_reference", "llcomp_mi_codec_decode_photo_views", "llcomp_mi_codec_decode_photo_views_host",
     "llcomp_mi_codec_decode_photo_warped_views", "llcomp_mi_codec_decode_photo_warped_views_host", "llcomp_mi_codec_photo_workspace_bytes",
+    "llcomp_mi_perspective_source_rect", "llcomp_mi_perspective_views_plan", "llcomp_mi_perspective_reference",
+    "llcomp_mi_codec_decode_perspective_views", "llcomp_mi_codec_decode_perspective_views_host",
+    "llcomp_mi_codec_decode_photo_perspective_views", "llcomp_mi_codec_decode_photo_perspective_views_host",
+    "llcomp_mi_codec_perspective_workspace_bytes", "llcomp_mi_codec_photo_perspective_workspace_bytes",
 ]
 
 u8p = C.POINTER(C.c_uint8)
@@ -88,6 +92,17 @@ class WarpGroup(C.Structure):
     """llcomp_mi_warp_group (include/llcomp_mi.h): 48 bytes, views at 8, fmt at 24, d_out at 32, fill at 40"""
     _fields_ = [("struct_size", C.c_uint32), ("n_views", C.c_uint32), ("views", C.POINTER(WarpView)), ("ow", C.c_uint32), ("oh", C.c_uint32),
                 ("fmt", C.POINTER(OutputFormat)), ("d_out", C.c_void_p), ("fill", u8p)]
+
+
+class PerspectiveView(C.Structure):
+    """llcomp_mi_perspective_view (include/llcomp_mi.h): 72 bytes, a at 8"""
+    _fields_ = [("frame", C.c_uint32), ("flags", C.c_uint32), ("a", C.c_double * 8)]
+
+
+class PerspectiveGroup(C.Structure):
+    """llcomp_mi_perspective_group (include/llcomp_mi.h): 48 bytes, llcomp_mi_warp_group's fields around the perspective view"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_views", C.c_uint32), ("views", C.POINTER(PerspectiveView)), ("ow", C.c_uint32),
+                ("oh", C.c_uint32), ("fmt", C.POINTER(OutputFormat)), ("d_out", C.c_void_p), ("fill", u8p)]
 
 
 PHOTO_MAX_OPS = 8
@@ -419,6 +434,30 @@ def load():
         L.llcomp_mi_codec_decode_photo_warped_views_host.argtypes = [C.c_void_p, ptrs, sizes, wgrp, C.c_uint32, pgrp, C.c_void_p, C.c_void_p]
         L.llcomp_mi_codec_photo_workspace_bytes.restype = C.c_uint64
         L.llcomp_mi_codec_photo_workspace_bytes.argtypes = [C.c_void_p, C.c_uint64]
+    if "LLCOMP_MI_LIB" not in os.environ or hasattr(L, "llcomp_mi_perspective_source_rect"):  # views under a projective map
+        u32p, f64p, ptrs, sizes = C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)
+        qgrp, pgrp = C.POINTER(PerspectiveGroup), C.POINTER(PhotoGroup)
+        L.llcomp_mi_perspective_source_rect.restype = C.c_int
+        L.llcomp_mi_perspective_source_rect.argtypes = [C.c_uint32, C.c_uint32, f64p, C.c_uint32, C.c_uint32, C.c_uint32, u32p, u32p]
+        L.llcomp_mi_perspective_views_plan.restype = C.c_int
+        L.llcomp_mi_perspective_views_plan.argtypes = [C.c_uint32] * 7 + [qgrp, C.c_uint32, u32p, u32p, u32p, u32p]
+        L.llcomp_mi_perspective_reference.restype = C.c_int
+        L.llcomp_mi_perspective_reference.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, f64p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                                      C.c_uint32, C.c_void_p]
+        L.llcomp_mi_codec_decode_perspective_views.restype = C.c_int
+        L.llcomp_mi_codec_decode_perspective_views.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, qgrp, C.c_uint32, C.c_void_p,
+                                                               C.c_void_p]
+        L.llcomp_mi_codec_decode_perspective_views_host.restype = C.c_int
+        L.llcomp_mi_codec_decode_perspective_views_host.argtypes = [C.c_void_p, ptrs, sizes, qgrp, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.llcomp_mi_codec_decode_photo_perspective_views.restype = C.c_int
+        L.llcomp_mi_codec_decode_photo_perspective_views.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, qgrp, C.c_uint32, pgrp,
+                                                                     C.c_void_p, C.c_void_p]
+        L.llcomp_mi_codec_decode_photo_perspective_views_host.restype = C.c_int
+        L.llcomp_mi_codec_decode_photo_perspective_views_host.argtypes = [C.c_void_p, ptrs, sizes, qgrp, C.c_uint32, pgrp, C.c_void_p, C.c_void_p]
+        L.llcomp_mi_codec_perspective_workspace_bytes.restype = C.c_uint64
+        L.llcomp_mi_codec_perspective_workspace_bytes.argtypes = [C.c_void_p, C.c_uint64]
+        L.llcomp_mi_codec_photo_perspective_workspace_bytes.restype = C.c_uint64
+        L.llcomp_mi_codec_photo_perspective_workspace_bytes.argtypes = [C.c_void_p, C.c_uint64]
     if "LLCOMP_MI_LIB" not in os.environ and L.llcomp_mi_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.llcomp_mi_abi_version()}, this binding was written for {ABI_VERSION}: rebuild the library")
     _lib = L

@@ -533,6 +533,11 @@ int windows_warp(llcomp_mi_codec* k, const WindowsPlan& p, const WarpTail& tail,
     const int32_t* d_tabs = reinterpret_cast<const int32_t*>(d_block + tail.tabs_at());
     const uint8_t* const d_tables = d_block + tail.tables_at();
     return windows_groups(k, tail.groups, d_tables, photo, d_chains, s, [&](const WarpOut& vg, uint32_t at, uint32_t cnt, uint8_t* dst) -> int {
+        if (!tail.ps.empty()) {  // a perspective call: its own entries, its own gather
+            HIP_TRY(launch_persp(k->d_box, reinterpret_cast<const PerspEntry*>(d_block) + vg.first + at, d_block + tail.fills_at() + vg.fill_at,
+                                 d_tables + vg.table_at, vg.out, dst, cnt, g.c, p.wmax, p.hmax, g.w, g.h, vg.ow, vg.oh, s));
+            return LLCOMP_MI_OK;
+        }
         HIP_TRY(launch_warp(k->d_box, d_ws + vg.first + at, d_tabs, d_block + tail.fills_at() + vg.fill_at, d_tables + vg.table_at, vg.out, dst, cnt, g.c,
                             p.wmax, p.hmax, g.w, g.h, vg.ow, vg.oh, s));
         return LLCOMP_MI_OK;
@@ -1346,15 +1351,25 @@ int views_call(llcomp_mi_codec* k, WindowsSource src, const llcomp_mi_view_group
 // Warped views: the views decode on the views' SOURCE rectangles up to the boxes (warp_plan.hpp: warp_setup -- views_union and
 // regions_setup_sized, unchanged), then the warp tail: one gather launch per group reads every view from its frame's box.  With no
 // used frame (every view all fill) nothing is read.
-int warped_call(llcomp_mi_codec* k, WindowsSource src, const llcomp_mi_warp_group* groups, uint32_t n_groups, const llcomp_mi_photo_group* photo,
-                void* d_status, void* stream) {
+// Perspective groups (llcomp_mi_perspective_group) take the same body: persp_setup stages PerspEntry in the tail, and windows_warp
+// launches the perspective gather for them.
+int warped_setup(const llcomp_mi_codec* k, const llcomp_mi_warp_group* groups, uint32_t n_groups, WarpPlan& p) {
+    return warp_setup(k->g, k->tune, groups, n_groups, p);
+}
+int warped_setup(const llcomp_mi_codec* k, const llcomp_mi_perspective_group* groups, uint32_t n_groups, WarpPlan& p) {
+    return persp_setup(k->g, k->tune, groups, n_groups, p);
+}
+template <class Group>
+int warped_call(llcomp_mi_codec* k, WindowsSource src, const Group* groups, uint32_t n_groups, const llcomp_mi_photo_group* photo, void* d_status,
+                void* stream) {
     if (!source_ok(k, src, d_status)) return LLCOMP_MI_BAD_ARGS;
     WarpPlan p;
-    if (int rc = warp_setup(k->g, k->tune, groups, n_groups, p)) return rc;
+    if (int rc = warped_setup(k, groups, n_groups, p)) return rc;
     PhotoTail pt;
     if (int rc = photo_tail_of(k->g, p.tail.groups, photo, pt)) return rc;
     if (int rc = host_gather(k, src, p, p.u.rects.data(), &p.u.used)) return rc;
-    const uint64_t bound = warp_tables_bound(k->g, p.total_views) + (pt.any() ? photo_tables_bound(p.total_views) : 0);
+    const uint64_t tables = p.tail.ps.empty() ? warp_tables_bound(k->g, p.total_views) : persp_tables_bound(k->g, p.total_views);
+    const uint64_t bound = tables + (pt.any() ? photo_tables_bound(p.total_views) : 0);
     return decode_windows(k, WindowsCall{p, p.tail, pt.any() ? &pt : nullptr, bound, src, nullptr}, d_status, stream);
 }
 
@@ -1448,6 +1463,33 @@ int llcomp_mi_codec_decode_photo_warped_views_host(llcomp_mi_codec* k, const uin
                                                    const llcomp_mi_warp_group* groups, uint32_t n_groups, const llcomp_mi_photo_group* photo,
                                                    void* d_status, void* stream) {
     return warped_call(k, host_source(data, lens), groups, n_groups, photo, d_status, stream);
+}
+
+int llcomp_mi_codec_decode_perspective_views(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                             const llcomp_mi_perspective_group* groups, uint32_t n_groups, void* d_status, void* stream) {
+    return warped_call(k, device_source(d_payload, payload_bytes, d_slice_len), groups, n_groups, nullptr, d_status, stream);
+}
+int llcomp_mi_codec_decode_perspective_views_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens,
+                                                  const llcomp_mi_perspective_group* groups, uint32_t n_groups, void* d_status, void* stream) {
+    return warped_call(k, host_source(data, lens), groups, n_groups, nullptr, d_status, stream);
+}
+int llcomp_mi_codec_decode_photo_perspective_views(llcomp_mi_codec* k, const void* d_payload, uint64_t payload_bytes, const void* d_slice_len,
+                                                   const llcomp_mi_perspective_group* groups, uint32_t n_groups,
+                                                   const llcomp_mi_photo_group* photo, void* d_status, void* stream) {
+    return warped_call(k, device_source(d_payload, payload_bytes, d_slice_len), groups, n_groups, photo, d_status, stream);
+}
+int llcomp_mi_codec_decode_photo_perspective_views_host(llcomp_mi_codec* k, const uint8_t* const* data, const size_t* lens,
+                                                        const llcomp_mi_perspective_group* groups, uint32_t n_groups,
+                                                        const llcomp_mi_photo_group* photo, void* d_status, void* stream) {
+    return warped_call(k, host_source(data, lens), groups, n_groups, photo, d_status, stream);
+}
+uint64_t llcomp_mi_codec_perspective_workspace_bytes(const llcomp_mi_codec* k, uint64_t total_views) {
+    if (!k) return 0;
+    return k->workspace_bytes + persp_tables_bound(k->g, total_views);
+}
+uint64_t llcomp_mi_codec_photo_perspective_workspace_bytes(const llcomp_mi_codec* k, uint64_t total_views) {
+    if (!k) return 0;
+    return llcomp_mi_codec_photo_workspace_bytes(k, total_views) + persp_tables_bound(k->g, total_views) - warp_tables_bound(k->g, total_views);
 }
 
 uint64_t llcomp_mi_codec_photo_workspace_bytes(const llcomp_mi_codec* k, uint64_t total_views) {

@@ -16,5 +16,9 @@ namespace llcomp_mi {
 hipError_t launch_warp(const uint8_t* d_box, const WarpEntry* d_ws, const int32_t* d_tabs, const uint8_t* d_fill, const void* d_table,
                        const OutFormat& o, void* d_out, uint32_t views, uint32_t c, uint32_t bw, uint32_t bh, uint32_t w, uint32_t h, uint32_t ow,
                        uint32_t oh, hipStream_t stream);
+// The same for the views of a perspective call (entries d_ps, no index tables): a kernel of its own, so that the affine instantiations
+// keep their registers.
+hipError_t launch_persp(const uint8_t* d_box, const PerspEntry* d_ps, const uint8_t* d_fill, const void* d_table, const OutFormat& o, void* d_out,
+                        uint32_t views, uint32_t c, uint32_t bw, uint32_t bh, uint32_t w, uint32_t h, uint32_t ow, uint32_t oh, hipStream_t stream);
 
 }  // namespace llcomp_mi

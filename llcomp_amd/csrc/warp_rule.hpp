@@ -2,7 +2,8 @@
 // are compiled into the gather kernel (warp_kernels.hip) and into llcomp_mi_warp_reference and the planner (warp_plan.cpp).  The rule is
 // PIL's Image.transform(AFFINE) in IEEE binary64 with every operation rounded by itself, so nothing here may be contracted into a fused
 // multiply-add: hipcc does that on the device by default, and the pragma below switches it off for every file that includes this header
-// (new files only: the existing sources never include it and are built as they were).
+// (new files only: the existing sources never include it and are built as they were).  The perspective views' coordinate rule
+// (PIL's PERSPECTIVE: two true divisions per pixel) is at the end; from the coordinate on it shares everything above.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -115,5 +116,26 @@ inline void warp_scale_table(double m_scale, double m_off, uint32_t n_out, uint3
     }
 }
 LLMI_HD inline bool warp_is_scale(const double* m) { return m[1] == 0.0 && m[3] == 0.0; }
+
+// Perspective views (include/llcomp_mi.h: "Views under a projective map"): PIL's Image.transform(PERSPECTIVE).  The denominator and
+// the source coordinate of output pixel (x, y) under a[0..7]; the two quotients are true binary64 divisions (whose expansion on the GPU
+// uses fused multiply-adds of its own and is correctly rounded), the sums and products above them are rounded one by one.
+LLMI_HD inline double persp_den(const double* a, uint32_t x, uint32_t y) {
+    const double xs = double(x) + 0.5, ys = double(y) + 0.5;
+    const double g = a[6] * xs, k = a[7] * ys;
+    const double gk = g + k;
+    return gk + 1.0;
+}
+LLMI_HD inline void persp_xy(const double* a, uint32_t x, uint32_t y, double& xin, double& yin) {
+    const double xs = double(x) + 0.5, ys = double(y) + 0.5;
+    const double p = a[0] * xs, q = a[1] * ys, d = a[3] * xs, e = a[4] * ys, g = a[6] * xs, k = a[7] * ys;
+    const double pq = p + q, de = d + e, gk = g + k;
+    const double nx = pq + a[2], ny = de + a[5], den = gk + 1.0;
+    xin = nx / den;
+    yin = ny / den;
+}
+// NEAREST: PIL's COORD(v) = v < 0 ? -1 : (int) v of one coordinate, for an axis of n pixels; what lies at or beyond n is outside either
+// way and is -1 here too, so nothing that does not fit an int32 is ever converted
+LLMI_HD inline int32_t persp_index(double t, uint32_t n) { return t >= 0.0 && t < double(n) ? int32_t(t) : -1; }
 
 }  // namespace llcomp_mi
