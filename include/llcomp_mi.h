@@ -591,6 +591,51 @@ typedef struct llcomp_mi_photo_group {
  * functions as the GPU's kernels and states the rule as llcomp_mi_warp_reference does; it is not fast.  BAD_ARGS, out untouched: a NULL
  * src or out, a side of 0, a NULL ops with n_ops > 0, and the limits above (c other than 1 and 3 also with no op).  Host-only. */
 int llcomp_mi_photo_reference(const uint8_t* src, uint32_t w, uint32_t h, uint32_t c, const llcomp_mi_photo_op* ops, uint32_t n_ops, uint8_t* out);
+/* Batch mixing (llcomp_mi_codec_mix_batch below: torchvision's and timm's RandomErasing, MixUp and CutMix), in place on a dense batch
+ * that a decode call has written: n samples of E = c * oh * ow elements of dtype U8, F16, BF16 or F32 (LLCOMP_MI_DTYPE_*) in layout HWC
+ * [n][oh][ow][c] or CHW [n][c][oh][ow] (LLCOMP_MI_LAYOUT_*), aligned to the element's size and to nothing more.  Sample i has one record
+ * (below); the call has erase_value, c floats (NULL = zeros).  The rule for the element at channel ch, row y, column x of sample i:
+ *   1. Erase, per sample and ahead of the mix, as RandomErasing stands ahead of the collate in the recipes:
+ *        e_i(ch, y, x) = erase_value[ch] converted to the dtype where (x, y) lies in erase_i, the element as it stood before the call
+ *        elsewhere.  The conversion rounds to nearest even for F16 and BF16 (overflow to +-inf); U8 takes integers 0..255 only.
+ *        (torch: img[..., y:y+h, x:x+w] = torch.tensor(value)[:, None, None])
+ *   2. Mix, with p = partner_i:
+ *        p == i:                      e_i
+ *        else (x, y) in box_i:        e_p                                     (CutMix: out[..., y1:y2, x1:x2] = rolled[..., y1:y2, x1:x2])
+ *        else with LLCOMP_MI_MIX_BLEND: rd(rd(e_i * w_own) + rd(e_p * w_partner))  (MixUp)
+ *        else:                        e_i
+ *      Both products and the sum are IEEE binary32 operations on the widened elements, each rounded by itself (no fused multiply-add);
+ *      rd rounds to the dtype, to nearest even, and is the identity for F32.  With w_own = (float)lam and w_partner = (float)(1.0 - lam)
+ *      for a double lam these are the bits of torchvision's inpt.roll(1, 0).mul(1.0 - lam).add_(inpt.mul(lam)) and of timm's
+ *      x.mul_(lam).add_(x.flip(0).mul_(1 - lam)) as torch computes them on the CPU.  BLEND always computes, also for w_own = 1.  A blend
+ *      whose result is a NaN writes the dtype's quiet NaN 0x7FC00000 / 0x7E00 / 0x7FC0, whatever the payloads were.
+ * The partners form a permutation of 0..n-1 (roll: partner_i = (i + n - 1) % n; flip: n - 1 - i), so that the call runs in place.
+ * NOT covered: RandomErasing(value="random"), which is normal noise per pixel; and the labels, which are n numbers the caller mixes
+ * from lam and the boxes. */
+#define LLCOMP_MI_MIX_BLEND 1u
+typedef struct llcomp_mi_mix_sample {
+    uint32_t partner;       /* the sample whose pixels are mixed in; == i: none */
+    uint32_t flags;         /* bit 0 LLCOMP_MI_MIX_BLEND */
+    float w_own, w_partner; /* BLEND's weights */
+    uint32_t box[4];        /* x, y, w, h in output pixels: CutMix's box; w or h 0 = none */
+    uint32_t erase[4];      /* x, y, w, h: RandomErasing's rectangle; w or h 0 = none */
+} llcomp_mi_mix_sample;     /* 48 bytes */
+/* What a call does with n records (DESIGN.md "Batch mixing"): the partner permutation cycle by cycle, every cycle of more than
+ * llcomp_mi_mix_segment() samples cut into segments of at most that many.  order[n]: the samples, each cycle from its smallest sample
+ * along the partners (order[j + 1] = partner of order[j] inside a cycle); seg_first[*n_segments + 1] (room for n + 1): where every
+ * segment begins in order, the last entry n; *n_saved: the segments of the cycles that were cut -- the samples at their heads are copied
+ * aside before anything is written.  order and seg_first may be NULL.  BAD_ARGS, outputs untouched: a NULL samples, n_segments or
+ * n_saved, n = 0 or above 65535, a partner >= n, partners that are no permutation, flag bits above 0, a weight that is not finite.
+ * Host-only. */
+int llcomp_mi_mix_plan(uint32_t n, const llcomp_mi_mix_sample* samples, uint32_t* order, uint32_t* seg_first, uint32_t* n_segments,
+                       uint32_t* n_saved);
+uint32_t llcomp_mi_mix_segment(void);
+/* The rule above on host memory: batch -> out, both n * c * oh * ow elements; out may be batch, and overlaps it in no other way.  It is
+ * compiled from the same functions as the GPU's kernels; it is not fast.  BAD_ARGS, out untouched: a NULL batch, samples or out,
+ * llcomp_mi_mix_plan's cases, a side or c of 0, an unknown dtype or layout, a box or erase rectangle that leaves ow x oh, BLEND on U8,
+ * an erase value that is not finite, a U8 erase value that is no integer from 0 to 255.  Host-only. */
+int llcomp_mi_mix_reference(const void* batch, uint32_t n, uint32_t c, uint32_t ow, uint32_t oh, uint32_t dtype, uint32_t layout,
+                            const llcomp_mi_mix_sample* samples, const float* erase_value, void* out);
 uint32_t llcomp_mi_slice_count(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar);
 /* Slice width for one-row slices (tile_h = 1) when `frames` frames are coded per call: the widest slice (64..480 pixels) that
  * still keeps about four wavefronts per SIMD busy.  A call that codes few frames is latency-bound with wide slices; this
@@ -928,6 +973,20 @@ int llcomp_mi_codec_decode_photo_perspective_views_host(llcomp_mi_codec* codec, 
  * llcomp_mi_codec_photo_workspace_bytes' maximum would raise that function's value for its present callers. */
 uint64_t llcomp_mi_codec_perspective_workspace_bytes(const llcomp_mi_codec* codec, uint64_t total_views);
 uint64_t llcomp_mi_codec_photo_perspective_workspace_bytes(const llcomp_mi_codec* codec, uint64_t total_views);
+/* Batch mixing (the rule: "Batch mixing" above) in place on d_batch, n samples of the codec's c channels and ow x oh pixels in device
+ * memory, asynchronously on `stream` -- behind the decode call that wrote the batch when that ran on the same stream.  One read and one
+ * write per element at most: a sample that is its own partner writes its erase rectangle and nothing else, an element that keeps its
+ * value is not written.  samples (n records) and erase_value (c floats or NULL) are HOST memory, read during the call only: they travel
+ * with the plan in ONE copy from the codec's pinned ring into a device buffer of this call's own.  The heads of the segments of cut cycles
+ * (llcomp_mi_mix_plan) are copied into a buffer of the codec's first.  BAD_ARGS, nothing queued: a NULL codec, d_batch or samples, a
+ * d_batch that is not aligned to the element, and llcomp_mi_mix_reference's cases. */
+int llcomp_mi_codec_mix_batch(llcomp_mi_codec* codec, void* d_batch, uint32_t n, uint32_t ow, uint32_t oh, uint32_t dtype, uint32_t layout,
+                              const llcomp_mi_mix_sample* samples, const float* erase_value, void* stream);
+/* The bound on llcomp_mi_codec_allocated_bytes with such calls of up to n samples of ow x oh among the codec's calls:
+ * llcomp_mi_codec_workspace_bytes, the table (68 bytes per sample and 4 * c per call) and the saved heads: for n above
+ * llcomp_mi_mix_segment(), 2 * n / (llcomp_mi_mix_segment() + 1) slots, each c * oh * ow elements rounded up to 16 bytes and 16 more.
+ * 0 for a NULL codec or an unknown dtype. */
+uint64_t llcomp_mi_codec_mix_workspace_bytes(const llcomp_mi_codec* codec, uint32_t n, uint32_t ow, uint32_t oh, uint32_t dtype);
 /* Stage-A only (context + prediction model), for tests and profiling: d_sym u32[frames*h*w*c],
  * low 16 bits = folded context (0..7925), high 16 bits = folded residual (two's complement). */
 int llcomp_mi_codec_model(llcomp_mi_codec* codec, const void* d_px, void* d_sym, void* stream);

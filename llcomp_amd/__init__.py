@@ -30,6 +30,8 @@ with ctypes and keeps the reference's names and error behaviour:
     PerspectiveGroup / perspective_source_rect / perspective_views_plan / perspective_reference / perspective_coeffs /
         Codec.decode_perspective_views(_host) / Codec.perspective_workspace_bytes  (views under a projective map: a view =
         (frame, a0..a7[, flags]), byte for byte PIL's Image.transform(PERSPECTIVE) -- RandomPerspective -- under the same three filters)
+    mix_samples / mix_plan / mix_reference / Codec.mix_batch / Codec.mix_workspace_bytes  (RandomErasing, MixUp and CutMix in place on
+        the float batch a decode call wrote, bit for bit torch's expressions on the CPU)
     RawImage(pixels, width, height, channels)     <->  llcomp::RawImage         (/root/reference/llcomp.hpp:454-459)
     EXT = ".llcomp"                               <->  llcomp::ext              (/root/reference/llcomp.hpp:18)
 
@@ -48,6 +50,7 @@ from ._lib import View as _View, ViewGroup as _ViewGroup
 from ._lib import WarpView as _WarpView, WarpGroup as _WarpGroup
 from ._lib import PerspectiveView as _PerspectiveView, PerspectiveGroup as _PerspectiveGroup
 from ._lib import PhotoOp as _PhotoOp, PhotoChain as _PhotoChain, PhotoGroup as _PhotoGroup
+from ._lib import MixSample as _MixSample
 
 EXT = ".llcomp"
 FORMAT_LEGACY, FORMAT_SLICED = 0, 1
@@ -497,6 +500,127 @@ def photo_reference(frame, ops):
     arr = (_PhotoOp * max(1, len(raw)))(*[_PhotoOp(op, p) for op, p in raw])
     out = np.zeros_like(a)
     _check(_lib.load().llcomp_mi_photo_reference(a.ctypes.data, w, h, c, arr, len(raw), out.ctypes.data))
+    return out
+
+
+MIX_BLEND = 1
+
+
+def _layout_code(layout):
+    lay = {"hwc": LAYOUT_HWC, "chw": LAYOUT_CHW}.get(str(layout).lower()) if not isinstance(layout, int) else layout
+    if lay is None:
+        raise LlcompError(BAD_ARGS, f"layout must be 'hwc' or 'chw', got {layout!r}")
+    return lay
+
+
+def _mix_rects(r, n, what):
+    """None / one (x, y, w, h) for every sample / n of them, each (x, y, w, h) or None -> n tuples"""
+    if r is None:
+        return [(0, 0, 0, 0)] * n
+    r = list(r)
+    if len(r) == 4 and all(isinstance(v, (int, np.integer)) for v in r):
+        r = [r] * n
+    if len(r) != n:
+        raise LlcompError(BAD_ARGS, f"{what} must be one (x, y, w, h) or {n} of them, got {len(r)}")
+    out = []
+    for q in r:
+        q = (0, 0, 0, 0) if q is None else tuple(int(v) for v in q)
+        if len(q) != 4 or min(q) < 0 or max(q) > 0xFFFFFFFF:
+            raise LlcompError(BAD_ARGS, f"{what}: a rectangle is (x, y, w, h) of unsigned values, got {q!r}")
+        out.append(q)
+    return out
+
+
+def mix_samples(n, partner=None, lam=None, boxes=None, erase=None):
+    """The records of a mix_batch call (llcomp_mi_mix_sample), n of them as a ctypes array.  partner: None (every sample by itself),
+    "roll" (torchvision's inpt.roll(1, 0): sample i mixes with i - 1), "flip" (timm's x.flip(0): with n - 1 - i) or n indices, a
+    permutation.  lam: None, one value or n of them (None: that sample does not blend): MixUp's weight of the sample itself -- the
+    record takes w_own = float32(lam) and w_partner = float32(1.0 - lam), lam a double, which is what torch's mul(lam) and
+    mul(1.0 - lam) compute with.  boxes: CutMix's box, None, one (x, y, w, h) or n of them (None: none).  erase: RandomErasing's
+    rectangle, the same way.  The library checks the records."""
+    n = int(n)
+    if n <= 0:
+        raise LlcompError(BAD_ARGS, f"n must be positive, got {n}")
+    if partner is None:
+        part = list(range(n))
+    elif isinstance(partner, str):
+        if partner not in ("roll", "flip"):
+            raise LlcompError(BAD_ARGS, f"partner must be None, 'roll', 'flip' or {n} indices, got {partner!r}")
+        part = [(i + n - 1) % n for i in range(n)] if partner == "roll" else [n - 1 - i for i in range(n)]
+    else:
+        part = [int(v) for v in partner]
+        if len(part) != n or min(part) < 0 or max(part) > 0xFFFFFFFF:
+            raise LlcompError(BAD_ARGS, f"partner must be {n} indices, got {len(part)}")
+    if lam is None or isinstance(lam, (int, float, np.integer, np.floating)):
+        lams = [lam] * n
+    else:
+        lams = list(lam)
+        if len(lams) != n:
+            raise LlcompError(BAD_ARGS, f"lam must be one value or {n} of them, got {len(lams)}")
+    bx, er = _mix_rects(boxes, n, "boxes"), _mix_rects(erase, n, "erase")
+    arr = (_MixSample * n)()
+    for i in range(n):
+        s = arr[i]
+        s.partner = part[i]
+        if lams[i] is not None:
+            lam_i = float(lams[i])
+            s.flags = MIX_BLEND
+            s.w_own, s.w_partner = float(np.float32(lam_i)), float(np.float32(1.0 - lam_i))
+        s.box[:] = bx[i]
+        s.erase[:] = er[i]
+    return arr
+
+
+def _mix_records(samples, n=None):
+    if not isinstance(samples, C.Array) or samples._type_ is not _MixSample:
+        raise LlcompError(BAD_ARGS, "samples must come from mix_samples()")
+    if n is not None and len(samples) != int(n):
+        raise LlcompError(BAD_ARGS, f"{n} samples take {n} records, got {len(samples)}")
+    return samples
+
+
+def mix_segment():
+    """the samples one thread of the mixing kernel walks: a longer cycle of partners is cut (llcomp_mi_mix_segment)"""
+    return int(_lib.load().llcomp_mi_mix_segment())
+
+
+def mix_plan(samples):
+    """What a mix_batch call does with these records (llcomp_mi_mix_plan, host only) -> (order, seg_first, n_saved): the samples cycle
+    by cycle along their partners, where every segment begins in that order (one more entry: n), and how many segment heads are saved
+    first.  LlcompError(BAD_ARGS) for records the calls refuse by themselves."""
+    samples = _mix_records(samples)
+    n = len(samples)
+    order, seg = np.zeros(n, np.uint32), np.zeros(n + 1, np.uint32)
+    ns, nv = C.c_uint32(0), C.c_uint32(0)
+    u32p = C.POINTER(C.c_uint32)
+    _check(_lib.load().llcomp_mi_mix_plan(n, samples, order.ctypes.data_as(u32p), seg.ctypes.data_as(u32p), C.byref(ns), C.byref(nv)))
+    return order, seg[:ns.value + 1].copy(), int(nv.value)
+
+
+def _mix_erase_value(erase_value, c):
+    if erase_value is None:
+        return None
+    a = np.asarray(erase_value, dtype=np.float32).reshape(-1)
+    if a.size == 1:
+        a = np.full(c, a[0], np.float32)
+    if a.size != c:
+        raise LlcompError(BAD_ARGS, f"erase_value takes {c} values, got {a.size}")
+    return (C.c_float * c)(*a.tolist())
+
+
+def mix_reference(batch, samples, layout="chw", erase_value=None, dtype=None):
+    """The rule of the batch mixing on a host array (llcomp_mi_mix_reference): batch [n, c, oh, ow] (layout "chw") or [n, oh, ow, c]
+    ("hwc") of uint8, float32, float16, or uint16 holding bfloat16 bits with dtype="bfloat16" -> the mixed batch, a new array."""
+    a = np.ascontiguousarray(batch)
+    code = _dtype_code(a.dtype if dtype is None else dtype)
+    if a.ndim != 4 or not a.size or a.dtype != _NP_OF_DTYPE[code]:
+        raise LlcompError(BAD_ARGS, f"a batch is 4-D {_NP_OF_DTYPE[code].__name__}, got {a.dtype} of shape {a.shape}")
+    lay = _layout_code(layout)
+    n = a.shape[0]
+    c, oh, ow = a.shape[1:] if lay == LAYOUT_CHW else (a.shape[3], a.shape[1], a.shape[2])
+    ev = _mix_erase_value(erase_value, c)
+    out = np.empty_like(a)
+    _check(_lib.load().llcomp_mi_mix_reference(a.ctypes.data, n, c, ow, oh, code, lay, _mix_records(samples, n), ev, out.ctypes.data))
     return out
 
 
@@ -1463,6 +1587,18 @@ class Codec:
         """the bound on .allocated_bytes() for views and warped views calls with photometric chains (a group with photo=) of up to
         total_views views with outputs no larger than the image (llcomp_mi_codec_photo_workspace_bytes)"""
         return self._L.llcomp_mi_codec_photo_workspace_bytes(self._h, int(total_views))
+
+    def mix_batch(self, d_batch, n, ow, oh, samples, dtype="float32", layout="chw", erase_value=None, stream=0):
+        """RandomErasing, MixUp and CutMix in place on a dense batch in device memory (llcomp_mi_codec_mix_batch): n samples of the
+        codec's channels and ow x oh pixels in the dtype and layout a decode call wrote them in; samples from mix_samples(); erase_value:
+        one value or one per channel (default zeros).  Asynchronous on `stream`; samples and erase_value are read during the call."""
+        ev = _mix_erase_value(erase_value, self.c)
+        _check(self._L.llcomp_mi_codec_mix_batch(self._h, d_batch, int(n), int(ow), int(oh), _dtype_code(dtype), _layout_code(layout),
+                                                 _mix_records(samples, n), ev, stream))
+
+    def mix_workspace_bytes(self, n, ow, oh, dtype="float32"):
+        """the bound on .allocated_bytes() with mix_batch calls of up to n samples of ow x oh (llcomp_mi_codec_mix_workspace_bytes)"""
+        return self._L.llcomp_mi_codec_mix_workspace_bytes(self._h, int(n), int(ow), int(oh), _dtype_code(dtype))
 
     def views_workspace_bytes(self, total_views):
         """.workspace_bytes for calls of up to total_views views (llcomp_mi_codec_views_workspace_bytes): the staged tables grow with them"""

@@ -50,6 +50,8 @@ SYMBOLS = [
     "llcomp_mi_codec_decode_perspective_views", "llcomp_mi_codec_decode_perspective_views_host",
     "llcomp_mi_codec_decode_photo_perspective_views", "llcomp_mi_codec_decode_photo_perspective_views_host",
     "llcomp_mi_codec_perspective_workspace_bytes", "llcomp_mi_codec_photo_perspective_workspace_bytes",
+    "llcomp_mi_mix_plan", "llcomp_mi_mix_segment", "llcomp_mi_mix_reference", "llcomp_mi_codec_mix_batch",
+    "llcomp_mi_codec_mix_workspace_bytes",
 ]
 
 u8p = C.POINTER(C.c_uint8)
@@ -121,6 +123,12 @@ class PhotoChain(C.Structure):
 class PhotoGroup(C.Structure):
     """llcomp_mi_photo_group (include/llcomp_mi.h): 16 bytes, chains at 8"""
     _fields_ = [("struct_size", C.c_uint32), ("chains", C.POINTER(PhotoChain))]
+
+
+class MixSample(C.Structure):
+    """llcomp_mi_mix_sample (include/llcomp_mi.h): 48 bytes"""
+    _fields_ = [("partner", C.c_uint32), ("flags", C.c_uint32), ("w_own", C.c_float), ("w_partner", C.c_float), ("box", C.c_uint32 * 4),
+                ("erase", C.c_uint32 * 4)]
 
 
 class Info(C.Structure):
@@ -458,6 +466,18 @@ def load():
         L.llcomp_mi_codec_perspective_workspace_bytes.argtypes = [C.c_void_p, C.c_uint64]
         L.llcomp_mi_codec_photo_perspective_workspace_bytes.restype = C.c_uint64
         L.llcomp_mi_codec_photo_perspective_workspace_bytes.argtypes = [C.c_void_p, C.c_uint64]
+    if "LLCOMP_MI_LIB" not in os.environ or hasattr(L, "llcomp_mi_mix_plan"):  # batch mixing
+        u32p, recs, f32p = C.POINTER(C.c_uint32), C.POINTER(MixSample), C.POINTER(C.c_float)
+        L.llcomp_mi_mix_plan.restype = C.c_int
+        L.llcomp_mi_mix_plan.argtypes = [C.c_uint32, recs, u32p, u32p, u32p, u32p]
+        L.llcomp_mi_mix_segment.restype = C.c_uint32
+        L.llcomp_mi_mix_segment.argtypes = []
+        L.llcomp_mi_mix_reference.restype = C.c_int
+        L.llcomp_mi_mix_reference.argtypes = [C.c_void_p] + [C.c_uint32] * 6 + [recs, f32p, C.c_void_p]
+        L.llcomp_mi_codec_mix_batch.restype = C.c_int
+        L.llcomp_mi_codec_mix_batch.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 5 + [recs, f32p, C.c_void_p]
+        L.llcomp_mi_codec_mix_workspace_bytes.restype = C.c_uint64
+        L.llcomp_mi_codec_mix_workspace_bytes.argtypes = [C.c_void_p] + [C.c_uint32] * 4
     if "LLCOMP_MI_LIB" not in os.environ and L.llcomp_mi_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.llcomp_mi_abi_version()}, this binding was written for {ABI_VERSION}: rebuild the library")
     _lib = L

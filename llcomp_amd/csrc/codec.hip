@@ -16,6 +16,7 @@
 #include "container.hpp"
 #include "geometry.hpp"
 #include "kernels.hpp"
+#include "mix.hpp"
 #include "photo.hpp"
 #include "resize.hpp"
 #include "snapshot.hpp"
@@ -832,6 +833,8 @@ void codec_release(llcomp_mi_codec* k) {
     dev_free(k->d_mid, k->done);
     dev_free(k->d_photo, k->done);
     dev_free(k->d_photo_tab, k->done);
+    dev_free(k->d_mix_tab, k->done);
+    dev_free(k->d_mix, k->done);
     dev_free(k->d_upd_goff, k->done);
     for (uint32_t i = 0; i < llcomp_mi_codec::kRegionsRing; ++i) {
         if (!k->h_regions[i]) continue;
@@ -1490,6 +1493,47 @@ uint64_t llcomp_mi_codec_perspective_workspace_bytes(const llcomp_mi_codec* k, u
 uint64_t llcomp_mi_codec_photo_perspective_workspace_bytes(const llcomp_mi_codec* k, uint64_t total_views) {
     if (!k) return 0;
     return llcomp_mi_codec_photo_workspace_bytes(k, total_views) + persp_tables_bound(k->g, total_views) - warp_tables_bound(k->g, total_views);
+}
+
+// Batch mixing (DESIGN.md "Batch mixing"): every refusal first (mix_check_call), then the plan, the table through a slot of the pinned
+// ring into d_mix_tab in one copy, the heads of the segments of cut cycles into d_mix (k_mix_save), and k_mix, all on the caller's stream.
+int llcomp_mi_codec_mix_batch(llcomp_mi_codec* k, void* d_batch, uint32_t n, uint32_t ow, uint32_t oh, uint32_t dtype, uint32_t layout,
+                              const llcomp_mi_mix_sample* samples, const float* erase_value, void* stream) {
+    if (!k || !d_batch || !samples) return LLCOMP_MI_BAD_ARGS;
+    const uint32_t c = k->g.c;
+    std::vector<uint32_t> erase_bits;
+    if (int rc = mix_check_call(n, c, ow, oh, dtype, layout, samples, erase_value, erase_bits)) return rc;
+    const uint32_t esize = dtype == LLCOMP_MI_DTYPE_U8 ? 1u : dtype == LLCOMP_MI_DTYPE_F32 ? 4u : 2u;
+    if (misaligned(d_batch, esize)) return LLCOMP_MI_BAD_ARGS;
+    MixPlan p;
+    mix_plan(n, samples, p);
+    const MixTable t(n, p.segs.size(), c);
+    const uint64_t saved_bytes = p.n_saved * mix_slot_stride(uint64_t(c) * ow * oh * esize);
+    DeviceGuard guard(k->device);
+    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
+    if (int rc = ensure_regions_ring(k)) return rc;
+    if (int rc = ensure_grown(k, k->d_mix_tab, k->mix_tab_cap, t.bytes, mix_table_bound(n, c))) return rc;
+    if (saved_bytes)
+        if (int rc = ensure_grown(k, k->d_mix, k->mix_cap, saved_bytes, saved_bytes)) return rc;
+    uint32_t slot = 0;
+    if (int rc = regions_slot_take(k, t.bytes, mix_table_bound(n, c), slot)) return rc;
+    mix_table_put(n, samples, p, erase_bits, k->h_regions[slot]);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DoneGuard done_guard{k, s};
+    HIP_TRY(hipMemcpyAsync(k->d_mix_tab, k->h_regions[slot], t.bytes, hipMemcpyHostToDevice, s));
+    if (int rc = regions_slot_queued(k, slot, s)) return rc;
+    MixLaunch m{};
+    m.d_batch = static_cast<uint8_t*>(d_batch), m.d_saved = saved_bytes ? k->d_mix : nullptr, m.d_table = k->d_mix_tab;
+    m.n = n, m.c = c, m.ow = ow, m.oh = oh, m.dtype = dtype, m.layout = layout;
+    m.n_segments = uint32_t(p.segs.size()), m.n_saved = p.n_saved;
+    HIP_TRY(launch_mix(m, s));
+    return LLCOMP_MI_OK;
+}
+
+uint64_t llcomp_mi_codec_mix_workspace_bytes(const llcomp_mi_codec* k, uint32_t n, uint32_t ow, uint32_t oh, uint32_t dtype) {
+    const uint64_t esize = dtype == LLCOMP_MI_DTYPE_U8 ? 1u : dtype == LLCOMP_MI_DTYPE_F32 ? 4u : (dtype == LLCOMP_MI_DTYPE_F16 || dtype == LLCOMP_MI_DTYPE_BF16) ? 2u : 0u;
+    if (!k || !esize) return 0;
+    return k->workspace_bytes + mix_table_bound(n, k->g.c) + mix_saved_bound(n) * mix_slot_stride(uint64_t(k->g.c) * ow * oh * esize);
 }
 
 uint64_t llcomp_mi_codec_photo_workspace_bytes(const llcomp_mi_codec* k, uint64_t total_views) {

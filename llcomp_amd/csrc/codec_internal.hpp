@@ -63,6 +63,13 @@ struct llcomp_mi_codec {
     uint64_t photo_cap = 0;
     uint8_t* d_photo_tab = nullptr;
     uint64_t photo_tab_cap = 0;
+    // batch mixing (llcomp_mi_codec_mix_batch): where a call's one copy lands -- the records, the order, the segments and the erase values
+    // (mix_plan.hpp: MixTable) -- and the saved heads of the segments of cut cycles, one slot of mix_slot_stride bytes each; both grown
+    // by the calls that need more
+    uint8_t* d_mix_tab = nullptr;
+    uint64_t mix_tab_cap = 0;
+    uint8_t* d_mix = nullptr;
+    uint64_t mix_cap = 0;
     // region update (llcomp_mi_codec_encode_region / _update_region): the encoder runs on the box's sub-geometry, which can have MORE lane
     // groups than the full one, so its group offsets go to an array of their own, u64[n_slices + 1]; behind it, u64[lane groups + 1], the
     // full geometry's group offsets for the NEW table (d_group_off holds the old table's).  The decoded box shares d_box with the resized
