@@ -636,6 +636,36 @@ uint32_t llcomp_mi_mix_segment(void);
  * an erase value that is not finite, a U8 erase value that is no integer from 0 to 255.  Host-only. */
 int llcomp_mi_mix_reference(const void* batch, uint32_t n, uint32_t c, uint32_t ow, uint32_t oh, uint32_t dtype, uint32_t layout,
                             const llcomp_mi_mix_sample* samples, const float* erase_value, void* out);
+/* Batch orientation (llcomp_mi_codec_orient_batch below: RandomVerticalFlip, RandomHorizontalFlip on the finished batch, PIL's
+ * Image.transpose, np.rot90), in place on a dense batch as the batch mixing takes it: n samples of c * oh * ow elements of dtype U8, F16,
+ * BF16 or F32 in layout HWC [n][oh][ow][c] or CHW [n][c][oh][ow], aligned to the element's size and to nothing more.  Sample i has one
+ * code, codes[i]: 0 for none, otherwise PIL's Image.Transpose value plus 1.  The rule for the pixel at row y, column x of sample i, all
+ * c channels of a pixel alike:  out(x, y) = in(sx, sy)  with
+ *   code  name              PIL method  (sx, sy)
+ *   0     NONE              -           (x, y)
+ *   1     FLIP_LEFT_RIGHT   0           (ow-1-x, y)
+ *   2     FLIP_TOP_BOTTOM   1           (x, oh-1-y)
+ *   3     ROTATE_90         2           (ow-1-y, x)          counter-clockwise, np.rot90(a, 1)
+ *   4     ROTATE_180        3           (ow-1-x, oh-1-y)
+ *   5     ROTATE_270        4           (y, oh-1-x)          np.rot90(a, 3)
+ *   6     TRANSPOSE         5           (y, x)
+ *   7     TRANSVERSE        6           (ow-1-y, oh-1-x)
+ * Codes 3, 5, 6 and 7 would change the shape of a sample that is not square; the batch stays dense and the call runs in place, so they
+ * take ow == oh only.  Elements are moved, never interpreted: NaN payloads, negative zeros and every other bit pattern survive, and only
+ * the element's size tells the dtypes apart.  In CHW every plane of a sample is oriented alike; in HWC a pixel's c elements travel
+ * together.
+ * NOT covered: the transposing codes on outputs that are not square, and an out-of-place form (batch -> another buffer). */
+enum {
+    LLCOMP_MI_ORIENT_NONE = 0, LLCOMP_MI_ORIENT_FLIP_LEFT_RIGHT = 1, LLCOMP_MI_ORIENT_FLIP_TOP_BOTTOM = 2, LLCOMP_MI_ORIENT_ROTATE_90 = 3,
+    LLCOMP_MI_ORIENT_ROTATE_180 = 4, LLCOMP_MI_ORIENT_ROTATE_270 = 5, LLCOMP_MI_ORIENT_TRANSPOSE = 6, LLCOMP_MI_ORIENT_TRANSVERSE = 7
+};
+/* The rule above on host memory: batch -> out, both n * c * oh * ow elements; out may be batch, and overlaps it in no other way.  It is
+ * compiled from the same functions as the GPU's kernel; it is not fast.  BAD_ARGS, out untouched: a NULL batch, codes or out, n = 0 or
+ * above 65535, a side or c of 0, an unknown dtype or layout, a code above 7, a transposing code (3, 5, 6, 7) with ow != oh.  Host-only. */
+int llcomp_mi_orient_reference(const void* batch, uint32_t n, uint32_t c, uint32_t ow, uint32_t oh, uint32_t dtype, uint32_t layout,
+                               const uint8_t* codes, void* out);
+/* The side, in pixels, of the tile of llcomp_mi_codec_orient_batch's kernel (DESIGN.md "Batch orientation"): a constant */
+uint32_t llcomp_mi_orient_tile(void);
 uint32_t llcomp_mi_slice_count(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar);
 /* Slice width for one-row slices (tile_h = 1) when `frames` frames are coded per call: the widest slice (64..480 pixels) that
  * still keeps about four wavefronts per SIMD busy.  A call that codes few frames is latency-bound with wide slices; this
@@ -987,6 +1017,20 @@ int llcomp_mi_codec_mix_batch(llcomp_mi_codec* codec, void* d_batch, uint32_t n,
  * llcomp_mi_mix_segment(), 2 * n / (llcomp_mi_mix_segment() + 1) slots, each c * oh * ow elements rounded up to 16 bytes and 16 more.
  * 0 for a NULL codec or an unknown dtype. */
 uint64_t llcomp_mi_codec_mix_workspace_bytes(const llcomp_mi_codec* codec, uint32_t n, uint32_t ow, uint32_t oh, uint32_t dtype);
+/* Batch orientation (the rule: "Batch orientation" above) in place on d_batch, n samples of the codec's c channels and ow x oh pixels
+ * in device memory, asynchronously on `stream` -- behind the decode call that wrote the batch when that ran on the same stream, and
+ * ahead of llcomp_mi_codec_mix_batch.  No scratch in device memory: a workgroup reads the orbits of its pixels into LDS and writes
+ * them back, so every element of an oriented sample is read once and written once at most; an element that is its own image is not
+ * touched (the middle column of a mirror of odd width, the centre of an odd square) or, on the diagonal of a transposition, written
+ * with the value it held; a sample with code 0 costs no workgroup.  codes (n bytes) is HOST memory, read during the call only: the oriented samples and their codes travel in ONE copy from
+ * the codec's pinned ring into a device buffer of this call's own.  A call whose codes are all 0 queues nothing.  BAD_ARGS, nothing
+ * queued: a NULL codec, d_batch or codes, a d_batch that is not aligned to the element, and llcomp_mi_orient_reference's cases. */
+int llcomp_mi_codec_orient_batch(llcomp_mi_codec* codec, void* d_batch, uint32_t n, uint32_t ow, uint32_t oh, uint32_t dtype,
+                                 uint32_t layout, const uint8_t* codes, void* stream);
+/* The bound on llcomp_mi_codec_allocated_bytes with such calls of up to n samples among the codec's calls:
+ * llcomp_mi_codec_workspace_bytes + 8 * n, the table of a call that orients every sample (8 bytes per oriented sample).  0 for a NULL
+ * codec. */
+uint64_t llcomp_mi_codec_orient_workspace_bytes(const llcomp_mi_codec* codec, uint32_t n);
 /* Stage-A only (context + prediction model), for tests and profiling: d_sym u32[frames*h*w*c],
  * low 16 bits = folded context (0..7925), high 16 bits = folded residual (two's complement). */
 int llcomp_mi_codec_model(llcomp_mi_codec* codec, const void* d_px, void* d_sym, void* stream);

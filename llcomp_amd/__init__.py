@@ -32,6 +32,8 @@ with ctypes and keeps the reference's names and error behaviour:
         (frame, a0..a7[, flags]), byte for byte PIL's Image.transform(PERSPECTIVE) -- RandomPerspective -- under the same three filters)
     mix_samples / mix_plan / mix_reference / Codec.mix_batch / Codec.mix_workspace_bytes  (RandomErasing, MixUp and CutMix in place on
         the float batch a decode call wrote, bit for bit torch's expressions on the CPU)
+    ORIENT_* / orient_code / orient_reference / Codec.orient_batch / Codec.orient_workspace_bytes  (a flip, quarter turn or transposition
+        per sample, in place on the batch a decode call wrote: RandomVerticalFlip, PIL's Image.transpose, np.rot90)
     RawImage(pixels, width, height, channels)     <->  llcomp::RawImage         (/root/reference/llcomp.hpp:454-459)
     EXT = ".llcomp"                               <->  llcomp::ext              (/root/reference/llcomp.hpp:18)
 
@@ -621,6 +623,60 @@ def mix_reference(batch, samples, layout="chw", erase_value=None, dtype=None):
     ev = _mix_erase_value(erase_value, c)
     out = np.empty_like(a)
     _check(_lib.load().llcomp_mi_mix_reference(a.ctypes.data, n, c, ow, oh, code, lay, _mix_records(samples, n), ev, out.ctypes.data))
+    return out
+
+
+# the orientations of Codec.orient_batch (LLCOMP_MI_ORIENT_*): 0 for none, otherwise PIL's Image.Transpose value plus 1
+(ORIENT_NONE, ORIENT_FLIP_LEFT_RIGHT, ORIENT_FLIP_TOP_BOTTOM, ORIENT_ROTATE_90, ORIENT_ROTATE_180, ORIENT_ROTATE_270, ORIENT_TRANSPOSE,
+ ORIENT_TRANSVERSE) = range(8)
+ORIENT_NAMES = ("none", "flip_left_right", "flip_top_bottom", "rotate_90", "rotate_180", "rotate_270", "transpose", "transverse")
+
+
+def orient_code(orientation):
+    """ORIENT_* of a code (0..7), of None, or of a name in any letter case: "none" or PIL's Image.Transpose names ("FLIP_LEFT_RIGHT",
+    "FLIP_TOP_BOTTOM", "ROTATE_90", "ROTATE_180", "ROTATE_270", "TRANSPOSE", "TRANSVERSE"); BAD_ARGS for anything else"""
+    if orientation is None:
+        return ORIENT_NONE
+    if isinstance(orientation, str) and orientation.lower() in ORIENT_NAMES:
+        return ORIENT_NAMES.index(orientation.lower())
+    if isinstance(orientation, (int, np.integer)) and not isinstance(orientation, bool) and 0 <= int(orientation) < len(ORIENT_NAMES):
+        return int(orientation)
+    raise LlcompError(BAD_ARGS, f"an orientation is None, one of {ORIENT_NAMES} or its code 0..{len(ORIENT_NAMES) - 1}, got {orientation!r}")
+
+
+def _orient_codes(codes, n):
+    """n orientations (codes, names or None), or one for every sample -> a ctypes u8 array; a code the library would refuse (above 7)
+    is passed on for it to refuse"""
+    per_sample = [codes] * n if codes is None or isinstance(codes, (str, int, np.integer)) else list(codes)
+    if len(per_sample) != n:
+        raise LlcompError(BAD_ARGS, f"{n} samples take {n} orientations, got {len(per_sample)}")
+    vals = []
+    for v in per_sample:
+        if isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 0 <= int(v) <= 255:
+            vals.append(int(v))
+        else:
+            vals.append(orient_code(v))
+    return (C.c_uint8 * max(1, n))(*vals)
+
+
+def orient_tile():
+    """the side, in pixels, of the orientation kernel's tile (llcomp_mi_orient_tile)"""
+    return int(_lib.load().llcomp_mi_orient_tile())
+
+
+def orient_reference(batch, codes, layout="chw", dtype=None):
+    """The rule of the batch orientation on a host array (llcomp_mi_orient_reference): batch [n, c, oh, ow] (layout "chw") or
+    [n, oh, ow, c] ("hwc") of uint8, float32, float16, or uint16 holding bfloat16 bits with dtype="bfloat16"; codes: n orientations
+    (orient_code) or one for every sample -> the oriented batch, a new array of the same shape (the transposing codes take squares)."""
+    a = np.ascontiguousarray(batch)
+    code = _dtype_code(a.dtype if dtype is None else dtype)
+    if a.ndim != 4 or not a.size or a.dtype != _NP_OF_DTYPE[code]:
+        raise LlcompError(BAD_ARGS, f"a batch is 4-D {_NP_OF_DTYPE[code].__name__}, got {a.dtype} of shape {a.shape}")
+    lay = _layout_code(layout)
+    n = a.shape[0]
+    c, oh, ow = a.shape[1:] if lay == LAYOUT_CHW else (a.shape[3], a.shape[1], a.shape[2])
+    out = np.empty_like(a)
+    _check(_lib.load().llcomp_mi_orient_reference(a.ctypes.data, n, c, ow, oh, code, lay, _orient_codes(codes, n), out.ctypes.data))
     return out
 
 
@@ -1599,6 +1655,21 @@ class Codec:
     def mix_workspace_bytes(self, n, ow, oh, dtype="float32"):
         """the bound on .allocated_bytes() with mix_batch calls of up to n samples of ow x oh (llcomp_mi_codec_mix_workspace_bytes)"""
         return self._L.llcomp_mi_codec_mix_workspace_bytes(self._h, int(n), int(ow), int(oh), _dtype_code(dtype))
+
+    def orient_batch(self, d_batch, n, ow, oh, codes, dtype="float32", layout="chw", stream=0):
+        """A flip, quarter turn or transposition per sample, in place on a dense batch in device memory (llcomp_mi_codec_orient_batch):
+        n samples of the codec's channels and ow x oh pixels in the dtype and layout a decode call wrote them in; codes: n orientations
+        (orient_code: ORIENT_*, PIL's names or None) or one for every sample.  The transposing codes take ow == oh.  It goes behind
+        the decode and ahead of mix_batch on the same stream."""
+        n = int(n)
+        if n <= 0:
+            raise LlcompError(BAD_ARGS, f"n must be positive, got {n}")
+        _check(self._L.llcomp_mi_codec_orient_batch(self._h, d_batch, n, int(ow), int(oh), _dtype_code(dtype), _layout_code(layout),
+                                                    _orient_codes(codes, n), stream))
+
+    def orient_workspace_bytes(self, n):
+        """the bound on .allocated_bytes() with orient_batch calls of up to n samples (llcomp_mi_codec_orient_workspace_bytes)"""
+        return self._L.llcomp_mi_codec_orient_workspace_bytes(self._h, int(n))
 
     def views_workspace_bytes(self, total_views):
         """.workspace_bytes for calls of up to total_views views (llcomp_mi_codec_views_workspace_bytes): the staged tables grow with them"""

@@ -52,6 +52,7 @@ SYMBOLS = [
     "llcomp_mi_codec_perspective_workspace_bytes", "llcomp_mi_codec_photo_perspective_workspace_bytes",
     "llcomp_mi_mix_plan", "llcomp_mi_mix_segment", "llcomp_mi_mix_reference", "llcomp_mi_codec_mix_batch",
     "llcomp_mi_codec_mix_workspace_bytes",
+    "llcomp_mi_orient_reference", "llcomp_mi_orient_tile", "llcomp_mi_codec_orient_batch", "llcomp_mi_codec_orient_workspace_bytes",
 ]
 
 u8p = C.POINTER(C.c_uint8)
@@ -478,6 +479,15 @@ def load():
         L.llcomp_mi_codec_mix_batch.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 5 + [recs, f32p, C.c_void_p]
         L.llcomp_mi_codec_mix_workspace_bytes.restype = C.c_uint64
         L.llcomp_mi_codec_mix_workspace_bytes.argtypes = [C.c_void_p] + [C.c_uint32] * 4
+    if "LLCOMP_MI_LIB" not in os.environ or hasattr(L, "llcomp_mi_orient_reference"):  # batch orientation
+        L.llcomp_mi_orient_reference.restype = C.c_int
+        L.llcomp_mi_orient_reference.argtypes = [C.c_void_p] + [C.c_uint32] * 6 + [u8p, C.c_void_p]
+        L.llcomp_mi_orient_tile.restype = C.c_uint32
+        L.llcomp_mi_orient_tile.argtypes = []
+        L.llcomp_mi_codec_orient_batch.restype = C.c_int
+        L.llcomp_mi_codec_orient_batch.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 5 + [u8p, C.c_void_p]
+        L.llcomp_mi_codec_orient_workspace_bytes.restype = C.c_uint64
+        L.llcomp_mi_codec_orient_workspace_bytes.argtypes = [C.c_void_p, C.c_uint32]
     if "LLCOMP_MI_LIB" not in os.environ and L.llcomp_mi_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.llcomp_mi_abi_version()}, this binding was written for {ABI_VERSION}: rebuild the library")
     _lib = L

@@ -17,6 +17,8 @@
 #include "geometry.hpp"
 #include "kernels.hpp"
 #include "mix.hpp"
+#include "orient.hpp"
+#include "orient_rule.hpp"
 #include "photo.hpp"
 #include "resize.hpp"
 #include "snapshot.hpp"
@@ -835,6 +837,7 @@ void codec_release(llcomp_mi_codec* k) {
     dev_free(k->d_photo_tab, k->done);
     dev_free(k->d_mix_tab, k->done);
     dev_free(k->d_mix, k->done);
+    dev_free(k->d_orient_tab, k->done);
     dev_free(k->d_upd_goff, k->done);
     for (uint32_t i = 0; i < llcomp_mi_codec::kRegionsRing; ++i) {
         if (!k->h_regions[i]) continue;
@@ -1534,6 +1537,43 @@ uint64_t llcomp_mi_codec_mix_workspace_bytes(const llcomp_mi_codec* k, uint32_t 
     const uint64_t esize = dtype == LLCOMP_MI_DTYPE_U8 ? 1u : dtype == LLCOMP_MI_DTYPE_F32 ? 4u : (dtype == LLCOMP_MI_DTYPE_F16 || dtype == LLCOMP_MI_DTYPE_BF16) ? 2u : 0u;
     if (!k || !esize) return 0;
     return k->workspace_bytes + mix_table_bound(n, k->g.c) + mix_saved_bound(n) * mix_slot_stride(uint64_t(k->g.c) * ow * oh * esize);
+}
+
+// Batch orientation (DESIGN.md "Batch orientation"): every refusal first (orient_check_call), then the table of the oriented samples
+// through a slot of the pinned ring into d_orient_tab in one copy, and k_orient, all on the caller's stream.  Codes that are all 0:
+// nothing is queued.
+int llcomp_mi_codec_orient_batch(llcomp_mi_codec* k, void* d_batch, uint32_t n, uint32_t ow, uint32_t oh, uint32_t dtype, uint32_t layout,
+                                 const uint8_t* codes, void* stream) {
+    if (!k || !d_batch || !codes) return LLCOMP_MI_BAD_ARGS;
+    const uint32_t c = k->g.c;
+    if (int rc = orient_check_call(n, c, ow, oh, dtype, layout, codes)) return rc;
+    if (misaligned(d_batch, orient_esize(dtype))) return LLCOMP_MI_BAD_ARGS;
+    std::vector<OrientEntry> table;
+    orient_table(n, codes, table);
+    if (table.empty()) return LLCOMP_MI_OK;
+    const uint64_t bytes = table.size() * sizeof(OrientEntry);
+    DeviceGuard guard(k->device);
+    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
+    if (int rc = ensure_regions_ring(k)) return rc;
+    if (int rc = ensure_grown(k, k->d_orient_tab, k->orient_tab_cap, bytes, orient_table_bound(n))) return rc;
+    uint32_t slot = 0;
+    if (int rc = regions_slot_take(k, bytes, orient_table_bound(n), slot)) return rc;
+    std::memcpy(k->h_regions[slot], table.data(), bytes);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DoneGuard done_guard{k, s};
+    HIP_TRY(hipMemcpyAsync(k->d_orient_tab, k->h_regions[slot], bytes, hipMemcpyHostToDevice, s));
+    if (int rc = regions_slot_queued(k, slot, s)) return rc;
+    OrientLaunch o{};
+    o.d_batch = static_cast<uint8_t*>(d_batch), o.d_table = k->d_orient_tab, o.n_entries = uint32_t(table.size());
+    for (const OrientEntry& e : table) o.code_set |= 1u << e.code;
+    o.c = c, o.ow = ow, o.oh = oh, o.dtype = dtype, o.layout = layout;
+    HIP_TRY(launch_orient(o, s));
+    return LLCOMP_MI_OK;
+}
+
+uint64_t llcomp_mi_codec_orient_workspace_bytes(const llcomp_mi_codec* k, uint32_t n) {
+    if (!k) return 0;
+    return k->workspace_bytes + orient_table_bound(n);
 }
 
 uint64_t llcomp_mi_codec_photo_workspace_bytes(const llcomp_mi_codec* k, uint64_t total_views) {
