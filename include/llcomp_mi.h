@@ -666,6 +666,57 @@ int llcomp_mi_orient_reference(const void* batch, uint32_t n, uint32_t c, uint32
                                const uint8_t* codes, void* out);
 /* The side, in pixels, of the tile of llcomp_mi_codec_orient_batch's kernel (DESIGN.md "Batch orientation"): a constant */
 uint32_t llcomp_mi_orient_tile(void);
+/* Batch composition (llcomp_mi_codec_compose_batch below: Mosaic, make_grid contact sheets, torchvision's batch_images collate,
+ * RandomZoomOut on a batch, jigsaw shuffles, rectangle copy-paste, ResizeMix, CutMix between two batches, Cutout with several holes,
+ * GridMask, Hide-and-Seek): rectangles of a source batch land at positions of a destination batch, the rest is a fill or stays.  Two
+ * dense batches of the same c, dtype (U8, F16, BF16, F32) and layout (HWC or CHW), aligned to the element's size and to nothing more:
+ * src, n_src samples of iw x ih, and dst, n_dst samples of ow x oh.  The call has a list of n_pieces records (below), fill_value (c
+ * floats, NULL = zeros) and call flags.  The rule for the element at channel ch, row y, column x of dst sample d: take the LAST piece p
+ * in list order with dst_p == d whose rectangle [dx, dx + w) x [dy, dy + h) holds (x, y) -- painter's order, later pieces win.
+ *   p is a FILL piece:           fill_value[ch] converted to the dtype
+ *   any other p:                 src(src_p, ch, sy_p + y - dy_p, sx_p + x - dx_p), moved as bits
+ *   no such piece, KEEP set:     the element as it stood; it is not written
+ *   no such piece, KEEP not set: fill_value[ch] converted
+ * Elements are moved, never interpreted: NaN payloads and negative zeros survive, and only the element's size tells the dtypes apart.
+ * The fill converts as the batch mixing's erase_value does: to nearest even for F16 and BF16, U8 takes integers 0..255 only, a value that
+ * is not finite is refused.  Pieces come in any order of dst, may overlap and may be hidden entirely; a piece with w or h 0 is ignored
+ * (but checked).  src may be NULL with n_src == 0 when every piece is a FILL piece (with KEEP: the in-place erase of many rectangles);
+ * otherwise the byte ranges of the two batches must not overlap.
+ * BAD_ARGS: a NULL pieces with n_pieces > 0; n_dst or n_src above 65535, n_dst == 0, n_pieces above 2^20; ow, oh or c of 0, iw or ih
+ * of 0 with n_src > 0; a row of ow * c or iw * c elements or more than 2^31, a batch no address space holds; an unknown dtype or
+ * layout; a piece with dst >= n_dst; a piece that is no FILL piece with src >= n_src or a source rectangle that leaves iw x ih; a piece
+ * whose rectangle leaves ow x oh; a FILL piece with src, sx or sy not 0; flag or reserved bits that are not defined; a bad fill value;
+ * more than llcomp_mi_compose_max_pieces_per_sample() = 1024 pieces with w and h above 0 on one dst sample.
+ * NOT covered: pieces that resample or mirror (views do that at decode), masks that are not rectangles (CopyPaste with instance masks),
+ * the labels and boxes, and a src and dst that differ in dtype or layout. */
+#define LLCOMP_MI_COMPOSE_FILL 1u /* piece flag */
+#define LLCOMP_MI_COMPOSE_KEEP 1u /* call flag: elements no piece covers keep their value and are not written */
+typedef struct llcomp_mi_compose_piece {
+    uint32_t dst, src;       /* sample of dst; sample of src (0 for a FILL piece) */
+    uint32_t dx, dy, sx, sy; /* where the rectangle lands; where it is read (0, 0 for a FILL piece) */
+    uint32_t w, h;           /* w or h 0: the piece is ignored */
+    uint32_t flags;          /* bit 0 LLCOMP_MI_COMPOSE_FILL: the rectangle is the call's fill value, nothing is read */
+    uint32_t reserved;       /* 0 */
+} llcomp_mi_compose_piece;   /* 40 bytes */
+/* The rule above on host memory.  out (n_dst samples) may be dst_in, and overlaps src in no way; dst_in is read only under KEEP and may
+ * be NULL without it.  It is compiled from the same functions as the GPU's kernel; it is not fast.  BAD_ARGS, out untouched: the cases
+ * above, a NULL out, a NULL dst_in under KEEP, a NULL src with n_src > 0.  Host-only. */
+int llcomp_mi_compose_reference(const void* src, uint32_t n_src, uint32_t iw, uint32_t ih, const void* dst_in, uint32_t n_dst, uint32_t ow,
+                                uint32_t oh, uint32_t c, uint32_t dtype, uint32_t layout, const llcomp_mi_compose_piece* pieces,
+                                uint32_t n_pieces, const float* fill_value, uint32_t flags, void* out);
+/* What a call does (DESIGN.md "Batch composition"): samples[*n_samples] (room for n_dst), the dst samples that get workgroups, ascending
+ * -- all of them, or under KEEP those with a piece of w and h above 0; first[*n_samples + 1] (room for n_dst + 1) and order (room for
+ * n_pieces): sample j's pieces are order[first[j] .. first[j + 1]), indices into pieces in the call's order, the ignored ones left out;
+ * *n_workgroups: the workgroups of the call's one kernel, 0 for a call that queues nothing.  samples, first and order may be NULL.
+ * BAD_ARGS, outputs untouched: the cases above, a NULL n_samples or n_workgroups.  Host-only. */
+int llcomp_mi_compose_plan(uint32_t n_src, uint32_t iw, uint32_t ih, uint32_t n_dst, uint32_t ow, uint32_t oh, uint32_t c, uint32_t dtype,
+                           uint32_t layout, const llcomp_mi_compose_piece* pieces, uint32_t n_pieces, uint32_t flags, uint32_t* samples,
+                           uint32_t* first, uint32_t* order, uint32_t* n_samples, uint64_t* n_workgroups);
+/* The kernel's tile: llcomp_mi_compose_tile() pixels across (128) and llcomp_mi_compose_tile_rows(pixel_bytes) rows, where pixel_bytes
+ * is the element's size in CHW and c elements in HWC: the power of two, at most 64, that keeps a tile within 16 KiB.  Constants. */
+uint32_t llcomp_mi_compose_tile(void);
+uint32_t llcomp_mi_compose_tile_rows(uint32_t pixel_bytes);
+uint32_t llcomp_mi_compose_max_pieces_per_sample(void);
 uint32_t llcomp_mi_slice_count(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar);
 /* Slice width for one-row slices (tile_h = 1) when `frames` frames are coded per call: the widest slice (64..480 pixels) that
  * still keeps about four wavefronts per SIMD busy.  A call that codes few frames is latency-bound with wide slices; this
@@ -1031,6 +1082,22 @@ int llcomp_mi_codec_orient_batch(llcomp_mi_codec* codec, void* d_batch, uint32_t
  * llcomp_mi_codec_workspace_bytes + 8 * n, the table of a call that orients every sample (8 bytes per oriented sample).  0 for a NULL
  * codec. */
 uint64_t llcomp_mi_codec_orient_workspace_bytes(const llcomp_mi_codec* codec, uint32_t n);
+/* Batch composition (the rule: "Batch composition" above): rectangles of d_src, n_src samples of the codec's c channels and iw x ih
+ * pixels, into d_dst, n_dst samples of ow x oh, both in device memory, asynchronously on `stream` -- behind the decode call that wrote
+ * src when that ran on the same stream.  One kernel, no scratch in device memory: every dst element is written at most once (exactly
+ * once without KEEP), in aligned 16-byte stores wherever a whole 16-byte unit of dst memory comes from one piece or from the fill; no
+ * byte outside either batch is read or written.  Under KEEP a dst sample without pieces costs no workgroup, and a call with no piece of
+ * w and h above 0 queues nothing.  pieces and fill_value are HOST memory, read during the call only: they travel with the plan in ONE
+ * copy from the codec's pinned ring into a device buffer of this call's own.  d_src may be NULL with n_src == 0.  BAD_ARGS, nothing
+ * queued: a NULL codec or d_dst, a NULL d_src with n_src > 0, a pointer that is not aligned to the element, byte ranges of the two
+ * batches that overlap, and llcomp_mi_compose_plan's cases. */
+int llcomp_mi_codec_compose_batch(llcomp_mi_codec* codec, const void* d_src, uint32_t n_src, uint32_t iw, uint32_t ih, void* d_dst,
+                                  uint32_t n_dst, uint32_t ow, uint32_t oh, uint32_t dtype, uint32_t layout,
+                                  const llcomp_mi_compose_piece* pieces, uint32_t n_pieces, const float* fill_value, uint32_t flags,
+                                  void* stream);
+/* The bound on llcomp_mi_codec_allocated_bytes with such calls of up to n_dst dst samples and n_pieces pieces among the codec's calls:
+ * llcomp_mi_codec_workspace_bytes + 12 * n_dst + 32 * n_pieces + 4 * c, the table of a call.  0 for a NULL codec. */
+uint64_t llcomp_mi_codec_compose_workspace_bytes(const llcomp_mi_codec* codec, uint32_t n_dst, uint32_t n_pieces);
 /* Stage-A only (context + prediction model), for tests and profiling: d_sym u32[frames*h*w*c],
  * low 16 bits = folded context (0..7925), high 16 bits = folded residual (two's complement). */
 int llcomp_mi_codec_model(llcomp_mi_codec* codec, const void* d_px, void* d_sym, void* stream);

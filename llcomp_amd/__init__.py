@@ -34,6 +34,9 @@ with ctypes and keeps the reference's names and error behaviour:
         the float batch a decode call wrote, bit for bit torch's expressions on the CPU)
     ORIENT_* / orient_code / orient_reference / Codec.orient_batch / Codec.orient_workspace_bytes  (a flip, quarter turn or transposition
         per sample, in place on the batch a decode call wrote: RandomVerticalFlip, PIL's Image.transpose, np.rot90)
+    COMPOSE_FILL / COMPOSE_KEEP / compose_pieces / compose_plan / compose_tile / compose_reference / grid_pieces / mosaic_pieces /
+        Codec.compose_batch / Codec.compose_workspace_bytes  (rectangles of one decoded batch into the canvases of another, the rest a
+        fill or kept: Mosaic, make_grid, batch_images, Cutout with several holes, GridMask)
     RawImage(pixels, width, height, channels)     <->  llcomp::RawImage         (/root/reference/llcomp.hpp:454-459)
     EXT = ".llcomp"                               <->  llcomp::ext              (/root/reference/llcomp.hpp:18)
 
@@ -52,6 +55,7 @@ from ._lib import View as _View, ViewGroup as _ViewGroup
 from ._lib import WarpView as _WarpView, WarpGroup as _WarpGroup
 from ._lib import PerspectiveView as _PerspectiveView, PerspectiveGroup as _PerspectiveGroup
 from ._lib import PhotoOp as _PhotoOp, PhotoChain as _PhotoChain, PhotoGroup as _PhotoGroup
+from ._lib import ComposePiece as _ComposePiece
 from ._lib import MixSample as _MixSample
 
 EXT = ".llcomp"
@@ -678,6 +682,134 @@ def orient_reference(batch, codes, layout="chw", dtype=None):
     out = np.empty_like(a)
     _check(_lib.load().llcomp_mi_orient_reference(a.ctypes.data, n, c, ow, oh, code, lay, _orient_codes(codes, n), out.ctypes.data))
     return out
+
+
+# Codec.compose_batch (LLCOMP_MI_COMPOSE_*): a piece's flag, and the call's
+COMPOSE_FILL = 1
+COMPOSE_KEEP = 1
+_COMPOSE_FIELDS = ("dst", "src", "dx", "dy", "sx", "sy", "w", "h", "flags")
+
+
+def compose_pieces(records):
+    """The pieces of a compose_batch call (llcomp_mi_compose_piece) as a ctypes array: every record a tuple (dst, src, dx, dy, sx, sy,
+    w, h[, flags]) or a dict of those names (what it leaves out is 0).  A FILL piece has flags=COMPOSE_FILL and src, sx, sy 0.  The
+    library checks the records."""
+    if isinstance(records, C.Array) and records._type_ is _ComposePiece:
+        return records
+    records = list(records)
+    arr = (_ComposePiece * len(records))()
+    for i, r in enumerate(records):
+        if isinstance(r, dict):
+            if set(r) - set(_COMPOSE_FIELDS):
+                raise LlcompError(BAD_ARGS, f"a piece has {_COMPOSE_FIELDS}, got {sorted(set(r) - set(_COMPOSE_FIELDS))}")
+            vals = [r.get(name, 0) for name in _COMPOSE_FIELDS]
+        else:
+            vals = list(r)
+            if len(vals) not in (8, 9):
+                raise LlcompError(BAD_ARGS, f"a piece is (dst, src, dx, dy, sx, sy, w, h[, flags]), got {r!r}")
+            vals += [0] * (9 - len(vals))
+        vals = [int(v) for v in vals]
+        if min(vals) < 0 or max(vals) > 0xFFFFFFFF:
+            raise LlcompError(BAD_ARGS, f"a piece takes unsigned values, got {r!r}")
+        for name, v in zip(_COMPOSE_FIELDS, vals):
+            setattr(arr[i], name, v)
+    return arr
+
+
+def compose_tile(pixel_bytes=None):
+    """the kernel's tile: its width in pixels (llcomp_mi_compose_tile), or with pixel_bytes -- the element's size in CHW, c elements in
+    HWC -- its rows (llcomp_mi_compose_tile_rows)"""
+    L = _lib.load()
+    return int(L.llcomp_mi_compose_tile()) if pixel_bytes is None else int(L.llcomp_mi_compose_tile_rows(int(pixel_bytes)))
+
+
+def compose_max_pieces_per_sample():
+    """the most pieces with w and h above 0 on one dst sample (llcomp_mi_compose_max_pieces_per_sample)"""
+    return int(_lib.load().llcomp_mi_compose_max_pieces_per_sample())
+
+
+def compose_plan(n_src, iw, ih, n_dst, ow, oh, c, pieces, dtype="float32", layout="chw", keep=False):
+    """What a compose_batch call does (llcomp_mi_compose_plan, host only) -> (samples, first, order, n_workgroups): the dst samples that
+    get workgroups, where every sample's pieces begin in order (one more entry: their number), the pieces' indices by dst sample, each
+    sample's in the call's order without the empty ones, and the workgroups of the kernel.  LlcompError(BAD_ARGS) for a call that is
+    refused by itself."""
+    recs = compose_pieces(pieces)
+    n_dst = int(n_dst)
+    samples, first, order = np.zeros(max(n_dst, 1), np.uint32), np.zeros(max(n_dst, 1) + 1, np.uint32), np.zeros(max(len(recs), 1), np.uint32)
+    ns, nw = C.c_uint32(0), C.c_uint64(0)
+    u32p = C.POINTER(C.c_uint32)
+    _check(_lib.load().llcomp_mi_compose_plan(int(n_src), int(iw), int(ih), n_dst, int(ow), int(oh), int(c), _dtype_code(dtype), _layout_code(layout),
+                                              recs, len(recs), COMPOSE_KEEP if keep else 0, samples.ctypes.data_as(u32p),
+                                              first.ctypes.data_as(u32p), order.ctypes.data_as(u32p), C.byref(ns), C.byref(nw)))
+    n = ns.value
+    return samples[:n].copy(), first[:n + 1].copy(), order[:int(first[n])].copy(), int(nw.value)
+
+
+def _compose_fill(fill, c):
+    return _mix_erase_value(fill, c)
+
+
+def compose_reference(src, dst, pieces, layout="chw", fill=None, keep=False, dtype=None):
+    """The rule of the batch composition on host arrays (llcomp_mi_compose_reference): src [n_src, c, ih, iw] (layout "chw") or
+    [n_src, ih, iw, c] ("hwc"), or None when every piece is a FILL piece; dst the same way -- its values matter under keep only; both of
+    uint8, float32, float16, or uint16 holding bfloat16 bits with dtype="bfloat16" -> the composed dst batch, a new array."""
+    d = np.ascontiguousarray(dst)
+    code = _dtype_code(d.dtype if dtype is None else dtype)
+    if d.ndim != 4 or not d.size or d.dtype != _NP_OF_DTYPE[code]:
+        raise LlcompError(BAD_ARGS, f"a batch is 4-D {_NP_OF_DTYPE[code].__name__}, got {d.dtype} of shape {d.shape}")
+    lay = _layout_code(layout)
+    c, oh, ow = d.shape[1:] if lay == LAYOUT_CHW else (d.shape[3], d.shape[1], d.shape[2])
+    n_src = iw = ih = 0
+    s = None
+    if src is not None:
+        s = np.ascontiguousarray(src)
+        if s.ndim != 4 or s.dtype != d.dtype or (s.shape[1] if lay == LAYOUT_CHW else s.shape[3]) != c:
+            raise LlcompError(BAD_ARGS, f"src is a 4-D batch of dst's type and channels, got {s.dtype} of shape {s.shape}")
+        n_src = s.shape[0]
+        ih, iw = s.shape[2:] if lay == LAYOUT_CHW else s.shape[1:3]
+    recs = compose_pieces(pieces)
+    out = np.empty_like(d)
+    _check(_lib.load().llcomp_mi_compose_reference(s.ctypes.data if n_src else None, n_src, iw, ih, d.ctypes.data, d.shape[0], ow, oh, c, code, lay,
+                                                   recs, len(recs), _compose_fill(fill, c), COMPOSE_KEEP if keep else 0, out.ctypes.data))
+    return out
+
+
+def grid_pieces(n, iw, ih, nrow=8, padding=2):
+    """The pieces that lay n samples of iw x ih out as torchvision.utils.make_grid(nrow=, padding=) does, on ONE canvas (dst sample 0)
+    -> (pieces, ow, oh); the canvas's fill is make_grid's pad_value.  (make_grid returns a single picture as it is; this lays it
+    out with its border like the others.)"""
+    n, iw, ih, nrow, padding = int(n), int(iw), int(ih), int(nrow), int(padding)
+    if n <= 0 or iw <= 0 or ih <= 0 or nrow <= 0 or padding < 0:
+        raise LlcompError(BAD_ARGS, "grid_pieces takes n, iw, ih, nrow above 0 and a padding of 0 or more")
+    xmaps = min(nrow, n)
+    ymaps = -(-n // xmaps)
+    cw, ch = iw + padding, ih + padding
+    recs = [(0, k, (k % xmaps) * cw + padding, (k // xmaps) * ch + padding, 0, 0, iw, ih) for k in range(n)]
+    return compose_pieces(recs), cw * xmaps + padding, ch * ymaps + padding
+
+
+def mosaic_pieces(centres, iw, ih, s):
+    """The pieces of YOLO's 4-picture mosaic as Ultralytics' load_mosaic places them: canvas i, 2s x 2s, takes src samples 4i .. 4i + 3
+    of iw x ih around centres[i] = (xc, yc) -- top left, top right, bottom left, bottom right, each clipped to its quadrant and read
+    from the corner of its picture that touches the centre.  The canvas's fill is 114 there.  -> the pieces"""
+    iw, ih, s = int(iw), int(ih), int(s)
+    recs = []
+    for i, (xc, yc) in enumerate(centres):
+        xc, yc = int(xc), int(yc)
+        if not (0 <= xc <= 2 * s and 0 <= yc <= 2 * s):
+            raise LlcompError(BAD_ARGS, f"a mosaic centre lies in the canvas of {2 * s} x {2 * s}, got {(xc, yc)}")
+        boxes = (
+            (max(xc - iw, 0), max(yc - ih, 0), xc, yc, "br"),
+            (xc, max(yc - ih, 0), min(xc + iw, 2 * s), yc, "bl"),
+            (max(xc - iw, 0), yc, xc, min(2 * s, yc + ih), "tr"),
+            (xc, yc, min(xc + iw, 2 * s), min(2 * s, yc + ih), "tl"),
+        )
+        for k, (x1, y1, x2, y2, corner) in enumerate(boxes):
+            w, h = x2 - x1, y2 - y1
+            sx = iw - w if corner in ("br", "tr") else 0
+            sy = ih - h if corner in ("br", "bl") else 0
+            recs.append((i, 4 * i + k, x1, y1, sx, sy, w, h))
+    return compose_pieces(recs)
 
 
 def _view_groups(groups, c, signed=False):
@@ -1670,6 +1802,22 @@ class Codec:
     def orient_workspace_bytes(self, n):
         """the bound on .allocated_bytes() with orient_batch calls of up to n samples (llcomp_mi_codec_orient_workspace_bytes)"""
         return self._L.llcomp_mi_codec_orient_workspace_bytes(self._h, int(n))
+
+    def compose_batch(self, d_src, n_src, iw, ih, d_dst, n_dst, ow, oh, pieces, dtype="float32", layout="chw", fill=None, keep=False, stream=0):
+        """Rectangles of one dense batch into another, the rest a fill or kept (llcomp_mi_codec_compose_batch): d_src, n_src samples of
+        the codec's channels and iw x ih pixels (None and 0 when every piece is a FILL piece), d_dst, n_dst samples of ow x oh, both in
+        device memory in the same dtype and layout; pieces from compose_pieces(), grid_pieces() or mosaic_pieces(), or records for
+        compose_pieces(); fill: one value or one per channel (default zeros); keep: what no piece covers stays and is not written.
+        Asynchronous on `stream`, behind the decode that wrote d_src; pieces and fill are read during the call."""
+        recs = compose_pieces(pieces)
+        _check(self._L.llcomp_mi_codec_compose_batch(self._h, d_src, int(n_src), int(iw), int(ih), d_dst, int(n_dst), int(ow), int(oh),
+                                                     _dtype_code(dtype), _layout_code(layout), recs, len(recs), _compose_fill(fill, self.c),
+                                                     COMPOSE_KEEP if keep else 0, stream))
+
+    def compose_workspace_bytes(self, n_dst, n_pieces):
+        """the bound on .allocated_bytes() with compose_batch calls of up to n_dst dst samples and n_pieces pieces
+        (llcomp_mi_codec_compose_workspace_bytes)"""
+        return self._L.llcomp_mi_codec_compose_workspace_bytes(self._h, int(n_dst), int(n_pieces))
 
     def views_workspace_bytes(self, total_views):
         """.workspace_bytes for calls of up to total_views views (llcomp_mi_codec_views_workspace_bytes): the staged tables grow with them"""

@@ -53,6 +53,8 @@ SYMBOLS = [
     "llcomp_mi_mix_plan", "llcomp_mi_mix_segment", "llcomp_mi_mix_reference", "llcomp_mi_codec_mix_batch",
     "llcomp_mi_codec_mix_workspace_bytes",
     "llcomp_mi_orient_reference", "llcomp_mi_orient_tile", "llcomp_mi_codec_orient_batch", "llcomp_mi_codec_orient_workspace_bytes",
+    "llcomp_mi_compose_reference", "llcomp_mi_compose_plan", "llcomp_mi_compose_tile", "llcomp_mi_compose_tile_rows",
+    "llcomp_mi_compose_max_pieces_per_sample", "llcomp_mi_codec_compose_batch", "llcomp_mi_codec_compose_workspace_bytes",
 ]
 
 u8p = C.POINTER(C.c_uint8)
@@ -130,6 +132,12 @@ class MixSample(C.Structure):
     """llcomp_mi_mix_sample (include/llcomp_mi.h): 48 bytes"""
     _fields_ = [("partner", C.c_uint32), ("flags", C.c_uint32), ("w_own", C.c_float), ("w_partner", C.c_float), ("box", C.c_uint32 * 4),
                 ("erase", C.c_uint32 * 4)]
+
+
+class ComposePiece(C.Structure):
+    """llcomp_mi_compose_piece (include/llcomp_mi.h): 40 bytes"""
+    _fields_ = [("dst", C.c_uint32), ("src", C.c_uint32), ("dx", C.c_uint32), ("dy", C.c_uint32), ("sx", C.c_uint32), ("sy", C.c_uint32),
+                ("w", C.c_uint32), ("h", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class Info(C.Structure):
@@ -488,6 +496,24 @@ def load():
         L.llcomp_mi_codec_orient_batch.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 5 + [u8p, C.c_void_p]
         L.llcomp_mi_codec_orient_workspace_bytes.restype = C.c_uint64
         L.llcomp_mi_codec_orient_workspace_bytes.argtypes = [C.c_void_p, C.c_uint32]
+    if "LLCOMP_MI_LIB" not in os.environ or hasattr(L, "llcomp_mi_compose_reference"):  # batch composition
+        u32p, recs, f32p = C.POINTER(C.c_uint32), C.POINTER(ComposePiece), C.POINTER(C.c_float)
+        L.llcomp_mi_compose_reference.restype = C.c_int
+        L.llcomp_mi_compose_reference.argtypes = [C.c_void_p] + [C.c_uint32] * 3 + [C.c_void_p] + [C.c_uint32] * 6 + [recs, C.c_uint32, f32p,
+                                                                                                                  C.c_uint32, C.c_void_p]
+        L.llcomp_mi_compose_plan.restype = C.c_int
+        L.llcomp_mi_compose_plan.argtypes = [C.c_uint32] * 9 + [recs, C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p, C.POINTER(C.c_uint64)]
+        L.llcomp_mi_compose_tile.restype = C.c_uint32
+        L.llcomp_mi_compose_tile.argtypes = []
+        L.llcomp_mi_compose_tile_rows.restype = C.c_uint32
+        L.llcomp_mi_compose_tile_rows.argtypes = [C.c_uint32]
+        L.llcomp_mi_compose_max_pieces_per_sample.restype = C.c_uint32
+        L.llcomp_mi_compose_max_pieces_per_sample.argtypes = []
+        L.llcomp_mi_codec_compose_batch.restype = C.c_int
+        L.llcomp_mi_codec_compose_batch.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 3 + [C.c_void_p] + [C.c_uint32] * 5 + [
+            recs, C.c_uint32, f32p, C.c_uint32, C.c_void_p]
+        L.llcomp_mi_codec_compose_workspace_bytes.restype = C.c_uint64
+        L.llcomp_mi_codec_compose_workspace_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
     if "LLCOMP_MI_LIB" not in os.environ and L.llcomp_mi_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.llcomp_mi_abi_version()}, this binding was written for {ABI_VERSION}: rebuild the library")
     _lib = L

@@ -17,6 +17,8 @@
 #include "geometry.hpp"
 #include "kernels.hpp"
 #include "mix.hpp"
+#include "compose.hpp"
+#include "compose_rule.hpp"
 #include "orient.hpp"
 #include "orient_rule.hpp"
 #include "photo.hpp"
@@ -838,6 +840,7 @@ void codec_release(llcomp_mi_codec* k) {
     dev_free(k->d_mix_tab, k->done);
     dev_free(k->d_mix, k->done);
     dev_free(k->d_orient_tab, k->done);
+    dev_free(k->d_compose_tab, k->done);
     dev_free(k->d_upd_goff, k->done);
     for (uint32_t i = 0; i < llcomp_mi_codec::kRegionsRing; ++i) {
         if (!k->h_regions[i]) continue;
@@ -1574,6 +1577,48 @@ int llcomp_mi_codec_orient_batch(llcomp_mi_codec* k, void* d_batch, uint32_t n, 
 uint64_t llcomp_mi_codec_orient_workspace_bytes(const llcomp_mi_codec* k, uint32_t n) {
     if (!k) return 0;
     return k->workspace_bytes + orient_table_bound(n);
+}
+
+// Batch composition (DESIGN.md "Batch composition"): every refusal first (compose_check_call, compose_check_memory), then the plan, the
+// table through a slot of the pinned ring into d_compose_tab in one copy, and k_compose, all on the caller's stream.  Under KEEP a call
+// without a piece of w and h above 0 queues nothing.
+int llcomp_mi_codec_compose_batch(llcomp_mi_codec* k, const void* d_src, uint32_t n_src, uint32_t iw, uint32_t ih, void* d_dst, uint32_t n_dst,
+                                  uint32_t ow, uint32_t oh, uint32_t dtype, uint32_t layout, const llcomp_mi_compose_piece* pieces,
+                                  uint32_t n_pieces, const float* fill_value, uint32_t flags, void* stream) {
+    if (!k || !d_dst) return LLCOMP_MI_BAD_ARGS;
+    const uint32_t c = k->g.c;
+    std::vector<uint32_t> fill_bits;
+    if (int rc = compose_check_call(n_src, iw, ih, n_dst, ow, oh, c, dtype, layout, pieces, n_pieces, fill_value, flags, fill_bits)) return rc;
+    const uint32_t esize = compose_esize(dtype);
+    if (int rc = compose_check_memory(d_src, uint64_t(n_src) * c * iw * ih * esize, d_dst, uint64_t(n_dst) * c * ow * oh * esize, esize)) return rc;
+    ComposePlan p;
+    compose_plan(n_dst, pieces, n_pieces, flags, p);
+    if (p.samples.empty()) return LLCOMP_MI_OK;
+    const ComposeTable t(p.samples.size(), p.order.size(), c);
+    const uint64_t bound = compose_table_bound(n_dst, n_pieces, c);
+    DeviceGuard guard(k->device);
+    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
+    if (int rc = ensure_regions_ring(k)) return rc;
+    if (int rc = ensure_grown(k, k->d_compose_tab, k->compose_tab_cap, t.bytes, bound)) return rc;
+    uint32_t slot = 0;
+    if (int rc = regions_slot_take(k, t.bytes, bound, slot)) return rc;
+    compose_table_put(pieces, p, fill_bits, layout, k->h_regions[slot]);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DoneGuard done_guard{k, s};
+    HIP_TRY(hipMemcpyAsync(k->d_compose_tab, k->h_regions[slot], t.bytes, hipMemcpyHostToDevice, s));
+    if (int rc = regions_slot_queued(k, slot, s)) return rc;
+    ComposeLaunch o{};
+    o.d_src = n_src ? static_cast<const uint8_t*>(d_src) : nullptr, o.d_dst = static_cast<uint8_t*>(d_dst), o.d_table = k->d_compose_tab;
+    o.n_samples = uint32_t(p.samples.size()), o.n_recs = uint32_t(p.order.size());
+    o.n_src = n_src, o.iw = iw, o.ih = ih, o.ow = ow, o.oh = oh, o.c = c, o.dtype = dtype, o.layout = layout;
+    o.keep = flags & LLCOMP_MI_COMPOSE_KEEP;
+    HIP_TRY(launch_compose(o, s));
+    return LLCOMP_MI_OK;
+}
+
+uint64_t llcomp_mi_codec_compose_workspace_bytes(const llcomp_mi_codec* k, uint32_t n_dst, uint32_t n_pieces) {
+    if (!k) return 0;
+    return k->workspace_bytes + compose_table_bound(n_dst, n_pieces, k->g.c);
 }
 
 uint64_t llcomp_mi_codec_photo_workspace_bytes(const llcomp_mi_codec* k, uint64_t total_views) {
