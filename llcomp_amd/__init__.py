@@ -603,28 +603,35 @@ def mix_plan(samples):
     return order, seg[:ns.value + 1].copy(), int(nv.value)
 
 
-def _mix_erase_value(erase_value, c):
-    if erase_value is None:
+def _per_channel(values, c, what):
+    """one value or c of them (None: the library's zeros) -> a ctypes float array for the batch calls, or None"""
+    if values is None:
         return None
-    a = np.asarray(erase_value, dtype=np.float32).reshape(-1)
+    a = np.asarray(values, dtype=np.float32).reshape(-1)
     if a.size == 1:
         a = np.full(c, a[0], np.float32)
     if a.size != c:
-        raise LlcompError(BAD_ARGS, f"erase_value takes {c} values, got {a.size}")
+        raise LlcompError(BAD_ARGS, f"{what} takes {c} values, got {a.size}")
     return (C.c_float * c)(*a.tolist())
 
 
-def mix_reference(batch, samples, layout="chw", erase_value=None, dtype=None):
-    """The rule of the batch mixing on a host array (llcomp_mi_mix_reference): batch [n, c, oh, ow] (layout "chw") or [n, oh, ow, c]
-    ("hwc") of uint8, float32, float16, or uint16 holding bfloat16 bits with dtype="bfloat16" -> the mixed batch, a new array."""
+def _batch_array(batch, dtype, layout):
+    """a host batch [n, c, h, w] ("chw") or [n, h, w, c] ("hwc") for the references of the batch calls -> (the contiguous array, dtype
+    code, layout code, n, c, h, w)"""
     a = np.ascontiguousarray(batch)
     code = _dtype_code(a.dtype if dtype is None else dtype)
     if a.ndim != 4 or not a.size or a.dtype != _NP_OF_DTYPE[code]:
         raise LlcompError(BAD_ARGS, f"a batch is 4-D {_NP_OF_DTYPE[code].__name__}, got {a.dtype} of shape {a.shape}")
     lay = _layout_code(layout)
-    n = a.shape[0]
-    c, oh, ow = a.shape[1:] if lay == LAYOUT_CHW else (a.shape[3], a.shape[1], a.shape[2])
-    ev = _mix_erase_value(erase_value, c)
+    c, h, w = a.shape[1:] if lay == LAYOUT_CHW else (a.shape[3], a.shape[1], a.shape[2])
+    return a, code, lay, a.shape[0], c, h, w
+
+
+def mix_reference(batch, samples, layout="chw", erase_value=None, dtype=None):
+    """The rule of the batch mixing on a host array (llcomp_mi_mix_reference): batch [n, c, oh, ow] (layout "chw") or [n, oh, ow, c]
+    ("hwc") of uint8, float32, float16, or uint16 holding bfloat16 bits with dtype="bfloat16" -> the mixed batch, a new array."""
+    a, code, lay, n, c, oh, ow = _batch_array(batch, dtype, layout)
+    ev = _per_channel(erase_value, c, "erase_value")
     out = np.empty_like(a)
     _check(_lib.load().llcomp_mi_mix_reference(a.ctypes.data, n, c, ow, oh, code, lay, _mix_records(samples, n), ev, out.ctypes.data))
     return out
@@ -672,13 +679,7 @@ def orient_reference(batch, codes, layout="chw", dtype=None):
     """The rule of the batch orientation on a host array (llcomp_mi_orient_reference): batch [n, c, oh, ow] (layout "chw") or
     [n, oh, ow, c] ("hwc") of uint8, float32, float16, or uint16 holding bfloat16 bits with dtype="bfloat16"; codes: n orientations
     (orient_code) or one for every sample -> the oriented batch, a new array of the same shape (the transposing codes take squares)."""
-    a = np.ascontiguousarray(batch)
-    code = _dtype_code(a.dtype if dtype is None else dtype)
-    if a.ndim != 4 or not a.size or a.dtype != _NP_OF_DTYPE[code]:
-        raise LlcompError(BAD_ARGS, f"a batch is 4-D {_NP_OF_DTYPE[code].__name__}, got {a.dtype} of shape {a.shape}")
-    lay = _layout_code(layout)
-    n = a.shape[0]
-    c, oh, ow = a.shape[1:] if lay == LAYOUT_CHW else (a.shape[3], a.shape[1], a.shape[2])
+    a, code, lay, n, c, oh, ow = _batch_array(batch, dtype, layout)
     out = np.empty_like(a)
     _check(_lib.load().llcomp_mi_orient_reference(a.ctypes.data, n, c, ow, oh, code, lay, _orient_codes(codes, n), out.ctypes.data))
     return out
@@ -745,20 +746,11 @@ def compose_plan(n_src, iw, ih, n_dst, ow, oh, c, pieces, dtype="float32", layou
     return samples[:n].copy(), first[:n + 1].copy(), order[:int(first[n])].copy(), int(nw.value)
 
 
-def _compose_fill(fill, c):
-    return _mix_erase_value(fill, c)
-
-
 def compose_reference(src, dst, pieces, layout="chw", fill=None, keep=False, dtype=None):
     """The rule of the batch composition on host arrays (llcomp_mi_compose_reference): src [n_src, c, ih, iw] (layout "chw") or
     [n_src, ih, iw, c] ("hwc"), or None when every piece is a FILL piece; dst the same way -- its values matter under keep only; both of
     uint8, float32, float16, or uint16 holding bfloat16 bits with dtype="bfloat16" -> the composed dst batch, a new array."""
-    d = np.ascontiguousarray(dst)
-    code = _dtype_code(d.dtype if dtype is None else dtype)
-    if d.ndim != 4 or not d.size or d.dtype != _NP_OF_DTYPE[code]:
-        raise LlcompError(BAD_ARGS, f"a batch is 4-D {_NP_OF_DTYPE[code].__name__}, got {d.dtype} of shape {d.shape}")
-    lay = _layout_code(layout)
-    c, oh, ow = d.shape[1:] if lay == LAYOUT_CHW else (d.shape[3], d.shape[1], d.shape[2])
+    d, code, lay, n_dst, c, oh, ow = _batch_array(dst, dtype, layout)
     n_src = iw = ih = 0
     s = None
     if src is not None:
@@ -769,8 +761,8 @@ def compose_reference(src, dst, pieces, layout="chw", fill=None, keep=False, dty
         ih, iw = s.shape[2:] if lay == LAYOUT_CHW else s.shape[1:3]
     recs = compose_pieces(pieces)
     out = np.empty_like(d)
-    _check(_lib.load().llcomp_mi_compose_reference(s.ctypes.data if n_src else None, n_src, iw, ih, d.ctypes.data, d.shape[0], ow, oh, c, code, lay,
-                                                   recs, len(recs), _compose_fill(fill, c), COMPOSE_KEEP if keep else 0, out.ctypes.data))
+    _check(_lib.load().llcomp_mi_compose_reference(s.ctypes.data if n_src else None, n_src, iw, ih, d.ctypes.data, n_dst, ow, oh, c, code, lay,
+                                                   recs, len(recs), _per_channel(fill, c, "fill"), COMPOSE_KEEP if keep else 0, out.ctypes.data))
     return out
 
 
@@ -1780,7 +1772,7 @@ class Codec:
         """RandomErasing, MixUp and CutMix in place on a dense batch in device memory (llcomp_mi_codec_mix_batch): n samples of the
         codec's channels and ow x oh pixels in the dtype and layout a decode call wrote them in; samples from mix_samples(); erase_value:
         one value or one per channel (default zeros).  Asynchronous on `stream`; samples and erase_value are read during the call."""
-        ev = _mix_erase_value(erase_value, self.c)
+        ev = _per_channel(erase_value, self.c, "erase_value")
         _check(self._L.llcomp_mi_codec_mix_batch(self._h, d_batch, int(n), int(ow), int(oh), _dtype_code(dtype), _layout_code(layout),
                                                  _mix_records(samples, n), ev, stream))
 
@@ -1811,7 +1803,7 @@ class Codec:
         Asynchronous on `stream`, behind the decode that wrote d_src; pieces and fill are read during the call."""
         recs = compose_pieces(pieces)
         _check(self._L.llcomp_mi_codec_compose_batch(self._h, d_src, int(n_src), int(iw), int(ih), d_dst, int(n_dst), int(ow), int(oh),
-                                                     _dtype_code(dtype), _layout_code(layout), recs, len(recs), _compose_fill(fill, self.c),
+                                                     _dtype_code(dtype), _layout_code(layout), recs, len(recs), _per_channel(fill, self.c, "fill"),
                                                      COMPOSE_KEEP if keep else 0, stream))
 
     def compose_workspace_bytes(self, n_dst, n_pieces):

@@ -15,6 +15,7 @@
 #include "codec_internal.hpp"
 #include "container.hpp"
 #include "geometry.hpp"
+#include "batch_ops.hpp"
 #include "kernels.hpp"
 #include "mix.hpp"
 #include "compose.hpp"
@@ -387,6 +388,29 @@ int ensure_grown(llcomp_mi_codec* k, uint8_t*& p, uint64_t& cap, uint64_t bytes,
 
 // The staging buffer in HBM for `bytes` (bound: stage_bound, plus resized_tables_bound / views_tables_bound for a call with a resample tail)
 int ensure_stage(llcomp_mi_codec* k, uint64_t bytes, uint64_t bound) { return ensure_grown(k, k->d_stage, k->stage_cap, bytes, bound); }
+
+// A batch call's table on its way to the device (DESIGN.md "Batch calls: what the three share"): `tab` grown to `bytes` (at most
+// `bound`), a slot of the pinned ring, fill(slot) writes the table, ONE copy on s, the slot's event behind it, then launch(tab).  Nothing
+// is queued on s before every allocation has succeeded, the one of a second buffer of the call's included (`more`, grown to
+// more_bytes behind the table: the mixing's saved heads; 0: none).
+template <class Fill, class Launch>
+int batch_table_call(llcomp_mi_codec* k, uint8_t*& tab, uint64_t& cap, uint64_t bytes, uint64_t bound, hipStream_t s, Fill&& fill, Launch&& launch,
+                     uint8_t** more = nullptr, uint64_t* more_cap = nullptr, uint64_t more_bytes = 0) {
+    DeviceGuard guard(k->device);
+    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
+    if (int rc = ensure_regions_ring(k)) return rc;
+    if (int rc = ensure_grown(k, tab, cap, bytes, bound)) return rc;
+    if (more_bytes)
+        if (int rc = ensure_grown(k, *more, *more_cap, more_bytes, more_bytes)) return rc;
+    uint32_t slot = 0;
+    if (int rc = regions_slot_take(k, bytes, bound, slot)) return rc;
+    fill(k->h_regions[slot]);
+    DoneGuard done_guard{k, s};
+    HIP_TRY(hipMemcpyAsync(tab, k->h_regions[slot], bytes, hipMemcpyHostToDevice, s));
+    if (int rc = regions_slot_queued(k, slot, s)) return rc;
+    HIP_TRY(launch(tab));
+    return LLCOMP_MI_OK;
+}
 
 // The decode chain on geometry `sub` -- the codec's own, or the sub-geometry of a region, a box or a class -- in order on `s`: a state
 // generation of its own (a sub-geometry maps slices to lane groups differently, and the tagged tables are shared with the full decodes);
@@ -1501,77 +1525,60 @@ uint64_t llcomp_mi_codec_photo_perspective_workspace_bytes(const llcomp_mi_codec
     return llcomp_mi_codec_photo_workspace_bytes(k, total_views) + persp_tables_bound(k->g, total_views) - warp_tables_bound(k->g, total_views);
 }
 
-// Batch mixing (DESIGN.md "Batch mixing"): every refusal first (mix_check_call), then the plan, the table through a slot of the pinned
-// ring into d_mix_tab in one copy, the heads of the segments of cut cycles into d_mix (k_mix_save), and k_mix, all on the caller's stream.
+// The batch calls (DESIGN.md "Batch calls: what the three share"): every refusal first (the call's *_check_call), then the plan, then
+// batch_table_call with the call's own table buffer, all on the caller's stream.
+//
+// Batch mixing (DESIGN.md "Batch mixing"): the heads of the segments of cut cycles go into d_mix (k_mix_save) ahead of k_mix.
 int llcomp_mi_codec_mix_batch(llcomp_mi_codec* k, void* d_batch, uint32_t n, uint32_t ow, uint32_t oh, uint32_t dtype, uint32_t layout,
                               const llcomp_mi_mix_sample* samples, const float* erase_value, void* stream) {
     if (!k || !d_batch || !samples) return LLCOMP_MI_BAD_ARGS;
     const uint32_t c = k->g.c;
     std::vector<uint32_t> erase_bits;
     if (int rc = mix_check_call(n, c, ow, oh, dtype, layout, samples, erase_value, erase_bits)) return rc;
-    const uint32_t esize = dtype == LLCOMP_MI_DTYPE_U8 ? 1u : dtype == LLCOMP_MI_DTYPE_F32 ? 4u : 2u;
-    if (misaligned(d_batch, esize)) return LLCOMP_MI_BAD_ARGS;
+    if (misaligned(d_batch, batch_esize(dtype))) return LLCOMP_MI_BAD_ARGS;
     MixPlan p;
     mix_plan(n, samples, p);
-    const MixTable t(n, p.segs.size(), c);
-    const uint64_t saved_bytes = p.n_saved * mix_slot_stride(uint64_t(c) * ow * oh * esize);
-    DeviceGuard guard(k->device);
-    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
-    if (int rc = ensure_regions_ring(k)) return rc;
-    if (int rc = ensure_grown(k, k->d_mix_tab, k->mix_tab_cap, t.bytes, mix_table_bound(n, c))) return rc;
-    if (saved_bytes)
-        if (int rc = ensure_grown(k, k->d_mix, k->mix_cap, saved_bytes, saved_bytes)) return rc;
-    uint32_t slot = 0;
-    if (int rc = regions_slot_take(k, t.bytes, mix_table_bound(n, c), slot)) return rc;
-    mix_table_put(n, samples, p, erase_bits, k->h_regions[slot]);
+    const uint64_t saved_bytes = p.n_saved * mix_slot_stride(uint64_t(c) * ow * oh * batch_esize(dtype));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    DoneGuard done_guard{k, s};
-    HIP_TRY(hipMemcpyAsync(k->d_mix_tab, k->h_regions[slot], t.bytes, hipMemcpyHostToDevice, s));
-    if (int rc = regions_slot_queued(k, slot, s)) return rc;
-    MixLaunch m{};
-    m.d_batch = static_cast<uint8_t*>(d_batch), m.d_saved = saved_bytes ? k->d_mix : nullptr, m.d_table = k->d_mix_tab;
-    m.n = n, m.c = c, m.ow = ow, m.oh = oh, m.dtype = dtype, m.layout = layout;
-    m.n_segments = uint32_t(p.segs.size()), m.n_saved = p.n_saved;
-    HIP_TRY(launch_mix(m, s));
-    return LLCOMP_MI_OK;
+    return batch_table_call(
+        k, k->d_mix_tab, k->mix_tab_cap, MixTable(n, p.segs.size(), c).bytes, mix_table_bound(n, c), s,
+        [&](uint8_t* at) { mix_table_put(n, samples, p, erase_bits, at); },
+        [&](const uint8_t* d_table) {
+            MixLaunch m{};
+            m.d_batch = static_cast<uint8_t*>(d_batch), m.d_saved = saved_bytes ? k->d_mix : nullptr, m.d_table = d_table;
+            m.n = n, m.c = c, m.ow = ow, m.oh = oh, m.dtype = dtype, m.layout = layout;
+            m.n_segments = uint32_t(p.segs.size()), m.n_saved = p.n_saved;
+            return launch_mix(m, s);
+        },
+        &k->d_mix, &k->mix_cap, saved_bytes);
 }
 
 uint64_t llcomp_mi_codec_mix_workspace_bytes(const llcomp_mi_codec* k, uint32_t n, uint32_t ow, uint32_t oh, uint32_t dtype) {
-    const uint64_t esize = dtype == LLCOMP_MI_DTYPE_U8 ? 1u : dtype == LLCOMP_MI_DTYPE_F32 ? 4u : (dtype == LLCOMP_MI_DTYPE_F16 || dtype == LLCOMP_MI_DTYPE_BF16) ? 2u : 0u;
-    if (!k || !esize) return 0;
-    return k->workspace_bytes + mix_table_bound(n, k->g.c) + mix_saved_bound(n) * mix_slot_stride(uint64_t(k->g.c) * ow * oh * esize);
+    if (!k || !batch_esize(dtype)) return 0;
+    return k->workspace_bytes + mix_table_bound(n, k->g.c) + mix_saved_bound(n) * mix_slot_stride(uint64_t(k->g.c) * ow * oh * batch_esize(dtype));
 }
 
-// Batch orientation (DESIGN.md "Batch orientation"): every refusal first (orient_check_call), then the table of the oriented samples
-// through a slot of the pinned ring into d_orient_tab in one copy, and k_orient, all on the caller's stream.  Codes that are all 0:
-// nothing is queued.
+// Batch orientation (DESIGN.md "Batch orientation"): the table holds the oriented samples.  Codes that are all 0: nothing is queued.
 int llcomp_mi_codec_orient_batch(llcomp_mi_codec* k, void* d_batch, uint32_t n, uint32_t ow, uint32_t oh, uint32_t dtype, uint32_t layout,
                                  const uint8_t* codes, void* stream) {
     if (!k || !d_batch || !codes) return LLCOMP_MI_BAD_ARGS;
     const uint32_t c = k->g.c;
     if (int rc = orient_check_call(n, c, ow, oh, dtype, layout, codes)) return rc;
-    if (misaligned(d_batch, orient_esize(dtype))) return LLCOMP_MI_BAD_ARGS;
+    if (misaligned(d_batch, batch_esize(dtype))) return LLCOMP_MI_BAD_ARGS;
     std::vector<OrientEntry> table;
     orient_table(n, codes, table);
     if (table.empty()) return LLCOMP_MI_OK;
     const uint64_t bytes = table.size() * sizeof(OrientEntry);
-    DeviceGuard guard(k->device);
-    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
-    if (int rc = ensure_regions_ring(k)) return rc;
-    if (int rc = ensure_grown(k, k->d_orient_tab, k->orient_tab_cap, bytes, orient_table_bound(n))) return rc;
-    uint32_t slot = 0;
-    if (int rc = regions_slot_take(k, bytes, orient_table_bound(n), slot)) return rc;
-    std::memcpy(k->h_regions[slot], table.data(), bytes);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    DoneGuard done_guard{k, s};
-    HIP_TRY(hipMemcpyAsync(k->d_orient_tab, k->h_regions[slot], bytes, hipMemcpyHostToDevice, s));
-    if (int rc = regions_slot_queued(k, slot, s)) return rc;
-    OrientLaunch o{};
-    o.d_batch = static_cast<uint8_t*>(d_batch), o.d_table = k->d_orient_tab, o.n_entries = uint32_t(table.size());
-    for (const OrientEntry& e : table) o.code_set |= 1u << e.code;
-    o.c = c, o.ow = ow, o.oh = oh, o.dtype = dtype, o.layout = layout;
-    HIP_TRY(launch_orient(o, s));
-    return LLCOMP_MI_OK;
+    return batch_table_call(
+        k, k->d_orient_tab, k->orient_tab_cap, bytes, orient_table_bound(n), s, [&](uint8_t* at) { std::memcpy(at, table.data(), bytes); },
+        [&](const uint8_t* d_table) {
+            OrientLaunch o{};
+            o.d_batch = static_cast<uint8_t*>(d_batch), o.d_table = d_table, o.n_entries = uint32_t(table.size());
+            for (const OrientEntry& e : table) o.code_set |= 1u << e.code;
+            o.c = c, o.ow = ow, o.oh = oh, o.dtype = dtype, o.layout = layout;
+            return launch_orient(o, s);
+        });
 }
 
 uint64_t llcomp_mi_codec_orient_workspace_bytes(const llcomp_mi_codec* k, uint32_t n) {
@@ -1579,9 +1586,8 @@ uint64_t llcomp_mi_codec_orient_workspace_bytes(const llcomp_mi_codec* k, uint32
     return k->workspace_bytes + orient_table_bound(n);
 }
 
-// Batch composition (DESIGN.md "Batch composition"): every refusal first (compose_check_call, compose_check_memory), then the plan, the
-// table through a slot of the pinned ring into d_compose_tab in one copy, and k_compose, all on the caller's stream.  Under KEEP a call
-// without a piece of w and h above 0 queues nothing.
+// Batch composition (DESIGN.md "Batch composition"): compose_check_memory refuses too.  Under KEEP a call without a piece of w and h
+// above 0 queues nothing.
 int llcomp_mi_codec_compose_batch(llcomp_mi_codec* k, const void* d_src, uint32_t n_src, uint32_t iw, uint32_t ih, void* d_dst, uint32_t n_dst,
                                   uint32_t ow, uint32_t oh, uint32_t dtype, uint32_t layout, const llcomp_mi_compose_piece* pieces,
                                   uint32_t n_pieces, const float* fill_value, uint32_t flags, void* stream) {
@@ -1589,31 +1595,23 @@ int llcomp_mi_codec_compose_batch(llcomp_mi_codec* k, const void* d_src, uint32_
     const uint32_t c = k->g.c;
     std::vector<uint32_t> fill_bits;
     if (int rc = compose_check_call(n_src, iw, ih, n_dst, ow, oh, c, dtype, layout, pieces, n_pieces, fill_value, flags, fill_bits)) return rc;
-    const uint32_t esize = compose_esize(dtype);
+    const uint32_t esize = batch_esize(dtype);
     if (int rc = compose_check_memory(d_src, uint64_t(n_src) * c * iw * ih * esize, d_dst, uint64_t(n_dst) * c * ow * oh * esize, esize)) return rc;
     ComposePlan p;
     compose_plan(n_dst, pieces, n_pieces, flags, p);
     if (p.samples.empty()) return LLCOMP_MI_OK;
-    const ComposeTable t(p.samples.size(), p.order.size(), c);
-    const uint64_t bound = compose_table_bound(n_dst, n_pieces, c);
-    DeviceGuard guard(k->device);
-    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
-    if (int rc = ensure_regions_ring(k)) return rc;
-    if (int rc = ensure_grown(k, k->d_compose_tab, k->compose_tab_cap, t.bytes, bound)) return rc;
-    uint32_t slot = 0;
-    if (int rc = regions_slot_take(k, t.bytes, bound, slot)) return rc;
-    compose_table_put(pieces, p, fill_bits, layout, k->h_regions[slot]);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    DoneGuard done_guard{k, s};
-    HIP_TRY(hipMemcpyAsync(k->d_compose_tab, k->h_regions[slot], t.bytes, hipMemcpyHostToDevice, s));
-    if (int rc = regions_slot_queued(k, slot, s)) return rc;
-    ComposeLaunch o{};
-    o.d_src = n_src ? static_cast<const uint8_t*>(d_src) : nullptr, o.d_dst = static_cast<uint8_t*>(d_dst), o.d_table = k->d_compose_tab;
-    o.n_samples = uint32_t(p.samples.size()), o.n_recs = uint32_t(p.order.size());
-    o.n_src = n_src, o.iw = iw, o.ih = ih, o.ow = ow, o.oh = oh, o.c = c, o.dtype = dtype, o.layout = layout;
-    o.keep = flags & LLCOMP_MI_COMPOSE_KEEP;
-    HIP_TRY(launch_compose(o, s));
-    return LLCOMP_MI_OK;
+    return batch_table_call(
+        k, k->d_compose_tab, k->compose_tab_cap, ComposeTable(p.samples.size(), p.order.size(), c).bytes, compose_table_bound(n_dst, n_pieces, c), s,
+        [&](uint8_t* at) { compose_table_put(pieces, p, fill_bits, layout, at); },
+        [&](const uint8_t* d_table) {
+            ComposeLaunch o{};
+            o.d_src = n_src ? static_cast<const uint8_t*>(d_src) : nullptr, o.d_dst = static_cast<uint8_t*>(d_dst), o.d_table = d_table;
+            o.n_samples = uint32_t(p.samples.size()), o.n_recs = uint32_t(p.order.size());
+            o.n_src = n_src, o.iw = iw, o.ih = ih, o.ow = ow, o.oh = oh, o.c = c, o.dtype = dtype, o.layout = layout;
+            o.keep = flags & LLCOMP_MI_COMPOSE_KEEP;
+            return launch_compose(o, s);
+        });
 }
 
 uint64_t llcomp_mi_codec_compose_workspace_bytes(const llcomp_mi_codec* k, uint32_t n_dst, uint32_t n_pieces) {

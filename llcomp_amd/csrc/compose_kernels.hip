@@ -1,7 +1,7 @@
 // compose_kernels.hip -- the batch composition on the GPU (include/llcomp_mi.h: "Batch composition"; DESIGN.md "Batch composition"):
 // rectangles of a src batch into a dst batch, the rest a fill or kept, in ONE kernel with no scratch in device memory.  The rule, the
 // address functions, the units a tile owns and what a thread does with one unit (compose_decide, compose_finish: the shifted copy) are compose_rule.hpp's,
-// the functions the host check walks without a GPU; the table is compose_plan.hpp's.
+// the functions the host check walks without a GPU; the table is compose_plan.hpp's, the 16-byte chunk batch_chunk.hpp's.
 //
 // A workgroup owns one tile of one plane of one dst sample (blockIdx.z: an entry of the table's samples, so the sample and its run of
 // pieces are the same in every thread and the records are read through uniform addresses).  Its first wavefront filters the sample's
@@ -14,6 +14,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "batch_chunk.hpp"
 #include "compose_rule.hpp"
 
 namespace llcomp_mi {
@@ -32,22 +33,16 @@ struct ComposeArgs {
     const uint32_t* fill;
 };
 
-typedef uint32_t Vec4 __attribute__((ext_vector_type(4)));
-template <uint32_t ES> struct ComposeElem;
-template <> struct ComposeElem<1> { using T = uint8_t; };
-template <> struct ComposeElem<2> { using T = uint16_t; };
-template <> struct ComposeElem<4> { using T = uint32_t; };
-
 // the memory of compose_rule.hpp's functions: global memory as it is
 template <uint32_t ES>
 struct DeviceMem {
-    using T = typename ComposeElem<ES>::T;
+    using T = typename ElemOf<ES>::T;
     __device__ __forceinline__ ComposeChunk load16(uint64_t a) const {
-        const Vec4 v = *reinterpret_cast<const Vec4*>(__builtin_assume_aligned(reinterpret_cast<const void*>(a), 16));
+        const Chunk v = *reinterpret_cast<const Chunk*>(__builtin_assume_aligned(reinterpret_cast<const void*>(a), 16));
         return ComposeChunk{{v[0], v[1], v[2], v[3]}};
     }
     __device__ __forceinline__ void store16(uint64_t a, const ComposeChunk& c) const {
-        *reinterpret_cast<Vec4*>(__builtin_assume_aligned(reinterpret_cast<void*>(a), 16)) = Vec4{c.w[0], c.w[1], c.w[2], c.w[3]};
+        *reinterpret_cast<Chunk*>(__builtin_assume_aligned(reinterpret_cast<void*>(a), 16)) = Chunk{c.w[0], c.w[1], c.w[2], c.w[3]};
     }
     __device__ __forceinline__ uint32_t load_el(uint64_t a) const { return *reinterpret_cast<const T*>(a); }
     __device__ __forceinline__ void store_el(uint64_t a, uint32_t bits) const { *reinterpret_cast<T*>(a) = T(bits); }
@@ -102,7 +97,7 @@ __global__ __launch_bounds__(kComposeThreads) void k_compose(ComposeArgs a) {
 }  // namespace
 
 hipError_t launch_compose(const ComposeLaunch& o, hipStream_t stream) {
-    const uint32_t es = compose_esize(o.dtype);
+    const uint32_t es = batch_esize(o.dtype);
     const ComposeTable t(o.n_samples, o.n_recs, o.c);
     ComposeArgs a{};
     a.g = compose_geom(reinterpret_cast<uintptr_t>(o.d_dst), reinterpret_cast<uintptr_t>(o.d_src), o.n_src, o.iw, o.ih, o.ow, o.oh, o.c, es,

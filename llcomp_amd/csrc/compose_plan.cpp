@@ -12,14 +12,12 @@ static_assert(sizeof(llcomp_mi_compose_piece) == 40 && sizeof(ComposeRec) == 32 
 int compose_check_call(uint32_t n_src, uint32_t iw, uint32_t ih, uint32_t n_dst, uint32_t ow, uint32_t oh, uint32_t c, uint32_t dtype, uint32_t layout,
                        const llcomp_mi_compose_piece* pieces, uint32_t n_pieces, const float* fill_value, uint32_t flags,
                        std::vector<uint32_t>& fill_bits) {
-    const uint32_t es = compose_esize(dtype);
-    if (!es || (layout != LLCOMP_MI_LAYOUT_HWC && layout != LLCOMP_MI_LAYOUT_CHW)) return LLCOMP_MI_BAD_ARGS;
-    if (!n_dst || n_dst > kComposeMaxSamples || n_src > kComposeMaxSamples || n_pieces > kComposeMaxPieces) return LLCOMP_MI_BAD_ARGS;
-    if (!c || !ow || !oh || (n_src && (!iw || !ih)) || (n_pieces && !pieces) || (flags & ~LLCOMP_MI_COMPOSE_KEEP)) return LLCOMP_MI_BAD_ARGS;
-    const uint32_t cs = layout == LLCOMP_MI_LAYOUT_CHW ? 1u : c;
+    if (int rc = batch_check_shape(n_dst, c, ow, oh, dtype, layout)) return rc;
+    if (n_src)  // (no src batch is fine: FILL pieces only)
+        if (int rc = batch_check_shape(n_src, c, iw, ih, dtype, layout)) return rc;
+    if (n_pieces > kComposeMaxPieces || (n_pieces && !pieces) || (flags & ~LLCOMP_MI_COMPOSE_KEEP)) return LLCOMP_MI_BAD_ARGS;
+    const uint32_t es = batch_esize(dtype), cs = layout == LLCOMP_MI_LAYOUT_CHW ? 1u : c;
     if (uint64_t(ow) * cs >= (1ull << 31) || (n_src && uint64_t(iw) * cs >= (1ull << 31))) return LLCOMP_MI_BAD_ARGS;
-    if (((static_cast<unsigned __int128>(c) * ow * oh * es * n_dst) >> 62) != 0) return LLCOMP_MI_BAD_ARGS;  // (no address space holds it)
-    if (n_src && ((static_cast<unsigned __int128>(c) * iw * ih * es * n_src) >> 62) != 0) return LLCOMP_MI_BAD_ARGS;
     const ComposeGeom g = compose_geom(0, 0, 0, 0, 0, ow, oh, c, es, cs == 1, false);
     if (g.planes > 65535u || uint64_t(g.tiles_x) * g.tiles_y > 0x7FFFFFFFu) return LLCOMP_MI_BAD_ARGS;  // (the kernel's grid)
     std::vector<uint32_t> on_sample(n_dst, 0u);
@@ -34,11 +32,7 @@ int compose_check_call(uint32_t n_src, uint32_t iw, uint32_t ih, uint32_t n_dst,
         }
         if (!compose_empty(p) && ++on_sample[p.dst] > kComposeMaxPiecesPerSample) return LLCOMP_MI_BAD_ARGS;
     }
-    std::vector<uint32_t> bits(c, 0u);
-    for (uint32_t ch = 0; ch < c; ++ch)
-        if (!mix_erase_bits(dtype, fill_value ? fill_value[ch] : 0.0f, bits[ch])) return LLCOMP_MI_BAD_ARGS;
-    fill_bits.swap(bits);
-    return LLCOMP_MI_OK;
+    return batch_value_bits(dtype, c, fill_value, fill_bits);
 }
 
 int compose_check_memory(const void* src, uint64_t src_bytes, const void* dst, uint64_t dst_bytes, uint32_t esize) {
@@ -67,7 +61,7 @@ void compose_plan(uint32_t n_dst, const llcomp_mi_compose_piece* pieces, uint32_
 
 uint64_t compose_workgroups(const ComposePlan& p, uint32_t ow, uint32_t oh, uint32_t c, uint32_t dtype, uint32_t layout) {
     const bool chw = layout == LLCOMP_MI_LAYOUT_CHW;
-    const ComposeGeom g = compose_geom(0, 0, 0, 0, 0, ow, oh, c, compose_esize(dtype), chw, false);
+    const ComposeGeom g = compose_geom(0, 0, 0, 0, 0, ow, oh, c, batch_esize(dtype), chw, false);
     return uint64_t(p.samples.size()) * g.planes * g.tiles_x * g.tiles_y;
 }
 
@@ -88,7 +82,7 @@ int compose_reference(const void* src, uint32_t n_src, uint32_t iw, uint32_t ih,
     std::vector<uint32_t> fill;
     if (int rc = compose_check_call(n_src, iw, ih, n_dst, ow, oh, c, dtype, layout, pieces, n_pieces, fill_value, flags, fill)) return rc;
     const bool keep = flags & LLCOMP_MI_COMPOSE_KEEP, chw = layout == LLCOMP_MI_LAYOUT_CHW;
-    const uint32_t es = compose_esize(dtype);
+    const uint32_t es = batch_esize(dtype);
     const uint64_t dst_bytes = uint64_t(n_dst) * c * ow * oh * es;
     if (keep && !dst_in) return LLCOMP_MI_BAD_ARGS;
     if (int rc = compose_check_memory(src, uint64_t(n_src) * c * iw * ih * es, out, dst_bytes, es)) return rc;

@@ -7,10 +7,12 @@
 // of one plane of one dst sample, compose_tile_rows rows by kComposeTile pixels, and takes the tile's rows in the 16-byte units of dst
 // MEMORY they lie in: a unit that straddles the border of two tiles of a row belongs to the tile that holds the unit's first element
 // of the row, whole, so every (row, unit) has one owner and one thread (compose_row_units, compose_decide, compose_finish).
+// The element's size and the shape of a batch: batch_ops.hpp (through mix_rule.hpp); an element's place in a unit: batch_chunk.hpp.
 #pragma once
 #include <cstdint>
 
 #include "../../include/llcomp_mi.h"
+#include "batch_chunk.hpp"
 #include "mix_rule.hpp"
 
 #if defined(__clang__)
@@ -22,7 +24,6 @@
 namespace llcomp_mi {
 
 constexpr uint32_t kComposeTile = 128;                // pixels across a tile (llcomp_mi_compose_tile)
-constexpr uint32_t kComposeMaxSamples = 65535;        // of either batch (a dst sample is a layer of the kernel's grid)
 constexpr uint32_t kComposeMaxPieces = 1u << 20;      // of a call
 constexpr uint32_t kComposeMaxPiecesPerSample = 1024; // with w and h above 0 on one dst sample (llcomp_mi_compose_max_pieces_per_sample)
 constexpr uint32_t kComposeListCap = 256;             // pieces of a workgroup's short list in LDS; a sample with more resolves against its whole run
@@ -35,7 +36,6 @@ LLMI_HD constexpr uint32_t compose_tile_rows(uint32_t pixel_bytes) {
     while (r > 1 && uint64_t(kComposeTile) * r * pixel_bytes > 16384u) r /= 2;
     return r;
 }
-LLMI_HD inline uint32_t compose_esize(uint32_t dtype) { return mix_esize(dtype); }
 
 // (x, y) of a dst sample lies in the piece's rectangle
 LLMI_HD inline bool compose_covers(const llcomp_mi_compose_piece& p, uint32_t x, uint32_t y) { return x - p.dx < p.w && y - p.dy < p.h; }
@@ -126,7 +126,7 @@ LLMI_HD inline int32_t compose_resolve(const ComposeRec* list, uint32_t n, uint3
     return -1;
 }
 
-// 16 bytes
+// 16 bytes, for the host check as for the kernel; an element's word and shift in w: batch_chunk.hpp (chunk_or, chunk_get)
 struct ComposeChunk {
     uint32_t w[4];
 };
@@ -147,19 +147,13 @@ LLMI_HD inline ComposeChunk compose_shift(const ComposeChunk& lo, const ComposeC
     return ComposeChunk{{compose_alignbyte(w[1], w[0], r), compose_alignbyte(w[2], w[1], r), compose_alignbyte(w[3], w[2], r),
                          compose_alignbyte(w[4], w[3], r)}};
 }
-template <uint32_t ES>
-LLMI_HD inline void compose_chunk_or(ComposeChunk& v, uint32_t e, uint32_t bits) {  // (into a chunk of zeros)
-    if constexpr (ES == 4) v.w[e] = bits;
-    else if constexpr (ES == 2) v.w[e >> 1] |= bits << (16 * (e & 1));
-    else v.w[e >> 2] |= bits << (8 * (e & 3));
-}
 // The fill pattern of phase ph: the unit's element e is of channel (ph + e) % cmod.  fill: the channels' values in the dtype, from the
 // plane's own on in CHW (cmod 1)
 template <uint32_t ES>
 LLMI_HD inline ComposeChunk compose_pattern(const uint32_t* fill, uint32_t cmod, uint32_t ph) {
     ComposeChunk v{{0u, 0u, 0u, 0u}};
     for (uint32_t e = 0; e < 16 / ES; ++e) {
-        compose_chunk_or<ES>(v, e, fill[ph]);
+        chunk_or<ES>(v.w, e, fill[ph]);
         if (++ph >= cmod) ph = 0;
     }
     return v;
@@ -195,12 +189,6 @@ LLMI_HD inline ComposeChunk compose_merge(const ComposeChunk& acc, const Compose
         o.w[d] = (acc.w[d] & ~bytes) | (v.w[d] & bytes);
     }
     return o;
-}
-template <uint32_t ES>
-LLMI_HD inline uint32_t compose_chunk_get(const ComposeChunk& v, uint32_t e) {
-    if constexpr (ES == 4) return v.w[e];
-    else if constexpr (ES == 2) return (v.w[e >> 1] >> (16 * (e & 1))) & 0xFFFFu;
-    else return (v.w[e >> 2] >> (8 * (e & 3))) & 0xFFu;
 }
 // the fill pattern of a unit whose element 0 is the row's element eu (below 0: in front of the row)
 template <uint32_t ES>
@@ -285,7 +273,7 @@ LLMI_HD inline void compose_finish(const ComposeGeom& g, const ComposeWork& k, c
             } else {  // at the first or the last bytes of the src batch: the elements that belong, one by one
                 LLMI_UNROLL
                 for (uint32_t p = 0; p < PER; ++p)
-                    if ((m >> p) & 1u) compose_chunk_or<ES>(v, p, mem.load_el(s + uint64_t(p) * ES));
+                    if ((m >> p) & 1u) chunk_or<ES>(v.w, p, mem.load_el(s + uint64_t(p) * ES));
             }
         }
         acc = compose_merge<ES>(acc, v, m);
@@ -298,7 +286,7 @@ LLMI_HD inline void compose_finish(const ComposeGeom& g, const ComposeWork& k, c
     if (claimed == (1u << PER) - 1u) return mem.store16(t.u, acc);
     LLMI_UNROLL
     for (uint32_t p = 0; p < PER; ++p)
-        if ((claimed >> p) & 1u) mem.store_el(t.u + uint64_t(p) * ES, compose_chunk_get<ES>(acc, p));
+        if ((claimed >> p) & 1u) mem.store_el(t.u + uint64_t(p) * ES, chunk_get<ES>(acc.w, p));
 }
 
 // One tile's rows and units, thread `tid` of `threads`: what the kernel's threads do behind the filter's barrier.  A thread decides

@@ -1,35 +1,18 @@
 // mix_kernels.hip -- the batch mixing on the GPU (include/llcomp_mi.h: "Batch mixing"; DESIGN.md "Batch mixing"): RandomErasing, MixUp and
 // CutMix in place on a dense batch, one read and one write per element at most.  The rule is mix_rule.hpp's, the functions
-// llcomp_mi_mix_reference is compiled from; what the host decides -- the segments, the saved heads, the table -- is mix_plan.hpp's.
+// llcomp_mi_mix_reference is compiled from; what the host decides -- the segments, the saved heads, the table -- is mix_plan.hpp's; the
+// 16-byte chunk is batch_chunk.hpp's.
 #include "mix.hpp"
 
 #include <hip/hip_runtime.h>
 
+#include "batch_chunk.hpp"
 #include "mix_rule.hpp"
 
 namespace llcomp_mi {
 namespace {
 
 constexpr uint32_t kMixThreads = 256;
-
-// Sixteen bytes of a sample: PER = 16 / ES elements, element e in word e * ES / 4
-typedef uint32_t Chunk __attribute__((ext_vector_type(4)));
-template <uint32_t ES>
-__device__ __forceinline__ uint32_t chunk_get(const Chunk& v, uint32_t e) {
-    if constexpr (ES == 4) return v[e];
-    else if constexpr (ES == 2) return (v[e >> 1] >> (16 * (e & 1))) & 0xFFFFu;
-    else return (v[e >> 2] >> (8 * (e & 3))) & 0xFFu;
-}
-template <uint32_t ES>
-__device__ __forceinline__ void chunk_set(Chunk& v, uint32_t e, uint32_t bits) {
-    if constexpr (ES == 4) v[e] = bits;
-    else if constexpr (ES == 2) v[e >> 1] = (v[e >> 1] & ~(0xFFFFu << (16 * (e & 1)))) | (bits << (16 * (e & 1)));
-    else v[e >> 2] = (v[e >> 2] & ~(0xFFu << (8 * (e & 3)))) | (bits << (8 * (e & 3)));
-}
-template <uint32_t ES> struct ElemOf;
-template <> struct ElemOf<1> { using T = uint8_t; };
-template <> struct ElemOf<2> { using T = uint16_t; };
-template <> struct ElemOf<4> { using T = uint32_t; };
 
 // The chunk at p: one 16-byte access where it is whole and aligned (vec); otherwise its elements `mask`, one by one (p itself may lie
 // outside the sample: the elements outside the mask are never touched)
@@ -88,7 +71,7 @@ __global__ __launch_bounds__(kMixThreads) void k_mix(uint8_t* __restrict__ batch
                                                     const MixSeg* __restrict__ segs, const uint32_t* __restrict__ erase_bits, uint64_t el,
                                                     uint64_t n_chunks, uint64_t slot_stride, uint32_t lead, uint32_t vec_ok, uint32_t c, uint32_t ow,
                                                     uint32_t oh) {
-    constexpr uint32_t ES = DT == LLCOMP_MI_DTYPE_U8 ? 1u : DT == LLCOMP_MI_DTYPE_F32 ? 4u : 2u, PER = 16 / ES, ALL = (1u << PER) - 1u;
+    constexpr uint32_t ES = batch_esize(DT), PER = 16 / ES, ALL = (1u << PER) - 1u;
     const uint64_t k = uint64_t(blockIdx.x) * kMixThreads + threadIdx.x;
     if (k >= n_chunks) return;
     const MixSeg seg = segs[blockIdx.y];
@@ -174,7 +157,7 @@ __global__ __launch_bounds__(kMixThreads) void k_mix(uint8_t* __restrict__ batch
 
 template <uint32_t DT, bool CHW>
 hipError_t launch_one(const MixLaunch& m, hipStream_t stream) {
-    const uint32_t es = mix_esize(DT), per = 16 / es;
+    constexpr uint32_t es = batch_esize(DT), per = 16 / es;
     const uint64_t el = uint64_t(m.c) * m.ow * m.oh, sample_bytes = el * es;
     const MixTable t(m.n, m.n_segments, m.c);
     const MixSeg* segs = reinterpret_cast<const MixSeg*>(m.d_table + t.segs_at);
@@ -199,14 +182,10 @@ hipError_t launch_one(const MixLaunch& m, hipStream_t stream) {
 }  // namespace
 
 hipError_t launch_mix(const MixLaunch& m, hipStream_t stream) {
-    const bool chw = m.layout == LLCOMP_MI_LAYOUT_CHW;
-    switch (m.dtype) {
-        case LLCOMP_MI_DTYPE_U8: return chw ? launch_one<LLCOMP_MI_DTYPE_U8, true>(m, stream) : launch_one<LLCOMP_MI_DTYPE_U8, false>(m, stream);
-        case LLCOMP_MI_DTYPE_F32: return chw ? launch_one<LLCOMP_MI_DTYPE_F32, true>(m, stream) : launch_one<LLCOMP_MI_DTYPE_F32, false>(m, stream);
-        case LLCOMP_MI_DTYPE_F16: return chw ? launch_one<LLCOMP_MI_DTYPE_F16, true>(m, stream) : launch_one<LLCOMP_MI_DTYPE_F16, false>(m, stream);
-        case LLCOMP_MI_DTYPE_BF16: return chw ? launch_one<LLCOMP_MI_DTYPE_BF16, true>(m, stream) : launch_one<LLCOMP_MI_DTYPE_BF16, false>(m, stream);
-        default: return hipErrorInvalidValue;
-    }
+    hipError_t e = hipErrorInvalidValue;
+    batch_dispatch(m.dtype, m.layout == LLCOMP_MI_LAYOUT_CHW,
+                   [&](auto dt, auto chw) { e = launch_one<decltype(dt)::value, decltype(chw)::value>(m, stream); });
+    return e;
 }
 
 }  // namespace llcomp_mi

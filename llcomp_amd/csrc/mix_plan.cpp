@@ -9,7 +9,7 @@
 namespace llcomp_mi {
 
 int mix_check_records(uint32_t n, const llcomp_mi_mix_sample* samples) {
-    if (!samples || !n || n > kMixMaxSamples) return LLCOMP_MI_BAD_ARGS;
+    if (!samples || !n || n > kBatchMaxSamples) return LLCOMP_MI_BAD_ARGS;
     std::vector<uint8_t> taken(n, 0);
     for (uint32_t i = 0; i < n; ++i) {
         const llcomp_mi_mix_sample& s = samples[i];
@@ -23,19 +23,14 @@ int mix_check_records(uint32_t n, const llcomp_mi_mix_sample* samples) {
 
 int mix_check_call(uint32_t n, uint32_t c, uint32_t ow, uint32_t oh, uint32_t dtype, uint32_t layout, const llcomp_mi_mix_sample* samples,
                    const float* erase_value, std::vector<uint32_t>& erase_bits) {
-    if (!c || !ow || !oh || !mix_esize(dtype) || (layout != LLCOMP_MI_LAYOUT_HWC && layout != LLCOMP_MI_LAYOUT_CHW)) return LLCOMP_MI_BAD_ARGS;
+    if (int rc = batch_check_shape(n, c, ow, oh, dtype, layout)) return rc;
     if (int rc = mix_check_records(n, samples)) return rc;
-    if (((static_cast<unsigned __int128>(c) * ow * oh * mix_esize(dtype) * n) >> 62) != 0) return LLCOMP_MI_BAD_ARGS;  // (no address space holds it)
     for (uint32_t i = 0; i < n; ++i) {
         const llcomp_mi_mix_sample& s = samples[i];
         if (!mix_rect_ok(s.box, ow, oh) || !mix_rect_ok(s.erase, ow, oh)) return LLCOMP_MI_BAD_ARGS;
         if ((s.flags & LLCOMP_MI_MIX_BLEND) && dtype == LLCOMP_MI_DTYPE_U8) return LLCOMP_MI_BAD_ARGS;
     }
-    std::vector<uint32_t> bits(c, 0u);
-    for (uint32_t ch = 0; ch < c; ++ch)
-        if (!mix_erase_bits(dtype, erase_value ? erase_value[ch] : 0.0f, bits[ch])) return LLCOMP_MI_BAD_ARGS;
-    erase_bits.swap(bits);
-    return LLCOMP_MI_OK;
+    return batch_value_bits(dtype, c, erase_value, erase_bits);
 }
 
 void mix_plan(uint32_t n, const llcomp_mi_mix_sample* samples, MixPlan& p) {
@@ -87,7 +82,7 @@ inline void put_el(uint8_t* p, uint64_t e, uint32_t esize, uint32_t v) { std::me
 template <uint32_t DT, bool CHW>
 void reference_body(const uint8_t* src, uint8_t* out, uint32_t n, uint32_t c, uint32_t ow, uint32_t oh, const llcomp_mi_mix_sample* samples,
                     const uint32_t* ev) {
-    const uint32_t esize = mix_esize(DT);
+    const uint32_t esize = batch_esize(DT);
     const uint64_t el = uint64_t(c) * ow * oh;
     for (uint32_t i = 0; i < n; ++i) {
         const llcomp_mi_mix_sample& s = samples[i];
@@ -114,30 +109,14 @@ int mix_reference(const void* batch, uint32_t n, uint32_t c, uint32_t ow, uint32
     const uint8_t* src = static_cast<const uint8_t*>(batch);
     std::vector<uint8_t> before;
     if (out == batch) {  // every sample from the batch as it stands before the call: a copy of it
-        const uint64_t bytes = uint64_t(n) * c * ow * oh * mix_esize(dtype);
+        const uint64_t bytes = uint64_t(n) * c * ow * oh * batch_esize(dtype);
         before.assign(src, src + size_t(bytes));
         src = before.data();
     }
     uint8_t* o = static_cast<uint8_t*>(out);
-    const bool chw = layout == LLCOMP_MI_LAYOUT_CHW;
-    switch (dtype) {
-        case LLCOMP_MI_DTYPE_U8:
-            chw ? reference_body<LLCOMP_MI_DTYPE_U8, true>(src, o, n, c, ow, oh, samples, ev.data())
-                : reference_body<LLCOMP_MI_DTYPE_U8, false>(src, o, n, c, ow, oh, samples, ev.data());
-            break;
-        case LLCOMP_MI_DTYPE_F32:
-            chw ? reference_body<LLCOMP_MI_DTYPE_F32, true>(src, o, n, c, ow, oh, samples, ev.data())
-                : reference_body<LLCOMP_MI_DTYPE_F32, false>(src, o, n, c, ow, oh, samples, ev.data());
-            break;
-        case LLCOMP_MI_DTYPE_F16:
-            chw ? reference_body<LLCOMP_MI_DTYPE_F16, true>(src, o, n, c, ow, oh, samples, ev.data())
-                : reference_body<LLCOMP_MI_DTYPE_F16, false>(src, o, n, c, ow, oh, samples, ev.data());
-            break;
-        default:
-            chw ? reference_body<LLCOMP_MI_DTYPE_BF16, true>(src, o, n, c, ow, oh, samples, ev.data())
-                : reference_body<LLCOMP_MI_DTYPE_BF16, false>(src, o, n, c, ow, oh, samples, ev.data());
-            break;
-    }
+    batch_dispatch(dtype, layout == LLCOMP_MI_LAYOUT_CHW, [&](auto dt, auto chw) {
+        reference_body<decltype(dt)::value, decltype(chw)::value>(src, o, n, c, ow, oh, samples, ev.data());
+    });
     return LLCOMP_MI_OK;
 }
 

@@ -17,7 +17,6 @@ namespace llcomp_mi {
 #endif
 constexpr uint32_t kMixSegment = LLMI_MIX_SEGMENT;
 static_assert(kMixSegment >= 2, "a segment of one sample would save every sample of a cycle");
-constexpr uint32_t kMixMaxSamples = 65535;  // (a segment is a row of the kernel's grid)
 constexpr uint32_t kMixNoSlot = 0xFFFFFFFFu;
 
 // One segment: samples order[first .. first + count), each the partner of the one before it.  The partner of the LAST one is the head of
@@ -48,11 +47,11 @@ struct MixTable {
 };
 inline uint64_t mix_table_bound(uint64_t n, uint32_t c) { return MixTable(n, n, c).bytes; }
 
-// The records by themselves: BAD_ARGS for n = 0 or above kMixMaxSamples, a partner >= n, partners that are no permutation, flag bits
-// above 0, a weight that is not finite
+// The records by themselves: BAD_ARGS for n = 0 or above kBatchMaxSamples (batch_ops.hpp), a partner >= n, partners that are no
+// permutation, flag bits above 0, a weight that is not finite
 int mix_check_records(uint32_t n, const llcomp_mi_mix_sample* samples);
-// ... and a whole call: the shape, dtype and layout, the rectangles within ow x oh, BLEND on U8, and the erase values, which come back
-// in the dtype in erase_bits[c] (NULL erase_value: zeros)
+// ... and a whole call: the batch (batch_ops.hpp: batch_check_shape), the rectangles within ow x oh, BLEND on U8, and the erase values,
+// which come back in the dtype in erase_bits[c] (NULL erase_value: zeros)
 int mix_check_call(uint32_t n, uint32_t c, uint32_t ow, uint32_t oh, uint32_t dtype, uint32_t layout, const llcomp_mi_mix_sample* samples,
                    const float* erase_value, std::vector<uint32_t>& erase_bits);
 // The plan of checked records

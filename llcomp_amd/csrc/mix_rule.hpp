@@ -2,13 +2,14 @@
 // kernels (mix_kernels.hip) and into llcomp_mi_mix_reference and the planner's checks (mix_plan.cpp).  The rule is torch's on the CPU:
 // every product and the sum of a blend in IEEE binary32, each rounded by itself and then to the element's type, so nothing here may be
 // contracted into a fused multiply-add: hipcc does that on the device by default, and the pragma below switches it off for every file
-// that includes this header.
+// that includes this header.  The element's size and the shape of a batch: batch_ops.hpp.
 #pragma once
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
 #include "../../include/llcomp_mi.h"
-#include "geometry.hpp"
+#include "batch_ops.hpp"
 
 #if defined(__clang__)
 #pragma clang fp contract(off)
@@ -16,11 +17,6 @@
 // (g++ builds of the host checks target baseline x86-64, which has no fused multiply-add to contract into)
 
 namespace llcomp_mi {
-
-// The element's size in bytes, 0 for a dtype that is none
-LLMI_HD inline uint32_t mix_esize(uint32_t dtype) {
-    return dtype == LLCOMP_MI_DTYPE_U8 ? 1u : dtype == LLCOMP_MI_DTYPE_F32 ? 4u : (dtype == LLCOMP_MI_DTYPE_F16 || dtype == LLCOMP_MI_DTYPE_BF16) ? 2u : 0u;
-}
 
 LLMI_HD inline uint32_t mix_f32_bits(float f) {
     uint32_t u;
@@ -177,6 +173,15 @@ LLMI_HD inline bool mix_erase_bits(uint32_t dtype, float v, uint32_t& bits) {
         case LLCOMP_MI_DTYPE_BF16: bits = mix_round<LLCOMP_MI_DTYPE_BF16>(v); return true;
         default: return false;
     }
+}
+// ... and a call's value per channel (the mixing's erase value, the composition's fill; NULL: zeros) as bits[c] in the dtype; BAD_ARGS,
+// and bits as it was, for a value the dtype cannot take
+inline int batch_value_bits(uint32_t dtype, uint32_t c, const float* values, std::vector<uint32_t>& bits) {
+    std::vector<uint32_t> b(c, 0u);
+    for (uint32_t ch = 0; ch < c; ++ch)
+        if (!mix_erase_bits(dtype, values ? values[ch] : 0.0f, b[ch])) return LLCOMP_MI_BAD_ARGS;
+    bits.swap(b);
+    return LLCOMP_MI_OK;
 }
 
 }  // namespace llcomp_mi

@@ -1,7 +1,7 @@
 // orient_kernels.hip -- the batch orientation on the GPU (include/llcomp_mi.h: "Batch orientation"; DESIGN.md "Batch orientation"): flips,
 // quarter turns and transpositions per sample, in place on a dense batch with no scratch in device memory.  The rule, the fundamental
 // domains and the images of rectangles are orient_rule.hpp's, the functions llcomp_mi_orient_reference is compiled from; the table is
-// orient_plan.hpp's.
+// orient_plan.hpp's, the 16-byte chunk batch_chunk.hpp's.
 //
 // A workgroup owns one tile of its code's fundamental domain: kOrientTile pixels wide, orient_tile_rows() tall, clipped to the domain's
 // box; a pixel of the tile outside the domain (under a diagonal, right of the middle of a half turn's middle row) is masked out.  The
@@ -15,6 +15,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "batch_chunk.hpp"
 #include "orient_rule.hpp"
 
 namespace llcomp_mi {
@@ -64,24 +65,6 @@ struct OrientArgs {
     uint32_t pieces;   // pieces to a pixel
     uint32_t rows;     // of a tile
 };
-
-typedef uint32_t Chunk __attribute__((ext_vector_type(4)));
-template <uint32_t ES> struct ElemOf;
-template <> struct ElemOf<1> { using T = uint8_t; };
-template <> struct ElemOf<2> { using T = uint16_t; };
-template <> struct ElemOf<4> { using T = uint32_t; };
-template <uint32_t ES>
-__device__ __forceinline__ uint32_t chunk_get(const Chunk& v, uint32_t e) {
-    if constexpr (ES == 4) return v[e];
-    else if constexpr (ES == 2) return (v[e >> 1] >> (16 * (e & 1))) & 0xFFFFu;
-    else return (v[e >> 2] >> (8 * (e & 3))) & 0xFFu;
-}
-template <uint32_t ES>
-__device__ __forceinline__ void chunk_or(Chunk& v, uint32_t e, uint32_t bits) {  // (into a chunk of zeros)
-    if constexpr (ES == 4) v[e] = bits;
-    else if constexpr (ES == 2) v[e >> 1] |= bits << (16 * (e & 1));
-    else v[e >> 2] |= bits << (8 * (e & 3));
-}
 
 // What a workgroup knows of its tile, the same in every thread
 struct OrientTile {
@@ -251,7 +234,7 @@ uint64_t orient_grid_tiles(uint32_t code_set, uint32_t ow, uint32_t oh, uint32_t
 }  // namespace
 
 hipError_t launch_orient(const OrientLaunch& o, hipStream_t stream) {
-    const uint32_t es = orient_esize(o.dtype);
+    const uint32_t es = batch_esize(o.dtype);
     const bool chw = o.layout == LLCOMP_MI_LAYOUT_CHW;
     OrientArgs a{};
     a.batch = o.d_batch, a.table = reinterpret_cast<const OrientEntry*>(o.d_table);

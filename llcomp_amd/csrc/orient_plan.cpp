@@ -8,9 +8,8 @@
 namespace llcomp_mi {
 
 int orient_check_call(uint32_t n, uint32_t c, uint32_t ow, uint32_t oh, uint32_t dtype, uint32_t layout, const uint8_t* codes) {
-    if (!codes || !n || n > kOrientMaxSamples || !c || !ow || !oh || !orient_esize(dtype)) return LLCOMP_MI_BAD_ARGS;
-    if (layout != LLCOMP_MI_LAYOUT_HWC && layout != LLCOMP_MI_LAYOUT_CHW) return LLCOMP_MI_BAD_ARGS;
-    if (((static_cast<unsigned __int128>(c) * ow * oh * orient_esize(dtype) * n) >> 62) != 0) return LLCOMP_MI_BAD_ARGS;  // (no address space holds it)
+    if (!codes) return LLCOMP_MI_BAD_ARGS;
+    if (int rc = batch_check_shape(n, c, ow, oh, dtype, layout)) return rc;
     for (uint32_t i = 0; i < n; ++i)
         if (codes[i] >= kOrientCodes || (orient_transposes(codes[i]) && ow != oh)) return LLCOMP_MI_BAD_ARGS;
     return LLCOMP_MI_OK;
@@ -26,7 +25,7 @@ int orient_reference(const void* batch, uint32_t n, uint32_t c, uint32_t ow, uin
                      void* out) {
     if (!batch || !out) return LLCOMP_MI_BAD_ARGS;
     if (int rc = orient_check_call(n, c, ow, oh, dtype, layout, codes)) return rc;
-    const uint32_t esize = orient_esize(dtype);
+    const uint32_t esize = batch_esize(dtype);
     const uint64_t sample_bytes = uint64_t(c) * ow * oh * esize;
     const uint8_t* src = static_cast<const uint8_t*>(batch);
     std::vector<uint8_t> before;

@@ -20,8 +20,8 @@ struct OrientEntry {
 };
 inline uint64_t orient_table_bound(uint64_t n) { return n * sizeof(OrientEntry); }
 
-// A whole call but for its pointers into memory: BAD_ARGS for a NULL codes, n = 0 or above kOrientMaxSamples, a side or c of 0, an
-// unknown dtype or layout, a code above 7, a transposing code with ow != oh, a batch no address space holds
+// A whole call but for its pointers into memory: BAD_ARGS for a NULL codes, a batch that is none (batch_ops.hpp: batch_check_shape), a
+// code above 7, a transposing code with ow != oh
 int orient_check_call(uint32_t n, uint32_t c, uint32_t ow, uint32_t oh, uint32_t dtype, uint32_t layout, const uint8_t* codes);
 // The table of a checked call: the samples whose code is not 0, in order
 void orient_table(uint32_t n, const uint8_t* codes, std::vector<OrientEntry>& table);

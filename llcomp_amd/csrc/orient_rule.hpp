@@ -1,16 +1,16 @@
 // orient_rule.hpp -- the rule of the batch orientation (include/llcomp_mi.h: "Batch orientation"), stated ONCE: these functions are
 // compiled into the kernel (orient_kernels.hip) and into llcomp_mi_orient_reference and the checks (orient_plan.cpp).  A code is 0 or
 // PIL's Image.Transpose value plus 1; out(x, y) = in(orient_src(code, ow, oh, x, y)); elements move, nothing is computed on them.
+// The element's size and the shape of a batch: batch_ops.hpp.
 #pragma once
 #include <cstdint>
 
 #include "../../include/llcomp_mi.h"
-#include "geometry.hpp"
+#include "batch_ops.hpp"
 
 namespace llcomp_mi {
 
 constexpr uint32_t kOrientCodes = 8;
-constexpr uint32_t kOrientMaxSamples = 65535;  // (an oriented sample is a layer of the kernel's grid)
 
 struct OrientXY {
     uint32_t x, y;
@@ -19,10 +19,6 @@ struct OrientRect {  // x0 <= x < x1, y0 <= y < y1
     uint32_t x0, y0, x1, y1;
 };
 
-// The element's size in bytes, 0 for a dtype that is none
-LLMI_HD inline uint32_t orient_esize(uint32_t dtype) {
-    return dtype == LLCOMP_MI_DTYPE_U8 ? 1u : dtype == LLCOMP_MI_DTYPE_F32 ? 4u : (dtype == LLCOMP_MI_DTYPE_F16 || dtype == LLCOMP_MI_DTYPE_BF16) ? 2u : 0u;
-}
 // The codes that exchange the axes: they keep the shape of a square sample only
 LLMI_HD inline bool orient_transposes(uint32_t code) {
     return code == LLCOMP_MI_ORIENT_ROTATE_90 || code == LLCOMP_MI_ORIENT_ROTATE_270 || code == LLCOMP_MI_ORIENT_TRANSPOSE ||

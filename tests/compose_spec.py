@@ -7,8 +7,8 @@ import math
 
 import numpy as np
 
-NP_NAME = {"uint8": np.uint8, "float32": np.float32, "float16": np.float16, "bfloat16": np.uint16}
-BITS = {1: np.uint8, 2: np.uint16, 4: np.uint32}
+from batch_support import bits_of, gen_batch  # noqa: F401  (the tests take them from here)
+
 FILL = 1
 
 
@@ -43,20 +43,6 @@ def apply(src, dst, pieces, layout, dtype, fill=None, keep=False):
         else:
             out[d, dy:dy + h, dx:dx + w, :] = fv_b if flags & FILL else src[s, sy:sy + h, sx:sx + w, :]
     return out
-
-
-def gen_batch(dtype, n, c, h, w, layout, seed):
-    """arbitrary bit patterns as the numpy type the library takes for the dtype (bfloat16: uint16)"""
-    t = np.dtype(NP_NAME[dtype])
-    shape = (n, c, h, w) if layout == "chw" else (n, h, w, c)
-    raw = np.random.default_rng(seed).integers(0, 256, size=int(np.prod(shape)) * t.itemsize, dtype=np.uint8)
-    return raw.view(t).reshape(shape)
-
-
-def bits_of(a):
-    """an array of any of the four element types -> its bit patterns (a NaN compares equal to itself there)"""
-    a = np.ascontiguousarray(a)
-    return a.view(BITS[a.itemsize])
 
 
 def random_pieces(rng, n_src, iw, ih, n_dst, ow, oh, n):

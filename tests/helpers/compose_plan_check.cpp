@@ -98,7 +98,7 @@ void walk(const ComposeGeom& g, const ComposeSample* samples, uint32_t n_samples
 }
 
 int run(const Call& c, std::mt19937& rng) {
-    const uint32_t es = compose_esize(c.dtype);
+    const uint32_t es = batch_esize(c.dtype);
     const bool chw = c.layout == LLCOMP_MI_LAYOUT_CHW, keep = c.flags & LLCOMP_MI_COMPOSE_KEEP;
     const size_t src_bytes = size_t(c.n_src) * c.c * c.iw * c.ih * es, dst_bytes = size_t(c.n_dst) * c.c * c.ow * c.oh * es;
     // operator new[] aligns to 16: the batches begin src_off / dst_off bytes behind that and end where their arrays end
@@ -179,7 +179,7 @@ Call draw(uint32_t dtype, uint32_t layout, uint32_t src_off, uint32_t dst_off, b
     Call c{};
     c.dtype = dtype, c.layout = layout, c.src_off = src_off, c.dst_off = dst_off;
     c.c = cs[rng() % 3];
-    const uint32_t rows = compose_tile_rows(compose_esize(dtype) * (layout == LLCOMP_MI_LAYOUT_CHW ? 1u : c.c));
+    const uint32_t rows = compose_tile_rows(batch_esize(dtype) * (layout == LLCOMP_MI_LAYOUT_CHW ? 1u : c.c));
     c.n_src = rng() % 8 ? 1 + rng() % 3 : 0, c.n_dst = 1 + rng() % 3;
     c.iw = 1 + rng() % (big ? 160 : 40), c.ih = 1 + rng() % (big ? 24 : 9);
     c.ow = big ? kComposeTile - 2 + rng() % (kComposeTile + 5) : 1 + rng() % 48;
@@ -274,7 +274,7 @@ int main() {
     // every byte offset of src against every byte offset of dst, small drawn calls
     for (uint32_t dtype : kDtypes)
         for (uint32_t layout : kLayouts) {
-            const uint32_t es = compose_esize(dtype);
+            const uint32_t es = batch_esize(dtype);
             for (uint32_t so = 0; so < 16; so += es)
                 for (uint32_t d0 = 0; d0 < 16; d0 += es, ++rounds)
                     if (run(draw(dtype, layout, so, d0, false, rng), rng)) return 1;
@@ -282,7 +282,7 @@ int main() {
     // shapes around the tile's borders, offsets drawn
     for (uint32_t dtype : kDtypes)
         for (uint32_t layout : kLayouts) {
-            const uint32_t es = compose_esize(dtype);
+            const uint32_t es = batch_esize(dtype);
             for (uint32_t i = 0; i < 12; ++i, ++rounds)
                 if (run(draw(dtype, layout, rng() % 16 / es * es, rng() % 16 / es * es, true, rng), rng)) return 1;
         }

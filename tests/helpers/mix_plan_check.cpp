@@ -94,7 +94,7 @@ int check_plan(uint32_t n, uint32_t kind, std::mt19937& rng) {
 }
 
 int check_reference(uint32_t dtype, uint32_t layout, std::mt19937& rng) {
-    const uint32_t n = 1 + rng() % 12, c = rng() % 2 ? 3 : 1, ow = 1 + rng() % 9, oh = 1 + rng() % 7, es = mix_esize(dtype);
+    const uint32_t n = 1 + rng() % 12, c = rng() % 2 ? 3 : 1, ow = 1 + rng() % 9, oh = 1 + rng() % 7, es = batch_esize(dtype);
     const size_t bytes = size_t(n) * c * ow * oh * es;
     const std::unique_ptr<llcomp_mi_mix_sample[]> s = heap_records(n, rng() % 4, ow, oh, dtype != LLCOMP_MI_DTYPE_U8, rng);
     std::unique_ptr<uint8_t[]> batch(new uint8_t[bytes]), out(new uint8_t[bytes]), twice(new uint8_t[bytes]);

@@ -55,7 +55,7 @@ int check_table(uint32_t n, uint32_t kind, std::mt19937& rng) {
 
 int check_reference(uint32_t dtype, uint32_t layout, std::mt19937& rng) {
     const bool square = rng() % 2;
-    const uint32_t n = 1 + rng() % 9, c = rng() % 2 ? 3 : 1, ow = 1 + rng() % 9, oh = square ? ow : 1 + rng() % 7, es = orient_esize(dtype);
+    const uint32_t n = 1 + rng() % 9, c = rng() % 2 ? 3 : 1, ow = 1 + rng() % 9, oh = square ? ow : 1 + rng() % 7, es = batch_esize(dtype);
     const size_t bytes = size_t(n) * c * ow * oh * es;
     const std::unique_ptr<uint8_t[]> codes = heap_codes(n, 2, ow == oh, rng);
     std::unique_ptr<uint8_t[]> batch(new uint8_t[bytes]), out(new uint8_t[bytes]), twice(new uint8_t[bytes]);

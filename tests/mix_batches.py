@@ -1,11 +1,8 @@
 """What the tests of the batch mixing share (test_mix_rule.py, test_gpu_mix_batch.py): a case -- partner, lam, boxes, erase, erase values
 -- once as the arguments of llcomp_amd.mix_samples and once as those of tests/mix_spec.py, and a batch between torch's [n, c, h, w] and
 the bit patterns in either layout that the library takes."""
-import numpy as np
-
 import mix_spec
-
-NP_NAME = {"uint8": np.uint8, "float32": np.float32, "float16": np.float16, "bfloat16": np.uint16}
+from batch_support import NP_NAME, bits_of  # noqa: F401
 
 
 def to_layout(t, layout):
@@ -13,12 +10,6 @@ def to_layout(t, layout):
     b = mix_spec.bits(t if layout == "chw" else t.permute(0, 2, 3, 1))
     name = {v: k for k, v in mix_spec.DTYPES.items()}[t.dtype]
     return b.view(NP_NAME[name]) if name != "bfloat16" else b
-
-
-def bits_of(a):
-    """a numpy batch of any of the four element types -> its bit patterns"""
-    a = np.ascontiguousarray(a)
-    return a.view({1: np.uint8, 2: np.uint16, 4: np.uint32}[a.itemsize])
 
 
 class Case:

@@ -3,10 +3,10 @@ the sample seen as [c, h, w] or [h, w, c].  It calls nothing of the library.  A 
 plus 1; np.rot90 turns counter-clockwise, as PIL's ROTATE_90 does."""
 import numpy as np
 
+from batch_support import bits_of, gen_batch  # noqa: F401  (the tests take them from here)
+
 NAMES = ("none", "flip_left_right", "flip_top_bottom", "rotate_90", "rotate_180", "rotate_270", "transpose", "transverse")
 TRANSPOSING = (3, 5, 6, 7)
-NP_NAME = {"uint8": np.uint8, "float32": np.float32, "float16": np.float16, "bfloat16": np.uint16}
-BITS = {1: np.uint8, 2: np.uint16, 4: np.uint32}
 
 
 def orient_sample(a, code, layout):
@@ -40,18 +40,3 @@ def apply(batch, codes, layout):
     for i, code in enumerate(codes):
         out[i] = orient_sample(batch[i], int(code), layout)
     return out
-
-
-def gen_batch(dtype, n, c, h, w, layout, seed):
-    """arbitrary bit patterns -- NaNs with payloads, infinities, negative zeros and subnormals among them -- as the numpy type the
-    library takes for the dtype (bfloat16: uint16)"""
-    t = np.dtype(NP_NAME[dtype])
-    shape = (n, c, h, w) if layout == "chw" else (n, h, w, c)
-    raw = np.random.default_rng(seed).integers(0, 256, size=int(np.prod(shape)) * t.itemsize, dtype=np.uint8)
-    return raw.view(t).reshape(shape)
-
-
-def bits_of(a):
-    """an array of any of the four element types -> its bit patterns (a NaN compares equal to itself there)"""
-    a = np.ascontiguousarray(a)
-    return a.view(BITS[a.itemsize])

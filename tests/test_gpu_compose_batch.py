@@ -9,21 +9,11 @@ import numpy as np
 import pytest
 
 import compose_spec
-from compose_spec import FILL, bits_of
+from batch_support import DTYPES, ESIZE, bits_of, guards_intact, mi, put, stream  # noqa: F401
+from compose_spec import FILL
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 256
-DTYPES = ("uint8", "float32", "float16", "bfloat16")
-ESIZE = {"uint8": 1, "float32": 4, "float16": 2, "bfloat16": 2}
-
-
-@pytest.fixture(scope="module")
-def mi():
-    import llcomp_amd
-
-    assert llcomp_amd.device_count() >= 1, "GPU tests need a HIP device"
-    return llcomp_amd
 
 
 @pytest.fixture(scope="module")
@@ -32,24 +22,6 @@ def codecs(mi):
     yield made
     for k in made.values():
         k.close()
-
-
-def stream():
-    import torch
-
-    return torch.cuda.current_stream().cuda_stream
-
-
-def put(batch, offset_bytes):
-    """the numpy batch in a device buffer, offset_bytes past a 256-byte boundary behind GUARD bytes of 0x5A, GUARD more behind it"""
-    import torch
-
-    lo = GUARD + offset_bytes
-    buf = torch.full((lo + batch.nbytes + GUARD,), 0x5A, dtype=torch.uint8, device="cuda")
-    assert buf.data_ptr() % 256 == 0
-    if batch.nbytes:
-        buf[lo:lo + batch.nbytes] = torch.from_numpy(np.ascontiguousarray(batch).reshape(-1).view(np.uint8).copy()).cuda()
-    return buf, lo
 
 
 def run(mi, codec, src, dst, pieces, dtype, layout, fill=None, keep=False, src_offset=0, dst_offset=0, expect_error=False, **kw):
@@ -77,10 +49,10 @@ def run(mi, codec, src, dst, pieces, dtype, layout, fill=None, keep=False, src_o
     assert (err is not None) == expect_error, err
     assert err is None or err.status == mi.BAD_ARGS
     host = dbuf.cpu().numpy()
-    assert (host[:dlo] == 0x5A).all() and (host[dlo + dst.nbytes:] == 0x5A).all(), "a byte outside the dst batch was written"
+    assert guards_intact(host, dlo, dst.nbytes), "a byte outside the dst batch was written"
     if src is not None:
         shost = sbuf.cpu().numpy()
-        assert (shost[:slo] == 0x5A).all() and (shost[slo + src.nbytes:] == 0x5A).all()
+        assert guards_intact(shost, slo, src.nbytes)
         assert np.array_equal(shost[slo:slo + src.nbytes], np.ascontiguousarray(src).reshape(-1).view(np.uint8)), "the src batch was written"
     return bits_of(host[dlo:dlo + dst.nbytes].copy().view(dst.dtype).reshape(dst.shape))
 

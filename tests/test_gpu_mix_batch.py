@@ -7,25 +7,15 @@ import numpy as np
 import pytest
 
 import mix_spec
-from mix_batches import NP_NAME, Case, bits_of, to_layout
+from batch_support import DTYPES, ESIZE, NP_NAME, bits_of, guards_intact, mi, put, stream  # noqa: F401
+from mix_batches import Case, to_layout
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 256
-DTYPES = ("uint8", "float32", "float16", "bfloat16")
-ESIZE = {"uint8": 1, "float32": 4, "float16": 2, "bfloat16": 2}
 LAM = 0.3712345678901234
 # (ow, oh, c): the smallest batch element; no whole 16-byte chunk; E * esize no multiple of 16; chunks that straddle rows; whole chunks
 # only; the general case
 SHAPES = ((1, 1, 1), (3, 1, 3), (5, 3, 3), (7, 5, 1), (8, 2, 1), (33, 9, 3))
-
-
-@pytest.fixture(scope="module")
-def mi():
-    import llcomp_amd
-
-    assert llcomp_amd.device_count() >= 1, "GPU tests need a HIP device"
-    return llcomp_amd
 
 
 @pytest.fixture(scope="module")
@@ -36,12 +26,6 @@ def codecs(mi):
         k.close()
 
 
-def stream():
-    import torch
-
-    return torch.cuda.current_stream().cuda_stream
-
-
 def run(mi, codec, batch, case, layout, offset=0, samples=None, expect_error=False):
     """mix_batch on the torch batch [n, c, h, w] in the layout, `offset` elements past a 256-byte boundary -> the batch's bits after
     the call; the bytes around it have to be untouched"""
@@ -50,10 +34,7 @@ def run(mi, codec, batch, case, layout, offset=0, samples=None, expect_error=Fal
     name = {v: k for k, v in mix_spec.DTYPES.items()}[batch.dtype]
     raw = to_layout(batch, layout)
     n, (c, h, w) = len(batch), batch.shape[1:]
-    lo = GUARD + offset * ESIZE[name]
-    buf = torch.full((lo + raw.nbytes + GUARD,), 0x5A, dtype=torch.uint8, device="cuda")
-    assert buf.data_ptr() % 256 == 0
-    buf[lo:lo + raw.nbytes] = torch.from_numpy(raw.reshape(-1).view(np.uint8)).cuda()
+    buf, lo = put(raw, offset * ESIZE[name])
     err = None
     try:
         codec.mix_batch(buf.data_ptr() + lo, n, w, h, case.samples(mi, n) if samples is None else samples, dtype=name, layout=layout,
@@ -63,7 +44,7 @@ def run(mi, codec, batch, case, layout, offset=0, samples=None, expect_error=Fal
     torch.cuda.synchronize()
     assert (err is not None) == expect_error, err
     host = buf.cpu().numpy()
-    assert (host[:lo] == 0x5A).all() and (host[lo + raw.nbytes:] == 0x5A).all(), "a byte outside the batch was written"
+    assert guards_intact(host, lo, raw.nbytes), "a byte outside the batch was written"
     return bits_of(host[lo:lo + raw.nbytes].copy().view(NP_NAME[name]).reshape(raw.shape))
 
 

@@ -9,23 +9,12 @@ import numpy as np
 import pytest
 
 import orient_spec
-from orient_spec import bits_of
+from batch_support import DTYPES, ESIZE, bits_of, guards_intact, mi, put, stream  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 256
-DTYPES = ("uint8", "float32", "float16", "bfloat16")
-ESIZE = {"uint8": 1, "float32": 4, "float16": 2, "bfloat16": 2}
 ALL_CODES = [0, 1, 2, 3, 4, 5, 6, 7, 3]  # every code, and a second ROTATE_90
 KEEPING = [0, 1, 2, 4]                   # the codes that keep the shape of a sample that is not square
-
-
-@pytest.fixture(scope="module")
-def mi():
-    import llcomp_amd
-
-    assert llcomp_amd.device_count() >= 1, "GPU tests need a HIP device"
-    return llcomp_amd
 
 
 @pytest.fixture(scope="module")
@@ -36,12 +25,6 @@ def codecs(mi):
         k.close()
 
 
-def stream():
-    import torch
-
-    return torch.cuda.current_stream().cuda_stream
-
-
 def run(mi, codec, batch, codes, dtype, layout, offset=0, expect_error=False, **kw):
     """orient_batch on the numpy batch ([n, c, h, w] or [n, h, w, c] by the layout), `offset` elements past a 256-byte boundary -> the
     batch's bits after the call; the bytes around it have to be untouched.  kw replaces arguments of the call (the refusals;
@@ -50,10 +33,7 @@ def run(mi, codec, batch, codes, dtype, layout, offset=0, expect_error=False, **
 
     n = len(batch)
     (c, h, w) = batch.shape[1:] if layout == "chw" else (batch.shape[3], batch.shape[1], batch.shape[2])
-    lo = GUARD + offset * ESIZE[dtype]
-    buf = torch.full((lo + batch.nbytes + GUARD,), 0x5A, dtype=torch.uint8, device="cuda")
-    assert buf.data_ptr() % 256 == 0
-    buf[lo:lo + batch.nbytes] = torch.from_numpy(np.ascontiguousarray(batch).reshape(-1).view(np.uint8).copy()).cuda()
+    buf, lo = put(batch, offset * ESIZE[dtype])
     args = dict(d_batch=buf.data_ptr() + lo, n=n, ow=w, oh=h, codes=codes, dtype=dtype, layout=layout, stream=stream())
     args.update({name[5:] if name.startswith("call_") else name: v for name, v in kw.items()})
     err = None
@@ -65,7 +45,7 @@ def run(mi, codec, batch, codes, dtype, layout, offset=0, expect_error=False, **
     assert (err is not None) == expect_error, err
     assert err is None or err.status == mi.BAD_ARGS
     host = buf.cpu().numpy()
-    assert (host[:lo] == 0x5A).all() and (host[lo + batch.nbytes:] == 0x5A).all(), "a byte outside the batch was written"
+    assert guards_intact(host, lo, batch.nbytes), "a byte outside the batch was written"
     return bits_of(host[lo:lo + batch.nbytes].copy().view(batch.dtype).reshape(batch.shape))
 
 
