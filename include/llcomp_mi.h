@@ -687,8 +687,8 @@ uint32_t llcomp_mi_orient_tile(void);
  * layout; a piece with dst >= n_dst; a piece that is no FILL piece with src >= n_src or a source rectangle that leaves iw x ih; a piece
  * whose rectangle leaves ow x oh; a FILL piece with src, sx or sy not 0; flag or reserved bits that are not defined; a bad fill value;
  * more than llcomp_mi_compose_max_pieces_per_sample() = 1024 pieces with w and h above 0 on one dst sample.
- * NOT covered: pieces that resample or mirror (views do that at decode), masks that are not rectangles (CopyPaste with instance masks),
- * the labels and boxes, and a src and dst that differ in dtype or layout. */
+ * NOT covered: pieces that resample or mirror (views do that at decode), and a src and dst that differ in dtype or layout.  Masks that
+ * are not rectangles: "Batch copy-paste" below; the boxes of id maps: "Label boxes" below. */
 #define LLCOMP_MI_COMPOSE_FILL 1u /* piece flag */
 #define LLCOMP_MI_COMPOSE_KEEP 1u /* call flag: elements no piece covers keep their value and are not written */
 typedef struct llcomp_mi_compose_piece {
@@ -717,6 +717,68 @@ int llcomp_mi_compose_plan(uint32_t n_src, uint32_t iw, uint32_t ih, uint32_t n_
 uint32_t llcomp_mi_compose_tile(void);
 uint32_t llcomp_mi_compose_tile_rows(uint32_t pixel_bytes);
 uint32_t llcomp_mi_compose_max_pieces_per_sample(void);
+/* Batch copy-paste (llcomp_mi_codec_paste_batch below: Simple Copy-Paste of Ghiasi et al., torchvision's reference SimpleCopyPaste, the
+ * paste of class maps, the renumbering of instances in id maps): the OBJECTS of one decoded sample land in another, chosen by the ids
+ * of an id map.  Three dense batches: src, n_src samples of iw x ih, and dst, n_dst samples of ow x oh, of the same c, dtype (U8, F16,
+ * BF16, F32) and layout (HWC or CHW), aligned to the element and to nothing more; and mask, n_src samples of ih x iw BYTES at any byte
+ * address, mask[s] the id map of src[s]: mask(s, y, x) = mask[(s * ih + y) * iw + x].  The call has a list of n_pieces records (below),
+ * in painter's order.  Piece p SELECTS (x, y) of dst sample d when dst_p == d, (x, y) lies in [dx, dx + w) x [dy, dy + h), and bit m of
+ * ids_p is set for m = mask(src_p, sy + y - dy, sx + x - dx).  The element at channel ch, row y, column x of d takes the LAST piece of
+ * the list that selects (x, y):
+ *   p is a VALUE piece:  value_p converted to the dtype, the same for every channel
+ *   any other p:         src(src_p, ch, sy_p + y - dy_p, sx_p + x - dx_p), moved as bits
+ *   no such piece:       the element stays AND IS NOT WRITTEN -- the call is always in place on dst, there is no fill
+ * The value converts as the composition's fill does: to nearest even for F16 and BF16, U8 takes integers 0..255 only, a value that is
+ * not finite is refused.  A piece with w or h 0, or with no id bit set, is checked and ignored.  Elements are never interpreted: NaN
+ * payloads and negative zeros survive.  dst must not overlap src or mask in bytes; src and mask may overlap or be the same buffer (for
+ * c == 1 U8 the id maps are their own source: that is how a class map is pasted).  It covers binary masks (all bits but bit 0), one
+ * instance or a drawn subset of instances per piece, and a VALUE piece per instance with the id it gets in the dst map -- the second
+ * call of a Copy-Paste, on the maps.
+ * BAD_ARGS: a dst or a src that is no dense batch (n above 65535 or 0, a side or c of 0, an unknown dtype or layout, a batch no address
+ * space holds); n_src == 0 with n_pieces > 0; a NULL pieces with n_pieces > 0; n_pieces above 2^20; a row of ow * c or iw * c elements
+ * of 2^31 elements or more; a piece with dst >= n_dst or src >= n_src, with a source rectangle that leaves iw x ih or a dst rectangle
+ * that leaves ow x oh, with flag bits above bit 0, with a value that is not 0 without VALUE, or with a bad value under VALUE; more than
+ * llcomp_mi_paste_max_pieces_per_sample() = 256 pieces with w and h above 0 on one dst sample.
+ * NOT covered: more than 256 ids per map (16-bit id maps), blended (alpha or Gaussian) paste borders, a src and dst of different dtype
+ * or layout, pieces that resample or mirror (views do that at decode), a dst that overlaps its src, per-piece fills per channel. */
+#define LLCOMP_MI_PASTE_VALUE 1u
+typedef struct llcomp_mi_paste_piece {
+    uint32_t dst, src;
+    uint32_t dx, dy, sx, sy, w, h;
+    uint32_t flags;        /* bit 0 LLCOMP_MI_PASTE_VALUE */
+    float value;           /* VALUE's value; 0 without VALUE */
+    uint32_t ids[8];       /* 256 bits: bit m set = mask byte m is selected */
+} llcomp_mi_paste_piece;   /* 72 bytes */
+/* The rule above on host memory.  out (n_dst samples) may be dst_in -- otherwise dst_in is copied into it first -- and overlaps src and
+ * mask in no way.  It is compiled from the same functions as the GPU's kernel; it is not fast.  BAD_ARGS, out untouched: the cases
+ * above, a NULL out or dst_in, a NULL src or mask with n_pieces > 0, src or out not aligned to the element.  Host-only. */
+int llcomp_mi_paste_reference(const void* src, const void* mask, uint32_t n_src, uint32_t iw, uint32_t ih, const void* dst_in, uint32_t n_dst,
+                              uint32_t ow, uint32_t oh, uint32_t c, uint32_t dtype, uint32_t layout, const llcomp_mi_paste_piece* pieces,
+                              uint32_t n_pieces, void* out);
+/* What a call does, as llcomp_mi_compose_plan: samples[*n_samples] (room for n_dst), the dst samples with a piece that is not ignored,
+ * ascending; first[*n_samples + 1] and order (room for n_pieces): sample j's pieces are order[first[j] .. first[j + 1]), indices into
+ * pieces in the call's order, the ignored ones left out; *n_workgroups: the workgroups of the call's one kernel (the composition's
+ * tiles), 0 for a call that queues nothing.  samples, first and order may be NULL.  BAD_ARGS, outputs untouched: the cases above, a NULL
+ * n_samples or n_workgroups.  Host-only. */
+int llcomp_mi_paste_plan(uint32_t n_src, uint32_t iw, uint32_t ih, uint32_t n_dst, uint32_t ow, uint32_t oh, uint32_t c, uint32_t dtype,
+                         uint32_t layout, const llcomp_mi_paste_piece* pieces, uint32_t n_pieces, uint32_t* samples, uint32_t* first,
+                         uint32_t* order, uint32_t* n_samples, uint64_t* n_workgroups);
+uint32_t llcomp_mi_paste_max_pieces_per_sample(void);
+/* Label boxes (llcomp_mi_codec_label_boxes below: torchvision's masks_to_boxes of every instance of an id map, with the areas): maps is
+ * n samples of oh x ow bytes, dense, at any byte address -- an instance id or class id per pixel, as the containers of label images
+ * decode, behind any crop, affine, perspective, flip, mosaic or paste.  The output is n * 256 records; for sample i and id m, record
+ * i * 256 + m has count, the number of pixels equal to m, and [x0, x1) x [y0, y1), their bounding box; with count == 0 it is
+ * {0, ow, oh, 0, 0}, the identities of min and max, so records of two maps merge by min, max and add.  masks_to_boxes of instance m is
+ * (x0, y0, x1 - 1, y1 - 1), and count its area.  Every record is written: the caller initialises nothing.
+ * BAD_ARGS: n of 0 or above 65535, ow or oh of 0, ow * oh of 2^32 or more, a batch no address space holds, a NULL pointer.
+ * NOT covered: more than 256 ids per map (16-bit id maps). */
+typedef struct llcomp_mi_label_box {
+    uint32_t count, x0, y0, x1, y1;
+} llcomp_mi_label_box;     /* 20 bytes */
+/* The rule above on host memory: out holds n * 256 records.  Host-only. */
+int llcomp_mi_label_boxes_reference(const void* maps, uint32_t n, uint32_t ow, uint32_t oh, llcomp_mi_label_box* out);
+/* The rows of the band of a sample that a workgroup of llcomp_mi_codec_label_boxes takes (DESIGN.md "Label boxes"): a constant */
+uint32_t llcomp_mi_label_boxes_rows(void);
 uint32_t llcomp_mi_slice_count(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar);
 /* Slice width for one-row slices (tile_h = 1) when `frames` frames are coded per call: the widest slice (64..480 pixels) that
  * still keeps about four wavefronts per SIMD busy.  A call that codes few frames is latency-bound with wide slices; this
@@ -1098,6 +1160,26 @@ int llcomp_mi_codec_compose_batch(llcomp_mi_codec* codec, const void* d_src, uin
 /* The bound on llcomp_mi_codec_allocated_bytes with such calls of up to n_dst dst samples and n_pieces pieces among the codec's calls:
  * llcomp_mi_codec_workspace_bytes + 12 * n_dst + 32 * n_pieces + 4 * c, the table of a call.  0 for a NULL codec. */
 uint64_t llcomp_mi_codec_compose_workspace_bytes(const llcomp_mi_codec* codec, uint32_t n_dst, uint32_t n_pieces);
+/* Batch copy-paste (the rule: "Batch copy-paste" above): the pieces of d_src, n_src samples of the codec's c channels and iw x ih
+ * pixels, that the id maps d_mask select, into d_dst, n_dst samples of ow x oh, all in device memory, asynchronously on `stream` --
+ * behind the decode calls that wrote them when those ran on the same stream.  One kernel, no scratch in device memory: a dst element is
+ * written at most once, and only if a piece selects it; no byte outside the three batches is read, none outside dst is written.  A dst
+ * sample without a piece that is not ignored costs no workgroup, and a call without one queues nothing.  pieces is HOST memory, read
+ * during the call only: the records travel with the plan in ONE copy from the codec's pinned ring into a device buffer of this call's
+ * own.  BAD_ARGS, nothing queued: a NULL codec or d_dst, a NULL d_src or d_mask with n_pieces > 0, d_src or d_dst not aligned to the
+ * element, a dst whose bytes overlap src's or mask's, and llcomp_mi_paste_plan's cases. */
+int llcomp_mi_codec_paste_batch(llcomp_mi_codec* codec, const void* d_src, const void* d_mask, uint32_t n_src, uint32_t iw, uint32_t ih,
+                                void* d_dst, uint32_t n_dst, uint32_t ow, uint32_t oh, uint32_t dtype, uint32_t layout,
+                                const llcomp_mi_paste_piece* pieces, uint32_t n_pieces, void* stream);
+/* The bound on llcomp_mi_codec_allocated_bytes with such calls of up to n_dst dst samples and n_pieces pieces among the codec's calls:
+ * llcomp_mi_codec_workspace_bytes + 12 * n_dst + 68 * n_pieces, the table of a call.  0 for a NULL codec. */
+uint64_t llcomp_mi_codec_paste_workspace_bytes(const llcomp_mi_codec* codec, uint32_t n_dst, uint32_t n_pieces);
+/* Label boxes (the rule: "Label boxes" above): the 256 records of each of the n id maps at d_maps, oh x ow bytes each whatever the
+ * codec's c, into d_boxes, n * 256 records in device memory, asynchronously on `stream`.  The codec gives the device and nothing else:
+ * no table, no workspace.  Two kernels: one writes the identities, one has a workgroup per band of llcomp_mi_label_boxes_rows() rows of
+ * a sample, which merges its records into d_boxes with integer atomics, so the result does not depend on order.  BAD_ARGS, nothing
+ * queued: a NULL codec, the reference's cases, d_boxes not aligned to 4, d_boxes overlapping the maps. */
+int llcomp_mi_codec_label_boxes(llcomp_mi_codec* codec, const void* d_maps, uint32_t n, uint32_t ow, uint32_t oh, void* d_boxes, void* stream);
 /* Stage-A only (context + prediction model), for tests and profiling: d_sym u32[frames*h*w*c],
  * low 16 bits = folded context (0..7925), high 16 bits = folded residual (two's complement). */
 int llcomp_mi_codec_model(llcomp_mi_codec* codec, const void* d_px, void* d_sym, void* stream);

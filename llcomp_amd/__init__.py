@@ -37,6 +37,10 @@ with ctypes and keeps the reference's names and error behaviour:
     COMPOSE_FILL / COMPOSE_KEEP / compose_pieces / compose_plan / compose_tile / compose_reference / grid_pieces / mosaic_pieces /
         Codec.compose_batch / Codec.compose_workspace_bytes  (rectangles of one decoded batch into the canvases of another, the rest a
         fill or kept: Mosaic, make_grid, batch_images, Cutout with several holes, GridMask)
+    PASTE_VALUE / paste_pieces / paste_plan / paste_reference / paste_max_pieces_per_sample / Codec.paste_batch /
+        Codec.paste_workspace_bytes  (the objects of one decoded sample into another, chosen by the ids of an id map: Simple Copy-Paste)
+    LABEL_BOX_DTYPE / label_boxes_reference / label_boxes_rows / Codec.label_boxes  (the pixel count and bounding box of each of the 256
+        ids of every id map of a batch: torchvision's masks_to_boxes)
     RawImage(pixels, width, height, channels)     <->  llcomp::RawImage         (/root/reference/llcomp.hpp:454-459)
     EXT = ".llcomp"                               <->  llcomp::ext              (/root/reference/llcomp.hpp:18)
 
@@ -56,6 +60,7 @@ from ._lib import WarpView as _WarpView, WarpGroup as _WarpGroup
 from ._lib import PerspectiveView as _PerspectiveView, PerspectiveGroup as _PerspectiveGroup
 from ._lib import PhotoOp as _PhotoOp, PhotoChain as _PhotoChain, PhotoGroup as _PhotoGroup
 from ._lib import ComposePiece as _ComposePiece
+from ._lib import PastePiece as _PastePiece
 from ._lib import MixSample as _MixSample
 
 EXT = ".llcomp"
@@ -802,6 +807,104 @@ def mosaic_pieces(centres, iw, ih, s):
             sy = ih - h if corner in ("br", "bl") else 0
             recs.append((i, 4 * i + k, x1, y1, sx, sy, w, h))
     return compose_pieces(recs)
+
+
+# Codec.paste_batch (LLCOMP_MI_PASTE_VALUE): a piece's flag
+PASTE_VALUE = 1
+
+
+def paste_pieces(records):
+    """The pieces of a paste_batch call (llcomp_mi_paste_piece) as a ctypes array: every record a tuple (dst, src, dx, dy, sx, sy, w, h,
+    ids[, value]).  ids: an iterable of ints 0..255, the mask bytes the piece selects, or "nonzero" for all of them but 0 (a binary
+    mask).  A value makes a VALUE piece: the selected pixels take the value in every channel, not src's.  The library checks the rest."""
+    if isinstance(records, C.Array) and records._type_ is _PastePiece:
+        return records
+    records = list(records)
+    arr = (_PastePiece * len(records))()
+    for i, r in enumerate(records):
+        vals = list(r) if isinstance(r, (tuple, list)) else []
+        if len(vals) not in (9, 10):
+            raise LlcompError(BAD_ARGS, f"a piece is (dst, src, dx, dy, sx, sy, w, h, ids[, value]), got {r!r}")
+        nums = [int(v) for v in vals[:8]]
+        if min(nums) < 0 or max(nums) > 0xFFFFFFFF:
+            raise LlcompError(BAD_ARGS, f"a piece takes unsigned values, got {r!r}")
+        for name, v in zip(("dst", "src", "dx", "dy", "sx", "sy", "w", "h"), nums):
+            setattr(arr[i], name, v)
+        ids = vals[8]
+        if isinstance(ids, str):
+            if ids != "nonzero":
+                raise LlcompError(BAD_ARGS, f'ids are ints 0..255 or "nonzero", got {ids!r}')
+            ids = range(1, 256)
+        for m in ids:
+            m = int(m)
+            if not 0 <= m <= 255:
+                raise LlcompError(BAD_ARGS, f"an id is 0..255, got {m}")
+            arr[i].ids[m >> 5] |= 1 << (m & 31)
+        if len(vals) == 10 and vals[9] is not None:
+            arr[i].flags, arr[i].value = PASTE_VALUE, float(vals[9])
+    return arr
+
+
+def paste_max_pieces_per_sample():
+    """the most pieces with w and h above 0 on one dst sample (llcomp_mi_paste_max_pieces_per_sample)"""
+    return int(_lib.load().llcomp_mi_paste_max_pieces_per_sample())
+
+
+def paste_plan(n_src, iw, ih, n_dst, ow, oh, c, pieces, dtype="float32", layout="chw"):
+    """What a paste_batch call does (llcomp_mi_paste_plan, host only) -> (samples, first, order, n_workgroups), as compose_plan: the dst
+    samples with a piece that is not ignored, where every sample's pieces begin in order, the pieces' indices by dst sample without the
+    ignored ones (w or h 0, no id), and the workgroups of the kernel."""
+    recs = paste_pieces(pieces)
+    n_dst = int(n_dst)
+    samples, first, order = np.zeros(max(n_dst, 1), np.uint32), np.zeros(max(n_dst, 1) + 1, np.uint32), np.zeros(max(len(recs), 1), np.uint32)
+    ns, nw = C.c_uint32(0), C.c_uint64(0)
+    u32p = C.POINTER(C.c_uint32)
+    _check(_lib.load().llcomp_mi_paste_plan(int(n_src), int(iw), int(ih), n_dst, int(ow), int(oh), int(c), _dtype_code(dtype), _layout_code(layout),
+                                            recs, len(recs), samples.ctypes.data_as(u32p), first.ctypes.data_as(u32p), order.ctypes.data_as(u32p),
+                                            C.byref(ns), C.byref(nw)))
+    n = ns.value
+    return samples[:n].copy(), first[:n + 1].copy(), order[:int(first[n])].copy(), int(nw.value)
+
+
+def paste_reference(src, mask, dst, pieces, layout="chw", dtype=None):
+    """The rule of the batch copy-paste on host arrays (llcomp_mi_paste_reference): src [n_src, c, ih, iw] (layout "chw") or
+    [n_src, ih, iw, c] ("hwc"), mask [n_src, ih, iw] uint8 (it may be src itself for c = 1 uint8), dst as src; both of uint8, float32,
+    float16, or uint16 holding bfloat16 bits with dtype="bfloat16" -> the pasted dst batch, a new array."""
+    d, code, lay, n_dst, c, oh, ow = _batch_array(dst, dtype, layout)
+    s = np.ascontiguousarray(src)
+    if s.ndim != 4 or s.dtype != d.dtype or (s.shape[1] if lay == LAYOUT_CHW else s.shape[3]) != c:
+        raise LlcompError(BAD_ARGS, f"src is a 4-D batch of dst's type and channels, got {s.dtype} of shape {s.shape}")
+    n_src = s.shape[0]
+    ih, iw = s.shape[2:] if lay == LAYOUT_CHW else s.shape[1:3]
+    m = s if mask is src else np.ascontiguousarray(mask)
+    if m.dtype != np.uint8 or m.size != n_src * ih * iw:
+        raise LlcompError(BAD_ARGS, f"mask is uint8 [n_src, ih, iw], got {m.dtype} of shape {m.shape}")
+    recs = paste_pieces(pieces)
+    out = np.empty_like(d)
+    _check(_lib.load().llcomp_mi_paste_reference(s.ctypes.data, m.ctypes.data, n_src, iw, ih, d.ctypes.data, n_dst, ow, oh, c, code, lay, recs,
+                                                 len(recs), out.ctypes.data))
+    return out
+
+
+# a record of Codec.label_boxes (llcomp_mi_label_box): the pixels of an id and their box [x0, x1) x [y0, y1)
+LABEL_BOX_DTYPE = np.dtype([("count", "<u4"), ("x0", "<u4"), ("y0", "<u4"), ("x1", "<u4"), ("y1", "<u4")])
+
+
+def label_boxes_rows():
+    """the rows of the band of a sample that a workgroup of the label boxes' kernel takes (llcomp_mi_label_boxes_rows)"""
+    return int(_lib.load().llcomp_mi_label_boxes_rows())
+
+
+def label_boxes_reference(maps):
+    """The rule of the label boxes on a host array (llcomp_mi_label_boxes_reference): maps [n, oh, ow] uint8 -> [n, 256] records of
+    LABEL_BOX_DTYPE; an id without a pixel has (0, ow, oh, 0, 0)."""
+    a = np.ascontiguousarray(maps)
+    if a.ndim != 3 or a.dtype != np.uint8:
+        raise LlcompError(BAD_ARGS, f"maps are uint8 [n, oh, ow], got {a.dtype} of shape {a.shape}")
+    n, oh, ow = a.shape
+    out = np.zeros((max(n, 1), 256), LABEL_BOX_DTYPE)
+    _check(_lib.load().llcomp_mi_label_boxes_reference(a.ctypes.data if a.size else None, n, ow, oh, out.ctypes.data))
+    return out[:n]
 
 
 def _view_groups(groups, c, signed=False):
@@ -1810,6 +1913,26 @@ class Codec:
         """the bound on .allocated_bytes() with compose_batch calls of up to n_dst dst samples and n_pieces pieces
         (llcomp_mi_codec_compose_workspace_bytes)"""
         return self._L.llcomp_mi_codec_compose_workspace_bytes(self._h, int(n_dst), int(n_pieces))
+
+    def paste_batch(self, d_src, d_mask, n_src, iw, ih, d_dst, n_dst, ow, oh, pieces, dtype="float32", layout="chw", stream=0):
+        """The pieces of one dense batch that an id map selects, into another, in place (llcomp_mi_codec_paste_batch): d_src, n_src
+        samples of iw x ih, d_mask, their id maps (n_src x ih x iw bytes at any address; it may be d_src for c = 1 uint8), and d_dst,
+        n_dst samples of ow x oh, in device memory; src and dst of the codec's channels in the same dtype and layout; pieces from
+        paste_pieces(), or records for it.  What no piece selects stays and is not written.  Asynchronous on `stream`."""
+        recs = paste_pieces(pieces)
+        _check(self._L.llcomp_mi_codec_paste_batch(self._h, d_src, d_mask, int(n_src), int(iw), int(ih), d_dst, int(n_dst), int(ow), int(oh),
+                                                   _dtype_code(dtype), _layout_code(layout), recs, len(recs), stream))
+
+    def paste_workspace_bytes(self, n_dst, n_pieces):
+        """the bound on .allocated_bytes() with paste_batch calls of up to n_dst dst samples and n_pieces pieces
+        (llcomp_mi_codec_paste_workspace_bytes)"""
+        return self._L.llcomp_mi_codec_paste_workspace_bytes(self._h, int(n_dst), int(n_pieces))
+
+    def label_boxes(self, d_maps, n, ow, oh, d_boxes, stream=0):
+        """The pixel count and bounding box of each of the 256 ids of n id maps (llcomp_mi_codec_label_boxes): d_maps, n x oh x ow bytes
+        at any address, -> d_boxes, n * 256 records of LABEL_BOX_DTYPE (20 bytes each, 4-byte aligned), both in device memory; every
+        record is written.  Asynchronous on `stream`."""
+        _check(self._L.llcomp_mi_codec_label_boxes(self._h, d_maps, int(n), int(ow), int(oh), d_boxes, stream))
 
     def views_workspace_bytes(self, total_views):
         """.workspace_bytes for calls of up to total_views views (llcomp_mi_codec_views_workspace_bytes): the staged tables grow with them"""

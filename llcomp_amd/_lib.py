@@ -55,6 +55,9 @@ SYMBOLS = [
     "llcomp_mi_orient_reference", "llcomp_mi_orient_tile", "llcomp_mi_codec_orient_batch", "llcomp_mi_codec_orient_workspace_bytes",
     "llcomp_mi_compose_reference", "llcomp_mi_compose_plan", "llcomp_mi_compose_tile", "llcomp_mi_compose_tile_rows",
     "llcomp_mi_compose_max_pieces_per_sample", "llcomp_mi_codec_compose_batch", "llcomp_mi_codec_compose_workspace_bytes",
+    "llcomp_mi_paste_reference", "llcomp_mi_paste_plan", "llcomp_mi_paste_max_pieces_per_sample", "llcomp_mi_codec_paste_batch",
+    "llcomp_mi_codec_paste_workspace_bytes",
+    "llcomp_mi_label_boxes_reference", "llcomp_mi_label_boxes_rows", "llcomp_mi_codec_label_boxes",
 ]
 
 u8p = C.POINTER(C.c_uint8)
@@ -138,6 +141,17 @@ class ComposePiece(C.Structure):
     """llcomp_mi_compose_piece (include/llcomp_mi.h): 40 bytes"""
     _fields_ = [("dst", C.c_uint32), ("src", C.c_uint32), ("dx", C.c_uint32), ("dy", C.c_uint32), ("sx", C.c_uint32), ("sy", C.c_uint32),
                 ("w", C.c_uint32), ("h", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PastePiece(C.Structure):
+    """llcomp_mi_paste_piece (include/llcomp_mi.h): 72 bytes, ids at 40"""
+    _fields_ = [("dst", C.c_uint32), ("src", C.c_uint32), ("dx", C.c_uint32), ("dy", C.c_uint32), ("sx", C.c_uint32), ("sy", C.c_uint32),
+                ("w", C.c_uint32), ("h", C.c_uint32), ("flags", C.c_uint32), ("value", C.c_float), ("ids", C.c_uint32 * 8)]
+
+
+class LabelBox(C.Structure):
+    """llcomp_mi_label_box (include/llcomp_mi.h): 20 bytes"""
+    _fields_ = [("count", C.c_uint32), ("x0", C.c_uint32), ("y0", C.c_uint32), ("x1", C.c_uint32), ("y1", C.c_uint32)]
 
 
 class Info(C.Structure):
@@ -514,6 +528,26 @@ def load():
             recs, C.c_uint32, f32p, C.c_uint32, C.c_void_p]
         L.llcomp_mi_codec_compose_workspace_bytes.restype = C.c_uint64
         L.llcomp_mi_codec_compose_workspace_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+    if "LLCOMP_MI_LIB" not in os.environ or hasattr(L, "llcomp_mi_paste_reference"):  # batch copy-paste
+        u32p, recs = C.POINTER(C.c_uint32), C.POINTER(PastePiece)
+        L.llcomp_mi_paste_reference.restype = C.c_int
+        L.llcomp_mi_paste_reference.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 3 + [C.c_void_p] + [C.c_uint32] * 6 + [recs, C.c_uint32, C.c_void_p]
+        L.llcomp_mi_paste_plan.restype = C.c_int
+        L.llcomp_mi_paste_plan.argtypes = [C.c_uint32] * 9 + [recs, C.c_uint32, u32p, u32p, u32p, u32p, C.POINTER(C.c_uint64)]
+        L.llcomp_mi_paste_max_pieces_per_sample.restype = C.c_uint32
+        L.llcomp_mi_paste_max_pieces_per_sample.argtypes = []
+        L.llcomp_mi_codec_paste_batch.restype = C.c_int
+        L.llcomp_mi_codec_paste_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_uint32] * 3 + [C.c_void_p] + [C.c_uint32] * 5 + [
+            recs, C.c_uint32, C.c_void_p]
+        L.llcomp_mi_codec_paste_workspace_bytes.restype = C.c_uint64
+        L.llcomp_mi_codec_paste_workspace_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+    if "LLCOMP_MI_LIB" not in os.environ or hasattr(L, "llcomp_mi_label_boxes_reference"):  # label boxes
+        L.llcomp_mi_label_boxes_reference.restype = C.c_int
+        L.llcomp_mi_label_boxes_reference.argtypes = [C.c_void_p] + [C.c_uint32] * 3 + [C.c_void_p]
+        L.llcomp_mi_label_boxes_rows.restype = C.c_uint32
+        L.llcomp_mi_label_boxes_rows.argtypes = []
+        L.llcomp_mi_codec_label_boxes.restype = C.c_int
+        L.llcomp_mi_codec_label_boxes.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 3 + [C.c_void_p, C.c_void_p]
     if "LLCOMP_MI_LIB" not in os.environ and L.llcomp_mi_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.llcomp_mi_abi_version()}, this binding was written for {ABI_VERSION}: rebuild the library")
     _lib = L

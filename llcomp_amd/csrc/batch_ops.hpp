@@ -1,5 +1,5 @@
-// batch_ops.hpp -- what every batch call knows (llcomp_mi_codec_mix_batch, _orient_batch, _compose_batch; DESIGN.md "Batch calls: what
-// the three share"): the element's size, the most samples of a batch, the check that a dense batch is one, and the way from a call's
+// batch_ops.hpp -- what every batch call knows (llcomp_mi_codec_mix_batch, _orient_batch, _compose_batch, _paste_batch and, for the shape
+// check, _label_boxes; DESIGN.md "Batch calls: what the three share"): the element's size, the most samples of a batch, the check that a dense batch is one, and the way from a call's
 // dtype and layout to the templates compiled for them.  Header only, host and device, plain C++: the planners (*_plan.cpp), the kernels
 // (*_kernels.hip), the drivers (codec.hip) and the stand-alone host checks all read it.  The 16-byte chunk of the kernels: batch_chunk.hpp.
 #pragma once

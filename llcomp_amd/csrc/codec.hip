@@ -20,8 +20,12 @@
 #include "mix.hpp"
 #include "compose.hpp"
 #include "compose_rule.hpp"
+#include "label_boxes.hpp"
+#include "label_boxes_rule.hpp"
 #include "orient.hpp"
 #include "orient_rule.hpp"
+#include "paste.hpp"
+#include "paste_rule.hpp"
 #include "photo.hpp"
 #include "resize.hpp"
 #include "snapshot.hpp"
@@ -865,6 +869,7 @@ void codec_release(llcomp_mi_codec* k) {
     dev_free(k->d_mix, k->done);
     dev_free(k->d_orient_tab, k->done);
     dev_free(k->d_compose_tab, k->done);
+    dev_free(k->d_paste_tab, k->done);
     dev_free(k->d_upd_goff, k->done);
     for (uint32_t i = 0; i < llcomp_mi_codec::kRegionsRing; ++i) {
         if (!k->h_regions[i]) continue;
@@ -1617,6 +1622,53 @@ int llcomp_mi_codec_compose_batch(llcomp_mi_codec* k, const void* d_src, uint32_
 uint64_t llcomp_mi_codec_compose_workspace_bytes(const llcomp_mi_codec* k, uint32_t n_dst, uint32_t n_pieces) {
     if (!k) return 0;
     return k->workspace_bytes + compose_table_bound(n_dst, n_pieces, k->g.c);
+}
+
+// Batch copy-paste (DESIGN.md "Batch copy-paste"): paste_check_memory refuses too.  A call without a piece that selects anything queues
+// nothing.
+int llcomp_mi_codec_paste_batch(llcomp_mi_codec* k, const void* d_src, const void* d_mask, uint32_t n_src, uint32_t iw, uint32_t ih, void* d_dst,
+                                uint32_t n_dst, uint32_t ow, uint32_t oh, uint32_t dtype, uint32_t layout, const llcomp_mi_paste_piece* pieces,
+                                uint32_t n_pieces, void* stream) {
+    if (!k || !d_dst) return LLCOMP_MI_BAD_ARGS;
+    const uint32_t c = k->g.c;
+    std::vector<uint32_t> value_bits;
+    if (int rc = paste_check_call(n_src, iw, ih, n_dst, ow, oh, c, dtype, layout, pieces, n_pieces, value_bits)) return rc;
+    const uint32_t esize = batch_esize(dtype);
+    if (int rc = paste_check_memory(d_src, uint64_t(n_src) * c * iw * ih * esize, d_mask, uint64_t(n_src) * iw * ih, d_dst,
+                                    uint64_t(n_dst) * c * ow * oh * esize, esize, n_pieces))
+        return rc;
+    PastePlan p;
+    paste_plan(n_dst, pieces, n_pieces, p);
+    if (p.samples.empty()) return LLCOMP_MI_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return batch_table_call(
+        k, k->d_paste_tab, k->paste_tab_cap, PasteTable(p.samples.size(), p.order.size()).bytes, paste_table_bound(n_dst, n_pieces), s,
+        [&](uint8_t* at) { paste_table_put(pieces, p, value_bits, c, layout, at); },
+        [&](const uint8_t* d_table) {
+            PasteLaunch o{};
+            o.d_src = static_cast<const uint8_t*>(d_src), o.d_mask = static_cast<const uint8_t*>(d_mask), o.d_dst = static_cast<uint8_t*>(d_dst);
+            o.d_table = d_table, o.n_samples = uint32_t(p.samples.size()), o.n_recs = uint32_t(p.order.size());
+            o.n_src = n_src, o.iw = iw, o.ih = ih, o.ow = ow, o.oh = oh, o.c = c, o.dtype = dtype, o.layout = layout;
+            return launch_paste(o, s);
+        });
+}
+
+uint64_t llcomp_mi_codec_paste_workspace_bytes(const llcomp_mi_codec* k, uint32_t n_dst, uint32_t n_pieces) {
+    if (!k) return 0;
+    return k->workspace_bytes + paste_table_bound(n_dst, n_pieces);
+}
+
+// Label boxes (DESIGN.md "Label boxes"): the codec gives the device; no table, no workspace.
+int llcomp_mi_codec_label_boxes(llcomp_mi_codec* k, const void* d_maps, uint32_t n, uint32_t ow, uint32_t oh, void* d_boxes, void* stream) {
+    if (!k || !d_maps || !d_boxes) return LLCOMP_MI_BAD_ARGS;
+    if (int rc = label_boxes_check_call(n, ow, oh)) return rc;
+    const uint64_t m = reinterpret_cast<uintptr_t>(d_maps), b = reinterpret_cast<uintptr_t>(d_boxes);
+    const uint64_t map_bytes = uint64_t(n) * ow * oh, box_bytes = uint64_t(n) * kLabelIds * sizeof(llcomp_mi_label_box);
+    if (misaligned(d_boxes, 4) || (m < b + box_bytes && b < m + map_bytes)) return LLCOMP_MI_BAD_ARGS;
+    DeviceGuard guard(k->device);
+    if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
+    HIP_TRY(launch_label_boxes(static_cast<const uint8_t*>(d_maps), n, ow, oh, static_cast<uint8_t*>(d_boxes), static_cast<hipStream_t>(stream)));
+    return LLCOMP_MI_OK;
 }
 
 uint64_t llcomp_mi_codec_photo_workspace_bytes(const llcomp_mi_codec* k, uint64_t total_views) {

@@ -78,6 +78,10 @@ struct llcomp_mi_codec {
     // (compose_plan.hpp: ComposeTable); grown by the calls that need more
     uint8_t* d_compose_tab = nullptr;
     uint64_t compose_tab_cap = 0;
+    // batch copy-paste (llcomp_mi_codec_paste_batch): where a call's one copy lands, the samples and the pieces with their id sets
+    // (paste_plan.hpp: PasteTable); grown by the calls that need more
+    uint8_t* d_paste_tab = nullptr;
+    uint64_t paste_tab_cap = 0;
     // region update (llcomp_mi_codec_encode_region / _update_region): the encoder runs on the box's sub-geometry, which can have MORE lane
     // groups than the full one, so its group offsets go to an array of their own, u64[n_slices + 1]; behind it, u64[lane groups + 1], the
     // full geometry's group offsets for the NEW table (d_group_off holds the old table's).  The decoded box shares d_box with the resized

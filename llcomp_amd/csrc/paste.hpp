@@ -1,0 +1,24 @@
+// paste.hpp -- the launcher of the batch copy-paste's kernel (paste_kernels.hip; codec.hip: llcomp_mi_codec_paste_batch; DESIGN.md "Batch
+// copy-paste").  What the host decides -- the checks, the sort by dst, the table: paste_plan.hpp.  The rule: paste_rule.hpp.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "paste_plan.hpp"
+
+namespace llcomp_mi {
+
+// One call: k_paste, one workgroup per tile, per plane (CHW) and per entry of the table's samples.  d_table: the call's table in device
+// memory (PasteTable), 4-byte aligned.
+struct PasteLaunch {
+    const uint8_t* d_src;
+    const uint8_t* d_mask;  // n_src * ih * iw bytes at any address
+    uint8_t* d_dst;         // src and dst aligned to the element
+    const uint8_t* d_table;
+    uint32_t n_samples, n_recs;  // of the table: the dst samples with workgroups, the pieces that are not ignored
+    uint32_t n_src, iw, ih, ow, oh, c, dtype, layout;  // checked (paste_check_call)
+};
+hipError_t launch_paste(const PasteLaunch& o, hipStream_t stream);
+
+}  // namespace llcomp_mi

@@ -1,0 +1,248 @@
+// paste_rule.hpp -- the rule of the batch copy-paste (include/llcomp_mi.h: "Batch copy-paste"), stated ONCE: these functions are compiled
+// into the kernel (paste_kernels.hip), into llcomp_mi_paste_reference and the planner's checks (paste_plan.cpp) and into the host check
+// that walks the kernel's own decisions without a GPU (tests/helpers/paste_plan_check.cpp).
+//
+// The batches, the tiles, the 16-byte units of dst MEMORY a tile owns, the shifted copy and the merge are the composition's
+// (compose_rule.hpp), by #include: a thread owns units of dst memory exactly as in k_compose, which is what keeps "written at most once"
+// true although WHICH elements are written now depends on device data.  What is the paste's own: the record with its id set, the mask
+// bytes of a unit's pixel span (paste_fetch_of, paste_selected) and the walk of the short list from the back (paste_finish), where an
+// element falls through a piece that covers it without selecting it.
+// Mem: load16 / store16 of aligned 16-byte units, load_el<N> of an N-byte element (N = 1: a mask byte), store_el of a dst element.
+#pragma once
+#include <cstdint>
+
+#include "../../include/llcomp_mi.h"
+#include "compose_rule.hpp"
+
+namespace llcomp_mi {
+
+constexpr uint32_t kPasteMaxPieces = 1u << 20;      // of a call
+constexpr uint32_t kPasteMaxPiecesPerSample = 256;  // with w and h above 0 on one dst sample: the workgroup's list in LDS
+
+LLMI_HD inline bool paste_id_set(const uint32_t* ids, uint32_t m) { return (ids[m >> 5] >> (m & 31u)) & 1u; }
+LLMI_HD inline bool paste_covers(const llcomp_mi_paste_piece& p, uint32_t x, uint32_t y) { return x - p.dx < p.w && y - p.dy < p.h; }
+LLMI_HD inline bool paste_empty(const llcomp_mi_paste_piece& p) { return !p.w || !p.h; }
+// ... or one that selects nothing: checked and ignored
+LLMI_HD inline bool paste_idle(const llcomp_mi_paste_piece& p) {
+    uint32_t any = 0;
+    for (uint32_t i = 0; i < 8; ++i) any |= p.ids[i];
+    return paste_empty(p) || !any;
+}
+
+// A piece as the kernel reads it: ComposeRec's eight words (columns in elements), the value in the dtype's bits, the id set.  68 bytes
+struct PasteRec {
+    ComposeRec r;
+    uint32_t value;
+    uint32_t ids[8];
+};
+LLMI_HD inline PasteRec paste_rec(const llcomp_mi_paste_piece& p, uint32_t cs, uint32_t value_bits) {
+    PasteRec o;
+    o.r = ComposeRec{p.src, p.dx * cs, p.dy, p.sx * cs, p.sy, p.w * cs, p.h, p.flags};
+    o.value = value_bits;
+    for (uint32_t i = 0; i < 8; ++i) o.ids[i] = p.ids[i];
+    return o;
+}
+
+// One call as the kernel sees it: the composition's geometry under KEEP (there is no fill) and the mask batch, bytes at any address
+struct PasteGeom {
+    ComposeGeom g;
+    uint64_t mask, mask_bytes;
+    uint32_t iw;
+};
+LLMI_HD inline PasteGeom paste_geom(uint64_t dst, uint64_t src, uint64_t mask, uint32_t n_src, uint32_t iw, uint32_t ih, uint32_t ow, uint32_t oh,
+                                    uint32_t c, uint32_t esize, bool chw) {
+    PasteGeom pg;
+    pg.g = compose_geom(dst, src, n_src, iw, ih, ow, oh, c, esize, chw, true);
+    pg.mask = mask, pg.mask_bytes = uint64_t(n_src) * iw * ih, pg.iw = iw;
+    return pg;
+}
+// THE address of mask(s, y, 0)
+LLMI_HD inline uint64_t paste_mask_row(const PasteGeom& pg, uint32_t s, uint32_t y) { return pg.mask + (uint64_t(s) * pg.g.ih + y) * pg.iw; }
+
+// THE rule, per pixel: does piece p select (x, y) of its dst sample?
+template <class Mem>
+LLMI_HD inline bool paste_selects(const PasteGeom& pg, const llcomp_mi_paste_piece& p, uint32_t x, uint32_t y, Mem& mem) {
+    if (!paste_covers(p, x, y)) return false;
+    return paste_id_set(p.ids, mem.template load_el<1>(paste_mask_row(pg, p.src, p.sy + (y - p.dy)) + p.sx + (x - p.dx)));
+}
+
+// What a workgroup knows beside its geometry, the same in every thread
+struct PasteWork {
+    const PasteRec* list;  // the pieces that matter to the tile, in order
+    uint32_t n_list;
+    uint32_t d, pl;  // the dst sample and the plane
+};
+
+// The mask bytes of the elements [e0, e1) of the unit's row in piece r: byte 0 is the pixel of e0, at `at`; the unit's element p0 is
+// e0 and its channel is ph0 (HWC; CHW: 0).  They lie in the aligned unit at a, from byte sh on, and, with two, in the next one;
+// inside: those units lie whole in the mask batch.
+struct PasteFetch {
+    uint64_t at, a;
+    uint32_t sh, two, inside;
+    uint32_t p0, n_el, ph0;
+};
+LLMI_HD inline PasteFetch paste_fetch_of(const PasteGeom& pg, const ComposeRec& r, uint32_t y, int32_t eu, uint32_t e0, uint32_t e1) {
+    const uint32_t cs = pg.g.cs, se0 = r.sxe + (e0 - r.dxe), spx0 = cs == 1 ? se0 : se0 / cs;
+    PasteFetch f;
+    f.ph0 = se0 - spx0 * cs, f.p0 = uint32_t(int32_t(e0) - eu), f.n_el = e1 - e0;  // (a pixel has an element at least: n_el bytes hold them)
+    f.at = paste_mask_row(pg, r.src, r.sy + (y - r.dy)) + spx0;
+    f.a = f.at & ~uint64_t(15), f.sh = uint32_t(f.at & 15u), f.two = f.sh + f.n_el > 16u;
+    f.inside = f.a >= pg.mask && f.a + (f.two ? 32u : 16u) <= pg.mask + pg.mask_bytes;
+    return f;
+}
+
+// What a thread does with one unit of dst memory at address u in row y, decided before anything is read: nothing where no piece of the
+// list reaches the unit's elements of the row; otherwise the walk from piece `hit` down, whose mask units (f) the tile pass asks for
+// ahead of the walk
+struct PasteTodo {
+    uint32_t work;
+    uint32_t y, e_lo, e_hi;  // the unit's elements of the row
+    int32_t eu;              // the row's element that the unit's first would be (compose_rule.hpp: ComposeTodo)
+    int32_t hit;
+    uint64_t u;
+    PasteFetch f;
+};
+// the elements of the unit's row that r reaches: [e0, e1), false for none
+LLMI_HD inline bool paste_reach(const ComposeRec& r, const PasteTodo& t, uint32_t& e0, uint32_t& e1) {
+    if (t.y - r.dy >= r.h) return false;
+    e0 = t.e_lo > r.dxe ? t.e_lo : r.dxe, e1 = t.e_hi < r.dxe + r.ew ? t.e_hi : r.dxe + r.ew;
+    return e0 < e1;
+}
+template <uint32_t ES>
+LLMI_HD inline PasteTodo paste_decide(const PasteGeom& pg, const PasteWork& k, uint32_t y, uint64_t row_addr, uint64_t u) {
+    const uint64_t row_end = row_addr + uint64_t(pg.g.rwd) * ES;
+    PasteTodo t{};
+    t.y = y, t.u = u;
+    t.eu = int32_t((int64_t(u) - int64_t(row_addr)) / int64_t(ES));
+    t.e_lo = t.eu > 0 ? uint32_t(t.eu) : 0u;
+    t.e_hi = u + 16 < row_end ? uint32_t((u + 16 - row_addr) / ES) : pg.g.rwd;
+    t.hit = -1;
+    for (uint32_t i = k.n_list; i-- > 0;) {
+        uint32_t e0, e1;
+        if (!paste_reach(k.list[i].r, t, e0, e1)) continue;
+        t.work = 1, t.hit = int32_t(i);
+        t.f = paste_fetch_of(pg, k.list[i].r, y, t.eu, e0, e1);
+        break;
+    }
+    return t;
+}
+
+// The elements of [e0, e1) of the unit that r selects, as a mask with bit p for the unit's element p: the mask bytes of their pixels as
+// ONE shifted copy of the aligned units that hold them (lo, hi: already loaded when `have`), single bytes only where such a unit sticks
+// out of the mask batch; each byte against the id words; a pixel's bit to its elements (c of them in HWC, one in CHW).
+template <uint32_t ES, class Mem>
+LLMI_HD inline uint32_t paste_selected(const PasteGeom& pg, const PasteRec& r, const PasteFetch& f, bool have, const ComposeChunk& lo,
+                                       const ComposeChunk& hi, Mem& mem) {
+    constexpr uint32_t PER = 16 / ES;
+    const uint32_t cs = pg.g.cs;
+    ComposeChunk mv{{0u, 0u, 0u, 0u}};
+    if (f.inside) {
+        const ComposeChunk zero{{0u, 0u, 0u, 0u}};
+        const ComposeChunk a = have ? lo : mem.load16(f.a);
+        mv = f.sh ? compose_shift(a, f.two ? (have ? hi : mem.load16(f.a + 16)) : zero, f.sh) : a;
+    } else {  // at the first or the last bytes of the mask batch: the bytes that belong, one by one
+        const uint32_t npx = cs == 1 ? f.n_el : (f.ph0 + f.n_el + cs - 1) / cs;
+        LLMI_UNROLL
+        for (uint32_t j = 0; j < PER; ++j)
+            if (j < npx) chunk_or<1>(mv.w, j, mem.template load_el<1>(f.at + j));
+    }
+    uint32_t selpx = 0;
+    LLMI_UNROLL
+    for (uint32_t j = 0; j < PER; ++j) selpx |= uint32_t(paste_id_set(r.ids, chunk_get<1>(mv.w, j))) << j;
+    const uint32_t span = compose_span(f.p0, f.p0 + f.n_el);
+    if (cs == 1) return (selpx << f.p0) & span;
+    uint32_t em = 0, j = 0, ph = f.ph0;
+    LLMI_UNROLL
+    for (uint32_t p = 0; p < PER; ++p) {
+        if (!((span >> p) & 1u)) continue;
+        em |= ((selpx >> j) & 1u) << p;
+        if (++ph == cs) ph = 0, ++j;
+    }
+    return em;
+}
+
+// a VALUE piece's unit: the value in every element
+template <uint32_t ES>
+LLMI_HD inline ComposeChunk paste_value_unit(uint32_t bits) {
+    const uint32_t w = ES == 4 ? bits : ES == 2 ? (bits & 0xFFFFu) * 0x00010001u : (bits & 0xFFu) * 0x01010101u;
+    return ComposeChunk{{w, w, w, w}};
+}
+
+// ... and the walk.  The list from `hit` down: every piece that reaches elements nobody has claimed yet is asked which of them it
+// selects, and gives those from its own shifted copy of the unit (compose_rule.hpp) or from its value, until the unit's elements of the
+// row are claimed or the list ends.  16 bytes are stored when all 16 are claimed, the claimed elements one by one otherwise, nothing
+// when none is.
+template <uint32_t ES, class Mem>
+LLMI_HD inline void paste_finish(const PasteGeom& pg, const PasteWork& k, const PasteTodo& t, const ComposeChunk& lo, const ComposeChunk& hi, Mem& mem) {
+    constexpr uint32_t PER = 16 / ES;
+    if (!t.work) return;
+    const ComposeGeom& g = pg.g;
+    const uint32_t need = compose_span(uint32_t(int32_t(t.e_lo) - t.eu), uint32_t(int32_t(t.e_hi) - t.eu));
+    ComposeChunk acc{{0u, 0u, 0u, 0u}};
+    uint32_t claimed = 0;
+    for (uint32_t i = uint32_t(t.hit) + 1; i-- > 0 && claimed != need;) {
+        const PasteRec& r = k.list[i];
+        uint32_t e0, e1;
+        if (!paste_reach(r.r, t, e0, e1)) continue;
+        const uint32_t open = compose_span(uint32_t(int32_t(e0) - t.eu), uint32_t(int32_t(e1) - t.eu)) & ~claimed;
+        if (!open) continue;
+        const bool first = int32_t(i) == t.hit;
+        const uint32_t m = paste_selected<ES>(pg, r, first ? t.f : paste_fetch_of(pg, r.r, t.y, t.eu, e0, e1), first, lo, hi, mem) & open;
+        if (!m) continue;
+        ComposeChunk v{{0u, 0u, 0u, 0u}};
+        if (r.r.flags & LLCOMP_MI_PASTE_VALUE) {
+            v = paste_value_unit<ES>(r.value);
+        } else {
+            const uint64_t s = compose_src_of_unit(g, ES, r.r, k.pl, t.y, t.eu);
+            if (compose_src_units_inside(g, s)) {
+                const ComposeChunk a = mem.load16(s & ~uint64_t(15));
+                v = (s & 15u) ? compose_shift(a, mem.load16((s & ~uint64_t(15)) + 16), uint32_t(s & 15u)) : a;
+            } else {  // at the first or the last bytes of the src batch: the elements that belong, one by one
+                LLMI_UNROLL
+                for (uint32_t p = 0; p < PER; ++p)
+                    if ((m >> p) & 1u) chunk_or<ES>(v.w, p, mem.template load_el<ES>(s + uint64_t(p) * ES));
+            }
+        }
+        acc = compose_merge<ES>(acc, v, m);
+        claimed |= m;
+    }
+    if (!claimed) return;
+    if (claimed == (1u << PER) - 1u) return mem.store16(t.u, acc);
+    LLMI_UNROLL
+    for (uint32_t p = 0; p < PER; ++p)
+        if ((claimed >> p) & 1u) mem.store_el(t.u + uint64_t(p) * ES, chunk_get<ES>(acc.w, p));
+}
+
+// One tile's rows and units, thread `tid` of `threads`, as compose_tile_pass: a thread decides kPasteBatch units and asks for the mask
+// units of all of them before it walks the first, so that its loads are in flight together.
+constexpr uint32_t kPasteBatch = 2;
+template <uint32_t ES, class Mem>
+LLMI_HD inline void paste_tile_pass(const PasteGeom& pg, const PasteWork& k, const ComposeTileBox& b, uint32_t tid, uint32_t threads, Mem& mem) {
+    const ComposeGeom& g = pg.g;
+    const uint32_t upr = compose_units_per_row(g.tile_w, ES), total = (b.y1 - b.y0) * upr;
+    for (uint32_t i0 = tid; i0 < total; i0 += threads * kPasteBatch) {
+        PasteTodo todo[kPasteBatch];
+        ComposeChunk lo[kPasteBatch], hi[kPasteBatch];
+        LLMI_UNROLL
+        for (uint32_t j = 0; j < kPasteBatch; ++j) {
+            const uint32_t i = i0 + j * threads;
+            todo[j] = PasteTodo{};
+            lo[j] = hi[j] = ComposeChunk{{0u, 0u, 0u, 0u}};
+            if (i >= total) continue;
+            const uint32_t row = i / upr, col = i - row * upr, y = b.y0 + row;
+            const uint64_t row_addr = compose_dst_row(g, ES, k.d, k.pl, y);
+            const ComposeUnits un = compose_row_units(b, ES, row_addr);
+            const uint64_t u = un.first + 16 * uint64_t(col);
+            if (u >= un.end) continue;
+            todo[j] = paste_decide<ES>(pg, k, y, row_addr, u);
+            if (todo[j].work && todo[j].f.inside) {
+                lo[j] = mem.load16(todo[j].f.a);
+                if (todo[j].f.two) hi[j] = mem.load16(todo[j].f.a + 16);
+            }
+        }
+        LLMI_UNROLL
+        for (uint32_t j = 0; j < kPasteBatch; ++j) paste_finish<ES>(pg, k, todo[j], lo[j], hi[j], mem);
+    }
+}
+
+}  // namespace llcomp_mi
