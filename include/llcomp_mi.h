@@ -739,8 +739,9 @@ uint32_t llcomp_mi_compose_max_pieces_per_sample(void);
  * of 2^31 elements or more; a piece with dst >= n_dst or src >= n_src, with a source rectangle that leaves iw x ih or a dst rectangle
  * that leaves ow x oh, with flag bits above bit 0, with a value that is not 0 without VALUE, or with a bad value under VALUE; more than
  * llcomp_mi_paste_max_pieces_per_sample() = 256 pieces with w and h above 0 on one dst sample.
- * NOT covered: more than 256 ids per map (16-bit id maps), blended (alpha or Gaussian) paste borders, a src and dst of different dtype
- * or layout, pieces that resample or mirror (views do that at decode), a dst that overlaps its src, per-piece fills per channel. */
+ * NOT covered: blended (alpha or Gaussian) paste borders, a src and dst of different dtype or layout, pieces that resample or mirror
+ * (views do that at decode), a dst that overlaps its src, per-piece fills per channel.  More than 256 ids per map (16-bit id maps):
+ * "Batch copy-paste by 16-bit ids" below. */
 #define LLCOMP_MI_PASTE_VALUE 1u
 typedef struct llcomp_mi_paste_piece {
     uint32_t dst, src;
@@ -764,6 +765,40 @@ int llcomp_mi_paste_plan(uint32_t n_src, uint32_t iw, uint32_t ih, uint32_t n_ds
                          uint32_t layout, const llcomp_mi_paste_piece* pieces, uint32_t n_pieces, uint32_t* samples, uint32_t* first,
                          uint32_t* order, uint32_t* n_samples, uint64_t* n_workgroups);
 uint32_t llcomp_mi_paste_max_pieces_per_sample(void);
+/* Batch copy-paste by 16-bit ids (llcomp_mi_codec_paste_batch16 below): the rule of "Batch copy-paste" with a 16-bit mask, for the
+ * instance and panoptic label sets with more than 256 ids per map (Cityscapes' class * 1000 + k, Mapillary Vistas' class * 256 + k,
+ * ADE20K, KITTI-STEP, cell masks).  src, dst, painter's order, "the last piece that selects a pixel gives it" and "what no piece
+ * selects stays and is not written" are unchanged.  mask is n_src samples of ih x iw little-endian uint16_t, dense, aligned to 2 bytes
+ * and to nothing more: mask16(s, y, x).  A u16 map stored as a two-channel container (low byte in channel 0) decodes to one with the
+ * nearest filter in U8 HWC.  Piece p selects (x, y) when its rectangle holds the pixel and, for m = mask16(src_p, sy + y - dy,
+ * sx + x - dx), m - id_base < 256 holds in 32-bit unsigned arithmetic and bit m - id_base of ids is set.  A set of ids wider than 256
+ * is several pieces over the same rectangle; the per-sample limit stays llcomp_mi_paste_max_pieces_per_sample() = 256 pieces.
+ * id_base + 255 may pass 65535: those bits select nothing, and a piece with no other bit set is checked and ignored.  A VALUE piece's
+ * value is given as BITS, value_bits, the element's bits in its low esize bytes, the same in every channel: a VALUE piece writes a new
+ * 16-bit id into a dst map that is passed as a 2-byte dtype with c == 1 (elements are never interpreted, so F16 or BF16 serve) -- the
+ * renumbering call of a Copy-Paste.  dst must not overlap src or mask in bytes; src and mask may be one buffer: for U8 HWC with c == 2,
+ * and for a 2-byte dtype with c == 1, the id maps are their own source -- that is how a 16-bit class or instance map is pasted by id.
+ * BAD_ARGS: the cases of "Batch copy-paste" (but for its value), an id_base above 65535, a value_bits that is not 0 without VALUE or
+ * that has bits above the element.
+ * NOT covered: ids of 3 or 4 bytes (COCO panoptic's RGB ids), maps at odd addresses, blended borders, and what "Batch copy-paste" does
+ * not cover. */
+typedef struct llcomp_mi_paste_piece16 {
+    uint32_t dst, src;
+    uint32_t dx, dy, sx, sy, w, h;
+    uint32_t flags;        /* bit 0 LLCOMP_MI_PASTE_VALUE */
+    uint32_t value_bits;   /* VALUE: the element's bits in its low esize bytes, the same in every channel; 0 without VALUE */
+    uint32_t id_base;      /* 0..65535 */
+    uint32_t ids[8];       /* bit j set: id id_base + j is selected */
+} llcomp_mi_paste_piece16; /* 76 bytes */
+/* The rule above on host memory, as llcomp_mi_paste_reference.  BAD_ARGS, out untouched: the cases above, a NULL out or dst_in, a NULL
+ * src or mask with n_pieces > 0, src or out not aligned to the element, a mask not aligned to 2 bytes.  Host-only. */
+int llcomp_mi_paste16_reference(const void* src, const void* mask, uint32_t n_src, uint32_t iw, uint32_t ih, const void* dst_in, uint32_t n_dst,
+                                uint32_t ow, uint32_t oh, uint32_t c, uint32_t dtype, uint32_t layout, const llcomp_mi_paste_piece16* pieces,
+                                uint32_t n_pieces, void* out);
+/* What a call does: the outputs of llcomp_mi_paste_plan.  Host-only. */
+int llcomp_mi_paste16_plan(uint32_t n_src, uint32_t iw, uint32_t ih, uint32_t n_dst, uint32_t ow, uint32_t oh, uint32_t c, uint32_t dtype,
+                           uint32_t layout, const llcomp_mi_paste_piece16* pieces, uint32_t n_pieces, uint32_t* samples, uint32_t* first,
+                           uint32_t* order, uint32_t* n_samples, uint64_t* n_workgroups);
 /* Label boxes (llcomp_mi_codec_label_boxes below: torchvision's masks_to_boxes of every instance of an id map, with the areas): maps is
  * n samples of oh x ow bytes, dense, at any byte address -- an instance id or class id per pixel, as the containers of label images
  * decode, behind any crop, affine, perspective, flip, mosaic or paste.  The output is n * 256 records; for sample i and id m, record
@@ -771,7 +806,7 @@ uint32_t llcomp_mi_paste_max_pieces_per_sample(void);
  * {0, ow, oh, 0, 0}, the identities of min and max, so records of two maps merge by min, max and add.  masks_to_boxes of instance m is
  * (x0, y0, x1 - 1, y1 - 1), and count its area.  Every record is written: the caller initialises nothing.
  * BAD_ARGS: n of 0 or above 65535, ow or oh of 0, ow * oh of 2^32 or more, a batch no address space holds, a NULL pointer.
- * NOT covered: more than 256 ids per map (16-bit id maps). */
+ * More than 256 ids per map (16-bit id maps): "Label boxes of listed ids" below. */
 typedef struct llcomp_mi_label_box {
     uint32_t count, x0, y0, x1, y1;
 } llcomp_mi_label_box;     /* 20 bytes */
@@ -779,6 +814,21 @@ typedef struct llcomp_mi_label_box {
 int llcomp_mi_label_boxes_reference(const void* maps, uint32_t n, uint32_t ow, uint32_t oh, llcomp_mi_label_box* out);
 /* The rows of the band of a sample that a workgroup of llcomp_mi_codec_label_boxes takes (DESIGN.md "Label boxes"): a constant */
 uint32_t llcomp_mi_label_boxes_rows(void);
+/* Label boxes of listed ids (llcomp_mi_codec_label_boxes16 below: "Label boxes" above for the 16-bit id maps of instance and panoptic
+ * label sets -- Cityscapes' class * 1000 + k, Mapillary Vistas' class * 256 + k, ADE20K, KITTI-STEP, cell masks): maps is n samples of
+ * oh x ow little-endian uint16_t, dense, aligned to 2 bytes and to nothing more -- what a u16 map stored as a two-channel container
+ * (low byte in channel 0) decodes to with the nearest filter in U8 HWC.  The caller NAMES the ids it wants: sample i lists
+ * ids[first[i] .. first[i + 1]), strictly ascending, first[0] == 0, at most llcomp_mi_label_boxes16_max_ids() = 4096 ids per sample and
+ * first[n] <= 2^20 in all.  The output is first[n] records of llcomp_mi_label_box: record first[i] + j is for id ids[first[i] + j] of
+ * sample i, its pixel count and box, {0, ow, oh, 0, 0} without a pixel.  Every record is written.  Pixels whose id is not listed are
+ * counted nowhere; a sample with an empty list costs nothing.
+ * BAD_ARGS: the cases of "Label boxes", a NULL ids or first, first[0] != 0, a first that decreases, a list of more than 4096 ids, more
+ * than 2^20 ids in all, a list that is not strictly ascending, maps not aligned to 2 bytes.
+ * NOT covered: ids of 3 or 4 bytes (COCO panoptic's RGB ids), maps at odd addresses. */
+int llcomp_mi_label_boxes16_reference(const void* maps, uint32_t n, uint32_t ow, uint32_t oh, const uint16_t* ids, const uint32_t* first,
+                                      llcomp_mi_label_box* out);
+/* The most ids a sample lists: 22 bytes of a workgroup's LDS per listed id, one workgroup to a CU at the top capacity.  A constant. */
+uint32_t llcomp_mi_label_boxes16_max_ids(void);
 uint32_t llcomp_mi_slice_count(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar);
 /* Slice width for one-row slices (tile_h = 1) when `frames` frames are coded per call: the widest slice (64..480 pixels) that
  * still keeps about four wavefronts per SIMD busy.  A call that codes few frames is latency-bound with wide slices; this
@@ -1174,12 +1224,36 @@ int llcomp_mi_codec_paste_batch(llcomp_mi_codec* codec, const void* d_src, const
 /* The bound on llcomp_mi_codec_allocated_bytes with such calls of up to n_dst dst samples and n_pieces pieces among the codec's calls:
  * llcomp_mi_codec_workspace_bytes + 12 * n_dst + 68 * n_pieces, the table of a call.  0 for a NULL codec. */
 uint64_t llcomp_mi_codec_paste_workspace_bytes(const llcomp_mi_codec* codec, uint32_t n_dst, uint32_t n_pieces);
+/* Batch copy-paste by 16-bit ids (the rule: "Batch copy-paste by 16-bit ids" above): llcomp_mi_codec_paste_batch with d_mask the 16-bit
+ * id maps, n_src x ih x iw uint16_t aligned to 2 bytes, and pieces of llcomp_mi_paste_piece16.  One kernel on the composition's tiles
+ * and 16-byte units of dst memory; a unit's mask pixels come as shifted copies of the one to three aligned units of mask memory that
+ * hold them.  BAD_ARGS, nothing queued: llcomp_mi_codec_paste_batch's cases, a d_mask not aligned to 2 bytes, and
+ * llcomp_mi_paste16_plan's cases. */
+int llcomp_mi_codec_paste_batch16(llcomp_mi_codec* codec, const void* d_src, const void* d_mask, uint32_t n_src, uint32_t iw, uint32_t ih,
+                                  void* d_dst, uint32_t n_dst, uint32_t ow, uint32_t oh, uint32_t dtype, uint32_t layout,
+                                  const llcomp_mi_paste_piece16* pieces, uint32_t n_pieces, void* stream);
+/* The bound on llcomp_mi_codec_allocated_bytes with such calls of up to n_dst dst samples and n_pieces pieces among the codec's calls:
+ * llcomp_mi_codec_workspace_bytes + 12 * n_dst + 72 * n_pieces, the table of a call.  0 for a NULL codec. */
+uint64_t llcomp_mi_codec_paste16_workspace_bytes(const llcomp_mi_codec* codec, uint32_t n_dst, uint32_t n_pieces);
 /* Label boxes (the rule: "Label boxes" above): the 256 records of each of the n id maps at d_maps, oh x ow bytes each whatever the
  * codec's c, into d_boxes, n * 256 records in device memory, asynchronously on `stream`.  The codec gives the device and nothing else:
  * no table, no workspace.  Two kernels: one writes the identities, one has a workgroup per band of llcomp_mi_label_boxes_rows() rows of
  * a sample, which merges its records into d_boxes with integer atomics, so the result does not depend on order.  BAD_ARGS, nothing
  * queued: a NULL codec, the reference's cases, d_boxes not aligned to 4, d_boxes overlapping the maps. */
 int llcomp_mi_codec_label_boxes(llcomp_mi_codec* codec, const void* d_maps, uint32_t n, uint32_t ow, uint32_t oh, void* d_boxes, void* stream);
+/* Label boxes of listed ids (the rule: "Label boxes of listed ids" above): the first[n] records of the ids listed for the n 16-bit id
+ * maps at d_maps, oh x ow uint16_t each whatever the codec's c, into d_boxes in device memory, asynchronously on `stream`.  ids and
+ * first are HOST memory, read during the call only: they travel in ONE copy from the codec's pinned ring into a device buffer of this
+ * call's own.  Two kernels: one writes the identities, one has a workgroup per band of llcomp_mi_label_boxes_rows() rows of a LISTED
+ * sample, which holds the sample's list and records in LDS (capacities of 256, 1024 and 4096 ids: the call runs the smallest that
+ * holds its longest list), finds every run's id by binary search, and merges into d_boxes with integer atomics, so the result does
+ * not depend on order.  A call with first[n] == 0 queues nothing.  BAD_ARGS, nothing queued and nothing written: a NULL codec, the
+ * reference's cases, d_boxes not aligned to 4, records that overlap the maps. */
+int llcomp_mi_codec_label_boxes16(llcomp_mi_codec* codec, const void* d_maps, uint32_t n, uint32_t ow, uint32_t oh, const uint16_t* ids,
+                                  const uint32_t* first, void* d_boxes, void* stream);
+/* The bound on llcomp_mi_codec_allocated_bytes with such calls of up to n samples and total_ids listed ids among the codec's calls:
+ * llcomp_mi_codec_workspace_bytes + 4 * (2 * n + 1) + 2 * total_ids, the table of a call.  0 for a NULL codec. */
+uint64_t llcomp_mi_codec_label_boxes16_workspace_bytes(const llcomp_mi_codec* codec, uint32_t n, uint32_t total_ids);
 /* Stage-A only (context + prediction model), for tests and profiling: d_sym u32[frames*h*w*c],
  * low 16 bits = folded context (0..7925), high 16 bits = folded residual (two's complement). */
 int llcomp_mi_codec_model(llcomp_mi_codec* codec, const void* d_px, void* d_sym, void* stream);

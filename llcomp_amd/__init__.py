@@ -39,8 +39,12 @@ with ctypes and keeps the reference's names and error behaviour:
         fill or kept: Mosaic, make_grid, batch_images, Cutout with several holes, GridMask)
     PASTE_VALUE / paste_pieces / paste_plan / paste_reference / paste_max_pieces_per_sample / Codec.paste_batch /
         Codec.paste_workspace_bytes  (the objects of one decoded sample into another, chosen by the ids of an id map: Simple Copy-Paste)
+    PastePiece16 / paste_pieces16 / paste16_plan / paste16_reference / Codec.paste_batch16 / Codec.paste16_workspace_bytes  (the same
+        selected by a 16-bit id map, a piece a window of 256 ids from id_base on: Cityscapes, Mapillary Vistas, ADE20K instance ids)
     LABEL_BOX_DTYPE / label_boxes_reference / label_boxes_rows / Codec.label_boxes  (the pixel count and bounding box of each of the 256
         ids of every id map of a batch: torchvision's masks_to_boxes)
+    label_boxes16_reference / label_boxes16_max_ids / Codec.label_boxes16 / Codec.label_boxes16_workspace_bytes  (the same for the ids
+        the caller lists per sample, in 16-bit id maps: Cityscapes, Mapillary Vistas, ADE20K instance ids)
     RawImage(pixels, width, height, channels)     <->  llcomp::RawImage         (/root/reference/llcomp.hpp:454-459)
     EXT = ".llcomp"                               <->  llcomp::ext              (/root/reference/llcomp.hpp:18)
 
@@ -61,6 +65,7 @@ from ._lib import PerspectiveView as _PerspectiveView, PerspectiveGroup as _Pers
 from ._lib import PhotoOp as _PhotoOp, PhotoChain as _PhotoChain, PhotoGroup as _PhotoGroup
 from ._lib import ComposePiece as _ComposePiece
 from ._lib import PastePiece as _PastePiece
+from ._lib import PastePiece16
 from ._lib import MixSample as _MixSample
 
 EXT = ".llcomp"
@@ -886,6 +891,93 @@ def paste_reference(src, mask, dst, pieces, layout="chw", dtype=None):
     return out
 
 
+def paste_pieces16(records):
+    """The pieces of a paste_batch16 call (llcomp_mi_paste_piece16) as a ctypes array: every record a tuple (dst, src, dx, dy, sx, sy, w,
+    h, ids[, value_bits]).  ids: an iterable of ints 0..65535, the ids of the 16-bit mask the record selects, or "nonzero" for all of
+    them but 0.  A record becomes one piece per window of 256 ids that holds one of its ids, windows ascending, in the records' order:
+    a window begins at its lowest id.  value_bits makes VALUE pieces: the selected pixels take these bits as their element in every
+    channel, not src's.  A record without an id gives one piece that selects nothing.  The library checks the rest."""
+    if isinstance(records, C.Array) and records._type_ is PastePiece16:
+        return records
+    out = []
+    for r in list(records):
+        vals = list(r) if isinstance(r, (tuple, list)) else []
+        if len(vals) not in (9, 10):
+            raise LlcompError(BAD_ARGS, f"a piece is (dst, src, dx, dy, sx, sy, w, h, ids[, value_bits]), got {r!r}")
+        nums = [int(v) for v in vals[:8]]
+        if min(nums) < 0 or max(nums) > 0xFFFFFFFF:
+            raise LlcompError(BAD_ARGS, f"a piece takes unsigned values, got {r!r}")
+        ids = vals[8]
+        if isinstance(ids, str):
+            if ids != "nonzero":
+                raise LlcompError(BAD_ARGS, f'ids are ints 0..65535 or "nonzero", got {ids!r}')
+            ids = range(1, 65536)
+        ids = np.unique(np.asarray(list(ids), np.int64).reshape(-1))
+        if ids.size and (ids[0] < 0 or ids[-1] > 0xFFFF):
+            raise LlcompError(BAD_ARGS, f"an id is 0..65535, got {int(ids[0] if ids[0] < 0 else ids[-1])}")
+        value = None
+        if len(vals) == 10 and vals[9] is not None:
+            value = int(vals[9])
+            if not 0 <= value <= 0xFFFFFFFF:
+                raise LlcompError(BAD_ARGS, f"value_bits are the element's bits, got {vals[9]!r}")
+        at = 0
+        while True:
+            p = PastePiece16()
+            for name, v in zip(("dst", "src", "dx", "dy", "sx", "sy", "w", "h"), nums):
+                setattr(p, name, v)
+            if value is not None:
+                p.flags, p.value_bits = PASTE_VALUE, value
+            if ids.size:
+                p.id_base = int(ids[at])
+                end = int(np.searchsorted(ids, p.id_base + 256))
+                for m in ids[at:end]:
+                    d = int(m) - p.id_base
+                    p.ids[d >> 5] |= 1 << (d & 31)
+                at = end
+            out.append(p)
+            if at >= ids.size:
+                break
+    arr = (PastePiece16 * len(out))()
+    for i, p in enumerate(out):
+        arr[i] = p
+    return arr
+
+
+def paste16_plan(n_src, iw, ih, n_dst, ow, oh, c, pieces, dtype="float32", layout="chw"):
+    """What a paste_batch16 call does (llcomp_mi_paste16_plan, host only) -> (samples, first, order, n_workgroups), as paste_plan; order
+    indexes the pieces of paste_pieces16(pieces), one per window."""
+    recs = paste_pieces16(pieces)
+    n_dst = int(n_dst)
+    samples, first, order = np.zeros(max(n_dst, 1), np.uint32), np.zeros(max(n_dst, 1) + 1, np.uint32), np.zeros(max(len(recs), 1), np.uint32)
+    ns, nw = C.c_uint32(0), C.c_uint64(0)
+    u32p = C.POINTER(C.c_uint32)
+    _check(_lib.load().llcomp_mi_paste16_plan(int(n_src), int(iw), int(ih), n_dst, int(ow), int(oh), int(c), _dtype_code(dtype), _layout_code(layout),
+                                              recs, len(recs), samples.ctypes.data_as(u32p), first.ctypes.data_as(u32p), order.ctypes.data_as(u32p),
+                                              C.byref(ns), C.byref(nw)))
+    n = ns.value
+    return samples[:n].copy(), first[:n + 1].copy(), order[:int(first[n])].copy(), int(nw.value)
+
+
+def paste16_reference(src, mask, dst, pieces, layout="chw", dtype=None):
+    """The rule of the batch copy-paste by 16-bit ids on host arrays (llcomp_mi_paste16_reference): src and dst as paste_reference's,
+    mask [n_src, ih, iw] uint16 -- or src itself where src IS the id maps: uint8 "hwc" with c = 2, or a 2-byte dtype with c = 1 -> the
+    pasted dst batch, a new array."""
+    d, code, lay, n_dst, c, oh, ow = _batch_array(dst, dtype, layout)
+    s = np.ascontiguousarray(src)
+    if s.ndim != 4 or s.dtype != d.dtype or (s.shape[1] if lay == LAYOUT_CHW else s.shape[3]) != c:
+        raise LlcompError(BAD_ARGS, f"src is a 4-D batch of dst's type and channels, got {s.dtype} of shape {s.shape}")
+    n_src = s.shape[0]
+    ih, iw = s.shape[2:] if lay == LAYOUT_CHW else s.shape[1:3]
+    m = s if mask is src else np.ascontiguousarray(mask)
+    if (m is not s and m.dtype != np.uint16) or m.nbytes != 2 * n_src * ih * iw:
+        raise LlcompError(BAD_ARGS, f"mask is uint16 [n_src, ih, iw], got {m.dtype} of shape {m.shape}")
+    recs = paste_pieces16(pieces)
+    out = np.empty_like(d)
+    _check(_lib.load().llcomp_mi_paste16_reference(s.ctypes.data, m.ctypes.data, n_src, iw, ih, d.ctypes.data, n_dst, ow, oh, c, code, lay, recs,
+                                                   len(recs), out.ctypes.data))
+    return out
+
+
 # a record of Codec.label_boxes (llcomp_mi_label_box): the pixels of an id and their box [x0, x1) x [y0, y1)
 LABEL_BOX_DTYPE = np.dtype([("count", "<u4"), ("x0", "<u4"), ("y0", "<u4"), ("x1", "<u4"), ("y1", "<u4")])
 
@@ -905,6 +997,38 @@ def label_boxes_reference(maps):
     out = np.zeros((max(n, 1), 256), LABEL_BOX_DTYPE)
     _check(_lib.load().llcomp_mi_label_boxes_reference(a.ctypes.data if a.size else None, n, ow, oh, out.ctypes.data))
     return out[:n]
+
+
+def label_boxes16_max_ids():
+    """the most ids a sample of label_boxes16 lists (llcomp_mi_label_boxes16_max_ids)"""
+    return int(_lib.load().llcomp_mi_label_boxes16_max_ids())
+
+
+def _label_lists(ids, n):
+    """per-sample sequences of ids -> (ids uint16 [total], first uint32 [n + 1]); the library checks the order and the lengths"""
+    lists = [np.asarray(list(l), np.int64).reshape(-1) for l in ids]
+    if len(lists) != n:
+        raise LlcompError(BAD_ARGS, f"ids holds one sequence per sample, got {len(lists)} for {n} samples")
+    if any(l.size and (l.min() < 0 or l.max() > 0xFFFF) for l in lists):
+        raise LlcompError(BAD_ARGS, "an id is 0..65535")
+    first = np.zeros(n + 1, np.uint32)
+    first[1:] = np.cumsum([l.size for l in lists])
+    flat = np.concatenate(lists + [np.zeros(0, np.int64)]).astype(np.uint16)
+    return np.ascontiguousarray(np.append(flat, np.uint16(0))), first  # (a pointer that is never NULL)
+
+
+def label_boxes16_reference(maps, ids):
+    """The rule of the label boxes of listed ids on a host array (llcomp_mi_label_boxes16_reference): maps [n, oh, ow] uint16, ids a
+    sequence of n sequences of ids, each strictly ascending -> a flat array of LABEL_BOX_DTYPE, one record per listed id in the lists'
+    order; an id without a pixel has (0, ow, oh, 0, 0)."""
+    a = np.ascontiguousarray(maps)
+    if a.ndim != 3 or a.dtype != np.uint16:
+        raise LlcompError(BAD_ARGS, f"maps are uint16 [n, oh, ow], got {a.dtype} of shape {a.shape}")
+    n, oh, ow = a.shape
+    flat, first = _label_lists(ids, n)
+    out = np.zeros(max(int(first[n]), 1), LABEL_BOX_DTYPE)
+    _check(_lib.load().llcomp_mi_label_boxes16_reference(a.ctypes.data if a.size else None, n, ow, oh, flat.ctypes.data, first.ctypes.data, out.ctypes.data))
+    return out[:int(first[n])]
 
 
 def _view_groups(groups, c, signed=False):
@@ -1928,11 +2052,37 @@ class Codec:
         (llcomp_mi_codec_paste_workspace_bytes)"""
         return self._L.llcomp_mi_codec_paste_workspace_bytes(self._h, int(n_dst), int(n_pieces))
 
+    def paste_batch16(self, d_src, d_mask, n_src, iw, ih, d_dst, n_dst, ow, oh, pieces, dtype="float32", layout="chw", stream=0):
+        """paste_batch selected by 16-bit id maps (llcomp_mi_codec_paste_batch16): d_mask, n_src x ih x iw uint16 aligned to 2 bytes (it
+        may be d_src for uint8 "hwc" with c = 2, or a 2-byte dtype with c = 1); pieces from paste_pieces16(), or records for it.  What no
+        piece selects stays and is not written.  Asynchronous on `stream`."""
+        recs = paste_pieces16(pieces)
+        _check(self._L.llcomp_mi_codec_paste_batch16(self._h, d_src, d_mask, int(n_src), int(iw), int(ih), d_dst, int(n_dst), int(ow), int(oh),
+                                                     _dtype_code(dtype), _layout_code(layout), recs, len(recs), stream))
+
+    def paste16_workspace_bytes(self, n_dst, n_pieces):
+        """the bound on .allocated_bytes() with paste_batch16 calls of up to n_dst dst samples and n_pieces pieces
+        (llcomp_mi_codec_paste16_workspace_bytes)"""
+        return self._L.llcomp_mi_codec_paste16_workspace_bytes(self._h, int(n_dst), int(n_pieces))
+
     def label_boxes(self, d_maps, n, ow, oh, d_boxes, stream=0):
         """The pixel count and bounding box of each of the 256 ids of n id maps (llcomp_mi_codec_label_boxes): d_maps, n x oh x ow bytes
         at any address, -> d_boxes, n * 256 records of LABEL_BOX_DTYPE (20 bytes each, 4-byte aligned), both in device memory; every
         record is written.  Asynchronous on `stream`."""
         _check(self._L.llcomp_mi_codec_label_boxes(self._h, d_maps, int(n), int(ow), int(oh), d_boxes, stream))
+
+    def label_boxes16(self, d_maps, n, ow, oh, ids, d_boxes, stream=0):
+        """The pixel count and bounding box of the ids listed for each of n 16-bit id maps (llcomp_mi_codec_label_boxes16): d_maps,
+        n x oh x ow uint16 aligned to 2 bytes; ids, a sequence of n sequences of ids, each strictly ascending and of at most
+        label_boxes16_max_ids() ids -> d_boxes, one record of LABEL_BOX_DTYPE per listed id in the lists' order (4-byte aligned), both in
+        device memory; every record is written.  Asynchronous on `stream`; ids is read during the call."""
+        flat, first = _label_lists(ids, int(n))
+        _check(self._L.llcomp_mi_codec_label_boxes16(self._h, d_maps, int(n), int(ow), int(oh), flat.ctypes.data, first.ctypes.data, d_boxes, stream))
+
+    def label_boxes16_workspace_bytes(self, n, total_ids):
+        """the bound on .allocated_bytes() with label_boxes16 calls of up to n samples and total_ids listed ids
+        (llcomp_mi_codec_label_boxes16_workspace_bytes)"""
+        return self._L.llcomp_mi_codec_label_boxes16_workspace_bytes(self._h, int(n), int(total_ids))
 
     def views_workspace_bytes(self, total_views):
         """.workspace_bytes for calls of up to total_views views (llcomp_mi_codec_views_workspace_bytes): the staged tables grow with them"""

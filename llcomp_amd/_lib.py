@@ -58,6 +58,9 @@ SYMBOLS = [
     "llcomp_mi_paste_reference", "llcomp_mi_paste_plan", "llcomp_mi_paste_max_pieces_per_sample", "llcomp_mi_codec_paste_batch",
     "llcomp_mi_codec_paste_workspace_bytes",
     "llcomp_mi_label_boxes_reference", "llcomp_mi_label_boxes_rows", "llcomp_mi_codec_label_boxes",
+    "llcomp_mi_paste16_reference", "llcomp_mi_paste16_plan", "llcomp_mi_codec_paste_batch16", "llcomp_mi_codec_paste16_workspace_bytes",
+    "llcomp_mi_label_boxes16_reference", "llcomp_mi_label_boxes16_max_ids", "llcomp_mi_codec_label_boxes16",
+    "llcomp_mi_codec_label_boxes16_workspace_bytes",
 ]
 
 u8p = C.POINTER(C.c_uint8)
@@ -141,6 +144,13 @@ class ComposePiece(C.Structure):
     """llcomp_mi_compose_piece (include/llcomp_mi.h): 40 bytes"""
     _fields_ = [("dst", C.c_uint32), ("src", C.c_uint32), ("dx", C.c_uint32), ("dy", C.c_uint32), ("sx", C.c_uint32), ("sy", C.c_uint32),
                 ("w", C.c_uint32), ("h", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PastePiece16(C.Structure):
+    """llcomp_mi_paste_piece16 (include/llcomp_mi.h): 76 bytes, ids at 44"""
+    _fields_ = [("dst", C.c_uint32), ("src", C.c_uint32), ("dx", C.c_uint32), ("dy", C.c_uint32), ("sx", C.c_uint32), ("sy", C.c_uint32),
+                ("w", C.c_uint32), ("h", C.c_uint32), ("flags", C.c_uint32), ("value_bits", C.c_uint32), ("id_base", C.c_uint32),
+                ("ids", C.c_uint32 * 8)]
 
 
 class PastePiece(C.Structure):
@@ -541,6 +551,17 @@ def load():
             recs, C.c_uint32, C.c_void_p]
         L.llcomp_mi_codec_paste_workspace_bytes.restype = C.c_uint64
         L.llcomp_mi_codec_paste_workspace_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+    if "LLCOMP_MI_LIB" not in os.environ or hasattr(L, "llcomp_mi_paste16_reference"):  # batch copy-paste by 16-bit ids
+        u32p, recs = C.POINTER(C.c_uint32), C.POINTER(PastePiece16)
+        L.llcomp_mi_paste16_reference.restype = C.c_int
+        L.llcomp_mi_paste16_reference.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 3 + [C.c_void_p] + [C.c_uint32] * 6 + [recs, C.c_uint32, C.c_void_p]
+        L.llcomp_mi_paste16_plan.restype = C.c_int
+        L.llcomp_mi_paste16_plan.argtypes = [C.c_uint32] * 9 + [recs, C.c_uint32, u32p, u32p, u32p, u32p, C.POINTER(C.c_uint64)]
+        L.llcomp_mi_codec_paste_batch16.restype = C.c_int
+        L.llcomp_mi_codec_paste_batch16.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_uint32] * 3 + [C.c_void_p] + [C.c_uint32] * 5 + [
+            recs, C.c_uint32, C.c_void_p]
+        L.llcomp_mi_codec_paste16_workspace_bytes.restype = C.c_uint64
+        L.llcomp_mi_codec_paste16_workspace_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
     if "LLCOMP_MI_LIB" not in os.environ or hasattr(L, "llcomp_mi_label_boxes_reference"):  # label boxes
         L.llcomp_mi_label_boxes_reference.restype = C.c_int
         L.llcomp_mi_label_boxes_reference.argtypes = [C.c_void_p] + [C.c_uint32] * 3 + [C.c_void_p]
@@ -548,6 +569,15 @@ def load():
         L.llcomp_mi_label_boxes_rows.argtypes = []
         L.llcomp_mi_codec_label_boxes.restype = C.c_int
         L.llcomp_mi_codec_label_boxes.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 3 + [C.c_void_p, C.c_void_p]
+    if "LLCOMP_MI_LIB" not in os.environ or hasattr(L, "llcomp_mi_label_boxes16_reference"):  # label boxes of listed ids
+        L.llcomp_mi_label_boxes16_reference.restype = C.c_int
+        L.llcomp_mi_label_boxes16_reference.argtypes = [C.c_void_p] + [C.c_uint32] * 3 + [C.c_void_p] * 3
+        L.llcomp_mi_label_boxes16_max_ids.restype = C.c_uint32
+        L.llcomp_mi_label_boxes16_max_ids.argtypes = []
+        L.llcomp_mi_codec_label_boxes16.restype = C.c_int
+        L.llcomp_mi_codec_label_boxes16.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 3 + [C.c_void_p] * 4
+        L.llcomp_mi_codec_label_boxes16_workspace_bytes.restype = C.c_uint64
+        L.llcomp_mi_codec_label_boxes16_workspace_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
     if "LLCOMP_MI_LIB" not in os.environ and L.llcomp_mi_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.llcomp_mi_abi_version()}, this binding was written for {ABI_VERSION}: rebuild the library")
     _lib = L

@@ -21,10 +21,14 @@
 #include "compose.hpp"
 #include "compose_rule.hpp"
 #include "label_boxes.hpp"
+#include "label_boxes16.hpp"
+#include "label_boxes16_rule.hpp"
 #include "label_boxes_rule.hpp"
 #include "orient.hpp"
 #include "orient_rule.hpp"
 #include "paste.hpp"
+#include "paste16.hpp"
+#include "paste16_rule.hpp"
 #include "paste_rule.hpp"
 #include "photo.hpp"
 #include "resize.hpp"
@@ -870,6 +874,8 @@ void codec_release(llcomp_mi_codec* k) {
     dev_free(k->d_orient_tab, k->done);
     dev_free(k->d_compose_tab, k->done);
     dev_free(k->d_paste_tab, k->done);
+    dev_free(k->d_paste16_tab, k->done);
+    dev_free(k->d_label16_tab, k->done);
     dev_free(k->d_upd_goff, k->done);
     for (uint32_t i = 0; i < llcomp_mi_codec::kRegionsRing; ++i) {
         if (!k->h_regions[i]) continue;
@@ -1658,6 +1664,38 @@ uint64_t llcomp_mi_codec_paste_workspace_bytes(const llcomp_mi_codec* k, uint32_
     return k->workspace_bytes + paste_table_bound(n_dst, n_pieces);
 }
 
+// Batch copy-paste by 16-bit ids (DESIGN.md "Batch copy-paste by 16-bit ids"): as above with paste16_plan.hpp's checks and table.
+int llcomp_mi_codec_paste_batch16(llcomp_mi_codec* k, const void* d_src, const void* d_mask, uint32_t n_src, uint32_t iw, uint32_t ih, void* d_dst,
+                                  uint32_t n_dst, uint32_t ow, uint32_t oh, uint32_t dtype, uint32_t layout, const llcomp_mi_paste_piece16* pieces,
+                                  uint32_t n_pieces, void* stream) {
+    if (!k || !d_dst) return LLCOMP_MI_BAD_ARGS;
+    const uint32_t c = k->g.c;
+    if (int rc = paste16_check_call(n_src, iw, ih, n_dst, ow, oh, c, dtype, layout, pieces, n_pieces)) return rc;
+    const uint32_t esize = batch_esize(dtype);
+    if (int rc = paste16_check_memory(d_src, uint64_t(n_src) * c * iw * ih * esize, d_mask, 2 * uint64_t(n_src) * iw * ih, d_dst,
+                                      uint64_t(n_dst) * c * ow * oh * esize, esize, n_pieces))
+        return rc;
+    PastePlan p;
+    paste16_plan(n_dst, pieces, n_pieces, p);
+    if (p.samples.empty()) return LLCOMP_MI_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return batch_table_call(
+        k, k->d_paste16_tab, k->paste16_tab_cap, PasteTable16(p.samples.size(), p.order.size()).bytes, paste16_table_bound(n_dst, n_pieces), s,
+        [&](uint8_t* at) { paste16_table_put(pieces, p, c, layout, at); },
+        [&](const uint8_t* d_table) {
+            PasteLaunch o{};
+            o.d_src = static_cast<const uint8_t*>(d_src), o.d_mask = static_cast<const uint8_t*>(d_mask), o.d_dst = static_cast<uint8_t*>(d_dst);
+            o.d_table = d_table, o.n_samples = uint32_t(p.samples.size()), o.n_recs = uint32_t(p.order.size());
+            o.n_src = n_src, o.iw = iw, o.ih = ih, o.ow = ow, o.oh = oh, o.c = c, o.dtype = dtype, o.layout = layout;
+            return launch_paste16(o, s);
+        });
+}
+
+uint64_t llcomp_mi_codec_paste16_workspace_bytes(const llcomp_mi_codec* k, uint32_t n_dst, uint32_t n_pieces) {
+    if (!k) return 0;
+    return k->workspace_bytes + paste16_table_bound(n_dst, n_pieces);
+}
+
 // Label boxes (DESIGN.md "Label boxes"): the codec gives the device; no table, no workspace.
 int llcomp_mi_codec_label_boxes(llcomp_mi_codec* k, const void* d_maps, uint32_t n, uint32_t ow, uint32_t oh, void* d_boxes, void* stream) {
     if (!k || !d_maps || !d_boxes) return LLCOMP_MI_BAD_ARGS;
@@ -1669,6 +1707,32 @@ int llcomp_mi_codec_label_boxes(llcomp_mi_codec* k, const void* d_maps, uint32_t
     if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
     HIP_TRY(launch_label_boxes(static_cast<const uint8_t*>(d_maps), n, ow, oh, static_cast<uint8_t*>(d_boxes), static_cast<hipStream_t>(stream)));
     return LLCOMP_MI_OK;
+}
+
+// Label boxes of listed ids (DESIGN.md "Label boxes of listed ids"): the lists travel as the batch calls' tables do.  A call without
+// a listed id has no record to write and queues nothing.
+int llcomp_mi_codec_label_boxes16(llcomp_mi_codec* k, const void* d_maps, uint32_t n, uint32_t ow, uint32_t oh, const uint16_t* ids,
+                                  const uint32_t* first, void* d_boxes, void* stream) {
+    if (!k || !d_maps) return LLCOMP_MI_BAD_ARGS;
+    uint32_t longest = 0, n_listed = 0;
+    if (int rc = label_boxes16_check_call(n, ow, oh, ids, first, &longest, &n_listed)) return rc;
+    const uint32_t total = first[n];
+    const uint64_t m = reinterpret_cast<uintptr_t>(d_maps), b = reinterpret_cast<uintptr_t>(d_boxes);
+    const uint64_t map_bytes = 2 * uint64_t(n) * ow * oh, box_bytes = uint64_t(total) * sizeof(llcomp_mi_label_box);
+    if (misaligned(d_maps, 2) || (total && (!d_boxes || misaligned(d_boxes, 4) || (m < b + box_bytes && b < m + map_bytes)))) return LLCOMP_MI_BAD_ARGS;
+    if (!total) return LLCOMP_MI_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return batch_table_call(
+        k, k->d_label16_tab, k->label16_tab_cap, Label16Table(n, n_listed, total).bytes, label16_table_bound(n, total), s,
+        [&](uint8_t* at) { label16_table_put(n, ids, first, n_listed, at); },
+        [&](const uint8_t* d_table) {
+            return launch_label_boxes16(static_cast<const uint8_t*>(d_maps), n, ow, oh, d_table, n_listed, total, longest, static_cast<uint8_t*>(d_boxes), s);
+        });
+}
+
+uint64_t llcomp_mi_codec_label_boxes16_workspace_bytes(const llcomp_mi_codec* k, uint32_t n, uint32_t total_ids) {
+    if (!k) return 0;
+    return k->workspace_bytes + label16_table_bound(n, total_ids);
 }
 
 uint64_t llcomp_mi_codec_photo_workspace_bytes(const llcomp_mi_codec* k, uint64_t total_views) {

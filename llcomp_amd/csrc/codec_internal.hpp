@@ -82,6 +82,13 @@ struct llcomp_mi_codec {
     // (paste_plan.hpp: PasteTable); grown by the calls that need more
     uint8_t* d_paste_tab = nullptr;
     uint64_t paste_tab_cap = 0;
+    // batch copy-paste by 16-bit ids (llcomp_mi_codec_paste_batch16): the same with records of 72 bytes (paste16_plan.hpp: PasteTable16)
+    uint8_t* d_paste16_tab = nullptr;
+    uint64_t paste16_tab_cap = 0;
+    // label boxes of listed ids (llcomp_mi_codec_label_boxes16): where a call's one copy lands, the lists' bounds, the listed samples and
+    // the ids (label_boxes16_rule.hpp: Label16Table); grown by the calls that need more
+    uint8_t* d_label16_tab = nullptr;
+    uint64_t label16_tab_cap = 0;
     // region update (llcomp_mi_codec_encode_region / _update_region): the encoder runs on the box's sub-geometry, which can have MORE lane
     // groups than the full one, so its group offsets go to an array of their own, u64[n_slices + 1]; behind it, u64[lane groups + 1], the
     // full geometry's group offsets for the NEW table (d_group_off holds the old table's).  The decoded box shares d_box with the resized

@@ -1,0 +1,20 @@
+// label_boxes16.hpp -- the launcher of the kernels of the label boxes of listed ids (label_boxes16_kernels.hip; codec.hip:
+// llcomp_mi_codec_label_boxes16; DESIGN.md "Label boxes of listed ids") and the writer of the call's table (label_boxes16.cpp).  The
+// rule: label_boxes16_rule.hpp.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace llcomp_mi {
+
+// The call's table (Label16Table) at `at`: first[n + 1], the n_listed samples with a list, the ids.  Checked lists.
+void label16_table_put(uint32_t n, const uint16_t* ids, const uint32_t* first, uint32_t n_listed, uint8_t* at);
+
+// One call: k_label_boxes16_init over the `total` = first[n] records, then k_label_boxes16<K>, one workgroup per band and listed
+// sample, K the smallest capacity that holds `longest` ids.  d_maps: n samples of oh x ow uint16_t, 2-byte aligned; d_table: the table
+// above in device memory, 4-byte aligned; d_boxes: `total` records of 20 bytes, 4-byte aligned.  Checked (label_boxes16_check_call).
+hipError_t launch_label_boxes16(const uint8_t* d_maps, uint32_t n, uint32_t ow, uint32_t oh, const uint8_t* d_table, uint32_t n_listed, uint32_t total,
+                                uint32_t longest, uint8_t* d_boxes, hipStream_t stream);
+
+}  // namespace llcomp_mi
