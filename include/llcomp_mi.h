@@ -829,6 +829,49 @@ int llcomp_mi_label_boxes16_reference(const void* maps, uint32_t n, uint32_t ow,
                                       llcomp_mi_label_box* out);
 /* The most ids a sample lists: 22 bytes of a workgroup's LDS per listed id, one workgroup to a CU at the top capacity.  A constant. */
 uint32_t llcomp_mi_label_boxes16_max_ids(void);
+/* Label targets (llcomp_mi_codec_label_targets below: what a loss or a head takes from the id maps that the label boxes take -- a
+ * class-index tensor for CrossEntropyLoss, one-hot planes for Dice, focal and smoothed losses, one binary mask per instance for Mask
+ * R-CNN, Mask2Former and Copy-Paste's targets).  maps is n samples of P = oh * ow pixels, dense: map_bytes 1, bytes at any address, or
+ * map_bytes 2, little-endian uint16_t aligned to 2 bytes.  Sample i lists ids[first[i] .. first[i + 1]), strictly ascending,
+ * first[0] == 0, at most 4096 ids per sample and first[n] <= 2^20 in all as "Label boxes of listed ids", with one int32_t value per
+ * listed id; for map_bytes 1 an id is at most 255.  The value of a pixel is
+ *   v(i, p) = values[first[i] + j] if map(i, p) == ids[first[i] + j], else default_value;
+ * several ids may share a value (the instances of a class).
+ * INDEX: out[i * P + p] = v(i, p) as uint8_t, int32_t or int64_t (sign-extended): torch's lut[map.long()].  Every element is written,
+ * those of a sample with an empty list too.
+ * PLANES: sample i owns the planes plane_first[i] .. plane_first[i + 1]), K_i of them, at most llcomp_mi_label_targets_max_planes() =
+ * 4096, plane_first[0] == 0; element (plane_first[i] + k) * P + p is on_bits where v(i, p) == k, else off_bits, in dtype
+ * LLCOMP_MI_DTYPE_U8, _F16, _BF16 or _F32.  on_bits and off_bits are the element's bits in their low esize bytes (1 and 0; 0x3C00 and 0
+ * for F16; label smoothing passes the bits of 1 - eps + eps / K and eps / K).  A value outside [0, K_i) selects no plane ("ignore").
+ * Every element of every plane is written once.  One-hot planes [n][K][oh][ow] are plane_first[i] = i * K; the masks of the listed
+ * instances are values 0, 1, 2, ... with default_value -1.
+ * The output is dense and aligned to its element's size and to nothing more.
+ * BAD_ARGS: the cases of "Label boxes of listed ids"; a NULL struct, values or (PLANES) plane_first; a struct_size below the struct's;
+ * a map_bytes that is not 1 or 2, a kind or dtype that is none; an id above 255 with map_bytes 1; with INDEX U8 a value or default
+ * outside 0..255; plane_first[0] != 0, a plane_first that decreases, more than 4096 planes of a sample; on_bits or off_bits with bits
+ * above the element; an output of 2^62 bytes or more.
+ * NOT covered: HWC one-hot ([n][oh][ow][K]), in-place conversion, ids of 3 or 4 bytes, 16-bit maps at odd addresses, a table kept on
+ * the device across calls, targets as a job of the streaming pipeline, soft or blended mask borders, boxes or labels from the lists. */
+enum { LLCOMP_MI_TARGET_INDEX = 0, LLCOMP_MI_TARGET_PLANES = 1 };
+enum { LLCOMP_MI_TARGET_U8 = 0, LLCOMP_MI_TARGET_I32 = 1, LLCOMP_MI_TARGET_I64 = 2 };   /* INDEX dtypes */
+typedef struct llcomp_mi_label_targets {
+    uint32_t struct_size, map_bytes, kind, dtype;   /* dtype: LLCOMP_MI_TARGET_* for INDEX, LLCOMP_MI_DTYPE_* for PLANES */
+    int32_t default_value;
+    uint32_t on_bits, off_bits;                     /* PLANES */
+    const uint16_t* ids;                            /* host arrays, read during the call */
+    const int32_t* values;
+    const uint32_t* first;                          /* first[n + 1] */
+    const uint32_t* plane_first;                    /* PLANES: plane_first[n + 1] */
+} llcomp_mi_label_targets;                          /* 64 bytes, ids at 32 */
+/* The rule above on host memory: out holds llcomp_mi_label_targets_out_bytes bytes.  BAD_ARGS, out untouched: the cases above, a NULL
+ * maps or out, maps (map_bytes 2) or out not aligned to their element.  Host-only. */
+int llcomp_mi_label_targets_reference(const void* maps, uint32_t n, uint32_t ow, uint32_t oh, const llcomp_mi_label_targets* targets, void* out);
+/* The bytes of a call's output: n * P elements for INDEX, plane_first[n] * P for PLANES; 0 for a bad call. */
+uint64_t llcomp_mi_label_targets_out_bytes(uint32_t n, uint32_t ow, uint32_t oh, const llcomp_mi_label_targets* targets);
+/* The pixels of the segment of a sample that a workgroup of llcomp_mi_codec_label_targets takes (DESIGN.md "Label targets"), and the
+ * most planes of a sample: constants */
+uint32_t llcomp_mi_label_targets_segment(void);
+uint32_t llcomp_mi_label_targets_max_planes(void);
 uint32_t llcomp_mi_slice_count(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar);
 /* Slice width for one-row slices (tile_h = 1) when `frames` frames are coded per call: the widest slice (64..480 pixels) that
  * still keeps about four wavefronts per SIMD busy.  A call that codes few frames is latency-bound with wide slices; this
@@ -1254,6 +1297,21 @@ int llcomp_mi_codec_label_boxes16(llcomp_mi_codec* codec, const void* d_maps, ui
 /* The bound on llcomp_mi_codec_allocated_bytes with such calls of up to n samples and total_ids listed ids among the codec's calls:
  * llcomp_mi_codec_workspace_bytes + 4 * (2 * n + 1) + 2 * total_ids, the table of a call.  0 for a NULL codec. */
 uint64_t llcomp_mi_codec_label_boxes16_workspace_bytes(const llcomp_mi_codec* codec, uint32_t n, uint32_t total_ids);
+/* Label targets (the rule: "Label targets" above): the index tensor or the planes of the n id maps at d_maps, oh x ow pixels each
+ * whatever the codec's c, into d_out in device memory, asynchronously on `stream`.  The arrays of `targets` are HOST memory, read
+ * during the call only: first, the samples that get workgroups, plane_first, the values and the ids travel in ONE copy from the
+ * codec's pinned ring into a device buffer of this call's own.  One kernel: a workgroup per segment of
+ * llcomp_mi_label_targets_segment() pixels of a sample (PLANES: and per chunk of 32 of its planes) holds the sample's table in LDS (a
+ * dense table of 256 values for map_bytes 1; the list and its values at capacities of 256, 1024 and 4096 ids for map_bytes 2), reads
+ * the segment's map pixels once in aligned 16-byte units, leaves their values in LDS, and writes the aligned 16-byte units of output
+ * memory that the segment covers with one 16-byte store each; a unit covered in part gets exactly its own elements.  INDEX: every
+ * sample gets workgroups; PLANES: a sample without planes costs none, a call without planes queues nothing.
+ * BAD_ARGS, nothing queued and nothing written: a NULL codec, d_maps or d_out, the reference's cases, an output that overlaps the maps. */
+int llcomp_mi_codec_label_targets(llcomp_mi_codec* codec, const void* d_maps, uint32_t n, uint32_t ow, uint32_t oh,
+                                  const llcomp_mi_label_targets* targets, void* d_out, void* stream);
+/* The bound on llcomp_mi_codec_allocated_bytes with such calls of up to n samples and total_ids listed ids among the codec's calls:
+ * llcomp_mi_codec_workspace_bytes + 4 * (3 * n + 2) + 6 * total_ids, the table of a call.  0 for a NULL codec. */
+uint64_t llcomp_mi_codec_label_targets_workspace_bytes(const llcomp_mi_codec* codec, uint32_t n, uint32_t total_ids);
 /* Stage-A only (context + prediction model), for tests and profiling: d_sym u32[frames*h*w*c],
  * low 16 bits = folded context (0..7925), high 16 bits = folded residual (two's complement). */
 int llcomp_mi_codec_model(llcomp_mi_codec* codec, const void* d_px, void* d_sym, void* stream);

@@ -45,6 +45,9 @@ with ctypes and keeps the reference's names and error behaviour:
         ids of every id map of a batch: torchvision's masks_to_boxes)
     label_boxes16_reference / label_boxes16_max_ids / Codec.label_boxes16 / Codec.label_boxes16_workspace_bytes  (the same for the ids
         the caller lists per sample, in 16-bit id maps: Cityscapes, Mapillary Vistas, ADE20K instance ids)
+    TARGET_* / label_targets_reference / label_targets_segment / label_targets_max_planes / Codec.label_targets /
+        Codec.label_targets_workspace_bytes  (what a loss takes from the id maps: lut[map] as a class-index tensor, one-hot planes with
+        label smoothing, one binary mask per listed instance)
     RawImage(pixels, width, height, channels)     <->  llcomp::RawImage         (/root/reference/llcomp.hpp:454-459)
     EXT = ".llcomp"                               <->  llcomp::ext              (/root/reference/llcomp.hpp:18)
 
@@ -1029,6 +1032,91 @@ def label_boxes16_reference(maps, ids):
     out = np.zeros(max(int(first[n]), 1), LABEL_BOX_DTYPE)
     _check(_lib.load().llcomp_mi_label_boxes16_reference(a.ctypes.data if a.size else None, n, ow, oh, flat.ctypes.data, first.ctypes.data, out.ctypes.data))
     return out[:int(first[n])]
+
+
+# label targets (LLCOMP_MI_TARGET_*; include/llcomp_mi.h "Label targets"): the two kinds, and INDEX's dtypes
+TARGET_INDEX, TARGET_PLANES = 0, 1
+TARGET_U8, TARGET_I32, TARGET_I64 = 0, 1, 2
+TARGET_KINDS = ("index", "planes")
+_TARGET_INDEX_DTYPES = {"uint8": (TARGET_U8, np.uint8), "int32": (TARGET_I32, np.int32), "int64": (TARGET_I64, np.int64)}
+
+
+def label_targets_segment():
+    """the pixels of the segment of a sample that a workgroup of the label targets' kernel takes (llcomp_mi_label_targets_segment)"""
+    return int(_lib.load().llcomp_mi_label_targets_segment())
+
+
+def label_targets_max_planes():
+    """the most planes a sample of label_targets owns (llcomp_mi_label_targets_max_planes)"""
+    return int(_lib.load().llcomp_mi_label_targets_max_planes())
+
+
+def _target_bits(value, code):
+    """a number -> the bits of the element of DTYPE_* `code` that holds it, converted on the host by numpy (bfloat16: float32 rounded
+    to nearest even)"""
+    if code == DTYPE_U8:
+        if not 0 <= int(value) <= 255:
+            raise LlcompError(BAD_ARGS, f"on and off of uint8 planes are 0..255, got {value!r}")
+        return int(value)
+    if code == DTYPE_F16:
+        return int(np.array(value, np.float16).view(np.uint16))
+    b = int(np.array(value, np.float32).view(np.uint32))
+    return b if code == DTYPE_F32 else ((b + 0x7FFF + ((b >> 16) & 1)) >> 16) & 0xFFFF
+
+
+def _label_targets(ids, values, n, map_bytes, kind, dtype, default, planes, on, off):
+    """the arguments of a label targets call -> (LabelTargets, what must stay alive, the numpy type of the output's elements, the
+    output's planes or None); the library checks the lists, the values and the planes"""
+    if isinstance(kind, str) and kind.lower() in TARGET_KINDS:
+        kind = TARGET_KINDS.index(kind.lower())
+    if kind not in (TARGET_INDEX, TARGET_PLANES):
+        raise LlcompError(BAD_ARGS, f"kind must be one of {TARGET_KINDS}, got {kind!r}")
+    flat, first = _label_lists(ids, n)
+    vals = [np.asarray(list(l), np.int64).reshape(-1) for l in values]
+    if [v.size for v in vals] != np.diff(first.astype(np.int64)).tolist():
+        raise LlcompError(BAD_ARGS, "values holds one value per listed id")
+    flat_v = np.concatenate(vals + [np.zeros(1, np.int64)])
+    if flat_v.min() < -0x80000000 or flat_v.max() > 0x7FFFFFFF or not -0x80000000 <= int(default) <= 0x7FFFFFFF:
+        raise LlcompError(BAD_ARGS, "a value is an int32")
+    flat_v = np.ascontiguousarray(flat_v.astype(np.int32))
+    t = _lib.LabelTargets(C.sizeof(_lib.LabelTargets), int(map_bytes), kind, 0, int(default), 0, 0, flat.ctypes.data, flat_v.ctypes.data, first.ctypes.data, None)
+    keep = [flat, flat_v, first]
+    if kind == TARGET_INDEX:
+        name = "int64" if dtype is None else str(dtype).replace("torch.", "")
+        if name not in _TARGET_INDEX_DTYPES:
+            raise LlcompError(BAD_ARGS, f"dtype of an index tensor must be uint8, int32 or int64, got {dtype!r}")
+        t.dtype, np_type = _TARGET_INDEX_DTYPES[name]
+        return t, keep, np_type, None
+    t.dtype = _dtype_code(dtype)
+    if planes is None:
+        raise LlcompError(BAD_ARGS, "planes= is an int, or one count per sample")
+    counts = [int(planes)] * n if isinstance(planes, (int, np.integer)) else [int(k) for k in planes]
+    if len(counts) != n or any(k < 0 or k > 0xFFFF for k in counts):
+        raise LlcompError(BAD_ARGS, f"planes holds one count per sample, got {len(counts)} for {n} samples")
+    plane_first = np.zeros(n + 1, np.uint32)
+    plane_first[1:] = np.cumsum(counts)
+    keep.append(plane_first)
+    t.plane_first = plane_first.ctypes.data
+    t.on_bits = _target_bits(1 if on is None else on, t.dtype)
+    t.off_bits = _target_bits(0 if off is None else off, t.dtype)
+    return t, keep, _NP_OF_DTYPE[t.dtype], counts
+
+
+def label_targets_reference(maps, ids, values, kind="index", dtype=None, default=0, planes=None, on=None, off=None):
+    """The rule of the label targets on a host array (llcomp_mi_label_targets_reference): maps [n, oh, ow] uint8 or uint16; ids a
+    sequence of n sequences of ids, each strictly ascending, values one int32 per listed id; a pixel's value is its id's, or `default`.
+    kind "index" -> [n, oh, ow] of dtype uint8, int32 or int64 (the default).  kind "planes" -> the planes whose index the pixel's value
+    is hold `on` (1), the others `off` (0), in dtype uint8 (the default), float32, float16 or bfloat16 (as uint16 bit patterns):
+    [n, K, oh, ow] for planes=K, [sum of planes, oh, ow] for one count per sample."""
+    a = np.ascontiguousarray(maps)
+    if a.ndim != 3 or a.dtype not in (np.uint8, np.uint16):
+        raise LlcompError(BAD_ARGS, f"maps are uint8 or uint16 [n, oh, ow], got {a.dtype} of shape {a.shape}")
+    n, oh, ow = a.shape
+    t, keep, np_type, counts = _label_targets(ids, values, n, a.itemsize, kind, dtype, default, planes, on, off)
+    shape = (n, oh, ow) if counts is None else (n, counts[0], oh, ow) if isinstance(planes, (int, np.integer)) else (sum(counts), oh, ow)
+    out = np.zeros(int(np.prod(shape)) + 1, np_type)
+    _check(_lib.load().llcomp_mi_label_targets_reference(a.ctypes.data if a.size else None, n, ow, oh, C.byref(t), out.ctypes.data))
+    return out[:-1].reshape(shape)
 
 
 def _view_groups(groups, c, signed=False):
@@ -2083,6 +2171,24 @@ class Codec:
         """the bound on .allocated_bytes() with label_boxes16 calls of up to n samples and total_ids listed ids
         (llcomp_mi_codec_label_boxes16_workspace_bytes)"""
         return self._L.llcomp_mi_codec_label_boxes16_workspace_bytes(self._h, int(n), int(total_ids))
+
+    def label_targets(self, d_maps, n, ow, oh, ids, values, d_out, map_dtype="uint8", kind="index", dtype=None, default=0, planes=None, on=None, off=None,
+                      stream=0):
+        """What a loss takes from n id maps (llcomp_mi_codec_label_targets): d_maps, n x oh x ow pixels of map_dtype "uint8" (any
+        address) or "uint16" (aligned to 2 bytes); ids, values, kind, dtype, default, planes, on and off as label_targets_reference ->
+        d_out, the index tensor [n, oh, ow] or the planes, dense and aligned to its element, both in device memory and not overlapping;
+        every element is written once.  planes= is an int for one-hot [n, K, oh, ow], or one count per sample.  Asynchronous on
+        `stream`; the lists are read during the call."""
+        name = str(map_dtype).replace("torch.", "")
+        if name not in ("uint8", "uint16"):
+            raise LlcompError(BAD_ARGS, f"map_dtype must be uint8 or uint16, got {map_dtype!r}")
+        t, keep, _, _ = _label_targets(ids, values, int(n), 1 if name == "uint8" else 2, kind, dtype, default, planes, on, off)
+        _check(self._L.llcomp_mi_codec_label_targets(self._h, d_maps, int(n), int(ow), int(oh), C.byref(t), d_out, stream))
+
+    def label_targets_workspace_bytes(self, n, total_ids):
+        """the bound on .allocated_bytes() with label_targets calls of up to n samples and total_ids listed ids
+        (llcomp_mi_codec_label_targets_workspace_bytes)"""
+        return self._L.llcomp_mi_codec_label_targets_workspace_bytes(self._h, int(n), int(total_ids))
 
     def views_workspace_bytes(self, total_views):
         """.workspace_bytes for calls of up to total_views views (llcomp_mi_codec_views_workspace_bytes): the staged tables grow with them"""

@@ -61,6 +61,8 @@ SYMBOLS = [
     "llcomp_mi_paste16_reference", "llcomp_mi_paste16_plan", "llcomp_mi_codec_paste_batch16", "llcomp_mi_codec_paste16_workspace_bytes",
     "llcomp_mi_label_boxes16_reference", "llcomp_mi_label_boxes16_max_ids", "llcomp_mi_codec_label_boxes16",
     "llcomp_mi_codec_label_boxes16_workspace_bytes",
+    "llcomp_mi_label_targets_reference", "llcomp_mi_label_targets_out_bytes", "llcomp_mi_label_targets_segment",
+    "llcomp_mi_label_targets_max_planes", "llcomp_mi_codec_label_targets", "llcomp_mi_codec_label_targets_workspace_bytes",
 ]
 
 u8p = C.POINTER(C.c_uint8)
@@ -162,6 +164,13 @@ class PastePiece(C.Structure):
 class LabelBox(C.Structure):
     """llcomp_mi_label_box (include/llcomp_mi.h): 20 bytes"""
     _fields_ = [("count", C.c_uint32), ("x0", C.c_uint32), ("y0", C.c_uint32), ("x1", C.c_uint32), ("y1", C.c_uint32)]
+
+
+class LabelTargets(C.Structure):
+    """llcomp_mi_label_targets (include/llcomp_mi.h): 64 bytes, ids at 32"""
+    _fields_ = [("struct_size", C.c_uint32), ("map_bytes", C.c_uint32), ("kind", C.c_uint32), ("dtype", C.c_uint32), ("default_value", C.c_int32),
+                ("on_bits", C.c_uint32), ("off_bits", C.c_uint32), ("ids", C.c_void_p), ("values", C.c_void_p), ("first", C.c_void_p),
+                ("plane_first", C.c_void_p)]
 
 
 class Info(C.Structure):
@@ -578,6 +587,19 @@ def load():
         L.llcomp_mi_codec_label_boxes16.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 3 + [C.c_void_p] * 4
         L.llcomp_mi_codec_label_boxes16_workspace_bytes.restype = C.c_uint64
         L.llcomp_mi_codec_label_boxes16_workspace_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+    if "LLCOMP_MI_LIB" not in os.environ or hasattr(L, "llcomp_mi_label_targets_reference"):  # label targets
+        L.llcomp_mi_label_targets_reference.restype = C.c_int
+        L.llcomp_mi_label_targets_reference.argtypes = [C.c_void_p] + [C.c_uint32] * 3 + [C.POINTER(LabelTargets), C.c_void_p]
+        L.llcomp_mi_label_targets_out_bytes.restype = C.c_uint64
+        L.llcomp_mi_label_targets_out_bytes.argtypes = [C.c_uint32] * 3 + [C.POINTER(LabelTargets)]
+        L.llcomp_mi_label_targets_segment.restype = C.c_uint32
+        L.llcomp_mi_label_targets_segment.argtypes = []
+        L.llcomp_mi_label_targets_max_planes.restype = C.c_uint32
+        L.llcomp_mi_label_targets_max_planes.argtypes = []
+        L.llcomp_mi_codec_label_targets.restype = C.c_int
+        L.llcomp_mi_codec_label_targets.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 3 + [C.POINTER(LabelTargets), C.c_void_p, C.c_void_p]
+        L.llcomp_mi_codec_label_targets_workspace_bytes.restype = C.c_uint64
+        L.llcomp_mi_codec_label_targets_workspace_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
     if "LLCOMP_MI_LIB" not in os.environ and L.llcomp_mi_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.llcomp_mi_abi_version()}, this binding was written for {ABI_VERSION}: rebuild the library")
     _lib = L

@@ -23,6 +23,7 @@
 #include "label_boxes.hpp"
 #include "label_boxes16.hpp"
 #include "label_boxes16_rule.hpp"
+#include "label_targets.hpp"
 #include "label_boxes_rule.hpp"
 #include "orient.hpp"
 #include "orient_rule.hpp"
@@ -876,6 +877,7 @@ void codec_release(llcomp_mi_codec* k) {
     dev_free(k->d_paste_tab, k->done);
     dev_free(k->d_paste16_tab, k->done);
     dev_free(k->d_label16_tab, k->done);
+    dev_free(k->d_target_tab, k->done);
     dev_free(k->d_upd_goff, k->done);
     for (uint32_t i = 0; i < llcomp_mi_codec::kRegionsRing; ++i) {
         if (!k->h_regions[i]) continue;
@@ -1733,6 +1735,32 @@ int llcomp_mi_codec_label_boxes16(llcomp_mi_codec* k, const void* d_maps, uint32
 uint64_t llcomp_mi_codec_label_boxes16_workspace_bytes(const llcomp_mi_codec* k, uint32_t n, uint32_t total_ids) {
     if (!k) return 0;
     return k->workspace_bytes + label16_table_bound(n, total_ids);
+}
+
+// Label targets (DESIGN.md "Label targets"): the lists, the values and the planes travel as the batch calls' tables do.  A call without
+// a sample that gets workgroups -- PLANES without a plane -- has nothing to write and queues nothing.
+int llcomp_mi_codec_label_targets(llcomp_mi_codec* k, const void* d_maps, uint32_t n, uint32_t ow, uint32_t oh, const llcomp_mi_label_targets* targets,
+                                  void* d_out, void* stream) {
+    if (!k || !d_maps || !d_out) return LLCOMP_MI_BAD_ARGS;
+    TargetCall c;
+    if (int rc = label_targets_check_call(n, ow, oh, targets, c)) return rc;
+    const llcomp_mi_label_targets& t = *targets;
+    const uint64_t m = reinterpret_cast<uintptr_t>(d_maps), o = reinterpret_cast<uintptr_t>(d_out);
+    const uint64_t map_bytes = uint64_t(n) * ow * oh * t.map_bytes;
+    if (misaligned(d_maps, t.map_bytes) || misaligned(d_out, c.esize) || (m < o + c.out_bytes && o < m + map_bytes)) return LLCOMP_MI_BAD_ARGS;
+    if (!c.n_work) return LLCOMP_MI_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return batch_table_call(
+        k, k->d_target_tab, k->target_tab_cap, TargetTable(n, c.n_work, c.total, t.kind == LLCOMP_MI_TARGET_PLANES).bytes, target_table_bound(n, c.total), s,
+        [&](uint8_t* at) { target_table_put(n, t, c, at); },
+        [&](const uint8_t* d_table) {
+            return launch_label_targets(static_cast<const uint8_t*>(d_maps), n, ow, oh, t, c, d_table, static_cast<uint8_t*>(d_out), s);
+        });
+}
+
+uint64_t llcomp_mi_codec_label_targets_workspace_bytes(const llcomp_mi_codec* k, uint32_t n, uint32_t total_ids) {
+    if (!k) return 0;
+    return k->workspace_bytes + target_table_bound(n, total_ids);
 }
 
 uint64_t llcomp_mi_codec_photo_workspace_bytes(const llcomp_mi_codec* k, uint64_t total_views) {

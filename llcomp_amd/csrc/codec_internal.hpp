@@ -89,6 +89,10 @@ struct llcomp_mi_codec {
     // the ids (label_boxes16_rule.hpp: Label16Table); grown by the calls that need more
     uint8_t* d_label16_tab = nullptr;
     uint64_t label16_tab_cap = 0;
+    // label targets (llcomp_mi_codec_label_targets): where a call's one copy lands, the lists' and the planes' bounds, the samples that
+    // get workgroups, the values and the ids (label_targets_rule.hpp: TargetTable); grown by the calls that need more
+    uint8_t* d_target_tab = nullptr;
+    uint64_t target_tab_cap = 0;
     // region update (llcomp_mi_codec_encode_region / _update_region): the encoder runs on the box's sub-geometry, which can have MORE lane
     // groups than the full one, so its group offsets go to an array of their own, u64[n_slices + 1]; behind it, u64[lane groups + 1], the
     // full geometry's group offsets for the NEW table (d_group_off holds the old table's).  The decoded box shares d_box with the resized

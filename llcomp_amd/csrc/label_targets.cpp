@@ -1,0 +1,82 @@
+// label_targets.cpp -- the host half of the label targets (include/llcomp_mi.h: "Label targets"): llcomp_mi_label_targets_reference,
+// which walks the kernel's own workgroups, threads and units (label_targets_rule.hpp) on host memory, the call's table, and the
+// accessors.  Plain C++, no GPU.
+#include <cstring>
+#include <vector>
+
+#include "label_targets_rule.hpp"
+
+namespace llcomp_mi {
+namespace {
+
+struct PlainTargetMem {
+    LabelChunk load16(uint64_t a) const {
+        LabelChunk v;
+        std::memcpy(&v, reinterpret_cast<const void*>(uintptr_t(a)), 16);  // (little-endian hosts, like the containers)
+        return v;
+    }
+    template <uint32_t N>
+    uint32_t load_el(uint64_t a) const {
+        uint32_t v = 0;
+        std::memcpy(&v, reinterpret_cast<const void*>(uintptr_t(a)), N);
+        return v;
+    }
+};
+struct PlainTargetSink {
+    void store16(uint64_t a, const LabelChunk& c) const { std::memcpy(reinterpret_cast<void*>(uintptr_t(a)), &c, 16); }
+    template <uint32_t ES>
+    void store_el(uint64_t a, uint64_t bits) const {
+        std::memcpy(reinterpret_cast<void*>(uintptr_t(a)), &bits, ES);
+    }
+};
+
+}  // namespace
+
+void target_table_put(uint32_t n, const llcomp_mi_label_targets& t, const TargetCall& c, uint8_t* at) {
+    const bool planes = t.kind == LLCOMP_MI_TARGET_PLANES;
+    const TargetTable tab(n, c.n_work, c.total, planes);
+    std::memcpy(at + tab.first_at, t.first, 4 * (size_t(n) + 1));
+    uint32_t k = 0;
+    for (uint32_t i = 0; i < n; ++i)
+        if (!planes || t.plane_first[i + 1] != t.plane_first[i]) std::memcpy(at + tab.samples_at + 4 * size_t(k++), &i, 4);
+    if (planes) std::memcpy(at + tab.planes_at, t.plane_first, 4 * (size_t(n) + 1));
+    if (c.total) {
+        std::memcpy(at + tab.values_at, t.values, 4 * size_t(c.total));
+        std::memcpy(at + tab.ids_at, t.ids, 2 * size_t(c.total));
+    }
+}
+
+}  // namespace llcomp_mi
+
+extern "C" {
+
+uint32_t llcomp_mi_label_targets_segment(void) { return llcomp_mi::kTargetSegment; }
+uint32_t llcomp_mi_label_targets_max_planes(void) { return llcomp_mi::kTargetMaxPlanes; }
+
+uint64_t llcomp_mi_label_targets_out_bytes(uint32_t n, uint32_t ow, uint32_t oh, const llcomp_mi_label_targets* targets) {
+    llcomp_mi::TargetCall c;
+    return llcomp_mi::label_targets_check_call(n, ow, oh, targets, c) == LLCOMP_MI_OK ? c.out_bytes : 0;
+}
+
+int llcomp_mi_label_targets_reference(const void* maps, uint32_t n, uint32_t ow, uint32_t oh, const llcomp_mi_label_targets* targets, void* out) {
+    using namespace llcomp_mi;
+    TargetCall c;
+    if (int rc = label_targets_check_call(n, ow, oh, targets, c)) return rc;
+    const llcomp_mi_label_targets& t = *targets;
+    const uintptr_t m = reinterpret_cast<uintptr_t>(maps), o = reinterpret_cast<uintptr_t>(out);
+    if (!maps || !out || (m & (t.map_bytes - 1)) || (o & (c.esize - 1))) return LLCOMP_MI_BAD_ARGS;
+    const TargetGeom g = target_geom(m, o, n, ow, oh, t.map_bytes);
+    const TargetParams a{t.kind, c.esize, t.default_value, t.on_bits, t.off_bits};
+    const uint32_t K = t.map_bytes == 1 ? 256u : label16_capacity(c.longest), chunks = target_plane_chunks(t.kind, c.most_planes);
+    std::vector<uint16_t> list(K);
+    std::vector<uint32_t> vals(K), v(kTargetSegment);
+    PlainTargetMem mem;
+    PlainTargetSink sink;
+    for (uint32_t i = 0; i < n; ++i)
+        for (uint32_t seg = 0; seg < g.segments; ++seg)
+            for (uint32_t z = 0; z < chunks; ++z)
+                label_targets_host_workgroup(g, a, t.map_bytes, t.first, t.plane_first, t.values, t.ids, i, seg, z, mem, sink, list, vals, v);
+    return LLCOMP_MI_OK;
+}
+
+}  // extern "C"
