@@ -7,7 +7,9 @@ the bank; only the host-API legs build them on the host.
 
 Every leg frees what it holds before the next starts, and skips (stating both numbers) when the device has less free memory than the
 codec's workspace_bytes plus the leg's own buffers.  Legs a-d and f print one "LARGE" line each: the codec's workspace bytes ("n/a" for
-the host-API legs d), the least free device memory seen, wall time."""
+the host-API legs d), the least free device memory seen, wall time.
+
+The batch calls (mix_batch to label_targets) and the formatted view outputs at these sizes: tests/test_gpu_large_batches.py."""
 import os
 import time
 import zlib
