@@ -70,7 +70,18 @@ typedef enum llcomp_mi_status {
     LLCOMP_MI_OUTPUT_OVERFLOW = 6, /* caller-provided output capacity too small (reference: heap overflow, D1) */
     LLCOMP_MI_HIP_ERROR = 7,       /* a HIP call failed, or a kernel found its own launch assumptions violated and refused to run */
     LLCOMP_MI_NO_DEVICE = 8,
-    LLCOMP_MI_NOMEM = 9,
+    LLCOMP_MI_NOMEM = 9,           /* An allocation of device or pinned memory failed.  The contract, for EVERY call that can return it: it
+                                      is returned before anything is queued on the caller's stream and before an output or the status
+                                      word is written (as BAD_ARGS is); the object the call was made on stays usable -- what it already
+                                      held it still holds or has given back whole, and the same call succeeds once the memory is there;
+                                      llcomp_mi_codec_allocated_bytes stays true; nothing leaks.  A buffer that had to grow may have been
+                                      given back before its replacement was refused: the codec then holds less, never something half set
+                                      up.  The host-buffer calls (llcomp_mi_encode, _decode, _decode_region, _update_region and their
+                                      _into forms) work on a lane of the library's own: they may have copied the caller's INPUT into the
+                                      lane's buffers by then, and the caller's output buffer is untouched.  Two allocations are optional
+                                      and never fail a call: the 2-D decoder's 16-byte feedback mailbox (without it the bank cache stays
+                                      on in every launch) and the events of the chunked encoder's second stream (without them the pass
+                                      runs in order on the caller's stream); the bytes are the same. */
     LLCOMP_MI_BUSY = 10,           /* streaming pipeline: every slot is occupied / the oldest job is still in flight */
     LLCOMP_MI_DEVICE_FAILED = 11   /* a call over a device list: one of the devices failed (HIP error, out of memory, no such device) and
                                       nothing was published; llcomp_mi_last_device_error tells which one and why.  Verdicts about the
@@ -931,14 +942,15 @@ uint32_t llcomp_mi_codec_slices(const llcomp_mi_codec* codec);        /* total =
  * wavefront.  No effect on any output byte: tests use it to make sure they run the family they mean to. */
 uint32_t llcomp_mi_codec_kernel_family(const llcomp_mi_codec* codec);
 /* Device bytes the codec can hold at most.  The per-slice state tables (decoding 2-D slices; 63 KB per slice) and the snapshot
- * arrays of the 2-D encoder (22 B per sample) are allocated by the first call that needs them, so an encode-only or decode-only
- * codec stays below this figure; that first call can return LLCOMP_MI_NOMEM. */
+ * arrays of the 2-D encoder (22 B per sample; 28 B and the coder's parking records of 64 B per slice where slices are above 4096
+ * samples) are allocated by the first call that needs them, so an encode-only or decode-only codec stays below this figure; that
+ * first call can return LLCOMP_MI_NOMEM. */
 uint64_t llcomp_mi_codec_workspace_bytes(const llcomp_mi_codec* codec);
 /* Diagnostic: the device bytes the codec holds right now (what the calls so far have allocated; never above
  * llcomp_mi_codec_workspace_bytes, except through a resized regions decode to an output larger than the image, or a views decode of
  * more views than frames: llcomp_mi_codec_views_workspace_bytes; the padded, warped and photometric calls have bounds of their own). */
 uint64_t llcomp_mi_codec_allocated_bytes(const llcomp_mi_codec* codec);
-/* Allocates NOW what the first encode (LLCOMP_MI_PREPARE_ENCODE: the 2-D encoder's snapshot arrays, or its state tables) and / or
+/* Allocates NOW what the first encode (LLCOMP_MI_PREPARE_ENCODE: the 2-D encoder's snapshot arrays with their parking records, or its state tables) and / or
  * the first decode (LLCOMP_MI_PREPARE_DECODE: the state tables of 2-D slices) would otherwise allocate inside the call -- for callers
  * that need the first call to be like every other one (no hipMalloc behind work already queued on their stream, no NOMEM in the
  * middle of a pipeline).  Idempotent; LLCOMP_MI_NOMEM when the device cannot give the memory. */

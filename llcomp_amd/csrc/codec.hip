@@ -173,9 +173,28 @@ int ensure_snapshot_arrays(llcomp_mi_codec* k, const Geometry& g) {
     const bool own = snapshot_mode(k->g);
     const bool chunked = snapshot_chunked(g);
     const uint64_t need = snapshot_elems(g);
-    if (k->d_snap_sorted && need <= k->snap_el && (!chunked || k->d_snap_ctx)) return LLCOMP_MI_OK;
+    // (ready: the arrays AND, for chunks, the parking records with the second stream's events behind them -- one condition, so that a
+    // call which ran out of memory half way is not taken for one that set everything up)
+    if (k->d_snap_sorted && need <= k->snap_el && (!chunked || (k->d_snap_ctx && k->d_seg_state))) return LLCOMP_MI_OK;
     const uint64_t el = own ? snapshot_elems(k->g) : std::max(need, std::min(2 * k->snap_el, region_snapshot_bound(k->g)));
     const bool with_chunks = own ? snapshot_chunked(k->g) : true;  // (a region of a codec without the pass: its slices may be above 4096 samples)
+    // the coder's parking records, the second stream and the events of the fork / join come FIRST: a failure here changes nothing, and one
+    // of the arrays below leaves records that are complete and counted
+    if (with_chunks && !k->d_seg_state) {
+        if (dev_alloc(reinterpret_cast<void**>(&k->d_seg_state), uint64_t(k->g.n_slices) * 64) != hipSuccess) { k->d_seg_state = nullptr; return LLCOMP_MI_NOMEM; }
+        k->allocated_bytes += uint64_t(k->g.n_slices) * 64;
+        if (k->overlap) {
+            bool ok = (k->aux_shared ? (k->aux = shared_second_stream(k->device)) != nullptr
+                                     : hipStreamCreateWithFlags(&k->aux, hipStreamNonBlocking) == hipSuccess) &&
+                      hipEventCreateWithFlags(&k->ev_fork, hipEventDisableTiming) == hipSuccess;
+            for (uint32_t c = 0; ok && c < kSnapMaxChunks; ++c)
+                if (!k->ev_chunk[c]) ok = hipEventCreateWithFlags(&k->ev_chunk[c], hipEventDisableTiming) == hipSuccess;
+            if (!ok) {  // no second stream to be had: the pass runs on the caller's (slower at few frames in flight, same bytes)
+                (void)hipGetLastError();
+                k->overlap = false;
+            }
+        }
+    }
     if (k->d_snap_sorted) {
         if (k->done && k->done->ev && hipEventSynchronize(k->done->ev) != hipSuccess) return LLCOMP_MI_HIP_ERROR;
         dev_free(k->d_snap_sorted);
@@ -200,22 +219,17 @@ int ensure_snapshot_arrays(llcomp_mi_codec* k, const Geometry& g) {
     }
     k->snap_el = el;
     k->allocated_bytes += el * (with_chunks ? 28 : 18);
-    if (with_chunks && !k->d_seg_state) {  // the coder's parking records, the second stream and the events of the fork / join
-        if (dev_alloc(reinterpret_cast<void**>(&k->d_seg_state), uint64_t(k->g.n_slices) * 64) != hipSuccess) { k->d_seg_state = nullptr; return LLCOMP_MI_NOMEM; }
-        k->allocated_bytes += uint64_t(k->g.n_slices) * 64;
-        if (k->overlap) {
-            bool ok = (k->aux_shared ? (k->aux = shared_second_stream(k->device)) != nullptr
-                                     : hipStreamCreateWithFlags(&k->aux, hipStreamNonBlocking) == hipSuccess) &&
-                      hipEventCreateWithFlags(&k->ev_fork, hipEventDisableTiming) == hipSuccess;
-            for (uint32_t c = 0; ok && c < kSnapMaxChunks; ++c)
-                if (!k->ev_chunk[c]) ok = hipEventCreateWithFlags(&k->ev_chunk[c], hipEventDisableTiming) == hipSuccess;
-            if (!ok) {  // no second stream to be had: the pass runs on the caller's (slower at few frames in flight, same bytes)
-                (void)hipGetLastError();
-                k->overlap = false;
-            }
-        }
-    }
     return LLCOMP_MI_OK;
+}
+
+// What the decode chain and the encoder on geometry g allocate at their first call: every entry point asks for it AHEAD of the first
+// thing it queues or writes, so that LLCOMP_MI_NOMEM leaves the outputs, the status word and the stream as BAD_ARGS does
+// (include/llcomp_mi.h, by the status codes).  next_state_generation and encode_streams then find everything in place.
+int ensure_decode(llcomp_mi_codec* k, const Geometry& g) { return ensure_state_tables(k, slices_need_state_tables(g)); }
+int ensure_encode(llcomp_mi_codec* k, const Geometry& g) {
+    if (!snapshot_mode(g) || snapshot_chunked(g))
+        if (int rc = ensure_state_tables(k, slices_need_state_tables(g))) return rc;
+    return snapshot_mode(g) ? ensure_snapshot_arrays(k, g) : LLCOMP_MI_OK;
 }
 
 // The 2-D decoder's bank cache, per LAUNCH (codec_internal.hpp).  A wavefront that finds fewer than one hit in eight gives the cache up
@@ -246,7 +260,7 @@ bool use_bank_cache(llcomp_mi_codec* k, const Geometry& g) {
 // ... behind a cached launch: {cached wavefronts, bypassed wavefronts} -> the pinned mailbox, and the event that says it has arrived
 void queue_feedback(llcomp_mi_codec* k, hipStream_t s) {
     if (!k->h_feedback) {
-        if (hipHostMalloc(reinterpret_cast<void**>(&k->h_feedback), 16, hipHostMallocDefault) != hipSuccess) { k->h_feedback = nullptr; (void)hipGetLastError(); return; }
+        if (host_alloc_pinned(reinterpret_cast<void**>(&k->h_feedback), 16, hipHostMallocDefault) != hipSuccess) { k->h_feedback = nullptr; (void)hipGetLastError(); return; }
         k->h_feedback[0] = k->h_feedback[1] = 0;
         if (hipEventCreateWithFlags(&k->fb_event, hipEventDisableTiming) != hipSuccess) { k->fb_event = nullptr; (void)hipGetLastError(); return; }
     }
@@ -316,7 +330,7 @@ int ensure_regions_ring(llcomp_mi_codec* k) {
     const uint64_t bytes = uint64_t(k->g.frames) * sizeof(RegionsFrame);
     for (uint32_t i = 0; i < llcomp_mi_codec::kRegionsRing; ++i) {
         if (k->h_regions[i]) continue;
-        if (hipHostMalloc(reinterpret_cast<void**>(&k->h_regions[i]), bytes, hipHostMallocDefault) != hipSuccess) {
+        if (host_alloc_pinned(reinterpret_cast<void**>(&k->h_regions[i]), bytes, hipHostMallocDefault) != hipSuccess) {
             k->h_regions[i] = nullptr;
             (void)hipGetLastError();
             return LLCOMP_MI_NOMEM;
@@ -354,14 +368,14 @@ int regions_slot_take(llcomp_mi_codec* k, uint64_t bytes, uint64_t bound, uint32
     }
     if (bytes <= k->h_regions_cap[slot]) return LLCOMP_MI_OK;
     const uint64_t cap = std::max(bytes, std::min(2 * k->h_regions_cap[slot], bound));
-    (void)hipHostFree(k->h_regions[slot]);
-    k->h_regions[slot] = nullptr;
-    k->h_regions_cap[slot] = 0;
-    if (hipHostMalloc(reinterpret_cast<void**>(&k->h_regions[slot]), cap, hipHostMallocDefault) != hipSuccess) {
-        k->h_regions[slot] = nullptr;
+    // (the replacement first: a failure leaves the ring as it was, every slot of it still there for the calls that fit)
+    uint8_t* grown = nullptr;
+    if (host_alloc_pinned(reinterpret_cast<void**>(&grown), cap, hipHostMallocDefault) != hipSuccess) {
         (void)hipGetLastError();
         return LLCOMP_MI_NOMEM;
     }
+    (void)host_free_pinned(k->h_regions[slot]);
+    k->h_regions[slot] = grown;
     k->h_regions_cap[slot] = cap;
     return LLCOMP_MI_OK;
 }
@@ -684,6 +698,8 @@ int decode_windows(llcomp_mi_codec* k, const WindowsCall& c, void* d_status, voi
     if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
     if (!gp)
         if (int rc = ensure_region_arrays(k)) return rc;
+    for (uint32_t i = 0; i < p.n_classes; ++i)
+        if (int rc = ensure_decode(k, p.classes[i].sub)) return rc;
     if (int rc = any_tail ? ensure_regions_ring(k) : ensure_regions_table(k)) return rc;
     if (!table_only)
         if (int rc = ensure_stage(k, bytes, bound)) return rc;
@@ -884,7 +900,7 @@ void codec_release(llcomp_mi_codec* k) {
         // (a copy out of the slot may still be queued on a caller's stream: it must not read freed memory)
         if (k->regions_ev_live[i] && k->regions_ev[i] && hipEventQuery(k->regions_ev[i]) == hipErrorNotReady) (void)hipEventSynchronize(k->regions_ev[i]);
         (void)hipGetLastError();
-        (void)hipHostFree(k->h_regions[i]);
+        (void)host_free_pinned(k->h_regions[i]);
     }
     for (auto& ev : k->regions_ev) if (ev) (void)hipEventDestroy(ev);
     dev_free(k->d_snap_sorted, k->done);
@@ -903,7 +919,7 @@ void codec_release(llcomp_mi_codec* k) {
         // memory.  Its own event says when it has arrived (usually long ago); only a codec destroyed right behind such a call waits.
         if (k->fb_pending && k->fb_event && hipEventQuery(k->fb_event) == hipErrorNotReady) (void)hipEventSynchronize(k->fb_event);
         (void)hipGetLastError();
-        (void)hipHostFree(k->h_feedback);
+        (void)host_free_pinned(k->h_feedback);
     }
     if (k->fb_event) (void)hipEventDestroy(k->fb_event);
     for (auto& sp : k->spans) { (void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b); }
@@ -1010,8 +1026,9 @@ int llcomp_mi::codec_create(llcomp_mi_codec** out, int32_t device, uint32_t fram
     // where the codec's family does not (region_snapshot_bound; the decoded box is the resized path's)
     const uint64_t b_update = (uint64_t(g.n_slices) + 1 + lane_groups(g) + 1) * 8 +
                               (snap ? 0 : region_snapshot_bound(g) ? region_snapshot_bound(g) * 28 + uint64_t(g.n_slices) * 64 : 0);
-    k->workspace_bytes = b_sym + b_lanes + b_states + b_scratch + b_off + 8 + snap_el * (snapshot_chunked(g) ? 28 : 18) + b_region + b_regions +
-                         b_resized + b_update;
+    // (snapshot_chunked: the five arrays and the coder's parking records, 64 bytes per slice)
+    const uint64_t b_snap = snap_el * (snapshot_chunked(g) ? 28 : 18) + (snap && snapshot_chunked(g) ? uint64_t(g.n_slices) * 64 : 0);
+    k->workspace_bytes = b_sym + b_lanes + b_states + b_scratch + b_off + 8 + b_snap + b_region + b_regions + b_resized + b_update;
     const bool ok = dev_alloc(&k->d_sym_or_rec, b_sym) == hipSuccess && dev_alloc(&k->d_lane_order, b_lanes) == hipSuccess &&
                     dev_alloc(reinterpret_cast<void**>(&k->d_scratch), b_scratch) == hipSuccess &&
                     dev_alloc(reinterpret_cast<void**>(&k->d_group_off), b_off) == hipSuccess &&
@@ -1100,6 +1117,7 @@ int llcomp_mi_codec_encode(llcomp_mi_codec* k, const void* d_px, void* d_payload
     if (misaligned(d_slice_len, 4) || misaligned(d_total, 8) || misaligned(d_status, 4)) return LLCOMP_MI_BAD_ARGS;
     DeviceGuard guard(k->device);
     if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
+    if (int rc = ensure_encode(k, k->g)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     DoneGuard done_guard{k, s};
     HIP_TRY(hipMemsetAsync(d_status, 0, 4, s));
@@ -1119,6 +1137,7 @@ int llcomp_mi_codec_decode(llcomp_mi_codec* k, const void* d_payload, uint64_t p
     if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Geometry& g = k->g;
+    if (int rc = ensure_decode(k, g)) return rc;
     DoneGuard done_guard{k, s};
     HIP_TRY(hipMemsetAsync(d_status, 0, 4, s));
     const int rc = decode_chain(
@@ -1159,6 +1178,7 @@ int llcomp_mi_codec_decode_region(llcomp_mi_codec* k, const void* d_payload, uin
     DeviceGuard guard(k->device);
     if (!guard.ok) return LLCOMP_MI_HIP_ERROR;
     if (int rc = ensure_region_arrays(k)) return rc;
+    if (int rc = ensure_decode(k, sub)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Geometry& g = k->g;
     DoneGuard done_guard{k, s};
@@ -1223,7 +1243,9 @@ int update_box_pixels(llcomp_mi_codec* k, const UpdatePlan& p, const void* d_pay
 int update_ensure(llcomp_mi_codec* k, const UpdatePlan& p) {
     if (int rc = ensure_region_arrays(k)) return rc;
     if (int rc = ensure_update_arrays(k)) return rc;
+    if (int rc = ensure_encode(k, p.sub)) return rc;
     if (p.whole) return LLCOMP_MI_OK;
+    if (int rc = ensure_decode(k, p.sub)) return rc;
     const uint64_t samples = uint64_t(k->g.frames) * k->g.w * k->g.h * k->g.c;
     return ensure_grown(k, k->d_box, k->box_cap, uint64_t(p.sub.frames) * p.sub.w * p.sub.h * p.sub.c, samples);
 }
@@ -1855,3 +1877,69 @@ int llcomp_mi_codec_get_profile(llcomp_mi_codec* k, double* ms8, uint32_t* n_enc
 
 }  // extern "C"
 
+#if defined(LLMI_TEST_FAIL_ALLOC) && LLMI_TEST_FAIL_ALLOC
+// The guard build with the allocation fault injector (devmem.hip; tests/test_gpu_alloc_failures.py calls this after every injected
+// failure and makes its follow-up call only on 0): a host-only walk of the codec object.  0, or the number of the first broken invariant:
+//    1  a buffer the codec is created with is missing
+//    2  the snapshot arrays are there in part (sorted / banks / residuals / snap_el; context / chunk states)
+//    3  snapshot arrays with chunks without the coder's parking records
+//    4  parking records, overlap on, and the second stream or one of its events missing
+//    5  d_region_len without d_region_off, or the reverse
+//    6  d_regions without a slot of the pinned ring or one of its events, or a slot too small for a table
+//    7  a slot of the ring and its capacity disagree
+//    8  a grown buffer and its capacity disagree (the n-th of the list below: 8 + 100 * n)
+//    9  a pointer of the object is no live block of the allocator (the n-th of the walk: 9 + 100 * n)
+//   10  allocated_bytes is not the sum of what the object's blocks were asked for
+//   11  what the codec holds, the batch calls' tables and the chains' buffers aside, is above workspace_bytes
+extern "C" int llmi_test_codec_consistent(const llcomp_mi_codec* k) {
+    if (!k) return -1;
+    if (!k->d_sym_or_rec || !k->d_lane_order || !k->d_scratch || !k->d_group_off || !k->d_total_tmp || !k->d_counters) return 1;
+    const bool some = k->d_snap_sorted || k->d_snap_banks || k->d_snap_res || k->snap_el;
+    const bool all = k->d_snap_sorted && k->d_snap_banks && k->d_snap_res && k->snap_el;
+    if (some != all || !k->d_snap_ctx != !k->d_snap_io || (k->d_snap_ctx && !all)) return 2;
+    if (k->d_snap_ctx && !k->d_seg_state) return 3;
+    if (k->d_seg_state && k->overlap) {
+        if (!k->aux || !k->ev_fork) return 4;
+        for (hipEvent_t ev : k->ev_chunk)
+            if (!ev) return 4;
+    }
+    if (!k->d_region_len != !k->d_region_off) return 5;
+    for (uint32_t i = 0; i < llcomp_mi_codec::kRegionsRing; ++i) {
+        if (k->d_regions && (!k->h_regions[i] || !k->regions_ev[i] || k->h_regions_cap[i] < uint64_t(k->g.frames) * sizeof(RegionsFrame))) return 6;
+        if (!k->h_regions[i] != !k->h_regions_cap[i]) return 7;
+    }
+    const struct { const void* p; uint64_t cap; } grown[] = {
+        {k->d_stage, k->stage_cap},           {k->d_box, k->box_cap},           {k->d_mid, k->mid_cap},           {k->d_photo, k->photo_cap},
+        {k->d_photo_tab, k->photo_tab_cap},   {k->d_mix_tab, k->mix_tab_cap},   {k->d_mix, k->mix_cap},           {k->d_orient_tab, k->orient_tab_cap},
+        {k->d_compose_tab, k->compose_tab_cap}, {k->d_paste_tab, k->paste_tab_cap}, {k->d_paste16_tab, k->paste16_tab_cap},
+        {k->d_label16_tab, k->label16_tab_cap}, {k->d_target_tab, k->target_tab_cap}};
+    int n = 0;
+    for (const auto& gb : grown) {
+        if (!gb.p != !gb.cap) return 8 + 100 * n;
+        ++n;
+    }
+    const void* const held[] = {k->d_sym_or_rec,  k->d_lane_order, k->d_states,     k->d_scratch,     k->d_group_off,   k->d_total_tmp, k->d_region_len,
+                                k->d_region_off,  k->d_regions,    k->d_stage,      k->d_box,         k->d_mid,         k->d_photo,     k->d_photo_tab,
+                                k->d_mix_tab,     k->d_mix,        k->d_orient_tab, k->d_compose_tab, k->d_paste_tab,   k->d_paste16_tab,
+                                k->d_label16_tab, k->d_target_tab, k->d_upd_goff,   k->d_snap_sorted, k->d_snap_banks,  k->d_snap_res,
+                                k->d_snap_ctx,    k->d_snap_io,    k->d_seg_state};
+    uint64_t sum = 0;
+    n = 0;
+    for (const void* p : held) {
+        if (p) {
+            const uint64_t asked = test_block_requested(p);
+            if (asked == ~0ull) return 9 + 100 * n;
+            sum += asked;
+        }
+        ++n;
+    }
+    if (test_block_requested(k->d_counters) == ~0ull) return 9 + 100 * n;  // (the counters are not part of allocated_bytes)
+    if (sum != k->allocated_bytes) return 10;
+    uint64_t aside = k->photo_cap + k->photo_tab_cap + k->mix_tab_cap + k->mix_cap + k->orient_tab_cap + k->compose_tab_cap + k->paste_tab_cap +
+                     k->paste16_tab_cap + k->label16_tab_cap + k->target_tab_cap;
+    const uint64_t stage = stage_bound(k->g) + resized_tables_bound(k->g);  // (what workspace_bytes counts for d_stage: more views add more)
+    if (k->stage_cap > stage) aside += k->stage_cap - stage;
+    if (k->allocated_bytes - aside > k->workspace_bytes) return 11;
+    return 0;
+}
+#endif

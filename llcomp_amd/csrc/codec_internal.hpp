@@ -244,5 +244,13 @@ void dev_release_idle();
 uint64_t dev_idle_bytes();
 void dev_set_limit(uint64_t bytes_per_device);  // parked bytes allowed per device (0: every free goes to the driver)
 uint64_t dev_limit();
+// ... and every pinned buffer from here: hipHostMalloc and hipHostFree
+hipError_t host_alloc_pinned(void** p, size_t bytes, unsigned int flags);
+hipError_t host_free_pinned(void* p);
+#if defined(LLMI_TEST_FAIL_ALLOC) && LLMI_TEST_FAIL_ALLOC
+// the guard build with the allocation fault injector (devmem.hip): the bytes the holder of live block p asked for, ~0 for a pointer that
+// is no live block
+uint64_t test_block_requested(const void* p);
+#endif
 
 }  // namespace llcomp_mi

@@ -27,7 +27,108 @@
 
 #include "codec_internal.hpp"
 
+// -DLLMI_TEST_FAIL_ALLOC=1 (csrc/Makefile `guards`: ../libllcomp_mi_failalloc.so, tests/test_gpu_alloc_failures.py): an allocation fault
+// injector in front of every device and pinned allocation of the library.  Requests are numbered from 0 in the order they arrive; the test
+// names the ordinals that fail with hipErrorOutOfMemory WITHOUT touching the driver or the cache, or makes the next raw allocations fail so
+// that dev_alloc's release-and-retry path runs.  The product build has none of it.
+#ifndef LLMI_TEST_FAIL_ALLOC
+#define LLMI_TEST_FAIL_ALLOC 0
+#endif
+
+#if LLMI_TEST_FAIL_ALLOC
+namespace {
+struct TestInjector {
+    std::mutex mu;
+    uint64_t requests = 0;                           // dev_alloc + host_alloc_pinned calls so far
+    uint64_t fail_first = 0, fail_count = 0;         // ordinals [fail_first, fail_first + fail_count) fail
+    uint32_t fail_raw = 0;                           // the next raw_alloc calls that fail
+    std::unordered_map<const void*, uint64_t> live;  // device blocks handed out and not parked -> the bytes their caller asked for
+    uint64_t live_bytes = 0;
+    std::unordered_map<const void*, uint64_t> pinned;  // pinned buffers handed out and not freed
+};
+TestInjector& injector() {
+    static TestInjector* t = new TestInjector;
+    return *t;
+}
+bool test_request_fails() {
+    TestInjector& t = injector();
+    std::lock_guard<std::mutex> lock(t.mu);
+    const uint64_t ordinal = t.requests++;
+    return ordinal >= t.fail_first && ordinal - t.fail_first < t.fail_count;
+}
+bool test_raw_fails() {
+    TestInjector& t = injector();
+    std::lock_guard<std::mutex> lock(t.mu);
+    if (!t.fail_raw) return false;
+    --t.fail_raw;
+    return true;
+}
+void test_block_out(const void* p, uint64_t bytes) {
+    TestInjector& t = injector();
+    std::lock_guard<std::mutex> lock(t.mu);
+    t.live[p] = bytes;
+    t.live_bytes += bytes;
+}
+void test_block_back(const void* p) {
+    TestInjector& t = injector();
+    std::lock_guard<std::mutex> lock(t.mu);
+    auto it = t.live.find(p);
+    if (it == t.live.end()) return;
+    t.live_bytes -= it->second;
+    t.live.erase(it);
+}
+}  // namespace
+
+extern "C" {
+uint64_t llmi_test_alloc_requests(void) {
+    TestInjector& t = injector();
+    std::lock_guard<std::mutex> lock(t.mu);
+    return t.requests;
+}
+void llmi_test_fail_requests(uint64_t first, uint64_t count) {
+    TestInjector& t = injector();
+    std::lock_guard<std::mutex> lock(t.mu);
+    t.fail_first = first;
+    t.fail_count = count;
+}
+void llmi_test_fail_raw(uint32_t n) {
+    TestInjector& t = injector();
+    std::lock_guard<std::mutex> lock(t.mu);
+    t.fail_raw = n;
+}
+uint64_t llmi_test_live_blocks(void) {
+    TestInjector& t = injector();
+    std::lock_guard<std::mutex> lock(t.mu);
+    return t.live.size();
+}
+uint32_t llmi_test_fail_raw_left(void) {
+    TestInjector& t = injector();
+    std::lock_guard<std::mutex> lock(t.mu);
+    return t.fail_raw;
+}
+uint64_t llmi_test_live_pinned(void) {
+    TestInjector& t = injector();
+    std::lock_guard<std::mutex> lock(t.mu);
+    return t.pinned.size();
+}
+uint64_t llmi_test_live_requested_bytes(void) {
+    TestInjector& t = injector();
+    std::lock_guard<std::mutex> lock(t.mu);
+    return t.live_bytes;
+}
+}
+#endif
+
 namespace llcomp_mi {
+
+#if LLMI_TEST_FAIL_ALLOC
+uint64_t test_block_requested(const void* p) {
+    TestInjector& t = injector();
+    std::lock_guard<std::mutex> lock(t.mu);
+    auto it = t.live.find(p);
+    return it == t.live.end() ? ~0ull : it->second;
+}
+#endif
 
 // An event that says "the work that used these blocks is done".  A codec object records one on the caller's stream at the
 // end of every encode / decode; when the codec is destroyed its blocks are parked WITH that event, and whoever takes such
@@ -82,6 +183,9 @@ uint64_t rounded(uint64_t bytes) {
 // fragments (after many allocate / free cycles) the same kernels ran up to 2x slower (TLB reach).  Large blocks ask for
 // physically contiguous memory first; any refusal falls back to a plain hipMalloc.
 hipError_t raw_alloc(void** p, uint64_t bytes) {
+#if LLMI_TEST_FAIL_ALLOC
+    if (test_raw_fails()) return hipErrorOutOfMemory;
+#endif
     if (bytes >= (64ull << 20) && hipExtMallocWithFlags(p, bytes, hipDeviceMallocContiguous) == hipSuccess) return hipSuccess;
     (void)hipGetLastError();
     return hipMalloc(p, bytes);
@@ -120,6 +224,9 @@ void enforce_limit_locked(DevPool& dp, int dev) {
 
 hipError_t dev_alloc(void** p, uint64_t bytes) {
     *p = nullptr;
+#if LLMI_TEST_FAIL_ALLOC
+    if (test_request_fails()) return hipErrorOutOfMemory;
+#endif
     int dev = 0;
     if (hipError_t e = hipGetDevice(&dev)) return e;
     const uint64_t need = rounded(bytes ? bytes : 1);
@@ -154,7 +261,38 @@ hipError_t dev_alloc(void** p, uint64_t bytes) {
         (void)hipGetLastError();
         if (hipDeviceSynchronize() != hipSuccess) (void)hipGetLastError();
     }
+#if LLMI_TEST_FAIL_ALLOC
+    test_block_out(*p, bytes);
+#endif
     return hipSuccess;
+}
+
+// every pinned allocation of the library: hipHostMalloc, and nothing else in the product build
+hipError_t host_alloc_pinned(void** p, size_t bytes, unsigned int flags) {
+#if LLMI_TEST_FAIL_ALLOC
+    *p = nullptr;
+    if (test_request_fails()) return hipErrorOutOfMemory;
+    const hipError_t e = hipHostMalloc(p, bytes, flags);
+    if (e == hipSuccess) {
+        TestInjector& t = injector();
+        std::lock_guard<std::mutex> lock(t.mu);
+        t.pinned[*p] = bytes;
+    }
+    return e;
+#else
+    return hipHostMalloc(p, bytes, flags);
+#endif
+}
+// ... and its free: hipHostFree, and nothing else in the product build
+hipError_t host_free_pinned(void* p) {
+#if LLMI_TEST_FAIL_ALLOC
+    {
+        TestInjector& t = injector();
+        std::lock_guard<std::mutex> lock(t.mu);
+        t.pinned.erase(p);
+    }
+#endif
+    return hipHostFree(p);
 }
 
 void dev_free(void* p, const std::shared_ptr<DoneEvent>& done) {
@@ -163,6 +301,9 @@ void dev_free(void* p, const std::shared_ptr<DoneEvent>& done) {
     std::lock_guard<std::mutex> lock(dp.mu);
     auto it = dp.owned.find(p);
     if (it == dp.owned.end()) return;  // not ours (never happens: every buffer of the library comes from dev_alloc)
+#if LLMI_TEST_FAIL_ALLOC
+    test_block_back(p);
+#endif
     it->second.done = done;
     const int dev = it->second.dev;
     dp.idle.insert({{dev, it->second.size}, p});

@@ -36,7 +36,7 @@ void lane_destroy(HostLane* l) {
         dev_free(l->d_container);
         dev_free(l->d_len_legacy);
         dev_free(l->d_meta);
-        if (l->h_meta) (void)hipHostFree(l->h_meta);
+        if (l->h_meta) (void)host_free_pinned(l->h_meta);
         if (l->stream) (void)hipStreamDestroy(l->stream);
     }
     codec_release(l->k);  // the lane's stream was synchronised above; nothing else runs on this codec
@@ -88,7 +88,7 @@ int lane_create(HostLane** out, int dev, uint32_t w, uint32_t h, uint32_t c, uin
                     dev_alloc(reinterpret_cast<void**>(&l->d_px), raw + 4) == hipSuccess &&
                     dev_alloc(reinterpret_cast<void**>(&l->d_len_legacy), 4) == hipSuccess &&
                     dev_alloc(reinterpret_cast<void**>(&l->d_meta), l->meta_bytes()) == hipSuccess &&
-                    hipHostMalloc(reinterpret_cast<void**>(&l->h_meta), l->meta_bytes(), hipHostMallocDefault) == hipSuccess;
+                    host_alloc_pinned(reinterpret_cast<void**>(&l->h_meta), l->meta_bytes(), hipHostMallocDefault) == hipSuccess;
     if (!ok) {
         lane_destroy(l);
         return LLCOMP_MI_NOMEM;
@@ -564,12 +564,12 @@ void* llcomp_mi_host_alloc(size_t bytes) {
     // portable: a buffer from here is handed to EVERY device of a device list (multidev.hip: each GPU copies its rows / its payload
     // straight out of / into the caller's buffer), not only to the device that was current when it was allocated
     void* p = nullptr;
-    if (hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocPortable | hipHostMallocMapped) != hipSuccess) return nullptr;
+    if (host_alloc_pinned(&p, bytes ? bytes : 1, hipHostMallocPortable | hipHostMallocMapped) != hipSuccess) return nullptr;
     return p;
 }
 
 void llcomp_mi_host_free(void* p) {
-    if (p) (void)hipHostFree(p);
+    if (p) (void)host_free_pinned(p);
 }
 
 }  // extern "C"

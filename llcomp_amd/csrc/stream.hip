@@ -241,7 +241,7 @@ int llcomp_mi_stream_create_ex(llcomp_mi_stream** out, int32_t device, uint32_t 
         sl.part_len.assign(s->fpj, 0);
         s->out_cap = std::max<uint64_t>(s->raw * s->fpj, uint64_t(LLCOMP_MI_SLICED_HEADER_BYTES) * s->fpj + 4ull * s->spf * s->fpj + sl.lane->payload_cap);
         // (portable: behind a device list an encode result of THIS device's pipeline is handed to the decode job of another's)
-        if (hipHostMalloc(reinterpret_cast<void**>(&sl.h_out), s->out_cap, hipHostMallocPortable | hipHostMallocMapped) != hipSuccess) rc = LLCOMP_MI_NOMEM;
+        if (host_alloc_pinned(reinterpret_cast<void**>(&sl.h_out), s->out_cap, hipHostMallocPortable | hipHostMallocMapped) != hipSuccess) rc = LLCOMP_MI_NOMEM;
         else if (hipEventCreateWithFlags(&sl.e1, hipEventDisableTiming) != hipSuccess ||
                  hipEventCreateWithFlags(&sl.e2, hipEventDisableTiming) != hipSuccess)
             rc = LLCOMP_MI_HIP_ERROR;
@@ -291,7 +291,7 @@ void llcomp_mi_stream_destroy(llcomp_mi_stream* s) {
     DeviceGuard guard(s->device);
     for (Slot& sl : s->slots) {
         if (sl.lane && sl.lane->stream) (void)hipStreamSynchronize(sl.lane->stream);
-        if (sl.h_out) (void)hipHostFree(sl.h_out);
+        if (sl.h_out) (void)host_free_pinned(sl.h_out);
         if (sl.e1) (void)hipEventDestroy(sl.e1);
         if (sl.e2) (void)hipEventDestroy(sl.e2);
         lane_destroy(sl.lane);
