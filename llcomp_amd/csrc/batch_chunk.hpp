@@ -1,13 +1,21 @@
 // batch_chunk.hpp -- sixteen bytes of a batch as the batch kernels hold them (mix_kernels.hip, orient_kernels.hip, compose_kernels.hip;
 // DESIGN.md "Batch calls: what the three share"): four words, PER = 16 / ES elements, element e in word e * ES / 4.  The words are
-// anything with a [] of uint32_t: the kernels' vector type Chunk below, and the array of compose_rule.hpp's ComposeChunk, which the
-// host check walks too -- so the element's word and shift are stated here once, for the device and for g++.
+// anything with a [] of uint32_t: the kernels' vector type Chunk below, and the array of BatchChunk, the unit of the rules that the host
+// checks walk too (compose_rule.hpp, paste_rule.hpp, label_boxes_rule.hpp, label_targets_rule.hpp) -- so the element's word and shift
+// are stated here once, for the device and for g++.  And the two memories those rules run on: DeviceMem, global memory as it is, and
+// PlainMem, host memory as it is (the references); the host checks bring checking ones of the same four functions.
 #pragma once
 #include <cstdint>
+#include <cstring>
 
 #include "geometry.hpp"
 
 #define LLMI_CHUNK_FN LLMI_HD inline __attribute__((always_inline))
+#if defined(__clang__)
+#define LLMI_UNROLL _Pragma("unroll")
+#else
+#define LLMI_UNROLL
+#endif
 
 namespace llcomp_mi {
 
@@ -18,6 +26,14 @@ template <uint32_t ES> struct ElemOf;
 template <> struct ElemOf<1> { using T = uint8_t; };
 template <> struct ElemOf<2> { using T = uint16_t; };
 template <> struct ElemOf<4> { using T = uint32_t; };
+template <> struct ElemOf<8> { using T = uint64_t; };
+
+// 16 bytes, for the host checks as for the kernels; the names the composition's and the label calls' rules and checks know it by
+struct BatchChunk {
+    uint32_t w[4];
+};
+using ComposeChunk = BatchChunk;
+using LabelChunk = BatchChunk;
 
 template <uint32_t ES, class W>
 LLMI_CHUNK_FN uint32_t chunk_get(const W& v, uint32_t e) {
@@ -37,5 +53,57 @@ LLMI_CHUNK_FN void chunk_or(W& v, uint32_t e, uint32_t bits) {  // (into a chunk
     else if constexpr (ES == 2) v[e >> 1] |= bits << (16 * (e & 1));
     else v[e >> 2] |= bits << (8 * (e & 3));
 }
+
+// The memory of the rules: load16 / store16 of aligned 16-byte units, load_el<N> / store_el<N> of an N-byte element at an address
+// aligned to N (the bits in the low N bytes)
+#if defined(__HIPCC__)
+struct DeviceMem {
+    __device__ inline __attribute__((always_inline)) BatchChunk load16(uint64_t a) const {
+        const Chunk v = *reinterpret_cast<const Chunk*>(__builtin_assume_aligned(reinterpret_cast<const void*>(a), 16));
+        return BatchChunk{{v[0], v[1], v[2], v[3]}};
+    }
+    __device__ inline __attribute__((always_inline)) void store16(uint64_t a, const BatchChunk& c) const {
+        *reinterpret_cast<Chunk*>(__builtin_assume_aligned(reinterpret_cast<void*>(a), 16)) = Chunk{c.w[0], c.w[1], c.w[2], c.w[3]};
+    }
+    template <uint32_t N>
+    __device__ inline __attribute__((always_inline)) uint32_t load_el(uint64_t a) const {
+        return *reinterpret_cast<const typename ElemOf<N>::T*>(a);
+    }
+    template <uint32_t N>
+    __device__ inline __attribute__((always_inline)) void store_el(uint64_t a, uint64_t bits) const {
+        *reinterpret_cast<typename ElemOf<N>::T*>(a) = static_cast<typename ElemOf<N>::T>(bits);
+    }
+};
+#endif
+// The aligned unit at u of a batch of N-byte pixels at [base, base + bytes), of which the pixels [p0, p1) are wanted: read whole where
+// it lies inside the batch, pixel by pixel where it sticks out (the other pixels: zeros).  What the label calls read their maps with.
+template <uint32_t N, class Mem>
+LLMI_CHUNK_FN BatchChunk chunk_read(uint64_t base, uint64_t bytes, uint64_t u, uint32_t p0, uint32_t p1, Mem& mem) {
+    if (u >= base && u + 16 <= base + bytes) return mem.load16(u);
+    BatchChunk v{{0u, 0u, 0u, 0u}};
+    LLMI_UNROLL
+    for (uint32_t p = 0; p < 16 / N; ++p)
+        if (p >= p0 && p < p1) chunk_or<N>(v.w, p, mem.template load_el<N>(u + N * p));
+    return v;
+}
+
+struct PlainMem {  // (little-endian hosts, like the containers)
+    BatchChunk load16(uint64_t a) const {
+        BatchChunk v;
+        std::memcpy(&v, reinterpret_cast<const void*>(uintptr_t(a)), 16);
+        return v;
+    }
+    void store16(uint64_t a, const BatchChunk& c) const { std::memcpy(reinterpret_cast<void*>(uintptr_t(a)), &c, 16); }
+    template <uint32_t N>
+    uint32_t load_el(uint64_t a) const {
+        uint32_t v = 0;
+        std::memcpy(&v, reinterpret_cast<const void*>(uintptr_t(a)), N);
+        return v;
+    }
+    template <uint32_t N>
+    void store_el(uint64_t a, uint64_t bits) const {
+        std::memcpy(reinterpret_cast<void*>(uintptr_t(a)), &bits, N);
+    }
+};
 
 }  // namespace llcomp_mi

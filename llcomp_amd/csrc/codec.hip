@@ -21,15 +21,12 @@
 #include "compose.hpp"
 #include "compose_rule.hpp"
 #include "label_boxes.hpp"
-#include "label_boxes16.hpp"
-#include "label_boxes16_rule.hpp"
-#include "label_targets.hpp"
 #include "label_boxes_rule.hpp"
+#include "label_lists.hpp"
+#include "label_targets.hpp"
 #include "orient.hpp"
 #include "orient_rule.hpp"
 #include "paste.hpp"
-#include "paste16.hpp"
-#include "paste16_rule.hpp"
 #include "paste_rule.hpp"
 #include "photo.hpp"
 #include "resize.hpp"
@@ -433,6 +430,38 @@ int batch_table_call(llcomp_mi_codec* k, uint8_t*& tab, uint64_t& cap, uint64_t 
     if (int rc = regions_slot_queued(k, slot, s)) return rc;
     HIP_TRY(launch(tab));
     return LLCOMP_MI_OK;
+}
+
+// The batch copy-paste of either width of id map (DESIGN.md "Batch copy-paste", "Batch copy-paste by 16-bit ids"), P its piece type:
+// paste_plan.hpp's checks, plan and table through the width's own table buffer.  A call without a piece that selects anything queues
+// nothing.
+template <class P>
+int paste_batch_call(llcomp_mi_codec* k, uint8_t*& tab, uint64_t& cap, const void* d_src, const void* d_mask, uint32_t n_src, uint32_t iw, uint32_t ih,
+                     void* d_dst, uint32_t n_dst, uint32_t ow, uint32_t oh, uint32_t dtype, uint32_t layout, const P* pieces, uint32_t n_pieces,
+                     void* stream) {
+    constexpr uint32_t MB = kPasteMaskBytesOf<P>;
+    if (!k || !d_dst) return LLCOMP_MI_BAD_ARGS;
+    const uint32_t c = k->g.c;
+    std::vector<uint32_t> value_bits;
+    if (int rc = paste_check_call(n_src, iw, ih, n_dst, ow, oh, c, dtype, layout, pieces, n_pieces, value_bits)) return rc;
+    const uint32_t esize = batch_esize(dtype);
+    if (int rc = paste_check_memory(d_src, uint64_t(n_src) * c * iw * ih * esize, d_mask, MB * uint64_t(n_src) * iw * ih, d_dst,
+                                    uint64_t(n_dst) * c * ow * oh * esize, esize, MB, n_pieces))
+        return rc;
+    PastePlan p;
+    paste_plan(n_dst, pieces, n_pieces, p);
+    if (p.samples.empty()) return LLCOMP_MI_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return batch_table_call(
+        k, tab, cap, PasteTable<MB>(p.samples.size(), p.order.size()).bytes, paste_table_bound<MB>(n_dst, n_pieces), s,
+        [&](uint8_t* at) { paste_table_put(pieces, p, value_bits, c, layout, at); },
+        [&](const uint8_t* d_table) {
+            PasteLaunch o{};
+            o.d_src = static_cast<const uint8_t*>(d_src), o.d_mask = static_cast<const uint8_t*>(d_mask), o.d_dst = static_cast<uint8_t*>(d_dst);
+            o.d_table = d_table, o.n_samples = uint32_t(p.samples.size()), o.n_recs = uint32_t(p.order.size());
+            o.n_src = n_src, o.iw = iw, o.ih = ih, o.ow = ow, o.oh = oh, o.c = c, o.dtype = dtype, o.layout = layout;
+            return launch_paste(o, MB, s);
+        });
 }
 
 // The decode chain on geometry `sub` -- the codec's own, or the sub-geometry of a region, a box or a class -- in order on `s`: a state
@@ -1654,70 +1683,30 @@ uint64_t llcomp_mi_codec_compose_workspace_bytes(const llcomp_mi_codec* k, uint3
     return k->workspace_bytes + compose_table_bound(n_dst, n_pieces, k->g.c);
 }
 
-// Batch copy-paste (DESIGN.md "Batch copy-paste"): paste_check_memory refuses too.  A call without a piece that selects anything queues
-// nothing.
+// Batch copy-paste (DESIGN.md "Batch copy-paste"): paste_batch_call with the 8-bit call's table buffer.
 int llcomp_mi_codec_paste_batch(llcomp_mi_codec* k, const void* d_src, const void* d_mask, uint32_t n_src, uint32_t iw, uint32_t ih, void* d_dst,
                                 uint32_t n_dst, uint32_t ow, uint32_t oh, uint32_t dtype, uint32_t layout, const llcomp_mi_paste_piece* pieces,
                                 uint32_t n_pieces, void* stream) {
-    if (!k || !d_dst) return LLCOMP_MI_BAD_ARGS;
-    const uint32_t c = k->g.c;
-    std::vector<uint32_t> value_bits;
-    if (int rc = paste_check_call(n_src, iw, ih, n_dst, ow, oh, c, dtype, layout, pieces, n_pieces, value_bits)) return rc;
-    const uint32_t esize = batch_esize(dtype);
-    if (int rc = paste_check_memory(d_src, uint64_t(n_src) * c * iw * ih * esize, d_mask, uint64_t(n_src) * iw * ih, d_dst,
-                                    uint64_t(n_dst) * c * ow * oh * esize, esize, n_pieces))
-        return rc;
-    PastePlan p;
-    paste_plan(n_dst, pieces, n_pieces, p);
-    if (p.samples.empty()) return LLCOMP_MI_OK;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    return batch_table_call(
-        k, k->d_paste_tab, k->paste_tab_cap, PasteTable(p.samples.size(), p.order.size()).bytes, paste_table_bound(n_dst, n_pieces), s,
-        [&](uint8_t* at) { paste_table_put(pieces, p, value_bits, c, layout, at); },
-        [&](const uint8_t* d_table) {
-            PasteLaunch o{};
-            o.d_src = static_cast<const uint8_t*>(d_src), o.d_mask = static_cast<const uint8_t*>(d_mask), o.d_dst = static_cast<uint8_t*>(d_dst);
-            o.d_table = d_table, o.n_samples = uint32_t(p.samples.size()), o.n_recs = uint32_t(p.order.size());
-            o.n_src = n_src, o.iw = iw, o.ih = ih, o.ow = ow, o.oh = oh, o.c = c, o.dtype = dtype, o.layout = layout;
-            return launch_paste(o, s);
-        });
+    if (!k) return LLCOMP_MI_BAD_ARGS;
+    return paste_batch_call(k, k->d_paste_tab, k->paste_tab_cap, d_src, d_mask, n_src, iw, ih, d_dst, n_dst, ow, oh, dtype, layout, pieces, n_pieces, stream);
 }
 
 uint64_t llcomp_mi_codec_paste_workspace_bytes(const llcomp_mi_codec* k, uint32_t n_dst, uint32_t n_pieces) {
     if (!k) return 0;
-    return k->workspace_bytes + paste_table_bound(n_dst, n_pieces);
+    return k->workspace_bytes + paste_table_bound<1>(n_dst, n_pieces);
 }
 
-// Batch copy-paste by 16-bit ids (DESIGN.md "Batch copy-paste by 16-bit ids"): as above with paste16_plan.hpp's checks and table.
+// Batch copy-paste by 16-bit ids (DESIGN.md "Batch copy-paste by 16-bit ids"): the same with the 16-bit call's table buffer.
 int llcomp_mi_codec_paste_batch16(llcomp_mi_codec* k, const void* d_src, const void* d_mask, uint32_t n_src, uint32_t iw, uint32_t ih, void* d_dst,
                                   uint32_t n_dst, uint32_t ow, uint32_t oh, uint32_t dtype, uint32_t layout, const llcomp_mi_paste_piece16* pieces,
                                   uint32_t n_pieces, void* stream) {
-    if (!k || !d_dst) return LLCOMP_MI_BAD_ARGS;
-    const uint32_t c = k->g.c;
-    if (int rc = paste16_check_call(n_src, iw, ih, n_dst, ow, oh, c, dtype, layout, pieces, n_pieces)) return rc;
-    const uint32_t esize = batch_esize(dtype);
-    if (int rc = paste16_check_memory(d_src, uint64_t(n_src) * c * iw * ih * esize, d_mask, 2 * uint64_t(n_src) * iw * ih, d_dst,
-                                      uint64_t(n_dst) * c * ow * oh * esize, esize, n_pieces))
-        return rc;
-    PastePlan p;
-    paste16_plan(n_dst, pieces, n_pieces, p);
-    if (p.samples.empty()) return LLCOMP_MI_OK;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    return batch_table_call(
-        k, k->d_paste16_tab, k->paste16_tab_cap, PasteTable16(p.samples.size(), p.order.size()).bytes, paste16_table_bound(n_dst, n_pieces), s,
-        [&](uint8_t* at) { paste16_table_put(pieces, p, c, layout, at); },
-        [&](const uint8_t* d_table) {
-            PasteLaunch o{};
-            o.d_src = static_cast<const uint8_t*>(d_src), o.d_mask = static_cast<const uint8_t*>(d_mask), o.d_dst = static_cast<uint8_t*>(d_dst);
-            o.d_table = d_table, o.n_samples = uint32_t(p.samples.size()), o.n_recs = uint32_t(p.order.size());
-            o.n_src = n_src, o.iw = iw, o.ih = ih, o.ow = ow, o.oh = oh, o.c = c, o.dtype = dtype, o.layout = layout;
-            return launch_paste16(o, s);
-        });
+    if (!k) return LLCOMP_MI_BAD_ARGS;
+    return paste_batch_call(k, k->d_paste16_tab, k->paste16_tab_cap, d_src, d_mask, n_src, iw, ih, d_dst, n_dst, ow, oh, dtype, layout, pieces, n_pieces, stream);
 }
 
 uint64_t llcomp_mi_codec_paste16_workspace_bytes(const llcomp_mi_codec* k, uint32_t n_dst, uint32_t n_pieces) {
     if (!k) return 0;
-    return k->workspace_bytes + paste16_table_bound(n_dst, n_pieces);
+    return k->workspace_bytes + paste_table_bound<2>(n_dst, n_pieces);
 }
 
 // Label boxes (DESIGN.md "Label boxes"): the codec gives the device; no table, no workspace.

@@ -82,11 +82,11 @@ struct llcomp_mi_codec {
     // (paste_plan.hpp: PasteTable); grown by the calls that need more
     uint8_t* d_paste_tab = nullptr;
     uint64_t paste_tab_cap = 0;
-    // batch copy-paste by 16-bit ids (llcomp_mi_codec_paste_batch16): the same with records of 72 bytes (paste16_plan.hpp: PasteTable16)
+    // batch copy-paste by 16-bit ids (llcomp_mi_codec_paste_batch16): the same with records of 72 bytes (paste_plan.hpp: PasteTable<2>)
     uint8_t* d_paste16_tab = nullptr;
     uint64_t paste16_tab_cap = 0;
     // label boxes of listed ids (llcomp_mi_codec_label_boxes16): where a call's one copy lands, the lists' bounds, the listed samples and
-    // the ids (label_boxes16_rule.hpp: Label16Table); grown by the calls that need more
+    // the ids (label_lists.hpp: Label16Table); grown by the calls that need more
     uint8_t* d_label16_tab = nullptr;
     uint64_t label16_tab_cap = 0;
     // label targets (llcomp_mi_codec_label_targets): where a call's one copy lands, the lists' and the planes' bounds, the samples that

@@ -33,19 +33,12 @@ struct ComposeArgs {
     const uint32_t* fill;
 };
 
-// the memory of compose_rule.hpp's functions: global memory as it is
+// the memory of compose_rule.hpp's functions: global memory as it is (batch_chunk.hpp: DeviceMem), with the element's size bound --
+// the rule's load_el / store_el name no size, and its host check's memory is written to that
 template <uint32_t ES>
-struct DeviceMem {
-    using T = typename ElemOf<ES>::T;
-    __device__ __forceinline__ ComposeChunk load16(uint64_t a) const {
-        const Chunk v = *reinterpret_cast<const Chunk*>(__builtin_assume_aligned(reinterpret_cast<const void*>(a), 16));
-        return ComposeChunk{{v[0], v[1], v[2], v[3]}};
-    }
-    __device__ __forceinline__ void store16(uint64_t a, const ComposeChunk& c) const {
-        *reinterpret_cast<Chunk*>(__builtin_assume_aligned(reinterpret_cast<void*>(a), 16)) = Chunk{c.w[0], c.w[1], c.w[2], c.w[3]};
-    }
-    __device__ __forceinline__ uint32_t load_el(uint64_t a) const { return *reinterpret_cast<const T*>(a); }
-    __device__ __forceinline__ void store_el(uint64_t a, uint32_t bits) const { *reinterpret_cast<T*>(a) = T(bits); }
+struct ComposeMem : DeviceMem {
+    __device__ __forceinline__ uint32_t load_el(uint64_t a) const { return DeviceMem::load_el<ES>(a); }
+    __device__ __forceinline__ void store_el(uint64_t a, uint32_t bits) const { DeviceMem::store_el<ES>(a, bits); }
 };
 
 template <uint32_t ES>
@@ -85,7 +78,7 @@ __global__ __launch_bounds__(kComposeThreads) void k_compose(ComposeArgs a) {
     k.list = list, k.n_list = n_list, k.fill = fill, k.cmod = cmod, k.patterns = patterns, k.d = sm.dst, k.pl = pl;
     if (!k.n_list && g.keep) return;
     k.solo = filtered && compose_solo(list, k.n_list, box);
-    DeviceMem<ES> mem;
+    ComposeMem<ES> mem;
     if (filtered) {
         compose_tile_pass<ES>(g, k, box, threadIdx.x, kComposeThreads, mem);
     } else {  // (the same pass with the records in global memory)

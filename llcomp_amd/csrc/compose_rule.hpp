@@ -15,12 +15,6 @@
 #include "batch_chunk.hpp"
 #include "mix_rule.hpp"
 
-#if defined(__clang__)
-#define LLMI_UNROLL _Pragma("unroll")
-#else
-#define LLMI_UNROLL
-#endif
-
 namespace llcomp_mi {
 
 constexpr uint32_t kComposeTile = 128;                // pixels across a tile (llcomp_mi_compose_tile)
@@ -126,10 +120,7 @@ LLMI_HD inline int32_t compose_resolve(const ComposeRec* list, uint32_t n, uint3
     return -1;
 }
 
-// 16 bytes, for the host check as for the kernel; an element's word and shift in w: batch_chunk.hpp (chunk_or, chunk_get)
-struct ComposeChunk {
-    uint32_t w[4];
-};
+// (ComposeChunk, 16 bytes for the host check as for the kernel, and an element's word and shift in its w: batch_chunk.hpp)
 LLMI_HD inline uint32_t compose_alignbyte(uint32_t hi, uint32_t lo, uint32_t r) {  // bytes r .. r + 3 of hi:lo
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_alignbyte(hi, lo, r);

@@ -1,11 +1,14 @@
-// label_boxes_rule.hpp -- the rule of the label boxes (include/llcomp_mi.h: "Label boxes"), stated ONCE: the record's identity, the
-// update of a record by a run of equal bytes, and what a thread does with one 16-byte unit of map memory (label_boxes_unit).  Compiled
-// into the kernel (label_boxes_kernels.hip) and into llcomp_mi_label_boxes_reference (label_boxes.cpp), which walks the kernel's own
-// bands and units on the host.
+// label_boxes_rule.hpp -- the rule of the label boxes of both calls (include/llcomp_mi.h: "Label boxes", "Label boxes of listed ids"),
+// stated ONCE, templated on MB, the map's bytes per pixel (1 or 2): the record's identity, the update of a record by a run of equal
+// ids, and what a thread does with one 16-byte unit of map memory (label_boxes_unit).  Compiled into the kernels
+// (label_boxes_kernels.hip), into llcomp_mi_label_boxes_reference and llcomp_mi_label_boxes16_reference (label_boxes.cpp), which walk
+// the kernels' own bands, threads and units on the host, and into the stand-alone host check.  The lists of the listed call:
+// label_lists.hpp.
 //
 // A sample's rows are dense, so a band of kLabelBoxRows rows is one byte range; a workgroup takes it in the aligned 16-byte units of
-// MEMORY it lies in, of which a thread uses the bytes that belong to the band -- the others are the neighbouring band's or sample's.
-// Mem: load16 of an aligned unit, load_el<1> of a byte.  Sink: run(id, x_first, x_end, y, length), in any order.
+// MEMORY it lies in, 16 / MB pixels each, of which a thread uses the pixels that belong to the band -- the others are the neighbouring
+// band's or sample's.  A 2-byte map is aligned to 2 bytes, so a band's bounds are even and a pixel never straddles a unit.
+// Mem: batch_chunk.hpp's (load16 of an aligned unit, load_el<MB> of a pixel).  Sink: run(id, x_first, x_end, y, length), in any order.
 #pragma once
 #include <cstdint>
 
@@ -13,16 +16,11 @@
 #include "batch_chunk.hpp"
 #include "batch_ops.hpp"
 
-#if defined(__clang__)
-#define LLMI_LABEL_UNROLL _Pragma("unroll")
-#else
-#define LLMI_LABEL_UNROLL
-#endif
-
 namespace llcomp_mi {
 
-constexpr uint32_t kLabelIds = 256;      // records of a sample
+constexpr uint32_t kLabelIds = 256;      // records of a sample of the dense call
 constexpr uint32_t kLabelBoxRows = 32;   // rows of a workgroup's band (llcomp_mi_label_boxes_rows)
+constexpr uint32_t kLabelThreads = 256;  // of a workgroup
 
 // the record of an id without a pixel: the identities of min and max
 LLMI_HD inline llcomp_mi_label_box label_box_identity(uint32_t ow, uint32_t oh) { return llcomp_mi_label_box{0u, ow, oh, 0u, 0u}; }
@@ -33,7 +31,7 @@ LLMI_HD inline void label_box_update(llcomp_mi_label_box& b, uint32_t x_first, u
     b.y0 = y < b.y0 ? y : b.y0, b.y1 = y + 1 > b.y1 ? y + 1 : b.y1;
 }
 
-// A whole call but for its pointers
+// A whole call of the dense kind but for its pointers
 LLMI_HD inline int label_boxes_check_call(uint32_t n, uint32_t ow, uint32_t oh) {
     if (int rc = batch_check_shape(n, 1, ow, oh, LLCOMP_MI_DTYPE_U8, LLCOMP_MI_LAYOUT_HWC)) return rc;
     return uint64_t(ow) * oh >= (1ull << 32) ? LLCOMP_MI_BAD_ARGS : LLCOMP_MI_OK;
@@ -43,42 +41,34 @@ struct LabelGeom {
     uint64_t maps, bytes;  // the batch's first byte and its size
     uint32_t ow, oh, bands;
 };
+template <uint32_t MB>
 LLMI_HD inline LabelGeom label_geom(uint64_t maps, uint32_t n, uint32_t ow, uint32_t oh) {
-    return LabelGeom{maps, uint64_t(n) * ow * oh, ow, oh, (oh + kLabelBoxRows - 1) / kLabelBoxRows};
+    return LabelGeom{maps, MB * uint64_t(n) * ow * oh, ow, oh, (oh + kLabelBoxRows - 1) / kLabelBoxRows};
 }
 // the bytes of band b of sample i: [lo, hi)
+template <uint32_t MB>
 LLMI_HD inline void label_band(const LabelGeom& g, uint32_t i, uint32_t b, uint64_t& sample, uint64_t& lo, uint64_t& hi) {
     const uint32_t y0 = b * kLabelBoxRows, y1 = g.oh - y0 < kLabelBoxRows ? g.oh : y0 + kLabelBoxRows;
-    sample = g.maps + uint64_t(i) * g.ow * g.oh;
-    lo = sample + uint64_t(y0) * g.ow, hi = sample + uint64_t(y1) * g.ow;
+    sample = g.maps + MB * uint64_t(i) * g.ow * g.oh;
+    lo = sample + MB * uint64_t(y0) * g.ow, hi = sample + MB * uint64_t(y1) * g.ow;
 }
 
-struct LabelChunk {
-    uint32_t w[4];
-};
-
-// The unit at the aligned address u, which holds bytes of the band [lo, hi) of the sample at `sample`: its bytes of the band, runs of
-// equal bytes within a row collapsed, one update per run.  The unit is read whole where it lies inside the batch, byte by byte where
-// it sticks out.
-template <class Mem, class Sink>
+// The unit at the aligned address u, which holds pixels of the band [lo, hi) of the sample at `sample`: its pixels of the band, runs of
+// equal ids within a row collapsed, one update per run.  The unit is read whole where it lies inside the batch, pixel by pixel where
+// it sticks out (chunk_read).
+template <uint32_t MB, class Mem, class Sink>
 LLMI_HD inline void label_boxes_unit(const LabelGeom& g, uint64_t sample, uint64_t lo, uint64_t hi, uint64_t u, Mem& mem, Sink& sink) {
-    const uint32_t p0 = u < lo ? uint32_t(lo - u) : 0u, p1 = u + 16 > hi ? uint32_t(hi - u) : 16u;
+    constexpr uint32_t PER = 16 / MB;
+    const uint32_t p0 = (u < lo ? uint32_t(lo - u) : 0u) / MB, p1 = (u + 16 > hi ? uint32_t(hi - u) : 16u) / MB;
     if (p0 >= p1) return;
-    LabelChunk v{{0u, 0u, 0u, 0u}};
-    if (u >= g.maps && u + 16 <= g.maps + g.bytes) {
-        v = mem.load16(u);
-    } else {
-        LLMI_LABEL_UNROLL
-        for (uint32_t p = 0; p < 16; ++p)
-            if (p >= p0 && p < p1) chunk_or<1>(v.w, p, mem.template load_el<1>(u + p));
-    }
-    const uint32_t off = uint32_t(u + p0 - sample);
+    const LabelChunk v = chunk_read<MB>(g.maps, g.bytes, u, p0, p1, mem);
+    const uint32_t off = uint32_t((u + MB * p0 - sample) / MB);  // (in pixels: ow * oh < 2^32)
     uint32_t y = off / g.ow, x = off - y * g.ow;
     uint32_t id = 0, xs = x;
-    LLMI_LABEL_UNROLL
-    for (uint32_t p = 0; p < 16; ++p) {  // (p is a constant in every turn: the unit's words are never indexed by a variable)
+    LLMI_UNROLL
+    for (uint32_t p = 0; p < PER; ++p) {  // (p is a constant in every turn: the unit's words are never indexed by a variable)
         if (p < p0 || p >= p1) continue;
-        const uint32_t m = chunk_get<1>(v.w, p);
+        const uint32_t m = chunk_get<MB>(v.w, p);
         if (p == p0) {
             id = m;
             continue;
@@ -93,6 +83,12 @@ LLMI_HD inline void label_boxes_unit(const LabelGeom& g, uint64_t sample, uint64
         }
     }
     sink.run(id, xs, x + 1, y, x + 1 - xs);
+}
+
+// Thread t of the workgroup of the band [lo, hi): the band's aligned units t, t + 256, ...
+template <uint32_t MB, class Mem, class Sink>
+LLMI_HD inline void label_boxes_thread(const LabelGeom& g, uint64_t sample, uint64_t lo, uint64_t hi, uint32_t t, Mem& mem, Sink& sink) {
+    for (uint64_t u = (lo & ~uint64_t(15)) + 16 * uint64_t(t); u < hi; u += 16 * uint64_t(kLabelThreads)) label_boxes_unit<MB>(g, sample, lo, hi, u, mem, sink);
 }
 
 }  // namespace llcomp_mi

@@ -7,30 +7,6 @@
 #include "label_targets_rule.hpp"
 
 namespace llcomp_mi {
-namespace {
-
-struct PlainTargetMem {
-    LabelChunk load16(uint64_t a) const {
-        LabelChunk v;
-        std::memcpy(&v, reinterpret_cast<const void*>(uintptr_t(a)), 16);  // (little-endian hosts, like the containers)
-        return v;
-    }
-    template <uint32_t N>
-    uint32_t load_el(uint64_t a) const {
-        uint32_t v = 0;
-        std::memcpy(&v, reinterpret_cast<const void*>(uintptr_t(a)), N);
-        return v;
-    }
-};
-struct PlainTargetSink {
-    void store16(uint64_t a, const LabelChunk& c) const { std::memcpy(reinterpret_cast<void*>(uintptr_t(a)), &c, 16); }
-    template <uint32_t ES>
-    void store_el(uint64_t a, uint64_t bits) const {
-        std::memcpy(reinterpret_cast<void*>(uintptr_t(a)), &bits, ES);
-    }
-};
-
-}  // namespace
 
 void target_table_put(uint32_t n, const llcomp_mi_label_targets& t, const TargetCall& c, uint8_t* at) {
     const bool planes = t.kind == LLCOMP_MI_TARGET_PLANES;
@@ -70,12 +46,11 @@ int llcomp_mi_label_targets_reference(const void* maps, uint32_t n, uint32_t ow,
     const uint32_t K = t.map_bytes == 1 ? 256u : label16_capacity(c.longest), chunks = target_plane_chunks(t.kind, c.most_planes);
     std::vector<uint16_t> list(K);
     std::vector<uint32_t> vals(K), v(kTargetSegment);
-    PlainTargetMem mem;
-    PlainTargetSink sink;
+    PlainMem mem;  // (batch_chunk.hpp: host memory as it is, for the maps and for the output)
     for (uint32_t i = 0; i < n; ++i)
         for (uint32_t seg = 0; seg < g.segments; ++seg)
             for (uint32_t z = 0; z < chunks; ++z)
-                label_targets_host_workgroup(g, a, t.map_bytes, t.first, t.plane_first, t.values, t.ids, i, seg, z, mem, sink, list, vals, v);
+                label_targets_host_workgroup(g, a, t.map_bytes, t.first, t.plane_first, t.values, t.ids, i, seg, z, mem, mem, list, vals, v);
     return LLCOMP_MI_OK;
 }
 

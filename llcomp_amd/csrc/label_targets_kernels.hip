@@ -53,28 +53,6 @@ static_assert(sizeof(TargetLds<2, 4096, kPlanes>) == 32768 && 5 * sizeof(TargetL
 static_assert(kLabel16Capacities[0] == 256 && kLabel16Capacities[1] == 1024 && kLabel16Capacities[2] == 4096 && kLabel16MaxIds == 4096, "the three capacities compiled below");
 static_assert(kTargetMaxPlanes < kTargetNoPlane, "a plane index fits the LDS's uint16_t");
 
-typedef uint32_t TargetV4 __attribute__((ext_vector_type(4)));
-struct TargetDeviceMem {
-    __device__ __forceinline__ LabelChunk load16(uint64_t a) const {
-        const TargetV4 v = *reinterpret_cast<const TargetV4*>(__builtin_assume_aligned(reinterpret_cast<const void*>(a), 16));
-        return LabelChunk{{v[0], v[1], v[2], v[3]}};
-    }
-    template <uint32_t N>
-    __device__ __forceinline__ uint32_t load_el(uint64_t a) const {
-        return *reinterpret_cast<const typename ElemOf<N>::T*>(a);
-    }
-};
-struct TargetDeviceSink {
-    __device__ __forceinline__ void store16(uint64_t a, const LabelChunk& c) const {
-        *reinterpret_cast<TargetV4*>(__builtin_assume_aligned(reinterpret_cast<void*>(a), 16)) = TargetV4{c.w[0], c.w[1], c.w[2], c.w[3]};
-    }
-    template <uint32_t ES>
-    __device__ __forceinline__ void store_el(uint64_t a, uint64_t bits) const {
-        if constexpr (ES == 8) *reinterpret_cast<uint64_t*>(a) = bits;
-        else *reinterpret_cast<typename ElemOf<ES>::T*>(a) = static_cast<typename ElemOf<ES>::T>(bits);
-    }
-};
-
 // first[n + 1], samples[gridDim.y], plane_first[n + 1] (PLANES), values and ids: the call's table (TargetTable)
 template <uint32_t MB, uint32_t K, uint32_t KIND>
 __global__ __launch_bounds__(kTargetThreads) void k_label_targets(TargetGeom g, TargetParams a, const uint32_t* __restrict__ first, const uint32_t* __restrict__ samples,
@@ -107,13 +85,12 @@ __global__ __launch_bounds__(kTargetThreads) void k_label_targets(TargetGeom g, 
     }
     uint32_t s0, s1;
     target_segment(g, blockIdx.x, s0, s1);
-    TargetDeviceMem mem;
+    DeviceMem mem;  // (batch_chunk.hpp: global memory as it is, for the maps and for the output)
     TargetLookup<MB, const uint16_t*, const uint32_t*> look{{list, cnt}, vals, target_table_value(a.kind, a.default_value, planes)};
     label_targets_read_thread<MB>(g, i, s0, s1, t, mem, look, v);
     __syncthreads();
-    TargetDeviceSink sink;
     const TargetV<KIND>* cv = v;
-    label_targets_write_any<KIND>(g, i, s0, s1, plane0, k0, k1, t, a, cv, sink);
+    label_targets_write_any<KIND>(g, i, s0, s1, plane0, k0, k1, t, a, cv, mem);
 }
 
 template <uint32_t MB, uint32_t K>

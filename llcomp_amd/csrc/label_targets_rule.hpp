@@ -1,5 +1,5 @@
 // label_targets_rule.hpp -- the rule of the label targets (include/llcomp_mi.h: "Label targets"), stated ONCE on top of batch_ops.hpp,
-// batch_chunk.hpp and label_boxes16_rule.hpp, whose list check and list search it keeps: the check of a call, the table a call travels
+// batch_chunk.hpp and label_lists.hpp, whose list check and list search it keeps: the check of a call, the table a call travels
 // in, the value of a pixel, and what a thread does with one 16-byte unit of MAP memory (label_targets_read_unit) and with one 16-byte
 // unit of OUTPUT memory (label_targets_write_thread).  Compiled into the kernel (label_targets_kernels.hip), into
 // llcomp_mi_label_targets_reference (label_targets.cpp) and into the stand-alone host check, which both walk the kernel's own
@@ -11,11 +11,12 @@
 // builds the aligned 16-byte units of output memory that the segment covers from them.  A unit that the segment covers only in part
 // -- its other elements are the neighbouring segment's, plane's or sample's, or lie outside the output -- gets exactly its own
 // elements, element by element: compose_rule.hpp's unit rule.  No output byte is written twice, none outside the output is touched.
-// Mem: load16 of an aligned unit, load_el<MB> of a pixel.  Sink: store16 of an aligned unit, store_el<ES> of an element.
+// Mem: batch_chunk.hpp's (load16 of an aligned unit, load_el<MB> of a pixel; store16 of an aligned unit, store_el<ES> of an element).
 #pragma once
 #include <cstdint>
 
-#include "label_boxes16_rule.hpp"
+#include "batch_chunk.hpp"
+#include "label_lists.hpp"
 
 namespace llcomp_mi {
 
@@ -148,22 +149,15 @@ struct TargetLookup {
 
 // The unit at the aligned address u, which holds pixels of the segment whose map bytes are [lo, hi): the values of its pixels of the
 // segment into v, v[0] the segment's first pixel.  The unit is read whole where it lies inside the maps, pixel by pixel where it sticks
-// out.  (MB 2: lo and hi are even.)
+// out (chunk_read).  (MB 2: lo and hi are even.)
 template <uint32_t MB, class Mem, class Lookup, class V>
 LLMI_HD inline void label_targets_read_unit(const TargetGeom& g, uint64_t lo, uint64_t hi, uint64_t u, Mem& mem, Lookup& look, V& v) {
     constexpr uint32_t PER = 16 / MB;
     const uint32_t p0 = (u < lo ? uint32_t(lo - u) : 0u) / MB, p1 = (u + 16 > hi ? uint32_t(hi - u) : 16u) / MB;
     if (p0 >= p1) return;
-    LabelChunk c{{0u, 0u, 0u, 0u}};
-    if (u >= g.maps && u + 16 <= g.maps + g.map_bytes) {
-        c = mem.load16(u);
-    } else {
-        LLMI_LABEL_UNROLL
-        for (uint32_t p = 0; p < PER; ++p)
-            if (p >= p0 && p < p1) chunk_or<MB>(c.w, p, mem.template load_el<MB>(u + MB * p));
-    }
+    const BatchChunk c = chunk_read<MB>(g.maps, g.map_bytes, u, p0, p1, mem);
     const uint32_t at = u < lo ? 0u : uint32_t((u - lo) / MB);  // of pixel p0 in the segment
-    LLMI_LABEL_UNROLL
+    LLMI_UNROLL
     for (uint32_t p = 0; p < PER; ++p)  // (p is a constant in every turn: the unit's words are never indexed by a variable)
         if (p >= p0 && p < p1) v[at + p - p0] = look(chunk_get<MB>(c.w, p));
 }
@@ -198,12 +192,12 @@ LLMI_HD inline void label_targets_write_thread(uint64_t a0, uint64_t a1, uint32_
         const uint32_t e0 = u < a0 ? uint32_t(a0 - u) / ES : 0u, e1 = u + 16 > a1 ? uint32_t(a1 - u) / ES : PER;
         const uint32_t at = u < a0 ? 0u : uint32_t((u - a0) / ES);  // of element e0 in the segment
         if (e0 == 0 && e1 == PER) {
-            LabelChunk c{{0u, 0u, 0u, 0u}};
-            LLMI_LABEL_UNROLL
+            BatchChunk c{{0u, 0u, 0u, 0u}};
+            LLMI_UNROLL
             for (uint32_t e = 0; e < PER; ++e) target_unit_put<ES>(c.w, e, target_element<KIND, ES>(uint32_t(v[at + e]), k, a));
             sink.store16(u, c);
         } else {
-            LLMI_LABEL_UNROLL
+            LLMI_UNROLL
             for (uint32_t e = 0; e < PER; ++e)
                 if (e >= e0 && e < e1) sink.template store_el<ES>(u + ES * e, target_element<KIND, ES>(uint32_t(v[at + e - e0]), k, a));
         }

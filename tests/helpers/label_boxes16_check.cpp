@@ -1,12 +1,13 @@
-// label_boxes16_check.cpp -- the label boxes of listed ids (llcomp_amd/csrc/label_boxes16_rule.hpp) walked on the host under a sanitizer,
-// workgroup by workgroup and thread by thread as k_label_boxes16<K> does -- the table's listed samples, a workgroup per band, the list
-// and the records of the band in arrays of the capacity K the call would launch, label_boxes16_thread for each of the 256 threads, then
-// the merge of the records that have a pixel -- through a memory that checks every access: an address read lies in the maps, a
-// 16-byte access is aligned and inside the batch, a 2-byte one aligned; a record merged lies inside the call's records, a list slot
-// inside the capacity.  The result is compared with llcomp_mi_label_boxes16_reference and with a count pixel by pixel.  Host code only;
-// built and run by tests/test_label_boxes16_sanitizers.py:
+// label_boxes16_check.cpp -- the label boxes of both calls (llcomp_amd/csrc/label_boxes_rule.hpp, label_lists.hpp) walked on the host
+// under a sanitizer, workgroup by workgroup and thread by thread as k_label_boxes16<K> and k_label_boxes do -- for the listed call the
+// table's listed samples, a workgroup per band, the list and the records of the band in arrays of the capacity K the call would launch,
+// for the dense call 256 records per band; label_boxes_thread for each of the 256 threads, then the merge of the records that have a
+// pixel -- through a memory that checks every access: an address read lies in the maps, a 16-byte access is aligned and inside the
+// batch, a pixel's one aligned to the pixel; a record merged lies inside the call's records, a list slot inside the capacity.  The
+// result is compared with llcomp_mi_label_boxes16_reference or llcomp_mi_label_boxes_reference and with a count pixel by pixel.  Host
+// code only; built and run by tests/test_label_boxes16_sanitizers.py:
 //   g++ -std=c++17 -O1 -g -Wall -Wextra -Werror -fsanitize=address,undefined -fno-sanitize-recover=all -I llcomp_amd/csrc
-//       tests/helpers/label_boxes16_check.cpp llcomp_amd/csrc/label_boxes16.cpp
+//       tests/helpers/label_boxes16_check.cpp llcomp_amd/csrc/label_boxes.cpp
 // Prints "ok <rounds>".
 #include <algorithm>
 #include <cstdio>
@@ -16,7 +17,8 @@
 #include <vector>
 
 #include "../../include/llcomp_mi.h"
-#include "label_boxes16_rule.hpp"
+#include "label_boxes_rule.hpp"
+#include "label_lists.hpp"
 
 using namespace llcomp_mi;
 
@@ -36,6 +38,7 @@ namespace {
 
 struct HostMem {
     uint64_t maps, bytes;
+    uint32_t mb;  // the map's bytes per pixel
     bool bad = false;
     LabelChunk load16(uint64_t a) {
         LabelChunk c{{0, 0, 0, 0}};
@@ -46,14 +49,20 @@ struct HostMem {
     template <uint32_t N>
     uint32_t load_el(uint64_t a) {
         uint32_t v = 0;
-        if (N != 2 || (a & 1) || a < maps || a + 2 > maps + bytes) return bad = true, v;
-        std::memcpy(&v, reinterpret_cast<const void*>(uintptr_t(a)), 2);
+        if (N != mb || (a & (N - 1)) || a < maps || a + N > maps + bytes) return bad = true, v;
+        std::memcpy(&v, reinterpret_cast<const void*>(uintptr_t(a)), N);
         return v;
     }
 };
+// the dense call's finder: the id is the slot, of 256
+struct Identity {
+    uint32_t count;
+    uint32_t find(uint32_t id) const { return id; }
+};
 // the workgroup's arrays of K slots
+template <class Finder>
 struct WgSink {
-    LabelFinder<const uint16_t*> finder;
+    Finder finder;
     std::vector<llcomp_mi_label_box>& recs;
     bool bad = false;
     void run(uint32_t id, uint32_t x_first, uint32_t x_end, uint32_t y, uint32_t length) {
@@ -63,6 +72,56 @@ struct WgSink {
         label_box_update(recs[j], x_first, x_end, y, length);
     }
 };
+// One workgroup: band b of sample i with cnt records, which are out[0 .. cnt) of the call's
+template <uint32_t MB, class Finder>
+bool workgroup(const LabelGeom& g, uint32_t i, uint32_t b, const Finder& finder, uint32_t cnt, HostMem& mem, llcomp_mi_label_box* out) {
+    std::vector<llcomp_mi_label_box> recs(cnt, label_box_identity(g.ow, g.oh));
+    uint64_t sample, lo, hi;
+    label_band<MB>(g, i, b, sample, lo, hi);
+    for (uint32_t tid = 0; tid < kLabelThreads; ++tid) {
+        WgSink<Finder> sink{finder, recs};
+        label_boxes_thread<MB>(g, sample, lo, hi, tid, mem, sink);
+        if (sink.bad) return false;
+    }
+    for (uint32_t j = 0; j < cnt; ++j) {
+        if (!recs[j].count) continue;
+        llcomp_mi_label_box& o = out[j];
+        o.count += recs[j].count;
+        o.x0 = std::min(o.x0, recs[j].x0), o.y0 = std::min(o.y0, recs[j].y0), o.x1 = std::max(o.x1, recs[j].x1), o.y1 = std::max(o.y1, recs[j].y1);
+    }
+    return true;
+}
+
+// the dense call on n byte maps at byte offset `off`
+int run8(uint32_t n, uint32_t ow, uint32_t oh, uint32_t off, std::mt19937& rng) {
+    const size_t px = size_t(n) * ow * oh;
+    std::unique_ptr<uint8_t[]> buf(new uint8_t[off + px]);  // (operator new[] aligns to 16; the batch ends where the array ends)
+    CHECK(reinterpret_cast<uintptr_t>(buf.get()) % 16 == 0);
+    uint8_t* maps = buf.get() + off;
+    for (size_t i = 0; i < px;) {  // runs of drawn lengths
+        const uint8_t id = rng() % 4 ? uint8_t(rng() % 6) : uint8_t(rng());
+        for (uint32_t len = 1 + rng() % 12; len && i < px; --len) maps[i++] = id;
+    }
+    CHECK(label_boxes_check_call(n, ow, oh) == LLCOMP_MI_OK);
+    const uint32_t total = n * kLabelIds;
+    std::vector<llcomp_mi_label_box> ref(total + 1, llcomp_mi_label_box{9, 9, 9, 9, 9}), out(total);
+    CHECK(llcomp_mi_label_boxes_reference(maps, n, ow, oh, ref.data()) == LLCOMP_MI_OK && ref[total].count == 9);
+    for (uint32_t r = 0; r < total; ++r) out[r] = label_box_identity(ow, oh);  // k_label_boxes_init
+    const LabelGeom g = label_geom<1>(reinterpret_cast<uintptr_t>(maps), n, ow, oh);
+    CHECK(g.bytes == px);
+    HostMem mem{g.maps, g.bytes, 1};
+    for (uint32_t i = 0; i < n; ++i)
+        for (uint32_t b = 0; b < g.bands; ++b) CHECK(workgroup<1>(g, i, b, Identity{kLabelIds}, kLabelIds, mem, out.data() + size_t(i) * kLabelIds));
+    CHECK(!mem.bad);
+    CHECK(std::memcmp(out.data(), ref.data(), total * sizeof(llcomp_mi_label_box)) == 0);
+    // ... and pixel by pixel
+    std::vector<llcomp_mi_label_box> w(total, label_box_identity(ow, oh));
+    for (uint32_t i = 0; i < n; ++i)
+        for (uint32_t y = 0; y < oh; ++y)
+            for (uint32_t x = 0; x < ow; ++x) label_box_update(w[size_t(i) * kLabelIds + maps[(size_t(i) * oh + y) * ow + x]], x, x + 1, y, 1);
+    CHECK(std::memcmp(w.data(), out.data(), total * sizeof(llcomp_mi_label_box)) == 0);
+    return 0;
+}
 
 int run(uint32_t n, uint32_t ow, uint32_t oh, uint32_t off, const std::vector<std::vector<uint16_t>>& lists, const std::vector<uint16_t>& pool,
         std::mt19937& rng) {
@@ -96,28 +155,15 @@ int run(uint32_t n, uint32_t ow, uint32_t oh, uint32_t off, const std::vector<st
     if (total) std::memcpy(tids.data(), table.get() + t.ids_at, 2 * total);
 
     for (uint32_t r = 0; r < total; ++r) out[r] = label_box_identity(ow, oh);  // k_label_boxes16_init
-    const LabelGeom16 g = label_geom16(reinterpret_cast<uintptr_t>(maps), n, ow, oh);
-    HostMem mem{g.maps, g.bytes};
+    const LabelGeom g = label_geom<2>(reinterpret_cast<uintptr_t>(maps), n, ow, oh);
+    HostMem mem{g.maps, g.bytes, 2};
     for (uint32_t z = 0; z < n_listed; ++z)
         for (uint32_t b = 0; b < g.bands; ++b) {  // one workgroup
             CHECK(tsamples[z] < n && (!z || tsamples[z - 1] < tsamples[z]));
             const uint32_t i = tsamples[z], at = tfirst[i], cnt = tfirst[i + 1] - at;
             CHECK(cnt && cnt <= K && at + cnt <= total);
             std::vector<uint16_t> list(tids.begin() + at, tids.begin() + at + cnt);
-            std::vector<llcomp_mi_label_box> recs(cnt, label_box_identity(ow, oh));
-            uint64_t sample, lo, hi;
-            label_band16(g, i, b, sample, lo, hi);
-            for (uint32_t tid = 0; tid < kLabel16Threads; ++tid) {
-                WgSink sink{{list.data(), cnt}, recs};
-                label_boxes16_thread(g, sample, lo, hi, tid, mem, sink);
-                CHECK(!sink.bad);
-            }
-            for (uint32_t j = 0; j < cnt; ++j) {
-                if (!recs[j].count) continue;
-                llcomp_mi_label_box& o = out[at + j];
-                o.count += recs[j].count;
-                o.x0 = std::min(o.x0, recs[j].x0), o.y0 = std::min(o.y0, recs[j].y0), o.x1 = std::max(o.x1, recs[j].x1), o.y1 = std::max(o.y1, recs[j].y1);
-            }
+            CHECK(workgroup<2>(g, i, b, LabelFinder<const uint16_t*>{list.data(), cnt}, cnt, mem, out.data() + at));
         }
     CHECK(!mem.bad);
     CHECK(!total || std::memcmp(out.data(), ref.data(), total * sizeof(llcomp_mi_label_box)) == 0);
@@ -200,6 +246,11 @@ int main() {
             if (run(2, 45, B + 3, off, {l, half}, pool, rng)) return 1;
             ++rounds;
         }
+    // the dense call: the same widths by the same heights, the byte maps at every byte offset
+    for (uint32_t ow : ows)
+        for (uint32_t oh : ohs)
+            for (uint32_t off = 0; off < 16; ++off, ++rounds)
+                if (run8(3, ow, oh, off, rng)) return 1;
     if (check_refusals()) return 1;
     std::printf("ok %u\n", rounds);
     return 0;
