@@ -791,8 +791,8 @@ uint32_t llcomp_mi_paste_max_pieces_per_sample(void);
  * and for a 2-byte dtype with c == 1, the id maps are their own source -- that is how a 16-bit class or instance map is pasted by id.
  * BAD_ARGS: the cases of "Batch copy-paste" (but for its value), an id_base above 65535, a value_bits that is not 0 without VALUE or
  * that has bits above the element.
- * NOT covered: ids of 3 or 4 bytes (COCO panoptic's RGB ids), maps at odd addresses, blended borders, and what "Batch copy-paste" does
- * not cover. */
+ * Ids of 3 or 4 bytes (COCO panoptic's RGB ids): "Wide id maps" below.  NOT covered: maps at odd addresses, blended borders, and what
+ * "Batch copy-paste" does not cover. */
 typedef struct llcomp_mi_paste_piece16 {
     uint32_t dst, src;
     uint32_t dx, dy, sx, sy, w, h;
@@ -835,7 +835,7 @@ uint32_t llcomp_mi_label_boxes_rows(void);
  * counted nowhere; a sample with an empty list costs nothing.
  * BAD_ARGS: the cases of "Label boxes", a NULL ids or first, first[0] != 0, a first that decreases, a list of more than 4096 ids, more
  * than 2^20 ids in all, a list that is not strictly ascending, maps not aligned to 2 bytes.
- * NOT covered: ids of 3 or 4 bytes (COCO panoptic's RGB ids), maps at odd addresses. */
+ * Ids of 3 or 4 bytes (COCO panoptic's RGB ids): "Wide id maps" below.  NOT covered: maps at odd addresses. */
 int llcomp_mi_label_boxes16_reference(const void* maps, uint32_t n, uint32_t ow, uint32_t oh, const uint16_t* ids, const uint32_t* first,
                                       llcomp_mi_label_box* out);
 /* The most ids a sample lists: 22 bytes of a workgroup's LDS per listed id, one workgroup to a CU at the top capacity.  A constant. */
@@ -861,7 +861,8 @@ uint32_t llcomp_mi_label_boxes16_max_ids(void);
  * a map_bytes that is not 1 or 2, a kind or dtype that is none; an id above 255 with map_bytes 1; with INDEX U8 a value or default
  * outside 0..255; plane_first[0] != 0, a plane_first that decreases, more than 4096 planes of a sample; on_bits or off_bits with bits
  * above the element; an output of 2^62 bytes or more.
- * NOT covered: HWC one-hot ([n][oh][ow][K]), in-place conversion, ids of 3 or 4 bytes, 16-bit maps at odd addresses, a table kept on
+ * Ids of 3 or 4 bytes: llcomp_mi_label_targets32, "Wide id maps" below (map_bytes 3 or 4 stays BAD_ARGS here).
+ * NOT covered: HWC one-hot ([n][oh][ow][K]), in-place conversion, 16-bit maps at odd addresses, a table kept on
  * the device across calls, targets as a job of the streaming pipeline, soft or blended mask borders, boxes or labels from the lists. */
 enum { LLCOMP_MI_TARGET_INDEX = 0, LLCOMP_MI_TARGET_PLANES = 1 };
 enum { LLCOMP_MI_TARGET_U8 = 0, LLCOMP_MI_TARGET_I32 = 1, LLCOMP_MI_TARGET_I64 = 2 };   /* INDEX dtypes */
@@ -883,6 +884,56 @@ uint64_t llcomp_mi_label_targets_out_bytes(uint32_t n, uint32_t ow, uint32_t oh,
  * most planes of a sample: constants */
 uint32_t llcomp_mi_label_targets_segment(void);
 uint32_t llcomp_mi_label_targets_max_planes(void);
+/* Wide id maps (llcomp_mi_codec_paste_batch32, llcomp_mi_codec_label_boxes32 and llcomp_mi_codec_label_targets32 below): "Batch
+ * copy-paste by 16-bit ids", "Label boxes of listed ids" and "Label targets" for id maps of 3 or 4 bytes per pixel -- COCO panoptic's id = R + 256 * G + 65536 * B, and the int32 maps of class * 1000 +
+ * instance sets whose ids pass 65535.  maps is n samples of oh x ow pixels, dense, of map_bytes little-endian bytes each:
+ *   map_bytes 3: at ANY byte address, the id is b0 | b1 << 8 | b2 << 16 -- what a panoptic PNG stored as a three-channel container
+ *                decodes to with the nearest filter in U8 HWC
+ *   map_bytes 4: aligned to 4 bytes and to nothing more -- a four-channel container, or an int32 tensor
+ * The map is never written, and no byte outside it is read.  The listed ids are uint32_t, every value of the map's width among them
+ * (0, 0xFFFFFF, 0xFFFFFFFF); the lists' limits, the records, the values, the kinds and the output dtypes are those of the 16-bit calls.
+ * BAD_ARGS: the 16-bit calls' cases; a map_bytes that is not 3 or 4; a listed id above 0xFFFFFF with map_bytes 3; a 4-byte map at an
+ * address that is no multiple of 4.
+ * NOT covered: 4-byte maps at addresses that are no multiples of 4, batches of 2^32 bytes and more (the arithmetic is 64-bit, the
+ * sizes are not tested yet), and what the 16-bit calls do not cover.
+ * Batch copy-paste by wide ids (llcomp_mi_codec_paste_batch32 below) is "Batch copy-paste by 16-bit ids" word for word -- painter's
+ * order, the last piece that selects a pixel gives it, what no piece selects stays and is not written, a dst element is written at
+ * most once, 256 pieces per dst sample -- with mask the wide map above, map_bytes 3 or 4.  id_base is any 32-bit value (above 0xFFFFFF
+ * with map_bytes 3: BAD_ARGS); a window that passes the top id selects nothing there, and a piece with no other bit set is checked and
+ * ignored.  RGB ids are sparse, so a window is mostly ONE id per piece; the limit of 256 pieces still holds a COCO image's segments.
+ * The maps may be their own source: map_bytes 3 as U8 HWC with c == 3; map_bytes 4 as U8 HWC with c == 4 or F32 with c == 1.
+ * LLCOMP_MI_PASTE_VALUE_PIXEL (this call only; with VALUE; U8 HWC with c <= 4): channel ch of a selected pixel takes byte ch of
+ * value_bits, whose bytes at and above c are 0 -- how a pasted segment gets a new 3-byte id in a dst map, the renumbering call of a
+ * Copy-Paste.  BAD_ARGS: the 16-bit call's cases, a map_bytes that is not 3 or 4, VALUE_PIXEL without VALUE or on another dtype,
+ * layout or c, value bytes at or above c, a 4-byte mask at an address that is no multiple of 4. */
+#define LLCOMP_MI_PASTE_VALUE_PIXEL 2u
+typedef struct llcomp_mi_paste_piece32 {
+    uint32_t dst, src;
+    uint32_t dx, dy, sx, sy, w, h;
+    uint32_t flags;        /* bit 0 LLCOMP_MI_PASTE_VALUE, bit 1 LLCOMP_MI_PASTE_VALUE_PIXEL */
+    uint32_t value_bits;
+    uint32_t id_base;      /* any 32-bit value; map_bytes 3: at most 0xFFFFFF */
+    uint32_t ids[8];       /* bit j set: id id_base + j is selected */
+} llcomp_mi_paste_piece32; /* 76 bytes, the layout of llcomp_mi_paste_piece16 */
+int llcomp_mi_paste32_reference(const void* src, const void* mask, uint32_t map_bytes, uint32_t n_src, uint32_t iw, uint32_t ih, const void* dst_in,
+                                uint32_t n_dst, uint32_t ow, uint32_t oh, uint32_t c, uint32_t dtype, uint32_t layout,
+                                const llcomp_mi_paste_piece32* pieces, uint32_t n_pieces, void* out);
+int llcomp_mi_paste32_plan(uint32_t map_bytes, uint32_t n_src, uint32_t iw, uint32_t ih, uint32_t n_dst, uint32_t ow, uint32_t oh, uint32_t c,
+                           uint32_t dtype, uint32_t layout, const llcomp_mi_paste_piece32* pieces, uint32_t n_pieces, uint32_t* samples,
+                           uint32_t* first, uint32_t* order, uint32_t* n_samples, uint64_t* n_workgroups);
+int llcomp_mi_label_boxes32_reference(const void* maps, uint32_t map_bytes, uint32_t n, uint32_t ow, uint32_t oh, const uint32_t* ids,
+                                      const uint32_t* first, llcomp_mi_label_box* out);
+typedef struct llcomp_mi_label_targets32 {
+    uint32_t struct_size, map_bytes, kind, dtype;   /* map_bytes 3 or 4; the rest as llcomp_mi_label_targets */
+    int32_t default_value;
+    uint32_t on_bits, off_bits;
+    const uint32_t* ids;
+    const int32_t* values;
+    const uint32_t* first;
+    const uint32_t* plane_first;
+} llcomp_mi_label_targets32;                        /* 64 bytes, ids at 32 */
+int llcomp_mi_label_targets32_reference(const void* maps, uint32_t n, uint32_t ow, uint32_t oh, const llcomp_mi_label_targets32* targets, void* out);
+uint64_t llcomp_mi_label_targets32_out_bytes(uint32_t n, uint32_t ow, uint32_t oh, const llcomp_mi_label_targets32* targets);
 uint32_t llcomp_mi_slice_count(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar);
 /* Slice width for one-row slices (tile_h = 1) when `frames` frames are coded per call: the widest slice (64..480 pixels) that
  * still keeps about four wavefronts per SIMD busy.  A call that codes few frames is latency-bound with wide slices; this
@@ -1324,6 +1375,27 @@ int llcomp_mi_codec_label_targets(llcomp_mi_codec* codec, const void* d_maps, ui
 /* The bound on llcomp_mi_codec_allocated_bytes with such calls of up to n samples and total_ids listed ids among the codec's calls:
  * llcomp_mi_codec_workspace_bytes + 4 * (3 * n + 2) + 6 * total_ids, the table of a call.  0 for a NULL codec. */
 uint64_t llcomp_mi_codec_label_targets_workspace_bytes(const llcomp_mi_codec* codec, uint32_t n, uint32_t total_ids);
+/* Wide id maps (the rule: "Wide id maps" above): llcomp_mi_codec_label_boxes16 and llcomp_mi_codec_label_targets for maps of 3 or 4
+ * bytes per pixel, with the same kernels' bands, segments, capacities and merges.  A listed id takes 24 bytes of a workgroup's LDS for
+ * the boxes (96 KiB at 4096 ids: still one workgroup to a CU) and 8 for the targets.  A thread takes the aligned 16-byte units of map
+ * memory as before; a 3-byte pixel belongs to the unit that holds its first byte, and the thread reads the last bytes of a pixel that
+ * straddles, at most two, from the next unit -- five or six pixels to a unit.  The tables travel in the 16-bit calls' buffers.
+ * BAD_ARGS, nothing queued and nothing written: the 16-bit calls' cases and the references'. */
+/* ... and llcomp_mi_codec_paste_batch16 for them: k_paste<3|4, ES> on the composition's tiles and units; a unit's npx mask pixels are
+ * map_bytes * npx bytes, one to four (3) or one to five (4) aligned mask units; the table travels in the 16-bit call's buffer, and the
+ * bound is llcomp_mi_codec_paste16_workspace_bytes's. */
+int llcomp_mi_codec_paste_batch32(llcomp_mi_codec* codec, const void* d_src, const void* d_mask, uint32_t map_bytes, uint32_t n_src, uint32_t iw,
+                                  uint32_t ih, void* d_dst, uint32_t n_dst, uint32_t ow, uint32_t oh, uint32_t dtype, uint32_t layout,
+                                  const llcomp_mi_paste_piece32* pieces, uint32_t n_pieces, void* stream);
+uint64_t llcomp_mi_codec_paste32_workspace_bytes(const llcomp_mi_codec* codec, uint32_t n_dst, uint32_t n_pieces);
+int llcomp_mi_codec_label_boxes32(llcomp_mi_codec* codec, const void* d_maps, uint32_t map_bytes, uint32_t n, uint32_t ow, uint32_t oh,
+                                  const uint32_t* ids, const uint32_t* first, void* d_boxes, void* stream);
+/* llcomp_mi_codec_workspace_bytes + 4 * (2 * n + 1) + 4 * total_ids, the table of a call.  0 for a NULL codec. */
+uint64_t llcomp_mi_codec_label_boxes32_workspace_bytes(const llcomp_mi_codec* codec, uint32_t n, uint32_t total_ids);
+int llcomp_mi_codec_label_targets32(llcomp_mi_codec* codec, const void* d_maps, uint32_t n, uint32_t ow, uint32_t oh,
+                                    const llcomp_mi_label_targets32* targets, void* d_out, void* stream);
+/* llcomp_mi_codec_workspace_bytes + 4 * (3 * n + 2) + 8 * total_ids, the table of a call.  0 for a NULL codec. */
+uint64_t llcomp_mi_codec_label_targets32_workspace_bytes(const llcomp_mi_codec* codec, uint32_t n, uint32_t total_ids);
 /* Stage-A only (context + prediction model), for tests and profiling: d_sym u32[frames*h*w*c],
  * low 16 bits = folded context (0..7925), high 16 bits = folded residual (two's complement). */
 int llcomp_mi_codec_model(llcomp_mi_codec* codec, const void* d_px, void* d_sym, void* stream);

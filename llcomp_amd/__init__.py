@@ -45,6 +45,10 @@ with ctypes and keeps the reference's names and error behaviour:
         ids of every id map of a batch: torchvision's masks_to_boxes)
     label_boxes16_reference / label_boxes16_max_ids / Codec.label_boxes16 / Codec.label_boxes16_workspace_bytes  (the same for the ids
         the caller lists per sample, in 16-bit id maps: Cityscapes, Mapillary Vistas, ADE20K instance ids)
+    PastePiece32 / PASTE_VALUE_PIXEL / paste_pieces32 / paste32_plan / paste32_reference / Codec.paste_batch32 /
+        Codec.paste32_workspace_bytes  (the copy-paste selected by id maps of 3 or 4 bytes per pixel; VALUE_PIXEL writes a 3-byte id)
+    label_boxes32_reference / label_targets32_reference / Codec.label_boxes32 / Codec.label_targets32 / their _workspace_bytes  (both
+        for id maps of 3 or 4 bytes per pixel: COCO panoptic's RGB ids, int32 class * 1000 + instance maps)
     TARGET_* / label_targets_reference / label_targets_segment / label_targets_max_planes / Codec.label_targets /
         Codec.label_targets_workspace_bytes  (what a loss takes from the id maps: lut[map] as a class-index tensor, one-hot planes with
         label smoothing, one binary mask per listed instance)
@@ -68,7 +72,7 @@ from ._lib import PerspectiveView as _PerspectiveView, PerspectiveGroup as _Pers
 from ._lib import PhotoOp as _PhotoOp, PhotoChain as _PhotoChain, PhotoGroup as _PhotoGroup
 from ._lib import ComposePiece as _ComposePiece
 from ._lib import PastePiece as _PastePiece
-from ._lib import PastePiece16
+from ._lib import PastePiece16, PastePiece32
 from ._lib import MixSample as _MixSample
 
 EXT = ".llcomp"
@@ -946,6 +950,101 @@ def paste_pieces16(records):
     return arr
 
 
+PASTE_VALUE_PIXEL = 2
+
+
+def paste_pieces32(records, map_bytes):
+    """The pieces of a paste_batch32 call (llcomp_mi_paste_piece32) as a ctypes array, as paste_pieces16: every record a tuple (dst,
+    src, dx, dy, sx, sy, w, h, ids[, value_bits[, pixel]]), ids an iterable of ints up to 0xFFFFFF (map_bytes 3) or 0xFFFFFFFF (4); one
+    piece per window of 256 ids that holds one of its ids -- RGB ids are sparse, so mostly one piece per id.  pixel=True with
+    value_bits makes VALUE_PIXEL pieces (uint8 "hwc", c <= 4): channel ch of a selected pixel takes byte ch of value_bits, which is how
+    a pasted segment gets a new 3-byte id in a dst map.  "nonzero" is not offered: a binary mask is no list of windows."""
+    if isinstance(records, C.Array) and records._type_ is PastePiece32:
+        return records
+    if int(map_bytes) not in (3, 4):
+        raise LlcompError(BAD_ARGS, f"map_bytes of a wide id map is 3 or 4, got {map_bytes!r}")
+    top = (1 << (8 * int(map_bytes))) - 1
+    out = []
+    for r in list(records):
+        vals = list(r) if isinstance(r, (tuple, list)) else []
+        if len(vals) not in (9, 10, 11):
+            raise LlcompError(BAD_ARGS, f"a piece is (dst, src, dx, dy, sx, sy, w, h, ids[, value_bits[, pixel]]), got {r!r}")
+        nums = [int(v) for v in vals[:8]]
+        if min(nums) < 0 or max(nums) > 0xFFFFFFFF:
+            raise LlcompError(BAD_ARGS, f"a piece takes unsigned values, got {r!r}")
+        if isinstance(vals[8], str):
+            raise LlcompError(BAD_ARGS, f"ids are ints 0..{top}, got {vals[8]!r}")
+        ids = np.unique(np.asarray(list(vals[8]), np.int64).reshape(-1))
+        if ids.size and (ids[0] < 0 or ids[-1] > top):
+            raise LlcompError(BAD_ARGS, f"an id is 0..{top}, got {int(ids[0] if ids[0] < 0 else ids[-1])}")
+        value = None
+        if len(vals) >= 10 and vals[9] is not None:
+            value = int(vals[9])
+            if not 0 <= value <= 0xFFFFFFFF:
+                raise LlcompError(BAD_ARGS, f"value_bits are the element's bits, got {vals[9]!r}")
+        pixel = len(vals) == 11 and bool(vals[10])
+        if pixel and value is None:
+            raise LlcompError(BAD_ARGS, "pixel=True needs value_bits")
+        at = 0
+        while True:
+            p = PastePiece32()
+            for name, v in zip(("dst", "src", "dx", "dy", "sx", "sy", "w", "h"), nums):
+                setattr(p, name, v)
+            if value is not None:
+                p.flags, p.value_bits = PASTE_VALUE | (PASTE_VALUE_PIXEL if pixel else 0), value
+            if ids.size:
+                p.id_base = int(ids[at])
+                end = int(np.searchsorted(ids, p.id_base + 256))
+                for m in ids[at:end]:
+                    d = int(m) - p.id_base
+                    p.ids[d >> 5] |= 1 << (d & 31)
+                at = end
+            out.append(p)
+            if at >= ids.size:
+                break
+    arr = (PastePiece32 * len(out))()
+    for i, p in enumerate(out):
+        arr[i] = p
+    return arr
+
+
+def paste32_plan(map_bytes, n_src, iw, ih, n_dst, ow, oh, c, pieces, dtype="float32", layout="chw"):
+    """What a paste_batch32 call does (llcomp_mi_paste32_plan, host only) -> (samples, first, order, n_workgroups), as paste16_plan."""
+    recs = paste_pieces32(pieces, map_bytes)
+    n_dst = int(n_dst)
+    samples, first, order = np.zeros(max(n_dst, 1), np.uint32), np.zeros(max(n_dst, 1) + 1, np.uint32), np.zeros(max(len(recs), 1), np.uint32)
+    ns, nw = C.c_uint32(0), C.c_uint64(0)
+    u32p = C.POINTER(C.c_uint32)
+    _check(_lib.load().llcomp_mi_paste32_plan(int(map_bytes), int(n_src), int(iw), int(ih), n_dst, int(ow), int(oh), int(c), _dtype_code(dtype),
+                                              _layout_code(layout), recs, len(recs), samples.ctypes.data_as(u32p), first.ctypes.data_as(u32p),
+                                              order.ctypes.data_as(u32p), C.byref(ns), C.byref(nw)))
+    n = ns.value
+    return samples[:n].copy(), first[:n + 1].copy(), order[:int(first[n])].copy(), int(nw.value)
+
+
+def paste32_reference(src, mask, dst, pieces, layout="chw", dtype=None):
+    """The rule of the batch copy-paste by wide ids on host arrays (llcomp_mi_paste32_reference): src and dst as paste_reference's, mask
+    [n_src, ih, iw, 3] uint8 or [n_src, ih, iw] uint32 -- or src itself where src IS the id maps: uint8 "hwc" with c = 3 (map_bytes 3)
+    or c = 4, or float32 with c = 1 (map_bytes 4) -> the pasted dst batch, a new array."""
+    d, code, lay, n_dst, c, oh, ow = _batch_array(dst, dtype, layout)
+    s = np.ascontiguousarray(src)
+    if s.ndim != 4 or s.dtype != d.dtype or (s.shape[1] if lay == LAYOUT_CHW else s.shape[3]) != c:
+        raise LlcompError(BAD_ARGS, f"src is a 4-D batch of dst's type and channels, got {s.dtype} of shape {s.shape}")
+    n_src = s.shape[0]
+    ih, iw = s.shape[2:] if lay == LAYOUT_CHW else s.shape[1:3]
+    if mask is src:
+        m, mb = s, s.nbytes // max(n_src * ih * iw, 1)
+    else:
+        m, mb = _wide_maps(mask)[:2]
+    if mb not in (3, 4) or m.nbytes != mb * n_src * ih * iw:
+        raise LlcompError(BAD_ARGS, f"mask is uint8 [n_src, ih, iw, 3] or uint32 [n_src, ih, iw], got {m.dtype} of shape {m.shape}")
+    recs = paste_pieces32(pieces, mb)
+    out = np.empty_like(d)
+    _check(_lib.load().llcomp_mi_paste32_reference(s.ctypes.data, m.ctypes.data, mb, n_src, iw, ih, d.ctypes.data, n_dst, ow, oh, c, code, lay, recs,
+                                                   len(recs), out.ctypes.data))
+    return out
+
+
 def paste16_plan(n_src, iw, ih, n_dst, ow, oh, c, pieces, dtype="float32", layout="chw"):
     """What a paste_batch16 call does (llcomp_mi_paste16_plan, host only) -> (samples, first, order, n_workgroups), as paste_plan; order
     indexes the pieces of paste_pieces16(pieces), one per window."""
@@ -1007,17 +1106,18 @@ def label_boxes16_max_ids():
     return int(_lib.load().llcomp_mi_label_boxes16_max_ids())
 
 
-def _label_lists(ids, n):
-    """per-sample sequences of ids -> (ids uint16 [total], first uint32 [n + 1]); the library checks the order and the lengths"""
+def _label_lists(ids, n, id_type=np.uint16):
+    """per-sample sequences of ids -> (ids of id_type [total], first uint32 [n + 1]); the library checks the order and the lengths"""
     lists = [np.asarray(list(l), np.int64).reshape(-1) for l in ids]
     if len(lists) != n:
         raise LlcompError(BAD_ARGS, f"ids holds one sequence per sample, got {len(lists)} for {n} samples")
-    if any(l.size and (l.min() < 0 or l.max() > 0xFFFF) for l in lists):
-        raise LlcompError(BAD_ARGS, "an id is 0..65535")
+    top = int(np.iinfo(id_type).max)
+    if any(l.size and (l.min() < 0 or l.max() > top) for l in lists):
+        raise LlcompError(BAD_ARGS, f"an id is 0..{top}")
     first = np.zeros(n + 1, np.uint32)
     first[1:] = np.cumsum([l.size for l in lists])
-    flat = np.concatenate(lists + [np.zeros(0, np.int64)]).astype(np.uint16)
-    return np.ascontiguousarray(np.append(flat, np.uint16(0))), first  # (a pointer that is never NULL)
+    flat = np.concatenate(lists + [np.zeros(0, np.int64)]).astype(id_type)
+    return np.ascontiguousarray(np.append(flat, id_type(0))), first  # (a pointer that is never NULL)
 
 
 def label_boxes16_reference(maps, ids):
@@ -1071,7 +1171,8 @@ def _label_targets(ids, values, n, map_bytes, kind, dtype, default, planes, on, 
         kind = TARGET_KINDS.index(kind.lower())
     if kind not in (TARGET_INDEX, TARGET_PLANES):
         raise LlcompError(BAD_ARGS, f"kind must be one of {TARGET_KINDS}, got {kind!r}")
-    flat, first = _label_lists(ids, n)
+    wide = int(map_bytes) > 2  # (the wide id maps: uint32 ids, llcomp_mi_label_targets32)
+    flat, first = _label_lists(ids, n, np.uint32 if wide else np.uint16)
     vals = [np.asarray(list(l), np.int64).reshape(-1) for l in values]
     if [v.size for v in vals] != np.diff(first.astype(np.int64)).tolist():
         raise LlcompError(BAD_ARGS, "values holds one value per listed id")
@@ -1079,7 +1180,8 @@ def _label_targets(ids, values, n, map_bytes, kind, dtype, default, planes, on, 
     if flat_v.min() < -0x80000000 or flat_v.max() > 0x7FFFFFFF or not -0x80000000 <= int(default) <= 0x7FFFFFFF:
         raise LlcompError(BAD_ARGS, "a value is an int32")
     flat_v = np.ascontiguousarray(flat_v.astype(np.int32))
-    t = _lib.LabelTargets(C.sizeof(_lib.LabelTargets), int(map_bytes), kind, 0, int(default), 0, 0, flat.ctypes.data, flat_v.ctypes.data, first.ctypes.data, None)
+    struct = _lib.LabelTargets32 if wide else _lib.LabelTargets
+    t = struct(C.sizeof(struct), int(map_bytes), kind, 0, int(default), 0, 0, flat.ctypes.data, flat_v.ctypes.data, first.ctypes.data, None)
     keep = [flat, flat_v, first]
     if kind == TARGET_INDEX:
         name = "int64" if dtype is None else str(dtype).replace("torch.", "")
@@ -1116,6 +1218,38 @@ def label_targets_reference(maps, ids, values, kind="index", dtype=None, default
     shape = (n, oh, ow) if counts is None else (n, counts[0], oh, ow) if isinstance(planes, (int, np.integer)) else (sum(counts), oh, ow)
     out = np.zeros(int(np.prod(shape)) + 1, np_type)
     _check(_lib.load().llcomp_mi_label_targets_reference(a.ctypes.data if a.size else None, n, ow, oh, C.byref(t), out.ctypes.data))
+    return out[:-1].reshape(shape)
+
+
+def _wide_maps(maps):
+    """host id maps of 3 or 4 bytes per pixel (include/llcomp_mi.h "Wide id maps") -> (the array, map_bytes, n, oh, ow):
+    [n, oh, ow, 3] uint8, the id b0 | b1 << 8 | b2 << 16, or [n, oh, ow] uint32"""
+    a = np.ascontiguousarray(maps)
+    if a.ndim == 4 and a.shape[3] == 3 and a.dtype == np.uint8:
+        return a, 3, a.shape[0], a.shape[1], a.shape[2]
+    if a.ndim == 3 and a.dtype == np.uint32:
+        return a, 4, a.shape[0], a.shape[1], a.shape[2]
+    raise LlcompError(BAD_ARGS, f"wide id maps are uint8 [n, oh, ow, 3] or uint32 [n, oh, ow], got {a.dtype} of shape {a.shape}")
+
+
+def label_boxes32_reference(maps, ids):
+    """label_boxes16_reference for id maps of 3 or 4 bytes per pixel (llcomp_mi_label_boxes32_reference): maps [n, oh, ow, 3] uint8 or
+    [n, oh, ow] uint32, ids a sequence of n strictly ascending sequences of ids up to 0xFFFFFF or 0xFFFFFFFF."""
+    a, mb, n, oh, ow = _wide_maps(maps)
+    flat, first = _label_lists(ids, n, np.uint32)
+    out = np.zeros(max(int(first[n]), 1), LABEL_BOX_DTYPE)
+    _check(_lib.load().llcomp_mi_label_boxes32_reference(a.ctypes.data if a.size else None, mb, n, ow, oh, flat.ctypes.data, first.ctypes.data, out.ctypes.data))
+    return out[:int(first[n])]
+
+
+def label_targets32_reference(maps, ids, values, kind="index", dtype=None, default=0, planes=None, on=None, off=None):
+    """label_targets_reference for id maps of 3 or 4 bytes per pixel (llcomp_mi_label_targets32_reference): maps [n, oh, ow, 3] uint8
+    or [n, oh, ow] uint32; everything else as there."""
+    a, mb, n, oh, ow = _wide_maps(maps)
+    t, keep, np_type, counts = _label_targets(ids, values, n, mb, kind, dtype, default, planes, on, off)
+    shape = (n, oh, ow) if counts is None else (n, counts[0], oh, ow) if isinstance(planes, (int, np.integer)) else (sum(counts), oh, ow)
+    out = np.zeros(int(np.prod(shape)) + 1, np_type)
+    _check(_lib.load().llcomp_mi_label_targets32_reference(a.ctypes.data if a.size else None, n, ow, oh, C.byref(t), out.ctypes.data))
     return out[:-1].reshape(shape)
 
 
@@ -2148,6 +2282,19 @@ class Codec:
         _check(self._L.llcomp_mi_codec_paste_batch16(self._h, d_src, d_mask, int(n_src), int(iw), int(ih), d_dst, int(n_dst), int(ow), int(oh),
                                                      _dtype_code(dtype), _layout_code(layout), recs, len(recs), stream))
 
+    def paste_batch32(self, d_src, d_mask, map_bytes, n_src, iw, ih, d_dst, n_dst, ow, oh, pieces, dtype="float32", layout="chw", stream=0):
+        """paste_batch selected by id maps of map_bytes 3 (any address) or 4 (aligned to 4 bytes) per pixel
+        (llcomp_mi_codec_paste_batch32): d_mask may be d_src for uint8 "hwc" with c = map_bytes, or float32 with c = 1 for map_bytes 4;
+        pieces from paste_pieces32(), or records for it.  What no piece selects stays and is not written.  Asynchronous on `stream`."""
+        recs = paste_pieces32(pieces, map_bytes)
+        _check(self._L.llcomp_mi_codec_paste_batch32(self._h, d_src, d_mask, int(map_bytes), int(n_src), int(iw), int(ih), d_dst, int(n_dst), int(ow),
+                                                     int(oh), _dtype_code(dtype), _layout_code(layout), recs, len(recs), stream))
+
+    def paste32_workspace_bytes(self, n_dst, n_pieces):
+        """the bound on .allocated_bytes() with paste_batch32 calls of up to n_dst dst samples and n_pieces pieces
+        (llcomp_mi_codec_paste32_workspace_bytes)"""
+        return self._L.llcomp_mi_codec_paste32_workspace_bytes(self._h, int(n_dst), int(n_pieces))
+
     def paste16_workspace_bytes(self, n_dst, n_pieces):
         """the bound on .allocated_bytes() with paste_batch16 calls of up to n_dst dst samples and n_pieces pieces
         (llcomp_mi_codec_paste16_workspace_bytes)"""
@@ -2184,6 +2331,31 @@ class Codec:
             raise LlcompError(BAD_ARGS, f"map_dtype must be uint8 or uint16, got {map_dtype!r}")
         t, keep, _, _ = _label_targets(ids, values, int(n), 1 if name == "uint8" else 2, kind, dtype, default, planes, on, off)
         _check(self._L.llcomp_mi_codec_label_targets(self._h, d_maps, int(n), int(ow), int(oh), C.byref(t), d_out, stream))
+
+    def label_boxes32(self, d_maps, map_bytes, n, ow, oh, ids, d_boxes, stream=0):
+        """label_boxes16 for id maps of map_bytes 3 (any address) or 4 (aligned to 4 bytes) per pixel (llcomp_mi_codec_label_boxes32):
+        ids a sequence of n strictly ascending sequences of ids up to 0xFFFFFF or 0xFFFFFFFF -> d_boxes, one record of LABEL_BOX_DTYPE
+        per listed id in the lists' order.  Asynchronous on `stream`; the maps are only read."""
+        flat, first = _label_lists(ids, int(n), np.uint32)
+        _check(self._L.llcomp_mi_codec_label_boxes32(self._h, d_maps, int(map_bytes), int(n), int(ow), int(oh), flat.ctypes.data, first.ctypes.data, d_boxes, stream))
+
+    def label_boxes32_workspace_bytes(self, n, total_ids):
+        """the bound on .allocated_bytes() with label_boxes32 calls of up to n samples and total_ids listed ids
+        (llcomp_mi_codec_label_boxes32_workspace_bytes)"""
+        return self._L.llcomp_mi_codec_label_boxes32_workspace_bytes(self._h, int(n), int(total_ids))
+
+    def label_targets32(self, d_maps, map_bytes, n, ow, oh, ids, values, d_out, kind="index", dtype=None, default=0, planes=None, on=None, off=None, stream=0):
+        """label_targets for id maps of map_bytes 3 (any address) or 4 (aligned to 4 bytes) per pixel (llcomp_mi_codec_label_targets32);
+        ids, values, kind, dtype, default, planes, on and off as label_targets_reference -> d_out.  Asynchronous on `stream`."""
+        if int(map_bytes) not in (3, 4):
+            raise LlcompError(BAD_ARGS, f"map_bytes of a wide id map is 3 or 4, got {map_bytes!r}")
+        t, keep, _, _ = _label_targets(ids, values, int(n), int(map_bytes), kind, dtype, default, planes, on, off)
+        _check(self._L.llcomp_mi_codec_label_targets32(self._h, d_maps, int(n), int(ow), int(oh), C.byref(t), d_out, stream))
+
+    def label_targets32_workspace_bytes(self, n, total_ids):
+        """the bound on .allocated_bytes() with label_targets32 calls of up to n samples and total_ids listed ids
+        (llcomp_mi_codec_label_targets32_workspace_bytes)"""
+        return self._L.llcomp_mi_codec_label_targets32_workspace_bytes(self._h, int(n), int(total_ids))
 
     def label_targets_workspace_bytes(self, n, total_ids):
         """the bound on .allocated_bytes() with label_targets calls of up to n samples and total_ids listed ids

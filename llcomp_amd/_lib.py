@@ -63,6 +63,10 @@ SYMBOLS = [
     "llcomp_mi_codec_label_boxes16_workspace_bytes",
     "llcomp_mi_label_targets_reference", "llcomp_mi_label_targets_out_bytes", "llcomp_mi_label_targets_segment",
     "llcomp_mi_label_targets_max_planes", "llcomp_mi_codec_label_targets", "llcomp_mi_codec_label_targets_workspace_bytes",
+    "llcomp_mi_label_boxes32_reference", "llcomp_mi_codec_label_boxes32", "llcomp_mi_codec_label_boxes32_workspace_bytes",
+    "llcomp_mi_label_targets32_reference", "llcomp_mi_label_targets32_out_bytes", "llcomp_mi_codec_label_targets32",
+    "llcomp_mi_codec_label_targets32_workspace_bytes",
+    "llcomp_mi_paste32_reference", "llcomp_mi_paste32_plan", "llcomp_mi_codec_paste_batch32", "llcomp_mi_codec_paste32_workspace_bytes",
 ]
 
 u8p = C.POINTER(C.c_uint8)
@@ -155,6 +159,10 @@ class PastePiece16(C.Structure):
                 ("ids", C.c_uint32 * 8)]
 
 
+class PastePiece32(PastePiece16):
+    """llcomp_mi_paste_piece32 (include/llcomp_mi.h): the same 76 bytes, id_base any 32-bit value, flags bit 1 VALUE_PIXEL"""
+
+
 class PastePiece(C.Structure):
     """llcomp_mi_paste_piece (include/llcomp_mi.h): 72 bytes, ids at 40"""
     _fields_ = [("dst", C.c_uint32), ("src", C.c_uint32), ("dx", C.c_uint32), ("dy", C.c_uint32), ("sx", C.c_uint32), ("sy", C.c_uint32),
@@ -171,6 +179,10 @@ class LabelTargets(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("map_bytes", C.c_uint32), ("kind", C.c_uint32), ("dtype", C.c_uint32), ("default_value", C.c_int32),
                 ("on_bits", C.c_uint32), ("off_bits", C.c_uint32), ("ids", C.c_void_p), ("values", C.c_void_p), ("first", C.c_void_p),
                 ("plane_first", C.c_void_p)]
+
+
+class LabelTargets32(LabelTargets):
+    """llcomp_mi_label_targets32 (include/llcomp_mi.h): the same 64 bytes, ids of uint32_t, map_bytes 3 or 4"""
 
 
 class Info(C.Structure):
@@ -600,6 +612,31 @@ def load():
         L.llcomp_mi_codec_label_targets.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 3 + [C.POINTER(LabelTargets), C.c_void_p, C.c_void_p]
         L.llcomp_mi_codec_label_targets_workspace_bytes.restype = C.c_uint64
         L.llcomp_mi_codec_label_targets_workspace_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+    if "LLCOMP_MI_LIB" not in os.environ or hasattr(L, "llcomp_mi_label_boxes32_reference"):  # wide id maps
+        L.llcomp_mi_label_boxes32_reference.restype = C.c_int
+        L.llcomp_mi_label_boxes32_reference.argtypes = [C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p] * 3
+        L.llcomp_mi_codec_label_boxes32.restype = C.c_int
+        L.llcomp_mi_codec_label_boxes32.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p] * 4
+        L.llcomp_mi_codec_label_boxes32_workspace_bytes.restype = C.c_uint64
+        L.llcomp_mi_codec_label_boxes32_workspace_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+        L.llcomp_mi_label_targets32_reference.restype = C.c_int
+        L.llcomp_mi_label_targets32_reference.argtypes = [C.c_void_p] + [C.c_uint32] * 3 + [C.POINTER(LabelTargets32), C.c_void_p]
+        L.llcomp_mi_label_targets32_out_bytes.restype = C.c_uint64
+        L.llcomp_mi_label_targets32_out_bytes.argtypes = [C.c_uint32] * 3 + [C.POINTER(LabelTargets32)]
+        L.llcomp_mi_codec_label_targets32.restype = C.c_int
+        L.llcomp_mi_codec_label_targets32.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 3 + [C.POINTER(LabelTargets32), C.c_void_p, C.c_void_p]
+        L.llcomp_mi_codec_label_targets32_workspace_bytes.restype = C.c_uint64
+        L.llcomp_mi_codec_label_targets32_workspace_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+    if "LLCOMP_MI_LIB" not in os.environ or hasattr(L, "llcomp_mi_paste32_reference"):  # batch copy-paste by wide ids
+        recs32, u32p = C.POINTER(PastePiece32), C.POINTER(C.c_uint32)
+        L.llcomp_mi_paste32_reference.restype = C.c_int
+        L.llcomp_mi_paste32_reference.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p] + [C.c_uint32] * 6 + [recs32, C.c_uint32, C.c_void_p]
+        L.llcomp_mi_paste32_plan.restype = C.c_int
+        L.llcomp_mi_paste32_plan.argtypes = [C.c_uint32] * 10 + [recs32, C.c_uint32, u32p, u32p, u32p, u32p, C.POINTER(C.c_uint64)]
+        L.llcomp_mi_codec_paste_batch32.restype = C.c_int
+        L.llcomp_mi_codec_paste_batch32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p] + [C.c_uint32] * 5 + [recs32, C.c_uint32, C.c_void_p]
+        L.llcomp_mi_codec_paste32_workspace_bytes.restype = C.c_uint64
+        L.llcomp_mi_codec_paste32_workspace_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
     if "LLCOMP_MI_LIB" not in os.environ and L.llcomp_mi_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.llcomp_mi_abi_version()}, this binding was written for {ABI_VERSION}: rebuild the library")
     _lib = L

@@ -67,7 +67,12 @@ struct DeviceMem {
     }
     template <uint32_t N>
     __device__ inline __attribute__((always_inline)) uint32_t load_el(uint64_t a) const {
-        return *reinterpret_cast<const typename ElemOf<N>::T*>(a);
+        if constexpr (N == 3) {  // (a 3-byte pixel, at any address: three byte loads)
+            const uint8_t* p = reinterpret_cast<const uint8_t*>(a);
+            return uint32_t(p[0]) | uint32_t(p[1]) << 8 | uint32_t(p[2]) << 16;
+        } else {
+            return *reinterpret_cast<const typename ElemOf<N>::T*>(a);
+        }
     }
     template <uint32_t N>
     __device__ inline __attribute__((always_inline)) void store_el(uint64_t a, uint64_t bits) const {
@@ -85,6 +90,46 @@ LLMI_CHUNK_FN BatchChunk chunk_read(uint64_t base, uint64_t bytes, uint64_t u, u
     for (uint32_t p = 0; p < 16 / N; ++p)
         if (p >= p0 && p < p1) chunk_or<N>(v.w, p, mem.template load_el<N>(u + N * p));
     return v;
+}
+
+// 3-byte pixels (the wide id maps, include/llcomp_mi.h "Wide id maps") lie at any byte address, so one may straddle two units: a pixel
+// BELONGS to the unit that holds its first byte, and that unit's thread reads the pixel's other bytes, at most two, from the next
+// unit.  WideChunk: a unit's four words and the next unit's first, bytes 0 .. 19 of a run of memory.
+struct WideChunk {
+    uint32_t w[5];
+};
+// the 3-byte pixel whose first byte is byte b <= 15 of the run (b a constant after unrolling: the words are never indexed by a variable)
+template <class W>
+LLMI_CHUNK_FN uint32_t chunk_get3(const W& w, uint32_t b) {
+    const uint32_t k = b >> 2, sh = 8 * (b & 3);
+    uint32_t v = w[k] >> sh;
+    if (sh > 8) v |= w[k + 1] << (32 - sh);
+    return v & 0xFFFFFFu;
+}
+// The bytes [b0, b1) of the run at the aligned address u, b0 < 16 and b1 <= 18, all of them inside the batch at [base, base + bytes):
+// the unit read whole where it lies inside the batch, byte by byte where it sticks out, and the bytes 16 and 17 one by one (the
+// other bytes: zeros, or the batch's)
+template <class Mem>
+LLMI_CHUNK_FN WideChunk chunk_read3(uint64_t base, uint64_t bytes, uint64_t u, uint32_t b0, uint32_t b1, Mem& mem) {
+    WideChunk v{{0u, 0u, 0u, 0u, 0u}};
+    if (u >= base && u + 16 <= base + bytes) {
+        const BatchChunk c = mem.load16(u);
+        v.w[0] = c.w[0], v.w[1] = c.w[1], v.w[2] = c.w[2], v.w[3] = c.w[3];
+    } else {
+        LLMI_UNROLL
+        for (uint32_t b = 0; b < 16; ++b)
+            if (b >= b0 && b < b1) chunk_or<1>(v.w, b, mem.template load_el<1>(u + b));
+    }
+    if (b1 > 16) v.w[4] = mem.template load_el<1>(u + 16);
+    if (b1 > 17) v.w[4] |= mem.template load_el<1>(u + 17) << 8;
+    return v;
+}
+// The 3-byte pixels of the byte range [lo, hi) -- lo a pixel's first byte, hi - lo a multiple of 3 -- that belong to the unit at u:
+// their count, 0 to 6; s: the first one's first byte in the unit.  The pixels' bytes are [s, s + 3 * count) of the unit's run.
+LLMI_CHUNK_FN uint32_t chunk_pixels3(uint64_t lo, uint64_t hi, uint64_t u, uint32_t& s) {
+    const uint64_t a0 = u <= lo ? lo : u + (3u - uint32_t((u - lo) % 3u)) % 3u, end = u + 16 < hi ? u + 16 : hi;
+    s = uint32_t(a0 - u);
+    return a0 < end ? (uint32_t(end - a0) + 2u) / 3u : 0u;
 }
 
 struct PlainMem {  // (little-endian hosts, like the containers)

@@ -446,7 +446,7 @@ int paste_batch_call(llcomp_mi_codec* k, uint8_t*& tab, uint64_t& cap, const voi
     if (int rc = paste_check_call(n_src, iw, ih, n_dst, ow, oh, c, dtype, layout, pieces, n_pieces, value_bits)) return rc;
     const uint32_t esize = batch_esize(dtype);
     if (int rc = paste_check_memory(d_src, uint64_t(n_src) * c * iw * ih * esize, d_mask, MB * uint64_t(n_src) * iw * ih, d_dst,
-                                    uint64_t(n_dst) * c * ow * oh * esize, esize, MB, n_pieces))
+                                    uint64_t(n_dst) * c * ow * oh * esize, esize, paste_mask_align(MB), n_pieces))
         return rc;
     PastePlan p;
     paste_plan(n_dst, pieces, n_pieces, p);
@@ -1709,6 +1709,26 @@ uint64_t llcomp_mi_codec_paste16_workspace_bytes(const llcomp_mi_codec* k, uint3
     return k->workspace_bytes + paste_table_bound<2>(n_dst, n_pieces);
 }
 
+// Batch copy-paste by wide ids (DESIGN.md "Wide id maps"): the same for masks of 3 or 4 bytes per pixel, the pieces cast to the
+// width's type, in the 16-bit call's table buffer (the records have its size).
+int llcomp_mi_codec_paste_batch32(llcomp_mi_codec* k, const void* d_src, const void* d_mask, uint32_t map_bytes, uint32_t n_src, uint32_t iw, uint32_t ih,
+                                  void* d_dst, uint32_t n_dst, uint32_t ow, uint32_t oh, uint32_t dtype, uint32_t layout, const llcomp_mi_paste_piece32* pieces,
+                                  uint32_t n_pieces, void* stream) {
+    if (!k) return LLCOMP_MI_BAD_ARGS;
+    if (map_bytes == 3)
+        return paste_batch_call(k, k->d_paste16_tab, k->paste16_tab_cap, d_src, d_mask, n_src, iw, ih, d_dst, n_dst, ow, oh, dtype, layout,
+                                static_cast<const PastePiece3*>(pieces), n_pieces, stream);
+    if (map_bytes == 4)
+        return paste_batch_call(k, k->d_paste16_tab, k->paste16_tab_cap, d_src, d_mask, n_src, iw, ih, d_dst, n_dst, ow, oh, dtype, layout,
+                                static_cast<const PastePiece4*>(pieces), n_pieces, stream);
+    return LLCOMP_MI_BAD_ARGS;
+}
+
+uint64_t llcomp_mi_codec_paste32_workspace_bytes(const llcomp_mi_codec* k, uint32_t n_dst, uint32_t n_pieces) {
+    if (!k) return 0;
+    return k->workspace_bytes + paste_table_bound<4>(n_dst, n_pieces);
+}
+
 // Label boxes (DESIGN.md "Label boxes"): the codec gives the device; no table, no workspace.
 int llcomp_mi_codec_label_boxes(llcomp_mi_codec* k, const void* d_maps, uint32_t n, uint32_t ow, uint32_t oh, void* d_boxes, void* stream) {
     if (!k || !d_maps || !d_boxes) return LLCOMP_MI_BAD_ARGS;
@@ -1772,6 +1792,56 @@ int llcomp_mi_codec_label_targets(llcomp_mi_codec* k, const void* d_maps, uint32
 uint64_t llcomp_mi_codec_label_targets_workspace_bytes(const llcomp_mi_codec* k, uint32_t n, uint32_t total_ids) {
     if (!k) return 0;
     return k->workspace_bytes + target_table_bound(n, total_ids);
+}
+
+// Wide id maps (DESIGN.md "Wide id maps"): the two calls above for maps of 3 or 4 bytes per pixel and lists of uint32_t ids, in the
+// 16-bit calls' table buffers.
+int llcomp_mi_codec_label_boxes32(llcomp_mi_codec* k, const void* d_maps, uint32_t map_bytes, uint32_t n, uint32_t ow, uint32_t oh, const uint32_t* ids,
+                                  const uint32_t* first, void* d_boxes, void* stream) {
+    if (!k || !d_maps) return LLCOMP_MI_BAD_ARGS;
+    uint32_t longest = 0, n_listed = 0;
+    if (int rc = label_boxes32_check_call(map_bytes, n, ow, oh, ids, first, &longest, &n_listed)) return rc;
+    const uint32_t total = first[n];
+    const uint64_t m = reinterpret_cast<uintptr_t>(d_maps), b = reinterpret_cast<uintptr_t>(d_boxes);
+    const uint64_t maps_bytes = map_bytes * uint64_t(n) * ow * oh, box_bytes = uint64_t(total) * sizeof(llcomp_mi_label_box);
+    if (label_map32_misaligned(m, map_bytes) || (total && (!d_boxes || misaligned(d_boxes, 4) || (m < b + box_bytes && b < m + maps_bytes)))) return LLCOMP_MI_BAD_ARGS;
+    if (!total) return LLCOMP_MI_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return batch_table_call(
+        k, k->d_label16_tab, k->label16_tab_cap, Label16Table(n, n_listed, total, 4).bytes, label32_table_bound(n, total), s,
+        [&](uint8_t* at) { label32_table_put(n, ids, first, n_listed, at); },
+        [&](const uint8_t* d_table) {
+            return launch_label_boxes32(static_cast<const uint8_t*>(d_maps), map_bytes, n, ow, oh, d_table, n_listed, total, longest, static_cast<uint8_t*>(d_boxes), s);
+        });
+}
+
+uint64_t llcomp_mi_codec_label_boxes32_workspace_bytes(const llcomp_mi_codec* k, uint32_t n, uint32_t total_ids) {
+    if (!k) return 0;
+    return k->workspace_bytes + label32_table_bound(n, total_ids);
+}
+
+int llcomp_mi_codec_label_targets32(llcomp_mi_codec* k, const void* d_maps, uint32_t n, uint32_t ow, uint32_t oh, const llcomp_mi_label_targets32* targets,
+                                    void* d_out, void* stream) {
+    if (!k || !d_maps || !d_out) return LLCOMP_MI_BAD_ARGS;
+    TargetCall c;
+    if (int rc = label_targets32_check_call(n, ow, oh, targets, c)) return rc;
+    const llcomp_mi_label_targets32& t = *targets;
+    const uint64_t m = reinterpret_cast<uintptr_t>(d_maps), o = reinterpret_cast<uintptr_t>(d_out);
+    const uint64_t maps_bytes = uint64_t(n) * ow * oh * t.map_bytes;
+    if (label_map32_misaligned(m, t.map_bytes) || misaligned(d_out, c.esize) || (m < o + c.out_bytes && o < m + maps_bytes)) return LLCOMP_MI_BAD_ARGS;
+    if (!c.n_work) return LLCOMP_MI_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return batch_table_call(
+        k, k->d_target_tab, k->target_tab_cap, TargetTable(n, c.n_work, c.total, t.kind == LLCOMP_MI_TARGET_PLANES, 4).bytes, target32_table_bound(n, c.total), s,
+        [&](uint8_t* at) { target32_table_put(n, t, c, at); },
+        [&](const uint8_t* d_table) {
+            return launch_label_targets32(static_cast<const uint8_t*>(d_maps), n, ow, oh, t, c, d_table, static_cast<uint8_t*>(d_out), s);
+        });
+}
+
+uint64_t llcomp_mi_codec_label_targets32_workspace_bytes(const llcomp_mi_codec* k, uint32_t n, uint32_t total_ids) {
+    if (!k) return 0;
+    return k->workspace_bytes + target32_table_bound(n, total_ids);
 }
 
 uint64_t llcomp_mi_codec_photo_workspace_bytes(const llcomp_mi_codec* k, uint64_t total_views) {

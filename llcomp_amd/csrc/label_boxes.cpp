@@ -36,14 +36,17 @@ void label_boxes_sample(const LabelGeom& g, uint32_t i, uint32_t cnt, Sink& sink
 
 }  // namespace
 
-void label16_table_put(uint32_t n, const uint16_t* ids, const uint32_t* first, uint32_t n_listed, uint8_t* at) {
-    const Label16Table tab(n, n_listed, first[n]);
+template <class Id>
+static void label_table_put(uint32_t n, const Id* ids, const uint32_t* first, uint32_t n_listed, uint8_t* at) {
+    const Label16Table tab(n, n_listed, first[n], sizeof(Id));
     std::memcpy(at + tab.first_at, first, 4 * (size_t(n) + 1));
     uint32_t k = 0;
     for (uint32_t i = 0; i < n; ++i)
         if (first[i + 1] != first[i]) std::memcpy(at + tab.samples_at + 4 * size_t(k++), &i, 4);
-    std::memcpy(at + tab.ids_at, ids, 2 * size_t(first[n]));
+    std::memcpy(at + tab.ids_at, ids, sizeof(Id) * size_t(first[n]));
 }
+void label16_table_put(uint32_t n, const uint16_t* ids, const uint32_t* first, uint32_t n_listed, uint8_t* at) { label_table_put(n, ids, first, n_listed, at); }
+void label32_table_put(uint32_t n, const uint32_t* ids, const uint32_t* first, uint32_t n_listed, uint8_t* at) { label_table_put(n, ids, first, n_listed, at); }
 
 }  // namespace llcomp_mi
 
@@ -75,6 +78,23 @@ int llcomp_mi_label_boxes16_reference(const void* maps, uint32_t n, uint32_t ow,
         if (!cnt) continue;
         PlainSink<LabelFinder<const uint16_t*>> sink{{ids + first[i], cnt}, out + first[i]};
         label_boxes_sample<2>(g, i, cnt, sink);
+    }
+    return LLCOMP_MI_OK;
+}
+
+int llcomp_mi_label_boxes32_reference(const void* maps, uint32_t map_bytes, uint32_t n, uint32_t ow, uint32_t oh, const uint32_t* ids, const uint32_t* first,
+                                      llcomp_mi_label_box* out) {
+    using namespace llcomp_mi;
+    if (int rc = label_boxes32_check_call(map_bytes, n, ow, oh, ids, first)) return rc;
+    const uint64_t m = reinterpret_cast<uintptr_t>(maps);
+    if (!maps || label_map32_misaligned(m, map_bytes) || (!out && first[n])) return LLCOMP_MI_BAD_ARGS;
+    const LabelGeom g = map_bytes == 3 ? label_geom<3>(m, n, ow, oh) : label_geom<4>(m, n, ow, oh);
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t cnt = first[i + 1] - first[i];
+        if (!cnt) continue;
+        PlainSink<LabelFinder<const uint32_t*>> sink{label_finder32(ids + first[i], cnt), out + first[i]};
+        if (map_bytes == 3) label_boxes_sample<3>(g, i, cnt, sink);
+        else label_boxes_sample<4>(g, i, cnt, sink);
     }
     return LLCOMP_MI_OK;
 }

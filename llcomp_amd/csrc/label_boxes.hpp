@@ -21,4 +21,10 @@ void label16_table_put(uint32_t n, const uint16_t* ids, const uint32_t* first, u
 hipError_t launch_label_boxes16(const uint8_t* d_maps, uint32_t n, uint32_t ow, uint32_t oh, const uint8_t* d_table, uint32_t n_listed, uint32_t total,
                                 uint32_t longest, uint8_t* d_boxes, hipStream_t stream);
 
+// The same of maps of map_bytes 3 or 4 (k_label_boxes32<MB, K>; llcomp_mi_codec_label_boxes32): the table's ids are uint32_t.  d_maps:
+// at any address for map_bytes 3, 4-byte aligned for 4.  Checked (label_boxes32_check_call).
+void label32_table_put(uint32_t n, const uint32_t* ids, const uint32_t* first, uint32_t n_listed, uint8_t* at);
+hipError_t launch_label_boxes32(const uint8_t* d_maps, uint32_t map_bytes, uint32_t n, uint32_t ow, uint32_t oh, const uint8_t* d_table, uint32_t n_listed,
+                                uint32_t total, uint32_t longest, uint8_t* d_boxes, hipStream_t stream);
+
 }  // namespace llcomp_mi

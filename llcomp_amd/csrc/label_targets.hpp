@@ -21,4 +21,10 @@ void target_table_put(uint32_t n, const llcomp_mi_label_targets& t, const Target
 hipError_t launch_label_targets(const uint8_t* d_maps, uint32_t n, uint32_t ow, uint32_t oh, const llcomp_mi_label_targets& t, const TargetCall& c,
                                 const uint8_t* d_table, uint8_t* d_out, hipStream_t stream);
 
+// The same for maps of t.map_bytes 3 or 4 (k_label_targets32<MB, K, KIND>; llcomp_mi_codec_label_targets32): the table's ids are
+// uint32_t.  d_maps: at any address for map_bytes 3, 4-byte aligned for 4.
+void target32_table_put(uint32_t n, const llcomp_mi_label_targets32& t, const TargetCall& c, uint8_t* at);
+hipError_t launch_label_targets32(const uint8_t* d_maps, uint32_t n, uint32_t ow, uint32_t oh, const llcomp_mi_label_targets32& t, const TargetCall& c,
+                                  const uint8_t* d_table, uint8_t* d_out, hipStream_t stream);
+
 }  // namespace llcomp_mi

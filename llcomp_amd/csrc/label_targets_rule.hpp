@@ -12,8 +12,11 @@
 // -- its other elements are the neighbouring segment's, plane's or sample's, or lie outside the output -- gets exactly its own
 // elements, element by element: compose_rule.hpp's unit rule.  No output byte is written twice, none outside the output is touched.
 // Mem: batch_chunk.hpp's (load16 of an aligned unit, load_el<MB> of a pixel; store16 of an aligned unit, store_el<ES> of an element).
+// MB 3 and 4 (include/llcomp_mi.h "Wide id maps"): lists of uint32_t ids through label_finder32; a 3-byte pixel belongs to the unit
+// that holds its first byte (batch_chunk.hpp: chunk_pixels3, chunk_read3); the output side does not know the map's width.
 #pragma once
 #include <cstdint>
+#include <type_traits>
 
 #include "batch_chunk.hpp"
 #include "label_lists.hpp"
@@ -26,6 +29,7 @@ constexpr uint32_t kTargetMaxPlanes = 4096;   // of a sample (llcomp_mi_label_ta
 constexpr uint32_t kTargetPlaneChunk = 32;    // planes of a workgroup: what one look-up of the segment is shared by
 constexpr uint32_t kTargetNoPlane = 0xFFFFu;  // PLANES: the value selects no plane
 constexpr uint32_t kTargetIdBytes = 2 + 4;    // of LDS per listed id, map_bytes 2: the id and its value
+constexpr uint32_t kTarget32IdBytes = 4 + 4;  // ... map_bytes 3 and 4
 
 // The element's size in bytes, 0 for a kind or dtype that is none
 LLMI_HD constexpr uint32_t target_esize(uint32_t kind, uint32_t dtype) {
@@ -44,11 +48,19 @@ struct TargetCall {
 
 // A whole call but for its device pointers: label_boxes16_check_call's check of the shape and of the lists (the bounds before any id
 // is read), then the values, the planes and the output's size
-inline int label_targets_check_call(uint32_t n, uint32_t ow, uint32_t oh, const llcomp_mi_label_targets* t, TargetCall& c) {
-    if (!t || t->struct_size < sizeof(llcomp_mi_label_targets) || (t->map_bytes != 1 && t->map_bytes != 2) || !t->values) return LLCOMP_MI_BAD_ARGS;
+// (T: llcomp_mi_label_targets, map_bytes 1 or 2, or llcomp_mi_label_targets32, map_bytes 3 or 4 -- the same fields but for the ids' type)
+template <class T>
+inline int label_targets_check_any(uint32_t n, uint32_t ow, uint32_t oh, const T* t, TargetCall& c) {
+    constexpr bool kWide = std::is_same<T, llcomp_mi_label_targets32>::value;
+    if (!t || t->struct_size < sizeof(T) || !t->values) return LLCOMP_MI_BAD_ARGS;
+    if (kWide ? t->map_bytes != 3 && t->map_bytes != 4 : t->map_bytes != 1 && t->map_bytes != 2) return LLCOMP_MI_BAD_ARGS;
     c.esize = target_esize(t->kind, t->dtype);
     if (!c.esize) return LLCOMP_MI_BAD_ARGS;
-    if (int rc = label_boxes16_check_call(n, ow, oh, t->ids, t->first, &c.longest, nullptr)) return rc;
+    if constexpr (kWide) {
+        if (int rc = label_boxes32_check_call(t->map_bytes, n, ow, oh, t->ids, t->first, &c.longest, nullptr)) return rc;
+    } else {
+        if (int rc = label_boxes16_check_call(n, ow, oh, t->ids, t->first, &c.longest, nullptr)) return rc;
+    }
     c.total = t->first[n];
     if (t->map_bytes == 1)
         for (uint32_t i = 0; i < n; ++i)  // (ascending: the last id of a list is its largest)
@@ -76,15 +88,23 @@ inline int label_targets_check_call(uint32_t n, uint32_t ow, uint32_t oh, const 
     return (c.out_bytes >> 62) != 0 ? LLCOMP_MI_BAD_ARGS : LLCOMP_MI_OK;
 }
 
+inline int label_targets_check_call(uint32_t n, uint32_t ow, uint32_t oh, const llcomp_mi_label_targets* t, TargetCall& c) {
+    return label_targets_check_any(n, ow, oh, t, c);
+}
+inline int label_targets32_check_call(uint32_t n, uint32_t ow, uint32_t oh, const llcomp_mi_label_targets32* t, TargetCall& c) {
+    return label_targets_check_any(n, ow, oh, t, c);
+}
+
 // The table of a call in device memory: first[n + 1], the n_work samples that get workgroups, ascending, plane_first[n + 1] (PLANES),
-// the values, the ids
+// the values, the ids, of id_bytes each
 struct TargetTable {
     uint64_t first_at, samples_at, planes_at, values_at, ids_at, bytes;
-    TargetTable(uint64_t n, uint64_t n_work, uint64_t total, bool planes)
+    TargetTable(uint64_t n, uint64_t n_work, uint64_t total, bool planes, uint64_t id_bytes = 2)
         : first_at(0), samples_at(4 * (n + 1)), planes_at(samples_at + 4 * n_work), values_at(planes_at + (planes ? 4 * (n + 1) : 0)),
-          ids_at(values_at + 4 * total), bytes(ids_at + 2 * total) {}
+          ids_at(values_at + 4 * total), bytes(ids_at + id_bytes * total) {}
 };
 inline uint64_t target_table_bound(uint64_t n, uint64_t total_ids) { return TargetTable(n, n, total_ids, true).bytes; }
+inline uint64_t target32_table_bound(uint64_t n, uint64_t total_ids) { return TargetTable(n, n, total_ids, true, 4).bytes; }
 
 struct TargetGeom {
     uint64_t maps, map_bytes;  // the maps' first byte and their size
@@ -131,10 +151,10 @@ LLMI_HD inline void label_targets_table_thread(uint32_t step, uint32_t t, const 
     }
 }
 
-// v(i, p) of a pixel's id, as the table has it: MB 1 by the dense table, MB 2 by LabelFinder in the list
+// v(i, p) of a pixel's id, as the table has it: MB 1 by the dense table, MB 2 and above by LabelFinder in the list
 template <uint32_t MB, class List, class Vals>
 struct TargetLookup {
-    LabelFinder<List> finder;
+    LabelFinder<List> finder;  // (MB 3 and 4: label_finder32's)
     Vals vals;
     uint32_t dflt;  // target_table_value of the default
     LLMI_HD inline uint32_t operator()(uint32_t id) {
@@ -152,14 +172,25 @@ struct TargetLookup {
 // out (chunk_read).  (MB 2: lo and hi are even.)
 template <uint32_t MB, class Mem, class Lookup, class V>
 LLMI_HD inline void label_targets_read_unit(const TargetGeom& g, uint64_t lo, uint64_t hi, uint64_t u, Mem& mem, Lookup& look, V& v) {
-    constexpr uint32_t PER = 16 / MB;
-    const uint32_t p0 = (u < lo ? uint32_t(lo - u) : 0u) / MB, p1 = (u + 16 > hi ? uint32_t(hi - u) : 16u) / MB;
-    if (p0 >= p1) return;
-    const BatchChunk c = chunk_read<MB>(g.maps, g.map_bytes, u, p0, p1, mem);
-    const uint32_t at = u < lo ? 0u : uint32_t((u - lo) / MB);  // of pixel p0 in the segment
-    LLMI_UNROLL
-    for (uint32_t p = 0; p < PER; ++p)  // (p is a constant in every turn: the unit's words are never indexed by a variable)
-        if (p >= p0 && p < p1) v[at + p - p0] = look(chunk_get<MB>(c.w, p));
+    if constexpr (MB == 3) {  // (the pixels that BELONG to the unit, the straddling one's last bytes from the next: batch_chunk.hpp)
+        uint32_t s;
+        const uint32_t npx = chunk_pixels3(lo, hi, u, s), b1 = s + 3 * npx, phase = s % 3;
+        if (!npx) return;
+        const WideChunk c = chunk_read3(g.maps, g.map_bytes, u, s, b1, mem);
+        uint32_t at = uint32_t(u + s - lo) / 3;  // of the unit's first pixel in the segment (whose bytes are 3 * kTargetSegment at most)
+        LLMI_UNROLL
+        for (uint32_t b = 0; b < 16; ++b)  // (b is a constant in every turn: a pixel's first byte)
+            if (b % 3 == phase && b >= s && b < b1) v[at++] = look(chunk_get3(c.w, b));
+    } else {
+        constexpr uint32_t PER = 16 / MB;
+        const uint32_t p0 = (u < lo ? uint32_t(lo - u) : 0u) / MB, p1 = (u + 16 > hi ? uint32_t(hi - u) : 16u) / MB;
+        if (p0 >= p1) return;
+        const BatchChunk c = chunk_read<MB>(g.maps, g.map_bytes, u, p0, p1, mem);
+        const uint32_t at = u < lo ? 0u : uint32_t((u - lo) / MB);  // of pixel p0 in the segment
+        LLMI_UNROLL
+        for (uint32_t p = 0; p < PER; ++p)  // (p is a constant in every turn: the unit's words are never indexed by a variable)
+            if (p >= p0 && p < p1) v[at + p - p0] = look(chunk_get<MB>(c.w, p));
+    }
 }
 // Thread t of the workgroup of segment [s0, s1) of sample i: the aligned units t, t + 256, ... of its map bytes
 template <uint32_t MB, class Mem, class Lookup, class V>
@@ -233,9 +264,9 @@ LLMI_HD inline void label_targets_write_any(const TargetGeom& g, uint32_t i, uin
 // after the other within a phase: the lists and the planes as the call's table has them, the workgroup's LDS arrays list, vals (of
 // the capacity the call runs at) and v (of kTargetSegment) the caller's -- llcomp_mi_label_targets_reference's plain ones, the
 // stand-alone check's checking ones.
-template <class Mem, class Sink, class List, class Vals, class V>
+template <class Id, class Mem, class Sink, class List, class Vals, class V>
 inline void label_targets_host_workgroup(const TargetGeom& g, const TargetParams& a, uint32_t mb, const uint32_t* first, const uint32_t* plane_first, const int32_t* values,
-                                         const uint16_t* ids, uint32_t i, uint32_t seg, uint32_t z, Mem& mem, Sink& sink, List& list, Vals& vals, V& v) {
+                                         const Id* ids, uint32_t i, uint32_t seg, uint32_t z, Mem& mem, Sink& sink, List& list, Vals& vals, V& v) {
     const bool planar = a.kind == LLCOMP_MI_TARGET_PLANES;
     const uint32_t planes = planar ? plane_first[i + 1] - plane_first[i] : 0u, plane0 = planar ? plane_first[i] : 0u;
     const uint32_t k0 = z * kTargetPlaneChunk, k1 = planes - k0 < kTargetPlaneChunk ? planes : k0 + kTargetPlaneChunk;
@@ -246,16 +277,22 @@ inline void label_targets_host_workgroup(const TargetGeom& g, const TargetParams
     for (uint32_t step = 0; step < 2; ++step)
         for (uint32_t t = 0; t < kTargetThreads; ++t) {
             if (mb == 1) label_targets_table_thread<1>(step, t, a, planes, ids + at, values + at, cnt, list, vals);
-            else label_targets_table_thread<2>(step, t, a, planes, ids + at, values + at, cnt, list, vals);
+            else label_targets_table_thread<2>(step, t, a, planes, ids + at, values + at, cnt, list, vals);  // (the list: the same for 2, 3 and 4)
         }
     const uint32_t dflt = target_table_value(a.kind, a.default_value, planes);
     for (uint32_t t = 0; t < kTargetThreads; ++t) {
         if (mb == 1) {
             TargetLookup<1, List&, Vals&> look{{list, cnt}, vals, dflt};
             label_targets_read_thread<1>(g, i, s0, s1, t, mem, look, v);
-        } else {
+        } else if (mb == 2) {
             TargetLookup<2, List&, Vals&> look{{list, cnt}, vals, dflt};
             label_targets_read_thread<2>(g, i, s0, s1, t, mem, look, v);
+        } else if (mb == 3) {
+            TargetLookup<3, List&, Vals&> look{label_finder32<List&>(list, cnt), vals, dflt};
+            label_targets_read_thread<3>(g, i, s0, s1, t, mem, look, v);
+        } else {
+            TargetLookup<4, List&, Vals&> look{label_finder32<List&>(list, cnt), vals, dflt};
+            label_targets_read_thread<4>(g, i, s0, s1, t, mem, look, v);
         }
     }
     for (uint32_t t = 0; t < kTargetThreads; ++t) {

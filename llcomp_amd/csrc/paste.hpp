@@ -20,7 +20,7 @@ struct PasteLaunch {
     uint32_t n_samples, n_recs;  // of the table: the dst samples with workgroups, the pieces that are not ignored
     uint32_t n_src, iw, ih, ow, oh, c, dtype, layout;  // checked (paste_check_call)
 };
-// mask_bytes: 1 or 2, the MB of the table's records
+// mask_bytes: 1, 2, 3 or 4, the MB of the table's records (3: a mask at any address)
 hipError_t launch_paste(const PasteLaunch& o, uint32_t mask_bytes, hipStream_t stream);
 
 }  // namespace llcomp_mi

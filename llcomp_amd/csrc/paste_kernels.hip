@@ -1,5 +1,5 @@
-// paste_kernels.hip -- the batch copy-paste on the GPU, for both widths of id map (include/llcomp_mi.h: "Batch copy-paste", "Batch
-// copy-paste by 16-bit ids"; DESIGN.md under the same names): the pieces of a src batch that an id map selects into a dst batch, in
+// paste_kernels.hip -- the batch copy-paste on the GPU, for the four widths of id map (include/llcomp_mi.h: "Batch copy-paste", "Batch
+// copy-paste by 16-bit ids", "Wide id maps"; DESIGN.md under the same names): the pieces of a src batch that an id map selects into a dst batch, in
 // place, in ONE kernel with no scratch in device memory.  The rule, the mask fetch and what a thread does with one unit (paste_decide,
 // paste_finish) are paste_rule.hpp's, on top of the composition's tiles, units and shifted copy (compose_rule.hpp) -- the functions the
 // host check walks without a GPU; the table is paste_plan.hpp's.
@@ -26,6 +26,8 @@ static_assert(kPasteLdsBytes<1> == 17424 && 8 * kPasteLdsBytes<1> <= 160 * 1024 
               "17 KiB of LDS: eight workgroups, all 32 wavefronts, to a CU as far as LDS goes (DESIGN.md \"Batch copy-paste\")");
 static_assert(kPasteLdsBytes<2> == 18448 && 8 * kPasteLdsBytes<2> <= 160 * 1024,
               "18 KiB of LDS: eight workgroups, all 32 wavefronts, to a CU as far as LDS goes (DESIGN.md \"Batch copy-paste by 16-bit ids\")");
+
+static_assert(kPasteLdsBytes<3> == 18448 && kPasteLdsBytes<4> == 18448, "the wide masks: the 16-bit call's LDS");
 
 template <uint32_t MB>
 struct PasteArgs {
@@ -93,7 +95,8 @@ hipError_t launch_width(const PasteLaunch& o, hipStream_t stream) {
 }  // namespace
 
 hipError_t launch_paste(const PasteLaunch& o, uint32_t mask_bytes, hipStream_t stream) {
-    return mask_bytes == 1 ? launch_width<1>(o, stream) : mask_bytes == 2 ? launch_width<2>(o, stream) : hipErrorInvalidValue;
+    return mask_bytes == 1 ? launch_width<1>(o, stream) : mask_bytes == 2 ? launch_width<2>(o, stream) : mask_bytes == 3 ? launch_width<3>(o, stream)
+           : mask_bytes == 4 ? launch_width<4>(o, stream) : hipErrorInvalidValue;
 }
 
 }  // namespace llcomp_mi

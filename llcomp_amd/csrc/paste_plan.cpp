@@ -9,6 +9,7 @@
 namespace llcomp_mi {
 
 static_assert(sizeof(llcomp_mi_paste_piece) == 72 && sizeof(llcomp_mi_paste_piece16) == 76 && sizeof(ComposeSample) == 12, "the table's records");
+static_assert(sizeof(llcomp_mi_paste_piece32) == 76 && sizeof(PastePiece3) == 76 && sizeof(PastePiece4) == 76, "one layout, so that an array of the one is an array of the other");
 
 namespace {
 // A piece's own refusals, and its value in the dtype's bits.  8-bit: the float value as batch_value_bits converts a fill
@@ -24,6 +25,22 @@ bool paste_piece_value(const llcomp_mi_paste_piece16& p, uint32_t dtype, uint32_
     bits = p.value_bits;
     return es >= 4 || !(p.value_bits >> (8 * es));
 }
+// wide: the base within the map's ids, value bits above the element; VALUE_PIXEL with VALUE, on U8 HWC with c <= 4 only, its bytes
+// at and above c zero
+template <class P>
+bool paste_piece_value_wide(const P& p, uint32_t dtype, uint32_t layout, uint32_t c, uint32_t& bits) {
+    const uint32_t es = batch_esize(dtype);
+    if (kPasteMaskBytesOf<P> == 3 && p.id_base > 0xFFFFFFu) return false;
+    if (!(p.flags & LLCOMP_MI_PASTE_VALUE)) return !p.value_bits && !(p.flags & LLCOMP_MI_PASTE_VALUE_PIXEL);
+    bits = p.value_bits;
+    if (p.flags & LLCOMP_MI_PASTE_VALUE_PIXEL)
+        return dtype == LLCOMP_MI_DTYPE_U8 && layout == LLCOMP_MI_LAYOUT_HWC && c <= 4 && (c == 4 || !(p.value_bits >> (8 * c)));
+    return es >= 4 || !(p.value_bits >> (8 * es));
+}
+bool paste_piece_value(const PastePiece3& p, uint32_t dtype, uint32_t layout, uint32_t c, uint32_t& bits) { return paste_piece_value_wide(p, dtype, layout, c, bits); }
+bool paste_piece_value(const PastePiece4& p, uint32_t dtype, uint32_t layout, uint32_t c, uint32_t& bits) { return paste_piece_value_wide(p, dtype, layout, c, bits); }
+template <class P>
+bool paste_piece_value(const P& p, uint32_t dtype, uint32_t, uint32_t, uint32_t& bits) { return paste_piece_value(p, dtype, bits); }
 }  // namespace
 
 template <class P>
@@ -40,10 +57,10 @@ int paste_check_call(uint32_t n_src, uint32_t iw, uint32_t ih, uint32_t n_dst, u
     std::vector<uint32_t> on_sample(n_dst, 0u), bits(n_pieces, 0u);
     for (uint32_t i = 0; i < n_pieces; ++i) {
         const P& p = pieces[i];
-        if (p.dst >= n_dst || p.src >= n_src || (p.flags & ~LLCOMP_MI_PASTE_VALUE)) return LLCOMP_MI_BAD_ARGS;
+        if (p.dst >= n_dst || p.src >= n_src || (p.flags & ~kPasteFlagBits<kPasteMaskBytesOf<P>>)) return LLCOMP_MI_BAD_ARGS;
         if (p.dx > ow || p.w > ow - p.dx || p.dy > oh || p.h > oh - p.dy) return LLCOMP_MI_BAD_ARGS;
         if (p.sx > iw || p.w > iw - p.sx || p.sy > ih || p.h > ih - p.sy) return LLCOMP_MI_BAD_ARGS;
-        if (!paste_piece_value(p, dtype, bits[i])) return LLCOMP_MI_BAD_ARGS;
+        if (!paste_piece_value(p, dtype, layout, c, bits[i])) return LLCOMP_MI_BAD_ARGS;
         if (!paste_empty(p) && ++on_sample[p.dst] > kPasteMaxPiecesPerSample) return LLCOMP_MI_BAD_ARGS;
     }
     value_bits.swap(bits);
@@ -86,7 +103,7 @@ void paste_table_put(const P* pieces, const PastePlan& p, const std::vector<uint
     constexpr uint32_t MB = kPasteMaskBytesOf<P>;
     const uint32_t cs = layout == LLCOMP_MI_LAYOUT_CHW ? 1u : c;
     const PasteTable<MB> t(p.samples.size(), p.order.size());
-    static_assert(sizeof(PasteRec<MB>) == 64 + 4 * MB, "PasteTable's record");
+    static_assert(sizeof(PasteRec<MB>) == (MB == 1 ? 68 : 72), "PasteTable's record");
     if (!p.samples.empty()) std::memcpy(at + t.samples_at, p.samples.data(), p.samples.size() * sizeof(ComposeSample));
     for (size_t j = 0; j < p.order.size(); ++j) {
         const PasteRec<MB> r = paste_rec(pieces[p.order[j]], cs, value_bits[p.order[j]]);
@@ -104,7 +121,7 @@ int paste_reference(const void* src, const void* mask, uint32_t n_src, uint32_t 
     const uint32_t es = batch_esize(dtype);
     const uint64_t dst_bytes = uint64_t(n_dst) * c * ow * oh * es;
     if (!dst_in) return LLCOMP_MI_BAD_ARGS;
-    if (int rc = paste_check_memory(src, uint64_t(n_src) * c * iw * ih * es, mask, MB * uint64_t(n_src) * iw * ih, out, dst_bytes, es, MB, n_pieces)) return rc;
+    if (int rc = paste_check_memory(src, uint64_t(n_src) * c * iw * ih * es, mask, MB * uint64_t(n_src) * iw * ih, out, dst_bytes, es, paste_mask_align(MB), n_pieces)) return rc;
     uint8_t* o = static_cast<uint8_t*>(out);
     if (out != dst_in) std::memmove(o, dst_in, size_t(dst_bytes));
     // the rule, element by element: the last piece that selects its pixel, through the kernel's own address functions
@@ -124,7 +141,9 @@ int paste_reference(const void* src, const void* mask, uint32_t n_src, uint32_t 
                     const P& p = pieces[last];
                     for (uint32_t k = 0; k < g.cs; ++k) {
                         uint8_t* e = row + (uint64_t(x) * g.cs + k) * es;
-                        if (p.flags & LLCOMP_MI_PASTE_VALUE) {
+                        if (p.flags & LLCOMP_MI_PASTE_VALUE_PIXEL) {  // (the wide call's, checked: U8 HWC)
+                            *e = uint8_t(value_bits[last] >> (8 * k));
+                        } else if (p.flags & LLCOMP_MI_PASTE_VALUE) {
                             std::memcpy(e, &value_bits[last], es);
                         } else {
                             const uint64_t s = compose_src_row(g, es, p.src, pl, p.sy + (y - p.dy)) + (uint64_t(p.sx + (x - p.dx)) * g.cs + k) * es;
@@ -167,6 +186,8 @@ int paste_plan_out(uint32_t n_src, uint32_t iw, uint32_t ih, uint32_t n_dst, uin
                                     uint32_t, uint32_t, const P*, uint32_t, void*);
 LLMI_PASTE_INSTANTIATE(llcomp_mi_paste_piece)
 LLMI_PASTE_INSTANTIATE(llcomp_mi_paste_piece16)
+LLMI_PASTE_INSTANTIATE(PastePiece3)
+LLMI_PASTE_INSTANTIATE(PastePiece4)
 #undef LLMI_PASTE_INSTANTIATE
 
 }  // namespace llcomp_mi
@@ -184,6 +205,25 @@ int llcomp_mi_paste16_plan(uint32_t n_src, uint32_t iw, uint32_t ih, uint32_t n_
                            uint32_t layout, const llcomp_mi_paste_piece16* pieces, uint32_t n_pieces, uint32_t* samples, uint32_t* first,
                            uint32_t* order, uint32_t* n_samples, uint64_t* n_workgroups) {
     return llcomp_mi::paste_plan_out(n_src, iw, ih, n_dst, ow, oh, c, dtype, layout, pieces, n_pieces, samples, first, order, n_samples, n_workgroups);
+}
+
+int llcomp_mi_paste32_plan(uint32_t map_bytes, uint32_t n_src, uint32_t iw, uint32_t ih, uint32_t n_dst, uint32_t ow, uint32_t oh, uint32_t c, uint32_t dtype,
+                           uint32_t layout, const llcomp_mi_paste_piece32* pieces, uint32_t n_pieces, uint32_t* samples, uint32_t* first, uint32_t* order,
+                           uint32_t* n_samples, uint64_t* n_workgroups) {
+    using namespace llcomp_mi;
+    if (map_bytes == 3)
+        return paste_plan_out(n_src, iw, ih, n_dst, ow, oh, c, dtype, layout, static_cast<const PastePiece3*>(pieces), n_pieces, samples, first, order, n_samples, n_workgroups);
+    if (map_bytes == 4)
+        return paste_plan_out(n_src, iw, ih, n_dst, ow, oh, c, dtype, layout, static_cast<const PastePiece4*>(pieces), n_pieces, samples, first, order, n_samples, n_workgroups);
+    return LLCOMP_MI_BAD_ARGS;
+}
+int llcomp_mi_paste32_reference(const void* src, const void* mask, uint32_t map_bytes, uint32_t n_src, uint32_t iw, uint32_t ih, const void* dst_in, uint32_t n_dst,
+                                uint32_t ow, uint32_t oh, uint32_t c, uint32_t dtype, uint32_t layout, const llcomp_mi_paste_piece32* pieces, uint32_t n_pieces,
+                                void* out) {
+    using namespace llcomp_mi;
+    if (map_bytes == 3) return paste_reference(src, mask, n_src, iw, ih, dst_in, n_dst, ow, oh, c, dtype, layout, static_cast<const PastePiece3*>(pieces), n_pieces, out);
+    if (map_bytes == 4) return paste_reference(src, mask, n_src, iw, ih, dst_in, n_dst, ow, oh, c, dtype, layout, static_cast<const PastePiece4*>(pieces), n_pieces, out);
+    return LLCOMP_MI_BAD_ARGS;
 }
 
 int llcomp_mi_paste_reference(const void* src, const void* mask, uint32_t n_src, uint32_t iw, uint32_t ih, const void* dst_in, uint32_t n_dst,

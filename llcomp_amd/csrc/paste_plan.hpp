@@ -23,18 +23,19 @@ struct PastePlan {
 template <uint32_t MB>
 struct PasteTable {
     uint64_t samples_at, recs_at, bytes;
-    PasteTable(uint64_t n_samples, uint64_t n_recs) : samples_at(0), recs_at(n_samples * sizeof(ComposeSample)), bytes(recs_at + n_recs * (64 + 4 * MB)) {}
+    PasteTable(uint64_t n_samples, uint64_t n_recs) : samples_at(0), recs_at(n_samples * sizeof(ComposeSample)), bytes(recs_at + n_recs * (MB == 1 ? 68 : 72)) {}
 };
 template <uint32_t MB>
 inline uint64_t paste_table_bound(uint64_t n_dst, uint64_t n_pieces) { return PasteTable<MB>(n_dst, n_pieces).bytes; }
 
+// (P: llcomp_mi_paste_piece, llcomp_mi_paste_piece16, or paste_rule.hpp's PastePiece3 / PastePiece4 for the wide call.)
 // A whole call but for its pointers into memory: include/llcomp_mi.h lists the refusals.  The pieces' values come back in the dtype's
 // bits in value_bits[n_pieces] (0 without VALUE).
 template <class P>
 int paste_check_call(uint32_t n_src, uint32_t iw, uint32_t ih, uint32_t n_dst, uint32_t ow, uint32_t oh, uint32_t c, uint32_t dtype, uint32_t layout,
                      const P* pieces, uint32_t n_pieces, std::vector<uint32_t>& value_bits);
-// ... and its pointers: a NULL dst, a NULL src or mask with pieces, src or dst not aligned to the element, a mask not aligned to its
-// mask_px bytes per pixel, a dst that overlaps src or mask
+// ... and its pointers: a NULL dst, a NULL src or mask with pieces, src or dst not aligned to the element, a mask not aligned to
+// mask_px (a power of two: paste_mask_align), a dst that overlaps src or mask
 int paste_check_memory(const void* src, uint64_t src_bytes, const void* mask, uint64_t mask_bytes, const void* dst, uint64_t dst_bytes,
                        uint32_t esize, uint32_t mask_px, uint32_t n_pieces);
 // The plan of a checked call

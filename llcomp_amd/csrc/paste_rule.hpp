@@ -1,5 +1,6 @@
 // paste_rule.hpp -- the rule of the batch copy-paste for both widths of id map (include/llcomp_mi.h: "Batch copy-paste" and "Batch
-// copy-paste by 16-bit ids"), stated ONCE, templated on MB, the mask's bytes per pixel (1 or 2), next to ES, the element's: these
+// copy-paste by 16-bit ids", "Wide id maps"), stated ONCE, templated on MB, the mask's bytes per pixel (1 or 2; 3 or 4 for the wide
+// id maps, whose windows have any 32-bit base and whose 3-byte pixels may straddle the shifted copies), next to ES, the element's: these
 // functions are compiled into the kernel (paste_kernels.hip), into the references and the planner's checks (paste_plan.cpp) and into
 // the host check that walks the kernel's own decisions without a GPU (tests/helpers/paste_check.cpp).
 //
@@ -28,6 +29,16 @@ constexpr uint32_t kPasteMaxPiecesPerSample = 256;  // with w and h above 0 on o
 template <class P> inline constexpr uint32_t kPasteMaskBytesOf = 0;
 template <> inline constexpr uint32_t kPasteMaskBytesOf<llcomp_mi_paste_piece> = 1;
 template <> inline constexpr uint32_t kPasteMaskBytesOf<llcomp_mi_paste_piece16> = 2;
+// The wide call's piece, llcomp_mi_paste_piece32, serves maps of 3 and of 4 bytes per pixel; inside, the two are two types of the same
+// layout, so that everything written over the piece type knows the width at compile time (codec.hip and paste_plan.cpp cast on entry)
+struct PastePiece3 : llcomp_mi_paste_piece32 {};
+struct PastePiece4 : llcomp_mi_paste_piece32 {};
+template <> inline constexpr uint32_t kPasteMaskBytesOf<PastePiece3> = 3;
+template <> inline constexpr uint32_t kPasteMaskBytesOf<PastePiece4> = 4;
+// the flag bits a width's pieces may carry: VALUE_PIXEL is the wide call's only
+template <uint32_t MB> inline constexpr uint32_t kPasteFlagBits = MB >= 3 ? (LLCOMP_MI_PASTE_VALUE | LLCOMP_MI_PASTE_VALUE_PIXEL) : LLCOMP_MI_PASTE_VALUE;
+// the alignment of a mask of MB bytes per pixel: a 3-byte map lies at any address
+LLMI_HD constexpr uint32_t paste_mask_align(uint32_t mb) { return mb == 3 ? 1u : mb; }
 
 // THE id test, of a record or of a piece.  MB 1: mask byte m against the 256 bits.  MB 2: id m against the window of 256 ids from
 // id_base on (32-bit unsigned arithmetic: ids below the base wrap above 255)
@@ -37,6 +48,8 @@ LLMI_HD inline bool paste_id_set(const R& r, uint32_t m) {
         return (r.ids[m >> 5] >> (m & 31u)) & 1u;
     } else {
         const uint32_t d = m - r.id_base;
+        if constexpr (MB == 4)  // (a window that passes 0xFFFFFFFF selects nothing there: an id below the base must not wrap into it)
+            if (m < r.id_base) return false;
         return d < 256u && ((r.ids[d >> 5] >> (d & 31u)) & 1u);
     }
 }
@@ -60,6 +73,20 @@ LLMI_HD inline bool paste_idle(const llcomp_mi_paste_piece16& p) {
     }
     return paste_empty(p) || !any;
 }
+// ... and for the wide windows below 2^24 or 2^32
+template <uint32_t MB>
+LLMI_HD inline bool paste_idle_wide(const llcomp_mi_paste_piece32& p) {
+    const uint64_t end = 1ull << (8 * MB);  // one past the top id
+    uint32_t any = 0;
+    for (uint32_t i = 0; i < 8; ++i) {
+        const uint64_t lo = uint64_t(p.id_base) + 32 * i;
+        const uint32_t keep = lo >= end ? 0u : end - lo >= 32u ? 0xFFFFFFFFu : (1u << uint32_t(end - lo)) - 1u;
+        any |= p.ids[i] & keep;
+    }
+    return paste_empty(p) || !any;
+}
+LLMI_HD inline bool paste_idle(const PastePiece3& p) { return paste_idle_wide<3>(p); }
+LLMI_HD inline bool paste_idle(const PastePiece4& p) { return paste_idle_wide<4>(p); }
 
 // A piece as the kernel reads it: ComposeRec's eight words (columns in elements), the value in the dtype's bits, the id set -- 68 bytes;
 // MB 2: and the window's base -- 72 bytes.  (The 8-bit kernel's list in LDS and its filter's copy carry no word of the other width.)
@@ -78,7 +105,11 @@ struct PasteRec<2> {
     uint32_t id_base;
     uint32_t ids[8];
 };
-static_assert(sizeof(PasteRec<1>) == 68 && sizeof(PasteRec<2>) == 72, "the table's records");
+template <>
+struct PasteRec<3> : PasteRec<2> {};  // (the wide records: the 16-bit record's words, the base any 32-bit value)
+template <>
+struct PasteRec<4> : PasteRec<2> {};
+static_assert(sizeof(PasteRec<1>) == 68 && sizeof(PasteRec<2>) == 72 && sizeof(PasteRec<3>) == 72 && sizeof(PasteRec<4>) == 72, "the table's records");
 LLMI_HD inline PasteRec<1> paste_rec(const llcomp_mi_paste_piece& p, uint32_t cs, uint32_t value_bits) {
     PasteRec<1> o;
     o.r = ComposeRec{p.src, p.dx * cs, p.dy, p.sx * cs, p.sy, p.w * cs, p.h, p.flags};
@@ -93,6 +124,16 @@ LLMI_HD inline PasteRec<2> paste_rec(const llcomp_mi_paste_piece16& p, uint32_t 
     for (uint32_t i = 0; i < 8; ++i) o.ids[i] = p.ids[i];
     return o;
 }
+template <class P, uint32_t MB = kPasteMaskBytesOf<P>>
+LLMI_HD inline PasteRec<MB> paste_rec_wide(const P& p, uint32_t cs, uint32_t value_bits) {
+    PasteRec<MB> o;
+    o.r = ComposeRec{p.src, p.dx * cs, p.dy, p.sx * cs, p.sy, p.w * cs, p.h, p.flags};
+    o.value = value_bits, o.id_base = p.id_base;
+    for (uint32_t i = 0; i < 8; ++i) o.ids[i] = p.ids[i];
+    return o;
+}
+LLMI_HD inline PasteRec<3> paste_rec(const PastePiece3& p, uint32_t cs, uint32_t value_bits) { return paste_rec_wide(p, cs, value_bits); }
+LLMI_HD inline PasteRec<4> paste_rec(const PastePiece4& p, uint32_t cs, uint32_t value_bits) { return paste_rec_wide(p, cs, value_bits); }
 
 // One call as the kernel sees it: the composition's geometry under KEEP (there is no fill) and the mask batch, MB bytes per pixel
 struct PasteGeom {
@@ -139,7 +180,7 @@ struct PasteFetch {
 // decides which memory is read: MB 1 takes the n_el bytes that hold the pixels of n_el elements whatever c is (a pixel has an element
 // at least), MB 2 the 2 * npx bytes of the pixels themselves.
 template <uint32_t MB>
-LLMI_HD constexpr uint32_t paste_fetch_bytes(uint32_t n_el, uint32_t npx) { return MB == 1 ? n_el : 2 * npx; }
+LLMI_HD constexpr uint32_t paste_fetch_bytes(uint32_t n_el, uint32_t npx) { return MB == 1 ? n_el : MB * npx; }
 template <uint32_t MB>
 LLMI_HD inline PasteFetch paste_fetch_of(const PasteGeom& pg, const ComposeRec& r, uint32_t y, int32_t eu, uint32_t e0, uint32_t e1) {
     const uint32_t cs = pg.g.cs, se0 = r.sxe + (e0 - r.dxe), spx0 = cs == 1 ? se0 : se0 / cs;
@@ -200,12 +241,44 @@ template <uint32_t MB, uint32_t ES>
 using PasteUnits = PasteMaskUnits<kPasteCopies<MB, ES> + 1>;
 static_assert(sizeof(PasteUnits<1, 1>) == 32 && sizeof(PasteUnits<1, 4>) == 32 && sizeof(PasteUnits<2, 2>) == 32 && sizeof(PasteUnits<2, 1>) == 48,
               "a third unit only for 2-byte masks under 1-byte elements");
+static_assert(sizeof(PasteUnits<3, 1>) == 64 && sizeof(PasteUnits<3, 2>) == 48 && sizeof(PasteUnits<3, 4>) == 32 && sizeof(PasteUnits<4, 1>) == 80 &&
+                  sizeof(PasteUnits<4, 2>) == 48 && sizeof(PasteUnits<4, 4>) == 32,
+              "the wide masks: up to 48 or 64 mask bytes of a unit's pixels, in one to four or one to five aligned units");
 template <uint32_t N, class Mem>
 LLMI_HD inline void paste_load_units(const PasteFetch& f, PasteMaskUnits<N>& m, Mem& mem) {  // (into units of zeros)
     m.u[0] = mem.load16(f.a);
     if (f.units > 1) m.u[1] = mem.load16(f.a + 16);
     if constexpr (N > 2)
         if (f.units > 2) m.u[2] = mem.load16(f.a + 32);
+    if constexpr (N > 3)
+        if (f.units > 3) m.u[3] = mem.load16(f.a + 48);
+    if constexpr (N > 4)
+        if (f.units > 4) m.u[4] = mem.load16(f.a + 64);
+}
+// MB 3: pixel j of the shifted copies is bytes 3 j .. 3 j + 2 of the array they form, and may straddle two words or two copies (j a
+// constant after unrolling: the words are never indexed by a variable)
+template <uint32_t COPIES>
+LLMI_CHUNK_FN uint32_t paste_px3(const ComposeChunk (&mv)[COPIES], uint32_t j) {
+    const uint32_t b = 3 * j, k = b >> 2, sh = 8 * (b & 3);
+    uint32_t v = mv[k >> 2].w[k & 3] >> sh;
+    if (sh > 8) v |= mv[(k + 1) >> 2].w[(k + 1) & 3] << (32 - sh);
+    return v & 0xFFFFFFu;
+}
+
+// pixel j of the shifted copies, and its place in copies of zeros
+template <uint32_t MB, uint32_t COPIES>
+LLMI_CHUNK_FN uint32_t paste_px(const ComposeChunk (&mv)[COPIES], uint32_t j) {
+    if constexpr (MB == 3) return paste_px3(mv, j);
+    else return chunk_get<MB>(mv[j / (16 / MB)].w, j % (16 / MB));
+}
+template <uint32_t MB, uint32_t COPIES>
+LLMI_CHUNK_FN void paste_px_put(ComposeChunk (&mv)[COPIES], uint32_t j, uint32_t bits) {
+    if constexpr (MB == 3) {
+        LLMI_UNROLL
+        for (uint32_t q = 0; q < 3; ++q) chunk_or<1>(mv[(3 * j + q) >> 4].w, (3 * j + q) & 15u, (bits >> (8 * q)) & 0xFFu);
+    } else {
+        chunk_or<MB>(mv[j / (16 / MB)].w, j % (16 / MB), bits);
+    }
 }
 
 // The elements of [e0, e1) of the unit that r selects, as a mask with bit p for the unit's element p: the mask pixels of their pixels
@@ -213,7 +286,7 @@ LLMI_HD inline void paste_load_units(const PasteFetch& f, PasteMaskUnits<N>& m, 
 // sticks out of the mask batch; each pixel against the id set; a pixel's bit to its elements (c of them in HWC, one in CHW).
 template <uint32_t MB, uint32_t ES, class Mem>
 LLMI_HD inline uint32_t paste_selected(const PasteGeom& pg, const PasteRec<MB>& r, const PasteFetch& f, bool have, const PasteUnits<MB, ES>& pre, Mem& mem) {
-    constexpr uint32_t PER = 16 / ES, COPIES = kPasteCopies<MB, ES>, PPC = 16 / MB;  // (pixels per copy)
+    constexpr uint32_t PER = 16 / ES, COPIES = kPasteCopies<MB, ES>;
     const uint32_t cs = pg.g.cs;
     ComposeChunk mv[COPIES];
     LLMI_UNROLL
@@ -227,11 +300,11 @@ LLMI_HD inline uint32_t paste_selected(const PasteGeom& pg, const PasteRec<MB>& 
     } else {  // at the first or the last bytes of the mask batch: the pixels that belong, one by one
         LLMI_UNROLL
         for (uint32_t j = 0; j < PER; ++j)
-            if (j < f.npx) chunk_or<MB>(mv[j / PPC].w, j % PPC, mem.template load_el<MB>(f.at + MB * uint64_t(j)));
+            if (j < f.npx) paste_px_put<MB>(mv, j, mem.template load_el<MB>(f.at + MB * uint64_t(j)));
     }
     uint32_t selpx = 0;
     LLMI_UNROLL
-    for (uint32_t j = 0; j < PER; ++j) selpx |= uint32_t(paste_id_set<MB>(r, chunk_get<MB>(mv[j / PPC].w, j % PPC))) << j;
+    for (uint32_t j = 0; j < PER; ++j) selpx |= uint32_t(paste_id_set<MB>(r, paste_px<MB>(mv, j))) << j;
     const uint32_t span = compose_span(f.p0, f.p0 + f.n_el);
     if (cs == 1) return (selpx << f.p0) & span;
     uint32_t em = 0, j = 0, ph = f.ph0;
@@ -249,6 +322,19 @@ template <uint32_t ES>
 LLMI_HD inline ComposeChunk paste_value_unit(uint32_t bits) {
     const uint32_t w = ES == 4 ? bits : ES == 2 ? (bits & 0xFFFFu) * 0x00010001u : (bits & 0xFFu) * 0x01010101u;
     return ComposeChunk{{w, w, w, w}};
+}
+
+// a VALUE_PIXEL piece's unit (U8 HWC, the wide call): element p of the unit is channel (eu + p) mod cs of its pixel and takes that byte
+// of the value; eu is negative for a unit that begins before its row
+LLMI_HD inline ComposeChunk paste_value_pixel_unit(uint32_t bits, uint32_t cs, int32_t eu) {
+    ComposeChunk v{{0u, 0u, 0u, 0u}};
+    uint32_t ph = uint32_t((eu % int32_t(cs) + int32_t(cs)) % int32_t(cs));
+    LLMI_UNROLL
+    for (uint32_t p = 0; p < 16; ++p) {
+        chunk_or<1>(v.w, p, (bits >> (8 * ph)) & 0xFFu);
+        ph = ph + 1 == cs ? 0 : ph + 1;
+    }
+    return v;
 }
 
 // ... and the walk.  The list from `hit` down: every piece that reaches elements nobody has claimed yet is asked which of them it
@@ -275,6 +361,8 @@ LLMI_HD inline void paste_finish(const PasteGeom& pg, const PasteWork<MB>& k, co
         ComposeChunk v{{0u, 0u, 0u, 0u}};
         if (r.r.flags & LLCOMP_MI_PASTE_VALUE) {
             v = paste_value_unit<ES>(r.value);
+            if constexpr (MB >= 3 && ES == 1)
+                if (r.r.flags & LLCOMP_MI_PASTE_VALUE_PIXEL) v = paste_value_pixel_unit(r.value, g.cs, t.eu);
         } else {
             const uint64_t s = compose_src_of_unit(g, ES, r.r, k.pl, t.y, t.eu);
             if (compose_src_units_inside(g, s)) {
