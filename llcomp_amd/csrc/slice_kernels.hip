@@ -1207,7 +1207,9 @@ __device__ __forceinline__ bool dec_residual(RangeDec& d, Bank& bank, const entr
 
 // One sample: fast path first, checked replay when the window ran dry (or the fast path saw nonsense because of it).
 // `hot` (wave-uniform, in / out): most lanes had a non-zero residual last time -- the entries of slots 1..7 are requested up front.
-template <bool INLDS>
+// SET (the hand-written block only): which of its two fixed low : copy register pairs the sample leaves its `low` in; consecutive
+// samples alternate, so the low a sample reads is never in the pair it writes.
+template <bool INLDS, int SET = 0>
 __device__ __forceinline__ bool dec_sample(RangeDec& d, Bank& bank, const entry_t* tab, uint32_t& hot, bool replay_always,
                                            uint32_t& v) {
 #if LLMI_ASM_DEC
@@ -1215,13 +1217,14 @@ __device__ __forceinline__ bool dec_sample(RangeDec& d, Bank& bank, const entry_
         // The fast path of the 1-row-slice kernels is one hand-written block (dec_rows_asm.hpp).  It reads low, range, the window and
         // the bank words and writes none of them: the coder's state behind the sample arrives in registers of its own, so what the
         // block read IS the rollback snapshot -- nothing is copied per sample, and the registers of two consecutive samples simply
-        // swap roles (the bulk loops below code two samples per turn for that).
-        uint32_t low, range, left;
-        unsigned long long win;
-        dec_rows_sample_asm(d.low, d.range, d.win, low, range, win, bank.w[0], bank.w[1], bank.w[2], bank.w[3], lds_address(bank.lds), hot, v,
-                            left);
+        // swap roles (the bulk loops below code two samples per turn for that).  low arrives as the high half of a pair whose low
+        // half is what the sample left of its private copy of the window's next three bytes.
+        uint32_t range;
+        unsigned long long low_left, win;
+        dec_rows_sample_asm<SET>(d.low, d.range, d.win, low_left, range, win, bank.w[0], bank.w[1], bank.w[2], bank.w[3], lds_address(bank.lds),
+                                 hot, v);
         // left == 0: more than three bytes wanted, or an invalid exponent -- replayed, and the verdict is formed there
-        if (__builtin_expect(left == 0 || replay_always, 0)) {
+        if (__builtin_expect(uint32_t(low_left) == 0 || replay_always, 0)) {
             ++d.replays;
             // the fast path has already stored new states: put the old ones back
             reinterpret_cast<uint32_t*>(bank.lds)[0] = bank.w[0];
@@ -1230,15 +1233,13 @@ __device__ __forceinline__ bool dec_sample(RangeDec& d, Bank& bank, const entry_
             reinterpret_cast<uint32_t*>(bank.lds)[192] = bank.w[3];
             // The replay starts from the untouched inputs, IN the registers of the block's outputs (the copy is written out, or
             // hipcc replays in place and has the fast path of every sample copy its results back instead).
-            asm("v_mov_b32_e32 %0, %3\n\tv_mov_b32_e32 %1, %4\n\tv_mov_b64_e32 %2, %5"
-                : "+v"(low), "+v"(range), "+v"(win)
-                : "v"(d.low), "v"(d.range), "v"(d.win));
-            d.low = low;
+            dec_rows_replay_inputs<SET>(d.low, d.range, d.win, low_left, range, win);
+            d.low = uint32_t(low_left >> 32);
             d.range = range;
             d.win = win;
             return dec_residual<false, true, true>(d, bank, tab, v);
         }
-        d.low = low;
+        d.low = uint32_t(low_left >> 32);
         d.range = range;
         d.win = win;
         return true;
@@ -1360,9 +1361,10 @@ __global__ __launch_bounds__(64, ROWS && NCH == 1 ? 8 : 1) void k_decode_slices(
         // reads stays inside its own stream and slice, and the call reports the error) -- so the loop has no per-lane exit,
         // and when all slices of the wavefront are equally wide it runs under a scalar counter with no per-lane tests at all.
         bool bad = false;
-        auto pixel = [&](auto model, auto start) {
+        auto pixel = [&](auto model, auto start, auto set) {
             constexpr int MODEL = decltype(model)::value;
             constexpr bool START = decltype(start)::value;
+            constexpr int SET = decltype(set)::value;  // the register pair the pixel's first sample leaves `low` in (dec_sample)
 #pragma unroll
             for (int k = 0; k < NCH; ++k) {
                 if (window_low(d)) dec_append(d);
@@ -1384,7 +1386,10 @@ __global__ __launch_bounds__(64, ROWS && NCH == 1 ? 8 : 1) void k_decode_slices(
                 uint32_t* bp = reinterpret_cast<uint32_t*>(bank0 + bofs);
                 Bank bank{{bp[0], bp[64], bp[128], bp[192]}, reinterpret_cast<uint8_t*>(bp)};
                 uint32_t v = 0;
-                if (!dec_sample<true>(d, bank, tab, hot, replay_always, v)) bad = true;
+                // (k is a constant once the loop is unrolled: the samples of a pixel alternate between the block's two pairs)
+                const bool ok = ((SET + k) & 1) ? dec_sample<true, 1>(d, bank, tab, hot, replay_always, v)
+                                                : dec_sample<true, 0>(d, bank, tab, hot, replay_always, v);
+                if (!ok) bad = true;
                 if constexpr (MODEL != kModelSmall) v = (v ^ sg) - sg;
                 const int val = int(int16_t(uint32_t(lv) + v));
                 held_val = val;
@@ -1398,17 +1403,19 @@ __global__ __launch_bounds__(64, ROWS && NCH == 1 ? 8 : 1) void k_decode_slices(
         const uint32_t sw0 = __builtin_amdgcn_readfirstlane(r.sw);
         const uint32_t n_bulk = __builtin_amdgcn_ballot_w64(r.sw != sw0) == 0 ? sw0 : 0;
         uint32_t x = 1;
-        pixel(no_model, std::true_type{});  // (a slice has at least one pixel; L == l here: no difference under either model)
+        constexpr std::integral_constant<int, 0> set0{};
+        constexpr std::integral_constant<int, 1> set1{};
+        pixel(no_model, std::true_type{}, set0);  // (a slice has at least one pixel; L == l here: no difference under either model)
         constexpr std::integral_constant<int, SMALL ? kModelSmall : kModelLarge> model{};
         if constexpr (NCH == 1) {
             for (; x + 1 < n_bulk; x += 2) {
-                pixel(model, std::false_type{});
-                pixel(model, std::false_type{});
+                pixel(model, std::false_type{}, set1);
+                pixel(model, std::false_type{}, set0);
             }
         } else {  // (interleaved channels: a pixel is several samples already)
-            for (; x < n_bulk; ++x) pixel(model, std::false_type{});
+            for (; x < n_bulk; ++x) pixel(model, std::false_type{}, set0);
         }
-        for (; x < r.sw; ++x) pixel(model, std::false_type{});
+        for (; x < r.sw; ++x) pixel(model, std::false_type{}, set1);
         if (bad) atomicOr(status, kStBadExponent);
         asm volatile("global_store_short %0, %1, %2" : : "v"(store_ofs), "v"(held_val), "s"(gbase) : "memory");
         publish_count(counters, kCtrDecReplays, d.replays);
