@@ -894,8 +894,8 @@ uint32_t llcomp_mi_label_targets_max_planes(void);
  * (0, 0xFFFFFF, 0xFFFFFFFF); the lists' limits, the records, the values, the kinds and the output dtypes are those of the 16-bit calls.
  * BAD_ARGS: the 16-bit calls' cases; a map_bytes that is not 3 or 4; a listed id above 0xFFFFFF with map_bytes 3; a 4-byte map at an
  * address that is no multiple of 4.
- * NOT covered: 4-byte maps at addresses that are no multiples of 4, batches of 2^32 bytes and more (the arithmetic is 64-bit, the
- * sizes are not tested yet), and what the 16-bit calls do not cover.
+ * NOT covered: 4-byte maps at addresses that are no multiples of 4, and what the 16-bit calls do not cover.  Batches of 2^32 bytes
+ * and more, and samples of more than 2^31 pixels, are covered (the arithmetic is 64-bit; tests/test_gpu_large_wide_id_maps.py).
  * Batch copy-paste by wide ids (llcomp_mi_codec_paste_batch32 below) is "Batch copy-paste by 16-bit ids" word for word -- painter's
  * order, the last piece that selects a pixel gives it, what no piece selects stays and is not written, a dst element is written at
  * most once, 256 pieces per dst sample -- with mask the wide map above, map_bytes 3 or 4.  id_base is any 32-bit value (above 0xFFFFFF
