@@ -750,7 +750,8 @@ uint32_t llcomp_mi_compose_max_pieces_per_sample(void);
  * of 2^31 elements or more; a piece with dst >= n_dst or src >= n_src, with a source rectangle that leaves iw x ih or a dst rectangle
  * that leaves ow x oh, with flag bits above bit 0, with a value that is not 0 without VALUE, or with a bad value under VALUE; more than
  * llcomp_mi_paste_max_pieces_per_sample() = 256 pieces with w and h above 0 on one dst sample.
- * NOT covered: blended (alpha or Gaussian) paste borders, a src and dst of different dtype or layout, pieces that resample or mirror
+ * Blended pastes under a per-pixel alpha: "Batch alpha paste" below.
+ * NOT covered: Gaussian paste borders made from the ids, a src and dst of different dtype or layout, pieces that resample or mirror
  * (views do that at decode), a dst that overlaps its src, per-piece fills per channel.  More than 256 ids per map (16-bit id maps):
  * "Batch copy-paste by 16-bit ids" below. */
 #define LLCOMP_MI_PASTE_VALUE 1u
@@ -791,7 +792,7 @@ uint32_t llcomp_mi_paste_max_pieces_per_sample(void);
  * and for a 2-byte dtype with c == 1, the id maps are their own source -- that is how a 16-bit class or instance map is pasted by id.
  * BAD_ARGS: the cases of "Batch copy-paste" (but for its value), an id_base above 65535, a value_bits that is not 0 without VALUE or
  * that has bits above the element.
- * Ids of 3 or 4 bytes (COCO panoptic's RGB ids): "Wide id maps" below.  NOT covered: maps at odd addresses, blended borders, and what
+ * Ids of 3 or 4 bytes (COCO panoptic's RGB ids): "Wide id maps" below.  NOT covered: maps at odd addresses, borders blended from the ids ("Batch alpha paste" below blends under an alpha batch), and what
  * "Batch copy-paste" does not cover. */
 typedef struct llcomp_mi_paste_piece16 {
     uint32_t dst, src;
@@ -934,6 +935,56 @@ typedef struct llcomp_mi_label_targets32 {
 } llcomp_mi_label_targets32;                        /* 64 bytes, ids at 32 */
 int llcomp_mi_label_targets32_reference(const void* maps, uint32_t n, uint32_t ow, uint32_t oh, const llcomp_mi_label_targets32* targets, void* out);
 uint64_t llcomp_mi_label_targets32_out_bytes(uint32_t n, uint32_t ow, uint32_t oh, const llcomp_mi_label_targets32* targets);
+/* Batch alpha paste (llcomp_mi_codec_alpha_paste_batch below): PIL's Image.paste(src, box, mask), Image.composite and
+ * Image.alpha_composite on dense batches, byte for byte -- the step of a compositing pipeline that blends per pixel: a sprite or an
+ * instance through a soft matte, a Copy-Paste with soft borders, a watermark.  src is n_src samples of iw x ih and dst n_dst samples of
+ * ow x oh, both of c channels in one dtype (U8, F16, BF16, F32) and one layout, aligned to the element and to nothing more.  alpha is
+ * n_src samples of ih x iw pixels of alpha_px_bytes (1..4) bytes each, dense, at ANY byte address; a pixel's alpha is byte alpha_byte
+ * (< alpha_px_bytes) of it, a byte for every dtype of the batches: a plain matte has alpha_px_bytes 1; the A channel of a U8 HWC RGBA
+ * batch, which may be src itself, alpha_px_bytes 4 and alpha_byte 3.  dst overlaps neither src nor alpha; neither is written.
+ * A piece is a rectangle as in the paste calls, (sx, sy) addressing src AND alpha.  The pieces of a dst sample apply in the list's
+ * order, each onto what the pieces before it left: painter's order forwards.  At most 256 pieces with w and h above 0 on one dst sample.
+ *   LLCOMP_MI_ALPHA_VALUE        the source element is value_bits, the element's bits, in every channel (src may then be NULL when
+ *                                no other piece reads it)
+ *   LLCOMP_MI_ALPHA_VALUE_PIXEL  with VALUE, U8 HWC with c <= 4: channel ch takes byte ch of value_bits -- PIL's paste of a colour
+ *   LLCOMP_MI_ALPHA_OVER         the OVER rule
+ * The PASTE rule (the default), d and s the dst and src elements, m the pixel's alpha byte:
+ *   m == 0: the element keeps its bits; m == 255: it takes s's bits, whatever d was;
+ *   U8 otherwise: t = d * (255 - m) + s * m + 128, out = ((t >> 8) + t) >> 8  (PIL's paste with an L mask, Image.composite)
+ *   F16, BF16, F32 otherwise: a = float(m) / 255.0f, out = rd(f32(d * (1.0f - a)) + f32(s * a)): every operation rounded in binary32
+ *     by itself, no fused multiply-add, one rounding to the dtype, a NaN the dtype's one quiet NaN -- torch's
+ *     (d * (1 - a) + s * a).to(dtype) with a = alpha.float() / 255 on the CPU
+ * The OVER rule (Image.alpha_composite): U8 HWC with c == 4, src and dst aligned to 4 bytes; the alpha is src's own channel 3 and the
+ * alpha argument is not read for such a piece; not with VALUE.  Per pixel with sa, da in 32-bit unsigned arithmetic: sa == 0: the
+ * pixel stays; otherwise outa255 = sa * 255 + da * (255 - sa), coef1 = sa * 255 * 255 * 128 / outa255, coef2 = 255 * 128 - coef1; a
+ * colour channel: t = s * coef1 + d * coef2 + (0x80 << 7), out = (((t >> 8) + t) >> 8) >> 7; alpha: t = outa255 + 0x80,
+ * out = ((t >> 8) + t) >> 8.
+ * BAD_ARGS: the paste calls' cases; alpha_px_bytes outside 1..4; alpha_byte >= alpha_px_bytes; unknown flag bits; OVER or VALUE_PIXEL
+ * on a shape it does not take, OVER with VALUE, VALUE_PIXEL without it; value_bits with bytes at or above the element's size, for
+ * VALUE_PIXEL at or above c, or without VALUE; a NULL alpha with a piece that is not OVER, a NULL src with one that is not VALUE.
+ * NOT covered: a src with another channel count than dst (an RGBA sprite onto an RGB canvas in one call), float alpha maps, a
+ * per-piece opacity, making a feathered matte from an id selection (the step towards Copy-Paste with Gaussian borders), Image.blend,
+ * and PIL's special case of a COLOUR pasted onto an RGBA pixel whose alpha is 0 (there PIL replaces the colour channels whatever the
+ * mask says; a VALUE_PIXEL piece follows the PASTE rule in every channel, which is PIL's result on L and RGB). */
+#define LLCOMP_MI_ALPHA_VALUE 1u
+#define LLCOMP_MI_ALPHA_VALUE_PIXEL 2u
+#define LLCOMP_MI_ALPHA_OVER 4u
+typedef struct llcomp_mi_alpha_piece {
+    uint32_t dst, src;
+    uint32_t dx, dy, sx, sy, w, h;
+    uint32_t flags;        /* LLCOMP_MI_ALPHA_* */
+    uint32_t value_bits;   /* with VALUE; otherwise 0 */
+} llcomp_mi_alpha_piece;   /* 40 bytes */
+/* The rule on host memory: out = dst_in with the pieces applied (out may be dst_in). */
+int llcomp_mi_alpha_paste_reference(const void* src, const void* alpha, uint32_t alpha_px_bytes, uint32_t alpha_byte, uint32_t n_src, uint32_t iw,
+                                    uint32_t ih, const void* dst_in, uint32_t n_dst, uint32_t ow, uint32_t oh, uint32_t c, uint32_t dtype,
+                                    uint32_t layout, const llcomp_mi_alpha_piece* pieces, uint32_t n_pieces, void* out);
+/* What a call does, as llcomp_mi_paste32_plan: the dst samples with a piece that is not ignored, samples[*n_samples]; where every
+ * sample's pieces begin, first[*n_samples + 1]; the pieces' indices by dst sample in the call's order, order[first[*n_samples]]; and
+ * the workgroups of the kernel.  samples, first and order may be NULL. */
+int llcomp_mi_alpha_paste_plan(uint32_t alpha_px_bytes, uint32_t alpha_byte, uint32_t n_src, uint32_t iw, uint32_t ih, uint32_t n_dst, uint32_t ow,
+                               uint32_t oh, uint32_t c, uint32_t dtype, uint32_t layout, const llcomp_mi_alpha_piece* pieces, uint32_t n_pieces,
+                               uint32_t* samples, uint32_t* first, uint32_t* order, uint32_t* n_samples, uint64_t* n_workgroups);
 uint32_t llcomp_mi_slice_count(uint32_t w, uint32_t h, uint32_t c, uint32_t tile_w, uint32_t tile_h, uint32_t planar);
 /* Slice width for one-row slices (tile_h = 1) when `frames` frames are coded per call: the widest slice (64..480 pixels) that
  * still keeps about four wavefronts per SIMD busy.  A call that codes few frames is latency-bound with wide slices; this
@@ -1396,6 +1447,22 @@ int llcomp_mi_codec_label_targets32(llcomp_mi_codec* codec, const void* d_maps, 
                                     const llcomp_mi_label_targets32* targets, void* d_out, void* stream);
 /* llcomp_mi_codec_workspace_bytes + 4 * (3 * n + 2) + 8 * total_ids, the table of a call.  0 for a NULL codec. */
 uint64_t llcomp_mi_codec_label_targets32_workspace_bytes(const llcomp_mi_codec* codec, uint32_t n, uint32_t total_ids);
+/* Batch alpha paste (the rule: "Batch alpha paste" above) on device memory, in place on d_dst, asynchronous on `stream`, in ONE kernel
+ * with no scratch in device memory: k_alpha_paste<AB, DT> on the composition's tiles and 16-byte units of dst memory.  A workgroup
+ * filters its sample's pieces against its tile into a short list in LDS (36-byte records, 9 KiB, and the 256 weights); a thread loads
+ * its unit of dst once, walks the list forwards -- per piece the alpha bytes of the unit's pixels as shifted copies of the aligned
+ * alpha units that hold them, the src unit as one shifted copy, the blend -- and stores the unit once: 16 bytes where the pieces
+ * reach all of its elements, the reached elements one by one otherwise.  No byte outside dst is written, none outside src or alpha
+ * read; a dst element that no piece reaches is not written, one whose alphas are all 0 keeps its bits.  Calls with an OVER piece run an
+ * instantiation of their own, so that the division costs the others no register.  The table travels in a buffer of its own, allocated
+ * by the first such call.  A call without a piece that has w and h queues nothing.
+ * BAD_ARGS, nothing queued and nothing written: a NULL codec or d_dst, the reference's cases.  NOMEM before anything is queued. */
+int llcomp_mi_codec_alpha_paste_batch(llcomp_mi_codec* codec, const void* d_src, const void* d_alpha, uint32_t alpha_px_bytes, uint32_t alpha_byte,
+                                      uint32_t n_src, uint32_t iw, uint32_t ih, void* d_dst, uint32_t n_dst, uint32_t ow, uint32_t oh, uint32_t dtype,
+                                      uint32_t layout, const llcomp_mi_alpha_piece* pieces, uint32_t n_pieces, void* stream);
+/* The bound on llcomp_mi_codec_allocated_bytes with such calls of up to n_dst dst samples and n_pieces pieces among the codec's calls:
+ * llcomp_mi_codec_workspace_bytes + 12 * n_dst + 36 * n_pieces, the table of a call.  0 for a NULL codec. */
+uint64_t llcomp_mi_codec_alpha_paste_workspace_bytes(const llcomp_mi_codec* codec, uint32_t n_dst, uint32_t n_pieces);
 /* Stage-A only (context + prediction model), for tests and profiling: d_sym u32[frames*h*w*c],
  * low 16 bits = folded context (0..7925), high 16 bits = folded residual (two's complement). */
 int llcomp_mi_codec_model(llcomp_mi_codec* codec, const void* d_px, void* d_sym, void* stream);

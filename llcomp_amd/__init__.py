@@ -47,6 +47,9 @@ with ctypes and keeps the reference's names and error behaviour:
         the caller lists per sample, in 16-bit id maps: Cityscapes, Mapillary Vistas, ADE20K instance ids)
     PastePiece32 / PASTE_VALUE_PIXEL / paste_pieces32 / paste32_plan / paste32_reference / Codec.paste_batch32 /
         Codec.paste32_workspace_bytes  (the copy-paste selected by id maps of 3 or 4 bytes per pixel; VALUE_PIXEL writes a 3-byte id)
+    AlphaPiece / ALPHA_VALUE / ALPHA_VALUE_PIXEL / ALPHA_OVER / alpha_pieces / alpha_paste_plan / alpha_paste_reference /
+        Codec.alpha_paste_batch / Codec.alpha_paste_workspace_bytes  (pieces blended under a per-pixel alpha byte: PIL's paste with a
+        mask, Image.composite and Image.alpha_composite, byte for byte; floats as torch's d * (1 - a) + s * a)
     label_boxes32_reference / label_targets32_reference / Codec.label_boxes32 / Codec.label_targets32 / their _workspace_bytes  (both
         for id maps of 3 or 4 bytes per pixel: COCO panoptic's RGB ids, int32 class * 1000 + instance maps)
     TARGET_* / label_targets_reference / label_targets_segment / label_targets_max_planes / Codec.label_targets /
@@ -73,6 +76,7 @@ from ._lib import PhotoOp as _PhotoOp, PhotoChain as _PhotoChain, PhotoGroup as 
 from ._lib import ComposePiece as _ComposePiece
 from ._lib import PastePiece as _PastePiece
 from ._lib import PastePiece16, PastePiece32
+from ._lib import AlphaPiece
 from ._lib import MixSample as _MixSample
 
 EXT = ".llcomp"
@@ -1042,6 +1046,77 @@ def paste32_reference(src, mask, dst, pieces, layout="chw", dtype=None):
     out = np.empty_like(d)
     _check(_lib.load().llcomp_mi_paste32_reference(s.ctypes.data, m.ctypes.data, mb, n_src, iw, ih, d.ctypes.data, n_dst, ow, oh, c, code, lay, recs,
                                                    len(recs), out.ctypes.data))
+    return out
+
+
+# Codec.alpha_paste_batch (LLCOMP_MI_ALPHA_*): a piece's flags
+ALPHA_VALUE = 1
+ALPHA_VALUE_PIXEL = 2
+ALPHA_OVER = 4
+
+
+def alpha_pieces(records):
+    """The pieces of an alpha_paste_batch call (llcomp_mi_alpha_piece) as a ctypes array: every record a tuple (dst, src, dx, dy, sx,
+    sy, w, h[, flags[, value_bits]]).  flags: 0 for PIL's paste under the alpha, ALPHA_VALUE for value_bits (the element's bits) as the
+    source in every channel, ALPHA_VALUE | ALPHA_VALUE_PIXEL for byte ch of value_bits in channel ch (uint8 "hwc", c <= 4: PIL's paste
+    of a colour), ALPHA_OVER for Image.alpha_composite.  The pieces apply in order.  The library checks the rest."""
+    if isinstance(records, C.Array) and records._type_ is AlphaPiece:
+        return records
+    rows = list(records)
+    arr = (AlphaPiece * len(rows))()
+    for i, r in enumerate(rows):
+        vals = list(r) if isinstance(r, (tuple, list)) else []
+        if len(vals) not in (8, 9, 10):
+            raise LlcompError(BAD_ARGS, f"a piece is (dst, src, dx, dy, sx, sy, w, h[, flags[, value_bits]]), got {r!r}")
+        nums = [int(v) for v in vals] + [0] * (10 - len(vals))
+        if min(nums) < 0 or max(nums) > 0xFFFFFFFF:
+            raise LlcompError(BAD_ARGS, f"a piece takes unsigned values, got {r!r}")
+        for name, v in zip(("dst", "src", "dx", "dy", "sx", "sy", "w", "h", "flags", "value_bits"), nums):
+            setattr(arr[i], name, v)
+    return arr
+
+
+def alpha_paste_plan(alpha_px_bytes, alpha_byte, n_src, iw, ih, n_dst, ow, oh, c, pieces, dtype="float32", layout="chw"):
+    """What an alpha_paste_batch call does (llcomp_mi_alpha_paste_plan, host only) -> (samples, first, order, n_workgroups), as
+    paste_plan: the ignored pieces are those with w or h of 0."""
+    recs = alpha_pieces(pieces)
+    n_dst = int(n_dst)
+    samples, first, order = np.zeros(max(n_dst, 1), np.uint32), np.zeros(max(n_dst, 1) + 1, np.uint32), np.zeros(max(len(recs), 1), np.uint32)
+    ns, nw = C.c_uint32(0), C.c_uint64(0)
+    u32p = C.POINTER(C.c_uint32)
+    _check(_lib.load().llcomp_mi_alpha_paste_plan(int(alpha_px_bytes), int(alpha_byte), int(n_src), int(iw), int(ih), n_dst, int(ow), int(oh), int(c),
+                                                  _dtype_code(dtype), _layout_code(layout), recs, len(recs), samples.ctypes.data_as(u32p),
+                                                  first.ctypes.data_as(u32p), order.ctypes.data_as(u32p), C.byref(ns), C.byref(nw)))
+    n = ns.value
+    return samples[:n].copy(), first[:n + 1].copy(), order[:int(first[n])].copy(), int(nw.value)
+
+
+def alpha_paste_reference(src, alpha, dst, pieces, layout="chw", dtype=None, alpha_byte=0):
+    """The rule of the batch alpha paste on host arrays (llcomp_mi_alpha_paste_reference): src and dst as paste_reference's (src None
+    when every piece is a VALUE piece); alpha uint8 [n_src, ih, iw] or [n_src, ih, iw, alpha_px_bytes] with a pixel's alpha in byte
+    alpha_byte -- or src itself, a uint8 "hwc" batch with c <= 4 (RGBA under its own A: alpha_byte 3) -- or None when every piece is an
+    OVER piece -> the blended dst batch, a new array."""
+    d, code, lay, n_dst, c, oh, ow = _batch_array(dst, dtype, layout)
+    s = None if src is None else np.ascontiguousarray(src)
+    if s is not None and (s.ndim != 4 or s.dtype != d.dtype or (s.shape[1] if lay == LAYOUT_CHW else s.shape[3]) != c):
+        raise LlcompError(BAD_ARGS, f"src is a 4-D batch of dst's type and channels, got {s.dtype} of shape {s.shape}")
+    m = s if alpha is src else None if alpha is None else np.ascontiguousarray(alpha)
+    if m is not None and (m.dtype != np.uint8 or m.ndim not in (3, 4)):
+        raise LlcompError(BAD_ARGS, f"alpha is uint8 [n_src, ih, iw] or [n_src, ih, iw, alpha_px_bytes], got {m.dtype} of shape {m.shape}")
+    if s is not None:
+        n_src = s.shape[0]
+        ih, iw = s.shape[2:] if lay == LAYOUT_CHW else s.shape[1:3]
+    elif m is not None:
+        n_src, ih, iw = m.shape[:3]
+    else:
+        raise LlcompError(BAD_ARGS, "a call reads src or alpha")
+    apx = 1 if m is None else m.nbytes // max(n_src * ih * iw, 1)
+    if m is not None and m.nbytes != apx * n_src * ih * iw:
+        raise LlcompError(BAD_ARGS, f"alpha is n_src x ih x iw pixels, got shape {m.shape}")
+    recs = alpha_pieces(pieces)
+    out = np.empty_like(d)
+    _check(_lib.load().llcomp_mi_alpha_paste_reference(None if s is None else s.ctypes.data, None if m is None else m.ctypes.data, apx, int(alpha_byte),
+                                                       n_src, iw, ih, d.ctypes.data, n_dst, ow, oh, c, code, lay, recs, len(recs), out.ctypes.data))
     return out
 
 
@@ -2294,6 +2369,24 @@ class Codec:
         """the bound on .allocated_bytes() with paste_batch32 calls of up to n_dst dst samples and n_pieces pieces
         (llcomp_mi_codec_paste32_workspace_bytes)"""
         return self._L.llcomp_mi_codec_paste32_workspace_bytes(self._h, int(n_dst), int(n_pieces))
+
+    def alpha_paste_batch(self, d_src, d_alpha, alpha_px_bytes, alpha_byte, n_src, iw, ih, d_dst, n_dst, ow, oh, pieces, dtype="float32", layout="chw",
+                          stream=0):
+        """Pieces of one dense batch blended into another under a per-pixel alpha byte, in place (llcomp_mi_codec_alpha_paste_batch):
+        PIL's paste with a mask, Image.composite and, with ALPHA_OVER pieces, Image.alpha_composite.  d_src, n_src samples of iw x ih
+        (None when every piece is a VALUE piece); d_alpha, n_src x ih x iw pixels of alpha_px_bytes (1..4) bytes at any address, a
+        pixel's alpha its byte alpha_byte (it may be d_src for uint8 "hwc" with c = alpha_px_bytes; None when every piece is OVER);
+        d_dst, n_dst samples of ow x oh; src and dst of the codec's channels in the same dtype and layout; pieces from alpha_pieces(),
+        or records for it, applied in order.  Asynchronous on `stream`."""
+        recs = alpha_pieces(pieces)
+        _check(self._L.llcomp_mi_codec_alpha_paste_batch(self._h, d_src, d_alpha, int(alpha_px_bytes), int(alpha_byte), int(n_src), int(iw), int(ih),
+                                                         d_dst, int(n_dst), int(ow), int(oh), _dtype_code(dtype), _layout_code(layout), recs, len(recs),
+                                                         stream))
+
+    def alpha_paste_workspace_bytes(self, n_dst, n_pieces):
+        """the bound on .allocated_bytes() with alpha_paste_batch calls of up to n_dst dst samples and n_pieces pieces
+        (llcomp_mi_codec_alpha_paste_workspace_bytes)"""
+        return self._L.llcomp_mi_codec_alpha_paste_workspace_bytes(self._h, int(n_dst), int(n_pieces))
 
     def paste16_workspace_bytes(self, n_dst, n_pieces):
         """the bound on .allocated_bytes() with paste_batch16 calls of up to n_dst dst samples and n_pieces pieces

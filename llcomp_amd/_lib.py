@@ -67,6 +67,8 @@ SYMBOLS = [
     "llcomp_mi_label_targets32_reference", "llcomp_mi_label_targets32_out_bytes", "llcomp_mi_codec_label_targets32",
     "llcomp_mi_codec_label_targets32_workspace_bytes",
     "llcomp_mi_paste32_reference", "llcomp_mi_paste32_plan", "llcomp_mi_codec_paste_batch32", "llcomp_mi_codec_paste32_workspace_bytes",
+    "llcomp_mi_alpha_paste_reference", "llcomp_mi_alpha_paste_plan", "llcomp_mi_codec_alpha_paste_batch",
+    "llcomp_mi_codec_alpha_paste_workspace_bytes",
 ]
 
 u8p = C.POINTER(C.c_uint8)
@@ -161,6 +163,12 @@ class PastePiece16(C.Structure):
 
 class PastePiece32(PastePiece16):
     """llcomp_mi_paste_piece32 (include/llcomp_mi.h): the same 76 bytes, id_base any 32-bit value, flags bit 1 VALUE_PIXEL"""
+
+
+class AlphaPiece(C.Structure):
+    """llcomp_mi_alpha_piece (include/llcomp_mi.h): 40 bytes"""
+    _fields_ = [("dst", C.c_uint32), ("src", C.c_uint32), ("dx", C.c_uint32), ("dy", C.c_uint32), ("sx", C.c_uint32), ("sy", C.c_uint32),
+                ("w", C.c_uint32), ("h", C.c_uint32), ("flags", C.c_uint32), ("value_bits", C.c_uint32)]
 
 
 class PastePiece(C.Structure):
@@ -637,6 +645,16 @@ def load():
         L.llcomp_mi_codec_paste_batch32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p] + [C.c_uint32] * 5 + [recs32, C.c_uint32, C.c_void_p]
         L.llcomp_mi_codec_paste32_workspace_bytes.restype = C.c_uint64
         L.llcomp_mi_codec_paste32_workspace_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+    if "LLCOMP_MI_LIB" not in os.environ or hasattr(L, "llcomp_mi_alpha_paste_reference"):  # batch alpha paste
+        arecs, u32p = C.POINTER(AlphaPiece), C.POINTER(C.c_uint32)
+        L.llcomp_mi_alpha_paste_reference.restype = C.c_int
+        L.llcomp_mi_alpha_paste_reference.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 5 + [C.c_void_p] + [C.c_uint32] * 6 + [arecs, C.c_uint32, C.c_void_p]
+        L.llcomp_mi_alpha_paste_plan.restype = C.c_int
+        L.llcomp_mi_alpha_paste_plan.argtypes = [C.c_uint32] * 11 + [arecs, C.c_uint32, u32p, u32p, u32p, u32p, C.POINTER(C.c_uint64)]
+        L.llcomp_mi_codec_alpha_paste_batch.restype = C.c_int
+        L.llcomp_mi_codec_alpha_paste_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_uint32] * 5 + [C.c_void_p] + [C.c_uint32] * 5 + [arecs, C.c_uint32, C.c_void_p]
+        L.llcomp_mi_codec_alpha_paste_workspace_bytes.restype = C.c_uint64
+        L.llcomp_mi_codec_alpha_paste_workspace_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
     if "LLCOMP_MI_LIB" not in os.environ and L.llcomp_mi_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {L.llcomp_mi_abi_version()}, this binding was written for {ABI_VERSION}: rebuild the library")
     _lib = L

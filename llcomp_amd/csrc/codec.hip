@@ -26,6 +26,8 @@
 #include "label_targets.hpp"
 #include "orient.hpp"
 #include "orient_rule.hpp"
+#include "alpha.hpp"
+#include "alpha_rule.hpp"
 #include "paste.hpp"
 #include "paste_rule.hpp"
 #include "photo.hpp"
@@ -921,6 +923,7 @@ void codec_release(llcomp_mi_codec* k) {
     dev_free(k->d_compose_tab, k->done);
     dev_free(k->d_paste_tab, k->done);
     dev_free(k->d_paste16_tab, k->done);
+    dev_free(k->d_alpha_tab, k->done);
     dev_free(k->d_label16_tab, k->done);
     dev_free(k->d_target_tab, k->done);
     dev_free(k->d_upd_goff, k->done);
@@ -1729,6 +1732,41 @@ uint64_t llcomp_mi_codec_paste32_workspace_bytes(const llcomp_mi_codec* k, uint3
     return k->workspace_bytes + paste_table_bound<4>(n_dst, n_pieces);
 }
 
+// Batch alpha paste (DESIGN.md "Batch alpha paste"): alpha_plan.hpp's checks, the copy-paste's plan and the table through the call's own
+// table buffer, which the first such call allocates.  A call without a piece that has w and h queues nothing.
+int llcomp_mi_codec_alpha_paste_batch(llcomp_mi_codec* k, const void* d_src, const void* d_alpha, uint32_t alpha_px_bytes, uint32_t alpha_byte, uint32_t n_src,
+                                      uint32_t iw, uint32_t ih, void* d_dst, uint32_t n_dst, uint32_t ow, uint32_t oh, uint32_t dtype, uint32_t layout,
+                                      const llcomp_mi_alpha_piece* pieces, uint32_t n_pieces, void* stream) {
+    if (!k || !d_dst) return LLCOMP_MI_BAD_ARGS;
+    const uint32_t c = k->g.c;
+    AlphaUses uses;
+    if (int rc = alpha_check_call(alpha_px_bytes, alpha_byte, n_src, iw, ih, n_dst, ow, oh, c, dtype, layout, pieces, n_pieces, uses)) return rc;
+    const uint32_t esize = batch_esize(dtype);
+    if (int rc = alpha_check_memory(d_src, uint64_t(n_src) * c * iw * ih * esize, d_alpha, uint64_t(alpha_px_bytes) * n_src * iw * ih, d_dst,
+                                    uint64_t(n_dst) * c * ow * oh * esize, esize, uses))
+        return rc;
+    PastePlan p;
+    alpha_plan(n_dst, pieces, n_pieces, p);
+    if (p.samples.empty()) return LLCOMP_MI_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return batch_table_call(
+        k, k->d_alpha_tab, k->alpha_tab_cap, AlphaTable(p.samples.size(), p.order.size()).bytes, alpha_table_bound(n_dst, n_pieces), s,
+        [&](uint8_t* at) { alpha_table_put(pieces, p, c, layout, at); },
+        [&](const uint8_t* d_table) {
+            AlphaLaunch o{};
+            o.d_src = static_cast<const uint8_t*>(d_src), o.d_alpha = static_cast<const uint8_t*>(d_alpha), o.d_dst = static_cast<uint8_t*>(d_dst);
+            o.d_table = d_table, o.n_samples = uint32_t(p.samples.size()), o.n_recs = uint32_t(p.order.size());
+            o.alpha_px_bytes = alpha_px_bytes, o.alpha_byte = alpha_byte;
+            o.n_src = n_src, o.iw = iw, o.ih = ih, o.n_dst = n_dst, o.ow = ow, o.oh = oh, o.c = c, o.dtype = dtype, o.layout = layout, o.over = uses.over;
+            return launch_alpha_paste(o, s);
+        });
+}
+
+uint64_t llcomp_mi_codec_alpha_paste_workspace_bytes(const llcomp_mi_codec* k, uint32_t n_dst, uint32_t n_pieces) {
+    if (!k) return 0;
+    return k->workspace_bytes + alpha_table_bound(n_dst, n_pieces);
+}
+
 // Label boxes (DESIGN.md "Label boxes"): the codec gives the device; no table, no workspace.
 int llcomp_mi_codec_label_boxes(llcomp_mi_codec* k, const void* d_maps, uint32_t n, uint32_t ow, uint32_t oh, void* d_boxes, void* stream) {
     if (!k || !d_maps || !d_boxes) return LLCOMP_MI_BAD_ARGS;
@@ -1970,7 +2008,7 @@ extern "C" int llmi_test_codec_consistent(const llcomp_mi_codec* k) {
     const struct { const void* p; uint64_t cap; } grown[] = {
         {k->d_stage, k->stage_cap},           {k->d_box, k->box_cap},           {k->d_mid, k->mid_cap},           {k->d_photo, k->photo_cap},
         {k->d_photo_tab, k->photo_tab_cap},   {k->d_mix_tab, k->mix_tab_cap},   {k->d_mix, k->mix_cap},           {k->d_orient_tab, k->orient_tab_cap},
-        {k->d_compose_tab, k->compose_tab_cap}, {k->d_paste_tab, k->paste_tab_cap}, {k->d_paste16_tab, k->paste16_tab_cap},
+        {k->d_compose_tab, k->compose_tab_cap}, {k->d_paste_tab, k->paste_tab_cap}, {k->d_paste16_tab, k->paste16_tab_cap}, {k->d_alpha_tab, k->alpha_tab_cap},
         {k->d_label16_tab, k->label16_tab_cap}, {k->d_target_tab, k->target_tab_cap}};
     int n = 0;
     for (const auto& gb : grown) {
@@ -1979,7 +2017,7 @@ extern "C" int llmi_test_codec_consistent(const llcomp_mi_codec* k) {
     }
     const void* const held[] = {k->d_sym_or_rec,  k->d_lane_order, k->d_states,     k->d_scratch,     k->d_group_off,   k->d_total_tmp, k->d_region_len,
                                 k->d_region_off,  k->d_regions,    k->d_stage,      k->d_box,         k->d_mid,         k->d_photo,     k->d_photo_tab,
-                                k->d_mix_tab,     k->d_mix,        k->d_orient_tab, k->d_compose_tab, k->d_paste_tab,   k->d_paste16_tab,
+                                k->d_mix_tab,     k->d_mix,        k->d_orient_tab, k->d_compose_tab, k->d_paste_tab,   k->d_paste16_tab, k->d_alpha_tab,
                                 k->d_label16_tab, k->d_target_tab, k->d_upd_goff,   k->d_snap_sorted, k->d_snap_banks,  k->d_snap_res,
                                 k->d_snap_ctx,    k->d_snap_io,    k->d_seg_state};
     uint64_t sum = 0;
@@ -1995,7 +2033,7 @@ extern "C" int llmi_test_codec_consistent(const llcomp_mi_codec* k) {
     if (test_block_requested(k->d_counters) == ~0ull) return 9 + 100 * n;  // (the counters are not part of allocated_bytes)
     if (sum != k->allocated_bytes) return 10;
     uint64_t aside = k->photo_cap + k->photo_tab_cap + k->mix_tab_cap + k->mix_cap + k->orient_tab_cap + k->compose_tab_cap + k->paste_tab_cap +
-                     k->paste16_tab_cap + k->label16_tab_cap + k->target_tab_cap;
+                     k->paste16_tab_cap + k->alpha_tab_cap + k->label16_tab_cap + k->target_tab_cap;
     const uint64_t stage = stage_bound(k->g) + resized_tables_bound(k->g);  // (what workspace_bytes counts for d_stage: more views add more)
     if (k->stage_cap > stage) aside += k->stage_cap - stage;
     if (k->allocated_bytes - aside > k->workspace_bytes) return 11;

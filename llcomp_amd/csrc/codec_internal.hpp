@@ -85,6 +85,10 @@ struct llcomp_mi_codec {
     // batch copy-paste by 16-bit ids (llcomp_mi_codec_paste_batch16): the same with records of 72 bytes (paste_plan.hpp: PasteTable<2>)
     uint8_t* d_paste16_tab = nullptr;
     uint64_t paste16_tab_cap = 0;
+    // batch alpha paste (llcomp_mi_codec_alpha_paste_batch): where a call's one copy lands, the samples and the pieces with their values
+    // (alpha_plan.hpp: AlphaTable, records of 36 bytes); allocated by the first such call, grown by the calls that need more
+    uint8_t* d_alpha_tab = nullptr;
+    uint64_t alpha_tab_cap = 0;
     // label boxes of listed ids (llcomp_mi_codec_label_boxes16): where a call's one copy lands, the lists' bounds, the listed samples and
     // the ids (label_lists.hpp: Label16Table); grown by the calls that need more
     uint8_t* d_label16_tab = nullptr;

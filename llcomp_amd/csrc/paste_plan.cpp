@@ -43,23 +43,27 @@ template <class P>
 bool paste_piece_value(const P& p, uint32_t dtype, uint32_t, uint32_t, uint32_t& bits) { return paste_piece_value(p, dtype, bits); }
 }  // namespace
 
-template <class P>
-int paste_check_call(uint32_t n_src, uint32_t iw, uint32_t ih, uint32_t n_dst, uint32_t ow, uint32_t oh, uint32_t c, uint32_t dtype, uint32_t layout,
-                     const P* pieces, uint32_t n_pieces, std::vector<uint32_t>& value_bits) {
+int paste_check_shapes(uint32_t n_src, uint32_t iw, uint32_t ih, uint32_t n_dst, uint32_t ow, uint32_t oh, uint32_t c, uint32_t dtype, uint32_t layout,
+                       bool has_pieces, uint32_t n_pieces) {
     if (int rc = batch_check_shape(n_dst, c, ow, oh, dtype, layout)) return rc;
     if (n_src || n_pieces)  // (no src batch is fine for a call without pieces)
         if (int rc = batch_check_shape(n_src, c, iw, ih, dtype, layout)) return rc;
-    if (n_pieces > kPasteMaxPieces || (n_pieces && !pieces)) return LLCOMP_MI_BAD_ARGS;
+    if (n_pieces > kPasteMaxPieces || (n_pieces && !has_pieces)) return LLCOMP_MI_BAD_ARGS;
     const uint32_t es = batch_esize(dtype), cs = layout == LLCOMP_MI_LAYOUT_CHW ? 1u : c;
     if (uint64_t(ow) * cs >= (1ull << 31) || (n_src && uint64_t(iw) * cs >= (1ull << 31))) return LLCOMP_MI_BAD_ARGS;
     const ComposeGeom g = compose_geom(0, 0, 0, 0, 0, ow, oh, c, es, cs == 1, true);
     if (g.planes > 65535u || uint64_t(g.tiles_x) * g.tiles_y > 0x7FFFFFFFu) return LLCOMP_MI_BAD_ARGS;  // (the kernel's grid)
+    return LLCOMP_MI_OK;
+}
+
+template <class P>
+int paste_check_call(uint32_t n_src, uint32_t iw, uint32_t ih, uint32_t n_dst, uint32_t ow, uint32_t oh, uint32_t c, uint32_t dtype, uint32_t layout,
+                     const P* pieces, uint32_t n_pieces, std::vector<uint32_t>& value_bits) {
+    if (int rc = paste_check_shapes(n_src, iw, ih, n_dst, ow, oh, c, dtype, layout, pieces != nullptr, n_pieces)) return rc;
     std::vector<uint32_t> on_sample(n_dst, 0u), bits(n_pieces, 0u);
     for (uint32_t i = 0; i < n_pieces; ++i) {
         const P& p = pieces[i];
-        if (p.dst >= n_dst || p.src >= n_src || (p.flags & ~kPasteFlagBits<kPasteMaskBytesOf<P>>)) return LLCOMP_MI_BAD_ARGS;
-        if (p.dx > ow || p.w > ow - p.dx || p.dy > oh || p.h > oh - p.dy) return LLCOMP_MI_BAD_ARGS;
-        if (p.sx > iw || p.w > iw - p.sx || p.sy > ih || p.h > ih - p.sy) return LLCOMP_MI_BAD_ARGS;
+        if (!paste_piece_fits(p, n_src, iw, ih, n_dst, ow, oh) || (p.flags & ~kPasteFlagBits<kPasteMaskBytesOf<P>>)) return LLCOMP_MI_BAD_ARGS;
         if (!paste_piece_value(p, dtype, layout, c, bits[i])) return LLCOMP_MI_BAD_ARGS;
         if (!paste_empty(p) && ++on_sample[p.dst] > kPasteMaxPiecesPerSample) return LLCOMP_MI_BAD_ARGS;
     }
@@ -80,17 +84,7 @@ int paste_check_memory(const void* src, uint64_t src_bytes, const void* mask, ui
 
 template <class P>
 void paste_plan(uint32_t n_dst, const P* pieces, uint32_t n_pieces, PastePlan& p) {
-    p = PastePlan{};
-    std::vector<uint32_t> at(size_t(n_dst) + 1, 0u);  // a counting sort: stable
-    for (uint32_t i = 0; i < n_pieces; ++i)
-        if (!paste_idle(pieces[i])) ++at[pieces[i].dst + 1];
-    for (uint32_t d = 0; d < n_dst; ++d) {
-        if (at[d + 1]) p.samples.push_back(ComposeSample{d, at[d], at[d + 1]});
-        at[d + 1] += at[d];
-    }
-    p.order.resize(at[n_dst]);
-    for (uint32_t i = 0; i < n_pieces; ++i)
-        if (!paste_idle(pieces[i])) p.order[at[pieces[i].dst]++] = i;
+    paste_plan_by(n_dst, pieces, n_pieces, p, [](const P& q) { return paste_idle(q); });
 }
 
 uint64_t paste_workgroups(const PastePlan& p, uint32_t ow, uint32_t oh, uint32_t c, uint32_t dtype, uint32_t layout) {
